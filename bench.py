@@ -13,7 +13,12 @@ Headline workload = BASELINE.json configs[1] (C2): ml-1m-shaped, d=128, L=200, H
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
-Besides the headline line items the JSON carries
+A plain run sets up, runs W warm-up steps, times K steps and prints the headline line (metric, value, unit, ms_per_step,
+higher_is_better, dtype, config).  `--dump-outputs DIR` writes what the last timed step returned (rows, top-100 lists, next
+items, windows) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+With `--full`, besides the headline line items the JSON carries the instrumented per-family pass (`roofline`,
+`step_roofline`, `kernels`), the self-check (`verified`), the path-search latencies and
   * `scoring`: irs_score_topk and its emission sweep alone on the catalog-scale shapes (1M x 128 = C3,
     1.25M x 256 = C4's per-GPU shard) for 1 / 32 / 1024 rows, each with its fraction of the bf16 MFMA peak
     (>= 315 rows) or of the HBM floor of streaming the bf16 catalog once (small row counts);
@@ -346,11 +351,14 @@ class Job:
         self.eng.bind_state_dict(sd)
         self.sd = sd
         self.seqs = gpu_windows(self.B, cfg.max_len, cfg.n_item, device, seed=100 + rank)
-        self.users = torch.randint(0, cfg.n_user, (self.B,), device=device, dtype=torch.int64)
+        gu = torch.Generator(device=device)  # seeded like the windows: the same users in every run
+        gu.manual_seed(200 + rank)
+        self.users = torch.randint(0, cfg.n_user, (self.B,), generator=gu, device=device, dtype=torch.int64)
         self.hep = torch.full((self.B,), cfg.max_len - 2, dtype=torch.int32, device=device)
         self.paths = torch.zeros((self.B, 1), dtype=torch.float32, device=device)
         self.carry = False
         self.last_status = None
+        self.last_out = None  # (rows, top-k values, top-k ids) of the latest single-GPU step: what --dump-outputs writes
         self.status = torch.zeros(self.B, dtype=torch.int32, device=device)
         self.comm = None
         if self.sharded:
@@ -368,6 +376,7 @@ class Job:
             val, ids, st = eng.score_topk(xr, self.k, self.sweep, carry=self.carry)
             self.carry = True
             self.last_status = st
+            self.last_out = (xr, val, ids)
             eng.path_step(self.seqs, self.hep, val, ids, 0, self.paths, self.status)
         else:
             # one search step below the C ABI (irs_generate_paths_sharded): decode -> row all-gather -> sweep of this rank's
@@ -547,6 +556,99 @@ def timed(job, steps, world):
     return dt
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files of all ranks together
+
+
+def step_outputs(job):
+    """What the timed path handed its caller in its last step, as host arrays with one row per user: the consumed rows, the
+    top-100 lists and their status (single GPU), the greedy next item, the path step's status and the windows it left."""
+    import torch
+    torch.cuda.synchronize()
+    out = {}
+    if job.last_out is not None:
+        xr, val, ids = job.last_out
+        out["rows"] = xr.cpu().numpy()
+        out["topk_values"] = val.cpu().numpy()
+        out["topk_ids"] = ids.cpu().numpy().astype(np.float64)
+        out["topk_status"] = job.last_status.cpu().numpy().astype(np.float64)
+    out["next_items"] = job.paths[:, 0].cpu().numpy()
+    out["path_status"] = job.status.cpu().numpy().astype(np.float64)
+    out["windows"] = job.seqs.cpu().numpy().astype(np.float64)
+    out["history_end"] = job.hep.cpu().numpy().astype(np.float64)
+    return out
+
+
+def write_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES, suffix=""):
+    """`arrays` (float32 / float64, one row per user) as outdir/<name><suffix>.npy.  Above `limit` bytes the same fixed, seeded
+    sample of users is kept in every array, and their indices are written as `sampled_rows`."""
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+    n = {a.shape[0] for a in arrays.values()}
+    assert len(n) == 1, {k: a.shape for k, a in arrays.items()}
+    n = n.pop()
+    per_row = sum(a.nbytes for a in arrays.values()) / max(n, 1)
+    if per_row * n > limit:
+        keep = max(1, int(limit // (per_row + 8)))
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sampled_rows"] = idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
+def run_config(args, job, world, packed_fraction=None):
+    """The `config` object of the result line."""
+    from influentialrs_amd._lib import IRS_GEMM_H3, IRS_GEMM_X6
+    cfg = job.cfg
+    gemm_mode = job.eng.decoder_gemm_effective
+    x6 = gemm_mode in (IRS_GEMM_X6, IRS_GEMM_H3)
+    out_cfg = {"workload": f"{args.workload}: n_item={cfg.n_item}, d={cfg.emb_dim}, L={cfg.max_len}, H={cfg.n_heads}, "
+                           f"layers={cfg.n_layers}, ffn={cfg.ffn_dim}; one greedy path-search step",
+               "users_per_step": job.B * world, "users_per_gpu": job.B, "top_k": 100,
+               "windows": "ml-1m-shaped history lengths (log-normal, median 95), pre-padded; decoder skips pad tokens "
+                          "(packed rows), results identical",
+               "packed_row_fraction": packed_fraction,
+               "sweep": args.sweep + (" filter + exact f32 re-score" if args.sweep == "bf16" else ""),
+               "decoder_gemm": (("h3: float32 operands split into two float16 planes (22 of 24 significand bits; weight planes pre-scaled by 2^8 out of the float16 subnormal range), three plane products per "
+                                 "float32 product on v_mfma_f32_32x32x16_f16" if gemm_mode == IRS_GEMM_H3 else
+                                 "x6: float32 operands split exactly into three bf16 planes, six plane products per float32 product on "
+                                 "v_mfma_f32_32x32x16_bf16") + ", float32 accumulation (fused layer kernel and embed + layer-0 q|k|v); attention "
+                                "and the last layer's rows on float32 MFMAs" if x6 else "float32 MFMAs"),
+               "decoder_layers": ("sequence-resident (irs_set_decoder_seq mode %d): layers 0 .. n-2 and the last layer's attention in ONE launch on "
+                                  "whole sequences per workgroup, K / V in LDS, x resident across layers" % job.eng.decoder_seq
+                                  if job.eng.decoder_seq_last else "layer kernel + packed-sequence attention kernel per layer (irs_set_decoder_seq mode %d)" % job.eng.decoder_seq),
+               "parallelism": "single GPU" if world == 1 else (
+                   f"rows data-parallel + item-sharded x{world}: RCCL all-gather of rows, one all_to_all of packed 64-bit top-100 keys "
+                   f"(irs_generate_paths_sharded: collectives below the C ABI, "
+                   f"{'step replayed from a captured hipGraph' if SHARDED_GRAPH and job.comm is not None and job.comm.is_rccl else 'plain stream launches'})"
+                   if job.sharded else
+                   f"users partitioned over {world} GPUs, catalog replicated ({cfg.n_item} items): no data-path collective")}
+    if packed_fraction is None:
+        del out_cfg["packed_row_fraction"]
+    return out_cfg
+
+
+def headline(args, world, value, dt, out_cfg):
+    """The fields every result line starts with (a plain run prints these alone)."""
+    return {
+        "metric": "scored user-item pairs/sec (whole node)",
+        "value": value,
+        "unit": "pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": out_cfg,
+    }
+
+
 def scoring_legs(device, reps=10):
     """irs_score_topk and its emission sweep alone on the catalog-scale shapes ('also report the scoring
     kernel in isolation'; the north star's 60 % MFMA target is quoted on this kernel)."""
@@ -620,6 +722,11 @@ def main():
     ap.add_argument("--batch", type=int, default=4096, help="users per rank per step")
     ap.add_argument("--n-item", type=int, default=0, help="override the catalog size")
     ap.add_argument("--sweep", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline (CPU baseline, instrumented "
+                    "per-family pass and rooflines, self-check, latency, scoring, C3, C4 / C5 legs); a plain run sets up, warms up, "
+                    "times --steps steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last step as "
+                    "DIR/<name>.npy (float32 / float64, at most 64 MB in all: a seeded sample of users beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-latency", action="store_true")
     ap.add_argument("--no-scoring", action="store_true", help="skip the catalog-scale scoring legs")
@@ -648,6 +755,8 @@ def main():
                          "exchanged, merged); 'replicate' = every rank holds the whole catalog and scores its own users, no "
                          "data-path collective; 'auto' = items from 262144 catalog entries up (a 3415-item catalog is 1.7 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -660,7 +769,7 @@ def main():
     if args.pmc_run:
         args.no_cpu_baseline = args.no_latency = args.no_scoring = args.no_c4 = args.no_c3 = True
     cpu = None
-    if not args.no_cpu_baseline and world == 1 and rank == 0:
+    if args.full and not args.no_cpu_baseline and world == 1 and rank == 0:
         cpu = cpu_baseline(args.workload if args.workload in ("c1", "c2", "default", "tiny") else "c2")
 
     import torch
@@ -703,10 +812,20 @@ def main():
     # the windows as the timed region finds them: every instrumented pass below restarts from this state, so that it
     # executes exactly the timed region's work (a window gains a token per step until it is full: 20 steps later the
     # decoder would run ~10 % more packed rows)
-    snap = (job.seqs.clone(), job.hep.clone())
+    snap = (job.seqs.clone(), job.hep.clone()) if args.full else None
     dt = timed(job, args.steps, world)
     users_total = job.B * world
     value = users_total * cfg.n_item * args.steps / dt
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, step_outputs(job), limit=DUMP_LIMIT_BYTES // world,
+                      suffix=f"_rank{rank}" if world > 1 else "")
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, value, dt, run_config(args, job, world))), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # second, instrumented pass: HIP events around every launch of each kernel family
     fam = {}
@@ -968,27 +1087,7 @@ def main():
         lat128 = per_user(min(128, job.B), 5, 30)
         lat1024 = per_user(min(1024, job.B), 3, 10)
 
-    out_cfg = {"workload": f"{args.workload}: n_item={cfg.n_item}, d={cfg.emb_dim}, L={cfg.max_len}, H={cfg.n_heads}, "
-                           f"layers={cfg.n_layers}, ffn={cfg.ffn_dim}; one greedy path-search step",
-               "users_per_step": users_total, "users_per_gpu": job.B, "top_k": 100,
-               "windows": "ml-1m-shaped history lengths (log-normal, median 95), pre-padded; decoder skips pad tokens "
-                          "(packed rows), results identical",
-               "packed_row_fraction": fam["linear"]["packed_fraction"],
-               "sweep": args.sweep + (" filter + exact f32 re-score" if args.sweep == "bf16" else ""),
-               "decoder_gemm": (("h3: float32 operands split into two float16 planes (22 of 24 significand bits; weight planes pre-scaled by 2^8 out of the float16 subnormal range), three plane products per "
-                                 "float32 product on v_mfma_f32_32x32x16_f16" if gemm_mode == IRS_GEMM_H3 else
-                                 "x6: float32 operands split exactly into three bf16 planes, six plane products per float32 product on "
-                                 "v_mfma_f32_32x32x16_bf16") + ", float32 accumulation (fused layer kernel and embed + layer-0 q|k|v); attention "
-                                "and the last layer's rows on float32 MFMAs" if x6 else "float32 MFMAs"),
-               "decoder_layers": ("sequence-resident (irs_set_decoder_seq mode %d): layers 0 .. n-2 and the last layer's attention in ONE launch on "
-                                  "whole sequences per workgroup, K / V in LDS, x resident across layers" % job.eng.decoder_seq
-                                  if job.eng.decoder_seq_last else "layer kernel + packed-sequence attention kernel per layer (irs_set_decoder_seq mode %d)" % job.eng.decoder_seq),
-               "parallelism": "single GPU" if world == 1 else (
-                   f"rows data-parallel + item-sharded x{world}: RCCL all-gather of rows, one all_to_all of packed 64-bit top-100 keys "
-                   f"(irs_generate_paths_sharded: collectives below the C ABI, "
-                   f"{'step replayed from a captured hipGraph' if SHARDED_GRAPH and job.comm is not None and job.comm.is_rccl else 'plain stream launches'})"
-                   if job.sharded else
-                   f"users partitioned over {world} GPUs, catalog replicated ({cfg.n_item} items): no data-path collective")}
+    out_cfg = run_config(args, job, world, fam["linear"]["packed_fraction"])
     del job
     torch.cuda.empty_cache()
 
@@ -1007,20 +1106,8 @@ def main():
             emitted[0] = True
         if rank != 0:
             return
-        out = {
-            "metric": "scored user-item pairs/sec (whole node)",
-            "value": value,
-            "unit": "pairs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": out_cfg,
+        out = headline(args, world, value, dt, out_cfg)
+        out.update({
             "verified": head_ok,
             "verified_how": dict(head_how, what="a comparison INSIDE this library (no oracle, no reference on the GPU box): sampled users of "
                                  "the timed loop's last windows, full-batch throughput kernels vs the same users 8 per call on the "
@@ -1044,7 +1131,7 @@ def main():
                                                           "users_per_gpu", "items_per_gpu", "workload", "parallelism", "verified",
                                                           "verified_how", "fallback_rows", "phase_ms_rank0")}),
             "cpu_baseline": cpu,
-        }
+        })
         if X["err"]:
             out["extras_error"] = X["err"]
         flat = {}

@@ -162,6 +162,30 @@ def test_bench_windows_are_zipf_without_repeats():
     assert counts[:10].sum() > 20 * max(counts[1000:1010].sum(), 1) / 10, "head items must dominate (Zipf)"
 
 
+def test_bench_write_outputs_keeps_every_user_or_one_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: float arrays one row per user, written whole below the size limit; above it the same
+    seeded sample of users in every array (the same one from run to run), within the limit, with its indices."""
+    import bench
+    n = 1000
+    arr = {"rows": np.arange(n * 16, dtype=np.float32).reshape(n, 16), "ids": np.arange(n, dtype=np.float64)}
+    assert bench.write_outputs(str(tmp_path / "all"), arr) == ["ids", "rows"]
+    assert np.array_equal(np.load(tmp_path / "all" / "rows.npy"), arr["rows"])
+    limit = 20_000
+    names = bench.write_outputs(str(tmp_path / "a"), arr, limit=limit)
+    bench.write_outputs(str(tmp_path / "b"), arr, limit=limit)
+    assert names == ["ids", "rows", "sampled_rows"]
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in names}
+    assert sum(a.nbytes for a in got.values()) <= limit
+    idx = got["sampled_rows"].astype(np.int64)
+    assert 0 < len(idx) < n and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got["ids"], idx) and np.array_equal(got["rows"], arr["rows"][idx])
+    for k in names:
+        assert got[k].dtype in (np.float32, np.float64)
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy"))
+    with pytest.raises(AssertionError):
+        bench.write_outputs(str(tmp_path / "c"), {"ids": np.arange(4)})
+
+
 def test_attention_block_deal_closed_form_equals_the_greedy_longest_first_rule():
     """k_attn16h deals its 16-query blocks (block qb costs qb + 1 key tiles) to four waves longest-first.  The kernel uses the
     closed form of that greedy rule -- the i-th largest block goes to wave i & 7 if that is below 4, else 7 - (i & 7): a

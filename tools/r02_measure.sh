@@ -3,10 +3,11 @@
 set -o pipefail
 V=${1:-r02_v3}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 600 python -m pytest tests -m gpu -q --durations=5 > gpurun_out/gputest_${V}.log 2>&1 || { tail -30 gpurun_out/gputest_${V}.log; exit 1; }; tail -4 gpurun_out/gputest_${V}.log
-timeout -k 10 600 python bench.py > gpurun_out/bench_${V}.json 2> gpurun_out/bench_${V}.err || { tail -5 gpurun_out/bench_${V}.err; exit 1; }
-python3 tools/sweep_bench.py --shapes 1000000,128,1024 1000000,128,32 1000000,128,1 1250000,256,1024 1250000,256,32 1250000,256,1 3415,128,1024 --reps 20 > gpurun_out/sweep_bench_${V}.txt 2>&1 || { tail -5 gpurun_out/sweep_bench_${V}.txt; exit 1; }; cat gpurun_out/sweep_bench_${V}.txt
-rocprofv3 --kernel-trace --stats -d gpurun_out/prof_bench -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-latency --no-scoring --no-c4 > gpurun_out/prof_bench.log 2>&1 || { tail -5 gpurun_out/prof_bench.log; exit 1; }
-python3 tools/rocpd_kernels.py $(ls gpurun_out/prof_bench/*/*.db | head -1) k_path_step > gpurun_out/c2_b4096_kernels_${V}.txt 2>&1; head -12 gpurun_out/c2_b4096_kernels_${V}.txt
-rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d gpurun_out/pmc_sweep2 -- python3 tools/sweep_bench.py --shapes 1000000,128,1024 1250000,256,1024 --reps 3 > gpurun_out/pmc_run.log 2>&1 || { tail -5 gpurun_out/pmc_run.log; exit 1; }
-python3 tools/pmc_summary.py gpurun_out/pmc_sweep2 k_sweep k_select k_refine k_prep > gpurun_out/sweep_pmc_${V}.txt; cat gpurun_out/sweep_pmc_${V}.txt
+OUT=${OUT:-measure_out}; mkdir -p "$OUT"  # where every output of this script goes
+timeout -k 10 600 python -m pytest tests -m gpu -q --durations=5 > $OUT/gputest_${V}.log 2>&1 || { tail -30 $OUT/gputest_${V}.log; exit 1; }; tail -4 $OUT/gputest_${V}.log
+timeout -k 10 600 python bench.py --full > $OUT/bench_${V}.json 2> $OUT/bench_${V}.err || { tail -5 $OUT/bench_${V}.err; exit 1; }
+python3 tools/sweep_bench.py --shapes 1000000,128,1024 1000000,128,32 1000000,128,1 1250000,256,1024 1250000,256,32 1250000,256,1 3415,128,1024 --reps 20 > $OUT/sweep_bench_${V}.txt 2>&1 || { tail -5 $OUT/sweep_bench_${V}.txt; exit 1; }; cat $OUT/sweep_bench_${V}.txt
+rocprofv3 --kernel-trace --stats -d $OUT/prof_bench -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-latency --no-scoring --no-c4 > $OUT/prof_bench.log 2>&1 || { tail -5 $OUT/prof_bench.log; exit 1; }
+python3 tools/rocpd_kernels.py $(ls $OUT/prof_bench/*/*.db | head -1) k_path_step > $OUT/c2_b4096_kernels_${V}.txt 2>&1; head -12 $OUT/c2_b4096_kernels_${V}.txt
+rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d $OUT/pmc_sweep2 -- python3 tools/sweep_bench.py --shapes 1000000,128,1024 1250000,256,1024 --reps 3 > $OUT/pmc_run.log 2>&1 || { tail -5 $OUT/pmc_run.log; exit 1; }
+python3 tools/pmc_summary.py $OUT/pmc_sweep2 k_sweep k_select k_refine k_prep > $OUT/sweep_pmc_${V}.txt; cat $OUT/sweep_pmc_${V}.txt

@@ -6,7 +6,7 @@ set -o pipefail
 cd $GRAFT_REPO_ROOT
 S=${1:-weak}
 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29519 \
-  bench.py --gpus 4 --steps 3 --warmup 1 --backend gloo --same-device --no-cpu-baseline --scaling $S --batch $([ $S = strong ] && echo 4096 || echo 1024) \
+  bench.py --full --gpus 4 --steps 3 --warmup 1 --backend gloo --same-device --no-cpu-baseline --scaling $S --batch $([ $S = strong ] && echo 4096 || echo 1024) \
   --c4-batch $([ $S = strong ] && echo 512 || echo 128) --c4-steps 2 --c3-batch $([ $S = strong ] && echo 1024 || echo 256) --c3-steps 3 --extras-timeout 700 \
   > gpurun_out/bench_rehearsal_4rank_$S.json 2> gpurun_out/bench_rehearsal_4rank_$S.err || { tail -20 gpurun_out/bench_rehearsal_4rank_$S.err; exit 1; }
 python3 - <<PY
