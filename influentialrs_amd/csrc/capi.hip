@@ -295,7 +295,7 @@ static void workspace_plan(const irs_ctx *ctx, ws_plan *p) {
     p->y = take(RL * D.d * 4);
     // (the sequence-resident layer kernel pads every sequence to whole 32-token tiles and every workgroup to 8 tiles: up to 256 rows
     //  per sequence in the fragment-major images)
-    const bool seq_shape = D.d == 128 && D.ffn_dim == 256 && D.n_heads == 4 && D.max_len <= 256 && D.n_layers > 1;
+    const bool seq_shape = irs_seq_shape(D);
     const size_t RLs = seq_shape ? (size_t)ctx->max_seqs * 256 : RL;
     const size_t RLf = (((RLs > RL ? RLs : RL) + 127) / 128) * 128; // 128-token tiles x 128 padded columns
     const size_t fcols = D.d > 128 ? (size_t)((D.d + 31) / 32) * 32 : 128; // (d = 256: eight column tiles per token tile)
@@ -409,15 +409,12 @@ extern "C" int irs_bind_workspace(irs_ctx *ctx, void *ws, size_t bytes) {
     ctx->seq_qrow = (int32_t *)(b + p.sqrow);
     ctx->seq_padq = (int32_t *)(b + p.spadq);
     ctx->m_dev = (int32_t *)(b + p.mdev);
-    {
-        const irs_dims &D_ = ctx->dims;
-        const bool seq_shape = D_.d == 128 && D_.ffn_dim == 256 && D_.n_heads == 4 && D_.max_len <= 256 && D_.n_layers > 1;
-        ctx->tile_seq = seq_shape ? (int32_t *)(b + p.tseq) : nullptr;
-        ctx->tile_idx = seq_shape ? (int32_t *)(b + p.tidx) : nullptr;
-        ctx->seq_row0 = seq_shape ? (int32_t *)(b + p.srow0) : nullptr;
-        ctx->qrow_tile = seq_shape ? (int32_t *)(b + p.qtile) : nullptr;
-        ctx->n_wg_dev = seq_shape ? (int32_t *)(b + p.nwg) : nullptr;
-    }
+    const bool seq_shape = irs_seq_shape(ctx->dims);
+    ctx->tile_seq = seq_shape ? (int32_t *)(b + p.tseq) : nullptr;
+    ctx->tile_idx = seq_shape ? (int32_t *)(b + p.tidx) : nullptr;
+    ctx->seq_row0 = seq_shape ? (int32_t *)(b + p.srow0) : nullptr;
+    ctx->qrow_tile = seq_shape ? (int32_t *)(b + p.qtile) : nullptr;
+    ctx->n_wg_dev = seq_shape ? (int32_t *)(b + p.nwg) : nullptr;
     ctx->x_local = (float *)(b + p.xlocal);
     ctx->keys_send = (uint64_t *)(b + p.ksend);
     ctx->keys_recv = (uint64_t *)(b + p.krecv);
@@ -694,15 +691,11 @@ extern "C" int irs_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int32_t B
 }
 
 // one search step on one device: decode -> rows at hep -> top-k -> choose/update
-static bool step_merged(const irs_ctx *ctx, int B) { // see irs_launch_decode: the single-workgroup plan kernel runs
-    return B <= 64 && ctx->dims.max_len >= 4;
-}
-
 static int enqueue_step(irs_ctx *ctx, int64_t *seq, const int64_t *user, int32_t *hep, int B, int k, int sweep,
                         int sample, int sample_k, uint64_t seed, float *paths, int path_ld, int32_t *status,
                         hipStream_t s, int carry = 0) {
     int rc;
-    const bool merged = step_merged(ctx, B);
+    const bool merged = irs_small_plan(ctx->dims, B); // (the decode below is rows-only: its plan is the single-workgroup one)
     ctx->step_pair = merged ? ctx->step_ctr : nullptr;
     rc = irs_launch_decode(ctx, seq, user, B, nullptr, hep, ctx->xrows, nullptr, s);
     ctx->step_pair = nullptr;

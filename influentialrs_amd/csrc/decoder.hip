@@ -1506,8 +1506,7 @@ struct BlockX6Args {
     // attention output in the same order (written and read back by the same wave), Xf = x'.
     // ALL of layers 0 .. n_lay - 1 in ONE launch (stage B): x stays in the wave's registers from layer to layer, the weight ring
     // runs through the layer boundaries (one empty step per layer keeps the slot numbering: 33 = 0 mod 3 steps), the parameter
-    // vectors of the next layer are re-staged into LDS at the boundary from a packed copy.  The last of them also writes the
-    // k | v rows the rows-only last layer reads.
+    // vectors of the next layer are re-staged into LDS at the boundary from a packed copy.
     const uint4 *Wbase;    // float16-plane stream of layer 0; layer l's stream = Wbase + l * wstride (x6_stream)
     long long wstride;     // in uint4
     int n_lay, nl_total;   // layers run here (n_layers - 1); streams in the arena (layer l's q | k | v sits in stream l - 1, layer 0's in stream nl_total - 1)
@@ -3087,7 +3086,7 @@ __device__ unsigned long long g_small_t[16];
 #else
 #define STAMP(i)
 #endif
-#define SMALL_ROWS_MAX 32768 // packed rows up to which the 16-token kernel beats the 128-token path (see irs_launch_decode)
+#define SMALL_ROWS_MAX 32768 // packed rows up to which the 16-token kernel beats the 128-token path (see decode_route)
 #define SMALL_MT2_ROWS 8192
 #define SB_NW 8 // waves per workgroup: two per SIMD, so that one wave's barrier / LDS / load waits hide behind the other's MFMAs
 // MT = 16-token tiles per workgroup: 1 on the latency path; 2 above SMALL_MT2_ROWS rows, where every weight fragment
@@ -5588,7 +5587,7 @@ __global__ void k_gather_rows(const float *__restrict__ x, const int32_t *__rest
 }
 
 // ------------------------------------------------------------------ host side
-static int g_lin_bk = 16, g_ln_bk = 16; // K-slab depth (tools/gemm_lab.hip flips these to compare 16 vs 32)
+// (every GEMM runs on 16-deep K slabs: tools/gemm_lab.hip times the BK = 32 instantiations against them)
 static int launch_linear(irs_ctx *ctx, const float *X, const float *W, const float *bias, const float *R, float *Y,
                          int M, int N, int K, bool relu, hipStream_t s, const float *g1 = nullptr,
                          const float *b1 = nullptr, const float *c = nullptr, const float *g2 = nullptr,
@@ -5616,23 +5615,15 @@ static int launch_linear(irs_ctx *ctx, const float *X, const float *W, const flo
         else hipLaunchKernelGGL((k_linear_ln<16, false, false, 8>), grid, dim3(256), 0, s, a);
     } else if (g1 != nullptr) { // fused residual + LayerNorm: whole rows per wave (N <= 128)
         dim3 grid((M + LIN_BM - 1) / LIN_BM);
-        const int bk = g_ln_bk;
-        const bool full = (N == LIN_BN) && (K % bk == 0) && al16(X) && al16(W) && al16(R) && al16(Y) && al16(Rf) && al16(Yf);
+        const bool full = (N == LIN_BN) && (K % 16 == 0) && al16(X) && al16(W) && al16(R) && al16(Y) && al16(Rf) && al16(Yf);
         if (Xf && !(full && al16(Xf))) {
             if (ctx) snprintf(ctx->err, sizeof(ctx->err), "launch_linear: fragment-major X needs the aligned N == 128 case");
             return IRS_E_INVALID;
         }
-        if (bk == 16) {
-            if (Xf) hipLaunchKernelGGL((k_linear_ln<16, true, true>), grid, dim3(256), 0, s, a);
-            else if (full) hipLaunchKernelGGL((k_linear_ln<16, true, false>), grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_linear_ln<16, false, false>), grid, dim3(256), 0, s, a);
-        } else {
-            if (Xf) hipLaunchKernelGGL((k_linear_ln<32, true, true>), grid, dim3(256), 0, s, a);
-            else if (full) hipLaunchKernelGGL((k_linear_ln<32, true, false>), grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_linear_ln<32, false, false>), grid, dim3(256), 0, s, a);
-        }
+        if (Xf) hipLaunchKernelGGL((k_linear_ln<16, true, true>), grid, dim3(256), 0, s, a);
+        else if (full) hipLaunchKernelGGL((k_linear_ln<16, true, false>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_linear_ln<16, false, false>), grid, dim3(256), 0, s, a);
     } else {
-        const int bk = g_lin_bk;
         static int n_cu = 0;
         if (n_cu == 0) {
             int dev = 0;
@@ -5640,24 +5631,18 @@ static int launch_linear(irs_ctx *ctx, const float *X, const float *W, const flo
                 hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
                 n_cu = 256;
         }
-        a.slots = n_cu * (bk == 16 ? 4 : 2); // matches the kernels' launch bounds
+        a.slots = n_cu * 4; // matches k_linear<.., 16, ..>'s launch bounds
         const int ntm = (M + LIN_BM - 1) / LIN_BM, ntn = (N + LIN_BN - 1) / LIN_BN;
         // exact unit count when M is known here, its upper bound over any device-side M otherwise
         dim3 grid(m_dev ? ntm + (a.slots - 1) * (ntn - 1) : (ntm / a.slots) * a.slots + (ntm % a.slots) * ntn);
-        const bool full = (K % bk == 0) && al16(X) && al16(W);
+        const bool full = (K % 16 == 0) && al16(X) && al16(W);
         if (Xf && !(full && al16(Xf))) {
             if (ctx) snprintf(ctx->err, sizeof(ctx->err), "launch_linear: fragment-major X needs aligned operands");
             return IRS_E_INVALID;
         }
-        if (bk == 16) {
-            if (Xf) hipLaunchKernelGGL((k_linear<true, 16, true>), grid, dim3(256), 0, s, a);
-            else if (full) hipLaunchKernelGGL((k_linear<true, 16, false>), grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_linear<false, 16, false>), grid, dim3(256), 0, s, a);
-        } else {
-            if (Xf) hipLaunchKernelGGL((k_linear<true, 32, true>), grid, dim3(256), 0, s, a);
-            else if (full) hipLaunchKernelGGL((k_linear<true, 32, false>), grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_linear<false, 32, false>), grid, dim3(256), 0, s, a);
-        }
+        if (Xf) hipLaunchKernelGGL((k_linear<true, 16, true>), grid, dim3(256), 0, s, a);
+        else if (full) hipLaunchKernelGGL((k_linear<true, 16, false>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_linear<false, 16, false>), grid, dim3(256), 0, s, a);
     }
     if (ctx) {
         irs_prof_end(ctx, IRS_PROF_LINEAR, s, 2.0 * M * (double)N * K,
@@ -5667,12 +5652,10 @@ static int launch_linear(irs_ctx *ctx, const float *X, const float *W, const flo
     return IRS_OK;
 }
 
-static int g_attn16 = 1; // 16-query-block attention kernel for head dim 32 (0: k_attn_mfma everywhere)
-
 // attn16 is the only attention kernel that can write the fragment-major image the fused block kernel consumes
 static bool attn16_ok(const irs_ctx *ctx, const float *qkv, const float *out) {
     const int L = ctx->dims.max_len, d = ctx->dims.d, H = ctx->dims.n_heads;
-    return g_attn16 && d % H == 0 && d / H == 32 && L <= 256 && d % 4 == 0 && ((((uintptr_t)qkv) | ((uintptr_t)out)) & 15) == 0;
+    return d % H == 0 && d / H == 32 && L <= 256 && d % 4 == 0 && ((((uintptr_t)qkv) | ((uintptr_t)out)) & 15) == 0;
 }
 
 static int launch_attn(irs_ctx *ctx, const float *qkv, const int64_t *seq, const float *r_u, float *out, int B,
@@ -5687,33 +5670,16 @@ static int launch_attn(irs_ctx *ctx, const float *qkv, const int64_t *seq, const
     const int mm = ctx->dims.mask_mode;
     irs_prof_begin(ctx, IRS_PROF_ATTN, s);
     if (frag_out && !attn16_ok(ctx, qkv, out)) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "fragment-major attention output needs the head-dim-32 kernel");
-    if (hd == 32 && v4 && L <= 256 && g_attn16) {
-        int S16 = (L + 7) & ~7; // attn16_vstride
-        if ((S16 & 15) != 8) S16 += 8;
-        const size_t lds16 = (size_t)32 * S16 * 4 + (size_t)((L + 15) & ~15) * 32 * 4 + 64;
+    if (hd == 32 && v4 && L <= 256) {
         const size_t lds16d = (size_t)2 * ((L + 15) & ~15) * 32 * 4 + 64; // LDS-DMA form: V row-major like K
         if (H * B <= 64) grid.z = (((L + 15) / 16) + 3) / 4; // latency path: one query block per wave
         if (kv_planes) { // K / V arrive as float16 plane pairs (k_block_x6's tail): the split-float16 attention
             if (grid.z != 1) IRS_FAIL(ctx, IRS_E_STATE, "plane-format K / V on the latency path");
-            if (tok_row)
-                hipLaunchKernelGGL((k_attn16h<16, true, 4>), grid, dim3(256), lds16d, s, qkv, seq, r_u, out, L, d, mm, off, cnt,
-                                   ctx->seq_padq, frag_out ? 1 : 0);
-            else
-                hipLaunchKernelGGL((k_attn16h<16, false, 4>), grid, dim3(256), lds16d, s, qkv, seq, r_u, out, L, d, mm, off, cnt,
-                                   nullptr, frag_out ? 1 : 0);
-        } else if (g_attn16 == 2) { // (lab A/B: the register-staged fill with the transposed V^T image)
-            if (tok_row)
-                hipLaunchKernelGGL((k_attn16<16, true, false>), grid, dim3(256), lds16, s, qkv, seq, r_u, out, L, d, mm, off, cnt,
-                                   ctx->seq_padq, frag_out ? 1 : 0, H);
-            else
-                hipLaunchKernelGGL((k_attn16<16, false, false>), grid, dim3(256), lds16, s, qkv, seq, r_u, out, L, d, mm, off, cnt,
-                                   nullptr, frag_out ? 1 : 0, H);
-        } else if (tok_row)
-            hipLaunchKernelGGL((k_attn16<16, true, true>), grid, dim3(256), lds16d, s, qkv, seq, r_u, out, L, d, mm, off, cnt,
-                               ctx->seq_padq, frag_out ? 1 : 0, H);
-        else
-            hipLaunchKernelGGL((k_attn16<16, false, true>), grid, dim3(256), lds16d, s, qkv, seq, r_u, out, L, d, mm, off, cnt,
-                               nullptr, frag_out ? 1 : 0, H);
+            hipLaunchKernelGGL((tok_row ? k_attn16h<16, true, 4> : k_attn16h<16, false, 4>), grid, dim3(256), lds16d, s, qkv, seq, r_u,
+                               out, L, d, mm, off, cnt, tok_row ? ctx->seq_padq : nullptr, frag_out ? 1 : 0);
+        } else
+            hipLaunchKernelGGL((tok_row ? k_attn16<16, true, true> : k_attn16<16, false, true>), grid, dim3(256), lds16d, s, qkv, seq,
+                               r_u, out, L, d, mm, off, cnt, tok_row ? ctx->seq_padq : nullptr, frag_out ? 1 : 0, H);
         irs_prof_end(ctx, IRS_PROF_ATTN, s, 2.0 * B * (double)H * L * L * hd, 4.0 * 4.0 * B * (double)L * d);
         IRS_CHECK_HIP(ctx, hipGetLastError());
         return IRS_OK;
@@ -5735,8 +5701,11 @@ static int launch_attn(irs_ctx *ctx, const float *qkv, const int64_t *seq, const
     return IRS_OK;
 }
 
+// the user embedding table the influence term r_u is computed from (IRN mask with bound user weights), else null: r_u = 0
+static const float *pif_table(const irs_ctx *ctx) { return ctx->dims.mask_mode == IRS_MASK_IRN ? ctx->user_emb : nullptr; }
+
 int irs_launch_pif(irs_ctx *ctx, const int64_t *user, int B, float *r_u, hipStream_t s) {
-    if (ctx->dims.mask_mode != IRS_MASK_IRN || !ctx->user_emb) {
+    if (!pif_table(ctx)) {
         hipLaunchKernelGGL(k_fill, dim3((B + 255) / 256), dim3(256), 0, s, r_u, 0.f, B);
     } else {
         hipLaunchKernelGGL(k_pif, dim3((B + 255) / 256), dim3(256), 0, s, user, ctx->user_emb, ctx->um_w, ctx->um_b,
@@ -5773,14 +5742,10 @@ static const uint4 *x6_stream(const irs_ctx *ctx, int npl, int layer) {
 }
 // streams 0 .. n_layers - 2: layer l's out-projection / FFN and layer l + 1's q | k | v; stream n_layers - 1: layer 0's
 // q | k | v alone (the embed kernel's; its other blocks are zero and never fetched)
-static bool seq_shape(const irs_ctx *ctx) {
-    const irs_dims &D = ctx->dims;
-    return D.d == 128 && D.ffn_dim == 256 && D.n_heads == 4 && D.max_len <= 256 && D.n_layers > 1;
-}
 static size_t x6_streams_bytes(const irs_ctx *ctx) { return (size_t)ctx->dims.n_layers * (x6_layer_b(ctx, 3) + x6_layer_b(ctx, 2)); }
 // (+ the sequence-resident kernel's packed parameter vectors: [n_layers][X6_SEQ_VECS] floats behind the streams)
 size_t irs_x6_bytes(const irs_ctx *ctx) {
-    return x6_shape(ctx) ? x6_streams_bytes(ctx) + (seq_shape(ctx) ? (size_t)ctx->dims.n_layers * X6_SEQ_VECS * 4 : 0) : 0;
+    return x6_shape(ctx) ? x6_streams_bytes(ctx) + (irs_seq_shape(ctx->dims) ? (size_t)ctx->dims.n_layers * X6_SEQ_VECS * 4 : 0) : 0;
 }
 static const float *seq_vecpack(const irs_ctx *ctx) {
     return reinterpret_cast<const float *>(reinterpret_cast<const char *>(ctx->w_x6) + x6_streams_bytes(ctx));
@@ -5824,7 +5789,7 @@ int irs_launch_pack_x6(irs_ctx *ctx, hipStream_t s) {
         }
         pack(nullptr, nullptr, nullptr, ctx->layer[0].sa_in_w, const_cast<uint4 *>(x6_stream(ctx, npl, nl - 1)));
     }
-    if (seq_shape(ctx)) { // (behind irs_launch_cross_const: c_l exists)
+    if (irs_seq_shape(ctx->dims)) { // (behind irs_launch_cross_const: c_l exists)
         for (int l = 0; l < nl; ++l) {
             const irs_layer_w &w = ctx->layer[l];
             hipLaunchKernelGGL(k_pack_seqvec, dim3((X6_SEQ_VECS + 255) / 256), dim3(256), 0, s, w.l1_b, w.l2_b, w.n3_w, w.n3_b,
@@ -5880,7 +5845,7 @@ int irs_launch_h3_range(irs_ctx *ctx, float *stats, hipStream_t s) {
         amax(w.n1_w, d, 2), amax(w.n2_w, d, 2), amax(w.n3_w, d, 2);
         amax(w.n1_b, d, 3), amax(w.n2_b, d, 3), amax(w.n3_b, d, 3);
         rmax(w.l1_w, F, d, 5);
-        if (seq_shape(ctx)) rmax(w.sa_in_w, 3 * d, d, 6); // (the sequence-resident attention splits q and k rows too)
+        if (irs_seq_shape(ctx->dims)) rmax(w.sa_in_w, 3 * d, d, 6); // (the sequence-resident attention splits q and k rows too)
         else rmax(w.sa_in_w + (size_t)2 * d * d, d, d, 6);
         amax(w.sa_out_w, (size_t)d * d, 7), amax(w.l1_w, (size_t)F * d, 7), amax(w.l2_w, (size_t)d * F, 7), amax(w.sa_in_w, (size_t)3 * d * d, 7);
         amax(w.l1_b, F, 7), amax(w.sa_in_b, (size_t)3 * d, 7);
@@ -5895,7 +5860,7 @@ float irs_h3_operand_bound(const irs_ctx *ctx, const float *st) {
     const float ln = sd * st[2] + st[3] + st[4];         // a LayerNorm output (+ c_l)
     const float xin = sd * fmaxf(a0, ln);                // norm of a layer's input row
     float v = xin * st[6] + st[7];                       // a V row (and the attention output, a convex combination of V rows)
-    if (seq_shape(ctx)) v *= SEQ_KQ_SCALE;               // ... and a q or k row (st[6] then covers all of W_in's rows)
+    if (irs_seq_shape(ctx->dims)) v *= SEQ_KQ_SCALE;               // ... and a q or k row (st[6] then covers all of W_in's rows)
     const float h = sd * ln * st[5] + st[7];             // a hidden activation
     return fmaxf(fmaxf(fmaxf(a0, ln), fmaxf(v, h)), st[7] * x6_wscale(2)); // (the weight planes hold 2^8 x the weights)
 }
@@ -5944,9 +5909,8 @@ static void x6_launch(int qp0, bool embed, int nt, int npl, int rows, const Bloc
 size_t irs_small_frag_floats(const irs_ctx *ctx) {
     const int d = ctx->dims.d, F = ctx->dims.ffn_dim;
     if (small_any_shape(d, F)) return (size_t)ctx->dims.n_layers * small_any_layer_floats(d, F);
-    if (small_wide_shape(d, F)) return (size_t)ctx->dims.n_layers * (small_wide_layer_floats(d, F) + (size_t)3 * d * d);
-    if (d != 128 || F != 256) return 0;
-    return (size_t)ctx->dims.n_layers * (SMALL_WF_LAYER + SMALL_WF_WIN);
+    if (!small_wide_shape(d, F) && !(d == 128 && F == 256)) return 0;
+    return (size_t)ctx->dims.n_layers * (small_wide_layer_floats(d, F) + (size_t)3 * d * d); // (d = 128: SMALL_WF_LAYER + SMALL_WF_WIN)
 }
 
 int irs_launch_pack_small(irs_ctx *ctx, hipStream_t s) {
@@ -5968,30 +5932,445 @@ int irs_launch_pack_small(irs_ctx *ctx, hipStream_t s) {
         IRS_CHECK_HIP(ctx, hipGetLastError());
         return IRS_OK;
     }
-    if (small_wide_shape(ctx->dims.d, ctx->dims.ffn_dim)) { // [n_layers][Wo | W1 | W2], then [n_layers][Win]
-        const int d = ctx->dims.d, F = ctx->dims.ffn_dim;
-        const size_t lf = small_wide_layer_floats(d, F);
-        auto pk = [&](const float *W, float *out, int N, int K) {
-            hipLaunchKernelGGL(k_pack_frag16, dim3((N * K / 4 + 255) / 256), dim3(256), 0, s, W, out, N, K);
-        };
-        for (int l = 0; l < nl; ++l) {
-            const irs_layer_w &w = ctx->layer[l];
-            float *o = ctx->w_frag16 + (size_t)l * lf;
-            pk(w.sa_out_w, o, d, d);
-            pk(w.l1_w, o + (size_t)d * d, F, d);
-            pk(w.l2_w, o + (size_t)d * d + (size_t)F * d, d, F);
-            pk(w.sa_in_w, ctx->w_frag16 + (size_t)nl * lf + (size_t)l * 3 * d * d, 3 * d, d);
-        }
-        IRS_CHECK_HIP(ctx, hipGetLastError());
-        return IRS_OK;
-    }
+    // d = 256 and d = 128 (F = 256): [n_layers][Wo | W1 | W2], then [n_layers][Win] (d = 128: the SMALL_WF_* offsets)
+    const int d = ctx->dims.d, F = ctx->dims.ffn_dim;
+    const size_t lf = small_wide_layer_floats(d, F);
+    auto pk = [&](const float *W, float *out, int N, int K) {
+        hipLaunchKernelGGL(k_pack_frag16, dim3((N * K / 4 + 255) / 256), dim3(256), 0, s, W, out, N, K);
+    };
     for (int l = 0; l < nl; ++l) {
         const irs_layer_w &w = ctx->layer[l];
-        float *o = ctx->w_frag16 + (size_t)l * SMALL_WF_LAYER;
-        hipLaunchKernelGGL(k_pack_frag16, dim3(16), dim3(256), 0, s, w.sa_out_w, o + SMALL_WF_WO, 128, 128);
-        hipLaunchKernelGGL(k_pack_frag16, dim3(32), dim3(256), 0, s, w.l1_w, o + SMALL_WF_W1, 256, 128);
-        hipLaunchKernelGGL(k_pack_frag16, dim3(32), dim3(256), 0, s, w.l2_w, o + SMALL_WF_W2, 128, 256);
-        hipLaunchKernelGGL(k_pack_frag16, dim3(48), dim3(256), 0, s, w.sa_in_w, ctx->w_frag16 + (size_t)nl * SMALL_WF_LAYER + (size_t)l * SMALL_WF_WIN, 384, 128);
+        float *o = ctx->w_frag16 + (size_t)l * lf;
+        pk(w.sa_out_w, o, d, d);
+        pk(w.l1_w, o + (size_t)d * d, F, d);
+        pk(w.l2_w, o + (size_t)d * d + (size_t)F * d, d, F);
+        pk(w.sa_in_w, ctx->w_frag16 + (size_t)nl * lf + (size_t)l * 3 * d * d, 3 * d, d);
+    }
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
+// ------------------------------------------------------------------ decode routes: chosen once per call by decode_route
+// A rows-only decode (the caller wants x[b, pos[b], :] only) runs on the PACKED non-pad tokens (every kernel behind the plan clamps
+// its row count to the device-side total) and evaluates the LAST layer for the one consumed row per sequence.
+enum class DecPlan { NONE, MULTI, SMALL, IN_EMBED }; // full decode; k_plan_count / scan / fill; k_plan_small; inside the embed kernel
+enum class DecEmbed { FULL, PACKED, FRAG, FRAG_QKV, SMALL16_QKV, ANY_QKV, SEQ };
+// the rest of a layer behind its attention: per-GEMM float32 kernels (GEMM_LN: LayerNorms fused into the GEMM epilogues),
+// fragment-major x / y (FRAG_*), or one 16-token layer kernel (SMALL16: d = 128, F = 256; WIDE: d = 256; ANY: other small shapes)
+enum class DecFam { GEMM, GEMM_LN, FRAG_GEMM, FRAG_BLOCK, FRAG_FUSED, SMALL16, WIDE, ANY };
+struct DecodeRoute {
+    bool rows_only, small_plan;
+    DecPlan plan;
+    DecEmbed embed;  // embedding; *_QKV: + layer 0's q | k | v; SEQ: + layers 0 .. n_layers - 2 and the front of the last one
+    DecFam layer;    // the layers before the rows-only last one (every layer of a full decode)
+    DecFam tail;     // the rest of the rows-only last layer (GEMM, GEMM_LN, SMALL16, WIDE or ANY)
+    bool frag;       // x / y live in the fragment-major images (act_xf / act_yf) between the layers
+    bool seq;        // the sequence-resident launch (ctx->seq_last)
+    bool kv_planes;  // the split-precision kernels hand K / V to the attention as float16 plane pairs (k_attn16h)
+    bool att_fused;  // self-attention runs inside the 16-token layer kernel (one sequence)
+    bool kv_only;    // the last fused launch before the rows-only last layer writes its k | v only (queries: B rows, later)
+    bool x6;         // the fragment-major fused kernels run on split-precision MFMAs (k_block_x6)
+    int npl, nt;     // k_block_x6's planes (3: bf16, 2: float16) and accumulator tiles per token (d / 32)
+};
+
+// the layer kernel of these families also computes the next layer's q | k | v
+static bool fam_writes_qkv(DecFam f) { return f != DecFam::GEMM && f != DecFam::GEMM_LN && f != DecFam::FRAG_GEMM; }
+
+static DecodeRoute decode_route(const irs_ctx *ctx, int B, bool rows_only) {
+    const irs_dims &D = ctx->dims;
+    const int L = D.max_len, d = D.d, F = D.ffn_dim, nl = D.n_layers, rows = B * L;
+    DecodeRoute r{rows_only, rows_only && irs_small_plan(D, B)}; // (small_plan: k_plan_small also computes r_u)
+    // The 16-token layer kernel's regime.  Measured crossover with the 128-token fragment-major path on C2 (L = 200):
+    // 564 vs 720 us per path step at 128 users, 921 vs 797 at 256 (the big path has a ~700 us floor per step: one round
+    // of 128-token tiles streams the weights serially through LDS whatever the number of tiles).
+    const bool small16 = d == 128 && F == 256 && ctx->w_frag16 && rows <= SMALL_ROWS_MAX;
+    // any other small shape: the generic fused layer tail.  Measured against the per-GEMM kernels (per path step):
+    // default (d = 30, L = 60) 235 vs 582 us at 64 users, 859 vs 1055 at 1024; config 1 (d = 64, L = 50) 259 vs 653
+    // at 64 users, 888 vs 1040 at 1024 -- ahead over the whole tested range
+    const bool any = small_any_shape(d, F) && ctx->w_frag16 && rows <= 65536;
+    // d = 256 (C4's decoder), rows-only decode of a throughput batch: the split-bf16 fused layer kernel at 8 accumulator tiles
+    // per token (k_block_x6<.., NT = 8>) with fragment-major activations, like d = 128.  Everything else at d = 256 (full
+    // decodes, small batches, IRS_GEMM_F32) keeps the per-GEMM float32 kernels.
+    const bool x6d = d == 256 && F == 256 && ctx->use_x6 && ctx->w_x6 && rows_only && rows >= 32768 && nl > 1 &&
+                     attn16_ok(ctx, ctx->act_qkv, ctx->act_yf);
+    // d = 256 below the throughput regime (C5's 32 beam windows, single users): the 16-token fused layer kernel for wide
+    // models (k_block_small_wide) instead of ~8 per-GEMM launches per layer
+    const bool wide = small_wide_shape(d, F) && ctx->w_frag16 && !x6d && rows < 32768;
+    // throughput shapes keep x / y ONLY in the fragment-major layout between the layers (see frag_index): the LN-fused GEMMs
+    // write it, read their residual from it, and the QKV / FFN1 GEMMs load it as their X operand
+    r.frag = (d <= LIN_BN && d % 32 == 0 && rows > 2048 && !small16 && !any) || x6d;
+    // d = 128 (or x6d), F = 256, head dim 32: attention writes its output fragment-major and ONE kernel does the rest of the
+    // layer (out-projection + LN1 / LN2, feed-forward + LN3, the next layer's q | k | v) with y, h, x' in registers
+    const bool fuse_block = r.frag && (d == 128 || x6d) && F == 256 && attn16_ok(ctx, ctx->act_qkv, ctx->act_yf);
+    r.x6 = ctx->use_x6 && ctx->w_x6;
+    r.npl = (ctx->use_x6 == IRS_GEMM_H3 && ctx->h3_ok) ? 2 : 3;
+    r.nt = x6d ? 8 : 4;
+    // ONE predicate for the writers of K / V planes (embed kernel, layer kernel tail) and their reader (launch_attn: k_attn16h): it
+    // includes the layer loop's own condition for the fused block + 16-query attention (fragment-major activations, head dim 32,
+    // L <= 256, 16-byte aligned workspace), so a V section is never written as planes for an attention kernel that reads float32
+    r.kv_planes = fuse_block && ctx->use_attn_h3 && ctx->h3_ok && r.x6 && nl > 1 &&
+                  rows * (long long)D.n_heads > 64 * (long long)L; // (not the z-split latency grid)
+    // one sequence (the reference IRN's own regime, and the latency metric's): self-attention runs inside the layer kernel;
+    // q | k | v alternate between two buffers so that the last (rows-only) layer reads ctx->act_qkv
+    r.att_fused = small16 && rows_only && B == 1 && D.n_heads == 4 && L <= 256 && ctx->act_qkv_b1 && nl > 1;
+    // the sequence-resident layer kernel: the throughput shape of config 2 / 3 on float16 planes, layers 0 .. n_layers - 2 and
+    // the front of the last one (its q | k | v and the attention of each consumed token's block) in ONE launch, K / V in LDS.
+    // use_seq: 0 never, 1 whenever the shape allows, 2 (default) where it measured ahead: >= SEQ_AUTO_MIN_SEQS sequences (one
+    // workgroup per CU: below ~4 rounds of workgroups the last, partly filled round costs more than the fusion saves --
+    // profiles/r05/seq_sizes.txt: 6-layer decode 0.98 vs 1.06 ms at 1024 users, 3.83 vs 3.98 at 4096, but 0.89 vs 0.80 at 768)
+    r.seq = (ctx->use_seq == 1 || (ctx->use_seq == 2 && B >= SEQ_AUTO_MIN_SEQS)) && rows_only && r.kv_planes && irs_seq_shape(D) &&
+            !r.small_plan && ctx->tile_seq && ctx->use_x6 == IRS_GEMM_H3 && ctx->h3_ok && B <= 1024 * SEQ_PLAN_PER_THREAD;
+
+    if (!rows_only) r.plan = DecPlan::NONE;
+    else if (r.small_plan && B == 1 && L <= 256 && nl > 1 && (r.att_fused || any)) r.plan = DecPlan::IN_EMBED;
+    else r.plan = r.small_plan ? DecPlan::SMALL : DecPlan::MULTI;
+
+    if (r.seq) r.embed = DecEmbed::SEQ;
+    else if (r.frag && (d == 128 || x6d) && nl > 1) r.embed = DecEmbed::FRAG_QKV;
+    else if (r.frag) r.embed = DecEmbed::FRAG;
+    else if (rows_only && small16 && nl > 1) r.embed = DecEmbed::SMALL16_QKV;
+    else if (rows_only && any && nl > 1) r.embed = DecEmbed::ANY_QKV;
+    else r.embed = rows_only ? DecEmbed::PACKED : DecEmbed::FULL;
+
+    if (fuse_block) r.layer = DecFam::FRAG_FUSED;
+    else if (r.frag) r.layer = (d == 128 && F == 256) ? DecFam::FRAG_BLOCK : DecFam::FRAG_GEMM;
+    else if (small16) r.layer = DecFam::SMALL16;
+    else if (wide) r.layer = DecFam::WIDE;
+    else if (any) r.layer = DecFam::ANY;
+    // (rows of 129..256 values: one workgroup per 128 tokens covers ALL columns, so below ~256 workgroups the unfused form --
+    //  one workgroup per 128 x 128 output block, then a LayerNorm pass -- fills the chip better: C5's 32 windows = 6400 rows
+    //  ran 4 % slower fused)
+    else if (d <= LIN_BN || (d <= 2 * LIN_BN && rows >= 32768)) r.layer = DecFam::GEMM_LN;
+    else r.layer = DecFam::GEMM;
+
+    // feeding the rows-only last layer: its queries are needed for B rows only -> the fused launch before it writes k | v
+    // (8 of 12 tiles), or, sequence-resident, nothing
+    r.kv_only = rows_only && nl > 1 && (r.layer == DecFam::FRAG_BLOCK || r.layer == DecFam::FRAG_FUSED);
+
+    if (d == 128 && F == 256) r.tail = DecFam::SMALL16;
+    else if (small_wide_shape(d, F) && ctx->w_frag16 && !r.frag) r.tail = DecFam::WIDE;
+    else if (small_any_shape(d, F) && ctx->w_frag16 && !r.frag && B <= 2048) r.tail = DecFam::ANY;
+    else r.tail = d <= LIN_BN ? DecFam::GEMM_LN : DecFam::GEMM;
+    return r;
+}
+
+// one irs_launch_decode call: its route and the buffers its launches share
+struct DecodeCall {
+    irs_ctx *ctx;
+    DecodeRoute r;
+    const int64_t *seq;
+    int B, rows;
+    float *x, *y;                                  // row-major x and the other buffer of the 16-token kernels (they swap)
+    hipStream_t s;
+    const int32_t *off, *cnt, *tok, *qrow, *m_dev; // the packing plan (rows-only decodes; null otherwise)
+};
+
+// the q | k | v buffer of layer l (att_fused: two buffers alternate, the last layer's is ctx->act_qkv)
+static float *qkv_buf(const DecodeCall &c, int l) {
+    return (!c.r.att_fused || ((c.ctx->dims.n_layers - 1 - l) & 1) == 0) ? c.ctx->act_qkv : c.ctx->act_qkv_b1;
+}
+
+// fragment-packed weights of the 16-token kernels (irs_launch_pack_small): layer l's Wo | W1 | W2, and layer l's W_in
+static const float *small_wf(const irs_ctx *ctx, DecFam f, int l) {
+    const int d = ctx->dims.d, F = ctx->dims.ffn_dim;
+    return ctx->w_frag16 + (size_t)l * (f == DecFam::ANY ? small_any_layer_floats(d, F) : small_wide_layer_floats(d, F));
+}
+static const float *small_wfin(const irs_ctx *ctx, DecFam f, int l) {
+    const int d = ctx->dims.d, F = ctx->dims.ffn_dim;
+    if (f == DecFam::ANY) return small_wf(ctx, f, l) + small_any_win_off(d, F);
+    return small_wf(ctx, f, ctx->dims.n_layers) + (size_t)l * 3 * d * d;
+}
+
+// the rest of layer l on M rows for a 16-token kernel; with next, the next layer's q | k | v into qkv as well
+static SmallBlockArgs small_args(const irs_ctx *ctx, DecFam f, int l, const float *ao, const float *x, const int32_t *xidx, float *xo,
+                                 float *qkv, int M, const int32_t *m_dev, bool next) {
+    const irs_layer_w &w = ctx->layer[l];
+    return SmallBlockArgs{ao, x, w.sa_out_w, w.sa_out_b, w.n1_w, w.n1_b, ctx->c_l + (size_t)l * ctx->dims.d, w.n2_w, w.n2_b,
+                          w.l1_w, w.l1_b, w.l2_w, w.l2_b, w.n3_w, w.n3_b, xo, next ? ctx->layer[l + 1].sa_in_w : nullptr,
+                          next ? ctx->layer[l + 1].sa_in_b : nullptr, qkv, M, m_dev, xidx, small_wf(ctx, f, l),
+                          next ? small_wfin(ctx, f, l + 1) : nullptr};
+}
+
+// one launch of a 16-token layer kernel on sb.M rows (mt2: 32 tokens per workgroup, SMALL16 only)
+static void launch_small(irs_ctx *ctx, DecFam f, const SmallBlockArgs &sb, bool att, bool mt2, hipStream_t s) {
+    const int d = ctx->dims.d, F = ctx->dims.ffn_dim, M = sb.M;
+    const bool qkv = sb.Win != nullptr;
+    irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
+    if (f == DecFam::WIDE) {
+        hipLaunchKernelGGL((qkv ? k_block_small_wide<256, true> : k_block_small_wide<256, false>), dim3((M + 15) / 16), dim3(512), 0, s, sb);
+    } else if (f == DecFam::ANY) {
+        launch_small_any(qkv, M, d, F, sb, s);
+    } else {
+        void (*k)(SmallBlockArgs) = mt2 ? (qkv ? k_block_small16<true, 2> : k_block_small16<false, 2>)
+                                  : att ? (qkv ? k_block_small16<true, 1, true> : k_block_small16<false, 1, true>)
+                                        : (qkv ? k_block_small16<true, 1> : k_block_small16<false, 1>);
+        hipLaunchKernelGGL(k, dim3(mt2 ? (M + 31) / 32 : (M + 15) / 16), dim3(64 * SB_NW), 0, s, sb);
+    }
+    irs_prof_end(ctx, IRS_PROF_LINEAR, s, 2.0 * M * ((double)d * d + 2.0 * d * F + (qkv ? 3.0 * d * d : 0.0)),
+                 4.0 * (3.0 + (qkv ? 3.0 : 0.0)) * M * (double)d);
+}
+
+static void launch_embed(const DecodeCall &c, const int32_t *pos, const int64_t *user) {
+    irs_ctx *ctx = c.ctx;
+    const DecodeRoute &r = c.r;
+    const int L = ctx->dims.max_len, d = ctx->dims.d, nl = ctx->dims.n_layers, rows = c.rows;
+    const float sqrtd = sqrtf((float)d);
+    float *xf = ctx->act_xf;
+    const hipStream_t s = c.s;
+    switch (r.embed) {
+    case DecEmbed::SEQ: { // the embedding is the prologue of the sequence-resident launch
+        BlockX6Args xa{};
+        xa.Af = ctx->act_yf, xa.Rf = xf, xa.Xf = xf, xa.QKV = ctx->act_qkv, xa.M = rows, xa.m_dev = c.m_dev, xa.qkv_pass0 = 3;
+        xa.seq_qrow = ctx->seq_qrow;
+        xa.seq = c.seq, xa.L = L;
+        xa.E = ctx->item_emb, xa.pe = ctx->pe, xa.tok_row = c.tok, xa.sqrtd = sqrtd, xa.n_item = ctx->dims.n_item;
+        xa.Wbase = x6_stream(ctx, 2, 0), xa.wstride = (long long)(x6_layer_b(ctx, 2) / 16), xa.n_lay = nl - 1, xa.nl_total = nl;
+        xa.vecpack = seq_vecpack(ctx);
+        xa.c = ctx->c_l; // (non-null: the second LayerNorm always runs)
+        xa.tile_seq = ctx->tile_seq, xa.tile_qb = ctx->tile_idx, xa.seq_off = ctx->seq_off, xa.seq_cnt = ctx->seq_cnt;
+        xa.seq_padq = ctx->seq_padq, xa.seq_row0 = ctx->seq_row0, xa.n_wg_dev = ctx->n_wg_dev, xa.r_u = ctx->act_ru;
+        xa.mask_mode = ctx->dims.mask_mode;
+        const double fl = (double)(nl - 1) * rows * (8.0 * d * d + 4.0 * d * ctx->dims.ffn_dim);
+        irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
+        irs_prof_begin(ctx, IRS_PROF_LAYER, s);
+        x6_launch_seq(c.B, xa, s);
+        irs_prof_end(ctx, IRS_PROF_LINEAR, s, fl, (double)(nl - 1) * 3.0 * 4.0 * rows * (double)d);
+        irs_prof_end(ctx, IRS_PROF_LAYER, s, fl, (double)(nl - 1) * 3.0 * 4.0 * rows * (double)d);
+        break;
+    }
+    case DecEmbed::FRAG_QKV: // embed + layer 0's q | k | v in one kernel
+        irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
+        if (r.x6) { // the same kernel on split-bf16 MFMAs: k_block_x6's q | k | v steps behind an embed prologue
+            BlockX6Args xa{};
+            xa.Wx = x6_stream(ctx, r.npl, nl - 1);
+            xa.bin = ctx->layer[0].sa_in_b, xa.Xf = xf, xa.QKV = ctx->act_qkv, xa.M = rows, xa.m_dev = c.m_dev;
+            xa.seq = c.seq, xa.E = ctx->item_emb, xa.pe = ctx->pe, xa.tok_row = c.tok, xa.L = L, xa.sqrtd = sqrtd, xa.n_item = ctx->dims.n_item;
+            xa.kv_planes = r.kv_planes ? 1 : 0;
+            x6_launch(0, true, r.nt, r.npl, rows, xa, s);
+        } else {
+            EmbedQkvArgs ea{c.seq, ctx->item_emb, ctx->pe, c.tok, c.m_dev, rows, L, sqrtd, ctx->dims.n_item, xf,
+                            ctx->layer[0].sa_in_w, ctx->layer[0].sa_in_b, ctx->act_qkv};
+            hipLaunchKernelGGL(k_embed_qkv, dim3((rows + 127) / 128), dim3(256), 0, s, ea);
+        }
+        irs_prof_end(ctx, IRS_PROF_LINEAR, s, 6.0 * rows * (double)d * d, 4.0 * 4.0 * rows * (double)d);
+        break;
+    case DecEmbed::FRAG:
+        hipLaunchKernelGGL(k_embed_frag, dim3((rows + 127) / 128), dim3(256), 0, s, c.seq, ctx->item_emb, ctx->pe, xf, c.tok, c.m_dev,
+                           rows, L, d, sqrtd, ctx->dims.n_item);
+        break;
+    case DecEmbed::SMALL16_QKV:
+    case DecEmbed::ANY_QKV: { // latency paths: embed + layer 0's q | k | v in one 16-token kernel
+        const DecFam f = r.embed == DecEmbed::SMALL16_QKV ? DecFam::SMALL16 : DecFam::ANY;
+        SmallEmbedArgs ea{c.seq, ctx->item_emb, ctx->pe, c.tok, c.m_dev, rows, L, sqrtd, ctx->dims.n_item, c.x,
+                          small_wfin(ctx, f, 0), ctx->layer[0].sa_in_b, qkv_buf(c, 0)};
+        const bool plan = r.plan == DecPlan::IN_EMBED; // one sequence: the kernel derives the plan k_plan_small would write
+        if (plan) {
+            ea.pos = pos, ea.cnt = ctx->seq_cnt, ea.off = ctx->seq_off, ea.qrow = ctx->seq_qrow, ea.tok_out = ctx->tok_row;
+            ea.padq = ctx->seq_padq, ea.mdev_out = ctx->m_dev, ea.user = user, ea.U = pif_table(ctx);
+            ea.uw = ctx->um_w, ea.ub = ctx->um_b, ea.r_u = ctx->act_ru, ea.ud = ctx->dims.u_dim, ea.n_user = ctx->dims.n_user;
+            ea.step_pair = ctx->step_pair;
+        }
+        const dim3 grid((rows + 15) / 16);
+        irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
+        if (f == DecFam::SMALL16) {
+            hipLaunchKernelGGL((plan ? k_embed_qkv_small16<true> : k_embed_qkv_small16<false>), grid, dim3(256), 0, s, ea);
+        } else {
+#define E_(T_) hipLaunchKernelGGL((plan ? k_embed_qkv_small_any<T_, true> : k_embed_qkv_small_any<T_, false>), grid, dim3(256), 0, s, ea, d)
+            switch (small_any_dp(d)) {
+            case 32: E_(2); break;
+            case 64: E_(4); break;
+            default: E_(6); break;
+            }
+#undef E_
+        }
+        irs_prof_end(ctx, IRS_PROF_LINEAR, s, 6.0 * rows * (double)d * d, 4.0 * 4.0 * rows * (double)d);
+        break;
+    }
+    case DecEmbed::PACKED:
+        hipLaunchKernelGGL(k_embed_packed, dim3((rows + 3) / 4), dim3(256), 0, s, c.seq, ctx->item_emb, ctx->pe, c.x, c.tok, c.m_dev,
+                           L, d, sqrtd, ctx->dims.n_item);
+        break;
+    case DecEmbed::FULL:
+        hipLaunchKernelGGL(k_embed, dim3((rows + 3) / 4), dim3(256), 0, s, c.seq, ctx->item_emb, ctx->pe, c.x, rows, L, d, sqrtd,
+                           ctx->dims.n_item);
+        break;
+    }
+}
+
+// the rest of layer l on M row-major rows with the per-GEMM float32 kernels (GEMM_LN / GEMM): attention output ao, residual res
+// -> out; mid holds LN2's output (the FFN's input and residual), tmp the unnormalised sums of the unfused form
+static int gemm_rest(irs_ctx *ctx, bool ln_fused, int l, const float *ao, const float *res, float *mid, float *tmp, float *out,
+                     int M, const int32_t *m_dev, hipStream_t s) {
+    const int d = ctx->dims.d, F = ctx->dims.ffn_dim;
+    const irs_layer_w &w = ctx->layer[l];
+    const float *cl = ctx->c_l + (size_t)l * d;
+    int rc;
+    if (ln_fused) {
+        // mid <- LN2(LN1(res + ao W_o^T + b_o) + c_l), fused into the GEMM epilogue
+        if ((rc = launch_linear(ctx, ao, w.sa_out_w, w.sa_out_b, res, mid, M, d, d, false, s, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b,
+                                nullptr, nullptr, m_dev)))
+            return rc;
+        // h = relu(mid W1^T + b1); out <- LN3(mid + h W2^T + b2)
+        if ((rc = launch_linear(ctx, mid, w.l1_w, w.l1_b, nullptr, ctx->act_h, M, F, d, true, s, nullptr, nullptr, nullptr, nullptr,
+                                nullptr, nullptr, nullptr, m_dev)))
+            return rc;
+        return launch_linear(ctx, ctx->act_h, w.l2_w, w.l2_b, mid, out, M, d, F, false, s, w.n3_w, w.n3_b, nullptr, nullptr, nullptr,
+                             nullptr, nullptr, m_dev);
+    }
+    // tmp = res + ao W_o^T + b_o ; mid = LN2(LN1(tmp) + c_l)          (packed rows: every kernel clamps to m_dev)
+    if ((rc = launch_linear(ctx, ao, w.sa_out_w, w.sa_out_b, res, tmp, M, d, d, false, s, nullptr, nullptr, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, m_dev)))
+        return rc;
+    hipLaunchKernelGGL(k_ln, dim3((M + 3) / 4), dim3(256), 0, s, tmp, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b, mid, M, d, m_dev);
+    // h = relu(mid W1^T + b1); tmp = mid + h W2^T + b2; out = LN3(tmp)
+    if ((rc = launch_linear(ctx, mid, w.l1_w, w.l1_b, nullptr, ctx->act_h, M, F, d, true, s, nullptr, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, m_dev)))
+        return rc;
+    if ((rc = launch_linear(ctx, ctx->act_h, w.l2_w, w.l2_b, mid, tmp, M, d, F, false, s, nullptr, nullptr, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, m_dev)))
+        return rc;
+    hipLaunchKernelGGL(k_ln, dim3((M + 3) / 4), dim3(256), 0, s, tmp, w.n3_w, w.n3_b, (const float *)nullptr, (const float *)nullptr,
+                       (const float *)nullptr, out, M, d, m_dev);
+    return IRS_OK;
+}
+
+// layer l behind its attention, fragment-major x / y (FRAG_* families)
+static int frag_layer(const DecodeCall &c, int l) {
+    irs_ctx *ctx = c.ctx;
+    const DecodeRoute &r = c.r;
+    const int d = ctx->dims.d, F = ctx->dims.ffn_dim, nl = ctx->dims.n_layers, rows = c.rows;
+    const irs_layer_w &w = ctx->layer[l];
+    const float *cl = ctx->c_l + (size_t)l * d;
+    const int32_t *m_dev = c.m_dev;
+    float *xf = ctx->act_xf, *yf = ctx->act_yf;
+    const hipStream_t s = c.s;
+    int rc;
+    const bool last = l + 1 == nl;
+    const bool tail = !last && r.layer != DecFam::FRAG_GEMM; // the layer kernel also writes the next layer's q | k | v
+    const bool kv_only = tail && r.kv_only && l + 2 == nl;
+    BlockArgs ba{};
+    ba.W1 = w.l1_w, ba.b1 = w.l1_b, ba.W2 = w.l2_w, ba.b2 = w.l2_b, ba.g = w.n3_w, ba.b = w.n3_b;
+    ba.Xf = last ? nullptr : xf, ba.Y = last ? c.x : nullptr, ba.M = rows, ba.m_dev = m_dev;
+    ba.Win = tail ? ctx->layer[l + 1].sa_in_w : nullptr, ba.bin = tail ? ctx->layer[l + 1].sa_in_b : nullptr;
+    ba.QKV = ctx->act_qkv;
+    ba.qkv_n0 = kv_only ? 128 : 0, ba.qkv_nt1 = kv_only ? 2 : 6;
+    const double ffn_flops = 4.0 * rows * (double)d * F + (tail ? (kv_only ? 4.0 : 6.0) * rows * (double)d * d : 0.0);
+    if (r.layer == DecFam::FRAG_FUSED) {
+        ba.Af = yf, ba.Rf = xf, ba.Wo = w.sa_out_w, ba.bo = w.sa_out_b;
+        ba.g1 = w.n1_w, ba.b1n = w.n1_b, ba.c = cl, ba.g2 = w.n2_w, ba.b2n = w.n2_b;
+        irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
+        if (tail) irs_prof_begin(ctx, IRS_PROF_LAYER, s); // (one family is enabled at a time)
+        if (tail && r.x6) { // the same layer tail on split-bf16 MFMAs
+            BlockX6Args xa{yf, xf, x6_stream(ctx, r.npl, l), w.sa_out_b, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b,
+                           w.l1_b, w.l2_b, w.n3_w, w.n3_b, ctx->layer[l + 1].sa_in_b, xf, ctx->act_qkv, rows, m_dev, kv_only ? 1 : 0};
+            xa.kv_planes = r.kv_planes ? 1 : 0;
+            x6_launch(kv_only ? 1 : 0, false, r.nt, r.npl, rows, xa, s);
+        } else if (r.nt == 8) IRS_FAIL(ctx, IRS_E_STATE, "d = 256 fused layer kernel without a successor layer");
+        else hipLaunchKernelGGL((tail ? k_block<true, true> : k_block<true, false>), dim3((rows + 127) / 128), dim3(256), 0, s, ba);
+        irs_prof_end(ctx, IRS_PROF_LINEAR, s, ffn_flops + 2.0 * rows * (double)d * d, (8.0 + 4.0 + (tail ? 12.0 : 0.0)) * rows * (double)d);
+        if (tail) irs_prof_end(ctx, IRS_PROF_LAYER, s, ffn_flops + 2.0 * rows * (double)d * d, (8.0 + 4.0 + 12.0) * rows * (double)d);
+        return IRS_OK;
+    }
+    // y <- LN2(LN1(x + ao W_o^T + b_o) + c_l): residual from xf, result to yf only
+    if ((rc = launch_linear(ctx, ctx->act_ao, w.sa_out_w, w.sa_out_b, nullptr, nullptr, rows, d, d, false, s, w.n1_w, w.n1_b, cl,
+                            w.n2_w, w.n2_b, xf, yf, m_dev)))
+        return rc;
+    // x <- LN3(y + relu(y W1^T + b1) W2^T + b2) back into xf (the last layer of a full decode writes the row-major x the caller
+    // receives instead); d = 128, F = 256 runs as one kernel with h in registers
+    if (r.layer == DecFam::FRAG_BLOCK) {
+        ba.Yf = yf;
+        irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
+        hipLaunchKernelGGL((tail ? k_block<false, true> : k_block<false, false>), dim3((rows + 127) / 128), dim3(256), 0, s, ba);
+        irs_prof_end(ctx, IRS_PROF_LINEAR, s, ffn_flops, (8.0 + (tail ? 12.0 : 0.0)) * rows * (double)d);
+        return IRS_OK;
+    }
+    if ((rc = launch_linear(ctx, nullptr, w.l1_w, w.l1_b, nullptr, ctx->act_h, rows, F, d, true, s, nullptr, nullptr, nullptr, nullptr,
+                            nullptr, nullptr, nullptr, m_dev, yf)))
+        return rc;
+    return launch_linear(ctx, ctx->act_h, w.l2_w, w.l2_b, nullptr, last ? c.x : nullptr, rows, d, F, false, s, w.n3_w, w.n3_b, nullptr,
+                         nullptr, nullptr, yf, last ? nullptr : xf, m_dev);
+}
+
+// layer l (before the rows-only last one, or any layer of a full decode) behind its q | k | v
+static int decode_layer(DecodeCall &c, int l) {
+    irs_ctx *ctx = c.ctx;
+    const DecodeRoute &r = c.r;
+    float *x = c.x, *y = c.y;
+    int rc;
+    const bool fused = r.layer == DecFam::FRAG_FUSED; // (attention writes its output fragment-major for the fused block)
+    if (!r.att_fused && (rc = launch_attn(ctx, ctx->act_qkv, c.seq, ctx->act_ru, fused ? ctx->act_yf : ctx->act_ao, c.B, c.s, c.off,
+                                          c.cnt, c.tok, fused, r.kv_planes)))
+        return rc;
+    switch (r.layer) {
+    case DecFam::FRAG_GEMM:
+    case DecFam::FRAG_BLOCK:
+    case DecFam::FRAG_FUSED:
+        return frag_layer(c, l);
+    case DecFam::SMALL16:
+    case DecFam::WIDE:
+    case DecFam::ANY: { // latency paths: the rest of the layer (and the next layer's q | k | v) in one launch; x -> y buffer
+        SmallBlockArgs sb = small_args(ctx, r.layer, l, ctx->act_ao, x, nullptr, y, qkv_buf(c, l + 1), c.rows, c.m_dev,
+                                       l + 1 < ctx->dims.n_layers);
+        if (r.att_fused) {
+            sb.QKVin = qkv_buf(c, l), sb.r_u = ctx->act_ru, sb.seq_last = c.seq + (ctx->dims.max_len - 1), sb.cnt = c.cnt;
+            sb.padq = ctx->seq_padq, sb.mask_mode = ctx->dims.mask_mode;
+        }
+        // 32 tokens per workgroup once the 16-token tiles outnumber the resident workgroups (2 per CU): per path
+        // step 518 vs 563 us at 128 users, but 267 vs 222 at 16 users; 64 tokens measured no better than 32
+        launch_small(ctx, r.layer, sb, r.att_fused, c.rows > SMALL_MT2_ROWS, c.s);
+        c.x = y; // the new x lives in the other buffer
+        c.y = x;
+        return IRS_OK;
+    }
+    default: // x in place (y: scratch)
+        return gemm_rest(ctx, r.layer == DecFam::GEMM_LN, l, ctx->act_ao, x, r.layer == DecFam::GEMM_LN ? y : x, y, x, c.rows, c.m_dev,
+                         c.s);
+    }
+}
+
+// the rows-only last layer l behind its q | k | v: attention and the rest of the layer for the B consumed rows -> xrows
+static int last_layer(const DecodeCall &c, int l, const int32_t *pos, float *xrows) {
+    irs_ctx *ctx = c.ctx;
+    const DecodeRoute &r = c.r;
+    const int L = ctx->dims.max_len, d = ctx->dims.d, H = ctx->dims.n_heads, B = c.B;
+    const irs_layer_w &w = ctx->layer[l];
+    const int32_t *qrow = c.qrow;
+    const hipStream_t s = c.s;
+    int rc;
+    float *xf = ctx->act_xf, *h_r = ctx->act_h;      // h_r: [B, d] queries (kv_only)
+    // [B, d] attention output rows, residual rows x[b, pos[b]], LN2 output and unnormalised sums of the per-GEMM tails
+    float *ao_r = ctx->act_ao, *x_r = ao_r + (size_t)B * d, *y_r = ao_r + (size_t)2 * B * d, *z_r = ao_r + (size_t)3 * B * d;
+    const float *q_r = nullptr;
+    const int nt = d > 128 ? d / 32 : 4;       // column tiles per token of the fragment-major images
+    if (r.seq) {
+        // the sequence-resident launch ran this layer's q | k | v and the attention of every consumed token's block: the
+        // residual row and the attention row come out of the fragment-major images by the tile-order row index
+        hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, xf, ctx->qrow_tile, x_r, d, nt);
+        hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, ctx->act_yf, ctx->qrow_tile, ao_r, d, nt);
+    } else if (r.kv_only) { // the previous layer's kernel wrote k | v only: queries for the B consumed rows here
+        hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, xf, qrow, x_r, d, nt);
+        if ((rc = launch_linear(ctx, x_r, w.sa_in_w, w.sa_in_b, nullptr, h_r, B, d, d, false, s))) return rc;
+        q_r = h_r;
+    }
+    irs_prof_begin(ctx, IRS_PROF_ATTN, s);
+    if (r.seq) {
+    } else if (d / H == 32 && L <= 256 && d % 4 == 0 && (((uintptr_t)ctx->act_qkv | (uintptr_t)q_r) & 15) == 0)
+        hipLaunchKernelGGL(k_attn_row32, dim3(H, B), dim3(256), 0, s, ctx->act_qkv, c.seq, ctx->act_ru, ao_r, L, d,
+                           ctx->dims.mask_mode, c.off, c.cnt, qrow, q_r, ctx->seq_padq);
+    else
+        hipLaunchKernelGGL(k_attn_row, dim3(H, B), dim3(64), 0, s, ctx->act_qkv, c.seq, ctx->act_ru, pos, ao_r, L, d, d / H,
+                           ctx->dims.mask_mode, c.off, c.cnt, c.tok, qrow, q_r);
+    irs_prof_end(ctx, IRS_PROF_ATTN, s, 4.0 * B * (double)L * d, 4.0 * 3.0 * B * (double)L * d);
+    const bool small = r.tail == DecFam::SMALL16 || r.tail == DecFam::WIDE || r.tail == DecFam::ANY;
+    const bool idx_res = small && !r.frag; // the layer kernel reads the residual rows x[qrow[b]] itself
+    if (r.frag && !r.kv_only) hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, xf, qrow, x_r, d, nt);
+    else if (!r.frag && !idx_res) hipLaunchKernelGGL(k_gather_rows_idx, dim3(B), dim3(64), 0, s, c.x, qrow, x_r, d);
+    if (small) { // one launch for the rest of the layer on the B consumed rows
+        const SmallBlockArgs sb = small_args(ctx, r.tail, l, ao_r, idx_res ? c.x : x_r, idx_res ? qrow : nullptr, xrows, nullptr, B,
+                                             nullptr, false);
+        launch_small(ctx, r.tail, sb, false, B > 2048, s);
+    } else if ((rc = gemm_rest(ctx, r.tail == DecFam::GEMM_LN, l, ao_r, x_r, y_r, z_r, xrows, B, nullptr, s))) {
+        return rc;
     }
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
@@ -5999,421 +6378,47 @@ int irs_launch_pack_small(irs_ctx *ctx, hipStream_t s) {
 
 int irs_launch_decode(irs_ctx *ctx, const int64_t *seq, const int64_t *user, int B, float *x_out, const int32_t *pos,
                       float *xrows, float *r_u_out, hipStream_t s) {
-    const int L = ctx->dims.max_len, d = ctx->dims.d, F = ctx->dims.ffn_dim;
-    const int rows = B * L;
+    const int L = ctx->dims.max_len, d = ctx->dims.d, nl = ctx->dims.n_layers;
+    const DecodeRoute r = decode_route(ctx, B, x_out == nullptr && pos && xrows && L >= 4);
     int rc;
-    // rows-only decode of a few sequences: the plan kernel also computes r_u (and hands the step counter over)
-    const bool small_plan = (x_out == nullptr) && pos && xrows && L >= 4 && B <= 64;
-    const bool rows_only = (x_out == nullptr) && pos && xrows && L >= 4;
-    if (ctx->step_pair && !small_plan) IRS_FAIL(ctx, IRS_E_STATE, "merged path step needs the single-workgroup plan kernel");
-    if (!small_plan && (rc = irs_launch_pif(ctx, user, B, ctx->act_ru, s)) != IRS_OK) return rc;
-    float *x = ctx->act_x, *y = ctx->act_y;
-    // rows-only decode: the caller wants x[b, pos[b], :] only.  Then (1) the decoder runs on the PACKED
-    // non-pad tokens (k_plan), every kernel clamping its row count to the device-side total, and (2) the
-    // LAST layer is evaluated for the one consumed row per sequence (all earlier layers need every valid
-    // row: they feed the next layer's keys and values).
-    const int32_t *off = nullptr, *cnt = nullptr, *tok = nullptr, *qrow = nullptr, *m_dev = nullptr;
-    // throughput shapes keep x / y ONLY in the fragment-major layout between the layers (see frag_index): the
-    // LN-fused GEMMs write it, read their residual from it, and the QKV / FFN1 GEMMs load it as their X operand
-    // The 16-token layer kernel's regime.  Measured crossover with the 128-token fragment-major path on C2 (L = 200):
-    // 564 vs 720 us per path step at 128 users, 921 vs 797 at 256 (the big path has a ~700 us floor per step: one round
-    // of 128-token tiles streams the weights serially through LDS whatever the number of tiles).
-    const bool small_cfg = d == 128 && F == 256 && ctx->w_frag16 && rows <= SMALL_ROWS_MAX;
-    // any other small shape: the generic fused layer tail.  Measured against the per-GEMM kernels (per path step):
-    // default (d = 30, L = 60) 235 vs 582 us at 64 users, 859 vs 1055 at 1024; config 1 (d = 64, L = 50) 259 vs 653
-    // at 64 users, 888 vs 1040 at 1024 -- ahead over the whole tested range
-    const bool any_cfg = small_any_shape(d, F) && ctx->w_frag16 && rows <= 65536;
-    // d = 256 (C4's decoder), rows-only decode of a throughput batch: the split-bf16 fused layer kernel at 8 accumulator tiles
-    // per token (k_block_x6<.., NT = 8>) with fragment-major activations, like d = 128.  Everything else at d = 256 (full
-    // decodes, small batches, IRS_GEMM_F32) keeps the per-GEMM float32 kernels.
-    const bool x6d = d == 256 && F == 256 && ctx->use_x6 && ctx->w_x6 && rows_only && rows >= 32768 && ctx->dims.n_layers > 1 &&
-                     attn16_ok(ctx, ctx->act_qkv, ctx->act_yf);
-    // the split-precision layer kernels hand K / V to the attention as float16 plane pairs (k_attn16h) unless switched off
-    // ONE predicate for the writers (embed kernel, layer kernel tail) and the reader (launch_attn: k_attn16h): it includes the
-    // layer loop's own condition for the fused block + 16-query attention (fragment-major activations, head dim 32, L <= 256,
-    // 16-byte aligned workspace), so a V section is never written as planes for an attention kernel that reads float32
-    const bool frag = (d <= LIN_BN && d % 32 == 0 && rows > 2048 && !small_cfg && !any_cfg) || x6d;
-    const bool fuse_block_cfg = frag && (d == 128 || x6d) && F == 256 && attn16_ok(ctx, ctx->act_qkv, ctx->act_yf);
-    const bool kv_planes = fuse_block_cfg && ctx->use_attn_h3 && ctx->h3_ok && ctx->use_x6 && ctx->w_x6 && ctx->dims.n_layers > 1 &&
-                           rows * (long long)ctx->dims.n_heads > 64 * (long long)L; // (not the z-split latency grid)
-    // d = 256 below the throughput regime (C5's 32 beam windows, single users): the 16-token fused layer kernel for wide
-    // models (k_block_small_wide) instead of ~8 per-GEMM launches per layer
-    const bool wide_cfg = small_wide_shape(d, F) && ctx->w_frag16 && !x6d && rows < 32768;
-    const size_t wide_lf = small_wide_layer_floats(d, F); // one wave (32 tokens) per workgroup: a few thousand tokens still reach every CU
-    // one sequence (the reference IRN's own regime, and the latency metric's): self-attention runs inside the layer
-    // kernel; q | k | v alternate between two buffers so that the last (rows-only) layer reads ctx->act_qkv
-    const bool att_fused = small_cfg && rows_only && B == 1 && ctx->dims.n_heads == 4 && L <= 256 && ctx->act_qkv_b1 &&
-                           ctx->dims.n_layers > 1;
-    auto qkv_in = [&](int l) { return (!att_fused || ((ctx->dims.n_layers - 1 - l) & 1) == 0) ? ctx->act_qkv : ctx->act_qkv_b1; };
-    float *xf = ctx->act_xf, *yf = ctx->act_yf;
-    // the sequence-resident layer kernel (round 5, opt-in: irs_set_decoder_seq / IRS_DECODER_SEQ=1): the throughput shape of
-    // config 2 / 3 on float16 planes; layers 0 .. n_layers - 2 are ONE launch each (q | k | v, attention and the layer body; K / V
-    // stay in LDS), the rows-only last layer runs as before on the k | v rows the last of them writes
-    // use_seq: 0 never, 1 whenever the shape allows, 2 (default) where it measured ahead: >= SEQ_AUTO_MIN_SEQS sequences (one
-    // workgroup per CU: below ~4 rounds of workgroups the last, partly filled round costs more than the fusion saves --
-    // profiles/r05/seq_sizes.txt: 6-layer decode 0.98 vs 1.06 ms at 1024 users, 3.83 vs 3.98 at 4096, but 0.89 vs 0.80 at 768)
-    const bool seq_mode = (ctx->use_seq == 1 || (ctx->use_seq == 2 && B >= SEQ_AUTO_MIN_SEQS)) && rows_only && kv_planes && d == 128 &&
-                          ctx->dims.n_heads == 4 && L <= 256 && !small_plan && ctx->tile_seq && ctx->use_x6 == IRS_GEMM_H3 && ctx->h3_ok &&
-                          B <= 1024 * SEQ_PLAN_PER_THREAD;
-    ctx->seq_last = seq_mode;
-    if (rows_only) {
-        const bool plan_in_embed = small_plan && B == 1 && L <= 256 && ctx->dims.n_layers > 1 && (att_fused || any_cfg);
-        if (plan_in_embed) {
-            // one sequence: the embedding kernel below derives the plan itself
-        } else if (small_plan) {
-            const bool pif = ctx->dims.mask_mode == IRS_MASK_IRN && ctx->user_emb;
-            hipLaunchKernelGGL(k_plan_small, dim3(1), dim3(1024), 0, s, seq, pos, B, L, ctx->seq_cnt, ctx->seq_off, ctx->seq_qrow,
-                               ctx->tok_row, ctx->seq_padq, ctx->m_dev, user, pif ? ctx->user_emb : nullptr, ctx->um_w, ctx->um_b,
-                               ctx->act_ru, ctx->dims.u_dim, ctx->dims.n_user, ctx->step_pair);
-        } else {
-            hipLaunchKernelGGL(k_plan_count, dim3((B + 3) / 4), dim3(256), 0, s, seq, pos, B, L, ctx->seq_cnt, ctx->tile_seq);
-            hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(1024), 0, s, ctx->seq_cnt, B, ctx->seq_off, ctx->m_dev);
-            hipLaunchKernelGGL(k_plan_fill, dim3((B + 3) / 4), dim3(256), 0, s, seq, pos, B, L, ctx->seq_off, ctx->seq_qrow,
-                               ctx->tok_row, ctx->seq_padq);
-        }
-        off = ctx->seq_off;
-        cnt = ctx->seq_cnt;
-        tok = ctx->tok_row;
-        qrow = ctx->seq_qrow;
-        m_dev = ctx->m_dev;
+    if (ctx->step_pair && !r.small_plan) IRS_FAIL(ctx, IRS_E_STATE, "merged path step needs the single-workgroup plan kernel");
+    if (!r.small_plan && (rc = irs_launch_pif(ctx, user, B, ctx->act_ru, s)) != IRS_OK) return rc;
+    ctx->seq_last = r.seq;
+    DecodeCall c{ctx, r, seq, B, B * L, ctx->act_x, ctx->act_y, s};
+    if (r.rows_only) c.off = ctx->seq_off, c.cnt = ctx->seq_cnt, c.tok = ctx->tok_row, c.qrow = ctx->seq_qrow, c.m_dev = ctx->m_dev;
+    if (r.plan == DecPlan::SMALL) {
+        hipLaunchKernelGGL(k_plan_small, dim3(1), dim3(1024), 0, s, seq, pos, B, L, ctx->seq_cnt, ctx->seq_off, ctx->seq_qrow,
+                           ctx->tok_row, ctx->seq_padq, ctx->m_dev, user, pif_table(ctx), ctx->um_w, ctx->um_b, ctx->act_ru,
+                           ctx->dims.u_dim, ctx->dims.n_user, ctx->step_pair);
+    } else if (r.plan == DecPlan::MULTI) {
+        hipLaunchKernelGGL(k_plan_count, dim3((B + 3) / 4), dim3(256), 0, s, seq, pos, B, L, ctx->seq_cnt, ctx->tile_seq);
+        hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(1024), 0, s, ctx->seq_cnt, B, ctx->seq_off, ctx->m_dev);
+        hipLaunchKernelGGL(k_plan_fill, dim3((B + 3) / 4), dim3(256), 0, s, seq, pos, B, L, ctx->seq_off, ctx->seq_qrow, ctx->tok_row,
+                           ctx->seq_padq);
     }
-    bool qkv0_done = false;
-    int l_begin = 0;
-    if (seq_mode) {
-        const int nl = ctx->dims.n_layers;
-        hipLaunchKernelGGL(k_plan_seq, dim3(1), dim3(1024), 0, s, ctx->seq_cnt, ctx->seq_off, ctx->seq_qrow, B, ctx->tile_seq, ctx->tile_idx,
-                           ctx->seq_row0, ctx->qrow_tile, ctx->n_wg_dev, B * SEQ_WG_TILES);
-        {   // layers 0 .. nl - 2 in ONE launch (x resident in registers from layer to layer); the last of them writes the k | v rows
-            BlockX6Args xa{};
-            xa.Af = yf, xa.Rf = xf, xa.Xf = xf, xa.QKV = ctx->act_qkv, xa.M = rows, xa.m_dev = m_dev, xa.qkv_pass0 = 3;
-            xa.seq_qrow = ctx->seq_qrow;
-            xa.seq = seq, xa.L = L;
-            xa.E = ctx->item_emb, xa.pe = ctx->pe, xa.tok_row = tok, xa.sqrtd = sqrtf((float)d), xa.n_item = ctx->dims.n_item; // (the embedding is the launch's prologue)
-            xa.Wbase = x6_stream(ctx, 2, 0), xa.wstride = (long long)(x6_layer_b(ctx, 2) / 16), xa.n_lay = nl - 1, xa.nl_total = nl;
-            xa.vecpack = seq_vecpack(ctx);
-            xa.c = ctx->c_l; // (non-null: the second LayerNorm always runs)
-            xa.tile_seq = ctx->tile_seq, xa.tile_qb = ctx->tile_idx, xa.seq_off = ctx->seq_off, xa.seq_cnt = ctx->seq_cnt;
-            xa.seq_padq = ctx->seq_padq, xa.seq_row0 = ctx->seq_row0, xa.n_wg_dev = ctx->n_wg_dev, xa.r_u = ctx->act_ru;
-            xa.mask_mode = ctx->dims.mask_mode;
-            const double fl = (double)(nl - 1) * rows * (8.0 * d * d + 4.0 * d * F);
-            irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
-            irs_prof_begin(ctx, IRS_PROF_LAYER, s);
-            x6_launch_seq(B, xa, s);
-            irs_prof_end(ctx, IRS_PROF_LINEAR, s, fl, (double)(nl - 1) * 3.0 * 4.0 * rows * (double)d);
-            irs_prof_end(ctx, IRS_PROF_LAYER, s, fl, (double)(nl - 1) * 3.0 * 4.0 * rows * (double)d);
-        }
-        qkv0_done = true;
-        l_begin = nl - 1;
-    } else if (frag && (d == 128 || x6d) && ctx->dims.n_layers > 1) { // embed + layer 0's QKV in one kernel
-        EmbedQkvArgs ea{seq, ctx->item_emb, ctx->pe, tok, m_dev, rows, L, sqrtf((float)d), ctx->dims.n_item, xf,
-                        ctx->layer[0].sa_in_w, ctx->layer[0].sa_in_b, ctx->act_qkv};
-        irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
-        if (ctx->use_x6 && ctx->w_x6) { // the same kernel on split-bf16 MFMAs: k_block_x6's q | k | v steps behind an embed prologue
-            BlockX6Args xa{};
-            const int npl = (ctx->use_x6 == IRS_GEMM_H3 && ctx->h3_ok) ? 2 : 3;
-            xa.Wx = x6_stream(ctx, npl, ctx->dims.n_layers - 1);
-            xa.bin = ctx->layer[0].sa_in_b, xa.Xf = xf, xa.QKV = ctx->act_qkv, xa.M = rows, xa.m_dev = m_dev;
-            xa.seq = seq, xa.E = ctx->item_emb, xa.pe = ctx->pe, xa.tok_row = tok, xa.L = L, xa.sqrtd = sqrtf((float)d), xa.n_item = ctx->dims.n_item;
-            xa.kv_planes = kv_planes ? 1 : 0;
-            x6_launch(0, true, x6d ? 8 : 4, npl, rows, xa, s);
-        } else
-        hipLaunchKernelGGL(k_embed_qkv, dim3((rows + 127) / 128), dim3(256), 0, s, ea);
-        irs_prof_end(ctx, IRS_PROF_LINEAR, s, 6.0 * rows * (double)d * d, 4.0 * 4.0 * rows * (double)d);
-        qkv0_done = true;
-    } else if (frag)
-        hipLaunchKernelGGL(k_embed_frag, dim3((rows + 127) / 128), dim3(256), 0, s, seq, ctx->item_emb, ctx->pe, xf, tok, m_dev,
-                           rows, L, d, sqrtf((float)d), ctx->dims.n_item);
-    else if (rows_only && small_cfg && ctx->dims.n_layers > 1) {
-        // latency path (the k_block_small16 regime): embed + layer 0's QKV in one 16-token kernel
-        SmallEmbedArgs ea{seq, ctx->item_emb, ctx->pe, tok, m_dev, rows, L, sqrtf((float)d), ctx->dims.n_item, x,
-                          ctx->w_frag16 + (size_t)ctx->dims.n_layers * SMALL_WF_LAYER, ctx->layer[0].sa_in_b, qkv_in(0)};
-        irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
-        if (att_fused) {
-            const bool pif = ctx->dims.mask_mode == IRS_MASK_IRN && ctx->user_emb;
-            ea.pos = pos, ea.cnt = ctx->seq_cnt, ea.off = ctx->seq_off, ea.qrow = ctx->seq_qrow, ea.tok_out = ctx->tok_row;
-            ea.padq = ctx->seq_padq, ea.mdev_out = ctx->m_dev, ea.user = user, ea.U = pif ? ctx->user_emb : nullptr;
-            ea.uw = ctx->um_w, ea.ub = ctx->um_b, ea.r_u = ctx->act_ru, ea.ud = ctx->dims.u_dim, ea.n_user = ctx->dims.n_user;
-            ea.step_pair = ctx->step_pair;
-            hipLaunchKernelGGL(k_embed_qkv_small16<true>, dim3((rows + 15) / 16), dim3(256), 0, s, ea);
-        } else
-            hipLaunchKernelGGL(k_embed_qkv_small16<false>, dim3((rows + 15) / 16), dim3(256), 0, s, ea);
-        irs_prof_end(ctx, IRS_PROF_LINEAR, s, 6.0 * rows * (double)d * d, 4.0 * 4.0 * rows * (double)d);
-        qkv0_done = true;
-    } else if (rows_only && any_cfg && ctx->dims.n_layers > 1) {
-        SmallEmbedArgs ea{seq, ctx->item_emb, ctx->pe, tok, m_dev, rows, L, sqrtf((float)d), ctx->dims.n_item, x,
-                          ctx->w_frag16 + small_any_win_off(d, F), ctx->layer[0].sa_in_b, ctx->act_qkv};
-        irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
-        const dim3 grid((rows + 15) / 16);
-        const bool plan1 = small_plan && B == 1 && L <= 256; // the plan of the one sequence is derived in the kernel
-        if (plan1) {
-            const bool pif = ctx->dims.mask_mode == IRS_MASK_IRN && ctx->user_emb;
-            ea.pos = pos, ea.cnt = ctx->seq_cnt, ea.off = ctx->seq_off, ea.qrow = ctx->seq_qrow, ea.tok_out = ctx->tok_row;
-            ea.padq = ctx->seq_padq, ea.mdev_out = ctx->m_dev, ea.user = user, ea.U = pif ? ctx->user_emb : nullptr;
-            ea.uw = ctx->um_w, ea.ub = ctx->um_b, ea.r_u = ctx->act_ru, ea.ud = ctx->dims.u_dim, ea.n_user = ctx->dims.n_user;
-            ea.step_pair = ctx->step_pair;
-        }
-#define E_(T_) do { if (plan1) hipLaunchKernelGGL((k_embed_qkv_small_any<T_, true>), grid, dim3(256), 0, s, ea, d); \
-                    else hipLaunchKernelGGL((k_embed_qkv_small_any<T_, false>), grid, dim3(256), 0, s, ea, d); } while (0)
-        switch (small_any_dp(d)) {
-        case 32: E_(2); break;
-        case 64: E_(4); break;
-        default: E_(6); break;
-        }
-#undef E_
-        irs_prof_end(ctx, IRS_PROF_LINEAR, s, 6.0 * rows * (double)d * d, 4.0 * 4.0 * rows * (double)d);
-        qkv0_done = true;
-    } else if (rows_only)
-        hipLaunchKernelGGL(k_embed_packed, dim3((rows + 3) / 4), dim3(256), 0, s, seq, ctx->item_emb, ctx->pe, x, tok, m_dev,
-                           L, d, sqrtf((float)d), ctx->dims.n_item);
-    else
-        hipLaunchKernelGGL(k_embed, dim3((rows + 3) / 4), dim3(256), 0, s, seq, ctx->item_emb, ctx->pe, x, rows, L, d,
-                           sqrtf((float)d), ctx->dims.n_item);
+    if (r.seq)
+        hipLaunchKernelGGL(k_plan_seq, dim3(1), dim3(1024), 0, s, ctx->seq_cnt, ctx->seq_off, ctx->seq_qrow, B, ctx->tile_seq,
+                           ctx->tile_idx, ctx->seq_row0, ctx->qrow_tile, ctx->n_wg_dev, B * SEQ_WG_TILES);
+    launch_embed(c, pos, user);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     if (r_u_out) IRS_CHECK_HIP(ctx, hipMemcpyAsync(r_u_out, ctx->act_ru, sizeof(float) * B, hipMemcpyDeviceToDevice, s));
-    bool qkv_done = qkv0_done, q_split = seq_mode; // (seq_mode: the last fused layer wrote k | v only)
-    const int32_t *qrow_f = seq_mode ? ctx->qrow_tile : qrow; // the consumed rows in the fragment-major image's own row order
-    for (int l = l_begin; l < ctx->dims.n_layers; ++l) {
+    const bool embed_qkv = r.embed == DecEmbed::SEQ || r.embed == DecEmbed::FRAG_QKV || r.embed == DecEmbed::SMALL16_QKV ||
+                           r.embed == DecEmbed::ANY_QKV;
+    const int l0 = r.seq ? nl - 1 : 0; // (the sequence-resident launch ran the layers before the last)
+    for (int l = l0; l < nl; ++l) {
         const irs_layer_w &w = ctx->layer[l];
-        const bool last_rows = rows_only && (l + 1 == ctx->dims.n_layers);
-        // qkv = x W_in^T + b_in (already produced by the previous layer's fused feed-forward kernel where that ran)
-        if (!qkv_done &&
-            (rc = launch_linear(ctx, x, w.sa_in_w, w.sa_in_b, nullptr, ctx->act_qkv, rows, 3 * d, d, false, s, nullptr, nullptr,
-                                nullptr, nullptr, nullptr, nullptr, nullptr, m_dev, frag ? xf : nullptr)))
+        // qkv = x W_in^T + b_in, unless the embed kernel or the previous layer's kernel produced it
+        if (!(l == l0 ? embed_qkv : fam_writes_qkv(r.layer)) &&
+            (rc = launch_linear(ctx, c.x, w.sa_in_w, w.sa_in_b, nullptr, ctx->act_qkv, c.rows, 3 * d, d, false, s, nullptr, nullptr,
+                                nullptr, nullptr, nullptr, nullptr, nullptr, c.m_dev, r.frag ? ctx->act_xf : nullptr)))
             return rc;
-        qkv_done = false;
-        const float *cl = ctx->c_l + (size_t)l * d;
-        if (last_rows) {
-            float *ao_r = ctx->act_ao;                 // [B, d] attention output rows
-            float *x_r = ctx->act_ao + (size_t)B * d;  // [B, d] residual rows x[b, pos[b]]
-            float *y_r = ctx->act_ao + (size_t)2 * B * d;
-            float *h_r = ctx->act_h;                   // [B, F]
-            const float *q_r = nullptr;
-            if (seq_mode) {
-                // the sequence-resident launch ran this layer's q | k | v and the attention of every consumed token's block: the
-                // residual row and the attention row come out of the fragment-major images by the tile-order row index
-                hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, xf, qrow_f, x_r, d, 4);
-                hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, yf, qrow_f, ao_r, d, 4);
-            } else if (q_split) { // the previous layer's kernel wrote k | v only: queries for the B consumed rows here
-                hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, xf, qrow_f, x_r, d, d > 128 ? d / 32 : 4);
-                if ((rc = launch_linear(ctx, x_r, w.sa_in_w, w.sa_in_b, nullptr, h_r, B, d, d, false, s))) return rc;
-                q_r = h_r;
-            }
-            irs_prof_begin(ctx, IRS_PROF_ATTN, s);
-            if (seq_mode) {
-            } else if (d / ctx->dims.n_heads == 32 && L <= 256 && d % 4 == 0 && (((uintptr_t)ctx->act_qkv | (uintptr_t)q_r) & 15) == 0)
-                hipLaunchKernelGGL(k_attn_row32, dim3(ctx->dims.n_heads, B), dim3(256), 0, s, ctx->act_qkv, seq, ctx->act_ru,
-                                   ao_r, L, d, ctx->dims.mask_mode, off, cnt, qrow, q_r, ctx->seq_padq);
-            else
-                hipLaunchKernelGGL(k_attn_row, dim3(ctx->dims.n_heads, B), dim3(64), 0, s, ctx->act_qkv, seq, ctx->act_ru, pos,
-                                   ao_r, L, d, d / ctx->dims.n_heads, ctx->dims.mask_mode, off, cnt, tok, qrow, q_r);
-            irs_prof_end(ctx, IRS_PROF_ATTN, s, 4.0 * B * (double)L * d, 4.0 * 3.0 * B * (double)L * d);
-            const bool fused_tail = d == 128 && F == 256;
-            const bool any_tail = small_any_shape(d, F) && ctx->w_frag16 && !frag && B <= 2048;
-            const bool wide_tail = small_wide_shape(d, F) && ctx->w_frag16 && !frag && !q_split;
-            const bool idx_res = (fused_tail || any_tail || wide_tail) && !frag; // the layer kernel reads the residual rows x[qrow[b]] itself
-            if (frag && !q_split) hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, xf, qrow, x_r, d, d > 128 ? d / 32 : 4);
-            else if (!frag && !idx_res) hipLaunchKernelGGL(k_gather_rows_idx, dim3(B), dim3(64), 0, s, x, qrow, x_r, d);
-            if (fused_tail) { // one launch for the rest of the layer on the B consumed rows
-                SmallBlockArgs sb{ao_r, idx_res ? x : x_r, w.sa_out_w, w.sa_out_b, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b, w.l1_w, w.l1_b, w.l2_w, w.l2_b,
-                                  w.n3_w, w.n3_b, xrows, nullptr, nullptr, nullptr, B, nullptr, idx_res ? qrow : nullptr,
-                                  ctx->w_frag16 + (size_t)l * SMALL_WF_LAYER, nullptr};
-                irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
-                if (B > 2048) hipLaunchKernelGGL((k_block_small16<false, 2>), dim3((B + 31) / 32), dim3(64 * SB_NW), 0, s, sb);
-                else hipLaunchKernelGGL((k_block_small16<false, 1>), dim3((B + 15) / 16), dim3(64 * SB_NW), 0, s, sb);
-                irs_prof_end(ctx, IRS_PROF_LINEAR, s, 2.0 * B * ((double)d * d + 2.0 * d * F), 4.0 * 3.0 * B * (double)d);
-            } else if (wide_tail) { // the same for d = 256
-                SmallBlockArgs sb{ao_r, x, w.sa_out_w, w.sa_out_b, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b, w.l1_w, w.l1_b, w.l2_w, w.l2_b,
-                                  w.n3_w, w.n3_b, xrows, nullptr, nullptr, nullptr, B, nullptr, qrow,
-                                  ctx->w_frag16 + (size_t)l * wide_lf, nullptr};
-                irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
-                hipLaunchKernelGGL((k_block_small_wide<256, false>), dim3((B + 15) / 16), dim3(512), 0, s, sb);
-                irs_prof_end(ctx, IRS_PROF_LINEAR, s, 2.0 * B * ((double)d * d + 2.0 * d * F), 4.0 * 3.0 * B * (double)d);
-            } else if (any_tail) {
-                SmallBlockArgs sb{ao_r, x, w.sa_out_w, w.sa_out_b, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b, w.l1_w, w.l1_b, w.l2_w, w.l2_b,
-                                  w.n3_w, w.n3_b, xrows, nullptr, nullptr, nullptr, B, nullptr, qrow,
-                                  ctx->w_frag16 + (size_t)l * small_any_layer_floats(d, F), nullptr};
-                irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
-                launch_small_any(false, B, d, F, sb, s);
-                irs_prof_end(ctx, IRS_PROF_LINEAR, s, 2.0 * B * ((double)d * d + 2.0 * d * F), 4.0 * 3.0 * B * (double)d);
-            } else if (d <= LIN_BN) {
-                if ((rc = launch_linear(ctx, ao_r, w.sa_out_w, w.sa_out_b, x_r, y_r, B, d, d, false, s, w.n1_w, w.n1_b, cl, w.n2_w,
-                                        w.n2_b)))
-                    return rc;
-                if ((rc = launch_linear(ctx, y_r, w.l1_w, w.l1_b, nullptr, h_r, B, F, d, true, s))) return rc;
-                if ((rc = launch_linear(ctx, h_r, w.l2_w, w.l2_b, y_r, xrows, B, d, F, false, s, w.n3_w, w.n3_b))) return rc;
-            } else { // wider than the LN-fused GEMMs: residual GEMM, then LayerNorm, on the B rows
-                float *z_r = ctx->act_ao + (size_t)3 * B * d;
-                if ((rc = launch_linear(ctx, ao_r, w.sa_out_w, w.sa_out_b, x_r, z_r, B, d, d, false, s))) return rc;
-                hipLaunchKernelGGL(k_ln, dim3((B + 3) / 4), dim3(256), 0, s, z_r, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b, y_r, B, d,
-                                   (const int32_t *)nullptr);
-                if ((rc = launch_linear(ctx, y_r, w.l1_w, w.l1_b, nullptr, h_r, B, F, d, true, s))) return rc;
-                if ((rc = launch_linear(ctx, h_r, w.l2_w, w.l2_b, y_r, z_r, B, d, F, false, s))) return rc;
-                hipLaunchKernelGGL(k_ln, dim3((B + 3) / 4), dim3(256), 0, s, z_r, w.n3_w, w.n3_b, (const float *)nullptr,
-                                   (const float *)nullptr, (const float *)nullptr, xrows, B, d, (const int32_t *)nullptr);
-            }
-            IRS_CHECK_HIP(ctx, hipGetLastError());
-            return IRS_OK;
-        }
-        // d = 128, F = 256, head dim 32: attention writes its output fragment-major and ONE kernel does the rest of
-        // the layer (out-projection + LN1/LN2, feed-forward + LN3, the next layer's QKV) with y, h, x' in registers
-        const bool fuse_block = fuse_block_cfg;
-        if (!att_fused &&
-            (rc = launch_attn(ctx, ctx->act_qkv, seq, ctx->act_ru, fuse_block ? yf : ctx->act_ao, B, s, off, cnt, tok, fuse_block,
-                              kv_planes)))
-            return rc;
-        if (frag) {
-            const bool last = l + 1 == ctx->dims.n_layers;
-            const bool tail = !last && (d == 128 || x6d) && F == 256;
-            BlockArgs ba{};
-            ba.W1 = w.l1_w, ba.b1 = w.l1_b, ba.W2 = w.l2_w, ba.b2 = w.l2_b, ba.g = w.n3_w, ba.b = w.n3_b;
-            ba.Xf = last ? nullptr : xf, ba.Y = last ? x : nullptr, ba.M = rows, ba.m_dev = m_dev;
-            ba.Win = tail ? ctx->layer[l + 1].sa_in_w : nullptr, ba.bin = tail ? ctx->layer[l + 1].sa_in_b : nullptr;
-            ba.QKV = ctx->act_qkv;
-            // feeding the rows-only last layer: its queries are needed for B rows only -> write k | v, 8 of 12 tiles
-            const bool kv_only = tail && rows_only && l + 2 == ctx->dims.n_layers;
-            ba.qkv_n0 = kv_only ? 128 : 0, ba.qkv_nt1 = kv_only ? 2 : 6;
-            q_split = kv_only;
-            const double ffn_flops = 4.0 * rows * (double)d * F + (tail ? (kv_only ? 4.0 : 6.0) * rows * (double)d * d : 0.0);
-            if (fuse_block) {
-                ba.Af = yf, ba.Rf = xf, ba.Wo = w.sa_out_w, ba.bo = w.sa_out_b;
-                ba.g1 = w.n1_w, ba.b1n = w.n1_b, ba.c = cl, ba.g2 = w.n2_w, ba.b2n = w.n2_b;
-                irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
-                if (tail) irs_prof_begin(ctx, IRS_PROF_LAYER, s); // (one family is enabled at a time)
-                if (tail && ctx->use_x6 && ctx->w_x6) { // the same layer tail on split-bf16 MFMAs
-                    const int npl = (ctx->use_x6 == IRS_GEMM_H3 && ctx->h3_ok) ? 2 : 3;
-                    BlockX6Args xa{yf, xf, x6_stream(ctx, npl, l), w.sa_out_b, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b,
-                                   w.l1_b, w.l2_b, w.n3_w, w.n3_b, ctx->layer[l + 1].sa_in_b, xf, ctx->act_qkv, rows, m_dev, kv_only ? 1 : 0};
-                    xa.kv_planes = kv_planes ? 1 : 0;
-                    x6_launch(kv_only ? 1 : 0, false, x6d ? 8 : 4, npl, rows, xa, s);
-                } else if (x6d) IRS_FAIL(ctx, IRS_E_STATE, "d = 256 fused layer kernel without a successor layer");
-                else if (tail) hipLaunchKernelGGL((k_block<true, true>), dim3((rows + 127) / 128), dim3(256), 0, s, ba);
-                else hipLaunchKernelGGL((k_block<true, false>), dim3((rows + 127) / 128), dim3(256), 0, s, ba);
-                irs_prof_end(ctx, IRS_PROF_LINEAR, s, ffn_flops + 2.0 * rows * (double)d * d, (8.0 + 4.0 + (tail ? 12.0 : 0.0)) * rows * (double)d);
-                if (tail) irs_prof_end(ctx, IRS_PROF_LAYER, s, ffn_flops + 2.0 * rows * (double)d * d, (8.0 + 4.0 + 12.0) * rows * (double)d);
-                qkv_done = tail;
-                IRS_CHECK_HIP(ctx, hipGetLastError());
-                continue;
-            }
-            // y <- LN2(LN1(x + ao W_o^T + b_o) + c_l): residual from xf, result to yf only
-            if ((rc = launch_linear(ctx, ctx->act_ao, w.sa_out_w, w.sa_out_b, nullptr, nullptr, rows, d, d, false, s, w.n1_w,
-                                    w.n1_b, cl, w.n2_w, w.n2_b, xf, yf, m_dev)))
-                return rc;
-            // x <- LN3(y + relu(y W1^T + b1) W2^T + b2) back into xf (the last layer of a full decode writes the
-            // row-major x the caller receives instead); d = 128, F = 256 runs as one kernel with h in registers
-            if (d == 128 && F == 256) {
-                ba.Yf = yf;
-                irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
-                if (tail) hipLaunchKernelGGL((k_block<false, true>), dim3((rows + 127) / 128), dim3(256), 0, s, ba);
-                else hipLaunchKernelGGL((k_block<false, false>), dim3((rows + 127) / 128), dim3(256), 0, s, ba);
-                irs_prof_end(ctx, IRS_PROF_LINEAR, s, ffn_flops, (8.0 + (tail ? 12.0 : 0.0)) * rows * (double)d);
-                qkv_done = tail;
-            } else {
-                if ((rc = launch_linear(ctx, nullptr, w.l1_w, w.l1_b, nullptr, ctx->act_h, rows, F, d, true, s, nullptr, nullptr,
-                                        nullptr, nullptr, nullptr, nullptr, nullptr, m_dev, yf)))
-                    return rc;
-                if ((rc = launch_linear(ctx, ctx->act_h, w.l2_w, w.l2_b, nullptr, last ? x : nullptr, rows, d, F, false, s, w.n3_w,
-                                        w.n3_b, nullptr, nullptr, nullptr, yf, last ? nullptr : xf, m_dev)))
-                    return rc;
-            }
-        } else if (small_cfg) {
-            // latency path: the rest of the layer (and the next layer's QKV) in one launch per 16 (or 32) tokens; x -> y buffer
-            const bool last = l + 1 == ctx->dims.n_layers;
-            SmallBlockArgs sb{ctx->act_ao, x, w.sa_out_w, w.sa_out_b, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b, w.l1_w, w.l1_b, w.l2_w, w.l2_b,
-                              w.n3_w, w.n3_b, y, last ? nullptr : ctx->layer[l + 1].sa_in_w, last ? nullptr : ctx->layer[l + 1].sa_in_b,
-                              qkv_in(l + 1), rows, m_dev, nullptr, ctx->w_frag16 ? ctx->w_frag16 + (size_t)l * SMALL_WF_LAYER : nullptr,
-                              (last || !ctx->w_frag16) ? nullptr
-                                                       : ctx->w_frag16 + (size_t)ctx->dims.n_layers * SMALL_WF_LAYER + (size_t)(l + 1) * SMALL_WF_WIN};
-            if (att_fused) {
-                sb.QKVin = qkv_in(l), sb.r_u = ctx->act_ru, sb.seq_last = seq + (L - 1), sb.cnt = cnt, sb.padq = ctx->seq_padq;
-                sb.mask_mode = ctx->dims.mask_mode;
-            }
-            irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
-            // 32 tokens per workgroup once the 16-token tiles outnumber the resident workgroups (2 per CU): per path
-            // step 518 vs 563 us at 128 users, but 267 vs 222 at 16 users; 64 tokens measured no better than 32
-            if (rows > SMALL_MT2_ROWS) {
-                if (sb.Win) hipLaunchKernelGGL((k_block_small16<true, 2>), dim3((rows + 31) / 32), dim3(64 * SB_NW), 0, s, sb);
-                else hipLaunchKernelGGL((k_block_small16<false, 2>), dim3((rows + 31) / 32), dim3(64 * SB_NW), 0, s, sb);
-            } else if (att_fused) {
-                if (sb.Win) hipLaunchKernelGGL((k_block_small16<true, 1, true>), dim3((rows + 15) / 16), dim3(64 * SB_NW), 0, s, sb);
-                else hipLaunchKernelGGL((k_block_small16<false, 1, true>), dim3((rows + 15) / 16), dim3(64 * SB_NW), 0, s, sb);
-            } else {
-                if (sb.Win) hipLaunchKernelGGL((k_block_small16<true, 1>), dim3((rows + 15) / 16), dim3(64 * SB_NW), 0, s, sb);
-                else hipLaunchKernelGGL((k_block_small16<false, 1>), dim3((rows + 15) / 16), dim3(64 * SB_NW), 0, s, sb);
-            }
-            irs_prof_end(ctx, IRS_PROF_LINEAR, s, 2.0 * rows * ((double)d * d + 2.0 * d * F + (last ? 0.0 : 3.0 * d * d)),
-                         4.0 * (3.0 + (last ? 0.0 : 3.0)) * rows * (double)d);
-            qkv_done = !last;
-            float *tswap = x; // the new x lives in the other buffer
-            x = y;
-            y = tswap;
-        } else if (wide_cfg) {
-            // d = 256, small batches: the rest of the layer (and the next layer's QKV) in one launch per 16 tokens; x -> y buffer
-            const bool last = l + 1 == ctx->dims.n_layers;
-            SmallBlockArgs sb{ctx->act_ao, x, w.sa_out_w, w.sa_out_b, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b, w.l1_w, w.l1_b, w.l2_w, w.l2_b,
-                              w.n3_w, w.n3_b, y, last ? nullptr : ctx->layer[l + 1].sa_in_w, last ? nullptr : ctx->layer[l + 1].sa_in_b,
-                              ctx->act_qkv, rows, m_dev, nullptr, ctx->w_frag16 + (size_t)l * wide_lf,
-                              last ? nullptr : ctx->w_frag16 + (size_t)ctx->dims.n_layers * wide_lf + (size_t)(l + 1) * 3 * d * d};
-            irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
-            if (last) hipLaunchKernelGGL((k_block_small_wide<256, false>), dim3((rows + 15) / 16), dim3(512), 0, s, sb);
-            else hipLaunchKernelGGL((k_block_small_wide<256, true>), dim3((rows + 15) / 16), dim3(512), 0, s, sb);
-            irs_prof_end(ctx, IRS_PROF_LINEAR, s, 2.0 * rows * ((double)d * d + 2.0 * d * F + (last ? 0.0 : 3.0 * d * d)),
-                         4.0 * (3.0 + (last ? 0.0 : 3.0)) * rows * (double)d);
-            qkv_done = !last;
-            float *tswap = x; // the new x lives in the other buffer
-            x = y;
-            y = tswap;
-        } else if (any_cfg) {
-            // launch-bound small shapes: the rest of the layer (and the next layer's QKV) in one launch per 16 tokens
-            const bool last = l + 1 == ctx->dims.n_layers;
-            SmallBlockArgs sb{ctx->act_ao, x, w.sa_out_w, w.sa_out_b, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b, w.l1_w, w.l1_b, w.l2_w, w.l2_b,
-                              w.n3_w, w.n3_b, y, last ? nullptr : ctx->layer[l + 1].sa_in_w, last ? nullptr : ctx->layer[l + 1].sa_in_b,
-                              ctx->act_qkv, rows, m_dev, nullptr, ctx->w_frag16 + (size_t)l * small_any_layer_floats(d, F),
-                              last ? nullptr : ctx->w_frag16 + (size_t)(l + 1) * small_any_layer_floats(d, F) + small_any_win_off(d, F)};
-            irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
-            launch_small_any(!last, rows, d, F, sb, s);
-            irs_prof_end(ctx, IRS_PROF_LINEAR, s, 2.0 * rows * ((double)d * d + 2.0 * d * F + (last ? 0.0 : 3.0 * d * d)),
-                         4.0 * (3.0 + (last ? 0.0 : 3.0)) * rows * (double)d);
-            qkv_done = !last;
-            float *tswap = x; // the new x lives in the other buffer
-            x = y;
-            y = tswap;
-        } else if (d <= LIN_BN || (d <= 2 * LIN_BN && rows >= 32768)) {
-            // (rows of 129..256 values: one workgroup per 128 tokens covers ALL columns, so below ~256 workgroups the
-            //  unfused form -- one workgroup per 128 x 128 output block, then a LayerNorm pass -- fills the chip better:
-            //  C5's 32 windows = 6400 rows ran 4 % slower fused)
-            // x <- LN2(LN1(x + ao W_o^T + b_o) + c_l), fused into the GEMM epilogue (y, not in place)
-            if ((rc = launch_linear(ctx, ctx->act_ao, w.sa_out_w, w.sa_out_b, x, y, rows, d, d, false, s, w.n1_w, w.n1_b,
-                                    cl, w.n2_w, w.n2_b, nullptr, nullptr, m_dev)))
-                return rc;
-            // h = relu(y W1^T + b1); x <- LN3(y + h W2^T + b2)
-            if ((rc = launch_linear(ctx, y, w.l1_w, w.l1_b, nullptr, ctx->act_h, rows, F, d, true, s, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, nullptr, nullptr, m_dev)))
-                return rc;
-            if ((rc = launch_linear(ctx, ctx->act_h, w.l2_w, w.l2_b, y, x, rows, d, F, false, s, w.n3_w, w.n3_b, nullptr,
-                                    nullptr, nullptr, nullptr, nullptr, m_dev)))
-                return rc;
-        } else {
-            // y = x + ao W_o^T + b_o ; x = LN2(LN1(y) + c_l)          (packed rows: every kernel clamps to m_dev)
-            if ((rc = launch_linear(ctx, ctx->act_ao, w.sa_out_w, w.sa_out_b, x, y, rows, d, d, false, s, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, nullptr, nullptr, m_dev)))
-                return rc;
-            hipLaunchKernelGGL(k_ln, dim3((rows + 3) / 4), dim3(256), 0, s, y, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b, x,
-                               rows, d, m_dev);
-            // h = relu(x W1^T + b1); y = x + h W2^T + b2; x = LN3(y)
-            if ((rc = launch_linear(ctx, x, w.l1_w, w.l1_b, nullptr, ctx->act_h, rows, F, d, true, s, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, nullptr, nullptr, m_dev)))
-                return rc;
-            if ((rc = launch_linear(ctx, ctx->act_h, w.l2_w, w.l2_b, x, y, rows, d, F, false, s, nullptr, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, nullptr, m_dev)))
-                return rc;
-            hipLaunchKernelGGL(k_ln, dim3((rows + 3) / 4), dim3(256), 0, s, y, w.n3_w, w.n3_b, (const float *)nullptr,
-                               (const float *)nullptr, (const float *)nullptr, x, rows, d, m_dev);
-        }
+        if (r.rows_only && l + 1 == nl) return last_layer(c, l, pos, xrows);
+        if ((rc = decode_layer(c, l))) return rc;
         IRS_CHECK_HIP(ctx, hipGetLastError());
     }
-    if (x_out) IRS_CHECK_HIP(ctx, hipMemcpyAsync(x_out, x, sizeof(float) * (size_t)rows * d, hipMemcpyDeviceToDevice, s));
+    if (x_out) IRS_CHECK_HIP(ctx, hipMemcpyAsync(x_out, c.x, sizeof(float) * (size_t)c.rows * d, hipMemcpyDeviceToDevice, s));
     if (pos && xrows) {
-        hipLaunchKernelGGL(k_gather_rows, dim3(B), dim3(64), 0, s, x, pos, xrows, B, L, d);
+        hipLaunchKernelGGL(k_gather_rows, dim3(B), dim3(64), 0, s, c.x, pos, xrows, B, L, d);
         IRS_CHECK_HIP(ctx, hipGetLastError());
     }
     return IRS_OK;

@@ -88,7 +88,7 @@ struct irs_ctx {
     int use_x6;       // decoder GEMMs of the throughput path on split-bf16 MFMAs (IRS_DECODER_GEMM=x6|f32)
     bool h3_ok;       // finalisation's float16 range bound holds (else IRS_GEMM_H3 runs as IRS_GEMM_X6 and V stays float32)
     float h3_bound;   // the largest operand magnitude the bound weights allow (irs_h3_operand_bound)
-    int use_seq;      // sequence-resident decoder for the d = 128 throughput shape: 0 off, 1 on, 2 auto (default: from 1024 sequences up)
+    int use_seq;      // sequence-resident decoder for the d = 128 throughput shape: 0 off, 1 on, 2 auto (default: from 384 sequences up)
     bool seq_last;    // the last irs_decode took it
     int use_attn_h3;  // throughput attention on split-float16 MFMAs over K / V planes written by the layer kernel (default on; IRS_ATTN_GEMM=f32 off)
     int lse_no_ring;  // IRS_LSE_RING=0: the register-fragment log-sum-exp kernel at <= 32 rows too (A/B measurements, tests)
@@ -192,6 +192,15 @@ struct irs_ctx {
 // profiling bracket helpers (no-ops unless the family is enabled)
 void irs_prof_begin(irs_ctx *ctx, int family, hipStream_t s);
 void irs_prof_end(irs_ctx *ctx, int family, hipStream_t s, double flops, double bytes);
+
+// ---- decode shapes: the workspace (capi.hip) and the decoder's route choice (decoder.hip: decode_route) must agree on them
+// the sequence-resident layer kernel's shape (k_block_x6<.., SEQ>): its plan tables exist in the workspace only for it
+static inline bool irs_seq_shape(const irs_dims &D) {
+    return D.d == 128 && D.ffn_dim == 256 && D.n_heads == 4 && D.max_len <= 256 && D.n_layers > 1;
+}
+// a rows-only decode of B sequences is planned by ONE workgroup (k_plan_small), which also computes r_u and, around a decode of
+// the merged path loop (ctx->step_pair), hands the step counter over
+static inline bool irs_small_plan(const irs_dims &D, int B) { return B <= 64 && D.max_len >= 4; }
 
 // ---- decoder.hip ----
 int irs_launch_pif(irs_ctx *ctx, const int64_t *user, int B, float *r_u, hipStream_t s);

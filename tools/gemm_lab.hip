@@ -23,6 +23,18 @@ static float time_it(std::function<void()> f, int reps) {
     return ms / reps;
 }
 
+// the BK = 32 instantiations of the throughput GEMMs (the library runs BK = 16 only), launched the way launch_linear launches
+// its BK = 16 ones for aligned operands, K % 32 == 0 and M above the latency path's range
+static void launch_bk32(LinArgs a, int n_cu) {
+    if (a.g1) {
+        hipLaunchKernelGGL((k_linear_ln<32, true, false>), dim3((a.M + LIN_BM - 1) / LIN_BM), dim3(256), 0, 0, a);
+        return;
+    }
+    a.slots = n_cu * 2; // k_linear<.., 32, ..>'s launch bounds
+    const int ntm = (a.M + LIN_BM - 1) / LIN_BM, ntn = (a.N + LIN_BN - 1) / LIN_BN;
+    hipLaunchKernelGGL((k_linear<true, 32, false>), dim3((ntm / a.slots) * a.slots + (ntm % a.slots) * ntn), dim3(256), 0, 0, a);
+}
+
 // fp32 MFMA issue-rate probe: no memory traffic, NACC independent accumulator tiles per wave.
 template <int NACC>
 __global__ void __launch_bounds__(256) k_mfma_peak(float *out, int iters) {
@@ -41,6 +53,8 @@ __global__ void __launch_bounds__(256) k_mfma_peak(float *out, int iters) {
 
 int main(int argc, char **argv) {
     int M = argc > 1 ? atoi(argv[1]) : 204800;
+    int n_cu = 256;
+    CK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, 0));
     {
         float *o; CK(hipMalloc(&o, 4));
         const int iters = 4096;
@@ -68,8 +82,8 @@ int main(int argc, char **argv) {
         LinArgs af = a; af.Rf = R; af.Yf = Y2;
         double gf = 2.0 * M * sh.N * sh.K / 1e9;
         for (int bk : {32, 16}) {
-            g_lin_bk = bk; g_ln_bk = bk;
-            float ms = time_it([&] { launch_linear(nullptr, a.X, a.W, a.bias, a.R, a.Y, M, sh.N, sh.K, sh.relu, 0, a.g1, a.b1, a.c, a.g2, a.b2, nullptr, nullptr); }, 20);
+            float ms = bk == 32 ? time_it([&] { launch_bk32(a, n_cu); }, 20)
+                                : time_it([&] { launch_linear(nullptr, a.X, a.W, a.bias, a.R, a.Y, M, sh.N, sh.K, sh.relu, 0, a.g1, a.b1, a.c, a.g2, a.b2, nullptr, nullptr); }, 20);
             printf("%s BK=%2d : %8.1f us  %6.1f TF\n", sh.name, bk, ms * 1e3, gf / ms);
         }
     }
