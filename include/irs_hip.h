@@ -423,6 +423,13 @@ int irs_get_decoder_gemm_effective(const irs_ctx *ctx); /* the mode that runs (I
 int irs_set_decoder_seq(irs_ctx *ctx, int32_t mode);
 int irs_get_decoder_seq(const irs_ctx *ctx);
 int irs_decoder_seq_last(const irs_ctx *ctx);
+/* irs_decoder_route_last (tests): the kernel route the last irs_decode took, as int32 fields in this order:
+ *   rows_only, small_plan, plan, embed, layer, tail, frag, seq, kv_planes, att_fused, kv_only, x6, npl, nt
+ * plan: 0 NONE (full decode), 1 MULTI, 2 SMALL, 3 IN_EMBED; embed: 0 FULL, 1 PACKED, 2 FRAG, 3 FRAG_QKV, 4 SMALL16_QKV, 5 ANY_QKV,
+ * 6 SEQ; layer / tail: 0 GEMM, 1 GEMM_LN, 2 FRAG_GEMM, 3 FRAG_BLOCK, 4 FRAG_FUSED, 5 SMALL16, 6 WIDE, 7 ANY; the flags 0 / 1.
+ * Writes min(n, IRS_ROUTE_FIELDS) fields to out and returns that number; IRS_E_STATE before any decode.  Launches nothing. */
+#define IRS_ROUTE_FIELDS 14
+int irs_decoder_route_last(const irs_ctx *ctx, int32_t *out, int32_t n);
 /* (tests / lab) device address of a decoder workspace buffer: 0 x (fragment-major), 1 attention output (fragment-major), 2 / 3 the
  * sequence-resident plan's tile -> sequence / tile index, 4 image row of a sequence, 5 tile-order consumed row, 6 workgroup count,
  * 7 / 8 packed offset / count per sequence, 9 q | k | v rows, 10 packed consumed row.  Null for an unknown index. */

@@ -17,6 +17,14 @@ IRS_MASK_IRN, IRS_MASK_CAUSAL = 0, 1
 IRS_SWEEP_BF16, IRS_SWEEP_F32, IRS_SWEEP_EXHAUSTIVE = 0, 1, 2
 IRS_ROW_FALLBACK, IRS_ROW_NO_CANDIDATE, IRS_ROW_FEWER_THAN_K = 1, 2, 4
 IRS_GEMM_F32, IRS_GEMM_X6, IRS_GEMM_H3 = 0, 1, 2
+# irs_decoder_route_last (include/irs_hip.h): its field order and the names of the enum-valued fields, in the order of
+# decoder.hip's enum class DecPlan / DecEmbed / DecFam (tests/test_decoder_routes.py checks that they agree)
+ROUTE_FIELDS = ("rows_only", "small_plan", "plan", "embed", "layer", "tail", "frag", "seq", "kv_planes", "att_fused", "kv_only",
+                "x6", "npl", "nt")
+ROUTE_PLANS = ("NONE", "MULTI", "SMALL", "IN_EMBED")
+ROUTE_EMBEDS = ("FULL", "PACKED", "FRAG", "FRAG_QKV", "SMALL16_QKV", "ANY_QKV", "SEQ")
+ROUTE_FAMILIES = ("GEMM", "GEMM_LN", "FRAG_GEMM", "FRAG_BLOCK", "FRAG_FUSED", "SMALL16", "WIDE", "ANY")
+ROUTE_NAMES = {"plan": ROUTE_PLANS, "embed": ROUTE_EMBEDS, "layer": ROUTE_FAMILIES, "tail": ROUTE_FAMILIES}
 IRS_PROF_NONE, IRS_PROF_LINEAR, IRS_PROF_ATTN, IRS_PROF_SWEEP, IRS_PROF_REFINE, IRS_PROF_SWEEP_EMIT, IRS_PROF_LAYER = 0, 1, 2, 3, 4, 5, 6
 
 
@@ -90,6 +98,7 @@ SIGNATURES = {
     "irs_set_decoder_seq": (c_int32, [c_void_p, c_int32]),
     "irs_get_decoder_seq": (c_int32, [c_void_p]),
     "irs_decoder_seq_last": (c_int32, [c_void_p]),
+    "irs_decoder_route_last": (c_int32, [c_void_p, POINTER(c_int32), c_int32]),
     "irs_debug_ptr": (c_void_p, [c_void_p, c_int32]),
     "irs_h3_range_bound": (c_float, [c_void_p]),
     "irs_prof_enable": (c_int32, [c_void_p, c_int32]),

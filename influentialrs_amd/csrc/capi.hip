@@ -474,6 +474,13 @@ extern "C" int irs_set_decoder_seq(irs_ctx *ctx, int32_t mode) {
 }
 extern "C" int irs_get_decoder_seq(const irs_ctx *ctx) { return ctx ? ctx->use_seq : IRS_E_INVALID; }
 extern "C" int irs_decoder_seq_last(const irs_ctx *ctx) { return ctx ? (ctx->seq_last ? 1 : 0) : IRS_E_INVALID; }
+extern "C" int irs_decoder_route_last(const irs_ctx *ctx, int32_t *out, int32_t n) {
+    if (!ctx || !out || n < 0) return IRS_E_INVALID;
+    if (ctx->route_n == 0) return IRS_E_STATE;
+    const int m = n < ctx->route_n ? n : ctx->route_n;
+    for (int i = 0; i < m; ++i) out[i] = ctx->route_last[i];
+    return m;
+}
 // (lab / tests: device addresses of decoder workspace buffers, so that a test can look at what a decode left behind)
 extern "C" void *irs_debug_ptr(const irs_ctx *ctx, int32_t which) {
     if (!ctx) return nullptr;

@@ -6384,6 +6384,11 @@ int irs_launch_decode(irs_ctx *ctx, const int64_t *seq, const int64_t *user, int
     if (ctx->step_pair && !r.small_plan) IRS_FAIL(ctx, IRS_E_STATE, "merged path step needs the single-workgroup plan kernel");
     if (!r.small_plan && (rc = irs_launch_pif(ctx, user, B, ctx->act_ru, s)) != IRS_OK) return rc;
     ctx->seq_last = r.seq;
+    // (the field order of irs_decoder_route_last, include/irs_hip.h)
+    const int32_t packed[IRS_ROUTE_FIELDS] = {r.rows_only, r.small_plan, (int32_t)r.plan, (int32_t)r.embed, (int32_t)r.layer,
+                                              (int32_t)r.tail, r.frag, r.seq, r.kv_planes, r.att_fused, r.kv_only, r.x6, r.npl, r.nt};
+    for (int i = 0; i < IRS_ROUTE_FIELDS; ++i) ctx->route_last[i] = packed[i];
+    ctx->route_n = IRS_ROUTE_FIELDS;
     DecodeCall c{ctx, r, seq, B, B * L, ctx->act_x, ctx->act_y, s};
     if (r.rows_only) c.off = ctx->seq_off, c.cnt = ctx->seq_cnt, c.tok = ctx->tok_row, c.qrow = ctx->seq_qrow, c.m_dev = ctx->m_dev;
     if (r.plan == DecPlan::SMALL) {

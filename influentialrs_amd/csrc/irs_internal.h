@@ -90,6 +90,8 @@ struct irs_ctx {
     float h3_bound;   // the largest operand magnitude the bound weights allow (irs_h3_operand_bound)
     int use_seq;      // sequence-resident decoder for the d = 128 throughput shape: 0 off, 1 on, 2 auto (default: from 384 sequences up)
     bool seq_last;    // the last irs_decode took it
+    int32_t route_last[IRS_ROUTE_FIELDS]; // the last irs_launch_decode's DecodeRoute, packed (irs_decoder_route_last)
+    int route_n;      // fields in route_last: 0 before the first decode
     int use_attn_h3;  // throughput attention on split-float16 MFMAs over K / V planes written by the layer kernel (default on; IRS_ATTN_GEMM=f32 off)
     int lse_no_ring;  // IRS_LSE_RING=0: the register-fragment log-sum-exp kernel at <= 32 rows too (A/B measurements, tests)
     bool finalized;

@@ -487,6 +487,22 @@ class Engine:
         return bool(self.lib.irs_decoder_seq_last(self.h))
 
     @property
+    def decoder_route_last(self) -> Dict[str, object]:
+        """(tests) The kernel route the last decode took (irs_decoder_route_last): plan / embed / layer / tail as their enum
+        names (_lib.ROUTE_NAMES), the flags as bools, npl / nt as ints."""
+        n = len(_lib.ROUTE_FIELDS)
+        buf = (ctypes.c_int32 * n)()
+        got = self.lib.irs_decoder_route_last(self.h, buf, n)
+        if got < 0:
+            raise IrsError(f"irs_decoder_route_last failed ({got}): no decode has run on this engine yet")
+        if got != n:
+            raise IrsError(f"irs_decoder_route_last wrote {got} fields, expected {n}")
+        out: Dict[str, object] = {}
+        for name, v in zip(_lib.ROUTE_FIELDS, buf):
+            out[name] = _lib.ROUTE_NAMES[name][v] if name in _lib.ROUTE_NAMES else (int(v) if name in ("npl", "nt") else bool(v))
+        return out
+
+    @property
     def sharded_overlap(self) -> bool:
         """irs_set_sharded_overlap: generate_paths_sharded runs two user micro-batches per step with the collectives on a side
         stream (greedy choice; same results).  Off by default."""

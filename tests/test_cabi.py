@@ -56,6 +56,11 @@ def test_create_validates_without_a_device():
         assert lib.irs_bind_weight(h, b"nonsense", fake, 1) == -1
         # nothing runs before weights are finalized and a workspace is bound
         assert lib.irs_score_topk(h, fake, 1, 10, 0, fake, fake, fake, None) == -2
+        # no decode has run: no route to report (and a null context or buffer is an argument error)
+        out = (ctypes.c_int32 * len(_lib.ROUTE_FIELDS))()
+        assert lib.irs_decoder_route_last(h, out, len(out)) == -2
+        assert lib.irs_decoder_route_last(None, out, len(out)) == -1
+        assert lib.irs_decoder_route_last(h, None, len(out)) == -1
     finally:
         lib.irs_destroy(h)
 
