@@ -222,6 +222,45 @@ int irs_ce_forward(irs_ctx *ctx, const float *dev_xrows, const int64_t *dev_labe
 int irs_ce_grad_logits(irs_ctx *ctx, const float *dev_xrows, const int64_t *dev_labels0, const float *dev_lse, int32_t M,
                        float scale, float *dev_out, int64_t ld, void *stream);
 
+/* ---- native decoder trunk for training (opt-in; replaces the train-mode nn.TransformerDecoder autograd of
+ *      InfluentialNet._decoding_autograd, influentialRS.py:157-200 as called by IRSNN.train_batch :278-310, and of
+ *      SampleNet.decoding, uRS.py:52-64, as called by Evaluator.train_batch, evaluator.py:53-92) ------------------
+ * irs_train_forward runs embedding -> n_layers post-norm decoder layers over sequences of length L <= max_len (the
+ * cross-attention memory is the all-zero [max_len, B, d] tensor of the reference) and keeps in `saved` what
+ * irs_train_backward needs; irs_train_backward takes dL/dx and writes every trunk parameter gradient into `grads`.
+ * Both read the LIVE bound float32 weights (an optimizer step in place needs no re-binding or re-finalisation; the
+ * cross-attention constant is recomputed from multihead_attn.in_proj_bias on every call).  Neither needs
+ * irs_finalize_weights or a workspace; they do not touch the inference state.
+ *  dev_seq int64 [B, L] 1-based ids, 0 = pad; dev_user int64 [B] (IRN mask; may be NULL for IRS_MASK_CAUSAL)
+ *  p dropout probability in [0, 1), seed the step's 64-bit dropout key; backward takes the same B, L, p, seed and saved
+ *  dev_saved >= irs_train_saved_bytes(B, L) bytes, 256-byte aligned: written by the forward, read (never modified
+ *            outside its scratch tail) by the backward, so the backward can be repeated with identical results
+ *  dev_x_out float [B, L, d] out; dev_dx float [B, L, d] in
+ *  dev_grads >= irs_train_grad_bytes() bytes, 256-byte aligned, fully overwritten: the gradient of state_dict key
+ *            `name` starts at float offset irs_train_grad_offset(name) (same names as irs_bind_weight; -1 = not a trunk
+ *            parameter).  Row 0 of the embedding gradient (padding_idx) is 0.  multihead_attn.in_proj_weight and
+ *            multihead_attn.in_proj_bias[0 : 2d] get exact zeros: with a zero memory they cannot change any output.
+ * Dropout (train-mode torch sites): masks come from Philox4x32-10 with key {lo32(seed), hi32(seed)}; element e of
+ * (site, layer) is word (e & 3) of the block for counter {lo32(e >> 2), hi32(e >> 2), layer, site} and is kept iff
+ * (word >> 8) >= ceil(p * 2^24); kept values are scaled by 1 / (1 - p).  Sites and flat element indices (m = b L + i):
+ *   0 embedding            m d + c            (layer 0)
+ *   1 self-attention probs ((b H + h) L + i) L + j
+ *   2 dropout1             m d + c
+ *   3 cross-attention probs ((b H + h) L + i) max_len + j
+ *   4 dropout2             m d + c
+ *   5 feed-forward hidden  m ffn_dim + f
+ *   6 dropout3             m d + c
+ * Gradients are reduced in a fixed order: two identical calls give identical bits.  B * L <= IRS_TRAIN_MAX_TOKENS. */
+#define IRS_TRAIN_MAX_TOKENS (1 << 22)
+size_t irs_train_saved_bytes(const irs_ctx *ctx, int32_t B, int32_t L); /* 0 for an invalid shape */
+size_t irs_train_grad_bytes(const irs_ctx *ctx);
+int64_t irs_train_grad_offset(const irs_ctx *ctx, const char *name);
+int irs_train_forward(irs_ctx *ctx, const int64_t *dev_seq, const int64_t *dev_user, int32_t B, int32_t L, float p,
+                      uint64_t seed, void *dev_saved, size_t saved_bytes, float *dev_x_out, void *stream);
+int irs_train_backward(irs_ctx *ctx, const int64_t *dev_seq, const int64_t *dev_user, int32_t B, int32_t L, float p,
+                       uint64_t seed, void *dev_saved, size_t saved_bytes, const float *dev_dx, float *dev_grads,
+                       size_t grad_bytes, void *stream);
+
 /* Merge W per-shard top-k lists (after the RCCL all-gather) into
  * the global top-k with the same total order.
  *  dev_val_in float [W, M, k], dev_ids_in int64 [W, M, k] (ids -1 ignored) */

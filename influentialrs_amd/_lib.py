@@ -63,6 +63,13 @@ SIGNATURES = {
     "irs_ce_grad_logits": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, ctypes.c_float, c_void_p, c_int64, c_void_p]),
     "irs_build_eval_batch": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64,
                                        c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "irs_train_saved_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),
+    "irs_train_grad_bytes": (c_size_t, [c_void_p]),
+    "irs_train_grad_offset": (c_int64, [c_void_p, c_char_p]),
+    "irs_train_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_uint64, c_void_p, c_size_t,
+                                    c_void_p, c_void_p]),
+    "irs_train_backward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_uint64, c_void_p, c_size_t,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]),
     "irs_merge_topk": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "irs_pack_topk": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "irs_merge_topk_keys": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),

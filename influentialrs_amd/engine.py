@@ -67,6 +67,7 @@ class Engine:
             self._ws = torch.empty(self.lib.irs_workspace_bytes(self.h) + 256, dtype=torch.uint8, device=self.device)
             self._check(self.lib.irs_bind_workspace(self.h, _ptr(self._ws), self._ws.numel()))
         self._arena = None
+        self._grad_off: Dict[str, int] = {}  # train_grad_offset cache
 
     # ------------------------------------------------------------------
     def __del__(self):
@@ -245,6 +246,48 @@ class Engine:
         self._call(self.lib.irs_ce_grad_logits, _ptr(xrows), _ptr(labels0), _ptr(lse), M, float(scale), _ptr(out),
                    int(out.stride(0)))
         return out
+
+    # ------------------------------------------------------------------ native training trunk
+    def train_saved_bytes(self, B: int, L: int) -> int:
+        n = self.lib.irs_train_saved_bytes(self.h, B, L)
+        if n == 0:
+            raise IrsError(f"train trunk: no saved state for B={B}, L={L} (need 1 <= L <= max_len={self.L})")
+        return n
+
+    def train_grad_offset(self, name: str) -> int:
+        """Float offset of state_dict key `name` in the gradient arena of train_backward, -1 if it is not a trunk parameter.
+        The layout depends on the context's dims only: each name is asked of the library once per engine."""
+        off = self._grad_off.get(name)
+        if off is None:
+            off = self._grad_off[name] = int(self.lib.irs_train_grad_offset(self.h, name.encode()))
+        return off
+
+    def train_forward(self, seqs: torch.Tensor, users: Optional[torch.Tensor], p: float, seed: int):
+        """Trunk forward of a training step: (x float32 [B, L, d], saved uint8 tensor for train_backward)."""
+        seqs = self._dev(seqs, torch.int64)
+        users = self._dev(users, torch.int64) if users is not None else None
+        B, L = seqs.shape
+        saved = torch.empty(self.train_saved_bytes(B, L), dtype=torch.uint8, device=self.device)
+        x = torch.empty((B, L, self.d), dtype=torch.float32, device=self.device)
+        self._call(self.lib.irs_train_forward, _ptr(seqs), _ptr(users), B, L, float(p), int(seed) & (2 ** 64 - 1), _ptr(saved),
+                   saved.numel(), _ptr(x))
+        return x, saved
+
+    def train_backward(self, seqs: torch.Tensor, users: Optional[torch.Tensor], p: float, seed: int, saved: torch.Tensor,
+                       dx: torch.Tensor) -> torch.Tensor:
+        """Every trunk parameter gradient for dL/dx, as one float32 arena (slice it with train_grad_offset)."""
+        seqs = self._dev(seqs, torch.int64)
+        users = self._dev(users, torch.int64) if users is not None else None
+        dx = self._dev(dx, torch.float32)
+        B, L = seqs.shape
+        if tuple(dx.shape) != (B, L, self.d):
+            raise IrsError(f"train_backward: dx shape {tuple(dx.shape)}, expected {(B, L, self.d)}")
+        saved = self._inplace(saved, torch.uint8, "train_backward saved state")
+        nb = self.lib.irs_train_grad_bytes(self.h)
+        grads = torch.empty(nb // 4, dtype=torch.float32, device=self.device)
+        self._call(self.lib.irs_train_backward, _ptr(seqs), _ptr(users), B, L, float(p), int(seed) & (2 ** 64 - 1),
+                   _ptr(saved), saved.numel(), _ptr(dx), _ptr(grads), nb)
+        return grads
 
     def merge_topk(self, val_in: torch.Tensor, ids_in: torch.Tensor):
         """[W, M, k] gathered per-shard lists -> global (val[M,k], ids0[M,k])."""

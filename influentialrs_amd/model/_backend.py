@@ -4,6 +4,7 @@ row-level operations the task handlers need.  No arithmetic of the hot path is
 done in torch here; torch supplies tensors, streams and collectives."""
 from __future__ import annotations
 
+import os
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -182,6 +183,72 @@ def project_ce(x: torch.Tensor, project: nn.Linear, labels0: torch.Tensor, backe
     # (grad mode is off inside Function.forward: whether this loss can lead to a weight update is decided here)
     may_update = torch.is_grad_enabled() and (x.requires_grad or project.weight.requires_grad or project.bias.requires_grad)
     return _ProjectCE.apply(x, project.weight, project.bias, labels0, backend, may_update)
+
+
+TRUNKS = ("torch", "hip")
+
+
+def train_trunk_default() -> str:
+    """The training trunk a new network selects: IRS_TRAIN_TRUNK = torch (default: stock nn.TransformerDecoder autograd) or
+    hip (the native trunk of include/irs_hip.h irs_train_*).  Any other value raises."""
+    v = os.environ.get("IRS_TRAIN_TRUNK", "torch")
+    return check_trunk(v, "IRS_TRAIN_TRUNK")
+
+
+def check_trunk(v, what: str = "trunk") -> str:
+    if v not in TRUNKS:
+        raise ValueError(f"{what} must be one of {TRUNKS}, got {v!r}")
+    return v
+
+
+class _TrunkHip(torch.autograd.Function):
+    """The train-mode decoder trunk (embedding, dropout, n_layers nn.TransformerDecoderLayer over the zero memory) on the
+    native kernels: forward = irs_train_forward (keeps its saved state), backward = irs_train_backward, whose gradient arena
+    is handed to autograd per parameter so that .grad accumulates as with the stock modules."""
+
+    @staticmethod
+    def forward(ctx, seq, user, p, seed, backend, names, *params):
+        eng = backend.get(1, 1, for_training=True)
+        x, saved = eng.train_forward(seq, user, p, seed)
+        ctx.save_for_backward(seq, user if user is not None else seq, saved)
+        ctx.has_user = user is not None
+        ctx.p, ctx.seed, ctx.backend, ctx.names = p, seed, backend, names
+        ctx.shapes = [prm.shape for prm in params]
+        return x
+
+    @staticmethod
+    def backward(ctx, gx):
+        seq, user, saved = ctx.saved_tensors
+        eng = ctx.backend.get(1, 1, for_training=True)
+        g = eng.train_backward(seq, user if ctx.has_user else None, ctx.p, ctx.seed, saved, gx.contiguous())
+        grads = []
+        for name, shape in zip(ctx.names, ctx.shapes):
+            off = eng.train_grad_offset(name)
+            grads.append(g[off:off + shape.numel()].view(shape))
+        return (None, None, None, None, None, None) + tuple(grads)
+
+
+def _trunk_params(net: nn.Module, emb_name: str):
+    out = [(n, p_) for n, p_ in net.named_parameters() if n == emb_name or n.startswith("decoder.layers.")]
+    return [n for n, _ in out], [p_ for _, p_ in out]
+
+
+def trunk_hip(net: nn.Module, seq: torch.Tensor, user: Optional[torch.Tensor], emb_name: str) -> torch.Tensor:
+    """[B, L, d] decoder output of the train-mode trunk on the native kernels (net.trunk == "hip")."""
+    dev = next(net.parameters()).device
+    if dev.type != "cuda":
+        raise IrsError("trunk='hip' runs the decoder trunk on the HIP engine: move the network to a GPU "
+                       "(or select trunk='torch')")
+    p = float(net.dropout) if net.training else 0.0
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout p={p} outside [0, 1)")
+    # one 62-bit dropout key per step from torch's default CPU generator: torch.manual_seed / utils.set_seed make runs
+    # reproducible, and no device sync is needed
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    names, params = _trunk_params(net, emb_name)
+    seq = seq.contiguous().to(torch.int64)
+    user = user.contiguous().to(torch.int64) if user is not None else None
+    return _TrunkHip.apply(seq, user, p, seed, net._hip, names, *params)
 
 
 def pad_ragged_ids(lists: Sequence, device, minus: int = 1) -> torch.Tensor:

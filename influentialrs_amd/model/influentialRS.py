@@ -5,8 +5,10 @@ tuples and state_dict key set as the reference, so
 `pipeline.py` can import this module in place of `model.influentialRS`
 unchanged.  In eval mode every forward / scoring / path-search call runs on the
 hand-written gfx950 kernels behind include/irs_hip.h; there is no CPU
-fallback (IrsError if the network is not on a GPU).  Training mode keeps the
-stock PyTorch autograd modules (training is a "next" row).
+fallback (IrsError if the network is not on a GPU).  Training mode runs the
+stock PyTorch autograd modules by default; net.trunk = "hip" (or
+IRS_TRAIN_TRUNK=hip) runs the decoder trunk's forward and backward on the
+native kernels instead.
 
 Behaviour pinned by the reference (file:line = /root/reference/model/influentialRS.py):
   * mask semantics are the AS-CALLED ones (allowed = r_u, last column = 1.0,
@@ -28,7 +30,7 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from .._lib import IRS_MASK_IRN, IRS_ROW_NO_CANDIDATE
-from ._backend import HipBackend, make_scheduler, pad_ragged_ids, project_ce
+from ._backend import HipBackend, check_trunk, make_scheduler, pad_ragged_ids, project_ce, train_trunk_default, trunk_hip
 from .layers import PositionalEncoding, get_item_index
 
 _SHARDED_GRAPH = os.environ.get("IRS_SHARDED_GRAPH", "0") == "1"  # captured sharded steps: opt-in (see _beam_paths)
@@ -68,6 +70,17 @@ class InfluentialNet(nn.Module):
                                     eps=1e-09, lr=config.lr1)
         self.pla_lr_scheduler = make_scheduler(self.optimizer)
         self._hip = HipBackend(self, IRS_MASK_IRN)
+        self.trunk = train_trunk_default()
+
+    @property
+    def trunk(self) -> str:
+        """Train-mode decoder trunk: "torch" (stock nn.TransformerDecoder autograd) or "hip" (native forward + backward,
+        include/irs_hip.h irs_train_*).  Default from IRS_TRAIN_TRUNK."""
+        return self._trunk
+
+    @trunk.setter
+    def trunk(self, v: str):
+        self._trunk = check_trunk(v)
 
     # ---- checkpoint contract: accept nn.DataParallel's "module." prefix (pipeline.py:140-142)
     def load_state_dict(self, state_dict, strict=True, **kw):
@@ -95,6 +108,9 @@ class InfluentialNet(nn.Module):
         return torch.repeat_interleave(m, self.n_heads, dim=0)
 
     def _decoding_autograd(self, dec_input_seq, user):
+        if self.trunk == "hip":
+            pi = self.user_mask_layer(self.user_embedder(user))
+            return trunk_hip(self, dec_input_seq, user, "item_embedder.weight"), pi
         pad = dec_input_seq.eq(self.PAD_ID)
         enc = torch.zeros(self.max_len, dec_input_seq.size(0), self.embed_dim, device=dec_input_seq.device)
         x = self.item_embedder(dec_input_seq) * math.sqrt(self.embed_dim) + self.pos_embedder(dec_input_seq)

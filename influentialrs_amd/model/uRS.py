@@ -3,7 +3,7 @@ evaluator's next-item recommender): same constructor, forward/decoding
 signatures and state_dict keys (word_embedder, pos_embedder.pe, decoder.*,
 project.*).  Standard causal 0/-inf mask + key padding on post-padded input
 (reference uRS.py:47-64).  Eval mode runs on the HIP engine; training mode is
-stock PyTorch autograd."""
+stock PyTorch autograd, or the native trunk with net.trunk = "hip"."""
 import math
 
 import torch
@@ -11,7 +11,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .._lib import IRS_MASK_CAUSAL
-from ._backend import HipBackend
+from ._backend import HipBackend, check_trunk, train_trunk_default, trunk_hip
 from .layers import PositionalEncoding
 
 
@@ -36,6 +36,16 @@ class SampleNet(nn.Module):
             num_layers=self.n_layers)
         self.project = nn.Linear(self.embed_dim, self.n_item)
         self._hip = HipBackend(self, IRS_MASK_CAUSAL)
+        self.trunk = train_trunk_default()
+
+    @property
+    def trunk(self) -> str:
+        """Train-mode decoder trunk: "torch" (stock autograd) or "hip" (native); default from IRS_TRAIN_TRUNK."""
+        return self._trunk
+
+    @trunk.setter
+    def trunk(self, v: str):
+        self._trunk = check_trunk(v)
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}
@@ -50,6 +60,8 @@ class SampleNet(nn.Module):
         return mask.float().masked_fill(mask == 0, float("-inf")).masked_fill(mask == 1, float(0.0))
 
     def _decoding_autograd(self, seq):
+        if self.trunk == "hip":
+            return trunk_hip(self, seq, None, "word_embedder.weight")
         pad = seq.eq(self.PAD_ID)
         enc = torch.zeros(self.max_len, seq.size(0), self.embed_dim, device=seq.device)
         x = self.word_embedder(seq) * math.sqrt(self.embed_dim) + self.pos_embedder(seq)
