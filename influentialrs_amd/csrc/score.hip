@@ -53,7 +53,6 @@ struct SweepArgs {
     // tile range and decomposition
     int tile_begin, tile_end, tiles_per_wave, n_strips, n_ublocks;
     int tile_stride; // PRE samples tiles tile_begin + i * tile_stride
-    int no_stagger;   // ring kernel, development switch: all waves take the step barrier at the same k-step
     int tiles_per_wg; // ring kernel, EMIT: tiles per workgroup strip (0: 4 * tiles_per_wave, the PRE group structure)
     // outputs
     float *gm;                   // PRE  [M_pad / 4][n_groups][4]: the four rows a selection workgroup owns are one contiguous block
@@ -308,158 +307,16 @@ __global__ void __launch_bounds__(256, 2) k_sweep_bf16(SweepArgs a) {
     }
 }
 
-// =============================== bf16 sweep, row-stationary 2 x RT blocks (>= one full row block) ===============================
-// k_sweep_bf16 reads one B fragment from LDS per MFMA and runs one dependent MFMA chain per wave; measured
-// in-kernel (s_memtime) that is ~415 cycles for 256 cycles of matrix work per 32x32 tile.  Once the sweep is
-// compute bound (hundreds of rows) the roles are swapped: a wave keeps the bf16 fragments of ITS RT row tiles
-// in registers for the whole kernel, the four waves of a workgroup share the streamed W tiles through LDS
-// (staged ST tiles at a time by all 256 threads: registers -> LDS, double buffered, one barrier per stage), and
-// two item tiles are multiplied at once: per k-step 2 fragment reads feed 2 x RT MFMAs on independent
-// accumulators (half the LDS traffic per MFMA, no dependent-issue stalls).  Tiles, PRE groups and every
-// accumulated value are identical to k_sweep_bf16's: the workgroup walks the 4 x tiles_per_wave tiles its four
-// waves would have walked there; group id = (strip * 4 + quarter) * 2 + lane half.
-template <int KS, int RT, int MODE>
-__global__ void __launch_bounds__(256, 2) k_sweep_bf16_rs(SweepArgs a) {
-    constexpr int ST = KS >= 16 ? 2 : 4;       // W tiles per stage (even)
-    constexpr int STAGE_U4 = ST * KS * 64;     // uint4 per stage (fragments)
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    uint4 *ws = reinterpret_cast<uint4 *>(smem);                                  // [2][ST][KS][64]
-    float *bs = reinterpret_cast<float *>(smem + (size_t)2 * STAGE_U4 * 16);      // [2][ST][32] bias
-    int strip, ublock;
-    if (!sweep_map(a, strip, ublock)) return;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6); // uniform for the compiler too: the emission queue's fill count stays scalar
-    const int r = lane & 31, h = lane >> 5;
-    const int ut0 = ublock * 4 * RT + wave * RT; // this wave's first row tile
-    EmitQ eq = emit_queue(smem + (size_t)2 * STAGE_U4 * 16 + 2 * ST * 32 * 4, wave);
-    const int ts = a.tile_stride, tpw = a.tiles_per_wave;
-    const int tfirst = a.tile_begin + strip * 4 * tpw * ts;
-    int ntile = 4 * tpw; // tiles this workgroup walks: t(i) = tfirst + i * ts, while < tile_end
-    {
-        const int avail = (a.tile_end - tfirst + ts - 1) / ts;
-        if (avail < ntile) ntile = avail;
-    }
-    if (ntile <= 0) return;
-    // this wave's rows: fragments in registers for the whole kernel
-    uint4 xr[RT][KS];
-    float aux[RT];
-#pragma unroll
-    for (int u = 0; u < RT; ++u) {
-        const bool live = ut0 + u < a.UT;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-            xr[u][ks] = live ? a.xb[((size_t)(ut0 + u) * KS + ks) * 64 + lane] : make_uint4(0u, 0u, 0u, 0u);
-        if (MODE == MODE_PRE) aux[u] = -INFINITY;
-        else aux[u] = live ? fmaxf(a.thr[(ut0 + u) * 32 + r], -3.0e38f) : INFINITY;
-    }
-    // staging: thread -> uint4 slots tid, tid + 256, ... of the stage image
-    constexpr int NLD = (STAGE_U4 + 255) / 256;
-    uint4 stg[NLD];
-    float stb = 0.f;
-    auto load_stage = [&](int i0) { // tiles i0 .. i0 + ST - 1 (clamped to the last tile: duplicates are never consumed)
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int idx = tid + j * 256;
-            if (idx < STAGE_U4) {
-                const int tl = idx / (KS * 64);
-                const int t = tfirst + min(i0 + tl, ntile - 1) * ts;
-                const unsigned int *p = reinterpret_cast<const unsigned int *>(a.wp + (size_t)t * KS * 64 + (idx - tl * KS * 64));
-                stg[j] = make_uint4(p[0], p[1], p[2], p[3]);
-            }
-        }
-        if (tid < ST * 32) {
-            const int t = tfirst + min(i0 + (tid >> 5), ntile - 1) * ts;
-            stb = a.bias[(size_t)t * 32 + (tid & 31)];
-        }
-    };
-    auto store_stage = [&](int buf) {
-#pragma unroll
-        for (int j = 0; j < NLD; ++j) {
-            const int idx = tid + j * 256;
-            if (idx < STAGE_U4) ws[buf * STAGE_U4 + idx] = stg[j];
-        }
-        if (tid < ST * 32) bs[buf * ST * 32 + tid] = stb;
-    };
-    load_stage(0);
-    store_stage(0);
-    __syncthreads();
-    int cur = 0;
-    int gcount = 0, gw = strip * 4; // PRE: tiles seen in the current group, group (= wave id of k_sweep_bf16)
-    for (int i0 = 0; i0 < ntile; i0 += ST) {
-        const bool more = i0 + ST < ntile;
-        if (more) load_stage(i0 + ST);
-#pragma unroll
-        for (int tl = 0; tl < ST; tl += 2) {
-            const int i = i0 + tl;
-            if (i < ntile) { // workgroup-uniform; tile i + 1 may be a clamped duplicate (ignored below)
-                const uint4 *w0 = ws + cur * STAGE_U4 + tl * KS * 64 + lane;
-                const uint4 *w1 = w0 + KS * 64;
-                f32x16 acc[2][RT];
-#pragma unroll
-                for (int ti = 0; ti < 2; ++ti) {
-                    const float *bt = bs + (cur * ST + tl + ti) * 32 + 4 * h;
-                    const float4 b0 = *reinterpret_cast<const float4 *>(bt), b1 = *reinterpret_cast<const float4 *>(bt + 8);
-                    const float4 b2 = *reinterpret_cast<const float4 *>(bt + 16), b3 = *reinterpret_cast<const float4 *>(bt + 24);
-                    f32x16 bv;
-                    bv[0] = b0.x, bv[1] = b0.y, bv[2] = b0.z, bv[3] = b0.w, bv[4] = b1.x, bv[5] = b1.y, bv[6] = b1.z, bv[7] = b1.w;
-                    bv[8] = b2.x, bv[9] = b2.y, bv[10] = b2.z, bv[11] = b2.w, bv[12] = b3.x, bv[13] = b3.y, bv[14] = b3.z, bv[15] = b3.w;
-                    const uint4 av = ti == 0 ? w0[0] : w1[0];
-#pragma unroll
-                    for (int u = 0; u < RT; ++u) // the bias vector is the C operand of each chain's first MFMA
-                        acc[ti][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, av),
-                                                                             __builtin_bit_cast(bf16x8, xr[u][0]), bv, 0, 0, 0);
-                }
-#pragma unroll
-                for (int ks = 1; ks < KS; ++ks) {
-                    const uint4 a0 = w0[ks * 64], a1 = w1[ks * 64];
-#pragma unroll
-                    for (int u = 0; u < RT; ++u) {
-                        acc[0][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a0),
-                                                                            __builtin_bit_cast(bf16x8, xr[u][ks]), acc[0][u], 0, 0, 0);
-                        acc[1][u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a1),
-                                                                            __builtin_bit_cast(bf16x8, xr[u][ks]), acc[1][u], 0, 0, 0);
-                    }
-                }
-#pragma unroll
-                for (int ti = 0; ti < 2; ++ti) {
-                    if (i + ti < ntile) {
-                        const int t = tfirst + (i + ti) * ts;
-#pragma unroll
-                        for (int u = 0; u < RT; ++u) {
-                            if (ut0 + u < a.UT) { // wave-uniform
-                                if (MODE == MODE_PRE) aux[u] = fmaxf(aux[u], max16(acc[ti][u]));
-                                else emit_candidates(a, acc[ti][u], aux[u], (ut0 + u) * 32 + r, t, h, eq, lane);
-                            }
-                        }
-                        if (MODE == MODE_PRE) {
-                            ++gcount;
-                            if (gcount == tpw || i + ti + 1 == ntile) { // end of a group: publish, restart
-#pragma unroll
-                                for (int u = 0; u < RT; ++u) {
-                                    if (ut0 + u < a.UT) a.gm[gm_index(a, gw * 2 + h, (ut0 + u) * 32 + r)] = aux[u];
-                                    aux[u] = -INFINITY;
-                                }
-                                gcount = 0;
-                                ++gw;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        if (more) store_stage(cur ^ 1);
-        __syncthreads();
-        cur ^= 1;
-    }
-    if (MODE == MODE_EMIT) emit_flush(a, eq, lane);
-}
-
 // =============================== bf16 sweep, LDS-DMA ring (compute-bound form) ===============================
-// What bounded k_sweep_bf16_rs (lab: tools/sweep_lab.hip, 1M x 128, 1024 rows): a bare MFMA stream with every
-// operand in registers takes 170-190 us on this chip (it holds ~1.5 GHz under dense bf16 MFMA work: ~60 % of the
-// 2.4 GHz peak is the ceiling); LDS fragment reads the compiler issues one k-step ahead add ~15 %, the 16-way maxima
-// of four accumulator sets, each followed at once by its own compare + branch, another ~15 %, and the emission
-// ~20 % more.  This kernel keeps the row-stationary blocking and changes everything around the MFMAs:
+// Once the sweep is compute bound (hundreds of rows) the streaming kernel's roles are swapped (row-stationary blocking):
+// a wave keeps the bf16 fragments of ITS RT row tiles in registers for the whole kernel and the waves of a workgroup
+// share the streamed W tiles through LDS.  The PRE pass walks the 4 x tiles_per_wave tiles the four waves of a
+// streaming workgroup would have walked; group id = (strip * 4 + quarter) * 2 + lane half.  What bounded the first
+// row-stationary form, which staged W registers -> LDS with one barrier per stage (round 1; lab results in
+// profiles/r02): a bare MFMA stream with every operand in registers takes 170-190 us at 1M x 128 x 1024 rows on this
+// chip (it holds ~1.5 GHz under dense bf16 MFMA work: ~60 % of the 2.4 GHz peak is the ceiling); LDS fragment reads the
+// compiler issues one k-step ahead add ~15 %, the 16-way maxima of four accumulator sets, each followed at once by its
+// own compare + branch, another ~15 %, and the emission ~20 % more.  This kernel changes everything around the MFMAs:
 //   * W tiles stream HBM -> LDS by LDS-DMA (global_load_lds_dwordx4: no VGPR staging, no ds_write pass) into a ring
 //     of NSLOT steps; ONE raw s_barrier per step, placed in the MIDDLE of a step's MFMAs, publishes step s + 1 and
 //     frees the slot of step s - 1 for the DMA of step s + NSLOT - 1 -- no wave ever waits at it for its own operands;
@@ -471,7 +328,8 @@ __global__ void __launch_bounds__(256, 2) k_sweep_bf16_rs(SweepArgs a) {
 //     branch-free block (their latencies overlap); only then are the sets with a hit handled;
 //   * hits go to the wave-private LDS queue of the other sweeps (ballot-compacted, scalar fill count), written
 //     with inline-asm stores.
-// Tiles, PRE groups and accumulated values are those of k_sweep_bf16 / k_sweep_bf16_rs (bit-identical output).
+// Tiles, PRE groups and accumulated values are those of k_sweep_bf16 (bit-identical output).  Production runs it at
+// d_pad = 16 only (KS = 1, where 16x16x32 has no full k-step); tools/sweep_lab.hip instantiates it at other KS.
 typedef __attribute__((address_space(3))) void irs_lds_void;
 typedef const __attribute__((address_space(1))) void irs_glb_void;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
@@ -512,7 +370,7 @@ __device__ __forceinline__ void ring_emit_one(EmitQ &q, unsigned int q_addr, flo
     }
 }
 
-template <int KS, int RT, int TPS, int NW, int WPS, int NSLOT, int MODE, int DBG = 0>
+template <int KS, int RT, int TPS, int NW, int WPS, int NSLOT, int MODE>
 __global__ void __launch_bounds__(NW * 64, WPS) k_sweep_ring(SweepArgs a) {
     static_assert(MODE == MODE_PRE || MODE == MODE_EMIT, "top-k modes only");
     constexpr int SLOT_B = TPS * KS * 1024;  // fragment bytes per ring slot
@@ -521,7 +379,7 @@ __global__ void __launch_bounds__(NW * 64, WPS) k_sweep_ring(SweepArgs a) {
     constexpr int D = NSLOT - 1;             // steps resident beyond the one being multiplied
     static_assert(NSLOT >= 3, "the ring advances in the middle of a step: at least three slots");
     constexpr int KSYNC = KS >= 2 ? KS / 2 : 0; // k-step in front of which the ring advances
-    constexpr int PD = KS >= 3 ? ((KS * TPS >= 32 || (DBG & 2)) ? 1 : 2) : KS - 1; // fragment prefetch distance in k-steps (registers at d_pad = 256)
+    constexpr int PD = KS >= 3 ? (KS * TPS >= 32 ? 1 : 2) : KS - 1; // fragment prefetch distance in k-steps (registers at d_pad = 256)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int strip, ublock;
     if (!sweep_map(a, strip, ublock)) return;
@@ -626,30 +484,19 @@ __global__ void __launch_bounds__(NW * 64, WPS) k_sweep_ring(SweepArgs a) {
     prefetch_head(0);
     head_landed();
     int gcount = 0, gw = strip * 4; // PRE: tiles seen in the current group; group (= wave id of k_sweep_bf16)
-    // Eight waves = two per SIMD running the same program between the same barriers would march in lockstep (MFMA
-    // phases together, epilogues together).  The second half of the workgroup takes the step's barrier in front
-    // of k-step 0 instead of k-step KSYNC: it then runs half a step behind the first half for the whole kernel,
-    // so a SIMD's two waves alternate between matrix work and epilogue.
-    const bool late = NW == 8 && wave >= NW / 2 && !a.no_stagger;
     for (int s = 0; s < nstep; ++s) {
         const unsigned int fa = frag_addr + (s % NSLOT) * SLOT_B;
         f32x16 acc[TPS][RT];
         // ---- MFMAs of step s; LDS reads run PD k-steps ahead; the ring advances in front of k-step KSYNC
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            if (KS > 1 && s + 1 < nstep && (late ? ks == 0 : ks == KSYNC)) {
+            if (KS > 1 && s + 1 < nstep && ks == KSYNC) {
                 // this wave's pieces of step s + 1 have landed: steps s + 1 .. s + D - 1 are in flight in a full
                 // pipeline (step s + D is issued behind the barrier), so all but the (D - 2) * PPW youngest DMAs
                 if (s + D <= nstep) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 2) * PPW) : "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier(); // step s + 1 is visible to all; every wave has left step s - 1
                 if (s + D < nstep) issue(s + D); // into the slot of step s - 1
-            }
-            if (DBG & 4) {
-                asm volatile("s_nop 15");
-                asm volatile("s_nop 15");
-                asm volatile("s_nop 15");
-                asm volatile("s_nop 15");
             }
             if (ks + PD < KS) {
                 switch (ks + PD) { // compile-time after unrolling
@@ -667,7 +514,7 @@ __global__ void __launch_bounds__(NW * 64, WPS) k_sweep_ring(SweepArgs a) {
             // k-steps < PD arrived with the head; reads younger than k-step ks's: those of the next min(PD, KS - 1 - ks) k-steps
             if (ks >= PD) {
                 u32x4 &f0 = af[ks % (PD + 1)][0];
-                const int younger = (DBG & 1) ? 0 : (KS - 1 - ks < PD ? KS - 1 - ks : PD) * TPS;
+                const int younger = (KS - 1 - ks < PD ? KS - 1 - ks : PD) * TPS;
                 if constexpr (TPS == 1) {
                     if (younger >= 2 * TPS) lds_wait<2 * TPS>(f0);
                     else if (younger >= TPS) lds_wait<TPS>(f0);
@@ -703,12 +550,6 @@ __global__ void __launch_bounds__(NW * 64, WPS) k_sweep_ring(SweepArgs a) {
             if (s + D < nstep) issue(s + D);
         }
         // the head of step s + 1 is requested before this step's epilogue runs
-        if (DBG & 8) {
-            asm volatile("s_nop 15");
-            asm volatile("s_nop 15");
-            asm volatile("s_nop 15");
-            asm volatile("s_nop 15");
-        }
         if (s + 1 < nstep) prefetch_head(s + 1);
         // ---- epilogue of step s
         if (MODE == MODE_PRE) {
@@ -2650,41 +2491,26 @@ static int resident_workgroups(K kern, int threads, size_t lds) {
     return prop.multiProcessorCount * per_cu;
 }
 
-template <int KS, int RT, int TPS, int NW, int MODE>
-static void launch_ring(SweepArgs &a, hipStream_t s) {
-    constexpr int NSLOT = 4; // two steps of DMA in flight behind the one being multiplied
-    a.n_ublocks = (a.UT + NW * RT - 1) / (NW * RT);
-    const size_t lds = (size_t)NSLOT * TPS * KS * 1024 + (size_t)NSLOT * TPS * 256 + (size_t)NW * (EMIT_Q * 12 + 16);
-    auto kern = k_sweep_ring<KS, RT, TPS, NW, 2, NSLOT, MODE>;
-    static std::atomic<int> slots_dev[IRS_MAX_DEVICES]; // per instantiation and device
-    const int dev_ = irs_cur_dev();
-    int slots = slots_dev[dev_].load(std::memory_order_acquire);
+// Resident workgroups of the ring kernel KERN on the current device, cached per instantiation and device.  LDS above
+// 64 KB is allowed first: the occupancy query and every launch need it.
+template <auto KERN>
+static int ring_slots(int threads, size_t lds) {
+    static std::atomic<int> slots_dev[IRS_MAX_DEVICES];
+    const int dev = irs_cur_dev();
+    int slots = slots_dev[dev].load(std::memory_order_acquire);
     if (!slots) {
         if (lds > 65536)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        slots = resident_workgroups(kern, NW * 64, lds);
-        slots_dev[dev_].store(slots, std::memory_order_release);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        slots = resident_workgroups(KERN, threads, lds);
+        slots_dev[dev].store(slots, std::memory_order_release);
     }
-    if (MODE == MODE_EMIT) {
-        // Equal strips, sized so that the grid is just under a whole number of rounds of resident workgroups: the
-        // time of a sweep is rounds x strip length, and a grid of 2.06 rounds costs 3 (measured: 322 vs 264 us).  Four rounds of shorter strips balance a little
-        // better than two or three of longer ones (lab: -4 % at both catalog shapes).
-        const int nt = a.tile_end - a.tile_begin;
-        int rounds = 4;
-        while (rounds > 1 && (long long)nt * a.n_ublocks < (long long)rounds * slots * 16) --rounds; // >= 16 tiles per strip
-        int strips = (int)((long long)rounds * slots / a.n_ublocks) & ~7; // strips of one XCD class are multiples of 8
-        if (strips < 8) strips = 8;
-        a.tiles_per_wg = (nt + strips - 1) / strips;
-        if (a.tiles_per_wg < 1) a.tiles_per_wg = 1;
-        a.n_strips = (nt + a.tiles_per_wg - 1) / a.tiles_per_wg;
-        a.tile_stride = 1;
-    } else
-        a.tiles_per_wg = 0;
-    dim3 grid(((a.n_strips + 7) / 8) * 8 * a.n_ublocks);
-    hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
+    return slots;
 }
 
-// grid of the ring kernels' EMIT pass: equal strips, just under a whole number of rounds of resident workgroups
+// grid of the ring kernels' EMIT pass.  Equal strips, sized so that the grid is just under a whole number of rounds of
+// resident workgroups: the time of a sweep is rounds x strip length, and a grid of 2.06 rounds costs 3 (measured: 322 vs
+// 264 us).  Four rounds of shorter strips balance a little better than two or three of longer ones (lab: -4 % at both
+// catalog shapes).
 static void ring_emit_grid(SweepArgs &a, int slots) {
     const int nt = a.tile_end - a.tile_begin;
     int rounds = 4;
@@ -2697,36 +2523,37 @@ static void ring_emit_grid(SweepArgs &a, int slots) {
     a.tile_stride = 1;
 }
 
+// one launch of a ring kernel with NW waves per workgroup (a.n_ublocks set); PRE keeps the group structure of sweep_decompose
+template <auto KERN, int NW, int MODE>
+static void launch_ring_kernel(SweepArgs &a, size_t lds, hipStream_t s) {
+    const int slots = ring_slots<KERN>(NW * 64, lds);
+    if (MODE == MODE_EMIT) ring_emit_grid(a, slots);
+    else a.tiles_per_wg = 0;
+    hipLaunchKernelGGL(KERN, dim3(((a.n_strips + 7) / 8) * 8 * a.n_ublocks), dim3(NW * 64), lds, s, a);
+}
+
+template <int KS, int RT, int TPS, int NW, int MODE>
+static void launch_ring(SweepArgs &a, hipStream_t s) {
+    constexpr int NSLOT = 4; // two steps of DMA in flight behind the one being multiplied
+    a.n_ublocks = (a.UT + NW * RT - 1) / (NW * RT);
+    const size_t lds = (size_t)NSLOT * TPS * KS * 1024 + (size_t)NSLOT * TPS * 256 + (size_t)NW * (EMIT_Q * 12 + 16);
+    launch_ring_kernel<k_sweep_ring<KS, RT, TPS, NW, 2, NSLOT, MODE>, NW, MODE>(a, lds, s);
+}
+
 template <int KS, int RT16, int NW, int MODE>
 static void launch_ring16(SweepArgs &a, hipStream_t s) {
     constexpr int NSLOT = 4;
     a.n_ublocks = (a.UT + NW * (RT16 / 2) - 1) / (NW * (RT16 / 2));
-    const size_t lds = ring16_lds_bytes(KS, RT16, NW, NSLOT);
-    auto kern = k_sweep_ring16<KS, RT16, NW, NSLOT, MODE>;
-    static std::atomic<int> slots_dev[IRS_MAX_DEVICES]; // per instantiation and device
-    const int dev_ = irs_cur_dev();
-    int slots = slots_dev[dev_].load(std::memory_order_acquire);
-    if (!slots) {
-        if (lds > 65536)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        slots = resident_workgroups(kern, NW * 64, lds);
-        slots_dev[dev_].store(slots, std::memory_order_release);
-    }
-    if (MODE == MODE_EMIT) ring_emit_grid(a, slots);
-    else a.tiles_per_wg = 0;
-    dim3 grid(((a.n_strips + 7) / 8) * 8 * a.n_ublocks);
-    hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
+    launch_ring_kernel<k_sweep_ring16<KS, RT16, NW, NSLOT, MODE>, NW, MODE>(a, ring16_lds_bytes(KS, RT16, NW, NSLOT), s);
 }
 
 template <int MODE>
 static int launch_sweep_bf16(irs_ctx *ctx, SweepArgs &a, hipStream_t s) {
-    const int KS = ctx->KS, UB = ub_bf16(KS);
-    // compute-bound regime (>= 256 rows), d_pad >= 32: the ring kernel on 16x16x32 MFMAs (sweep_variant 4: the 32x32x16
-    // ring, development A/B only)
-    if (a.UT >= 8 && KS >= 2 && ctx->sweep_variant == 0) {
-        // 4 row tiles of 16 rows per wave, 256 rows per workgroup: ~170 registers, three workgroups per CU.  (Lab, 1M x 128
-        // x 1024 rows: 209 us against 222 us with 8 row tiles per wave at two workgroups per CU, 274 us for the 32x32x16
-        // ring; 1.25M x 256: 491 us against 569 us.)
+    const int KS = ctx->KS;
+    if (a.UT >= 8 && KS >= 2) {
+        // compute-bound regime (>= 256 rows): the ring kernel on 16x16x32 MFMAs.  4 row tiles of 16 rows per wave, 256
+        // rows per workgroup: ~170 registers, three workgroups per CU.  (Lab, 1M x 128 x 1024 rows: 209 us against 222 us
+        // with 8 row tiles per wave at two workgroups per CU, 274 us for the 32x32x16 ring; 1.25M x 256: 491 us against 569 us.)
         switch (KS) {
         case 2: launch_ring16<2, 4, 4, MODE>(a, s); break;
         case 4: launch_ring16<4, 4, 4, MODE>(a, s); break;
@@ -2734,53 +2561,29 @@ static int launch_sweep_bf16(irs_ctx *ctx, SweepArgs &a, hipStream_t s) {
         case 16: launch_ring16<16, 4, 4, MODE>(a, s); break;
         default: IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "unsupported d_pad %d", ctx->d_pad);
         }
-        IRS_CHECK_HIP(ctx, hipGetLastError());
-        return IRS_OK;
-    }
-    if (a.UT >= 8 && ctx->sweep_variant != 1 && ctx->sweep_variant != 3) {
-        a.no_stagger = ctx->sweep_variant == 2;
+    } else if (a.UT >= 8 && KS == 1) {
+        // compute-bound regime at d_pad = 16 (KS = 1), where 16x16x32 has no full k-step: the 32x32x16 ring, 512 or 256
+        // rows per workgroup, whichever pads the row count less
         const int w512 = (a.UT + 15) / 16 * 16 - a.UT, w256 = (a.UT + 7) / 8 * 8 - a.UT;
-        const bool big = w512 <= w256;
+        if (w512 <= w256) launch_ring<1, 4, 1, 4, MODE>(a, s);
+        else launch_ring<1, 2, 2, 4, MODE>(a, s);
+    } else {
+        // fewer than 256 rows: bound by the catalog stream, the streaming kernel with the row block staged in LDS
+        const int UB = ub_bf16(KS);
+        a.n_ublocks = (a.UT + UB - 1) / UB;
+        dim3 grid(((a.n_strips + 7) / 8) * 8 * a.n_ublocks);
+        size_t lds = (size_t)UB * KS * 1024 + EMIT_Q_BYTES;
+#define L_(KS_, UB_) hipLaunchKernelGGL((k_sweep_bf16<KS_, UB_, MODE>), grid, dim3(256), lds, s, a)
         switch (KS) {
-        case 1: big ? launch_ring<1, 4, 1, 4, MODE>(a, s) : launch_ring<1, 2, 2, 4, MODE>(a, s); break;
-        case 2: big ? launch_ring<2, 4, 1, 4, MODE>(a, s) : launch_ring<2, 2, 2, 4, MODE>(a, s); break;
-        case 4: big ? launch_ring<4, 4, 1, 4, MODE>(a, s) : launch_ring<4, 2, 2, 4, MODE>(a, s); break;
-        case 8: big ? launch_ring<8, 4, 1, 4, MODE>(a, s) : launch_ring<8, 2, 2, 4, MODE>(a, s); break;
-        case 16: launch_ring<16, 2, 1, 4, MODE>(a, s); break; // 256 rows per workgroup: two row tiles per wave is all the register file holds
+        case 1: L_(1, 8); break;
+        case 2: L_(2, 8); break;
+        case 4: L_(4, 8); break;
+        case 8: L_(8, 8); break;
+        case 16: L_(16, 4); break;
         default: IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "unsupported d_pad %d", ctx->d_pad);
         }
-        IRS_CHECK_HIP(ctx, hipGetLastError());
-        return IRS_OK;
-    }
-    a.n_ublocks = (a.UT + UB - 1) / UB;
-    dim3 grid(((a.n_strips + 7) / 8) * 8 * a.n_ublocks);
-    if (a.UT >= UB && KS <= 8 && ctx->sweep_variant == 1) { // previous compute-bound form (kept for A/B measurements)
-        const int ST = KS >= 16 ? 2 : 4; // as in the kernel
-        const size_t lds_rs = (size_t)2 * ST * KS * 1024 + 2 * ST * 32 * 4 + EMIT_Q_BYTES;
-#define R_(KS_, RT_) hipLaunchKernelGGL((k_sweep_bf16_rs<KS_, RT_, MODE>), grid, dim3(256), lds_rs, s, a)
-        switch (KS) { // UB = 4 * RT must equal ub_bf16(KS)
-        case 1: R_(1, 2); break;
-        case 2: R_(2, 2); break;
-        case 4: R_(4, 2); break;
-        case 8: R_(8, 2); break;
-        default: IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "unsupported d_pad %d", ctx->d_pad);
-        }
-#undef R_
-        IRS_CHECK_HIP(ctx, hipGetLastError());
-        return IRS_OK;
-    }
-    size_t lds = (size_t)UB * KS * 1024 + EMIT_Q_BYTES;
-#define L_(KS_, UB_)                                                                                           \
-    hipLaunchKernelGGL((k_sweep_bf16<KS_, UB_, MODE>), grid, dim3(256), lds, s, a)
-    switch (KS) {
-    case 1: L_(1, 8); break;
-    case 2: L_(2, 8); break;
-    case 4: L_(4, 8); break;
-    case 8: L_(8, 8); break;
-    case 16: L_(16, 4); break;
-    default: IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "unsupported d_pad %d", ctx->d_pad);
-    }
 #undef L_
+    }
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }
@@ -2810,7 +2613,7 @@ static int launch_sweep_f32(irs_ctx *ctx, SweepArgs &a, hipStream_t s) {
     return IRS_OK;
 }
 
-static void sweep_common(irs_ctx *ctx, SweepArgs &a, const float *xrows, int M) {
+static void sweep_common(const irs_ctx *ctx, SweepArgs &a, const float *xrows, int M) {
     memset(&a, 0, sizeof(a));
     a.wp = ctx->wp;
     a.w32 = ctx->proj_w;
@@ -2853,6 +2656,26 @@ static bool lse_ring_ok(const irs_ctx *ctx, const SweepArgs &a) {
 // waves (= pairs of (max, sum) partial slots) a log-sum-exp sweep may use: the ring form runs 8 waves on every CU
 static int lse_wave_budget(const irs_ctx *ctx, const SweepArgs &a) {
     return lse_ring_ok(ctx, a) ? IRS_LSE_SLOTS_RING / 2 : ctx->lse_slots / 2;
+}
+
+// a log-sum-exp sweep over the whole shard into a bounded number of (max, sum) partial slots: tiles per wave from the
+// slot budget; *slots = the partial slots the sweep writes
+static int lse_decompose(irs_ctx *ctx, SweepArgs &a, int *slots) {
+    const int max_waves = lse_wave_budget(ctx, a);
+    int tpw = (ctx->n_tiles + max_waves - 1) / max_waves;
+    if (tpw < 1) tpw = 1;
+    sweep_decompose(a, 0, ctx->n_tiles, 1, tpw);
+    *slots = a.n_strips * 4 * 2;
+    if (*slots > 2 * max_waves) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "lse slots %d > %d", *slots, 2 * max_waves);
+    a.lse_part = ctx->lse_part;
+    return IRS_OK;
+}
+
+// arguments of a float32 sweep over the whole shard (count-before, dense logits, CE gradient)
+static void sweep_f32_whole(const irs_ctx *ctx, SweepArgs &a, const float *xrows, int M) {
+    sweep_common(ctx, a, xrows, M);
+    const int nub = (a.UT + ub_f32(ctx->KS) - 1) / ub_f32(ctx->KS);
+    sweep_decompose(a, 0, ctx->n_tiles, nub, 0);
 }
 
 template <bool EMIT>
@@ -2912,68 +2735,51 @@ bool irs_topk_is_direct(const irs_ctx *ctx, int M, int k) {
     return M <= 1024 && ctx->n_local <= DIRECT_MAX_ITEMS && k <= 256 && ctx->dims.d <= DIRECT_MAX_D;
 }
 
-// lse_max / lse_sum non-null: the rows' log-sum-exp over the shard as well (beam search).  On the swept path with the
-// bf16 filter it comes out of the SAME pass as the candidates: pre-pass and threshold on the bf16 catalog sample as
-// usual, then one sweep of the float32 catalog that emits against the threshold and accumulates (max, sum exp).
-int irs_launch_topk(irs_ctx *ctx, const float *xrows, int M, int k, int sweep, float *val, int64_t *ids0,
-                    int32_t *status, hipStream_t s, const irs_path_args *path, float *lse_max, float *lse_sum, int carry) {
-    if (path && !irs_topk_is_direct(ctx, M, k)) IRS_FAIL(ctx, IRS_E_STATE, "fused path step needs the one-launch top-k");
-    if (irs_topk_is_direct(ctx, M, k)) {
-        // latency path on a small shard: one kernel, no fallback needed
-        irs_prof_begin(ctx, IRS_PROF_REFINE, s);
-        const unsigned int tiles = (unsigned)((ctx->n_local + DIRECT_TILE - 1) / DIRECT_TILE);
-        unsigned int *arrive = reinterpret_cast<unsigned int *>(ctx->step_ctr) + 8;
-        const irs_path_args pa = path ? *path : irs_path_args{};
-        if (M <= 32)
-            hipLaunchKernelGGL(k_topk_direct<0>, dim3(tiles, M), dim3(256), 0, s, xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b,
-                               (int)ctx->n_local, ctx->shard.item_lo, k, ctx->cand, arrive, val, ids0, status, pa, M);
-        else {
-            hipLaunchKernelGGL(k_topk_direct<1>, dim3(tiles, (M + DIRECT_ROWS - 1) / DIRECT_ROWS), dim3(256), 0, s, xrows, ctx->dims.d,
-                               ctx->proj_w, ctx->proj_b, (int)ctx->n_local, ctx->shard.item_lo, k, ctx->cand, arrive, val, ids0,
-                               status, irs_path_args{}, M);
-            hipLaunchKernelGGL(k_topk_direct<2>, dim3(1, M), dim3(256), 0, s, xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b,
-                               (int)ctx->n_local, ctx->shard.item_lo, k, ctx->cand, arrive, val, ids0, status, pa, M);
-        }
-        irs_prof_end(ctx, IRS_PROF_REFINE, s, 2.0 * ctx->dims.d * (double)M * (double)ctx->n_local, 0.0);
-        IRS_CHECK_HIP(ctx, hipGetLastError());
-        return lse_max ? irs_launch_lse(ctx, xrows, M, lse_max, lse_sum, s) : IRS_OK;
+// How one irs_launch_topk call runs, decided once from the shapes and the context.
+enum TopkForm {
+    TOPK_DIRECT1, // direct, one launch (<= 32 rows): scoring and selection in one kernel
+    TOPK_DIRECT2, // direct, two launches: scoring, then selection with one workgroup per row
+    TOPK_SWEPT,   // prep, pre-pass + threshold selection, emission sweep, refine (+ cooperative fallback)
+};
+struct TopkPlan {
+    TopkForm form;
+    bool fused_lse; // swept: the emission sweep runs on the float32 catalog and accumulates the log-sum-exp as well
+    bool lse_after; // the log-sum-exp is wanted and comes from its own sweep after the top-k
+    bool reuse_thr; // swept: the previous step's thresholds are carried; no pre-pass, no selection
+    bool coop_fb;   // swept: fallback rows are redone cooperatively (k_exh_strips) instead of inside k_refine
+    int stride;     // pre-pass: sampled tiles 0, stride, 2 stride, ...
+    int nt0;        // pre-pass: sampled tiles
+    int tpw0;       // pre-pass: tiles per wave
+    int r_sel;      // rank of the sampled group maximum that becomes the emission threshold
+};
+
+static TopkPlan topk_plan(const irs_ctx *ctx, const float *xrows, int M, int k, int sweep, bool want_lse, int carry) {
+    TopkPlan p{};
+    if (irs_topk_is_direct(ctx, M, k)) { // latency path on a small shard: no fallback needed
+        p.form = M <= 32 ? TOPK_DIRECT1 : TOPK_DIRECT2;
+        p.lse_after = want_lse;
+        return p;
     }
+    p.form = TOPK_SWEPT;
     SweepArgs a;
     sweep_common(ctx, a, xrows, M);
-    const int M_pad = a.M_pad;
-    const bool fused_lse = lse_max && sweep == IRS_SWEEP_BF16 && lse_fast_ok(ctx, a);
-    const int d = ctx->dims.d;
+    p.fused_lse = want_lse && sweep == IRS_SWEEP_BF16 && lse_fast_ok(ctx, a);
+    p.lse_after = want_lse && !p.fused_lse;
+    // big shards: rows that need the exhaustive path are recorded by k_refine and redone cooperatively (see k_exh_strips);
+    // on small shards one workgroup walks the shard faster than two more launches cost
+    p.coop_fb = ctx->n_local >= IRS_COOP_FALLBACK_MIN_ITEMS && ctx->exh_keys != nullptr;
     const int nt = ctx->n_tiles;
-    int rc;
-    static_assert(IRS_CAND_BUCKETS == 64, "k_prep_x resets one bucket counter per lane");
-    // big shards: rows that need the exhaustive path are recorded by k_refine and redone cooperatively (see k_exh_strips)
-    const bool coop_fb = ctx->n_local >= IRS_COOP_FALLBACK_MIN_ITEMS && ctx->exh_keys != nullptr;
     // Threshold carry (round 5): inside a path search the rows of step t + 1 are the rows of step t one item later -- a row's k-th
     // score moves by ~0.02 per step while the emission threshold sits ~0.2-0.4 below it (profiles/r05/thr_drift_probe.txt) -- so the
     // pre-pass and the threshold selection run on the first step and then every carry_period-th one; in between the thresholds of
     // the previous step are reused (k_prep_x re-derives the validation level for the new rows' eps).  k_refine validates as always:
     // a threshold that no longer fits costs that row the exhaustive path, never a wrong list.
-    // (Only where the threshold is the speculative one of a 1/8 or 1/16 sample -- ~3k-4k candidates per row: shards of 262144 items and
-    //  more.  On a smaller shard the pre-pass sees every tile and the threshold is the tight k-th group maximum: the next step's rows
-    //  would miss it often, and the pre-pass is cheap there anyway.)
-    const bool reuse_thr = carry && ctx->carry_period > 0 && sweep == IRS_SWEEP_BF16 && !fused_lse && ctx->thr_valid && ctx->thr_M == M &&
-                           ctx->thr_k == k && ctx->thr_age + 1 < ctx->carry_period && nt >= 2 * 8 * 1024;
-    if (sweep == IRS_SWEEP_BF16) {
-        // |approx - exact| <= eps[row] for every item of the shard: see k_prep_x
-        const float acc_factor = (float)(ctx->d_pad + 8) * 2.384185791015625e-07f; // (d_pad + 8) 2^-22
-        hipLaunchKernelGGL(k_prep_x, dim3((M_pad + 3) / 4), dim3(256), 0, s, xrows, M, M_pad, d, ctx->KS,
-                           ctx->xb, ctx->eps, ctx->wnorm_max, acc_factor, ctx->cand_cnt, status, coop_fb ? ctx->fb_count : nullptr,
-                           reuse_thr ? ctx->thr : nullptr, reuse_thr ? ctx->ref_tmp : nullptr);
-    } else {
-        IRS_CHECK_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int32_t) * M, s));
-        IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->cand_cnt, 0, sizeof(unsigned int) * (size_t)M_pad * IRS_CAND_BUCKETS, s));
-        hipLaunchKernelGGL(k_zero_eps, dim3((M_pad + 255) / 256), dim3(256), 0, s, ctx->eps, M_pad);
-    }
-    IRS_CHECK_HIP(ctx, hipGetLastError());
-    const int UBh = (sweep == IRS_SWEEP_BF16) ? ub_bf16(ctx->KS) : ub_f32(ctx->KS);
-    const int nub = (a.UT + UBh - 1) / UBh;
-
-    if (!reuse_thr) {
+    // (Only where the threshold is the speculative one of the 1/16 sample -- ~4k candidates per row: shards of 524288 items and
+    //  more.  On a smaller shard the pre-pass sees more of the catalog and the threshold is tighter: the next step's rows would
+    //  miss it more often, and the pre-pass is cheap there anyway.)
+    p.reuse_thr = carry && ctx->carry_period > 0 && sweep == IRS_SWEEP_BF16 && !p.fused_lse && ctx->thr_valid && ctx->thr_M == M &&
+                  ctx->thr_k == k && ctx->thr_age + 1 < ctx->carry_period && nt >= 2 * 8 * 1024;
+    if (p.reuse_thr) return p;
     // pre-pass over a strided sample of item tiles: >= 1024 tiles (32768 items) or 1/8 of the shard; 1/16 where that still is
     // >= 1024 tiles (shards of 524288 items and more; round 4).  The threshold is then the ceil(4k/16) = 25th largest sampled
     // group maximum per row (r_sel below) instead of the 38th of twice as many: ~4k emitted items per row instead of ~3k (a third
@@ -2982,21 +2788,9 @@ int irs_launch_topk(irs_ctx *ctx, const float *xrows, int M, int k, int sweep, f
     int nt0 = nt >= 16 * 1024 ? nt / 16 : nt / 8;
     if (nt0 < 1024) nt0 = 1024;
     if (nt0 > nt) nt0 = nt;
-    const int stride = nt / nt0; // >= 1; sampled tiles 0, stride, 2 stride, ...
-    nt0 = (nt + stride - 1) / stride;
-    int tpw0 = (nt0 + 1023) / 1024; // -> at most ~2048 group maxima per row
-    sweep_decompose(a, 0, nt, nub, tpw0, stride);
-    int n_waves0 = a.n_strips * 4;
-    int G = 2 * n_waves0;
-    if (G > SEL2_G) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "pre-pass groups %d > %d", G, SEL2_G);
-    a.gm = ctx->gm;
-    a.n_groups = G;
-    irs_prof_begin(ctx, IRS_PROF_SWEEP, s);
-    if (sweep == IRS_SWEEP_BF16) rc = launch_sweep_bf16<MODE_PRE>(ctx, a, s);
-    else rc = launch_sweep_f32<MODE_PRE>(ctx, a, s);
-    irs_prof_end(ctx, IRS_PROF_SWEEP, s, 2.0 * d * (double)M * nt0 * 32.0,
-                 (double)nt0 * 32.0 * ctx->d_pad * (sweep == IRS_SWEEP_BF16 ? 2.0 : 4.0));
-    if (rc) return rc;
+    p.stride = nt / nt0; // >= 1
+    p.nt0 = (nt + p.stride - 1) / p.stride;
+    p.tpw0 = (p.nt0 + 1023) / 1024; // -> at most ~2048 group maxima per row
     // Emission threshold = r-th largest sampled group maximum (minus 2 eps).  r = k is rigorous (>= k items
     // score above it).  With a 1/stride sample, r ~ 3k/stride targets ~3k emitted items per row instead of
     // ~k*stride; k_refine validates that >= k items really lie above it and otherwise hands the row to the
@@ -3005,57 +2799,115 @@ int irs_launch_topk(irs_ctx *ctx, const float *xrows, int M, int k, int sweep, f
     //  landed in the 1/stride sample: Binomial(k - 1, 1/stride) >= r_sel.  k = 100: 6e-11 per row at stride 8 with r = 38;
     //  1.1e-5 at stride 16 with r = 19 -- one row in 100 000, seen in the soak run -- so the 1/16 sample targets 4k emitted
     //  items, r = 25: 1.5e-9.)
-    int r_sel = k;
-    if (stride > 1) {
-        r_sel = ((stride >= 16 ? 4 : 3) * k + stride - 1) / stride;
-        if (r_sel < 8) r_sel = 8;
-        if (r_sel > k) r_sel = k;
+    p.r_sel = k;
+    if (p.stride > 1) {
+        p.r_sel = ((p.stride >= 16 ? 4 : 3) * k + p.stride - 1) / p.stride;
+        if (p.r_sel < 8) p.r_sel = 8;
+        if (p.r_sel > k) p.r_sel = k;
     }
-    hipLaunchKernelGGL(k_select_thr_bits, dim3((M_pad + 3) / 4), dim3(256), 0, s, ctx->gm, G, M, M_pad, r_sel, ctx->eps,
+    return p;
+}
+
+// direct forms; a path step is taken by the selection workgroups (MODE 0 or 2), right after they rank their row
+static int topk_direct(irs_ctx *ctx, const TopkPlan &p, const float *xrows, int M, int k, float *val, int64_t *ids0,
+                       int32_t *status, const irs_path_args *path, hipStream_t s) {
+    irs_prof_begin(ctx, IRS_PROF_REFINE, s);
+    const unsigned int tiles = (unsigned)((ctx->n_local + DIRECT_TILE - 1) / DIRECT_TILE);
+    unsigned int *arrive = reinterpret_cast<unsigned int *>(ctx->step_ctr) + 8;
+    const irs_path_args pa = path ? *path : irs_path_args{};
+    if (p.form == TOPK_DIRECT1)
+        hipLaunchKernelGGL(k_topk_direct<0>, dim3(tiles, M), dim3(256), 0, s, xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b,
+                           (int)ctx->n_local, ctx->shard.item_lo, k, ctx->cand, arrive, val, ids0, status, pa, M);
+    else {
+        hipLaunchKernelGGL(k_topk_direct<1>, dim3(tiles, (M + DIRECT_ROWS - 1) / DIRECT_ROWS), dim3(256), 0, s, xrows, ctx->dims.d,
+                           ctx->proj_w, ctx->proj_b, (int)ctx->n_local, ctx->shard.item_lo, k, ctx->cand, arrive, val, ids0,
+                           status, irs_path_args{}, M);
+        hipLaunchKernelGGL(k_topk_direct<2>, dim3(1, M), dim3(256), 0, s, xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b,
+                           (int)ctx->n_local, ctx->shard.item_lo, k, ctx->cand, arrive, val, ids0, status, pa, M);
+    }
+    irs_prof_end(ctx, IRS_PROF_REFINE, s, 2.0 * ctx->dims.d * (double)M * (double)ctx->n_local, 0.0);
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
+// swept, 1: the rows' bf16 fragments and error bounds (bf16), or zero bounds (float32); row status and candidate counters reset
+static int topk_prep(irs_ctx *ctx, const TopkPlan &p, const float *xrows, int M, int M_pad, int sweep, int32_t *status,
+                     hipStream_t s) {
+    static_assert(IRS_CAND_BUCKETS == 64, "k_prep_x resets one bucket counter per lane");
+    if (sweep == IRS_SWEEP_BF16) {
+        // |approx - exact| <= eps[row] for every item of the shard: see k_prep_x
+        const float acc_factor = (float)(ctx->d_pad + 8) * 2.384185791015625e-07f; // (d_pad + 8) 2^-22
+        hipLaunchKernelGGL(k_prep_x, dim3((M_pad + 3) / 4), dim3(256), 0, s, xrows, M, M_pad, ctx->dims.d, ctx->KS,
+                           ctx->xb, ctx->eps, ctx->wnorm_max, acc_factor, ctx->cand_cnt, status, p.coop_fb ? ctx->fb_count : nullptr,
+                           p.reuse_thr ? ctx->thr : nullptr, p.reuse_thr ? ctx->ref_tmp : nullptr);
+    } else {
+        IRS_CHECK_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int32_t) * M, s));
+        IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->cand_cnt, 0, sizeof(unsigned int) * (size_t)M_pad * IRS_CAND_BUCKETS, s));
+        hipLaunchKernelGGL(k_zero_eps, dim3((M_pad + 255) / 256), dim3(256), 0, s, ctx->eps, M_pad);
+    }
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
+// swept, 2: pre-pass over the sampled tiles (per-wave group maxima), then the emission threshold of every row
+static int topk_select(irs_ctx *ctx, const TopkPlan &p, SweepArgs &a, int M, int sweep, hipStream_t s) {
+    sweep_decompose(a, 0, ctx->n_tiles, 1, p.tpw0, p.stride); // (tiles per wave given: the grid hint is not used)
+    const int G = 2 * a.n_strips * 4;
+    if (G > SEL2_G) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "pre-pass groups %d > %d", G, SEL2_G);
+    a.gm = ctx->gm;
+    a.n_groups = G;
+    irs_prof_begin(ctx, IRS_PROF_SWEEP, s);
+    const int rc = sweep == IRS_SWEEP_BF16 ? launch_sweep_bf16<MODE_PRE>(ctx, a, s) : launch_sweep_f32<MODE_PRE>(ctx, a, s);
+    irs_prof_end(ctx, IRS_PROF_SWEEP, s, 2.0 * ctx->dims.d * (double)M * p.nt0 * 32.0,
+                 (double)p.nt0 * 32.0 * ctx->d_pad * (sweep == IRS_SWEEP_BF16 ? 2.0 : 4.0));
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_select_thr_bits, dim3((a.M_pad + 3) / 4), dim3(256), 0, s, ctx->gm, G, M, a.M_pad, p.r_sel, ctx->eps,
                        ctx->thr, ctx->ref_tmp);
     IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
 
-    ctx->thr_valid = (sweep == IRS_SWEEP_BF16), ctx->thr_M = M, ctx->thr_k = k, ctx->thr_age = 0;
-    } else
-        ++ctx->thr_age;
-    // emission sweep over the whole shard
+// swept, 3: emission sweep over the whole shard (fused: with the log-sum-exp partials, reduced behind it)
+static int topk_emit(irs_ctx *ctx, const TopkPlan &p, SweepArgs &a, int M, int sweep, float *lse_max, float *lse_sum,
+                     hipStream_t s) {
     a.thr = ctx->thr;
     a.cnt = ctx->cand_cnt;
     a.cand = ctx->cand;
-    int lse_slots = 0;
-    if (fused_lse) { // bounded number of (max, sum) partials: tiles per wave from the slot budget, like irs_launch_lse
-        const int max_waves = lse_wave_budget(ctx, a);
-        int tpw = (nt + max_waves - 1) / max_waves;
-        if (tpw < 1) tpw = 1;
-        sweep_decompose(a, 0, nt, 1, tpw);
-        lse_slots = a.n_strips * 4 * 2;
-        if (lse_slots > 2 * max_waves) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "lse slots %d > %d", lse_slots, 2 * max_waves);
-        a.lse_part = ctx->lse_part;
-    } else
-        sweep_decompose(a, 0, nt, nub, 0);
-    const double emit_bytes = (double)nt * 32.0 * ctx->d_pad * ((sweep == IRS_SWEEP_BF16 && !fused_lse) ? 2.0 : 4.0);
+    int lse_slots = 0, rc;
+    if (p.fused_lse) {
+        if ((rc = lse_decompose(ctx, a, &lse_slots))) return rc;
+    } else {
+        const int UB = sweep == IRS_SWEEP_BF16 ? ub_bf16(ctx->KS) : ub_f32(ctx->KS);
+        sweep_decompose(a, 0, ctx->n_tiles, (a.UT + UB - 1) / UB, 0);
+    }
+    const double flops = 2.0 * ctx->dims.d * (double)M * (double)ctx->n_local;
+    const double bytes = (double)ctx->n_tiles * 32.0 * ctx->d_pad * ((sweep == IRS_SWEEP_BF16 && !p.fused_lse) ? 2.0 : 4.0);
     irs_prof_begin(ctx, IRS_PROF_SWEEP, s);
     irs_prof_begin(ctx, IRS_PROF_SWEEP_EMIT, s); // (one family is enabled at a time)
-    if (fused_lse) rc = launch_lse_f32<true>(ctx, a, s);
+    if (p.fused_lse) rc = launch_lse_f32<true>(ctx, a, s);
     else if (sweep == IRS_SWEEP_BF16) rc = launch_sweep_bf16<MODE_EMIT>(ctx, a, s);
     else rc = launch_sweep_f32<MODE_EMIT>(ctx, a, s);
-    irs_prof_end(ctx, IRS_PROF_SWEEP, s, 2.0 * d * (double)M * (double)ctx->n_local, emit_bytes);
-    irs_prof_end(ctx, IRS_PROF_SWEEP_EMIT, s, 2.0 * d * (double)M * (double)ctx->n_local, emit_bytes);
+    irs_prof_end(ctx, IRS_PROF_SWEEP, s, flops, bytes);
+    irs_prof_end(ctx, IRS_PROF_SWEEP_EMIT, s, flops, bytes);
     if (rc) return rc;
-    if (fused_lse) {
-        hipLaunchKernelGGL(k_lse_reduce, dim3(M), dim3(256), 0, s, ctx->lse_part, lse_slots, M_pad, M, lse_max, lse_sum);
+    if (p.fused_lse) {
+        hipLaunchKernelGGL(k_lse_reduce, dim3(M), dim3(256), 0, s, ctx->lse_part, lse_slots, a.M_pad, M, lse_max, lse_sum);
         IRS_CHECK_HIP(ctx, hipGetLastError());
     }
+    return IRS_OK;
+}
 
+// swept, 4: exact re-scoring and order of the candidates; rows that need the exhaustive path are redone in k_refine or,
+// cooperatively, by the two kernels behind it (they carry IRS_ROW_FALLBACK)
+static int topk_refine(irs_ctx *ctx, const TopkPlan &p, const float *xrows, int M, int k, int sweep, float *val, int64_t *ids0,
+                       int32_t *status, hipStream_t s) {
+    const int d = ctx->dims.d;
     irs_prof_begin(ctx, IRS_PROF_REFINE, s);
-    // big shards: rows that need the exhaustive path are recorded by k_refine and redone cooperatively (see k_exh_strips);
-    // on small shards one workgroup walks the shard faster than two more launches cost
-    const bool coop = coop_fb;
-    if (coop && sweep != IRS_SWEEP_BF16) IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->fb_count, 0, sizeof(unsigned int), s)); // (bf16: k_prep_x reset it)
+    if (p.coop_fb && sweep != IRS_SWEEP_BF16) IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->fb_count, 0, sizeof(unsigned int), s)); // (bf16: k_prep_x reset it)
     hipLaunchKernelGGL(k_refine, dim3(M), dim3(256), 0, s, xrows, d, ctx->proj_w, ctx->proj_b, ctx->cand_cnt, ctx->cand,
                        ctx->eps, ctx->ref_tmp, k, ctx->shard.item_lo, ctx->n_local, val, ids0, status,
-                       coop ? ctx->fb_count : nullptr, ctx->fb_list);
-    if (coop) {
+                       p.coop_fb ? ctx->fb_count : nullptr, ctx->fb_list);
+    if (p.coop_fb) {
         int ns = EXH_STRIPS;
         while (ns > 1 && (long long)ns * k > EXH_KEYS_PER_ROW) ns >>= 1;
         hipLaunchKernelGGL(k_exh_strips, dim3(ns, 4), dim3(256), 0, s, xrows, d, ctx->proj_w, ctx->proj_b, ctx->n_local, k, ns,
@@ -3063,10 +2915,34 @@ int irs_launch_topk(irs_ctx *ctx, const float *xrows, int M, int k, int sweep, f
         hipLaunchKernelGGL(k_exh_merge, dim3(EXH_FB_MAX), dim3(256), 0, s, xrows, d, ctx->proj_w, ctx->proj_b, ctx->n_local,
                            ctx->shard.item_lo, k, ns, ctx->fb_count, ctx->fb_list, ctx->exh_keys, val, ids0, status);
     }
-    irs_prof_end(ctx, IRS_PROF_REFINE, s, 0.0, 0.0); // (rows flagged IRS_ROW_FALLBACK were redone exhaustively: inside k_refine or by the two kernels behind it)
+    irs_prof_end(ctx, IRS_PROF_REFINE, s, 0.0, 0.0);
     IRS_CHECK_HIP(ctx, hipGetLastError());
-    if (lse_max && !fused_lse) return irs_launch_lse(ctx, xrows, M, lse_max, lse_sum, s);
     return IRS_OK;
+}
+
+// lse_max / lse_sum non-null: the rows' log-sum-exp over the shard as well (beam search).  On the swept path with the
+// bf16 filter it comes out of the SAME pass as the candidates: pre-pass and threshold on the bf16 catalog sample as
+// usual, then one sweep of the float32 catalog that emits against the threshold and accumulates (max, sum exp).
+int irs_launch_topk(irs_ctx *ctx, const float *xrows, int M, int k, int sweep, float *val, int64_t *ids0,
+                    int32_t *status, hipStream_t s, const irs_path_args *path, float *lse_max, float *lse_sum, int carry) {
+    const TopkPlan p = topk_plan(ctx, xrows, M, k, sweep, lse_max != nullptr, carry);
+    if (path && p.form == TOPK_SWEPT) IRS_FAIL(ctx, IRS_E_STATE, "fused path step needs the direct top-k");
+    int rc;
+    if (p.form != TOPK_SWEPT) {
+        if ((rc = topk_direct(ctx, p, xrows, M, k, val, ids0, status, path, s))) return rc;
+    } else {
+        SweepArgs a;
+        sweep_common(ctx, a, xrows, M);
+        if ((rc = topk_prep(ctx, p, xrows, M, a.M_pad, sweep, status, s))) return rc;
+        if (p.reuse_thr) ++ctx->thr_age;
+        else {
+            if ((rc = topk_select(ctx, p, a, M, sweep, s))) return rc;
+            ctx->thr_valid = sweep == IRS_SWEEP_BF16, ctx->thr_M = M, ctx->thr_k = k, ctx->thr_age = 0;
+        }
+        if ((rc = topk_emit(ctx, p, a, M, sweep, lse_max, lse_sum, s))) return rc;
+        if ((rc = topk_refine(ctx, p, xrows, M, k, sweep, val, ids0, status, s))) return rc;
+    }
+    return p.lse_after ? irs_launch_lse(ctx, xrows, M, lse_max, lse_sum, s) : IRS_OK;
 }
 
 // exhaustive exact top-k for every row (tests / yard-stick): sweep = -1 through the C ABI
@@ -3089,12 +2965,10 @@ int irs_launch_gather(irs_ctx *ctx, const float *xrows, int M, const int64_t *id
 int irs_launch_count_before(irs_ctx *ctx, const float *xrows, int M, const float *ref_score, const int64_t *ref_id0,
                             const int64_t *excl, int n_excl, int64_t *count, hipStream_t s) {
     SweepArgs a;
-    sweep_common(ctx, a, xrows, M);
+    sweep_f32_whole(ctx, a, xrows, M);
     IRS_CHECK_HIP(ctx, hipMemsetAsync(count, 0, sizeof(int64_t) * M, s));
     int64_t *ref_local = reinterpret_cast<int64_t *>(ctx->cand); // scratch: [M] int64
     hipLaunchKernelGGL(k_localize_ref, dim3((M + 255) / 256), dim3(256), 0, s, ref_id0, ctx->shard.item_lo, ref_local, M);
-    const int nub = (a.UT + ub_f32(ctx->KS) - 1) / ub_f32(ctx->KS);
-    sweep_decompose(a, 0, ctx->n_tiles, nub, 0);
     a.ref_score = ref_score;
     a.ref_id = ref_local;
     a.count = reinterpret_cast<unsigned long long *>(count);
@@ -3114,9 +2988,7 @@ int irs_launch_count_before(irs_ctx *ctx, const float *xrows, int M, const float
 
 int irs_launch_dense(irs_ctx *ctx, const float *xrows, int M, float *out, int64_t ld, hipStream_t s) {
     SweepArgs a;
-    sweep_common(ctx, a, xrows, M);
-    const int nub = (a.UT + ub_f32(ctx->KS) - 1) / ub_f32(ctx->KS);
-    sweep_decompose(a, 0, ctx->n_tiles, nub, 0);
+    sweep_f32_whole(ctx, a, xrows, M);
     a.dense = out;
     a.ld = ld;
     irs_prof_begin(ctx, IRS_PROF_SWEEP, s);
@@ -3203,11 +3075,9 @@ int irs_launch_ce_reduce(irs_ctx *ctx, const float *lse, const float *lab_score,
 int irs_launch_ce_grad(irs_ctx *ctx, const float *xrows, const int64_t *labels0, const float *lse, int M, float scale,
                        float *out, int64_t ld, hipStream_t s) {
     SweepArgs a;
-    sweep_common(ctx, a, xrows, M);
+    sweep_f32_whole(ctx, a, xrows, M);
     int64_t *lab_local = reinterpret_cast<int64_t *>(ctx->cand); // scratch: [M] int64
     hipLaunchKernelGGL(k_ce_localize, dim3((M + 255) / 256), dim3(256), 0, s, labels0, ctx->shard.item_lo, lab_local, M);
-    const int nub = (a.UT + ub_f32(ctx->KS) - 1) / ub_f32(ctx->KS);
-    sweep_decompose(a, 0, ctx->n_tiles, nub, 0);
     a.dense = out;
     a.ld = ld;
     a.ce_lse = lse;
@@ -3223,17 +3093,9 @@ int irs_launch_ce_grad(irs_ctx *ctx, const float *xrows, const int64_t *labels0,
 int irs_launch_lse(irs_ctx *ctx, const float *xrows, int M, float *out_max, float *out_sum, hipStream_t s) {
     SweepArgs a;
     sweep_common(ctx, a, xrows, M);
-    const int nub = (a.UT + ub_f32(ctx->KS) - 1) / ub_f32(ctx->KS);
-    // bounded number of partial slots: tiles per wave from the slot budget
-    int max_waves = lse_wave_budget(ctx, a);
-    int tpw = (ctx->n_tiles + max_waves - 1) / max_waves;
-    if (tpw < 1) tpw = 1;
-    sweep_decompose(a, 0, ctx->n_tiles, nub, tpw);
-    int slots = a.n_strips * 4 * 2;
-    if (slots > 2 * max_waves) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "lse slots %d > %d", slots, 2 * max_waves);
-    a.lse_part = ctx->lse_part;
+    int slots, rc;
+    if ((rc = lse_decompose(ctx, a, &slots))) return rc;
     irs_prof_begin(ctx, IRS_PROF_SWEEP, s);
-    int rc = IRS_OK;
     if (lse_fast_ok(ctx, a)) rc = launch_lse_f32<false>(ctx, a, s);
     else rc = launch_sweep_f32<MODE_LSE>(ctx, a, s);
     irs_prof_end(ctx, IRS_PROF_SWEEP, s, 2.0 * ctx->dims.d * (double)M * (double)ctx->n_local,
