@@ -140,6 +140,18 @@ __global__ void __launch_bounds__(256) k_plan_fill(const int64_t *__restrict__ s
     }
 }
 
+// compute units of the current device (the persistent GEMM's slot count, the rounds of the sequence-resident launch)
+static int irs_cu_count() {
+    static int n_cu = 0;
+    if (n_cu == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
+            n_cu = 256;
+    }
+    return n_cu;
+}
+
 // ------------------------------------------------------------------ plan of the sequence-resident layer kernel (round 5)
 // k_block_x6<.., SEQ> wants every sequence inside ONE workgroup of 8 wave tiles = 16 half tiles of 16 tokens.  A sequence of nb
 // 16-token blocks takes nb CONSECUTIVE half tiles of its workgroup, [slot, slot + nb) (the first version gave every sequence
@@ -158,11 +170,27 @@ __global__ void __launch_bounds__(256) k_plan_fill(const int64_t *__restrict__ s
 // per plan, most of it those round trips.)
 //   tile_seq[2 t + h] / tile_qb[2 t + h]: sequence (-1: none, preset by k_plan_count) and block index in lanes 16 h .. 16 h + 15 of
 //   grid tile t = 8 wg + wave; seq_row0[b]: first row of the sequence in its workgroup's K / V images (16 x slot); qrow_tile[b]:
-//   tile-order row of the consumed token; n_wg[0]: workgroups in use.
+//   tile-order row of the consumed token; n_wg[0]: workgroups in use; n_wg[1]: the first half-live workgroup (= n_wg[0]: none).
 #define SEQ_WG_TILES 8
 #define SEQ_WG_BLOCKS 16
 #define SEQ_AUTO_MIN_SEQS 384
 #define SEQ_RMAX 48
+// The tail rule (round 6).  One workgroup fits a CU, so the launch runs in rounds of n_cu workgroups and a last round of a few
+// workgroups costs a whole one.  A workgroup whose live tiles all sit on waves 4 .. 7 -- one wave per SIMD; its other four waves
+// only keep the ring going (k_block_x6's idle path) -- finishes in a fraction of a full one's time (profiles/r06).  So the plan
+// first counts the workgroups it would open (n) and, when the last round n mod n_cu is short enough, opens full workgroups only
+// for the whole rounds in front of it; every workgroup opened after that takes SEQ_TAIL_BLOCKS blocks, in half tiles [8, 16).
+// The plan is largest first, so these HALF-LIVE workgroups are the last, highest ids: dispatched last, about one per CU.
+// "Short enough" = at most half a round, AND the half-live workgroups it turns into number at most n_cu: r full workgroups
+// become 2 r to 2.5 r half-live ones -- bins of 8 blocks pack sequences of 2 .. 8 blocks worse than bins of 16 -- and two of them
+// on one CU would cost more than the full round they replace, so the plan counts them too before it decides.  A sequence of
+// more than SEQ_TAIL_BLOCKS blocks cannot go there: the rule applies only if the workgroups such classes open fit the whole
+// rounds (they come first, so the order of ids holds).
+// Inputs: the block counts and the CU count, nothing else.  n_wg[1] = the first half-live id (= n_wg[0] when there is none).
+#define SEQ_TAIL_BLOCKS 8
+#ifndef SEQ_LAB_PLAN
+#define SEQ_LAB_PLAN 0
+#endif
 // half tile (0 .. nb - 1, relative to the sequence's first) of block blk of a sequence of nb blocks starting at an even / odd half
 __host__ __device__ __forceinline__ int seq_half_of_block(bool slot_odd, int nb, int blk) {
     const int mir = nb - 1 - blk;
@@ -182,18 +210,20 @@ __host__ __device__ __forceinline__ int seq_half_of_block(bool slot_odd, int nb,
 __global__ void __launch_bounds__(1024) k_plan_seq(const int32_t *__restrict__ cnt, const int32_t *__restrict__ off,
                                                    const int32_t *__restrict__ qrow, int B, int32_t *__restrict__ tile_seq,
                                                    int32_t *__restrict__ tile_qb, int32_t *__restrict__ seq_row0,
-                                                   int32_t *__restrict__ qrow_tile, int32_t *__restrict__ n_wg, int tiles_cap) {
-    constexpr int C = SEQ_WG_BLOCKS, PT = SEQ_PLAN_PER_THREAD;
+                                                   int32_t *__restrict__ qrow_tile, int32_t *__restrict__ n_wg, int tiles_cap,
+                                                   int n_cu) {
+    constexpr int C = SEQ_WG_BLOCKS, PT = SEQ_PLAN_PER_THREAD, CT = SEQ_TAIL_BLOCKS;
     __shared__ int s_hist[C + 1], s_start[C + 2];
     __shared__ int p_n[C], p_s[C][SEQ_RMAX], p_l[C][SEQ_RMAX]; // pool f = 1 .. 15: ranges of workgroup ids with f free blocks
     __shared__ int c_cum[C + 1], c_q[C], c_exist, c_newbase, s_nwg;
+    __shared__ int s_cap, s_tail0, c_norm, c_nnorm; // the tail rule: full workgroups allowed, first tail id; per class: items / workgroups opened full
     // the sequences sorted by block count (largest first) and each one's consumed token, in LDS: the class loop below loads nothing
     // from memory (the first version re-read a sorted index array and three per-sequence values there: a round trip per class)
     __shared__ unsigned short s_order[1024 * PT], s_pt[1024 * PT];
     const int tid = threadIdx.x;
     if (tid <= C) s_hist[tid] = 0;
     if (tid < C) p_n[tid] = 0;
-    if (tid == 0) s_nwg = 0;
+    if (tid == 0) s_nwg = 0, s_tail0 = -1;
     __syncthreads();
     int my_T[PT], my_rk[PT];
 #pragma unroll
@@ -218,6 +248,66 @@ __global__ void __launch_bounds__(1024) k_plan_seq(const int32_t *__restrict__ c
             s_start[T] = run;
             run += s_hist[T];
         }
+        // the tail rule (see above): the plan below, replayed on the COUNT of workgroups per free-block count alone -- what the
+        // class loop does to the pools, without their id ranges and without placing anything.  Once without a cap (the
+        // workgroups of the plain plan, and those its classes above CT blocks open) and, if the last round is short, once more
+        // with the cap (the half-live workgroups the rule would open).  This arithmetic and the class loop's must stay in step;
+        // they differ only when a pool's range list is full (SEQ_RMAX): the plan then drops a range and opens more workgroups
+        // than counted -- the order of ids holds, only the rounds are no longer the counted ones.
+        // (fully unrolled, the counts in registers, every divisor a constant: a loop over an LDS table took 20 us here)
+        auto count = [&](const int cap, int &nwg, int &nbig, int &ntail) __attribute__((always_inline)) {
+            int dc[C];
+            nwg = 0, nbig = 0, ntail = 0;
+#pragma unroll
+            for (int f = 0; f < C; ++f) dc[f] = 0;
+#pragma unroll
+            for (int T = C; T >= 1; --T) {
+                int left = s_hist[T];
+                if (left > 0) {
+#pragma unroll
+                    for (int f = T; f < C; ++f) {
+                        const int q = f / T, have = dc[f] * q, used = left < have ? left : have;
+                        if (used > 0) {
+                            const int fl = used / q, pa = used - fl * q;
+                            left -= used;
+                            dc[f] -= fl + (pa ? 1 : 0), dc[f - T * q] += fl;
+#pragma unroll
+                            for (int p = 1; p < q; ++p)
+                                if (pa == p) dc[f - T * p] += 1;
+                        }
+                    }
+                    const int q = C / T;
+                    if (T <= CT) { // behind the cap: half-live workgroups
+                        const int qt = T <= CT ? CT / T : 1, room = cap > nwg ? cap - nwg : 0;
+                        if ((long long)room * q < left) {
+                            const int tl = left - room * q, flt = tl / qt, pat = tl - flt * qt;
+                            left = room * q;
+                            dc[CT - T * qt] += flt, nwg += flt + (pat ? 1 : 0), ntail += flt + (pat ? 1 : 0);
+#pragma unroll
+                            for (int p = 1; p < qt; ++p)
+                                if (pat == p) dc[CT - T * p] += 1;
+                        }
+                    }
+                    const int fl = left / q, pa = left - fl * q;
+                    dc[C - T * q] += fl, nwg += fl + (pa ? 1 : 0);
+#pragma unroll
+                    for (int p = 1; p < q; ++p)
+                        if (pa == p) dc[C - T * p] += 1;
+                }
+                if (T == CT + 1) nbig = nwg; // the workgroups the classes that cannot go to the tail open
+            }
+        };
+        int nwg, nbig, ntail;
+        count(0x7FFFFFFF, nwg, nbig, ntail);
+        const int rounds = n_cu > 0 ? nwg / n_cu : 0, rem = nwg - rounds * n_cu;
+        s_cap = 0x7FFFFFFF;
+        if (SEQ_LAB_PLAN == 0 && n_cu > 0 && rem > 0 && 2 * rem <= n_cu && nbig <= rounds * n_cu) {
+            int nwg2, nbig2;
+            count(rounds * n_cu, nwg2, nbig2, ntail);
+            if (ntail <= n_cu) s_cap = rounds * n_cu; // (more than one half-live workgroup per CU would cost more than the full round)
+        }
+        if (SEQ_LAB_PLAN == 1) s_cap = 0;          // (lab) every sequence of at most CT blocks in a half-live workgroup
+        if (SEQ_LAB_PLAN == 2) s_cap = 0x7FFFFFFF; // (lab) the plan without the rule
     }
     __syncthreads();
 #pragma unroll
@@ -258,7 +348,14 @@ __global__ void __launch_bounds__(1024) k_plan_seq(const int32_t *__restrict__ c
             c_cum[C] = tot;
             c_exist = n < tot ? n : tot;
             c_newbase = s_nwg;
-            s_nwg += (n - c_exist + qnew - 1) / qnew;
+            // new workgroups: full ones while the cap lasts (a class above CT blocks: always), half-live ones behind them
+            const int nnew = n - c_exist, room = s_cap > s_nwg ? s_cap - s_nwg : 0;
+            const bool spill = T <= CT && nnew > 0 && (long long)room * qnew < nnew;
+            c_norm = spill ? room * qnew : nnew;
+            c_nnorm = (c_norm + qnew - 1) / qnew;
+            const int ntail = spill ? (nnew - c_norm + CT / T - 1) / (CT / T) : 0;
+            if (ntail > 0 && s_tail0 < 0) s_tail0 = c_newbase + c_nnorm;
+            s_nwg += c_nnorm + ntail;
         }
         __syncthreads();
         const int exist = c_exist, base = s_start[T];
@@ -275,10 +372,14 @@ __global__ void __launch_bounds__(1024) k_plan_seq(const int32_t *__restrict__ c
                 while (r < p_n[f] - 1 && bl >= p_l[f][r]) bl -= p_l[f][r], ++r;
                 w = p_s[f][r] + bl;
                 slot = (C - f) + k * T;
-            } else {
+            } else if (i - exist < c_norm) {
                 const int j_ = i - exist;
                 w = c_newbase + j_ / qnew;
                 slot = (j_ % qnew) * T;
+            } else { // a half-live workgroup: half tiles [C - CT, C) = the tiles of waves 4 .. 7, one wave per SIMD
+                const int j_ = i - exist - c_norm, qt = CT / T;
+                w = c_newbase + c_nnorm + j_ / qt;
+                slot = (C - CT) + (j_ % qt) * T;
             }
             if (w * SEQ_WG_TILES >= tiles_cap) continue; // (cannot happen: at most one workgroup per sequence)
             // the sequence's T blocks onto the half tiles [slot, slot + T) of workgroup w
@@ -304,13 +405,18 @@ __global__ void __launch_bounds__(1024) k_plan_seq(const int32_t *__restrict__ c
                 take_prefix(f, full, f - T * q);
                 if (part) take_prefix(f, 1, f - T * part);
             }
-            const int nnew = n - exist, fullnew = nnew / qnew, partnew = nnew % qnew;
+            const int nnew = c_norm, fullnew = nnew / qnew, partnew = nnew % qnew;
             append(C - T * qnew, c_newbase, fullnew);
             if (partnew) append(C - T * partnew, c_newbase + fullnew, 1);
+            if (n - exist > c_norm) { // (T <= CT) a half-live workgroup enters the pools with the free blocks of its live half
+                const int ntl = n - exist - c_norm, qt = CT / T, fullt = ntl / qt, partt = ntl % qt;
+                append(CT - T * qt, c_newbase + c_nnorm, fullt);
+                if (partt) append(CT - T * partt, c_newbase + c_nnorm + fullt, 1);
+            }
         }
         __syncthreads();
     }
-    if (tid == 0) n_wg[0] = s_nwg;
+    if (tid == 0) n_wg[0] = s_nwg, n_wg[1] = s_tail0 < 0 ? s_nwg : s_tail0;
 }
 
 // Few sequences (the latency path): count, scan and fill in ONE workgroup of 16 waves, together with the
@@ -1614,6 +1720,9 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
 #ifndef SEQ_EXP
 #define SEQ_EXP 0 // (lab, tools/seq_lab.sh: 1 = no attention compute, 2 = asynchronous tail reads: timing experiments, results wrong)
 #endif
+#ifndef SEQ_IDLE_SKIP
+#define SEQ_IDLE_SKIP 1 // (lab: 0 = a wave with two empty halves runs every step on zeros, as it did through round 5)
+#endif
 // SEQ layout of the dynamic LDS behind the ring and the parameter vectors (x6_seq_lds_bytes)
 #define X6_SEQ_VECS (256 + 12 * 32 * 4 + 384)   // floats: the parameter vectors + this layer's in-projection bias
 #define X6_SEQ_KIMG (3 * 16384 + X6_SEQ_VECS * 4)  // K image of ONE head: 256 token rows x 32 float32, chunk-swizzled (k_attn16h's)
@@ -1677,7 +1786,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     const int m0 = blockIdx.x * (32 * NW);
     const int M = SEQ ? 0x7FFFFFFF : (a.m_dev ? min(a.M, a.m_dev[0]) : a.M);
     // SEQ: this wave's tile = TWO 16-token blocks, one per half h (lanes 16 h .. 16 h + 15 of li): block sh_qb[h] of sequence
-    // sh_b[h] (-1: nothing there; a wave with two empty halves still takes part in every step and barrier).  Normally the two are
+    // sh_b[h] (-1: nothing there; a wave with two empty halves keeps the ring and the barriers going: the idle path below).  Normally the two are
     // mirror images of ONE sequence (blocks i and nb - 1 - i: causal attention costs qb + 1 key tiles for block qb, so every
     // wave of a sequence gets nb + 1 of them); the odd middle blocks of two sequences may share a tile (k_plan_seq).
     int sh_b[2] = {-1, -1}, sh_qb[2] = {0, 0}, sh_cnt[2] = {0, 0}, sh_pq[2] = {-1, -1}, sh_row0[2] = {0, 0}, sh_pb[2] = {-1, -1};
@@ -1860,6 +1969,64 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             }
         });
     };
+    if constexpr (SEQ && SEQ_IDLE_SKIP) {
+        // ================= a wave with two empty halves: the ring duty and the barriers of the schedule below, nothing else.
+        // Its tiles would be zeros that only this wave reads back (the attention scratch, the x' tile; the host gathers consumed
+        // rows from live tiles only), and the K / V images take no rows from it -- so it issues its PPW pieces of every step at
+        // the step's mid-point, waits for them like X6_PUBLISH, stands at every workgroup barrier (one per step, one behind each
+        // head's image writes, the empty step between two layers), re-stages its share of the parameter vectors, and leaves the
+        // matrix pipe, the LDS pipe and the registers of its SIMD to the live wave it shares it with.  One loop, entered once:
+        // the live waves' instruction stream below is the one it was.
+        if (sh_b[0] < 0 && sh_b[1] < 0) {
+            issue(S0);
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); // (the vecs stores above too)
+            __builtin_amdgcn_s_barrier();
+            x6_static_for<1, LEAD>([&](auto ic) __attribute__((always_inline)) { issue(S0 + decltype(ic)::value); }); // (as the live path)
+            static_assert(LEAD == 2 && S0 == 0, "the waits below are vmcnt(0): X6_PUBLISH with three ring slots");
+#pragma unroll 1
+            for (ly = 0; ly <= a.n_lay; ++ly) {
+                last_rt = ly == a.n_lay;
+                nsteps_rt = last_rt ? NFRONT : (1 << 20);
+                dma_src = a.Wbase + (long long)ly * a.wstride + (PPW * wave + PPG / 2) * 64 + lane;
+                dma_src_q = a.Wbase + (long long)(ly == 0 ? a.nl_total - 1 : ly - 1) * a.wstride + (PPW * wave + PPG / 2) * 64 + lane;
+                dma_src_qn = dma_src;
+                float nvi[(X6_SEQ_VECS + 64 * NW - 1) / (64 * NW)];
+                if (!last_rt) {
+#pragma unroll
+                    for (int k = 0; k < (X6_SEQ_VECS + 64 * NW - 1) / (64 * NW); ++k)
+                        nvi[k] = (tid + 64 * NW * k < X6_SEQ_VECS) ? a.vecpack[(size_t)(ly + 1) * X6_SEQ_VECS + tid + 64 * NW * k] : 0.f;
+                }
+                // (unrolled: the ring slot of a step is part of the DMA's address arithmetic, a constant per step)
+                x6_static_for<0, NFRONT>([&](auto ic) __attribute__((always_inline)) {
+                    constexpr int i = decltype(ic)::value;
+                    if (i + 1 < nsteps_rt) { // X6_PUBLISH(i)
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        __builtin_amdgcn_s_barrier();
+                        if (i + LEAD < nsteps_rt) issue(i + LEAD);
+                    }
+                    if constexpr (i % 3 == 2) __builtin_amdgcn_s_barrier(); // head i / 3's rows are in the images
+                });
+                if (last_rt) break;
+                x6_static_for<NFRONT, NFRONT + NPRE>([&](auto ic) __attribute__((always_inline)) {
+                    constexpr int i = decltype(ic)::value;
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    issue(i + LEAD);
+                });
+                // the empty step between two layers
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int k = 0; k < (X6_SEQ_VECS + 64 * NW - 1) / (64 * NW); ++k)
+                    if (tid + 64 * NW * k < X6_SEQ_VECS) vecs[tid + 64 * NW * k] = nvi[k];
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                issue(SEQ_LSTEPS - 1 + LEAD);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (no LDS-DMA piece in flight when the wave ends)
+            return;
+        }
+    }
     // accumulators start from the residual x; the attention output tile 0 is requested with it
     f32x16 acc[NT];
     f32x16 at[NT]; // attention output tiles (B operand source of the out-projection): all requested here, so that
@@ -5624,14 +5791,7 @@ static int launch_linear(irs_ctx *ctx, const float *X, const float *W, const flo
         else if (full) hipLaunchKernelGGL((k_linear_ln<16, true, false>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((k_linear_ln<16, false, false>), grid, dim3(256), 0, s, a);
     } else {
-        static int n_cu = 0;
-        if (n_cu == 0) {
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess ||
-                hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-                n_cu = 256;
-        }
-        a.slots = n_cu * 4; // matches k_linear<.., 16, ..>'s launch bounds
+        a.slots = irs_cu_count() * 4; // matches k_linear<.., 16, ..>'s launch bounds
         const int ntm = (M + LIN_BM - 1) / LIN_BM, ntn = (N + LIN_BN - 1) / LIN_BN;
         // exact unit count when M is known here, its upper bound over any device-side M otherwise
         dim3 grid(m_dev ? ntm + (a.slots - 1) * (ntn - 1) : (ntm / a.slots) * a.slots + (ntm % a.slots) * ntn);
@@ -6401,9 +6561,10 @@ int irs_launch_decode(irs_ctx *ctx, const int64_t *seq, const int64_t *user, int
         hipLaunchKernelGGL(k_plan_fill, dim3((B + 3) / 4), dim3(256), 0, s, seq, pos, B, L, ctx->seq_off, ctx->seq_qrow, ctx->tok_row,
                            ctx->seq_padq);
     }
+    const int n_cu = r.seq ? irs_cu_count() : 0; // (the rounds of the sequence-resident launch: the plan's tail rule)
     if (r.seq)
         hipLaunchKernelGGL(k_plan_seq, dim3(1), dim3(1024), 0, s, ctx->seq_cnt, ctx->seq_off, ctx->seq_qrow, B, ctx->tile_seq,
-                           ctx->tile_idx, ctx->seq_row0, ctx->qrow_tile, ctx->n_wg_dev, B * SEQ_WG_TILES);
+                           ctx->tile_idx, ctx->seq_row0, ctx->qrow_tile, ctx->n_wg_dev, B * SEQ_WG_TILES, n_cu);
     launch_embed(c, pos, user);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     if (r_u_out) IRS_CHECK_HIP(ctx, hipMemcpyAsync(r_u_out, ctx->act_ru, sizeof(float) * B, hipMemcpyDeviceToDevice, s));
