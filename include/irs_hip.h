@@ -222,6 +222,32 @@ int irs_ce_forward(irs_ctx *ctx, const float *dev_xrows, const int64_t *dev_labe
 int irs_ce_grad_logits(irs_ctx *ctx, const float *dev_xrows, const int64_t *dev_labels0, const float *dev_lse, int32_t M,
                        float scale, float *dev_out, int64_t ld, void *stream);
 
+/* The whole backward of projection + cross entropy WITHOUT dL/dlogits (opt-in; replaces the autograd of nn.Linear +
+ * nn.CrossEntropyLoss as the reference runs it in IRSNN.train_batch, influentialRS.py:278-310, and Evaluator.train_batch,
+ * evaluator.py:53-68 -- and this library's own irs_ce_grad_logits + two GEMMs + column sum per row chunk).  With
+ *   G[m][j] = scale * (exp(logit_mj - lse[m]) - [j == label[m]]),   G[m][:] = 0 for ignored rows (label < 0):
+ *   dev_dx float [M, d]        = G W              always overwritten; an ignored row is exactly zero
+ *   dev_dw float [n_local, d]  (+)= G^T X         overwritten (accumulate == 0) or added to (accumulate != 0)
+ *   dev_db float [n_local]     (+)= colsum G      likewise
+ * G is never stored: an item-owned pass (dw, db) and a row-owned pass (dx) each recompute the logits tiles they need on the
+ * float32 matrix pipe and consume G from registers -- four GEMM-sized products where the chunked route has three, and no
+ * M x n_item traffic.  Labels >= n_item match no column, as in irs_ce_grad_logits.  dev_lse is irs_ce_forward's.
+ * `accumulate` lets a caller walk M > max_rows in row blocks and still write dw / db in place, once per block.
+ * project.weight / project.bias are read where they were bound (no finalisation, no workspace needed); the derived bf16
+ * catalog is marked stale exactly as irs_ce_forward / irs_ce_grad_logits do.  One device holds the whole catalog
+ * (IRS_E_UNSUPPORTED otherwise).  M > max_rows, null pointers, rows not 8-byte aligned and a scratch smaller than
+ * irs_ce_backward_scratch_bytes(M) (or not 16-byte aligned) return IRS_E_INVALID before any launch.
+ * dev_scratch is caller-owned, like the trunk's `saved` arena: it holds the partial outputs of a pass whose owned side has
+ * too few tiles to fill the device (small catalogs: dw / db partials per row group; few rows: dx partials per catalog
+ * group), never anything of order M x n_item: at most 64 MiB + 4 (M d + n_local d) bytes (not monotone in M: a caller
+ * that walks row blocks of several sizes asks for each).  The number of groups is a
+ * function of (M, n_local, d) alone and partials are added in group order; there are no float atomics: two identical calls
+ * give identical bits.  Nothing is allocated; all work goes on the caller's stream. */
+size_t irs_ce_backward_scratch_bytes(const irs_ctx *ctx, int32_t M); /* 0 for an invalid M */
+int irs_ce_backward(irs_ctx *ctx, const float *dev_xrows, const int64_t *dev_labels0, const float *dev_lse, int32_t M,
+                    float scale, int32_t accumulate, float *dev_dx, float *dev_dw, float *dev_db, void *dev_scratch,
+                    size_t scratch_bytes, void *stream);
+
 /* ---- native decoder trunk for training (opt-in; replaces the train-mode nn.TransformerDecoder autograd of
  *      InfluentialNet._decoding_autograd, influentialRS.py:157-200 as called by IRSNN.train_batch :278-310, and of
  *      SampleNet.decoding, uRS.py:52-64, as called by Evaluator.train_batch, evaluator.py:53-92) ------------------

@@ -61,6 +61,9 @@ SIGNATURES = {
                                      c_void_p, c_void_p]),
     "irs_ce_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "irs_ce_grad_logits": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, ctypes.c_float, c_void_p, c_int64, c_void_p]),
+    "irs_ce_backward_scratch_bytes": (c_size_t, [c_void_p, c_int32]),
+    "irs_ce_backward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_size_t, c_void_p]),
     "irs_build_eval_batch": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64,
                                        c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "irs_train_saved_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),

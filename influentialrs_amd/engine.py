@@ -247,6 +247,36 @@ class Engine:
                    int(out.stride(0)))
         return out
 
+    def ce_backward_scratch_bytes(self, M: int) -> int:
+        n = self.lib.irs_ce_backward_scratch_bytes(self.h, M)
+        if n == 0:
+            raise IrsError(f"ce_backward: no scratch size for M={M} (need 1 <= M <= max_rows={self.max_rows})")
+        return n
+
+    def ce_backward(self, xrows: torch.Tensor, labels0: torch.Tensor, lse: torch.Tensor, scale: float, accumulate: bool,
+                    dx: torch.Tensor, dw: torch.Tensor, db: torch.Tensor, scratch: torch.Tensor):
+        """dx[M, d] = G W (overwritten), dw[n_local, d] (+)= G^T X, db[n_local] (+)= colsum G with
+        G = scale * (softmax(logits) - onehot(label)), ignored rows 0, never stored (irs_ce_backward).  All three are
+        written in place; scratch: uint8, at least ce_backward_scratch_bytes(M) bytes."""
+        xrows = self._dev(xrows, torch.float32)
+        labels0 = self._dev(labels0, torch.int64)
+        lse = self._dev(lse, torch.float32)
+        if xrows.dim() != 2 or xrows.shape[1] != self.d:
+            raise IrsError(f"ce_backward: rows of shape {tuple(xrows.shape)}, expected [M, {self.d}]")
+        M = xrows.shape[0]
+        if tuple(labels0.shape) != (M,) or tuple(lse.shape) != (M,):
+            raise IrsError(f"ce_backward: labels {tuple(labels0.shape)} / lse {tuple(lse.shape)}, expected [{M}]")
+        dx = self._inplace(dx, torch.float32, "ce_backward dx")
+        dw = self._inplace(dw, torch.float32, "ce_backward dw")
+        db = self._inplace(db, torch.float32, "ce_backward db")
+        scratch = self._inplace(scratch, torch.uint8, "ce_backward scratch")
+        if tuple(dx.shape) != (M, self.d) or tuple(dw.shape) != (self.n_local, self.d) or tuple(db.shape) != (self.n_local,):
+            raise IrsError(f"ce_backward: dx {tuple(dx.shape)} / dw {tuple(dw.shape)} / db {tuple(db.shape)}, expected "
+                           f"{(M, self.d)} / {(self.n_local, self.d)} / {(self.n_local,)}")
+        self._call(self.lib.irs_ce_backward, _ptr(xrows), _ptr(labels0), _ptr(lse), M, float(scale), 1 if accumulate else 0,
+                   _ptr(dx), _ptr(dw), _ptr(db), _ptr(scratch), scratch.numel())
+        return dx, dw, db
+
     # ------------------------------------------------------------------ native training trunk
     def train_saved_bytes(self, B: int, L: int) -> int:
         n = self.lib.irs_train_saved_bytes(self.h, B, L)

@@ -27,6 +27,17 @@ class HipBackend:
         self.rank, self.world = 0, 1
         self._stale = False  # a training entry point ran since the derived weights were built
         self.comm: Optional[Comm] = None  # collectives below the C ABI (item-sharded search loops)
+        self.ce_backward = ce_backward_default()
+
+    @property
+    def ce_backward(self) -> str:
+        """Backward of projection + cross entropy: "chunked" (irs_ce_grad_logits per row chunk + torch GEMMs) or "fused"
+        (irs_ce_backward: no dL/dlogits buffer).  Default from IRS_CE_BACKWARD."""
+        return self._ce_backward
+
+    @ce_backward.setter
+    def ce_backward(self, v: str):
+        self._ce_backward = check_ce_backward(v)
 
     def __deepcopy__(self, memo):
         """copy.deepcopy(net): the copy gets its own backend and builds its own engine on first use (an engine is a
@@ -38,6 +49,7 @@ class HipBackend:
         new.mask_mode, new.sweep = self.mask_mode, self.sweep
         new.engine, new._fp, new.group, new._stale, new.comm = None, None, None, False, None
         new.rank, new.world = self.rank, self.world
+        new._ce_backward = self._ce_backward
         return new
 
     def set_sharding(self, rank: int, world: int, drop_full: bool = True):
@@ -128,7 +140,8 @@ class _ProjectCE(torch.autograd.Function):
     """mean over valid rows of CrossEntropy(project(x), label) -- nn.Linear + nn.CrossEntropyLoss of the reference's
     train_batch (influentialRS.py:278-310, evaluator.py:53-68) -- without the [M, n_item] logits: forward =
     irs_ce_forward (float32 log-sum-exp sweep + label gather), backward = irs_ce_grad_logits per row chunk (the
-    softmax gradient written once by the sweep's epilogue) followed by the two plain GEMMs dX = G W, dW = G^T X."""
+    softmax gradient written once by the sweep's epilogue) followed by the two plain GEMMs dX = G W, dW = G^T X -- or,
+    with backend.ce_backward == "fused", irs_ce_backward per block of ROWS rows, which never stores dL/dlogits."""
     ROWS = 8192          # rows per engine call
     CHUNK_BYTES = 1 << 30  # budget of the dL/dlogits chunk
 
@@ -163,6 +176,18 @@ class _ProjectCE(torch.autograd.Function):
         if ctx.n_valid == 0:
             return torch.zeros_like(xd), torch.zeros_like(weight), torch.zeros(N, dtype=torch.float32, device=xd.device), None, None, None
         eng = ctx.backend.get(1, min(M, _ProjectCE.ROWS), for_training=True)
+        if ctx.backend.ce_backward == "fused":
+            dx = torch.empty_like(xd)
+            dW = torch.empty_like(weight)
+            db = torch.empty(N, dtype=torch.float32, device=xd.device)
+            # (the size follows the split of each pass, which is not monotone in the row count: ask for every block size used)
+            blocks = {min(M, _ProjectCE.ROWS), M % _ProjectCE.ROWS or _ProjectCE.ROWS} if M > _ProjectCE.ROWS else {M}
+            scratch = torch.empty(max(eng.ce_backward_scratch_bytes(m) for m in blocks), dtype=torch.uint8, device=xd.device)
+            for c0 in range(0, M, _ProjectCE.ROWS):
+                c1 = min(M, c0 + _ProjectCE.ROWS)
+                eng.ce_backward(xd[c0:c1], labels0[c0:c1], lse[c0:c1], 1.0, c0 > 0, dx[c0:c1], dW, db, scratch)
+            sc = (g.double() / tot[1]).to(torch.float32)
+            return dx.mul_(sc), dW.mul_(sc), db.mul_(sc), None, None, None
         mc = max(32, min(_ProjectCE.ROWS, M, (_ProjectCE.CHUNK_BYTES // (4 * N)) // 32 * 32))
         G = torch.empty((mc, N), dtype=torch.float32, device=xd.device)
         dx = torch.empty_like(xd)
@@ -183,6 +208,21 @@ def project_ce(x: torch.Tensor, project: nn.Linear, labels0: torch.Tensor, backe
     # (grad mode is off inside Function.forward: whether this loss can lead to a weight update is decided here)
     may_update = torch.is_grad_enabled() and (x.requires_grad or project.weight.requires_grad or project.bias.requires_grad)
     return _ProjectCE.apply(x, project.weight, project.bias, labels0, backend, may_update)
+
+
+CE_BACKWARDS = ("chunked", "fused")
+
+
+def ce_backward_default() -> str:
+    """The projection + cross-entropy backward a new network selects: IRS_CE_BACKWARD = chunked (default) or fused
+    (include/irs_hip.h irs_ce_backward).  Any other value raises."""
+    return check_ce_backward(os.environ.get("IRS_CE_BACKWARD", "chunked"), "IRS_CE_BACKWARD")
+
+
+def check_ce_backward(v, what: str = "ce_backward") -> str:
+    if v not in CE_BACKWARDS:
+        raise ValueError(f"{what} must be one of {CE_BACKWARDS}, got {v!r}")
+    return v
 
 
 TRUNKS = ("torch", "hip")

@@ -82,6 +82,16 @@ class InfluentialNet(nn.Module):
     def trunk(self, v: str):
         self._trunk = check_trunk(v)
 
+    @property
+    def ce_backward(self) -> str:
+        """Backward of projection + cross entropy: "chunked" (dL/dlogits per row chunk + torch GEMMs) or "fused"
+        (include/irs_hip.h irs_ce_backward: no dL/dlogits buffer).  Default from IRS_CE_BACKWARD."""
+        return self._hip.ce_backward
+
+    @ce_backward.setter
+    def ce_backward(self, v: str):
+        self._hip.ce_backward = v
+
     # ---- checkpoint contract: accept nn.DataParallel's "module." prefix (pipeline.py:140-142)
     def load_state_dict(self, state_dict, strict=True, **kw):
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}
