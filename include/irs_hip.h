@@ -315,6 +315,8 @@ int irs_merge_topk_keys(irs_ctx *ctx, const uint64_t *dev_keys_in, int32_t W, in
  *  dev_seq int64 [B, L], dev_target / dev_label int64 [B] out
  *  dev_raw int64 [B, raw_len] out, right-aligned zero-padded raw windows, dev_raw_n int32 [B] their lengths (both may be NULL)
  *  dev_status int32 [B] in/out (may be NULL): IRS_ROW_NO_CANDIDATE is OR-ed in when no target was found
+ *               (the catalog or the pool is contained in the raw window); target[b] is then 0
+ * A user without events has label 0 and an empty raw window; a user with one event has that label and an empty window.
  * Needs L - gap_len - 1 >= 1 (the reference's slice arithmetic is only meaningful there). */
 int irs_build_eval_batch(irs_ctx *ctx, const int64_t *dev_items, const int64_t *dev_offsets, int32_t B, int32_t raw_len,
                          int32_t gap_len, const int64_t *dev_targets_in, const int64_t *dev_pool, int64_t n_pool,
@@ -331,7 +333,11 @@ int irs_build_eval_batch(irs_ctx *ctx, const int64_t *dev_items, const int64_t *
  *  dev_seq  int64 [B, L] in/out     dev_hep int32 [B] in/out
  *  dev_val  float [B, k], dev_ids0 int64 [B, k]: merged top-k (descending)
  *  dev_paths float [B, path_ld] out (ids stored as float32 like the reference, :407)
- *  dev_status int32 [B] in/out: IRS_ROW_NO_CANDIDATE is OR-ed in */
+ *  dev_status int32 [B] in/out: IRS_ROW_NO_CANDIDATE is OR-ed in
+ * The list of a row ends at its first negative id0.  A row without a survivor (IRS_ROW_NO_CANDIDATE) gets
+ * paths[b, step] = 0 and keeps its window, its hep and its earlier path entries.  Other rows, other columns of
+ * dev_paths, dev_val and dev_ids0 are not written.  step >= path_ld, k < 1, B < 1 and null pointers return
+ * IRS_E_INVALID, sample != 0 with sample_k outside [1, IRS_MAX_SAMPLE_K] IRS_E_UNSUPPORTED, all before any launch. */
 int irs_path_step(irs_ctx *ctx, int64_t *dev_seq, int32_t *dev_hep, int32_t B, const float *dev_val,
                   const int64_t *dev_ids0, int32_t k, int32_t step, float *dev_paths, int32_t path_ld, int32_t sample,
                   int32_t sample_k, uint64_t seed, int32_t *dev_status, void *stream);
@@ -347,12 +353,25 @@ int irs_generate_paths(irs_ctx *ctx, int64_t *dev_seq, const int64_t *dev_user, 
 
 /* ---- beam search over persuasion paths (BUILD-DEFINED: the reference has no beam
  *      search -- SURVEY fact 4; BASELINE.json config 5).  Beam width W <= 32, path
- *      length P <= 64.  W == 1 is the greedy search of irs_generate_paths id for id.
+ *      length P <= 64.  W == 1 is the greedy search of irs_generate_paths id for id, for every row that has a
+ *      candidate at every step.  The two differ on a row that runs out of candidates (IRS_ROW_NO_CANDIDATE on both
+ *      sides; the reference raises IndexError there, so nothing downstream may rely on either): irs_path_step /
+ *      irs_generate_paths keep the earlier path entries and write 0 at the failed step, window and hep unchanged;
+ *      the beam step turns the only beam into a dead beam (below): the whole path is zeroed and its score is -inf.
  * One step for B users x W beams given each beam row's merged top-k (descending) and,
  * for W > 1, its row-wise (max, sum exp) over the whole catalog:
  *   candidates = first W window-survivors of every live beam, scored
  *   cum + (val - max - log(sumexp)); best W by (score desc, parent asc, rank asc) survive.
- * State is ping-ponged: *_in -> *_out ([B, W, ...] row-major; cum = -inf marks a dead beam). */
+ * State is ping-ponged: *_in -> *_out ([B, W, ...] row-major; cum = -inf marks a dead beam).
+ * A beam's list ends at its first negative id0.  Dead input beams contribute nothing, whatever their lists hold.
+ * When a user has fewer than W candidates in all, its trailing output beams are dead: cum = -inf, an all-zero path,
+ * and the window and hep of that user's INPUT beam 0 (a well-formed window to decode; never selected again).
+ * A live output beam copies paths_in[parent, 0 .. step) and writes the item at [step] and 0 after it, so whatever
+ * paths_in holds at and beyond `step` is dropped.
+ * dev_status int32 [B] in/out: IRS_ROW_NO_CANDIDATE is OR-ed into a user's word when ANY live input beam of that user
+ * has no survivor, even if the user's other beams still fill all W output beams; a dead input beam never sets it.
+ * W < 1, k < 1, step >= P, null pointers and W > 1 without dev_lse_max / dev_lse_sum return IRS_E_INVALID, W > 32
+ * IRS_E_UNSUPPORTED, all before any launch. */
 int irs_beam_step(irs_ctx *ctx, const int64_t *dev_seq_in, const int32_t *dev_hep_in, const double *dev_cum_in,
                   const float *dev_paths_in, const float *dev_val, const int64_t *dev_ids0, const float *dev_lse_max,
                   const float *dev_lse_sum, int32_t B, int32_t W, int32_t k, int32_t step, int32_t P,

@@ -19,6 +19,13 @@ def make_engine(cfg, sd_np, *, evaluator=False, max_rows=64, max_seqs=0, rank=0,
     return eng
 
 
+def path_only_engine(max_len, *, n_item=64, max_k=128, device="cuda:0"):
+    """Engine with a 1-layer dummy decoder and the window length a case needs, for tests of the path-search kernels
+    alone (path / beam step, pack / merge, evaluation batch): they take their inputs from the caller, not from a model."""
+    cfg = synth.make_config("tiny", n_item=n_item, emb_dim=16, n_heads=2, n_layers=1, max_len=max_len, ffn_dim=8, n_user=2)
+    return make_engine(cfg, synth.irn_state_dict(cfg, seed=1), max_rows=64, max_seqs=1, max_k=max_k, device=device)
+
+
 def scoring_only_engine(n_item, d, W, b, *, max_rows=64, rank=0, world=1, max_k=100, device="cuda:0"):
     """Engine with a 1-layer dummy decoder, for tests of the scoring kernels alone."""
     nh = d // 32 if d % 32 == 0 else 1

@@ -44,7 +44,7 @@ def test_beam1_equals_greedy_and_reference(golden, use_graph, gname, cfgname):
 
 
 @pytest.mark.parametrize("cfgname,beam,P,use_graph", [("tiny", 4, 7, False), ("tiny", 4, 6, True), ("tiny", 32, 5, False),
-                                                      ("default", 3, 5, True)])
+                                                      ("default", 3, 5, True), ("tiny", 1, 6, False), ("tiny", 1, 6, True)])
 def test_beam_matches_cpu_restatement(oracle, cfgname, beam, P, use_graph):
     cfg, sd, seqs, users, targets = _setup(cfgname, 3)
     B, L = seqs.shape
@@ -63,7 +63,7 @@ def test_beam_matches_cpu_restatement(oracle, cfgname, beam, P, use_graph):
     if beam == 1:  # the greedy entry point (irs_generate_paths) walks the same paths
         seq2 = torch.from_numpy(seqs).cuda()
         hep2 = torch.full((B,), L - 2, dtype=torch.int32, device="cuda")
-        gp = eng.generate_paths(seq2, torch.from_numpy(users).cuda(), hep2, P, use_graph=not graph)
+        gp = eng.generate_paths(seq2, torch.from_numpy(users).cuda(), hep2, P, use_graph=not use_graph)
         gp = (gp[0] if isinstance(gp, tuple) else gp).cpu().numpy()
         assert np.array_equal(gp, paths[:, 0])
     # scores are sorted, windows end with the path
