@@ -1706,9 +1706,27 @@ __device__ __forceinline__ x6_u32x4 x6_rd_sync(unsigned int base) {
     return v;
 }
 
+// The IRN target column of one (sequence, head) as float32, rebuilt from the float16 planes of the images: the target key's eight
+// channels of this lane and its eight values of the target V row.  The two blocks of a wave normally belong to one sequence: the
+// second block of a head finds what the first left here (seq = the sequence the values belong to, -1: none yet for this head).
+struct SeqTarget {
+    int seq;
+    float k[8], v[8];
+};
+// the masked keys of block qb's diagonal tile (bit = key 16 qb + bit) of a sequence of L tokens with its one pad at pq (-1: none)
+__device__ __forceinline__ unsigned int seq_diag_mask(int L, int qb, bool tgt, int pq) {
+    // masked keys of the diagonal tile: beyond the sequence, the IRN target column where there is one (tgt; added separately), the one pad
+    unsigned int pm = 0;
+    const int k0_ = 16 * qb;
+    if (L <= k0_) return 0; // (a block beyond the sequence computes nothing)
+    if (L - k0_ < 16) pm = (0xFFFFu << (L - k0_)) & 0xFFFFu;
+    if (tgt && L - 1 >= k0_ && L - 1 < k0_ + 16) pm |= 1u << (L - 1 - k0_); // (the last key is the target column only where the window has a target item: without one it is the last history item, a causal key like any other -- k_attn_row's rule)
+    if (pq >= k0_ && pq < k0_ + 16) pm |= 1u << (pq - k0_);
+    return pm;
+}
 // one 16-query block of the sequence-resident kernel's attention (defined behind k_attn16h, whose mathematics it shares)
-__device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, int PL, int L, int qb, bool irn, float tgt_add, bool tgt_ok,
-                                               int pq, const float *qscr, float4 *of, bool store);
+__device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, int PL, int L, int qb, unsigned int pm_diag, float tgt_add,
+                                               bool tgt_ok, int pq, const float *qscr, float4 *of, bool store, int seq, SeqTarget &tg);
 // k and q of the sequence-resident attention are split into float16 planes as they are.  (Measured, profiles/r05/README.md: planes
 // of 16 k and 16 q -- low planes of elements below 2^-3 are subnormal float16, 2^-25 absolute instead of 2^-22 relative -- change
 // nothing: rows against the two-kernel path max 1.88e-5 / mean 3.98e-7 with the factor, 1.87e-5 / 4.0e-7 without, and four more
@@ -1793,6 +1811,10 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     int sh_off[2] = {0, 0};
     float sh_ru[2] = {0.f, 0.f};
     bool sh_tgt[2] = {false, false};
+    // what the attention of a block needs beside these and does not change from head to head or layer to layer, once per wave in
+    // scalar registers: the diagonal tile's masked keys (seq_diag_mask) and the target column's additive term
+    unsigned int sh_pm[2] = {0, 0};
+    float sh_tadd[2] = {0.f, 0.f};
     if constexpr (SEQ) {
         if ((int)blockIdx.x >= a.n_wg_dev[0]) return;
         const int tg_ = blockIdx.x * NW + wave;
@@ -1810,6 +1832,8 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                 sh_ru[h] = irn_ ? a.r_u[b_] : 0.f;
                 sh_tgt[h] = irn_ && a.seq[(int64_t)b_ * a.L + a.L - 1] != 0;
                 sh_pb[h] = (__builtin_amdgcn_readfirstlane(a.seq_qrow[b_]) - off_) >> 4;
+                sh_pm[h] = seq_diag_mask(sh_cnt[h], sh_qb[h], sh_tgt[h], sh_pq[h]);
+                sh_tadd[h] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, irn_ ? (1.0f - sh_ru[h]) * 1.4426950408889634f : 0.f)));
             }
         }
     }
@@ -2576,14 +2600,16 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             asm volatile("" ::: "memory");
             X6_PH(1)
             if (!(SEQ_EXP & 1)) {
+                SeqTarget tg; // (this head's images: what the first block of a sequence rebuilds, its mirror block reuses)
+                tg.seq = -1;
 #pragma unroll 1
                 for (int blk = 0; blk < 2; ++blk) {
                     const int b_ = blk ? sh_b[1] : sh_b[0], qb_ = blk ? sh_qb[1] : sh_qb[0], row0_ = blk ? sh_row0[1] : sh_row0[0];
                     if (b_ >= 0 && last_rt && qb_ != (blk ? sh_pb[1] : sh_pb[0])) continue; // (the model's last layer: only the consumed token's block)
                     // (an empty half: block index beyond a zero-length sequence -> zeros, the layer body multiplies whole tiles)
-                    seq_attn_block(Kimg + row0_ * 32, Vimg + row0_ * 64, 16384, b_ >= 0 ? (blk ? sh_cnt[1] : sh_cnt[0]) : 0, b_ >= 0 ? qb_ : 16, irn_,
-                                   irn_ ? (1.0f - (blk ? sh_ru[1] : sh_ru[0])) * 1.4426950408889634f : 0.f, blk ? sh_tgt[1] : sh_tgt[0],
-                                   blk ? sh_pq[1] : sh_pq[0], scr + 16 * blk * 36, ao4 + (size_t)h * 4 * 64 + 16 * blk, true);
+                    seq_attn_block(Kimg + row0_ * 32, Vimg + row0_ * 64, 16384, b_ >= 0 ? (blk ? sh_cnt[1] : sh_cnt[0]) : 0, b_ >= 0 ? qb_ : 16,
+                                   blk ? sh_pm[1] : sh_pm[0], blk ? sh_tadd[1] : sh_tadd[0], blk ? sh_tgt[1] : sh_tgt[0],
+                                   blk ? sh_pq[1] : sh_pq[0], scr + 16 * blk * 36, ao4 + (size_t)h * 4 * 64 + 16 * blk, true, b_, tg);
                 }
             }
             asm volatile("" ::: "memory");
@@ -3432,7 +3458,7 @@ __global__ void __launch_bounds__(64 * SB_NW) k_block_small16(SmallBlockArgs a) 
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int j = 16 * (ahalf + 2 * i) + 4 * gq + r;
-                    const bool ok = j <= qi && j < aL && j != pq && !(irn && j == aL - 1);
+                    const bool ok = j <= qi && j < aL && j != pq && !(tgt_ok && j == aL - 1);
                     const float v = ok ? sacc[i][r] : -INFINITY;
                     sacc[i][r] = v;
                     mx = fmaxf(mx, v);
@@ -4384,18 +4410,18 @@ __global__ void __launch_bounds__(256) k_attn_mfma(const float *__restrict__ qkv
             Vs[idx] = vv;
         }
     }
+    // the target (original position Lmax-1, never a pad when present) is the last row of the sequence
+    const bool tgt_ok = irn && (seq[(int64_t)b * Lmax + Lmax - 1] != 0);
     for (int kb = wave; kb < NB; kb += 4) { // masked-key bitmask of each key block
         int j = kb * 32 + lq;
         const int64_t jr = base + (j < L ? j : L - 1);
-        bool masked = (j >= L) || (seq[tok_row ? (int64_t)tok_row[jr] : jr] == 0) || (irn && j == L - 1);
+        bool masked = (j >= L) || (seq[tok_row ? (int64_t)tok_row[jr] : jr] == 0) || (tgt_ok && j == L - 1); // (the last key is the target column only where the window has a target item: without one it is the last history item, a causal key like any other -- k_attn_row's rule)
         unsigned long long bal = __ballot(masked);
         if (lane == 0) padbits[kb] = (unsigned int)bal;
     }
     __syncthreads();
     const float add_allowed = irn ? r_u[b] : 0.f;
     const float scale = 1.0f / sqrtf((float)hd);
-    // the target (original position Lmax-1, never a pad when present) is the last row of the sequence
-    const bool tgt_ok = irn && (seq[(int64_t)b * Lmax + Lmax - 1] != 0);
 
     for (int pass = 0; pass < 2; ++pass) {
         const int qb = pass == 0 ? wave : NB - 1 - wave;
@@ -4700,9 +4726,10 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) k_attn16(const float
     // masked-key bitmask of each 32-key block.  A packed sequence holds no pads except possibly its pos token
     // (index padq[b], recorded by the plan): no global loads on that path.
     const int pq = padq ? padq[b] : -1;
+    const bool tgt_ok = irn && (seq[(int64_t)b * Lmax + Lmax - 1] != 0);
     for (int kb = wave; kb < (L + 31) / 32; kb += NW) {
         const int j = kb * 32 + (lane & 31);
-        bool masked = (j >= L) || (irn && j == L - 1);
+        bool masked = (j >= L) || (tgt_ok && j == L - 1); // (the last key is the target column only where the window has a target item: without one it is the last history item, a causal key like any other -- k_attn_row's rule)
         if (padq) masked = masked || (j == pq);
         else masked = masked || (seq[base + (j < L ? j : L - 1)] == 0);
         const unsigned long long bal = __ballot(masked);
@@ -4735,7 +4762,6 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) k_attn16(const float
     const float LOG2E = 1.4426950408889634f;
     const float tgt_add = irn ? (1.0f - r_u[b]) * LOG2E : 0.f;
     const float scale = LOG2E / sqrtf((float)HD);
-    const bool tgt_ok = irn && (seq[(int64_t)b * Lmax + Lmax - 1] != 0);
 
     while (qb_next >= 0) {
         const int qb = qb_next;
@@ -5057,9 +5083,10 @@ __global__ void __launch_bounds__(64 * NW, 3) k_attn16h(const float *__restrict_
     int qb_next = mine ? 31 - __builtin_clz(mine) : -1;
     if (qb_next >= 0) load_q(qb_next, qn0, qn1);
     const int pq = pq_;
+    const bool tgt_ok = irn && (last_id != 0);
     for (int kb = wave; kb < (L + 31) / 32; kb += NW) {
         const int j = kb * 32 + (lane & 31);
-        bool masked = (j >= L) || (irn && j == L - 1);
+        bool masked = (j >= L) || (tgt_ok && j == L - 1); // (the last key is the target column only where the window has a target item: without one it is the last history item, a causal key like any other -- k_attn_row's rule)
         if (padq) masked = masked || (j == pq);
         else masked = masked || (seq[base + (j < L ? j : L - 1)] == 0);
         const unsigned long long bal = __ballot(masked);
@@ -5070,7 +5097,6 @@ __global__ void __launch_bounds__(64 * NW, 3) k_attn16h(const float *__restrict_
     const float LOG2E = 1.4426950408889634f;
     const float tgt_add = irn ? (1.0f - ru_) * LOG2E : 0.f;
     const float scale = LOG2E / sqrtf((float)HD);
-    const bool tgt_ok = irn && (last_id != 0);
     // this lane's addresses: K row read (key = 16 kt + lq, chunk gq), V transposed read (block row (lane & 15) >> 2, columns
     // 16 ct + 4 (lane & 3) ..)
     const int tq = (lane & 15) >> 2, tp = lane & 3;
@@ -5294,8 +5320,10 @@ __global__ void __launch_bounds__(64 * NW, 3) k_attn16h(const float *__restrict_
 // based at the sequence's first row.  The query rows come from the wave's q scratch ([16 rows][36] float32), the normalised
 // output goes to the fragment-major scratch tile (`of` = the tile's float4 base + 16 blk: lane (lq, gq) writes token column lq);
 // query rows beyond the sequence store zeros (the layer body multiplies whole tiles: they must stay finite).
-__device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, int PL, int L, int qb, bool irn, float tgt_add, bool tgt_ok,
-                                               int pq, const float *qscr, float4 *of, bool store) {
+// pm_diag = the masked keys of the diagonal tile and tgt_add come from the caller, which computes them once per wave
+// (seq_diag_mask); `seq` / `tg`: the target column's operands are rebuilt only when `tg` holds another sequence's (SeqTarget).
+__device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, int PL, int L, int qb, unsigned int pm_diag, float tgt_add,
+                                               bool tgt_ok, int pq, const float *qscr, float4 *of, bool store, int seq, SeqTarget &tg) {
     typedef __attribute__((ext_vector_type(4))) float f32x4;
     constexpr int HD = 32, MAXT = 16;
     int lane = threadIdx.x & 63;
@@ -5353,14 +5381,6 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
         sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, Q[0], sa, 0, 0, 0);
         if (SEQ_KQ_SCALE != 1.0f) sa *= 1.0f / (SEQ_KQ_SCALE * SEQ_KQ_SCALE);
     };
-    // masked keys of the diagonal tile: beyond the sequence, the IRN target column (added separately), the one pad
-    unsigned int pm_diag = 0;
-    {
-        const int k0_ = 16 * qb;
-        if (L - k0_ < 16) pm_diag = (0xFFFFu << (L - k0_)) & 0xFFFFu;
-        if (irn && L - 1 >= k0_ && L - 1 < k0_ + 16) pm_diag |= 1u << (L - 1 - k0_);
-        if (pq >= k0_ && pq < k0_ + 16) pm_diag |= 1u << (pq - k0_);
-    }
     auto mask_diag = [&](int kt, f32x4 &sa) __attribute__((always_inline)) {
         const unsigned int pmk = pm_diag >> (4 * gq);
         const int qlim = lq - 4 * gq;
@@ -5407,32 +5427,29 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
     }
     // ---- the IRN target column (key L - 1, +1.0 where every other visible key carries +r_u, visible to every query)
     float st = -INFINITY;
-    float vt[8];
     if (tgt_ok) {
-        const int jt = L - 1;
-        const char *kr = Kc + jt * 128;
-        const int sw = (jt >> 1) & 7;
-        const x6_f16x8 th = *reinterpret_cast<const x6_f16x8 *>(kr + ((gq ^ sw) << 4));
-        const x6_f16x8 tl = *reinterpret_cast<const x6_f16x8 *>(kr + (((4 + gq) ^ sw) << 4));
-        const float4 k0 = make_float4((float)th[0] + (float)tl[0], (float)th[1] + (float)tl[1], (float)th[2] + (float)tl[2], (float)th[3] + (float)tl[3]);
-        const float4 k1 = make_float4((float)th[4] + (float)tl[4], (float)th[5] + (float)tl[5], (float)th[6] + (float)tl[6], (float)th[7] + (float)tl[7]);
-        float part = qf[0] * k0.x;
-        part = __fmaf_rn(qf[1], k0.y, part);
-        part = __fmaf_rn(qf[2], k0.z, part);
-        part = __fmaf_rn(qf[3], k0.w, part);
-        part = __fmaf_rn(qf[4], k1.x, part);
-        part = __fmaf_rn(qf[5], k1.y, part);
-        part = __fmaf_rn(qf[6], k1.z, part);
-        part = __fmaf_rn(qf[7], k1.w, part);
-        st = quad16_sum(part) * (1.0f / (SEQ_KQ_SCALE * SEQ_KQ_SCALE)) + tgt_add;
+        if (tg.seq != seq) { // (wave-uniform) the first block of this sequence under this head: key L - 1 and its V row from their planes
+            tg.seq = seq;
+            const int jt = L - 1;
+            const char *kr = Kc + jt * 128;
+            const int sw = (jt >> 1) & 7;
+            const x6_f16x8 th = *reinterpret_cast<const x6_f16x8 *>(kr + ((gq ^ sw) << 4));
+            const x6_f16x8 tl = *reinterpret_cast<const x6_f16x8 *>(kr + (((4 + gq) ^ sw) << 4));
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-            typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-            const char *vr = Vp + jt * 64 + ((((2 * ct + (gq >> 1)) ^ (((jt >> 2) & 1) << 1))) << 4) + 8 * (gq & 1);
-            const f16x4 b0 = *reinterpret_cast<const f16x4 *>(vr), b1 = *reinterpret_cast<const f16x4 *>(vr + PL);
+            for (int e = 0; e < 8; ++e) tg.k[e] = (float)th[e] + (float)tl[e];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) vt[4 * ct + r] = (float)b0[r] + (float)b1[r];
+            for (int ct = 0; ct < 2; ++ct) {
+                typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
+                const char *vr = Vp + jt * 64 + ((((2 * ct + (gq >> 1)) ^ (((jt >> 2) & 1) << 1))) << 4) + 8 * (gq & 1);
+                const f16x4 b0 = *reinterpret_cast<const f16x4 *>(vr), b1 = *reinterpret_cast<const f16x4 *>(vr + PL);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) tg.v[4 * ct + r] = (float)b0[r] + (float)b1[r];
+            }
         }
+        float part = qf[0] * tg.k[0];
+#pragma unroll
+        for (int e = 1; e < 8; ++e) part = __fmaf_rn(qf[e], tg.k[e], part);
+        st = quad16_sum(part) * (1.0f / (SEQ_KQ_SCALE * SEQ_KQ_SCALE)) + tgt_add;
     }
     mx = quad16_max(mx);
     float m = fmaxf(mx, st);
@@ -5452,47 +5469,52 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
         const float pt = __builtin_amdgcn_exp2f(st - m);
         l = (gq == 0) ? pt : 0.f;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) ot[e] = pt * vt[e];
+        for (int e = 0; e < 8; ++e) ot[e] = pt * tg.v[e];
     }
-#pragma unroll
-    for (int kp = 0; kp < MAXT / 2; ++kp) {
+    // V rows of a tile pair: row r = 32 kp + 4 gq + tq (+ 16 for the pair's second tile), 16-byte chunk (2 ct + (tp >> 1)) ^ swizzle with
+    // swizzle = ((r >> 2) & 1) << 1 = (gq & 1) << 1 for every pair -- so ct = 1 is ct = 0 with bit 5 of the offset flipped, and
+    // every read of the block is one of two lane addresses plus a constant
+    const int vo_ = (4 * gq + tq) * 64 + ((((tp >> 1) ^ ((gq & 1) << 1))) << 4) + 8 * (tp & 1);
+    const char *const vb[2] = {Vp + vo_, Vp + (vo_ ^ 32)};
+    // one pair of key tiles; on1 (wave-uniform) = the pair's second tile exists: one that does not contributes p = 0 and reads
+    // nothing past the image
+    auto pv_pair = [&](int kp, bool on1) __attribute__((always_inline)) {
         const int k0t = 2 * kp, k1t = 2 * kp + 1;
-        const bool on0 = k0t <= qb, on1 = k1t <= qb;
-        if (on0 || on1) { // wave-uniform
-            float pa[8];
+        float pa[8];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                pa[r] = on0 ? __builtin_amdgcn_exp2f(sacc[k0t][r] - m) : 0.f;
-                pa[4 + r] = on1 ? __builtin_amdgcn_exp2f(sacc[k1t][r] - m) : 0.f;
-                l += pa[r] + pa[4 + r];
-            }
-            x6_f16x8 P[2];
-            attn_split8h(pa, P);
-            const int r0 = k0t * 16 + 4 * gq + tq, r1 = r0 + 16;
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct) {
-                const int o0 = r0 * 64 + ((((2 * ct + (tp >> 1)) ^ (((r0 >> 2) & 1) << 1))) << 4) + 8 * (tp & 1);
-                const int o1 = r1 * 64 + ((((2 * ct + (tp >> 1)) ^ (((r1 >> 2) & 1) << 1))) << 4) + 8 * (tp & 1);
-                x6_f16x8 V[2];
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    const attn_s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) attn_s16x4 *)(Vp + p * PL + o0));
-                    attn_s16x4 a1 = {0, 0, 0, 0};
-                    if (on1) a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) attn_s16x4 *)(Vp + p * PL + o1));
-                    typedef __attribute__((ext_vector_type(8))) short s16x8;
-                    const s16x8 both = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-                    V[p] = __builtin_bit_cast(x6_f16x8, both);
-                }
-                f32x4 oo = o[kp & 1][ct];
-                oo = __builtin_amdgcn_mfma_f32_16x16x32_f16(V[0], P[1], oo, 0, 0, 0);
-                oo = __builtin_amdgcn_mfma_f32_16x16x32_f16(V[1], P[0], oo, 0, 0, 0);
-                oo = __builtin_amdgcn_mfma_f32_16x16x32_f16(V[0], P[0], oo, 0, 0, 0);
-                o[kp & 1][ct] = oo;
-            }
+        for (int r = 0; r < 4; ++r) {
+            pa[r] = __builtin_amdgcn_exp2f(sacc[k0t][r] - m);
+            pa[4 + r] = on1 ? __builtin_amdgcn_exp2f(sacc[k1t][r] - m) : 0.f;
+            l += pa[r] + pa[4 + r];
         }
+        x6_f16x8 P[2];
+        attn_split8h(pa, P);
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+            x6_f16x8 V[2];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const char *va = vb[ct] + p * PL + kp * 2048;
+                const attn_s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) attn_s16x4 *)(va));
+                attn_s16x4 a1 = {0, 0, 0, 0};
+                if (on1) a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) attn_s16x4 *)(va + 1024));
+                typedef __attribute__((ext_vector_type(8))) short s16x8;
+                const s16x8 both = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+                V[p] = __builtin_bit_cast(x6_f16x8, both);
+            }
+            f32x4 oo = o[kp & 1][ct];
+            oo = __builtin_amdgcn_mfma_f32_16x16x32_f16(V[0], P[1], oo, 0, 0, 0);
+            oo = __builtin_amdgcn_mfma_f32_16x16x32_f16(V[1], P[0], oo, 0, 0, 0);
+            oo = __builtin_amdgcn_mfma_f32_16x16x32_f16(V[0], P[0], oo, 0, 0, 0);
+            o[kp & 1][ct] = oo;
+        }
+    };
+#pragma unroll
+    for (int kp = 0; kp < MAXT / 2; ++kp) { // (wave-uniform branches)
+        if (2 * kp <= qb) pv_pair(kp, 2 * kp + 1 <= qb);
     }
     const float lt = quad16_sum(l);
-    const float inv = qi < L ? 1.0f / lt : 0.f;
+    const float inv = 1.0f / lt; // (rows beyond the sequence: whatever this gives, zeros are stored)
     if (store) {
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
