@@ -345,7 +345,9 @@ int irs_path_step(irs_ctx *ctx, int64_t *dev_seq, int32_t *dev_hep, int32_t B, c
 /* Whole greedy/sampled path generation on ONE device holding the full catalog
  * (world == 1): max_path_len x { decode, top-k, path step } enqueued on the
  * stream; with use_graph != 0 one step is captured once into a hipGraph and
- * replayed.  dev_seq is the working window (modified); dev_hep int32 [B]
+ * replayed (while a profiling family is enabled, irs_prof_enable, every search
+ * loop runs on the stream and records its brackets: same paths and status).
+ * dev_seq is the working window (modified); dev_hep int32 [B]
  * initial history end positions (L - gap_len - 2, per row). */
 int irs_generate_paths(irs_ctx *ctx, int64_t *dev_seq, const int64_t *dev_user, int32_t *dev_hep, int32_t B,
                        int32_t max_path_len, int32_t k, int32_t sweep, int32_t sample, int32_t sample_k,

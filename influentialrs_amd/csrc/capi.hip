@@ -106,9 +106,7 @@ extern "C" int irs_create(irs_ctx **out, const irs_dims *dims, const irs_shard *
 
 extern "C" void irs_destroy(irs_ctx *ctx) {
     if (!ctx) return;
-    if (ctx->graph_exec) hipGraphExecDestroy(ctx->graph_exec);
-    if (ctx->beam_graph) hipGraphExecDestroy(ctx->beam_graph);
-    if (ctx->sh_graph) hipGraphExecDestroy(ctx->sh_graph);
+    irs_drop_graphs(ctx);
     if (ctx->sh_side) {
         for (int i = 0; i < 8; ++i) (void)hipEventDestroy(ctx->sh_ev[i]);
         (void)hipStreamDestroy(ctx->sh_side);
@@ -260,18 +258,7 @@ extern "C" int irs_finalize_weights(irs_ctx *ctx, void *arena, size_t bytes, voi
     ctx->finalized = true;
     ctx->proj_stale = false;
     ctx->thr_valid = 0; // (carried emission thresholds belong to the catalog they were selected on)
-    if (ctx->sh_graph) {
-        hipGraphExecDestroy(ctx->sh_graph);
-        ctx->sh_graph = nullptr;
-    }
-    if (ctx->graph_exec) {
-        hipGraphExecDestroy(ctx->graph_exec);
-        ctx->graph_exec = nullptr;
-    }
-    if (ctx->beam_graph) {
-        hipGraphExecDestroy(ctx->beam_graph);
-        ctx->beam_graph = nullptr;
-    }
+    irs_drop_graphs(ctx);
     return IRS_OK;
 }
 
@@ -422,33 +409,15 @@ extern "C" int irs_bind_workspace(irs_ctx *ctx, void *ws, size_t bytes) {
     ctx->fb_count = (unsigned int *)(b + p.fbcount);
     ctx->fb_list = (int32_t *)(b + p.fblist);
     ctx->exh_keys = ctx->n_local >= IRS_COOP_FALLBACK_MIN_ITEMS ? (unsigned long long *)(b + p.exhkeys) : nullptr;
-    if (ctx->sh_graph) {
-        hipGraphExecDestroy(ctx->sh_graph);
-        ctx->sh_graph = nullptr;
-    }
-    if (ctx->beam_graph) {
-        hipGraphExecDestroy(ctx->beam_graph);
-        ctx->beam_graph = nullptr;
-    }
-    if (ctx->graph_exec) {
-        hipGraphExecDestroy(ctx->graph_exec);
-        ctx->graph_exec = nullptr;
-    }
+    irs_drop_graphs(ctx);
     return IRS_OK;
 }
 
-static void drop_graphs(irs_ctx *ctx) { // captured steps hold kernel choices and buffer addresses
-    if (ctx->sh_graph) {
-        hipGraphExecDestroy(ctx->sh_graph);
-        ctx->sh_graph = nullptr;
-    }
-    if (ctx->beam_graph) {
-        hipGraphExecDestroy(ctx->beam_graph);
-        ctx->beam_graph = nullptr;
-    }
-    if (ctx->graph_exec) {
-        hipGraphExecDestroy(ctx->graph_exec);
-        ctx->graph_exec = nullptr;
+// captured steps hold kernel choices, workspace addresses and derived weights: whatever changes one of them drops all three
+void irs_drop_graphs(irs_ctx *ctx) {
+    for (irs_step_graph *g : {&ctx->g_greedy, &ctx->g_beam, &ctx->g_sharded}) {
+        if (g->exec) (void)hipGraphExecDestroy(g->exec);
+        g->exec = nullptr;
     }
 }
 
@@ -458,7 +427,7 @@ extern "C" int irs_set_decoder_gemm(irs_ctx *ctx, int32_t mode) {
         IRS_FAIL(ctx, IRS_E_INVALID, "decoder GEMM mode %d (IRS_GEMM_F32, IRS_GEMM_X6 or IRS_GEMM_H3)", mode);
     if (ctx->use_x6 != mode) {
         ctx->use_x6 = mode;
-        drop_graphs(ctx);
+        irs_drop_graphs(ctx);
     }
     return IRS_OK;
 }
@@ -468,7 +437,7 @@ extern "C" int irs_set_decoder_seq(irs_ctx *ctx, int32_t mode) {
     if (mode < 0 || mode > 2) IRS_FAIL(ctx, IRS_E_INVALID, "decoder seq mode %d (0 off, 1 on, 2 auto)", mode);
     if (ctx->use_seq != mode) {
         ctx->use_seq = mode;
-        drop_graphs(ctx);
+        irs_drop_graphs(ctx);
     }
     return IRS_OK;
 }
@@ -721,6 +690,69 @@ static int enqueue_step(irs_ctx *ctx, int64_t *seq, const int64_t *user, int32_t
     return merged ? IRS_OK : irs_launch_inc(ctx, ctx->step_ctr, s);
 }
 
+// ------------------------------------------------------------------ what the search loops share
+int irs_replay_steps(irs_ctx *ctx, irs_step_graph *g, const irs_step_key &key, const std::function<int(hipStream_t)> &body,
+                     int times, hipStream_t s, int *capture_failed) {
+    if (capture_failed) *capture_failed = 0;
+    if (!g->exec || memcmp(&g->key, &key, sizeof(key))) {
+        if (g->exec) (void)hipGraphExecDestroy(g->exec);
+        g->exec = nullptr;
+        hipStream_t cs = nullptr;
+        hipGraph_t graph = nullptr;
+        int rc = IRS_OK;
+        hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
+        if (e == hipSuccess && (e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal)) == hipSuccess) {
+            rc = body(cs);
+            const hipError_t e2 = hipStreamEndCapture(cs, &graph); // (a failed body's capture is ended too)
+            if (rc == IRS_OK) e = e2;
+        }
+        if (rc == IRS_OK && e == hipSuccess) e = hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0);
+        if (graph) (void)hipGraphDestroy(graph);
+        if (cs) (void)hipStreamDestroy(cs);
+        if (rc != IRS_OK || e != hipSuccess) {
+            g->exec = nullptr;
+            if (capture_failed) *capture_failed = rc != IRS_OK ? IRS_CAPTURE_BODY : IRS_CAPTURE_HIP;
+            if (rc != IRS_OK) return rc;
+            IRS_FAIL(ctx, IRS_E_HIP, "graph capture failed: %s", hipGetErrorString(e));
+        }
+        g->key = key;
+    }
+    for (int i = 0; i < times; ++i) IRS_CHECK_HIP(ctx, hipGraphLaunch(g->exec, s));
+    return IRS_OK;
+}
+
+// (the sharded entry points have checked `sweep` before they come here)
+int irs_check_k(irs_ctx *ctx, const char *fn, int k, int world, int sweep, int sample, int sample_k) {
+    if (k < 1 || k > ctx->dims.max_k || (int64_t)k * world > 2048) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad k", fn);
+    if (sweep != IRS_SWEEP_BF16 && sweep != IRS_SWEEP_F32) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad sweep", fn);
+    if (sample && (sample_k < 1 || sample_k > IRS_MAX_SAMPLE_K))
+        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: sample_k must be in [1, %d]", fn, IRS_MAX_SAMPLE_K);
+    return IRS_OK;
+}
+
+int irs_check_beam_args(irs_ctx *ctx, const char *fn, const void *seq0, const void *hep0, const void *paths, const void *scores,
+                        const void *status, int B, int W, int P) {
+    if (!seq0 || !hep0 || !paths || !scores || !status || B < 1) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad arguments", fn);
+    if (W < 1 || W > 32) IRS_FAIL(ctx, IRS_E_INVALID, "%s: beam width must be in [1, 32]", fn);
+    if (P < 1 || P > IRS_MAX_PATH) IRS_FAIL(ctx, IRS_E_INVALID, "%s: path length must be in [1, %d]", fn, IRS_MAX_PATH);
+    return IRS_OK;
+}
+
+int irs_search_begin(irs_ctx *ctx, int32_t *status, int B, hipStream_t s) {
+    IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->step_ctr, 0, 2 * sizeof(int32_t), s));
+    IRS_CHECK_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int32_t) * B, s));
+    return IRS_OK;
+}
+
+int irs_beam_finish(irs_ctx *ctx, size_t rows, int P, float *paths, double *scores, int64_t *seq_final, hipStream_t s) {
+    const int fin = P & 1;
+    IRS_CHECK_HIP(ctx, hipMemcpyAsync(paths, ctx->bm_paths[fin], rows * P * sizeof(float), hipMemcpyDeviceToDevice, s));
+    IRS_CHECK_HIP(ctx, hipMemcpyAsync(scores, ctx->bm_cum[fin], rows * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (seq_final)
+        IRS_CHECK_HIP(ctx, hipMemcpyAsync(seq_final, ctx->bm_seq[fin], rows * ctx->dims.max_len * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    return IRS_OK;
+}
+
 extern "C" int irs_generate_paths(irs_ctx *ctx, int64_t *seq, const int64_t *user, int32_t *hep, int32_t B,
                                   int32_t max_path_len, int32_t k, int32_t sweep, int32_t sample, int32_t sample_k,
                                   uint64_t seed, int32_t use_graph, float *paths, int32_t *status, void *stream) {
@@ -729,67 +761,21 @@ extern "C" int irs_generate_paths(irs_ctx *ctx, int64_t *seq, const int64_t *use
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_generate_paths needs the whole catalog on one device");
     if (!seq || !hep || !paths || !status || B < 1 || max_path_len < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths: bad arguments");
     if (B > ctx->max_seqs || B > ctx->max_rows) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths: B too large");
-    if (k < 1 || k > ctx->dims.max_k) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths: bad k");
-    if (sweep != IRS_SWEEP_BF16 && sweep != IRS_SWEEP_F32) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths: bad sweep");
-    if (sample && (sample_k < 1 || sample_k > IRS_MAX_SAMPLE_K))
-        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_generate_paths: sample_k must be in [1, %d]", IRS_MAX_SAMPLE_K);
+    if ((rc = irs_check_k(ctx, "irs_generate_paths", k, 1, sweep, sample, sample_k))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->step_ctr, 0, 2 * sizeof(int32_t), s));
-    IRS_CHECK_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int32_t) * B, s));
-    if (!use_graph) {
-        for (int i = 0; i < max_path_len; ++i) // (steps behind the first may reuse the previous step's emission thresholds)
-            if ((rc = enqueue_step(ctx, seq, user, hep, B, k, sweep, sample, sample_k, seed, paths, max_path_len, status, s, i > 0)))
-                return rc;
-        return IRS_OK;
+    if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
+    if (irs_may_capture(ctx, use_graph)) { // one step per graph; a captured step never carries emission thresholds
+        irs_step_key key = {};
+        key.kind = IRS_STEP_GREEDY, key.B = B, key.P = max_path_len, key.k = k, key.sweep = sweep;
+        key.sample = sample, key.sample_k = sample_k, key.seed = seed;
+        key.seq = seq, key.user = user, key.hep = hep, key.paths = paths, key.status = status;
+        return irs_replay_steps(ctx, &ctx->g_greedy, key, [&](hipStream_t q) {
+            return enqueue_step(ctx, seq, user, hep, B, k, sweep, sample, sample_k, seed, paths, max_path_len, status, q);
+        }, max_path_len, s);
     }
-    bool reuse = ctx->graph_exec && ctx->graph_B == B && ctx->graph_P == max_path_len && ctx->graph_k == k && ctx->graph_sweep == sweep &&
-                 ctx->graph_sample == sample && ctx->graph_sample_k == sample_k && ctx->graph_seq == seq &&
-                 ctx->graph_user == user && ctx->graph_hep == hep && ctx->graph_paths == paths &&
-                 ctx->graph_status == status && ctx->graph_seed == seed && ctx->prof_family == IRS_PROF_NONE;
-    if (!reuse) {
-        if (ctx->graph_exec) {
-            hipGraphExecDestroy(ctx->graph_exec);
-            ctx->graph_exec = nullptr;
-        }
-        int saved_prof = ctx->prof_family;
-        ctx->prof_family = IRS_PROF_NONE; // event records are not captured
-        hipStream_t cs;
-        IRS_CHECK_HIP(ctx, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-        hipGraph_t graph = nullptr;
-        hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-        if (e == hipSuccess) {
-            rc = enqueue_step(ctx, seq, user, hep, B, k, sweep, sample, sample_k, seed, paths, max_path_len, status, cs);
-            hipError_t e2 = hipStreamEndCapture(cs, &graph);
-            if (rc == IRS_OK && e2 != hipSuccess) e = e2;
-        }
-        ctx->prof_family = saved_prof;
-        if (e != hipSuccess || rc != IRS_OK || !graph) {
-            hipStreamDestroy(cs);
-            if (graph) hipGraphDestroy(graph);
-            if (rc) return rc;
-            IRS_FAIL(ctx, IRS_E_HIP, "graph capture failed: %s", hipGetErrorString(e));
-        }
-        e = hipGraphInstantiate(&ctx->graph_exec, graph, nullptr, nullptr, 0);
-        hipGraphDestroy(graph);
-        hipStreamDestroy(cs);
-        if (e != hipSuccess) {
-            ctx->graph_exec = nullptr;
-            IRS_FAIL(ctx, IRS_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-        }
-        ctx->graph_B = B;
-        ctx->graph_P = max_path_len;
-        ctx->graph_k = k;
-        ctx->graph_sweep = sweep;
-        ctx->graph_sample = sample;
-        ctx->graph_sample_k = sample_k;
-        ctx->graph_seq = seq;
-        ctx->graph_user = (void *)user;
-        ctx->graph_hep = hep;
-        ctx->graph_paths = paths;
-        ctx->graph_status = status;
-        ctx->graph_seed = seed;
-    }
-    for (int i = 0; i < max_path_len; ++i) IRS_CHECK_HIP(ctx, hipGraphLaunch(ctx->graph_exec, s));
+    for (int i = 0; i < max_path_len; ++i) // (steps behind the first may reuse the previous step's emission thresholds)
+        if ((rc = enqueue_step(ctx, seq, user, hep, B, k, sweep, sample, sample_k, seed, paths, max_path_len, status, s, i > 0)))
+            return rc;
     return IRS_OK;
 }
 
@@ -831,67 +817,30 @@ extern "C" int irs_beam_search(irs_ctx *ctx, const int64_t *seq0, const int64_t 
     int rc = ready_filter(ctx, sweep);
     if (rc) return rc;
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_beam_search needs the whole catalog on one device");
-    if (!seq0 || !hep0 || !paths || !scores || !status || B < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search: bad arguments");
-    if (W < 1 || W > 32) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search: beam width must be in [1, 32]");
-    if (P < 1 || P > IRS_MAX_PATH) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search: path length must be in [1, %d]", IRS_MAX_PATH);
+    if ((rc = irs_check_beam_args(ctx, "irs_beam_search", seq0, hep0, paths, scores, status, B, W, P))) return rc;
     if ((int64_t)B * W > ctx->max_seqs || (int64_t)B * W > ctx->max_rows)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search: B*W=%d exceeds max_seqs=%d / max_rows=%d", B * W, ctx->max_seqs, ctx->max_rows);
-    if (k < 1 || k > ctx->dims.max_k) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search: bad k");
-    if (sweep != IRS_SWEEP_BF16 && sweep != IRS_SWEEP_F32) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search: bad sweep");
+    if ((rc = irs_check_k(ctx, "irs_beam_search", k, 1, sweep, 0, 0))) return rc;
     if (ctx->dims.mask_mode == IRS_MASK_IRN && !user) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search: user is null");
     hipStream_t s = (hipStream_t)stream;
-    IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->step_ctr, 0, 2 * sizeof(int32_t), s));
-    IRS_CHECK_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int32_t) * B, s));
+    if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
     if ((rc = irs_launch_beam_init(ctx, seq0, user, hep0, B, W, P, ctx->bm_seq[0], ctx->bm_user, ctx->bm_hep[0],
                                    ctx->bm_cum[0], ctx->bm_paths[0], s)))
         return rc;
     int done = 0;
-    if (use_graph && P >= 2 && ctx->prof_family == IRS_PROF_NONE) {
-        // NOTE: `status` is baked into the captured graph, so it is part of the cache key via its address below
-        static_assert(sizeof(void *) == 8, "64-bit only");
-        bool reuse = ctx->beam_graph && ctx->beam_B == B && ctx->beam_W == W && ctx->beam_k == k &&
-                     ctx->beam_sweep == sweep && ctx->beam_P == P && ctx->beam_status == (void *)status;
-        if (!reuse) {
-            if (ctx->beam_graph) {
-                hipGraphExecDestroy(ctx->beam_graph);
-                ctx->beam_graph = nullptr;
-            }
-            hipStream_t cs;
-            IRS_CHECK_HIP(ctx, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-            hipGraph_t graph = nullptr;
-            hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-            if (e == hipSuccess) {
-                rc = enqueue_beam_step(ctx, 0, B, W, k, sweep, P, status, cs);
-                if (rc == IRS_OK) rc = enqueue_beam_step(ctx, 1, B, W, k, sweep, P, status, cs);
-                hipError_t e2 = hipStreamEndCapture(cs, &graph);
-                if (rc == IRS_OK && e2 != hipSuccess) e = e2;
-            }
-            if (e == hipSuccess && rc == IRS_OK && graph) e = hipGraphInstantiate(&ctx->beam_graph, graph, nullptr, nullptr, 0);
-            if (graph) hipGraphDestroy(graph);
-            hipStreamDestroy(cs);
-            if (rc) return rc;
-            if (e != hipSuccess) {
-                ctx->beam_graph = nullptr;
-                IRS_FAIL(ctx, IRS_E_HIP, "beam graph capture failed: %s", hipGetErrorString(e));
-            }
-            ctx->beam_B = B;
-            ctx->beam_W = W;
-            ctx->beam_k = k;
-            ctx->beam_sweep = sweep;
-            ctx->beam_P = P;
-            ctx->beam_status = status;
-        }
-        for (; done + 2 <= P; done += 2) IRS_CHECK_HIP(ctx, hipGraphLaunch(ctx->beam_graph, s));
+    if (irs_may_capture(ctx, use_graph) && P >= 2) { // the two ping-pong steps per graph; an odd last step runs on the stream
+        irs_step_key key = {}; // (the steps work on the context's beam buffers: of the caller's pointers only `status` is baked in)
+        key.kind = IRS_STEP_BEAM, key.B = B, key.W = W, key.P = P, key.k = k, key.sweep = sweep, key.status = status;
+        if ((rc = irs_replay_steps(ctx, &ctx->g_beam, key, [&](hipStream_t q) {
+                int r = enqueue_beam_step(ctx, 0, B, W, k, sweep, P, status, q);
+                return r ? r : enqueue_beam_step(ctx, 1, B, W, k, sweep, P, status, q);
+            }, P / 2, s)))
+            return rc;
+        done = P / 2 * 2;
     }
     for (; done < P; ++done)
         if ((rc = enqueue_beam_step(ctx, done & 1, B, W, k, sweep, P, status, s))) return rc;
-    const int fin = P & 1;
-    const size_t rows = (size_t)B * W;
-    IRS_CHECK_HIP(ctx, hipMemcpyAsync(paths, ctx->bm_paths[fin], rows * P * sizeof(float), hipMemcpyDeviceToDevice, s));
-    IRS_CHECK_HIP(ctx, hipMemcpyAsync(scores, ctx->bm_cum[fin], rows * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (seq_final)
-        IRS_CHECK_HIP(ctx, hipMemcpyAsync(seq_final, ctx->bm_seq[fin], rows * ctx->dims.max_len * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    return IRS_OK;
+    return irs_beam_finish(ctx, (size_t)B * W, P, paths, scores, seq_final, s);
 }
 
 // ------------------------------------------------------------------ profiling hooks

@@ -282,7 +282,7 @@ extern "C" int irs_set_sharded_overlap(irs_ctx *ctx, int32_t on) {
 extern "C" int irs_get_sharded_overlap(const irs_ctx *ctx) { return ctx ? ctx->sh_overlap : IRS_E_INVALID; }
 
 extern "C" int irs_sharded_graph_state(const irs_ctx *ctx) {
-    return ctx ? ((ctx->sh_graph ? 1 : 0) | (ctx->sh_nograph ? 2 : 0)) : 0;
+    return ctx ? ((ctx->g_sharded.exec ? 1 : 0) | (ctx->sh_nograph ? 2 : 0)) : 0;
 }
 
 // ---- small kernels of the sharded loops
@@ -312,42 +312,17 @@ static int ready_sharded(irs_ctx *ctx, irs_comm *comm, const char *fn, int sweep
     return IRS_OK;
 }
 
-// capture `body` into a graph once per key and replay it `times` times; falls back to plain launches when the
-// communicator cannot be captured (callbacks) or capture fails with the collectives inside
-template <typename F>
-static int run_steps(irs_ctx *ctx, irs_comm *comm, bool use_graph, hipGraphExec_t *exec, bool reuse, int times, hipStream_t s, F &&body) {
-    int rc;
-    if (use_graph && comm->rccl && ctx->prof_family == IRS_PROF_NONE && !ctx->sh_nograph) {
-        if (!reuse || !*exec) {
-            if (*exec) {
-                (void)hipGraphExecDestroy(*exec);
-                *exec = nullptr;
-            }
-            hipStream_t cs;
-            IRS_CHECK_HIP(ctx, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-            hipGraph_t graph = nullptr;
-            hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-            rc = IRS_OK;
-            if (e == hipSuccess) {
-                rc = body(cs);
-                hipError_t e2 = hipStreamEndCapture(cs, &graph);
-                if (rc == IRS_OK && e2 != hipSuccess) e = e2;
-            }
-            if (e == hipSuccess && rc == IRS_OK && graph) e = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
-            if (graph) (void)hipGraphDestroy(graph);
-            (void)hipStreamDestroy(cs);
-            if (rc != IRS_OK || e != hipSuccess) {
-                // nothing of a captured step has executed: the state is untouched.  A collective library that cannot be
-                // captured makes this context fall back to plain stream launches from now on (same results).
-                *exec = nullptr;
-                ctx->sh_nograph = 1;
-                (void)hipGetLastError();
-            }
-        }
-        if (*exec) {
-            for (int i = 0; i < times; ++i) IRS_CHECK_HIP(ctx, hipGraphLaunch(*exec, s));
-            return IRS_OK;
-        }
+// `times` steps of a sharded loop: the captured body replayed when `graph` (RCCL, no profiling, sh_nograph clear), else
+// plain launches.  A capture that fails with the collectives inside has executed nothing: the context falls back to plain
+// stream launches from now on (same results).
+static int replay_or_stream(irs_ctx *ctx, bool graph, const irs_step_key &key, const std::function<int(hipStream_t)> &body, int times,
+                            hipStream_t s) {
+    int rc, capture_failed = 0;
+    if (graph) {
+        rc = irs_replay_steps(ctx, &ctx->g_sharded, key, body, times, s, &capture_failed);
+        if (!capture_failed) return rc;
+        ctx->sh_nograph = 1;
+        (void)hipGetLastError();
     }
     for (int i = 0; i < times; ++i)
         if ((rc = body(s))) return rc;
@@ -365,15 +340,12 @@ extern "C" int irs_generate_paths_sharded(irs_ctx *ctx, irs_comm *comm, int64_t 
     if (ctx->dims.mask_mode == IRS_MASK_IRN && !user) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths_sharded: user is null");
     if (B > ctx->max_seqs || (int64_t)B * world > ctx->max_rows)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths_sharded: B=%d needs max_seqs >= B and max_rows >= world * B = %d", B, B * world);
-    if (k < 1 || k > ctx->dims.max_k || (int64_t)k * world > 2048) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths_sharded: bad k");
-    if (sample && (sample_k < 1 || sample_k > IRS_MAX_SAMPLE_K))
-        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_generate_paths_sharded: sample_k must be in [1, %d]", IRS_MAX_SAMPLE_K);
+    if ((rc = irs_check_k(ctx, "irs_generate_paths_sharded", k, world, sweep, sample, sample_k))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int rows = B * world;
-    IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->step_ctr, 0, 2 * sizeof(int32_t), s));
-    IRS_CHECK_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int32_t) * B, s));
+    if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
     int step_no = 0; // (stream launches: steps behind the first may reuse the previous step's emission thresholds; a captured step never does)
-    const bool graph_path = use_graph && comm->rccl && ctx->prof_family == IRS_PROF_NONE && !ctx->sh_nograph;
+    const bool graph_path = irs_may_capture(ctx, use_graph) && comm->rccl && !ctx->sh_nograph;
     auto body = [&](hipStream_t q) -> int {
         int r;
         const int carry = (!graph_path && step_no++ > 0) ? 1 : 0;
@@ -442,17 +414,11 @@ extern "C" int irs_generate_paths_sharded(irs_ctx *ctx, irs_comm *comm, int64_t 
             if ((rc = body2(s))) return rc;
         return IRS_OK;
     }
-    const bool reuse = ctx->sh_graph && ctx->sh_kind == 1 && ctx->sh_comm == comm && ctx->sh_B == B && ctx->sh_W == 1 &&
-                       ctx->sh_P == max_path_len && ctx->sh_k == k && ctx->sh_sweep == sweep && ctx->sh_sample == sample &&
-                       ctx->sh_sample_k == sample_k && ctx->sh_seed == seed && ctx->sh_ptr[0] == seq && ctx->sh_ptr[1] == (void *)user &&
-                       ctx->sh_ptr[2] == hep && ctx->sh_ptr[3] == paths && ctx->sh_ptr[4] == status;
-    rc = run_steps(ctx, comm, use_graph != 0, &ctx->sh_graph, reuse, max_path_len, s, body);
-    if (rc == IRS_OK && use_graph && comm->rccl) {
-        ctx->sh_kind = 1, ctx->sh_comm = comm, ctx->sh_B = B, ctx->sh_W = 1, ctx->sh_P = max_path_len, ctx->sh_k = k, ctx->sh_sweep = sweep;
-        ctx->sh_sample = sample, ctx->sh_sample_k = sample_k, ctx->sh_seed = seed;
-        ctx->sh_ptr[0] = seq, ctx->sh_ptr[1] = (void *)user, ctx->sh_ptr[2] = hep, ctx->sh_ptr[3] = paths, ctx->sh_ptr[4] = status;
-    }
-    return rc;
+    irs_step_key key = {};
+    key.kind = IRS_STEP_GREEDY, key.comm = comm, key.B = B, key.W = 1, key.P = max_path_len, key.k = k, key.sweep = sweep;
+    key.sample = sample, key.sample_k = sample_k, key.seed = seed;
+    key.seq = seq, key.user = user, key.hep = hep, key.paths = paths, key.status = status;
+    return replay_or_stream(ctx, graph_path, key, body, max_path_len, s);
 }
 
 // ------------------------------------------------------------------ beam search, item-sharded
@@ -463,11 +429,9 @@ extern "C" int irs_beam_search_sharded(irs_ctx *ctx, irs_comm *comm, const int64
     int rc = ready_sharded(ctx, comm, "irs_beam_search_sharded", sweep);
     if (rc) return rc;
     const int world = comm->world, R = B * W;
-    if (!seq0 || !hep0 || !paths || !scores || !status || B < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_sharded: bad arguments");
-    if (W < 1 || W > 32) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_sharded: beam width must be in [1, 32]");
-    if (P < 1 || P > IRS_MAX_PATH) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_sharded: path length must be in [1, %d]", IRS_MAX_PATH);
+    if ((rc = irs_check_beam_args(ctx, "irs_beam_search_sharded", seq0, hep0, paths, scores, status, B, W, P))) return rc;
     if (ctx->dims.mask_mode == IRS_MASK_IRN && !user) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_sharded: user is null");
-    if (k < 1 || k > ctx->dims.max_k || (int64_t)k * world > 2048) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_sharded: bad k");
+    if ((rc = irs_check_k(ctx, "irs_beam_search_sharded", k, world, sweep, 0, 0))) return rc;
     const int rows_all = split_decode ? R : R * world; // rows every rank sweeps
     if (R > ctx->max_seqs || (int64_t)R * world > ctx->max_rows) // (split_decode: the gathered key lists are world x R x k)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_sharded: B*W=%d needs max_seqs >= %d and max_rows >= %d", R, R, R * world);
@@ -478,8 +442,7 @@ extern "C" int irs_beam_search_sharded(irs_ctx *ctx, irs_comm *comm, const int64
     if (split_decode && (int64_t)per_split * world > ctx->max_rows)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_sharded: split_decode gathers %d rows, max_rows is %d", per_split * world, ctx->max_rows);
     hipStream_t s = (hipStream_t)stream;
-    IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->step_ctr, 0, 2 * sizeof(int32_t), s));
-    IRS_CHECK_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int32_t) * B, s));
+    if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
     if ((rc = irs_launch_beam_init(ctx, seq0, user, hep0, B, W, P, ctx->bm_seq[0], ctx->bm_user, ctx->bm_hep[0], ctx->bm_cum[0],
                                    ctx->bm_paths[0], s)))
         return rc;
@@ -524,23 +487,18 @@ extern "C" int irs_beam_search_sharded(irs_ctx *ctx, irs_comm *comm, const int64
         return irs_launch_inc(ctx, ctx->step_ctr, q);
     };
     int done = 0;
-    if (use_graph && comm->rccl && P >= 2 && ctx->prof_family == IRS_PROF_NONE) {
-        const bool reuse = ctx->sh_graph && ctx->sh_kind == 2 + (split_decode ? 1 : 0) && ctx->sh_comm == comm && ctx->sh_B == B &&
-                           ctx->sh_W == W && ctx->sh_P == P && ctx->sh_k == k && ctx->sh_sweep == sweep && ctx->sh_ptr[4] == status;
+    if (irs_may_capture(ctx, use_graph) && comm->rccl && P >= 2) { // (with sh_nograph set: the same pairs on the stream)
+        irs_step_key key = {}; // (the steps work on the context's beam buffers: of the caller's pointers only `status` is baked in)
+        key.kind = split_decode ? IRS_STEP_SHARDED_BEAM_SPLIT : IRS_STEP_SHARDED_BEAM, key.comm = comm;
+        key.B = B, key.W = W, key.P = P, key.k = k, key.sweep = sweep, key.status = status;
         auto two = [&](hipStream_t q) -> int {
             int r = step(0, q);
             return r ? r : step(1, q);
         };
-        if ((rc = run_steps(ctx, comm, true, &ctx->sh_graph, reuse, P / 2, s, two))) return rc;
-        ctx->sh_kind = 2 + (split_decode ? 1 : 0), ctx->sh_comm = comm, ctx->sh_B = B, ctx->sh_W = W, ctx->sh_P = P, ctx->sh_k = k;
-        ctx->sh_sweep = sweep, ctx->sh_ptr[4] = status;
+        if ((rc = replay_or_stream(ctx, !ctx->sh_nograph, key, two, P / 2, s))) return rc;
         done = (P / 2) * 2;
     }
     for (; done < P; ++done)
         if ((rc = step(done & 1, s))) return rc;
-    const int fin = P & 1;
-    IRS_CHECK_HIP(ctx, hipMemcpyAsync(paths, ctx->bm_paths[fin], (size_t)R * P * sizeof(float), hipMemcpyDeviceToDevice, s));
-    IRS_CHECK_HIP(ctx, hipMemcpyAsync(scores, ctx->bm_cum[fin], (size_t)R * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (seq_final) IRS_CHECK_HIP(ctx, hipMemcpyAsync(seq_final, ctx->bm_seq[fin], (size_t)R * L * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    return IRS_OK;
+    return irs_beam_finish(ctx, (size_t)R, P, paths, scores, seq_final, s);
 }

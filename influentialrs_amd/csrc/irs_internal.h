@@ -23,6 +23,7 @@
 #endif
 
 #include <atomic>
+#include <functional>
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) and occupancy are PER DEVICE: the "done once" flags of the launchers are a
 // bit per device ordinal (setting the attribute twice from two host threads is harmless, so a plain atomic mask suffices)
 #define IRS_MAX_DEVICES 32
@@ -61,6 +62,21 @@ struct irs_layer_w {
 
 struct irs_prof_ev {
     hipEvent_t a, b;
+};
+
+// ---- captured steps.  A search loop captures its step body once as a hipGraph and replays it.  The body bakes in kernel
+// choices, workspace addresses and every argument of the call, so the cache key holds all of them: a loop fills ONE key (fields
+// it does not bake in stay zero) and irs_replay_steps compares it as a whole.
+enum { IRS_STEP_GREEDY = 1, IRS_STEP_BEAM, IRS_STEP_SHARDED_BEAM, IRS_STEP_SHARDED_BEAM_SPLIT };
+struct irs_step_key {
+    int32_t kind, B, W, P, k, sweep, sample, sample_k;
+    uint64_t seed;
+    const void *comm, *seq, *user, *hep, *paths, *status;
+};
+static_assert(sizeof(irs_step_key) == 8 * sizeof(int32_t) + 7 * 8, "irs_step_key is compared with memcmp: no padding");
+struct irs_step_graph {
+    hipGraphExec_t exec; // null: nothing captured
+    irs_step_key key;
 };
 
 struct irs_ctx {
@@ -147,22 +163,13 @@ struct irs_ctx {
     float *x_local;           // [max_seqs][d] this rank's decoded rows (the all-gather's send buffer)
     uint64_t *keys_send, *keys_recv; // [max_rows][max_k] packed per-shard lists
     float *lse_gmax;          // [max_rows] all-reduced row maxima
-    hipGraphExec_t sh_graph;  // captured sharded step (greedy: one step; beam: two)
-    int sh_kind, sh_B, sh_W, sh_P, sh_k, sh_sweep, sh_sample, sh_sample_k, sh_nograph;
+    int sh_nograph;           // a capture with the collectives inside failed: the sharded loops stay on stream launches
     int sh_overlap;           // irs_set_sharded_overlap: the greedy sharded loop runs two user micro-batches per step, collectives on sh_side
     hipStream_t sh_side;      // (created on first use)
     hipEvent_t sh_ev[8];
-    uint64_t sh_seed;
-    void *sh_comm, *sh_ptr[5];
-    hipGraphExec_t beam_graph;
-    int beam_B, beam_W, beam_k, beam_sweep, beam_P;
-    void *beam_status; // the status buffer baked into the captured beam steps
 
-    // graph cache for irs_generate_paths
-    hipGraphExec_t graph_exec;
-    int graph_B, graph_P, graph_k, graph_sweep, graph_sample, graph_sample_k;
-    void *graph_seq, *graph_user, *graph_hep, *graph_paths, *graph_status;
-    uint64_t graph_seed;
+    // captured steps of the search loops (irs_replay_steps): three independent caches, dropped together by irs_drop_graphs
+    irs_step_graph g_greedy, g_beam, g_sharded;
 
     // profiling
     int prof_family;
@@ -192,6 +199,22 @@ struct irs_ctx {
 // profiling bracket helpers (no-ops unless the family is enabled)
 void irs_prof_begin(irs_ctx *ctx, int family, hipStream_t s);
 void irs_prof_end(irs_ctx *ctx, int family, hipStream_t s, double flops, double bytes);
+
+// ---- captured steps, and what the four search entry points share (capi.hip)
+// Replays the captured `body` `times` times on `s`; captures it first, on a private stream, unless `g` holds an equal key.  A
+// failed capture leaves `g` empty and nothing has run: the return value is the body's own code (*capture_failed =
+// IRS_CAPTURE_BODY) or IRS_E_HIP with HIP's message in ctx->err (IRS_CAPTURE_HIP).  A failed replay leaves *capture_failed 0.
+enum { IRS_CAPTURE_BODY = 1, IRS_CAPTURE_HIP = 2 };
+int irs_replay_steps(irs_ctx *ctx, irs_step_graph *g, const irs_step_key &key, const std::function<int(hipStream_t)> &body,
+                     int times, hipStream_t s, int *capture_failed = nullptr);
+void irs_drop_graphs(irs_ctx *ctx);
+// event records are not captured: with a profiling family enabled every loop runs on the stream and records its brackets
+static inline bool irs_may_capture(const irs_ctx *ctx, int use_graph) { return use_graph && ctx->prof_family == IRS_PROF_NONE; }
+int irs_check_k(irs_ctx *ctx, const char *fn, int k, int world, int sweep, int sample, int sample_k);
+int irs_check_beam_args(irs_ctx *ctx, const char *fn, const void *seq0, const void *hep0, const void *paths, const void *scores,
+                        const void *status, int B, int W, int P);
+int irs_search_begin(irs_ctx *ctx, int32_t *status, int B, hipStream_t s); // step counter and status to zero
+int irs_beam_finish(irs_ctx *ctx, size_t rows, int P, float *paths, double *scores, int64_t *seq_final, hipStream_t s);
 
 // ---- decode shapes: the workspace (capi.hip) and the decoder's route choice (decoder.hip: decode_route) must agree on them
 // the sequence-resident layer kernel's shape (k_block_x6<.., SEQ>): its plan tables exist in the workspace only for it
