@@ -205,7 +205,8 @@ int irs_score_topk_lse(irs_ctx *ctx, const float *dev_xrows, int32_t M, int32_t 
 
 /* Training side: CrossEntropyLoss(project(x)[valid], label - 1) of IRSNN.train_batch /
  * get_loss_on_eval_data (influentialRS.py:252-310) and Evaluator.train_batch (evaluator.py:53-92) WITHOUT the
- * [M, n_item] logits the reference materialises.  One device holds the whole catalog.  project.weight / bias are
+ * [M, n_item] logits the reference materialises.  One device holds the whole catalog (IRS_E_UNSUPPORTED otherwise; an item-sharded
+ * catalog: irs_ce_forward_sharded / irs_ce_backward_sharded, multi-GPU section).  project.weight / bias are
  * read where they were bound: an optimizer step that updates them in place needs no re-finalisation for these two.
  * They do mark the context's derived catalog (bf16 copy, filter norms) as possibly stale: the entry points that
  * filter through it (irs_score_topk / _topk_lse with IRS_SWEEP_BF16, irs_generate_paths, irs_beam_search) return
@@ -451,6 +452,38 @@ int irs_beam_search_sharded(irs_ctx *ctx, irs_comm *comm, const int64_t *dev_seq
                             const int32_t *dev_hep0, int32_t B, int32_t W, int32_t P, int32_t k, int32_t sweep,
                             int32_t split_decode, int32_t use_graph, float *dev_paths, double *dev_scores,
                             int64_t *dev_seq_final, int32_t *dev_status, void *stream);
+
+/* irs_ce_forward / irs_ce_backward over an item-sharded catalog: the vocabulary-parallel form of CrossEntropyLoss(project(x)[valid],
+ * label - 1) as the reference runs it on one device in IRSNN.train_batch / get_loss_on_eval_data (influentialRS.py:252-310) and
+ * Evaluator.train_batch / get_loss_on_eval_data (evaluator.py:53-92).  Rows are data-parallel: every rank passes ITS OWN B rows
+ * (the same B on every rank) with GLOBAL 0-based labels (-1 = row ignored) and holds item rows [item_lo, item_hi) of project.*;
+ * the loss is the one over the WORLD's rows.  Needs max_rows >= world * B (IRS_E_INVALID otherwise).  Both work over either kind
+ * of communicator and with world == 1, where they equal irs_ce_forward / irs_ce_backward bit for bit.  project.* are read where
+ * they were bound and the derived bf16 catalog is marked stale, exactly as irs_ce_forward does.  Nothing is allocated: the
+ * gathered rows, labels and per-shard terms live in the bound workspace, the backward's partial outputs in the caller's scratch;
+ * all kernels and collectives are enqueued on the caller's stream.  Null pointers, B < 1, world * B > max_rows and (backward) a
+ * scratch smaller than irs_ce_backward_sharded_scratch_bytes(B) or not 16-byte aligned return IRS_E_INVALID before any launch or
+ * collective; unbound weights / workspace IRS_E_STATE.
+ *  irs_ce_forward_sharded: all-gather of rows and labels (rank-major) -> the float32 log-sum-exp sweep and the label gather of
+ *                   irs_ce_forward over this shard for all world * B rows (label score -inf where the label is outside the
+ *                   shard) -> all-gather of the per-shard (lse, label score) -> per row, shards in rank order:
+ *                   lse = m + log sum_r exp(lse_r - m), m = max_r lse_r; label score = the one entry that is not -inf.
+ *                   dev_lse / dev_label_score float [B]: this rank's own rows.  dev_loss double [3] as irs_ce_forward's, over the
+ *                   rows of the whole world in gathered order: identical bits on every rank.  Ignored rows and labels >= n_item
+ *                   behave as in irs_ce_forward.
+ *  irs_ce_backward_sharded: dev_lse float [B] is the forward's (global).  All-gather of rows, labels and lse -> the two passes of
+ *                   irs_ce_backward over this shard for all world * B rows: dev_dw [n_local, d] / dev_db [n_local] are then
+ *                   COMPLETE for the shard (overwritten or, accumulate != 0, added to; no reduction over ranks), the dx partial
+ *                   [world * B, d] goes to the scratch -> one all-to-all hands every rank the world's partials of its own B rows
+ *                   -> dev_dx float [B, d] = their sum in rank order (always overwritten; an ignored row is exactly zero).  No
+ *                   float atomics and no all-reduce of dx: two identical calls give identical bits.  Scratch: the single-device
+ *                   backward's at world * B rows plus 8 world B d bytes. */
+int irs_ce_forward_sharded(irs_ctx *ctx, irs_comm *comm, const float *dev_xrows_local, const int64_t *dev_labels0_local, int32_t B,
+                           float *dev_lse, float *dev_label_score, double *dev_loss, void *stream);
+size_t irs_ce_backward_sharded_scratch_bytes(const irs_ctx *ctx, int32_t B); /* 0 for an invalid B */
+int irs_ce_backward_sharded(irs_ctx *ctx, irs_comm *comm, const float *dev_xrows_local, const int64_t *dev_labels0_local,
+                            const float *dev_lse, int32_t B, float scale, int32_t accumulate, float *dev_dx, float *dev_dw,
+                            float *dev_db, void *dev_scratch, size_t scratch_bytes, void *stream);
 
 /* Opt-in overlap of irs_generate_paths_sharded's collectives with its compute (round 5; greedy choice only): the step's users run
  * as TWO micro-batches, the row all-gather and the key all_to_all of one on a side stream (chained by events) while the other

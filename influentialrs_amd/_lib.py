@@ -99,6 +99,10 @@ SIGNATURES = {
                                              c_int32, c_int32, c_uint64, c_int32, c_void_p, c_void_p, c_void_p]),
     "irs_beam_search_sharded": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                           c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "irs_ce_forward_sharded": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "irs_ce_backward_sharded_scratch_bytes": (c_size_t, [c_void_p, c_int32]),
+    "irs_ce_backward_sharded": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_int32, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "irs_sharded_graph_state": (c_int32, [c_void_p]),
     "irs_set_sharded_overlap": (c_int32, [c_void_p, c_int32]),
     "irs_get_sharded_overlap": (c_int32, [c_void_p]),

@@ -319,6 +319,8 @@ static int ce_bwd_sum(irs_ctx *ctx, const float *part, int groups, int64_t n, in
     return IRS_OK;
 }
 
+size_t irs_ce_bwd_scratch(const irs_ctx *ctx, int M) { return ce_bwd_plan(ctx, M).bytes; }
+
 extern "C" size_t irs_ce_backward_scratch_bytes(const irs_ctx *ctx, int32_t M) {
     if (!ctx || M < 1 || M > ctx->max_rows) return 0;
     return ce_bwd_plan(ctx, M).bytes;
@@ -337,8 +339,14 @@ extern "C" int irs_ce_backward(irs_ctx *ctx, const float *xrows, const int64_t *
     if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_ce_backward: scratch must be 16-byte aligned");
     if (((uintptr_t)xrows) & 7) IRS_FAIL(ctx, IRS_E_INVALID, "irs_ce_backward: rows must be 8-byte aligned");
     if (!ctx->proj_w || !ctx->proj_b) IRS_FAIL(ctx, IRS_E_STATE, "irs_ce_backward: project.weight / project.bias not bound");
-    hipStream_t s = (hipStream_t)stream;
     ctx->proj_stale = true; // as irs_ce_forward: the caller is about to move project.* under the bf16 catalog copy
+    return irs_launch_ce_backward(ctx, xrows, labels0, lse, M, scale, accumulate, dx, dw, db, scratch, (hipStream_t)stream);
+}
+
+// the two passes over this context's shard (irs_ce_backward; irs_ce_backward_sharded over the gathered rows)
+int irs_launch_ce_backward(irs_ctx *ctx, const float *xrows, const int64_t *labels0, const float *lse, int M, float scale,
+                           int accumulate, float *dx, float *dw, float *db, void *scratch, hipStream_t s) {
+    const CeBwdPlan p = ce_bwd_plan(ctx, M);
     char *sc = static_cast<char *>(scratch);
     int rc;
     CeBwdArgs a;

@@ -259,6 +259,15 @@ static int comm_check(irs_ctx *ctx, const irs_comm *c, const char *fn) {
     return IRS_OK;
 }
 
+// the same three for the other translation units (ce_sharded.hip)
+int irs_comm_check(irs_ctx *ctx, const irs_comm *c, const char *fn) { return comm_check(ctx, c, fn); }
+int irs_comm_allgather(irs_ctx *ctx, irs_comm *c, const void *send, void *recv, size_t bytes, hipStream_t s) {
+    return comm_allgather(ctx, c, send, recv, bytes, s);
+}
+int irs_comm_alltoall(irs_ctx *ctx, irs_comm *c, const void *send, void *recv, size_t bytes, hipStream_t s) {
+    return comm_alltoall(ctx, c, send, recv, bytes, s);
+}
+
 extern "C" int irs_allgather_rows(irs_ctx *ctx, irs_comm *comm, const float *rows_local, int32_t B, float *rows_all, void *stream) {
     int rc = comm_check(ctx, comm, "irs_allgather_rows");
     if (rc) return rc;

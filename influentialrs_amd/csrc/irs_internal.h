@@ -163,6 +163,7 @@ struct irs_ctx {
     float *x_local;           // [max_seqs][d] this rank's decoded rows (the all-gather's send buffer)
     uint64_t *keys_send, *keys_recv; // [max_rows][max_k] packed per-shard lists
     float *lse_gmax;          // [max_rows] all-reduced row maxima
+    float *ce_pairs;          // [world][2][max_rows] gathered per-shard (lse, label score) of irs_ce_forward_sharded
     int sh_nograph;           // a capture with the collectives inside failed: the sharded loops stay on stream launches
     int sh_overlap;           // irs_set_sharded_overlap: the greedy sharded loop runs two user micro-batches per step, collectives on sh_side
     hipStream_t sh_side;      // (created on first use)
@@ -255,6 +256,16 @@ int irs_launch_ce_reduce(irs_ctx *ctx, const float *lse, const float *lab_score,
                          hipStream_t s);
 int irs_launch_ce_grad(irs_ctx *ctx, const float *xrows, const int64_t *labels0, const float *lse, int M, float scale,
                        float *out, int64_t ld, hipStream_t s);
+
+// ---- ce_backward.hip ---- (the fused backward over this context's shard; arguments already validated)
+size_t irs_ce_bwd_scratch(const irs_ctx *ctx, int M);
+int irs_launch_ce_backward(irs_ctx *ctx, const float *xrows, const int64_t *labels0, const float *lse, int M, float scale,
+                           int accumulate, float *dx, float *dw, float *db, void *scratch, hipStream_t s);
+
+// ---- comm.hip ---- (collectives in bytes, stream-ordered; irs_comm_check: the communicator is the context's shard)
+int irs_comm_check(irs_ctx *ctx, const irs_comm *c, const char *fn);
+int irs_comm_allgather(irs_ctx *ctx, irs_comm *c, const void *send, void *recv, size_t bytes_per_rank, hipStream_t s);
+int irs_comm_alltoall(irs_ctx *ctx, irs_comm *c, const void *send, void *recv, size_t bytes_per_rank, hipStream_t s);
 
 // ---- path.hip ----
 int irs_launch_merge(irs_ctx *ctx, const float *val_in, const int64_t *ids_in, int W, int M, int k, float *val,

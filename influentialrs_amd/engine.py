@@ -518,6 +518,56 @@ class Engine:
         status = status.clone()
         return (paths, scores, status, fin) if want_windows else (paths, scores, status)
 
+    # ---- projection + cross entropy over the item-sharded catalog (ce_sharded.hip); every rank calls them together
+    def ce_forward_sharded(self, comm: "Comm", xrows: torch.Tensor, labels0: torch.Tensor):
+        """ce_forward of this rank's B rows (the same B on every rank; labels0 global 0-based, -1 = ignored) against the
+        WHOLE catalog: (lse[B], label_score[B], loss[3] float64 over the rows of the whole world, identical on every rank)."""
+        xrows = self._dev(xrows, torch.float32)
+        labels0 = self._dev(labels0, torch.int64)
+        if xrows.dim() != 2 or xrows.shape[1] != self.d or tuple(labels0.shape) != (xrows.shape[0],):
+            raise IrsError(f"ce_forward_sharded: rows {tuple(xrows.shape)} / labels {tuple(labels0.shape)}, expected "
+                           f"[B, {self.d}] / [B]")
+        B = xrows.shape[0]
+        lse = torch.empty(B, dtype=torch.float32, device=self.device)
+        ls = torch.empty(B, dtype=torch.float32, device=self.device)
+        loss = torch.empty(3, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.irs_ce_forward_sharded(self.h, comm.h, _ptr(xrows), _ptr(labels0), B, _ptr(lse), _ptr(ls),
+                                                        _ptr(loss), self._stream()))
+        return lse, ls, loss
+
+    def ce_backward_sharded_scratch_bytes(self, B: int) -> int:
+        n = self.lib.irs_ce_backward_sharded_scratch_bytes(self.h, B)
+        if n == 0:
+            raise IrsError(f"ce_backward_sharded: no scratch size for B={B} (need 1 <= world * B <= max_rows={self.max_rows})")
+        return n
+
+    def ce_backward_sharded(self, comm: "Comm", xrows: torch.Tensor, labels0: torch.Tensor, lse: torch.Tensor, scale: float,
+                            accumulate: bool, dx: torch.Tensor, dw: torch.Tensor, db: torch.Tensor, scratch: torch.Tensor):
+        """ce_backward over the item-sharded catalog (irs_ce_backward_sharded): dx[B, d] of this rank's rows (overwritten),
+        dw[n_local, d] / db[n_local] of this rank's shard (+)= over the rows of the whole world.  lse: ce_forward_sharded's.
+        scratch: uint8, at least ce_backward_sharded_scratch_bytes(B) bytes."""
+        xrows = self._dev(xrows, torch.float32)
+        labels0 = self._dev(labels0, torch.int64)
+        lse = self._dev(lse, torch.float32)
+        if xrows.dim() != 2 or xrows.shape[1] != self.d:
+            raise IrsError(f"ce_backward_sharded: rows of shape {tuple(xrows.shape)}, expected [B, {self.d}]")
+        B = xrows.shape[0]
+        if tuple(labels0.shape) != (B,) or tuple(lse.shape) != (B,):
+            raise IrsError(f"ce_backward_sharded: labels {tuple(labels0.shape)} / lse {tuple(lse.shape)}, expected [{B}]")
+        dx = self._inplace(dx, torch.float32, "ce_backward_sharded dx")
+        dw = self._inplace(dw, torch.float32, "ce_backward_sharded dw")
+        db = self._inplace(db, torch.float32, "ce_backward_sharded db")
+        scratch = self._inplace(scratch, torch.uint8, "ce_backward_sharded scratch")
+        if tuple(dx.shape) != (B, self.d) or tuple(dw.shape) != (self.n_local, self.d) or tuple(db.shape) != (self.n_local,):
+            raise IrsError(f"ce_backward_sharded: dx {tuple(dx.shape)} / dw {tuple(dw.shape)} / db {tuple(db.shape)}, expected "
+                           f"{(B, self.d)} / {(self.n_local, self.d)} / {(self.n_local,)}")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.irs_ce_backward_sharded(self.h, comm.h, _ptr(xrows), _ptr(labels0), _ptr(lse), B, float(scale),
+                                                         1 if accumulate else 0, _ptr(dx), _ptr(dw), _ptr(db), _ptr(scratch),
+                                                         scratch.numel(), self._stream()))
+        return dx, dw, db
+
     # ------------------------------------------------------------------ decoder GEMM arithmetic
     @property
     def decoder_gemm(self) -> int:

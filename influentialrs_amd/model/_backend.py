@@ -72,6 +72,36 @@ class HipBackend:
                 proj.out_features = hi - lo
             self._fp = None
 
+    def holds_shard(self) -> bool:
+        """Item-sharded AND the module's own project.* are cut down to this rank's rows (set_sharding with drop_full): the
+        loss then has to be the vocabulary-parallel one (project_ce_sharded)."""
+        proj = getattr(self.net, "project", None)
+        if self.world <= 1 or proj is None:
+            return False
+        from ..engine import shard_bounds
+        lo, hi = shard_bounds(self.net.n_item, self.world, self.rank)
+        return proj.weight.shape[0] == hi - lo < self.net.n_item
+
+    def allreduce_replicated_grads(self):
+        """After loss.backward() of a sharded training step: every parameter but project.* is replicated and holds the
+        gradient of this rank's rows only -- SUM over torch.distributed, as ONE flat buffer, so that the replicas take
+        the same optimizer step.  project.* gradients are complete for the shard (irs_ce_backward_sharded) and stay."""
+        import torch.distributed as dist
+        grads = [p_.grad for n, p_ in self.net.named_parameters() if not n.startswith("project.") and p_.grad is not None]
+        if self.world <= 1 or not grads:
+            return
+        flat = torch.cat([g.reshape(-1) for g in grads])
+        if dist.get_backend() == "gloo" and flat.is_cuda:  # (gloo is only dependable on host tensors: ..dist.ShardGroup)
+            h = flat.cpu()
+            dist.all_reduce(h, op=dist.ReduceOp.SUM)
+            flat.copy_(h)
+        else:
+            dist.all_reduce(flat, op=dist.ReduceOp.SUM)
+        off = 0
+        for g in grads:
+            g.copy_(flat[off:off + g.numel()].view_as(g))
+            off += g.numel()
+
     def _fingerprint(self):
         return tuple((t.data_ptr(), t._version) for t in self.net.state_dict(keep_vars=True).values())
 
@@ -201,6 +231,72 @@ class _ProjectCE(torch.autograd.Function):
             db += Gc.sum(0)
         sc = (g.double() / tot[1]).to(torch.float32)  # dL/dloss / n_valid, kept on the device
         return dx * sc, dW * sc, db * sc, None, None, None
+
+
+class _ProjectCESharded(torch.autograd.Function):
+    """_ProjectCE over an item-sharded catalog: `weight` / `bias` are this rank's rows of project.*, x / labels0 this rank's
+    rows of the batch (the SAME number on every rank; labels global), and the loss is the mean over the valid rows of the
+    WHOLE world -- identical on every rank.  forward = irs_ce_forward_sharded per row block, backward =
+    irs_ce_backward_sharded with `accumulate` across blocks, scaled by g / global n_valid: dx of the own rows, dW / db of
+    the own shard over the world's rows (complete: never reduced over ranks).  Both ce_backward settings take this route:
+    under sharding "chunked" runs the fused kernels too (a dL/dlogits chunk of the world's rows per rank is what sharding
+    is there to avoid).  A block is ROWS / world rows per rank, so the engine's workspace is that of the unsharded loss."""
+
+    @staticmethod
+    def _block(world):
+        return max(1, _ProjectCE.ROWS // world)
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, labels0, backend, may_update):
+        M = x.shape[0]
+        blk = _ProjectCESharded._block(backend.world)
+        eng = backend.get(1, backend.world * min(M, blk), for_training=True, may_update=may_update)
+        xd = x.detach().contiguous()
+        lse = torch.empty(M, dtype=torch.float32, device=x.device)
+        tot = torch.zeros(3, dtype=torch.float64, device=x.device)
+        for c0 in range(0, M, blk):
+            c1 = min(M, c0 + blk)
+            l, _, t = eng.ce_forward_sharded(backend.comm, xd[c0:c1], labels0[c0:c1])
+            lse[c0:c1] = l
+            tot += t
+        _, n_valid, n_bad = tot.tolist()  # (the triple is the world's: every rank takes the same branch below)
+        if n_bad > 0:
+            raise IndexError(f"Target out of bounds: {int(n_bad)} label(s) >= n_item {backend.net.n_item} (nn.CrossEntropyLoss "
+                             "raises here, reference influentialRS.py:270,301)")
+        ctx.save_for_backward(xd, weight, labels0, lse, tot)
+        ctx.backend = backend
+        ctx.n_valid = n_valid
+        if n_valid == 0:
+            return torch.full((), float("nan"), dtype=torch.float32, device=x.device)
+        return (tot[0] / tot[1]).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        xd, weight, labels0, lse, tot = ctx.saved_tensors
+        M, d = xd.shape
+        N = weight.shape[0]
+        if ctx.n_valid == 0:
+            return torch.zeros_like(xd), torch.zeros_like(weight), torch.zeros(N, dtype=torch.float32, device=xd.device), None, None, None
+        backend = ctx.backend
+        blk = _ProjectCESharded._block(backend.world)
+        eng = backend.get(1, backend.world * min(M, blk), for_training=True)
+        dx = torch.empty_like(xd)
+        dW = torch.empty_like(weight)
+        db = torch.empty(N, dtype=torch.float32, device=xd.device)
+        blocks = {min(M, blk), M % blk or blk} if M > blk else {M}
+        scratch = torch.empty(max(eng.ce_backward_sharded_scratch_bytes(m) for m in blocks), dtype=torch.uint8, device=xd.device)
+        for c0 in range(0, M, blk):
+            c1 = min(M, c0 + blk)
+            eng.ce_backward_sharded(backend.comm, xd[c0:c1], labels0[c0:c1], lse[c0:c1], 1.0, c0 > 0, dx[c0:c1], dW, db, scratch)
+        sc = (g.double() / tot[1]).to(torch.float32)
+        return dx.mul_(sc), dW.mul_(sc), db.mul_(sc), None, None, None
+
+
+def project_ce_sharded(x: torch.Tensor, project: nn.Linear, labels0: torch.Tensor, backend: "HipBackend") -> torch.Tensor:
+    """project_ce for a module that holds only its shard of project.* (HipBackend.holds_shard): the global loss, the same
+    scalar on every rank.  Every rank calls it together, with the same number of rows."""
+    may_update = torch.is_grad_enabled() and (x.requires_grad or project.weight.requires_grad or project.bias.requires_grad)
+    return _ProjectCESharded.apply(x, project.weight, project.bias, labels0, backend, may_update)
 
 
 def project_ce(x: torch.Tensor, project: nn.Linear, labels0: torch.Tensor, backend: "HipBackend") -> torch.Tensor:

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 import torch.optim as optim
 
-from ._backend import make_scheduler, project_ce
+from ._backend import make_scheduler, project_ce, project_ce_sharded
 from .layers import get_end_index
 
 
@@ -36,7 +36,9 @@ class Evaluator(nn.Module):
         rows = x.reshape(-1, net.embed_dim)
         tgt = target[:, 1:].reshape(-1)
         labels0 = torch.where(tgt.gt(self.PAD_ID), tgt - 1, torch.full_like(tgt, -1)).to(torch.int64)
-        if net._hip.world != 1 or rows.device.type != "cuda":  # sharded or CPU module: the reference's own formulation
+        if rows.device.type == "cuda" and net._hip.holds_shard():  # the module holds only its rows of project.*
+            return project_ce_sharded(rows, net.project, labels0, net._hip)
+        if net._hip.world != 1 or rows.device.type != "cuda":  # whole module on a sharded engine, or CPU: the reference's own formulation
             out = net.project(rows)
             mask = labels0.ge(0)
             return self.loss_function(out[mask], labels0[mask])
@@ -47,6 +49,8 @@ class Evaluator(nn.Module):
         loss = self._masked_loss(target)
         self.optimizer.zero_grad()
         loss.backward()
+        if self.net._hip.holds_shard():  # replicated parameters: SUM of the ranks' gradients; project.* stay local
+            self.net._hip.allreduce_replicated_grads()
         self.optimizer.step()
         return loss.item()
 

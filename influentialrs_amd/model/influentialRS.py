@@ -30,7 +30,7 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from .._lib import IRS_MASK_IRN, IRS_ROW_NO_CANDIDATE
-from ._backend import HipBackend, check_trunk, make_scheduler, pad_ragged_ids, project_ce, train_trunk_default, trunk_hip
+from ._backend import HipBackend, check_trunk, make_scheduler, pad_ragged_ids, project_ce, project_ce_sharded, train_trunk_default, trunk_hip
 from .layers import PositionalEncoding, get_item_index
 
 _SHARDED_GRAPH = os.environ.get("IRS_SHARDED_GRAPH", "0") == "1"  # captured sharded steps: opt-in (see _beam_paths)
@@ -100,8 +100,14 @@ class InfluentialNet(nn.Module):
     def shard_items(self, rank: int, world: int, drop_full: bool = True):
         """Hold only rows [lo, hi) of the catalog on this GPU.  With drop_full (default) the
         module's own project.weight / project.bias are cut down to the shard -- call it after
-        load_state_dict: from then on this rank's state_dict() carries the LOCAL rows only and the
-        training-mode forward (a full nn.Linear) is not available on it."""
+        load_state_dict: from then on this rank's state_dict() carries the LOCAL rows only.  forward() (the
+        [B, L, n_item] logits of a full nn.Linear) is not available on such a module; the handlers' losses are:
+        IRSNN / Evaluator.train_batch and get_loss_on_eval_data take the vocabulary-parallel projection + cross
+        entropy (include/irs_hip.h irs_ce_forward_sharded / irs_ce_backward_sharded) -- every rank passes its own
+        slice of the batch (the same number of sequences), gets the loss of the WHOLE batch, and train_batch
+        SUM-all-reduces the gradients of the replicated parameters before its optimizer step; project.* gradients
+        are the shard's own.  Both ce_backward settings run the fused kernels there.  A module kept whole
+        (drop_full=False) keeps the reference's own formulation on its full nn.Linear."""
         self._hip.set_sharding(rank, world, drop_full)
 
     # ---- training-mode path: stock PyTorch autograd, per-row as-called mask
@@ -192,7 +198,9 @@ class IRSNN(nn.Module):
         rows = x[:, :-1, :].reshape(-1, net.embed_dim)
         tgt = seqs[:, 1:].reshape(-1)
         labels0 = torch.where(tgt.gt(self.PAD_ID), tgt - 1, torch.full_like(tgt, -1)).to(torch.int64)
-        if net._hip.world != 1 or rows.device.type != "cuda":  # sharded or CPU module: the reference's own formulation
+        if rows.device.type == "cuda" and net._hip.holds_shard():  # the module holds only its rows of project.*
+            return project_ce_sharded(rows, net.project, labels0, net._hip)
+        if net._hip.world != 1 or rows.device.type != "cuda":  # whole module on a sharded engine, or CPU: the reference's own formulation
             out = net.project(rows)
             mask = labels0.ge(0)
             return self.loss_function(out[mask], labels0[mask])
@@ -210,6 +218,8 @@ class IRSNN(nn.Module):
         loss = self._masked_loss(seqs, users)
         self.optimizer.zero_grad()
         loss.backward()
+        if self.net._hip.holds_shard():  # replicated parameters: SUM of the ranks' gradients; project.* stay local
+            self.net._hip.allreduce_replicated_grads()
         self.optimizer.step()
         return loss.item()
 
