@@ -354,6 +354,34 @@ int irs_generate_paths(irs_ctx *ctx, int64_t *dev_seq, const int64_t *dev_user, 
                        int32_t max_path_len, int32_t k, int32_t sweep, int32_t sample, int32_t sample_k,
                        uint64_t seed, int32_t use_graph, float *dev_paths, int32_t *dev_status, void *stream);
 
+/* irs_generate_paths that stops where it has arrived (the reference never does: "the tail is zeroed afterwards",
+ * influentialRS.py:459-467, after every user has been decoded and scored max_path_len times).  A user's target is
+ * seq[b][L-1]; the user is FINISHED after the first step whose chosen item equals it.  dev_paths [B, max_path_len] holds the
+ * chosen items up to and including the target and exact 0.0f after it: what irs_generate_paths followed by the reference's
+ * host zeroing produces, id for id.  A user who never reaches its target gets the row irs_generate_paths writes.  dev_status
+ * keeps the bits of a row's live steps.
+ * The steps run on the caller's stream.  After every check_every-th step (>= 1) the live users are compacted on the device
+ * (stable order, an index map back to the caller's rows; compacted seq / user / hep live in the bound workspace, nothing is
+ * allocated) and the live count comes to the host in ONE 4-byte asynchronous copy followed by a wait for the stream: that
+ * host read per check is the price of deciding the next step's batch size, and the reason this loop is never replayed from a
+ * hipGraph (no use_graph).  The following steps decode, score and step the live rows only; the call returns as soon as none
+ * is left.  Between two checks a finished user may still be stepped; its path tail stays zero.  The first step after a
+ * compaction that removed rows selects its top-k thresholds afresh (irs_score_topk, not _carry).
+ *  dev_seq / dev_hep: the working state, modified; the rows of FINISHED users are unspecified afterwards (and once rows have
+ *            been removed, the rows of the others stop where the compaction left them): pass a copy.
+ *  host_stats int64 [2], HOST memory, may be NULL: { steps_run, row_steps }, row_steps = the sum over the steps run of the
+ *            rows decoded in that step (irs_generate_paths: max_path_len and B * max_path_len).
+ * Checks, before any launch: those of irs_generate_paths; check_every < 1 -> IRS_E_INVALID; world != 1 and
+ * max_path_len > 64 (the staging rows of the workspace) -> IRS_E_UNSUPPORTED.
+ * On any other error (a HIP error inside the loop) the call returns at once: host_stats is not written and dev_paths, dev_status,
+ * dev_seq and dev_hep hold the steps enqueued so far -- treat all of them as unspecified.
+ * sample != 0 is allowed and deterministic (two identical calls give identical paths), but a user's draws are NOT those of
+ * irs_generate_paths for the same seed: the counter RNG is keyed by the launch row, and compaction changes launch rows.
+ * Sampled mode is distribution-level parity either way. */
+int irs_generate_paths_until(irs_ctx *ctx, int64_t *dev_seq, const int64_t *dev_user, int32_t *dev_hep, int32_t B,
+                             int32_t max_path_len, int32_t k, int32_t sweep, int32_t sample, int32_t sample_k, uint64_t seed,
+                             int32_t check_every, float *dev_paths, int32_t *dev_status, int64_t *host_stats, void *stream);
+
 /* ---- beam search over persuasion paths (BUILD-DEFINED: the reference has no beam
  *      search -- SURVEY fact 4; BASELINE.json config 5).  Beam width W <= 32, path
  *      length P <= 64.  W == 1 is the greedy search of irs_generate_paths id for id, for every row that has a

@@ -80,6 +80,8 @@ SIGNATURES = {
                                 c_int32, c_int32, c_int32, c_uint64, c_void_p, c_void_p]),
     "irs_generate_paths": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                      c_int32, c_uint64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "irs_generate_paths_until": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                           c_int32, c_uint64, c_int32, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
     "irs_beam_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p]),

@@ -266,6 +266,7 @@ extern "C" int irs_finalize_weights(irs_ctx *ctx, void *arena, size_t bytes, voi
 struct ws_plan {
     size_t x, y, xf, yf, qkv, qkv_b1, ao, h, ru, xb, eps, thr, gm, cnt, cand, lse, ref, xrows, tval, tids, status, step, pos;
     size_t bseq[2], bhep[2], bcum[2], bpaths[2], buser, lmax, lsum, tokrow, scnt, soff, sqrow, spadq, mdev, tseq, tidx, srow0, qtile, nwg, xlocal, ksend, krecv, gmax, cepairs, fbcount, fblist, exhkeys, total;
+    size_t useq[2], uuser[2], uhep[2], umap[2], ufin, udst, ustatus, ustage, ucount;
 };
 
 static void workspace_plan(const irs_ctx *ctx, ws_plan *p) {
@@ -338,6 +339,17 @@ static void workspace_plan(const irs_ctx *ctx, ws_plan *p) {
     p->fbcount = take(256);
     p->fblist = take((size_t)ctx->max_rows * 4);
     p->exhkeys = ctx->n_local >= IRS_COOP_FALLBACK_MIN_ITEMS ? take((size_t)IRS_EXH_SCRATCH_KEYS * 8) : 0;
+    for (int i = 0; i < 2; ++i) { // irs_generate_paths_until: the live users' compacted state
+        p->useq[i] = take((size_t)ctx->max_seqs * D.max_len * 8);
+        p->uuser[i] = take((size_t)ctx->max_seqs * 8);
+        p->uhep[i] = take((size_t)ctx->max_seqs * 4);
+        p->umap[i] = take((size_t)ctx->max_seqs * 4);
+    }
+    p->ufin = take((size_t)ctx->max_seqs * 4);
+    p->udst = take((size_t)ctx->max_seqs * 4);
+    p->ustatus = take((size_t)ctx->max_seqs * 4);
+    p->ustage = take((size_t)ctx->max_seqs * IRS_MAX_PATH * 4);
+    p->ucount = take(256);
     p->total = off;
 }
 
@@ -411,6 +423,17 @@ extern "C" int irs_bind_workspace(irs_ctx *ctx, void *ws, size_t bytes) {
     ctx->fb_count = (unsigned int *)(b + p.fbcount);
     ctx->fb_list = (int32_t *)(b + p.fblist);
     ctx->exh_keys = ctx->n_local >= IRS_COOP_FALLBACK_MIN_ITEMS ? (unsigned long long *)(b + p.exhkeys) : nullptr;
+    for (int i = 0; i < 2; ++i) {
+        ctx->un_seq[i] = (int64_t *)(b + p.useq[i]);
+        ctx->un_user[i] = (int64_t *)(b + p.uuser[i]);
+        ctx->un_hep[i] = (int32_t *)(b + p.uhep[i]);
+        ctx->un_map[i] = (int32_t *)(b + p.umap[i]);
+    }
+    ctx->un_fin = (int32_t *)(b + p.ufin);
+    ctx->un_dst = (int32_t *)(b + p.udst);
+    ctx->un_status = (int32_t *)(b + p.ustatus);
+    ctx->un_stage = (float *)(b + p.ustage);
+    ctx->un_count = (int32_t *)(b + p.ucount);
     irs_drop_graphs(ctx);
     return IRS_OK;
 }
@@ -778,6 +801,68 @@ extern "C" int irs_generate_paths(irs_ctx *ctx, int64_t *seq, const int64_t *use
     for (int i = 0; i < max_path_len; ++i) // (steps behind the first may reuse the previous step's emission thresholds)
         if ((rc = enqueue_step(ctx, seq, user, hep, B, k, sweep, sample, sample_k, seed, paths, max_path_len, status, s, i > 0)))
             return rc;
+    return IRS_OK;
+}
+
+// The same search, stopped where it has arrived: a user is finished after the step that chose its target (seq[b][L - 1]).  Steps
+// run on the live users only, compacted (stable order) into the workspace after every check_every-th step; the chosen item of a
+// compacted row is scattered to the caller's row through the index map.  The batch size of a step is decided on the host from a
+// 4-byte copy of the live count, so this loop is never captured.
+extern "C" int irs_generate_paths_until(irs_ctx *ctx, int64_t *seq, const int64_t *user, int32_t *hep, int32_t B,
+                                        int32_t max_path_len, int32_t k, int32_t sweep, int32_t sample, int32_t sample_k,
+                                        uint64_t seed, int32_t check_every, float *paths, int32_t *status, int64_t *host_stats,
+                                        void *stream) {
+    int rc = ready_filter(ctx, sweep);
+    if (rc) return rc;
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_generate_paths_until needs the whole catalog on one device");
+    if (!seq || !hep || !paths || !status || B < 1 || max_path_len < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths_until: bad arguments");
+    if (B > ctx->max_seqs || B > ctx->max_rows) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths_until: B too large");
+    if ((rc = irs_check_k(ctx, "irs_generate_paths_until", k, 1, sweep, sample, sample_k))) return rc;
+    if (check_every < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths_until: check_every must be >= 1");
+    if (max_path_len > IRS_MAX_PATH)
+        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_generate_paths_until: max_path_len %d > %d", max_path_len, IRS_MAX_PATH);
+    hipStream_t s = (hipStream_t)stream;
+    const int P = max_path_len;
+    if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
+    IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->un_fin, 0, sizeof(int32_t) * B, s));
+    IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->un_status, 0, sizeof(int32_t) * B, s));
+    // the first steps run in place on the caller's rows (identity map); the first compaction that removes a row moves the rest
+    int64_t *cseq = seq;
+    const int64_t *cuser = user;
+    int32_t *chep = hep;
+    const int32_t *cmap = nullptr;
+    int live = B, side = 0, carry = 0;
+    int64_t steps = 0, row_steps = 0;
+    // (an error below returns at once: host_stats unwritten, paths / status / seq / hep partly written -- see the header; the step
+    //  counter pair is left wherever the last step put it, and every search loop resets it in irs_search_begin)
+    for (int i = 0; i < P && live > 0; ++i) {
+        // (the step writes stage[row][i]: it reads the index from the same device counter as irs_generate_paths' steps)
+        if ((rc = enqueue_step(ctx, cseq, cuser, chep, live, k, sweep, sample, sample_k, seed, ctx->un_stage, P, ctx->un_status, s, carry)))
+            return rc;
+        if ((rc = irs_launch_until_record(ctx, ctx->un_stage, P, i, cmap, cseq, live, ctx->un_fin, ctx->un_status, paths, status, s)))
+            return rc;
+        ++steps, row_steps += live, carry = 1;
+        if ((i + 1) % check_every || i + 1 == P) continue; // no check due, or nothing left to decide after the last step
+        if ((rc = irs_launch_until_scan(ctx, ctx->un_fin, live, ctx->un_dst, ctx->un_count, s))) return rc;
+        IRS_CHECK_HIP(ctx, hipMemcpyAsync(&ctx->un_count_host, ctx->un_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        IRS_CHECK_HIP(ctx, hipStreamSynchronize(s));
+        const int left = ctx->un_count_host;
+        if (left < 0 || left > live) IRS_FAIL(ctx, IRS_E_STATE, "irs_generate_paths_until: live count %d of %d rows", left, live);
+        if (left == live) continue;
+        if (left > 0) {
+            if ((rc = irs_launch_until_gather(ctx, ctx->un_dst, live, cseq, cuser, chep, cmap, ctx->un_seq[side], ctx->un_user[side],
+                                              ctx->un_hep[side], ctx->un_map[side], s)))
+                return rc;
+            cseq = ctx->un_seq[side], cuser = cuser ? ctx->un_user[side] : nullptr, chep = ctx->un_hep[side], cmap = ctx->un_map[side];
+            side ^= 1;
+            IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->un_fin, 0, sizeof(int32_t) * left, s));
+            // B <= 64 hands the step index over in a second word that larger batches do not keep: both words, from the host's count
+            if ((rc = irs_launch_set_step(ctx, ctx->step_ctr, i + 1, s))) return rc;
+        }
+        live = left;
+        carry = 0; // other rows, another M: the next top-k selects its thresholds afresh
+    }
+    if (host_stats) host_stats[0] = steps, host_stats[1] = row_steps;
     return IRS_OK;
 }
 

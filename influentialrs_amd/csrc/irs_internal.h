@@ -159,6 +159,17 @@ struct irs_ctx {
     float *bm_paths[2];  // [max_seqs][IRS_MAX_PATH]
     int64_t *bm_user;    // [max_seqs]
     float *lse_max, *lse_sum; // [max_rows]
+    // stop-at-target search (irs_generate_paths_until): the live users' compacted state, ping-pong [2]
+    int64_t *un_seq[2];  // [max_seqs][L]
+    int64_t *un_user[2]; // [max_seqs]
+    int32_t *un_hep[2];  // [max_seqs]
+    int32_t *un_map[2];  // [max_seqs] compacted row -> the caller's row
+    int32_t *un_fin;     // [max_seqs] the compacted row has chosen its target
+    int32_t *un_dst;     // [max_seqs] row of a live user after the next compaction (-1: finished)
+    int32_t *un_status;  // [max_seqs] status bits of the step just run, by compacted row
+    float *un_stage;     // [max_seqs][IRS_MAX_PATH] chosen items by compacted row (column `step` is read, then scattered)
+    int32_t *un_count;   // [1] live users
+    int32_t un_count_host; // where the 4-byte copy of un_count lands
     // item-sharded loops (comm.hip)
     float *x_local;           // [max_seqs][d] this rank's decoded rows (the all-gather's send buffer)
     uint64_t *keys_send, *keys_recv; // [max_rows][max_k] packed per-shard lists
@@ -276,6 +287,14 @@ int irs_launch_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int B, const 
                          int step, const int32_t *step_ptr, float *paths, int path_ld, int sample, int sample_k,
                          uint64_t seed, int32_t *status, hipStream_t s, int32_t *step_next = nullptr);
 int irs_launch_inc(irs_ctx *ctx, int32_t *ctr, hipStream_t s);
+// the stop-at-target loop's own kernels (irs_generate_paths_until, capi.hip); map == nullptr is the identity
+int irs_launch_until_record(irs_ctx *ctx, const float *stage, int P, int step, const int32_t *map, const int64_t *seq, int B,
+                            int32_t *fin, int32_t *step_status, float *paths, int32_t *status, hipStream_t s);
+int irs_launch_until_scan(irs_ctx *ctx, const int32_t *fin, int B, int32_t *dst, int32_t *count, hipStream_t s);
+int irs_launch_until_gather(irs_ctx *ctx, const int32_t *dst, int B, const int64_t *seq, const int64_t *user, const int32_t *hep,
+                            const int32_t *map, int64_t *seq_out, int64_t *user_out, int32_t *hep_out, int32_t *map_out,
+                            hipStream_t s);
+int irs_launch_set_step(irs_ctx *ctx, int32_t *step_pair, int step, hipStream_t s);
 int irs_launch_beam_init(irs_ctx *ctx, const int64_t *seq0, const int64_t *user0, const int32_t *hep0, int B, int W,
                          int P, int64_t *seq, int64_t *user, int32_t *hep, double *cum, float *paths, hipStream_t s);
 int irs_launch_beam_step(irs_ctx *ctx, const int64_t *seq_in, const int32_t *hep_in, const double *cum_in,

@@ -288,6 +288,120 @@ int irs_launch_inc(irs_ctx *ctx, int32_t *ctr, hipStream_t s) {
     return IRS_OK;
 }
 
+// ------------------------------------------------------------------ stop-at-target search (irs_generate_paths_until)
+// The reference never stops at the target: it runs every step for every user and zeroes the tail on the host afterwards
+// (model/influentialRS.py:459-467).  Here a user is finished after the step that chose seq[b][L - 1]; the three kernels below
+// record a step of the live (compacted) rows into the caller's rows, and compact the rows that are still live.
+
+// After a step on B compacted rows: the chosen item (stage[r][step]) and the step's status bits go to the caller's row map[r].
+// The comparison is the host's (float32 path entry == int64 target, both as doubles).  A row that finishes here gets its tail
+// zeroed once; a row that finished at an earlier step (still stepped until the next compaction) writes nothing.  One wave per row.
+// `stage` is never cleared: this kernel relies on the path step writing stage[r][step] for EVERY row of EVERY step -- the chosen item,
+// or 0 for a row without a candidate (irs_path_step_row writes paths[row][step] before it looks at `found`) -- so that no entry of
+// an earlier step or call is ever read.  All lanes of the row's wave read fin[r] and step_status[r] before lane 0 rewrites them.
+__global__ void __launch_bounds__(256) k_until_record(const float *__restrict__ stage, int P, int step,
+                                                      const int32_t *__restrict__ map, const int64_t *__restrict__ seq, int L, int B,
+                                                      int32_t *__restrict__ fin, int32_t *__restrict__ step_status,
+                                                      float *__restrict__ paths, int32_t *__restrict__ status) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= B) return;
+    const int was = fin[r];
+    const int bits = step_status[r];
+    if (bits && lane == 0) step_status[r] = 0;
+    if (was) return;
+    const int orig = map ? map[r] : r;
+    const float item = stage[(size_t)r * P + step];
+    const bool done = (double)item == (double)seq[(size_t)r * L + L - 1];
+    float *row = paths + (size_t)orig * P;
+    if (lane == 0) {
+        row[step] = item;
+        if (bits) status[orig] |= bits;
+        if (done) fin[r] = 1;
+    }
+    if (done)
+        for (int p = step + 1 + lane; p < P; p += 64) row[p] = 0.f;
+}
+
+// dst[r] = number of live rows before r (the row's place after compaction), -1 for a finished row; count[0] = live rows.
+// ONE workgroup walks the rows 1024 at a time: ballot + popcount inside a wave, the 16 wave totals through LDS.
+__global__ void __launch_bounds__(1024) k_until_scan(const int32_t *__restrict__ fin, int B, int32_t *__restrict__ dst,
+                                                     int32_t *__restrict__ count) {
+    __shared__ int s_wave[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int base = 0;
+    for (int r0 = 0; r0 < B; r0 += 1024) {
+        const int r = r0 + tid;
+        const bool live = r < B && fin[r] == 0;
+        const unsigned long long m = __ballot(live);
+        const int before = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wave[wave] = __popcll(m);
+        __syncthreads();
+        int off = 0, total = 0;
+        for (int w = 0; w < 16; ++w) {
+            const int c = s_wave[w];
+            off += w < wave ? c : 0;
+            total += c;
+        }
+        if (r < B) dst[r] = live ? base + off + before : -1;
+        base += total;
+        __syncthreads();
+    }
+    if (tid == 0) count[0] = base;
+}
+
+// Row r of the current state moves to row dst[r] of the other buffer set (never in place); one wave per row.
+__global__ void __launch_bounds__(256) k_until_gather(const int32_t *__restrict__ dst, int B, int L,
+                                                      const int64_t *__restrict__ seq, const int64_t *__restrict__ user,
+                                                      const int32_t *__restrict__ hep, const int32_t *__restrict__ map,
+                                                      int64_t *__restrict__ seq_out, int64_t *__restrict__ user_out,
+                                                      int32_t *__restrict__ hep_out, int32_t *__restrict__ map_out) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= B) return;
+    const int t = dst[r];
+    if (t < 0) return;
+    for (int p = lane; p < L; p += 64) seq_out[(size_t)t * L + p] = seq[(size_t)r * L + p];
+    if (lane == 0) {
+        if (user) user_out[t] = user[r];
+        hep_out[t] = hep[r];
+        map_out[t] = map ? map[r] : r;
+    }
+}
+
+__global__ void k_set_step(int32_t *step_pair, int step) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) step_pair[0] = step, step_pair[1] = step;
+}
+
+int irs_launch_until_record(irs_ctx *ctx, const float *stage, int P, int step, const int32_t *map, const int64_t *seq, int B,
+                            int32_t *fin, int32_t *step_status, float *paths, int32_t *status, hipStream_t s) {
+    hipLaunchKernelGGL(k_until_record, dim3((B + 3) / 4), dim3(256), 0, s, stage, P, step, map, seq, ctx->dims.max_len, B, fin,
+                       step_status, paths, status);
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
+int irs_launch_until_scan(irs_ctx *ctx, const int32_t *fin, int B, int32_t *dst, int32_t *count, hipStream_t s) {
+    hipLaunchKernelGGL(k_until_scan, dim3(1), dim3(1024), 0, s, fin, B, dst, count);
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
+int irs_launch_until_gather(irs_ctx *ctx, const int32_t *dst, int B, const int64_t *seq, const int64_t *user, const int32_t *hep,
+                            const int32_t *map, int64_t *seq_out, int64_t *user_out, int32_t *hep_out, int32_t *map_out,
+                            hipStream_t s) {
+    hipLaunchKernelGGL(k_until_gather, dim3((B + 3) / 4), dim3(256), 0, s, dst, B, ctx->dims.max_len, seq, user, hep, map, seq_out,
+                       user_out, hep_out, map_out);
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
+int irs_launch_set_step(irs_ctx *ctx, int32_t *step_pair, int step, hipStream_t s) {
+    hipLaunchKernelGGL(k_set_step, dim3(1), dim3(64), 0, s, step_pair, step);
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
 // ------------------------------------------------------------------ evaluation batch on the device
 // Replaces the per-user Python of DataProvider.get_random_evaluate_data (data_provider.py:398-449: history =
 // all but the last event, label = the last event, target = a random item absent from the last raw_len

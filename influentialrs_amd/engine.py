@@ -408,6 +408,33 @@ class Engine:
                                                 int(sample), sample_k, seed, int(use_graph), _ptr(paths), _ptr(status))
         return paths, status
 
+    def generate_paths_until(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
+                             k: int = 100, sweep: int = IRS_SWEEP_BF16, sample=False, sample_k=3, seed=0,
+                             check_every: int = 1, paths: Optional[torch.Tensor] = None,
+                             status: Optional[torch.Tensor] = None):
+        """generate_paths that stops a user at its target (seqs[b, L - 1]) and the call when nobody is left
+        (irs_generate_paths_until): returns (paths, status, steps_run, row_steps).  Paths are zero behind the target.
+        `seqs` and `hep` are working state: modified, and unspecified afterwards.  One host read of 4 bytes per check."""
+        seqs = self._inplace(seqs, torch.int64, "generate_paths_until: seqs")
+        hep = self._inplace(hep, torch.int32, "generate_paths_until: hep")
+        if users is not None:
+            users = self._dev(users, torch.int64)
+        B = seqs.shape[0]
+        if seqs.shape[1] != self.L or hep.shape[0] != B or (users is not None and users.shape[0] != B):
+            raise IrsError("generate_paths_until: inconsistent shapes")
+        if paths is None:
+            paths = torch.zeros((B, max_path_len), dtype=torch.float32, device=self.device)
+        if status is None:
+            status = torch.zeros(B, dtype=torch.int32, device=self.device)
+        paths = self._inplace(paths, torch.float32, "generate_paths_until: paths")
+        status = self._inplace(status, torch.int32, "generate_paths_until: status")
+        if paths.shape != (B, max_path_len):
+            raise IrsError("generate_paths_until: paths must be [B, max_path_len]")
+        stats = (ctypes.c_int64 * 2)(0, 0)
+        self._call(self.lib.irs_generate_paths_until, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
+                                                      int(sample), sample_k, seed, check_every, _ptr(paths), _ptr(status), stats)
+        return paths, status, int(stats[0]), int(stats[1])
+
     # ------------------------------------------------------------------ beam search (build-defined extension)
     def beam_step(self, state_in, val, ids0, lse, step: int, state_out, status):
         """One beam step; state = (seq[B,W,L] i64, hep[B,W] i32, cum[B,W] f64, paths[B,W,P] f32)."""

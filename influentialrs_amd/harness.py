@@ -90,6 +90,8 @@ def test_model(config, rows: Sequence, irn, device, result_dir: str = None, verb
         irn.eval()
         paths, histories, targets, reverse_ranks, r_us = [], [], [], [], []
         n_early_success, hit = 0, 0
+        # (config.stop_at_target: the search stops a user at its target; a handler without the keyword is called as before)
+        stop = {"stop_at_target": True} if getattr(config, "stop_at_target", False) else {}
         for raw, seq, u, t, l in eval_batches_irs(rows, config.batch_size, config.max_len, config.gap_len):
             t, l, u, seq = t.to(device), l.to(device), u.to(device), seq.to(device)
             r_u = irn.get_pif_in_batch(seq, u)
@@ -98,7 +100,7 @@ def test_model(config, rows: Sequence, irn, device, result_dir: str = None, verb
             hit += hit_count
             reverse_ranks = rr if len(reverse_ranks) == 0 else np.concatenate([reverse_ranks, rr])
             p, t_out, h, early_success = irn.get_seq_in_batch(seq, u, t, config.max_path_len, config.gap_len, config.sample,
-                                                              config.sample_k)
+                                                              config.sample_k, **stop)
             n_early_success += early_success
             if len(paths) == 0:
                 paths, histories, targets = p, h, t_out

@@ -34,6 +34,9 @@ from ._backend import HipBackend, check_trunk, make_scheduler, pad_ragged_ids, p
 from .layers import PositionalEncoding, get_item_index
 
 _SHARDED_GRAPH = os.environ.get("IRS_SHARDED_GRAPH", "0") == "1"  # captured sharded steps: opt-in (see _beam_paths)
+# get_seq_in_batch(stop_at_target=True): live users are counted (one 4-byte host read) and compacted after every step; larger
+# values trade finished users stepped for fewer reads.  1 is the issue's default, not a measured choice: nothing is measured yet.
+STOP_CHECK_EVERY = 1
 
 
 class InfluentialNet(nn.Module):
@@ -295,10 +298,15 @@ class IRSNN(nn.Module):
         return paths[:, 0].contiguous(), status
 
     def get_seq_in_batch(self, seqs, users, targets, max_path_len=20, gap_len=20, sample=False, sample_k=3,
-                         beam_width=1):
+                         beam_width=1, stop_at_target=False):
         """Persuasion-path generation (reference :392-470): returns
         (paths float32 [B, max_path_len], targets int64 [B], list of B history arrays, n_early_success).
-        beam_width > 1 (extension, not in the reference) returns the best beam's path."""
+        beam_width > 1 (extension, not in the reference) returns the best beam's path.
+        stop_at_target=True (extension; greedy / sampled search on one device): a user is no longer decoded once its path has
+        reached the window's target, and the search returns when nobody is left (irs_generate_paths_until).  Same return
+        values: the reference computes those steps and zeroes them here, on the host."""
+        if stop_at_target and beam_width > 1:
+            raise ValueError("stop_at_target is not built for beam search (beam_width > 1): irs_beam_search runs every step")
         self.net.eval()
         B, L = seqs.shape
         dev = seqs.device
@@ -310,6 +318,14 @@ class IRSNN(nn.Module):
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if sample else 0
         if beam_width > 1:
             paths_t, status = self._beam_paths(work, users, max_path_len, gap_len, beam_width)
+        elif stop_at_target:
+            if hip.world != 1:
+                raise ValueError("stop_at_target is not built for an item-sharded catalog: irs_generate_paths_sharded runs "
+                                 "every step")
+            eng = hip.get(B, B)
+            paths_t, status, _, _ = eng.generate_paths_until(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
+                                                             sample=sample, sample_k=sample_k, seed=seed,
+                                                             check_every=STOP_CHECK_EVERY)
         elif hip.world == 1:
             eng = hip.get(B, B)
             paths_t, status = eng.generate_paths(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
