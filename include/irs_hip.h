@@ -419,6 +419,61 @@ int irs_beam_search(irs_ctx *ctx, const int64_t *dev_seq0, const int64_t *dev_us
                     int32_t W, int32_t P, int32_t k, int32_t sweep, int32_t use_graph, float *dev_paths,
                     double *dev_scores, int64_t *dev_seq_final, int32_t *dev_status, void *stream);
 
+/* ---- beam search with an end symbol (BUILD-DEFINED like the beam search itself; W == 1 is pinned to the reference through
+ *      irs_generate_paths_until).  The end symbol of a window is its target, seq[L-1].  A beam that has just chosen it is
+ *      FINISHED (fin = 1): it is not expanded again and competes with its final score.  A user is DONE once nothing is left
+ *      to decide for it; done users are skipped by the step and retired by the loop. */
+#define IRS_BEAM_STOP_ALL 0  /* done: no output beam is both live (cum > -inf) and unfinished */
+#define IRS_BEAM_STOP_BEST 1 /* done also as soon as output beam 0 is finished */
+/* irs_beam_step with the flags: per beam dev_fin_in / dev_fin_out int32 [B, W], per user dev_done int32 [B] in/out.
+ * A user whose done is 0 on entry:
+ *   a live unfinished beam (cum > -inf, fin 0) contributes its first W window-survivors exactly as in irs_beam_step: score
+ *     cum + (val - max - log(sumexp)), index parent * W + rank;
+ *   a finished beam (fin 1) contributes ONE candidate, itself: score cum, unchanged, index parent * W + 0.  Its rows of
+ *     dev_val / dev_ids0 / dev_lse_* are never read (NaNs and negative ids there do not matter) and it never sets
+ *     IRS_ROW_NO_CANDIDATE.  (fin 1 with cum -inf is not a state the step produces: such a beam contributes nothing.)
+ *   the best W candidates by (score desc, index asc) become the output beams.  A surviving finished beam is copied whole:
+ *     window, hep, cum, all P path entries, fin 1.  A new beam is built as in irs_beam_step and gets fin 1 exactly when its
+ *     item equals the PARENT window's seq[L-1].  Dead output beams are irs_beam_step's, with fin 0.
+ *   done becomes 1 under the stop rule above, else 0.
+ * A user whose done is 1 on entry: all W beams are copied from in to out unchanged (window, hep, cum, P path entries, fin);
+ *   status and done are not written.  The result of a search therefore does not depend on how often the host looks.
+ * IRS_BEAM_STOP_BEST is sound because a step adds a log-probability <= 0 to an unfinished beam and a finished beam 0 wins
+ * every tie by index (it re-enters as index 0): later steps could only lower the others.  Float caveat: val, max and sumexp
+ * are float32 results of separate reductions; where max is not the exact maximum of the scores val was taken from, an
+ * increment can exceed 0 by an ulp, so ALL and BEST may differ for an unfinished beam within that ulp of beam 0.
+ * With every fin_in 0, done 0 and no chosen item equal to its target the outputs equal irs_beam_step's bit for bit (fin_out
+ * and done 0); with W == 1 the path is irs_generate_paths_until's: the target, then exact zeros.
+ * Checks, before any launch: those of irs_beam_step; null dev_fin_in / dev_fin_out / dev_done, stop_rule outside {0, 1} ->
+ * IRS_E_INVALID.  Like irs_beam_step it works on the caller's lists, whatever shard the context holds. */
+int irs_beam_step_until(irs_ctx *ctx, const int64_t *dev_seq_in, const int32_t *dev_hep_in, const double *dev_cum_in,
+                        const float *dev_paths_in, const int32_t *dev_fin_in, const float *dev_val, const int64_t *dev_ids0,
+                        const float *dev_lse_max, const float *dev_lse_sum, int32_t B, int32_t W, int32_t k, int32_t step,
+                        int32_t P, int32_t stop_rule, int64_t *dev_seq_out, int32_t *dev_hep_out, double *dev_cum_out,
+                        float *dev_paths_out, int32_t *dev_fin_out, int32_t *dev_done, int32_t *dev_status, void *stream);
+
+/* irs_beam_search with the end symbol, on ONE device holding the full catalog: beam init (fin 0, done 0), then per step
+ * { decode live * W windows, top-k with the row log-sum-exp, irs_beam_step_until } on the users that are still live.  After
+ * every check_every-th step except the last, `done` is scanned on the device and the live count comes to the host in ONE
+ * 4-byte asynchronous copy followed by a wait for the stream (the stream drains once per check); when users are done, their
+ * beams are written to the caller's rows and the live users are compacted (stable order, an index map back to the caller's
+ * rows, never in place: into the step's free input set of the workspace).  The call returns when nobody is left; after the
+ * last step the remaining users are written out through the map.  Every caller row is written exactly once.  The loop is
+ * never replayed from a hipGraph (the batch size of a step is decided on the host: no use_graph), and it leaves the
+ * captured steps of the other loops valid.
+ *  inputs as irs_beam_search; dev_paths float [B, W, P], dev_scores double [B, W] out (beam 0 = best; W == 1 takes no
+ *  log-sum-exp, as in irs_beam_search: the one score is then a sum of raw scores, not of log-probabilities, and may be > 0);
+ *  dev_fin int32 [B, W] out, may be NULL; dev_seq_final int64 [B, W, L] out, may be NULL; dev_status int32 [B] out;
+ *  host_stats int64 [2], HOST memory, may be NULL: { steps_run, window_steps }, window_steps = the sum over the steps run
+ *            of the live * W windows decoded in that step (irs_beam_search: P and B * W * P).
+ * Checks, before any launch: those of irs_beam_search; stop_rule outside {0, 1} and check_every < 1 -> IRS_E_INVALID;
+ * world != 1 -> IRS_E_UNSUPPORTED.  A live count outside [0, live] returns IRS_E_STATE without launching anything further.
+ * On a HIP error inside the loop the call returns at once: host_stats is not written, the outputs are unspecified. */
+int irs_beam_search_until(irs_ctx *ctx, const int64_t *dev_seq0, const int64_t *dev_user, const int32_t *dev_hep0, int32_t B,
+                          int32_t W, int32_t P, int32_t k, int32_t sweep, int32_t stop_rule, int32_t check_every,
+                          float *dev_paths, double *dev_scores, int32_t *dev_fin, int64_t *dev_seq_final,
+                          int32_t *dev_status, int64_t *host_stats, void *stream);
+
 /* ---- multi-GPU: the exchange steps and the sharded search loops below the ABI (section 8 row B2's
  *      `allgather_merge(ctx, comm, ...)`).  One process per GPU; rank r holds item rows [item_lo, item_hi) (irs_shard).
  * A communicator is either RCCL (librccl.so is dlopen()ed on first use: ncclCommInitRank over a 128-byte unique id the

@@ -267,6 +267,7 @@ struct ws_plan {
     size_t x, y, xf, yf, qkv, qkv_b1, ao, h, ru, xb, eps, thr, gm, cnt, cand, lse, ref, xrows, tval, tids, status, step, pos;
     size_t bseq[2], bhep[2], bcum[2], bpaths[2], buser, lmax, lsum, tokrow, scnt, soff, sqrow, spadq, mdev, tseq, tidx, srow0, qtile, nwg, xlocal, ksend, krecv, gmax, cepairs, fbcount, fblist, exhkeys, total;
     size_t useq[2], uuser[2], uhep[2], umap[2], ufin, udst, ustatus, ustage, ucount;
+    size_t buser2, bfin[2], bdone[2];
 };
 
 static void workspace_plan(const irs_ctx *ctx, ws_plan *p) {
@@ -350,6 +351,11 @@ static void workspace_plan(const irs_ctx *ctx, ws_plan *p) {
     p->ustatus = take((size_t)ctx->max_seqs * 4);
     p->ustage = take((size_t)ctx->max_seqs * IRS_MAX_PATH * 4);
     p->ucount = take(256);
+    p->buser2 = take((size_t)ctx->max_seqs * 8); // irs_beam_search_until: the per-row arrays only (24 bytes per sequence)
+    for (int i = 0; i < 2; ++i) {
+        p->bfin[i] = take((size_t)ctx->max_seqs * 4);
+        p->bdone[i] = take((size_t)ctx->max_seqs * 4);
+    }
     p->total = off;
 }
 
@@ -434,6 +440,11 @@ extern "C" int irs_bind_workspace(irs_ctx *ctx, void *ws, size_t bytes) {
     ctx->un_status = (int32_t *)(b + p.ustatus);
     ctx->un_stage = (float *)(b + p.ustage);
     ctx->un_count = (int32_t *)(b + p.ucount);
+    ctx->bm_user2 = (int64_t *)(b + p.buser2);
+    for (int i = 0; i < 2; ++i) {
+        ctx->bm_fin[i] = (int32_t *)(b + p.bfin[i]);
+        ctx->bm_done[i] = (int32_t *)(b + p.bdone[i]);
+    }
     irs_drop_graphs(ctx);
     return IRS_OK;
 }
@@ -928,6 +939,91 @@ extern "C" int irs_beam_search(irs_ctx *ctx, const int64_t *seq0, const int64_t 
     for (; done < P; ++done)
         if ((rc = enqueue_beam_step(ctx, done & 1, B, W, k, sweep, P, status, s))) return rc;
     return irs_beam_finish(ctx, (size_t)B * W, P, paths, scores, seq_final, s);
+}
+
+// ------------------------------------------------------------------ beam search with an end symbol
+extern "C" int irs_beam_step_until(irs_ctx *ctx, const int64_t *seq_in, const int32_t *hep_in, const double *cum_in,
+                                   const float *paths_in, const int32_t *fin_in, const float *val, const int64_t *ids0,
+                                   const float *lse_max, const float *lse_sum, int32_t B, int32_t W, int32_t k, int32_t step,
+                                   int32_t P, int32_t stop_rule, int64_t *seq_out, int32_t *hep_out, double *cum_out,
+                                   float *paths_out, int32_t *fin_out, int32_t *done, int32_t *status, void *stream) {
+    if (!ctx) return IRS_E_INVALID;
+    if (!seq_in || !hep_in || !cum_in || !paths_in || !fin_in || !val || !ids0 || !seq_out || !hep_out || !cum_out ||
+        !paths_out || !fin_out || !done || !status || B < 1 || W < 1 || k < 1 || P < 1 || step < 0 || step >= P)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_until: bad arguments");
+    if (W > 1 && (!lse_max || !lse_sum)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_until: W > 1 needs the row log-sum-exp");
+    if (stop_rule != IRS_BEAM_STOP_ALL && stop_rule != IRS_BEAM_STOP_BEST)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_until: stop_rule %d (IRS_BEAM_STOP_ALL or IRS_BEAM_STOP_BEST)", stop_rule);
+    return irs_launch_beam_step_until(ctx, seq_in, hep_in, cum_in, paths_in, fin_in, val, ids0, W > 1 ? lse_max : nullptr,
+                                      W > 1 ? lse_sum : nullptr, B, W, k, step, nullptr, P, stop_rule, seq_out, hep_out, cum_out,
+                                      paths_out, fin_out, done, nullptr, status, (hipStream_t)stream);
+}
+
+// The loop.  The beam state of the live users sits in set `cur` of the ping-pong buffers; a step reads it and writes set cur ^ 1,
+// a compaction reads THAT and writes the set the step has just freed.  user / done / map move at compactions only (side `aux`).
+// The buffers and the step counter are the ones a cached beam graph bakes in: irs_beam_search re-initialises all of them.
+extern "C" int irs_beam_search_until(irs_ctx *ctx, const int64_t *seq0, const int64_t *user, const int32_t *hep0, int32_t B,
+                                     int32_t W, int32_t P, int32_t k, int32_t sweep, int32_t stop_rule, int32_t check_every,
+                                     float *paths, double *scores, int32_t *fin, int64_t *seq_final, int32_t *status,
+                                     int64_t *host_stats, void *stream) {
+    int rc = ready_filter(ctx, sweep);
+    if (rc) return rc;
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_beam_search_until needs the whole catalog on one device");
+    if ((rc = irs_check_beam_args(ctx, "irs_beam_search_until", seq0, hep0, paths, scores, status, B, W, P))) return rc;
+    if ((int64_t)B * W > ctx->max_seqs || (int64_t)B * W > ctx->max_rows)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_until: B*W=%d exceeds max_seqs=%d / max_rows=%d", B * W, ctx->max_seqs, ctx->max_rows);
+    if ((rc = irs_check_k(ctx, "irs_beam_search_until", k, 1, sweep, 0, 0))) return rc;
+    if (ctx->dims.mask_mode == IRS_MASK_IRN && !user) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_until: user is null");
+    if (stop_rule != IRS_BEAM_STOP_ALL && stop_rule != IRS_BEAM_STOP_BEST)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_until: stop_rule %d (IRS_BEAM_STOP_ALL or IRS_BEAM_STOP_BEST)", stop_rule);
+    if (check_every < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_until: check_every must be >= 1");
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
+    if ((rc = irs_launch_beam_init(ctx, seq0, user, hep0, B, W, P, ctx->bm_seq[0], ctx->bm_user, ctx->bm_hep[0],
+                                   ctx->bm_cum[0], ctx->bm_paths[0], s)))
+        return rc;
+    IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->bm_fin[0], 0, sizeof(int32_t) * B * W, s));
+    IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->bm_done[0], 0, sizeof(int32_t) * B, s));
+    int64_t *const usr[2] = {ctx->bm_user, ctx->bm_user2};
+    const int32_t *cmap = nullptr; // identity until the first compaction; then un_map[aux]
+    int live = B, cur = 0, aux = 0;
+    int64_t steps = 0, window_steps = 0;
+    float *const lmax = W > 1 ? ctx->lse_max : nullptr, *const lsum = W > 1 ? ctx->lse_sum : nullptr;
+    for (int i = 0; i < P; ++i) {
+        const int out = cur ^ 1, rows = live * W;
+        if ((rc = irs_launch_decode(ctx, ctx->bm_seq[cur], usr[aux], rows, nullptr, ctx->bm_hep[cur], ctx->xrows, nullptr, s))) return rc;
+        if ((rc = irs_launch_topk(ctx, ctx->xrows, rows, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, lmax, lsum)))
+            return rc;
+        if ((rc = irs_launch_beam_step_until(ctx, ctx->bm_seq[cur], ctx->bm_hep[cur], ctx->bm_cum[cur], ctx->bm_paths[cur],
+                                             ctx->bm_fin[cur], ctx->top_val, ctx->top_ids, lmax, lsum, live, W, k, 0, ctx->step_ctr, P,
+                                             stop_rule, ctx->bm_seq[out], ctx->bm_hep[out], ctx->bm_cum[out], ctx->bm_paths[out],
+                                             ctx->bm_fin[out], ctx->bm_done[aux], cmap, status, s)))
+            return rc;
+        if ((rc = irs_launch_inc(ctx, ctx->step_ctr, s))) return rc;
+        cur = out, ++steps, window_steps += rows;
+        if ((i + 1) % check_every || i + 1 == P) continue; // no check due, or the last step: whoever is left leaves below
+        if ((rc = irs_launch_until_scan(ctx, ctx->bm_done[aux], live, ctx->un_dst, ctx->un_count, s))) return rc;
+        IRS_CHECK_HIP(ctx, hipMemcpyAsync(&ctx->un_count_host, ctx->un_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        IRS_CHECK_HIP(ctx, hipStreamSynchronize(s));
+        const int left = ctx->un_count_host;
+        if (left < 0 || left > live) IRS_FAIL(ctx, IRS_E_STATE, "irs_beam_search_until: live count %d of %d users", left, live);
+        if (left == live) continue;
+        const int to = cur ^ 1; // the set the step has just read: free
+        if ((rc = irs_launch_beam_retire(ctx, ctx->un_dst, live, W, P, ctx->bm_seq[cur], usr[aux], ctx->bm_hep[cur], ctx->bm_cum[cur],
+                                         ctx->bm_paths[cur], ctx->bm_fin[cur], cmap, ctx->bm_seq[to], usr[aux ^ 1], ctx->bm_hep[to],
+                                         ctx->bm_cum[to], ctx->bm_paths[to], ctx->bm_fin[to], ctx->un_map[aux ^ 1],
+                                         ctx->bm_done[aux ^ 1], paths, scores, fin, seq_final, s)))
+            return rc;
+        cur = to, aux ^= 1, cmap = ctx->un_map[aux], live = left;
+        if (live == 0) break;
+    }
+    if (live > 0 &&
+        (rc = irs_launch_beam_retire(ctx, nullptr, live, W, P, ctx->bm_seq[cur], usr[aux], ctx->bm_hep[cur], ctx->bm_cum[cur],
+                                     ctx->bm_paths[cur], ctx->bm_fin[cur], cmap, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                     nullptr, nullptr, paths, scores, fin, seq_final, s)))
+        return rc;
+    if (host_stats) host_stats[0] = steps, host_stats[1] = window_steps;
+    return IRS_OK;
 }
 
 // ------------------------------------------------------------------ profiling hooks

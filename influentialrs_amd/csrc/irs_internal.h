@@ -158,6 +158,11 @@ struct irs_ctx {
     double *bm_cum[2];   // [max_seqs]
     float *bm_paths[2];  // [max_seqs][IRS_MAX_PATH]
     int64_t *bm_user;    // [max_seqs]
+    // irs_beam_search_until: the flags of the beam state, and the second side of what a compaction moves besides the ping-pong
+    // sets above (the map is un_map[2], the scan's places and count un_dst / un_count / un_count_host below)
+    int64_t *bm_user2;   // [max_seqs]
+    int32_t *bm_fin[2];  // [max_seqs] the beam has chosen its target
+    int32_t *bm_done[2]; // [max_seqs] (by user) nothing is left to decide
     float *lse_max, *lse_sum; // [max_rows]
     // stop-at-target search (irs_generate_paths_until): the live users' compacted state, ping-pong [2]
     int64_t *un_seq[2];  // [max_seqs][L]
@@ -302,6 +307,20 @@ int irs_launch_beam_step(irs_ctx *ctx, const int64_t *seq_in, const int32_t *hep
                          const float *lse_sum, int B, int W, int k, int step, const int32_t *step_ptr, int P,
                          int64_t *seq_out, int32_t *hep_out, double *cum_out, float *paths_out, int32_t *status,
                          hipStream_t s);
+
+// irs_beam_step_until / irs_beam_search_until (map: compacted user -> the caller's status row, nullptr = identity; retire: dst ==
+// nullptr sends every user to the caller's outputs)
+int irs_launch_beam_step_until(irs_ctx *ctx, const int64_t *seq_in, const int32_t *hep_in, const double *cum_in,
+                               const float *paths_in, const int32_t *fin_in, const float *val, const int64_t *ids0,
+                               const float *lse_max, const float *lse_sum, int B, int W, int k, int step,
+                               const int32_t *step_ptr, int P, int stop_rule, int64_t *seq_out, int32_t *hep_out,
+                               double *cum_out, float *paths_out, int32_t *fin_out, int32_t *done, const int32_t *map,
+                               int32_t *status, hipStream_t s);
+int irs_launch_beam_retire(irs_ctx *ctx, const int32_t *dst, int B, int W, int P, const int64_t *seq, const int64_t *user,
+                           const int32_t *hep, const double *cum, const float *paths, const int32_t *fin, const int32_t *map,
+                           int64_t *seq_o, int64_t *user_o, int32_t *hep_o, double *cum_o, float *paths_o, int32_t *fin_o,
+                           int32_t *map_o, int32_t *done_o, float *out_paths, double *out_scores, int32_t *out_fin,
+                           int64_t *out_seq, hipStream_t s);
 
 int irs_launch_build_eval_batch(irs_ctx *ctx, const int64_t *items, const int64_t *offsets, int B, int raw_len, int gap_len,
                                 const int64_t *targets_in, const int64_t *pool, int64_t n_pool, uint64_t seed, int64_t *seq,

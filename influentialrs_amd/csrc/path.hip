@@ -97,7 +97,23 @@ __global__ void __launch_bounds__(256) k_merge(const float *__restrict__ val_in,
 // A beam's candidates are taken 64 at a time into registers (one per lane) before the survivor scan, so the
 // scan is a chain of v_readlane + ballot, not of dependent global loads; the W best of the W*W candidates are ordered
 // by rank counting (no barriers) instead of a full sort.
+//
+// UNTIL (irs_beam_step_until / irs_beam_search_until): the target of a window, seq[L - 1], is the search's end symbol.  A beam
+// that has chosen it is FINISHED (fin = 1): it is no longer expanded, it competes with its final score as ONE candidate
+// (index parent * W + 0; its val / ids0 / lse rows are never read and it never sets IRS_ROW_NO_CANDIDATE) and, when it survives,
+// it is copied whole (window, hep, cum, all P path entries).  A user is DONE when no output beam is both live and unfinished
+// (IRS_BEAM_STOP_ALL), or already when output beam 0 is finished (IRS_BEAM_STOP_BEST); a user that is done on entry is copied
+// through, so a search gives the same result however rarely the host looks at `done`.
+// Why BEST may stop there: a step adds log p(item | beam) <= 0 to an unfinished beam (val <= max and sum exp >= 1, the maximum's
+// own term), so no later candidate scores above its unfinished ancestor of this step, all of which rank behind beam 0; a
+// candidate that ties beam 0 loses by index, because a finished beam 0 re-enters as index 0 * W + 0, the smallest there is.  So
+// beam 0 would stay beam 0 to the last step.  The float caveat: val, max and sum exp are float32 results of separate
+// reductions.  Where a row's `max` is not the exact maximum of the scores its `val` were taken from (another summation order,
+// a max taken over rounded scores), val - max can exceed 0 by an ulp of the score, and an unfinished beam within that ulp
+// behind beam 0 could still overtake it under IRS_BEAM_STOP_ALL; BEST then returns the earlier answer.
+// The instantiation without UNTIL is the kernel as it was: every addition sits behind `if constexpr`.
 #define BEAM_MAXW 32
+template <bool UNTIL>
 __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ seq_in, const int32_t *__restrict__ hep_in,
                                                     const double *__restrict__ cum_in, const float *__restrict__ paths_in,
                                                     const float *__restrict__ val, const int64_t *__restrict__ ids0,
@@ -105,14 +121,33 @@ __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ 
                                                     int W, int L, int k, int step_arg, const int32_t *__restrict__ step_ptr,
                                                     int P, int64_t *__restrict__ seq_out, int32_t *__restrict__ hep_out,
                                                     double *__restrict__ cum_out, float *__restrict__ paths_out,
-                                                    int32_t *__restrict__ status) {
+                                                    int32_t *__restrict__ status, const int32_t *__restrict__ fin_in,
+                                                    int32_t *__restrict__ fin_out, int32_t *__restrict__ done, int stop_rule,
+                                                    const int32_t *__restrict__ map) {
     __shared__ double c_score[BEAM_MAXW * BEAM_MAXW];
     __shared__ int64_t c_item[BEAM_MAXW * BEAM_MAXW];
     __shared__ int c_order[BEAM_MAXW];
+    __shared__ int s_flags[2]; // UNTIL: [0] some output beam is live and unfinished, [1] output beam 0 is finished
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, nthr = blockDim.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwave = nthr >> 6;
     const int step = step_ptr ? step_ptr[0] : step_arg;
     const int WW = W * W;
+    if constexpr (UNTIL) {
+        if (done[b]) { // (the same for the whole workgroup) a user that is done: every beam goes from in to out as it is
+            for (int j = wave; j < W; j += nwave) {
+                const size_t row = (size_t)b * W + j;
+                for (int p = lane; p < L; p += 64) seq_out[row * L + p] = seq_in[row * L + p];
+                for (int p = lane; p < P; p += 64) paths_out[row * P + p] = paths_in[row * P + p];
+                if (lane == 0) {
+                    hep_out[row] = hep_in[row];
+                    cum_out[row] = cum_in[row];
+                    fin_out[row] = fin_in[row];
+                }
+            }
+            return;
+        }
+        if (tid < 2) s_flags[tid] = 0;
+    }
     for (int i = tid; i < WW; i += nthr) {
         c_score[i] = -INFINITY;
         c_item[i] = 0;
@@ -124,6 +159,12 @@ __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ 
         const int row = b * W + j;
         const double cj = cum_in[row];
         int found = 0;
+        if constexpr (UNTIL) {
+            if (fin_in[row]) { // a finished beam: itself, with its final score; its lists are not read
+                if (lane == 0 && cj > -INFINITY) c_score[j * W] = cj;
+                continue;
+            }
+        }
         if (cj > -INFINITY) {
             const int64_t *w = seq_in + (size_t)row * L;
             const int wl = hep_in[row] + 1;
@@ -160,7 +201,7 @@ __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ 
                     }
                 }
             }
-            if (found == 0 && lane == 0) atomicOr(&status[b], IRS_ROW_NO_CANDIDATE);
+            if (found == 0 && lane == 0) atomicOr(&status[(UNTIL && map) ? map[b] : b], IRS_ROW_NO_CANDIDATE);
         }
     }
     __syncthreads();
@@ -191,6 +232,7 @@ __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ 
             if (lane == 0) {
                 cum_out[orow] = -INFINITY;
                 hep_out[orow] = hep_in[b * W];
+                if constexpr (UNTIL) fin_out[orow] = 0;
             }
             continue;
         }
@@ -200,6 +242,19 @@ __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ 
         const int64_t *wi = seq_in + (size_t)prow * L;
         const float *pi = paths_in + (size_t)prow * P;
         const int he = hep_in[prow];
+        if constexpr (UNTIL) {
+            if (fin_in[prow]) { // a finished beam that survived: copied whole
+                for (int p = lane; p < L; p += 64) wo[p] = wi[p];
+                for (int p = lane; p < P; p += 64) po[p] = pi[p];
+                if (lane == 0) {
+                    hep_out[orow] = he;
+                    cum_out[orow] = sc;
+                    fin_out[orow] = 1;
+                    if (t == 0) s_flags[1] = 1;
+                }
+                continue;
+            }
+        }
         if (he < L - 2) { // grow
             for (int p = lane; p < L; p += 64) wo[p] = (p == he + 1) ? item : wi[p];
             if (lane == 0) hep_out[orow] = he + 1;
@@ -209,6 +264,18 @@ __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ 
         }
         for (int p = lane; p < P; p += 64) po[p] = (p < step) ? pi[p] : (p == step ? (float)item : 0.f);
         if (lane == 0) cum_out[orow] = sc;
+        if constexpr (UNTIL) {
+            const int f = item == wi[L - 1] ? 1 : 0; // the end symbol: the parent window's target
+            if (lane == 0) {
+                fin_out[orow] = f;
+                if (!f) atomicOr(&s_flags[0], 1);
+                if (f && t == 0) s_flags[1] = 1;
+            }
+        }
+    }
+    if constexpr (UNTIL) {
+        __syncthreads();
+        if (tid == 0) done[b] = (!s_flags[0] || (stop_rule == IRS_BEAM_STOP_BEST && s_flags[1])) ? 1 : 0;
     }
 }
 
@@ -244,8 +311,84 @@ int irs_launch_beam_step(irs_ctx *ctx, const int64_t *seq_in, const int32_t *hep
     if (W < 1 || W > BEAM_MAXW) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam width %d outside [1, %d]", W, BEAM_MAXW);
     if (ctx->dims.max_len > 256) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam step: window length %d > 256", ctx->dims.max_len);
     const int waves = W < 4 ? 4 : (W > 16 ? 16 : W);
-    hipLaunchKernelGGL(k_beam_step, dim3(B), dim3(64 * waves), 0, s, seq_in, hep_in, cum_in, paths_in, val, ids0, lse_max,
-                       lse_sum, W, ctx->dims.max_len, k, step, step_ptr, P, seq_out, hep_out, cum_out, paths_out, status);
+    hipLaunchKernelGGL(k_beam_step<false>, dim3(B), dim3(64 * waves), 0, s, seq_in, hep_in, cum_in, paths_in, val, ids0, lse_max,
+                       lse_sum, W, ctx->dims.max_len, k, step, step_ptr, P, seq_out, hep_out, cum_out, paths_out, status,
+                       (const int32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, 0, (const int32_t *)nullptr);
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
+// (map: compacted user -> the caller's row of `status`; nullptr is the identity)
+int irs_launch_beam_step_until(irs_ctx *ctx, const int64_t *seq_in, const int32_t *hep_in, const double *cum_in,
+                               const float *paths_in, const int32_t *fin_in, const float *val, const int64_t *ids0,
+                               const float *lse_max, const float *lse_sum, int B, int W, int k, int step,
+                               const int32_t *step_ptr, int P, int stop_rule, int64_t *seq_out, int32_t *hep_out,
+                               double *cum_out, float *paths_out, int32_t *fin_out, int32_t *done, const int32_t *map,
+                               int32_t *status, hipStream_t s) {
+    if (W < 1 || W > BEAM_MAXW) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam width %d outside [1, %d]", W, BEAM_MAXW);
+    if (ctx->dims.max_len > 256) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam step: window length %d > 256", ctx->dims.max_len);
+    const int waves = W < 4 ? 4 : (W > 16 ? 16 : W);
+    hipLaunchKernelGGL(k_beam_step<true>, dim3(B), dim3(64 * waves), 0, s, seq_in, hep_in, cum_in, paths_in, val, ids0, lse_max,
+                       lse_sum, W, ctx->dims.max_len, k, step, step_ptr, P, seq_out, hep_out, cum_out, paths_out, status, fin_in,
+                       fin_out, done, stop_rule, map);
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
+// After a step of irs_beam_search_until: a done user's W beams leave for the caller's outputs at user row map[r]; a live user's
+// beams move to user slot dst[r] of the OTHER state set (never in place: the step's input set is free by then), with its map entry
+// and a cleared done flag.  dst is k_until_scan's over `done` (-1: done); dst == nullptr: every user leaves (the last step).
+// One wave per beam row.
+__global__ void __launch_bounds__(256) k_beam_retire(const int32_t *__restrict__ dst, int B, int W, int L, int P,
+                                                     const int64_t *__restrict__ seq, const int64_t *__restrict__ user,
+                                                     const int32_t *__restrict__ hep, const double *__restrict__ cum,
+                                                     const float *__restrict__ paths, const int32_t *__restrict__ fin,
+                                                     const int32_t *__restrict__ map, int64_t *__restrict__ seq_o,
+                                                     int64_t *__restrict__ user_o, int32_t *__restrict__ hep_o,
+                                                     double *__restrict__ cum_o, float *__restrict__ paths_o,
+                                                     int32_t *__restrict__ fin_o, int32_t *__restrict__ map_o,
+                                                     int32_t *__restrict__ done_o, float *__restrict__ out_paths,
+                                                     double *__restrict__ out_scores, int32_t *__restrict__ out_fin,
+                                                     int64_t *__restrict__ out_seq) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= B * W) return;
+    const int r = row / W, j = row - r * W;
+    const int t = dst ? dst[r] : -1;
+    if (t < 0) {
+        const size_t orow = (size_t)(map ? map[r] : r) * W + j;
+        for (int p = lane; p < P; p += 64) out_paths[orow * P + p] = paths[(size_t)row * P + p];
+        if (out_seq)
+            for (int p = lane; p < L; p += 64) out_seq[orow * L + p] = seq[(size_t)row * L + p];
+        if (lane == 0) {
+            out_scores[orow] = cum[row];
+            if (out_fin) out_fin[orow] = fin[row];
+        }
+        return;
+    }
+    const size_t trow = (size_t)t * W + j;
+    for (int p = lane; p < L; p += 64) seq_o[trow * L + p] = seq[(size_t)row * L + p];
+    for (int p = lane; p < P; p += 64) paths_o[trow * P + p] = paths[(size_t)row * P + p];
+    if (lane == 0) {
+        user_o[trow] = user[row];
+        hep_o[trow] = hep[row];
+        cum_o[trow] = cum[row];
+        fin_o[trow] = fin[row];
+        if (j == 0) {
+            map_o[t] = map ? map[r] : r;
+            done_o[t] = 0;
+        }
+    }
+}
+
+int irs_launch_beam_retire(irs_ctx *ctx, const int32_t *dst, int B, int W, int P, const int64_t *seq, const int64_t *user,
+                           const int32_t *hep, const double *cum, const float *paths, const int32_t *fin, const int32_t *map,
+                           int64_t *seq_o, int64_t *user_o, int32_t *hep_o, double *cum_o, float *paths_o, int32_t *fin_o,
+                           int32_t *map_o, int32_t *done_o, float *out_paths, double *out_scores, int32_t *out_fin,
+                           int64_t *out_seq, hipStream_t s) {
+    hipLaunchKernelGGL(k_beam_retire, dim3((B * W + 3) / 4), dim3(256), 0, s, dst, B, W, ctx->dims.max_len, P, seq, user, hep, cum,
+                       paths, fin, map, seq_o, user_o, hep_o, cum_o, paths_o, fin_o, map_o, done_o, out_paths, out_scores, out_fin,
+                       out_seq);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }

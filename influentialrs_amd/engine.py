@@ -469,6 +469,59 @@ class Engine:
                                              int(use_graph), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(status))
         return (paths, scores, status, fin) if want_windows else (paths, scores, status)
 
+    def beam_step_until(self, state_in, val, ids0, lse, step: int, stop_rule: int, state_out, done, status):
+        """One beam step with the end symbol (irs_beam_step_until); state = beam_step's four tensors plus fin[B,W] i32;
+        done[B] i32 is read and written."""
+        kinds = (torch.int64, torch.int32, torch.float64, torch.float32, torch.int32)
+        seq_i, hep_i, cum_i, paths_i, fin_i = (self._inplace(t, k, "beam_step_until: state_in") for t, k in zip(state_in, kinds))
+        seq_o, hep_o, cum_o, paths_o, fin_o = (self._inplace(t, k, "beam_step_until: state_out") for t, k in zip(state_out, kinds))
+        done = self._inplace(done, torch.int32, "beam_step_until: done")
+        status = self._inplace(status, torch.int32, "beam_step_until: status")
+        val, ids0 = self._dev(val, torch.float32), self._dev(ids0, torch.int64)
+        B, W, _ = seq_i.shape
+        lmax, lsum = lse if lse is not None else (None, None)
+        if lmax is not None:
+            lmax, lsum = self._dev(lmax, torch.float32), self._dev(lsum, torch.float32)
+        self._call(self.lib.irs_beam_step_until, _ptr(seq_i), _ptr(hep_i), _ptr(cum_i), _ptr(paths_i), _ptr(fin_i), _ptr(val),
+                   _ptr(ids0), _ptr(lmax), _ptr(lsum), B, W, val.shape[1], step, paths_i.shape[2], int(stop_rule), _ptr(seq_o),
+                   _ptr(hep_o), _ptr(cum_o), _ptr(paths_o), _ptr(fin_o), _ptr(done), _ptr(status))
+
+    def beam_search_until(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
+                          beam: int, k: int = 100, sweep: int = IRS_SWEEP_BF16, stop_rule: int = _lib.IRS_BEAM_STOP_BEST,
+                          check_every: int = 1, want_windows: bool = False, paths: Optional[torch.Tensor] = None,
+                          scores: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
+                          fin: Optional[torch.Tensor] = None):
+        """Beam search that ends a beam at its target (seqs[b, L - 1]) and retires finished users (irs_beam_search_until):
+        (paths[B,W,P] f32, scores[B,W] f64, status[B] i32, fin[B,W] i32, steps_run, window_steps[, windows[B,W,L]]); beam 0 is
+        the best.  One host read of 4 bytes per check."""
+        seqs = self._dev(seqs, torch.int64)
+        hep = self._dev(hep, torch.int32)
+        if users is not None:
+            users = self._dev(users, torch.int64)
+        B = seqs.shape[0]
+        if seqs.shape[1] != self.L or hep.shape[0] != B or (users is not None and users.shape[0] != B):
+            raise IrsError("beam_search_until: inconsistent shapes")
+        if paths is None:
+            paths = torch.zeros((B, beam, max_path_len), dtype=torch.float32, device=self.device)
+        if scores is None:
+            scores = torch.zeros((B, beam), dtype=torch.float64, device=self.device)
+        if status is None:
+            status = torch.zeros(B, dtype=torch.int32, device=self.device)
+        if fin is None:
+            fin = torch.zeros((B, beam), dtype=torch.int32, device=self.device)
+        paths = self._inplace(paths, torch.float32, "beam_search_until: paths")
+        scores = self._inplace(scores, torch.float64, "beam_search_until: scores")
+        status = self._inplace(status, torch.int32, "beam_search_until: status")
+        fin = self._inplace(fin, torch.int32, "beam_search_until: fin")
+        if paths.shape != (B, beam, max_path_len) or scores.shape != (B, beam) or fin.shape != (B, beam) or status.shape != (B,):
+            raise IrsError("beam_search_until: paths [B, W, P], scores / fin [B, W], status [B]")
+        win = torch.empty((B, beam, self.L), dtype=torch.int64, device=self.device) if want_windows else None
+        stats = (ctypes.c_int64 * 2)(0, 0)
+        self._call(self.lib.irs_beam_search_until, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
+                   int(stop_rule), int(check_every), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(win), _ptr(status), stats)
+        out = (paths, scores, status, fin, int(stats[0]), int(stats[1]))
+        return out + (win,) if want_windows else out
+
     # ------------------------------------------------------------------ item-sharded loops below the ABI (comm.hip)
     def allgather_rows(self, comm: "Comm", rows_local: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         rows_local = self._dev(rows_local, torch.float32)

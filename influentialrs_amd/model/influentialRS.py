@@ -29,7 +29,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.optim as optim
 
-from .._lib import IRS_MASK_IRN, IRS_ROW_NO_CANDIDATE
+from .._lib import IRS_BEAM_STOP_ALL, IRS_BEAM_STOP_BEST, IRS_MASK_IRN, IRS_ROW_NO_CANDIDATE
 from ._backend import HipBackend, check_trunk, make_scheduler, pad_ragged_ids, project_ce, project_ce_sharded, train_trunk_default, trunk_hip
 from .layers import PositionalEncoding, get_item_index
 
@@ -37,6 +37,9 @@ _SHARDED_GRAPH = os.environ.get("IRS_SHARDED_GRAPH", "0") == "1"  # captured sha
 # get_seq_in_batch(stop_at_target=True): live users are counted (one 4-byte host read) and compacted after every step; larger
 # values trade finished users stepped for fewer reads.  1 is the issue's default, not a measured choice: nothing is measured yet.
 STOP_CHECK_EVERY = 1
+# get_seq_in_batch(beam_width > 1, beam_stop=...): the same trade for irs_beam_search_until, as unmeasured
+BEAM_STOP_CHECK_EVERY = 1
+_BEAM_STOP_RULES = {"best": IRS_BEAM_STOP_BEST, "all": IRS_BEAM_STOP_ALL}
 
 
 class InfluentialNet(nn.Module):
@@ -274,16 +277,24 @@ class IRSNN(nn.Module):
             rr.append(np.reciprocal(float(ranks[i])))
         return hit_count, np.array(rr)
 
-    def _beam_paths(self, seqs, users, max_path_len, gap_len, beam_width):
+    def _beam_paths(self, seqs, users, max_path_len, gap_len, beam_width, beam_stop=None):
         """Best-beam paths [B, P] + status via the build-defined beam search (no reference
         counterpart; beam_width == 1 equals the greedy search).  All beams and their
-        cumulative log-probabilities are kept in self.last_beams = (paths[B,W,P], scores[B,W])."""
+        cumulative log-probabilities are kept in self.last_beams = (paths[B,W,P], scores[B,W]).
+        beam_stop "best" / "all": irs_beam_search_until -- a beam ends at its target, finished users are retired;
+        self.last_beam_stop = dict(finished [B,W], steps, window_steps)."""
         B, L = seqs.shape
         dev = seqs.device
         hip = self.net._hip
         W = beam_width
         hep = torch.full((B,), L - (gap_len + 1) - 1, dtype=torch.int32, device=dev)
-        if hip.world == 1:
+        if beam_stop is not None:
+            eng = hip.get(B * W, B * W)
+            paths, scores, status, fin, steps, window_steps = eng.beam_search_until(
+                seqs.contiguous(), users, hep, max_path_len, W, k=100, sweep=hip.sweep, stop_rule=_BEAM_STOP_RULES[beam_stop],
+                check_every=BEAM_STOP_CHECK_EVERY)
+            self.last_beam_stop = dict(finished=fin.detach().cpu().numpy(), steps=steps, window_steps=window_steps)
+        elif hip.world == 1:
             eng = hip.get(B * W, B * W)
             paths, scores, status = eng.beam_search(seqs.contiguous(), users, hep, max_path_len, W, k=100, sweep=hip.sweep)
         else:  # item-sharded: the whole loop runs below the C ABI (irs_beam_search_sharded: row all-gather, packed top-100
@@ -298,15 +309,27 @@ class IRSNN(nn.Module):
         return paths[:, 0].contiguous(), status
 
     def get_seq_in_batch(self, seqs, users, targets, max_path_len=20, gap_len=20, sample=False, sample_k=3,
-                         beam_width=1, stop_at_target=False):
+                         beam_width=1, stop_at_target=False, beam_stop=None):
         """Persuasion-path generation (reference :392-470): returns
         (paths float32 [B, max_path_len], targets int64 [B], list of B history arrays, n_early_success).
         beam_width > 1 (extension, not in the reference) returns the best beam's path.
         stop_at_target=True (extension; greedy / sampled search on one device): a user is no longer decoded once its path has
         reached the window's target, and the search returns when nobody is left (irs_generate_paths_until).  Same return
-        values: the reference computes those steps and zeroes them here, on the host."""
+        values: the reference computes those steps and zeroes them here, on the host.
+        beam_stop="best" / "all" (extension; beam_width > 1 on one device): the beam search with the window's target as its end
+        symbol (irs_beam_search_until) -- a beam that has chosen the target is frozen and competes with its final score, and a
+        user is retired once its best beam is finished ("best") or all its live beams are ("all").  A different search from
+        beam_stop=None, not the same paths cut short; self.last_beam_stop holds which beams finished and the work done."""
         if stop_at_target and beam_width > 1:
             raise ValueError("stop_at_target is not built for beam search (beam_width > 1): irs_beam_search runs every step")
+        if beam_stop is not None:
+            if beam_stop not in _BEAM_STOP_RULES:
+                raise ValueError(f"beam_stop={beam_stop!r}: use \"best\", \"all\" or None (irs_beam_search, every step)")
+            if beam_width == 1:
+                raise ValueError("beam_stop needs beam_width > 1: use stop_at_target=True for the greedy / sampled search")
+            if self.net._hip.world != 1:
+                raise ValueError("beam_stop is not built for an item-sharded catalog: use beam_stop=None "
+                                 "(irs_beam_search_sharded runs every step)")
         self.net.eval()
         B, L = seqs.shape
         dev = seqs.device
@@ -317,7 +340,7 @@ class IRSNN(nn.Module):
         hep = torch.full((B,), L - (gap_len + 1) - 1, dtype=torch.int32, device=dev)
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if sample else 0
         if beam_width > 1:
-            paths_t, status = self._beam_paths(work, users, max_path_len, gap_len, beam_width)
+            paths_t, status = self._beam_paths(work, users, max_path_len, gap_len, beam_width, beam_stop)
         elif stop_at_target:
             if hip.world != 1:
                 raise ValueError("stop_at_target is not built for an item-sharded catalog: irs_generate_paths_sharded runs "
