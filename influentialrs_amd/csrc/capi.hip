@@ -3,6 +3,7 @@
 #include <stdlib.h>
 
 #include <new>
+#include <type_traits>
 
 #include "irs_internal.h"
 
@@ -122,11 +123,6 @@ extern "C" void irs_destroy(irs_ctx *ctx) {
 }
 
 // ------------------------------------------------------------------ weights
-static bool ends_with(const char *s, const char *suf) {
-    size_t ls = strlen(s), lf = strlen(suf);
-    return ls >= lf && strcmp(s + ls - lf, suf) == 0;
-}
-
 extern "C" int irs_bind_weight(irs_ctx *ctx, const char *name, const float *p, int64_t numel) {
     if (!ctx || !name || !p) return IRS_E_INVALID;
     if (strncmp(name, "module.", 7) == 0) name += 7;
@@ -183,7 +179,6 @@ extern "C" int irs_bind_weight(irs_ctx *ctx, const char *name, const float *p, i
     if (want >= 0 && numel != want) IRS_FAIL(ctx, IRS_E_INVALID, "weight '%s': numel %lld, expected %lld", name, (long long)numel, (long long)want);
     *slot = p;
     ctx->finalized = false;
-    (void)ends_with;
     return IRS_OK;
 }
 
@@ -263,188 +258,118 @@ extern "C" int irs_finalize_weights(irs_ctx *ctx, void *arena, size_t bytes, voi
 }
 
 // ------------------------------------------------------------------ workspace
-struct ws_plan {
-    size_t x, y, xf, yf, qkv, qkv_b1, ao, h, ru, xb, eps, thr, gm, cnt, cand, lse, ref, xrows, tval, tids, status, step, pos;
-    size_t bseq[2], bhep[2], bcum[2], bpaths[2], buser, lmax, lsum, tokrow, scnt, soff, sqrow, spadq, mdev, tseq, tidx, srow0, qtile, nwg, xlocal, ksend, krecv, gmax, cepairs, fbcount, fblist, exhkeys, total;
-    size_t useq[2], uuser[2], uhep[2], umap[2], ufin, udst, ustatus, ustage, ucount;
-    size_t buser2, bfin[2], bdone[2];
-};
-
-static void workspace_plan(const irs_ctx *ctx, ws_plan *p) {
-    const irs_dims &D = ctx->dims;
-    const size_t RL = (size_t)ctx->max_seqs * D.max_len;
-    const size_t mp = ctx->m_pad_max;
+// The one walk over the workspace.  Every buffer is named here once: its irs_ctx field, its size, and its presence condition if it
+// has one.  A buffer takes its bytes rounded up to 256; an absent one takes none and is bound to nullptr.  base == nullptr: nothing
+// is assigned.  Returns the total.
+static size_t workspace_walk(irs_ctx *ctx, char *base) {
     size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = align_up(off + bytes, 256);
-        return o;
+    auto take = [&](auto *&field, size_t bytes, bool present = true) {
+        if (base) field = present ? (std::remove_reference_t<decltype(field)>)(base + off) : nullptr;
+        if (present) off = align_up(off + bytes, 256);
     };
-    p->x = take(RL * D.d * 4);
-    p->y = take(RL * D.d * 4);
+    const irs_dims &D = ctx->dims;
+    const size_t S = ctx->max_seqs, R = ctx->max_rows, mp = ctx->m_pad_max, RL = S * D.max_len;
+    // decoder activations
+    take(ctx->act_x, RL * D.d * 4);
+    take(ctx->act_y, RL * D.d * 4);
     // (the sequence-resident layer kernel pads every sequence to whole 32-token tiles and every workgroup to 8 tiles: up to 256 rows
     //  per sequence in the fragment-major images)
     const bool seq_shape = irs_seq_shape(D);
-    const size_t RLs = seq_shape ? (size_t)ctx->max_seqs * 256 : RL;
+    const size_t RLs = seq_shape ? S * 256 : RL;
     const size_t RLf = (((RLs > RL ? RLs : RL) + 127) / 128) * 128; // 128-token tiles x 128 padded columns
     const size_t fcols = D.d > 128 ? (size_t)((D.d + 31) / 32) * 32 : 128; // (d = 256: eight column tiles per token tile)
-    p->xf = take(RLf * fcols * 4);
-    p->yf = take(RLf * fcols * 4);
-    p->qkv = take(RL * 3 * D.d * 4);
-    p->qkv_b1 = take((RL < 256 ? RL : 256) * 3 * D.d * 4);
-    p->ao = take(RL * D.d * 4);
-    p->h = take(RL * D.ffn_dim * 4);
-    p->ru = take((size_t)ctx->max_seqs * 4);
-    p->xb = take(mp * ctx->d_pad * 2);
-    p->eps = take(mp * 4);
-    p->thr = take(mp * 4);
-    p->gm = take((size_t)IRS_MAX_GROUPS * mp * 4);
-    p->cnt = take(mp * (size_t)IRS_CAND_BUCKETS * 4);
-    p->cand = take(mp * (size_t)IRS_CAND_CAP * 8);
-    {
-        size_t lse_b = (size_t)ctx->lse_slots * mp * 8, ring_b = (size_t)IRS_LSE_SLOTS_RING * 32 * 8; // (the ring form: <= 32 rows, more slots)
-        p->lse = take(lse_b > ring_b ? lse_b : ring_b);
+    take(ctx->act_xf, RLf * fcols * 4); // fragment-major copies of x / y (residual inputs of the LN-fused GEMMs)
+    take(ctx->act_yf, RLf * fcols * 4);
+    take(ctx->act_qkv, RL * 3 * D.d * 4);
+    take(ctx->act_qkv_b1, (RL < 256 ? RL : 256) * 3 * D.d * 4); // second q | k | v buffer of the single-sequence fused-attention path
+    take(ctx->act_ao, RL * D.d * 4);
+    take(ctx->act_h, RL * D.ffn_dim * 4);
+    take(ctx->act_ru, S * 4);
+    // scoring
+    take(ctx->xb, mp * ctx->d_pad * 2);
+    take(ctx->eps, mp * 4);
+    take(ctx->thr, mp * 4);
+    take(ctx->gm, (size_t)IRS_MAX_GROUPS * mp * 4);
+    take(ctx->cand_cnt, mp * (size_t)IRS_CAND_BUCKETS * 4);
+    take(ctx->cand, mp * (size_t)IRS_CAND_CAP * 8);
+    const size_t lse_b = (size_t)ctx->lse_slots * mp * 8, ring_b = (size_t)IRS_LSE_SLOTS_RING * 32 * 8; // (the ring form: <= 32 rows, more slots)
+    take(ctx->lse_part, lse_b > ring_b ? lse_b : ring_b);
+    take(ctx->ref_tmp, mp * 4);
+    // path generation scratch
+    take(ctx->xrows, R * D.d * 4);
+    take(ctx->top_val, R * D.max_k * 4);
+    take(ctx->top_ids, R * D.max_k * 8);
+    take(ctx->row_status, R * 4);
+    take(ctx->step_ctr, 256); // [0..1] step pair of the path loops, [8..40) arrival counters of k_topk_direct
+    take(ctx->pos_tmp, S * 4);
+    // beam-search state
+    for (irs_beam_state &b : ctx->bm) {
+        take(b.seq, RL * 8);
+        take(b.hep, S * 4);
+        take(b.cum, S * 8);
+        take(b.paths, S * IRS_MAX_PATH * 4);
     }
-    p->ref = take(mp * 4);
-    p->xrows = take((size_t)ctx->max_rows * D.d * 4);
-    p->tval = take((size_t)ctx->max_rows * D.max_k * 4);
-    p->tids = take((size_t)ctx->max_rows * D.max_k * 8);
-    p->status = take((size_t)ctx->max_rows * 4);
-    p->step = take(256);
-    p->pos = take((size_t)ctx->max_seqs * 4);
+    take(ctx->bm_side[0].user, S * 8);
+    take(ctx->lse_max, R * 4);
+    take(ctx->lse_sum, R * 4);
+    // packed (pad-free) decode plan
+    take(ctx->tok_row, RL * 4);
+    take(ctx->seq_cnt, S * 4);
+    take(ctx->seq_off, S * 4);
+    take(ctx->seq_qrow, S * 4);
+    take(ctx->seq_padq, S * 4);
+    take(ctx->m_dev, 256);
+    // plan of the sequence-resident layer kernel
+    take(ctx->tile_seq, S * 16 * 4, seq_shape);
+    take(ctx->tile_idx, S * 16 * 4, seq_shape);
+    take(ctx->seq_row0, S * 4, seq_shape);
+    take(ctx->qrow_tile, S * 4, seq_shape);
+    take(ctx->n_wg_dev, 256, seq_shape);
+    // item-sharded loops (comm.hip): this rank's decoded rows, the exchange buffers, the all-reduced row maxima
+    take(ctx->x_local, S * D.d * 4);
+    take(ctx->keys_send, R * D.max_k * 8);
+    take(ctx->keys_recv, R * D.max_k * 8);
+    take(ctx->lse_gmax, R * 4);
+    take(ctx->ce_pairs, (size_t)ctx->shard.world * 2 * R * 4); // irs_ce_forward_sharded (ce_sharded.hip)
+    // cooperative exhaustive fallback: the recorded rows, and on large shards the per-strip lists
+    take(ctx->fb_count, 256);
+    take(ctx->fb_list, R * 4);
+    take(ctx->exh_keys, (size_t)IRS_EXH_SCRATCH_KEYS * 8, ctx->n_local >= IRS_COOP_FALLBACK_MIN_ITEMS);
+    // irs_generate_paths_until: the live users' compacted state
     for (int i = 0; i < 2; ++i) {
-        p->bseq[i] = take((size_t)ctx->max_seqs * D.max_len * 8);
-        p->bhep[i] = take((size_t)ctx->max_seqs * 4);
-        p->bcum[i] = take((size_t)ctx->max_seqs * 8);
-        p->bpaths[i] = take((size_t)ctx->max_seqs * IRS_MAX_PATH * 4);
+        take(ctx->un_seq[i], RL * 8);
+        take(ctx->un_user[i], S * 8);
+        take(ctx->un_hep[i], S * 4);
+        take(ctx->un_map[i], S * 4);
     }
-    p->buser = take((size_t)ctx->max_seqs * 8);
-    p->lmax = take((size_t)ctx->max_rows * 4);
-    p->lsum = take((size_t)ctx->max_rows * 4);
-    p->tokrow = take(RL * 4);
-    p->scnt = take((size_t)ctx->max_seqs * 4);
-    p->soff = take((size_t)ctx->max_seqs * 4);
-    p->sqrow = take((size_t)ctx->max_seqs * 4);
-    p->spadq = take((size_t)ctx->max_seqs * 4);
-    p->mdev = take(256);
-    p->tseq = seq_shape ? take((size_t)ctx->max_seqs * 16 * 4) : 0;
-    p->tidx = seq_shape ? take((size_t)ctx->max_seqs * 16 * 4) : 0;
-    p->srow0 = seq_shape ? take((size_t)ctx->max_seqs * 4) : 0;
-    p->qtile = seq_shape ? take((size_t)ctx->max_seqs * 4) : 0;
-    p->nwg = seq_shape ? take(256) : 0;
-    p->xlocal = take((size_t)ctx->max_seqs * D.d * 4);
-    p->ksend = take((size_t)ctx->max_rows * D.max_k * 8); // exchange buffers of the item-sharded loops (comm.hip)
-    p->krecv = take((size_t)ctx->max_rows * D.max_k * 8);
-    p->gmax = take((size_t)ctx->max_rows * 4);
-    p->cepairs = take((size_t)ctx->shard.world * 2 * ctx->max_rows * 4); // irs_ce_forward_sharded (ce_sharded.hip)
-    p->fbcount = take(256);
-    p->fblist = take((size_t)ctx->max_rows * 4);
-    p->exhkeys = ctx->n_local >= IRS_COOP_FALLBACK_MIN_ITEMS ? take((size_t)IRS_EXH_SCRATCH_KEYS * 8) : 0;
-    for (int i = 0; i < 2; ++i) { // irs_generate_paths_until: the live users' compacted state
-        p->useq[i] = take((size_t)ctx->max_seqs * D.max_len * 8);
-        p->uuser[i] = take((size_t)ctx->max_seqs * 8);
-        p->uhep[i] = take((size_t)ctx->max_seqs * 4);
-        p->umap[i] = take((size_t)ctx->max_seqs * 4);
-    }
-    p->ufin = take((size_t)ctx->max_seqs * 4);
-    p->udst = take((size_t)ctx->max_seqs * 4);
-    p->ustatus = take((size_t)ctx->max_seqs * 4);
-    p->ustage = take((size_t)ctx->max_seqs * IRS_MAX_PATH * 4);
-    p->ucount = take(256);
-    p->buser2 = take((size_t)ctx->max_seqs * 8); // irs_beam_search_until: the per-row arrays only (24 bytes per sequence)
+    take(ctx->un_fin, S * 4);
+    take(ctx->un_dst, S * 4);
+    take(ctx->un_status, S * 4);
+    take(ctx->un_stage, S * IRS_MAX_PATH * 4);
+    take(ctx->un_count, 256);
+    // irs_beam_search_until: the per-row arrays only (24 bytes per sequence)
+    take(ctx->bm_side[1].user, S * 8);
     for (int i = 0; i < 2; ++i) {
-        p->bfin[i] = take((size_t)ctx->max_seqs * 4);
-        p->bdone[i] = take((size_t)ctx->max_seqs * 4);
+        take(ctx->bm[i].fin, S * 4);
+        take(ctx->bm_side[i].done, S * 4);
     }
-    p->total = off;
+    return off;
 }
 
 extern "C" size_t irs_workspace_bytes(const irs_ctx *ctx) {
-    if (!ctx) return 0;
-    ws_plan p;
-    workspace_plan(ctx, &p);
-    return p.total;
+    return ctx ? workspace_walk(const_cast<irs_ctx *>(ctx), nullptr) : 0; // (no base: the walk writes nothing)
 }
 
 extern "C" int irs_bind_workspace(irs_ctx *ctx, void *ws, size_t bytes) {
     if (!ctx || !ws) return IRS_E_INVALID;
-    ws_plan p;
-    workspace_plan(ctx, &p);
-    if (bytes < p.total) IRS_FAIL(ctx, IRS_E_INVALID, "workspace too small: %zu < %zu", bytes, p.total);
+    const size_t need = workspace_walk(ctx, nullptr);
+    if (bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "workspace too small: %zu < %zu", bytes, need);
     if (((uintptr_t)ws) & 255) IRS_FAIL(ctx, IRS_E_INVALID, "workspace must be 256-byte aligned");
-    char *b = (char *)ws;
-    ctx->ws = b;
+    ctx->ws = (char *)ws;
     ctx->ws_bytes = bytes;
-    ctx->act_x = (float *)(b + p.x);
-    ctx->act_y = (float *)(b + p.y);
-    ctx->act_xf = (float *)(b + p.xf);
-    ctx->act_yf = (float *)(b + p.yf);
-    ctx->act_qkv = (float *)(b + p.qkv);
-    ctx->act_qkv_b1 = (float *)(b + p.qkv_b1);
-    ctx->act_ao = (float *)(b + p.ao);
-    ctx->act_h = (float *)(b + p.h);
-    ctx->act_ru = (float *)(b + p.ru);
-    ctx->xb = (uint4 *)(b + p.xb);
-    ctx->eps = (float *)(b + p.eps);
-    ctx->thr = (float *)(b + p.thr);
+    workspace_walk(ctx, ctx->ws);
     ctx->thr_valid = 0;
-    ctx->gm = (float *)(b + p.gm);
-    ctx->cand_cnt = (unsigned int *)(b + p.cnt);
-    ctx->cand = (unsigned long long *)(b + p.cand);
-    ctx->lse_part = (float *)(b + p.lse);
-    ctx->ref_tmp = (float *)(b + p.ref);
-    ctx->xrows = (float *)(b + p.xrows);
-    ctx->top_val = (float *)(b + p.tval);
-    ctx->top_ids = (int64_t *)(b + p.tids);
-    ctx->row_status = (int32_t *)(b + p.status);
-    ctx->step_ctr = (int32_t *)(b + p.step); // [0..1] step pair of the path loops, [8..40) arrival counters of k_topk_direct
     IRS_CHECK_HIP(ctx, hipMemset(ctx->step_ctr, 0, 256));
-    ctx->pos_tmp = (int32_t *)(b + p.pos);
-    for (int i = 0; i < 2; ++i) {
-        ctx->bm_seq[i] = (int64_t *)(b + p.bseq[i]);
-        ctx->bm_hep[i] = (int32_t *)(b + p.bhep[i]);
-        ctx->bm_cum[i] = (double *)(b + p.bcum[i]);
-        ctx->bm_paths[i] = (float *)(b + p.bpaths[i]);
-    }
-    ctx->bm_user = (int64_t *)(b + p.buser);
-    ctx->lse_max = (float *)(b + p.lmax);
-    ctx->lse_sum = (float *)(b + p.lsum);
-    ctx->tok_row = (int32_t *)(b + p.tokrow);
-    ctx->seq_cnt = (int32_t *)(b + p.scnt);
-    ctx->seq_off = (int32_t *)(b + p.soff);
-    ctx->seq_qrow = (int32_t *)(b + p.sqrow);
-    ctx->seq_padq = (int32_t *)(b + p.spadq);
-    ctx->m_dev = (int32_t *)(b + p.mdev);
-    const bool seq_shape = irs_seq_shape(ctx->dims);
-    ctx->tile_seq = seq_shape ? (int32_t *)(b + p.tseq) : nullptr;
-    ctx->tile_idx = seq_shape ? (int32_t *)(b + p.tidx) : nullptr;
-    ctx->seq_row0 = seq_shape ? (int32_t *)(b + p.srow0) : nullptr;
-    ctx->qrow_tile = seq_shape ? (int32_t *)(b + p.qtile) : nullptr;
-    ctx->n_wg_dev = seq_shape ? (int32_t *)(b + p.nwg) : nullptr;
-    ctx->x_local = (float *)(b + p.xlocal);
-    ctx->keys_send = (uint64_t *)(b + p.ksend);
-    ctx->keys_recv = (uint64_t *)(b + p.krecv);
-    ctx->lse_gmax = (float *)(b + p.gmax);
-    ctx->ce_pairs = (float *)(b + p.cepairs);
-    ctx->fb_count = (unsigned int *)(b + p.fbcount);
-    ctx->fb_list = (int32_t *)(b + p.fblist);
-    ctx->exh_keys = ctx->n_local >= IRS_COOP_FALLBACK_MIN_ITEMS ? (unsigned long long *)(b + p.exhkeys) : nullptr;
-    for (int i = 0; i < 2; ++i) {
-        ctx->un_seq[i] = (int64_t *)(b + p.useq[i]);
-        ctx->un_user[i] = (int64_t *)(b + p.uuser[i]);
-        ctx->un_hep[i] = (int32_t *)(b + p.uhep[i]);
-        ctx->un_map[i] = (int32_t *)(b + p.umap[i]);
-    }
-    ctx->un_fin = (int32_t *)(b + p.ufin);
-    ctx->un_dst = (int32_t *)(b + p.udst);
-    ctx->un_status = (int32_t *)(b + p.ustatus);
-    ctx->un_stage = (float *)(b + p.ustage);
-    ctx->un_count = (int32_t *)(b + p.ucount);
-    ctx->bm_user2 = (int64_t *)(b + p.buser2);
-    for (int i = 0; i < 2; ++i) {
-        ctx->bm_fin[i] = (int32_t *)(b + p.bfin[i]);
-        ctx->bm_done[i] = (int32_t *)(b + p.bdone[i]);
-    }
     irs_drop_graphs(ctx);
     return IRS_OK;
 }
@@ -527,7 +452,7 @@ static int ready(irs_ctx *ctx) {
 
 // entry points that filter through the bf16 catalog copy and its norms: a training entry point since the last
 // irs_finalize_weights means project.* may have moved under them (the filter's |approx - exact| <= eps would not hold)
-static int ready_filter(irs_ctx *ctx, int sweep) {
+int irs_ready_filter(irs_ctx *ctx, int sweep) {
     int rc = ready(ctx);
     if (rc) return rc;
     if (ctx->proj_stale && sweep == IRS_SWEEP_BF16)
@@ -564,7 +489,7 @@ static int check_rows(irs_ctx *ctx, const char *fn, const void *xrows, int M) {
 
 extern "C" int irs_score_topk_carry(irs_ctx *ctx, const float *xrows, int32_t M, int32_t k, int32_t sweep, float *val,
                                     int64_t *ids0, int32_t *status, void *stream) {
-    int rc = ready_filter(ctx, sweep);
+    int rc = irs_ready_filter(ctx, sweep);
     if (rc) return rc;
     if ((rc = check_rows(ctx, "irs_score_topk_carry", xrows, M))) return rc;
     if (k < 1 || k > ctx->dims.max_k || !val || !ids0 || !status) IRS_FAIL(ctx, IRS_E_INVALID, "irs_score_topk_carry: bad k / outputs");
@@ -574,7 +499,7 @@ extern "C" int irs_score_topk_carry(irs_ctx *ctx, const float *xrows, int32_t M,
 
 extern "C" int irs_score_topk(irs_ctx *ctx, const float *xrows, int32_t M, int32_t k, int32_t sweep, float *val,
                               int64_t *ids0, int32_t *status, void *stream) {
-    int rc = ready_filter(ctx, sweep);
+    int rc = irs_ready_filter(ctx, sweep);
     if (rc) return rc;
     if ((rc = check_rows(ctx, "irs_score_topk", xrows, M))) return rc;
     if (k < 1 || k > ctx->dims.max_k || !val || !ids0 || !status) IRS_FAIL(ctx, IRS_E_INVALID, "irs_score_topk: bad k / outputs");
@@ -620,7 +545,7 @@ extern "C" int irs_score_lse(irs_ctx *ctx, const float *xrows, int32_t M, float 
 
 extern "C" int irs_score_topk_lse(irs_ctx *ctx, const float *xrows, int32_t M, int32_t k, int32_t sweep, float *val,
                                   int64_t *ids0, int32_t *status, float *omax, float *osum, void *stream) {
-    int rc = ready_filter(ctx, sweep);
+    int rc = irs_ready_filter(ctx, sweep);
     if (rc) return rc;
     if ((rc = check_rows(ctx, "irs_score_topk_lse", xrows, M))) return rc;
     if (k < 1 || k > ctx->dims.max_k || !val || !ids0 || !status || !omax || !osum)
@@ -686,8 +611,9 @@ extern "C" int irs_build_eval_batch(irs_ctx *ctx, const int64_t *items, const in
     if (!ctx) return IRS_E_INVALID;
     if (!items || !offsets || !seq || !target || !label || B < 1 || raw_len < 1 || gap_len < 0 || (pool && n_pool < 1))
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_build_eval_batch: bad arguments");
-    return irs_launch_build_eval_batch(ctx, items, offsets, B, raw_len, gap_len, targets_in, pool, n_pool, seed, seq, target,
-                                       label, raw, raw_n, status, (hipStream_t)stream);
+    const irs_eval_batch_args a{items, offsets, B, ctx->dims.max_len, raw_len, gap_len, ctx->dims.n_item, targets_in, pool, n_pool, seed,
+                               seq, target, label, raw, raw_n, status};
+    return irs_launch_build_eval_batch(ctx, a, (hipStream_t)stream);
 }
 
 extern "C" int irs_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int32_t B, const float *val, const int64_t *ids0,
@@ -698,31 +624,26 @@ extern "C" int irs_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int32_t B
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_path_step: bad arguments");
     if (sample && (sample_k < 1 || sample_k > IRS_MAX_SAMPLE_K))
         IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_path_step: sample_k must be in [1, %d]", IRS_MAX_SAMPLE_K);
-    return irs_launch_path_step(ctx, seq, hep, B, val, ids0, k, step, nullptr, paths, path_ld, sample, sample_k, seed,
-                                status, (hipStream_t)stream);
+    const irs_path_args pa{seq, hep, ctx->dims.max_len, paths, path_ld, sample, sample_k, seed, status, nullptr, step, nullptr, 1};
+    return irs_launch_path_step(ctx, pa, B, val, ids0, k, (hipStream_t)stream);
 }
 
-// one search step on one device: decode -> rows at hep -> top-k -> choose/update
-static int enqueue_step(irs_ctx *ctx, int64_t *seq, const int64_t *user, int32_t *hep, int B, int k, int sweep,
-                        int sample, int sample_k, uint64_t seed, float *paths, int path_ld, int32_t *status,
-                        hipStream_t s, int carry = 0) {
+// one search step on one device: decode -> rows at hep -> top-k -> choose/update.  `pa` is the loop's (loop_path_args): the step
+// index comes from the device counter
+static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int B, int k, int sweep, hipStream_t s, int carry = 0) {
     int rc;
     const bool merged = irs_small_plan(ctx->dims, B); // (the decode below is rows-only: its plan is the single-workgroup one)
+    pa.step_next = merged ? ctx->step_ctr + 1 : nullptr;
     ctx->step_pair = merged ? ctx->step_ctr : nullptr;
-    rc = irs_launch_decode(ctx, seq, user, B, nullptr, hep, ctx->xrows, nullptr, s);
+    rc = irs_launch_decode(ctx, pa.seq, user, B, nullptr, pa.hep, ctx->xrows, nullptr, s);
     ctx->step_pair = nullptr;
     if (rc) return rc;
     // small shard, few rows: the workgroup that ranks a row's candidates also takes the row's path step
-    if (merged && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k)) {
-        const irs_path_args pa{seq, hep, ctx->dims.max_len, paths, path_ld, sample, sample_k, (unsigned long long)seed, status,
-                               ctx->step_ctr, 0, ctx->step_ctr + 1, 1};
+    if (merged && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k))
         return irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, &pa);
-    }
     if ((rc = irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, nullptr, nullptr, carry)))
         return rc;
-    if ((rc = irs_launch_path_step(ctx, seq, hep, B, ctx->top_val, ctx->top_ids, k, 0, ctx->step_ctr, paths, path_ld,
-                                   sample, sample_k, seed, status, s, merged ? ctx->step_ctr + 1 : nullptr)))
-        return rc;
+    if ((rc = irs_launch_path_step(ctx, pa, B, ctx->top_val, ctx->top_ids, k, s))) return rc;
     return merged ? IRS_OK : irs_launch_inc(ctx, ctx->step_ctr, s);
 }
 
@@ -766,11 +687,45 @@ int irs_check_k(irs_ctx *ctx, const char *fn, int k, int world, int sweep, int s
     return IRS_OK;
 }
 
-int irs_check_beam_args(irs_ctx *ctx, const char *fn, const void *seq0, const void *hep0, const void *paths, const void *scores,
-                        const void *status, int B, int W, int P) {
-    if (!seq0 || !hep0 || !paths || !scores || !status || B < 1) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad arguments", fn);
+int irs_check_beam_args(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W, int P) {
+    if (!ptrs_ok || B < 1) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad arguments", fn);
     if (W < 1 || W > 32) IRS_FAIL(ctx, IRS_E_INVALID, "%s: beam width must be in [1, 32]", fn);
     if (P < 1 || P > IRS_MAX_PATH) IRS_FAIL(ctx, IRS_E_INVALID, "%s: path length must be in [1, %d]", fn, IRS_MAX_PATH);
+    return IRS_OK;
+}
+
+// the common opening of the four single-device search entry points.  W == 0: a greedy loop over B rows; else a beam search over
+// B * W rows.  ptrs_ok: none of the call's required pointers is null
+static int check_search(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W, int P, int k, int sweep, int sample, int sample_k) {
+    int rc = irs_ready_filter(ctx, sweep);
+    if (rc) return rc;
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s needs the whole catalog on one device", fn);
+    if (W) {
+        if ((rc = irs_check_beam_args(ctx, fn, ptrs_ok, B, W, P))) return rc;
+        if ((int64_t)B * W > ctx->max_seqs || (int64_t)B * W > ctx->max_rows)
+            IRS_FAIL(ctx, IRS_E_INVALID, "%s: B*W=%d exceeds max_seqs=%d / max_rows=%d", fn, B * W, ctx->max_seqs, ctx->max_rows);
+    } else {
+        if (!ptrs_ok || B < 1 || P < 1) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad arguments", fn);
+        if (B > ctx->max_seqs || B > ctx->max_rows) IRS_FAIL(ctx, IRS_E_INVALID, "%s: B too large", fn);
+    }
+    return irs_check_k(ctx, fn, k, 1, sweep, sample, sample_k);
+}
+
+// the path step's arguments inside a search loop: the step index comes from the device counter
+static irs_path_args loop_path_args(irs_ctx *ctx, int64_t *seq, int32_t *hep, float *paths, int P, int sample, int sample_k,
+                                    uint64_t seed, int32_t *status) {
+    return irs_path_args{seq, hep, ctx->dims.max_len, paths, P, sample, sample_k, seed, status, ctx->step_ctr, 0, nullptr, 1};
+}
+
+// The check of the two until loops: places of the live rows in un_dst (irs_launch_until_scan over `fin`), their number in *left
+// after a 4-byte copy and a synchronise.  `what`: what the caller's message calls a row
+static int live_count(irs_ctx *ctx, const char *fn, const char *what, const int32_t *fin, int live, int *left, hipStream_t s) {
+    int rc = irs_launch_until_scan(ctx, fin, live, ctx->un_dst, ctx->un_count, s);
+    if (rc) return rc;
+    IRS_CHECK_HIP(ctx, hipMemcpyAsync(&ctx->un_count_host, ctx->un_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    IRS_CHECK_HIP(ctx, hipStreamSynchronize(s));
+    *left = ctx->un_count_host;
+    if (*left < 0 || *left > live) IRS_FAIL(ctx, IRS_E_STATE, "%s: live count %d of %d %s", fn, *left, live, what);
     return IRS_OK;
 }
 
@@ -782,36 +737,32 @@ int irs_search_begin(irs_ctx *ctx, int32_t *status, int B, hipStream_t s) {
 
 int irs_beam_finish(irs_ctx *ctx, size_t rows, int P, float *paths, double *scores, int64_t *seq_final, hipStream_t s) {
     const int fin = P & 1;
-    IRS_CHECK_HIP(ctx, hipMemcpyAsync(paths, ctx->bm_paths[fin], rows * P * sizeof(float), hipMemcpyDeviceToDevice, s));
-    IRS_CHECK_HIP(ctx, hipMemcpyAsync(scores, ctx->bm_cum[fin], rows * sizeof(double), hipMemcpyDeviceToDevice, s));
+    IRS_CHECK_HIP(ctx, hipMemcpyAsync(paths, ctx->bm[fin].paths, rows * P * sizeof(float), hipMemcpyDeviceToDevice, s));
+    IRS_CHECK_HIP(ctx, hipMemcpyAsync(scores, ctx->bm[fin].cum, rows * sizeof(double), hipMemcpyDeviceToDevice, s));
     if (seq_final)
-        IRS_CHECK_HIP(ctx, hipMemcpyAsync(seq_final, ctx->bm_seq[fin], rows * ctx->dims.max_len * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        IRS_CHECK_HIP(ctx, hipMemcpyAsync(seq_final, ctx->bm[fin].seq, rows * ctx->dims.max_len * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
     return IRS_OK;
 }
 
 extern "C" int irs_generate_paths(irs_ctx *ctx, int64_t *seq, const int64_t *user, int32_t *hep, int32_t B,
                                   int32_t max_path_len, int32_t k, int32_t sweep, int32_t sample, int32_t sample_k,
                                   uint64_t seed, int32_t use_graph, float *paths, int32_t *status, void *stream) {
-    int rc = ready_filter(ctx, sweep);
+    int rc = check_search(ctx, "irs_generate_paths", seq && hep && paths && status, B, 0, max_path_len, k, sweep, sample, sample_k);
     if (rc) return rc;
-    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_generate_paths needs the whole catalog on one device");
-    if (!seq || !hep || !paths || !status || B < 1 || max_path_len < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths: bad arguments");
-    if (B > ctx->max_seqs || B > ctx->max_rows) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths: B too large");
-    if ((rc = irs_check_k(ctx, "irs_generate_paths", k, 1, sweep, sample, sample_k))) return rc;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
+    const irs_path_args pa = loop_path_args(ctx, seq, hep, paths, max_path_len, sample, sample_k, seed, status);
     if (irs_may_capture(ctx, use_graph)) { // one step per graph; a captured step never carries emission thresholds
         irs_step_key key = {};
         key.kind = IRS_STEP_GREEDY, key.B = B, key.P = max_path_len, key.k = k, key.sweep = sweep;
         key.sample = sample, key.sample_k = sample_k, key.seed = seed;
         key.seq = seq, key.user = user, key.hep = hep, key.paths = paths, key.status = status;
         return irs_replay_steps(ctx, &ctx->g_greedy, key, [&](hipStream_t q) {
-            return enqueue_step(ctx, seq, user, hep, B, k, sweep, sample, sample_k, seed, paths, max_path_len, status, q);
+            return enqueue_step(ctx, pa, user, B, k, sweep, q);
         }, max_path_len, s);
     }
     for (int i = 0; i < max_path_len; ++i) // (steps behind the first may reuse the previous step's emission thresholds)
-        if ((rc = enqueue_step(ctx, seq, user, hep, B, k, sweep, sample, sample_k, seed, paths, max_path_len, status, s, i > 0)))
-            return rc;
+        if ((rc = enqueue_step(ctx, pa, user, B, k, sweep, s, i > 0))) return rc;
     return IRS_OK;
 }
 
@@ -823,12 +774,8 @@ extern "C" int irs_generate_paths_until(irs_ctx *ctx, int64_t *seq, const int64_
                                         int32_t max_path_len, int32_t k, int32_t sweep, int32_t sample, int32_t sample_k,
                                         uint64_t seed, int32_t check_every, float *paths, int32_t *status, int64_t *host_stats,
                                         void *stream) {
-    int rc = ready_filter(ctx, sweep);
+    int rc = check_search(ctx, "irs_generate_paths_until", seq && hep && paths && status, B, 0, max_path_len, k, sweep, sample, sample_k);
     if (rc) return rc;
-    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_generate_paths_until needs the whole catalog on one device");
-    if (!seq || !hep || !paths || !status || B < 1 || max_path_len < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths_until: bad arguments");
-    if (B > ctx->max_seqs || B > ctx->max_rows) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths_until: B too large");
-    if ((rc = irs_check_k(ctx, "irs_generate_paths_until", k, 1, sweep, sample, sample_k))) return rc;
     if (check_every < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths_until: check_every must be >= 1");
     if (max_path_len > IRS_MAX_PATH)
         IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_generate_paths_until: max_path_len %d > %d", max_path_len, IRS_MAX_PATH);
@@ -837,34 +784,29 @@ extern "C" int irs_generate_paths_until(irs_ctx *ctx, int64_t *seq, const int64_
     if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
     IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->un_fin, 0, sizeof(int32_t) * B, s));
     IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->un_status, 0, sizeof(int32_t) * B, s));
-    // the first steps run in place on the caller's rows (identity map); the first compaction that removes a row moves the rest
-    int64_t *cseq = seq;
+    // the first steps run in place on the caller's rows (identity map); the first compaction that removes a row moves the rest.
+    // (the step writes stage[row][i]: it reads the index from the same device counter as irs_generate_paths' steps)
+    irs_path_args pa = loop_path_args(ctx, seq, hep, ctx->un_stage, P, sample, sample_k, seed, ctx->un_status);
     const int64_t *cuser = user;
-    int32_t *chep = hep;
     const int32_t *cmap = nullptr;
     int live = B, side = 0, carry = 0;
     int64_t steps = 0, row_steps = 0;
     // (an error below returns at once: host_stats unwritten, paths / status / seq / hep partly written -- see the header; the step
     //  counter pair is left wherever the last step put it, and every search loop resets it in irs_search_begin)
     for (int i = 0; i < P && live > 0; ++i) {
-        // (the step writes stage[row][i]: it reads the index from the same device counter as irs_generate_paths' steps)
-        if ((rc = enqueue_step(ctx, cseq, cuser, chep, live, k, sweep, sample, sample_k, seed, ctx->un_stage, P, ctx->un_status, s, carry)))
-            return rc;
-        if ((rc = irs_launch_until_record(ctx, ctx->un_stage, P, i, cmap, cseq, live, ctx->un_fin, ctx->un_status, paths, status, s)))
+        if ((rc = enqueue_step(ctx, pa, cuser, live, k, sweep, s, carry))) return rc;
+        if ((rc = irs_launch_until_record(ctx, ctx->un_stage, P, i, cmap, pa.seq, live, ctx->un_fin, ctx->un_status, paths, status, s)))
             return rc;
         ++steps, row_steps += live, carry = 1;
         if ((i + 1) % check_every || i + 1 == P) continue; // no check due, or nothing left to decide after the last step
-        if ((rc = irs_launch_until_scan(ctx, ctx->un_fin, live, ctx->un_dst, ctx->un_count, s))) return rc;
-        IRS_CHECK_HIP(ctx, hipMemcpyAsync(&ctx->un_count_host, ctx->un_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        IRS_CHECK_HIP(ctx, hipStreamSynchronize(s));
-        const int left = ctx->un_count_host;
-        if (left < 0 || left > live) IRS_FAIL(ctx, IRS_E_STATE, "irs_generate_paths_until: live count %d of %d rows", left, live);
+        int left;
+        if ((rc = live_count(ctx, "irs_generate_paths_until", "rows", ctx->un_fin, live, &left, s))) return rc;
         if (left == live) continue;
         if (left > 0) {
-            if ((rc = irs_launch_until_gather(ctx, ctx->un_dst, live, cseq, cuser, chep, cmap, ctx->un_seq[side], ctx->un_user[side],
+            if ((rc = irs_launch_until_gather(ctx, ctx->un_dst, live, pa.seq, cuser, pa.hep, cmap, ctx->un_seq[side], ctx->un_user[side],
                                               ctx->un_hep[side], ctx->un_map[side], s)))
                 return rc;
-            cseq = ctx->un_seq[side], cuser = cuser ? ctx->un_user[side] : nullptr, chep = ctx->un_hep[side], cmap = ctx->un_map[side];
+            pa.seq = ctx->un_seq[side], cuser = cuser ? ctx->un_user[side] : nullptr, pa.hep = ctx->un_hep[side], cmap = ctx->un_map[side];
             side ^= 1;
             IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->un_fin, 0, sizeof(int32_t) * left, s));
             // B <= 64 hands the step index over in a second word that larger batches do not keep: both words, from the host's count
@@ -878,6 +820,11 @@ extern "C" int irs_generate_paths_until(irs_ctx *ctx, int64_t *seq, const int64_
 }
 
 // ------------------------------------------------------------------ beam search
+// (a step only reads its input state: the public steps' const inputs go into the kernels' one state type)
+static irs_beam_state beam_state(const int64_t *seq, const int32_t *hep, const double *cum, const float *paths, const int32_t *fin) {
+    return irs_beam_state{(int64_t *)seq, (int32_t *)hep, (double *)cum, (float *)paths, (int32_t *)fin};
+}
+
 extern "C" int irs_beam_step(irs_ctx *ctx, const int64_t *seq_in, const int32_t *hep_in, const double *cum_in,
                              const float *paths_in, const float *val, const int64_t *ids0, const float *lse_max,
                              const float *lse_sum, int32_t B, int32_t W, int32_t k, int32_t step, int32_t P,
@@ -888,56 +835,56 @@ extern "C" int irs_beam_step(irs_ctx *ctx, const int64_t *seq_in, const int32_t 
         !status || B < 1 || W < 1 || k < 1 || P < 1 || step < 0 || step >= P)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step: bad arguments");
     if (W > 1 && (!lse_max || !lse_sum)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step: W > 1 needs the row log-sum-exp");
-    return irs_launch_beam_step(ctx, seq_in, hep_in, cum_in, paths_in, val, ids0, W > 1 ? lse_max : nullptr,
-                                W > 1 ? lse_sum : nullptr, B, W, k, step, nullptr, P, seq_out, hep_out, cum_out,
-                                paths_out, status, (hipStream_t)stream);
+    const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k};
+    return irs_launch_beam_step(ctx, beam_state(seq_in, hep_in, cum_in, paths_in, nullptr), {seq_out, hep_out, cum_out, paths_out, nullptr},
+                                cand, B, W, step, nullptr, P, status, nullptr, (hipStream_t)stream);
 }
 
-static int enqueue_beam_step(irs_ctx *ctx, int in, int B, int W, int k, int sweep, int P, int32_t *status, hipStream_t s) {
-    const int out = in ^ 1, rows = B * W;
+// The tail of every beam loop's step, the sharded one's too: the beam step from side `in` to the other on the lists in top_val /
+// top_ids, then the step counter.  until == nullptr: the plain step
+int irs_enqueue_beam_tail(irs_ctx *ctx, int in, const float *lse_max, const float *lse_sum, int B, int W, int k, int P, int32_t *status,
+                          const irs_beam_until *until, hipStream_t s) {
+    const irs_beam_cand cand{ctx->top_val, ctx->top_ids, lse_max, lse_sum, k};
+    const int rc = irs_launch_beam_step(ctx, ctx->bm[in], ctx->bm[in ^ 1], cand, B, W, 0, ctx->step_ctr, P, status, until, s);
+    return rc ? rc : irs_launch_inc(ctx, ctx->step_ctr, s);
+}
+
+// one beam step of B users on one device: decode -> top-k (+ log-sum-exp) of the B * W rows -> beam step -> step counter
+static int enqueue_beam_step(irs_ctx *ctx, int in, const int64_t *user, int B, int W, int k, int sweep, int P, int32_t *status,
+                             const irs_beam_until *until, hipStream_t s) {
+    const int rows = B * W;
+    float *const lmax = W > 1 ? ctx->lse_max : nullptr, *const lsum = W > 1 ? ctx->lse_sum : nullptr;
     int rc;
-    if ((rc = irs_launch_decode(ctx, ctx->bm_seq[in], ctx->bm_user, rows, nullptr, ctx->bm_hep[in], ctx->xrows, nullptr, s))) return rc;
+    if ((rc = irs_launch_decode(ctx, ctx->bm[in].seq, user, rows, nullptr, ctx->bm[in].hep, ctx->xrows, nullptr, s))) return rc;
     // W > 1: top-k and log-sum-exp out of one call (one pass over the float32 catalog on the swept path)
-    if ((rc = irs_launch_topk(ctx, ctx->xrows, rows, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr,
-                              W > 1 ? ctx->lse_max : nullptr, W > 1 ? ctx->lse_sum : nullptr)))
+    if ((rc = irs_launch_topk(ctx, ctx->xrows, rows, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, lmax, lsum)))
         return rc;
-    if ((rc = irs_launch_beam_step(ctx, ctx->bm_seq[in], ctx->bm_hep[in], ctx->bm_cum[in], ctx->bm_paths[in], ctx->top_val,
-                                   ctx->top_ids, W > 1 ? ctx->lse_max : nullptr, W > 1 ? ctx->lse_sum : nullptr, B, W, k, 0,
-                                   ctx->step_ctr, P, ctx->bm_seq[out], ctx->bm_hep[out], ctx->bm_cum[out],
-                                   ctx->bm_paths[out], status, s)))
-        return rc;
-    return irs_launch_inc(ctx, ctx->step_ctr, s);
+    return irs_enqueue_beam_tail(ctx, in, lmax, lsum, B, W, k, P, status, until, s);
 }
 
 extern "C" int irs_beam_search(irs_ctx *ctx, const int64_t *seq0, const int64_t *user, const int32_t *hep0, int32_t B,
                                int32_t W, int32_t P, int32_t k, int32_t sweep, int32_t use_graph, float *paths,
                                double *scores, int64_t *seq_final, int32_t *status, void *stream) {
-    int rc = ready_filter(ctx, sweep);
+    int rc = check_search(ctx, "irs_beam_search", seq0 && hep0 && paths && scores && status, B, W, P, k, sweep, 0, 0);
     if (rc) return rc;
-    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_beam_search needs the whole catalog on one device");
-    if ((rc = irs_check_beam_args(ctx, "irs_beam_search", seq0, hep0, paths, scores, status, B, W, P))) return rc;
-    if ((int64_t)B * W > ctx->max_seqs || (int64_t)B * W > ctx->max_rows)
-        IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search: B*W=%d exceeds max_seqs=%d / max_rows=%d", B * W, ctx->max_seqs, ctx->max_rows);
-    if ((rc = irs_check_k(ctx, "irs_beam_search", k, 1, sweep, 0, 0))) return rc;
     if (ctx->dims.mask_mode == IRS_MASK_IRN && !user) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search: user is null");
     hipStream_t s = (hipStream_t)stream;
+    int64_t *const usr = ctx->bm_side[0].user;
     if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
-    if ((rc = irs_launch_beam_init(ctx, seq0, user, hep0, B, W, P, ctx->bm_seq[0], ctx->bm_user, ctx->bm_hep[0],
-                                   ctx->bm_cum[0], ctx->bm_paths[0], s)))
-        return rc;
+    if ((rc = irs_launch_beam_init(ctx, seq0, user, hep0, B, W, P, ctx->bm[0], usr, s))) return rc;
     int done = 0;
     if (irs_may_capture(ctx, use_graph) && P >= 2) { // the two ping-pong steps per graph; an odd last step runs on the stream
         irs_step_key key = {}; // (the steps work on the context's beam buffers: of the caller's pointers only `status` is baked in)
         key.kind = IRS_STEP_BEAM, key.B = B, key.W = W, key.P = P, key.k = k, key.sweep = sweep, key.status = status;
         if ((rc = irs_replay_steps(ctx, &ctx->g_beam, key, [&](hipStream_t q) {
-                int r = enqueue_beam_step(ctx, 0, B, W, k, sweep, P, status, q);
-                return r ? r : enqueue_beam_step(ctx, 1, B, W, k, sweep, P, status, q);
+                int r = enqueue_beam_step(ctx, 0, usr, B, W, k, sweep, P, status, nullptr, q);
+                return r ? r : enqueue_beam_step(ctx, 1, usr, B, W, k, sweep, P, status, nullptr, q);
             }, P / 2, s)))
             return rc;
         done = P / 2 * 2;
     }
     for (; done < P; ++done)
-        if ((rc = enqueue_beam_step(ctx, done & 1, B, W, k, sweep, P, status, s))) return rc;
+        if ((rc = enqueue_beam_step(ctx, done & 1, usr, B, W, k, sweep, P, status, nullptr, s))) return rc;
     return irs_beam_finish(ctx, (size_t)B * W, P, paths, scores, seq_final, s);
 }
 
@@ -954,74 +901,50 @@ extern "C" int irs_beam_step_until(irs_ctx *ctx, const int64_t *seq_in, const in
     if (W > 1 && (!lse_max || !lse_sum)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_until: W > 1 needs the row log-sum-exp");
     if (stop_rule != IRS_BEAM_STOP_ALL && stop_rule != IRS_BEAM_STOP_BEST)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_until: stop_rule %d (IRS_BEAM_STOP_ALL or IRS_BEAM_STOP_BEST)", stop_rule);
-    return irs_launch_beam_step_until(ctx, seq_in, hep_in, cum_in, paths_in, fin_in, val, ids0, W > 1 ? lse_max : nullptr,
-                                      W > 1 ? lse_sum : nullptr, B, W, k, step, nullptr, P, stop_rule, seq_out, hep_out, cum_out,
-                                      paths_out, fin_out, done, nullptr, status, (hipStream_t)stream);
+    const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k};
+    const irs_beam_until until{done, nullptr, stop_rule};
+    return irs_launch_beam_step(ctx, beam_state(seq_in, hep_in, cum_in, paths_in, fin_in), {seq_out, hep_out, cum_out, paths_out, fin_out},
+                                cand, B, W, step, nullptr, P, status, &until, (hipStream_t)stream);
 }
 
-// The loop.  The beam state of the live users sits in set `cur` of the ping-pong buffers; a step reads it and writes set cur ^ 1,
-// a compaction reads THAT and writes the set the step has just freed.  user / done / map move at compactions only (side `aux`).
-// The buffers and the step counter are the ones a cached beam graph bakes in: irs_beam_search re-initialises all of them.
+// The loop.  The beam state of the live users sits in side `cur` of ctx->bm; a step reads it and writes side cur ^ 1, a compaction
+// reads THAT and writes the side the step has just freed.  user / done / map (`sd`) move at compactions only, between the two
+// sides of ctx->bm_side and un_map.  The buffers and the step counter are the ones a cached beam graph bakes in: irs_beam_search
+// re-initialises all of them.
 extern "C" int irs_beam_search_until(irs_ctx *ctx, const int64_t *seq0, const int64_t *user, const int32_t *hep0, int32_t B,
                                      int32_t W, int32_t P, int32_t k, int32_t sweep, int32_t stop_rule, int32_t check_every,
                                      float *paths, double *scores, int32_t *fin, int64_t *seq_final, int32_t *status,
                                      int64_t *host_stats, void *stream) {
-    int rc = ready_filter(ctx, sweep);
+    int rc = check_search(ctx, "irs_beam_search_until", seq0 && hep0 && paths && scores && status, B, W, P, k, sweep, 0, 0);
     if (rc) return rc;
-    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_beam_search_until needs the whole catalog on one device");
-    if ((rc = irs_check_beam_args(ctx, "irs_beam_search_until", seq0, hep0, paths, scores, status, B, W, P))) return rc;
-    if ((int64_t)B * W > ctx->max_seqs || (int64_t)B * W > ctx->max_rows)
-        IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_until: B*W=%d exceeds max_seqs=%d / max_rows=%d", B * W, ctx->max_seqs, ctx->max_rows);
-    if ((rc = irs_check_k(ctx, "irs_beam_search_until", k, 1, sweep, 0, 0))) return rc;
     if (ctx->dims.mask_mode == IRS_MASK_IRN && !user) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_until: user is null");
     if (stop_rule != IRS_BEAM_STOP_ALL && stop_rule != IRS_BEAM_STOP_BEST)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_until: stop_rule %d (IRS_BEAM_STOP_ALL or IRS_BEAM_STOP_BEST)", stop_rule);
     if (check_every < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_until: check_every must be >= 1");
     hipStream_t s = (hipStream_t)stream;
+    irs_beam_side sd = ctx->bm_side[0]; // (its map is null: the identity until the first compaction)
+    const irs_beam_out res{paths, scores, fin, seq_final};
     if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
-    if ((rc = irs_launch_beam_init(ctx, seq0, user, hep0, B, W, P, ctx->bm_seq[0], ctx->bm_user, ctx->bm_hep[0],
-                                   ctx->bm_cum[0], ctx->bm_paths[0], s)))
-        return rc;
-    IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->bm_fin[0], 0, sizeof(int32_t) * B * W, s));
-    IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->bm_done[0], 0, sizeof(int32_t) * B, s));
-    int64_t *const usr[2] = {ctx->bm_user, ctx->bm_user2};
-    const int32_t *cmap = nullptr; // identity until the first compaction; then un_map[aux]
+    if ((rc = irs_launch_beam_init(ctx, seq0, user, hep0, B, W, P, ctx->bm[0], sd.user, s))) return rc;
+    IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->bm[0].fin, 0, sizeof(int32_t) * B * W, s));
+    IRS_CHECK_HIP(ctx, hipMemsetAsync(sd.done, 0, sizeof(int32_t) * B, s));
     int live = B, cur = 0, aux = 0;
     int64_t steps = 0, window_steps = 0;
-    float *const lmax = W > 1 ? ctx->lse_max : nullptr, *const lsum = W > 1 ? ctx->lse_sum : nullptr;
     for (int i = 0; i < P; ++i) {
-        const int out = cur ^ 1, rows = live * W;
-        if ((rc = irs_launch_decode(ctx, ctx->bm_seq[cur], usr[aux], rows, nullptr, ctx->bm_hep[cur], ctx->xrows, nullptr, s))) return rc;
-        if ((rc = irs_launch_topk(ctx, ctx->xrows, rows, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, lmax, lsum)))
-            return rc;
-        if ((rc = irs_launch_beam_step_until(ctx, ctx->bm_seq[cur], ctx->bm_hep[cur], ctx->bm_cum[cur], ctx->bm_paths[cur],
-                                             ctx->bm_fin[cur], ctx->top_val, ctx->top_ids, lmax, lsum, live, W, k, 0, ctx->step_ctr, P,
-                                             stop_rule, ctx->bm_seq[out], ctx->bm_hep[out], ctx->bm_cum[out], ctx->bm_paths[out],
-                                             ctx->bm_fin[out], ctx->bm_done[aux], cmap, status, s)))
-            return rc;
-        if ((rc = irs_launch_inc(ctx, ctx->step_ctr, s))) return rc;
-        cur = out, ++steps, window_steps += rows;
+        const irs_beam_until until{sd.done, sd.map, stop_rule};
+        if ((rc = enqueue_beam_step(ctx, cur, sd.user, live, W, k, sweep, P, status, &until, s))) return rc;
+        cur ^= 1, ++steps, window_steps += live * W;
         if ((i + 1) % check_every || i + 1 == P) continue; // no check due, or the last step: whoever is left leaves below
-        if ((rc = irs_launch_until_scan(ctx, ctx->bm_done[aux], live, ctx->un_dst, ctx->un_count, s))) return rc;
-        IRS_CHECK_HIP(ctx, hipMemcpyAsync(&ctx->un_count_host, ctx->un_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        IRS_CHECK_HIP(ctx, hipStreamSynchronize(s));
-        const int left = ctx->un_count_host;
-        if (left < 0 || left > live) IRS_FAIL(ctx, IRS_E_STATE, "irs_beam_search_until: live count %d of %d users", left, live);
+        int left;
+        if ((rc = live_count(ctx, "irs_beam_search_until", "users", sd.done, live, &left, s))) return rc;
         if (left == live) continue;
-        const int to = cur ^ 1; // the set the step has just read: free
-        if ((rc = irs_launch_beam_retire(ctx, ctx->un_dst, live, W, P, ctx->bm_seq[cur], usr[aux], ctx->bm_hep[cur], ctx->bm_cum[cur],
-                                         ctx->bm_paths[cur], ctx->bm_fin[cur], cmap, ctx->bm_seq[to], usr[aux ^ 1], ctx->bm_hep[to],
-                                         ctx->bm_cum[to], ctx->bm_paths[to], ctx->bm_fin[to], ctx->un_map[aux ^ 1],
-                                         ctx->bm_done[aux ^ 1], paths, scores, fin, seq_final, s)))
-            return rc;
-        cur = to, aux ^= 1, cmap = ctx->un_map[aux], live = left;
+        aux ^= 1; // the survivors move to the side the step has just read (free), and to the other side of user / done / map
+        const irs_beam_side to{ctx->bm_side[aux].user, ctx->bm_side[aux].done, ctx->un_map[aux]};
+        if ((rc = irs_launch_beam_retire(ctx, ctx->un_dst, live, W, P, ctx->bm[cur], sd, ctx->bm[cur ^ 1], to, res, s))) return rc;
+        cur ^= 1, sd = to, live = left;
         if (live == 0) break;
     }
-    if (live > 0 &&
-        (rc = irs_launch_beam_retire(ctx, nullptr, live, W, P, ctx->bm_seq[cur], usr[aux], ctx->bm_hep[cur], ctx->bm_cum[cur],
-                                     ctx->bm_paths[cur], ctx->bm_fin[cur], cmap, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                     nullptr, nullptr, paths, scores, fin, seq_final, s)))
-        return rc;
+    if (live > 0 && (rc = irs_launch_beam_retire(ctx, nullptr, live, W, P, ctx->bm[cur], sd, {}, {}, res, s))) return rc;
     if (host_stats) host_stats[0] = steps, host_stats[1] = window_steps;
     return IRS_OK;
 }

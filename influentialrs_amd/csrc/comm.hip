@@ -313,10 +313,7 @@ __global__ void k_short_list(const int64_t *__restrict__ ids0, int k, int n, int
 static int ready_sharded(irs_ctx *ctx, irs_comm *comm, const char *fn, int sweep) {
     int rc = comm_check(ctx, comm, fn);
     if (rc) return rc;
-    if (!ctx->finalized) IRS_FAIL(ctx, IRS_E_STATE, "weights not finalized (irs_finalize_weights)");
-    if (!ctx->ws) IRS_FAIL(ctx, IRS_E_STATE, "workspace not bound (irs_bind_workspace)");
-    if (ctx->proj_stale && sweep == IRS_SWEEP_BF16)
-        IRS_FAIL(ctx, IRS_E_STATE, "project.* may have changed since irs_finalize_weights: call it before filtering through the bf16 catalog");
+    if ((rc = irs_ready_filter(ctx, sweep))) return rc;
     if (sweep != IRS_SWEEP_BF16 && sweep != IRS_SWEEP_F32) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad sweep", fn);
     return IRS_OK;
 }
@@ -355,6 +352,7 @@ extern "C" int irs_generate_paths_sharded(irs_ctx *ctx, irs_comm *comm, int64_t 
     if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
     int step_no = 0; // (stream launches: steps behind the first may reuse the previous step's emission thresholds; a captured step never does)
     const bool graph_path = irs_may_capture(ctx, use_graph) && comm->rccl && !ctx->sh_nograph;
+    const irs_path_args pa{seq, hep, ctx->dims.max_len, paths, max_path_len, sample, sample_k, seed, status, ctx->step_ctr, 0, nullptr, 1};
     auto body = [&](hipStream_t q) -> int {
         int r;
         const int carry = (!graph_path && step_no++ > 0) ? 1 : 0;
@@ -366,9 +364,7 @@ extern "C" int irs_generate_paths_sharded(irs_ctx *ctx, irs_comm *comm, int64_t 
         if ((r = comm_alltoall(ctx, comm, ctx->keys_send, ctx->keys_recv, (size_t)B * k * sizeof(uint64_t), q))) return r;
         if ((r = irs_launch_merge_keys(ctx, ctx->keys_recv, world, B, k, ctx->top_val, ctx->top_ids, q))) return r;
         hipLaunchKernelGGL(k_short_list, dim3((B + 255) / 256), dim3(256), 0, q, ctx->top_ids, k, B, status);
-        if ((r = irs_launch_path_step(ctx, seq, hep, B, ctx->top_val, ctx->top_ids, k, 0, ctx->step_ctr, paths, max_path_len, sample,
-                                      sample_k, seed, status, q)))
-            return r;
+        if ((r = irs_launch_path_step(ctx, pa, B, ctx->top_val, ctx->top_ids, k, q))) return r;
         return irs_launch_inc(ctx, ctx->step_ctr, q);
     };
     // ---- opt-in (irs_set_sharded_overlap): the step's users as TWO micro-batches, the collectives on a side stream chained by
@@ -412,9 +408,9 @@ extern "C" int irs_generate_paths_sharded(irs_ctx *ctx, irs_comm *comm, int64_t 
             IRS_CHECK_HIP(ctx, hipStreamWaitEvent(q, ctx->sh_ev[6 + h], 0));
             if ((r = irs_launch_merge_keys(ctx, kr[h], world, Bh[h], k, ctx->top_val, ctx->top_ids, q))) return r;
             hipLaunchKernelGGL(k_short_list, dim3((Bh[h] + 255) / 256), dim3(256), 0, q, ctx->top_ids, k, Bh[h], status + o0[h]);
-            if ((r = irs_launch_path_step(ctx, seq + (size_t)o0[h] * L, hep + o0[h], Bh[h], ctx->top_val, ctx->top_ids, k, 0, ctx->step_ctr,
-                                          paths + (size_t)o0[h] * max_path_len, max_path_len, sample, sample_k, seed, status + o0[h], q)))
-                return r;
+            irs_path_args ph = pa; // this half's rows
+            ph.seq += (size_t)o0[h] * L, ph.hep += o0[h], ph.paths += (size_t)o0[h] * max_path_len, ph.status += o0[h];
+            if ((r = irs_launch_path_step(ctx, ph, Bh[h], ctx->top_val, ctx->top_ids, k, q))) return r;
         }
         return irs_launch_inc(ctx, ctx->step_ctr, q);
     };
@@ -438,7 +434,7 @@ extern "C" int irs_beam_search_sharded(irs_ctx *ctx, irs_comm *comm, const int64
     int rc = ready_sharded(ctx, comm, "irs_beam_search_sharded", sweep);
     if (rc) return rc;
     const int world = comm->world, R = B * W;
-    if ((rc = irs_check_beam_args(ctx, "irs_beam_search_sharded", seq0, hep0, paths, scores, status, B, W, P))) return rc;
+    if ((rc = irs_check_beam_args(ctx, "irs_beam_search_sharded", seq0 && hep0 && paths && scores && status, B, W, P))) return rc;
     if (ctx->dims.mask_mode == IRS_MASK_IRN && !user) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_sharded: user is null");
     if ((rc = irs_check_k(ctx, "irs_beam_search_sharded", k, world, sweep, 0, 0))) return rc;
     const int rows_all = split_decode ? R : R * world; // rows every rank sweeps
@@ -452,23 +448,21 @@ extern "C" int irs_beam_search_sharded(irs_ctx *ctx, irs_comm *comm, const int64
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_search_sharded: split_decode gathers %d rows, max_rows is %d", per_split * world, ctx->max_rows);
     hipStream_t s = (hipStream_t)stream;
     if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
-    if ((rc = irs_launch_beam_init(ctx, seq0, user, hep0, B, W, P, ctx->bm_seq[0], ctx->bm_user, ctx->bm_hep[0], ctx->bm_cum[0],
-                                   ctx->bm_paths[0], s)))
-        return rc;
+    int64_t *const usr = ctx->bm_side[0].user;
+    if ((rc = irs_launch_beam_init(ctx, seq0, user, hep0, B, W, P, ctx->bm[0], usr, s))) return rc;
     const int d = ctx->dims.d, L = ctx->dims.max_len;
     auto step = [&](int in, hipStream_t q) -> int {
-        const int out = in ^ 1;
         int r;
         const float *lmax = nullptr, *lsum = nullptr;
         if (split_decode) {
             const int per = per_split, r0 = comm->rank * per; // this rank's slice of the (replicated) beam windows
             const int mine = R - r0 < per ? (R - r0 > 0 ? R - r0 : 0) : per;
-            if (mine > 0 && (r = irs_launch_decode(ctx, ctx->bm_seq[in] + (size_t)r0 * L, ctx->bm_user + r0, mine, nullptr, ctx->bm_hep[in] + r0,
+            if (mine > 0 && (r = irs_launch_decode(ctx, ctx->bm[in].seq + (size_t)r0 * L, usr + r0, mine, nullptr, ctx->bm[in].hep + r0,
                                                    ctx->x_local, nullptr, q)))
                 return r;
             if ((r = comm_allgather(ctx, comm, ctx->x_local, ctx->xrows, (size_t)per * d * sizeof(float), q))) return r;
         } else {
-            if ((r = irs_launch_decode(ctx, ctx->bm_seq[in], ctx->bm_user, R, nullptr, ctx->bm_hep[in], ctx->x_local, nullptr, q))) return r;
+            if ((r = irs_launch_decode(ctx, ctx->bm[in].seq, usr, R, nullptr, ctx->bm[in].hep, ctx->x_local, nullptr, q))) return r;
             if ((r = comm_allgather(ctx, comm, ctx->x_local, ctx->xrows, (size_t)R * d * sizeof(float), q))) return r;
         }
         if ((r = irs_launch_topk(ctx, ctx->xrows, rows_all, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, q, nullptr,
@@ -489,11 +483,7 @@ extern "C" int irs_beam_search_sharded(irs_ctx *ctx, irs_comm *comm, const int64
             lmax = ctx->lse_gmax + own0;
             lsum = ctx->lse_sum + own0;
         }
-        if ((r = irs_launch_beam_step(ctx, ctx->bm_seq[in], ctx->bm_hep[in], ctx->bm_cum[in], ctx->bm_paths[in], ctx->top_val,
-                                      ctx->top_ids, lmax, lsum, B, W, k, 0, ctx->step_ctr, P, ctx->bm_seq[out], ctx->bm_hep[out],
-                                      ctx->bm_cum[out], ctx->bm_paths[out], status, q)))
-            return r;
-        return irs_launch_inc(ctx, ctx->step_ctr, q);
+        return irs_enqueue_beam_tail(ctx, in, lmax, lsum, B, W, k, P, status, nullptr, q);
     };
     int done = 0;
     if (irs_may_capture(ctx, use_graph) && comm->rccl && P >= 2) { // (with sh_nograph set: the same pairs on the stream)

@@ -79,6 +79,48 @@ struct irs_step_graph {
     irs_step_key key;
 };
 
+// ---- beam-search state.  A step reads one side of the ping-pong state and writes the other; the kernels take these by value.
+struct irs_beam_state {
+    int64_t *seq; // [max_seqs][L]
+    int32_t *hep; // [max_seqs]
+    double *cum;  // [max_seqs]
+    float *paths; // [max_seqs][P <= IRS_MAX_PATH]
+    int32_t *fin; // [max_seqs] the beam has chosen its target (the until forms only)
+};
+// what moves at the compactions of irs_beam_search_until only; the plain and the sharded search use side 0's `user`
+struct irs_beam_side {
+    int64_t *user;      // [max_seqs]
+    int32_t *done;      // [max_seqs] (by user) nothing is left to decide
+    int32_t *map;  // compacted user -> the caller's row; null = identity (the loop sets it: un_map[side] after a compaction)
+};
+struct irs_beam_cand { // the candidate lists of a step's rows; lse_* null: W == 1
+    const float *val;
+    const int64_t *ids0;
+    const float *lse_max, *lse_sum;
+    int k;
+};
+struct irs_beam_until { // what a step of the until forms takes besides (map as in irs_beam_side)
+    int32_t *done;
+    const int32_t *map;
+    int stop_rule;
+};
+struct irs_beam_out { // the caller's outputs of irs_beam_search_until; fin and seq may be null
+    float *paths;
+    double *scores;
+    int32_t *fin;
+    int64_t *seq;
+};
+struct irs_eval_batch_args { // irs_build_eval_batch's arguments as the kernel takes them
+    const int64_t *items, *offsets;
+    int B, L, raw_len, gap_len;
+    int64_t n_item;
+    const int64_t *targets_in, *pool;
+    int64_t n_pool;
+    unsigned long long seed;
+    int64_t *seq, *target, *label, *raw;
+    int32_t *raw_n, *status;
+};
+
 struct irs_ctx {
     irs_dims dims;
     irs_shard shard;
@@ -152,17 +194,10 @@ struct irs_ctx {
     int32_t *step_pair; // set around a decode launched by the merged small-batch path loop: the plan kernel copies
                         // step_pair[1] over step_pair[0]
     int32_t *pos_tmp;   // [max_seqs]
-    // beam-search state, ping-pong [2]
-    int64_t *bm_seq[2];  // [max_seqs][L]
-    int32_t *bm_hep[2];  // [max_seqs]
-    double *bm_cum[2];   // [max_seqs]
-    float *bm_paths[2];  // [max_seqs][IRS_MAX_PATH]
-    int64_t *bm_user;    // [max_seqs]
-    // irs_beam_search_until: the flags of the beam state, and the second side of what a compaction moves besides the ping-pong
-    // sets above (the map is un_map[2], the scan's places and count un_dst / un_count / un_count_host below)
-    int64_t *bm_user2;   // [max_seqs]
-    int32_t *bm_fin[2];  // [max_seqs] the beam has chosen its target
-    int32_t *bm_done[2]; // [max_seqs] (by user) nothing is left to decide
+    // beam-search state: the two sides of the ping-pong, and of what irs_beam_search_until moves at a compaction (its map is
+    // un_map[2], the scan's places and count un_dst / un_count / un_count_host below)
+    irs_beam_state bm[2];
+    irs_beam_side bm_side[2];
     float *lse_max, *lse_sum; // [max_rows]
     // stop-at-target search (irs_generate_paths_until): the live users' compacted state, ping-pong [2]
     int64_t *un_seq[2];  // [max_seqs][L]
@@ -228,8 +263,11 @@ void irs_drop_graphs(irs_ctx *ctx);
 // event records are not captured: with a profiling family enabled every loop runs on the stream and records its brackets
 static inline bool irs_may_capture(const irs_ctx *ctx, int use_graph) { return use_graph && ctx->prof_family == IRS_PROF_NONE; }
 int irs_check_k(irs_ctx *ctx, const char *fn, int k, int world, int sweep, int sample, int sample_k);
-int irs_check_beam_args(irs_ctx *ctx, const char *fn, const void *seq0, const void *hep0, const void *paths, const void *scores,
-                        const void *status, int B, int W, int P);
+int irs_check_beam_args(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W, int P); // ptrs_ok: no required pointer is null
+int irs_ready_filter(irs_ctx *ctx, int sweep); // finalized, workspace bound, and no stale bf16 catalog under a filtering sweep
+// beam step from ctx->bm[in] to ctx->bm[in ^ 1] on the lists in top_val / top_ids, then the step counter (until == nullptr: plain)
+int irs_enqueue_beam_tail(irs_ctx *ctx, int in, const float *lse_max, const float *lse_sum, int B, int W, int k, int P, int32_t *status,
+                          const irs_beam_until *until, hipStream_t s);
 int irs_search_begin(irs_ctx *ctx, int32_t *status, int B, hipStream_t s); // step counter and status to zero
 int irs_beam_finish(irs_ctx *ctx, size_t rows, int P, float *paths, double *scores, int64_t *seq_final, hipStream_t s);
 
@@ -288,9 +326,7 @@ int irs_launch_merge(irs_ctx *ctx, const float *val_in, const int64_t *ids_in, i
                      int64_t *ids0, hipStream_t s);
 int irs_launch_merge_keys(irs_ctx *ctx, const uint64_t *keys_in, int W, int M, int k, float *val, int64_t *ids0, hipStream_t s);
 int irs_launch_pack_topk(irs_ctx *ctx, const float *val, const int64_t *ids0, int64_t n, uint64_t *keys, hipStream_t s);
-int irs_launch_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int B, const float *val, const int64_t *ids0, int k,
-                         int step, const int32_t *step_ptr, float *paths, int path_ld, int sample, int sample_k,
-                         uint64_t seed, int32_t *status, hipStream_t s, int32_t *step_next = nullptr);
+int irs_launch_path_step(irs_ctx *ctx, const irs_path_args &pa, int B, const float *val, const int64_t *ids0, int k, hipStream_t s);
 int irs_launch_inc(irs_ctx *ctx, int32_t *ctr, hipStream_t s);
 // the stop-at-target loop's own kernels (irs_generate_paths_until, capi.hip); map == nullptr is the identity
 int irs_launch_until_record(irs_ctx *ctx, const float *stage, int P, int step, const int32_t *map, const int64_t *seq, int B,
@@ -300,32 +336,17 @@ int irs_launch_until_gather(irs_ctx *ctx, const int32_t *dst, int B, const int64
                             const int32_t *map, int64_t *seq_out, int64_t *user_out, int32_t *hep_out, int32_t *map_out,
                             hipStream_t s);
 int irs_launch_set_step(irs_ctx *ctx, int32_t *step_pair, int step, hipStream_t s);
-int irs_launch_beam_init(irs_ctx *ctx, const int64_t *seq0, const int64_t *user0, const int32_t *hep0, int B, int W,
-                         int P, int64_t *seq, int64_t *user, int32_t *hep, double *cum, float *paths, hipStream_t s);
-int irs_launch_beam_step(irs_ctx *ctx, const int64_t *seq_in, const int32_t *hep_in, const double *cum_in,
-                         const float *paths_in, const float *val, const int64_t *ids0, const float *lse_max,
-                         const float *lse_sum, int B, int W, int k, int step, const int32_t *step_ptr, int P,
-                         int64_t *seq_out, int32_t *hep_out, double *cum_out, float *paths_out, int32_t *status,
-                         hipStream_t s);
+int irs_launch_beam_init(irs_ctx *ctx, const int64_t *seq0, const int64_t *user0, const int32_t *hep0, int B, int W, int P,
+                         const irs_beam_state &st, int64_t *user, hipStream_t s);
+// until == nullptr: the plain step (fin is not touched); else the step of irs_beam_step_until / irs_beam_search_until
+int irs_launch_beam_step(irs_ctx *ctx, const irs_beam_state &in, const irs_beam_state &out, const irs_beam_cand &cand, int B, int W,
+                         int step, const int32_t *step_ptr, int P, int32_t *status, const irs_beam_until *until, hipStream_t s);
+// dst == nullptr sends every user to the caller's outputs (out / side_out are then not touched)
+int irs_launch_beam_retire(irs_ctx *ctx, const int32_t *dst, int B, int W, int P, const irs_beam_state &in,
+                           const irs_beam_side &side_in, const irs_beam_state &out, const irs_beam_side &side_out,
+                           const irs_beam_out &res, hipStream_t s);
 
-// irs_beam_step_until / irs_beam_search_until (map: compacted user -> the caller's status row, nullptr = identity; retire: dst ==
-// nullptr sends every user to the caller's outputs)
-int irs_launch_beam_step_until(irs_ctx *ctx, const int64_t *seq_in, const int32_t *hep_in, const double *cum_in,
-                               const float *paths_in, const int32_t *fin_in, const float *val, const int64_t *ids0,
-                               const float *lse_max, const float *lse_sum, int B, int W, int k, int step,
-                               const int32_t *step_ptr, int P, int stop_rule, int64_t *seq_out, int32_t *hep_out,
-                               double *cum_out, float *paths_out, int32_t *fin_out, int32_t *done, const int32_t *map,
-                               int32_t *status, hipStream_t s);
-int irs_launch_beam_retire(irs_ctx *ctx, const int32_t *dst, int B, int W, int P, const int64_t *seq, const int64_t *user,
-                           const int32_t *hep, const double *cum, const float *paths, const int32_t *fin, const int32_t *map,
-                           int64_t *seq_o, int64_t *user_o, int32_t *hep_o, double *cum_o, float *paths_o, int32_t *fin_o,
-                           int32_t *map_o, int32_t *done_o, float *out_paths, double *out_scores, int32_t *out_fin,
-                           int64_t *out_seq, hipStream_t s);
-
-int irs_launch_build_eval_batch(irs_ctx *ctx, const int64_t *items, const int64_t *offsets, int B, int raw_len, int gap_len,
-                                const int64_t *targets_in, const int64_t *pool, int64_t n_pool, uint64_t seed, int64_t *seq,
-                                int64_t *target, int64_t *label, int64_t *raw, int32_t *raw_n, int32_t *status,
-                                hipStream_t s);
+int irs_launch_build_eval_batch(irs_ctx *ctx, const irs_eval_batch_args &a, hipStream_t s);
 
 // ---- small device helpers ----
 #ifdef __HIPCC__

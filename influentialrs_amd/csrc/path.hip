@@ -8,16 +8,11 @@
 #include "irs_internal.h"
 
 // One wave per row (the row body lives in irs_internal.h: the one-launch small-shard top-k runs it in its tail).
-__global__ void __launch_bounds__(256) k_path_step(int64_t *__restrict__ seq, int32_t *__restrict__ hep, int B, int L,
-                                                   const float *__restrict__ val, const int64_t *__restrict__ ids0,
-                                                   int k, int step_arg, const int32_t *__restrict__ step_ptr,
-                                                   float *__restrict__ paths, int path_ld, int sample, int sample_k,
-                                                   unsigned long long seed, int32_t *__restrict__ status,
-                                                   int32_t *__restrict__ step_next) {
+__global__ void __launch_bounds__(256) k_path_step(const irs_path_args pa, int B, const float *__restrict__ val,
+                                                   const int64_t *__restrict__ ids0, int k) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= B) return;
-    const irs_path_args pa{seq, hep, L, paths, path_ld, sample, sample_k, seed, status, step_ptr, step_arg, step_next, 1};
     irs_path_step_row(pa, row, lane, val, ids0, k);
 }
 
@@ -114,16 +109,9 @@ __global__ void __launch_bounds__(256) k_merge(const float *__restrict__ val_in,
 // The instantiation without UNTIL is the kernel as it was: every addition sits behind `if constexpr`.
 #define BEAM_MAXW 32
 template <bool UNTIL>
-__global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ seq_in, const int32_t *__restrict__ hep_in,
-                                                    const double *__restrict__ cum_in, const float *__restrict__ paths_in,
-                                                    const float *__restrict__ val, const int64_t *__restrict__ ids0,
-                                                    const float *__restrict__ lse_max, const float *__restrict__ lse_sum,
-                                                    int W, int L, int k, int step_arg, const int32_t *__restrict__ step_ptr,
-                                                    int P, int64_t *__restrict__ seq_out, int32_t *__restrict__ hep_out,
-                                                    double *__restrict__ cum_out, float *__restrict__ paths_out,
-                                                    int32_t *__restrict__ status, const int32_t *__restrict__ fin_in,
-                                                    int32_t *__restrict__ fin_out, int32_t *__restrict__ done, int stop_rule,
-                                                    const int32_t *__restrict__ map) {
+__global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, const irs_beam_state out, const irs_beam_cand cand,
+                                                    int W, int L, int step_arg, const int32_t *__restrict__ step_ptr, int P,
+                                                    int32_t *__restrict__ status, const irs_beam_until until) {
     __shared__ double c_score[BEAM_MAXW * BEAM_MAXW];
     __shared__ int64_t c_item[BEAM_MAXW * BEAM_MAXW];
     __shared__ int c_order[BEAM_MAXW];
@@ -131,17 +119,17 @@ __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, nthr = blockDim.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nwave = nthr >> 6;
     const int step = step_ptr ? step_ptr[0] : step_arg;
-    const int WW = W * W;
+    const int WW = W * W, k = cand.k;
     if constexpr (UNTIL) {
-        if (done[b]) { // (the same for the whole workgroup) a user that is done: every beam goes from in to out as it is
+        if (until.done[b]) { // (the same for the whole workgroup) a user that is done: every beam goes from in to out as it is
             for (int j = wave; j < W; j += nwave) {
                 const size_t row = (size_t)b * W + j;
-                for (int p = lane; p < L; p += 64) seq_out[row * L + p] = seq_in[row * L + p];
-                for (int p = lane; p < P; p += 64) paths_out[row * P + p] = paths_in[row * P + p];
+                for (int p = lane; p < L; p += 64) out.seq[row * L + p] = in.seq[row * L + p];
+                for (int p = lane; p < P; p += 64) out.paths[row * P + p] = in.paths[row * P + p];
                 if (lane == 0) {
-                    hep_out[row] = hep_in[row];
-                    cum_out[row] = cum_in[row];
-                    fin_out[row] = fin_in[row];
+                    out.hep[row] = in.hep[row];
+                    out.cum[row] = in.cum[row];
+                    out.fin[row] = in.fin[row];
                 }
             }
             return;
@@ -157,17 +145,17 @@ __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ 
     // phase 1: survivors of every live beam (one wave per beam)
     for (int j = wave; j < W; j += nwave) {
         const int row = b * W + j;
-        const double cj = cum_in[row];
+        const double cj = in.cum[row];
         int found = 0;
         if constexpr (UNTIL) {
-            if (fin_in[row]) { // a finished beam: itself, with its final score; its lists are not read
+            if (in.fin[row]) { // a finished beam: itself, with its final score; its lists are not read
                 if (lane == 0 && cj > -INFINITY) c_score[j * W] = cj;
                 continue;
             }
         }
         if (cj > -INFINITY) {
-            const int64_t *w = seq_in + (size_t)row * L;
-            const int wl = hep_in[row] + 1;
+            const int64_t *w = in.seq + (size_t)row * L;
+            const int wl = in.hep[row] + 1;
             int64_t wv[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -175,12 +163,12 @@ __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ 
                 wv[i] = (p < wl && p < L) ? w[p] : (int64_t)-1;
             }
             double norm = 0.0;
-            if (lse_max) norm = (double)lse_max[row] + log((double)lse_sum[row]);
+            if (cand.lse_max) norm = (double)cand.lse_max[row] + log((double)cand.lse_sum[row]);
             bool more = true;
             for (int c0 = 0; c0 < k && found < W && more; c0 += 64) { // 64 candidates per round, one per lane
                 const int cl = c0 + lane;
-                const int64_t cid = cl < k ? ids0[(size_t)row * k + cl] : (int64_t)-1;
-                const float cv = cl < k ? val[(size_t)row * k + cl] : 0.f;
+                const int64_t cid = cl < k ? cand.ids0[(size_t)row * k + cl] : (int64_t)-1;
+                const float cv = cl < k ? cand.val[(size_t)row * k + cl] : 0.f;
                 for (int c = 0; c < 64 && c0 + c < k && found < W; ++c) {
                     const int64_t id0 = __shfl(cid, c, 64);
                     if (id0 < 0) { // end of the list (fewer than k items on this shard / excluded)
@@ -201,7 +189,7 @@ __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ 
                     }
                 }
             }
-            if (found == 0 && lane == 0) atomicOr(&status[(UNTIL && map) ? map[b] : b], IRS_ROW_NO_CANDIDATE);
+            if (found == 0 && lane == 0) atomicOr(&status[(UNTIL && until.map) ? until.map[b] : b], IRS_ROW_NO_CANDIDATE);
         }
     }
     __syncthreads();
@@ -223,33 +211,33 @@ __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ 
         const int ci = c_order[t];
         const double sc = ci < WW ? c_score[ci] : -INFINITY;
         const int orow = b * W + t;
-        int64_t *wo = seq_out + (size_t)orow * L;
-        float *po = paths_out + (size_t)orow * P;
+        int64_t *wo = out.seq + (size_t)orow * L;
+        float *po = out.paths + (size_t)orow * P;
         if (!(sc > -INFINITY)) { // dead beam: keep a well-formed (copied) window, never selected again
-            const int64_t *wi = seq_in + (size_t)(b * W) * L;
+            const int64_t *wi = in.seq + (size_t)(b * W) * L;
             for (int p = lane; p < L; p += 64) wo[p] = wi[p];
             for (int p = lane; p < P; p += 64) po[p] = 0.f;
             if (lane == 0) {
-                cum_out[orow] = -INFINITY;
-                hep_out[orow] = hep_in[b * W];
-                if constexpr (UNTIL) fin_out[orow] = 0;
+                out.cum[orow] = -INFINITY;
+                out.hep[orow] = in.hep[b * W];
+                if constexpr (UNTIL) out.fin[orow] = 0;
             }
             continue;
         }
         const int parent = ci / W;
         const int prow = b * W + parent;
         const int64_t item = c_item[ci];
-        const int64_t *wi = seq_in + (size_t)prow * L;
-        const float *pi = paths_in + (size_t)prow * P;
-        const int he = hep_in[prow];
+        const int64_t *wi = in.seq + (size_t)prow * L;
+        const float *pi = in.paths + (size_t)prow * P;
+        const int he = in.hep[prow];
         if constexpr (UNTIL) {
-            if (fin_in[prow]) { // a finished beam that survived: copied whole
+            if (in.fin[prow]) { // a finished beam that survived: copied whole
                 for (int p = lane; p < L; p += 64) wo[p] = wi[p];
                 for (int p = lane; p < P; p += 64) po[p] = pi[p];
                 if (lane == 0) {
-                    hep_out[orow] = he;
-                    cum_out[orow] = sc;
-                    fin_out[orow] = 1;
+                    out.hep[orow] = he;
+                    out.cum[orow] = sc;
+                    out.fin[orow] = 1;
                     if (t == 0) s_flags[1] = 1;
                 }
                 continue;
@@ -257,17 +245,17 @@ __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ 
         }
         if (he < L - 2) { // grow
             for (int p = lane; p < L; p += 64) wo[p] = (p == he + 1) ? item : wi[p];
-            if (lane == 0) hep_out[orow] = he + 1;
+            if (lane == 0) out.hep[orow] = he + 1;
         } else { // shift, target stays last
             for (int p = lane; p < L; p += 64) wo[p] = (p < L - 2) ? wi[p + 1] : (p == L - 2 ? item : wi[L - 1]);
-            if (lane == 0) hep_out[orow] = he;
+            if (lane == 0) out.hep[orow] = he;
         }
         for (int p = lane; p < P; p += 64) po[p] = (p < step) ? pi[p] : (p == step ? (float)item : 0.f);
-        if (lane == 0) cum_out[orow] = sc;
+        if (lane == 0) out.cum[orow] = sc;
         if constexpr (UNTIL) {
             const int f = item == wi[L - 1] ? 1 : 0; // the end symbol: the parent window's target
             if (lane == 0) {
-                fin_out[orow] = f;
+                out.fin[orow] = f;
                 if (!f) atomicOr(&s_flags[0], 1);
                 if (f && t == 0) s_flags[1] = 1;
             }
@@ -275,62 +263,39 @@ __global__ void __launch_bounds__(1024) k_beam_step(const int64_t *__restrict__ 
     }
     if constexpr (UNTIL) {
         __syncthreads();
-        if (tid == 0) done[b] = (!s_flags[0] || (stop_rule == IRS_BEAM_STOP_BEST && s_flags[1])) ? 1 : 0;
+        if (tid == 0) until.done[b] = (!s_flags[0] || (until.stop_rule == IRS_BEAM_STOP_BEST && s_flags[1])) ? 1 : 0;
     }
 }
 
 // beam state initialisation: beam 0 = the input window with score 0, others dead copies
 __global__ void k_beam_init(const int64_t *__restrict__ seq0, const int64_t *__restrict__ user0,
-                            const int32_t *__restrict__ hep0, int B, int W, int L, int P, int64_t *__restrict__ seq,
-                            int64_t *__restrict__ user, int32_t *__restrict__ hep, double *__restrict__ cum,
-                            float *__restrict__ paths) {
+                            const int32_t *__restrict__ hep0, int B, int W, int L, int P, const irs_beam_state st,
+                            int64_t *__restrict__ user) {
     const int row = blockIdx.x; // b * W + j
     const int b = row / W, j = row % W;
-    for (int p = threadIdx.x; p < L; p += blockDim.x) seq[(size_t)row * L + p] = seq0[(size_t)b * L + p];
-    for (int p = threadIdx.x; p < P; p += blockDim.x) paths[(size_t)row * P + p] = 0.f;
+    for (int p = threadIdx.x; p < L; p += blockDim.x) st.seq[(size_t)row * L + p] = seq0[(size_t)b * L + p];
+    for (int p = threadIdx.x; p < P; p += blockDim.x) st.paths[(size_t)row * P + p] = 0.f;
     if (threadIdx.x == 0) {
         user[row] = user0 ? user0[b] : 0;
-        hep[row] = hep0[b];
-        cum[row] = (j == 0) ? 0.0 : -INFINITY;
+        st.hep[row] = hep0[b];
+        st.cum[row] = (j == 0) ? 0.0 : -INFINITY;
     }
 }
 
-int irs_launch_beam_init(irs_ctx *ctx, const int64_t *seq0, const int64_t *user0, const int32_t *hep0, int B, int W,
-                         int P, int64_t *seq, int64_t *user, int32_t *hep, double *cum, float *paths, hipStream_t s) {
-    hipLaunchKernelGGL(k_beam_init, dim3(B * W), dim3(64), 0, s, seq0, user0, hep0, B, W, ctx->dims.max_len, P, seq,
-                       user, hep, cum, paths);
+int irs_launch_beam_init(irs_ctx *ctx, const int64_t *seq0, const int64_t *user0, const int32_t *hep0, int B, int W, int P,
+                         const irs_beam_state &st, int64_t *user, hipStream_t s) {
+    hipLaunchKernelGGL(k_beam_init, dim3(B * W), dim3(64), 0, s, seq0, user0, hep0, B, W, ctx->dims.max_len, P, st, user);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }
 
-int irs_launch_beam_step(irs_ctx *ctx, const int64_t *seq_in, const int32_t *hep_in, const double *cum_in,
-                         const float *paths_in, const float *val, const int64_t *ids0, const float *lse_max,
-                         const float *lse_sum, int B, int W, int k, int step, const int32_t *step_ptr, int P,
-                         int64_t *seq_out, int32_t *hep_out, double *cum_out, float *paths_out, int32_t *status,
-                         hipStream_t s) {
+int irs_launch_beam_step(irs_ctx *ctx, const irs_beam_state &in, const irs_beam_state &out, const irs_beam_cand &cand, int B, int W,
+                         int step, const int32_t *step_ptr, int P, int32_t *status, const irs_beam_until *until, hipStream_t s) {
     if (W < 1 || W > BEAM_MAXW) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam width %d outside [1, %d]", W, BEAM_MAXW);
     if (ctx->dims.max_len > 256) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam step: window length %d > 256", ctx->dims.max_len);
     const int waves = W < 4 ? 4 : (W > 16 ? 16 : W);
-    hipLaunchKernelGGL(k_beam_step<false>, dim3(B), dim3(64 * waves), 0, s, seq_in, hep_in, cum_in, paths_in, val, ids0, lse_max,
-                       lse_sum, W, ctx->dims.max_len, k, step, step_ptr, P, seq_out, hep_out, cum_out, paths_out, status,
-                       (const int32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, 0, (const int32_t *)nullptr);
-    IRS_CHECK_HIP(ctx, hipGetLastError());
-    return IRS_OK;
-}
-
-// (map: compacted user -> the caller's row of `status`; nullptr is the identity)
-int irs_launch_beam_step_until(irs_ctx *ctx, const int64_t *seq_in, const int32_t *hep_in, const double *cum_in,
-                               const float *paths_in, const int32_t *fin_in, const float *val, const int64_t *ids0,
-                               const float *lse_max, const float *lse_sum, int B, int W, int k, int step,
-                               const int32_t *step_ptr, int P, int stop_rule, int64_t *seq_out, int32_t *hep_out,
-                               double *cum_out, float *paths_out, int32_t *fin_out, int32_t *done, const int32_t *map,
-                               int32_t *status, hipStream_t s) {
-    if (W < 1 || W > BEAM_MAXW) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam width %d outside [1, %d]", W, BEAM_MAXW);
-    if (ctx->dims.max_len > 256) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam step: window length %d > 256", ctx->dims.max_len);
-    const int waves = W < 4 ? 4 : (W > 16 ? 16 : W);
-    hipLaunchKernelGGL(k_beam_step<true>, dim3(B), dim3(64 * waves), 0, s, seq_in, hep_in, cum_in, paths_in, val, ids0, lse_max,
-                       lse_sum, W, ctx->dims.max_len, k, step, step_ptr, P, seq_out, hep_out, cum_out, paths_out, status, fin_in,
-                       fin_out, done, stop_rule, map);
+    hipLaunchKernelGGL(until ? k_beam_step<true> : k_beam_step<false>, dim3(B), dim3(64 * waves), 0, s, in, out, cand, W,
+                       ctx->dims.max_len, step, step_ptr, P, status, until ? *until : irs_beam_until{});
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }
@@ -340,55 +305,44 @@ int irs_launch_beam_step_until(irs_ctx *ctx, const int64_t *seq_in, const int32_
 // and a cleared done flag.  dst is k_until_scan's over `done` (-1: done); dst == nullptr: every user leaves (the last step).
 // One wave per beam row.
 __global__ void __launch_bounds__(256) k_beam_retire(const int32_t *__restrict__ dst, int B, int W, int L, int P,
-                                                     const int64_t *__restrict__ seq, const int64_t *__restrict__ user,
-                                                     const int32_t *__restrict__ hep, const double *__restrict__ cum,
-                                                     const float *__restrict__ paths, const int32_t *__restrict__ fin,
-                                                     const int32_t *__restrict__ map, int64_t *__restrict__ seq_o,
-                                                     int64_t *__restrict__ user_o, int32_t *__restrict__ hep_o,
-                                                     double *__restrict__ cum_o, float *__restrict__ paths_o,
-                                                     int32_t *__restrict__ fin_o, int32_t *__restrict__ map_o,
-                                                     int32_t *__restrict__ done_o, float *__restrict__ out_paths,
-                                                     double *__restrict__ out_scores, int32_t *__restrict__ out_fin,
-                                                     int64_t *__restrict__ out_seq) {
+                                                     const irs_beam_state in, const irs_beam_side side_in, const irs_beam_state out,
+                                                     const irs_beam_side side_out, const irs_beam_out res) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= B * W) return;
     const int r = row / W, j = row - r * W;
     const int t = dst ? dst[r] : -1;
     if (t < 0) {
-        const size_t orow = (size_t)(map ? map[r] : r) * W + j;
-        for (int p = lane; p < P; p += 64) out_paths[orow * P + p] = paths[(size_t)row * P + p];
-        if (out_seq)
-            for (int p = lane; p < L; p += 64) out_seq[orow * L + p] = seq[(size_t)row * L + p];
+        const size_t orow = (size_t)(side_in.map ? side_in.map[r] : r) * W + j;
+        for (int p = lane; p < P; p += 64) res.paths[orow * P + p] = in.paths[(size_t)row * P + p];
+        if (res.seq)
+            for (int p = lane; p < L; p += 64) res.seq[orow * L + p] = in.seq[(size_t)row * L + p];
         if (lane == 0) {
-            out_scores[orow] = cum[row];
-            if (out_fin) out_fin[orow] = fin[row];
+            res.scores[orow] = in.cum[row];
+            if (res.fin) res.fin[orow] = in.fin[row];
         }
         return;
     }
     const size_t trow = (size_t)t * W + j;
-    for (int p = lane; p < L; p += 64) seq_o[trow * L + p] = seq[(size_t)row * L + p];
-    for (int p = lane; p < P; p += 64) paths_o[trow * P + p] = paths[(size_t)row * P + p];
+    for (int p = lane; p < L; p += 64) out.seq[trow * L + p] = in.seq[(size_t)row * L + p];
+    for (int p = lane; p < P; p += 64) out.paths[trow * P + p] = in.paths[(size_t)row * P + p];
     if (lane == 0) {
-        user_o[trow] = user[row];
-        hep_o[trow] = hep[row];
-        cum_o[trow] = cum[row];
-        fin_o[trow] = fin[row];
+        side_out.user[trow] = side_in.user[row];
+        out.hep[trow] = in.hep[row];
+        out.cum[trow] = in.cum[row];
+        out.fin[trow] = in.fin[row];
         if (j == 0) {
-            map_o[t] = map ? map[r] : r;
-            done_o[t] = 0;
+            side_out.map[t] = side_in.map ? side_in.map[r] : r;
+            side_out.done[t] = 0;
         }
     }
 }
 
-int irs_launch_beam_retire(irs_ctx *ctx, const int32_t *dst, int B, int W, int P, const int64_t *seq, const int64_t *user,
-                           const int32_t *hep, const double *cum, const float *paths, const int32_t *fin, const int32_t *map,
-                           int64_t *seq_o, int64_t *user_o, int32_t *hep_o, double *cum_o, float *paths_o, int32_t *fin_o,
-                           int32_t *map_o, int32_t *done_o, float *out_paths, double *out_scores, int32_t *out_fin,
-                           int64_t *out_seq, hipStream_t s) {
-    hipLaunchKernelGGL(k_beam_retire, dim3((B * W + 3) / 4), dim3(256), 0, s, dst, B, W, ctx->dims.max_len, P, seq, user, hep, cum,
-                       paths, fin, map, seq_o, user_o, hep_o, cum_o, paths_o, fin_o, map_o, done_o, out_paths, out_scores, out_fin,
-                       out_seq);
+int irs_launch_beam_retire(irs_ctx *ctx, const int32_t *dst, int B, int W, int P, const irs_beam_state &in,
+                           const irs_beam_side &side_in, const irs_beam_state &out, const irs_beam_side &side_out,
+                           const irs_beam_out &res, hipStream_t s) {
+    hipLaunchKernelGGL(k_beam_retire, dim3((B * W + 3) / 4), dim3(256), 0, s, dst, B, W, ctx->dims.max_len, P, in, side_in, out,
+                       side_out, res);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }
@@ -416,11 +370,8 @@ int irs_launch_pack_topk(irs_ctx *ctx, const float *val, const int64_t *ids0, in
     return IRS_OK;
 }
 
-int irs_launch_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int B, const float *val, const int64_t *ids0, int k,
-                         int step, const int32_t *step_ptr, float *paths, int path_ld, int sample, int sample_k,
-                         uint64_t seed, int32_t *status, hipStream_t s, int32_t *step_next) {
-    hipLaunchKernelGGL(k_path_step, dim3((B + 3) / 4), dim3(256), 0, s, seq, hep, B, ctx->dims.max_len, val, ids0, k,
-                       step, step_ptr, paths, path_ld, sample, sample_k, (unsigned long long)seed, status, step_next);
+int irs_launch_path_step(irs_ctx *ctx, const irs_path_args &pa, int B, const float *val, const int64_t *ids0, int k, hipStream_t s) {
+    hipLaunchKernelGGL(k_path_step, dim3((B + 3) / 4), dim3(256), 0, s, pa, B, val, ids0, k);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }
@@ -552,31 +503,25 @@ int irs_launch_set_step(irs_ctx *ctx, int32_t *step_pair, int step, hipStream_t 
 // One wave per user.  The target is drawn by rejection from a counter RNG (splitmix64 of (seed, user,
 // attempt)) over [1, n_item] or over an explicit candidate pool (the reference's `popular_item` set):
 // distributional parity with random.sample, exact parity of everything else.
-__global__ void __launch_bounds__(64) k_build_eval_batch(const int64_t *__restrict__ items, const int64_t *__restrict__ offsets,
-                                                         int B, int L, int raw_len, int gap_len, int64_t n_item,
-                                                         const int64_t *__restrict__ targets_in, const int64_t *__restrict__ pool,
-                                                         int64_t n_pool, unsigned long long seed, int64_t *__restrict__ seq,
-                                                         int64_t *__restrict__ target, int64_t *__restrict__ label,
-                                                         int64_t *__restrict__ raw, int32_t *__restrict__ raw_n,
-                                                         int32_t *__restrict__ status) {
+__global__ void __launch_bounds__(64) k_build_eval_batch(const irs_eval_batch_args a) {
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int64_t lo = offsets[b], hi = offsets[b + 1];
+    const int64_t lo = a.offsets[b], hi = a.offsets[b + 1];
     const int64_t n_hist = hi - lo - 1;                       // history = all but the last event
-    const int rn = (int)(n_hist < raw_len ? (n_hist < 0 ? 0 : n_hist) : raw_len);
-    const int64_t *rw = items + lo + (n_hist - rn);           // the raw window, oldest first
+    const int rn = (int)(n_hist < a.raw_len ? (n_hist < 0 ? 0 : n_hist) : a.raw_len);
+    const int64_t *rw = a.items + lo + (n_hist - rn);         // the raw window, oldest first
     int64_t tgt = 0;
-    if (targets_in) {
-        tgt = targets_in[b];
+    if (a.targets_in) {
+        tgt = a.targets_in[b];
     } else {
-        const int64_t space = pool ? n_pool : n_item;
+        const int64_t space = a.pool ? a.n_pool : a.n_item;
         bool found = false;
         for (int attempt = 0; attempt < 256 && !found; ++attempt) {
-            unsigned long long z = seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)b * 2654435761ull + (unsigned long long)attempt + 1ull);
+            unsigned long long z = a.seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)b * 2654435761ull + (unsigned long long)attempt + 1ull);
             z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
             z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
             z = z ^ (z >> 31);
             const unsigned long long pick = __umul64hi(z, (unsigned long long)space); // uniform in [0, space)
-            const int64_t cand = pool ? pool[pick] : (int64_t)pick + 1;
+            const int64_t cand = a.pool ? a.pool[pick] : (int64_t)pick + 1;
             bool hit = false;
             for (int i = lane; i < rn; i += 64) hit |= (rw[i] == cand);
             if (!__any(hit)) {
@@ -584,36 +529,30 @@ __global__ void __launch_bounds__(64) k_build_eval_batch(const int64_t *__restri
                 found = true;
             }
         }
-        if (!found && lane == 0 && status) status[b] |= IRS_ROW_NO_CANDIDATE;
+        if (!found && lane == 0 && a.status) a.status[b] |= IRS_ROW_NO_CANDIDATE;
     }
-    const int l_history = L - gap_len - 1;
+    const int l_history = a.L - a.gap_len - 1;
     const int nh = rn < l_history ? rn : l_history;           // seq[-l_history:] of the raw window
-    const int start = L - nh - gap_len - 1;
-    int64_t *row = seq + (int64_t)b * L;
-    for (int t = lane; t < L; t += 64) {
+    const int start = a.L - nh - a.gap_len - 1;
+    int64_t *row = a.seq + (int64_t)b * a.L;
+    for (int t = lane; t < a.L; t += 64) {
         int64_t v = 0;
         if (t >= start && t < start + nh) v = rw[rn - nh + (t - start)];
-        if (t == L - 1) v = tgt;
+        if (t == a.L - 1) v = tgt;
         row[t] = v;
     }
-    if (raw)
-        for (int i = lane; i < raw_len; i += 64) raw[(int64_t)b * raw_len + i] = (i >= raw_len - rn) ? rw[i - (raw_len - rn)] : 0;
+    if (a.raw)
+        for (int i = lane; i < a.raw_len; i += 64) a.raw[(int64_t)b * a.raw_len + i] = (i >= a.raw_len - rn) ? rw[i - (a.raw_len - rn)] : 0;
     if (lane == 0) {
-        target[b] = tgt;
-        label[b] = (hi > lo) ? items[hi - 1] : 0;
-        if (raw_n) raw_n[b] = rn;
+        a.target[b] = tgt;
+        a.label[b] = (hi > lo) ? a.items[hi - 1] : 0;
+        if (a.raw_n) a.raw_n[b] = rn;
     }
 }
 
-int irs_launch_build_eval_batch(irs_ctx *ctx, const int64_t *items, const int64_t *offsets, int B, int raw_len, int gap_len,
-                                const int64_t *targets_in, const int64_t *pool, int64_t n_pool, uint64_t seed, int64_t *seq,
-                                int64_t *target, int64_t *label, int64_t *raw, int32_t *raw_n, int32_t *status,
-                                hipStream_t s) {
-    const int L = ctx->dims.max_len;
-    if (L - gap_len - 1 < 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "gap_len %d leaves no history slot in a window of %d", gap_len, L);
-    hipLaunchKernelGGL(k_build_eval_batch, dim3(B), dim3(64), 0, s, items, offsets, B, L, raw_len, gap_len,
-                       (int64_t)ctx->dims.n_item, targets_in, pool, n_pool, (unsigned long long)seed, seq, target, label, raw,
-                       raw_n, status);
+int irs_launch_build_eval_batch(irs_ctx *ctx, const irs_eval_batch_args &a, hipStream_t s) {
+    if (a.L - a.gap_len - 1 < 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "gap_len %d leaves no history slot in a window of %d", a.gap_len, a.L);
+    hipLaunchKernelGGL(k_build_eval_batch, dim3(a.B), dim3(64), 0, s, a);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }
