@@ -72,6 +72,8 @@ extern "C" {
 #define IRS_ROW_NO_CANDIDATE 2 /* every one of the k candidates is in the window
                                   (the reference raises IndexError at influentialRS.py:429) */
 #define IRS_ROW_FEWER_THAN_K 4 /* catalog shard has fewer than k items; tail filled with (-inf, -1) */
+#define IRS_ROW_RESCUED 8      /* the window hid the row's top-k list; irs_topk_ensure_survivors replaced it by the exact
+                                  best items outside the window */
 
 #define IRS_MAX_SAMPLE_K 8 /* sampled path steps draw among at most this many survivors (reference default: 3);
                               larger sample_k -> IRS_E_UNSUPPORTED */
@@ -473,6 +475,57 @@ int irs_beam_search_until(irs_ctx *ctx, const int64_t *dev_seq0, const int64_t *
                           int32_t W, int32_t P, int32_t k, int32_t sweep, int32_t stop_rule, int32_t check_every,
                           float *dev_paths, double *dev_scores, int32_t *dev_fin, int64_t *dev_seq_final,
                           int32_t *dev_status, int64_t *host_stats, void *stream);
+
+/* ---- exact candidates when the window hides the top-k (opt-in; BUILD-DEFINED: the reference raises IndexError at
+ *      influentialRS.py:429 for one user, and has no beam search to starve) -------------------------------------------
+ * Every search step chooses among the k best items of the catalog after dropping those in the row's window
+ * seq[m, 0 .. hep[m]]; nothing guarantees that any of them survives.  irs_topk_ensure_survivors repairs such rows
+ * exactly, so that a step on its lists returns what the same step would return with k = n_item.
+ * A row's list is val[m, 0 .. k) / ids0[m, 0 .. k); it ends at the first negative id.  A SURVIVOR is an entry whose item
+ * ids0 + 1 does not occur in seq[m, 0 .. hep[m]] (the path step's own test: positions beyond hep[m] do not count).  A row
+ * is STARVED when its list has k valid entries (a list that ended early already is the whole catalog), fewer than `want`
+ * of them survive, and the row is not skipped: cum[m] == -inf (a dead beam), fin[m] != 0 (a finished beam) or
+ * done[m / rows_per_status] != 0 (a finished user) skip it; each of the three pointers may be NULL.
+ * For the starved rows only, the exact best items of the whole catalog outside the window are computed -- float32 chain of
+ * irs_score_topk bit for bit, the library's total order -- and the list is rewritten: with n = min(want, catalog items
+ * outside the window), entries [0, n) are those items with their exact scores, descending; if n < k, entry n is
+ * (-inf, -1), so the list ends there; IRS_ROW_RESCUED is OR-ed into dev_status[m / rows_per_status] (several beams of a
+ * user may set it).  n == 0 leaves an empty list: the unchanged step then sets IRS_ROW_NO_CANDIDATE, which with this pass
+ * means what it says -- no item of the catalog lies outside the window.  Rows that are not starved are not written.
+ * Launches: a 4-byte memset, a flag pass (one wave per row) and two kernels that return at once when no row is starved;
+ * otherwise one pass over the float32 catalog, cut into item strips, serves all starved rows together (any number of
+ * them), and an item is tested against the window only after its score has beaten the row's running threshold.  No float
+ * atomics: two identical calls give identical bits.  Nothing is allocated; all work goes on the caller's stream.
+ *  dev_xrows float [M, d] the rows the lists were scored from; dev_seq int64 [M, L]; dev_hep int32 [M]
+ *  dev_cum double [M], dev_fin int32 [M], dev_done int32 [M / rows_per_status]: may be NULL
+ *  dev_val float [M, k], dev_ids0 int64 [M, k], dev_status int32 [M / rows_per_status]: in / out
+ *  dev_scratch: caller-owned like irs_ce_backward's, >= irs_survivor_scratch_bytes(M, want) bytes, 16-byte aligned.  It holds
+ *            the count and the list of the starved rows and the per-strip keys, never anything of order rows x n_item:
+ *            256 + 4 rows (rounded up to 16) + 8 rows strips want bytes, strips = the largest power of two <= min(256,
+ *            n_local / 128) (at least 1), halved while strips > 1 and rows x strips x want > 2^21.  Bound: 272 + 4 rows +
+ *            8 max(2^21, rows x want) bytes, i.e. 16 MiB + 4 rows until rows x want exceeds 2^21.
+ * Checks, all before any launch: null required pointers, M < 1, k outside [1, max_k], want outside [1, min(k, 32)],
+ * rows_per_status < 1 or not dividing M, a scratch too small or not 16-byte aligned -> IRS_E_INVALID; world != 1 (the pass
+ * needs the whole catalog) -> IRS_E_UNSUPPORTED; weights or workspace unbound -> IRS_E_STATE.
+ *
+ * irs_bind_survivor_scratch makes the four single-device loops do this themselves (NULL / 0 unbinds; a non-null scratch
+ * must be 16-byte aligned).  While a scratch is bound, irs_generate_paths, irs_generate_paths_until, irs_beam_search and
+ * irs_beam_search_until enqueue the pass between their top-k and their step, with want = 1 (greedy), sample_k (sampled)
+ * or W (beam; the beam loops pass their cum / fin / done), so that their result is what the same loop returns with
+ * k = n_item.  In sampled mode a row with at least sample_k survivors is untouched and draws as it does unbound for the
+ * same seed; a starved row draws among the exact best sample_k admissible items.  A bound scratch smaller than
+ * irs_survivor_scratch_bytes(rows of the call, want) returns IRS_E_INVALID before any launch.  The route where one
+ * workgroup ranks and steps a row is not taken while a scratch is bound (top-k, pass and step are separate launches).
+ * Binding or unbinding drops the captured steps; a captured step replays the pass like any other launch.  With nothing
+ * bound every entry point launches exactly what it launched before this pass existed.
+ * The sharded loops return IRS_E_UNSUPPORTED while a scratch is bound: a shard can only rescue a row against its own
+ * items, and the exact answer needs the other shards' items outside the window as well. */
+size_t irs_survivor_scratch_bytes(const irs_ctx *ctx, int32_t rows, int32_t want); /* 0 for invalid arguments */
+int irs_topk_ensure_survivors(irs_ctx *ctx, const float *dev_xrows, const int64_t *dev_seq, const int32_t *dev_hep, int32_t M,
+                              int32_t rows_per_status, int32_t k, int32_t want, const double *dev_cum, const int32_t *dev_fin,
+                              const int32_t *dev_done, float *dev_val, int64_t *dev_ids0, int32_t *dev_status,
+                              void *dev_scratch, size_t scratch_bytes, void *stream);
+int irs_bind_survivor_scratch(irs_ctx *ctx, void *dev_scratch, size_t bytes);
 
 /* ---- multi-GPU: the exchange steps and the sharded search loops below the ABI (section 8 row B2's
  *      `allgather_merge(ctx, comm, ...)`).  One process per GPU; rank r holds item rows [item_lo, item_hi) (irs_shard).

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(HERE, "libirs_hip.so")
 
 IRS_MASK_IRN, IRS_MASK_CAUSAL = 0, 1
 IRS_SWEEP_BF16, IRS_SWEEP_F32, IRS_SWEEP_EXHAUSTIVE = 0, 1, 2
-IRS_ROW_FALLBACK, IRS_ROW_NO_CANDIDATE, IRS_ROW_FEWER_THAN_K = 1, 2, 4
+IRS_ROW_FALLBACK, IRS_ROW_NO_CANDIDATE, IRS_ROW_FEWER_THAN_K, IRS_ROW_RESCUED = 1, 2, 4, 8
 IRS_GEMM_F32, IRS_GEMM_X6, IRS_GEMM_H3 = 0, 1, 2
 IRS_BEAM_STOP_ALL, IRS_BEAM_STOP_BEST = 0, 1
 # irs_decoder_route_last (include/irs_hip.h): its field order and the names of the enum-valued fields, in the order of
@@ -94,6 +94,10 @@ SIGNATURES = {
     "irs_beam_search_until": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                         c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64),
                                         c_void_p]),
+    "irs_survivor_scratch_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),
+    "irs_topk_ensure_survivors": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "irs_bind_survivor_scratch": (c_int32, [c_void_p, c_void_p, c_size_t]),
     "irs_comm_unique_id": (c_int32, [c_void_p]),
     "irs_comm_init_rccl": (c_int32, [POINTER(c_void_p), c_void_p, c_int32, c_int32]),
     "irs_comm_init_callbacks": (c_int32, [POINTER(c_void_p), c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -630,7 +630,9 @@ extern "C" int irs_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int32_t B
 
 // one search step on one device: decode -> rows at hep -> top-k -> choose/update.  `pa` is the loop's (loop_path_args): the step
 // index comes from the device counter
-static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int B, int k, int sweep, hipStream_t s, int carry = 0) {
+// surv_fin (may be null): rows the survivor pass skips -- the until loop's finished rows, stepped until the next compaction
+static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int B, int k, int sweep, hipStream_t s, int carry = 0,
+                        const int32_t *surv_fin = nullptr) {
     int rc;
     const bool merged = irs_small_plan(ctx->dims, B); // (the decode below is rows-only: its plan is the single-workgroup one)
     pa.step_next = merged ? ctx->step_ctr + 1 : nullptr;
@@ -639,12 +641,55 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
     ctx->step_pair = nullptr;
     if (rc) return rc;
     // small shard, few rows: the workgroup that ranks a row's candidates also takes the row's path step
-    if (merged && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k))
+    // (not while exact candidates are bound: the survivor pass goes between the ranking and the step)
+    if (merged && !ctx->surv_scratch && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k))
         return irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, &pa);
     if ((rc = irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, nullptr, nullptr, carry)))
         return rc;
+    if (ctx->surv_scratch) {
+        const irs_surv_args sa{ctx->xrows, pa.seq, pa.hep, B, 1, k, pa.sample ? pa.sample_k : 1, ctx->surv_rows, nullptr, surv_fin, nullptr,
+                               ctx->top_val, ctx->top_ids, pa.status, nullptr};
+        if ((rc = irs_launch_survivors(ctx, sa, ctx->surv_scratch, s))) return rc;
+    }
     if ((rc = irs_launch_path_step(ctx, pa, B, ctx->top_val, ctx->top_ids, k, s))) return rc;
     return merged ? IRS_OK : irs_launch_inc(ctx, ctx->step_ctr, s);
+}
+
+// ------------------------------------------------------------------ exact candidates (survivors.hip)
+extern "C" size_t irs_survivor_scratch_bytes(const irs_ctx *ctx, int32_t rows, int32_t want) {
+    if (!ctx || rows < 1 || want < 1 || want > 32) return 0;
+    return irs_surv_scratch(ctx, rows, want);
+}
+
+extern "C" int irs_topk_ensure_survivors(irs_ctx *ctx, const float *xrows, const int64_t *seq, const int32_t *hep, int32_t M,
+                                         int32_t rows_per_status, int32_t k, int32_t want, const double *cum, const int32_t *fin,
+                                         const int32_t *done, float *val, int64_t *ids0, int32_t *status, void *scratch,
+                                         size_t scratch_bytes, void *stream) {
+    if (!ctx) return IRS_E_INVALID;
+    if (!xrows || !seq || !hep || !val || !ids0 || !status || !scratch) IRS_FAIL(ctx, IRS_E_INVALID, "irs_topk_ensure_survivors: null pointer");
+    if (M < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_topk_ensure_survivors: M must be >= 1");
+    if (k < 1 || k > ctx->dims.max_k) IRS_FAIL(ctx, IRS_E_INVALID, "irs_topk_ensure_survivors: k must be in [1, %d]", ctx->dims.max_k);
+    if (want < 1 || want > k || want > 32) IRS_FAIL(ctx, IRS_E_INVALID, "irs_topk_ensure_survivors: want must be in [1, min(k, 32)]");
+    if (rows_per_status < 1 || M % rows_per_status)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_topk_ensure_survivors: rows_per_status must be >= 1 and divide M");
+    if (scratch_bytes < irs_surv_scratch(ctx, M, want))
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_topk_ensure_survivors: scratch too small: %zu < %zu", scratch_bytes, irs_surv_scratch(ctx, M, want));
+    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_topk_ensure_survivors: scratch must be 16-byte aligned");
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_topk_ensure_survivors needs the whole catalog on one device");
+    const int rc = ready(ctx);
+    if (rc) return rc;
+    const irs_surv_args sa{xrows, seq, hep, M, rows_per_status, k, want, M, cum, fin, done, val, ids0, status, nullptr};
+    return irs_launch_survivors(ctx, sa, scratch, (hipStream_t)stream);
+}
+
+extern "C" int irs_bind_survivor_scratch(irs_ctx *ctx, void *scratch, size_t bytes) {
+    if (!ctx) return IRS_E_INVALID;
+    if ((scratch == nullptr) != (bytes == 0)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_survivor_scratch: a scratch and its size go together");
+    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_survivor_scratch: scratch must be 16-byte aligned");
+    ctx->surv_scratch = scratch;
+    ctx->surv_bytes = bytes;
+    irs_drop_graphs(ctx); // (a captured step holds or lacks the pass)
+    return IRS_OK;
 }
 
 // ------------------------------------------------------------------ what the search loops share
@@ -708,7 +753,15 @@ static int check_search(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W
         if (!ptrs_ok || B < 1 || P < 1) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad arguments", fn);
         if (B > ctx->max_seqs || B > ctx->max_rows) IRS_FAIL(ctx, IRS_E_INVALID, "%s: B too large", fn);
     }
-    return irs_check_k(ctx, fn, k, 1, sweep, sample, sample_k);
+    if ((rc = irs_check_k(ctx, fn, k, 1, sweep, sample, sample_k))) return rc;
+    if (ctx->surv_scratch) { // exact candidates: the bound scratch must serve this call's rows
+        const int rows = W ? B * W : B, want = W ? W : (sample ? sample_k : 1);
+        if (want > k) IRS_FAIL(ctx, IRS_E_INVALID, "%s: exact candidates need k >= %d", fn, want);
+        const size_t need = irs_surv_scratch(ctx, rows, want);
+        if (ctx->surv_bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bound survivor scratch too small: %zu < %zu", fn, ctx->surv_bytes, need);
+        ctx->surv_rows = rows;
+    }
+    return IRS_OK;
 }
 
 // the path step's arguments inside a search loop: the step index comes from the device counter
@@ -794,7 +847,7 @@ extern "C" int irs_generate_paths_until(irs_ctx *ctx, int64_t *seq, const int64_
     // (an error below returns at once: host_stats unwritten, paths / status / seq / hep partly written -- see the header; the step
     //  counter pair is left wherever the last step put it, and every search loop resets it in irs_search_begin)
     for (int i = 0; i < P && live > 0; ++i) {
-        if ((rc = enqueue_step(ctx, pa, cuser, live, k, sweep, s, carry))) return rc;
+        if ((rc = enqueue_step(ctx, pa, cuser, live, k, sweep, s, carry, ctx->un_fin))) return rc;
         if ((rc = irs_launch_until_record(ctx, ctx->un_stage, P, i, cmap, pa.seq, live, ctx->un_fin, ctx->un_status, paths, status, s)))
             return rc;
         ++steps, row_steps += live, carry = 1;
@@ -859,6 +912,12 @@ static int enqueue_beam_step(irs_ctx *ctx, int in, const int64_t *user, int B, i
     // W > 1: top-k and log-sum-exp out of one call (one pass over the float32 catalog on the swept path)
     if ((rc = irs_launch_topk(ctx, ctx->xrows, rows, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, lmax, lsum)))
         return rc;
+    if (ctx->surv_scratch) { // exact candidates: a live unfinished beam of a user that is not done sees its best W admissible items
+        const irs_surv_args sa{ctx->xrows, ctx->bm[in].seq, ctx->bm[in].hep, rows, W, k, W, ctx->surv_rows, ctx->bm[in].cum,
+                               until ? ctx->bm[in].fin : nullptr, until ? until->done : nullptr, ctx->top_val, ctx->top_ids, status,
+                               until ? until->map : nullptr};
+        if ((rc = irs_launch_survivors(ctx, sa, ctx->surv_scratch, s))) return rc;
+    }
     return irs_enqueue_beam_tail(ctx, in, lmax, lsum, B, W, k, P, status, until, s);
 }
 

@@ -313,6 +313,8 @@ __global__ void k_short_list(const int64_t *__restrict__ ids0, int k, int n, int
 static int ready_sharded(irs_ctx *ctx, irs_comm *comm, const char *fn, int sweep) {
     int rc = comm_check(ctx, comm, fn);
     if (rc) return rc;
+    if (ctx->surv_scratch) // (a shard could only rescue a starved row against its own items: irs_bind_survivor_scratch)
+        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: exact candidates (irs_bind_survivor_scratch) need the whole catalog on one device", fn);
     if ((rc = irs_ready_filter(ctx, sweep))) return rc;
     if (sweep != IRS_SWEEP_BF16 && sweep != IRS_SWEEP_F32) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad sweep", fn);
     return IRS_OK;

@@ -223,6 +223,12 @@ struct irs_ctx {
     // captured steps of the search loops (irs_replay_steps): three independent caches, dropped together by irs_drop_graphs
     irs_step_graph g_greedy, g_beam, g_sharded;
 
+    // exact candidates (irs_bind_survivor_scratch): the caller's scratch while bound; the single-device loops then run the
+    // survivor pass between their top-k and their step, the sharded loops refuse
+    void *surv_scratch;
+    size_t surv_bytes;
+    int surv_rows; // rows of the running search call (its first step's): the scratch layout its later, smaller steps keep
+
     // profiling
     int prof_family;
     irs_prof_ev *prof_ev;
@@ -315,6 +321,24 @@ int irs_launch_ce_grad(irs_ctx *ctx, const float *xrows, const int64_t *labels0,
 size_t irs_ce_bwd_scratch(const irs_ctx *ctx, int M);
 int irs_launch_ce_backward(irs_ctx *ctx, const float *xrows, const int64_t *labels0, const float *lse, int M, float scale,
                            int accumulate, float *dx, float *dw, float *db, void *scratch, hipStream_t s);
+
+// ---- survivors.hip ---- (exact candidates for rows whose window hides their top-k; arguments already validated)
+struct irs_surv_args {
+    const float *xrows;  // [M][d]
+    const int64_t *seq;  // [M][L]
+    const int32_t *hep;  // [M]
+    int M, rps, k, want; // rps: rows per status word
+    int rows_cap;        // rows the scratch was sized for (>= M): irs_surv_scratch(rows_cap, want) bytes
+    const double *cum;   // [M] or null: -inf skips the row
+    const int32_t *fin;  // [M] or null: != 0 skips the row
+    const int32_t *done; // [M / rps] or null: != 0 skips the user's rows
+    float *val;          // [M][k] in / out
+    int64_t *ids0;       // [M][k] in / out
+    int32_t *status;     // IRS_ROW_RESCUED goes to status[u], u = row / rps, or to status[status_map[u]]
+    const int32_t *status_map;
+};
+size_t irs_surv_scratch(const irs_ctx *ctx, int rows, int want);
+int irs_launch_survivors(irs_ctx *ctx, const irs_surv_args &a, void *scratch, hipStream_t s);
 
 // ---- comm.hip ---- (collectives in bytes, stream-ordered; irs_comm_check: the communicator is the context's shard)
 int irs_comm_check(irs_ctx *ctx, const irs_comm *c, const char *fn);

@@ -1,0 +1,233 @@
+// Exact candidates for rows whose top-k list is hidden by their window (irs_topk_ensure_survivors, include/irs_hip.h).
+// A search step chooses among the k best items of the catalog after dropping those in the row's window; when fewer than `want`
+// of them survive, the row is STARVED: the step would see fewer continuations than the catalog holds.  Three launches repair it:
+//   k_surv_flag    one wave per row: counts the list's survivors with the path step's own membership test and records the
+//                  starved rows (count + list in the caller's scratch);
+//   k_surv_strips  the recorded rows' exact scores over the whole float32 shard, cut into item strips like k_exh_strips
+//                  (score.hip): a workgroup keeps the best `want` keys of its strip that are NOT in the row's window;
+//   k_surv_merge   one workgroup per recorded row: the best `want` of the strips' keys become the row's list.
+// The last two return at once when nothing was recorded.  No float atomics, and a row's result does not depend on its place
+// in the recorded list: two identical calls give identical bits.
+#include "irs_internal.h"
+
+#define SURV_STRIPS 256          // item strips of a large shard
+#define SURV_STRIP_MIN_ITEMS 128 // a strip holds at least this many items (smaller shards: fewer strips, down to one)
+#define SURV_KEYS_CAP (1 << 21)  // rows x strips x want <= this (16 MiB of keys) while strips > 1: the strip count shrinks
+#define SURV_BUF 512             // keys of LDS per selection: compacted to `want` (<= 32) whenever more than 256 are held
+#define SURV_ROW_GROUPS 64       // workgroups that share the recorded rows, per strip and in the merge: each loops over its rows
+#define SURV_HDR 256             // bytes in front of the list: word 0 is the count
+
+static inline size_t surv_align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+static int surv_strips(int64_t n_local, int rows, int want) {
+    int ns = 1;
+    while (ns < SURV_STRIPS && (int64_t)ns * 2 * SURV_STRIP_MIN_ITEMS <= n_local) ns <<= 1;
+    while (ns > 1 && (int64_t)rows * ns * want > SURV_KEYS_CAP) ns >>= 1;
+    return ns;
+}
+
+size_t irs_surv_scratch(const irs_ctx *ctx, int rows, int want) {
+    const int ns = surv_strips(ctx->n_local, rows, want);
+    return SURV_HDR + surv_align16((size_t)rows * sizeof(int32_t)) + (size_t)rows * ns * want * sizeof(unsigned long long);
+}
+
+// ---- flag pass: one wave per row.  The list is walked in order, 64 ids at a time (one per lane, broadcast by shuffle): it ends
+// at the first negative id (a list that ended early is the whole catalog: not starved), and the walk stops as soon as `want`
+// survivors are seen.  Only a row that shows all k valid entries and fewer than `want` survivors is recorded.
+__global__ void __launch_bounds__(256) k_surv_flag(const int64_t *__restrict__ seq, int L, const int32_t *__restrict__ hep, int M,
+                                                   int rps, int k, int want, const double *__restrict__ cum,
+                                                   const int32_t *__restrict__ fin, const int32_t *__restrict__ done,
+                                                   const int64_t *__restrict__ ids0, unsigned int *__restrict__ count,
+                                                   int32_t *__restrict__ list) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= M) return;
+    if (cum && cum[row] == -INFINITY) return;
+    if (fin && fin[row] != 0) return;
+    if (done && done[row / rps] != 0) return;
+    const int64_t *w = seq + (size_t)row * L;
+    const int wl = hep[row] + 1; // window = seq[row, 0 .. hep]
+    int64_t wv[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int p = lane + 64 * i;
+        wv[i] = (p < wl && p < L) ? w[p] : (int64_t)-1;
+    }
+    int found = 0;
+    bool ended = false;
+    for (int c0 = 0; c0 < k && !ended && found < want; c0 += 64) {
+        const int c = c0 + lane;
+        const long long mine = c < k ? (long long)ids0[(size_t)row * k + c] : -1ll;
+        const int n_here = k - c0 < 64 ? k - c0 : 64;
+        for (int i = 0; i < n_here; ++i) {
+            const long long id0 = __shfl(mine, i, 64);
+            if (id0 < 0) {
+                ended = true;
+                break;
+            }
+            const int64_t item = id0 + 1;
+            bool hit = false;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) hit |= (wv[q] == item);
+            if (!__any(hit) && ++found >= want) break;
+        }
+    }
+    if (!ended && found < want && lane == 0) list[atomicAdd(count, 1u)] = row;
+}
+
+// bitonic sort of n (a power of two) values in LDS by the whole workgroup; DESC: largest first
+template <typename T, bool DESC>
+__device__ __forceinline__ void surv_bitonic(T *a, int n) {
+    for (int size = 2; size <= n; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            for (int i = threadIdx.x; i < n / 2; i += blockDim.x) {
+                const int lo = 2 * i - (i & (stride - 1));
+                const int hi = lo + stride;
+                const bool first = ((lo & size) == 0) == DESC; // this pair keeps its larger value first
+                const T u = a[lo], v = a[hi];
+                if ((u < v) == first) {
+                    a[lo] = v;
+                    a[hi] = u;
+                }
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// Streaming top-`want` of the keys keyfn(j), j in [j0, j1) (0 = no key): leaves the best min(n, want) admitted keys sorted
+// descending in buf[0 ..) and returns their number.  admit(key) is asked only for a key that has beaten the running threshold
+// (the want-th best admitted key so far), so its cost is paid for the few keys that could still enter the result.
+// The held count is read into a register between two barriers: no thread can append to the next chunk while another still
+// decides whether to compact.
+template <typename KeyFn, typename AdmitFn>
+__device__ __forceinline__ unsigned int surv_select(KeyFn &&keyfn, AdmitFn &&admit, int64_t j0, int64_t j1, int want,
+                                                    unsigned long long *buf) {
+    __shared__ unsigned int s_n;
+    __shared__ unsigned long long s_thr;
+    const int tid = threadIdx.x;
+    __syncthreads();
+    if (tid == 0) {
+        s_n = 0;
+        s_thr = 0ull;
+    }
+    __syncthreads();
+    for (int64_t base = j0; base < j1; base += 256) {
+        const int64_t j = base + tid;
+        if (j < j1) {
+            const unsigned long long key = keyfn(j);
+            if (key > s_thr && admit(key)) buf[atomicAdd(&s_n, 1u)] = key; // (at most 256 held at the loop's top: the slot is < SURV_BUF)
+        }
+        __syncthreads();
+        const unsigned int n = s_n;
+        __syncthreads();
+        if (n > SURV_BUF - 256) {
+            for (int i = n + tid; i < SURV_BUF; i += 256) buf[i] = 0ull;
+            surv_bitonic<unsigned long long, true>(buf, SURV_BUF);
+            if (tid == 0) {
+                s_n = (n < (unsigned int)want) ? n : want;
+                if (n >= (unsigned int)want) s_thr = buf[want - 1];
+            }
+            __syncthreads();
+        }
+    }
+    const unsigned int n = s_n;
+    for (int i = n + tid; i < SURV_BUF; i += 256) buf[i] = 0ull;
+    surv_bitonic<unsigned long long, true>(buf, SURV_BUF);
+    return n < (unsigned int)want ? n : (unsigned int)want;
+}
+
+// ---- exhaustive pass over the strips.  grid (strips, y): workgroup (s, y) serves recorded rows y, y + gridDim.y, ... on strip s,
+// so one pass over the float32 shard serves all recorded rows together (a strip stays in cache from row to row).  The row's
+// window ids are sorted into LDS once per (workgroup, row); an item is searched there only after its key has beaten the
+// running threshold.
+__global__ void __launch_bounds__(256) k_surv_strips(const float *__restrict__ x, int d, const float *__restrict__ W,
+                                                     const float *__restrict__ bias, int64_t n_local, int64_t item_lo,
+                                                     const int64_t *__restrict__ seq, int L, const int32_t *__restrict__ hep,
+                                                     int want, int n_strips, const unsigned int *__restrict__ count,
+                                                     const int32_t *__restrict__ list, unsigned long long *__restrict__ keys) {
+    __shared__ unsigned long long buf[SURV_BUF];
+    __shared__ float xs[256];
+    __shared__ long long win[256];
+    const unsigned int n_rows = *count;
+    if (n_rows == 0u) return;
+    const int tid = threadIdx.x;
+    const int strip = blockIdx.x;
+    const int64_t per = (n_local + n_strips - 1) / n_strips;
+    const int64_t j0 = (int64_t)strip * per, j1 = (j0 + per < n_local) ? j0 + per : n_local;
+    for (unsigned int fi = blockIdx.y; fi < n_rows; fi += gridDim.y) {
+        const int row = list[fi];
+        int wl = hep[row] + 1;
+        wl = wl < 0 ? 0 : (wl > L ? L : wl);
+        __syncthreads();
+        for (int i = tid; i < d; i += 256) xs[i] = x[(size_t)row * d + i];
+        win[tid] = tid < wl ? (long long)seq[(size_t)row * L + tid] : 0x7FFFFFFFFFFFFFFFll; // (L <= 256 = the workgroup)
+        surv_bitonic<long long, false>(win, 256);
+        const unsigned int n = surv_select(
+            [&](int64_t j) -> unsigned long long {
+                const float e = irs_chain(xs, W + (size_t)j * d, bias[j], d);
+                return ((unsigned long long)irs_fkey(e) << 32) | (0xFFFFFFFFu - (unsigned int)j);
+            },
+            [&](unsigned long long key) -> bool { // the item is not in win[0 .. wl)
+                const long long item = (long long)(item_lo + (int64_t)(0xFFFFFFFFu - (unsigned int)key) + 1);
+                int lo = 0, hi = wl;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (win[mid] < item) lo = mid + 1;
+                    else hi = mid;
+                }
+                return !(lo < wl && win[lo] == item);
+            },
+            j0, j1, want, buf);
+        unsigned long long *o = keys + ((size_t)fi * n_strips + strip) * want;
+        for (int i = tid; i < want; i += 256) o[i] = i < (int)n ? buf[i] : 0ull;
+    }
+}
+
+// ---- list rewrite: the best `want` of a recorded row's strip keys, in the library's order; the list ends behind them
+__global__ void __launch_bounds__(256) k_surv_merge(int64_t item_lo, int k, int want, int n_strips, int rps,
+                                                    const unsigned int *__restrict__ count, const int32_t *__restrict__ list,
+                                                    const unsigned long long *__restrict__ keys, const int32_t *__restrict__ status_map,
+                                                    float *__restrict__ val, int64_t *__restrict__ ids, int32_t *__restrict__ status) {
+    __shared__ unsigned long long buf[SURV_BUF];
+    const unsigned int n_rows = *count;
+    if (n_rows == 0u) return;
+    for (unsigned int fi = blockIdx.x; fi < n_rows; fi += gridDim.x) {
+        const int row = list[fi];
+        const unsigned long long *src = keys + (size_t)fi * n_strips * want;
+        const unsigned int n = surv_select([&](int64_t j) -> unsigned long long { return src[j]; },
+                                           [](unsigned long long) -> bool { return true; }, 0, (int64_t)n_strips * want, want, buf);
+        for (int i = threadIdx.x; i <= (int)n && i < k; i += 256) {
+            const unsigned long long kk = buf[i];
+            const bool live = i < (int)n;
+            val[(size_t)row * k + i] = live ? irs_unkey((unsigned int)(kk >> 32)) : -INFINITY;
+            ids[(size_t)row * k + i] = live ? item_lo + (int64_t)(0xFFFFFFFFu - (unsigned int)kk) : (int64_t)-1;
+        }
+        if (threadIdx.x == 0) {
+            const int u = row / rps;
+            atomicOr(&status[status_map ? status_map[u] : u], IRS_ROW_RESCUED);
+        }
+        __syncthreads();
+    }
+}
+
+int irs_launch_survivors(irs_ctx *ctx, const irs_surv_args &a, void *scratch, hipStream_t s) {
+    // the layout is the one the scratch was sized for (rows_cap >= M rows): the strip count is not monotone in the row count
+    const int ns = surv_strips(ctx->n_local, a.rows_cap, a.want);
+    unsigned int *count = (unsigned int *)scratch;
+    int32_t *list = (int32_t *)((char *)scratch + SURV_HDR);
+    unsigned long long *keys = (unsigned long long *)((char *)list + surv_align16((size_t)a.rows_cap * sizeof(int32_t)));
+    const int L = ctx->dims.max_len;
+    IRS_CHECK_HIP(ctx, hipMemsetAsync(count, 0, sizeof(unsigned int), s));
+    hipLaunchKernelGGL(k_surv_flag, dim3((a.M + 3) / 4), dim3(256), 0, s, a.seq, L, a.hep, a.M, a.rps, a.k, a.want, a.cum, a.fin, a.done,
+                       a.ids0, count, list);
+    int ny = 4096 / ns < 4 ? 4 : (4096 / ns > SURV_ROW_GROUPS ? SURV_ROW_GROUPS : 4096 / ns);
+    if (ny > a.M) ny = a.M;
+    hipLaunchKernelGGL(k_surv_strips, dim3(ns, ny), dim3(256), 0, s, a.xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b, ctx->n_local,
+                       ctx->shard.item_lo, a.seq, L, a.hep, a.want, ns, count, list, keys);
+    hipLaunchKernelGGL(k_surv_merge, dim3(a.M < SURV_ROW_GROUPS ? a.M : SURV_ROW_GROUPS), dim3(256), 0, s, ctx->shard.item_lo, a.k, a.want, ns, a.rps, count, list,
+                       keys, a.status_map, a.val, a.ids0, a.status);
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}

@@ -7,6 +7,7 @@ return device tensors; nothing synchronises unless the caller does.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from typing import Dict, Optional, Tuple
 
@@ -370,6 +371,64 @@ class Engine:
                                                   _ptr(seq), _ptr(tgt), _ptr(lab), _ptr(raw), _ptr(raw_n), _ptr(status))
         return seq, tgt, lab, raw, raw_n, status
 
+    # ------------------------------------------------------------------ exact candidates (survivors.hip)
+    def survivor_scratch_bytes(self, rows: int, want: int) -> int:
+        n = int(self.lib.irs_survivor_scratch_bytes(self.h, rows, want))
+        if n == 0:
+            raise IrsError(f"survivor_scratch_bytes: rows={rows} / want={want} (want in [1, 32])")
+        return n
+
+    def ensure_survivors(self, xrows: torch.Tensor, seqs: torch.Tensor, hep: torch.Tensor, val: torch.Tensor, ids0: torch.Tensor,
+                         status: torch.Tensor, want: int = 1, rows_per_status: int = 1, cum: Optional[torch.Tensor] = None,
+                         fin: Optional[torch.Tensor] = None, done: Optional[torch.Tensor] = None,
+                         scratch: Optional[torch.Tensor] = None):
+        """irs_topk_ensure_survivors: rows whose k candidates leave fewer than `want` survivors outside the window
+        seqs[m, :hep[m] + 1] get the exact best `want` admissible items of the whole catalog (val / ids0 rewritten in place,
+        IRS_ROW_RESCUED in status[m // rows_per_status]); other rows are not written.  Returns (val, ids0, status)."""
+        xrows = self._dev(xrows, torch.float32)
+        seqs, hep = self._dev(seqs, torch.int64), self._dev(hep, torch.int32)
+        val = self._inplace(val, torch.float32, "ensure_survivors: val")
+        ids0 = self._inplace(ids0, torch.int64, "ensure_survivors: ids0")
+        status = self._inplace(status, torch.int32, "ensure_survivors: status")
+        M = xrows.shape[0]
+        if (xrows.shape[1] != self.d or seqs.shape != (M, self.L) or hep.numel() != M or val.shape != ids0.shape or val.shape[0] != M
+                or rows_per_status < 1 or M % rows_per_status or status.numel() != M // rows_per_status):
+            raise IrsError("ensure_survivors: inconsistent shapes")
+        cum = None if cum is None else self._dev(cum, torch.float64)
+        fin = None if fin is None else self._dev(fin, torch.int32)
+        done = None if done is None else self._dev(done, torch.int32)
+        if (cum is not None and cum.numel() != M) or (fin is not None and fin.numel() != M) or (
+                done is not None and done.numel() != M // rows_per_status):
+            raise IrsError("ensure_survivors: cum / fin are per row, done per status word")
+        if scratch is None:
+            scratch = torch.empty(self.survivor_scratch_bytes(M, want), dtype=torch.uint8, device=self.device)
+        self._call(self.lib.irs_topk_ensure_survivors, _ptr(xrows), _ptr(seqs), _ptr(hep), M, rows_per_status, val.shape[1], want,
+                   _ptr(cum), _ptr(fin), _ptr(done), _ptr(val), _ptr(ids0), _ptr(status), _ptr(scratch),
+                   scratch.numel() * scratch.element_size())
+        return val, ids0, status
+
+    @contextlib.contextmanager
+    def _exact_candidates(self, on: bool, rows: int, want: int, graph: bool = False):
+        """While a search call runs with exact_candidates: a scratch sized for the call's rows, bound before and unbound after
+        (irs_bind_survivor_scratch).  Binding and unbinding each drop ALL captured steps of the context, so with the keyword set
+        use_graph saves nothing: the step is captured again on every call, and steps captured by earlier calls are lost.  A
+        caller that wants a captured step with the pass inside binds a scratch of its own once (irs_bind_survivor_scratch) and
+        calls without the keyword.  graph: the call replays a captured step -- the stream is drained before the unbind destroys it."""
+        if not on:
+            yield
+            return
+        scratch = torch.empty(self.survivor_scratch_bytes(rows, want), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.irs_bind_survivor_scratch(self.h, _ptr(scratch), scratch.numel()))
+        try:
+            yield
+        finally:
+            stream = torch.cuda.current_stream(self.device)
+            if graph:
+                stream.synchronize()
+            # (the loops only enqueue: the scratch must outlive the work on the stream)
+            scratch.record_stream(stream)
+            self._check(self.lib.irs_bind_survivor_scratch(self.h, None, 0))
+
     # ------------------------------------------------------------------ path search
     def path_step(self, seqs, hep, val, ids0, step: int, paths, status, sample=False, sample_k=3, seed=0):
         seqs = self._inplace(seqs, torch.int64, "path_step: seqs")
@@ -386,9 +445,11 @@ class Engine:
     def generate_paths(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
                        k: int = 100, sweep: int = IRS_SWEEP_BF16, sample=False, sample_k=3, seed=0,
                        use_graph: bool = False, paths: Optional[torch.Tensor] = None,
-                       status: Optional[torch.Tensor] = None):
+                       status: Optional[torch.Tensor] = None, exact_candidates: bool = False):
         """Runs the whole search loop on the device.  `seqs` and `hep` are the
-        working window state and are modified in place."""
+        working window state and are modified in place.  exact_candidates: a row whose k candidates are hidden by its window
+        chooses among the exact best admissible items of the catalog instead (IRS_ROW_RESCUED; the result of k = n_item).
+        With the keyword set use_graph saves nothing: the step is captured again on every call (_exact_candidates)."""
         seqs = self._inplace(seqs, torch.int64, "generate_paths: seqs")
         hep = self._inplace(hep, torch.int32, "generate_paths: hep")
         if users is not None:
@@ -404,14 +465,15 @@ class Engine:
         status = self._inplace(status, torch.int32, "generate_paths: status")
         if paths.shape != (B, max_path_len):
             raise IrsError("generate_paths: paths must be [B, max_path_len]")
-        self._call(self.lib.irs_generate_paths, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
-                                                int(sample), sample_k, seed, int(use_graph), _ptr(paths), _ptr(status))
+        with self._exact_candidates(exact_candidates, B, sample_k if sample else 1, bool(use_graph)):
+            self._call(self.lib.irs_generate_paths, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
+                                                    int(sample), sample_k, seed, int(use_graph), _ptr(paths), _ptr(status))
         return paths, status
 
     def generate_paths_until(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
                              k: int = 100, sweep: int = IRS_SWEEP_BF16, sample=False, sample_k=3, seed=0,
                              check_every: int = 1, paths: Optional[torch.Tensor] = None,
-                             status: Optional[torch.Tensor] = None):
+                             status: Optional[torch.Tensor] = None, exact_candidates: bool = False):
         """generate_paths that stops a user at its target (seqs[b, L - 1]) and the call when nobody is left
         (irs_generate_paths_until): returns (paths, status, steps_run, row_steps).  Paths are zero behind the target.
         `seqs` and `hep` are working state: modified, and unspecified afterwards.  One host read of 4 bytes per check."""
@@ -431,8 +493,9 @@ class Engine:
         if paths.shape != (B, max_path_len):
             raise IrsError("generate_paths_until: paths must be [B, max_path_len]")
         stats = (ctypes.c_int64 * 2)(0, 0)
-        self._call(self.lib.irs_generate_paths_until, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
-                                                      int(sample), sample_k, seed, check_every, _ptr(paths), _ptr(status), stats)
+        with self._exact_candidates(exact_candidates, B, sample_k if sample else 1):
+            self._call(self.lib.irs_generate_paths_until, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
+                                                          int(sample), sample_k, seed, check_every, _ptr(paths), _ptr(status), stats)
         return paths, status, int(stats[0]), int(stats[1])
 
     # ------------------------------------------------------------------ beam search (build-defined extension)
@@ -454,7 +517,7 @@ class Engine:
 
     def beam_search(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
                     beam: int, k: int = 100, sweep: int = IRS_SWEEP_BF16, use_graph: bool = False,
-                    want_windows: bool = False):
+                    want_windows: bool = False, exact_candidates: bool = False):
         """(paths[B,W,P] f32, scores[B,W] f64, status[B] i32[, windows[B,W,L]]); beam 0 is the best."""
         seqs = self._dev(seqs, torch.int64)
         hep = self._dev(hep, torch.int32)
@@ -465,8 +528,9 @@ class Engine:
         scores = torch.zeros((B, beam), dtype=torch.float64, device=self.device)
         status = torch.zeros(B, dtype=torch.int32, device=self.device)
         fin = torch.empty((B, beam, self.L), dtype=torch.int64, device=self.device) if want_windows else None
-        self._call(self.lib.irs_beam_search, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
-                                             int(use_graph), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(status))
+        with self._exact_candidates(exact_candidates, B * beam, beam, bool(use_graph)):
+            self._call(self.lib.irs_beam_search, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
+                                                 int(use_graph), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(status))
         return (paths, scores, status, fin) if want_windows else (paths, scores, status)
 
     def beam_step_until(self, state_in, val, ids0, lse, step: int, stop_rule: int, state_out, done, status):
@@ -490,7 +554,7 @@ class Engine:
                           beam: int, k: int = 100, sweep: int = IRS_SWEEP_BF16, stop_rule: int = _lib.IRS_BEAM_STOP_BEST,
                           check_every: int = 1, want_windows: bool = False, paths: Optional[torch.Tensor] = None,
                           scores: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
-                          fin: Optional[torch.Tensor] = None):
+                          fin: Optional[torch.Tensor] = None, exact_candidates: bool = False):
         """Beam search that ends a beam at its target (seqs[b, L - 1]) and retires finished users (irs_beam_search_until):
         (paths[B,W,P] f32, scores[B,W] f64, status[B] i32, fin[B,W] i32, steps_run, window_steps[, windows[B,W,L]]); beam 0 is
         the best.  One host read of 4 bytes per check."""
@@ -517,8 +581,9 @@ class Engine:
             raise IrsError("beam_search_until: paths [B, W, P], scores / fin [B, W], status [B]")
         win = torch.empty((B, beam, self.L), dtype=torch.int64, device=self.device) if want_windows else None
         stats = (ctypes.c_int64 * 2)(0, 0)
-        self._call(self.lib.irs_beam_search_until, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
-                   int(stop_rule), int(check_every), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(win), _ptr(status), stats)
+        with self._exact_candidates(exact_candidates, B * beam, beam):
+            self._call(self.lib.irs_beam_search_until, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
+                       int(stop_rule), int(check_every), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(win), _ptr(status), stats)
         out = (paths, scores, status, fin, int(stats[0]), int(stats[1]))
         return out + (win,) if want_windows else out
 

@@ -92,6 +92,9 @@ def test_model(config, rows: Sequence, irn, device, result_dir: str = None, verb
         n_early_success, hit = 0, 0
         # (config.stop_at_target: the search stops a user at its target; a handler without the keyword is called as before)
         stop = {"stop_at_target": True} if getattr(config, "stop_at_target", False) else {}
+        # (config.exact_candidates: rows whose top-100 is hidden by their window choose among the exact best admissible items)
+        if getattr(config, "exact_candidates", False):
+            stop["exact_candidates"] = True
         for raw, seq, u, t, l in eval_batches_irs(rows, config.batch_size, config.max_len, config.gap_len):
             t, l, u, seq = t.to(device), l.to(device), u.to(device), seq.to(device)
             r_u = irn.get_pif_in_batch(seq, u)

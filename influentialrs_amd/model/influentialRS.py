@@ -20,6 +20,7 @@ Behaviour pinned by the reference (file:line = /root/reference/model/influential
   * candidate width 100 (:421); all 100 in the window -> IndexError (:429);
   * selection order is (score desc, id asc); torch's tie order is unspecified.
 """
+import functools
 import math
 import os
 
@@ -175,6 +176,20 @@ class InfluentialNet(nn.Module):
         return xr
 
 
+def _takes_exact_candidates(fn):
+    """Gives get_seq_in_batch its keyword exact_candidates=False.  It is taken here, keyword only, so that the declared
+    parameter list stays what it was (it ends with beam_stop): positional callers and code that reads the signature are not
+    disturbed.  The search reads the switch from self._exact_candidates for the time of the call."""
+    @functools.wraps(fn)
+    def call(self, *args, exact_candidates=False, **kw):
+        prev, self._exact_candidates = getattr(self, "_exact_candidates", False), bool(exact_candidates)
+        try:
+            return fn(self, *args, **kw)
+        finally:
+            self._exact_candidates = prev
+    return call
+
+
 class IRSNN(nn.Module):
     """Task handler (reference :219-470)."""
 
@@ -277,7 +292,7 @@ class IRSNN(nn.Module):
             rr.append(np.reciprocal(float(ranks[i])))
         return hit_count, np.array(rr)
 
-    def _beam_paths(self, seqs, users, max_path_len, gap_len, beam_width, beam_stop=None):
+    def _beam_paths(self, seqs, users, max_path_len, gap_len, beam_width, beam_stop=None, exact_candidates=False):
         """Best-beam paths [B, P] + status via the build-defined beam search (no reference
         counterpart; beam_width == 1 equals the greedy search).  All beams and their
         cumulative log-probabilities are kept in self.last_beams = (paths[B,W,P], scores[B,W]).
@@ -292,11 +307,12 @@ class IRSNN(nn.Module):
             eng = hip.get(B * W, B * W)
             paths, scores, status, fin, steps, window_steps = eng.beam_search_until(
                 seqs.contiguous(), users, hep, max_path_len, W, k=100, sweep=hip.sweep, stop_rule=_BEAM_STOP_RULES[beam_stop],
-                check_every=BEAM_STOP_CHECK_EVERY)
+                check_every=BEAM_STOP_CHECK_EVERY, exact_candidates=exact_candidates)
             self.last_beam_stop = dict(finished=fin.detach().cpu().numpy(), steps=steps, window_steps=window_steps)
         elif hip.world == 1:
             eng = hip.get(B * W, B * W)
-            paths, scores, status = eng.beam_search(seqs.contiguous(), users, hep, max_path_len, W, k=100, sweep=hip.sweep)
+            paths, scores, status = eng.beam_search(seqs.contiguous(), users, hep, max_path_len, W, k=100, sweep=hip.sweep,
+                                                    exact_candidates=exact_candidates)
         else:  # item-sharded: the whole loop runs below the C ABI (irs_beam_search_sharded: row all-gather, packed top-100
             # all-to-all, log-sum-exp all-reduce per step, one stream-ordered sequence; captured into a hipGraph over RCCL)
             eng = hip.get(B * W, B * W * hip.world)
@@ -308,6 +324,7 @@ class IRSNN(nn.Module):
         self.last_beams = (paths.detach().cpu().numpy(), scores.detach().cpu().numpy())
         return paths[:, 0].contiguous(), status
 
+    @_takes_exact_candidates
     def get_seq_in_batch(self, seqs, users, targets, max_path_len=20, gap_len=20, sample=False, sample_k=3,
                          beam_width=1, stop_at_target=False, beam_stop=None):
         """Persuasion-path generation (reference :392-470): returns
@@ -319,7 +336,15 @@ class IRSNN(nn.Module):
         beam_stop="best" / "all" (extension; beam_width > 1 on one device): the beam search with the window's target as its end
         symbol (irs_beam_search_until) -- a beam that has chosen the target is frozen and competes with its final score, and a
         user is retired once its best beam is finished ("best") or all its live beams are ("all").  A different search from
-        beam_stop=None, not the same paths cut short; self.last_beam_stop holds which beams finished and the work done."""
+        beam_stop=None, not the same paths cut short; self.last_beam_stop holds which beams finished and the work done.
+        exact_candidates=True (extension, keyword only, taken by _takes_exact_candidates; one device, off by default): a row
+        whose top-100 candidates are hidden by its window chooses among the exact best admissible items of the whole catalog
+        (irs_bind_survivor_scratch), so the search returns what it would return with k = n_item; the IndexError below remains
+        only for a catalog contained in the window."""
+        exact_candidates = getattr(self, "_exact_candidates", False)
+        if exact_candidates and self.net._hip.world != 1:
+            raise ValueError("exact_candidates is not built for an item-sharded catalog: a shard can only rescue a row against "
+                             "its own items")
         if stop_at_target and beam_width > 1:
             raise ValueError("stop_at_target is not built for beam search (beam_width > 1): irs_beam_search runs every step")
         if beam_stop is not None:
@@ -340,7 +365,7 @@ class IRSNN(nn.Module):
         hep = torch.full((B,), L - (gap_len + 1) - 1, dtype=torch.int32, device=dev)
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if sample else 0
         if beam_width > 1:
-            paths_t, status = self._beam_paths(work, users, max_path_len, gap_len, beam_width, beam_stop)
+            paths_t, status = self._beam_paths(work, users, max_path_len, gap_len, beam_width, beam_stop, exact_candidates)
         elif stop_at_target:
             if hip.world != 1:
                 raise ValueError("stop_at_target is not built for an item-sharded catalog: irs_generate_paths_sharded runs "
@@ -348,11 +373,12 @@ class IRSNN(nn.Module):
             eng = hip.get(B, B)
             paths_t, status, _, _ = eng.generate_paths_until(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
                                                              sample=sample, sample_k=sample_k, seed=seed,
-                                                             check_every=STOP_CHECK_EVERY)
+                                                             check_every=STOP_CHECK_EVERY, exact_candidates=exact_candidates)
         elif hip.world == 1:
             eng = hip.get(B, B)
             paths_t, status = eng.generate_paths(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
-                                                 sample=sample, sample_k=sample_k, seed=seed, use_graph=False)
+                                                 sample=sample, sample_k=sample_k, seed=seed, use_graph=False,
+                                                 exact_candidates=exact_candidates)
         else:  # item-sharded: irs_generate_paths_sharded (decode, row all-gather, shard sweep, key all-to-all, merge, path
             # step per search step, below the C ABI on one stream)
             eng = hip.get(B, B * hip.world)
@@ -360,7 +386,8 @@ class IRSNN(nn.Module):
                                                          sample=sample, sample_k=sample_k, seed=seed, use_graph=False)
         if int((status & IRS_ROW_NO_CANDIDATE).sum().item()) > 0:
             raise IndexError("index 0 is out of bounds: every top-100 candidate is already in the window "
-                             "(same condition as reference influentialRS.py:429)")
+                             "(same condition as reference influentialRS.py:429)" if not exact_candidates else
+                             "index 0 is out of bounds: every item of the catalog is already in the window")
         n_early_success = 0
         paths = paths_t.detach().cpu().numpy()
         targets = targets.detach().cpu().numpy()
