@@ -7,11 +7,9 @@
 //   6 x nn.TransformerDecoderLayer    model/influentialRS.py:67-74,189-193 (post-norm, relu, eps 1e-5)
 //   cross-attention over zero memory  model/influentialRS.py:172-173  -> constant c_l
 //
-// Kernels: k_embed, k_pif, k_linear (fp32 MFMA 32x32x2, 128x128 tiles, fused
-// bias / relu / residual), k_attn (per (sequence, head) with the mask computed
-// in registers, never materialised), k_ln (LN1 [+ c_l, LN2] fused), k_gather_rows.
-// fp32 MFMA is an exact k-ordered fma chain (no TF32-like path on gfx950), so
-// decoder rows agree with the fp32 reference to ~1e-6.
+// Kernel families: packed-decode plan (k_plan_*); embedding, optionally with q | k | v (k_embed*), and r_u (k_pif); per-GEMM float32
+// linears with fused LayerNorm (k_linear*, k_ln); whole-layer kernels (k_block, k_block_x6 with its sequence-resident form,
+// k_block_small*); attention per (sequence, head), masks never materialised (k_attn16, k_attn_mfma, k_attn_row*); packing, gathers.
 #include "irs_internal.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -1602,7 +1600,7 @@ struct BlockX6Args {
     int64_t n_item;
     // != 0 (with the q tail, QP0 = 0): the V section of a q | k | v row is written as float16 PLANE PAIRS -- per
     // (token, head) [32 f16 h | 32 f16 l], h = f16(v), l = f16(v - h), the same 128 bytes as 32 floats -- the operand format
-    // of k_attn16h; the q and k sections stay float32.  (The k | v-only tail that feeds the rows-only last layer keeps float32:
+    // of k_attn16's plane form; the q and k sections stay float32.  (The k | v-only tail that feeds the rows-only last layer keeps float32:
     // k_attn_row32 reads it.)
     int kv_planes;
     // SEQ instantiation (round 5, k_block_x6<.., SEQ = true>: the sequence-resident layer kernel).  A workgroup of eight waves owns
@@ -1724,7 +1722,7 @@ __device__ __forceinline__ unsigned int seq_diag_mask(int L, int qb, bool tgt, i
     if (pq >= k0_ && pq < k0_ + 16) pm |= 1u << (pq - k0_);
     return pm;
 }
-// one 16-query block of the sequence-resident kernel's attention (defined behind k_attn16h, whose mathematics it shares)
+// one 16-query block of the sequence-resident kernel's attention (defined behind k_attn16, whose plane form's mathematics it shares)
 __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, int PL, int L, int qb, unsigned int pm_diag, float tgt_add,
                                                bool tgt_ok, int pq, const float *qscr, float4 *of, bool store, int seq, SeqTarget &tg);
 // k and q of the sequence-resident attention are split into float16 planes as they are.  (Measured, profiles/r05/README.md: planes
@@ -1743,7 +1741,7 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
 #endif
 // SEQ layout of the dynamic LDS behind the ring and the parameter vectors (x6_seq_lds_bytes)
 #define X6_SEQ_VECS (256 + 12 * 32 * 4 + 384)   // floats: the parameter vectors + this layer's in-projection bias
-#define X6_SEQ_KIMG (3 * 16384 + X6_SEQ_VECS * 4)  // K image of ONE head: 256 token rows x 32 float32, chunk-swizzled (k_attn16h's)
+#define X6_SEQ_KIMG (3 * 16384 + X6_SEQ_VECS * 4)  // K image of ONE head: 256 token rows x 32 float32, chunk-swizzled (k_attn16's)
 #define X6_SEQ_VIMG (X6_SEQ_KIMG + 32768)        // V image: 2 float16 planes x 256 rows x 64 B
 #define X6_SEQ_SCR (X6_SEQ_VIMG + 32768)         // per wave: the q tile as [32 tokens][36] float32
 #define X6_SEQ_SCR_B 4608
@@ -4553,14 +4551,14 @@ __global__ void __launch_bounds__(256) k_attn_mfma(const float *__restrict__ qkv
 //   S^T[key][q] = K . Q^T : lane (q = lane%16, gq = lane/16) holds Q[q][8gq .. 8gq+7] (B operand) and reads
 //                 K[key][8gq .. 8gq+7] as two ds_read_b128 (A operand); C register r <-> key 4gq + r
 //   O^T[c][q] += V^T . P^T: the S accumulator is the B operand (register j <-> key 4gq + j); the A operand
-//                 V^T[c][4gq .. 4gq+3] is ONE ds_read_b128 from the transposed V image
+//                 V[4gq .. 4gq+3][c] comes from the row-major V image (float32 form), or both are split into float16
+//                 planes (PLANES; below)
 // A query block keeps ALL its score tiles in registers (<= MAXT tiles of 4 registers): the softmax is two-pass
 // (one max / shuffle pair per query block, no running rescale), the score tiles are independent MFMA chains and
 // P.V runs on four accumulators -- the online form's per-tile shuffle + rescale chain was the critical path.
-// LDS: K [L][32] with the 16-byte chunk index XOR (key&7)^((key>>3)&1), V^T [32][S] with S = 8 mod 16 floats --
-// both conflict-free for the four 16-lane groups ds_read_b128 is serviced in.  Keys in [L, 16 ceil(L/16)) of
-// the last tile carry p = 0; their K rows are zero-filled, their V^T columns are zero-filled up to S (a column
-// index >= S aliases the next row's first keys: finite values times 0).
+// LDS: K [L][32] with the 16-byte chunk index XOR (key&7)^((key>>3)&1): conflict-free for the four 16-lane groups
+// ds_read_b128 is serviced in; the V image per form (at the fill, below).  Keys in [L, 16 ceil(L/16)) of the last tile
+// carry p = 0; their K and V rows repeat row L - 1 (finite values times 0).
 // Sum / maximum over the four lanes that share lane & 15 (l, l ^ 16, l ^ 32, l ^ 48), every lane getting the result:
 // gfx950's v_permlane16_swap / v_permlane32_swap (vector ALU) instead of two ds_bpermute round trips through the LDS
 // crossbar, each awaited at once.  With both operands the same register, the swap leaves {rows 0,0,2,2} and
@@ -4579,12 +4577,6 @@ __device__ __forceinline__ float quad16_max(float v) {
     return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
 }
 
-__device__ __forceinline__ int attn16_vstride(int Lmax) {
-    int S = (Lmax + 7) & ~7;
-    if ((S & 15) != 8) S += 8;
-    return S;
-}
-
 // FAST (packed sequences: the plan guarantees at most ONE masked token below the diagonal, index padq[b]): an
 // off-diagonal tile is then unmasked unless it holds that token, so the per-pair mask words, the do/skip logic
 // and the live-tile bits of the general form reduce to two comparisons of the pair index with the block index.
@@ -4596,16 +4588,16 @@ __device__ unsigned long long g_attn_stamp[8 * 65536];
 #else
 #define ATTN_T(i_)
 #endif
-// DMA (round 4; the production form): K and V of the (sequence, head) go HBM -> LDS by LDS-DMA (global_load_lds_dwordx4), 8
-// whole 128-byte key rows per instruction, straight from the row-major q | k | v rows the layer kernel writes -- no VGPR
-// staging, no ds_write pass, no transposed copy.  The DMA writes LDS lane-linearly, so the two swizzles live on the SOURCE
-// side (lane (row jl, chunk p) fetches the row's chunk p ^ sw): K keeps its conflict-free ds_read_b128 image (sw = (key & 7)
-// ^ ((key >> 3) & 1)); V stays ROW-major [key][32] with the two 64-byte halves of a row exchanged on keys with bit 2 set
-// (sw = 4 ((key >> 2) & 1)): the O^T += V^T P^T step reads its A operand V[4 gq + j][16 ct + lq] as four ds_read_b32 (two
-// ds_read2_b32), and a 32-lane half (lane groups gq and gq + 1: keys 4 apart) then covers 32 distinct banks.  The register
-// form's transposed V^T image cost ~1K cycles of 8-way conflicted ds_write_b32 per wave and fill, its staging loads'
-// issue dominated a fill (39 % of a wave's life, profiles/r03/attn16_lab_stamps.txt), and PMC showed an LDS conflict
-// ratio of 0.47.  Keys in [L, L16) re-read row L - 1 (finite values times p = 0).
+// The fill (round 4): K and V of the (sequence, head) go HBM -> LDS by LDS-DMA (global_load_lds_dwordx4), 8 whole 128-byte key
+// rows per instruction, straight from the row-major q | k | v rows the layer kernel writes -- no VGPR staging, no ds_write pass,
+// no transposed copy.  The DMA writes LDS lane-linearly, so the swizzles live on the SOURCE side (lane (row jl, chunk p) fetches
+// the row's chunk p ^ sw): K keeps its conflict-free ds_read_b128 image (sw = (key & 7) ^ ((key >> 3) & 1)); a float32 V stays
+// ROW-major [key][32] with the two 64-byte halves of a row exchanged on keys with bit 2 set (sw = 4 ((key >> 2) & 1)): the
+// O^T += V^T P^T step reads its A operand V[4 gq + j][16 ct + lq] as four ds_read_b32 (two ds_read2_b32), and a 32-lane half
+// (lane groups gq and gq + 1: keys 4 apart) then covers 32 distinct banks.  Keys in [L, L16) re-read row L - 1 (finite values
+// times p = 0).  (Pruned: the register-staged fill with a transposed V^T image -- ~1K cycles of 8-way conflicted ds_write_b32
+// per wave and fill, its staging loads' issue 39 % of a wave's life, LDS conflict ratio 0.47 -- lost by 6 %:
+// profiles/r03/attn16_lab_stamps.txt, HISTORY.md.)
 // A score tile is consumed behind wave-uniform branches (pad in this tile? diagonal tile?).  The compiler pads the distance between a
 // matrix instruction and the first vector instruction that reads its result only along the fall-through path; on a taken edge the
 // reader may come too early -- the hardware does not interlock it, and whether it bites depends on how the wave was arbitrated
@@ -4615,106 +4607,152 @@ __device__ unsigned long long g_attn_stamp[8 * 65536];
 #define ATTN_MFMA_LANDED2(a_, b_) asm volatile("s_nop 7\n\ts_nop 3" : "+v"(a_), "+v"(b_));
 typedef __attribute__((address_space(3))) void attn_lds_void;
 typedef const __attribute__((address_space(1))) void attn_glb_void;
-// NW = waves per workgroup (4).  Measured and not kept (tools/attn_lab, profiles/r04/attn_lab_variants_r04.txt): NW = 8 -- the
-// same LDS images serving twice the waves, two workgroups per CU, four waves per SIMD -- is 45 % SLOWER (the block phase is
-// MFMA-issue bound at three waves per SIMD already: 94 % of the pipe's cycles while three waves are in their blocks); touching
-// the K / V rows of the workgroup 256 or 768 dispatch slots ahead with dropped loads (an L2 prefetch) is 4 % slower.
+// Four waves per workgroup.  Measured and not kept (profiles/r04/attn_lab_variants_r04.txt): 8 waves -- the same LDS images
+// serving twice the waves, two workgroups per CU, four waves per SIMD, blocks dealt by the run-time greedy loop -- is 45 % SLOWER
+// (the block phase is MFMA-issue bound at three waves per SIMD already: 94 % of the pipe's cycles while three waves are in their
+// blocks); touching the K / V rows of the workgroup 256 or 768 dispatch slots ahead with dropped loads (an L2 prefetch) is 4 %
+// slower.
 // Also measured and not kept: ONE workgroup for the four heads of a short sequence (wave = head, the other three workgroups
 // of the group returning at once): 227 vs 129 us on a batch of 40-token sequences -- a launch of short sequences is bound by
 // the rate at which workgroups are DISPATCHED (~8 ns per workgroup chip-wide: 16384 workgroups = 129 us whatever they do), and
 // workgroups that return at once are dispatched all the same.  What that regime needs is fewer dispatches: a persistent
 // grid over a work list built by the plan kernel (profiles/r04/README.md).
-template <int MAXT, bool FAST, bool DMA = false, int NW = 4>
-__global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) k_attn16(const float *__restrict__ qkv, const int64_t *__restrict__ seq,
-                                                const float *__restrict__ r_u, float *__restrict__ out, int Lmax, int d,
-                                                int mask_mode, const int32_t *__restrict__ off,
-                                                const int32_t *__restrict__ cnt, const int32_t *__restrict__ padq,
-                                                int out_frag, int H) {
-    static_assert(NW == 4 || DMA, "the register-staged fill is written for four waves");
+//
+// PLANES (round 4; k_attn16h until the two forms became one template): O^T += V^T P^T on the 16-bit matrix pipe the way the layer kernel's IRS_GEMM_H3 mode multiplies: two
+// FLOAT16 planes per float32 operand (h = f16(x), l = f16(x - h): 22 of 24 significand bits), three plane products (h.l, l.h, h.h)
+// on v_mfma_f32_16x16x32_f16 -- a pair of key tiles costs 6 matrix instructions of 16 cycles instead of 16 of 32.  The SCORES
+// stay on the exact float32 chain (v_mfma_f32_16x16x4_f32 on the float32 K image) in both forms: an error in a score is
+// exponentiated, and a first form with K and q on float16 planes as well -- 26-37 % faster in the lab -- was 1e-3 off on rows
+// whose logits are large (layer 0 of the synthetic models: |q||k| ~ 2000, so 2^-22 |q||k| is 5e-4 in the exponent); an error
+// in p or V is not amplified.  (Round 5 measured the three-product float16 form of the scores here again, K planes written by the
+// layer kernel's tail like V: the 6-layer decode of 4096 users 1.5 % faster only -- at three workgroups per CU this kernel is
+// bound by vector-instruction issue, not by the matrix pipe -- with the rows' maximum distance to the float32-MFMA kernels 8.3e-5
+// instead of 2.7e-5 and 2.7e-4 on a full decode's last-layer rows (test_throughput_shape_decode_matches_small_batches_and_oracle):
+// not kept.  The sequence-resident kernel, whose attention phase WAS matrix-pipe heavy at two waves per SIMD, keeps it: -9 %.)
+// What made the bf16 form of round 3 (k_attn16x) lose is gone:
+//   * V arrives ALREADY SPLIT: the layer kernel's q | k | v tail (k_block_x6, kv_planes) writes each (token, head) V
+//     row as [32 f16 h | 32 f16 l] -- the same 128 bytes as 32 floats -- so the fill is pure LDS-DMA (16 key rows x 64 B of
+//     one plane per instruction, chunks swizzled on the source side) and costs no vector instruction;
+//   * two planes are 256 B per key, the float32 images' footprint: three workgroups per CU as before;
+//   * p = exp2(s - m) is split into two planes (3 vector instructions per value: v_cvt_pk_f16_f32, back, subtract, again).
+// The plane images are [plane][key][64 B], V^T operands come by the transposing ds_read_b64_tr_b16, and the two score tiles of a
+// pair sit side by side as the 32-key B operand.
+typedef __attribute__((ext_vector_type(4))) short attn_s16x4; // operand type of the transposing LDS read
+__device__ __forceinline__ void attn_split8h(const float (&v)[8], x6_f16x8 (&P)[2]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const _Float16 h = (_Float16)v[j];
+        P[0][j] = h;
+        P[1][j] = (_Float16)(v[j] - (float)h);
+    }
+}
+// The head count for the fragment-major store: the float32 form takes it as an argument; the plane form, launched only over
+// (head, sequence) grids, reads the x extent of its grid (its argument is this empty struct: one byte behind out_frag).
+struct attn_grid_heads {
+    __device__ operator size_t() const { return gridDim.x; }
+};
+// One kernel, two forms.  Per form (PLANES) are only the V image and its fill, the V operand read with the P.V product, the
+// target column's V row, and WHERE the per-sequence scalars are read; everything else is stated once.
+template <int MAXT, bool FAST, bool PLANES>
+__global__ void __launch_bounds__(256, 3) k_attn16(const float *__restrict__ qkv, const int64_t *__restrict__ seq,
+                                                  const float *__restrict__ r_u, float *__restrict__ out, int Lmax, int d,
+                                                  int mask_mode, const int32_t *__restrict__ off,
+                                                  const int32_t *__restrict__ cnt, const int32_t *__restrict__ padq,
+                                                  int out_frag, std::conditional_t<PLANES, attn_grid_heads, int> H) {
     typedef __attribute__((ext_vector_type(4))) float f32x4;
     constexpr int HD = 32;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int S = attn16_vstride(Lmax);
-    const int Lcap16 = (Lmax + 15) & ~15;
-    float *const Vt0 = reinterpret_cast<float *>(smem);             // [32][S]   (DMA: V [Lmax rounded to 16][32], halves swizzled)
-    float *const Ks0 = Vt0 + (DMA ? Lcap16 * HD : 32 * S);          // [Lmax rounded to 16][32], swizzled chunks
-    unsigned int *padbits = reinterpret_cast<unsigned int *>(Ks0 + (size_t)Lcap16 * HD); // [ceil(L/32)] (+ the work item at word 12)
+    const bool irn = (mask_mode == IRS_MASK_IRN);
+    // ---- per-sequence scalars.  PLANES (always behind a plan when FAST: all the pointers exist) reads every one in ONE batch of
+    // loads up front: the form that read each where it was first used -- "cnt if present", "off if present", the pad index in
+    // front of the mask words, r_u and the target id behind the fill barrier -- was five dependent scalar round trips per wave,
+    // two of them behind the barrier.  The float32 form still reads each where it is first used.
+    int L_, pq_ = -1;
+    int64_t base_, last_id = 0;
+    float ru_ = 0.f;
+    if constexpr (PLANES) {
+        last_id = seq[(int64_t)blockIdx.y * Lmax + Lmax - 1];
+        if constexpr (FAST) {
+            L_ = cnt[blockIdx.y], base_ = (int64_t)off[blockIdx.y], pq_ = padq[blockIdx.y];
+            ru_ = (irn ? r_u : reinterpret_cast<const float *>(cnt))[blockIdx.y];
+        } else {
+            L_ = cnt ? cnt[blockIdx.y] : Lmax;
+            base_ = off ? (int64_t)off[blockIdx.y] : (int64_t)blockIdx.y * Lmax;
+            if (padq) pq_ = padq[blockIdx.y];
+            if (irn) ru_ = r_u[blockIdx.y];
+        }
+    }
+    // ---- LDS: the V image (float32 [key][32] with swizzled halves, or two float16 planes of [key][64 B]), K float32 [key][32]
+    // with swizzled chunks, the mask words -- 256 B per key in either form
+    const int L16max = (Lmax + 15) & ~15;
+    const int PL = L16max * 64; // bytes of one plane image
+    char *const Vp = smem;
+    float *const Vf = reinterpret_cast<float *>(smem);
+    const int VB = PLANES ? 2 * PL : L16max * HD * 4; // bytes of the V image, and of the K image
+    float *const Ks = reinterpret_cast<float *>(smem + VB);
+    unsigned int *const padbits = reinterpret_cast<unsigned int *>(smem + 2 * VB); // [ceil(L/32)]
+    const int h = blockIdx.x, b = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lq = lane & 15, gq = lane >> 4;
     const int ld = 3 * d;
-    const bool irn = (mask_mode == IRS_MASK_IRN);
-    const int h = blockIdx.x, b = blockIdx.y;
-    {
-    const int L = cnt ? cnt[b] : Lmax;
-    const int64_t base = off ? (int64_t)off[b] : (int64_t)b * Lmax;
+    if constexpr (!PLANES) {
+        L_ = cnt ? cnt[b] : Lmax;
+        base_ = off ? (int64_t)off[b] : (int64_t)b * Lmax;
+    }
+    const int L = L_;
+    const int64_t base = base_;
     const int L16 = (L + 15) & ~15, NB16 = L16 >> 4;
-    float *Vt = Vt0, *Ks = Ks0;
-    // gridDim.z > 1 (few sequences, the latency path): the query blocks of a (sequence, head) are dealt one per wave
-    // over 4 gridDim.z waves, largest first -- a wave's dependent chain is then one block instead of three, on
+    // gridDim.z > 1 (few sequences, the latency path; float32 form only): the query blocks of a (sequence, head) are dealt one
+    // per wave over 4 gridDim.z waves, largest first -- a wave's dependent chain is then one block instead of three, on
     // three times as many CUs.  Workgroup z owns blocks NB16-1-4z .. NB16-4-4z; each stages the whole K / V of the
     // (sequence, head) -- the loads of a fill are all in flight together, and the IRN target column needs key L-1.
     const int zsplit = blockIdx.z;
-    if (gridDim.z > 1 && 4 * zsplit >= NB16) return;
+    if (!PLANES && gridDim.z > 1 && 4 * zsplit >= NB16) return;
     if (L <= 0) return; // (a plan never yields an empty sequence: the consumed row always counts)
     ATTN_T(0);
-    if constexpr (DMA) {
+    // ---- the fill.  K, and a float32 V with it: 8 key rows x 128 B per instruction (the LDS destination is wave-uniform).  V
+    // planes: 16 key rows x 64 B of ONE plane per instruction (4 lanes per row), chunks swizzled by ((key >> 2) & 1) << 1 for the
+    // transposing reads; the pair partner of an odd last tile is not read at all (its operand half is zero).
+    {
         const int jl = lane >> 3, p = lane & 7;
-        for (int i = wave; i < (L16 >> 3); i += NW) { // 8 key rows per instruction; the LDS destination is wave-uniform
+        for (int i = wave; i < (L16 >> 3); i += 4) {
             const int j = 8 * i + jl;
             const float *row = qkv + (base + (j < L ? j : L - 1)) * ld + h * HD;
             const int swk = (j & 7) ^ ((j >> 3) & 1), swv = ((j >> 2) & 1) << 2;
             __builtin_amdgcn_global_load_lds((attn_glb_void *)(row + d + 4 * (p ^ swk)), (attn_lds_void *)(Ks + i * 256), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((attn_glb_void *)(row + 2 * d + 4 * (p ^ swv)), (attn_lds_void *)(Vt + i * 256), 16, 0, 0);
+            if constexpr (!PLANES)
+                __builtin_amdgcn_global_load_lds((attn_glb_void *)(row + 2 * d + 4 * (p ^ swv)), (attn_lds_void *)(Vf + i * 256), 16, 0, 0);
         }
     }
-    // K / V of this (sequence, head) -> LDS.  8 consecutive lanes take the 8 16-byte chunks of one key row, so a
-    // load instruction covers 8 whole 128-byte K_h (V_h) slices -- in-kernel timing showed the ISSUE of these
-    // loads, not their latency, dominating the fill when every lane touched a different row.  K's ds_write_b128
-    // stays conflict-free; the transposed V^T ds_write_b32 are 8-way conflicted (a row stride S = 8 mod 16 puts
-    // all 8 chunks of a key on one bank), ~1K cycles per wave once, cheaper than the slow loads were.  ALL global
-    // loads are issued before the first LDS store (one memory round trip per workgroup).
-    float4 kv[DMA ? 1 : MAXT / 2], vv[DMA ? 1 : MAXT / 2];
-    if constexpr (!DMA) {
-        const int jl = tid >> 3, c4 = tid & 7; // 8 lanes per key row: 128-byte contiguous K_h / V_h slices
+    if constexpr (PLANES) {
+        const char *qb8 = reinterpret_cast<const char *>(qkv);
+        const int jl = lane >> 2, c = lane & 3;
+        for (int i = wave; i < NB16; i += 4) {
+            const int j = 16 * i + jl;
+            const char *row = qb8 + ((base + (j < L ? j : L - 1)) * ld) * 4 + h * 128;
+            const int swv = ((j >> 2) & 1) << 1;
 #pragma unroll
-        for (int it = 0; it < MAXT / 2; ++it) {
-            const int j = jl + 32 * it;
-            kv[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-            vv[it] = kv[it];
-            if (j < L) {
-                const float *row = qkv + (base + j) * ld + h * HD + 4 * c4;
-                kv[it] = *reinterpret_cast<const float4 *>(row + d);
-                vv[it] = *reinterpret_cast<const float4 *>(row + 2 * d);
-            }
+            for (int p = 0; p < 2; ++p)
+                __builtin_amdgcn_global_load_lds((attn_glb_void *)(row + 2 * d * 4 + p * 64 + ((c ^ swv) << 4)),
+                                                 (attn_lds_void *)(Vp + p * PL + i * 1024), 16, 0, 0);
         }
     }
     ATTN_T(1);
     // (the assignment below and the first Q request run while the K / V rows are in flight)
-    // longest-first assignment of the 16-query blocks (block qb costs qb + 1 key tiles) to the 4 waves
+    // ---- longest-first assignment of the 16-query blocks (block qb costs qb + 1 key tiles) to the four waves.  With costs n, n - 1,
+    // .. the greedy rule (next block to the least loaded wave, ties to the lowest wave) deals the blocks 0 1 2 3 3 2 1 0 0 1 ..
+    // in descending order: the i-th largest block goes to wave i & 7 (< 4) or 7 - (i & 7) -- a constant bit pattern over i,
+    // reversed into block order (the loop form was ~150 instructions per wave; tests/test_host_logic.py checks the identity).
     unsigned int mine = 0;
-    if (gridDim.z > 1) {
+    if (!PLANES && gridDim.z > 1) {
         const int v = 4 * zsplit + wave;
         if (v < NB16) mine = 1u << (NB16 - 1 - v);
-    } else if constexpr (NW == 4) { // the closed form of the greedy deal below (k_attn16h; tests/test_host_logic.py holds the identity)
-        mine = __builtin_bitreverse32((0x01010101u << wave) | (0x01010101u << (7 - wave))) >> (32 - NB16);
     } else {
-        int load[NW];
-#pragma unroll
-        for (int w = 0; w < NW; ++w) load[w] = 0;
-        for (int qb = NB16 - 1; qb >= 0; --qb) {
-            int w = 0;
-#pragma unroll
-            for (int v = 1; v < NW; ++v)
-                if (load[v] < load[w]) w = v;
-#pragma unroll
-            for (int v = 0; v < NW; ++v) // (static indices: a run-time index would send the array to scratch)
-                if (v == w) load[v] += qb + 1;
-            if (w == wave) mine |= 1u << qb;
-        }
+        mine = __builtin_bitreverse32((0x01010101u << wave) | (0x01010101u << (7 - wave))) >> (32 - NB16);
     }
-    // Q of a query block: lane (q, gq) holds Q[q][8gq .. 8gq+7]; the next block's rows are requested one block
-    // ahead (the first one before the K / V fill) so their latency is never exposed
-    auto load_q = [&](int qb, float4 &t0, float4 &t1) {
+    // ---- Q of a query block: lane (q, gq) holds Q[q][8gq .. 8gq+7]; the next block's rows are requested one block
+    // ahead (the first one before the K / V fill has landed) so their latency is never exposed
+    auto load_q = [&](int qb, float4 &t0, float4 &t1) __attribute__((always_inline)) {
         const int qi = qb * 16 + lq;
         const float *qrow = qkv + (base + (qi < L ? qi : L - 1)) * ld + h * HD + 8 * gq;
         t0 = *reinterpret_cast<const float4 *>(qrow);
@@ -4723,11 +4761,11 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) k_attn16(const float
     float4 qn0 = make_float4(0.f, 0.f, 0.f, 0.f), qn1 = qn0;
     int qb_next = mine ? 31 - __builtin_clz(mine) : -1;
     if (qb_next >= 0) load_q(qb_next, qn0, qn1);
-    // masked-key bitmask of each 32-key block.  A packed sequence holds no pads except possibly its pos token
+    // ---- masked-key bitmask of each 32-key block.  A packed sequence holds no pads except possibly its pos token
     // (index padq[b], recorded by the plan): no global loads on that path.
-    const int pq = padq ? padq[b] : -1;
-    const bool tgt_ok = irn && (seq[(int64_t)b * Lmax + Lmax - 1] != 0);
-    for (int kb = wave; kb < (L + 31) / 32; kb += NW) {
+    const int pq = PLANES ? pq_ : (padq ? padq[b] : -1);
+    const bool tgt_ok = irn && ((PLANES ? last_id : seq[(int64_t)b * Lmax + Lmax - 1]) != 0);
+    for (int kb = wave; kb < (L + 31) / 32; kb += 4) {
         const int j = kb * 32 + (lane & 31);
         bool masked = (j >= L) || (tgt_ok && j == L - 1); // (the last key is the target column only where the window has a target item: without one it is the last history item, a causal key like any other -- k_attn_row's rule)
         if (padq) masked = masked || (j == pq);
@@ -4735,24 +4773,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) k_attn16(const float
         const unsigned long long bal = __ballot(masked);
         if (lane == 0) padbits[kb] = (unsigned int)bal;
     }
-    if constexpr (DMA) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's DMA pieces have landed (the barrier below publishes them)
-    } else {
-        const int jl = tid >> 3, c4 = tid & 7;
-#pragma unroll
-        for (int it = 0; it < MAXT / 2; ++it) {
-            const int j = jl + 32 * it;
-            if (j < L16) {
-                *reinterpret_cast<float4 *>(Ks + j * HD + ((c4 ^ (j & 7) ^ ((j >> 3) & 1)) << 2)) = kv[it];
-                if (j < S) {
-                    Vt[(4 * c4 + 0) * S + j] = vv[it].x;
-                    Vt[(4 * c4 + 1) * S + j] = vv[it].y;
-                    Vt[(4 * c4 + 2) * S + j] = vv[it].z;
-                    Vt[(4 * c4 + 3) * S + j] = vv[it].w;
-                }
-            }
-        }
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's DMA pieces have landed (the barrier below publishes them)
     ATTN_T(2);
     __syncthreads();
     ATTN_T(3);
@@ -4760,8 +4781,10 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) k_attn16(const float
     // mask's "+ r_u on every allowed key" is applied as "- r_u on the target column" instead (softmax is
     // shift-invariant over the unmasked keys): two VALU operations per score fewer.
     const float LOG2E = 1.4426950408889634f;
-    const float tgt_add = irn ? (1.0f - r_u[b]) * LOG2E : 0.f;
+    const float tgt_add = irn ? (1.0f - (PLANES ? ru_ : r_u[b])) * LOG2E : 0.f;
     const float scale = LOG2E / sqrtf((float)HD);
+    // (PLANES) this lane's transposed V read: block row (lane & 15) >> 2, columns 16 ct + 4 (lane & 3) ..
+    const int tq = (lane & 15) >> 2, tp = lane & 3;
 
     while (qb_next >= 0) {
         const int qb = qb_next;
@@ -4776,344 +4799,8 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : 3) k_attn16(const float
             qf[0] = t0.x * sc, qf[1] = t0.y * sc, qf[2] = t0.z * sc, qf[3] = t0.w * sc;
             qf[4] = t1.x * sc, qf[5] = t1.y * sc, qf[6] = t1.z * sc, qf[7] = t1.w * sc;
         }
-        // ---- pass 1: every visible score tile of this query block, masked, with the running maximum
-        f32x4 sacc[MAXT];
-        float mx = -INFINITY;
-        auto score_tile = [&](int kt, f32x4 &sa) {
-            const int key = kt * 16 + lq;
-            const float *kr = Ks + key * HD;
-            const int sw = (key & 7) ^ ((key >> 3) & 1);
-            const float4 k0 = *reinterpret_cast<const float4 *>(kr + (((2 * gq) ^ sw) << 2));
-            const float4 k1 = *reinterpret_cast<const float4 *>(kr + (((2 * gq + 1) ^ sw) << 2));
-            sa = {0.f, 0.f, 0.f, 0.f};
-            sa = __builtin_amdgcn_mfma_f32_16x16x4f32(k0.x, qf[0], sa, 0, 0, 0);
-            sa = __builtin_amdgcn_mfma_f32_16x16x4f32(k0.y, qf[1], sa, 0, 0, 0);
-            sa = __builtin_amdgcn_mfma_f32_16x16x4f32(k0.z, qf[2], sa, 0, 0, 0);
-            sa = __builtin_amdgcn_mfma_f32_16x16x4f32(k0.w, qf[3], sa, 0, 0, 0);
-            sa = __builtin_amdgcn_mfma_f32_16x16x4f32(k1.x, qf[4], sa, 0, 0, 0);
-            sa = __builtin_amdgcn_mfma_f32_16x16x4f32(k1.y, qf[5], sa, 0, 0, 0);
-            sa = __builtin_amdgcn_mfma_f32_16x16x4f32(k1.z, qf[6], sa, 0, 0, 0);
-            sa = __builtin_amdgcn_mfma_f32_16x16x4f32(k1.w, qf[7], sa, 0, 0, 0);
-        };
-        auto mask_tile = [&](int kt, unsigned int pm, f32x4 &sa) {
-            ATTN_MFMA_LANDED(sa)
-            if (pm == 0u && kt < qb) { // clean off-diagonal tile: no masking
-                mx = fmaxf(fmaxf(mx, sa[0]), fmaxf(sa[1], fmaxf(sa[2], sa[3])));
-            } else {
-                const unsigned int pmk = pm >> (4 * gq);
-                const int qlim = (kt < qb) ? 64 : lq - 4 * gq; // key index within the tile, minus 4gq, must be <= qlim
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const bool ok = !((pmk >> r) & 1u) && (r <= qlim);
-                    const float v = ok ? sa[r] : -INFINITY;
-                    sa[r] = v;
-                    mx = fmaxf(mx, v);
-                }
-            }
-        };
-        unsigned int live = 0; // tiles with at least one unmasked key (wave-uniform)
-        if (FAST) {
-            const int pq_pair = pq >= 0 ? pq >> 5 : -1; // tile pair / lane group / register holding the one masked token
-            auto pad_fix = [&](int kt, f32x4 &sa) {
-                if ((pq >> 4) == kt) {
-                    const bool mine = ((pq >> 2) & 3) == gq;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) sa[r] = (mine && (pq & 3) == r) ? -INFINITY : sa[r];
-                }
-            };
-            const unsigned int pm_diag = (padbits[qb >> 1] >> (16 * (qb & 1))) & 0xFFFFu;
-            // (pairs in groups of two under one guard: a block of few tiles does not walk every pair's own comparisons)
-#pragma unroll
-            for (int kg = 0; kg < MAXT / 4; ++kg) {
-            if (4 * kg <= qb) {
-#pragma unroll
-            for (int kp = 2 * kg; kp < 2 * kg + 2; ++kp) {
-                const int k0t = 2 * kp, k1t = 2 * kp + 1;
-                if (k1t <= qb) { // two independent MFMA chains; tile k0t lies below the diagonal
-                    score_tile(k0t, sacc[k0t]);
-                    score_tile(k1t, sacc[k1t]);
-                    ATTN_MFMA_LANDED2(sacc[k0t], sacc[k1t])
-                    if (kp == pq_pair) {
-                        pad_fix(k0t, sacc[k0t]);
-                        if (k1t < qb) pad_fix(k1t, sacc[k1t]);
-                    }
-                    mx = fmaxf(fmaxf(mx, sacc[k0t][0]), fmaxf(sacc[k0t][1], fmaxf(sacc[k0t][2], sacc[k0t][3])));
-                    if (k1t < qb) mx = fmaxf(fmaxf(mx, sacc[k1t][0]), fmaxf(sacc[k1t][1], fmaxf(sacc[k1t][2], sacc[k1t][3])));
-                    else mask_tile(k1t, pm_diag, sacc[k1t]);
-                } else if (k0t == qb) {
-                    score_tile(k0t, sacc[k0t]);
-                    mask_tile(k0t, pm_diag, sacc[k0t]);
-                }
-            }
-            }
-            }
-            live = (2u << qb) - 1u;
-        } else {
-#pragma unroll
-        for (int kp = 0; kp < MAXT / 2; ++kp) {
-            const int k0t = 2 * kp, k1t = 2 * kp + 1;
-            const unsigned int pw = (k0t <= qb) ? padbits[kp] : 0xFFFFFFFFu;
-            const unsigned int pm0 = pw & 0xFFFFu, pm1 = pw >> 16;
-            const bool do0 = pm0 != 0xFFFFu, do1 = (k1t <= qb) && pm1 != 0xFFFFu;
-            if (do0 && do1) { // two independent MFMA chains
-                score_tile(k0t, sacc[k0t]);
-                score_tile(k1t, sacc[k1t]);
-                mask_tile(k0t, pm0, sacc[k0t]);
-                mask_tile(k1t, pm1, sacc[k1t]);
-                live |= 3u << k0t;
-            } else if (do0) {
-                score_tile(k0t, sacc[k0t]);
-                mask_tile(k0t, pm0, sacc[k0t]);
-                live |= 1u << k0t;
-            } else if (do1) {
-                score_tile(k1t, sacc[k1t]);
-                mask_tile(k1t, pm1, sacc[k1t]);
-                live |= 2u << k0t;
-            }
-        }
-        }
-        // ---- the IRN target column (key L-1, +1.0, visible to every query): s = q . K[L-1] + 1.0
-        float st = -INFINITY;
-        if (tgt_ok) {
-            const int jt = L - 1;
-            const float *kr = Ks + jt * HD;
-            const int sw = (jt & 7) ^ ((jt >> 3) & 1);
-            const float4 k0 = *reinterpret_cast<const float4 *>(kr + (((2 * gq) ^ sw) << 2));
-            const float4 k1 = *reinterpret_cast<const float4 *>(kr + (((2 * gq + 1) ^ sw) << 2));
-            float part = qf[0] * k0.x;
-            part = __fmaf_rn(qf[1], k0.y, part);
-            part = __fmaf_rn(qf[2], k0.z, part);
-            part = __fmaf_rn(qf[3], k0.w, part);
-            part = __fmaf_rn(qf[4], k1.x, part);
-            part = __fmaf_rn(qf[5], k1.y, part);
-            part = __fmaf_rn(qf[6], k1.z, part);
-            part = __fmaf_rn(qf[7], k1.w, part);
-            st = quad16_sum(part) + tgt_add;
-        }
-        mx = quad16_max(mx);
-        float m = fmaxf(mx, st);
-        if (m == -INFINITY) m = 0.f; // nothing visible: every exp2(-inf - 0) is 0, l = 0 -> NaN row like torch
-        // ---- pass 2: p = exp(s - m), O^T += V^T P^T on four accumulators (tile parity x column tile)
-        float l = 0.f;
-        f32x4 o[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[i][ct][r] = 0.f;
-        if (tgt_ok) {
-            const float pt = __builtin_amdgcn_exp2f(st - m);
-            l = (gq == 0) ? pt : 0.f; // the four lanes of a query are summed at the end
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct) {
-                if constexpr (DMA) {
-                    const int jt = L - 1;
-                    const float4 vt4 = *reinterpret_cast<const float4 *>(Vt + jt * HD + (((4 * ct + gq) ^ (((jt >> 2) & 1) << 2)) << 2));
-                    o[0][ct][0] = pt * vt4.x, o[0][ct][1] = pt * vt4.y, o[0][ct][2] = pt * vt4.z, o[0][ct][3] = pt * vt4.w;
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o[0][ct][r] = pt * Vt[(16 * ct + 4 * gq + r) * S + L - 1];
-                }
-            }
-        }
-#pragma unroll
-        for (int kg = 0; kg < MAXT / 4; ++kg) {
-        if (!FAST || 4 * kg <= qb) { // FAST: tiles in groups of four under one guard
-#pragma unroll
-        for (int kt = 4 * kg; kt < 4 * kg + 4; ++kt) {
-            if (FAST ? (kt <= qb) : ((live >> kt) & 1u) != 0u) { // wave-uniform; tiles beyond qb are never live
-                f32x4 pa;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float pv = __builtin_amdgcn_exp2f(sacc[kt][r] - m);
-                    pa[r] = pv;
-                    l += pv;
-                }
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct) {
-                    float4 v4;
-                    if constexpr (DMA) { // V[kt 16 + 4 gq + j][16 ct + lq], j = 0 .. 3 (rows 128 bytes apart)
-                        const float *vb = Vt + (kt * 16 + 4 * gq) * HD + ((16 * ct + lq) ^ ((gq & 1) << 4));
-                        v4 = make_float4(vb[0], vb[HD], vb[2 * HD], vb[3 * HD]);
-                    } else
-                        v4 = *reinterpret_cast<const float4 *>(Vt + (16 * ct + lq) * S + kt * 16 + 4 * gq);
-                    f32x4 oo = o[kt & 1][ct];
-                    oo = __builtin_amdgcn_mfma_f32_16x16x4f32(v4.x, pa[0], oo, 0, 0, 0);
-                    oo = __builtin_amdgcn_mfma_f32_16x16x4f32(v4.y, pa[1], oo, 0, 0, 0);
-                    oo = __builtin_amdgcn_mfma_f32_16x16x4f32(v4.z, pa[2], oo, 0, 0, 0);
-                    oo = __builtin_amdgcn_mfma_f32_16x16x4f32(v4.w, pa[3], oo, 0, 0, 0);
-                    o[kt & 1][ct] = oo;
-                }
-            }
-        }
-        }
-        }
-        const float lt = quad16_sum(l);
-        const float inv = 1.0f / lt; // 0 (fully masked) -> inf, 0 * inf = NaN like torch
-        if (qi < L) {
-            if (out_frag) { // fragment-major image (d = 128: column block tn = head): the fused block kernel's B operand
-                const int64_t tk = base + qi;
-                float4 *of = reinterpret_cast<float4 *>(out) + ((size_t)(tk >> 5) * H + h) * 4 * 64 + (gq & 1) * 32 + (tk & 31);
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct)
-                    of[(2 * ct + (gq >> 1)) * 64] =
-                        make_float4((o[0][ct][0] + o[1][ct][0]) * inv, (o[0][ct][1] + o[1][ct][1]) * inv,
-                                    (o[0][ct][2] + o[1][ct][2]) * inv, (o[0][ct][3] + o[1][ct][3]) * inv);
-            } else {
-                float *orow = out + (base + qi) * d + h * HD + 4 * gq;
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct)
-                    *reinterpret_cast<float4 *>(orow + 16 * ct) =
-                        make_float4((o[0][ct][0] + o[1][ct][0]) * inv, (o[0][ct][1] + o[1][ct][1]) * inv,
-                                    (o[0][ct][2] + o[1][ct][2]) * inv, (o[0][ct][3] + o[1][ct][3]) * inv);
-            }
-        }
-    }
-    ATTN_T(4);
-    } // work items
-}
-
-// ------------------------------------------------------------------ attention, head dim 32, split-float16 MFMAs (round 4)
-// k_attn16 with O^T += V^T P^T on the 16-bit matrix pipe the way the layer kernel's IRS_GEMM_H3 mode multiplies: two FLOAT16
-// planes per float32 operand (h = f16(x), l = f16(x - h): 22 of 24 significand bits), three plane products (h.l, l.h, h.h)
-// on v_mfma_f32_16x16x32_f16 -- a pair of key tiles costs 6 matrix instructions of 16 cycles instead of 16 of 32.  The SCORES
-// stay on the exact float32 chain (v_mfma_f32_16x16x4_f32 on a float32 K image, as in k_attn16): an error in a score is
-// exponentiated, and a first form with K and q on float16 planes as well -- 26-37 % faster in the lab -- was 1e-3 off on rows
-// whose logits are large (layer 0 of the synthetic models: |q||k| ~ 2000, so 2^-22 |q||k| is 5e-4 in the exponent); an error
-// in p or V is not amplified.  (Round 5 measured the three-product float16 form of the scores here again, K planes written by the
-// layer kernel's tail like V: the 6-layer decode of 4096 users 1.5 % faster only -- at three workgroups per CU this kernel is
-// bound by vector-instruction issue, not by the matrix pipe -- with the rows' maximum distance to the float32-MFMA kernels 8.3e-5
-// instead of 2.7e-5 and 2.7e-4 on a full decode's last-layer rows (test_throughput_shape_decode_matches_small_batches_and_oracle):
-// not kept.  The sequence-resident kernel, whose attention phase WAS matrix-pipe heavy at two waves per SIMD, keeps it: -9 %.)
-// What made the bf16 form of round 3 (k_attn16x) lose is gone:
-//   * V arrives ALREADY SPLIT: the layer kernel's q | k | v tail (k_block_x6, kv_planes) writes each (token, head) V
-//     row as [32 f16 h | 32 f16 l] -- the same 128 bytes as 32 floats -- so the fill is pure LDS-DMA (16 key rows x 64 B of
-//     one plane per instruction, chunks swizzled on the source side) and costs no vector instruction;
-//   * two planes are 256 B per key, the float32 images' footprint: three workgroups per CU as before;
-//   * p = exp2(s - m) is split into two planes (3 vector instructions per value: v_cvt_pk_f16_f32, back, subtract, again).
-// Everything else is k_attn16x's structure: [plane][key][64 B] images, V in front of K, V^T operands by the transposing
-// ds_read_b64_tr_b16, the two score tiles of a pair side by side as the 32-key B operand, two-pass softmax, LPT blocks.
-typedef __attribute__((ext_vector_type(4))) short attn_s16x4; // operand type of the transposing LDS read
-__device__ __forceinline__ void attn_split8h(const float (&v)[8], x6_f16x8 (&P)[2]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const _Float16 h = (_Float16)v[j];
-        P[0][j] = h;
-        P[1][j] = (_Float16)(v[j] - (float)h);
-    }
-}
-template <int MAXT, bool FAST, int NW>
-__global__ void __launch_bounds__(64 * NW, 3) k_attn16h(const float *__restrict__ qkv, const int64_t *__restrict__ seq,
-                                                       const float *__restrict__ r_u, float *__restrict__ out, int Lmax, int d,
-                                                       int mask_mode, const int32_t *__restrict__ off,
-                                                       const int32_t *__restrict__ cnt, const int32_t *__restrict__ padq,
-                                                       int out_frag) {
-    typedef __attribute__((ext_vector_type(4))) float f32x4;
-    constexpr int HD = 32;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    // every per-sequence scalar of the kernel in ONE batch of loads (packed form: all the pointers exist).  The form that read
-    // each where it was first used -- "cnt if present", "off if present", the pad index in front of the mask words, r_u and the
-    // target id behind the fill barrier -- was five dependent scalar round trips per wave, two of them behind the barrier.
-    const bool irn = (mask_mode == IRS_MASK_IRN);
-    int L_, pq_ = -1;
-    int64_t base_;
-    float ru_ = 0.f;
-    const int64_t last_id = seq[(int64_t)blockIdx.y * Lmax + Lmax - 1];
-    if constexpr (FAST) {
-        L_ = cnt[blockIdx.y], base_ = (int64_t)off[blockIdx.y], pq_ = padq[blockIdx.y];
-        ru_ = (irn ? r_u : reinterpret_cast<const float *>(cnt))[blockIdx.y];
-    } else {
-        L_ = cnt ? cnt[blockIdx.y] : Lmax;
-        base_ = off ? (int64_t)off[blockIdx.y] : (int64_t)blockIdx.y * Lmax;
-        if (padq) pq_ = padq[blockIdx.y];
-        if (irn) ru_ = r_u[blockIdx.y];
-    }
-    const int L = L_;
-    const int L16max = (Lmax + 15) & ~15;
-    const int PL = L16max * 64;                 // bytes of one plane image
-    char *Vp = smem;                            // V: [2 planes][L16][64 B]
-    float *Ks = reinterpret_cast<float *>(smem + 2 * PL); // K: float32 [L16][32], chunk-swizzled like k_attn16's (256 B per key in all)
-    unsigned int *padbits = reinterpret_cast<unsigned int *>(smem + 4 * PL); // [ceil(L/32)]
-    const int h = blockIdx.x, b = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lq = lane & 15, gq = lane >> 4;
-    const int64_t base = base_;
-    const int ld = 3 * d;
-    const int L16 = (L + 15) & ~15, NB16 = L16 >> 4;
-    if (L <= 0) return;
-    // Fill by LDS-DMA.  K: float32 rows, 8 key rows x 128 B per instruction, chunk p of key j from source chunk p ^ (j & 7) ^
-    // ((j >> 3) & 1) (k_attn16's conflict-free ds_read_b128 image).  V: the two float16 planes the layer kernel wrote, 16 key
-    // rows x 64 B of ONE plane per instruction (4 lanes per row), chunks swizzled by ((key >> 2) & 1) << 1 for the transposing
-    // reads.  Keys in [L, L16) re-read row L - 1 (finite values times p = 0); the pair partner of an odd last tile is not
-    // read at all (its operand half is zero).
-    {
-        const char *qb8 = reinterpret_cast<const char *>(qkv);
-        const int jl8 = lane >> 3, p8 = lane & 7;
-        for (int i = wave; i < (L16 >> 3); i += NW) {
-            const int j = 8 * i + jl8;
-            const float *row = qkv + (base + (j < L ? j : L - 1)) * ld + h * HD;
-            const int swk = (j & 7) ^ ((j >> 3) & 1);
-            __builtin_amdgcn_global_load_lds((attn_glb_void *)(row + d + 4 * (p8 ^ swk)), (attn_lds_void *)(Ks + i * 256), 16, 0, 0);
-        }
-        const int jl = lane >> 2, c = lane & 3;
-        for (int i = wave; i < NB16; i += NW) {
-            const int j = 16 * i + jl;
-            const char *row = qb8 + ((base + (j < L ? j : L - 1)) * ld) * 4 + h * 128;
-            const int swv = ((j >> 2) & 1) << 1;
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-                __builtin_amdgcn_global_load_lds((attn_glb_void *)(row + 2 * d * 4 + p * 64 + ((c ^ swv) << 4)),
-                                                 (attn_lds_void *)(Vp + p * PL + i * 1024), 16, 0, 0);
-        }
-    }
-    // longest-first assignment of the 16-query blocks (block qb costs qb + 1 key tiles) to the four waves.  With costs n, n - 1,
-    // .. the greedy rule (next block to the least loaded wave, ties to the lowest wave) deals the blocks 0 1 2 3 3 2 1 0 0 1 ..
-    // in descending order: the i-th largest block goes to wave i & 7 (< 4) or 7 - (i & 7) -- a constant bit pattern over i,
-    // reversed into block order (the loop form was ~150 instructions per wave; tests/test_host_logic.py checks the identity).
-    static_assert(NW == 4, "the closed form of the longest-first deal");
-    unsigned int mine = __builtin_bitreverse32((0x01010101u << wave) | (0x01010101u << (7 - wave))) >> (32 - NB16);
-    auto load_q = [&](int qb, float4 &t0, float4 &t1) {
-        const int qi = qb * 16 + lq;
-        const float *qrow = qkv + (base + (qi < L ? qi : L - 1)) * ld + h * HD + 8 * gq;
-        t0 = *reinterpret_cast<const float4 *>(qrow);
-        t1 = *reinterpret_cast<const float4 *>(qrow + 4);
-    };
-    float4 qn0 = make_float4(0.f, 0.f, 0.f, 0.f), qn1 = qn0;
-    int qb_next = mine ? 31 - __builtin_clz(mine) : -1;
-    if (qb_next >= 0) load_q(qb_next, qn0, qn1);
-    const int pq = pq_;
-    const bool tgt_ok = irn && (last_id != 0);
-    for (int kb = wave; kb < (L + 31) / 32; kb += NW) {
-        const int j = kb * 32 + (lane & 31);
-        bool masked = (j >= L) || (tgt_ok && j == L - 1); // (the last key is the target column only where the window has a target item: without one it is the last history item, a causal key like any other -- k_attn_row's rule)
-        if (padq) masked = masked || (j == pq);
-        else masked = masked || (seq[base + (j < L ? j : L - 1)] == 0);
-        const unsigned long long bal = __ballot(masked);
-        if (lane == 0) padbits[kb] = (unsigned int)bal;
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's DMA pieces have landed (the barrier publishes them)
-    __syncthreads();
-    const float LOG2E = 1.4426950408889634f;
-    const float tgt_add = irn ? (1.0f - ru_) * LOG2E : 0.f;
-    const float scale = LOG2E / sqrtf((float)HD);
-    // this lane's addresses: K row read (key = 16 kt + lq, chunk gq), V transposed read (block row (lane & 15) >> 2, columns
-    // 16 ct + 4 (lane & 3) ..)
-    const int tq = (lane & 15) >> 2, tp = lane & 3;
-
-    while (qb_next >= 0) {
-        const int qb = qb_next;
-        mine &= ~(1u << qb);
-        const int qi = qb * 16 + lq;
-        float qf[8];
-        {
-            const float4 t0 = qn0, t1 = qn1;
-            qb_next = mine ? 31 - __builtin_clz(mine) : -1;
-            if (qb_next >= 0) load_q(qb_next, qn0, qn1);
-            const float sc = qi < L ? scale : 0.f;
-            qf[0] = t0.x * sc, qf[1] = t0.y * sc, qf[2] = t0.z * sc, qf[3] = t0.w * sc;
-            qf[4] = t1.x * sc, qf[5] = t1.y * sc, qf[6] = t1.z * sc, qf[7] = t1.w * sc;
-        }
+        // ---- pass 1: every visible score tile of this query block, masked, with the running maximum.
+        //   S^T[key][q] = K . Q^T on the exact float32 chain, in both forms
         f32x4 sacc[MAXT];
         float mx = -INFINITY;
         auto score_tile = [&](int kt, f32x4 &sa) __attribute__((always_inline)) {
@@ -5132,13 +4819,16 @@ __global__ void __launch_bounds__(64 * NW, 3) k_attn16h(const float *__restrict_
             sa = __builtin_amdgcn_mfma_f32_16x16x4f32(k1.z, qf[6], sa, 0, 0, 0);
             sa = __builtin_amdgcn_mfma_f32_16x16x4f32(k1.w, qf[7], sa, 0, 0, 0);
         };
+        auto tile_max = [&](const f32x4 &sa) __attribute__((always_inline)) {
+            mx = fmaxf(fmaxf(mx, sa[0]), fmaxf(sa[1], fmaxf(sa[2], sa[3])));
+        };
         auto mask_tile = [&](int kt, unsigned int pm, f32x4 &sa) __attribute__((always_inline)) {
             ATTN_MFMA_LANDED(sa)
-            if (pm == 0u && kt < qb) {
-                mx = fmaxf(fmaxf(mx, sa[0]), fmaxf(sa[1], fmaxf(sa[2], sa[3])));
+            if (pm == 0u && kt < qb) { // clean off-diagonal tile: no masking
+                tile_max(sa);
             } else {
                 const unsigned int pmk = pm >> (4 * gq);
-                const int qlim = (kt < qb) ? 64 : lq - 4 * gq;
+                const int qlim = (kt < qb) ? 64 : lq - 4 * gq; // key index within the tile, minus 4gq, must be <= qlim
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const bool ok = !((pmk >> r) & 1u) && (r <= qlim);
@@ -5148,9 +4838,9 @@ __global__ void __launch_bounds__(64 * NW, 3) k_attn16h(const float *__restrict_
                 }
             }
         };
-        unsigned int live = 0;
+        unsigned int live = 0; // tiles with at least one unmasked key (wave-uniform)
         if (FAST) {
-            const int pq_pair = pq >= 0 ? pq >> 5 : -1;
+            const int pq_pair = pq >= 0 ? pq >> 5 : -1; // tile pair / lane group / register holding the one masked token
             auto pad_fix = [&](int kt, f32x4 &sa) __attribute__((always_inline)) {
                 if ((pq >> 4) == kt) {
                     const bool mine_ = ((pq >> 2) & 3) == gq;
@@ -5159,13 +4849,14 @@ __global__ void __launch_bounds__(64 * NW, 3) k_attn16h(const float *__restrict_
                 }
             };
             const unsigned int pm_diag = (padbits[qb >> 1] >> (16 * (qb & 1))) & 0xFFFFu;
+            // (pairs in groups of two under one guard: a block of few tiles does not walk every pair's own comparisons)
 #pragma unroll
             for (int kg = 0; kg < MAXT / 4; ++kg) {
                 if (4 * kg <= qb) {
 #pragma unroll
                     for (int kp = 2 * kg; kp < 2 * kg + 2; ++kp) {
                         const int k0t = 2 * kp, k1t = 2 * kp + 1;
-                        if (k1t <= qb) {
+                        if (k1t <= qb) { // two independent MFMA chains; tile k0t lies below the diagonal
                             score_tile(k0t, sacc[k0t]);
                             score_tile(k1t, sacc[k1t]);
                             ATTN_MFMA_LANDED2(sacc[k0t], sacc[k1t])
@@ -5173,8 +4864,8 @@ __global__ void __launch_bounds__(64 * NW, 3) k_attn16h(const float *__restrict_
                                 pad_fix(k0t, sacc[k0t]);
                                 if (k1t < qb) pad_fix(k1t, sacc[k1t]);
                             }
-                            mx = fmaxf(fmaxf(mx, sacc[k0t][0]), fmaxf(sacc[k0t][1], fmaxf(sacc[k0t][2], sacc[k0t][3])));
-                            if (k1t < qb) mx = fmaxf(fmaxf(mx, sacc[k1t][0]), fmaxf(sacc[k1t][1], fmaxf(sacc[k1t][2], sacc[k1t][3])));
+                            tile_max(sacc[k0t]);
+                            if (k1t < qb) tile_max(sacc[k1t]);
                             else mask_tile(k1t, pm_diag, sacc[k1t]);
                         } else if (k0t == qb) {
                             score_tile(k0t, sacc[k0t]);
@@ -5191,21 +4882,37 @@ __global__ void __launch_bounds__(64 * NW, 3) k_attn16h(const float *__restrict_
                 const unsigned int pw = (k0t <= qb) ? padbits[kp] : 0xFFFFFFFFu;
                 const unsigned int pm0 = pw & 0xFFFFu, pm1 = pw >> 16;
                 const bool do0 = pm0 != 0xFFFFu, do1 = (k1t <= qb) && pm1 != 0xFFFFu;
-                if (do0) {
+                if constexpr (PLANES) {
+                    if (do0) {
+                        score_tile(k0t, sacc[k0t]);
+                        mask_tile(k0t, pm0, sacc[k0t]);
+                        live |= 1u << k0t;
+                    }
+                    if (do1) {
+                        score_tile(k1t, sacc[k1t]);
+                        mask_tile(k1t, pm1, sacc[k1t]);
+                        live |= 2u << k0t;
+                    }
+                } else if (do0 && do1) { // two independent MFMA chains
+                    score_tile(k0t, sacc[k0t]);
+                    score_tile(k1t, sacc[k1t]);
+                    mask_tile(k0t, pm0, sacc[k0t]);
+                    mask_tile(k1t, pm1, sacc[k1t]);
+                    live |= 3u << k0t;
+                } else if (do0) {
                     score_tile(k0t, sacc[k0t]);
                     mask_tile(k0t, pm0, sacc[k0t]);
                     live |= 1u << k0t;
-                }
-                if (do1) {
+                } else if (do1) {
                     score_tile(k1t, sacc[k1t]);
                     mask_tile(k1t, pm1, sacc[k1t]);
                     live |= 2u << k0t;
                 }
             }
         }
-        // ---- the IRN target column (key L-1, +1.0, visible to every query): float32 arithmetic on the summed planes
+        // ---- the IRN target column (key L-1, +1.0, visible to every query): s = q . K[L-1] + 1.0 in float32 arithmetic
         float st = -INFINITY;
-        float vt[8]; // V[L-1][16 ct + 4 gq + r], ct = 0, 1
+        float vt[8]; // (PLANES) V[L-1][16 ct + 4 gq + r], ct = 0, 1: the two planes summed
         if (tgt_ok) {
             const int jt = L - 1;
             const float *kr = Ks + jt * HD;
@@ -5221,19 +4928,22 @@ __global__ void __launch_bounds__(64 * NW, 3) k_attn16h(const float *__restrict_
             part = __fmaf_rn(qf[6], k1.z, part);
             part = __fmaf_rn(qf[7], k1.w, part);
             st = quad16_sum(part) + tgt_add;
+            if constexpr (PLANES) {
 #pragma unroll
-            for (int ct = 0; ct < 2; ++ct) { // columns 16 ct + 4 gq .. + 3: chunk 2 ct + (gq >> 1), half gq & 1
-                typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-                const char *vr = Vp + jt * 64 + ((((2 * ct + (gq >> 1)) ^ (((jt >> 2) & 1) << 1))) << 4) + 8 * (gq & 1);
-                const f16x4 b0 = *reinterpret_cast<const f16x4 *>(vr), b1 = *reinterpret_cast<const f16x4 *>(vr + PL);
+                for (int ct = 0; ct < 2; ++ct) { // columns 16 ct + 4 gq .. + 3: chunk 2 ct + (gq >> 1), half gq & 1
+                    typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
+                    const char *vr = Vp + jt * 64 + ((((2 * ct + (gq >> 1)) ^ (((jt >> 2) & 1) << 1))) << 4) + 8 * (gq & 1);
+                    const f16x4 b0 = *reinterpret_cast<const f16x4 *>(vr), b1 = *reinterpret_cast<const f16x4 *>(vr + PL);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) vt[4 * ct + r] = (float)b0[r] + (float)b1[r];
+                    for (int r = 0; r < 4; ++r) vt[4 * ct + r] = (float)b0[r] + (float)b1[r];
+                }
             }
         }
         mx = quad16_max(mx);
         float m = fmaxf(mx, st);
-        if (m == -INFINITY) m = 0.f;
-        // ---- pass 2: p = exp2(s - m); O^T += V^T P^T, one 32-key MFMA step per pair of tiles
+        if (m == -INFINITY) m = 0.f; // nothing visible: every exp2(-inf - 0) is 0, l = 0 -> NaN row like torch
+        // ---- pass 2: p = exp2(s - m), O^T += V^T P^T on four accumulators (tile or pair parity x column tile).  The target
+        // column's contribution starts the float32 form's accumulators; the plane form adds it in float32 at the end (ot).
         float l = 0.f;
         f32x4 o[2][2];
 #pragma unroll
@@ -5242,78 +4952,123 @@ __global__ void __launch_bounds__(64 * NW, 3) k_attn16h(const float *__restrict_
             for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) o[i][ct][r] = 0.f;
-        float ot[8]; // the target column's contribution (float32, added at the end)
+        float ot[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) ot[e] = 0.f;
         if (tgt_ok) {
             const float pt = __builtin_amdgcn_exp2f(st - m);
-            l = (gq == 0) ? pt : 0.f;
+            l = (gq == 0) ? pt : 0.f; // the four lanes of a query are summed at the end
+            if constexpr (PLANES) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) ot[e] = pt * vt[e];
-        }
-#pragma unroll
-        for (int kp = 0; kp < MAXT / 2; ++kp) {
-            const int k0t = 2 * kp, k1t = 2 * kp + 1;
-            const bool on0 = FAST ? (k0t <= qb) : (((live >> k0t) & 1u) != 0u);
-            const bool on1 = FAST ? (k1t <= qb) : (((live >> k1t) & 1u) != 0u);
-            if (on0 || on1) { // wave-uniform
-                float pa[8];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    pa[r] = on0 ? __builtin_amdgcn_exp2f(sacc[k0t][r] - m) : 0.f;
-                    pa[4 + r] = on1 ? __builtin_amdgcn_exp2f(sacc[k1t][r] - m) : 0.f;
-                    l += pa[r] + pa[4 + r];
-                }
-                x6_f16x8 P[2];
-                attn_split8h(pa, P);
-                const int r0 = k0t * 16 + 4 * gq + tq, r1 = r0 + 16;
+                for (int e = 0; e < 8; ++e) ot[e] = pt * vt[e];
+            } else {
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
-                    const int o0 = r0 * 64 + ((((2 * ct + (tp >> 1)) ^ (((r0 >> 2) & 1) << 1))) << 4) + 8 * (tp & 1);
-                    const int o1 = r1 * 64 + ((((2 * ct + (tp >> 1)) ^ (((r1 >> 2) & 1) << 1))) << 4) + 8 * (tp & 1);
-                    x6_f16x8 V[2];
+                    const int jt = L - 1;
+                    const float4 vt4 = *reinterpret_cast<const float4 *>(Vf + jt * HD + (((4 * ct + gq) ^ (((jt >> 2) & 1) << 2)) << 2));
+                    o[0][ct][0] = pt * vt4.x, o[0][ct][1] = pt * vt4.y, o[0][ct][2] = pt * vt4.z, o[0][ct][3] = pt * vt4.w;
+                }
+            }
+        }
+        if constexpr (!PLANES) { // v_mfma_f32_16x16x4_f32: the S accumulator is the B operand (register j <-> key 4gq + j)
 #pragma unroll
-                    for (int p = 0; p < 2; ++p) {
-                        const attn_s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) attn_s16x4 *)(Vp + p * PL + o0));
-                        attn_s16x4 a1 = {0, 0, 0, 0}; // (wave-uniform: a pair whose second tile does not exist reads nothing past the image)
-                        if (on1) a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) attn_s16x4 *)(Vp + p * PL + o1));
-                        typedef __attribute__((ext_vector_type(8))) short s16x8;
-                        const s16x8 both = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-                        V[p] = __builtin_bit_cast(x6_f16x8, both);
+            for (int kg = 0; kg < MAXT / 4; ++kg) {
+                if (!FAST || 4 * kg <= qb) { // FAST: tiles in groups of four under one guard
+#pragma unroll
+                    for (int kt = 4 * kg; kt < 4 * kg + 4; ++kt) {
+                        if (FAST ? (kt <= qb) : ((live >> kt) & 1u) != 0u) { // wave-uniform; tiles beyond qb are never live
+                            f32x4 pa;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const float pv = __builtin_amdgcn_exp2f(sacc[kt][r] - m);
+                                pa[r] = pv;
+                                l += pv;
+                            }
+#pragma unroll
+                            for (int ct = 0; ct < 2; ++ct) { // V[kt 16 + 4 gq + j][16 ct + lq], j = 0 .. 3 (rows 128 bytes apart)
+                                const float *vb = Vf + (kt * 16 + 4 * gq) * HD + ((16 * ct + lq) ^ ((gq & 1) << 4));
+                                const float4 v4 = make_float4(vb[0], vb[HD], vb[2 * HD], vb[3 * HD]);
+                                f32x4 oo = o[kt & 1][ct];
+                                oo = __builtin_amdgcn_mfma_f32_16x16x4f32(v4.x, pa[0], oo, 0, 0, 0);
+                                oo = __builtin_amdgcn_mfma_f32_16x16x4f32(v4.y, pa[1], oo, 0, 0, 0);
+                                oo = __builtin_amdgcn_mfma_f32_16x16x4f32(v4.z, pa[2], oo, 0, 0, 0);
+                                oo = __builtin_amdgcn_mfma_f32_16x16x4f32(v4.w, pa[3], oo, 0, 0, 0);
+                                o[kt & 1][ct] = oo;
+                            }
+                        }
                     }
-                    f32x4 oo = o[kp & 1][ct];
-                    oo = __builtin_amdgcn_mfma_f32_16x16x32_f16(V[0], P[1], oo, 0, 0, 0);
-                    oo = __builtin_amdgcn_mfma_f32_16x16x32_f16(V[1], P[0], oo, 0, 0, 0);
-                    oo = __builtin_amdgcn_mfma_f32_16x16x32_f16(V[0], P[0], oo, 0, 0, 0);
-                    o[kp & 1][ct] = oo;
+                }
+            }
+        } else { // one 32-key v_mfma_f32_16x16x32_f16 step of three plane products per pair of tiles
+#pragma unroll
+            for (int kp = 0; kp < MAXT / 2; ++kp) {
+                const int k0t = 2 * kp, k1t = 2 * kp + 1;
+                const bool on0 = FAST ? (k0t <= qb) : (((live >> k0t) & 1u) != 0u);
+                const bool on1 = FAST ? (k1t <= qb) : (((live >> k1t) & 1u) != 0u);
+                if (on0 || on1) { // wave-uniform
+                    float pa[8];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        pa[r] = on0 ? __builtin_amdgcn_exp2f(sacc[k0t][r] - m) : 0.f;
+                        pa[4 + r] = on1 ? __builtin_amdgcn_exp2f(sacc[k1t][r] - m) : 0.f;
+                        l += pa[r] + pa[4 + r];
+                    }
+                    x6_f16x8 P[2];
+                    attn_split8h(pa, P);
+                    const int r0 = k0t * 16 + 4 * gq + tq, r1 = r0 + 16;
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) {
+                        const int o0 = r0 * 64 + ((((2 * ct + (tp >> 1)) ^ (((r0 >> 2) & 1) << 1))) << 4) + 8 * (tp & 1);
+                        const int o1 = r1 * 64 + ((((2 * ct + (tp >> 1)) ^ (((r1 >> 2) & 1) << 1))) << 4) + 8 * (tp & 1);
+                        x6_f16x8 V[2];
+#pragma unroll
+                        for (int p = 0; p < 2; ++p) {
+                            const attn_s16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) attn_s16x4 *)(Vp + p * PL + o0));
+                            attn_s16x4 a1 = {0, 0, 0, 0}; // (wave-uniform: a pair whose second tile does not exist reads nothing past the image)
+                            if (on1) a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) attn_s16x4 *)(Vp + p * PL + o1));
+                            typedef __attribute__((ext_vector_type(8))) short s16x8;
+                            const s16x8 both = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+                            V[p] = __builtin_bit_cast(x6_f16x8, both);
+                        }
+                        f32x4 oo = o[kp & 1][ct];
+                        oo = __builtin_amdgcn_mfma_f32_16x16x32_f16(V[0], P[1], oo, 0, 0, 0);
+                        oo = __builtin_amdgcn_mfma_f32_16x16x32_f16(V[1], P[0], oo, 0, 0, 0);
+                        oo = __builtin_amdgcn_mfma_f32_16x16x32_f16(V[0], P[0], oo, 0, 0, 0);
+                        o[kp & 1][ct] = oo;
+                    }
                 }
             }
         }
         const float lt = quad16_sum(l);
-        const float inv = 1.0f / lt;
+        const float inv = 1.0f / lt; // 0 (fully masked) -> inf, 0 * inf = NaN like torch
         if (qi < L) {
-            if (out_frag) {
-                const int64_t tk = base + qi;
-                float4 *of = reinterpret_cast<float4 *>(out) + ((size_t)(tk >> 5) * gridDim.x + h) * 4 * 64 + (gq & 1) * 32 + (tk & 31);
+            auto res = [&](int ct) __attribute__((always_inline)) { // columns 16 ct + 4 gq .. + 3 of this lane's query
+                float v[4];
 #pragma unroll
-                for (int ct = 0; ct < 2; ++ct)
-                    of[(2 * ct + (gq >> 1)) * 64] =
-                        make_float4(((o[0][ct][0] + o[1][ct][0]) + ot[4 * ct + 0]) * inv, ((o[0][ct][1] + o[1][ct][1]) + ot[4 * ct + 1]) * inv,
-                                    ((o[0][ct][2] + o[1][ct][2]) + ot[4 * ct + 2]) * inv, ((o[0][ct][3] + o[1][ct][3]) + ot[4 * ct + 3]) * inv);
+                for (int r = 0; r < 4; ++r) {
+                    v[r] = o[0][ct][r] + o[1][ct][r];
+                    if constexpr (PLANES) v[r] += ot[4 * ct + r];
+                    v[r] *= inv;
+                }
+                return make_float4(v[0], v[1], v[2], v[3]);
+            };
+            if (out_frag) { // fragment-major image (d = 128: column block tn = head): the fused block kernel's B operand
+                const int64_t tk = base + qi;
+                float4 *of = reinterpret_cast<float4 *>(out) + ((size_t)(tk >> 5) * (size_t)H + h) * 4 * 64 + (gq & 1) * 32 + (tk & 31);
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) of[(2 * ct + (gq >> 1)) * 64] = res(ct);
             } else {
                 float *orow = out + (base + qi) * d + h * HD + 4 * gq;
 #pragma unroll
-                for (int ct = 0; ct < 2; ++ct)
-                    *reinterpret_cast<float4 *>(orow + 16 * ct) =
-                        make_float4(((o[0][ct][0] + o[1][ct][0]) + ot[4 * ct + 0]) * inv, ((o[0][ct][1] + o[1][ct][1]) + ot[4 * ct + 1]) * inv,
-                                    ((o[0][ct][2] + o[1][ct][2]) + ot[4 * ct + 2]) * inv, ((o[0][ct][3] + o[1][ct][3]) + ot[4 * ct + 3]) * inv);
+                for (int ct = 0; ct < 2; ++ct) *reinterpret_cast<float4 *>(orow + 16 * ct) = res(ct);
             }
         }
     }
+    ATTN_T(4);
 }
 
 // ------------------------------------------------------------------ one query block of the sequence-resident kernel (round 5)
-// k_attn16h's block body (FAST form: a packed sequence, at most one pad below the diagonal; two-pass softmax with every score
+// The block body of k_attn16's plane form (FAST form: a packed sequence, at most one pad below the diagonal; two-pass softmax with every score
 // tile of the block in registers, O^T += V^T P^T on float16 plane pairs through the transposing LDS read) with the SCORES too on
 // exact float16 plane products (three v_mfma_f32_16x16x32_f16 per tile instead of eight 16x16x4_f32), on images the layer
 // kernel's own waves wrote: Ks = [key][2 planes x 32 float16] chunk-swizzled, Vp = [2 planes][PL bytes] of [key][64 B], both
@@ -5777,58 +5532,56 @@ __global__ void k_gather_rows(const float *__restrict__ x, const int32_t *__rest
 
 // ------------------------------------------------------------------ host side
 // (every GEMM runs on 16-deep K slabs: tools/gemm_lab.hip times the BK = 32 instantiations against them)
-static int launch_linear(irs_ctx *ctx, const float *X, const float *W, const float *bias, const float *R, float *Y,
-                         int M, int N, int K, bool relu, hipStream_t s, const float *g1 = nullptr,
-                         const float *b1 = nullptr, const float *c = nullptr, const float *g2 = nullptr,
-                         const float *b2 = nullptr, const float *Rf = nullptr, float *Yf = nullptr,
-                         const int32_t *m_dev = nullptr, const float *Xf = nullptr) {
-    LinArgs a{X, W, bias, R, Y, M, N, K, relu ? 1 : 0, g1, b1, c, g2, b2, Rf, Yf, m_dev, 0, Xf};
-    if (Xf && !(K <= 128 && K % 32 == 0 && M > 2048)) {
+// a.slots is set here; every other field is the caller's (unset fields of a LinArgs{} mean "absent")
+static int launch_linear(irs_ctx *ctx, const LinArgs &args, hipStream_t s) {
+    LinArgs a = args;
+    const int M = a.M, N = a.N, K = a.K;
+    if (a.Xf && !(K <= 128 && K % 32 == 0 && M > 2048)) {
         if (ctx) snprintf(ctx->err, sizeof(ctx->err), "launch_linear: fragment-major X needs K <= 128, K %% 32 == 0, M > 2048");
         return IRS_E_INVALID;
     }
     if (ctx) irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
     auto al16 = [](const void *p) { return p == nullptr || (((uintptr_t)p) & 15) == 0; };
-    if ((M <= 2048 || (M <= 8192 && g1 == nullptr && Xf == nullptr && N >= 256)) && K <= 256) { // latency path: one wave per 32x32 tile, operands straight from L2
+    if ((M <= 2048 || (M <= 8192 && a.g1 == nullptr && a.Xf == nullptr && N >= 256)) && K <= 256) { // latency path: one wave per 32x32 tile, operands straight from L2
         // (wide outputs keep it up to 8192 rows: C5's 6400 rows x d = 256 give the 128 x 128 tiling 100-300 workgroups)
-        if (g1 != nullptr) hipLaunchKernelGGL(k_linear_small<true>, dim3(1, (M + 31) / 32), dim3(256), 0, s, a);
+        if (a.g1 != nullptr) hipLaunchKernelGGL(k_linear_small<true>, dim3(1, (M + 31) / 32), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(k_linear_small<false>, dim3((N + 127) / 128, (M + 31) / 32), dim3(256), 0, s, a);
-    } else if (g1 != nullptr && N > LIN_BN) { // fused residual + LayerNorm, rows of up to 256 values (8 tiles per token)
-        if (N > 2 * LIN_BN || Xf || Rf || Yf) {
+    } else if (a.g1 != nullptr && N > LIN_BN) { // fused residual + LayerNorm, rows of up to 256 values (8 tiles per token)
+        if (N > 2 * LIN_BN || a.Xf || a.Rf || a.Yf) {
             if (ctx) snprintf(ctx->err, sizeof(ctx->err), "launch_linear: LayerNorm epilogue needs N <= 256 (and row-major operands above 128)");
             return IRS_E_INVALID;
         }
         dim3 grid((M + LIN_BM - 1) / LIN_BM);
-        const bool full = (N == 2 * LIN_BN) && (K % 16 == 0) && al16(X) && al16(W) && al16(R) && al16(Y);
+        const bool full = (N == 2 * LIN_BN) && (K % 16 == 0) && al16(a.X) && al16(a.W) && al16(a.R) && al16(a.Y);
         if (full) hipLaunchKernelGGL((k_linear_ln<16, true, false, 8>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((k_linear_ln<16, false, false, 8>), grid, dim3(256), 0, s, a);
-    } else if (g1 != nullptr) { // fused residual + LayerNorm: whole rows per wave (N <= 128)
+    } else if (a.g1 != nullptr) { // fused residual + LayerNorm: whole rows per wave (N <= 128)
         dim3 grid((M + LIN_BM - 1) / LIN_BM);
-        const bool full = (N == LIN_BN) && (K % 16 == 0) && al16(X) && al16(W) && al16(R) && al16(Y) && al16(Rf) && al16(Yf);
-        if (Xf && !(full && al16(Xf))) {
+        const bool full = (N == LIN_BN) && (K % 16 == 0) && al16(a.X) && al16(a.W) && al16(a.R) && al16(a.Y) && al16(a.Rf) && al16(a.Yf);
+        if (a.Xf && !(full && al16(a.Xf))) {
             if (ctx) snprintf(ctx->err, sizeof(ctx->err), "launch_linear: fragment-major X needs the aligned N == 128 case");
             return IRS_E_INVALID;
         }
-        if (Xf) hipLaunchKernelGGL((k_linear_ln<16, true, true>), grid, dim3(256), 0, s, a);
+        if (a.Xf) hipLaunchKernelGGL((k_linear_ln<16, true, true>), grid, dim3(256), 0, s, a);
         else if (full) hipLaunchKernelGGL((k_linear_ln<16, true, false>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((k_linear_ln<16, false, false>), grid, dim3(256), 0, s, a);
     } else {
         a.slots = irs_cu_count() * 4; // matches k_linear<.., 16, ..>'s launch bounds
         const int ntm = (M + LIN_BM - 1) / LIN_BM, ntn = (N + LIN_BN - 1) / LIN_BN;
         // exact unit count when M is known here, its upper bound over any device-side M otherwise
-        dim3 grid(m_dev ? ntm + (a.slots - 1) * (ntn - 1) : (ntm / a.slots) * a.slots + (ntm % a.slots) * ntn);
-        const bool full = (K % 16 == 0) && al16(X) && al16(W);
-        if (Xf && !(full && al16(Xf))) {
+        dim3 grid(a.m_dev ? ntm + (a.slots - 1) * (ntn - 1) : (ntm / a.slots) * a.slots + (ntm % a.slots) * ntn);
+        const bool full = (K % 16 == 0) && al16(a.X) && al16(a.W);
+        if (a.Xf && !(full && al16(a.Xf))) {
             if (ctx) snprintf(ctx->err, sizeof(ctx->err), "launch_linear: fragment-major X needs aligned operands");
             return IRS_E_INVALID;
         }
-        if (Xf) hipLaunchKernelGGL((k_linear<true, 16, true>), grid, dim3(256), 0, s, a);
+        if (a.Xf) hipLaunchKernelGGL((k_linear<true, 16, true>), grid, dim3(256), 0, s, a);
         else if (full) hipLaunchKernelGGL((k_linear<true, 16, false>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((k_linear<false, 16, false>), grid, dim3(256), 0, s, a);
     }
     if (ctx) {
         irs_prof_end(ctx, IRS_PROF_LINEAR, s, 2.0 * M * (double)N * K,
-                     4.0 * ((double)M * K + (double)N * K + (double)M * N * (R ? 2 : 1)));
+                     4.0 * ((double)M * K + (double)N * K + (double)M * N * (a.R ? 2 : 1)));
         IRS_CHECK_HIP(ctx, hipGetLastError());
     }
     return IRS_OK;
@@ -5857,10 +5610,10 @@ static int launch_attn(irs_ctx *ctx, const float *qkv, const int64_t *seq, const
         if (H * B <= 64) grid.z = (((L + 15) / 16) + 3) / 4; // latency path: one query block per wave
         if (kv_planes) { // K / V arrive as float16 plane pairs (k_block_x6's tail): the split-float16 attention
             if (grid.z != 1) IRS_FAIL(ctx, IRS_E_STATE, "plane-format K / V on the latency path");
-            hipLaunchKernelGGL((tok_row ? k_attn16h<16, true, 4> : k_attn16h<16, false, 4>), grid, dim3(256), lds16d, s, qkv, seq, r_u,
-                               out, L, d, mm, off, cnt, tok_row ? ctx->seq_padq : nullptr, frag_out ? 1 : 0);
+            hipLaunchKernelGGL((tok_row ? k_attn16<16, true, true> : k_attn16<16, false, true>), grid, dim3(256), lds16d, s, qkv, seq, r_u,
+                               out, L, d, mm, off, cnt, tok_row ? ctx->seq_padq : nullptr, frag_out ? 1 : 0, attn_grid_heads{});
         } else
-            hipLaunchKernelGGL((tok_row ? k_attn16<16, true, true> : k_attn16<16, false, true>), grid, dim3(256), lds16d, s, qkv, seq,
+            hipLaunchKernelGGL((tok_row ? k_attn16<16, true, false> : k_attn16<16, false, false>), grid, dim3(256), lds16d, s, qkv, seq,
                                r_u, out, L, d, mm, off, cnt, tok_row ? ctx->seq_padq : nullptr, frag_out ? 1 : 0, H);
         irs_prof_end(ctx, IRS_PROF_ATTN, s, 2.0 * B * (double)H * L * L * hd, 4.0 * 4.0 * B * (double)L * d);
         IRS_CHECK_HIP(ctx, hipGetLastError());
@@ -6148,7 +5901,7 @@ struct DecodeRoute {
     DecFam tail;     // the rest of the rows-only last layer (GEMM, GEMM_LN, SMALL16, WIDE or ANY)
     bool frag;       // x / y live in the fragment-major images (act_xf / act_yf) between the layers
     bool seq;        // the sequence-resident launch (ctx->seq_last)
-    bool kv_planes;  // the split-precision kernels hand K / V to the attention as float16 plane pairs (k_attn16h)
+    bool kv_planes;  // the split-precision kernels hand K / V to the attention as float16 plane pairs (k_attn16<.., PLANES>)
     bool att_fused;  // self-attention runs inside the 16-token layer kernel (one sequence)
     bool kv_only;    // the last fused launch before the rows-only last layer writes its k | v only (queries: B rows, later)
     bool x6;         // the fragment-major fused kernels run on split-precision MFMAs (k_block_x6)
@@ -6187,7 +5940,7 @@ static DecodeRoute decode_route(const irs_ctx *ctx, int B, bool rows_only) {
     r.x6 = ctx->use_x6 && ctx->w_x6;
     r.npl = (ctx->use_x6 == IRS_GEMM_H3 && ctx->h3_ok) ? 2 : 3;
     r.nt = x6d ? 8 : 4;
-    // ONE predicate for the writers of K / V planes (embed kernel, layer kernel tail) and their reader (launch_attn: k_attn16h): it
+    // ONE predicate for the writers of K / V planes (embed kernel, layer kernel tail) and their reader (launch_attn: k_attn16<.., PLANES>): it
     // includes the layer loop's own condition for the fused block + 16-query attention (fragment-major activations, head dim 32,
     // L <= 256, 16-byte aligned workspace), so a V section is never written as planes for an attention kernel that reads float32
     r.kv_planes = fuse_block && ctx->use_attn_h3 && ctx->h3_ok && r.x6 && nl > 1 &&
@@ -6387,30 +6140,28 @@ static int gemm_rest(irs_ctx *ctx, bool ln_fused, int l, const float *ao, const 
     const irs_layer_w &w = ctx->layer[l];
     const float *cl = ctx->c_l + (size_t)l * d;
     int rc;
+    LinArgs o{}, f1{}, f2{}; // out-projection, FFN 1, FFN 2 (packed rows: every kernel clamps to m_dev)
+    o.X = ao, o.W = w.sa_out_w, o.bias = w.sa_out_b, o.R = res, o.N = d, o.K = d;
+    f1.X = mid, f1.W = w.l1_w, f1.bias = w.l1_b, f1.Y = ctx->act_h, f1.N = F, f1.K = d, f1.relu = 1;
+    f2.X = ctx->act_h, f2.W = w.l2_w, f2.bias = w.l2_b, f2.R = mid, f2.N = d, f2.K = F;
+    o.M = f1.M = f2.M = M, o.m_dev = f1.m_dev = f2.m_dev = m_dev;
     if (ln_fused) {
         // mid <- LN2(LN1(res + ao W_o^T + b_o) + c_l), fused into the GEMM epilogue
-        if ((rc = launch_linear(ctx, ao, w.sa_out_w, w.sa_out_b, res, mid, M, d, d, false, s, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b,
-                                nullptr, nullptr, m_dev)))
-            return rc;
+        o.Y = mid, o.g1 = w.n1_w, o.b1 = w.n1_b, o.c = cl, o.g2 = w.n2_w, o.b2 = w.n2_b;
+        if ((rc = launch_linear(ctx, o, s))) return rc;
         // h = relu(mid W1^T + b1); out <- LN3(mid + h W2^T + b2)
-        if ((rc = launch_linear(ctx, mid, w.l1_w, w.l1_b, nullptr, ctx->act_h, M, F, d, true, s, nullptr, nullptr, nullptr, nullptr,
-                                nullptr, nullptr, nullptr, m_dev)))
-            return rc;
-        return launch_linear(ctx, ctx->act_h, w.l2_w, w.l2_b, mid, out, M, d, F, false, s, w.n3_w, w.n3_b, nullptr, nullptr, nullptr,
-                             nullptr, nullptr, m_dev);
+        if ((rc = launch_linear(ctx, f1, s))) return rc;
+        f2.Y = out, f2.g1 = w.n3_w, f2.b1 = w.n3_b;
+        return launch_linear(ctx, f2, s);
     }
-    // tmp = res + ao W_o^T + b_o ; mid = LN2(LN1(tmp) + c_l)          (packed rows: every kernel clamps to m_dev)
-    if ((rc = launch_linear(ctx, ao, w.sa_out_w, w.sa_out_b, res, tmp, M, d, d, false, s, nullptr, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, m_dev)))
-        return rc;
+    // tmp = res + ao W_o^T + b_o ; mid = LN2(LN1(tmp) + c_l)
+    o.Y = tmp;
+    if ((rc = launch_linear(ctx, o, s))) return rc;
     hipLaunchKernelGGL(k_ln, dim3((M + 3) / 4), dim3(256), 0, s, tmp, w.n1_w, w.n1_b, cl, w.n2_w, w.n2_b, mid, M, d, m_dev);
     // h = relu(mid W1^T + b1); tmp = mid + h W2^T + b2; out = LN3(tmp)
-    if ((rc = launch_linear(ctx, mid, w.l1_w, w.l1_b, nullptr, ctx->act_h, M, F, d, true, s, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, nullptr, m_dev)))
-        return rc;
-    if ((rc = launch_linear(ctx, ctx->act_h, w.l2_w, w.l2_b, mid, tmp, M, d, F, false, s, nullptr, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, m_dev)))
-        return rc;
+    if ((rc = launch_linear(ctx, f1, s))) return rc;
+    f2.Y = tmp;
+    if ((rc = launch_linear(ctx, f2, s))) return rc;
     hipLaunchKernelGGL(k_ln, dim3((M + 3) / 4), dim3(256), 0, s, tmp, w.n3_w, w.n3_b, (const float *)nullptr, (const float *)nullptr,
                        (const float *)nullptr, out, M, d, m_dev);
     return IRS_OK;
@@ -6454,9 +6205,10 @@ static int frag_layer(const DecodeCall &c, int l) {
         return IRS_OK;
     }
     // y <- LN2(LN1(x + ao W_o^T + b_o) + c_l): residual from xf, result to yf only
-    if ((rc = launch_linear(ctx, ctx->act_ao, w.sa_out_w, w.sa_out_b, nullptr, nullptr, rows, d, d, false, s, w.n1_w, w.n1_b, cl,
-                            w.n2_w, w.n2_b, xf, yf, m_dev)))
-        return rc;
+    LinArgs o{};
+    o.X = ctx->act_ao, o.W = w.sa_out_w, o.bias = w.sa_out_b, o.M = rows, o.N = d, o.K = d, o.m_dev = m_dev;
+    o.g1 = w.n1_w, o.b1 = w.n1_b, o.c = cl, o.g2 = w.n2_w, o.b2 = w.n2_b, o.Rf = xf, o.Yf = yf;
+    if ((rc = launch_linear(ctx, o, s))) return rc;
     // x <- LN3(y + relu(y W1^T + b1) W2^T + b2) back into xf (the last layer of a full decode writes the row-major x the caller
     // receives instead); d = 128, F = 256 runs as one kernel with h in registers
     if (r.layer == DecFam::FRAG_BLOCK) {
@@ -6466,11 +6218,12 @@ static int frag_layer(const DecodeCall &c, int l) {
         irs_prof_end(ctx, IRS_PROF_LINEAR, s, ffn_flops, (8.0 + (tail ? 12.0 : 0.0)) * rows * (double)d);
         return IRS_OK;
     }
-    if ((rc = launch_linear(ctx, nullptr, w.l1_w, w.l1_b, nullptr, ctx->act_h, rows, F, d, true, s, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, nullptr, m_dev, yf)))
-        return rc;
-    return launch_linear(ctx, ctx->act_h, w.l2_w, w.l2_b, nullptr, last ? c.x : nullptr, rows, d, F, false, s, w.n3_w, w.n3_b, nullptr,
-                         nullptr, nullptr, yf, last ? nullptr : xf, m_dev);
+    LinArgs f1{}, f2{};
+    f1.Xf = yf, f1.W = w.l1_w, f1.bias = w.l1_b, f1.Y = ctx->act_h, f1.M = rows, f1.N = F, f1.K = d, f1.relu = 1, f1.m_dev = m_dev;
+    if ((rc = launch_linear(ctx, f1, s))) return rc;
+    f2.X = ctx->act_h, f2.W = w.l2_w, f2.bias = w.l2_b, f2.Y = last ? c.x : nullptr, f2.M = rows, f2.N = d, f2.K = F, f2.m_dev = m_dev;
+    f2.g1 = w.n3_w, f2.b1 = w.n3_b, f2.Rf = yf, f2.Yf = last ? nullptr : xf;
+    return launch_linear(ctx, f2, s);
 }
 
 // layer l (before the rows-only last one, or any layer of a full decode) behind its q | k | v
@@ -6531,7 +6284,9 @@ static int last_layer(const DecodeCall &c, int l, const int32_t *pos, float *xro
         hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, ctx->act_yf, ctx->qrow_tile, ao_r, d, nt);
     } else if (r.kv_only) { // the previous layer's kernel wrote k | v only: queries for the B consumed rows here
         hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, xf, qrow, x_r, d, nt);
-        if ((rc = launch_linear(ctx, x_r, w.sa_in_w, w.sa_in_b, nullptr, h_r, B, d, d, false, s))) return rc;
+        LinArgs q{};
+        q.X = x_r, q.W = w.sa_in_w, q.bias = w.sa_in_b, q.Y = h_r, q.M = B, q.N = d, q.K = d;
+        if ((rc = launch_linear(ctx, q, s))) return rc;
         q_r = h_r;
     }
     irs_prof_begin(ctx, IRS_PROF_ATTN, s);
@@ -6596,10 +6351,12 @@ int irs_launch_decode(irs_ctx *ctx, const int64_t *seq, const int64_t *user, int
     for (int l = l0; l < nl; ++l) {
         const irs_layer_w &w = ctx->layer[l];
         // qkv = x W_in^T + b_in, unless the embed kernel or the previous layer's kernel produced it
-        if (!(l == l0 ? embed_qkv : fam_writes_qkv(r.layer)) &&
-            (rc = launch_linear(ctx, c.x, w.sa_in_w, w.sa_in_b, nullptr, ctx->act_qkv, c.rows, 3 * d, d, false, s, nullptr, nullptr,
-                                nullptr, nullptr, nullptr, nullptr, nullptr, c.m_dev, r.frag ? ctx->act_xf : nullptr)))
-            return rc;
+        if (!(l == l0 ? embed_qkv : fam_writes_qkv(r.layer))) {
+            LinArgs q{};
+            q.X = c.x, q.Xf = r.frag ? ctx->act_xf : nullptr, q.W = w.sa_in_w, q.bias = w.sa_in_b, q.Y = ctx->act_qkv;
+            q.M = c.rows, q.N = 3 * d, q.K = d, q.m_dev = c.m_dev;
+            if ((rc = launch_linear(ctx, q, s))) return rc;
+        }
         if (r.rows_only && l + 1 == nl) return last_layer(c, l, pos, xrows);
         if ((rc = decode_layer(c, l))) return rc;
         IRS_CHECK_HIP(ctx, hipGetLastError());

@@ -1,4 +1,4 @@
-// Development lab for the throughput attention kernel (not product code): k_attn16<16, FAST> on synthetic packed sequences
+// Development lab for the throughput attention kernel (not product code): k_attn16<16, FAST, PLANES> on synthetic packed sequences
 // with in-kernel s_memtime stamps (-DATTN_STAMP): how a workgroup's life splits into issuing the K / V loads, waiting for
 // them + staging them into LDS, the barrier, and the query blocks.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DIRS_LAB -DATTN_STAMP tools/attn_lab.hip -o tools/attn_lab ; run: tools/attn_lab [sequences=4096]
@@ -37,29 +37,25 @@ int main(int argc, char **argv) {
     unsigned long long z = 88172645463325252ull;
     for (auto &v : hq) { z ^= z << 13; z ^= z >> 7; z ^= z << 17; v = ((float)((z >> 40) & 0xFFFFFF) * (1.0f / 16777216.0f) * 2 - 1) * 0.7f; }
     std::vector<int64_t> hseq((size_t)B * L, 1);
-    float *qkv, *out, *ru;
+    float *qkv, *ru;
     int64_t *seq;
     int32_t *doff, *dcnt, *dpadq;
     CK(hipMalloc(&qkv, hq.size() * 4)); CK(hipMemcpy(qkv, hq.data(), hq.size() * 4, hipMemcpyHostToDevice));
-    CK(hipMalloc(&out, ((size_t)M + 128) * d * 4)); CK(hipMemset(out, 0, ((size_t)M + 128) * d * 4));
     CK(hipMalloc(&ru, B * 4)); CK(hipMemset(ru, 0, B * 4));
     CK(hipMalloc(&seq, hseq.size() * 8)); CK(hipMemcpy(seq, hseq.data(), hseq.size() * 8, hipMemcpyHostToDevice));
     CK(hipMalloc(&doff, B * 4)); CK(hipMemcpy(doff, off.data(), B * 4, hipMemcpyHostToDevice));
     CK(hipMalloc(&dcnt, B * 4)); CK(hipMemcpy(dcnt, cnt.data(), B * 4, hipMemcpyHostToDevice));
     CK(hipMalloc(&dpadq, B * 4)); CK(hipMemcpy(dpadq, padq.data(), B * 4, hipMemcpyHostToDevice));
-    int S16 = (L + 7) & ~7;
-    if ((S16 & 15) != 8) S16 += 8;
-    const size_t lds16 = (size_t)32 * S16 * 4 + (size_t)((L + 15) & ~15) * 32 * 4 + 64;
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    // A/B in one process, interleaved (guide rule 24): the register-staged fill with the transposed V^T image against the
-    // LDS-DMA fill with the row-major V image; outputs compared bit for bit (same MFMA chains, same operands)
+    // (the register-staged fill with the transposed V^T image, timed here against the LDS-DMA fill in round 3 --
+    // profiles/r03/attn16_lab_stamps.txt -- left the tree with the kernel's template arm)
     const size_t lds16d = (size_t)2 * ((L + 15) & ~15) * 32 * 4 + 64;
-    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_attn16<16, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16d));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_attn16<16, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16d));
     float *out2;
     CK(hipMalloc(&out2, ((size_t)M + 128) * d * 4)); CK(hipMemset(out2, 0, ((size_t)M + 128) * d * 4));
     // (the persistent work-list form measured here in round 4 -- profiles/r04/attn_lab_persist_r04.txt -- left the tree in round 5)
-    const int variant = argc > 2 ? atoi(argv[2]) : 2; // 0: register fill only, 1: DMA only, 2: both interleaved, 3: the DMA family
+    const int variant = argc > 2 ? atoi(argv[2]) : 1; // 1: the float32 form, 4: float32 against float16 planes
     auto timed = [&](const char *name, auto launch) {
         float ms;
         CK(hipEventRecord(e0));
@@ -69,10 +65,8 @@ int main(int argc, char **argv) {
         printf("%-44s %d sequences x %d heads, %lld packed rows: %8.1f us\n", name, B, H, M, ms * 1e3);
     };
     for (int rep = 0; rep < 5; ++rep) {
-        if (variant == 0 || variant == 2)
-            timed("k_attn16<16, FAST> register fill:", [&] { hipLaunchKernelGGL((k_attn16<16, true, false>), dim3(H, B), dim3(256), lds16, 0, qkv, seq, ru, out, L, d, IRS_MASK_IRN, doff, dcnt, dpadq, 1, H); });
-        if (variant >= 1 && variant != 4)
-            timed("k_attn16<16, FAST> LDS-DMA fill :", [&] { hipLaunchKernelGGL((k_attn16<16, true, true>), dim3(H, B), dim3(256), lds16d, 0, qkv, seq, ru, out2, L, d, IRS_MASK_IRN, doff, dcnt, dpadq, 1, H); });
+        if (variant != 4)
+            timed("k_attn16<16, FAST> float32:", [&] { hipLaunchKernelGGL((k_attn16<16, true, false>), dim3(H, B), dim3(256), lds16d, 0, qkv, seq, ru, out2, L, d, IRS_MASK_IRN, doff, dcnt, dpadq, 1, H); });
     }
     if (variant == 4) { // the split-float16 attention on plane-format K / V against the float32 kernel on the same values
         float *qkvp, *out4;
@@ -80,8 +74,8 @@ int main(int argc, char **argv) {
         CK(hipMalloc(&out4, ((size_t)M + 128) * d * 4)); CK(hipMemset(out4, 0, ((size_t)M + 128) * d * 4));
         hipLaunchKernelGGL(k_lab_to_planes, dim3((unsigned)((M * 2 * d + 255) / 256)), dim3(256), 0, 0, qkv, qkvp, M, d);
         for (int rep = 0; rep < 3; ++rep) {
-            timed("k_attn16<16, FAST> LDS-DMA fill, float32:", [&] { hipLaunchKernelGGL((k_attn16<16, true, true>), dim3(H, B), dim3(256), lds16d, 0, qkv, seq, ru, out2, L, d, IRS_MASK_IRN, doff, dcnt, dpadq, 1, H); });
-            timed("k_attn16h<16, FAST> split-float16 planes:", [&] { hipLaunchKernelGGL((k_attn16h<16, true, 4>), dim3(H, B), dim3(256), lds16d, 0, qkvp, seq, ru, out4, L, d, IRS_MASK_IRN, doff, dcnt, dpadq, 1); });
+            timed("k_attn16<16, FAST> float32:", [&] { hipLaunchKernelGGL((k_attn16<16, true, false>), dim3(H, B), dim3(256), lds16d, 0, qkv, seq, ru, out2, L, d, IRS_MASK_IRN, doff, dcnt, dpadq, 1, H); });
+            timed("k_attn16<16, FAST, PLANES> float16 planes:", [&] { hipLaunchKernelGGL((k_attn16<16, true, true>), dim3(H, B), dim3(256), lds16d, 0, qkvp, seq, ru, out4, L, d, IRS_MASK_IRN, doff, dcnt, dpadq, 1, attn_grid_heads{}); });
         }
         std::vector<float> h1((size_t)M * d), h2((size_t)M * d);
         CK(hipMemcpy(h1.data(), out2, h1.size() * 4, hipMemcpyDeviceToHost));
@@ -94,14 +88,6 @@ int main(int argc, char **argv) {
         int sb = 0; while (sb + 1 < B && off[sb + 1] <= tok) ++sb;
         printf("split-float16 vs float32 attention: max %.3g  mean %.3g  values > 1e-4: %zu; worst at token %lld = sequence %d (length %d) position %lld head %zu: %g vs %g\n",
                md, sum / h1.size(), n4, tok, sb, cnt[sb], tok - off[sb], head_, h2[worst], h1[worst]);
-    }
-    if (variant == 2) {
-        std::vector<float> h1((size_t)M * d), h2((size_t)M * d);
-        CK(hipMemcpy(h1.data(), out, h1.size() * 4, hipMemcpyDeviceToHost));
-        CK(hipMemcpy(h2.data(), out2, h2.size() * 4, hipMemcpyDeviceToHost));
-        size_t nd = 0; double md = 0;
-        for (size_t i = 0; i < h1.size(); ++i) { if (memcmp(&h1[i], &h2[i], 4)) { ++nd; md = fmax(md, fabs((double)h1[i] - h2[i])); } }
-        printf("outputs: %zu of %zu values differ (max abs %.3g)\n", nd, h1.size(), md);
     }
 #ifdef ATTN_STAMP
     {

@@ -83,7 +83,7 @@ int main(int argc, char **argv) {
         double gf = 2.0 * M * sh.N * sh.K / 1e9;
         for (int bk : {32, 16}) {
             float ms = bk == 32 ? time_it([&] { launch_bk32(a, n_cu); }, 20)
-                                : time_it([&] { launch_linear(nullptr, a.X, a.W, a.bias, a.R, a.Y, M, sh.N, sh.K, sh.relu, 0, a.g1, a.b1, a.c, a.g2, a.b2, nullptr, nullptr); }, 20);
+                                : time_it([&] { launch_linear(nullptr, a, 0); }, 20);
             printf("%s BK=%2d : %8.1f us  %6.1f TF\n", sh.name, bk, ms * 1e3, gf / ms);
         }
     }

@@ -20,7 +20,7 @@ KERNELS = [  # label, regex on the kernel name, algorithmic HBM bytes per packed
     ("layer", r"k_block_x6<0, 4, false", 4 * D * 6, "in: attention output + residual x; out: x' + the next layer's q | k | v"),
     ("layer_kv_only", r"k_block_x6<1, 4, false", 4 * D * 5, "the same, k | v only (feeds the rows-only last layer)"),
     ("embed_qkv0", r"k_block_x6<0, 4, true", 4 * D * 5, "K1: in: embedding row; out: x + layer 0's q | k | v"),
-    ("attention", r"k_attn16h<", 4 * D * 4, "in: q | k | v rows; out: attention output (fragment-major)"),
+    ("attention", r"k_attn16h<|k_attn16<16, (true|false), true>", 4 * D * 4, "in: q | k | v rows; out: attention output (fragment-major)"),
     ("attention_last_row", r"k_attn_row32", 4 * D * 2, "in: k | v rows of every token; out: one row per sequence"),
     # the sequence-resident decoder (irs_set_decoder_seq; default from 1024 sequences up): ONE launch per step
     ("seq_decoder", r"k_block_x6<3, 8, false, 4, 2, true>", 4 * D * 2, "embedding + layers 0 .. n-2 with attention + the last layer's q|k|v and attention: "
