@@ -1693,6 +1693,12 @@ __device__ __forceinline__ x6_u32x4 x6_gld(const void *p) {
     return v;
 }
 
+// an 8-byte LDS store the compiler does not track (k_block_x6<.., SEQ>: the K / V image rows written inside a step)
+template <int OFF>
+__device__ __forceinline__ void x6_wr64(unsigned int addr, __attribute__((ext_vector_type(4))) _Float16 v) {
+    asm volatile("ds_write_b64 %0, %1 offset:%2" :: "v"(addr), "v"(v), "i"(OFF));
+}
+
 // the same read with its wait inside the statement: the value is valid when the statement ends, whatever the register
 // allocator does next (at NT = 8 the prologue runs at ~270 live registers and the compiler parked the four first fragments
 // in AGPRs right behind their reads -- copies of registers whose data had not landed: rows wrong by ~1e-4, found by scanning
@@ -1739,6 +1745,9 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
 #ifndef SEQ_IDLE_SKIP
 #define SEQ_IDLE_SKIP 1 // (lab: 0 = a wave with two empty halves runs every step on zeros, as it did through round 5)
 #endif
+#ifndef SEQ_FRONT_RIDE
+#define SEQ_FRONT_RIDE 1 // (lab, tools/seq_lab.sh: 0 = a head's steps in the order q, k, v with all three epilogues behind the v step, as through round 7)
+#endif
 // SEQ layout of the dynamic LDS behind the ring and the parameter vectors (x6_seq_lds_bytes)
 #define X6_SEQ_VECS (256 + 12 * 32 * 4 + 384)   // floats: the parameter vectors + this layer's in-projection bias
 #define X6_SEQ_KIMG (3 * 16384 + X6_SEQ_VECS * 4)  // K image of ONE head: 256 token rows x 32 float32, chunk-swizzled (k_attn16's)
@@ -1773,7 +1782,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     using x6_plane = typename std::conditional<NPL == 2, x6_f16x8, x6_bf16x8>::type;
     // (SEQ: three ring slots -- the K / V images and the q scratch take the rest of the CU's LDS)
     constexpr int D = 32 * NT, F = 256, NSLOT = SEQ ? 3 : x6_nslot(NPL), LEAD = NSLOT - 1, PPW = NP / NW, HT = NT / 4;
-    constexpr int NFRONT = SEQ ? 3 * NT : 0; // SEQ: the q | k | v steps of THIS layer run in front (head-major: q_h, k_h, v_h)
+    constexpr int NFRONT = SEQ ? 3 * NT : 0; // SEQ: the q | k | v steps of THIS layer run in front (head-major: k_h, v_h, q_h; front_blk)
     // the weight planes hold WS x the weights (x6_wscale): an accumulator of plane products holds WS x the product, IWS folds back
     constexpr float WS = x6_wscale(NPL), IWS = 1.0f / WS;
     // RESID_LATE (round 4, d = 128 with float16 planes): the workgroup's start no longer waits for its 128 KB of inputs.  The
@@ -1949,17 +1958,21 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     const uint4 *dma_src = (SEQ ? a.Wbase : a.Wx) + (PPW * wave + PPG / 2) * 64 + lane;
     const uint4 *dma_src_q = SEQ ? a.Wbase + (long long)(a.nl_total - 1) * a.wstride + (PPW * wave + PPG / 2) * 64 + lane : dma_src;
     const uint4 *dma_src_qn = dma_src; // (layer l + 1's q | k | v sits in stream l)
+    // SEQ: front step i = 3 h + p of head h computes component (p + 1) % 3 of q | k | v (0 q, 1 k, 2 v): k first, then v with K's
+    // epilogue riding it, then q with V's (SEQ_FRONT_RIDE = 0: q, k, v); it consumes q | k | v tile NT c + h of the stream's tail
+    // region.  The ONE place that knows the order: the live waves' refills, the idle path and the prefetch of the next layer's
+    // front all go through issue().
+    auto front_blk = [](int i) __attribute__((always_inline)) { return NPRE + NT * ((i % 3 + (SEQ_FRONT_RIDE ? 1 : 0)) % 3) + i / 3; };
     auto issue = [&](int i) __attribute__((always_inline)) {
-        // SEQ: front step i = 3 h + c (c = 0 q, 1 k, 2 v of head h) is q | k | v tile NT c + h of the OTHER stream's tail region;
+        // SEQ: front step i is block front_blk(i) of the OTHER stream's tail region;
         // body step i is block i - NFRONT of this layer's stream; behind the body: the last layer's k | v tail, else the empty
         // step (nothing to fetch) and then the NEXT layer's front steps
         const int ib = i - NFRONT;
-        int blk = (SEQ && i < NFRONT) ? NPRE + NT * (i % 3) + i / 3 : (ib < NPRE ? ib : ib + qoff);
+        int blk = (SEQ && i < NFRONT) ? front_blk(i) : (ib < NPRE ? ib : ib + qoff);
         const uint4 *dsrc = (SEQ && i < NFRONT) ? dma_src_q : dma_src;
         if (SEQ && ib >= NPRE && !last) {
             if (i == SEQ_LSTEPS - 1) return; // the empty step
-            const int j = i - SEQ_LSTEPS;
-            blk = NPRE + NT * (j % 3) + j / 3;
+            blk = front_blk(i - SEQ_LSTEPS);
             dsrc = dma_src_qn;
         }
         x6_static_for<0, NGRP>([&](auto gc) __attribute__((always_inline)) {
@@ -2450,7 +2463,13 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     else af[(v_) & RA] = x6_rd<((v_) - NV) * 1024>(sn_); /* next step's head (behind this step's barrier) */
 #define X6_WAIT_V(v_) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(af[(v_) & RA]) : "i"(RA));
 #endif
-#define X6_STEP1(I_, XP_, T_)                                                                                            \
+    // RIDE_: a callable invoked with the read index v_ (an integral_constant) in front of read v_ + RA of the step: vector
+    // work that does not depend on the step runs between its matrix instructions (SEQ: the K / V epilogues of the front).  It
+    // may issue LDS operations of its own in inline asm: a wave's LDS operations return in order, so they only make the
+    // step's counted waits stricter.
+    auto x6_no_ride = [](auto) __attribute__((always_inline)) {};
+#define X6_STEP1(I_, XP_, T_) X6_STEP1R(I_, XP_, T_, x6_no_ride)
+#define X6_STEP1R(I_, XP_, T_, RIDE_)                                                                                    \
     {                                                                                                                    \
         const int step_ = (I_);                                                                                          \
         unsigned long long sq_0 = 0, sq_1 = 0;                                                                           \
@@ -2464,6 +2483,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
         x6_static_for<0, NV>([&](auto vc_) __attribute__((always_inline)) {                                              \
             constexpr int v_ = decltype(vc_)::value;                                                                     \
             if constexpr (v_ == NV / 2) { X6_PUBLISH(step_) }                                                            \
+            RIDE_(vc_);                                                                                                  \
             X6_RD_V(v_ + RA)                                                                                             \
             X6_WAIT_V(v_)                                                                                                \
             const x6_plane w_ = __builtin_bit_cast(x6_plane, af[v_ & RA]);                                               \
@@ -2524,15 +2544,16 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     if constexpr (SEQ) {
         // ================= the sequence-resident front (round 5): this layer's q | k | v from x, head by head, K / V of the head
         // into the workgroup's LDS images, the attention of this wave's own 32 queries, its output to the scratch tiles the
-        // out-projection below reads back.  The three steps of a head run back to back with their result tiles in registers; the
-        // LDS traffic the compiler can see (image writes, the attention's reads) sits in ONE region per head, behind the v step,
-        // and that step leaves its ring refill to the end of the region: a compiler-visible LDS access behind an LDS-DMA issue
-        // gets a vmcnt(0) in front, i.e. it would drain the ring at every step.
+        // out-projection below reads back.  The three steps of a head (k, v, q) run back to back with their result tiles in registers;
+        // K's and V's image rows are written from inside the v and the q step by inline asm.  The LDS traffic the compiler can see (q's
+        // scratch store, the attention's reads) sits in ONE region per head, behind the head's last step, and with the builtin DMA
+        // that step leaves its ring refill to the end of the region: a compiler-visible LDS access behind an LDS-DMA issue gets a
+        // vmcnt(0) in front, i.e. it would drain the ring at every step.
         float *Kimg = reinterpret_cast<float *>(smem + X6_SEQ_KIMG);
         char *Vimg = smem + X6_SEQ_VIMG;
         float *scr = reinterpret_cast<float *>(smem + X6_SEQ_SCR + wave * X6_SEQ_SCR_B);
-        int irow = l_row0 + s_j, li_l = li; // this lane's row of the images (rows [L, 32 T) of a sequence hold finite values of dead tokens)
-        asm volatile("" : "+v"(irow), "+v"(li_l)); // (laundered like the addresses above)
+        int irow = l_row0 + s_j, li_l = li, sj_l = s_j; // this lane's row of the images (rows [L, 32 T) of a sequence hold finite values of dead tokens)
+        asm volatile("" : "+v"(irow), "+v"(li_l), "+v"(sj_l)); // (laundered like the addresses above)
         const bool irn_ = a.mask_mode == IRS_MASK_IRN;
         float4 *ao4 = reinterpret_cast<float4 *>(const_cast<float *>(a.Af)) + (size_t)mtile * NT * 4 * 64;
 #pragma unroll
@@ -2540,6 +2561,72 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             f32x16 tq, tk, tv, bt;
 #pragma unroll
             for (int r = 0; r < 16; ++r) tq[r] = 0.f, tk[r] = 0.f, tv[r] = 0.f;
+#if SEQ_FRONT_RIDE
+            // k, v, q: K's epilogue (bias, split into float16 planes, image row) rides the v step, V's the q step -- four values of
+            // a bias group are read (asm) in front of read 6 g + 3 and used three reads later, behind a wait of their own; the image
+            // stores are asm too (a compiler-visible LDS access behind the builtin DMA gets a vmcnt(0) in front, and the compiler may
+            // not move them into a phase it writes itself).  Behind the q step only q's bias + scratch store remain.
+            // Image writes against image reads: head h's K rows are written during step 3 h + 1 -- behind the mid-step barrier of step
+            // 3 h, which every wave reaches only after its attention of head h - 1: ONE workgroup barrier between the last read of the
+            // images and the first write (V, a step later: two).  Every row is complete at the barrier behind the q step.
+            x6_u32x4 rb;
+            auto front_ride = [&](auto vc, auto cc, const f32x16 &t) __attribute__((always_inline)) {
+                constexpr int v = decltype(vc)::value, c = decltype(cc)::value, g = v / 6; // c = 1: K, 2: V
+                static_assert(NV == 24 && RA == 3, "a bias group every six reads, used three reads behind its own read");
+                typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
+                if constexpr (v % 6 == 0) rb = x6_rd<32 * g>(vecs_addr + (unsigned int)((V_BQ + c * D + 32 * h) * 4));
+                if constexpr (v % 6 == 3) {
+#ifdef X6_NO_READS
+                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rb));
+#else
+                    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(rb) : "i"(RA)); // (the reads of fragments v - 3 + RA .. v - 1 + RA are behind it)
+#endif
+                    const float4 bb = __builtin_bit_cast(float4, rb);
+                    const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
+                    f16x4 hp, lp;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float x = __builtin_fmaf(t[4 * g + e], IWS, bv[e]);
+                        if constexpr (c == 1) x *= SEQ_KQ_SCALE; // (exact)
+                        const _Float16 hv = (_Float16)x;
+                        hp[e] = hv;
+                        lp[e] = (_Float16)(x - (float)hv);
+                    }
+                    if constexpr (c == 1) {
+                        // K as two float16 planes (the score products of seq_attn_block): 128 B per key = chunks 0 .. 3 plane h, 4 .. 7
+                        // plane l (chunk = 8 channels), chunk index ^ ((key >> 1) & 7): a tile's 16 keys x one chunk = 16 bank groups
+                        const int swk = (sj_l >> 1) & 7;
+                        const unsigned int krow = lds0 + X6_SEQ_KIMG + (unsigned int)(irow * 128 + 8 * lk);
+                        if (l_b >= 0) { // (rows [cnt, 16 nb) hold finite values of dead tokens: read with p = 0)
+                            x6_wr64<0>(krow + ((g ^ swk) << 4), hp);
+                            x6_wr64<0>(krow + (((4 + g) ^ swk) << 4), lp);
+                        }
+                    } else {
+                        const int swv = ((sj_l >> 2) & 1) << 1;
+                        const unsigned int slot = lds0 + X6_SEQ_VIMG + (unsigned int)(irow * 64 + ((g ^ swv) << 4) + 8 * lk);
+                        if (l_b >= 0) {
+                            x6_wr64<0>(slot, hp);
+                            x6_wr64<16384>(slot, lp);
+                        }
+                    }
+                }
+            };
+            auto ride_k = [&](auto vc) __attribute__((always_inline)) { front_ride(vc, std::integral_constant<int, 1>{}, tk); };
+            auto ride_v = [&](auto vc) __attribute__((always_inline)) { front_ride(vc, std::integral_constant<int, 2>{}, tv); };
+            X6_STEP1(3 * h, Yp, tk)
+            X6_STEP1R(3 * h + 1, Yp, tv, ride_k)
+            X6_STEP1R(3 * h + 2, Yp, tq, ride_v) // (builtin DMA: no ring refill behind this step, see X6_PUBLISH)
+            X6_PH(9)
+            bias_tile(bt, V_BQ + 32 * h);
+            {
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    *reinterpret_cast<float4 *>(scr + li_l * 36 + 8 * g + 4 * lk) =
+                        make_float4(__builtin_fmaf(tq[4 * g + 0], IWS, bt[4 * g + 0]), __builtin_fmaf(tq[4 * g + 1], IWS, bt[4 * g + 1]),
+                                    __builtin_fmaf(tq[4 * g + 2], IWS, bt[4 * g + 2]), __builtin_fmaf(tq[4 * g + 3], IWS, bt[4 * g + 3]));
+            }
+#else
+            // (lab: the order and placement through round 7 -- q, k, v, the three epilogues behind the v step)
             X6_STEP1(3 * h, Yp, tq)
             X6_STEP1(3 * h + 1, Yp, tk)
             X6_STEP1(3 * h + 2, Yp, tv) // (builtin DMA: no ring refill behind this step, see X6_PUBLISH)
@@ -2592,6 +2679,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                     *reinterpret_cast<f16x4 *>(slot + 16384) = lp;
                 }
             }
+#endif
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             X6_PH(0)
             __builtin_amdgcn_s_barrier(); // every wave's rows of head h are in the images
@@ -2611,7 +2699,8 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                 }
             }
             asm volatile("" ::: "memory");
-            // (the next head's image writes come three steps -- three workgroup barriers -- later: every wave is past its reads)
+            // (the next head's first image writes ride its v step, behind the mid-step barrier of its k step: every wave is past its
+            //  reads.  SEQ_FRONT_RIDE = 0: they come three steps -- three workgroup barriers -- later.)
             X6_PH(2)
             if (!SEQ_ASM_DMA && 3 * h + 2 + LEAD < nsteps) issue(3 * h + 2 + LEAD); // (builtin DMA: the refill the v step left out)
         }
@@ -2903,6 +2992,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
 #undef last
 #undef X6_STEP
 #undef X6_STEP1
+#undef X6_STEP1R
 #undef X6_RD_V
 #undef X6_WAIT_V
 #undef X6_PUBLISH

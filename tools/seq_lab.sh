@@ -1,11 +1,14 @@
 # Lab builds of the library with a SEQ_EXP timing switch in k_block_x6<.., SEQ> (results are then WRONG): tools/seqlab_<n>.so.
-# usage: bash tools/seq_lab.sh 1 2 3 ...   (run here, in the build container; the .so files travel to the GPU box)
+# usage: bash tools/seq_lab.sh 1 2 3 ...   (run where the library was built; the .so files travel with the tree)
+# names: <n> = SEQ_EXP=<n>; stamp / stamp1 = phase stamps (/ per-step stamps too); builtin_dma; front0 = the front's steps in the
+# order q, k, v with the three epilogues behind the v step (SEQ_FRONT_RIDE=0; the shipped form is k, v, q with riding epilogues);
+# stamp_front0 = both
 set -e
 cd "$(dirname "$0")/.."
 OBJ=influentialrs_amd/csrc/_obj
 for n in "$@"; do
-  if [ "$n" = stamp ]; then DEF="-DX6_STAMP=2"; elif [ "$n" = stamp_builtin_dma ]; then DEF="-DX6_STAMP=2 -DSEQ_ASM_DMA=0"; elif [ "$n" = stamp1 ]; then DEF="-DX6_STAMP=1"; elif [ "$n" = builtin_dma ]; then DEF="-DSEQ_ASM_DMA=0"; else DEF="-DSEQ_EXP=$n"; fi
+  if [ "$n" = stamp ]; then DEF="-DX6_STAMP=2"; elif [ "$n" = stamp_builtin_dma ]; then DEF="-DX6_STAMP=2 -DSEQ_ASM_DMA=0"; elif [ "$n" = stamp1 ]; then DEF="-DX6_STAMP=1"; elif [ "$n" = builtin_dma ]; then DEF="-DSEQ_ASM_DMA=0"; elif [ "$n" = front0 ]; then DEF="-DSEQ_FRONT_RIDE=0"; elif [ "$n" = stamp_front0 ]; then DEF="-DX6_STAMP=2 -DSEQ_FRONT_RIDE=0"; else DEF="-DSEQ_EXP=$n"; fi
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -DIRS_LAB $DEF -c influentialrs_amd/csrc/decoder.hip -o /tmp/decoder_seqlab_$n.o 2>/dev/null
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tools/seqlab_$n.so $OBJ/capi.o /tmp/decoder_seqlab_$n.o $OBJ/score.o $OBJ/path.o $OBJ/comm.o $OBJ/train.o $OBJ/ce_backward.o -ldl
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o tools/seqlab_$n.so $OBJ/capi.o /tmp/decoder_seqlab_$n.o $OBJ/score.o $OBJ/path.o $OBJ/comm.o $OBJ/train.o $OBJ/ce_backward.o $OBJ/ce_sharded.o $OBJ/survivors.o -ldl
   echo built tools/seqlab_$n.so
 done
