@@ -527,6 +527,46 @@ int irs_topk_ensure_survivors(irs_ctx *ctx, const float *dev_xrows, const int64_
                               void *dev_scratch, size_t scratch_bytes, void *stream);
 int irs_bind_survivor_scratch(irs_ctx *ctx, void *dev_scratch, size_t bytes);
 
+/* ---- bound exclusions: never offer an item the user has already seen (opt-in; BUILD-DEFINED: the reference's search filters
+ *      only the window, influentialRS.py:423-427, while its ranking metric filters the full raw history, :372-379) -------
+ * A context can hold a bound EXCLUSION SET.  While it does, every place that drops "the items in the row's window" drops
+ *   the window seq[row, 0 .. hep[row]], the row's user's exclusion list and, if no_repeat is on, the row's own non-zero
+ *   path entries paths[row, 0 .. step) (for a beam: the path of the input beam, i.e. of the parent of what it becomes)
+ * instead.  Everything else is as documented at the entry points: the order (score desc, id asc), greedy = the first
+ * survivor, sampled = the first sample_k survivors, beams = the first W survivors of every live beam, grow / shift of the
+ * window, the status bits, and IRS_ROW_NO_CANDIDATE when nothing survives (window, hep and path are then untouched); a
+ * finished beam of the until forms still contributes only itself, and its lists are not read.  With exact candidates bound
+ * as well (irs_bind_survivor_scratch), a row is starved when fewer than `want` entries of its list survive THIS test, and
+ * the pass returns the exact best items outside window + list (+ path).
+ *  dev_excl_ids0 int64 [users, n_excl], global 0-based ids, the format of irs_score_count_before's dev_excl_ids0: -1 marks
+ *            an unused slot (anywhere), duplicates are allowed, ids >= n_item never match.  n_excl in [0, 4096];
+ *            n_excl == 0 with a NULL list is legal together with no_repeat != 0 and means "no_repeat only".
+ *  no_repeat != 0 switches the path test on.  It needs the path in one wave: while it is bound, a call with a path length
+ *            (irs_path_step: a step index) above 64 returns IRS_E_UNSUPPORTED.
+ *  dev_scratch: caller-owned, >= irs_exclusion_scratch_bytes(users, n_excl) bytes = 4 users (rounded up to 16) + 8 users
+ *            stride, stride = n_excl rounded up to a power of two (0 for 0); 16-byte aligned.
+ * Binding enqueues ONE launch on `stream`, one workgroup per user: the row's valid ids (0 <= id < n_item) are sorted
+ * ascending in LDS and written to the scratch, followed by INT64_MAX up to `stride`, with the row's valid count.  The
+ * caller's list need not outlive the call; the scratch must stay valid, and untouched, until the unbind.  Every later
+ * membership test is a binary search in that sorted row (at most 13 probes), one candidate per lane, 64 per round.
+ * irs_bind_exclusions(ctx, NULL, 0, 0, 0, NULL, 0, stream) unbinds.  A second bind replaces the first.  Bind and unbind
+ * drop the captured steps of the context, as irs_bind_survivor_scratch does.
+ * Which list a row reads: irs_path_step, irs_generate_paths: row b's; irs_beam_step[_until], irs_beam_search[_until]: row /
+ * W; irs_topk_ensure_survivors: row / rows_per_status (it has no path argument and honours the list only);
+ * irs_generate_paths_until and irs_beam_search_until: the caller's original row, through the compaction map the loops keep
+ * -- a user keeps its own list after any number of compactions, and under no_repeat the greedy loop reads the path so far
+ * from the caller's dev_paths row through the same map.
+ * Refused before any launch: n_excl > 4096 and world != 1 -> IRS_E_UNSUPPORTED (the sharded loops return it too should a
+ * binding exist); n_excl < 0, users < 1, a list without n_excl >= 1 or n_excl >= 1 without a list, n_excl == 0 without
+ * no_repeat, a scratch that is NULL, too small or not 16-byte aligned -> IRS_E_INVALID.  While bound, a step or loop call
+ * with more users than were bound (B; M / rows_per_status) returns IRS_E_INVALID before any launch.
+ * The list is honoured by EVERY step and loop entry point while bound, the standalone steps included: unbind before an
+ * unrelated search.  The route where one workgroup ranks and steps a row is not taken while bound.  With nothing bound
+ * every entry point launches the kernels it launched before exclusions existed, and computes the same bits. */
+size_t irs_exclusion_scratch_bytes(const irs_ctx *ctx, int32_t users, int32_t n_excl); /* 0 for invalid arguments */
+int irs_bind_exclusions(irs_ctx *ctx, const int64_t *dev_excl_ids0, int32_t users, int32_t n_excl, int32_t no_repeat,
+                        void *dev_scratch, size_t bytes, void *stream);
+
 /* ---- multi-GPU: the exchange steps and the sharded search loops below the ABI (section 8 row B2's
  *      `allgather_merge(ctx, comm, ...)`).  One process per GPU; rank r holds item rows [item_lo, item_hi) (irs_shard).
  * A communicator is either RCCL (librccl.so is dlopen()ed on first use: ncclCommInitRank over a 128-byte unique id the

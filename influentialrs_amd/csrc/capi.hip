@@ -616,6 +616,57 @@ extern "C" int irs_build_eval_batch(irs_ctx *ctx, const int64_t *items, const in
     return irs_launch_build_eval_batch(ctx, a, (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ bound exclusions (irs_bind_exclusions)
+// What a kernel takes of the binding: all zero when nothing is bound.  div: rows per user slot; map: user slot -> bound user;
+// paths / path_ld / path_by_user: where a row's path so far lies (used under no_repeat only); the step index for the survivor pass
+static irs_excl excl_args(const irs_ctx *ctx, int div, const int32_t *map, const float *paths, int path_ld, int path_by_user,
+                          const int32_t *step_ptr, int step_arg) {
+    irs_excl e = {};
+    if (!ctx->excl_on) return e;
+    e.rows = ctx->excl_rows, e.cnt = ctx->excl_cnt, e.stride = ctx->excl_stride;
+    e.map = map, e.div = div;
+    if (ctx->excl_no_repeat) e.paths = paths, e.path_ld = path_ld, e.path_by_user = path_by_user, e.step_ptr = step_ptr, e.step_arg = step_arg;
+    e.on = 1;
+    return e;
+}
+// the call's users fit the binding; under no_repeat a wave holds the path in one entry per lane
+static int check_excl(irs_ctx *ctx, const char *fn, int users, int path_len) {
+    if (!ctx->excl_on) return IRS_OK;
+    if (users > ctx->excl_users) IRS_FAIL(ctx, IRS_E_INVALID, "%s: %d users, exclusions are bound for %d", fn, users, ctx->excl_users);
+    if (ctx->excl_no_repeat && path_len > IRS_MAX_PATH)
+        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: no_repeat is bound: path length %d > %d", fn, path_len, IRS_MAX_PATH);
+    return IRS_OK;
+}
+
+extern "C" size_t irs_exclusion_scratch_bytes(const irs_ctx *ctx, int32_t users, int32_t n_excl) {
+    if (!ctx || users < 1 || n_excl < 0 || n_excl > IRS_MAX_EXCL) return 0;
+    return irs_excl_scratch(users, n_excl);
+}
+
+extern "C" int irs_bind_exclusions(irs_ctx *ctx, const int64_t *excl_ids0, int32_t users, int32_t n_excl, int32_t no_repeat,
+                                   void *scratch, size_t bytes, void *stream) {
+    if (!ctx) return IRS_E_INVALID;
+    if (!excl_ids0 && users == 0 && n_excl == 0 && !no_repeat && !scratch && bytes == 0) { // unbind
+        if (ctx->excl_on) irs_drop_graphs(ctx);
+        ctx->excl_on = 0, ctx->excl_rows = nullptr, ctx->excl_cnt = nullptr, ctx->excl_users = ctx->excl_stride = ctx->excl_no_repeat = 0;
+        return IRS_OK;
+    }
+    if (n_excl < 0) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_exclusions: n_excl must be >= 0");
+    if (n_excl > IRS_MAX_EXCL) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_exclusions: n_excl %d > %d", n_excl, IRS_MAX_EXCL);
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_exclusions needs the whole catalog on one device");
+    if (users < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_exclusions: users must be >= 1");
+    if ((excl_ids0 == nullptr) != (n_excl == 0)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_exclusions: a list and n_excl >= 1 go together");
+    if (n_excl == 0 && !no_repeat) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_exclusions: neither a list nor no_repeat");
+    const size_t need = irs_excl_scratch(users, n_excl);
+    if (!scratch || bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_exclusions: scratch too small: %zu < %zu", scratch ? bytes : (size_t)0, need);
+    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_exclusions: scratch must be 16-byte aligned");
+    const int rc = irs_launch_excl_prepare(ctx, excl_ids0, users, n_excl, scratch, (hipStream_t)stream);
+    if (rc) return rc;
+    ctx->excl_on = 1, ctx->excl_users = users, ctx->excl_no_repeat = no_repeat ? 1 : 0;
+    irs_drop_graphs(ctx); // (a captured step holds the binding's pointers, or none)
+    return IRS_OK;
+}
+
 extern "C" int irs_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int32_t B, const float *val, const int64_t *ids0,
                              int32_t k, int32_t step, float *paths, int32_t path_ld, int32_t sample, int32_t sample_k,
                              uint64_t seed, int32_t *status, void *stream) {
@@ -624,7 +675,10 @@ extern "C" int irs_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int32_t B
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_path_step: bad arguments");
     if (sample && (sample_k < 1 || sample_k > IRS_MAX_SAMPLE_K))
         IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_path_step: sample_k must be in [1, %d]", IRS_MAX_SAMPLE_K);
-    const irs_path_args pa{seq, hep, ctx->dims.max_len, paths, path_ld, sample, sample_k, seed, status, nullptr, step, nullptr, 1};
+    const int rc = check_excl(ctx, "irs_path_step", B, step);
+    if (rc) return rc;
+    const irs_path_args pa{seq, hep, ctx->dims.max_len, paths, path_ld, sample, sample_k, seed, status, nullptr, step, nullptr, 1,
+                           excl_args(ctx, 1, nullptr, paths, path_ld, 1, nullptr, step)};
     return irs_launch_path_step(ctx, pa, B, val, ids0, k, (hipStream_t)stream);
 }
 
@@ -641,14 +695,15 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
     ctx->step_pair = nullptr;
     if (rc) return rc;
     // small shard, few rows: the workgroup that ranks a row's candidates also takes the row's path step
-    // (not while exact candidates are bound: the survivor pass goes between the ranking and the step)
-    if (merged && !ctx->surv_scratch && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k))
+    // (not while exact candidates are bound: the survivor pass goes between the ranking and the step; nor while exclusions are
+    //  bound: only the separate step kernel has the form that tests them)
+    if (merged && !ctx->surv_scratch && !ctx->excl_on && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k))
         return irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, &pa);
     if ((rc = irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, nullptr, nullptr, carry)))
         return rc;
     if (ctx->surv_scratch) {
         const irs_surv_args sa{ctx->xrows, pa.seq, pa.hep, B, 1, k, pa.sample ? pa.sample_k : 1, ctx->surv_rows, nullptr, surv_fin, nullptr,
-                               ctx->top_val, ctx->top_ids, pa.status, nullptr};
+                               ctx->top_val, ctx->top_ids, pa.status, nullptr, pa.ex};
         if ((rc = irs_launch_survivors(ctx, sa, ctx->surv_scratch, s))) return rc;
     }
     if ((rc = irs_launch_path_step(ctx, pa, B, ctx->top_val, ctx->top_ids, k, s))) return rc;
@@ -676,9 +731,11 @@ extern "C" int irs_topk_ensure_survivors(irs_ctx *ctx, const float *xrows, const
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_topk_ensure_survivors: scratch too small: %zu < %zu", scratch_bytes, irs_surv_scratch(ctx, M, want));
     if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_topk_ensure_survivors: scratch must be 16-byte aligned");
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_topk_ensure_survivors needs the whole catalog on one device");
-    const int rc = ready(ctx);
+    int rc = check_excl(ctx, "irs_topk_ensure_survivors", M / rows_per_status, 0);
     if (rc) return rc;
-    const irs_surv_args sa{xrows, seq, hep, M, rows_per_status, k, want, M, cum, fin, done, val, ids0, status, nullptr};
+    if ((rc = ready(ctx))) return rc;
+    const irs_surv_args sa{xrows, seq, hep, M, rows_per_status, k, want, M, cum, fin, done, val, ids0, status, nullptr,
+                           excl_args(ctx, rows_per_status, nullptr, nullptr, 0, 0, nullptr, 0)}; // (no path argument: the list only)
     return irs_launch_survivors(ctx, sa, scratch, (hipStream_t)stream);
 }
 
@@ -754,6 +811,7 @@ static int check_search(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W
         if (B > ctx->max_seqs || B > ctx->max_rows) IRS_FAIL(ctx, IRS_E_INVALID, "%s: B too large", fn);
     }
     if ((rc = irs_check_k(ctx, fn, k, 1, sweep, sample, sample_k))) return rc;
+    if ((rc = check_excl(ctx, fn, B, P))) return rc;
     if (ctx->surv_scratch) { // exact candidates: the bound scratch must serve this call's rows
         const int rows = W ? B * W : B, want = W ? W : (sample ? sample_k : 1);
         if (want > k) IRS_FAIL(ctx, IRS_E_INVALID, "%s: exact candidates need k >= %d", fn, want);
@@ -765,9 +823,12 @@ static int check_search(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W
 }
 
 // the path step's arguments inside a search loop: the step index comes from the device counter
+// (`out_paths`: the caller's path rows, which a bound no_repeat reads back: row b in irs_generate_paths, the compaction map's in
+//  the until loop, whose steps write `paths` = the stage)
 static irs_path_args loop_path_args(irs_ctx *ctx, int64_t *seq, int32_t *hep, float *paths, int P, int sample, int sample_k,
-                                    uint64_t seed, int32_t *status) {
-    return irs_path_args{seq, hep, ctx->dims.max_len, paths, P, sample, sample_k, seed, status, ctx->step_ctr, 0, nullptr, 1};
+                                    uint64_t seed, int32_t *status, const float *out_paths) {
+    return irs_path_args{seq, hep, ctx->dims.max_len, paths, P, sample, sample_k, seed, status, ctx->step_ctr, 0, nullptr, 1,
+                         excl_args(ctx, 1, nullptr, out_paths, P, 1, ctx->step_ctr, 0)};
 }
 
 // The check of the two until loops: places of the live rows in un_dst (irs_launch_until_scan over `fin`), their number in *left
@@ -804,7 +865,7 @@ extern "C" int irs_generate_paths(irs_ctx *ctx, int64_t *seq, const int64_t *use
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
-    const irs_path_args pa = loop_path_args(ctx, seq, hep, paths, max_path_len, sample, sample_k, seed, status);
+    const irs_path_args pa = loop_path_args(ctx, seq, hep, paths, max_path_len, sample, sample_k, seed, status, paths);
     if (irs_may_capture(ctx, use_graph)) { // one step per graph; a captured step never carries emission thresholds
         irs_step_key key = {};
         key.kind = IRS_STEP_GREEDY, key.B = B, key.P = max_path_len, key.k = k, key.sweep = sweep;
@@ -839,7 +900,7 @@ extern "C" int irs_generate_paths_until(irs_ctx *ctx, int64_t *seq, const int64_
     IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->un_status, 0, sizeof(int32_t) * B, s));
     // the first steps run in place on the caller's rows (identity map); the first compaction that removes a row moves the rest.
     // (the step writes stage[row][i]: it reads the index from the same device counter as irs_generate_paths' steps)
-    irs_path_args pa = loop_path_args(ctx, seq, hep, ctx->un_stage, P, sample, sample_k, seed, ctx->un_status);
+    irs_path_args pa = loop_path_args(ctx, seq, hep, ctx->un_stage, P, sample, sample_k, seed, ctx->un_status, paths);
     const int64_t *cuser = user;
     const int32_t *cmap = nullptr;
     int live = B, side = 0, carry = 0;
@@ -860,6 +921,7 @@ extern "C" int irs_generate_paths_until(irs_ctx *ctx, int64_t *seq, const int64_
                                               ctx->un_hep[side], ctx->un_map[side], s)))
                 return rc;
             pa.seq = ctx->un_seq[side], cuser = cuser ? ctx->un_user[side] : nullptr, pa.hep = ctx->un_hep[side], cmap = ctx->un_map[side];
+            pa.ex.map = cmap; // (a compacted row keeps its user's list, and under no_repeat its row of the caller's paths)
             side ^= 1;
             IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->un_fin, 0, sizeof(int32_t) * left, s));
             // B <= 64 hands the step index over in a second word that larger batches do not keep: both words, from the host's count
@@ -888,7 +950,10 @@ extern "C" int irs_beam_step(irs_ctx *ctx, const int64_t *seq_in, const int32_t 
         !status || B < 1 || W < 1 || k < 1 || P < 1 || step < 0 || step >= P)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step: bad arguments");
     if (W > 1 && (!lse_max || !lse_sum)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step: W > 1 needs the row log-sum-exp");
-    const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k};
+    const int rc = check_excl(ctx, "irs_beam_step", B, P);
+    if (rc) return rc;
+    const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k,
+                             excl_args(ctx, W, nullptr, paths_in, P, 0, nullptr, step)};
     return irs_launch_beam_step(ctx, beam_state(seq_in, hep_in, cum_in, paths_in, nullptr), {seq_out, hep_out, cum_out, paths_out, nullptr},
                                 cand, B, W, step, nullptr, P, status, nullptr, (hipStream_t)stream);
 }
@@ -896,8 +961,8 @@ extern "C" int irs_beam_step(irs_ctx *ctx, const int64_t *seq_in, const int32_t 
 // The tail of every beam loop's step, the sharded one's too: the beam step from side `in` to the other on the lists in top_val /
 // top_ids, then the step counter.  until == nullptr: the plain step
 int irs_enqueue_beam_tail(irs_ctx *ctx, int in, const float *lse_max, const float *lse_sum, int B, int W, int k, int P, int32_t *status,
-                          const irs_beam_until *until, hipStream_t s) {
-    const irs_beam_cand cand{ctx->top_val, ctx->top_ids, lse_max, lse_sum, k};
+                          const irs_beam_until *until, hipStream_t s, const irs_excl *ex) {
+    const irs_beam_cand cand{ctx->top_val, ctx->top_ids, lse_max, lse_sum, k, ex ? *ex : irs_excl{}};
     const int rc = irs_launch_beam_step(ctx, ctx->bm[in], ctx->bm[in ^ 1], cand, B, W, 0, ctx->step_ctr, P, status, until, s);
     return rc ? rc : irs_launch_inc(ctx, ctx->step_ctr, s);
 }
@@ -912,13 +977,15 @@ static int enqueue_beam_step(irs_ctx *ctx, int in, const int64_t *user, int B, i
     // W > 1: top-k and log-sum-exp out of one call (one pass over the float32 catalog on the swept path)
     if ((rc = irs_launch_topk(ctx, ctx->xrows, rows, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, lmax, lsum)))
         return rc;
+    // bound exclusions: a beam row's user through the loop's map, its path so far in the step's input state
+    const irs_excl ex = excl_args(ctx, W, until ? until->map : nullptr, ctx->bm[in].paths, P, 0, ctx->step_ctr, 0);
     if (ctx->surv_scratch) { // exact candidates: a live unfinished beam of a user that is not done sees its best W admissible items
         const irs_surv_args sa{ctx->xrows, ctx->bm[in].seq, ctx->bm[in].hep, rows, W, k, W, ctx->surv_rows, ctx->bm[in].cum,
                                until ? ctx->bm[in].fin : nullptr, until ? until->done : nullptr, ctx->top_val, ctx->top_ids, status,
-                               until ? until->map : nullptr};
+                               until ? until->map : nullptr, ex};
         if ((rc = irs_launch_survivors(ctx, sa, ctx->surv_scratch, s))) return rc;
     }
-    return irs_enqueue_beam_tail(ctx, in, lmax, lsum, B, W, k, P, status, until, s);
+    return irs_enqueue_beam_tail(ctx, in, lmax, lsum, B, W, k, P, status, until, s, &ex);
 }
 
 extern "C" int irs_beam_search(irs_ctx *ctx, const int64_t *seq0, const int64_t *user, const int32_t *hep0, int32_t B,
@@ -960,7 +1027,10 @@ extern "C" int irs_beam_step_until(irs_ctx *ctx, const int64_t *seq_in, const in
     if (W > 1 && (!lse_max || !lse_sum)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_until: W > 1 needs the row log-sum-exp");
     if (stop_rule != IRS_BEAM_STOP_ALL && stop_rule != IRS_BEAM_STOP_BEST)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_until: stop_rule %d (IRS_BEAM_STOP_ALL or IRS_BEAM_STOP_BEST)", stop_rule);
-    const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k};
+    const int rc = check_excl(ctx, "irs_beam_step_until", B, P);
+    if (rc) return rc;
+    const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k,
+                             excl_args(ctx, W, nullptr, paths_in, P, 0, nullptr, step)};
     const irs_beam_until until{done, nullptr, stop_rule};
     return irs_launch_beam_step(ctx, beam_state(seq_in, hep_in, cum_in, paths_in, fin_in), {seq_out, hep_out, cum_out, paths_out, fin_out},
                                 cand, B, W, step, nullptr, P, status, &until, (hipStream_t)stream);

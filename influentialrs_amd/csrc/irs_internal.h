@@ -49,6 +49,7 @@ static inline int irs_cur_dev() {
 #define IRS_REFINE_CAP 1024 // candidates exactly re-scored per row
 #define IRS_MAX_GROUPS 2048 // pre-pass group maxima per row (upper bound: the pre-pass is decomposed to stay below it)
 #define IRS_MAX_PATH 64     // beam-search path length bound
+#define IRS_MAX_EXCL 4096   // ids of a user's bound exclusion list (irs_bind_exclusions): one LDS sort, <= 13 probes per search
 #define IRS_LSE_SLOTS_RING 4096 // (max, sum) partial slots of the <= 32-row ring log-sum-exp sweep: 2048 waves x 2 lane halves
 #define IRS_COOP_FALLBACK_MIN_ITEMS 262144 // shards from this size up redo flagged rows cooperatively (score.hip: k_exh_strips)
 #define IRS_EXH_SCRATCH_KEYS (64 * 32768)  // EXH_FB_MAX x EXH_KEYS_PER_ROW keys of scratch for it
@@ -79,6 +80,19 @@ struct irs_step_graph {
     irs_step_key key;
 };
 
+// ---- bound exclusions as the kernels take them (irs_bind_exclusions; capi.hip: excl_args).  All zero: nothing is bound, and
+// every launcher then takes the kernel form without the test (what the library launched before exclusions existed).
+struct irs_excl {
+    const int64_t *rows;     // [users][stride] a user's valid ids0, ascending, INT64_MAX behind them
+    const int32_t *cnt;      // [users] valid ids of the row
+    const int32_t *map;      // user slot of this call -> bound user (the until loops' compaction map); null: the identity
+    const float *paths;      // no_repeat: the path rows whose non-zero entries [0, step) are dropped too; null: off
+    const int32_t *step_ptr; // the survivor pass's step index (the step kernels pass their own): device counter, or step_arg
+    int stride, div;         // div: rows per user slot (1, W, or rows_per_status): row r belongs to slot r / div
+    int path_ld, path_by_user; // the path row is the bound user's (the greedy loops: the caller's rows) or row r itself (beam state)
+    int step_arg, on;
+};
+
 // ---- beam-search state.  A step reads one side of the ping-pong state and writes the other; the kernels take these by value.
 struct irs_beam_state {
     int64_t *seq; // [max_seqs][L]
@@ -98,6 +112,7 @@ struct irs_beam_cand { // the candidate lists of a step's rows; lse_* null: W ==
     const int64_t *ids0;
     const float *lse_max, *lse_sum;
     int k;
+    irs_excl ex; // bound exclusions (zero: none); the path rows are the step's input state
 };
 struct irs_beam_until { // what a step of the until forms takes besides (map as in irs_beam_side)
     int32_t *done;
@@ -229,6 +244,13 @@ struct irs_ctx {
     size_t surv_bytes;
     int surv_rows; // rows of the running search call (its first step's): the scratch layout its later, smaller steps keep
 
+    // bound exclusions (irs_bind_exclusions): the prepared rows in the caller's scratch while bound; every step and loop entry
+    // point then drops window + list (+ path under no_repeat), the sharded loops refuse
+    int excl_on;                // a binding exists (a list, no_repeat, or both)
+    const int32_t *excl_cnt;    // [excl_users] valid ids of a user's row
+    const int64_t *excl_rows;   // [excl_users][excl_stride] ascending, INT64_MAX behind the valid ids
+    int excl_users, excl_stride, excl_no_repeat;
+
     // profiling
     int prof_family;
     irs_prof_ev *prof_ev;
@@ -273,7 +295,7 @@ int irs_check_beam_args(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W
 int irs_ready_filter(irs_ctx *ctx, int sweep); // finalized, workspace bound, and no stale bf16 catalog under a filtering sweep
 // beam step from ctx->bm[in] to ctx->bm[in ^ 1] on the lists in top_val / top_ids, then the step counter (until == nullptr: plain)
 int irs_enqueue_beam_tail(irs_ctx *ctx, int in, const float *lse_max, const float *lse_sum, int B, int W, int k, int P, int32_t *status,
-                          const irs_beam_until *until, hipStream_t s);
+                          const irs_beam_until *until, hipStream_t s, const irs_excl *ex = nullptr);
 int irs_search_begin(irs_ctx *ctx, int32_t *status, int B, hipStream_t s); // step counter and status to zero
 int irs_beam_finish(irs_ctx *ctx, size_t rows, int P, float *paths, double *scores, int64_t *seq_final, hipStream_t s);
 
@@ -336,7 +358,10 @@ struct irs_surv_args {
     int64_t *ids0;       // [M][k] in / out
     int32_t *status;     // IRS_ROW_RESCUED goes to status[u], u = row / rps, or to status[status_map[u]]
     const int32_t *status_map;
+    irs_excl ex;         // bound exclusions (zero: none)
 };
+size_t irs_excl_scratch(int users, int n_excl);
+int irs_launch_excl_prepare(irs_ctx *ctx, const int64_t *ids0, int users, int n_excl, void *scratch, hipStream_t s);
 size_t irs_surv_scratch(const irs_ctx *ctx, int rows, int want);
 int irs_launch_survivors(irs_ctx *ctx, const irs_surv_args &a, void *scratch, hipStream_t s);
 
@@ -433,7 +458,47 @@ struct irs_path_args {
     int step_arg;
     int32_t *step_next;
     int enabled;
+    irs_excl ex; // bound exclusions (zero: none)
 };
+
+// ---- membership in a bound exclusion set: the ONE test of the path step, the beam steps and the survivor pass.
+// A wave opens its row's view once: the user's sorted list, and (no_repeat) path entry `lane` of the row as an item, -1 for
+// none.  irs_excl_listed is the per-lane half: a binary search of one 0-based id in the sorted list (<= 13 probes at 4096
+// ids); the callers ballot it over the 64 candidates of a round.  The per-wave half is `view.pth == item`, OR-ed into the
+// window compare that the callers already reduce with __any.
+struct irs_excl_view {
+    const int64_t *list;
+    int n;
+    int64_t pth;
+};
+__device__ __forceinline__ bool irs_excl_listed(const int64_t *__restrict__ list, int n, int64_t id0) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (list[mid] < id0) lo = mid + 1;
+        else hi = mid;
+    }
+    return id0 >= 0 && lo < n && list[lo] == id0;
+}
+__device__ __forceinline__ int irs_excl_user(const irs_excl &ex, int row) {
+    const int slot = row / ex.div;
+    return ex.map ? ex.map[slot] : slot;
+}
+__device__ __forceinline__ irs_excl_view irs_excl_open(const irs_excl &ex, int row, int lane, int step) {
+    const int user = irs_excl_user(ex, row);
+    irs_excl_view v;
+    v.list = ex.rows ? ex.rows + (size_t)user * ex.stride : nullptr;
+    v.n = ex.rows ? ex.cnt[user] : 0;
+    v.pth = -1;
+    if (ex.paths && lane < step && lane < ex.path_ld) {
+        const float f = ex.paths[(size_t)(ex.path_by_user ? user : row) * ex.path_ld + lane];
+        if (f != 0.f) v.pth = (int64_t)f;
+    }
+    return v;
+}
+
+// EXCL: the form with a bound exclusion set (p_.ex.on); without it the body is the one the library always had.
+template <bool EXCL = false>
 __device__ __forceinline__ void irs_path_step_row(const irs_path_args &p_, int row, int lane, const float *__restrict__ val,
                                                   const int64_t *__restrict__ ids0, int k) {
     const int L = p_.L, path_ld = p_.path_ld, sample = p_.sample;
@@ -462,17 +527,43 @@ __device__ __forceinline__ void irs_path_step_row(const irs_path_args &p_, int r
     int64_t surv_id[IRS_MAX_SAMPLE_K];
     if (sample_k > IRS_MAX_SAMPLE_K) sample_k = IRS_MAX_SAMPLE_K; // the entry points reject larger values
     const int want = sample ? sample_k : 1;
-    for (int c = 0; c < k && found < want; ++c) {
-        int64_t id0 = ids0[(size_t)row * k + c];
-        if (id0 < 0) break;
-        int64_t item = id0 + 1;
-        bool hit = false;
+    if constexpr (EXCL) { // 64 candidates per round, one per lane: each lane searches its own in the user's list, one ballot
+        const irs_excl_view ev = irs_excl_open(p_.ex, row, lane, step);
+        bool more = true;
+        for (int c0 = 0; c0 < k && found < want && more; c0 += 64) {
+            const int cl = c0 + lane;
+            const int64_t cid = cl < k ? ids0[(size_t)row * k + cl] : (int64_t)-1;
+            const unsigned long long listed = __ballot(irs_excl_listed(ev.list, ev.n, cid));
+            for (int c = 0; c < 64 && c0 + c < k && found < want; ++c) {
+                const int64_t id0 = __shfl(cid, c, 64);
+                if (id0 < 0) {
+                    more = false;
+                    break;
+                }
+                const int64_t item = id0 + 1;
+                bool hit = (ev.pth == item);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) hit |= (wv[i] == item);
-        if (!__any(hit)) {
-            surv_val[found] = val[(size_t)row * k + c];
-            surv_id[found] = item;
-            ++found;
+                for (int i = 0; i < 4; ++i) hit |= (wv[i] == item);
+                if (!__any(hit) && !((listed >> c) & 1ull)) {
+                    surv_val[found] = val[(size_t)row * k + c0 + c];
+                    surv_id[found] = item;
+                    ++found;
+                }
+            }
+        }
+    } else {
+        for (int c = 0; c < k && found < want; ++c) {
+            int64_t id0 = ids0[(size_t)row * k + c];
+            if (id0 < 0) break;
+            int64_t item = id0 + 1;
+            bool hit = false;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) hit |= (wv[i] == item);
+            if (!__any(hit)) {
+                surv_val[found] = val[(size_t)row * k + c];
+                surv_id[found] = item;
+                ++found;
+            }
         }
     }
     if (found == 0) {

@@ -8,12 +8,14 @@
 #include "irs_internal.h"
 
 // One wave per row (the row body lives in irs_internal.h: the one-launch small-shard top-k runs it in its tail).
+// EXCL: with a bound exclusion set (irs_bind_exclusions); launched only while one is bound.
+template <bool EXCL>
 __global__ void __launch_bounds__(256) k_path_step(const irs_path_args pa, int B, const float *__restrict__ val,
                                                    const int64_t *__restrict__ ids0, int k) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= B) return;
-    irs_path_step_row(pa, row, lane, val, ids0, k);
+    irs_path_step_row<EXCL>(pa, row, lane, val, ids0, k);
 }
 
 __global__ void k_inc(int32_t *ctr) {
@@ -107,8 +109,11 @@ __global__ void __launch_bounds__(256) k_merge(const float *__restrict__ val_in,
 // a max taken over rounded scores), val - max can exceed 0 by an ulp of the score, and an unfinished beam within that ulp
 // behind beam 0 could still overtake it under IRS_BEAM_STOP_ALL; BEST then returns the earlier answer.
 // The instantiation without UNTIL is the kernel as it was: every addition sits behind `if constexpr`.
+// EXCL (irs_bind_exclusions): a beam's survivors are its candidates outside window + the user's bound list + (no_repeat) the
+// beam's own path so far, in.paths[row, 0 .. step): the parent's path of whatever it becomes.  All beams of a user read one list.
+// A finished beam and a dead beam open nothing.  Without EXCL the kernel is, again, the one it was.
 #define BEAM_MAXW 32
-template <bool UNTIL>
+template <bool UNTIL, bool EXCL>
 __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, const irs_beam_state out, const irs_beam_cand cand,
                                                     int W, int L, int step_arg, const int32_t *__restrict__ step_ptr, int P,
                                                     int32_t *__restrict__ status, const irs_beam_until until) {
@@ -164,11 +169,15 @@ __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, con
             }
             double norm = 0.0;
             if (cand.lse_max) norm = (double)cand.lse_max[row] + log((double)cand.lse_sum[row]);
+            irs_excl_view ev = {};
+            if constexpr (EXCL) ev = irs_excl_open(cand.ex, row, lane, step);
             bool more = true;
             for (int c0 = 0; c0 < k && found < W && more; c0 += 64) { // 64 candidates per round, one per lane
                 const int cl = c0 + lane;
                 const int64_t cid = cl < k ? cand.ids0[(size_t)row * k + cl] : (int64_t)-1;
                 const float cv = cl < k ? cand.val[(size_t)row * k + cl] : 0.f;
+                unsigned long long listed = 0ull;
+                if constexpr (EXCL) listed = __ballot(irs_excl_listed(ev.list, ev.n, cid));
                 for (int c = 0; c < 64 && c0 + c < k && found < W; ++c) {
                     const int64_t id0 = __shfl(cid, c, 64);
                     if (id0 < 0) { // end of the list (fewer than k items on this shard / excluded)
@@ -177,8 +186,10 @@ __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, con
                     }
                     const int64_t item = id0 + 1;
                     bool hit = false;
+                    if constexpr (EXCL) hit = (ev.pth == item);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) hit |= (wv[q] == item);
+                    if constexpr (EXCL) hit |= (bool)((listed >> c) & 1ull);
                     if (!__any(hit)) {
                         const float v = __shfl(cv, c, 64);
                         if (lane == 0) {
@@ -294,8 +305,10 @@ int irs_launch_beam_step(irs_ctx *ctx, const irs_beam_state &in, const irs_beam_
     if (W < 1 || W > BEAM_MAXW) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam width %d outside [1, %d]", W, BEAM_MAXW);
     if (ctx->dims.max_len > 256) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam step: window length %d > 256", ctx->dims.max_len);
     const int waves = W < 4 ? 4 : (W > 16 ? 16 : W);
-    hipLaunchKernelGGL(until ? k_beam_step<true> : k_beam_step<false>, dim3(B), dim3(64 * waves), 0, s, in, out, cand, W,
-                       ctx->dims.max_len, step, step_ptr, P, status, until ? *until : irs_beam_until{});
+    const auto kern = cand.ex.on ? (until ? k_beam_step<true, true> : k_beam_step<false, true>)
+                                 : (until ? k_beam_step<true, false> : k_beam_step<false, false>);
+    hipLaunchKernelGGL(kern, dim3(B), dim3(64 * waves), 0, s, in, out, cand, W, ctx->dims.max_len, step, step_ptr, P, status,
+                       until ? *until : irs_beam_until{});
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }
@@ -371,7 +384,7 @@ int irs_launch_pack_topk(irs_ctx *ctx, const float *val, const int64_t *ids0, in
 }
 
 int irs_launch_path_step(irs_ctx *ctx, const irs_path_args &pa, int B, const float *val, const int64_t *ids0, int k, hipStream_t s) {
-    hipLaunchKernelGGL(k_path_step, dim3((B + 3) / 4), dim3(256), 0, s, pa, B, val, ids0, k);
+    hipLaunchKernelGGL(pa.ex.on ? k_path_step<true> : k_path_step<false>, dim3((B + 3) / 4), dim3(256), 0, s, pa, B, val, ids0, k);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }

@@ -8,6 +8,8 @@
 //   k_surv_merge   one workgroup per recorded row: the best `want` of the strips' keys become the row's list.
 // The last two return at once when nothing was recorded.  No float atomics, and a row's result does not depend on its place
 // in the recorded list: two identical calls give identical bits.
+// With a bound exclusion set (irs_bind_exclusions; the EXCL forms, launched only while one is bound) "window" reads "window +
+// the user's list + (no_repeat) the row's path so far" in all of the above; k_excl_prepare, at the end, is the binding's launch.
 #include "irs_internal.h"
 
 #define SURV_STRIPS 256          // item strips of a large shard
@@ -34,7 +36,8 @@ size_t irs_surv_scratch(const irs_ctx *ctx, int rows, int want) {
 // ---- flag pass: one wave per row.  The list is walked in order, 64 ids at a time (one per lane, broadcast by shuffle): it ends
 // at the first negative id (a list that ended early is the whole catalog: not starved), and the walk stops as soon as `want`
 // survivors are seen.  Only a row that shows all k valid entries and fewer than `want` survivors is recorded.
-__global__ void __launch_bounds__(256) k_surv_flag(const int64_t *__restrict__ seq, int L, const int32_t *__restrict__ hep, int M,
+template <bool EXCL>
+__global__ void __launch_bounds__(256) k_surv_flag(const irs_excl ex, const int64_t *__restrict__ seq, int L, const int32_t *__restrict__ hep, int M,
                                                    int rps, int k, int want, const double *__restrict__ cum,
                                                    const int32_t *__restrict__ fin, const int32_t *__restrict__ done,
                                                    const int64_t *__restrict__ ids0, unsigned int *__restrict__ count,
@@ -55,10 +58,14 @@ __global__ void __launch_bounds__(256) k_surv_flag(const int64_t *__restrict__ s
     }
     int found = 0;
     bool ended = false;
+    irs_excl_view ev = {};
+    if constexpr (EXCL) ev = irs_excl_open(ex, row, lane, ex.step_ptr ? ex.step_ptr[0] : ex.step_arg);
     for (int c0 = 0; c0 < k && !ended && found < want; c0 += 64) {
         const int c = c0 + lane;
         const long long mine = c < k ? (long long)ids0[(size_t)row * k + c] : -1ll;
         const int n_here = k - c0 < 64 ? k - c0 : 64;
+        unsigned long long listed = 0ull;
+        if constexpr (EXCL) listed = __ballot(irs_excl_listed(ev.list, ev.n, (int64_t)mine));
         for (int i = 0; i < n_here; ++i) {
             const long long id0 = __shfl(mine, i, 64);
             if (id0 < 0) {
@@ -67,6 +74,7 @@ __global__ void __launch_bounds__(256) k_surv_flag(const int64_t *__restrict__ s
             }
             const int64_t item = id0 + 1;
             bool hit = false;
+            if constexpr (EXCL) hit = (ev.pth == item) || ((listed >> i) & 1ull);
 #pragma unroll
             for (int q = 0; q < 4; ++q) hit |= (wv[q] == item);
             if (!__any(hit) && ++found >= want) break;
@@ -141,15 +149,19 @@ __device__ __forceinline__ unsigned int surv_select(KeyFn &&keyfn, AdmitFn &&adm
 // ---- exhaustive pass over the strips.  grid (strips, y): workgroup (s, y) serves recorded rows y, y + gridDim.y, ... on strip s,
 // so one pass over the float32 shard serves all recorded rows together (a strip stays in cache from row to row).  The row's
 // window ids are sorted into LDS once per (workgroup, row); an item is searched there only after its key has beaten the
-// running threshold.
-__global__ void __launch_bounds__(256) k_surv_strips(const float *__restrict__ x, int d, const float *__restrict__ W,
+// running threshold.  EXCL: the row's path entries are sorted in with the window (INT64_MAX fills both), and an item that is in
+// neither is searched in the user's bound row.
+template <bool EXCL>
+__global__ void __launch_bounds__(256) k_surv_strips(const irs_excl ex, const float *__restrict__ x, int d, const float *__restrict__ W,
                                                      const float *__restrict__ bias, int64_t n_local, int64_t item_lo,
                                                      const int64_t *__restrict__ seq, int L, const int32_t *__restrict__ hep,
                                                      int want, int n_strips, const unsigned int *__restrict__ count,
                                                      const int32_t *__restrict__ list, unsigned long long *__restrict__ keys) {
     __shared__ unsigned long long buf[SURV_BUF];
     __shared__ float xs[256];
-    __shared__ long long win[256];
+    constexpr int WIN = EXCL ? 512 : 256; // EXCL: 256 window slots + IRS_MAX_PATH path slots, up to a power of two for the sort
+    static_assert(256 + IRS_MAX_PATH <= 512, "path entries share the sorted window");
+    __shared__ long long win[WIN];
     const unsigned int n_rows = *count;
     if (n_rows == 0u) return;
     const int tid = threadIdx.x;
@@ -163,7 +175,14 @@ __global__ void __launch_bounds__(256) k_surv_strips(const float *__restrict__ x
         __syncthreads();
         for (int i = tid; i < d; i += 256) xs[i] = x[(size_t)row * d + i];
         win[tid] = tid < wl ? (long long)seq[(size_t)row * L + tid] : 0x7FFFFFFFFFFFFFFFll; // (L <= 256 = the workgroup)
-        surv_bitonic<long long, false>(win, 256);
+        const int64_t *xl = nullptr; // EXCL: the user's bound row
+        int xn = 0;
+        if constexpr (EXCL) { // (thread tid < IRS_MAX_PATH opens path entry tid)
+            const irs_excl_view ev = irs_excl_open(ex, row, tid, ex.step_ptr ? ex.step_ptr[0] : ex.step_arg);
+            win[256 + tid] = (tid < IRS_MAX_PATH && ev.pth > 0) ? (long long)ev.pth : 0x7FFFFFFFFFFFFFFFll;
+            xl = ev.list, xn = ev.n;
+        }
+        surv_bitonic<long long, false>(win, WIN);
         const unsigned int n = surv_select(
             [&](int64_t j) -> unsigned long long {
                 const float e = irs_chain(xs, W + (size_t)j * d, bias[j], d);
@@ -171,13 +190,15 @@ __global__ void __launch_bounds__(256) k_surv_strips(const float *__restrict__ x
             },
             [&](unsigned long long key) -> bool { // the item is not in win[0 .. wl)
                 const long long item = (long long)(item_lo + (int64_t)(0xFFFFFFFFu - (unsigned int)key) + 1);
-                int lo = 0, hi = wl;
+                const int wn = EXCL ? WIN : wl; // (EXCL: window and path entries lie mixed in front of the fill)
+                int lo = 0, hi = wn;
                 while (lo < hi) {
                     const int mid = (lo + hi) >> 1;
                     if (win[mid] < item) lo = mid + 1;
                     else hi = mid;
                 }
-                return !(lo < wl && win[lo] == item);
+                if constexpr (EXCL) return !(lo < wn && win[lo] == item) && !irs_excl_listed(xl, xn, (int64_t)item - 1);
+                return !(lo < wn && win[lo] == item);
             },
             j0, j1, want, buf);
         unsigned long long *o = keys + ((size_t)fi * n_strips + strip) * want;
@@ -220,14 +241,60 @@ int irs_launch_survivors(irs_ctx *ctx, const irs_surv_args &a, void *scratch, hi
     unsigned long long *keys = (unsigned long long *)((char *)list + surv_align16((size_t)a.rows_cap * sizeof(int32_t)));
     const int L = ctx->dims.max_len;
     IRS_CHECK_HIP(ctx, hipMemsetAsync(count, 0, sizeof(unsigned int), s));
-    hipLaunchKernelGGL(k_surv_flag, dim3((a.M + 3) / 4), dim3(256), 0, s, a.seq, L, a.hep, a.M, a.rps, a.k, a.want, a.cum, a.fin, a.done,
+    hipLaunchKernelGGL(a.ex.on ? k_surv_flag<true> : k_surv_flag<false>, dim3((a.M + 3) / 4), dim3(256), 0, s, a.ex, a.seq, L, a.hep, a.M, a.rps, a.k, a.want, a.cum, a.fin, a.done,
                        a.ids0, count, list);
     int ny = 4096 / ns < 4 ? 4 : (4096 / ns > SURV_ROW_GROUPS ? SURV_ROW_GROUPS : 4096 / ns);
     if (ny > a.M) ny = a.M;
-    hipLaunchKernelGGL(k_surv_strips, dim3(ns, ny), dim3(256), 0, s, a.xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b, ctx->n_local,
+    hipLaunchKernelGGL(a.ex.on ? k_surv_strips<true> : k_surv_strips<false>, dim3(ns, ny), dim3(256), 0, s, a.ex, a.xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b, ctx->n_local,
                        ctx->shard.item_lo, a.seq, L, a.hep, a.want, ns, count, list, keys);
     hipLaunchKernelGGL(k_surv_merge, dim3(a.M < SURV_ROW_GROUPS ? a.M : SURV_ROW_GROUPS), dim3(256), 0, s, ctx->shard.item_lo, a.k, a.want, ns, a.rps, count, list,
                        keys, a.status_map, a.val, a.ids0, a.status);
     IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
+// ------------------------------------------------------------------ bound exclusions: the binding's one launch
+// One workgroup per user: the valid ids of the caller's row (0 <= id < n_item; -1 holes anywhere, duplicates kept) sorted
+// ascending in LDS, INT64_MAX behind them up to `stride` (the power of two the scratch rows have), and their number.
+static int excl_stride(int n_excl) {
+    int n2 = 1;
+    while (n2 < n_excl) n2 <<= 1;
+    return n_excl > 0 ? n2 : 0;
+}
+
+size_t irs_excl_scratch(int users, int n_excl) {
+    return surv_align16((size_t)users * sizeof(int32_t)) + (size_t)users * excl_stride(n_excl) * sizeof(int64_t);
+}
+
+__global__ void __launch_bounds__(256) k_excl_prepare(const int64_t *__restrict__ ids0, int n_excl, int stride, int64_t n_item,
+                                                      int32_t *__restrict__ cnt, int64_t *__restrict__ rows) {
+    __shared__ long long a[IRS_MAX_EXCL];
+    __shared__ int s_n;
+    const int u = blockIdx.x, tid = threadIdx.x;
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int i = tid; i < stride; i += 256) {
+        const long long id = i < n_excl ? (long long)ids0[(size_t)u * n_excl + i] : -1ll;
+        const bool ok = id >= 0 && id < (long long)n_item;
+        a[i] = ok ? id : 0x7FFFFFFFFFFFFFFFll;
+        mine += ok ? 1 : 0;
+    }
+    if (mine) atomicAdd(&s_n, mine);
+    if (stride > 1) surv_bitonic<long long, false>(a, stride);
+    else __syncthreads();
+    for (int i = tid; i < stride; i += 256) rows[(size_t)u * stride + i] = (int64_t)a[i];
+    if (tid == 0) cnt[u] = s_n;
+}
+
+int irs_launch_excl_prepare(irs_ctx *ctx, const int64_t *ids0, int users, int n_excl, void *scratch, hipStream_t s) {
+    int32_t *cnt = (int32_t *)scratch;
+    int64_t *rows = (int64_t *)((char *)scratch + surv_align16((size_t)users * sizeof(int32_t)));
+    const int stride = excl_stride(n_excl);
+    hipLaunchKernelGGL(k_excl_prepare, dim3(users), dim3(256), 0, s, ids0, n_excl, stride, ctx->dims.n_item, cnt, rows);
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    ctx->excl_cnt = cnt;
+    ctx->excl_rows = stride ? rows : nullptr;
+    ctx->excl_stride = stride;
     return IRS_OK;
 }

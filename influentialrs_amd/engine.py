@@ -429,6 +429,59 @@ class Engine:
             scratch.record_stream(stream)
             self._check(self.lib.irs_bind_survivor_scratch(self.h, None, 0))
 
+    # ------------------------------------------------------------------ bound exclusions (irs_bind_exclusions)
+    def exclusion_scratch_bytes(self, users: int, n_excl: int) -> int:
+        n = int(self.lib.irs_exclusion_scratch_bytes(self.h, users, n_excl))
+        if n == 0:
+            raise IrsError(f"exclusion_scratch_bytes: users={users} / n_excl={n_excl} (users >= 1, n_excl in [0, 4096])")
+        return n
+
+    def bind_exclusions(self, excl_ids0: Optional[torch.Tensor], users: Optional[int] = None, no_repeat: bool = False,
+                        scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """irs_bind_exclusions: excl_ids0 int64 [users, n_excl], global 0-based ids, -1 = unused slot (None: no_repeat only, for
+        `users` users).  Until unbind_exclusions every step and loop entry point drops window + list (+ the path so far under
+        no_repeat).  Returns the scratch, which the caller keeps alive while bound."""
+        if excl_ids0 is not None:
+            excl_ids0 = self._dev(excl_ids0, torch.int64)
+            if excl_ids0.dim() != 2 or (users is not None and users != excl_ids0.shape[0]):
+                raise IrsError("bind_exclusions: excl_ids0 must be [users, n_excl]")
+            users, n_excl = excl_ids0.shape
+            if n_excl == 0:
+                excl_ids0 = None
+        else:
+            n_excl = 0
+        if users is None:
+            raise IrsError("bind_exclusions: users is needed without a list")
+        if scratch is None:
+            scratch = torch.empty(self.exclusion_scratch_bytes(users, n_excl), dtype=torch.uint8, device=self.device)
+        self._call(self.lib.irs_bind_exclusions, _ptr(excl_ids0), users, n_excl, int(bool(no_repeat)), _ptr(scratch),
+                   scratch.numel() * scratch.element_size())
+        if excl_ids0 is not None:  # (the prepare launch reads the list on the stream; the caller's tensor need not outlive the call)
+            excl_ids0.record_stream(torch.cuda.current_stream(self.device))
+        return scratch
+
+    def unbind_exclusions(self):
+        self._call(self.lib.irs_bind_exclusions, None, 0, 0, 0, None, 0)
+
+    @contextlib.contextmanager
+    def _exclusions(self, excl_ids0: Optional[torch.Tensor], no_repeat: bool, users: int, graph: bool = False):
+        """While a search call runs with `exclude` / `no_repeat`: the lists bound before and unbound after, like _exact_candidates
+        (and with its cost: bind and unbind drop the context's captured steps)."""
+        if excl_ids0 is None and not no_repeat:
+            yield
+            return
+        if excl_ids0 is not None and excl_ids0.shape[0] != users:
+            raise IrsError(f"exclude: {excl_ids0.shape[0]} lists for {users} users")
+        scratch = self.bind_exclusions(excl_ids0, users, no_repeat)
+        try:
+            yield
+        finally:
+            stream = torch.cuda.current_stream(self.device)
+            if graph:
+                stream.synchronize()
+            scratch.record_stream(stream)
+            self.unbind_exclusions()
+
     # ------------------------------------------------------------------ path search
     def path_step(self, seqs, hep, val, ids0, step: int, paths, status, sample=False, sample_k=3, seed=0):
         seqs = self._inplace(seqs, torch.int64, "path_step: seqs")
@@ -445,11 +498,14 @@ class Engine:
     def generate_paths(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
                        k: int = 100, sweep: int = IRS_SWEEP_BF16, sample=False, sample_k=3, seed=0,
                        use_graph: bool = False, paths: Optional[torch.Tensor] = None,
-                       status: Optional[torch.Tensor] = None, exact_candidates: bool = False):
+                       status: Optional[torch.Tensor] = None, exact_candidates: bool = False,
+                       exclude: Optional[torch.Tensor] = None, no_repeat: bool = False):
         """Runs the whole search loop on the device.  `seqs` and `hep` are the
         working window state and are modified in place.  exact_candidates: a row whose k candidates are hidden by its window
         chooses among the exact best admissible items of the catalog instead (IRS_ROW_RESCUED; the result of k = n_item).
-        With the keyword set use_graph saves nothing: the step is captured again on every call (_exact_candidates)."""
+        With the keyword set use_graph saves nothing: the step is captured again on every call (_exact_candidates).
+        exclude (int64 [B, E], 0-based ids, -1 = unused) / no_repeat: bound for this call (irs_bind_exclusions): a step drops
+        window + the user's list (+ its own path so far); the same holds in the three other loops."""
         seqs = self._inplace(seqs, torch.int64, "generate_paths: seqs")
         hep = self._inplace(hep, torch.int32, "generate_paths: hep")
         if users is not None:
@@ -465,7 +521,8 @@ class Engine:
         status = self._inplace(status, torch.int32, "generate_paths: status")
         if paths.shape != (B, max_path_len):
             raise IrsError("generate_paths: paths must be [B, max_path_len]")
-        with self._exact_candidates(exact_candidates, B, sample_k if sample else 1, bool(use_graph)):
+        with self._exact_candidates(exact_candidates, B, sample_k if sample else 1, bool(use_graph)), \
+                self._exclusions(exclude, no_repeat, B, bool(use_graph)):
             self._call(self.lib.irs_generate_paths, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                     int(sample), sample_k, seed, int(use_graph), _ptr(paths), _ptr(status))
         return paths, status
@@ -473,7 +530,8 @@ class Engine:
     def generate_paths_until(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
                              k: int = 100, sweep: int = IRS_SWEEP_BF16, sample=False, sample_k=3, seed=0,
                              check_every: int = 1, paths: Optional[torch.Tensor] = None,
-                             status: Optional[torch.Tensor] = None, exact_candidates: bool = False):
+                             status: Optional[torch.Tensor] = None, exact_candidates: bool = False,
+                             exclude: Optional[torch.Tensor] = None, no_repeat: bool = False):
         """generate_paths that stops a user at its target (seqs[b, L - 1]) and the call when nobody is left
         (irs_generate_paths_until): returns (paths, status, steps_run, row_steps).  Paths are zero behind the target.
         `seqs` and `hep` are working state: modified, and unspecified afterwards.  One host read of 4 bytes per check."""
@@ -493,7 +551,7 @@ class Engine:
         if paths.shape != (B, max_path_len):
             raise IrsError("generate_paths_until: paths must be [B, max_path_len]")
         stats = (ctypes.c_int64 * 2)(0, 0)
-        with self._exact_candidates(exact_candidates, B, sample_k if sample else 1):
+        with self._exact_candidates(exact_candidates, B, sample_k if sample else 1), self._exclusions(exclude, no_repeat, B):
             self._call(self.lib.irs_generate_paths_until, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                           int(sample), sample_k, seed, check_every, _ptr(paths), _ptr(status), stats)
         return paths, status, int(stats[0]), int(stats[1])
@@ -517,7 +575,8 @@ class Engine:
 
     def beam_search(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
                     beam: int, k: int = 100, sweep: int = IRS_SWEEP_BF16, use_graph: bool = False,
-                    want_windows: bool = False, exact_candidates: bool = False):
+                    want_windows: bool = False, exact_candidates: bool = False, exclude: Optional[torch.Tensor] = None,
+                    no_repeat: bool = False):
         """(paths[B,W,P] f32, scores[B,W] f64, status[B] i32[, windows[B,W,L]]); beam 0 is the best."""
         seqs = self._dev(seqs, torch.int64)
         hep = self._dev(hep, torch.int32)
@@ -528,7 +587,8 @@ class Engine:
         scores = torch.zeros((B, beam), dtype=torch.float64, device=self.device)
         status = torch.zeros(B, dtype=torch.int32, device=self.device)
         fin = torch.empty((B, beam, self.L), dtype=torch.int64, device=self.device) if want_windows else None
-        with self._exact_candidates(exact_candidates, B * beam, beam, bool(use_graph)):
+        with self._exact_candidates(exact_candidates, B * beam, beam, bool(use_graph)), \
+                self._exclusions(exclude, no_repeat, B, bool(use_graph)):
             self._call(self.lib.irs_beam_search, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
                                                  int(use_graph), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(status))
         return (paths, scores, status, fin) if want_windows else (paths, scores, status)
@@ -554,7 +614,8 @@ class Engine:
                           beam: int, k: int = 100, sweep: int = IRS_SWEEP_BF16, stop_rule: int = _lib.IRS_BEAM_STOP_BEST,
                           check_every: int = 1, want_windows: bool = False, paths: Optional[torch.Tensor] = None,
                           scores: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
-                          fin: Optional[torch.Tensor] = None, exact_candidates: bool = False):
+                          fin: Optional[torch.Tensor] = None, exact_candidates: bool = False,
+                          exclude: Optional[torch.Tensor] = None, no_repeat: bool = False):
         """Beam search that ends a beam at its target (seqs[b, L - 1]) and retires finished users (irs_beam_search_until):
         (paths[B,W,P] f32, scores[B,W] f64, status[B] i32, fin[B,W] i32, steps_run, window_steps[, windows[B,W,L]]); beam 0 is
         the best.  One host read of 4 bytes per check."""
@@ -581,7 +642,7 @@ class Engine:
             raise IrsError("beam_search_until: paths [B, W, P], scores / fin [B, W], status [B]")
         win = torch.empty((B, beam, self.L), dtype=torch.int64, device=self.device) if want_windows else None
         stats = (ctypes.c_int64 * 2)(0, 0)
-        with self._exact_candidates(exact_candidates, B * beam, beam):
+        with self._exact_candidates(exact_candidates, B * beam, beam), self._exclusions(exclude, no_repeat, B):
             self._call(self.lib.irs_beam_search_until, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
                        int(stop_rule), int(check_every), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(win), _ptr(status), stats)
         out = (paths, scores, status, fin, int(stats[0]), int(stats[1]))

@@ -95,6 +95,9 @@ def test_model(config, rows: Sequence, irn, device, result_dir: str = None, verb
         # (config.exact_candidates: rows whose top-100 is hidden by their window choose among the exact best admissible items)
         if getattr(config, "exact_candidates", False):
             stop["exact_candidates"] = True
+        # (config.no_repeat / config.exclude_history: never offer an item twice / an item of the user's raw history)
+        if getattr(config, "no_repeat", False):
+            stop["no_repeat"] = True
         for raw, seq, u, t, l in eval_batches_irs(rows, config.batch_size, config.max_len, config.gap_len):
             t, l, u, seq = t.to(device), l.to(device), u.to(device), seq.to(device)
             r_u = irn.get_pif_in_batch(seq, u)
@@ -102,6 +105,8 @@ def test_model(config, rows: Sequence, irn, device, result_dir: str = None, verb
             hit_count, rr = irn.get_accuracy_metrics_in_batch(raw, seq, u, t, l, config.top_k, config.gap_len, config.use_h)
             hit += hit_count
             reverse_ranks = rr if len(reverse_ranks) == 0 else np.concatenate([reverse_ranks, rr])
+            if getattr(config, "exclude_history", False):
+                stop["exclude"] = raw
             p, t_out, h, early_success = irn.get_seq_in_batch(seq, u, t, config.max_path_len, config.gap_len, config.sample,
                                                               config.sample_k, **stop)
             n_early_success += early_success

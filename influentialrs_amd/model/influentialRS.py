@@ -179,15 +179,38 @@ class InfluentialNet(nn.Module):
 def _takes_exact_candidates(fn):
     """Gives get_seq_in_batch its keyword exact_candidates=False.  It is taken here, keyword only, so that the declared
     parameter list stays what it was (it ends with beam_stop): positional callers and code that reads the signature are not
-    disturbed.  The search reads the switch from self._exact_candidates for the time of the call."""
+    disturbed.  The search reads the switch from self._exact_candidates for the time of the call.
+    exclude=None and no_repeat=False (bound exclusions) are taken the same way, into self._exclude / self._no_repeat."""
     @functools.wraps(fn)
-    def call(self, *args, exact_candidates=False, **kw):
-        prev, self._exact_candidates = getattr(self, "_exact_candidates", False), bool(exact_candidates)
+    def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, **kw):
+        prev = (getattr(self, "_exact_candidates", False), getattr(self, "_exclude", None), getattr(self, "_no_repeat", False))
+        self._exact_candidates, self._exclude, self._no_repeat = bool(exact_candidates), exclude, bool(no_repeat)
         try:
             return fn(self, *args, **kw)
         finally:
-            self._exact_candidates = prev
+            self._exact_candidates, self._exclude, self._no_repeat = prev
     return call
+
+
+def exclusion_ids0(exclude, no_repeat, seqs, hep: int, device):
+    """The lists irs_bind_exclusions takes (int64 [B, E], 0-based ids, -1 = unused) from get_seq_in_batch's `exclude`: a list of
+    B arrays / tensors of 1-based ids like `raw`, or a [B, E] tensor padded with 0; None: no list.  no_repeat appends the
+    user's initial window seqs[b, :hep + 1], so that nothing the window ever held is offered again.  None when there is nothing."""
+    parts = []
+    if exclude is not None:
+        if torch.is_tensor(exclude):
+            if exclude.dim() != 2 or exclude.shape[0] != seqs.shape[0]:
+                raise ValueError(f"exclude: a [B, E] tensor padded with 0, or a list of B id arrays (got {tuple(exclude.shape)})")
+            parts.append(exclude.to(device).to(torch.int64) - 1)
+        else:
+            if len(exclude) != seqs.shape[0]:
+                raise ValueError(f"exclude: {len(exclude)} lists for {seqs.shape[0]} users")
+            parts.append(pad_ragged_ids(exclude, device))
+    if no_repeat:
+        parts.append(seqs[:, :hep + 1].to(device).to(torch.int64) - 1)
+    if not parts:
+        return None
+    return torch.cat(parts, dim=1).contiguous()
 
 
 class IRSNN(nn.Module):
@@ -292,7 +315,7 @@ class IRSNN(nn.Module):
             rr.append(np.reciprocal(float(ranks[i])))
         return hit_count, np.array(rr)
 
-    def _beam_paths(self, seqs, users, max_path_len, gap_len, beam_width, beam_stop=None, exact_candidates=False):
+    def _beam_paths(self, seqs, users, max_path_len, gap_len, beam_width, beam_stop=None, exact_candidates=False, excl=None):
         """Best-beam paths [B, P] + status via the build-defined beam search (no reference
         counterpart; beam_width == 1 equals the greedy search).  All beams and their
         cumulative log-probabilities are kept in self.last_beams = (paths[B,W,P], scores[B,W]).
@@ -307,12 +330,12 @@ class IRSNN(nn.Module):
             eng = hip.get(B * W, B * W)
             paths, scores, status, fin, steps, window_steps = eng.beam_search_until(
                 seqs.contiguous(), users, hep, max_path_len, W, k=100, sweep=hip.sweep, stop_rule=_BEAM_STOP_RULES[beam_stop],
-                check_every=BEAM_STOP_CHECK_EVERY, exact_candidates=exact_candidates)
+                check_every=BEAM_STOP_CHECK_EVERY, exact_candidates=exact_candidates, **(excl or {}))
             self.last_beam_stop = dict(finished=fin.detach().cpu().numpy(), steps=steps, window_steps=window_steps)
         elif hip.world == 1:
             eng = hip.get(B * W, B * W)
             paths, scores, status = eng.beam_search(seqs.contiguous(), users, hep, max_path_len, W, k=100, sweep=hip.sweep,
-                                                    exact_candidates=exact_candidates)
+                                                    exact_candidates=exact_candidates, **(excl or {}))
         else:  # item-sharded: the whole loop runs below the C ABI (irs_beam_search_sharded: row all-gather, packed top-100
             # all-to-all, log-sum-exp all-reduce per step, one stream-ordered sequence; captured into a hipGraph over RCCL)
             eng = hip.get(B * W, B * W * hip.world)
@@ -340,8 +363,18 @@ class IRSNN(nn.Module):
         exact_candidates=True (extension, keyword only, taken by _takes_exact_candidates; one device, off by default): a row
         whose top-100 candidates are hidden by its window chooses among the exact best admissible items of the whole catalog
         (irs_bind_survivor_scratch), so the search returns what it would return with k = n_item; the IndexError below remains
-        only for a catalog contained in the window."""
+        only for a catalog contained in the window.
+        exclude=None, no_repeat=False (extension, keyword only, taken the same way; one device, off by default): never offer
+        an item the user has already seen (irs_bind_exclusions).  exclude: a list of B arrays / tensors of 1-based ids like
+        `raw`, or a [B, E] tensor padded with 0; every step then drops window + the user's list.  no_repeat=True also drops
+        the path so far, and adds the user's initial window to its list: the search never offers anything the window ever held
+        nor anything it chose itself.  At most 4096 ids per user, the window's included.  A target that is in the user's
+        list can no longer be reached.  Combine with exact_candidates=True: a long list regularly hides the whole top-100."""
         exact_candidates = getattr(self, "_exact_candidates", False)
+        exclude, no_repeat = getattr(self, "_exclude", None), getattr(self, "_no_repeat", False)
+        if (exclude is not None or no_repeat) and self.net._hip.world != 1:
+            raise ValueError("exclude / no_repeat is not built for an item-sharded catalog: irs_bind_exclusions needs the whole "
+                             "catalog on one device")
         if exact_candidates and self.net._hip.world != 1:
             raise ValueError("exact_candidates is not built for an item-sharded catalog: a shard can only rescue a row against "
                              "its own items")
@@ -364,8 +397,10 @@ class IRSNN(nn.Module):
         work = seqs.to(torch.int64).clone(memory_format=torch.contiguous_format)  # the search updates it in place
         hep = torch.full((B,), L - (gap_len + 1) - 1, dtype=torch.int32, device=dev)
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if sample else 0
+        ids0 = exclusion_ids0(exclude, no_repeat, seqs, L - (gap_len + 1) - 1, dev)
+        excl = dict(exclude=ids0, no_repeat=no_repeat) if (ids0 is not None or no_repeat) else {}
         if beam_width > 1:
-            paths_t, status = self._beam_paths(work, users, max_path_len, gap_len, beam_width, beam_stop, exact_candidates)
+            paths_t, status = self._beam_paths(work, users, max_path_len, gap_len, beam_width, beam_stop, exact_candidates, excl)
         elif stop_at_target:
             if hip.world != 1:
                 raise ValueError("stop_at_target is not built for an item-sharded catalog: irs_generate_paths_sharded runs "
@@ -373,18 +408,21 @@ class IRSNN(nn.Module):
             eng = hip.get(B, B)
             paths_t, status, _, _ = eng.generate_paths_until(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
                                                              sample=sample, sample_k=sample_k, seed=seed,
-                                                             check_every=STOP_CHECK_EVERY, exact_candidates=exact_candidates)
+                                                             check_every=STOP_CHECK_EVERY, exact_candidates=exact_candidates, **excl)
         elif hip.world == 1:
             eng = hip.get(B, B)
             paths_t, status = eng.generate_paths(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
                                                  sample=sample, sample_k=sample_k, seed=seed, use_graph=False,
-                                                 exact_candidates=exact_candidates)
+                                                 exact_candidates=exact_candidates, **excl)
         else:  # item-sharded: irs_generate_paths_sharded (decode, row all-gather, shard sweep, key all-to-all, merge, path
             # step per search step, below the C ABI on one stream)
             eng = hip.get(B, B * hip.world)
             paths_t, status = eng.generate_paths_sharded(hip.comm, work, users, hep, max_path_len, k=100, sweep=hip.sweep,
                                                          sample=sample, sample_k=sample_k, seed=seed, use_graph=False)
         if int((status & IRS_ROW_NO_CANDIDATE).sum().item()) > 0:
+            if excl:
+                raise IndexError("index 0 is out of bounds: every admissible item is excluded (window + exclusion list"
+                                 + (" + path)" if no_repeat else ")") + ("" if exact_candidates else " among the top-100 candidates"))
             raise IndexError("index 0 is out of bounds: every top-100 candidate is already in the window "
                              "(same condition as reference influentialRS.py:429)" if not exact_candidates else
                              "index 0 is out of bounds: every item of the catalog is already in the window")
