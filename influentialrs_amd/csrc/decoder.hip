@@ -1615,9 +1615,13 @@ struct BlockX6Args {
     long long wstride;     // in uint4
     int n_lay, nl_total;   // layers run here (n_layers - 1); streams in the arena (layer l's q | k | v sits in stream l - 1, layer 0's in stream nl_total - 1)
     const float *vecpack;  // [n_lay + 1][X6_SEQ_VECS]: every parameter vector of a layer in the kernel's LDS order (k_pack_seqvec)
-    // Behind layer n_lay - 1 the kernel runs the FRONT of layer n_lay too (the model's last layer, of which the handlers consume one
-    // row per sequence): q | k | v of every token, K / V images, and the attention of the ONE 16-query block that holds the consumed
-    // token seq_qrow[b] -- its output row is gathered from the attention tiles by the host side; no k | v row reaches HBM.
+    // The launch ends behind layer n_lay - 1: its x' in Xf (tile order) is all the model's last layer needs.  The handlers consume
+    // one row per sequence of that layer, and for ONE query the K and V projections are absorbed (k_absorb_qu / _attn / _out behind
+    // k_attn_row32): score_j = (W_k,h^T q_h) . x'_j + q_h . b_k,h and out_h = W_v,h (sum_j p_j x'_j) + b_v,h -- no q | k | v of
+    // the last layer for every token, no K / V images, nothing written to Af for it.
+    // (SEQ_LAST_ABSORB = 0, lab: behind layer n_lay - 1 the kernel runs the FRONT of layer n_lay too -- q | k | v of every token,
+    // K / V images, and the attention of the ONE 16-query block that holds the consumed token seq_qrow[b]; its output row is
+    // gathered from the attention tiles by the host side.  seq_qrow is read by that form only.)
     const int32_t *seq_qrow;
     const int32_t *tile_seq, *tile_qb, *seq_off, *seq_cnt, *seq_padq, *seq_row0, *n_wg_dev;
     const float *r_u;
@@ -1747,6 +1751,12 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
 #endif
 #ifndef SEQ_FRONT_RIDE
 #define SEQ_FRONT_RIDE 1 // (lab, tools/seq_lab.sh: 0 = a head's steps in the order q, k, v with all three epilogues behind the v step, as through round 7)
+#endif
+#ifndef SEQ_LAST_ABSORB
+// 1: the launch runs layers 0 .. n_lay - 1 and ends; the model's last layer attends from x' with absorbed K / V projections
+// (k_absorb_qu, k_absorb_attn, k_absorb_out).  (lab, tools/seq_lab.sh last0: 0 = an extra trip of the layer loop runs the last
+// layer's front for every token and the attention of each consumed token's block, gathered by the host side, as before.)
+#define SEQ_LAST_ABSORB 1
 #endif
 // SEQ layout of the dynamic LDS behind the ring and the parameter vectors (x6_seq_lds_bytes)
 #define X6_SEQ_VECS (256 + 12 * 32 * 4 + 384)   // floats: the parameter vectors + this layer's in-projection bias
@@ -1943,8 +1953,11 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     // (the non-SEQ kernels see compile-time constants here: `nsteps` and `last` are macros over a constexpr condition)
     int ly = 0, nsteps_rt = nsteps_c;
     bool last_rt = true;
-#define nsteps (SEQ ? nsteps_rt : nsteps_c)
-#define last (!SEQ || last_rt)
+    // (SEQ_LAST_ABSORB: no trip of the layer loop is a front-only one -- `last` and `nsteps` are constants again; end_rt marks the
+    //  launch's last layer, which ends the ring behind its own steps: nothing is fetched at mid-step 31, no empty step follows)
+    bool end_rt = false;
+#define nsteps (SEQ ? (SEQ_LAST_ABSORB ? (1 << 20) : nsteps_rt) : nsteps_c)
+#define last (!SEQ || (!SEQ_LAST_ABSORB && last_rt))
     // DMA of sequence step i into slot i % NSLOT: this wave's pieces PPW wave .. PPW wave + PPW - 1.  The slot holds the
     // step's block in stream order, and the instruction's immediate offset moves the global source AND the LDS destination
     // (tools/dma_probe.hip), so the pieces share one address register pair and one M0: base = the middle piece, offsets
@@ -2019,14 +2032,18 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             x6_static_for<1, LEAD>([&](auto ic) __attribute__((always_inline)) { issue(S0 + decltype(ic)::value); }); // (as the live path)
             static_assert(LEAD == 2 && S0 == 0, "the waits below are vmcnt(0): X6_PUBLISH with three ring slots");
 #pragma unroll 1
-            for (ly = 0; ly <= a.n_lay; ++ly) {
+            for (ly = 0; ly < a.n_lay + (SEQ_LAST_ABSORB ? 0 : 1); ++ly) {
+#if SEQ_LAST_ABSORB
+                end_rt = ly == a.n_lay - 1; // (the ring ends with the live path's: behind the last full layer's own steps)
+#else
                 last_rt = ly == a.n_lay;
                 nsteps_rt = last_rt ? NFRONT : (1 << 20);
+#endif
                 dma_src = a.Wbase + (long long)ly * a.wstride + (PPW * wave + PPG / 2) * 64 + lane;
                 dma_src_q = a.Wbase + (long long)(ly == 0 ? a.nl_total - 1 : ly - 1) * a.wstride + (PPW * wave + PPG / 2) * 64 + lane;
                 dma_src_qn = dma_src;
                 float nvi[(X6_SEQ_VECS + 64 * NW - 1) / (64 * NW)];
-                if (!last_rt) {
+                if (!last && !end_rt) {
 #pragma unroll
                     for (int k = 0; k < (X6_SEQ_VECS + 64 * NW - 1) / (64 * NW); ++k)
                         nvi[k] = (tid + 64 * NW * k < X6_SEQ_VECS) ? a.vecpack[(size_t)(ly + 1) * X6_SEQ_VECS + tid + 64 * NW * k] : 0.f;
@@ -2034,20 +2051,21 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                 // (unrolled: the ring slot of a step is part of the DMA's address arithmetic, a constant per step)
                 x6_static_for<0, NFRONT>([&](auto ic) __attribute__((always_inline)) {
                     constexpr int i = decltype(ic)::value;
-                    if (i + 1 < nsteps_rt) { // X6_PUBLISH(i)
+                    if (i + 1 < nsteps) { // X6_PUBLISH(i)
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         __builtin_amdgcn_s_barrier();
-                        if (i + LEAD < nsteps_rt) issue(i + LEAD);
+                        if (i + LEAD < nsteps) issue(i + LEAD);
                     }
                     if constexpr (i % 3 == 2) __builtin_amdgcn_s_barrier(); // head i / 3's rows are in the images
                 });
-                if (last_rt) break;
+                if (last) break;
                 x6_static_for<NFRONT, NFRONT + NPRE>([&](auto ic) __attribute__((always_inline)) {
                     constexpr int i = decltype(ic)::value;
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     __builtin_amdgcn_s_barrier();
-                    issue(i + LEAD);
+                    if (!(i == NFRONT + NPRE - 1 && end_rt)) issue(i + LEAD); // (X6_PUBLISH: nothing is fetched behind the launch's last step)
                 });
+                if (end_rt) break; // (the launch's last layer: no empty step, no vectors, no next front)
                 // the empty step between two layers
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
@@ -2289,7 +2307,9 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
         X6_TI(st_b)                                                                                                       \
         __builtin_amdgcn_s_barrier();                                                                                    \
         X6_TI(st_c)                                                                                                       \
-        if ((I_) + LEAD < nsteps && !(SEQ && !SEQ_ASM_DMA && (I_) < NFRONT && (I_) % 3 == 2)) X6_ISSUE((I_) + LEAD); /* (SEQ with the builtin DMA: see the front phase) */ \
+        if ((I_) + LEAD < nsteps && !(SEQ && !SEQ_ASM_DMA && (I_) < NFRONT && (I_) % 3 == 2) &&                          \
+            !(SEQ && SEQ_LAST_ABSORB && (I_) == NFRONT + NPRE - 1 && end_rt)) /* (nothing is fetched behind the launch's last step) */ \
+            X6_ISSUE((I_) + LEAD); /* (SEQ with the builtin DMA: see the front phase) */ \
         if constexpr (RESID_LATE) { if ((I_) == 1) load_res(); }                                                         \
         X6_TI(st_d)                                                                                                       \
         st_wait += st_b - st_a, st_bar += st_c - st_b, st_iss += st_d - st_c;                                            \
@@ -2535,8 +2555,12 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             asm volatile("" : "+v"(vecs_addr), "+v"(fr_addr), "+v"(mtile), "+v"(fb_lo), "+v"(fb_hi));
             fbase = ((size_t)fb_hi << 32) | fb_lo;
         }
+#if SEQ_LAST_ABSORB
+        end_rt = ly == a.n_lay - 1; // the launch's last layer: the ring ends behind its own 32 steps (no empty step, no next front)
+#else
         last_rt = ly == a.n_lay; // the extra trip: only the front of the model's last layer, the ring ends behind its 12 steps
         nsteps_rt = last_rt ? NFRONT : (1 << 20);
+#endif
         dma_src = a.Wbase + (long long)ly * a.wstride + (PPW * wave + PPG / 2) * 64 + lane;
         dma_src_q = a.Wbase + (long long)(ly == 0 ? a.nl_total - 1 : ly - 1) * a.wstride + (PPW * wave + PPG / 2) * 64 + lane;
         dma_src_qn = dma_src;
@@ -2691,7 +2715,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
 #pragma unroll 1
                 for (int blk = 0; blk < 2; ++blk) {
                     const int b_ = blk ? sh_b[1] : sh_b[0], qb_ = blk ? sh_qb[1] : sh_qb[0], row0_ = blk ? sh_row0[1] : sh_row0[0];
-                    if (b_ >= 0 && last_rt && qb_ != (blk ? sh_pb[1] : sh_pb[0])) continue; // (the model's last layer: only the consumed token's block)
+                    if (b_ >= 0 && last && qb_ != (blk ? sh_pb[1] : sh_pb[0])) continue; // (the extra trip for the model's last layer: only the consumed token's block)
                     // (an empty half: block index beyond a zero-length sequence -> zeros, the layer body multiplies whole tiles)
                     seq_attn_block(Kimg + row0_ * 32, Vimg + row0_ * 64, 16384, b_ >= 0 ? (blk ? sh_cnt[1] : sh_cnt[0]) : 0, b_ >= 0 ? qb_ : 16,
                                    blk ? sh_pm[1] : sh_pm[0], blk ? sh_tadd[1] : sh_tadd[0], blk ? sh_tgt[1] : sh_tgt[0],
@@ -2704,7 +2728,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             X6_PH(2)
             if (!SEQ_ASM_DMA && 3 * h + 2 + LEAD < nsteps) issue(3 * h + 2 + LEAD); // (builtin DMA: the refill the v step left out)
         }
-        if (last_rt) return; // (the model's last layer goes on, for one row per sequence, in the small-batch kernels)
+        if (last) return; // (the extra trip: the model's last layer goes on, for one row per sequence, in the small-batch kernels)
         // ---- the layer body's inputs: the attention tiles this wave wrote and the residual, as loads the compiler does not see (it
         // would hoist and spread them over the front: registers) with ONE wait; the out-projection accumulates from zero and the
         // residual is added with b_o in front of LayerNorm 1, as in the RESID_LATE form.
@@ -2796,7 +2820,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                 __builtin_amdgcn_sched_barrier(0);
             }
         if constexpr (SEQ) {
-            if (!last) {
+            if (!last) { // (the launch's last layer too: vecpack has a row for the model's last layer, nothing re-stages these)
 #pragma unroll
                 for (int k = 0; k < (X6_SEQ_VECS + 64 * NW - 1) / (64 * NW); ++k)
                     nv[k] = (tid + 64 * NW * k < X6_SEQ_VECS) ? a.vecpack[(size_t)(ly + 1) * X6_SEQ_VECS + tid + 64 * NW * k] : 0.f;
@@ -2898,6 +2922,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
         }
     X6_T(st_p[4])
     X6_PH(7)
+    if (SEQ && SEQ_LAST_ABSORB && end_rt) return; // (the launch's last layer ends here: x' is stored, the ring is drained)
     if (SEQ && !last) {
         // ---- the empty step between two layers: publishes the next layer's first step (fetched at mid-step 31), frees step
         // 31's slot for its second one, re-stages the parameter vectors (every wave is past LayerNorm 3: nothing reads the old
@@ -2967,10 +2992,11 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     }; // (layer_body)
     if constexpr (SEQ) {
 #pragma unroll 1
-        for (ly = 0; ly <= a.n_lay; ++ly) layer_body();
+        for (ly = 0; ly < a.n_lay + (SEQ_LAST_ABSORB ? 0 : 1); ++ly) layer_body();
     } else
         layer_body();
     landed_all(); // the reads issued past the last step
+    if constexpr (SEQ && SEQ_LAST_ABSORB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (no LDS-DMA piece in flight when the wave ends: the ring's last issue is waited for at mid-step 30)
 #ifdef X6_STAMP
     X6_T(st_1)
     if (lane == 0 && a.stamps) {
@@ -5544,6 +5570,261 @@ __global__ void __launch_bounds__(256) k_attn_row32(const float *__restrict__ qk
     }
 }
 
+// ------------------------------------------------------------------ the last layer's one row per sequence, attended from x'
+// Behind the sequence-resident launch (d = 128, 4 heads of 32, L <= 256): x' of the last full layer lies fragment-major in TILE
+// order, and the model's last layer is consumed in ONE row per sequence.  For one query the K and V projections are absorbed:
+//   u_h = W_k,h^T q_h,  c_h = q_h . b_k,h:   score_j = q_h . (W_k,h x'_j + b_k,h) = u_h . x'_j + c_h
+//   m_h = sum_j p_j x'_j:                    out_h = sum_j p_j (W_v,h x'_j + b_v,h) = W_v,h m_h + b_v,h   (sum_j p_j = 1)
+// i.e. three d x d matrix-vector products per sequence and 2 n H d multiply-adds over its n tokens, instead of 2 n d^2 for the
+// K and V rows of every token.  Three launches: k_absorb_qu (x_c -> the residual rows, q, u, c; ABS_SQ sequences of a workgroup
+// share W_q and W_k), k_absorb_attn (one workgroup per sequence, ONE pass over its x' blocks for all four heads and both uses,
+// running maximum) and k_absorb_out (W_v, b_v; ABS_SO sequences per workgroup).  float32 __fmaf_rn chains in a fixed order, no atomics:
+// repeated calls give the same bits.  k_attn_row32's mask rule and its NaN row (l = 0) for a query without an allowed key.
+#define ABS_SQ 8
+#define ABS_SO 8
+#define ABS_WLD 132 // floats per staged weight row: thread r reads row r in 16-byte pieces, rows 4 banks apart
+// 64 rows [r0, r0 + 64) of a row-major [.][128] matrix into LDS (256 threads, coalesced)
+__device__ __forceinline__ void absorb_stage64(const float *__restrict__ W, int r0, float *Ws, int tid) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int idx = tid + 256 * k, row = idx >> 5, c4 = idx & 31;
+        *reinterpret_cast<float4 *>(Ws + row * ABS_WLD + 4 * c4) = *reinterpret_cast<const float4 *>(W + (size_t)(r0 + row) * 128 + 4 * c4);
+    }
+}
+// x_r[b] = x_c = x'[qrow_tile[b]] (k_gather_rows_frag's element index); q = (W_q x_c + b_q) / sqrt(32); u[b][h][:] = W_k,h^T q_h;
+// cq[b][h] = q_h . b_k,h
+__global__ void __launch_bounds__(256) k_absorb_qu(const float *__restrict__ xf, const int32_t *__restrict__ qrow_tile,
+                                                   const float *__restrict__ Win, const float *__restrict__ bin, float *__restrict__ x_r,
+                                                   float *__restrict__ u, float *__restrict__ cq, int B) {
+    constexpr int D = 128, HD = 32, S = ABS_SQ;
+    __shared__ __attribute__((aligned(16))) float Ws[64 * ABS_WLD];
+    __shared__ __attribute__((aligned(16))) float xs[S][D], qs[S][D];
+    const int tid = threadIdx.x, b0 = blockIdx.x * S;
+#pragma unroll
+    for (int k = 0; k < S * D / 256; ++k) {
+        const int idx = tid + 256 * k, s = idx >> 7, c = idx & 127, b = b0 + s;
+        float v = 0.f;
+        if (b < B) {
+            const int row = qrow_tile[b];
+            v = xf[(((size_t)(row >> 5) * 4 + (c >> 5)) * 4 + ((c >> 3) & 3)) * 256 + ((c >> 2) & 1) * 128 + (row & 31) * 4 + (c & 3)];
+            x_r[(size_t)b * D + c] = v;
+        }
+        xs[s][c] = v;
+    }
+    const float scale = 1.0f / sqrtf((float)HD);
+    {
+        const int r = tid & 63, sg = tid >> 6; // output row r of the staged 64, sequences 2 sg and 2 sg + 1
+        // both halves of W_q are requested before the first one is used
+        const float *wp = Win + (size_t)(tid >> 5) * D + 4 * (tid & 31); // + 8 k rows
+        float *wl = Ws + (tid >> 5) * ABS_WLD + 4 * (tid & 31);
+        const float4 wa0 = *reinterpret_cast<const float4 *>(wp + 0 * 8 * D), wa1 = *reinterpret_cast<const float4 *>(wp + 1 * 8 * D),
+                     wa2 = *reinterpret_cast<const float4 *>(wp + 2 * 8 * D), wa3 = *reinterpret_cast<const float4 *>(wp + 3 * 8 * D),
+                     wa4 = *reinterpret_cast<const float4 *>(wp + 4 * 8 * D), wa5 = *reinterpret_cast<const float4 *>(wp + 5 * 8 * D),
+                     wa6 = *reinterpret_cast<const float4 *>(wp + 6 * 8 * D), wa7 = *reinterpret_cast<const float4 *>(wp + 7 * 8 * D);
+        const float4 wb0 = *reinterpret_cast<const float4 *>(wp + 8 * 8 * D), wb1 = *reinterpret_cast<const float4 *>(wp + 9 * 8 * D),
+                     wb2 = *reinterpret_cast<const float4 *>(wp + 10 * 8 * D), wb3 = *reinterpret_cast<const float4 *>(wp + 11 * 8 * D),
+                     wb4 = *reinterpret_cast<const float4 *>(wp + 12 * 8 * D), wb5 = *reinterpret_cast<const float4 *>(wp + 13 * 8 * D),
+                     wb6 = *reinterpret_cast<const float4 *>(wp + 14 * 8 * D), wb7 = *reinterpret_cast<const float4 *>(wp + 15 * 8 * D);
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch) {
+            __syncthreads(); // (xs is written; the previous half's reads are done)
+#define ABS_ST(k_, a_, b_) *reinterpret_cast<float4 *>(wl + (k_) * 8 * ABS_WLD) = ch == 0 ? a_ : b_
+            ABS_ST(0, wa0, wb0), ABS_ST(1, wa1, wb1), ABS_ST(2, wa2, wb2), ABS_ST(3, wa3, wb3);
+            ABS_ST(4, wa4, wb4), ABS_ST(5, wa5, wb5), ABS_ST(6, wa6, wb6), ABS_ST(7, wa7, wb7);
+#undef ABS_ST
+            __syncthreads();
+            const float bq = bin[64 * ch + r];
+            float acc[2] = {bq, bq};
+#pragma unroll 8
+            for (int k4 = 0; k4 < D / 4; ++k4) {
+                const float4 w = *reinterpret_cast<const float4 *>(Ws + r * ABS_WLD + 4 * k4);
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const float4 x4 = *reinterpret_cast<const float4 *>(&xs[2 * sg + s][4 * k4]);
+                    acc[s] = __fmaf_rn(w.x, x4.x, acc[s]);
+                    acc[s] = __fmaf_rn(w.y, x4.y, acc[s]);
+                    acc[s] = __fmaf_rn(w.z, x4.z, acc[s]);
+                    acc[s] = __fmaf_rn(w.w, x4.w, acc[s]);
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) qs[2 * sg + s][64 * ch + r] = acc[s] * scale;
+        }
+    }
+    __syncthreads();
+    {
+        const int k = tid & 127, hf = tid >> 7; // input channel k, sequences 4 hf .. 4 hf + 3; W_k = rows [d, 2 d) of W_in
+#pragma unroll 1
+        for (int h = 0; h < 4; ++h) {
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 16
+            for (int c = 0; c < HD; ++c) {
+                const float w = Win[(size_t)(D + h * HD + c) * D + k];
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc[s] = __fmaf_rn(w, qs[4 * hf + s][h * HD + c], acc[s]);
+            }
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                if (b0 + 4 * hf + s < B) u[((size_t)(b0 + 4 * hf + s) * 4 + h) * D + k] = acc[s];
+        }
+    }
+    if (tid < 4 * S) {
+        const int s = tid >> 2, h = tid & 3;
+        float acc = 0.f;
+        for (int c = 0; c < HD; ++c) acc = __fmaf_rn(qs[s][h * HD + c], bin[D + h * HD + c], acc);
+        if (b0 + s < B) cq[(size_t)(b0 + s) * 4 + h] = acc;
+    }
+}
+
+// One workgroup per sequence b, one wave per head h.  um[b][h][:] holds u_h on entry and m_h = sum_j p_j x'_j on exit (p: softmax
+// over the allowed keys of s_hj = u_h . x'_j + c_h + k_attn_row32's additive term).  The sequence's 16-token blocks of x' go
+// through LDS ONCE for all four heads and both uses (two 8 KB buffers: block n + 1 is on its way in registers while block n is
+// used; one barrier per block): every thread moves two 16-byte pieces, a wave 1 KB = four 256-byte runs of the fragment-major
+// image.  Lane (r, q) = (lane & 15, lane >> 4) of a wave takes token 16 blk + r and its channels 16 k + 4 q + e (k < 8, e < 4):
+// a score is 32 multiply-adds against u_h (registers) + the two butterfly levels across q, a running maximum rescales, and the
+// lane accumulates p x' of its 32 channels, summed over the 16 token lanes once at the end.  Only the blocks that hold an allowed
+// key are read (0 .. i / 16, and the IRN target's); tile rows beyond cnt[b] are not read.
+__global__ void __launch_bounds__(256) k_absorb_attn(const float *__restrict__ xf, float *__restrict__ um, const float *__restrict__ cq,
+                                                     const int64_t *__restrict__ seq, const float *__restrict__ r_u, int Lmax,
+                                                     int mask_mode, const int32_t *__restrict__ off, const int32_t *__restrict__ cnt,
+                                                     const int32_t *__restrict__ qrow, const int32_t *__restrict__ padq,
+                                                     const int32_t *__restrict__ row0, const int32_t *__restrict__ qrow_tile) {
+    __shared__ __attribute__((aligned(16))) float xs[2][16 * 128]; // a block as in the image: piece (G = 4 k + q, r) at 16 G + r
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, h = tid >> 6, r = lane & 15, q = lane >> 4;
+    const int L = cnt[b];
+    int i = qrow[b] - off[b]; // query row within the packed sequence
+    if (i < 0) i = 0;
+    if (i >= L) i = L - 1;
+    int T = (L + 15) >> 4; // k_plan_seq's block count and placement
+    T = T < 1 ? 1 : (T > SEQ_WG_BLOCKS ? SEQ_WG_BLOCKS : T);
+    const int slot = row0[b] >> 4;
+    const int h0 = (qrow_tile[b] >> 8) * (2 * SEQ_WG_TILES) + slot; // the sequence's first half tile: 16 x its workgroup + slot
+    const bool irn = mask_mode == IRS_MASK_IRN;
+    const bool has_tgt = seq[(int64_t)b * Lmax + Lmax - 1] != 0;
+    const float add_allowed = irn ? r_u[b] : 0.f;
+    const int pq = padq[b];
+    const int ib = i >> 4;
+    const bool tgt_blk = irn && has_tgt && T - 1 > ib; // the target column sits in a block behind the query's
+    const int nblk = ib + 1 + (tgt_blk ? 1 : 0);
+    float *umh = um + ((size_t)b * 4 + h) * 128;
+    float4 u4[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) u4[k] = *reinterpret_cast<const float4 *>(umh + 16 * k + 4 * q);
+    const float ch = cq[(size_t)b * 4 + h];
+    auto blk_of = [&](int n) { return n <= ib ? n : T - 1; };
+    auto gload = [&](float4 (&g)[2], int blk) __attribute__((always_inline)) {
+        const int hidx = h0 + seq_half_of_block(slot & 1, T, blk);
+        const float *p = xf + (size_t)(hidx >> 1) * 4096 + (hidx & 1) * 64 + (tid >> 4) * 128 + (tid & 15) * 4;
+        const bool live = 16 * blk + (tid & 15) < L;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) g[kk] = live ? *reinterpret_cast<const float4 *>(p + 2048 * kk) : make_float4(0.f, 0.f, 0.f, 0.f);
+    };
+    auto sstore = [&](int buf, const float4 (&g)[2]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) *reinterpret_cast<float4 *>(&xs[buf][4 * (tid + 256 * kk)]) = g[kk];
+    };
+    float acc[32];
+#pragma unroll
+    for (int c = 0; c < 32; ++c) acc[c] = 0.f;
+    float mrun = -INFINITY, lsum = 0.f;
+    float4 g[2];
+    gload(g, blk_of(0));
+    sstore(0, g);
+    if (nblk > 1) gload(g, blk_of(1));
+    __syncthreads();
+#pragma unroll 1
+    for (int n = 0; n < nblk; ++n) {
+        const float *xb = &xs[n & 1][4 * (16 * q + r)];
+        float4 x[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k] = *reinterpret_cast<const float4 *>(xb + 256 * k);
+        const int j = 16 * blk_of(n) + r;
+        const bool is_tgt = irn && has_tgt && j == L - 1;
+        const bool ok = j < L && j != pq && (is_tgt || j <= i);
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            s = __fmaf_rn(u4[k].x, x[k].x, s);
+            s = __fmaf_rn(u4[k].y, x[k].y, s);
+            s = __fmaf_rn(u4[k].z, x[k].z, s);
+            s = __fmaf_rn(u4[k].w, x[k].w, s);
+        }
+        s = lanes_sum<48>(s); // over q: the four lanes of a token agree
+        const float sc = ok ? (s + ch) + (is_tgt ? 1.0f : add_allowed) : -INFINITY;
+        const float mnew = fmaxf(mrun, lanes_max<15>(sc)); // (the same bits in every lane of the wave)
+        if (mnew != mrun) { // (uniform) a new maximum: rescale what the earlier blocks left
+            const float al = mrun == -INFINITY ? 1.0f : __expf(mrun - mnew);
+            lsum *= al;
+#pragma unroll
+            for (int c = 0; c < 32; ++c) acc[c] *= al;
+            mrun = mnew;
+        }
+        const float p = sc == -INFINITY ? 0.f : __expf(sc - mnew);
+        lsum += p;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            acc[4 * k + 0] = __fmaf_rn(p, x[k].x, acc[4 * k + 0]);
+            acc[4 * k + 1] = __fmaf_rn(p, x[k].y, acc[4 * k + 1]);
+            acc[4 * k + 2] = __fmaf_rn(p, x[k].z, acc[4 * k + 2]);
+            acc[4 * k + 3] = __fmaf_rn(p, x[k].w, acc[4 * k + 3]);
+        }
+        if (n + 1 < nblk) { // (every wave is past its reads of block n - 1: the barrier that ended trip n - 1)
+            sstore((n + 1) & 1, g);
+            if (n + 2 < nblk) gload(g, blk_of(n + 2));
+        }
+        __syncthreads();
+    }
+    // over the 16 token lanes; lane r < 8 writes piece k = r: m_h[16 k + 4 q ..] = sum / l (l == 0 -> NaN like torch)
+    const float l = lanes_sum<15>(lsum);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float4 o = make_float4(lanes_sum<15>(acc[4 * k + 0]), lanes_sum<15>(acc[4 * k + 1]), lanes_sum<15>(acc[4 * k + 2]),
+                                     lanes_sum<15>(acc[4 * k + 3]));
+        if (r == k) *reinterpret_cast<float4 *>(umh + 16 * k + 4 * q) = make_float4(o.x / l, o.y / l, o.z / l, o.w / l);
+    }
+}
+
+// ao_r[b][32 h + c] = W_v,h[c] . m_h + b_v,h[c]  (W_v = rows [2 d, 3 d) of W_in)
+__global__ void __launch_bounds__(256) k_absorb_out(const float *__restrict__ m, const float *__restrict__ Win, const float *__restrict__ bin,
+                                                    float *__restrict__ ao_r, int B) {
+    constexpr int D = 128, S = ABS_SO;
+    __shared__ __attribute__((aligned(16))) float Ws[64 * ABS_WLD];
+    __shared__ __attribute__((aligned(16))) float ms[S][4 * D];
+    const int tid = threadIdx.x, b0 = blockIdx.x * S;
+#pragma unroll
+    for (int k = 0; k < S * 4 * D / 4 / 256; ++k) {
+        const int idx = tid + 256 * k, s = idx >> 7, c4 = idx & 127;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (b0 + s < B) v = *reinterpret_cast<const float4 *>(m + (size_t)(b0 + s) * 4 * D + 4 * c4);
+        *reinterpret_cast<float4 *>(&ms[s][4 * c4]) = v;
+    }
+    const int r = tid & 63, sg = tid >> 6; // output row r of the staged 64, sequences 2 sg and 2 sg + 1
+#pragma unroll 1
+    for (int ch = 0; ch < 2; ++ch) {
+        __syncthreads();
+        absorb_stage64(Win, 2 * D + 64 * ch, Ws, tid);
+        __syncthreads();
+        const int row = 64 * ch + r, h = row >> 5;
+        const float bv = bin[2 * D + row];
+        float acc[2] = {bv, bv};
+#pragma unroll 4
+        for (int k4 = 0; k4 < D / 4; ++k4) {
+            const float4 w = *reinterpret_cast<const float4 *>(Ws + r * ABS_WLD + 4 * k4);
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const float4 m4 = *reinterpret_cast<const float4 *>(&ms[2 * sg + s][h * D + 4 * k4]);
+                acc[s] = __fmaf_rn(w.x, m4.x, acc[s]);
+                acc[s] = __fmaf_rn(w.y, m4.y, acc[s]);
+                acc[s] = __fmaf_rn(w.z, m4.z, acc[s]);
+                acc[s] = __fmaf_rn(w.w, m4.w, acc[s]);
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+            if (b0 + 2 * sg + s < B) ao_r[(size_t)(b0 + 2 * sg + s) * D + row] = acc[s];
+    }
+}
+
 // ------------------------------------------------------------------ layer norm
 // y = LN(z; g1, b1); if (c) y = LN(y + c; g2, b2).  One wave per row, d <= 512.
 __global__ void __launch_bounds__(256) k_ln(const float *__restrict__ z, const float *__restrict__ g1,
@@ -6368,10 +6649,22 @@ static int last_layer(const DecodeCall &c, int l, const int32_t *pos, float *xro
     const float *q_r = nullptr;
     const int nt = d > 128 ? d / 32 : 4;       // column tiles per token of the fragment-major images
     if (r.seq) {
+#if SEQ_LAST_ABSORB
+        // the sequence-resident launch ended behind layer l - 1: this layer's consumed row attends from x' (tile order) with
+        // absorbed K / V projections; u | m ([B][4][d], in place) and c ([B][4]) lie in act_h, which this route does not use
+        // otherwise (B L ffn_dim floats, L >= 4: 8 B d)
+        float *um = ctx->act_h, *cq = um + (size_t)B * 4 * d;
+        hipLaunchKernelGGL(k_absorb_qu, dim3((B + ABS_SQ - 1) / ABS_SQ), dim3(256), 0, s, xf, ctx->qrow_tile, w.sa_in_w, w.sa_in_b, x_r, um,
+                           cq, B);
+        hipLaunchKernelGGL(k_absorb_attn, dim3(B), dim3(256), 0, s, xf, um, cq, c.seq, ctx->act_ru, L, ctx->dims.mask_mode, c.off, c.cnt,
+                           qrow, ctx->seq_padq, ctx->seq_row0, ctx->qrow_tile);
+        hipLaunchKernelGGL(k_absorb_out, dim3((B + ABS_SO - 1) / ABS_SO), dim3(256), 0, s, um, w.sa_in_w, w.sa_in_b, ao_r, B);
+#else
         // the sequence-resident launch ran this layer's q | k | v and the attention of every consumed token's block: the
         // residual row and the attention row come out of the fragment-major images by the tile-order row index
         hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, xf, ctx->qrow_tile, x_r, d, nt);
         hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, ctx->act_yf, ctx->qrow_tile, ao_r, d, nt);
+#endif
     } else if (r.kv_only) { // the previous layer's kernel wrote k | v only: queries for the B consumed rows here
         hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, xf, qrow, x_r, d, nt);
         LinArgs q{};
