@@ -68,13 +68,20 @@ __global__ void k_cross_const(const float *__restrict__ Wo, const float *__restr
 // t = pos[b] itself), in (b, t) order; cnt[b] / off[b] delimit sequence b; qrow[b] is the packed index of
 // (b, pos[b]); m_dev[0] = total.  Causality is order-preserving, so every kernel just works on shorter
 // sequences.
-// Three small kernels: count (one wave per sequence, ballots), scan (one workgroup), fill (one wave per sequence).
+// Two small kernels: count (one wave per sequence, ballots; the wave also writes the sequence's r_u, k_pif's expression) and
+// fill (one wave per sequence; a workgroup sums the counts of the sequences in front of its own -- at most 16 KB from L2 -- so
+// no scan launch sits between the two).  With the sequence-resident launch k_plan_seq runs between them and fill's wave also
+// writes its sequence's lines of that launch's tables (see there).
 __device__ __forceinline__ bool plan_valid(const int64_t *__restrict__ sq, int t, int L, int p) {
     return t < L && (sq[t] != 0 || t == p);
 }
 
+// U null: the model has no user table, r_u = 0 (irs_launch_pif).
 __global__ void __launch_bounds__(256) k_plan_count(const int64_t *__restrict__ seq, const int32_t *__restrict__ pos, int B,
-                                                    int L, int32_t *__restrict__ cnt, int32_t *__restrict__ tile_seq) {
+                                                    int L, int32_t *__restrict__ cnt, int32_t *__restrict__ tile_seq,
+                                                    const int64_t *__restrict__ user, const float *__restrict__ U, const float *__restrict__ w,
+                                                    const float *__restrict__ bias, float *__restrict__ r_u, int ud,
+                                                    int64_t n_user) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= B) return;
     if (tile_seq && lane < 16) tile_seq[16 * b + lane] = -1; // (the sequence-resident plan's table: 16 half tiles per possible workgroup)
@@ -83,58 +90,24 @@ __global__ void __launch_bounds__(256) k_plan_count(const int64_t *__restrict__ 
     const int64_t *sq = seq + (int64_t)b * L;
     int n = 0;
     for (int t0 = 0; t0 < L; t0 += 64) n += __popcll(__ballot(plan_valid(sq, t0 + lane, L, p)));
-    if (lane == 0) cnt[b] = n;
-}
-
-__global__ void __launch_bounds__(1024) k_plan_scan(const int32_t *__restrict__ cnt, int B, int32_t *__restrict__ off,
-                                                    int32_t *__restrict__ m_dev) {
-    __shared__ int s_scan[1024];
-    __shared__ int s_base;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < B; b0 += 1024) {
-        const int b = b0 + tid;
-        const int n = (b < B) ? cnt[b] : 0;
-        s_scan[tid] = n;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) { // inclusive Hillis-Steele scan
-            int v = (tid >= o) ? s_scan[tid - o] : 0;
-            __syncthreads();
-            s_scan[tid] += v;
-            __syncthreads();
+    // r_u: k_pif's chain (c ascending, + b[0] last); the lanes fetch the operands, every lane runs the same chain
+    float acc = 0.f;
+    if (U) {
+        int64_t u = user[b];
+        if (u < 0) u = 0;
+        if (u >= n_user) u = n_user - 1;
+        const float *e = U + u * (int64_t)ud;
+        for (int c0 = 0; c0 < ud; c0 += 64) {
+            const bool in = c0 + lane < ud;
+            const float ev = in ? e[c0 + lane] : 0.f, wv = in ? w[c0 + lane] : 0.f;
+            const int nc = ud - c0 < 64 ? ud - c0 : 64;
+            for (int c = 0; c < nc; ++c) acc = __fmaf_rn(__shfl(ev, c), __shfl(wv, c), acc);
         }
-        const int base = s_base;
-        if (b < B) off[b] = base + s_scan[tid] - n;
-        __syncthreads();
-        if (tid == 1023) s_base = base + s_scan[1023];
-        __syncthreads();
+        acc = acc + bias[0];
     }
-    if (tid == 0) m_dev[0] = s_base;
-}
-
-__global__ void __launch_bounds__(256) k_plan_fill(const int64_t *__restrict__ seq, const int32_t *__restrict__ pos, int B,
-                                                   int L, const int32_t *__restrict__ off, int32_t *__restrict__ qrow,
-                                                   int32_t *__restrict__ tok_row, int32_t *__restrict__ padq) {
-    const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (b >= B) return;
-    int p = pos[b];
-    p = p < 0 ? 0 : (p >= L ? L - 1 : p);
-    const int64_t *sq = seq + (int64_t)b * L;
-    int o = off[b];
-    for (int t0 = 0; t0 < L; t0 += 64) {
-        const int t = t0 + lane;
-        const bool v = plan_valid(sq, t, L, p);
-        const unsigned long long m = __ballot(v);
-        if (v) {
-            const int idx = o + __popcll(m & ((1ull << lane) - 1ull));
-            tok_row[idx] = b * L + t;
-            if (t == p) {
-                qrow[b] = idx;
-                padq[b] = (sq[t] == 0) ? idx - off[b] : -1; // the only pad a packed sequence can hold
-            }
-        }
-        o += __popcll(m);
+    if (lane == 0) {
+        cnt[b] = n;
+        r_u[b] = acc;
     }
 }
 
@@ -157,9 +130,8 @@ static int irs_cu_count() {
 // <= 16 blocks fits, so the packing is one-dimensional, best fit, largest first, done class by class (nb = 16 .. 1) with the
 // open workgroups kept as pools per free-block count f: the items of a class fill the pools' free blocks smallest f first (a
 // workgroup with f free blocks takes floor(f / nb) of them), the rest opens new workgroups.  Workgroups are created as
-// contiguous id ranges and move between pools a prefix at a time, so a pool is a short list of ranges and item i of a class
-// finds its (workgroup, first half tile) by arithmetic: every thread places its own items, one thread does the O(pools)
-// bookkeeping between classes (a one-thread walk over 4096 sequences took 1.7 ms).
+// contiguous id ranges, class by class, and item i of a class finds its (workgroup, first half tile) by arithmetic on what
+// one thread counted up front from the histogram (see k_plan_seq; a one-thread walk over 4096 sequences took 1.7 ms).
 // Which block goes to which of the sequence's half tiles depends on (slot parity, nb) alone (seq_half_of_block): the two halves of
 // a wave tile get MIRRORED blocks (i, nb - 1 - i) -- causal attention costs qb + 1 key tiles for block qb, so every wave of a
 // sequence gets nb + 1 of them -- and the one or two halves left over at an odd start / end get the middle block(s) and share
@@ -172,7 +144,6 @@ static int irs_cu_count() {
 #define SEQ_WG_TILES 8
 #define SEQ_WG_BLOCKS 16
 #define SEQ_AUTO_MIN_SEQS 384
-#define SEQ_RMAX 48
 // The tail rule (round 6).  One workgroup fits a CU, so the launch runs in rounds of n_cu workgroups and a last round of a few
 // workgroups costs a whole one.  A workgroup whose live tiles all sit on waves 4 .. 7 -- one wave per SIMD; its other four waves
 // only keep the ring going (k_block_x6's idle path) -- finishes in a fraction of a full one's time (profiles/r06).  So the plan
@@ -205,23 +176,45 @@ __host__ __device__ __forceinline__ int seq_half_of_block(bool slot_odd, int nb,
     return blk < mir ? 1 + 2 * blk : 2 + 2 * mir;
 }
 #define SEQ_PLAN_PER_THREAD 8 // x 1024: the sequences the plan kernel's LDS tables hold (the launch takes up to 8192 sequences)
-__global__ void __launch_bounds__(1024) k_plan_seq(const int32_t *__restrict__ cnt, const int32_t *__restrict__ off,
-                                                   const int32_t *__restrict__ qrow, int B, int32_t *__restrict__ tile_seq,
-                                                   int32_t *__restrict__ tile_qb, int32_t *__restrict__ seq_row0,
-                                                   int32_t *__restrict__ qrow_tile, int32_t *__restrict__ n_wg, int tiles_cap,
-                                                   int n_cu) {
+#ifdef PLAN_STAMP // (lab, tools/seq_lab.sh plan_stamp, tools/plan_stamps.py) s_memtime of thread 0 at the kernel's boundaries, [16 + wave]: the wave's end
+__device__ unsigned long long g_plan_t[32];
+extern "C" void *irs_lab_plan_stamps() {
+    void *p = nullptr;
+    return hipGetSymbolAddress(&p, HIP_SYMBOL(g_plan_t)) == hipSuccess ? p : nullptr;
+}
+#define PSTAMP(i) do { if (threadIdx.x == 0) g_plan_t[i] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define PSTAMP(i)
+#endif
+// What every class does to the pools depends on the histogram of block counts alone, not on where anything was placed.  So
+// thread 0 works the whole plan out up front on the COUNT of workgroups per free-block count (`count` below: unrolled, in
+// registers) and leaves one line per class in LDS: for every pool f the index of the first item that goes to it (c_cum), the
+// items that fit the pools (c_exist), the first new workgroup id and how many full and half-live ones the class opens.  Then
+// every thread OWNS the workgroups tid, tid + 1024, ... (their free-block counts live in its registers) and walks the classes
+// without a barrier: a workgroup with f >= T free blocks draws its rank r among the pool's workgroups from an LDS counter of
+// that (class, pool) -- any order packs equally well -- and pulls the items cum[f] + r q .. + q - 1 (q = f / T) that lie below
+// c_exist: it leaves its id at the first of them (s_first); a workgroup the class opens holds the items its id says.  Behind one
+// barrier every thread finds (workgroup, first half tile) of its own sequences by the same arithmetic and leaves
+// 16 x workgroup + half tile in place[b]; k_plan_fill's wave of sequence b, spread over all CUs, writes the table lines.
+// (The first version: thread 0 moved id ranges between pool lists in LDS between the classes, behind two barriers per class
+// that also waited for the class's table stores -- 57 K scattered 4-byte stores from ONE CU: 70 us, of which thread 0's two
+// sections took 24 and the placements with their barriers 33; profiles/step_front_tail.  A full range list dropped a range
+// there; here nothing can overflow, so the plan always opens the workgroups `count` counts.)
+__global__ void __launch_bounds__(1024) k_plan_seq(const int32_t *__restrict__ cnt, int B, int32_t *__restrict__ place,
+                                                   int32_t *__restrict__ n_wg, int n_cu) {
     constexpr int C = SEQ_WG_BLOCKS, PT = SEQ_PLAN_PER_THREAD, CT = SEQ_TAIL_BLOCKS;
     __shared__ int s_hist[C + 1], s_start[C + 2];
-    __shared__ int p_n[C], p_s[C][SEQ_RMAX], p_l[C][SEQ_RMAX]; // pool f = 1 .. 15: ranges of workgroup ids with f free blocks
-    __shared__ int c_cum[C + 1], c_q[C], c_exist, c_newbase, s_nwg;
-    __shared__ int s_cap, s_tail0, c_norm, c_nnorm; // the tail rule: full workgroups allowed, first tail id; per class: items / workgroups opened full
-    // the sequences sorted by block count (largest first) and each one's consumed token, in LDS: the class loop below loads nothing
-    // from memory (the first version re-read a sorted index array and three per-sequence values there: a round trip per class)
-    __shared__ unsigned short s_order[1024 * PT], s_pt[1024 * PT];
+    // the plan per class, [0]: without the tail rule's cap, [1]: with it; s_sel: the one that holds
+    __shared__ int c_cum[2][C + 1][C], c_exist[2][C + 1], c_newbase[2][C + 1], c_norm[2][C + 1], c_nnorm[2][C + 1], c_ntail[2][C + 1];
+    __shared__ int s_rank[C + 1][C]; // workgroups of pool f that have drawn their rank in class T
+    __shared__ int s_sel, s_nwg;
+    // per item (the sequences sorted by block count, largest first; inside a class by arrival) that is the FIRST one a pool's
+    // workgroup pulls: that workgroup
+    __shared__ unsigned short s_first[1024 * PT];
     const int tid = threadIdx.x;
+    PSTAMP(0);
     if (tid <= C) s_hist[tid] = 0;
-    if (tid < C) p_n[tid] = 0;
-    if (tid == 0) s_nwg = 0, s_tail0 = -1;
+    if (tid < (C + 1) * C) (&s_rank[0][0])[tid] = 0;
     __syncthreads();
     int my_T[PT], my_rk[PT];
 #pragma unroll
@@ -232,39 +225,42 @@ __global__ void __launch_bounds__(1024) k_plan_seq(const int32_t *__restrict__ c
             int nb = (cnt[b] + 15) >> 4;
             nb = nb < 1 ? 1 : (nb > C ? C : nb);
             my_T[j] = nb;
-            int pt = qrow[b] - off[b];
-            s_pt[b] = (unsigned short)(pt < 0 ? 0 : (pt > 65535 ? 65535 : pt));
         }
     }
 #pragma unroll
     for (int j = 0; j < PT; ++j)
         if (my_T[j]) my_rk[j] = atomicAdd(&s_hist[my_T[j]], 1); // rank inside the class: the order of arrival (any order packs equally well)
     __syncthreads();
-    if (tid == 0) {
+    if (tid >= 1 && tid <= C) { // largest first
         int run = 0;
-        for (int T = C; T >= 1; --T) { // largest first
-            s_start[T] = run;
-            run += s_hist[T];
-        }
-        // the tail rule (see above): the plan below, replayed on the COUNT of workgroups per free-block count alone -- what the
-        // class loop does to the pools, without their id ranges and without placing anything.  Once without a cap (the
-        // workgroups of the plain plan, and those its classes above CT blocks open) and, if the last round is short, once more
-        // with the cap (the half-live workgroups the rule would open).  This arithmetic and the class loop's must stay in step;
-        // they differ only when a pool's range list is full (SEQ_RMAX): the plan then drops a range and opens more workgroups
-        // than counted -- the order of ids holds, only the rounds are no longer the counted ones.
+        for (int U = C; U > tid; --U) run += s_hist[U];
+        s_start[tid] = run;
+    }
+    __syncthreads();
+    PSTAMP(1);
+    if (tid == 0) {
+        // Best fit, largest class first, on the counts dc[f] of workgroups with f free blocks: the items of class T fill the
+        // pools' free blocks smallest f first (fl workgroups take q = f / T items each and move to pool f - T q, one takes the
+        // pa left over), the rest opens new workgroups -- full ones while fewer than `cap` exist (a class above CT blocks:
+        // always), half-live ones behind them.  Once without a cap (the workgroups of the plain plan, and those its classes
+        // above CT blocks open) and, if the last round is short, once more with the cap (the tail rule, see above).
         // (fully unrolled, the counts in registers, every divisor a constant: a loop over an LDS table took 20 us here)
-        auto count = [&](const int cap, int &nwg, int &nbig, int &ntail) __attribute__((always_inline)) {
+        auto count = [&](const int cap, const int set, int &nwg, int &nbig, int &ntail, int &tail0) __attribute__((always_inline)) {
             int dc[C];
-            nwg = 0, nbig = 0, ntail = 0;
+            nwg = 0, nbig = 0, ntail = 0, tail0 = -1;
 #pragma unroll
             for (int f = 0; f < C; ++f) dc[f] = 0;
 #pragma unroll
             for (int T = C; T >= 1; --T) {
-                int left = s_hist[T];
+                const int n = s_hist[T];
+                int left = n;
                 if (left > 0) {
+                    int tot = 0;
 #pragma unroll
                     for (int f = T; f < C; ++f) {
                         const int q = f / T, have = dc[f] * q, used = left < have ? left : have;
+                        c_cum[set][T][f] = tot;
+                        tot += have;
                         if (used > 0) {
                             const int fl = used / q, pa = used - fl * q;
                             left -= used;
@@ -274,13 +270,16 @@ __global__ void __launch_bounds__(1024) k_plan_seq(const int32_t *__restrict__ c
                                 if (pa == p) dc[f - T * p] += 1;
                         }
                     }
-                    const int q = C / T;
+                    c_exist[set][T] = n - left, c_newbase[set][T] = nwg;
+                    const int q = C / T, base0 = nwg;
+                    int ntl = 0;
                     if (T <= CT) { // behind the cap: half-live workgroups
                         const int qt = T <= CT ? CT / T : 1, room = cap > nwg ? cap - nwg : 0;
                         if ((long long)room * q < left) {
                             const int tl = left - room * q, flt = tl / qt, pat = tl - flt * qt;
                             left = room * q;
-                            dc[CT - T * qt] += flt, nwg += flt + (pat ? 1 : 0), ntail += flt + (pat ? 1 : 0);
+                            ntl = flt + (pat ? 1 : 0);
+                            dc[CT - T * qt] += flt, nwg += ntl, ntail += ntl;
 #pragma unroll
                             for (int p = 1; p < qt; ++p)
                                 if (pat == p) dc[CT - T * p] += 1;
@@ -291,130 +290,148 @@ __global__ void __launch_bounds__(1024) k_plan_seq(const int32_t *__restrict__ c
 #pragma unroll
                     for (int p = 1; p < q; ++p)
                         if (pa == p) dc[C - T * p] += 1;
+                    // ids: the full workgroups first, the half-live ones behind them
+                    c_norm[set][T] = left, c_nnorm[set][T] = fl + (pa ? 1 : 0), c_ntail[set][T] = ntl;
+                    if (ntl > 0 && tail0 < 0) tail0 = base0 + fl + (pa ? 1 : 0);
                 }
                 if (T == CT + 1) nbig = nwg; // the workgroups the classes that cannot go to the tail open
             }
         };
-        int nwg, nbig, ntail;
-        count(0x7FFFFFFF, nwg, nbig, ntail);
+        int nwg, nbig, ntail, tail0, sel = 0;
+        count(0x7FFFFFFF, 0, nwg, nbig, ntail, tail0);
         const int rounds = n_cu > 0 ? nwg / n_cu : 0, rem = nwg - rounds * n_cu;
-        s_cap = 0x7FFFFFFF;
-        if (SEQ_LAB_PLAN == 0 && n_cu > 0 && rem > 0 && 2 * rem <= n_cu && nbig <= rounds * n_cu) {
-            int nwg2, nbig2;
-            count(rounds * n_cu, nwg2, nbig2, ntail);
-            if (ntail <= n_cu) s_cap = rounds * n_cu; // (more than one half-live workgroup per CU would cost more than the full round)
+        if (SEQ_LAB_PLAN == 1 || (SEQ_LAB_PLAN == 0 && n_cu > 0 && rem > 0 && 2 * rem <= n_cu && nbig <= rounds * n_cu)) {
+            int nwg2, nbig2, ntail2, tail02;
+            // (lab) SEQ_LAB_PLAN 1: every sequence of at most CT blocks in a half-live workgroup; 2: the plan without the rule
+            count(SEQ_LAB_PLAN == 1 ? 0 : rounds * n_cu, 1, nwg2, nbig2, ntail2, tail02);
+            // (more than one half-live workgroup per CU would cost more than the full round)
+            if (SEQ_LAB_PLAN == 1 || ntail2 <= n_cu) sel = 1, nwg = nwg2, tail0 = tail02;
         }
-        if (SEQ_LAB_PLAN == 1) s_cap = 0;          // (lab) every sequence of at most CT blocks in a half-live workgroup
-        if (SEQ_LAB_PLAN == 2) s_cap = 0x7FFFFFFF; // (lab) the plan without the rule
+        s_sel = sel, s_nwg = nwg;
+        n_wg[0] = nwg, n_wg[1] = tail0 < 0 ? nwg : tail0;
     }
     __syncthreads();
+    PSTAMP(2);
+    const int sel = s_sel, nwg_all = s_nwg;
+    int wf[PT]; // free blocks of the workgroups this thread owns (0: not opened yet, or full)
 #pragma unroll
-    for (int j = 0; j < PT; ++j)
-        if (my_T[j]) s_order[s_start[my_T[j]] + my_rk[j]] = (unsigned short)(tid + 1024 * j);
-    __syncthreads();
-    auto pool_bins = [&](int f) {
-        int n = 0;
-        for (int r = 0; r < p_n[f]; ++r) n += p_l[f][r];
-        return n;
-    };
-    auto append = [&](int f, int start, int len) { // (thread 0) `len` workgroups from `start` on now have f free blocks
-        if (f < 1 || len < 1) return;
-        if (p_n[f] > 0 && p_s[f][p_n[f] - 1] + p_l[f][p_n[f] - 1] == start) p_l[f][p_n[f] - 1] += len;
-        else if (p_n[f] < SEQ_RMAX) p_s[f][p_n[f]] = start, p_l[f][p_n[f]] = len, ++p_n[f];
-        // (a full list drops the range: those workgroups stay as filled as they are -- packing quality, never correctness)
-    };
-    auto take_prefix = [&](int f, int m, int dest) { // (thread 0) the first m workgroups of pool f move to pool dest
-        for (int r = 0; r < p_n[f] && m > 0; ++r) {
-            const int t = m < p_l[f][r] ? m : p_l[f][r];
-            append(dest, p_s[f][r], t);
-            p_s[f][r] += t, p_l[f][r] -= t, m -= t;
-        }
-        int w = 0;
-        for (int r = 0; r < p_n[f]; ++r)
-            if (p_l[f][r] > 0) p_s[f][w] = p_s[f][r], p_l[f][w] = p_l[f][r], ++w;
-        p_n[f] = w;
-    };
+    for (int k = 0; k < PT; ++k) wf[k] = 0;
     for (int T = C; T >= 1; --T) { // largest first
-        const int n = s_hist[T], qnew = C / T;
+        const int n = s_hist[T];
         if (n == 0) continue; // (uniform: s_hist is shared)
-        if (tid == 0) {
-            int tot = 0;
-            for (int f = T; f < C; ++f) {
-                c_cum[f] = tot, c_q[f] = f / T;
-                tot += pool_bins(f) * c_q[f];
-            }
-            c_cum[C] = tot;
-            c_exist = n < tot ? n : tot;
-            c_newbase = s_nwg;
-            // new workgroups: full ones while the cap lasts (a class above CT blocks: always), half-live ones behind them
-            const int nnew = n - c_exist, room = s_cap > s_nwg ? s_cap - s_nwg : 0;
-            const bool spill = T <= CT && nnew > 0 && (long long)room * qnew < nnew;
-            c_norm = spill ? room * qnew : nnew;
-            c_nnorm = (c_norm + qnew - 1) / qnew;
-            const int ntail = spill ? (nnew - c_norm + CT / T - 1) / (CT / T) : 0;
-            if (ntail > 0 && s_tail0 < 0) s_tail0 = c_newbase + c_nnorm;
-            s_nwg += c_nnorm + ntail;
-        }
-        __syncthreads();
-        const int exist = c_exist, base = s_start[T];
-        for (int i = tid; i < n; i += 1024) {
-            const int b = s_order[base + i];
-            int w, slot;
-            if (i < exist) {
-                int f = T;
-                while (f < C - 1 && i >= c_cum[f + 1]) ++f;
-                const int s_ = i - c_cum[f];
-                int bl = s_ / c_q[f];
-                const int k = s_ % c_q[f];
-                int r = 0;
-                while (r < p_n[f] - 1 && bl >= p_l[f][r]) bl -= p_l[f][r], ++r;
-                w = p_s[f][r] + bl;
-                slot = (C - f) + k * T;
-            } else if (i - exist < c_norm) {
-                const int j_ = i - exist;
-                w = c_newbase + j_ / qnew;
-                slot = (j_ % qnew) * T;
-            } else { // a half-live workgroup: half tiles [C - CT, C) = the tiles of waves 4 .. 7, one wave per SIMD
-                const int j_ = i - exist - c_norm, qt = CT / T;
-                w = c_newbase + c_nnorm + j_ / qt;
-                slot = (C - CT) + (j_ % qt) * T;
-            }
-            if (w * SEQ_WG_TILES >= tiles_cap) continue; // (cannot happen: at most one workgroup per sequence)
-            // the sequence's T blocks onto the half tiles [slot, slot + T) of workgroup w
-            const int h0 = 2 * SEQ_WG_TILES * w + slot;
-            for (int blk = 0; blk < T; ++blk) {
-                const int h = h0 + seq_half_of_block(slot & 1, T, blk);
-                tile_seq[h] = b, tile_qb[h] = blk;
-            }
-            seq_row0[b] = 16 * slot;
-            const int pt = s_pt[b];
-            int pb = pt >> 4; // the consumed token: block pb
-            pb = pb < 0 ? 0 : (pb >= T ? T - 1 : pb);
-            qrow_tile[b] = 16 * (h0 + seq_half_of_block(slot & 1, T, pb)) + (pt & 15);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int left = exist;
-            for (int f = T; f < C && left > 0; ++f) {
-                const int q = c_q[f], cap = pool_bins(f) * q;
-                const int used = left < cap ? left : cap;
-                left -= used;
-                const int full = used / q, part = used % q;
-                take_prefix(f, full, f - T * q);
-                if (part) take_prefix(f, 1, f - T * part);
-            }
-            const int nnew = c_norm, fullnew = nnew / qnew, partnew = nnew % qnew;
-            append(C - T * qnew, c_newbase, fullnew);
-            if (partnew) append(C - T * partnew, c_newbase + fullnew, 1);
-            if (n - exist > c_norm) { // (T <= CT) a half-live workgroup enters the pools with the free blocks of its live half
-                const int ntl = n - exist - c_norm, qt = CT / T, fullt = ntl / qt, partt = ntl % qt;
-                append(CT - T * qt, c_newbase + c_nnorm, fullt);
-                if (partt) append(CT - T * partt, c_newbase + c_nnorm + fullt, 1);
+        const int exist = c_exist[sel][T], newbase = c_newbase[sel][T], nnorm = c_nnorm[sel][T], ntl = c_ntail[sel][T],
+                  base = s_start[T];
+#pragma unroll
+        for (int k = 0; k < PT; ++k) {
+            const int w = tid + 1024 * k;
+            if (1024 * k >= nwg_all) break; // (uniform)
+            if (w < newbase) {
+                const int f = wf[k];
+                if (f >= T && exist > 0) { // a workgroup of pool f: items i0 .. i0 + q - 1 below exist
+                    const int q = f / T, i0 = c_cum[sel][T][f] + q * atomicAdd(&s_rank[T][f], 1);
+                    if (i0 < exist) {
+                        s_first[base + i0] = (unsigned short)w;
+                        wf[k] = f - T * (exist - i0 < q ? exist - i0 : q);
+                    }
+                }
+            } else if (w < newbase + nnorm) { // opened by this class, full: items exist + j qnew .. of the c_norm the class places so
+                const int qnew = C / T, j_ = w - newbase, norm = c_norm[sel][T];
+                wf[k] = C - T * (norm - j_ * qnew < qnew ? norm - j_ * qnew : qnew);
+            } else if (w < newbase + nnorm + ntl) { // opened half-live: the rest of the class, CT / T items each
+                const int qt = CT / T, j_ = w - newbase - nnorm, left = n - exist - c_norm[sel][T];
+                wf[k] = CT - T * (left - j_ * qt < qt ? left - j_ * qt : qt);
             }
         }
-        __syncthreads();
     }
-    if (tid == 0) n_wg[0] = s_nwg, n_wg[1] = s_tail0 < 0 ? s_nwg : s_tail0;
+    __syncthreads();
+    PSTAMP(3);
+    // every thread: (workgroup, first half tile) of its own sequences, item i of class T
+#pragma unroll
+    for (int j = 0; j < PT; ++j) {
+        const int T = my_T[j], i = my_rk[j];
+        if (T == 0) continue;
+        const int exist = c_exist[sel][T], norm = c_norm[sel][T], qnew = C / T;
+        int w, slot;
+        if (i < exist) { // in a workgroup of pool f with f free blocks: behind the C - f blocks it holds
+            int f = T;
+            while (f < C - 1 && i >= c_cum[sel][T][f + 1]) ++f;
+            const int s_ = i - c_cum[sel][T][f], q = f / T, r = s_ / q;
+            w = s_first[s_start[T] + c_cum[sel][T][f] + r * q];
+            slot = (C - f) + (s_ - r * q) * T;
+        } else if (i - exist < norm) {
+            const int j_ = i - exist;
+            w = c_newbase[sel][T] + j_ / qnew;
+            slot = (j_ % qnew) * T;
+        } else { // a half-live workgroup: half tiles [C - CT, C) = the tiles of waves 4 .. 7, one wave per SIMD
+            const int j_ = i - exist - norm, qt = T <= CT ? CT / T : 1;
+            w = c_newbase[sel][T] + c_nnorm[sel][T] + j_ / qt;
+            slot = (C - CT) + (j_ % qt) * T;
+        }
+        place[tid + 1024 * j] = 16 * w + slot;
+    }
+#ifdef PLAN_STAMP
+    if ((tid & 63) == 0) g_plan_t[16 + (tid >> 6)] = __builtin_amdgcn_s_memtime();
+#endif
+}
+
+// place (null: no sequence-resident launch): k_plan_seq's note per sequence, 16 x workgroup + first half tile, in seq_row0[b].
+// The wave then writes the sequence's lines of that launch's tables (layout: above k_plan_seq): lane blk the half tile of block blk.
+__global__ void __launch_bounds__(256) k_plan_fill(const int64_t *__restrict__ seq, const int32_t *__restrict__ pos, int B,
+                                                   int L, const int32_t *__restrict__ cnt, int32_t *__restrict__ off,
+                                                   int32_t *__restrict__ qrow, int32_t *__restrict__ tok_row,
+                                                   int32_t *__restrict__ padq, int32_t *__restrict__ m_dev,
+                                                   int32_t *__restrict__ tile_seq, int32_t *__restrict__ tile_qb,
+                                                   int32_t *__restrict__ seq_row0, int32_t *__restrict__ qrow_tile, int tiles_cap) {
+    __shared__ int s_part[4];
+    const int wave = threadIdx.x >> 6, b = blockIdx.x * 4 + wave, lane = threadIdx.x & 63;
+    int base = 0; // tokens of the sequences in front of this workgroup's four
+    for (int i = threadIdx.x; i < 4 * (int)blockIdx.x; i += 256) base += cnt[i];
+    for (int o = 32; o >= 1; o >>= 1) base += __shfl_xor(base, o);
+    if (lane == 0) s_part[wave] = base;
+    __syncthreads();
+    if (b >= B) return;
+    int o = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+    for (int i = 4 * blockIdx.x; i < b; ++i) o += cnt[i];
+    const int ob = o;
+    int p = pos[b];
+    p = p < 0 ? 0 : (p >= L ? L - 1 : p);
+    const int64_t *sq = seq + (int64_t)b * L;
+    if (lane == 0) off[b] = ob;
+    int below = 0; // valid tokens in front of the consumed one: its position in the packed sequence
+    for (int t0 = 0; t0 < L; t0 += 64) {
+        const int t = t0 + lane;
+        const bool v = plan_valid(sq, t, L, p);
+        const unsigned long long m = __ballot(v);
+        if (v) {
+            const int idx = o + __popcll(m & ((1ull << lane) - 1ull));
+            tok_row[idx] = b * L + t;
+            if (t == p) {
+                qrow[b] = idx;
+                padq[b] = (sq[t] == 0) ? idx - ob : -1; // the only pad a packed sequence can hold
+            }
+        }
+        const int nlow = p - t0; // tokens of this chunk in front of the consumed one
+        below += __popcll(m & (nlow >= 64 ? ~0ull : (nlow <= 0 ? 0ull : (1ull << nlow) - 1ull)));
+        o += __popcll(m);
+    }
+    if (b == B - 1 && lane == 0) m_dev[0] = o;
+    if (!tile_seq) return;
+    int T = (o - ob + 15) >> 4; // k_plan_seq's block count
+    T = T < 1 ? 1 : (T > SEQ_WG_BLOCKS ? SEQ_WG_BLOCKS : T);
+    const int pl = seq_row0[b], w = pl >> 4, slot = pl & 15;
+    if (w < 0 || w * SEQ_WG_TILES >= tiles_cap || slot + T > SEQ_WG_BLOCKS) return; // (cannot happen: at most one workgroup per sequence)
+    // the sequence's T blocks onto the half tiles [slot, slot + T) of workgroup w
+    const int h0 = 2 * SEQ_WG_TILES * w + slot;
+    if (lane < T) {
+        const int h = h0 + seq_half_of_block(slot & 1, T, lane);
+        tile_seq[h] = b, tile_qb[h] = lane;
+    }
+    if (lane == 0) {
+        seq_row0[b] = 16 * slot;
+        int pb = below >> 4; // the consumed token: block pb
+        pb = pb >= T ? T - 1 : pb;
+        qrow_tile[b] = 16 * (h0 + seq_half_of_block(slot & 1, T, pb)) + (below & 15);
+    }
 }
 
 // Few sequences (the latency path): count, scan and fill in ONE workgroup of 16 waves, together with the
@@ -6259,7 +6276,7 @@ int irs_launch_pack_small(irs_ctx *ctx, hipStream_t s) {
 // ------------------------------------------------------------------ decode routes: chosen once per call by decode_route
 // A rows-only decode (the caller wants x[b, pos[b], :] only) runs on the PACKED non-pad tokens (every kernel behind the plan clamps
 // its row count to the device-side total) and evaluates the LAST layer for the one consumed row per sequence.
-enum class DecPlan { NONE, MULTI, SMALL, IN_EMBED }; // full decode; k_plan_count / scan / fill; k_plan_small; inside the embed kernel
+enum class DecPlan { NONE, MULTI, SMALL, IN_EMBED }; // full decode; k_plan_count / fill; k_plan_small; inside the embed kernel
 enum class DecEmbed { FULL, PACKED, FRAG, FRAG_QKV, SMALL16_QKV, ANY_QKV, SEQ };
 // the rest of a layer behind its attention: per-GEMM float32 kernels (GEMM_LN: LayerNorms fused into the GEMM epilogues),
 // fragment-major x / y (FRAG_*), or one 16-token layer kernel (SMALL16: d = 128, F = 256; WIDE: d = 256; ANY: other small shapes)
@@ -6702,7 +6719,8 @@ int irs_launch_decode(irs_ctx *ctx, const int64_t *seq, const int64_t *user, int
     const DecodeRoute r = decode_route(ctx, B, x_out == nullptr && pos && xrows && L >= 4);
     int rc;
     if (ctx->step_pair && !r.small_plan) IRS_FAIL(ctx, IRS_E_STATE, "merged path step needs the single-workgroup plan kernel");
-    if (!r.small_plan && (rc = irs_launch_pif(ctx, user, B, ctx->act_ru, s)) != IRS_OK) return rc;
+    // (r_u: every plan writes it -- k_plan_small, k_plan_count, the embed kernel that plans a single sequence)
+    if (r.plan == DecPlan::NONE && (rc = irs_launch_pif(ctx, user, B, ctx->act_ru, s)) != IRS_OK) return rc;
     ctx->seq_last = r.seq;
     // (the field order of irs_decoder_route_last, include/irs_hip.h)
     const int32_t packed[IRS_ROUTE_FIELDS] = {r.rows_only, r.small_plan, (int32_t)r.plan, (int32_t)r.embed, (int32_t)r.layer,
@@ -6716,15 +6734,17 @@ int irs_launch_decode(irs_ctx *ctx, const int64_t *seq, const int64_t *user, int
                            ctx->tok_row, ctx->seq_padq, ctx->m_dev, user, pif_table(ctx), ctx->um_w, ctx->um_b, ctx->act_ru,
                            ctx->dims.u_dim, ctx->dims.n_user, ctx->step_pair);
     } else if (r.plan == DecPlan::MULTI) {
-        hipLaunchKernelGGL(k_plan_count, dim3((B + 3) / 4), dim3(256), 0, s, seq, pos, B, L, ctx->seq_cnt, ctx->tile_seq);
-        hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(1024), 0, s, ctx->seq_cnt, B, ctx->seq_off, ctx->m_dev);
-        hipLaunchKernelGGL(k_plan_fill, dim3((B + 3) / 4), dim3(256), 0, s, seq, pos, B, L, ctx->seq_off, ctx->seq_qrow, ctx->tok_row,
-                           ctx->seq_padq);
+        // count (+ r_u) [, k_plan_seq], fill (computes its own base; writes the sequence-resident launch's tables from
+        // k_plan_seq's notes): three dependent launches in stream order
+        hipLaunchKernelGGL(k_plan_count, dim3((B + 3) / 4), dim3(256), 0, s, seq, pos, B, L, ctx->seq_cnt, ctx->tile_seq, user,
+                           pif_table(ctx), ctx->um_w, ctx->um_b, ctx->act_ru, ctx->dims.u_dim, ctx->dims.n_user);
+        // (the rounds of the sequence-resident launch, for the plan's tail rule: the CU count)
+        if (r.seq)
+            hipLaunchKernelGGL(k_plan_seq, dim3(1), dim3(1024), 0, s, ctx->seq_cnt, B, ctx->seq_row0, ctx->n_wg_dev, irs_cu_count());
+        hipLaunchKernelGGL(k_plan_fill, dim3((B + 3) / 4), dim3(256), 0, s, seq, pos, B, L, ctx->seq_cnt, ctx->seq_off, ctx->seq_qrow,
+                           ctx->tok_row, ctx->seq_padq, ctx->m_dev, r.seq ? ctx->tile_seq : nullptr, ctx->tile_idx, ctx->seq_row0,
+                           ctx->qrow_tile, B * SEQ_WG_TILES);
     }
-    const int n_cu = r.seq ? irs_cu_count() : 0; // (the rounds of the sequence-resident launch: the plan's tail rule)
-    if (r.seq)
-        hipLaunchKernelGGL(k_plan_seq, dim3(1), dim3(1024), 0, s, ctx->seq_cnt, ctx->seq_off, ctx->seq_qrow, B, ctx->tile_seq,
-                           ctx->tile_idx, ctx->seq_row0, ctx->qrow_tile, ctx->n_wg_dev, B * SEQ_WG_TILES, n_cu);
     launch_embed(c, pos, user);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     if (r_u_out) IRS_CHECK_HIP(ctx, hipMemcpyAsync(r_u_out, ctx->act_ru, sizeof(float) * B, hipMemcpyDeviceToDevice, s));
