@@ -84,7 +84,7 @@ typedef struct irs_dims {
     int64_t n_item;   /* catalog size N (global) */
     int64_t n_user;   /* rows of user_embedder (0 for SampleNet) */
     int32_t d;        /* emb_dim (even, <= 256) */
-    int32_t max_len;  /* L (<= 256) */
+    int32_t max_len;  /* L (<= 256; <= IRS_MAX_LEN_LONG through irs_create_ex with IRS_CREATE_LONG_WINDOWS) */
     int32_t n_heads;  /* H, divides d; d / H <= 64 */
     int32_t ffn_dim;  /* F */
     int32_t n_layers;
@@ -108,6 +108,18 @@ int irs_abi_version(void);
 const char *irs_last_error(const irs_ctx *ctx); /* ctx may be NULL: last create() error */
 
 int irs_create(irs_ctx **out, const irs_dims *dims, const irs_shard *shard);
+/* irs_create with flags.  flags == 0 is irs_create exactly (max_len in [2, 256]).  IRS_CREATE_LONG_WINDOWS admits max_len in
+ * [2, IRS_MAX_LEN_LONG]; every other check is unchanged, and a context with max_len <= 256 is the one irs_create gives (same
+ * kernels, same routes, same bytes).  An unknown flag bit -> IRS_E_INVALID with a message (irs_last_error(NULL)).
+ * Above 256 the decoder's all-rows attention streams K / V through LDS in key chunks (k_attn_long) and the last layer's row
+ * walks key chunks of 256; the split-precision fused routes (sequence-resident launch, float16 K / V planes, the fused block
+ * and the attention inside the 16-token kernel) are never taken.  The bound of 1024 is what the search kernels pay per window:
+ * 16 window registers (64-bit) per lane in the path / beam / survivor-flag steps, a 32-word key bitmask in the attention, an
+ * 8 KB (16 KB with path entries) sort buffer in the survivor strips, and 2 x max_seqs x (8 L + 20) bytes of compaction copies
+ * in the _until loops. */
+#define IRS_CREATE_LONG_WINDOWS 1u
+#define IRS_MAX_LEN_LONG 1024
+int irs_create_ex(irs_ctx **out, const irs_dims *dims, const irs_shard *shard, uint32_t flags);
 void irs_destroy(irs_ctx *ctx);
 
 /* ---- weights -----------------------------------------------------------

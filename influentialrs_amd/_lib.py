@@ -8,12 +8,13 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libirs_hip.so")
 
 IRS_MASK_IRN, IRS_MASK_CAUSAL = 0, 1
+IRS_CREATE_LONG_WINDOWS, IRS_MAX_LEN_LONG = 1, 1024  # irs_create_ex: max_len above 256
 IRS_SWEEP_BF16, IRS_SWEEP_F32, IRS_SWEEP_EXHAUSTIVE = 0, 1, 2
 IRS_ROW_FALLBACK, IRS_ROW_NO_CANDIDATE, IRS_ROW_FEWER_THAN_K, IRS_ROW_RESCUED = 1, 2, 4, 8
 IRS_GEMM_F32, IRS_GEMM_X6, IRS_GEMM_H3 = 0, 1, 2
@@ -44,6 +45,7 @@ SIGNATURES = {
     "irs_abi_version": (c_int32, []),
     "irs_last_error": (c_char_p, [c_void_p]),
     "irs_create": (c_int32, [POINTER(c_void_p), POINTER(IrsDims), POINTER(IrsShard)]),
+    "irs_create_ex": (c_int32, [POINTER(c_void_p), POINTER(IrsDims), POINTER(IrsShard), c_uint32]),
     "irs_destroy": (None, [c_void_p]),
     "irs_bind_weight": (c_int32, [c_void_p, c_char_p, c_void_p, c_int64]),
     "irs_derived_bytes": (c_size_t, [c_void_p]),

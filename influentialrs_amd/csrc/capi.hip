@@ -18,7 +18,9 @@ extern "C" int irs_abi_version(void) { return IRS_ABI_VERSION; }
 
 extern "C" const char *irs_last_error(const irs_ctx *ctx) { return ctx ? ctx->err : g_create_err; }
 
-extern "C" int irs_create(irs_ctx **out, const irs_dims *dims, const irs_shard *shard) {
+extern "C" int irs_create(irs_ctx **out, const irs_dims *dims, const irs_shard *shard) { return irs_create_ex(out, dims, shard, 0u); }
+
+extern "C" int irs_create_ex(irs_ctx **out, const irs_dims *dims, const irs_shard *shard, uint32_t flags) {
     if (!out || !dims) {
         snprintf(g_create_err, sizeof(g_create_err), "irs_create: null argument");
         return IRS_E_INVALID;
@@ -31,7 +33,9 @@ extern "C" int irs_create(irs_ctx **out, const irs_dims *dims, const irs_shard *
     } while (0)
     if (D.n_item < 1) BAD("n_item must be >= 1");
     if (D.d < 2 || D.d > 256 || (D.d & 1)) BAD("emb_dim must be even and in [2, 256] (got %d)", D.d);
-    if (D.max_len < 2 || D.max_len > 256) BAD("max_len must be in [2, 256] (got %d)", D.max_len);
+    if (flags & ~IRS_CREATE_LONG_WINDOWS) BAD("irs_create_ex: unknown flag bits 0x%x", flags & ~IRS_CREATE_LONG_WINDOWS);
+    const int len_max = (flags & IRS_CREATE_LONG_WINDOWS) ? IRS_MAX_LEN_LONG : 256;
+    if (D.max_len < 2 || D.max_len > len_max) BAD("max_len must be in [2, %d] (got %d)", len_max, D.max_len);
     if (D.n_heads < 1 || D.d % D.n_heads) BAD("n_heads must divide emb_dim");
     if (D.d / D.n_heads > 64) BAD("head dim > 64 unsupported");
     if (D.n_layers < 1 || D.n_layers > IRS_MAX_LAYERS) BAD("n_layers out of range");

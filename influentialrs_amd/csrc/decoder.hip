@@ -9,7 +9,8 @@
 //
 // Kernel families: packed-decode plan (k_plan_*); embedding, optionally with q | k | v (k_embed*), and r_u (k_pif); per-GEMM float32
 // linears with fused LayerNorm (k_linear*, k_ln); whole-layer kernels (k_block, k_block_x6 with its sequence-resident form,
-// k_block_small*); attention per (sequence, head), masks never materialised (k_attn16, k_attn_mfma, k_attn_row*); packing, gathers.
+// k_block_small*); attention per (sequence, head), masks never materialised (k_attn16, k_attn_mfma, k_attn_row*; k_attn_long, k_attn_row_long behind
+// windows longer than 256 tokens); packing, gathers.
 #include "irs_internal.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -5415,6 +5416,262 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
 #undef SEQ_MFMA_LANDED
 }
 
+// ------------------------------------------------------------------ attention for long windows (256 < max_len <= IRS_MAX_LEN_LONG)
+// k_attn_mfma's mathematics, masks and interface (float32 MFMAs on the exact chain, 32-query x 32-key blocks, the S^T accumulator
+// as the B operand of O^T, the target column seeded per query), but nothing except the 32-word key bitmask is sized by L:
+//   * grid (head, sequence, ceil(Lmax / 128)): a workgroup serves 128 consecutive queries, one 32-query block per wave;
+//   * K_h / V_h stream through LDS in chunks of KC keys, double buffered: the loads of the next live chunk are requested into
+//     registers before the MFMAs of the current one and stored to the other buffer behind them -- one barrier per chunk;
+//   * KC = 64 keys (32 at head dims above 32): 2 x KC x (VW + HDP + 1) floats are 21 / 25 / 33 / 33 KB at HDP = 8 / 16 / 32 / 64,
+//     so four workgroups (16 waves) fit the 160 KB of a CU at every head dim, and the static allocation stays below 64 KB;
+//   * the online softmax (m, l, O^T) lives in registers across the chunks;
+//   * a chunk behind the workgroup's last query is never loaded, a key block behind a wave's own query block is not multiplied;
+//     a chunk whose keys are all masked (the pads in front of a pre-padded window; the seeded target alone) is neither loaded
+//     nor multiplied.  The running maximum stays -inf over such chunks and over fully masked blocks: `dead` below keeps
+//     exp(-inf - -inf) out, and a query without any visible key ends with l = 0 -> 0 * inf = NaN like torch.
+// Keys in [L, chunk end) are zero rows in LDS (p = 0 there).  The 32x32x2 float32 MFMA has 16 passes: its result may be read by
+// a vector instruction 20 wait states behind it, and both accumulators are consumed behind wave-uniform branches (see
+// ATTN_MFMA_LANDED), so both get the explicit wait.
+#define ATTN_MFMA32_LANDED(a_) asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" : "+v"(a_));
+template <int HDP, bool V4>
+__global__ void __launch_bounds__(256) k_attn_long(const float *__restrict__ qkv, const int64_t *__restrict__ seq,
+                                                   const float *__restrict__ r_u, float *__restrict__ out, int Lmax,
+                                                   int d, int hd, int mask_mode, const int32_t *__restrict__ off,
+                                                   const int32_t *__restrict__ cnt, const int32_t *__restrict__ tok_row) {
+    constexpr int HH = HDP / 2;
+    constexpr int VW = HDP < 32 ? 32 : HDP;
+    constexpr int CT = VW / 32;
+    constexpr int KLD = HDP + 1;
+    constexpr int KC = HDP > 32 ? 32 : 64;    // keys per chunk
+    constexpr int KBC = KC / 32;              // 32-key blocks per chunk
+    constexpr int C4 = HDP / 4;
+    constexpr int NS = V4 ? (KC * C4 + 255) / 256 : (KC * VW) / 256; // staged elements per thread and matrix
+    constexpr int MAXB = IRS_MAX_LEN_LONG / 32;
+    __shared__ __attribute__((aligned(16))) float Vs[2][KC * VW];
+    __shared__ float Ks[2][KC * KLD];
+    __shared__ unsigned int padbits[MAXB];
+    const int L = cnt ? cnt[blockIdx.y] : Lmax;
+    const int q0 = blockIdx.z * 128;
+    if (q0 >= L || L > IRS_MAX_LEN_LONG) return; // (workgroup-uniform, in front of every barrier)
+    const int NB = (L + 31) / 32;
+    const int h = blockIdx.x, b = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lq = lane & 31, kk = lane >> 5;
+    const int64_t base = off ? (int64_t)off[b] : (int64_t)b * Lmax;
+    const int ld = 3 * d;
+    const bool irn = (mask_mode == IRS_MASK_IRN);
+    const int kb_end = min(NB, 4 * (int)blockIdx.z + 4); // key blocks this workgroup's queries can see
+    const int c_end = (kb_end + KBC - 1) / KBC;          // ... and their chunks
+    const bool tgt_ok = irn && (seq[(int64_t)b * Lmax + Lmax - 1] != 0);
+    for (int kb = wave; kb < kb_end; kb += 4) { // masked-key bitmask of each key block (k_attn_mfma's rule)
+        int j = kb * 32 + lq;
+        const int64_t jr = base + (j < L ? j : L - 1);
+        bool masked = (j >= L) || (seq[tok_row ? (int64_t)tok_row[jr] : jr] == 0) || (tgt_ok && j == L - 1);
+        unsigned long long bal = __ballot(masked);
+        if (lane == 0) padbits[kb] = (unsigned int)bal;
+    }
+    if (V4 && VW > HDP) // (the float4 form never writes the padding columns of V again)
+        for (int idx = tid; idx < 2 * KC * (VW - HDP); idx += 256) (&Vs[0][0])[(idx / (VW - HDP)) * VW + HDP + idx % (VW - HDP)] = 0.f;
+    __syncthreads();
+    // first live chunk at or behind c (c_end: none); the same value in every thread
+    auto next_live = [&](int c) {
+        for (; c < c_end; ++c) {
+            bool live = false;
+#pragma unroll
+            for (int t = 0; t < KBC; ++t)
+                if (c * KBC + t < kb_end && padbits[c * KBC + t] != 0xFFFFFFFFu) live = true;
+            if (live) break;
+        }
+        return c;
+    };
+    float4 k4s[V4 ? NS : 1], v4s[V4 ? NS : 1];
+    float k1s[V4 ? 1 : NS], v1s[V4 ? 1 : NS];
+    auto stage_load = [&](int c) {
+        if constexpr (V4) {
+#pragma unroll
+            for (int it = 0; it < NS; ++it) {
+                const int idx = tid + 256 * it, jl = idx / C4, cc = (idx % C4) * 4, j = c * KC + jl;
+                k4s[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+                v4s[it] = k4s[it];
+                if (idx < KC * C4 && j < L && cc < hd) {
+                    const float *row = qkv + (base + j) * ld + h * hd + cc;
+                    k4s[it] = *reinterpret_cast<const float4 *>(row + d);
+                    v4s[it] = *reinterpret_cast<const float4 *>(row + 2 * d);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < NS; ++it) {
+                const int idx = tid + 256 * it, jl = idx / VW, cc = idx % VW, j = c * KC + jl;
+                k1s[it] = 0.f, v1s[it] = 0.f;
+                if (j < L && cc < hd) {
+                    const float *row = qkv + (base + j) * ld + h * hd + cc;
+                    k1s[it] = row[d];
+                    v1s[it] = row[2 * d];
+                }
+            }
+        }
+    };
+    auto stage_store = [&](int bf) {
+        if constexpr (V4) {
+#pragma unroll
+            for (int it = 0; it < NS; ++it) {
+                const int idx = tid + 256 * it, jl = idx / C4, cc = (idx % C4) * 4;
+                if (idx < KC * C4) {
+                    float *kd = &Ks[bf][jl * KLD + cc];
+                    kd[0] = k4s[it].x, kd[1] = k4s[it].y, kd[2] = k4s[it].z, kd[3] = k4s[it].w;
+                    *reinterpret_cast<float4 *>(&Vs[bf][jl * VW + cc]) = v4s[it];
+                }
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < NS; ++it) {
+                const int idx = tid + 256 * it, jl = idx / VW, cc = idx % VW;
+                if (cc < HDP) Ks[bf][jl * KLD + cc] = k1s[it];
+                Vs[bf][idx] = v1s[it];
+            }
+        }
+    };
+    const float add_allowed = irn ? r_u[b] : 0.f;
+    const float scale = 1.0f / sqrtf((float)hd);
+    const int qb = 4 * (int)blockIdx.z + wave; // this wave's query block (>= NB: it only helps to stage)
+    const int qi = qb * 32 + lq;
+    float qf[HH];
+    {
+        const float *qrow = qkv + (base + (qi < L ? qi : L - 1)) * ld + h * hd + kk * HH;
+        if (V4) {
+#pragma unroll
+            for (int s4 = 0; s4 < HH / 4; ++s4) {
+                float4 t = (kk * HH + 4 * s4 < hd) ? *reinterpret_cast<const float4 *>(qrow + 4 * s4) : make_float4(0.f, 0.f, 0.f, 0.f);
+                qf[4 * s4 + 0] = t.x * scale;
+                qf[4 * s4 + 1] = t.y * scale;
+                qf[4 * s4 + 2] = t.z * scale;
+                qf[4 * s4 + 3] = t.w * scale;
+            }
+        } else {
+#pragma unroll
+            for (int s2 = 0; s2 < HH; ++s2) qf[s2] = (kk * HH + s2 < hd) ? qrow[s2] * scale : 0.f;
+        }
+        if (qi >= L) {
+#pragma unroll
+            for (int s2 = 0; s2 < HH; ++s2) qf[s2] = 0.f;
+        }
+    }
+    float m = -INFINITY, l = 0.f;
+    f32x16 o[CT];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[ct][r] = 0.f;
+    if (tgt_ok) { // target column: s = q . K[L-1] + 1.0, p = 1 (its K / V row straight from the q | k | v rows)
+        const float *trow = qkv + (base + L - 1) * ld + h * hd;
+        float part = 0.f;
+#pragma unroll
+        for (int s2 = 0; s2 < HH; ++s2) part = __fmaf_rn(qf[s2], (kk * HH + s2 < hd) ? trow[d + kk * HH + s2] : 0.f, part);
+        const float st = lanes_sum<32>(part) + 1.0f;
+        m = st;
+        l = (kk == 0) ? 1.f : 0.f; // halves are summed at the end
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int col = ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+                o[ct][r] = col < hd ? trow[2 * d + col] : 0.f;
+            }
+    }
+    int c = next_live(0), bf = 0;
+    if (c < c_end) {
+        stage_load(c);
+        stage_store(0);
+    }
+    __syncthreads();
+    while (c < c_end) { // (workgroup-uniform)
+        const int cn = next_live(c + 1);
+        if (cn < c_end) stage_load(cn);
+        const float *Kc = Ks[bf], *Vc = Vs[bf];
+#pragma unroll 1
+        for (int t = 0; t < KBC; ++t) {
+            const int kb = c * KBC + t;
+            if (kb > qb || kb >= kb_end || qb >= NB) break; // the causal future of this wave's queries (wave-uniform)
+            const unsigned int pm = padbits[kb];
+            if (pm == 0xFFFFFFFFu) continue; // nothing visible in this key block
+            f32x16 sacc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
+            const float *kp = Kc + (t * 32 + lq) * KLD + kk * HH;
+#pragma unroll
+            for (int s2 = 0; s2 < HH; ++s2) sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(kp[s2], qf[s2], sacc, 0, 0, 0);
+            ATTN_MFMA32_LANDED(sacc)
+            float mx = -INFINITY;
+            if (pm == 0u && kb < qb) { // clean off-diagonal block: no masking
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    sacc[r] += add_allowed;
+                    mx = fmaxf(mx, sacc[r]);
+                }
+            } else {
+                const unsigned int pmk = pm >> (4 * kk);
+                const int qlim = (kb < qb) ? 64 : lq - 4 * kk; // key index (within block, minus 4kk) must be <= qlim
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int ki = (r & 3) + 8 * (r >> 2); // + 4kk = key index within the block
+                    bool ok = !((pmk >> ki) & 1u) && (ki <= qlim);
+                    float v = ok ? sacc[r] + add_allowed : -INFINITY;
+                    sacc[r] = v;
+                    mx = fmaxf(mx, v);
+                }
+            }
+            mx = lanes_max<32>(mx);
+            const float mn = fmaxf(m, mx);
+            const bool dead = (mn == -INFINITY);
+            const float alpha = dead ? 1.f : __expf(m - mn);
+            float ps = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float pv = dead ? 0.f : __expf(sacc[r] - mn);
+                sacc[r] = pv;
+                ps += pv;
+            }
+            l = l * alpha + ps;
+            m = mn;
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[ct][r] *= alpha;
+                const float *vp = Vc + (t * 32 + 4 * kk) * VW + ct * 32 + lq; // A: V^T[c = lq][key]
+#pragma unroll
+                for (int u = 0; u < 16; ++u)
+                    o[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[((u & 3) + 8 * (u >> 2)) * VW], sacc[u], o[ct], 0, 0, 0);
+                ATTN_MFMA32_LANDED(o[ct])
+            }
+        }
+        if (cn < c_end) stage_store(bf ^ 1);
+        __syncthreads();
+        bf ^= 1;
+        c = cn;
+    }
+    const float lt = lanes_sum<32>(l);
+    const float inv = 1.0f / lt; // 0 (no visible key) -> inf, 0 * inf = NaN like torch
+    if (qi < L) {
+        float *orow = out + (base + qi) * d + h * hd;
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int cc = ct * 32 + 8 * g + 4 * kk;
+                if (V4) {
+                    if (cc < hd)
+                        *reinterpret_cast<float4 *>(orow + cc) = make_float4(o[ct][4 * g] * inv, o[ct][4 * g + 1] * inv,
+                                                                              o[ct][4 * g + 2] * inv, o[ct][4 * g + 3] * inv);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (cc + e < hd) orow[cc + e] = o[ct][4 * g + e] * inv;
+                }
+            }
+    }
+}
+
 // ------------------------------------------------------------------ single-query attention (last layer, rows-only decode)
 // Only row pos[b] of the last layer is consumed by the scoring step (the reference computes all L
 // rows and uses output[index][history_end_pos], influentialRS.py:374,421).  One wave per (sequence,
@@ -5497,6 +5754,101 @@ __global__ void __launch_bounds__(64) k_attn_row(const float *__restrict__ qkv, 
             o = lanes_sum<32>(o);
             if (half == 0 && col < hd) out_rows[(int64_t)b * d + h * hd + col] = o / sum; // sum == 0 -> NaN like torch
         }
+    }
+}
+
+// The long form (256 < max_len <= IRS_MAX_LEN_LONG): the same wave, mask rule and inputs over key chunks of 256 with a running
+// maximum and sum.  A chunk behind the query that does not hold the target column, and a chunk without a visible key, is
+// skipped (the maximum stays where it was: no exp(-inf - -inf)); the two key-parity partial sums of a column are rescaled with
+// the same factor, so they are still combined once, at the end.
+__global__ void __launch_bounds__(64) k_attn_row_long(const float *__restrict__ qkv, const int64_t *__restrict__ seq,
+                                                      const float *__restrict__ r_u, const int32_t *__restrict__ pos,
+                                                      float *__restrict__ out_rows, int Lmax, int d, int hd, int mask_mode,
+                                                      const int32_t *__restrict__ off, const int32_t *__restrict__ cnt,
+                                                      const int32_t *__restrict__ tok_row, const int32_t *__restrict__ qrow,
+                                                      const float *__restrict__ qrows) {
+    __shared__ float p_s[256];
+    __shared__ float q_s[64];
+    const int h = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+    const int L = cnt ? cnt[b] : Lmax;
+    const int64_t base = off ? (int64_t)off[b] : (int64_t)b * Lmax;
+    const int ld = 3 * d;
+    int i = qrow ? qrow[b] - (int)base : pos[b]; // query row within the sequence
+    if (i < 0) i = 0;
+    if (i >= L) i = L - 1;
+    const bool has_tgt = (seq[(int64_t)b * Lmax + Lmax - 1] != 0);
+    const bool irn = (mask_mode == IRS_MASK_IRN);
+    const float add_allowed = irn ? r_u[b] : 0.f;
+    const float scale = 1.0f / sqrtf((float)hd);
+    if (lane < hd) q_s[lane] = (qrows ? qrows[(int64_t)b * d + h * hd + lane] : qkv[(base + i) * ld + h * hd + lane]) * scale;
+    __syncthreads();
+    const bool vec = (hd & 3) == 0 && (d & 3) == 0 && ((((uintptr_t)qkv) & 15) == 0);
+    const int c = lane & 31, half = lane >> 5;
+    float m = -INFINITY, sum = 0.f, o[2] = {0.f, 0.f};
+    for (int j0 = 0; j0 < L; j0 += 256) {
+        if (j0 > i && !(irn && has_tgt && L - 1 >= j0)) break; // only causal-future keys from here on
+        float sc[4];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int j = j0 + lane + 64 * t;
+            float s = -INFINITY;
+            if (j < L) {
+                const bool is_tgt = irn && has_tgt && (j == L - 1);
+                const int64_t jr = base + j;
+                const bool ok = (seq[tok_row ? (int64_t)tok_row[jr] : jr] != 0) && (is_tgt || j <= i);
+                if (ok) {
+                    const float *kr = qkv + (base + j) * ld + d + h * hd;
+                    float acc = 0.f;
+                    if (vec) {
+                        for (int cc = 0; cc < hd; cc += 4) {
+                            const float4 k4 = *reinterpret_cast<const float4 *>(kr + cc);
+                            acc = __fmaf_rn(q_s[cc], k4.x, acc);
+                            acc = __fmaf_rn(q_s[cc + 1], k4.y, acc);
+                            acc = __fmaf_rn(q_s[cc + 2], k4.z, acc);
+                            acc = __fmaf_rn(q_s[cc + 3], k4.w, acc);
+                        }
+                    } else {
+                        for (int cc = 0; cc < hd; ++cc) acc = __fmaf_rn(q_s[cc], kr[cc], acc);
+                    }
+                    s = acc + (is_tgt ? 1.0f : add_allowed);
+                }
+            }
+            sc[t] = s;
+            mx = fmaxf(mx, s);
+        }
+        mx = lanes_max<63>(mx);
+        if (mx == -INFINITY) continue; // no visible key in this chunk (the same in every lane)
+        const float mn = fmaxf(m, mx);
+        const float alpha = (m == -INFINITY) ? 0.f : __expf(m - mn); // (nothing accumulated yet: sum = o = 0)
+        __syncthreads(); // the previous chunk's P.V has read p_s
+        float ps = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float pv = (sc[t] == -INFINITY) ? 0.f : __expf(sc[t] - mn);
+            p_s[lane + 64 * t] = pv;
+            ps += pv;
+        }
+        sum = sum * alpha + wave_sum(ps);
+        m = mn;
+        __syncthreads();
+        const int jn = L - j0 < 256 ? L - j0 : 256;
+#pragma unroll
+        for (int cp = 0; cp < 2; ++cp) {
+            const int col = cp * 32 + c;
+            float acc = o[cp] * alpha;
+            if (col < hd) {
+                const float *vcol = qkv + (base + j0) * ld + 2 * d + h * hd + col;
+                for (int j = half; j < jn; j += 2) acc = __fmaf_rn(p_s[j], vcol[(int64_t)j * ld], acc);
+            }
+            o[cp] = acc;
+        }
+    }
+#pragma unroll
+    for (int cp = 0; cp < 2; ++cp) {
+        const int col = cp * 32 + c;
+        const float ov = lanes_sum<32>(o[cp]);
+        if (half == 0 && col < hd) out_rows[(int64_t)b * d + h * hd + col] = ov / sum; // sum == 0 -> NaN like torch
     }
 }
 
@@ -6007,6 +6359,25 @@ static int launch_attn(irs_ctx *ctx, const float *qkv, const int64_t *seq, const
         IRS_CHECK_HIP(ctx, hipGetLastError());
         return IRS_OK;
     }
+    if (L > 256) { // long windows: K / V stream through LDS in chunks (k_attn_long), 128 queries per workgroup
+        if (kv_planes) IRS_FAIL(ctx, IRS_E_STATE, "plane-format K / V behind a long window");
+        grid.z = (L + 127) / 128;
+#define AL_(HDP_)                                                                                                  \
+    do {                                                                                                           \
+        if (v4) hipLaunchKernelGGL((k_attn_long<HDP_, true>), grid, dim3(256), 0, s, qkv, seq, r_u, out, L, d, hd, mm, off, cnt, tok_row); \
+        else hipLaunchKernelGGL((k_attn_long<HDP_, false>), grid, dim3(256), 0, s, qkv, seq, r_u, out, L, d, hd, mm, off, cnt, tok_row);   \
+    } while (0)
+        switch (HDP) {
+        case 8: AL_(8); break;
+        case 16: AL_(16); break;
+        case 32: AL_(32); break;
+        default: AL_(64); break;
+        }
+#undef AL_
+        irs_prof_end(ctx, IRS_PROF_ATTN, s, 2.0 * B * (double)H * L * L * hd, 4.0 * 4.0 * B * (double)L * d);
+        IRS_CHECK_HIP(ctx, hipGetLastError());
+        return IRS_OK;
+    }
 #define A_(HDP_)                                                                                                   \
     do {                                                                                                           \
         if (v4) hipLaunchKernelGGL((k_attn_mfma<HDP_, true>), grid, dim3(256), lds, s, qkv, seq, r_u, out, L, d, hd, mm, off, cnt, tok_row); \
@@ -6463,7 +6834,9 @@ static void launch_embed(const DecodeCall &c, const int32_t *pos, const int64_t 
     }
     case DecEmbed::FRAG_QKV: // embed + layer 0's q | k | v in one kernel
         irs_prof_begin(ctx, IRS_PROF_LINEAR, s);
-        if (r.x6) { // the same kernel on split-bf16 MFMAs: k_block_x6's q | k | v steps behind an embed prologue
+        // (behind a long window the layers are the float32 FRAG_BLOCK family -- attn16_ok is false above 256 tokens, and at
+        //  max_len <= 256 r.x6 with this embed implies FRAG_FUSED -- so layer 0's q | k | v stay float32 as well)
+        if (r.x6 && r.layer == DecFam::FRAG_FUSED) { // the same kernel on split-bf16 MFMAs: k_block_x6's q | k | v steps behind an embed prologue
             BlockX6Args xa{};
             xa.Wx = x6_stream(ctx, r.npl, nl - 1);
             xa.bin = ctx->layer[0].sa_in_b, xa.Xf = xf, xa.QKV = ctx->act_qkv, xa.M = rows, xa.m_dev = c.m_dev;
@@ -6694,6 +7067,9 @@ static int last_layer(const DecodeCall &c, int l, const int32_t *pos, float *xro
     } else if (d / H == 32 && L <= 256 && d % 4 == 0 && (((uintptr_t)ctx->act_qkv | (uintptr_t)q_r) & 15) == 0)
         hipLaunchKernelGGL(k_attn_row32, dim3(H, B), dim3(256), 0, s, ctx->act_qkv, c.seq, ctx->act_ru, ao_r, L, d,
                            ctx->dims.mask_mode, c.off, c.cnt, qrow, q_r, ctx->seq_padq);
+    else if (L > 256) // long windows: key chunks of 256, running maximum and sum
+        hipLaunchKernelGGL(k_attn_row_long, dim3(H, B), dim3(64), 0, s, ctx->act_qkv, c.seq, ctx->act_ru, pos, ao_r, L, d, d / H,
+                           ctx->dims.mask_mode, c.off, c.cnt, c.tok, qrow, q_r);
     else
         hipLaunchKernelGGL(k_attn_row, dim3(H, B), dim3(64), 0, s, ctx->act_qkv, c.seq, ctx->act_ru, pos, ao_r, L, d, d / H,
                            ctx->dims.mask_mode, c.off, c.cnt, c.tok, qrow, q_r);

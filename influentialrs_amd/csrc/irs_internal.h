@@ -497,8 +497,35 @@ __device__ __forceinline__ irs_excl_view irs_excl_open(const irs_excl &ex, int r
     return v;
 }
 
+// ---- the register image of a window: the ONE membership test of the path step, the beam steps and the survivor flag pass.
+// A wave holds window slot lane + 64 i in register i of every lane (-1 beyond the window's last live slot), so "is this item in the
+// window" is SLOTS compares per lane and one __any.  SLOTS = 4 serves contexts with max_len <= 256, SLOTS = 16 the long windows
+// of irs_create_ex (max_len <= IRS_MAX_LEN_LONG); the launchers choose by ctx->dims.max_len (irs_window_slots).
+#define IRS_WIN_SLOTS_SHORT 4
+#define IRS_WIN_SLOTS_LONG (IRS_MAX_LEN_LONG / 64)
+static inline int irs_window_slots(const irs_ctx *ctx) { return ctx->dims.max_len > 256 ? IRS_WIN_SLOTS_LONG : IRS_WIN_SLOTS_SHORT; }
+template <int SLOTS>
+struct irs_window {
+    int64_t v[SLOTS];
+    // he: the window's last live slot (the window is w[0 .. he])
+    __device__ __forceinline__ void load(const int64_t *w, int he, int L, int lane) {
+#pragma unroll
+        for (int i = 0; i < SLOTS; ++i) {
+            int p = lane + 64 * i;
+            v[i] = (p < he + 1 && p < L) ? w[p] : (int64_t)-1;
+        }
+    }
+    // this lane's part of the test, OR-ed onto the caller's own terms (`hit`); the callers reduce with __any
+    __device__ __forceinline__ bool holds(int64_t item, bool hit = false) const {
+#pragma unroll
+        for (int i = 0; i < SLOTS; ++i) hit |= (v[i] == item);
+        return hit;
+    }
+};
+
 // EXCL: the form with a bound exclusion set (p_.ex.on); without it the body is the one the library always had.
-template <bool EXCL = false>
+// SLOTS: the window image's registers per lane (irs_window).
+template <bool EXCL = false, int SLOTS = IRS_WIN_SLOTS_SHORT>
 __device__ __forceinline__ void irs_path_step_row(const irs_path_args &p_, int row, int lane, const float *__restrict__ val,
                                                   const int64_t *__restrict__ ids0, int k) {
     const int L = p_.L, path_ld = p_.path_ld, sample = p_.sample;
@@ -513,14 +540,9 @@ __device__ __forceinline__ void irs_path_step_row(const irs_path_args &p_, int r
     if (step_next && row == 0 && lane == 0) step_next[0] = step + 1;
     int64_t *w = seq + (size_t)row * L;
     const int he = hep[row];
-    const int wl = he + 1; // window = seq[row, 0 .. he]
-    // window into registers (L <= 256 -> 4 per lane)
-    int64_t wv[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        int p = lane + 64 * i;
-        wv[i] = (p < wl && p < L) ? w[p] : (int64_t)-1;
-    }
+    // window = seq[row, 0 .. he], into registers (L <= 64 SLOTS)
+    irs_window<SLOTS> win;
+    win.load(w, he, L, lane);
     int64_t chosen = 0;
     int found = 0;
     float surv_val[IRS_MAX_SAMPLE_K];
@@ -541,9 +563,7 @@ __device__ __forceinline__ void irs_path_step_row(const irs_path_args &p_, int r
                     break;
                 }
                 const int64_t item = id0 + 1;
-                bool hit = (ev.pth == item);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) hit |= (wv[i] == item);
+                const bool hit = win.holds(item, ev.pth == item);
                 if (!__any(hit) && !((listed >> c) & 1ull)) {
                     surv_val[found] = val[(size_t)row * k + c0 + c];
                     surv_id[found] = item;
@@ -556,10 +576,7 @@ __device__ __forceinline__ void irs_path_step_row(const irs_path_args &p_, int r
             int64_t id0 = ids0[(size_t)row * k + c];
             if (id0 < 0) break;
             int64_t item = id0 + 1;
-            bool hit = false;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) hit |= (wv[i] == item);
-            if (!__any(hit)) {
+            if (!__any(win.holds(item))) {
                 surv_val[found] = val[(size_t)row * k + c];
                 surv_id[found] = item;
                 ++found;
@@ -602,9 +619,9 @@ __device__ __forceinline__ void irs_path_step_row(const irs_path_args &p_, int r
             hep[row] = he + 1;
         }
     } else { // shift left by one, keep the target last (influentialRS.py:442-450)
-        int64_t nv[4];
+        int64_t nv[SLOTS];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < SLOTS; ++i) {
             int p = lane + 64 * i;
             nv[i] = (p + 1 <= L - 2) ? w[p + 1] : 0;
         }
@@ -613,7 +630,7 @@ __device__ __forceinline__ void irs_path_step_row(const irs_path_args &p_, int r
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_s_waitcnt(0);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < SLOTS; ++i) {
             int p = lane + 64 * i;
             if (p < L - 2) w[p] = nv[i];
         }

@@ -9,13 +9,14 @@
 
 // One wave per row (the row body lives in irs_internal.h: the one-launch small-shard top-k runs it in its tail).
 // EXCL: with a bound exclusion set (irs_bind_exclusions); launched only while one is bound.
-template <bool EXCL>
+// SLOTS: the window image (irs_window): 4 registers per lane at max_len <= 256, 16 for long windows.
+template <bool EXCL, int SLOTS>
 __global__ void __launch_bounds__(256) k_path_step(const irs_path_args pa, int B, const float *__restrict__ val,
                                                    const int64_t *__restrict__ ids0, int k) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= B) return;
-    irs_path_step_row<EXCL>(pa, row, lane, val, ids0, k);
+    irs_path_step_row<EXCL, SLOTS>(pa, row, lane, val, ids0, k);
 }
 
 __global__ void k_inc(int32_t *ctr) {
@@ -113,7 +114,7 @@ __global__ void __launch_bounds__(256) k_merge(const float *__restrict__ val_in,
 // beam's own path so far, in.paths[row, 0 .. step): the parent's path of whatever it becomes.  All beams of a user read one list.
 // A finished beam and a dead beam open nothing.  Without EXCL the kernel is, again, the one it was.
 #define BEAM_MAXW 32
-template <bool UNTIL, bool EXCL>
+template <bool UNTIL, bool EXCL, int SLOTS>
 __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, const irs_beam_state out, const irs_beam_cand cand,
                                                     int W, int L, int step_arg, const int32_t *__restrict__ step_ptr, int P,
                                                     int32_t *__restrict__ status, const irs_beam_until until) {
@@ -160,13 +161,8 @@ __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, con
         }
         if (cj > -INFINITY) {
             const int64_t *w = in.seq + (size_t)row * L;
-            const int wl = in.hep[row] + 1;
-            int64_t wv[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                int p = lane + 64 * i;
-                wv[i] = (p < wl && p < L) ? w[p] : (int64_t)-1;
-            }
+            irs_window<SLOTS> win;
+            win.load(w, in.hep[row], L, lane);
             double norm = 0.0;
             if (cand.lse_max) norm = (double)cand.lse_max[row] + log((double)cand.lse_sum[row]);
             irs_excl_view ev = {};
@@ -187,8 +183,7 @@ __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, con
                     const int64_t item = id0 + 1;
                     bool hit = false;
                     if constexpr (EXCL) hit = (ev.pth == item);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) hit |= (wv[q] == item);
+                    hit = win.holds(item, hit);
                     if constexpr (EXCL) hit |= (bool)((listed >> c) & 1ull);
                     if (!__any(hit)) {
                         const float v = __shfl(cv, c, 64);
@@ -303,10 +298,13 @@ int irs_launch_beam_init(irs_ctx *ctx, const int64_t *seq0, const int64_t *user0
 int irs_launch_beam_step(irs_ctx *ctx, const irs_beam_state &in, const irs_beam_state &out, const irs_beam_cand &cand, int B, int W,
                          int step, const int32_t *step_ptr, int P, int32_t *status, const irs_beam_until *until, hipStream_t s) {
     if (W < 1 || W > BEAM_MAXW) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam width %d outside [1, %d]", W, BEAM_MAXW);
-    if (ctx->dims.max_len > 256) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam step: window length %d > 256", ctx->dims.max_len);
     const int waves = W < 4 ? 4 : (W > 16 ? 16 : W);
-    const auto kern = cand.ex.on ? (until ? k_beam_step<true, true> : k_beam_step<false, true>)
-                                 : (until ? k_beam_step<true, false> : k_beam_step<false, false>);
+    constexpr int S4 = IRS_WIN_SLOTS_SHORT, S16 = IRS_WIN_SLOTS_LONG;
+    const auto kern = irs_window_slots(ctx) == S4
+                          ? (cand.ex.on ? (until ? k_beam_step<true, true, S4> : k_beam_step<false, true, S4>)
+                                        : (until ? k_beam_step<true, false, S4> : k_beam_step<false, false, S4>))
+                          : (cand.ex.on ? (until ? k_beam_step<true, true, S16> : k_beam_step<false, true, S16>)
+                                        : (until ? k_beam_step<true, false, S16> : k_beam_step<false, false, S16>));
     hipLaunchKernelGGL(kern, dim3(B), dim3(64 * waves), 0, s, in, out, cand, W, ctx->dims.max_len, step, step_ptr, P, status,
                        until ? *until : irs_beam_until{});
     IRS_CHECK_HIP(ctx, hipGetLastError());
@@ -384,7 +382,10 @@ int irs_launch_pack_topk(irs_ctx *ctx, const float *val, const int64_t *ids0, in
 }
 
 int irs_launch_path_step(irs_ctx *ctx, const irs_path_args &pa, int B, const float *val, const int64_t *ids0, int k, hipStream_t s) {
-    hipLaunchKernelGGL(pa.ex.on ? k_path_step<true> : k_path_step<false>, dim3((B + 3) / 4), dim3(256), 0, s, pa, B, val, ids0, k);
+    constexpr int S4 = IRS_WIN_SLOTS_SHORT, S16 = IRS_WIN_SLOTS_LONG;
+    const auto kern = irs_window_slots(ctx) == S4 ? (pa.ex.on ? k_path_step<true, S4> : k_path_step<false, S4>)
+                                                  : (pa.ex.on ? k_path_step<true, S16> : k_path_step<false, S16>);
+    hipLaunchKernelGGL(kern, dim3((B + 3) / 4), dim3(256), 0, s, pa, B, val, ids0, k);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }

@@ -2120,7 +2120,8 @@ __device__ unsigned long long g_direct_t[16];
 // MODE 2 is the selection alone, one workgroup per row -- the last-arriver scheme would hand all 8 rows of a group to
 // the same workgroup, one after the other.
 #define DIRECT_ROWS 8
-template <int MODE>
+// SLOTS: the window image of the fused path step (irs_window): 4 registers per lane, 16 behind a long-window context.
+template <int MODE, int SLOTS = IRS_WIN_SLOTS_SHORT>
 __global__ void __launch_bounds__(256) k_topk_direct(const float *__restrict__ x, int d, const float *__restrict__ W,
                                                      const float *__restrict__ bias, int n_local, int64_t item_lo, int k,
                                                      unsigned long long *__restrict__ gkeys, unsigned int *__restrict__ arrive,
@@ -2333,7 +2334,7 @@ __global__ void __launch_bounds__(256) k_topk_direct(const float *__restrict__ x
     // the workgroup that has just ranked them -- one launch fewer per step
     if (pa.enabled) {
         __syncthreads(); // val / ids of this row are written
-        if (wave == 0) irs_path_step_row(pa, row, lane, val, ids, k);
+        if (wave == 0) irs_path_step_row<false, SLOTS>(pa, row, lane, val, ids, k);
     }
 #ifdef IRS_DIRECT_TIMING
     DSTAMP(9);
@@ -2815,14 +2816,16 @@ static int topk_direct(irs_ctx *ctx, const TopkPlan &p, const float *xrows, int 
     const unsigned int tiles = (unsigned)((ctx->n_local + DIRECT_TILE - 1) / DIRECT_TILE);
     unsigned int *arrive = reinterpret_cast<unsigned int *>(ctx->step_ctr) + 8;
     const irs_path_args pa = path ? *path : irs_path_args{};
+    constexpr int S16 = IRS_WIN_SLOTS_LONG;
+    const bool long_win = path && irs_window_slots(ctx) == S16; // (without a fused step the window image is not instantiated)
     if (p.form == TOPK_DIRECT1)
-        hipLaunchKernelGGL(k_topk_direct<0>, dim3(tiles, M), dim3(256), 0, s, xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b,
+        hipLaunchKernelGGL((long_win ? k_topk_direct<0, S16> : k_topk_direct<0>), dim3(tiles, M), dim3(256), 0, s, xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b,
                            (int)ctx->n_local, ctx->shard.item_lo, k, ctx->cand, arrive, val, ids0, status, pa, M);
     else {
         hipLaunchKernelGGL(k_topk_direct<1>, dim3(tiles, (M + DIRECT_ROWS - 1) / DIRECT_ROWS), dim3(256), 0, s, xrows, ctx->dims.d,
                            ctx->proj_w, ctx->proj_b, (int)ctx->n_local, ctx->shard.item_lo, k, ctx->cand, arrive, val, ids0,
                            status, irs_path_args{}, M);
-        hipLaunchKernelGGL(k_topk_direct<2>, dim3(1, M), dim3(256), 0, s, xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b,
+        hipLaunchKernelGGL((long_win ? k_topk_direct<2, S16> : k_topk_direct<2>), dim3(1, M), dim3(256), 0, s, xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b,
                            (int)ctx->n_local, ctx->shard.item_lo, k, ctx->cand, arrive, val, ids0, status, pa, M);
     }
     irs_prof_end(ctx, IRS_PROF_REFINE, s, 2.0 * ctx->dims.d * (double)M * (double)ctx->n_local, 0.0);

@@ -36,7 +36,7 @@ size_t irs_surv_scratch(const irs_ctx *ctx, int rows, int want) {
 // ---- flag pass: one wave per row.  The list is walked in order, 64 ids at a time (one per lane, broadcast by shuffle): it ends
 // at the first negative id (a list that ended early is the whole catalog: not starved), and the walk stops as soon as `want`
 // survivors are seen.  Only a row that shows all k valid entries and fewer than `want` survivors is recorded.
-template <bool EXCL>
+template <bool EXCL, int SLOTS>
 __global__ void __launch_bounds__(256) k_surv_flag(const irs_excl ex, const int64_t *__restrict__ seq, int L, const int32_t *__restrict__ hep, int M,
                                                    int rps, int k, int want, const double *__restrict__ cum,
                                                    const int32_t *__restrict__ fin, const int32_t *__restrict__ done,
@@ -49,13 +49,8 @@ __global__ void __launch_bounds__(256) k_surv_flag(const irs_excl ex, const int6
     if (fin && fin[row] != 0) return;
     if (done && done[row / rps] != 0) return;
     const int64_t *w = seq + (size_t)row * L;
-    const int wl = hep[row] + 1; // window = seq[row, 0 .. hep]
-    int64_t wv[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int p = lane + 64 * i;
-        wv[i] = (p < wl && p < L) ? w[p] : (int64_t)-1;
-    }
+    irs_window<SLOTS> win; // window = seq[row, 0 .. hep]
+    win.load(w, hep[row], L, lane);
     int found = 0;
     bool ended = false;
     irs_excl_view ev = {};
@@ -75,8 +70,7 @@ __global__ void __launch_bounds__(256) k_surv_flag(const irs_excl ex, const int6
             const int64_t item = id0 + 1;
             bool hit = false;
             if constexpr (EXCL) hit = (ev.pth == item) || ((listed >> i) & 1ull);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) hit |= (wv[q] == item);
+            hit = win.holds(item, hit);
             if (!__any(hit) && ++found >= want) break;
         }
     }
@@ -151,7 +145,8 @@ __device__ __forceinline__ unsigned int surv_select(KeyFn &&keyfn, AdmitFn &&adm
 // window ids are sorted into LDS once per (workgroup, row); an item is searched there only after its key has beaten the
 // running threshold.  EXCL: the row's path entries are sorted in with the window (INT64_MAX fills both), and an item that is in
 // neither is searched in the user's bound row.
-template <bool EXCL>
+// WSLOTS: window slots of the sort buffer, 256 (max_len <= 256) or IRS_MAX_LEN_LONG.
+template <bool EXCL, int WSLOTS>
 __global__ void __launch_bounds__(256) k_surv_strips(const irs_excl ex, const float *__restrict__ x, int d, const float *__restrict__ W,
                                                      const float *__restrict__ bias, int64_t n_local, int64_t item_lo,
                                                      const int64_t *__restrict__ seq, int L, const int32_t *__restrict__ hep,
@@ -159,8 +154,8 @@ __global__ void __launch_bounds__(256) k_surv_strips(const irs_excl ex, const fl
                                                      const int32_t *__restrict__ list, unsigned long long *__restrict__ keys) {
     __shared__ unsigned long long buf[SURV_BUF];
     __shared__ float xs[256];
-    constexpr int WIN = EXCL ? 512 : 256; // EXCL: 256 window slots + IRS_MAX_PATH path slots, up to a power of two for the sort
-    static_assert(256 + IRS_MAX_PATH <= 512, "path entries share the sorted window");
+    constexpr int WIN = EXCL ? 2 * WSLOTS : WSLOTS; // EXCL: the window slots + IRS_MAX_PATH path slots, up to a power of two for the sort
+    static_assert(IRS_MAX_PATH <= 256 && WSLOTS >= 256 && (WSLOTS & (WSLOTS - 1)) == 0, "path entries share the sorted window");
     __shared__ long long win[WIN];
     const unsigned int n_rows = *count;
     if (n_rows == 0u) return;
@@ -174,12 +169,19 @@ __global__ void __launch_bounds__(256) k_surv_strips(const irs_excl ex, const fl
         wl = wl < 0 ? 0 : (wl > L ? L : wl);
         __syncthreads();
         for (int i = tid; i < d; i += 256) xs[i] = x[(size_t)row * d + i];
-        win[tid] = tid < wl ? (long long)seq[(size_t)row * L + tid] : 0x7FFFFFFFFFFFFFFFll; // (L <= 256 = the workgroup)
+        if constexpr (WSLOTS == 256) // (L <= 256 = the workgroup)
+            win[tid] = tid < wl ? (long long)seq[(size_t)row * L + tid] : 0x7FFFFFFFFFFFFFFFll;
+        else
+            for (int p = tid; p < WSLOTS; p += 256) win[p] = p < wl ? (long long)seq[(size_t)row * L + p] : 0x7FFFFFFFFFFFFFFFll;
         const int64_t *xl = nullptr; // EXCL: the user's bound row
         int xn = 0;
         if constexpr (EXCL) { // (thread tid < IRS_MAX_PATH opens path entry tid)
             const irs_excl_view ev = irs_excl_open(ex, row, tid, ex.step_ptr ? ex.step_ptr[0] : ex.step_arg);
-            win[256 + tid] = (tid < IRS_MAX_PATH && ev.pth > 0) ? (long long)ev.pth : 0x7FFFFFFFFFFFFFFFll;
+            if constexpr (WSLOTS == 256)
+                win[256 + tid] = (tid < IRS_MAX_PATH && ev.pth > 0) ? (long long)ev.pth : 0x7FFFFFFFFFFFFFFFll;
+            else
+                for (int p = tid; p < WSLOTS; p += 256)
+                    win[WSLOTS + p] = (p < IRS_MAX_PATH && ev.pth > 0) ? (long long)ev.pth : 0x7FFFFFFFFFFFFFFFll;
             xl = ev.list, xn = ev.n;
         }
         surv_bitonic<long long, false>(win, WIN);
@@ -241,11 +243,17 @@ int irs_launch_survivors(irs_ctx *ctx, const irs_surv_args &a, void *scratch, hi
     unsigned long long *keys = (unsigned long long *)((char *)list + surv_align16((size_t)a.rows_cap * sizeof(int32_t)));
     const int L = ctx->dims.max_len;
     IRS_CHECK_HIP(ctx, hipMemsetAsync(count, 0, sizeof(unsigned int), s));
-    hipLaunchKernelGGL(a.ex.on ? k_surv_flag<true> : k_surv_flag<false>, dim3((a.M + 3) / 4), dim3(256), 0, s, a.ex, a.seq, L, a.hep, a.M, a.rps, a.k, a.want, a.cum, a.fin, a.done,
+    constexpr int S4 = IRS_WIN_SLOTS_SHORT, S16 = IRS_WIN_SLOTS_LONG;
+    const bool long_win = irs_window_slots(ctx) != S4;
+    const auto k_flag = long_win ? (a.ex.on ? k_surv_flag<true, S16> : k_surv_flag<false, S16>)
+                                 : (a.ex.on ? k_surv_flag<true, S4> : k_surv_flag<false, S4>);
+    const auto k_strips = long_win ? (a.ex.on ? k_surv_strips<true, IRS_MAX_LEN_LONG> : k_surv_strips<false, IRS_MAX_LEN_LONG>)
+                                   : (a.ex.on ? k_surv_strips<true, 256> : k_surv_strips<false, 256>);
+    hipLaunchKernelGGL(k_flag, dim3((a.M + 3) / 4), dim3(256), 0, s, a.ex, a.seq, L, a.hep, a.M, a.rps, a.k, a.want, a.cum, a.fin, a.done,
                        a.ids0, count, list);
     int ny = 4096 / ns < 4 ? 4 : (4096 / ns > SURV_ROW_GROUPS ? SURV_ROW_GROUPS : 4096 / ns);
     if (ny > a.M) ny = a.M;
-    hipLaunchKernelGGL(a.ex.on ? k_surv_strips<true> : k_surv_strips<false>, dim3(ns, ny), dim3(256), 0, s, a.ex, a.xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b, ctx->n_local,
+    hipLaunchKernelGGL(k_strips, dim3(ns, ny), dim3(256), 0, s, a.ex, a.xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b, ctx->n_local,
                        ctx->shard.item_lo, a.seq, L, a.hep, a.want, ns, count, list, keys);
     hipLaunchKernelGGL(k_surv_merge, dim3(a.M < SURV_ROW_GROUPS ? a.M : SURV_ROW_GROUPS), dim3(256), 0, s, ctx->shard.item_lo, a.k, a.want, ns, a.rps, count, list,
                        keys, a.status_map, a.val, a.ids0, a.status);

@@ -61,7 +61,11 @@ class Engine:
         h = ctypes.c_void_p()
         self._weights: Dict[str, torch.Tensor] = {}
         with torch.cuda.device(self.device):
-            rc = self.lib.irs_create(ctypes.byref(h), ctypes.byref(dims), ctypes.byref(shard))
+            if max_len > 256:  # long windows are opened explicitly (up to IRS_MAX_LEN_LONG; beyond: the library's message)
+                rc = self.lib.irs_create_ex(ctypes.byref(h), ctypes.byref(dims), ctypes.byref(shard),
+                                            _lib.IRS_CREATE_LONG_WINDOWS)
+            else:
+                rc = self.lib.irs_create(ctypes.byref(h), ctypes.byref(dims), ctypes.byref(shard))
             if rc != 0:
                 raise IrsError(f"irs_create failed ({rc}): {self.lib.irs_last_error(None).decode()}")
             self.h = h
