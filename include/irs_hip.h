@@ -579,6 +579,53 @@ size_t irs_exclusion_scratch_bytes(const irs_ctx *ctx, int32_t users, int32_t n_
 int irs_bind_exclusions(irs_ctx *ctx, const int64_t *dev_excl_ids0, int32_t users, int32_t n_excl, int32_t no_repeat,
                         void *dev_scratch, size_t bytes, void *stream);
 
+/* ---- path trace: how the target stands at every step of a greedy / sampled search (opt-in; replaces the saved-path round trip
+ *      through Evaluator.get_grad_in_batch -- t_probs, p_probs, IoI, mean path log-probability, evaluator.py:195-205 -- and
+ *      get_rr_increase_in_batch's rank before and after, evaluator.py:266-286, with their Python loop of decode + LogSoftmax +
+ *      gather per step) ----------------------------------------------------------------------------------------------------
+ * For row b at step i, measured BEFORE the step chooses: the window w = seq[b][0 .. hep[b]], the target t = seq[b][L-1], x the
+ * decoder row the step scores, e_j the exact float32 chain of x against item j (0-based) of the catalog (top of this section).
+ *   lse                = log sum_j exp(e_j) over the WHOLE catalog, window items included: the softmax of influentialRS.py:418.
+ *   lp_target[b][i]    = e_{t-1} - lse.
+ *   rank_target[b][i]  = 1 + #{ j : j+1 is not a non-pad entry of w, and (e_j, j) ranks before (e_{t-1}, t-1) } in the library's
+ *                        total order: score descending, id ascending, -0 folded onto +0.  Duplicates in the window count once; the
+ *                        target in its own window still has a rank.  A bound exclusion list and no_repeat do NOT enter the rank:
+ *                        it is the rank among what the window leaves, whatever else the step may drop.
+ *   lp_item[b][i]      = e_{c-1} - lse for the item c the step chose; 0 where it chose nothing (IRS_ROW_NO_CANDIDATE).
+ *   t == 0 (or t outside the catalog): lp_target = 0 and rank_target = 0.
+ * The values are formed as (double)e - ((double)max + log((double)sumexp)) from the float32 pair (max, sumexp = sum exp(e_j -
+ * max)) and rounded to float32 once; rank_target is int32.
+ * irs_score_target_trace is the sweep alone: ONE pass over the float32 catalog in chain order gives the (max, sumexp) partials
+ * (the partial slots of irs_score_lse, reduced in slot order) and the number of items ranked before (e_{t-1}, t-1); e_{t-1} is
+ * taken first, with irs_score_gather's arithmetic, and the window correction reads dev_seq / dev_hep where they lie (no [M, L]
+ * copy of ids is made; any max_len).  No float atomics (integer ones count): two identical calls give identical bits.
+ *  dev_xrows float [M, d], dev_seq int64 [M, L], dev_hep int32 [M]
+ *  dev_max / dev_sumexp / dev_target_score float [M] out (target_score -inf without a target), dev_rank int32 [M] out
+ *  dev_scratch: caller-owned, >= irs_path_trace_scratch_bytes(M) bytes (16 rows + 16 rows, each of six arrays rounded up to 256),
+ *            16-byte aligned.  Null pointers, M outside [1, max_rows], a scratch too small or misaligned -> IRS_E_INVALID; world != 1
+ *            -> IRS_E_UNSUPPORTED; all before any launch.
+ * irs_bind_path_trace makes the greedy / sampled loops record the three values: dev_lp_item / dev_lp_target float [users, ld],
+ * dev_rank_target int32 [users, ld], caller-owned; the scratch (>= irs_path_trace_scratch_bytes(users)) is caller-owned like
+ * irs_bind_survivor_scratch's and must stay valid until the unbind; irs_workspace_bytes does not change.  All three arrays NULL
+ * unbinds.  While bound:
+ *   irs_generate_paths (stream launches and the captured step alike) runs the sweep between its top-k and its step and a record
+ *     kernel after the step, and writes all max_path_len columns of rows [0, B); a caller cuts them after the arrival as it cuts
+ *     dev_paths.  irs_generate_paths_until zeroes rows [0, B) of the three arrays at entry and writes only the steps up to and
+ *     including the one that chose the target, at the caller's row (through its compaction map); a finished user that is still
+ *     stepped until the next compaction writes nothing.
+ *   the route where one workgroup ranks and steps a row is not taken (as under exclusions);
+ *   B > users or max_path_len > ld -> IRS_E_INVALID before any launch;
+ *   irs_beam_step[_until], irs_beam_search[_until] and the two _sharded loops return IRS_E_UNSUPPORTED (no trace is carried through
+ *     beam state, and a shard sees only its own items); a context with world != 1 refuses the binding itself.
+ * Binding and unbinding drop the captured steps; the bound pointers are part of a captured step's key.  With nothing bound every
+ * entry point launches exactly what it launched before. */
+size_t irs_path_trace_scratch_bytes(const irs_ctx *ctx, int32_t rows); /* 0 for invalid arguments */
+int irs_score_target_trace(irs_ctx *ctx, const float *dev_xrows, const int64_t *dev_seq, const int32_t *dev_hep, int32_t M,
+                           void *dev_scratch, size_t scratch_bytes, float *dev_max, float *dev_sumexp, float *dev_target_score,
+                           int32_t *dev_rank, void *stream);
+int irs_bind_path_trace(irs_ctx *ctx, float *dev_lp_item, float *dev_lp_target, int32_t *dev_rank_target, int32_t users, int32_t ld,
+                        void *dev_scratch, size_t bytes);
+
 /* ---- multi-GPU: the exchange steps and the sharded search loops below the ABI (section 8 row B2's
  *      `allgather_merge(ctx, comm, ...)`).  One process per GPU; rank r holds item rows [item_lo, item_hi) (irs_shard).
  * A communicator is either RCCL (librccl.so is dlopen()ed on first use: ncclCommInitRank over a 128-byte unique id the

@@ -102,6 +102,10 @@ SIGNATURES = {
     "irs_bind_survivor_scratch": (c_int32, [c_void_p, c_void_p, c_size_t]),
     "irs_exclusion_scratch_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),
     "irs_bind_exclusions": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    "irs_path_trace_scratch_bytes": (c_size_t, [c_void_p, c_int32]),
+    "irs_score_target_trace": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p]),
+    "irs_bind_path_trace": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t]),
     "irs_comm_unique_id": (c_int32, [c_void_p]),
     "irs_comm_init_rccl": (c_int32, [POINTER(c_void_p), c_void_p, c_int32, c_int32]),
     "irs_comm_init_callbacks": (c_int32, [POINTER(c_void_p), c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -689,8 +689,9 @@ extern "C" int irs_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int32_t B
 // one search step on one device: decode -> rows at hep -> top-k -> choose/update.  `pa` is the loop's (loop_path_args): the step
 // index comes from the device counter
 // surv_fin (may be null): rows the survivor pass skips -- the until loop's finished rows, stepped until the next compaction
+// row_map (may be null: the identity): compacted row -> the caller's row, for the bound path trace, which also skips surv_fin's rows
 static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int B, int k, int sweep, hipStream_t s, int carry = 0,
-                        const int32_t *surv_fin = nullptr) {
+                        const int32_t *surv_fin = nullptr, const int32_t *row_map = nullptr) {
     int rc;
     const bool merged = irs_small_plan(ctx->dims, B); // (the decode below is rows-only: its plan is the single-workgroup one)
     pa.step_next = merged ? ctx->step_ctr + 1 : nullptr;
@@ -700,8 +701,9 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
     if (rc) return rc;
     // small shard, few rows: the workgroup that ranks a row's candidates also takes the row's path step
     // (not while exact candidates are bound: the survivor pass goes between the ranking and the step; nor while exclusions are
-    //  bound: only the separate step kernel has the form that tests them)
-    if (merged && !ctx->surv_scratch && !ctx->excl_on && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k))
+    //  bound: only the separate step kernel has the form that tests them; nor while a path trace is bound: its sweep reads the
+    //  window before the step, its record kernel the lists after it)
+    if (merged && !ctx->surv_scratch && !ctx->excl_on && !ctx->tr_on && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k))
         return irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, &pa);
     if ((rc = irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, nullptr, nullptr, carry)))
         return rc;
@@ -710,7 +712,18 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
                                ctx->top_val, ctx->top_ids, pa.status, nullptr, pa.ex};
         if ((rc = irs_launch_survivors(ctx, sa, ctx->surv_scratch, s))) return rc;
     }
+    irs_trace_rows tr = {};
+    if (ctx->tr_on) { // how the target stands before the step chooses: into the scratch, by launch row
+        irs_trace_layout(ctx->tr_scratch, ctx->tr_users, &tr);
+        if ((rc = irs_launch_target_trace(ctx, ctx->xrows, pa.seq, pa.hep, B, tr, tr.mx, tr.sm, tr.ts, tr.rank, s))) return rc;
+    }
     if ((rc = irs_launch_path_step(ctx, pa, B, ctx->top_val, ctx->top_ids, k, s))) return rc;
+    if (ctx->tr_on) { // (the step index is still this step's: the merged loop publishes the next one in its second word)
+        const irs_trace_rec rec{tr.mx, tr.sm, tr.ts, tr.rank, ctx->tr_item, ctx->tr_target, ctx->tr_rank, ctx->tr_ld};
+        if ((rc = irs_launch_trace_record(ctx, rec, pa.seq, pa.hep, pa.paths, pa.path_ld, ctx->step_ctr, row_map, surv_fin, ctx->top_val,
+                                          ctx->top_ids, k, B, s)))
+            return rc;
+    }
     return merged ? IRS_OK : irs_launch_inc(ctx, ctx->step_ctr, s);
 }
 
@@ -750,6 +763,53 @@ extern "C" int irs_bind_survivor_scratch(irs_ctx *ctx, void *scratch, size_t byt
     ctx->surv_scratch = scratch;
     ctx->surv_bytes = bytes;
     irs_drop_graphs(ctx); // (a captured step holds or lacks the pass)
+    return IRS_OK;
+}
+
+// ------------------------------------------------------------------ path trace (irs_bind_path_trace)
+extern "C" size_t irs_path_trace_scratch_bytes(const irs_ctx *ctx, int32_t rows) {
+    if (!ctx || rows < 1 || rows > ctx->max_rows) return 0;
+    return irs_trace_layout(nullptr, rows, nullptr);
+}
+
+extern "C" int irs_score_target_trace(irs_ctx *ctx, const float *xrows, const int64_t *seq, const int32_t *hep, int32_t M,
+                                      void *scratch, size_t scratch_bytes, float *omax, float *osum, float *tscore, int32_t *rank,
+                                      void *stream) {
+    int rc = ready(ctx);
+    if (rc) return rc;
+    if ((rc = check_rows(ctx, "irs_score_target_trace", xrows, M))) return rc;
+    if (!seq || !hep || !scratch || !omax || !osum || !tscore || !rank) IRS_FAIL(ctx, IRS_E_INVALID, "irs_score_target_trace: null pointer");
+    if (scratch_bytes < irs_trace_layout(nullptr, M, nullptr))
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_score_target_trace: scratch too small: %zu < %zu", scratch_bytes, irs_trace_layout(nullptr, M, nullptr));
+    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_score_target_trace: scratch must be 16-byte aligned");
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_score_target_trace needs the whole catalog on one device");
+    irs_trace_rows tr;
+    irs_trace_layout(scratch, M, &tr);
+    return irs_launch_target_trace(ctx, xrows, seq, hep, M, tr, omax, osum, tscore, rank, (hipStream_t)stream);
+}
+
+extern "C" int irs_bind_path_trace(irs_ctx *ctx, float *lp_item, float *lp_target, int32_t *rank_target, int32_t users, int32_t ld,
+                                   void *scratch, size_t bytes) {
+    if (!ctx) return IRS_E_INVALID;
+    if (!lp_item && !lp_target && !rank_target) { // unbind
+        if (ctx->tr_on) irs_drop_graphs(ctx);
+        ctx->tr_on = 0, ctx->tr_item = ctx->tr_target = nullptr, ctx->tr_rank = nullptr, ctx->tr_users = ctx->tr_ld = 0, ctx->tr_scratch = nullptr;
+        return IRS_OK;
+    }
+    if (!lp_item || !lp_target || !rank_target) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_path_trace: the three arrays go together");
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_path_trace needs the whole catalog on one device");
+    if (users < 1 || users > ctx->max_rows || ld < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_path_trace: users in [1, max_rows=%d], ld >= 1", ctx->max_rows);
+    const size_t need = irs_trace_layout(nullptr, users, nullptr);
+    if (!scratch || bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_path_trace: scratch too small: %zu < %zu", scratch ? bytes : (size_t)0, need);
+    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_path_trace: scratch must be 16-byte aligned");
+    ctx->tr_on = 1, ctx->tr_item = lp_item, ctx->tr_target = lp_target, ctx->tr_rank = rank_target, ctx->tr_users = users, ctx->tr_ld = ld;
+    ctx->tr_scratch = scratch;
+    irs_drop_graphs(ctx); // (a captured step holds the sweep and the record kernel with these pointers, or neither)
+    return IRS_OK;
+}
+// the beam steps and loops carry no trace: they refuse while one is bound
+static int refuse_trace(irs_ctx *ctx, const char *fn) {
+    if (ctx->tr_on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a path trace is bound (irs_bind_path_trace): greedy and sampled loops only", fn);
     return IRS_OK;
 }
 
@@ -807,12 +867,15 @@ static int check_search(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W
     if (rc) return rc;
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s needs the whole catalog on one device", fn);
     if (W) {
+        if ((rc = refuse_trace(ctx, fn))) return rc;
         if ((rc = irs_check_beam_args(ctx, fn, ptrs_ok, B, W, P))) return rc;
         if ((int64_t)B * W > ctx->max_seqs || (int64_t)B * W > ctx->max_rows)
             IRS_FAIL(ctx, IRS_E_INVALID, "%s: B*W=%d exceeds max_seqs=%d / max_rows=%d", fn, B * W, ctx->max_seqs, ctx->max_rows);
     } else {
         if (!ptrs_ok || B < 1 || P < 1) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad arguments", fn);
         if (B > ctx->max_seqs || B > ctx->max_rows) IRS_FAIL(ctx, IRS_E_INVALID, "%s: B too large", fn);
+        if (ctx->tr_on && (B > ctx->tr_users || P > ctx->tr_ld))
+            IRS_FAIL(ctx, IRS_E_INVALID, "%s: B=%d / path length %d, the path trace is bound for [%d, %d]", fn, B, P, ctx->tr_users, ctx->tr_ld);
     }
     if ((rc = irs_check_k(ctx, fn, k, 1, sweep, sample, sample_k))) return rc;
     if ((rc = check_excl(ctx, fn, B, P))) return rc;
@@ -875,6 +938,7 @@ extern "C" int irs_generate_paths(irs_ctx *ctx, int64_t *seq, const int64_t *use
         key.kind = IRS_STEP_GREEDY, key.B = B, key.P = max_path_len, key.k = k, key.sweep = sweep;
         key.sample = sample, key.sample_k = sample_k, key.seed = seed;
         key.seq = seq, key.user = user, key.hep = hep, key.paths = paths, key.status = status;
+        key.tr_item = ctx->tr_item, key.tr_target = ctx->tr_target, key.tr_rank = ctx->tr_rank, key.tr_scratch = ctx->tr_scratch;
         return irs_replay_steps(ctx, &ctx->g_greedy, key, [&](hipStream_t q) {
             return enqueue_step(ctx, pa, user, B, k, sweep, q);
         }, max_path_len, s);
@@ -902,6 +966,12 @@ extern "C" int irs_generate_paths_until(irs_ctx *ctx, int64_t *seq, const int64_
     if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
     IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->un_fin, 0, sizeof(int32_t) * B, s));
     IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->un_status, 0, sizeof(int32_t) * B, s));
+    if (ctx->tr_on) { // the trace of a user ends with its arrival: zero behind it (rows [0, B), all ld columns)
+        const size_t n = (size_t)B * ctx->tr_ld * 4;
+        IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->tr_item, 0, n, s));
+        IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->tr_target, 0, n, s));
+        IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->tr_rank, 0, n, s));
+    }
     // the first steps run in place on the caller's rows (identity map); the first compaction that removes a row moves the rest.
     // (the step writes stage[row][i]: it reads the index from the same device counter as irs_generate_paths' steps)
     irs_path_args pa = loop_path_args(ctx, seq, hep, ctx->un_stage, P, sample, sample_k, seed, ctx->un_status, paths);
@@ -912,7 +982,7 @@ extern "C" int irs_generate_paths_until(irs_ctx *ctx, int64_t *seq, const int64_
     // (an error below returns at once: host_stats unwritten, paths / status / seq / hep partly written -- see the header; the step
     //  counter pair is left wherever the last step put it, and every search loop resets it in irs_search_begin)
     for (int i = 0; i < P && live > 0; ++i) {
-        if ((rc = enqueue_step(ctx, pa, cuser, live, k, sweep, s, carry, ctx->un_fin))) return rc;
+        if ((rc = enqueue_step(ctx, pa, cuser, live, k, sweep, s, carry, ctx->un_fin, cmap))) return rc;
         if ((rc = irs_launch_until_record(ctx, ctx->un_stage, P, i, cmap, pa.seq, live, ctx->un_fin, ctx->un_status, paths, status, s)))
             return rc;
         ++steps, row_steps += live, carry = 1;
@@ -954,8 +1024,9 @@ extern "C" int irs_beam_step(irs_ctx *ctx, const int64_t *seq_in, const int32_t 
         !status || B < 1 || W < 1 || k < 1 || P < 1 || step < 0 || step >= P)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step: bad arguments");
     if (W > 1 && (!lse_max || !lse_sum)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step: W > 1 needs the row log-sum-exp");
-    const int rc = check_excl(ctx, "irs_beam_step", B, P);
+    int rc = refuse_trace(ctx, "irs_beam_step");
     if (rc) return rc;
+    if ((rc = check_excl(ctx, "irs_beam_step", B, P))) return rc;
     const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k,
                              excl_args(ctx, W, nullptr, paths_in, P, 0, nullptr, step)};
     return irs_launch_beam_step(ctx, beam_state(seq_in, hep_in, cum_in, paths_in, nullptr), {seq_out, hep_out, cum_out, paths_out, nullptr},
@@ -1031,8 +1102,9 @@ extern "C" int irs_beam_step_until(irs_ctx *ctx, const int64_t *seq_in, const in
     if (W > 1 && (!lse_max || !lse_sum)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_until: W > 1 needs the row log-sum-exp");
     if (stop_rule != IRS_BEAM_STOP_ALL && stop_rule != IRS_BEAM_STOP_BEST)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_until: stop_rule %d (IRS_BEAM_STOP_ALL or IRS_BEAM_STOP_BEST)", stop_rule);
-    const int rc = check_excl(ctx, "irs_beam_step_until", B, P);
+    int rc = refuse_trace(ctx, "irs_beam_step_until");
     if (rc) return rc;
+    if ((rc = check_excl(ctx, "irs_beam_step_until", B, P))) return rc;
     const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k,
                              excl_args(ctx, W, nullptr, paths_in, P, 0, nullptr, step)};
     const irs_beam_until until{done, nullptr, stop_rule};

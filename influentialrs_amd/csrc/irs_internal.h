@@ -73,8 +73,9 @@ struct irs_step_key {
     int32_t kind, B, W, P, k, sweep, sample, sample_k;
     uint64_t seed;
     const void *comm, *seq, *user, *hep, *paths, *status;
+    const void *tr_item, *tr_target, *tr_rank, *tr_scratch; // the bound path trace (irs_bind_path_trace); null: none
 };
-static_assert(sizeof(irs_step_key) == 8 * sizeof(int32_t) + 7 * 8, "irs_step_key is compared with memcmp: no padding");
+static_assert(sizeof(irs_step_key) == 8 * sizeof(int32_t) + 11 * 8, "irs_step_key is compared with memcmp: no padding");
 struct irs_step_graph {
     hipGraphExec_t exec; // null: nothing captured
     irs_step_key key;
@@ -124,6 +125,31 @@ struct irs_beam_out { // the caller's outputs of irs_beam_search_until; fin and 
     double *scores;
     int32_t *fin;
     int64_t *seq;
+};
+// ---- path trace (irs_bind_path_trace).  The caller's scratch holds, per row of a step: the sweep's before-count and the local
+// id of the target, then what the record kernel reads after the step -- (max, sum exp), the target's score, its rank.
+struct irs_trace_rows {
+    unsigned long long *count; // [rows] items of the whole catalog ranked before the target
+    int64_t *refid;            // [rows] local 0-based id of the target, -1: no target (t == 0, or outside the catalog)
+    float *mx, *sm, *ts;       // [rows] max, sum exp(e - max), target score
+    int32_t *rank;             // [rows] 1 + count - window correction; 0: no target
+};
+static inline size_t irs_trace_layout(void *base, int rows, irs_trace_rows *o) {
+    const size_t r8 = ((size_t)rows * 8 + 255) / 256 * 256, r4 = ((size_t)rows * 4 + 255) / 256 * 256;
+    if (o) {
+        char *p = (char *)base;
+        o->count = (unsigned long long *)p, o->refid = (int64_t *)(p + r8);
+        o->mx = (float *)(p + 2 * r8), o->sm = (float *)(p + 2 * r8 + r4), o->ts = (float *)(p + 2 * r8 + 2 * r4);
+        o->rank = (int32_t *)(p + 2 * r8 + 3 * r4);
+    }
+    return 2 * r8 + 4 * r4;
+}
+struct irs_trace_rec { // what the record kernel takes: a step's rows (the scratch) and the caller's three [users][ld] arrays
+    const float *mx, *sm, *ts;
+    const int32_t *rank;
+    float *lp_item, *lp_target;
+    int32_t *rank_target;
+    int ld;
 };
 struct irs_eval_batch_args { // irs_build_eval_batch's arguments as the kernel takes them
     const int64_t *items, *offsets;
@@ -251,6 +277,14 @@ struct irs_ctx {
     const int64_t *excl_rows;   // [excl_users][excl_stride] ascending, INT64_MAX behind the valid ids
     int excl_users, excl_stride, excl_no_repeat;
 
+    // path trace (irs_bind_path_trace): the caller's three [tr_users][tr_ld] arrays and scratch while bound; the greedy loops then
+    // run the target sweep before their step and the record kernel after it, the beam and the sharded loops refuse
+    int tr_on;
+    float *tr_item, *tr_target;
+    int32_t *tr_rank;
+    int tr_users, tr_ld;
+    void *tr_scratch;
+
     // profiling
     int prof_family;
     irs_prof_ev *prof_ev;
@@ -332,6 +366,9 @@ int irs_launch_count_before(irs_ctx *ctx, const float *xrows, int M, const float
                             const int64_t *excl, int n_excl, int64_t *count, hipStream_t s);
 int irs_launch_dense(irs_ctx *ctx, const float *xrows, int M, float *out, int64_t ld, hipStream_t s);
 int irs_launch_lse(irs_ctx *ctx, const float *xrows, int M, float *out_max, float *out_sum, hipStream_t s);
+// the target sweep of the path trace: sc.count / sc.refid are its scratch, the four outputs go where the caller says
+int irs_launch_target_trace(irs_ctx *ctx, const float *xrows, const int64_t *seq, const int32_t *hep, int M, const irs_trace_rows &sc,
+                            float *out_max, float *out_sum, float *out_tscore, int32_t *out_rank, hipStream_t s);
 int irs_launch_refresh_bias(irs_ctx *ctx, hipStream_t s);
 int irs_launch_lse_combine(irs_ctx *ctx, const float *mx, const float *sm, float *lse, int M, hipStream_t s);
 int irs_launch_ce_reduce(irs_ctx *ctx, const float *lse, const float *lab_score, const int64_t *labels0, int M, double *out,
@@ -377,6 +414,11 @@ int irs_launch_merge_keys(irs_ctx *ctx, const uint64_t *keys_in, int W, int M, i
 int irs_launch_pack_topk(irs_ctx *ctx, const float *val, const int64_t *ids0, int64_t n, uint64_t *keys, hipStream_t s);
 int irs_launch_path_step(irs_ctx *ctx, const irs_path_args &pa, int B, const float *val, const int64_t *ids0, int k, hipStream_t s);
 int irs_launch_inc(irs_ctx *ctx, int32_t *ctr, hipStream_t s);
+// after a path step on B rows, before the step counter moves: the three traced values of step step_ptr[0] go to row map[r] (null: r)
+// of the caller's arrays; rows with fin[r] != 0 (null: none) are not written
+int irs_launch_trace_record(irs_ctx *ctx, const irs_trace_rec &t, const int64_t *seq, const int32_t *hep, const float *paths,
+                            int path_ld, const int32_t *step_ptr, const int32_t *map, const int32_t *fin, const float *val,
+                            const int64_t *ids0, int k, int B, hipStream_t s);
 // the stop-at-target loop's own kernels (irs_generate_paths_until, capi.hip); map == nullptr is the identity
 int irs_launch_until_record(irs_ctx *ctx, const float *stage, int P, int step, const int32_t *map, const int64_t *seq, int B,
                             int32_t *fin, int32_t *step_status, float *paths, int32_t *status, hipStream_t s);

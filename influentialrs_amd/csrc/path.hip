@@ -396,6 +396,53 @@ int irs_launch_inc(irs_ctx *ctx, int32_t *ctr, hipStream_t s) {
     return IRS_OK;
 }
 
+// ------------------------------------------------------------------ path trace (irs_bind_path_trace)
+// After a path step, before the step counter moves (and, in the until loop, before k_until_record sets fin): the item the step
+// chose is read back from the window it was put into -- seq[r][hep[r]] after a grow, seq[r][L - 2] after a shift; the path entry
+// is a float32 and only says whether anything was chosen -- and looked up in the lists the step chose from, whose score is the
+// chain's.  A chosen item is always in its list (NaN would say otherwise).  One wave per row.
+__global__ void __launch_bounds__(256) k_trace_record(const irs_trace_rec t, const int64_t *__restrict__ seq,
+                                                      const int32_t *__restrict__ hep, int L, const float *__restrict__ paths,
+                                                      int path_ld, const int32_t *__restrict__ step_ptr, const int32_t *__restrict__ map,
+                                                      const int32_t *__restrict__ fin, const float *__restrict__ val,
+                                                      const int64_t *__restrict__ ids0, int k, int B) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= B) return;
+    if (fin && fin[r]) return;
+    const int step = step_ptr[0];
+    const double lse = (double)t.mx[r] + log((double)t.sm[r]);
+    float lpi = 0.f;
+    if (paths[(size_t)r * path_ld + step] != 0.f) {
+        const int he = hep[r];
+        const int64_t id0 = seq[(size_t)r * L + (he < L - 2 ? (he > 0 ? he : 0) : L - 2)] - 1;
+        lpi = __uint_as_float(0x7FC00000u);
+        for (int c0 = 0; c0 < k; c0 += 64) {
+            const unsigned long long hit = __ballot(c0 + lane < k && ids0[(size_t)r * k + c0 + lane] == id0);
+            if (hit) {
+                lpi = (float)((double)val[(size_t)r * k + c0 + (__ffsll((long long)hit) - 1)] - lse);
+                break;
+            }
+        }
+    }
+    if (lane == 0) {
+        const size_t at = (size_t)(map ? map[r] : r) * t.ld + step;
+        const int rk = t.rank[r];
+        t.lp_item[at] = lpi;
+        t.lp_target[at] = rk ? (float)((double)t.ts[r] - lse) : 0.f;
+        t.rank_target[at] = rk;
+    }
+}
+
+int irs_launch_trace_record(irs_ctx *ctx, const irs_trace_rec &t, const int64_t *seq, const int32_t *hep, const float *paths,
+                            int path_ld, const int32_t *step_ptr, const int32_t *map, const int32_t *fin, const float *val,
+                            const int64_t *ids0, int k, int B, hipStream_t s) {
+    hipLaunchKernelGGL(k_trace_record, dim3((B + 3) / 4), dim3(256), 0, s, t, seq, hep, ctx->dims.max_len, paths, path_ld, step_ptr, map,
+                       fin, val, ids0, k, B);
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
 // ------------------------------------------------------------------ stop-at-target search (irs_generate_paths_until)
 // The reference never stops at the target: it runs every step for every user and zeroes the tail on the host afterwards
 // (model/influentialRS.py:459-467).  Here a user is finished after the step that chose seq[b][L - 1]; the three kernels below

@@ -40,6 +40,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 #define MODE_DENSE 3
 #define MODE_LSE 4
 #define MODE_CEGRAD 5 // DENSE's orientation; writes scale * (softmax - onehot(label)) instead of the logits
+#define MODE_TRACE 6  // COUNT against (ref_score, ref_id) and LSE's (max, sum exp) partials, both from the chain-order scores
 
 struct SweepArgs {
     // operands
@@ -1067,7 +1068,8 @@ __global__ void __launch_bounds__(256, 2) k_sweep_f32(SweepArgs a) {
     int t1 = min(t0 + a.tiles_per_wave * ts, a.tile_end);
 
     float aux[UB];        // PRE: running max; EMIT: thr; COUNT: ref score; LSE: running max
-    float aux2[UB];       // LSE: running sum
+    float aux2[UB];       // LSE, TRACE: running sum
+    float aux3[UB];       // TRACE: running max (aux holds the reference score)
     unsigned int cnt[UB]; // COUNT
     long long refid[UB];
 #pragma unroll
@@ -1075,10 +1077,11 @@ __global__ void __launch_bounds__(256, 2) k_sweep_f32(SweepArgs a) {
         int user = (ut0 + u) * 32 + r;
         aux[u] = -INFINITY;
         aux2[u] = 0.f;
+        aux3[u] = -INFINITY;
         cnt[u] = 0;
         refid[u] = -1;
         if (MODE == MODE_EMIT) aux[u] = (u < ubc) ? fmaxf(a.thr[user], -3.0e38f) : INFINITY;
-        if (MODE == MODE_COUNT) {
+        if (MODE == MODE_COUNT || MODE == MODE_TRACE) {
             aux[u] = (u < ubc && user < a.M) ? a.ref_score[user] : INFINITY;
             refid[u] = (u < ubc && user < a.M) ? (long long)a.ref_id[user] : -1;
         }
@@ -1161,12 +1164,22 @@ __global__ void __launch_bounds__(256, 2) k_sweep_f32(SweepArgs a) {
                 const int user = (ut0 + u) * 32 + r;
                 if (MODE == MODE_PRE) aux[u] = fmaxf(aux[u], max16(acc));
                 else if (MODE == MODE_EMIT) emit_candidates(a, acc, aux[u], user, t, h, eq, lane);
-                else if (MODE == MODE_COUNT) {
+                else if (MODE == MODE_COUNT || MODE == MODE_TRACE) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         long long it = (long long)t * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
                         bool before = acc[i] > aux[u] || (acc[i] == aux[u] && it < refid[u]);
                         cnt[u] += (before && it < a.n_local) ? 1u : 0u;
+                    }
+                    if (MODE == MODE_TRACE) { // the same registers once more: LSE's online (max, sum); pad items score -inf
+                        float m = fmaxf(aux3[u], max16(acc));
+                        if (m > -INFINITY) {
+                            float s = aux2[u] * __expf(aux3[u] - m);
+#pragma unroll
+                            for (int i = 0; i < 16; ++i) s += __expf(acc[i] - m);
+                            aux3[u] = m;
+                            aux2[u] = s;
+                        }
                     }
                 } else if (MODE == MODE_DENSE) {
                     const int64_t col = (int64_t)t * 32 + r;
@@ -1218,12 +1231,12 @@ __global__ void __launch_bounds__(256, 2) k_sweep_f32(SweepArgs a) {
         if (u >= ubc) continue;
         const int user = (ut0 + u) * 32 + r;
         if (MODE == MODE_PRE) a.gm[gm_index(a, gw * 2 + h, user)] = aux[u];
-        if (MODE == MODE_COUNT) {
+        if (MODE == MODE_COUNT || MODE == MODE_TRACE) {
             if (user < a.M && cnt[u]) atomicAdd(&a.count[user], (unsigned long long)cnt[u]);
         }
-        if (MODE == MODE_LSE) {
+        if (MODE == MODE_LSE || MODE == MODE_TRACE) {
             float *p = a.lse_part + ((size_t)(gw * 2 + h) * a.M_pad + user) * 2;
-            p[0] = aux[u];
+            p[0] = MODE == MODE_TRACE ? aux3[u] : aux[u];
             p[1] = aux2[u];
         }
     }
@@ -3106,6 +3119,95 @@ int irs_launch_lse(irs_ctx *ctx, const float *xrows, int M, float *out_max, floa
     if (rc) return rc;
     hipLaunchKernelGGL(k_lse_reduce, dim3(M), dim3(256), 0, s, ctx->lse_part, slots, a.M_pad, M, out_max,
                        out_sum);
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
+// ---- path trace: how the target stands in a row's softmax, before the step chooses (irs_score_target_trace, irs_bind_path_trace).
+// Three launches around one pass over the float32 catalog: the target's exact score (k_gather's arithmetic) and a cleared count;
+// the chain-order sweep (MODE_TRACE: before-count against (score, id) of the target, and the (max, sum exp) partials); the
+// partials' reduction (k_lse_reduce, slot order) and the window correction below.
+__global__ void __launch_bounds__(64) k_trace_target(const float *__restrict__ x, int d, const float *__restrict__ W,
+                                                     const float *__restrict__ bias, int64_t n_local, const int64_t *__restrict__ seq,
+                                                     int L, float *__restrict__ tscore, int64_t *__restrict__ refid,
+                                                     unsigned long long *__restrict__ count) {
+    __shared__ float xs[256];
+    const int row = blockIdx.x;
+    for (int i = threadIdx.x; i < d; i += 64) xs[i] = x[(size_t)row * d + i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int64_t j = seq[(size_t)row * L + L - 1] - 1;
+        const bool ok = j >= 0 && j < n_local;
+        tscore[row] = ok ? irs_chain(xs, W + (size_t)j * d, bias[j], d) : -INFINITY;
+        refid[row] = ok ? j : -1;
+        count[row] = 0ull;
+    }
+}
+
+// rank = 1 + count - #{distinct non-pad window items ranked before the target}.  The window is read where it lies,
+// seq[row][0 .. hep[row]] (any max_len), once, into LDS: a slot counts when no earlier slot holds its item (a scan of LDS without
+// an early exit, so the reads pipeline; a scan of global memory with one was most of this kernel's time), and only such a slot's
+// item is scored, to be compared with the target.  One wave per row.
+__global__ void __launch_bounds__(256) k_trace_rank(const float *__restrict__ x, int d, const float *__restrict__ W,
+                                                    const float *__restrict__ bias, int64_t n_local, const int64_t *__restrict__ seq,
+                                                    const int32_t *__restrict__ hep, int L, int M, const float *__restrict__ tscore,
+                                                    const int64_t *__restrict__ refid, const unsigned long long *__restrict__ count,
+                                                    int32_t *__restrict__ rank) {
+    __shared__ float xs[4][256];
+    __shared__ int64_t wl[4][IRS_MAX_LEN_LONG];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + wv;
+    int n = 0; // window slots: hep + 1, at most L
+    if (row < M) {
+        for (int i = lane; i < d; i += 64) xs[wv][i] = x[(size_t)row * d + i];
+        n = min(hep[row] + 1, L);
+        for (int p = lane; p < n; p += 64) wl[wv][p] = seq[(size_t)row * L + p];
+    }
+    __syncthreads();
+    if (row >= M) return;
+    const int64_t rid = refid[row];
+    if (rid < 0) {
+        if (lane == 0) rank[row] = 0;
+        return;
+    }
+    const float rs = tscore[row];
+    unsigned int sub = 0;
+    for (int p = lane; p < n; p += 64) {
+        const int64_t item = wl[wv][p], j = item - 1;
+        if (j < 0 || j >= n_local || j == rid) continue;
+        bool dup = false;
+        for (int q = 0; q < p; ++q) dup |= (wl[wv][q] == item);
+        if (dup) continue;
+        const float e = irs_chain(xs[wv], W + (size_t)j * d, bias[j], d);
+        sub += (e > rs || (e == rs && j < rid)) ? 1u : 0u;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sub += __shfl_xor(sub, off, 64);
+    if (lane == 0) rank[row] = (int32_t)(1ull + count[row] - (unsigned long long)sub);
+}
+
+int irs_launch_target_trace(irs_ctx *ctx, const float *xrows, const int64_t *seq, const int32_t *hep, int M, const irs_trace_rows &sc,
+                            float *out_max, float *out_sum, float *out_tscore, int32_t *out_rank, hipStream_t s) {
+    const int d = ctx->dims.d, L = ctx->dims.max_len;
+    hipLaunchKernelGGL(k_trace_target, dim3(M), dim3(64), 0, s, xrows, d, ctx->proj_w, ctx->proj_b, ctx->n_local, seq, L, out_tscore,
+                       sc.refid, sc.count);
+    SweepArgs a;
+    sweep_common(ctx, a, xrows, M);
+    const int max_waves = ctx->lse_slots / 2; // a wave writes two (max, sum) slots, one per lane half
+    sweep_decompose(a, 0, ctx->n_tiles, 1, (ctx->n_tiles + max_waves - 1) / max_waves);
+    const int slots = a.n_strips * 4 * 2;
+    if (slots > ctx->lse_slots) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "trace slots %d > %d", slots, ctx->lse_slots);
+    a.lse_part = ctx->lse_part;
+    a.ref_score = out_tscore;
+    a.ref_id = sc.refid;
+    a.count = sc.count;
+    irs_prof_begin(ctx, IRS_PROF_SWEEP, s);
+    const int rc = launch_sweep_f32<MODE_TRACE>(ctx, a, s);
+    irs_prof_end(ctx, IRS_PROF_SWEEP, s, 2.0 * d * (double)M * (double)ctx->n_local, (double)ctx->n_local * d * 4.0);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_lse_reduce, dim3(M), dim3(256), 0, s, ctx->lse_part, slots, a.M_pad, M, out_max, out_sum);
+    hipLaunchKernelGGL(k_trace_rank, dim3((M + 3) / 4), dim3(256), 0, s, xrows, d, ctx->proj_w, ctx->proj_b, ctx->n_local, seq, hep, L, M,
+                       out_tscore, sc.refid, sc.count, out_rank);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }

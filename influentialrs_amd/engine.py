@@ -486,6 +486,66 @@ class Engine:
             scratch.record_stream(stream)
             self.unbind_exclusions()
 
+    # ------------------------------------------------------------------ path trace (irs_bind_path_trace)
+    def path_trace_scratch_bytes(self, rows: int) -> int:
+        n = int(self.lib.irs_path_trace_scratch_bytes(self.h, rows))
+        if n == 0:
+            raise IrsError(f"path_trace_scratch_bytes: rows={rows} (need 1 <= rows <= max_rows={self.max_rows})")
+        return n
+
+    def score_target_trace(self, xrows: torch.Tensor, seqs: torch.Tensor, hep: torch.Tensor,
+                           scratch: Optional[torch.Tensor] = None):
+        """irs_score_target_trace: how each row's target seqs[m, L - 1] stands in the row's softmax, out of one pass over the
+        float32 catalog: (max[M], sumexp[M], target_score[M] float32, rank[M] int32).  The rank leaves out the non-pad items of
+        the window seqs[m, :hep[m] + 1]; log p(target) = target_score - (max + log(sumexp)).  A row without a target (0) gets
+        target_score -inf and rank 0."""
+        xrows = self._dev(xrows, torch.float32)
+        seqs, hep = self._dev(seqs, torch.int64), self._dev(hep, torch.int32)
+        M = xrows.shape[0]
+        if xrows.dim() != 2 or xrows.shape[1] != self.d or tuple(seqs.shape) != (M, self.L) or hep.numel() != M:
+            raise IrsError("score_target_trace: xrows [M, d], seqs [M, max_len], hep [M]")
+        if scratch is None:
+            scratch = torch.empty(self.path_trace_scratch_bytes(M), dtype=torch.uint8, device=self.device)
+        scratch = self._inplace(scratch, torch.uint8, "score_target_trace: scratch")
+        mx, sm, ts = (torch.empty(M, dtype=torch.float32, device=self.device) for _ in range(3))
+        rank = torch.empty(M, dtype=torch.int32, device=self.device)
+        self._call(self.lib.irs_score_target_trace, _ptr(xrows), _ptr(seqs), _ptr(hep), M, _ptr(scratch), scratch.numel(),
+                   _ptr(mx), _ptr(sm), _ptr(ts), _ptr(rank))
+        scratch.record_stream(torch.cuda.current_stream(self.device))
+        return mx, sm, ts, rank
+
+    def bind_path_trace(self, users: int, ld: int):
+        """irs_bind_path_trace: until unbind_path_trace the greedy / sampled loops record (lp_item, lp_target float32 [users, ld],
+        rank_target int32 [users, ld]); the beam and the sharded loops refuse.  Returns (lp_item, lp_target, rank_target,
+        scratch): the caller keeps all four alive while bound."""
+        lp_item = torch.zeros((users, ld), dtype=torch.float32, device=self.device)
+        lp_target = torch.zeros((users, ld), dtype=torch.float32, device=self.device)
+        rank = torch.zeros((users, ld), dtype=torch.int32, device=self.device)
+        scratch = torch.empty(self.path_trace_scratch_bytes(users), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.irs_bind_path_trace(self.h, _ptr(lp_item), _ptr(lp_target), _ptr(rank), users, ld, _ptr(scratch),
+                                                 scratch.numel()))
+        return lp_item, lp_target, rank, scratch
+
+    def unbind_path_trace(self):
+        self._check(self.lib.irs_bind_path_trace(self.h, None, None, None, 0, 0, None, 0))
+
+    @contextlib.contextmanager
+    def _path_trace(self, on: bool, users: int, ld: int, graph: bool = False):
+        """While a search call runs with trace=True: the three arrays and the scratch bound before and unbound after, like
+        _exact_candidates (and with its cost: bind and unbind drop the context's captured steps).  Yields the arrays, or None."""
+        if not on:
+            yield None
+            return
+        lp_item, lp_target, rank, scratch = self.bind_path_trace(users, ld)
+        try:
+            yield lp_item, lp_target, rank
+        finally:
+            stream = torch.cuda.current_stream(self.device)
+            if graph:
+                stream.synchronize()
+            scratch.record_stream(stream)
+            self.unbind_path_trace()
+
     # ------------------------------------------------------------------ path search
     def path_step(self, seqs, hep, val, ids0, step: int, paths, status, sample=False, sample_k=3, seed=0):
         seqs = self._inplace(seqs, torch.int64, "path_step: seqs")
@@ -503,13 +563,16 @@ class Engine:
                        k: int = 100, sweep: int = IRS_SWEEP_BF16, sample=False, sample_k=3, seed=0,
                        use_graph: bool = False, paths: Optional[torch.Tensor] = None,
                        status: Optional[torch.Tensor] = None, exact_candidates: bool = False,
-                       exclude: Optional[torch.Tensor] = None, no_repeat: bool = False):
+                       exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False):
         """Runs the whole search loop on the device.  `seqs` and `hep` are the
         working window state and are modified in place.  exact_candidates: a row whose k candidates are hidden by its window
         chooses among the exact best admissible items of the catalog instead (IRS_ROW_RESCUED; the result of k = n_item).
         With the keyword set use_graph saves nothing: the step is captured again on every call (_exact_candidates).
         exclude (int64 [B, E], 0-based ids, -1 = unused) / no_repeat: bound for this call (irs_bind_exclusions): a step drops
-        window + the user's list (+ its own path so far); the same holds in the three other loops."""
+        window + the user's list (+ its own path so far); the same holds in the three other loops.
+        trace: a path trace is bound for this call (irs_bind_path_trace) and the return value grows a third member, (lp_item,
+        lp_target float32 [B, max_path_len], rank_target int32 [B, max_path_len]): all columns are written; cut them where paths
+        is cut."""
         seqs = self._inplace(seqs, torch.int64, "generate_paths: seqs")
         hep = self._inplace(hep, torch.int32, "generate_paths: hep")
         if users is not None:
@@ -526,19 +589,21 @@ class Engine:
         if paths.shape != (B, max_path_len):
             raise IrsError("generate_paths: paths must be [B, max_path_len]")
         with self._exact_candidates(exact_candidates, B, sample_k if sample else 1, bool(use_graph)), \
-                self._exclusions(exclude, no_repeat, B, bool(use_graph)):
+                self._exclusions(exclude, no_repeat, B, bool(use_graph)), \
+                self._path_trace(trace, B, max_path_len, bool(use_graph)) as traced:
             self._call(self.lib.irs_generate_paths, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                     int(sample), sample_k, seed, int(use_graph), _ptr(paths), _ptr(status))
-        return paths, status
+        return (paths, status, traced) if trace else (paths, status)
 
     def generate_paths_until(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
                              k: int = 100, sweep: int = IRS_SWEEP_BF16, sample=False, sample_k=3, seed=0,
                              check_every: int = 1, paths: Optional[torch.Tensor] = None,
                              status: Optional[torch.Tensor] = None, exact_candidates: bool = False,
-                             exclude: Optional[torch.Tensor] = None, no_repeat: bool = False):
+                             exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False):
         """generate_paths that stops a user at its target (seqs[b, L - 1]) and the call when nobody is left
         (irs_generate_paths_until): returns (paths, status, steps_run, row_steps).  Paths are zero behind the target.
-        `seqs` and `hep` are working state: modified, and unspecified afterwards.  One host read of 4 bytes per check."""
+        `seqs` and `hep` are working state: modified, and unspecified afterwards.  One host read of 4 bytes per check.
+        trace: as in generate_paths, a fifth member (lp_item, lp_target, rank_target), exactly zero behind a user's arrival."""
         seqs = self._inplace(seqs, torch.int64, "generate_paths_until: seqs")
         hep = self._inplace(hep, torch.int32, "generate_paths_until: hep")
         if users is not None:
@@ -555,10 +620,12 @@ class Engine:
         if paths.shape != (B, max_path_len):
             raise IrsError("generate_paths_until: paths must be [B, max_path_len]")
         stats = (ctypes.c_int64 * 2)(0, 0)
-        with self._exact_candidates(exact_candidates, B, sample_k if sample else 1), self._exclusions(exclude, no_repeat, B):
+        with self._exact_candidates(exact_candidates, B, sample_k if sample else 1), self._exclusions(exclude, no_repeat, B), \
+                self._path_trace(trace, B, max_path_len) as traced:
             self._call(self.lib.irs_generate_paths_until, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                           int(sample), sample_k, seed, check_every, _ptr(paths), _ptr(status), stats)
-        return paths, status, int(stats[0]), int(stats[1])
+        out = (paths, status, int(stats[0]), int(stats[1]))
+        return out + (traced,) if trace else out
 
     # ------------------------------------------------------------------ beam search (build-defined extension)
     def beam_step(self, state_in, val, ids0, lse, step: int, state_out, status):

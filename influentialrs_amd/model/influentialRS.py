@@ -180,16 +180,42 @@ def _takes_exact_candidates(fn):
     """Gives get_seq_in_batch its keyword exact_candidates=False.  It is taken here, keyword only, so that the declared
     parameter list stays what it was (it ends with beam_stop): positional callers and code that reads the signature are not
     disturbed.  The search reads the switch from self._exact_candidates for the time of the call.
-    exclude=None and no_repeat=False (bound exclusions) are taken the same way, into self._exclude / self._no_repeat."""
+    exclude=None and no_repeat=False (bound exclusions) are taken the same way, into self._exclude / self._no_repeat, and
+    trace=False (the path trace) into self._trace."""
     @functools.wraps(fn)
-    def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, **kw):
-        prev = (getattr(self, "_exact_candidates", False), getattr(self, "_exclude", None), getattr(self, "_no_repeat", False))
-        self._exact_candidates, self._exclude, self._no_repeat = bool(exact_candidates), exclude, bool(no_repeat)
+    def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, trace=False, **kw):
+        prev = (getattr(self, "_exact_candidates", False), getattr(self, "_exclude", None), getattr(self, "_no_repeat", False),
+                getattr(self, "_trace", False))
+        self._exact_candidates, self._exclude, self._no_repeat, self._trace = bool(exact_candidates), exclude, bool(no_repeat), bool(trace)
         try:
             return fn(self, *args, **kw)
         finally:
-            self._exact_candidates, self._exclude, self._no_repeat = prev
+            self._exact_candidates, self._exclude, self._no_repeat, self._trace = prev
     return call
+
+
+def path_trace_summary(lp_item, lp_target, rank_target, paths, targets):
+    """get_seq_in_batch's last_trace from the search's arrays ([B, P] each; `paths` before the host cut or after it, `targets`
+    [B]).  A user's live steps end with its arrival (the first path entry equal to its target) or run to P; behind them the
+    three arrays are cut to 0 like the path.  Over the live steps, as Evaluator.get_grad_in_batch forms iois and avg_ps:
+    ioi = last lp_target - first, ior = first rank_target - last (positive: the target moved up), avg_lp_item = mean lp_item."""
+    lp_item = np.array(lp_item, dtype=np.float32)
+    lp_target = np.array(lp_target, dtype=np.float32)
+    rank_target = np.array(rank_target, dtype=np.int32)
+    B, P = lp_item.shape
+    n_steps = np.full(B, P, dtype=np.int64)
+    for i in range(B):
+        pos = get_item_index(np.asarray(paths[i]), np.asarray(targets).reshape(-1)[i])
+        if pos != -1:
+            n_steps[i] = pos + 1
+        for a in (lp_item, lp_target, rank_target):
+            a[i, n_steps[i]:] = 0
+    last = n_steps - 1
+    rows = np.arange(B)
+    return dict(lp_item=lp_item, lp_target=lp_target, rank_target=rank_target, n_steps=n_steps,
+                ioi=lp_target[rows, last].astype(np.float64) - lp_target[:, 0].astype(np.float64),
+                ior=rank_target[:, 0].astype(np.int64) - rank_target[rows, last].astype(np.int64),
+                avg_lp_item=np.array([lp_item[i, :n_steps[i]].astype(np.float64).mean() for i in range(B)]))
 
 
 def exclusion_ids0(exclude, no_repeat, seqs, hep: int, device):
@@ -369,9 +395,20 @@ class IRSNN(nn.Module):
         `raw`, or a [B, E] tensor padded with 0; every step then drops window + the user's list.  no_repeat=True also drops
         the path so far, and adds the user's initial window to its list: the search never offers anything the window ever held
         nor anything it chose itself.  At most 4096 ids per user, the window's included.  A target that is in the user's
-        list can no longer be reached.  Combine with exact_candidates=True: a long list regularly hides the whole top-100."""
+        list can no longer be reached.  Combine with exact_candidates=True: a long list regularly hides the whole top-100.
+        trace=True (extension, keyword only, taken the same way; greedy / sampled search on one device): the search records,
+        at every step and before it chooses, the log-probability and the rank of the target and the log-probability of the item
+        it then chose, under this model's softmax over the whole catalog (irs_bind_path_trace).  The return value is unchanged;
+        self.last_trace is path_trace_summary's dict: lp_item, lp_target, rank_target [B, max_path_len] cut after the arrival,
+        n_steps [B], ioi, ior, avg_lp_item."""
         exact_candidates = getattr(self, "_exact_candidates", False)
         exclude, no_repeat = getattr(self, "_exclude", None), getattr(self, "_no_repeat", False)
+        trace = getattr(self, "_trace", False)
+        if trace and beam_width > 1:
+            raise ValueError("trace is not built for beam search (beam_width > 1): no trace is carried through beam state")
+        if trace and self.net._hip.world != 1:
+            raise ValueError("trace is not built for an item-sharded catalog: irs_bind_path_trace needs the whole catalog on "
+                             "one device")
         if (exclude is not None or no_repeat) and self.net._hip.world != 1:
             raise ValueError("exclude / no_repeat is not built for an item-sharded catalog: irs_bind_exclusions needs the whole "
                              "catalog on one device")
@@ -406,14 +443,15 @@ class IRSNN(nn.Module):
                 raise ValueError("stop_at_target is not built for an item-sharded catalog: irs_generate_paths_sharded runs "
                                  "every step")
             eng = hip.get(B, B)
-            paths_t, status, _, _ = eng.generate_paths_until(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
-                                                             sample=sample, sample_k=sample_k, seed=seed,
-                                                             check_every=STOP_CHECK_EVERY, exact_candidates=exact_candidates, **excl)
+            paths_t, status, _, _, *traced = eng.generate_paths_until(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
+                                                                      sample=sample, sample_k=sample_k, seed=seed,
+                                                                      check_every=STOP_CHECK_EVERY,
+                                                                      exact_candidates=exact_candidates, trace=trace, **excl)
         elif hip.world == 1:
             eng = hip.get(B, B)
-            paths_t, status = eng.generate_paths(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
-                                                 sample=sample, sample_k=sample_k, seed=seed, use_graph=False,
-                                                 exact_candidates=exact_candidates, **excl)
+            paths_t, status, *traced = eng.generate_paths(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
+                                                          sample=sample, sample_k=sample_k, seed=seed, use_graph=False,
+                                                          exact_candidates=exact_candidates, trace=trace, **excl)
         else:  # item-sharded: irs_generate_paths_sharded (decode, row all-gather, shard sweep, key all-to-all, merge, path
             # step per search step, below the C ABI on one stream)
             eng = hip.get(B, B * hip.world)
@@ -429,6 +467,8 @@ class IRSNN(nn.Module):
         n_early_success = 0
         paths = paths_t.detach().cpu().numpy()
         targets = targets.detach().cpu().numpy()
+        if trace:
+            self.last_trace = path_trace_summary(*(a.detach().cpu().numpy() for a in traced[0]), paths, targets)
         histories = seqs[:, :-1].detach().cpu().numpy()
         actual_history = []
         for i in range(B):
