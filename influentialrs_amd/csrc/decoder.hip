@@ -13,6 +13,8 @@
 // windows longer than 256 tokens); packing, gathers.
 #include "irs_internal.h"
 
+#include <assert.h>
+
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 // ------------------------------------------------------------------ embed
@@ -1715,6 +1717,27 @@ __device__ __forceinline__ x6_u32x4 x6_gld(const void *p) {
     return v;
 }
 
+// ... and a 4-byte one (k_block_x6<.., SEQ>: the parameter vectors of layer 0)
+__device__ __forceinline__ unsigned int x6_gld32(const void *p) {
+    unsigned int v;
+    asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(p) : "memory");
+    return v;
+}
+
+// ... with its wait inside the statement (the value is valid when the statement ends)
+__device__ __forceinline__ unsigned int x6_gld32_sync(const void *p) {
+    unsigned int v;
+    asm volatile("global_load_dword %0, %1, off\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
+    return v;
+}
+
+// a 16-byte global store the compiler does not track: no wait of its making in front of it, the address an immediate offset from
+// one base per tile (k_block_x6<.., SEQ>: the x' tile of LayerNorm 3; what orders it before a later load is named at its site)
+template <int OFF>
+__device__ __forceinline__ void x6_gst(void *p, x6_u32x4 v) {
+    asm volatile("global_store_dwordx4 %0, %1, off offset:%2" :: "v"(p), "v"(v), "i"(OFF) : "memory");
+}
+
 // an 8-byte LDS store the compiler does not track (k_block_x6<.., SEQ>: the K / V image rows written inside a step)
 template <int OFF>
 __device__ __forceinline__ void x6_wr64(unsigned int addr, __attribute__((ext_vector_type(4))) _Float16 v) {
@@ -1775,6 +1798,12 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
 // (k_absorb_qu, k_absorb_attn, k_absorb_out).  (lab, tools/seq_lab.sh last0: 0 = an extra trip of the layer loop runs the last
 // layer's front for every token and the attention of each consumed token's block, gathered by the host side, as before.)
 #define SEQ_LAST_ABSORB 1
+#endif
+#ifndef SEQ_BATCHED_IO
+// 1: the prologue requests the 32 pieces of a token's embedding and position rows back to back and waits once; LayerNorm 3
+// stores its sixteen x' pieces from inline asm with no wait between them.  (lab, tools/seq_lab.sh io0: 0 = the placement up to
+// here -- a piece pair per round trip in the prologue, a compiler-written vmcnt(0) in front of every x' store.)
+#define SEQ_BATCHED_IO 1
 #endif
 // SEQ layout of the dynamic LDS behind the ring and the parameter vectors (x6_seq_lds_bytes)
 #define X6_SEQ_VECS (256 + 12 * 32 * 4 + 384)   // floats: the parameter vectors + this layer's in-projection bias
@@ -1906,7 +1935,23 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             vecs[V_O + 5 * D + tid] = a.c ? pv[11] : 0.f;
         }
     } else if constexpr (NT == 4) {
-        if constexpr (SEQ) {
+        if constexpr (SEQ && SEQ_BATCHED_IO) {
+            // layer 0's parameter vectors in ONE round trip: unconditional loads the compiler does not see (a lane beyond the
+            // vectors reads their last element and stores nothing), one wait.  (The plain form below compiled to three dependent
+            // round trips -- the conditional tail loads each behind the stores in front of them -- ahead of the prologue's gather.)
+            constexpr int NV_ = (X6_SEQ_VECS + 64 * NW - 1) / (64 * NW);
+            static_assert(NV_ == 5, "five operands in the wait below");
+            unsigned int vq[NV_];
+            x6_static_for<0, NV_>([&](auto kc) __attribute__((always_inline)) {
+                constexpr int k = decltype(kc)::value;
+                const int e = tid + 64 * NW * k;
+                vq[k] = x6_gld32(a.vecpack + (e < X6_SEQ_VECS ? e : X6_SEQ_VECS - 1));
+            });
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(vq[0]), "+v"(vq[1]), "+v"(vq[2]), "+v"(vq[3]), "+v"(vq[4]));
+#pragma unroll
+            for (int k = 0; k < NV_; ++k)
+                if (tid + 64 * NW * k < X6_SEQ_VECS) vecs[tid + 64 * NW * k] = __builtin_bit_cast(float, vq[k]);
+        } else if constexpr (SEQ) {
 #pragma unroll
             for (int k = 0; k < (X6_SEQ_VECS + 64 * NW - 1) / (64 * NW); ++k)
                 if (tid + 64 * NW * k < X6_SEQ_VECS) vecs[tid + 64 * NW * k] = a.vecpack[tid + 64 * NW * k];
@@ -2095,6 +2140,9 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                 issue(SEQ_LSTEPS - 1 + LEAD);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (no LDS-DMA piece in flight when the wave ends)
+            // (SEQ_BATCHED_IO: the wave ends HERE.  A return joins the live path's control flow at the kernel's end, and the
+            //  compiler then carries this loop's parameter loads as pending into the live prologue: a vmcnt wait in front of it.)
+            if constexpr (SEQ_BATCHED_IO) __builtin_amdgcn_endpgm();
             return;
         }
     }
@@ -2115,20 +2163,61 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
         }
         if constexpr (SEQ) { // x itself: the B operand of this layer's q | k | v steps (split into planes below)
             // = item_emb[seq] * sqrt(d) + pe[position] of this lane's token (k_embed_frag's arithmetic), gathered here: the
-            // separate embedding launch wrote and this prologue re-read 0.5 GB per C2 step and took 90 us; a workgroup's gather
-            // is a few microseconds of its ~500.  The tile is stored once: layer 0's residual.  Dead lanes hold zeros.
-            const bool live = l_b >= 0 && s_j < (l_h1 ? sh_cnt[1] : sh_cnt[0]);
-            const int orig = live ? a.tok_row[(l_h1 ? sh_off[1] : sh_off[0]) + s_j] : 0;
+            // separate embedding launch wrote and this prologue re-read 0.5 GB per C2 step and took 90 us.  Stamped
+            // (profiles/seq_round_trips/README.md): the whole prologue -- plan words, parameter vectors, this gather, the first
+            // step's DMA and barrier -- is 28.5 K of a wave's 820 K ticks on the bench windows, about 15 of its 440 us; with the
+            // gather as sixteen dependent round trips it was 30.9 K.  The tile is stored once: layer 0's residual.  Dead lanes hold zeros.
+            // (SEQ_BATCHED_IO) The token's index comes from a laundered copy of the lane: s_j itself lives through the layer loop, is
+            // spilled at the kernel's start and was reloaded from scratch in front of the tok_row load -- one more round trip in
+            // the chain tok_row -> seq -> rows.
+            bool h1_g = l_h1;
+            int lb_g = l_b, sj_g = s_j;
+            if constexpr (SEQ_BATCHED_IO) {
+                int ln_ = lane;
+                asm volatile("" : "+v"(ln_));
+                h1_g = (ln_ & 31) >= 16;
+                lb_g = h1_g ? sh_b[1] : sh_b[0];
+                sj_g = lb_g >= 0 ? 16 * (h1_g ? sh_qb[1] : sh_qb[0]) + (ln_ & 15) : 0x3FFFFFFF;
+            }
+            const bool live = lb_g >= 0 && sj_g < (h1_g ? sh_cnt[1] : sh_cnt[0]);
+            // (its own statement with the wait inside: the compiler otherwise merges what the idle waves' loop left pending into a
+            //  second wait at the head of this path)
+            int orig = 0;
+            if constexpr (SEQ_BATCHED_IO) {
+                if (live) orig = (int)x6_gld32_sync(a.tok_row + (h1_g ? sh_off[1] : sh_off[0]) + sj_g);
+            } else
+                orig = live ? a.tok_row[(h1_g ? sh_off[1] : sh_off[0]) + sj_g] : 0;
             int64_t id = live ? a.seq[orig] : 0;
             id = id < 0 ? 0 : (id > a.n_item ? a.n_item : id);
             const float *e_ = a.E + id * (int64_t)D + 4 * lk;
             const float *p_ = a.pe + (int64_t)(orig % a.L) * D + 4 * lk;
             float4 *xw = reinterpret_cast<float4 *>(const_cast<float *>(a.Rf)) + fbase;
+            // (SEQ_BATCHED_IO) The 16 + 16 pieces of the two rows are requested back to back by loads the compiler does not see and
+            // waited for ONCE: with plain loads the store of piece i may alias E / pe for the compiler, no later pair moves above
+            // it, and the gather is sixteen dependent round trips (load a pair, vmcnt(0), store) in front of the first DMA issue.
+            x6_u32x4 eq[SEQ_BATCHED_IO ? 4 * NT : 1], pq[SEQ_BATCHED_IO ? 4 * NT : 1];
+            if constexpr (SEQ_BATCHED_IO) {
+                static_assert(!SEQ_BATCHED_IO || NT == 4, "sixteen operands per statement");
+                x6_static_for<0, 4 * NT>([&](auto ic) __attribute__((always_inline)) {
+                    constexpr int i = decltype(ic)::value; // piece tn * 4 + g: floats tn * 32 + 8 g .. of the row
+                    eq[i] = x6_gld<32 * i>(e_), pq[i] = x6_gld<32 * i>(p_);
+                });
+                asm volatile("s_waitcnt vmcnt(0)"
+                             : "+v"(eq[0]), "+v"(eq[1]), "+v"(eq[2]), "+v"(eq[3]), "+v"(eq[4]), "+v"(eq[5]), "+v"(eq[6]), "+v"(eq[7]), "+v"(eq[8]),
+                               "+v"(eq[9]), "+v"(eq[10]), "+v"(eq[11]), "+v"(eq[12]), "+v"(eq[13]), "+v"(eq[14]), "+v"(eq[15]));
+                asm volatile("" : "+v"(pq[0]), "+v"(pq[1]), "+v"(pq[2]), "+v"(pq[3]), "+v"(pq[4]), "+v"(pq[5]), "+v"(pq[6]), "+v"(pq[7]), "+v"(pq[8]),
+                                  "+v"(pq[9]), "+v"(pq[10]), "+v"(pq[11]), "+v"(pq[12]), "+v"(pq[13]), "+v"(pq[14]), "+v"(pq[15]));
+            }
 #pragma unroll
             for (int tn = 0; tn < NT; ++tn)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const float4 e4 = *reinterpret_cast<const float4 *>(e_ + tn * 32 + 8 * g), p4 = *reinterpret_cast<const float4 *>(p_ + tn * 32 + 8 * g);
+                    float4 e4, p4;
+                    if constexpr (SEQ_BATCHED_IO) {
+                        e4 = __builtin_bit_cast(float4, eq[tn * 4 + g]), p4 = __builtin_bit_cast(float4, pq[tn * 4 + g]);
+                    } else {
+                        e4 = *reinterpret_cast<const float4 *>(e_ + tn * 32 + 8 * g), p4 = *reinterpret_cast<const float4 *>(p_ + tn * 32 + 8 * g);
+                    }
                     float4 t4 = make_float4(__fadd_rn(__fmul_rn(e4.x, a.sqrtd), p4.x), __fadd_rn(__fmul_rn(e4.y, a.sqrtd), p4.y),
                                             __fadd_rn(__fmul_rn(e4.z, a.sqrtd), p4.z), __fadd_rn(__fmul_rn(e4.w, a.sqrtd), p4.w));
                     if (!live) t4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -2907,12 +2996,26 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             }
         const float rstd = 1.0f / sqrtf(lanes_sum<32>(qs) * invn + 1e-5f);
         if constexpr (ASM_VECS) {
+            // (SEQ_BATCHED_IO) The sequence-resident launch always has an x' image (x6_launch_seq) and stores its sixteen pieces from
+            // inline asm, at immediate offsets from one base per tile, the base rebuilt HERE from scalars (the workgroup, the wave)
+            // and the lane.  (The plain form -- a test of a.Xf around each store, the address rebuilt from a pair reloaded from
+            // scratch -- compiled to a vmcnt(0) in front of every store: on gfx9 stores count in vmcnt, so each store waited for
+            // the previous one's acknowledgement, fifteen round trips per layer and wave.)  Nothing here waits for these stores:
+            // what orders them before the next layer's residual loads (load_res, of the same wave) is the explicit
+            // s_waitcnt vmcnt(0) of the empty step below, and behind the launch's last layer the one at the kernel's end.
+            char *xt = nullptr;
+            if constexpr (SEQ && SEQ_BATCHED_IO) {
+                int mt_ = (int)blockIdx.x * NW + wave; // = mtile, as a scalar
+                asm volatile("" : "+s"(mt_)); // (a value of this trip: the address is not hoisted out of the layer loop and spilled)
+                xt = reinterpret_cast<char *>(a.Xf) + ((size_t)mt_ * (4 * NT) * 64 + lane) * 16;
+            }
             vec_stream(std::integral_constant<int, 2>{}, std::integral_constant<int, V_G>{}, std::integral_constant<int, V_B>{}, x6_ic0{},
                        [&](auto gc, const float4 gg, const float4 be, const float4) __attribute__((always_inline)) {
                 constexpr int tn = decltype(gc)::value >> 2, g = decltype(gc)::value & 3;
                 const float4 o = make_float4((acc[tn][4 * g + 0] - mu) * rstd * gg.x + be.x, (acc[tn][4 * g + 1] - mu) * rstd * gg.y + be.y,
                                              (acc[tn][4 * g + 2] - mu) * rstd * gg.z + be.z, (acc[tn][4 * g + 3] - mu) * rstd * gg.w + be.w);
-                if (a.Xf) reinterpret_cast<float4 *>(a.Xf)[((size_t)(mtile * NT + tn) * 4 + g) * 64 + lane] = o;
+                if constexpr (SEQ && SEQ_BATCHED_IO) x6_gst<1024 * g>(xt + 4096 * tn, __builtin_bit_cast(x6_u32x4, o));
+                else if (a.Xf) reinterpret_cast<float4 *>(a.Xf)[((size_t)(mtile * NT + tn) * 4 + g) * 64 + lane] = o;
                 acc[tn][4 * g + 0] = o.x, acc[tn][4 * g + 1] = o.y, acc[tn][4 * g + 2] = o.z, acc[tn][4 * g + 3] = o.w;
             });
         } else {
@@ -6576,6 +6679,7 @@ extern "C" void *irs_lab_seq_stamps() { return g_seq_stamps; }
 static void x6_launch_seq(int wg_cap, const BlockX6Args &xa, hipStream_t s) {
     auto kern = k_block_x6<3, 8, false, 4, 2, true>;
     constexpr int lds = x6_seq_lds_bytes();
+    assert(xa.Xf && xa.Rf && "the sequence-resident kernel stores x' unconditionally (LayerNorm 3)");
     IRS_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
 #ifdef X6_STAMP
     BlockX6Args xs = xa; // (lab) 24 counters per wave

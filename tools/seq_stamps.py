@@ -50,6 +50,10 @@ print("workgroups %d; cycles per wave (s_memtime, 100 MHz): mean %.0f  min %.0f 
 ph = st[:, :, 8:8 + len(names)]
 acc = ph.sum(2)
 print("phases cover %.1f %% of a wave's life" % (100 * acc.mean() / tot.mean()))
+live = tot > 0  # (a wave on the idle path leaves no stamps)
+print("  %-72s %6.1f %%   (mean %.0f ticks over the live waves, p50 %.0f, max %.0f)" %
+      ("prologue: plan words, parameter vectors, embedding gather, first barrier", 100 * st[:, :, 5][live].mean() / tot[live].mean(),
+       st[:, :, 5][live].mean(), np.median(st[:, :, 5][live]), st[:, :, 5][live].max()))
 for i, nm in enumerate(names):
     print("  %-72s %6.1f %%   (mean %.0f ticks)" % (nm, 100 * ph[:, :, i].mean() / tot.mean(), ph[:, :, i].mean()))
 if st[:, :, 2].sum() > 0:  # (X6_STAMP=1 builds: the per-step stamps too)
