@@ -626,6 +626,61 @@ int irs_score_target_trace(irs_ctx *ctx, const float *dev_xrows, const int64_t *
 int irs_bind_path_trace(irs_ctx *ctx, float *dev_lp_item, float *dev_lp_target, int32_t *dev_rank_target, int32_t users, int32_t ld,
                         void *dev_scratch, size_t bytes);
 
+/* ---- guided choice: the Rec2Inf rule of the greedy path step (opt-in; replaces the Python double loop over users and steps of
+ *      the reference's get_path, main_baselines.py:93-121, and its distance cal_fv_dist, utils.py:202-206) ----------------------
+ * A context can hold one bound GUIDE: a feature table over the catalog and a candidate count k_c in [1, IRS_MAX_GUIDE_KC].
+ * While it does, a greedy path step does this for a row:
+ *   1. It walks the row's ranked list exactly as irs_path_step does, with the same admissibility test: the window seq[row, 0 ..
+ *      hep[row]], plus the bound exclusion list, plus the path under no_repeat.  The list ends at its first negative id.  The
+ *      first min(k_c, available) survivors are collected in rank order.
+ *   2. The target is t = seq[row][L-1] (1-based).  t == 0 (or t outside [1, n_item]): the row takes its first survivor, the
+ *      greedy choice.  Otherwise it takes the survivor with the smallest distance to t: walking the survivors in rank order, a
+ *      later one replaces the current best only if its distance is STRICTLY smaller, so ties go to the better rank; a NaN
+ *      distance never replaces anything and is replaced by any distance that is not a NaN (np.argsort(dists)[0]: NaN sorts
+ *      last; all NaN: the first survivor).  The target itself gets no preference beyond its distance 0 (the reference gives it
+ *      none).  A survivor whose id lies outside [1, n_item] is never looked up and counts as the farthest.
+ *   3. No survivor: IRS_ROW_NO_CANDIDATE, paths[row, step] = 0, window and hep untouched, as in irs_path_step.
+ *   4. Record, then grow or shift the window: byte for byte what irs_path_step does with its chosen item.
+ * Distances (table row i belongs to the 1-based item i: n_item + 1 rows, row 0 is never read -- the reference's fv[i]):
+ *   IRS_GUIDE_BINARY  F features, 1 <= F <= IRS_MAX_GUIDE_BITS, packed 32 to a word (feature f = bit f % 32 of word f / 32, the
+ *                     bits behind F zero); the distance is the popcount of the XOR over the ceil(F / 32) words (Hamming).
+ *   IRS_GUIDE_FLOAT   F float32 features, 1 <= F <= IRS_MAX_GUIDE_FLOATS, row stride F; the distance is the SQUARED Euclidean
+ *                     distance as ONE float32 chain, acc = fmaf(t_f - c_f, t_f - c_f, acc), f ascending from 0, acc starting at
+ *                     0 (t_f - c_f rounded to float32 once).  The square root is monotone and would only merge neighbours, so it
+ *                     is not taken.  The chain order is part of the semantics: chosen ids can be compared exactly.
+ * irs_guide_scratch_bytes: binary: the packed table, (n_item + 1) ceil(F / 32) words, rounded up to 256 bytes; float: 0 (the
+ *   table is read where it lies); 0 for invalid arguments as well.
+ * irs_bind_guide:
+ *   IRS_GUIDE_BINARY  dev_table uint8 [n_item + 1][F], nonzero = 1.  ONE launch on `stream` packs it into dev_scratch (16-byte
+ *                     aligned, >= irs_guide_scratch_bytes); the caller's table need not outlive that launch, the scratch must
+ *                     stay valid, and untouched, until the unbind.
+ *   IRS_GUIDE_FLOAT   dev_table float32 [n_item + 1][F], kept BY POINTER: the caller keeps it alive and unchanged until the
+ *                     unbind.  dev_scratch / bytes are ignored (NULL / 0).  Rows are read 16 bytes at a time where F % 4 == 0
+ *                     and the table is 16-byte aligned.
+ *   dev_table == NULL unbinds.  A second bind replaces the first.  Bind and unbind drop the captured steps of the context.
+ *   Refused before any launch: a null context, kind not one of the two, F < 1, k_c < 1, k_c > max_k, a binary scratch that is
+ *   NULL, too small or misaligned -> IRS_E_INVALID; k_c > IRS_MAX_GUIDE_KC, F beyond the limits above, world != 1 ->
+ *   IRS_E_UNSUPPORTED.
+ * While bound:
+ *   irs_path_step, irs_generate_paths (stream launches and the captured step alike) and irs_generate_paths_until apply the rule;
+ *     sample != 0 -> IRS_E_UNSUPPORTED (the rule is deterministic), k < k_c -> IRS_E_INVALID, before any launch;
+ *   irs_beam_step[_until], irs_beam_search[_until] and the two _sharded loops return IRS_E_UNSUPPORTED;
+ *   exclusions and no_repeat compose through the shared admissibility test; with exact candidates bound as well
+ *     (irs_bind_survivor_scratch) the loops ask the survivor pass for want = k_c, so a row with fewer than k_c admissible
+ *     entries in its list is repaired to the exact best k_c admissible items (size the scratch for want = k_c);
+ *   a bound path trace records the guided choice: lp_item is the chosen item's, found in the step's list as always;
+ *   the route where one workgroup ranks and steps a row is not taken (as under exclusions).
+ * No atomics: two identical calls give identical bytes.  With nothing bound every entry point launches exactly what it
+ * launched before. */
+#define IRS_GUIDE_BINARY 1
+#define IRS_GUIDE_FLOAT 2
+#define IRS_MAX_GUIDE_KC 32       /* the survivor pass's `want` limit */
+#define IRS_MAX_GUIDE_BITS 1024   /* features of a binary guide */
+#define IRS_MAX_GUIDE_FLOATS 512  /* features of a float guide */
+size_t irs_guide_scratch_bytes(const irs_ctx *ctx, int32_t kind, int32_t F);
+int irs_bind_guide(irs_ctx *ctx, int32_t kind, const void *dev_table, int32_t F, int32_t k_c, void *dev_scratch, size_t bytes,
+                   void *stream);
+
 /* ---- multi-GPU: the exchange steps and the sharded search loops below the ABI (section 8 row B2's
  *      `allgather_merge(ctx, comm, ...)`).  One process per GPU; rank r holds item rows [item_lo, item_hi) (irs_shard).
  * A communicator is either RCCL (librccl.so is dlopen()ed on first use: ncclCommInitRank over a 128-byte unique id the

@@ -19,6 +19,8 @@ IRS_SWEEP_BF16, IRS_SWEEP_F32, IRS_SWEEP_EXHAUSTIVE = 0, 1, 2
 IRS_ROW_FALLBACK, IRS_ROW_NO_CANDIDATE, IRS_ROW_FEWER_THAN_K, IRS_ROW_RESCUED = 1, 2, 4, 8
 IRS_GEMM_F32, IRS_GEMM_X6, IRS_GEMM_H3 = 0, 1, 2
 IRS_BEAM_STOP_ALL, IRS_BEAM_STOP_BEST = 0, 1
+IRS_GUIDE_BINARY, IRS_GUIDE_FLOAT = 1, 2  # irs_bind_guide
+IRS_MAX_GUIDE_KC, IRS_MAX_GUIDE_BITS, IRS_MAX_GUIDE_FLOATS = 32, 1024, 512
 # irs_decoder_route_last (include/irs_hip.h): its field order and the names of the enum-valued fields, in the order of
 # decoder.hip's enum class DecPlan / DecEmbed / DecFam (tests/test_decoder_routes.py checks that they agree)
 ROUTE_FIELDS = ("rows_only", "small_plan", "plan", "embed", "layer", "tail", "frag", "seq", "kv_planes", "att_fused", "kv_only",
@@ -106,6 +108,8 @@ SIGNATURES = {
     "irs_score_target_trace": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p]),
     "irs_bind_path_trace": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t]),
+    "irs_guide_scratch_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),
+    "irs_bind_guide": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "irs_comm_unique_id": (c_int32, [c_void_p]),
     "irs_comm_init_rccl": (c_int32, [POINTER(c_void_p), c_void_p, c_int32, c_int32]),
     "irs_comm_init_callbacks": (c_int32, [POINTER(c_void_p), c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -671,6 +671,58 @@ extern "C" int irs_bind_exclusions(irs_ctx *ctx, const int64_t *excl_ids0, int32
     return IRS_OK;
 }
 
+// ------------------------------------------------------------------ bound guide (irs_bind_guide; guide.hip)
+extern "C" size_t irs_guide_scratch_bytes(const irs_ctx *ctx, int32_t kind, int32_t F) {
+    if (!ctx || kind != IRS_GUIDE_BINARY || F < 1 || F > IRS_MAX_GUIDE_BITS) return 0; // (a float table is read where it lies)
+    return irs_guide_scratch(ctx->dims.n_item, kind, F);
+}
+
+extern "C" int irs_bind_guide(irs_ctx *ctx, int32_t kind, const void *table, int32_t F, int32_t k_c, void *scratch, size_t bytes,
+                              void *stream) {
+    if (!ctx) return IRS_E_INVALID;
+    if (!table) { // unbind
+        if (ctx->guide_on) irs_drop_graphs(ctx);
+        ctx->guide_on = 0, ctx->guide = irs_guide{};
+        return IRS_OK;
+    }
+    if (kind != IRS_GUIDE_BINARY && kind != IRS_GUIDE_FLOAT)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_guide: kind %d (IRS_GUIDE_BINARY or IRS_GUIDE_FLOAT)", kind);
+    if (F < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_guide: F must be >= 1");
+    if (k_c < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_guide: k_c must be >= 1");
+    if (k_c > IRS_MAX_GUIDE_KC) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide: k_c %d > %d", k_c, IRS_MAX_GUIDE_KC);
+    const int f_max = kind == IRS_GUIDE_BINARY ? IRS_MAX_GUIDE_BITS : IRS_MAX_GUIDE_FLOATS;
+    if (F > f_max) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide: F %d > %d (%s)", F, f_max, kind == IRS_GUIDE_BINARY ? "bits" : "floats");
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide needs the whole catalog on one device");
+    if (k_c > ctx->dims.max_k) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_guide: k_c %d > max_k %d", k_c, ctx->dims.max_k);
+    const int64_t rows = ctx->dims.n_item + 1;
+    irs_guide g{table, rows, F, 0, k_c, kind};
+    if (kind == IRS_GUIDE_BINARY) {
+        const size_t need = irs_guide_scratch(ctx->dims.n_item, kind, F);
+        if (!scratch || bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_guide: scratch too small: %zu < %zu", scratch ? bytes : (size_t)0, need);
+        if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_guide: scratch must be 16-byte aligned");
+        g.words = (F + 31) / 32, g.table = scratch;
+        const int rc = irs_launch_guide_pack(ctx, (const uint8_t *)table, rows, F, (uint32_t *)scratch, (hipStream_t)stream);
+        if (rc) return rc;
+    } else if (((uintptr_t)table) & 3) {
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_guide: a float table must be 4-byte aligned");
+    }
+    ctx->guide = g, ctx->guide_on = 1;
+    irs_drop_graphs(ctx); // (a captured step holds the guided kernel with this table, or the plain one)
+    return IRS_OK;
+}
+// the greedy entry points while a guide is bound: the rule is deterministic, and it chooses among k_c candidates of the list
+static int check_guide(irs_ctx *ctx, const char *fn, int k, int sample) {
+    if (!ctx->guide_on) return IRS_OK;
+    if (sample) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a guide is bound (irs_bind_guide): the guided choice is deterministic, sample must be 0", fn);
+    if (k < ctx->guide.k_c) IRS_FAIL(ctx, IRS_E_INVALID, "%s: a guide is bound (irs_bind_guide): k=%d < k_c=%d", fn, k, ctx->guide.k_c);
+    return IRS_OK;
+}
+// the beam steps and loops have no guided form: they refuse while a guide is bound
+static int refuse_guide(irs_ctx *ctx, const char *fn) {
+    if (ctx->guide_on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a guide is bound (irs_bind_guide): greedy loops only", fn);
+    return IRS_OK;
+}
+
 extern "C" int irs_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int32_t B, const float *val, const int64_t *ids0,
                              int32_t k, int32_t step, float *paths, int32_t path_ld, int32_t sample, int32_t sample_k,
                              uint64_t seed, int32_t *status, void *stream) {
@@ -679,8 +731,9 @@ extern "C" int irs_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int32_t B
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_path_step: bad arguments");
     if (sample && (sample_k < 1 || sample_k > IRS_MAX_SAMPLE_K))
         IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_path_step: sample_k must be in [1, %d]", IRS_MAX_SAMPLE_K);
-    const int rc = check_excl(ctx, "irs_path_step", B, step);
+    int rc = check_excl(ctx, "irs_path_step", B, step);
     if (rc) return rc;
+    if ((rc = check_guide(ctx, "irs_path_step", k, sample))) return rc;
     const irs_path_args pa{seq, hep, ctx->dims.max_len, paths, path_ld, sample, sample_k, seed, status, nullptr, step, nullptr, 1,
                            excl_args(ctx, 1, nullptr, paths, path_ld, 1, nullptr, step)};
     return irs_launch_path_step(ctx, pa, B, val, ids0, k, (hipStream_t)stream);
@@ -702,13 +755,14 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
     // small shard, few rows: the workgroup that ranks a row's candidates also takes the row's path step
     // (not while exact candidates are bound: the survivor pass goes between the ranking and the step; nor while exclusions are
     //  bound: only the separate step kernel has the form that tests them; nor while a path trace is bound: its sweep reads the
-    //  window before the step, its record kernel the lists after it)
-    if (merged && !ctx->surv_scratch && !ctx->excl_on && !ctx->tr_on && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k))
+    //  window before the step, its record kernel the lists after it; nor while a guide is bound: the guided step is a kernel of its own)
+    if (merged && !ctx->surv_scratch && !ctx->excl_on && !ctx->tr_on && !ctx->guide_on && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k))
         return irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, &pa);
     if ((rc = irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, nullptr, nullptr, carry)))
         return rc;
     if (ctx->surv_scratch) {
-        const irs_surv_args sa{ctx->xrows, pa.seq, pa.hep, B, 1, k, pa.sample ? pa.sample_k : 1, ctx->surv_rows, nullptr, surv_fin, nullptr,
+        const int want = ctx->guide_on ? ctx->guide.k_c : (pa.sample ? pa.sample_k : 1); // (a guided step chooses among k_c)
+        const irs_surv_args sa{ctx->xrows, pa.seq, pa.hep, B, 1, k, want, ctx->surv_rows, nullptr, surv_fin, nullptr,
                                ctx->top_val, ctx->top_ids, pa.status, nullptr, pa.ex};
         if ((rc = irs_launch_survivors(ctx, sa, ctx->surv_scratch, s))) return rc;
     }
@@ -863,8 +917,11 @@ int irs_check_beam_args(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W
 // the common opening of the four single-device search entry points.  W == 0: a greedy loop over B rows; else a beam search over
 // B * W rows.  ptrs_ok: none of the call's required pointers is null
 static int check_search(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W, int P, int k, int sweep, int sample, int sample_k) {
-    int rc = irs_ready_filter(ctx, sweep);
+    if (!ctx) return IRS_E_INVALID;
+    // (a bound guide is looked at first, like the bindings at the top of the sharded loops: what it refuses needs no weights)
+    int rc = W ? refuse_guide(ctx, fn) : check_guide(ctx, fn, k, sample);
     if (rc) return rc;
+    if ((rc = irs_ready_filter(ctx, sweep))) return rc;
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s needs the whole catalog on one device", fn);
     if (W) {
         if ((rc = refuse_trace(ctx, fn))) return rc;
@@ -880,7 +937,7 @@ static int check_search(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W
     if ((rc = irs_check_k(ctx, fn, k, 1, sweep, sample, sample_k))) return rc;
     if ((rc = check_excl(ctx, fn, B, P))) return rc;
     if (ctx->surv_scratch) { // exact candidates: the bound scratch must serve this call's rows
-        const int rows = W ? B * W : B, want = W ? W : (sample ? sample_k : 1);
+        const int rows = W ? B * W : B, want = W ? W : (ctx->guide_on ? ctx->guide.k_c : (sample ? sample_k : 1));
         if (want > k) IRS_FAIL(ctx, IRS_E_INVALID, "%s: exact candidates need k >= %d", fn, want);
         const size_t need = irs_surv_scratch(ctx, rows, want);
         if (ctx->surv_bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bound survivor scratch too small: %zu < %zu", fn, ctx->surv_bytes, need);
@@ -1026,6 +1083,7 @@ extern "C" int irs_beam_step(irs_ctx *ctx, const int64_t *seq_in, const int32_t 
     if (W > 1 && (!lse_max || !lse_sum)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step: W > 1 needs the row log-sum-exp");
     int rc = refuse_trace(ctx, "irs_beam_step");
     if (rc) return rc;
+    if ((rc = refuse_guide(ctx, "irs_beam_step"))) return rc;
     if ((rc = check_excl(ctx, "irs_beam_step", B, P))) return rc;
     const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k,
                              excl_args(ctx, W, nullptr, paths_in, P, 0, nullptr, step)};
@@ -1104,6 +1162,7 @@ extern "C" int irs_beam_step_until(irs_ctx *ctx, const int64_t *seq_in, const in
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_until: stop_rule %d (IRS_BEAM_STOP_ALL or IRS_BEAM_STOP_BEST)", stop_rule);
     int rc = refuse_trace(ctx, "irs_beam_step_until");
     if (rc) return rc;
+    if ((rc = refuse_guide(ctx, "irs_beam_step_until"))) return rc;
     if ((rc = check_excl(ctx, "irs_beam_step_until", B, P))) return rc;
     const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k,
                              excl_args(ctx, W, nullptr, paths_in, P, 0, nullptr, step)};

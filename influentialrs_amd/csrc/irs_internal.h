@@ -152,6 +152,13 @@ struct irs_trace_rec { // what the record kernel takes: a step's rows (the scrat
     int32_t *rank_target;
     int ld;
 };
+// ---- a bound guide as the guided path step takes it (irs_bind_guide; guide.hip).  table: the packed words [rows][words] of a
+// binary guide (in the caller's scratch) or the caller's float32 [rows][F] table, rows = n_item + 1, row i = 1-based item i.
+struct irs_guide {
+    const void *table;
+    int64_t rows;
+    int F, words, k_c, kind;
+};
 struct irs_eval_batch_args { // irs_build_eval_batch's arguments as the kernel takes them
     const int64_t *items, *offsets;
     int B, L, raw_len, gap_len;
@@ -285,6 +292,11 @@ struct irs_ctx {
     int32_t *tr_rank;
     int tr_users, tr_ld;
     void *tr_scratch;
+
+    // bound guide (irs_bind_guide): the Rec2Inf choice rule of the greedy path step -- among the first k_c admissible candidates,
+    // the one nearest to the target in the bound feature table; the beam and the sharded entry points then refuse
+    int guide_on;
+    irs_guide guide;
 
     // profiling
     int prof_family;
@@ -439,6 +451,13 @@ int irs_launch_beam_retire(irs_ctx *ctx, const int32_t *dst, int B, int W, int P
                            const irs_beam_out &res, hipStream_t s);
 
 int irs_launch_build_eval_batch(irs_ctx *ctx, const irs_eval_batch_args &a, hipStream_t s);
+
+// ---- guide.hip ---- (the Rec2Inf choice rule; arguments already validated)
+size_t irs_guide_scratch(int64_t n_item, int kind, int F);
+int irs_launch_guide_pack(irs_ctx *ctx, const uint8_t *table, int64_t rows, int F, uint32_t *packed, hipStream_t s);
+// the path step while a guide is bound (irs_launch_path_step chooses it)
+int irs_launch_path_step_guided(irs_ctx *ctx, const irs_path_args &pa, int B, const float *val, const int64_t *ids0, int k,
+                                hipStream_t s);
 
 // ---- small device helpers ----
 #ifdef __HIPCC__

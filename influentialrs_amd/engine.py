@@ -546,6 +546,65 @@ class Engine:
             scratch.record_stream(stream)
             self.unbind_path_trace()
 
+    # ------------------------------------------------------------------ bound guide (irs_bind_guide)
+    def guide_scratch_bytes(self, kind: int, F: int) -> int:
+        """irs_guide_scratch_bytes: the packed table of a binary guide; 0 for a float guide, which is read where it lies."""
+        if kind == _lib.IRS_GUIDE_FLOAT and 1 <= F <= _lib.IRS_MAX_GUIDE_FLOATS:
+            return 0
+        n = int(self.lib.irs_guide_scratch_bytes(self.h, kind, F))
+        if n == 0:
+            raise IrsError(f"guide_scratch_bytes: kind={kind} / F={F} (binary: F in [1, {_lib.IRS_MAX_GUIDE_BITS}], float: F in "
+                           f"[1, {_lib.IRS_MAX_GUIDE_FLOATS}])")
+        return n
+
+    def bind_guide(self, table: torch.Tensor, k_c: int = 5):
+        """irs_bind_guide: table [n_item + 1, F], row i = the features of the 1-based item i (row 0 is never read).  bool / uint8 /
+        any integer dtype: a binary guide (nonzero = 1, Hamming distance); floating: a float guide (converted to contiguous
+        float32, squared Euclidean distance).  Until unbind_guide the greedy step and loops choose, among the first k_c
+        admissible candidates, the one nearest to the target; the beam and the sharded loops refuse.  The engine holds the
+        table and the scratch until unbound."""
+        if not torch.is_tensor(table) or table.dim() != 2 or table.shape[0] != self.n_item + 1 or table.shape[1] < 1:
+            raise IrsError(f"bind_guide: table must be [n_item + 1 = {self.n_item + 1}, F >= 1], got "
+                           f"{tuple(table.shape) if torch.is_tensor(table) else type(table)}")
+        if table.device != self.device:
+            raise IrsError(f"bind_guide: table on {table.device}, engine on {self.device}")
+        F = table.shape[1]
+        if table.dtype.is_floating_point:
+            kind, held, scratch = _lib.IRS_GUIDE_FLOAT, table.to(torch.float32).contiguous(), None
+        elif table.dtype.is_complex:
+            raise IrsError("bind_guide: a complex table has no distance here")
+        else:
+            kind, held = _lib.IRS_GUIDE_BINARY, table.ne(0).to(torch.uint8).contiguous()
+            if F > _lib.IRS_MAX_GUIDE_BITS:
+                raise IrsError(f"bind_guide: F={F} > {_lib.IRS_MAX_GUIDE_BITS} binary features")
+            scratch = torch.empty(self.guide_scratch_bytes(kind, F), dtype=torch.uint8, device=self.device)
+        self._call(self.lib.irs_bind_guide, kind, _ptr(held), F, k_c, _ptr(scratch), scratch.numel() if scratch is not None else 0)
+        self._guide_held = (held, scratch)
+        return held, scratch
+
+    def unbind_guide(self):
+        self._call(self.lib.irs_bind_guide, 0, None, 0, 0, None, 0)
+        self._guide_held = None
+
+    @contextlib.contextmanager
+    def _guide(self, table: Optional[torch.Tensor], k_c: int, graph: bool = False):
+        """While a search call runs with guide=...: the table bound before and unbound after, like _exclusions (and with its
+        cost: bind and unbind drop the context's captured steps)."""
+        if table is None:
+            yield
+            return
+        held = self.bind_guide(table, k_c)
+        try:
+            yield
+        finally:
+            stream = torch.cuda.current_stream(self.device)
+            if graph:
+                stream.synchronize()
+            for t in held:  # (the loops only enqueue: table and scratch must outlive the work on the stream)
+                if t is not None:
+                    t.record_stream(stream)
+            self.unbind_guide()
+
     # ------------------------------------------------------------------ path search
     def path_step(self, seqs, hep, val, ids0, step: int, paths, status, sample=False, sample_k=3, seed=0):
         seqs = self._inplace(seqs, torch.int64, "path_step: seqs")
@@ -563,7 +622,8 @@ class Engine:
                        k: int = 100, sweep: int = IRS_SWEEP_BF16, sample=False, sample_k=3, seed=0,
                        use_graph: bool = False, paths: Optional[torch.Tensor] = None,
                        status: Optional[torch.Tensor] = None, exact_candidates: bool = False,
-                       exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False):
+                       exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
+                       guide: Optional[torch.Tensor] = None, guide_k: int = 5):
         """Runs the whole search loop on the device.  `seqs` and `hep` are the
         working window state and are modified in place.  exact_candidates: a row whose k candidates are hidden by its window
         chooses among the exact best admissible items of the catalog instead (IRS_ROW_RESCUED; the result of k = n_item).
@@ -572,7 +632,9 @@ class Engine:
         window + the user's list (+ its own path so far); the same holds in the three other loops.
         trace: a path trace is bound for this call (irs_bind_path_trace) and the return value grows a third member, (lp_item,
         lp_target float32 [B, max_path_len], rank_target int32 [B, max_path_len]): all columns are written; cut them where paths
-        is cut."""
+        is cut.
+        guide ([n_item + 1, F], see bind_guide) / guide_k: a guide is bound for this call (irs_bind_guide): a step takes, among
+        its first guide_k admissible candidates, the one nearest to the target seqs[b, L - 1] (the Rec2Inf rule); greedy only."""
         seqs = self._inplace(seqs, torch.int64, "generate_paths: seqs")
         hep = self._inplace(hep, torch.int32, "generate_paths: hep")
         if users is not None:
@@ -588,8 +650,9 @@ class Engine:
         status = self._inplace(status, torch.int32, "generate_paths: status")
         if paths.shape != (B, max_path_len):
             raise IrsError("generate_paths: paths must be [B, max_path_len]")
-        with self._exact_candidates(exact_candidates, B, sample_k if sample else 1, bool(use_graph)), \
-                self._exclusions(exclude, no_repeat, B, bool(use_graph)), \
+        want = guide_k if guide is not None else (sample_k if sample else 1)
+        with self._exact_candidates(exact_candidates, B, want, bool(use_graph)), \
+                self._exclusions(exclude, no_repeat, B, bool(use_graph)), self._guide(guide, guide_k, bool(use_graph)), \
                 self._path_trace(trace, B, max_path_len, bool(use_graph)) as traced:
             self._call(self.lib.irs_generate_paths, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                     int(sample), sample_k, seed, int(use_graph), _ptr(paths), _ptr(status))
@@ -599,11 +662,13 @@ class Engine:
                              k: int = 100, sweep: int = IRS_SWEEP_BF16, sample=False, sample_k=3, seed=0,
                              check_every: int = 1, paths: Optional[torch.Tensor] = None,
                              status: Optional[torch.Tensor] = None, exact_candidates: bool = False,
-                             exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False):
+                             exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
+                             guide: Optional[torch.Tensor] = None, guide_k: int = 5):
         """generate_paths that stops a user at its target (seqs[b, L - 1]) and the call when nobody is left
         (irs_generate_paths_until): returns (paths, status, steps_run, row_steps).  Paths are zero behind the target.
         `seqs` and `hep` are working state: modified, and unspecified afterwards.  One host read of 4 bytes per check.
-        trace: as in generate_paths, a fifth member (lp_item, lp_target, rank_target), exactly zero behind a user's arrival."""
+        trace: as in generate_paths, a fifth member (lp_item, lp_target, rank_target), exactly zero behind a user's arrival.
+        guide / guide_k: as in generate_paths -- with the Rec2Inf rule this loop is the reference's get_path."""
         seqs = self._inplace(seqs, torch.int64, "generate_paths_until: seqs")
         hep = self._inplace(hep, torch.int32, "generate_paths_until: hep")
         if users is not None:
@@ -620,8 +685,9 @@ class Engine:
         if paths.shape != (B, max_path_len):
             raise IrsError("generate_paths_until: paths must be [B, max_path_len]")
         stats = (ctypes.c_int64 * 2)(0, 0)
-        with self._exact_candidates(exact_candidates, B, sample_k if sample else 1), self._exclusions(exclude, no_repeat, B), \
-                self._path_trace(trace, B, max_path_len) as traced:
+        want = guide_k if guide is not None else (sample_k if sample else 1)
+        with self._exact_candidates(exact_candidates, B, want), self._exclusions(exclude, no_repeat, B), \
+                self._guide(guide, guide_k), self._path_trace(trace, B, max_path_len) as traced:
             self._call(self.lib.irs_generate_paths_until, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                           int(sample), sample_k, seed, check_every, _ptr(paths), _ptr(status), stats)
         out = (paths, status, int(stats[0]), int(stats[1]))

@@ -4,3 +4,4 @@
 (evaluator_pipeline.py:17-18), `from model.layers import PositionalEncoding,
 get_item_index` (influentialRS.py:19) keep working with this package in place
 of the reference's `model/` directory."""
+from .rec2inf import Rec2Inf  # noqa: E402,F401  (the paper's Rec2Inf framework over SampleNet; no reference module of that name)

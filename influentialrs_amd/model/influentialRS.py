@@ -181,16 +181,19 @@ def _takes_exact_candidates(fn):
     parameter list stays what it was (it ends with beam_stop): positional callers and code that reads the signature are not
     disturbed.  The search reads the switch from self._exact_candidates for the time of the call.
     exclude=None and no_repeat=False (bound exclusions) are taken the same way, into self._exclude / self._no_repeat, and
-    trace=False (the path trace) into self._trace."""
+    trace=False (the path trace) into self._trace, guide=None and guide_k=5 (the guided choice) into self._guide / self._guide_k."""
     @functools.wraps(fn)
-    def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, trace=False, **kw):
+    def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None, guide_k=5, **kw):
         prev = (getattr(self, "_exact_candidates", False), getattr(self, "_exclude", None), getattr(self, "_no_repeat", False),
                 getattr(self, "_trace", False))
+        prev_guide = (getattr(self, "_guide", None), getattr(self, "_guide_k", 5))
         self._exact_candidates, self._exclude, self._no_repeat, self._trace = bool(exact_candidates), exclude, bool(no_repeat), bool(trace)
+        self._guide, self._guide_k = guide, int(guide_k)
         try:
             return fn(self, *args, **kw)
         finally:
             self._exact_candidates, self._exclude, self._no_repeat, self._trace = prev
+            self._guide, self._guide_k = prev_guide
     return call
 
 
@@ -400,10 +403,27 @@ class IRSNN(nn.Module):
         at every step and before it chooses, the log-probability and the rank of the target and the log-probability of the item
         it then chose, under this model's softmax over the whole catalog (irs_bind_path_trace).  The return value is unchanged;
         self.last_trace is path_trace_summary's dict: lp_item, lp_target, rank_target [B, max_path_len] cut after the arrival,
-        n_steps [B], ioi, ior, avg_lp_item."""
+        n_steps [B], ioi, ior, avg_lp_item.
+        guide=None, guide_k=5 (extension, keyword only, taken the same way; greedy search on one device, off by default): the
+        Rec2Inf choice on IRN's own ranking (irs_bind_guide).  guide: a [n_item + 1, F] feature table on the net's device, row i
+        = the 1-based item i; integer / bool: binary features, Hamming distance; floating: squared Euclidean distance.  Every
+        step then offers, among its first guide_k admissible top-100 candidates, the one nearest to the user's target (ties: the
+        better rank) instead of the first.  model/rec2inf.py is the same rule on the plain recommender."""
         exact_candidates = getattr(self, "_exact_candidates", False)
         exclude, no_repeat = getattr(self, "_exclude", None), getattr(self, "_no_repeat", False)
         trace = getattr(self, "_trace", False)
+        guide, guide_k = getattr(self, "_guide", None), getattr(self, "_guide_k", 5)
+        if guide is not None:
+            if beam_width > 1:
+                raise ValueError("guide is not built for beam search (beam_width > 1): use beam_width=1 (the guided choice is a "
+                                 "rule of the greedy step)")
+            if sample:
+                raise ValueError("guide is not built for the sampled search: the guided choice is deterministic, use sample=False")
+            if self.net._hip.world != 1:
+                raise ValueError("guide is not built for an item-sharded catalog: irs_bind_guide needs the whole catalog on one "
+                                 "device")
+            if not 1 <= guide_k <= 32:
+                raise ValueError(f"guide_k={guide_k}: the guided step chooses among 1 to 32 candidates")
         if trace and beam_width > 1:
             raise ValueError("trace is not built for beam search (beam_width > 1): no trace is carried through beam state")
         if trace and self.net._hip.world != 1:
@@ -436,6 +456,7 @@ class IRSNN(nn.Module):
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if sample else 0
         ids0 = exclusion_ids0(exclude, no_repeat, seqs, L - (gap_len + 1) - 1, dev)
         excl = dict(exclude=ids0, no_repeat=no_repeat) if (ids0 is not None or no_repeat) else {}
+        guided = dict(guide=guide, guide_k=guide_k) if guide is not None else {}
         if beam_width > 1:
             paths_t, status = self._beam_paths(work, users, max_path_len, gap_len, beam_width, beam_stop, exact_candidates, excl)
         elif stop_at_target:
@@ -446,12 +467,13 @@ class IRSNN(nn.Module):
             paths_t, status, _, _, *traced = eng.generate_paths_until(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
                                                                       sample=sample, sample_k=sample_k, seed=seed,
                                                                       check_every=STOP_CHECK_EVERY,
-                                                                      exact_candidates=exact_candidates, trace=trace, **excl)
+                                                                      exact_candidates=exact_candidates, trace=trace, **excl,
+                                                                      **guided)
         elif hip.world == 1:
             eng = hip.get(B, B)
             paths_t, status, *traced = eng.generate_paths(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
                                                           sample=sample, sample_k=sample_k, seed=seed, use_graph=False,
-                                                          exact_candidates=exact_candidates, trace=trace, **excl)
+                                                          exact_candidates=exact_candidates, trace=trace, **excl, **guided)
         else:  # item-sharded: irs_generate_paths_sharded (decode, row all-gather, shard sweep, key all-to-all, merge, path
             # step per search step, below the C ABI on one stream)
             eng = hip.get(B, B * hip.world)
