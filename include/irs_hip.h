@@ -74,6 +74,8 @@ extern "C" {
 #define IRS_ROW_FEWER_THAN_K 4 /* catalog shard has fewer than k items; tail filled with (-inf, -1) */
 #define IRS_ROW_RESCUED 8      /* the window hid the row's top-k list; irs_topk_ensure_survivors replaced it by the exact
                                   best items outside the window */
+#define IRS_ROW_OFFERED 16     /* an arrival rule fired for the row (irs_set_arrival_rule): its list was rewritten to the
+                                  target alone */
 
 #define IRS_MAX_SAMPLE_K 8 /* sampled path steps draw among at most this many survivors (reference default: 3);
                               larger sample_k -> IRS_E_UNSUPPORTED */
@@ -680,6 +682,56 @@ int irs_bind_path_trace(irs_ctx *ctx, float *dev_lp_item, float *dev_lp_target, 
 size_t irs_guide_scratch_bytes(const irs_ctx *ctx, int32_t kind, int32_t F);
 int irs_bind_guide(irs_ctx *ctx, int32_t kind, const void *dev_table, int32_t F, int32_t k_c, void *dev_scratch, size_t bytes,
                    void *stream);
+
+/* ---- arrival rule: offer the target once its rank or probability allows (opt-in; a deployed recommender shows a slate, so a
+ *      persuasion path has done its work once the target stands among the best items the window leaves, not only when it is the
+ *      best of them) --------------------------------------------------------------------------------------------------------------
+ * A context can hold one ARRIVAL RULE, irs_set_arrival_rule(ctx, rank_max, lp_min):
+ *   rank_max >= 1 turns the rank clause on, rank_max == 0 turns it off; rank_max < 0 -> IRS_E_INVALID.
+ *   lp_min <= 0 turns the probability clause on (-inf included: it always holds); lp_min > 0 or NaN turns it off.
+ *   Both clauses off clears the rule.  Setting a rule on a context with world != 1 -> IRS_E_UNSUPPORTED.
+ *   Setting, changing or clearing the rule drops the captured steps; the rule is part of a captured step's key.
+ * The rule reads what the path trace records and nothing else: while a rule is set, irs_generate_paths (stream launches and the
+ * captured step alike) and irs_generate_paths_until need a bound path trace (irs_bind_path_trace) and return IRS_E_STATE with a
+ * message, before any launch, without one.  irs_beam_search[_until] and the two _sharded loops return IRS_E_UNSUPPORTED while a
+ * rule is set (they refuse a bound trace in any case).
+ * For a live row of a step, behind the top-k, the survivor pass and the trace sweep and BEFORE the step chooses, let
+ *   t  = seq[row][L-1],
+ *   rk = the row's rank_target of this step (the trace's: the rank among what the window leaves),
+ *   lp = rk ? (float)((double)ts - ((double)max + log((double)sumexp))) : 0 -- the very expression the trace stores as
+ *        lp_target, so that the decision can be replayed from the recorded arrays alone.
+ * The rule FIRES when rk != 0, the target is admissible under the step's own test, and at least one clause holds:
+ *   the rank clause is on and rk <= rank_max, or the probability clause is on and lp >= lp_min (a NaN lp never fires).
+ * The target is admissible when it lies in [1, n_item], is not in the window seq[row][0 .. hep[row]] (a window slot behind hep
+ * does not count), is not in the bound exclusion list of the row's user (looked up through the until loop's compaction map) and,
+ * under no_repeat, is not in the row's path so far.
+ * A row that fires has its candidate list rewritten: entry 0 becomes (ts, t - 1), entry 1 becomes (-inf, -1) when k > 1, and
+ * IRS_ROW_OFFERED is OR-ed into the row's status word.  A row that does not fire is not written; a finished row of the until loop
+ * (still stepped until the next compaction) is skipped.  Nothing else changes: the unchanged path step -- greedy, sampled or
+ * guided -- then chooses the target, its only survivor; the trace record finds the target in entry 0, so at a fired step lp_item
+ * equals lp_target bit for bit; irs_generate_paths_until sees the target chosen and retires the user; irs_generate_paths
+ * searches on behind the arrival, as the reference does.
+ * The rank is the trace's.  A rank among what a bound exclusion list and no_repeat ALSO leave is out of scope here: it needs a
+ * second count in the sweep and is the next lever.
+ * irs_arrival_offer is the kernel alone, on the outputs of irs_score_target_trace:
+ *  dev_seq int64 [M, L], dev_hep int32 [M]; dev_max / dev_sumexp / dev_target_score float [M], dev_rank int32 [M] in
+ *  dev_fin int32 [M] (may be NULL): rows with fin != 0 are skipped
+ *  dev_val float [M, k] / dev_ids0 int64 [M, k] in / out: the rows' ranked lists
+ *  rank_max, lp_min: as in irs_set_arrival_rule; both clauses off -> IRS_E_INVALID
+ *  dev_paths float [M or users, path_ld] (may be NULL), step: under a bound no_repeat the path entries [0, step) of the row's user
+ *            are inadmissible, as in irs_path_step; no_repeat bound and dev_paths NULL -> IRS_E_INVALID
+ *  dev_row_map int32 [M] (may be NULL: the identity): row -> bound user, for the exclusion list and the path row; its values
+ *            must lie in [0, users bound)
+ *  dev_status int32 [M] in / out: IRS_ROW_OFFERED is OR-ed in
+ * It honours bound exclusions as irs_path_step does.  Null pointers, M < 1, k outside [1, max_k], rank_max < 0, step < 0 or
+ * beyond path_ld, M above the bound users -> IRS_E_INVALID; world != 1 -> IRS_E_UNSUPPORTED; all before any launch.
+ * One wave per row, no LDS, no atomics: two identical calls give identical bytes.  With no rule set every entry point launches
+ * exactly what it launched before. */
+int irs_set_arrival_rule(irs_ctx *ctx, int32_t rank_max, float lp_min);
+int irs_arrival_offer(irs_ctx *ctx, const int64_t *dev_seq, const int32_t *dev_hep, int32_t M, const float *dev_max,
+                      const float *dev_sumexp, const float *dev_target_score, const int32_t *dev_rank, const int32_t *dev_fin,
+                      float *dev_val, int64_t *dev_ids0, int32_t k, int32_t rank_max, float lp_min, const float *dev_paths,
+                      int32_t path_ld, int32_t step, const int32_t *dev_row_map, int32_t *dev_status, void *stream);
 
 /* ---- multi-GPU: the exchange steps and the sharded search loops below the ABI (section 8 row B2's
  *      `allgather_merge(ctx, comm, ...)`).  One process per GPU; rank r holds item rows [item_lo, item_hi) (irs_shard).

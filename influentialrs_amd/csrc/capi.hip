@@ -771,6 +771,10 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
         irs_trace_layout(ctx->tr_scratch, ctx->tr_users, &tr);
         if ((rc = irs_launch_target_trace(ctx, ctx->xrows, pa.seq, pa.hep, B, tr, tr.mx, tr.sm, tr.ts, tr.rank, s))) return rc;
     }
+    // arrival rule: a row whose target stands well enough is offered the target alone (the entry points have seen to tr_on)
+    if (ctx->arr_on && (rc = irs_launch_arrival_offer(ctx, pa.seq, pa.hep, B, tr.mx, tr.sm, tr.ts, tr.rank, surv_fin, ctx->top_val,
+                                                      ctx->top_ids, k, ctx->arr_rank, ctx->arr_lp, pa.status, pa.ex, s)))
+        return rc;
     if ((rc = irs_launch_path_step(ctx, pa, B, ctx->top_val, ctx->top_ids, k, s))) return rc;
     if (ctx->tr_on) { // (the step index is still this step's: the merged loop publishes the next one in its second word)
         const irs_trace_rec rec{tr.mx, tr.sm, tr.ts, tr.rank, ctx->tr_item, ctx->tr_target, ctx->tr_rank, ctx->tr_ld};
@@ -867,6 +871,52 @@ static int refuse_trace(irs_ctx *ctx, const char *fn) {
     return IRS_OK;
 }
 
+// ------------------------------------------------------------------ arrival rule (irs_set_arrival_rule; path.hip: k_arrival_offer)
+extern "C" int irs_set_arrival_rule(irs_ctx *ctx, int32_t rank_max, float lp_min) {
+    if (!ctx) return IRS_E_INVALID;
+    if (rank_max < 0) IRS_FAIL(ctx, IRS_E_INVALID, "irs_set_arrival_rule: rank_max must be >= 0 (0: the rank clause is off)");
+    const int lp_on = irs_arrival_lp_on(lp_min) ? 1 : 0;
+    const int on = (rank_max >= 1 || lp_on) ? 1 : 0;
+    if (on && ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_set_arrival_rule needs the whole catalog on one device");
+    const float lp = lp_on ? lp_min : (on ? __builtin_nanf("") : 0.f); // (what the kernel takes: NaN is "clause off")
+    if (on != ctx->arr_on || rank_max != ctx->arr_rank || lp_on != ctx->arr_lp_on || memcmp(&lp, &ctx->arr_lp, sizeof(lp)))
+        irs_drop_graphs(ctx); // (a captured step holds the offer kernel with these two values, or lacks it)
+    ctx->arr_on = on, ctx->arr_rank = on ? rank_max : 0, ctx->arr_lp_on = lp_on, ctx->arr_lp = lp;
+    return IRS_OK;
+}
+// the greedy / sampled loops while a rule is set: the rule reads what the trace sweep leaves in the bound scratch
+static int check_arrival(irs_ctx *ctx, const char *fn) {
+    if (ctx && ctx->arr_on && !ctx->tr_on)
+        IRS_FAIL(ctx, IRS_E_STATE, "%s: an arrival rule is set (irs_set_arrival_rule) and no path trace is bound (irs_bind_path_trace): "
+                                   "the rule reads what the trace records", fn);
+    return IRS_OK;
+}
+// the beam loops have no offer: they refuse while a rule is set (with a trace bound they refuse already)
+static int refuse_arrival(irs_ctx *ctx, const char *fn) {
+    if (ctx->arr_on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: an arrival rule is set (irs_set_arrival_rule): greedy and sampled loops only", fn);
+    return IRS_OK;
+}
+
+extern "C" int irs_arrival_offer(irs_ctx *ctx, const int64_t *seq, const int32_t *hep, int32_t M, const float *mx, const float *sm,
+                                 const float *tscore, const int32_t *rank, const int32_t *fin, float *val, int64_t *ids0, int32_t k,
+                                 int32_t rank_max, float lp_min, const float *paths, int32_t path_ld, int32_t step,
+                                 const int32_t *row_map, int32_t *status, void *stream) {
+    if (!ctx) return IRS_E_INVALID;
+    if (!seq || !hep || !mx || !sm || !tscore || !rank || !val || !ids0 || !status) IRS_FAIL(ctx, IRS_E_INVALID, "irs_arrival_offer: null pointer");
+    if (M < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_arrival_offer: M must be >= 1");
+    if (k < 1 || k > ctx->dims.max_k) IRS_FAIL(ctx, IRS_E_INVALID, "irs_arrival_offer: k must be in [1, %d]", ctx->dims.max_k);
+    if (rank_max < 0) IRS_FAIL(ctx, IRS_E_INVALID, "irs_arrival_offer: rank_max must be >= 0 (0: the rank clause is off)");
+    if (rank_max == 0 && !irs_arrival_lp_on(lp_min)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_arrival_offer: both clauses are off");
+    if (step < 0 || (paths && (path_ld < 1 || step > path_ld)))
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_arrival_offer: step must be in [0, path_ld], path_ld >= 1");
+    if (ctx->excl_on && ctx->excl_no_repeat && !paths) IRS_FAIL(ctx, IRS_E_INVALID, "irs_arrival_offer: no_repeat is bound: dev_paths is null");
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_arrival_offer needs the whole catalog on one device");
+    const int rc = check_excl(ctx, "irs_arrival_offer", M, step);
+    if (rc) return rc;
+    return irs_launch_arrival_offer(ctx, seq, hep, M, mx, sm, tscore, rank, fin, val, ids0, k, rank_max, lp_min, status,
+                                    excl_args(ctx, 1, row_map, paths, path_ld, 1, nullptr, step), (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------ what the search loops share
 int irs_replay_steps(irs_ctx *ctx, irs_step_graph *g, const irs_step_key &key, const std::function<int(hipStream_t)> &body,
                      int times, hipStream_t s, int *capture_failed) {
@@ -921,6 +971,7 @@ static int check_search(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W
     // (a bound guide is looked at first, like the bindings at the top of the sharded loops: what it refuses needs no weights)
     int rc = W ? refuse_guide(ctx, fn) : check_guide(ctx, fn, k, sample);
     if (rc) return rc;
+    if (W && (rc = refuse_arrival(ctx, fn))) return rc;
     if ((rc = irs_ready_filter(ctx, sweep))) return rc;
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s needs the whole catalog on one device", fn);
     if (W) {
@@ -985,8 +1036,9 @@ int irs_beam_finish(irs_ctx *ctx, size_t rows, int P, float *paths, double *scor
 extern "C" int irs_generate_paths(irs_ctx *ctx, int64_t *seq, const int64_t *user, int32_t *hep, int32_t B,
                                   int32_t max_path_len, int32_t k, int32_t sweep, int32_t sample, int32_t sample_k,
                                   uint64_t seed, int32_t use_graph, float *paths, int32_t *status, void *stream) {
-    int rc = check_search(ctx, "irs_generate_paths", seq && hep && paths && status, B, 0, max_path_len, k, sweep, sample, sample_k);
+    int rc = check_arrival(ctx, "irs_generate_paths");
     if (rc) return rc;
+    if ((rc = check_search(ctx, "irs_generate_paths", seq && hep && paths && status, B, 0, max_path_len, k, sweep, sample, sample_k))) return rc;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
     const irs_path_args pa = loop_path_args(ctx, seq, hep, paths, max_path_len, sample, sample_k, seed, status, paths);
@@ -996,6 +1048,8 @@ extern "C" int irs_generate_paths(irs_ctx *ctx, int64_t *seq, const int64_t *use
         key.sample = sample, key.sample_k = sample_k, key.seed = seed;
         key.seq = seq, key.user = user, key.hep = hep, key.paths = paths, key.status = status;
         key.tr_item = ctx->tr_item, key.tr_target = ctx->tr_target, key.tr_rank = ctx->tr_rank, key.tr_scratch = ctx->tr_scratch;
+        key.arr_rank = ctx->arr_rank;
+        memcpy(&key.arr_lp_bits, &ctx->arr_lp, sizeof(key.arr_lp_bits));
         return irs_replay_steps(ctx, &ctx->g_greedy, key, [&](hipStream_t q) {
             return enqueue_step(ctx, pa, user, B, k, sweep, q);
         }, max_path_len, s);
@@ -1013,8 +1067,9 @@ extern "C" int irs_generate_paths_until(irs_ctx *ctx, int64_t *seq, const int64_
                                         int32_t max_path_len, int32_t k, int32_t sweep, int32_t sample, int32_t sample_k,
                                         uint64_t seed, int32_t check_every, float *paths, int32_t *status, int64_t *host_stats,
                                         void *stream) {
-    int rc = check_search(ctx, "irs_generate_paths_until", seq && hep && paths && status, B, 0, max_path_len, k, sweep, sample, sample_k);
+    int rc = check_arrival(ctx, "irs_generate_paths_until");
     if (rc) return rc;
+    if ((rc = check_search(ctx, "irs_generate_paths_until", seq && hep && paths && status, B, 0, max_path_len, k, sweep, sample, sample_k))) return rc;
     if (check_every < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths_until: check_every must be >= 1");
     if (max_path_len > IRS_MAX_PATH)
         IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_generate_paths_until: max_path_len %d > %d", max_path_len, IRS_MAX_PATH);

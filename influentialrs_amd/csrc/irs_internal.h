@@ -75,8 +75,10 @@ struct irs_step_key {
     uint64_t seed;
     const void *comm, *seq, *user, *hep, *paths, *status;
     const void *tr_item, *tr_target, *tr_rank, *tr_scratch; // the bound path trace (irs_bind_path_trace); null: none
+    int32_t arr_rank;     // the arrival rule (irs_set_arrival_rule): rank_max, 0: clause off
+    uint32_t arr_lp_bits; // the bits of ctx->arr_lp: lp_min, a NaN's while only the rank clause is on, 0 without a rule
 };
-static_assert(sizeof(irs_step_key) == 8 * sizeof(int32_t) + 11 * 8, "irs_step_key is compared with memcmp: no padding");
+static_assert(sizeof(irs_step_key) == 8 * sizeof(int32_t) + 11 * 8 + 2 * sizeof(int32_t), "irs_step_key is compared with memcmp: no padding");
 struct irs_step_graph {
     hipGraphExec_t exec; // null: nothing captured
     irs_step_key key;
@@ -298,6 +300,11 @@ struct irs_ctx {
     int guide_on;
     irs_guide guide;
 
+    // arrival rule (irs_set_arrival_rule): between the trace sweep and the path step, a live row whose target stands at rank
+    // <= arr_rank (0: clause off) or at log-probability >= arr_lp (arr_lp_on) is offered the target alone; needs a bound trace
+    int arr_on, arr_rank, arr_lp_on;
+    float arr_lp;
+
     // profiling
     int prof_family;
     irs_prof_ev *prof_ev;
@@ -335,6 +342,8 @@ enum { IRS_CAPTURE_BODY = 1, IRS_CAPTURE_HIP = 2 };
 int irs_replay_steps(irs_ctx *ctx, irs_step_graph *g, const irs_step_key &key, const std::function<int(hipStream_t)> &body,
                      int times, hipStream_t s, int *capture_failed = nullptr);
 void irs_drop_graphs(irs_ctx *ctx);
+// the probability clause of an arrival rule is on for lp_min <= 0 (-inf included); lp_min > 0 and NaN turn it off
+static inline bool irs_arrival_lp_on(float lp_min) { return lp_min <= 0.f; }
 // event records are not captured: with a profiling family enabled every loop runs on the stream and records its brackets
 static inline bool irs_may_capture(const irs_ctx *ctx, int use_graph) { return use_graph && ctx->prof_family == IRS_PROF_NONE; }
 int irs_check_k(irs_ctx *ctx, const char *fn, int k, int world, int sweep, int sample, int sample_k);
@@ -427,6 +436,12 @@ int irs_launch_merge_keys(irs_ctx *ctx, const uint64_t *keys_in, int W, int M, i
 int irs_launch_pack_topk(irs_ctx *ctx, const float *val, const int64_t *ids0, int64_t n, uint64_t *keys, hipStream_t s);
 int irs_launch_path_step(irs_ctx *ctx, const irs_path_args &pa, int B, const float *val, const int64_t *ids0, int k, hipStream_t s);
 int irs_launch_inc(irs_ctx *ctx, int32_t *ctr, hipStream_t s);
+// the arrival rule on B rows, behind the trace sweep (mx / sm / ts / rank by launch row) and before the path step: a row that
+// fires gets (ts, t - 1), (-inf, -1) at the head of its list and IRS_ROW_OFFERED in status[row]; rows with fin[r] != 0 (null:
+// none) are skipped.  `ex`: the step's bound exclusions (its map, its path rows and its step index: ex.step_ptr / ex.step_arg)
+int irs_launch_arrival_offer(irs_ctx *ctx, const int64_t *seq, const int32_t *hep, int B, const float *mx, const float *sm,
+                             const float *ts, const int32_t *rank, const int32_t *fin, float *val, int64_t *ids0, int k, int rank_max,
+                             float lp_min, int32_t *status, const irs_excl &ex, hipStream_t s);
 // after a path step on B rows, before the step counter moves: the three traced values of step step_ptr[0] go to row map[r] (null: r)
 // of the caller's arrays; rows with fin[r] != 0 (null: none) are not written
 int irs_launch_trace_record(irs_ctx *ctx, const irs_trace_rec &t, const int64_t *seq, const int32_t *hep, const float *paths,

@@ -444,6 +444,68 @@ int irs_launch_trace_record(irs_ctx *ctx, const irs_trace_rec &t, const int64_t 
     return IRS_OK;
 }
 
+// ------------------------------------------------------------------ arrival rule (irs_set_arrival_rule, irs_arrival_offer)
+// Behind the trace sweep, before the step chooses: a live row whose target stands at rank <= rank_max among what the window
+// leaves, or at log-probability >= lp_min (the expression k_trace_record stores, so the decision can be replayed from the
+// recorded arrays), and is admissible under the step's own test -- a catalog item outside the window seq[row][0 .. hep], the
+// user's bound list and (no_repeat) the row's path so far -- gets its list rewritten to the target alone: (ts, t - 1), then the
+// end mark.  The unchanged step kernels then choose it as the only survivor.  Rows that do not fire are not written.
+// One wave per row; no LDS, no atomics (the status word is this row's, and the step kernels behind write it the same way).
+template <bool EXCL, int SLOTS>
+__global__ void __launch_bounds__(256) k_arrival_offer(const int64_t *__restrict__ seq, const int32_t *__restrict__ hep, int L, int B,
+                                                       int64_t n_item, const float *__restrict__ mx, const float *__restrict__ sm,
+                                                       const float *__restrict__ ts, const int32_t *__restrict__ rank,
+                                                       const int32_t *__restrict__ fin, float *__restrict__ val,
+                                                       int64_t *__restrict__ ids0, int k, int rank_max, float lp_min,
+                                                       int32_t *__restrict__ status, const irs_excl ex) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= B) return;
+    if (fin && fin[row]) return;
+    const int rk = rank[row];
+    if (rk == 0) return; // no target
+    const float tsv = ts[row];
+    bool fire = rank_max >= 1 && rk <= rank_max;
+    if (!fire && lp_min <= 0.f) { // (the probability clause is on: irs_arrival_lp_on)
+        const float lp = (float)((double)tsv - ((double)mx[row] + log((double)sm[row])));
+        fire = lp >= lp_min; // (a NaN lp never fires)
+    }
+    if (!fire) return;
+    const int64_t *w = seq + (size_t)row * L;
+    const int64_t t = w[L - 1];
+    if (t < 1 || t > n_item) return;
+    irs_window<SLOTS> win;
+    win.load(w, hep[row], L, lane);
+    bool hit = false, listed = false;
+    if constexpr (EXCL) {
+        const irs_excl_view ev = irs_excl_open(ex, row, lane, ex.step_ptr ? ex.step_ptr[0] : ex.step_arg);
+        hit = (ev.pth == t);
+        listed = irs_excl_listed(ev.list, ev.n, t - 1); // (the same search in every lane)
+    }
+    hit = win.holds(t, hit);
+    if (__any(hit) || listed) return;
+    if (lane == 0) {
+        val[(size_t)row * k] = tsv;
+        ids0[(size_t)row * k] = t - 1;
+        status[row] |= IRS_ROW_OFFERED;
+    } else if (lane == 1 && k > 1) {
+        val[(size_t)row * k + 1] = -INFINITY;
+        ids0[(size_t)row * k + 1] = -1;
+    }
+}
+
+int irs_launch_arrival_offer(irs_ctx *ctx, const int64_t *seq, const int32_t *hep, int B, const float *mx, const float *sm,
+                             const float *ts, const int32_t *rank, const int32_t *fin, float *val, int64_t *ids0, int k, int rank_max,
+                             float lp_min, int32_t *status, const irs_excl &ex, hipStream_t s) {
+    constexpr int S4 = IRS_WIN_SLOTS_SHORT, S16 = IRS_WIN_SLOTS_LONG;
+    const auto kern = irs_window_slots(ctx) == S4 ? (ex.on ? k_arrival_offer<true, S4> : k_arrival_offer<false, S4>)
+                                                  : (ex.on ? k_arrival_offer<true, S16> : k_arrival_offer<false, S16>);
+    hipLaunchKernelGGL(kern, dim3((B + 3) / 4), dim3(256), 0, s, seq, hep, ctx->dims.max_len, B, ctx->dims.n_item, mx, sm, ts, rank, fin,
+                       val, ids0, k, rank_max, lp_min, status, ex);
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
 // ------------------------------------------------------------------ stop-at-target search (irs_generate_paths_until)
 // The reference never stops at the target: it runs every step for every user and zeroes the tail on the host afterwards
 // (model/influentialRS.py:459-467).  Here a user is finished after the step that chose seq[b][L - 1]; the three kernels below

@@ -605,6 +605,53 @@ class Engine:
                     t.record_stream(stream)
             self.unbind_guide()
 
+    # ------------------------------------------------------------------ arrival rule (irs_set_arrival_rule)
+    def set_arrival_rule(self, rank_max: Optional[int] = None, lp_min: Optional[float] = None):
+        """irs_set_arrival_rule: until cleared (both None) a live row of the greedy / sampled loops whose target stands at rank
+        <= rank_max among what the window leaves, or at log-probability >= lp_min, is offered the target alone
+        (IRS_ROW_OFFERED).  The loops then need a bound path trace (trace=True)."""
+        self._check(self.lib.irs_set_arrival_rule(self.h, 0 if rank_max is None else int(rank_max),
+                                                  float("nan") if lp_min is None else float(lp_min)))
+
+    def arrival_offer(self, seqs, hep, mx, sm, ts, rank, val, ids0, status, *, rank_max: Optional[int] = None,
+                      lp_min: Optional[float] = None, fin=None, paths=None, step: int = 0, row_map=None):
+        """irs_arrival_offer: the rule alone on the outputs of score_target_trace; val / ids0 / status are rewritten in place."""
+        seqs, hep = self._dev(seqs, torch.int64), self._dev(hep, torch.int32)
+        mx, sm, ts = (self._dev(t, torch.float32) for t in (mx, sm, ts))
+        rank = self._dev(rank, torch.int32)
+        val = self._inplace(val, torch.float32, "arrival_offer: val")
+        ids0 = self._inplace(ids0, torch.int64, "arrival_offer: ids0")
+        status = self._inplace(status, torch.int32, "arrival_offer: status")
+        M = seqs.shape[0]
+        if seqs.dim() != 2 or seqs.shape[1] != self.L or val.dim() != 2 or val.shape != ids0.shape or val.shape[0] != M or \
+                any(t.numel() != M for t in (hep, mx, sm, ts, rank, status)):
+            raise IrsError("arrival_offer: seqs [M, max_len], val / ids0 [M, k], the rest [M]")
+        fin = None if fin is None else self._dev(fin, torch.int32)
+        paths = None if paths is None else self._dev(paths, torch.float32)
+        row_map = None if row_map is None else self._dev(row_map, torch.int32)
+        if (fin is not None and fin.numel() != M) or (row_map is not None and row_map.numel() != M) or \
+                (paths is not None and paths.dim() != 2):
+            raise IrsError("arrival_offer: fin / row_map [M], paths [rows, path_ld]")
+        self._call(self.lib.irs_arrival_offer, _ptr(seqs), _ptr(hep), M, _ptr(mx), _ptr(sm), _ptr(ts), _ptr(rank), _ptr(fin),
+                   _ptr(val), _ptr(ids0), val.shape[1], 0 if rank_max is None else int(rank_max),
+                   float("nan") if lp_min is None else float(lp_min), _ptr(paths), paths.shape[1] if paths is not None else 0,
+                   step, _ptr(row_map), _ptr(status))
+
+    @contextlib.contextmanager
+    def _arrival_rule(self, rank_max: Optional[int], lp_min: Optional[float], graph: bool = False):
+        """While a search call runs with arrive_rank= / arrive_lp=: the rule set before and cleared after (set and clear drop the
+        context's captured steps, like the bindings)."""
+        if rank_max is None and lp_min is None:
+            yield
+            return
+        self.set_arrival_rule(rank_max, lp_min)
+        try:
+            yield
+        finally:
+            if graph:
+                torch.cuda.current_stream(self.device).synchronize()
+            self.set_arrival_rule(None, None)
+
     # ------------------------------------------------------------------ path search
     def path_step(self, seqs, hep, val, ids0, step: int, paths, status, sample=False, sample_k=3, seed=0):
         seqs = self._inplace(seqs, torch.int64, "path_step: seqs")
@@ -623,7 +670,8 @@ class Engine:
                        use_graph: bool = False, paths: Optional[torch.Tensor] = None,
                        status: Optional[torch.Tensor] = None, exact_candidates: bool = False,
                        exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
-                       guide: Optional[torch.Tensor] = None, guide_k: int = 5):
+                       guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
+                       arrive_lp: Optional[float] = None):
         """Runs the whole search loop on the device.  `seqs` and `hep` are the
         working window state and are modified in place.  exact_candidates: a row whose k candidates are hidden by its window
         chooses among the exact best admissible items of the catalog instead (IRS_ROW_RESCUED; the result of k = n_item).
@@ -634,7 +682,10 @@ class Engine:
         lp_target float32 [B, max_path_len], rank_target int32 [B, max_path_len]): all columns are written; cut them where paths
         is cut.
         guide ([n_item + 1, F], see bind_guide) / guide_k: a guide is bound for this call (irs_bind_guide): a step takes, among
-        its first guide_k admissible candidates, the one nearest to the target seqs[b, L - 1] (the Rec2Inf rule); greedy only."""
+        its first guide_k admissible candidates, the one nearest to the target seqs[b, L - 1] (the Rec2Inf rule); greedy only.
+        arrive_rank / arrive_lp: an arrival rule is set for this call (irs_set_arrival_rule; needs trace=True): a row whose
+        target stands at rank <= arrive_rank among what its window leaves, or at log-probability >= arrive_lp, is offered the
+        target at that step (IRS_ROW_OFFERED in its status word); this loop then searches on behind the arrival."""
         seqs = self._inplace(seqs, torch.int64, "generate_paths: seqs")
         hep = self._inplace(hep, torch.int32, "generate_paths: hep")
         if users is not None:
@@ -651,7 +702,7 @@ class Engine:
         if paths.shape != (B, max_path_len):
             raise IrsError("generate_paths: paths must be [B, max_path_len]")
         want = guide_k if guide is not None else (sample_k if sample else 1)
-        with self._exact_candidates(exact_candidates, B, want, bool(use_graph)), \
+        with self._arrival_rule(arrive_rank, arrive_lp, bool(use_graph)), self._exact_candidates(exact_candidates, B, want, bool(use_graph)), \
                 self._exclusions(exclude, no_repeat, B, bool(use_graph)), self._guide(guide, guide_k, bool(use_graph)), \
                 self._path_trace(trace, B, max_path_len, bool(use_graph)) as traced:
             self._call(self.lib.irs_generate_paths, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
@@ -663,12 +714,15 @@ class Engine:
                              check_every: int = 1, paths: Optional[torch.Tensor] = None,
                              status: Optional[torch.Tensor] = None, exact_candidates: bool = False,
                              exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
-                             guide: Optional[torch.Tensor] = None, guide_k: int = 5):
+                             guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
+                             arrive_lp: Optional[float] = None):
         """generate_paths that stops a user at its target (seqs[b, L - 1]) and the call when nobody is left
         (irs_generate_paths_until): returns (paths, status, steps_run, row_steps).  Paths are zero behind the target.
         `seqs` and `hep` are working state: modified, and unspecified afterwards.  One host read of 4 bytes per check.
         trace: as in generate_paths, a fifth member (lp_item, lp_target, rank_target), exactly zero behind a user's arrival.
-        guide / guide_k: as in generate_paths -- with the Rec2Inf rule this loop is the reference's get_path."""
+        guide / guide_k: as in generate_paths -- with the Rec2Inf rule this loop is the reference's get_path.
+        arrive_rank / arrive_lp: as in generate_paths (needs trace=True) -- a user is retired at the step that offered it its
+        target, so the search stops as soon as the rule allows."""
         seqs = self._inplace(seqs, torch.int64, "generate_paths_until: seqs")
         hep = self._inplace(hep, torch.int32, "generate_paths_until: hep")
         if users is not None:
@@ -686,7 +740,8 @@ class Engine:
             raise IrsError("generate_paths_until: paths must be [B, max_path_len]")
         stats = (ctypes.c_int64 * 2)(0, 0)
         want = guide_k if guide is not None else (sample_k if sample else 1)
-        with self._exact_candidates(exact_candidates, B, want), self._exclusions(exclude, no_repeat, B), \
+        with self._arrival_rule(arrive_rank, arrive_lp), self._exact_candidates(exact_candidates, B, want), \
+                self._exclusions(exclude, no_repeat, B), \
                 self._guide(guide, guide_k), self._path_trace(trace, B, max_path_len) as traced:
             self._call(self.lib.irs_generate_paths_until, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                           int(sample), sample_k, seed, check_every, _ptr(paths), _ptr(status), stats)

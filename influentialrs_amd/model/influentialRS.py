@@ -30,7 +30,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.optim as optim
 
-from .._lib import IRS_BEAM_STOP_ALL, IRS_BEAM_STOP_BEST, IRS_MASK_IRN, IRS_ROW_NO_CANDIDATE
+from .._lib import IRS_BEAM_STOP_ALL, IRS_BEAM_STOP_BEST, IRS_MASK_IRN, IRS_ROW_NO_CANDIDATE, IRS_ROW_OFFERED
 from ._backend import HipBackend, check_trunk, make_scheduler, pad_ragged_ids, project_ce, project_ce_sharded, train_trunk_default, trunk_hip
 from .layers import PositionalEncoding, get_item_index
 
@@ -181,19 +181,24 @@ def _takes_exact_candidates(fn):
     parameter list stays what it was (it ends with beam_stop): positional callers and code that reads the signature are not
     disturbed.  The search reads the switch from self._exact_candidates for the time of the call.
     exclude=None and no_repeat=False (bound exclusions) are taken the same way, into self._exclude / self._no_repeat, and
-    trace=False (the path trace) into self._trace, guide=None and guide_k=5 (the guided choice) into self._guide / self._guide_k."""
+    trace=False (the path trace) into self._trace, guide=None and guide_k=5 (the guided choice) into self._guide / self._guide_k,
+    arrive_rank=None and arrive_lp=None (the arrival rule) into self._arrive_rank / self._arrive_lp."""
     @functools.wraps(fn)
-    def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None, guide_k=5, **kw):
+    def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None, guide_k=5,
+             arrive_rank=None, arrive_lp=None, **kw):
         prev = (getattr(self, "_exact_candidates", False), getattr(self, "_exclude", None), getattr(self, "_no_repeat", False),
                 getattr(self, "_trace", False))
         prev_guide = (getattr(self, "_guide", None), getattr(self, "_guide_k", 5))
         self._exact_candidates, self._exclude, self._no_repeat, self._trace = bool(exact_candidates), exclude, bool(no_repeat), bool(trace)
+        prev_arrive = (getattr(self, "_arrive_rank", None), getattr(self, "_arrive_lp", None))
         self._guide, self._guide_k = guide, int(guide_k)
+        self._arrive_rank, self._arrive_lp = arrive_rank, arrive_lp
         try:
             return fn(self, *args, **kw)
         finally:
             self._exact_candidates, self._exclude, self._no_repeat, self._trace = prev
             self._guide, self._guide_k = prev_guide
+            self._arrive_rank, self._arrive_lp = prev_arrive
     return call
 
 
@@ -408,11 +413,33 @@ class IRSNN(nn.Module):
         Rec2Inf choice on IRN's own ranking (irs_bind_guide).  guide: a [n_item + 1, F] feature table on the net's device, row i
         = the 1-based item i; integer / bool: binary features, Hamming distance; floating: squared Euclidean distance.  Every
         step then offers, among its first guide_k admissible top-100 candidates, the one nearest to the user's target (ties: the
-        better rank) instead of the first.  model/rec2inf.py is the same rule on the plain recommender."""
+        better rank) instead of the first.  model/rec2inf.py is the same rule on the plain recommender.
+        arrive_rank=None, arrive_lp=None (extension, keyword only, taken the same way; greedy / sampled search on one device,
+        off by default): the arrival rule (irs_set_arrival_rule).  A recommender shows a slate, so a user counts as arrived at
+        the first step where the target stands at rank <= arrive_rank (>= 1) among what its window leaves, or where the model
+        gives it a log-probability >= arrive_lp (<= 0): the step then offers the target itself.  With stop_at_target=True the
+        user is retired there.  The keywords imply trace=True: self.last_trace is filled, and its `offered` (bool [B]) says for
+        whom the rule fired.  A target that the window, the exclusion list or (no_repeat) the path hides is never offered."""
         exact_candidates = getattr(self, "_exact_candidates", False)
         exclude, no_repeat = getattr(self, "_exclude", None), getattr(self, "_no_repeat", False)
         trace = getattr(self, "_trace", False)
         guide, guide_k = getattr(self, "_guide", None), getattr(self, "_guide_k", 5)
+        arrive_rank, arrive_lp = getattr(self, "_arrive_rank", None), getattr(self, "_arrive_lp", None)
+        if arrive_rank is not None or arrive_lp is not None:
+            if arrive_rank is not None and (isinstance(arrive_rank, bool) or int(arrive_rank) != arrive_rank or arrive_rank < 1):
+                raise ValueError(f"arrive_rank={arrive_rank!r}: a rank of 1 or more (None: no rank clause)")
+            if arrive_lp is not None and not float(arrive_lp) <= 0:
+                raise ValueError(f"arrive_lp={arrive_lp!r}: a log-probability, at most 0 (None: no probability clause)")
+            if beam_width > 1:
+                raise ValueError("arrive_rank / arrive_lp is not built for beam search (beam_width > 1): the arrival rule reads "
+                                 "the path trace, which is not carried through beam state")
+            if self.net._hip.world != 1:
+                raise ValueError("arrive_rank / arrive_lp is not built for an item-sharded catalog: irs_set_arrival_rule needs "
+                                 "the whole catalog on one device")
+            arrive_rank = None if arrive_rank is None else int(arrive_rank)
+            arrive_lp = None if arrive_lp is None else float(arrive_lp)
+            trace = True
+        arrive = dict(arrive_rank=arrive_rank, arrive_lp=arrive_lp) if (arrive_rank is not None or arrive_lp is not None) else {}
         if guide is not None:
             if beam_width > 1:
                 raise ValueError("guide is not built for beam search (beam_width > 1): use beam_width=1 (the guided choice is a "
@@ -468,12 +495,13 @@ class IRSNN(nn.Module):
                                                                       sample=sample, sample_k=sample_k, seed=seed,
                                                                       check_every=STOP_CHECK_EVERY,
                                                                       exact_candidates=exact_candidates, trace=trace, **excl,
-                                                                      **guided)
+                                                                      **guided, **arrive)
         elif hip.world == 1:
             eng = hip.get(B, B)
             paths_t, status, *traced = eng.generate_paths(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
                                                           sample=sample, sample_k=sample_k, seed=seed, use_graph=False,
-                                                          exact_candidates=exact_candidates, trace=trace, **excl, **guided)
+                                                          exact_candidates=exact_candidates, trace=trace, **excl, **guided,
+                                                          **arrive)
         else:  # item-sharded: irs_generate_paths_sharded (decode, row all-gather, shard sweep, key all-to-all, merge, path
             # step per search step, below the C ABI on one stream)
             eng = hip.get(B, B * hip.world)
@@ -491,6 +519,7 @@ class IRSNN(nn.Module):
         targets = targets.detach().cpu().numpy()
         if trace:
             self.last_trace = path_trace_summary(*(a.detach().cpu().numpy() for a in traced[0]), paths, targets)
+            self.last_trace["offered"] = (status & IRS_ROW_OFFERED).ne(0).detach().cpu().numpy()
         histories = seqs[:, :-1].detach().cpu().numpy()
         actual_history = []
         for i in range(B):
