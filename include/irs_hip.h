@@ -208,7 +208,8 @@ int irs_score_dense(irs_ctx *ctx, const float *dev_xrows, int32_t M, float *dev_
 /* Row-wise (max, sum exp(e - max)) over the shard (replaces Softmax /
  * LogSoftmax over N, influentialRS.py:418, evaluator.py:195, and
  * CrossEntropyLoss, evaluator.py:321).  Combine shards on the host side
- * (max of maxes, rescaled sum). */
+ * (max of maxes, rescaled sum).  max is the maximum of the shard's chain
+ * scores, bit for bit; the sum is a float32 sum in no fixed order. */
 int irs_score_lse(irs_ctx *ctx, const float *dev_xrows, int32_t M, float *dev_max, float *dev_sumexp, void *stream);
 
 /* irs_score_topk and irs_score_lse of the same rows out of ONE call: what a beam-search step needs (candidates +

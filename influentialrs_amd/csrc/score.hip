@@ -90,6 +90,16 @@ __device__ __forceinline__ float max16(const f32x16 &a) {
                  vmax3(vmax3(a[9], a[10], a[11]), vmax3(a[12], a[13], a[14]), a[15]));
 }
 
+// A 16-byte load gives lane (r, h) the four CONSECUTIVE k of its half, {8q + 4h + c}; the 32x32x2 MFMA takes k from half 0 and
+// k + 1 from half 1 of one register.  Two half exchanges (v_permlane32_swap: lanes 32-63 of the first register <-> lanes 0-31 of
+// the second) turn the float4 into {8q + 2c + h}: issued .x .y .z .w, the MFMAs then sum k = 0, 1, 2, ... -- the chain's order.
+// Every lane of the wave must be active.
+__device__ __forceinline__ float4 chain_pairs(float4 v) {
+    const auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v.x), __float_as_uint(v.y), false, false);
+    const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v.z), __float_as_uint(v.w), false, false);
+    return make_float4(__uint_as_float(a[0]), __uint_as_float(b[0]), __uint_as_float(a[1]), __uint_as_float(b[1]));
+}
+
 // workgroup -> (strip, ublock): the n_ublocks workgroups that stream the same
 // W strip get ids congruent mod 8, i.e. land on one XCD and share its L2.
 __device__ __forceinline__ bool sweep_map(const SweepArgs &a, int &strip, int &ublock) {
@@ -1026,8 +1036,8 @@ __global__ void __launch_bounds__(NW * 64, 2) k_sweep_ring16(SweepArgs a) {
 template <int KS, int UB, int MODE, bool VEC>
 __global__ void __launch_bounds__(256, 2) k_sweep_f32(SweepArgs a) {
     constexpr int QN = 2 * KS; // float4 groups per row (d_pad / 8)
-    // The log-sum-exp is a float32 sum of exp() over the catalog in no particular order: it does not need the chain's
-    // summation order, so each lane loads ONE float4 per 8 k (its half's four consecutive k) instead of two.
+    // The log-sum-exp reads no neighbour's k: each lane loads ONE float4 per 8 k (its half's four consecutive k) instead of
+    // two, and chain_pairs() exchanges halves in registers, so the scores (and the row maximum) are still the chain's.
     constexpr bool PERM = MODE == MODE_LSE && VEC;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float4 *xs4 = reinterpret_cast<float4 *>(smem); // [UB][QN][64]
@@ -1045,19 +1055,11 @@ __global__ void __launch_bounds__(256, 2) k_sweep_f32(SweepArgs a) {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (row < a.M) {
             const float *xr = a.x32 + (size_t)row * a.d;
-            if (PERM) { // half h holds k = 8q + 4h + c: same pairing on both operands, another summation order
-                int k = 8 * q + 4 * hh;
-                if (k < a.d) v.x = xr[k];
-                if (k + 1 < a.d) v.y = xr[k + 1];
-                if (k + 2 < a.d) v.z = xr[k + 2];
-                if (k + 3 < a.d) v.w = xr[k + 3];
-            } else {
-                int k = 8 * q + hh;
-                if (k < a.d) v.x = xr[k];
-                if (k + 2 < a.d) v.y = xr[k + 2];
-                if (k + 4 < a.d) v.z = xr[k + 4];
-                if (k + 6 < a.d) v.w = xr[k + 6];
-            }
+            int k = 8 * q + hh;
+            if (k < a.d) v.x = xr[k];
+            if (k + 2 < a.d) v.y = xr[k + 2];
+            if (k + 4 < a.d) v.z = xr[k + 4];
+            if (k + 6 < a.d) v.w = xr[k + 6];
         }
         xs4[i] = v;
     }
@@ -1094,7 +1096,7 @@ __global__ void __launch_bounds__(256, 2) k_sweep_f32(SweepArgs a) {
             const float *wr = a.w32 + (size_t)(item < a.n_local ? item : 0) * a.d + 4 * h;
 #pragma unroll
             for (int q = 0; q < QN; ++q) {
-                float4 s = *reinterpret_cast<const float4 *>(wr + 8 * q);
+                float4 s = chain_pairs(*reinterpret_cast<const float4 *>(wr + 8 * q));
                 if (item >= a.n_local) s = make_float4(0.f, 0.f, 0.f, 0.f);
                 af[q] = s;
             }
@@ -1243,13 +1245,13 @@ __global__ void __launch_bounds__(256, 2) k_sweep_f32(SweepArgs a) {
 }
 
 // Log-sum-exp over the catalog, one wave per SIMD (512 registers): a tile's 32 W rows go row-major from global
-// memory straight into MFMA A fragments (lane (r, h): row r, four consecutive k of half h per 8 k -- the pairing of
-// k is the same on both operands, the summation order is not the chain's, which a sum of exp() does not need), the
+// memory into MFMA A fragments (lane (r, h): one 16-byte load of row r, four consecutive k of half h per 8 k, then
+// chain_pairs(): two half exchanges in registers per load put k and k + 1 on the two halves, on both operands, so a
+// score is summed in the chain's order and the row maximum is the chain's, bit for bit), the
 // next tile's fragments are requested before the current tile's MFMAs start.  The x image sits in LDS.
 // EMIT: the same pass also emits every item whose float32 score reaches the row's emission threshold (a.thr, from the
 // bf16 pre-pass) -- a search that needs both the top-k and the log-sum-exp (beam search) then reads the float32
-// catalog once and the bf16 one not at all.  The scores here differ from the chain's by < eps[row] (a different
-// float32 summation order is within the accumulation term of eps), so k_refine's validity test holds unchanged.
+// catalog once and the bf16 one not at all.  The scores here are the chain's, so k_refine's validity test holds unchanged.
 // XREG (one row tile per workgroup, i.e. at most 32 rows -- a beam search's rows): the rows' fragments live in REGISTERS
 // (QN float4 per lane) and two fragment sets of W are in flight instead of three.  The LDS form's inner loop came out as
 // "ds_read_b128; s_waitcnt lgkmcnt(0); 4 MFMAs": with one wave per SIMD the LDS round trip (~120 cycles) stood in
@@ -1274,14 +1276,14 @@ __global__ void __launch_bounds__(256, 1) k_lse_f32(SweepArgs a) {
         const int row = ut0 * 32 + r;
 #pragma unroll
         for (int q = 0; q < QN; ++q)
-            xr4[q] = row < a.M ? *reinterpret_cast<const float4 *>(a.x32 + (size_t)row * a.d + 8 * q + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
+            xr4[q] = chain_pairs(row < a.M ? *reinterpret_cast<const float4 *>(a.x32 + (size_t)row * a.d + 8 * q + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f));
     } else {
         for (int i = tid; i < ubc * QN * 64; i += 256) {
             const int ln = i & 63, q = (i >> 6) % QN, u = (i >> 6) / QN;
             const int row = (ut0 + u) * 32 + (ln & 31);
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (row < a.M) v = *reinterpret_cast<const float4 *>(a.x32 + (size_t)row * a.d + 8 * q + 4 * (ln >> 5));
-            xs4[i] = v;
+            xs4[i] = chain_pairs(v); // (ln is this thread's own lane: 256 | i - tid; whole waves run the loop: 256 | ubc QN 64)
         }
         __syncthreads();
     }
@@ -1309,7 +1311,7 @@ __global__ void __launch_bounds__(256, 1) k_lse_f32(SweepArgs a) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) bc[q] = *reinterpret_cast<const float4 *>(a.bias + (size_t)tc * 32 + 8 * q + 4 * h);
         };
-        auto compute = [&](const float4(&af)[QN], const float4(&bc)[4], int t) {
+        auto compute = [&](float4(&af)[QN], const float4(&bc)[4], int t) {
 #pragma unroll
             for (int u = 0; u < UB; ++u) {
                 if (u < ubc) {
@@ -1323,11 +1325,15 @@ __global__ void __launch_bounds__(256, 1) k_lse_f32(SweepArgs a) {
                     }
 #pragma unroll
                     for (int q = 0; q < QN; ++q) {
+                        // the exchange: in place just ahead of the fragment's first use (the set is reloaded before its next), or, at
+                        // d_pad = 256, where the sets fill the register file, on a copy per row tile (two swaps per four MFMAs)
+                        if (KS < 16 && u == 0) af[q] = chain_pairs(af[q]);
+                        const float4 aq = KS < 16 ? af[q] : chain_pairs(af[q]);
                         const float4 bv = XREG ? xr4[q] : xs4[(u * QN + q) * 64 + lane];
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q].x, bv.x, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q].y, bv.y, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q].z, bv.z, acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[q].w, bv.w, acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aq.x, bv.x, acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aq.y, bv.y, acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aq.z, bv.z, acc, 0, 0, 0);
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aq.w, bv.w, acc, 0, 0, 0);
                     }
                     if (EMIT) emit_candidates(a, acc, thr[u], (ut0 + u) * 32 + r, t, h, eq, lane);
                     const float m = fmaxf(mx[u], max16(acc));
@@ -1399,7 +1405,7 @@ __global__ void __launch_bounds__(256, 1) k_lse_f32(SweepArgs a) {
 //     in flight, because the epilogue (emission queue, exp) is compiler code that must not find pending asm returns;
 //   * the rows' fragments live in registers as in XREG; one wave per SIMD.
 // Pad items read row 0 and carry bias -inf.  Summation order per score: that of k_lse_f32 (bias first, then k ascending in
-// the MFMA pairing), so the emitted candidates and the (max, sum) partials are those of the register form bit for bit.
+// the chain's order, chain_pairs() on every fragment read), so the emitted candidates and the (max, sum) partials are those of the register form bit for bit.
 template <int B_, int E_, class Fn>
 __device__ __forceinline__ void irs_static_for(Fn &&fn) {
     if constexpr (B_ < E_) {
@@ -1432,7 +1438,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_lse_ring(SweepArgs a) {
     float4 xr4[QN];
 #pragma unroll
     for (int q = 0; q < QN; ++q)
-        xr4[q] = r < a.M ? *reinterpret_cast<const float4 *>(a.x32 + (size_t)r * a.d + 8 * q + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
+        xr4[q] = chain_pairs(r < a.M ? *reinterpret_cast<const float4 *>(a.x32 + (size_t)r * a.d + 8 * q + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f));
     const int gw = strip * 4 + (wave & 3);
     const int ts = a.tile_stride;
     const int t0 = a.tile_begin + gw * a.tiles_per_wave * ts;
@@ -1519,7 +1525,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) k_lse_ring(SweepArgs a) {
                                 lds_wait<QS>(fa[SET][q]);
                             } else
                                 lds_wait<QS - 1 - q>(fa[SET][q]);
-                            const float4 af = __builtin_bit_cast(float4, fa[SET][q]);
+                            const float4 af = chain_pairs(__builtin_bit_cast(float4, fa[SET][q]));
                             const float4 bv = xr4[QS * C + q];
                             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, bv.x, acc, 0, 0, 0);
                             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, bv.y, acc, 0, 0, 0);

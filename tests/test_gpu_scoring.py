@@ -491,7 +491,8 @@ def test_rank_gather_dense_random_shapes_agree(n_item, d, M, k):
     """The other scoring entry points on randomly drawn shapes, against each other (all of them evaluate the same
     fixed-order float32 chain): gather == the dense logits at those ids, bit for bit; count_before == the rank
     counted on the dense logits (score desc, id asc, excluded ids skipped); the top-k's values == dense at its ids;
-    max + log(sum exp) == the same over the dense logits."""
+    max + log(sum exp) == the same over the dense logits.
+    (At most 48 rows, one row block: more than one row block, against references, is tests/test_gpu_sweep_modes.py.)"""
     M = min(M, 48)
     W, b = _weights(n_item, d, n_item + 3 * d)
     x = _rows(M, d, M + 11 * k)
