@@ -734,6 +734,72 @@ int irs_arrival_offer(irs_ctx *ctx, const int64_t *dev_seq, const int32_t *dev_h
                       float *dev_val, int64_t *dev_ids0, int32_t k, int32_t rank_max, float lp_min, const float *dev_paths,
                       int32_t path_ld, int32_t step, const int32_t *dev_row_map, int32_t *dev_status, void *stream);
 
+/* ---- path replay: every step of SAVED paths scored in one batched pass (opt-in; replaces the Python loop of dependent launches
+ *      of Evaluator.get_grad_in_batch, evaluator.py:162-243 -- one decode + LogSoftmax + gather per step -- and the two extra
+ *      decodes of get_rr_increase_in_batch, evaluator.py:245-290; and gives the loops that carry no trace -- beam, sharded, paths
+ *      read from paths_d_<n>.npy -- the trace's three values after the fact) ---------------------------------------------------
+ * A saved path is teacher-forced: the window before step i is known from the start window and the first i path items, so no
+ * step waits for another.  A REPLAY ROW is a pair (b, i): user b after i forced items.  Its window is the user's start window
+ * with path[b][0 .. i) applied by the layout's step rule; its consumed row is hep; its forced item is c = path[b][i] (0 when
+ * i == P, or when the path holds 0 there: the row then has no item).  dev_paths is int64 [B, path_ld], 1-based ids, P <= path_ld.
+ * Two layouts:
+ *   IRS_REPLAY_SLOT  the search loops' layout.  The start window is seq0[b][0 .. L) with the target in slot L-1 and hep0[b]
+ *                    given (in [0, L-2]).  The step rule is irs_path_step's: grow while hep < L-2 (the item goes to slot hep+1),
+ *                    otherwise shift slots [0, L-2] left by one and append at L-2; the target stays.  Closed form, with g = L-2
+ *                    - hep0: for i <= g slot p in (hep0, hep0+i] holds path[p-hep0-1], every other slot is seq0's, hep = hep0+i;
+ *                    for i > g slot p <= L-2 holds entry p+i-g of seq0[0 .. hep0] ++ path[0 .. i), hep = L-2.
+ *                    The target is seq0[b][L-1]: dev_target must be NULL.  Both mask modes (a causal context uses the layout as
+ *                    Rec2Inf does).
+ *   IRS_REPLAY_FULL  the evaluator's layout.  Windows are post-padded and all L slots are window; n0 is the index of the first
+ *                    0 of the start row (L if there is none).  The step rule is get_grad_in_batch's: write at n0+i while the
+ *                    window is not full, otherwise shift the WHOLE window left by one and append at L-1.  Closed form, with n =
+ *                    n0+i and s = max(n-L, 0): slot p holds entry p+s of seq0[0 .. n0) ++ path[0 .. i), 0 from entry n on;
+ *                    hep = min(n, L) - 1.  The target is dev_target[b] (required); slot L-1 is an ordinary window slot.
+ *                    IRS_MASK_CAUSAL contexts only for irs_replay_paths: the IRN mask gives column L-1 a meaning.
+ * Values of a row, defined exactly as the path trace defines them and formed with the same arithmetic: lse over the WHOLE
+ * catalog from the float32 pair (max, sumexp);
+ *   lp_target   = e_{t-1} - lse;    lp_item = e_{c-1} - lse, 0 without an item or with c outside [1, n_item];
+ *   rank_target = the rank among what the window seq[0 .. hep] leaves, in the library's total order;
+ * each log-probability is (double)e - ((double)max + log((double)sumexp)) rounded to float32 once; a target of 0 or outside the
+ * catalog gives 0 / 0.  A bound trace, guide, exclusion list or arrival rule does not enter: replay chooses nothing.
+ * A row is INVALID when b is outside [0, B), i is outside [0, P], one of path[b][0 .. i) is outside [1, n_item], the window
+ * would be empty (FULL with n0 + i == 0), or (SLOT) hep0[b] is outside [0, L-2].  An invalid row never faults and never reads
+ * out of bounds: it gets the user's start window if b is valid, otherwise user 0's (FULL: entries [0, n0) and zeros; the single
+ * item 1 in slot 0 when that is empty; SLOT: the row as it is, hep0 clamped into [0, L-2]), so every launched window is well
+ * formed; it records 0 / 0 / 0 and IRS_ROW_NO_CANDIDATE in dev_status[r].  Valid rows get IRS_ROW_OK.
+ * irs_replay_windows is the builder alone, as irs_score_target_trace is the sweep alone: one launch, one wave per row, no
+ * weights and no workspace needed, any mask mode, R up to 2^24, L up to IRS_MAX_LEN_LONG.
+ *  dev_seq0 int64 [B, L], dev_hep0 int32 [B] (SLOT; ignored and may be NULL for FULL), dev_user int64 [B] (may be NULL)
+ *  dev_row_user / dev_row_step int32 [R]: the rows, in any order, repeats allowed
+ *  dev_seq_out int64 [R, L], dev_hep_out int32 [R], dev_user_out int64 [R] (may be NULL; written when dev_user is given),
+ *  dev_status int32 [R] out
+ * irs_replay_paths walks the rows in order, in passes of `chunk` rows (in [1, min(max_rows, max_seqs)]) with a ragged last
+ * pass.  A pass is: windows -> the decoder with pos = hep and no [B, L, d] output -> the target's and the forced item's exact
+ * scores (irs_score_gather's arithmetic) -> the chain-order sweep, its reduction and the window correction of
+ * irs_score_target_trace, unchanged -> one record kernel that forms the three values.  All passes go on the caller's stream;
+ * no host reads, no allocation, no hipGraph, no float atomics: two identical calls give identical bits.
+ *  dev_target int64 [B] (FULL; NULL for SLOT); dev_lp_item / dev_lp_target float [R], dev_rank int32 [R], dev_status int32 [R] out
+ *  dev_scratch: caller-owned like irs_ce_backward's, >= irs_replay_scratch_bytes(chunk) bytes, 16-byte aligned: the pass's
+ *            windows, hep, users, items, targets, x rows, the item scores and the trace rows
+ *            (irs_path_trace_scratch_bytes(chunk)), each rounded up to 256 bytes.  irs_workspace_bytes does not change.
+ * Checks, all before any launch: a null pointer, R < 1 (R > 2^24), B < 1, P < 0, path_ld < P, a chunk out of range, an unknown
+ * layout, FULL without dev_target, SLOT with dev_target or without dev_hep0, an IRN context without dev_user, a scratch too
+ * small or misaligned -> IRS_E_INVALID; world != 1, FULL on an IRN context -> IRS_E_UNSUPPORTED; no weights or no workspace
+ * -> IRS_E_STATE.  Every other entry point launches exactly what it launched before. */
+#define IRS_REPLAY_SLOT 0
+#define IRS_REPLAY_FULL 1
+#define IRS_REPLAY_MAX_ROWS (1 << 24)
+size_t irs_replay_scratch_bytes(const irs_ctx *ctx, int32_t chunk); /* 0 for invalid arguments */
+int irs_replay_windows(irs_ctx *ctx, int32_t layout, const int64_t *dev_seq0, const int32_t *dev_hep0, const int64_t *dev_user,
+                       int32_t B, const int64_t *dev_paths, int32_t P, int32_t path_ld, const int32_t *dev_row_user,
+                       const int32_t *dev_row_step, int32_t R, int64_t *dev_seq_out, int32_t *dev_hep_out, int64_t *dev_user_out,
+                       int32_t *dev_status, void *stream);
+int irs_replay_paths(irs_ctx *ctx, int32_t layout, const int64_t *dev_seq0, const int32_t *dev_hep0, const int64_t *dev_user,
+                     const int64_t *dev_target, int32_t B, const int64_t *dev_paths, int32_t P, int32_t path_ld,
+                     const int32_t *dev_row_user, const int32_t *dev_row_step, int32_t R, int32_t chunk, void *dev_scratch,
+                     size_t scratch_bytes, float *dev_lp_item, float *dev_lp_target, int32_t *dev_rank, int32_t *dev_status,
+                     void *stream);
+
 /* ---- multi-GPU: the exchange steps and the sharded search loops below the ABI (section 8 row B2's
  *      `allgather_merge(ctx, comm, ...)`).  One process per GPU; rank r holds item rows [item_lo, item_hi) (irs_shard).
  * A communicator is either RCCL (librccl.so is dlopen()ed on first use: ncclCommInitRank over a 128-byte unique id the

@@ -21,6 +21,7 @@ IRS_ROW_OFFERED = 16  # irs_set_arrival_rule: the row's list was rewritten to th
 IRS_GEMM_F32, IRS_GEMM_X6, IRS_GEMM_H3 = 0, 1, 2
 IRS_BEAM_STOP_ALL, IRS_BEAM_STOP_BEST = 0, 1
 IRS_GUIDE_BINARY, IRS_GUIDE_FLOAT = 1, 2  # irs_bind_guide
+IRS_REPLAY_SLOT, IRS_REPLAY_FULL = 0, 1  # irs_replay_windows / irs_replay_paths: the search loops' layout, the evaluator's
 IRS_MAX_GUIDE_KC, IRS_MAX_GUIDE_BITS, IRS_MAX_GUIDE_FLOATS = 32, 1024, 512
 # irs_decoder_route_last (include/irs_hip.h): its field order and the names of the enum-valued fields, in the order of
 # decoder.hip's enum class DecPlan / DecEmbed / DecFam (tests/test_decoder_routes.py checks that they agree)
@@ -115,6 +116,12 @@ SIGNATURES = {
     "irs_arrival_offer": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                     c_void_p]),
+    "irs_replay_scratch_bytes": (c_size_t, [c_void_p, c_int32]),
+    "irs_replay_windows": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p,
+                                     c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "irs_replay_paths": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32,
+                                   c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
     "irs_comm_unique_id": (c_int32, [c_void_p]),
     "irs_comm_init_rccl": (c_int32, [POINTER(c_void_p), c_void_p, c_int32, c_int32]),
     "irs_comm_init_callbacks": (c_int32, [POINTER(c_void_p), c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

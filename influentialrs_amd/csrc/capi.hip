@@ -917,6 +917,73 @@ extern "C" int irs_arrival_offer(irs_ctx *ctx, const int64_t *seq, const int32_t
                                     excl_args(ctx, 1, row_map, paths, path_ld, 1, nullptr, step), (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ path replay (replay.hip)
+static int replay_chunk_max(const irs_ctx *ctx) { return ctx->max_rows < ctx->max_seqs ? ctx->max_rows : ctx->max_seqs; }
+
+extern "C" size_t irs_replay_scratch_bytes(const irs_ctx *ctx, int32_t chunk) {
+    if (!ctx || chunk < 1 || chunk > replay_chunk_max(ctx)) return 0;
+    return irs_replay_layout(nullptr, chunk, ctx->dims.max_len, ctx->dims.d, nullptr);
+}
+
+// what the builder and the replay share: the shapes, the layout and the pointers that go with it
+static int check_replay(irs_ctx *ctx, const char *fn, int layout, const void *seq0, const void *hep0, int B, const void *paths, int P,
+                        int path_ld, const void *row_user, const void *row_step, int R) {
+    if (layout != IRS_REPLAY_SLOT && layout != IRS_REPLAY_FULL) IRS_FAIL(ctx, IRS_E_INVALID, "%s: unknown layout %d", fn, layout);
+    if (!seq0 || !paths || !row_user || !row_step) IRS_FAIL(ctx, IRS_E_INVALID, "%s: null pointer", fn);
+    if (layout == IRS_REPLAY_SLOT && !hep0) IRS_FAIL(ctx, IRS_E_INVALID, "%s: IRS_REPLAY_SLOT needs dev_hep0", fn);
+    if (R < 1 || R > IRS_REPLAY_MAX_ROWS) IRS_FAIL(ctx, IRS_E_INVALID, "%s: R must be in [1, %d]", fn, IRS_REPLAY_MAX_ROWS);
+    if (B < 1 || P < 0 || path_ld < P) IRS_FAIL(ctx, IRS_E_INVALID, "%s: B >= 1, P >= 0 and path_ld >= P", fn);
+    return IRS_OK;
+}
+
+extern "C" int irs_replay_windows(irs_ctx *ctx, int32_t layout, const int64_t *seq0, const int32_t *hep0, const int64_t *user, int32_t B,
+                                  const int64_t *paths, int32_t P, int32_t path_ld, const int32_t *row_user, const int32_t *row_step,
+                                  int32_t R, int64_t *seq_out, int32_t *hep_out, int64_t *user_out, int32_t *status, void *stream) {
+    if (!ctx) return IRS_E_INVALID;
+    const int rc = check_replay(ctx, "irs_replay_windows", layout, seq0, hep0, B, paths, P, path_ld, row_user, row_step, R);
+    if (rc) return rc;
+    if (!seq_out || !hep_out || !status) IRS_FAIL(ctx, IRS_E_INVALID, "irs_replay_windows: null output");
+    const irs_replay_args a{layout, B, ctx->dims.max_len, P, path_ld, R, ctx->dims.n_item, seq0, hep0, user, nullptr, paths,
+                            row_user, row_step, seq_out, hep_out, user_out, status, nullptr, nullptr};
+    return irs_launch_replay_windows(ctx, a, (hipStream_t)stream);
+}
+
+extern "C" int irs_replay_paths(irs_ctx *ctx, int32_t layout, const int64_t *seq0, const int32_t *hep0, const int64_t *user,
+                                const int64_t *target, int32_t B, const int64_t *paths, int32_t P, int32_t path_ld,
+                                const int32_t *row_user, const int32_t *row_step, int32_t R, int32_t chunk, void *scratch,
+                                size_t scratch_bytes, float *lp_item, float *lp_target, int32_t *rank, int32_t *status, void *stream) {
+    if (!ctx) return IRS_E_INVALID;
+    int rc = check_replay(ctx, "irs_replay_paths", layout, seq0, hep0, B, paths, P, path_ld, row_user, row_step, R);
+    if (rc) return rc;
+    if (!lp_item || !lp_target || !rank || !status || !scratch) IRS_FAIL(ctx, IRS_E_INVALID, "irs_replay_paths: null pointer");
+    if (layout == IRS_REPLAY_FULL && !target) IRS_FAIL(ctx, IRS_E_INVALID, "irs_replay_paths: IRS_REPLAY_FULL needs dev_target");
+    if (layout == IRS_REPLAY_SLOT && target)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_replay_paths: IRS_REPLAY_SLOT takes the target from slot L-1: dev_target must be NULL");
+    if (ctx->dims.mask_mode == IRS_MASK_IRN && !user) IRS_FAIL(ctx, IRS_E_INVALID, "irs_replay_paths: user is null");
+    if (chunk < 1 || chunk > replay_chunk_max(ctx))
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_replay_paths: chunk must be in [1, min(max_rows, max_seqs) = %d]", replay_chunk_max(ctx));
+    const size_t need = irs_replay_layout(nullptr, chunk, ctx->dims.max_len, ctx->dims.d, nullptr);
+    if (scratch_bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "irs_replay_paths: scratch too small: %zu < %zu", scratch_bytes, need);
+    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_replay_paths: scratch must be 16-byte aligned");
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_replay_paths needs the whole catalog on one device");
+    if (layout == IRS_REPLAY_FULL && ctx->dims.mask_mode == IRS_MASK_IRN)
+        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_replay_paths: IRS_REPLAY_FULL on an IRS_MASK_IRN context (its mask gives column L-1 a meaning)");
+    if ((rc = ready(ctx))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    irs_replay_rows sc;
+    irs_replay_layout(scratch, chunk, ctx->dims.max_len, ctx->dims.d, &sc);
+    const int64_t *dec_user = ctx->dims.mask_mode == IRS_MASK_IRN ? sc.user : nullptr;
+    for (int r0 = 0; r0 < R; r0 += chunk) { // a pass: windows -> decode at hep, rows only -> target and item -> sweep -> record
+        const int m = R - r0 < chunk ? R - r0 : chunk;
+        const irs_replay_args a{layout, B, ctx->dims.max_len, P, path_ld, m, ctx->dims.n_item, seq0, hep0, user, target, paths,
+                                row_user + r0, row_step + r0, sc.seq, sc.hep, sc.user, status + r0, sc.item, sc.target};
+        if ((rc = irs_launch_replay_windows(ctx, a, s))) return rc;
+        if ((rc = irs_launch_decode(ctx, sc.seq, dec_user, m, nullptr, sc.hep, sc.x, nullptr, s))) return rc;
+        if ((rc = irs_launch_replay_score(ctx, sc, m, status + r0, lp_item + r0, lp_target + r0, rank + r0, s))) return rc;
+    }
+    return IRS_OK;
+}
+
 // ------------------------------------------------------------------ what the search loops share
 int irs_replay_steps(irs_ctx *ctx, irs_step_graph *g, const irs_step_key &key, const std::function<int(hipStream_t)> &body,
                      int times, hipStream_t s, int *capture_failed) {

@@ -391,6 +391,10 @@ int irs_launch_lse(irs_ctx *ctx, const float *xrows, int M, float *out_max, floa
 // the target sweep of the path trace: sc.count / sc.refid are its scratch, the four outputs go where the caller says
 int irs_launch_target_trace(irs_ctx *ctx, const float *xrows, const int64_t *seq, const int32_t *hep, int M, const irs_trace_rows &sc,
                             float *out_max, float *out_sum, float *out_tscore, int32_t *out_rank, hipStream_t s);
+// what irs_launch_target_trace runs behind its first launch (k_trace_target): the MODE_TRACE sweep against (out_tscore, sc.refid)
+// with sc.count cleared, the partials' reduction and the window correction.  The replay pass enters here with its own first launch.
+int irs_launch_trace_sweep(irs_ctx *ctx, const float *xrows, const int64_t *seq, const int32_t *hep, int M, const irs_trace_rows &sc,
+                           float *out_max, float *out_sum, float *out_tscore, int32_t *out_rank, hipStream_t s);
 int irs_launch_refresh_bias(irs_ctx *ctx, hipStream_t s);
 int irs_launch_lse_combine(irs_ctx *ctx, const float *mx, const float *sm, float *lse, int M, hipStream_t s);
 int irs_launch_ce_reduce(irs_ctx *ctx, const float *lse, const float *lab_score, const int64_t *labels0, int M, double *out,
@@ -473,6 +477,48 @@ int irs_launch_guide_pack(irs_ctx *ctx, const uint8_t *table, int64_t rows, int 
 // the path step while a guide is bound (irs_launch_path_step chooses it)
 int irs_launch_path_step_guided(irs_ctx *ctx, const irs_path_args &pa, int B, const float *val, const int64_t *ids0, int k,
                                 hipStream_t s);
+
+// ---- replay.hip ---- (path replay: irs_replay_windows / irs_replay_paths; arguments already validated)
+struct irs_replay_args { // the builder's arguments as the kernel takes them; the rows are [0, R) of row_user / row_step and of the outputs
+    int layout, B, L, P, path_ld, R;
+    int64_t n_item;
+    const int64_t *seq0;  // [B][L]
+    const int32_t *hep0;  // [B] (SLOT)
+    const int64_t *user;  // [B] or null
+    const int64_t *target;// [B] (FULL; only read for target_out)
+    const int64_t *paths; // [B][path_ld]
+    const int32_t *row_user, *row_step;
+    int64_t *seq_out;     // [R][L]
+    int32_t *hep_out;     // [R]
+    int64_t *user_out;    // [R] or null
+    int32_t *status;      // [R]
+    int64_t *item_out, *target_out; // [R] or null: the forced item (0: none) and the target (0: invalid row) of the replay pass
+};
+// the scratch of one pass of `chunk` rows, every array rounded up to 256 bytes; the trace rows last (irs_trace_layout)
+struct irs_replay_rows {
+    int64_t *seq, *user, *item, *target;
+    int32_t *hep;
+    float *iscore, *x;
+    irs_trace_rows tr;
+};
+static inline size_t irs_replay_layout(void *base, int chunk, int L, int d, irs_replay_rows *o) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t n_seq = up((size_t)chunk * L * 8), r8 = up((size_t)chunk * 8), r4 = up((size_t)chunk * 4), n_x = up((size_t)chunk * d * 4);
+    const size_t head = n_seq + 3 * r8 + 2 * r4 + n_x;
+    if (o) {
+        char *p = (char *)base;
+        o->seq = (int64_t *)p, o->user = (int64_t *)(p + n_seq), o->item = (int64_t *)(p + n_seq + r8);
+        o->target = (int64_t *)(p + n_seq + 2 * r8);
+        o->hep = (int32_t *)(p + n_seq + 3 * r8), o->iscore = (float *)(p + n_seq + 3 * r8 + r4);
+        o->x = (float *)(p + n_seq + 3 * r8 + 2 * r4);
+        irs_trace_layout(p + head, chunk, &o->tr);
+    }
+    return head + irs_trace_layout(nullptr, chunk, nullptr);
+}
+int irs_launch_replay_windows(irs_ctx *ctx, const irs_replay_args &a, hipStream_t s);
+// one pass behind the decode: scores of target and forced item, the trace sweep, the record into rows [0, M) of the caller's arrays
+int irs_launch_replay_score(irs_ctx *ctx, const irs_replay_rows &sc, int M, const int32_t *status, float *lp_item, float *lp_target,
+                            int32_t *rank, hipStream_t s);
 
 // ---- small device helpers ----
 #ifdef __HIPCC__

@@ -3197,6 +3197,13 @@ int irs_launch_target_trace(irs_ctx *ctx, const float *xrows, const int64_t *seq
     const int d = ctx->dims.d, L = ctx->dims.max_len;
     hipLaunchKernelGGL(k_trace_target, dim3(M), dim3(64), 0, s, xrows, d, ctx->proj_w, ctx->proj_b, ctx->n_local, seq, L, out_tscore,
                        sc.refid, sc.count);
+    return irs_launch_trace_sweep(ctx, xrows, seq, hep, M, sc, out_max, out_sum, out_tscore, out_rank, s);
+}
+
+// behind the launch that wrote out_tscore / sc.refid and cleared sc.count (k_trace_target, or the replay pass's k_replay_target)
+int irs_launch_trace_sweep(irs_ctx *ctx, const float *xrows, const int64_t *seq, const int32_t *hep, int M, const irs_trace_rows &sc,
+                           float *out_max, float *out_sum, float *out_tscore, int32_t *out_rank, hipStream_t s) {
+    const int d = ctx->dims.d, L = ctx->dims.max_len;
     SweepArgs a;
     sweep_common(ctx, a, xrows, M);
     const int max_waves = ctx->lse_slots / 2; // a wave writes two (max, sum) slots, one per lane half

@@ -546,6 +546,74 @@ class Engine:
             scratch.record_stream(stream)
             self.unbind_path_trace()
 
+    # ------------------------------------------------------------------ path replay (irs_replay_windows / irs_replay_paths)
+    def replay_scratch_bytes(self, chunk: int) -> int:
+        n = int(self.lib.irs_replay_scratch_bytes(self.h, chunk))
+        if n == 0:
+            raise IrsError(f"replay_scratch_bytes: chunk={chunk} (need 1 <= chunk <= min(max_rows, max_seqs) = "
+                           f"{min(self.max_rows, self.max_seqs)})")
+        return n
+
+    def _replay_inputs(self, what: str, layout: int, seq0, paths, row_user, row_step, hep0, users, P):
+        seq0, paths = self._dev(seq0, torch.int64), self._dev(paths, torch.int64)
+        row_user, row_step = self._dev(row_user, torch.int32), self._dev(row_step, torch.int32)
+        if seq0.dim() != 2 or seq0.shape[1] != self.L or paths.dim() != 2 or paths.shape[0] != seq0.shape[0] or \
+                row_user.dim() != 1 or row_user.shape != row_step.shape or row_user.numel() < 1:
+            raise IrsError(f"{what}: seq0 [B, max_len], paths [B, path_ld], row_user / row_step [R >= 1]")
+        B = seq0.shape[0]
+        hep0 = None if hep0 is None else self._dev(hep0, torch.int32)
+        users = None if users is None else self._dev(users, torch.int64)
+        if (hep0 is not None and hep0.numel() != B) or (users is not None and users.numel() != B):
+            raise IrsError(f"{what}: hep0 / users are per user [B]")
+        if layout == _lib.IRS_REPLAY_SLOT and hep0 is None:
+            raise IrsError(f"{what}: the slot layout needs hep0")
+        P = paths.shape[1] if P is None else int(P)
+        return seq0, paths, row_user, row_step, hep0, users, B, P
+
+    def replay_windows(self, layout: int, seq0, paths, row_user, row_step, *, hep0=None, users=None, P: Optional[int] = None):
+        """irs_replay_windows: the teacher-forced window of every row (row_user[r], row_step[r]) -- the user's start window
+        seq0[b] with paths[b, :i] applied by the layout's step rule (IRS_REPLAY_SLOT: the search loops', hep0 given;
+        IRS_REPLAY_FULL: the evaluator's post-padded windows).  paths int64 [B, path_ld], P = path_ld unless given.
+        Returns (seq [R, max_len] int64, hep [R] int32, users [R] int64 or None, status [R] int32)."""
+        seq0, paths, row_user, row_step, hep0, users, B, P = self._replay_inputs("replay_windows", layout, seq0, paths, row_user,
+                                                                                 row_step, hep0, users, P)
+        R = row_user.numel()
+        seq = torch.empty((R, self.L), dtype=torch.int64, device=self.device)
+        hep = torch.empty(R, dtype=torch.int32, device=self.device)
+        usr = torch.empty(R, dtype=torch.int64, device=self.device) if users is not None else None
+        status = torch.empty(R, dtype=torch.int32, device=self.device)
+        self._call(self.lib.irs_replay_windows, layout, _ptr(seq0), _ptr(hep0), _ptr(users), B, _ptr(paths), P, paths.shape[1],
+                   _ptr(row_user), _ptr(row_step), R, _ptr(seq), _ptr(hep), _ptr(usr), _ptr(status))
+        return seq, hep, usr, status
+
+    def replay_paths(self, layout: int, seq0, paths, row_user, row_step, *, hep0=None, users=None, targets=None,
+                     P: Optional[int] = None, chunk: Optional[int] = None, scratch: Optional[torch.Tensor] = None):
+        """irs_replay_paths: the path trace's three values for every row (row_user[r], row_step[r]) of saved paths, in passes of
+        `chunk` rows (default min(max_rows, max_seqs)): windows, one rows-only decode, one sweep of the float32 catalog per pass.
+        targets int64 [B]: the evaluator's layout (IRS_REPLAY_FULL); the slot layout reads them from seq0[:, -1].
+        Returns (lp_item [R], lp_target [R] float32, rank_target [R] int32, status [R] int32); an invalid row reads 0 / 0 / 0 and
+        IRS_ROW_NO_CANDIDATE."""
+        seq0, paths, row_user, row_step, hep0, users, B, P = self._replay_inputs("replay_paths", layout, seq0, paths, row_user,
+                                                                                 row_step, hep0, users, P)
+        targets = None if targets is None else self._dev(targets, torch.int64)
+        if targets is not None and targets.numel() != B:
+            raise IrsError("replay_paths: targets are per user [B]")
+        R = row_user.numel()
+        chunk = min(self.max_rows, self.max_seqs) if chunk is None else int(chunk)
+        if scratch is None:
+            scratch = torch.empty(self.replay_scratch_bytes(chunk), dtype=torch.uint8, device=self.device)
+        scratch = self._inplace(scratch, torch.uint8, "replay_paths: scratch")
+        lp_item, lp_target = (torch.empty(R, dtype=torch.float32, device=self.device) for _ in range(2))
+        rank = torch.empty(R, dtype=torch.int32, device=self.device)
+        status = torch.empty(R, dtype=torch.int32, device=self.device)
+        self._call(self.lib.irs_replay_paths, layout, _ptr(seq0), _ptr(hep0), _ptr(users), _ptr(targets), B, _ptr(paths), P,
+                   paths.shape[1], _ptr(row_user), _ptr(row_step), R, chunk, _ptr(scratch), scratch.numel(), _ptr(lp_item),
+                   _ptr(lp_target), _ptr(rank), _ptr(status))
+        for t in (scratch, seq0, paths, row_user, row_step, hep0, users, targets):  # (the passes only enqueue)
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(self.device))
+        return lp_item, lp_target, rank, status
+
     # ------------------------------------------------------------------ bound guide (irs_bind_guide)
     def guide_scratch_bytes(self, kind: int, F: int) -> int:
         """irs_guide_scratch_bytes: the packed table of a binary guide; 0 for a float guide, which is read where it lies."""

@@ -134,9 +134,12 @@ def test_model(config, rows: Sequence, irn, device, result_dir: str = None, verb
 
 # ------------------------------------------------------------------ pipeline.evaluate_prob
 def evaluate_prob(config, eval_config, evaluator, device, result_dir: str = None, results: dict = None,
-                  verbose: bool = True):
+                  verbose: bool = True, replay: bool = False):
     """Probability metrics of generated paths (reference pipeline.py:250-331).  The paths come from
-    `results` (what test_model returned) or from the .npy files under `result_dir`."""
+    `results` (what test_model returned) or from the .npy files under `result_dir`.
+    replay=True (extension, off by default): the rank and step-wise probability metrics -- irr, ir, t_probs, p_probs, ap, ii --
+    come from one batched replay of the paths (Evaluator.get_path_metrics_in_batch) instead of the step-by-step loop of
+    get_grad_in_batch and the two decodes of get_rr_increase_in_batch; the perplexity is get_pp_in_batch's either way."""
     say = print if verbose else (lambda *a, **k: None)
     if results is None:
         histories = np.load(os.path.join(result_dir, "histories.npy"), allow_pickle=True)
@@ -151,8 +154,12 @@ def evaluate_prob(config, eval_config, evaluator, device, result_dir: str = None
         for h, d, t, sp, lp in eval_batches_nn1(data, eval_config.batch_size):
             h, d, t, sp, lp = h.to(device), d.to(device), t.to(device), sp.to(device), lp.to(device)
             pp = evaluator.get_pp_in_batch(d, sp, lp)
-            irr, ir = evaluator.get_rr_increase_in_batch(h, d, t)
-            target_ps, path_ps, avg_ps, ii = evaluator.get_grad_in_batch(h, d, t, sp, lp)
+            if replay:
+                m = evaluator.get_path_metrics_in_batch(h, d, t, sp, lp)
+                irr, ir, target_ps, path_ps, avg_ps, ii = m["irr"], m["ir"], m["t_probs"], m["p_probs"], m["avg_ps"], m["iois"]
+            else:
+                irr, ir = evaluator.get_rr_increase_in_batch(h, d, t)
+                target_ps, path_ps, avg_ps, ii = evaluator.get_grad_in_batch(h, d, t, sp, lp)
             if len(perplexity) == 0:
                 perplexity, iis, irrs, irs, avg_acpt, p_probs, t_probs = pp, ii, irr, ir, avg_ps, path_ps, target_ps
             else:

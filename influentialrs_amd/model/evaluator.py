@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 import torch.optim as optim
 
+from .. import _lib
 from ._backend import make_scheduler, project_ce, project_ce_sharded
 from .layers import get_end_index
 
@@ -187,6 +188,60 @@ class Evaluator(nn.Module):
         irr = np.array([1 / end_r[i] - 1 / begin_r[i] for i in range(B)])
         ir = np.array([end_r[i] - begin_r[i] for i in range(B)])
         return irr, ir
+
+    REPLAY_CHUNK = 4096  # rows per pass of get_path_metrics_in_batch: one decode and one catalog sweep each
+
+    def get_path_metrics_in_batch(self, histories, new_seqs, targets, start_pos, l_paths):
+        """What get_grad_in_batch and get_rr_increase_in_batch return, out of ONE batched replay of the saved paths
+        (extension; irs_replay_paths, evaluator layout): a path is teacher-forced, so the window before every step is known
+        from the history and the path, and all sum(l_paths) windows are decoded and scored together instead of step by step.
+        Returns a dict: t_probs, p_probs float64 [B, S] and ranks int64 [B, S] (S = max l_path, zero-padded as get_grad_in_batch
+        pads), avg_ps, iois (lists, get_grad_in_batch's), irr, ir (arrays, get_rr_increase_in_batch's: its two rank rows are the
+        replay's steps 0 and l_path - 1).  The windows are max_len wide (histories has max_len + 1 columns); one device holds
+        the catalog.  The three methods it stands in for are unchanged."""
+        self.net.eval()
+        hip = self.net._hip
+        if hip.world != 1:
+            raise ValueError("get_path_metrics_in_batch is not built for an item-sharded catalog: irs_replay_paths needs the "
+                             "whole catalog on one device (use get_grad_in_batch / get_rr_increase_in_batch)")
+        dev = histories.device
+        if dev.type != "cuda":
+            raise ValueError("get_path_metrics_in_batch runs on the HIP engine only: move the evaluator and its batch to a GPU "
+                             "(there is no CPU fallback in this package)")
+        B, Lw = histories.size(0), histories.size(1) - 1
+        if Lw != self.net.max_len:
+            raise ValueError(f"get_path_metrics_in_batch: windows of {Lw} items, the evaluator's max_len is {self.net.max_len}")
+        l_host = l_paths.detach().cpu().long()  # (the rows are listed on the host)
+        if int(l_host.min().item()) < 1:
+            raise ValueError("get_path_metrics_in_batch: every path needs at least one step")
+        S, R = int(l_host.max().item()), int(l_host.sum().item())
+        l_dev, start_pos = l_host.to(dev), start_pos.to(dev).long()
+        off = torch.arange(S, device=dev).unsqueeze(0)
+        idx = (start_pos.unsqueeze(1) + off).clamp(max=new_seqs.size(1) - 1)
+        paths = torch.where(off < l_dev.unsqueeze(1), torch.gather(new_seqs.long(), 1, idx), torch.zeros_like(idx)).contiguous()
+        row_user = torch.repeat_interleave(torch.arange(B), l_host)
+        row_step = torch.arange(R) - torch.repeat_interleave(torch.cumsum(l_host, 0) - l_host, l_host)
+        chunk = min(R, self.REPLAY_CHUNK)
+        eng = hip.get(chunk, chunk)
+        lp_item, lp_target, rank, status = eng.replay_paths(
+            _lib.IRS_REPLAY_FULL, histories[:, :-1].long().contiguous(), paths, row_user.to(torch.int32).to(dev),
+            row_step.to(torch.int32).to(dev), targets=targets.to(dev).long(), chunk=chunk)
+        if int(status.ne(0).sum().item()) > 0:
+            raise IndexError("get_path_metrics_in_batch: a path item outside [1, n_item], or an empty history with an empty path")
+        t_probs, p_probs = np.zeros((B, S), dtype=np.float64), np.zeros((B, S), dtype=np.float64)
+        ranks = np.zeros((B, S), dtype=np.int64)
+        ru, rs = row_user.numpy(), row_step.numpy()
+        t_probs[ru, rs], p_probs[ru, rs], ranks[ru, rs] = lp_target.cpu().numpy(), lp_item.cpu().numpy(), rank.cpu().numpy()
+        avg_ps, iois = [], []
+        for i in range(B):
+            tp = t_probs[i][t_probs[i] < 0]
+            pp = p_probs[i][p_probs[i] < 0]
+            iois.append(tp[-1] - tp[0])
+            avg_ps.append(sum(pp) / len(pp))
+        begin_r, end_r = ranks[:, 0], ranks[np.arange(B), l_host.numpy() - 1]
+        irr = np.array([1 / end_r[i] - 1 / begin_r[i] for i in range(B)])
+        ir = np.array([end_r[i] - begin_r[i] for i in range(B)])
+        return dict(t_probs=t_probs, p_probs=p_probs, ranks=ranks, avg_ps=avg_ps, iois=iois, irr=irr, ir=ir)
 
     def get_pp_in_batch(self, new_seqs, start_pos, l_paths):
         """Mean negative log-likelihood of each path given its history

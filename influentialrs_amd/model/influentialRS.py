@@ -30,7 +30,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.optim as optim
 
-from .._lib import IRS_BEAM_STOP_ALL, IRS_BEAM_STOP_BEST, IRS_MASK_IRN, IRS_ROW_NO_CANDIDATE, IRS_ROW_OFFERED
+from .._lib import IRS_BEAM_STOP_ALL, IRS_BEAM_STOP_BEST, IRS_MASK_IRN, IRS_REPLAY_SLOT, IRS_ROW_NO_CANDIDATE, IRS_ROW_OFFERED
 from ._backend import HipBackend, check_trunk, make_scheduler, pad_ragged_ids, project_ce, project_ce_sharded, train_trunk_default, trunk_hip
 from .layers import PositionalEncoding, get_item_index
 
@@ -202,16 +202,17 @@ def _takes_exact_candidates(fn):
     return call
 
 
-def path_trace_summary(lp_item, lp_target, rank_target, paths, targets):
+def path_trace_summary(lp_item, lp_target, rank_target, paths, targets, n_live=None):
     """get_seq_in_batch's last_trace from the search's arrays ([B, P] each; `paths` before the host cut or after it, `targets`
-    [B]).  A user's live steps end with its arrival (the first path entry equal to its target) or run to P; behind them the
-    three arrays are cut to 0 like the path.  Over the live steps, as Evaluator.get_grad_in_batch forms iois and avg_ps:
+    [B]).  A user's live steps end with its arrival (the first path entry equal to its target) or run to P (n_live[b] where
+    given: a replayed path that ends early); behind them the three arrays are cut to 0 like the path.  Over the live steps, as
+    Evaluator.get_grad_in_batch forms iois and avg_ps:
     ioi = last lp_target - first, ior = first rank_target - last (positive: the target moved up), avg_lp_item = mean lp_item."""
     lp_item = np.array(lp_item, dtype=np.float32)
     lp_target = np.array(lp_target, dtype=np.float32)
     rank_target = np.array(rank_target, dtype=np.int32)
     B, P = lp_item.shape
-    n_steps = np.full(B, P, dtype=np.int64)
+    n_steps = np.full(B, P, dtype=np.int64) if n_live is None else np.array(n_live, dtype=np.int64)
     for i in range(B):
         pos = get_item_index(np.asarray(paths[i]), np.asarray(targets).reshape(-1)[i])
         if pos != -1:
@@ -348,6 +349,59 @@ class IRSNN(nn.Module):
                 hit_count += 1
             rr.append(np.reciprocal(float(ranks[i])))
         return hit_count, np.array(rr)
+
+    REPLAY_CHUNK = 4096  # rows per pass of replay_paths: one decode and one catalog sweep each
+
+    def replay_paths(self, seqs, users, paths, gap_len=0):
+        """The path trace of SAVED paths (extension; irs_replay_paths, the search loops' layout): what get_seq_in_batch(trace=True)
+        leaves in self.last_trace, for paths from any search -- greedy, beam, the sharded loops' front end, paths_d_<n>.npy.
+        seqs [B, L] are the search's input windows (target in the last slot, gap_len as passed to the search), paths [B, P] the
+        chosen items (float or integer, 0 = nothing).  A path is teacher-forced, so all steps of all users are decoded and
+        scored in one batch: user b's rows run up to and including its arrival (the first entry equal to its target), or over
+        its entries before the first 0.  Returns path_trace_summary's dict: lp_item, lp_target, rank_target [B, P] cut behind
+        the live steps, n_steps [B], ioi, ior, avg_lp_item.  One device holds the catalog."""
+        hip = self.net._hip
+        if hip.world != 1:
+            raise ValueError("replay_paths is not built for an item-sharded catalog: irs_replay_paths needs the whole catalog "
+                             "on one device")
+        dev = seqs.device
+        if dev.type != "cuda":
+            raise ValueError("replay_paths runs on the HIP engine only: move the network and its batch to a GPU (there is no "
+                             "CPU fallback in this package)")
+        self.net.eval()
+        B, L = seqs.shape
+        paths_np = np.asarray(paths.detach().cpu().numpy() if torch.is_tensor(paths) else paths)
+        if paths_np.ndim != 2 or paths_np.shape[0] != B:
+            raise ValueError(f"replay_paths: paths must be [B = {B}, P], got {paths_np.shape}")
+        items = paths_np.astype(np.int64)
+        P = items.shape[1]
+        targets = seqs[:, -1].detach().cpu().numpy()
+        n_live = np.zeros(B, dtype=np.int64)
+        for i in range(B):
+            zero = np.where(items[i] == 0)[0]
+            n_live[i] = zero[0] if len(zero) else P
+            pos = get_item_index(items[i, :n_live[i]], targets[i])
+            if pos != -1:
+                n_live[i] = pos + 1
+        if int(n_live.min()) < 1:
+            raise ValueError("replay_paths: every path needs at least one step")
+        n_t = torch.from_numpy(n_live)
+        R = int(n_live.sum())
+        row_user = torch.repeat_interleave(torch.arange(B), n_t)
+        row_step = torch.arange(R) - torch.repeat_interleave(torch.cumsum(n_t, 0) - n_t, n_t)
+        chunk = min(R, self.REPLAY_CHUNK)
+        eng = hip.get(chunk, chunk)
+        hep0 = torch.full((B,), L - (gap_len + 1) - 1, dtype=torch.int32, device=dev)
+        lp_item, lp_target, rank, status = eng.replay_paths(
+            IRS_REPLAY_SLOT, seqs.to(torch.int64).contiguous(), torch.from_numpy(items).to(dev), row_user.to(torch.int32).to(dev),
+            row_step.to(torch.int32).to(dev), hep0=hep0, users=users.to(dev).to(torch.int64), chunk=chunk)
+        if int(status.ne(0).sum().item()) > 0:
+            raise IndexError("replay_paths: a path item outside [1, n_item], or gap_len outside the window")
+        out = [np.zeros((B, P), dtype=np.float32), np.zeros((B, P), dtype=np.float32), np.zeros((B, P), dtype=np.int32)]
+        ru, rs = row_user.numpy(), row_step.numpy()
+        for a, v in zip(out, (lp_item, lp_target, rank)):
+            a[ru, rs] = v.cpu().numpy()
+        return path_trace_summary(*out, items, targets, n_live=n_live)
 
     def _beam_paths(self, seqs, users, max_path_len, gap_len, beam_width, beam_stop=None, exact_candidates=False, excl=None):
         """Best-beam paths [B, P] + status via the build-defined beam search (no reference
