@@ -160,9 +160,6 @@ static int irs_cu_count() {
 // rounds (they come first, so the order of ids holds).
 // Inputs: the block counts and the CU count, nothing else.  n_wg[1] = the first half-live id (= n_wg[0] when there is none).
 #define SEQ_TAIL_BLOCKS 8
-#ifndef SEQ_LAB_PLAN
-#define SEQ_LAB_PLAN 0
-#endif
 // half tile (0 .. nb - 1, relative to the sequence's first) of block blk of a sequence of nb blocks starting at an even / odd half
 __host__ __device__ __forceinline__ int seq_half_of_block(bool slot_odd, int nb, int blk) {
     const int mir = nb - 1 - blk;
@@ -303,12 +300,11 @@ __global__ void __launch_bounds__(1024) k_plan_seq(const int32_t *__restrict__ c
         int nwg, nbig, ntail, tail0, sel = 0;
         count(0x7FFFFFFF, 0, nwg, nbig, ntail, tail0);
         const int rounds = n_cu > 0 ? nwg / n_cu : 0, rem = nwg - rounds * n_cu;
-        if (SEQ_LAB_PLAN == 1 || (SEQ_LAB_PLAN == 0 && n_cu > 0 && rem > 0 && 2 * rem <= n_cu && nbig <= rounds * n_cu)) {
+        if (n_cu > 0 && rem > 0 && 2 * rem <= n_cu && nbig <= rounds * n_cu) {
             int nwg2, nbig2, ntail2, tail02;
-            // (lab) SEQ_LAB_PLAN 1: every sequence of at most CT blocks in a half-live workgroup; 2: the plan without the rule
-            count(SEQ_LAB_PLAN == 1 ? 0 : rounds * n_cu, 1, nwg2, nbig2, ntail2, tail02);
+            count(rounds * n_cu, 1, nwg2, nbig2, ntail2, tail02);
             // (more than one half-live workgroup per CU would cost more than the full round)
-            if (SEQ_LAB_PLAN == 1 || ntail2 <= n_cu) sel = 1, nwg = nwg2, tail0 = tail02;
+            if (ntail2 <= n_cu) sel = 1, nwg = nwg2, tail0 = tail02;
         }
         s_sel = sel, s_nwg = nwg;
         n_wg[0] = nwg, n_wg[1] = tail0 < 0 ? nwg : tail0;
@@ -1528,23 +1524,11 @@ __host__ __device__ constexpr int x6_step_b(int NPL) { return 8 * NPL * 1024; }
 #define X6_H3_WSHIFT 8
 __host__ __device__ constexpr float x6_wscale(int NPL) { return NPL == 2 ? (float)(1 << X6_H3_WSHIFT) : 1.0f; }
 __host__ __device__ constexpr size_t x6_layer_bytes(int NT, int NPL = 3) { return (size_t)x6_nstep(NT) * x6_step_b(NPL); }
-// ring slots (X6_NSLOT2 for float16 planes: their steps are 16 KB, so four fit twice per CU -- two steps of DMA in flight
+// ring slots (four for float16 planes: their steps are 16 KB, so four fit twice per CU -- two steps of DMA in flight
 // behind the one being multiplied)
-#ifndef X6_NSLOT2
-#define X6_NSLOT2 4
-#endif
-__host__ __device__ constexpr int x6_nslot(int NPL) { return NPL == 2 ? X6_NSLOT2 : 3; }
+__host__ __device__ constexpr int x6_nslot(int NPL) { return NPL == 2 ? 4 : 3; }
 __host__ __device__ constexpr int x6_lds_bytes(int NT, int NPL = 3) { return x6_nslot(NPL) * x6_step_b(NPL) + (256 + 12 * 32 * NT) * 4; }
 typedef __attribute__((ext_vector_type(8))) _Float16 x6_f16x8;
-#ifndef X6_RESID_LATE
-#define X6_RESID_LATE 1
-#endif
-#ifndef X6_RING4
-#define X6_RING4 4 // fragment register sets of k_block_x6 at d = 128, float16 planes (lab: 8 measured no faster, 16 more registers)
-#endif
-#ifndef X6_SPLIT_ACC4
-#define X6_SPLIT_ACC4 0 // one-tile steps at d = 128: 1 = h.h products on their own accumulator instead of a second read of W_h (lab: no faster, 16 more registers)
-#endif
 #ifndef X6_NW
 #define X6_NW 4 // waves per workgroup of k_block_x6 (tools/x6_lab measures both)
 #endif
@@ -1639,10 +1623,7 @@ struct BlockX6Args {
     // one row per sequence of that layer, and for ONE query the K and V projections are absorbed (k_absorb_qu / _attn / _out behind
     // k_attn_row32): score_j = (W_k,h^T q_h) . x'_j + q_h . b_k,h and out_h = W_v,h (sum_j p_j x'_j) + b_v,h -- no q | k | v of
     // the last layer for every token, no K / V images, nothing written to Af for it.
-    // (SEQ_LAST_ABSORB = 0, lab: behind layer n_lay - 1 the kernel runs the FRONT of layer n_lay too -- q | k | v of every token,
-    // K / V images, and the attention of the ONE 16-query block that holds the consumed token seq_qrow[b]; its output row is
-    // gathered from the attention tiles by the host side.  seq_qrow is read by that form only.)
-    const int32_t *seq_qrow;
+    const int32_t *seq_qrow; // each sequence's consumed token (the kernel does not read it: the last layer's handlers do, from the context)
     const int32_t *tile_seq, *tile_qb, *seq_off, *seq_cnt, *seq_padq, *seq_row0, *n_wg_dev;
     const float *r_u;
     int mask_mode;
@@ -1780,30 +1761,8 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
 // of 16 k and 16 q -- low planes of elements below 2^-3 are subnormal float16, 2^-25 absolute instead of 2^-22 relative -- change
 // nothing: rows against the two-kernel path max 1.88e-5 / mean 3.98e-7 with the factor, 1.87e-5 / 4.0e-7 without, and four more
 // vector instructions per score tile.)  Range: |k|, |q| < 65504 is the V rows' bound (irs_h3_operand_bound: st[6] covers all of W_in).
-#define SEQ_KQ_SCALE 1.0f
-#ifndef SEQ_ASM_DMA
-#define SEQ_ASM_DMA 1
-#endif
 #ifndef SEQ_EXP
 #define SEQ_EXP 0 // (lab, tools/seq_lab.sh: 1 = no attention compute, 2 = asynchronous tail reads: timing experiments, results wrong)
-#endif
-#ifndef SEQ_IDLE_SKIP
-#define SEQ_IDLE_SKIP 1 // (lab: 0 = a wave with two empty halves runs every step on zeros, as it did through round 5)
-#endif
-#ifndef SEQ_FRONT_RIDE
-#define SEQ_FRONT_RIDE 1 // (lab, tools/seq_lab.sh: 0 = a head's steps in the order q, k, v with all three epilogues behind the v step, as through round 7)
-#endif
-#ifndef SEQ_LAST_ABSORB
-// 1: the launch runs layers 0 .. n_lay - 1 and ends; the model's last layer attends from x' with absorbed K / V projections
-// (k_absorb_qu, k_absorb_attn, k_absorb_out).  (lab, tools/seq_lab.sh last0: 0 = an extra trip of the layer loop runs the last
-// layer's front for every token and the attention of each consumed token's block, gathered by the host side, as before.)
-#define SEQ_LAST_ABSORB 1
-#endif
-#ifndef SEQ_BATCHED_IO
-// 1: the prologue requests the 32 pieces of a token's embedding and position rows back to back and waits once; LayerNorm 3
-// stores its sixteen x' pieces from inline asm with no wait between them.  (lab, tools/seq_lab.sh io0: 0 = the placement up to
-// here -- a piece pair per round trip in the prologue, a compiler-written vmcnt(0) in front of every x' store.)
-#define SEQ_BATCHED_IO 1
 #endif
 // SEQ layout of the dynamic LDS behind the ring and the parameter vectors (x6_seq_lds_bytes)
 #define X6_SEQ_VECS (256 + 12 * 32 * 4 + 384)   // floats: the parameter vectors + this layer's in-projection bias
@@ -1849,7 +1808,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     // operations retire in order, so "all but the newest 8 + 16" is exactly that, and the first four steps' counted waits
     // allow one tile set beside the newest DMA group; the compiler's own waits bring each attention tile in when its step
     // splits it.  (tools/x6_lab stamps: the start was 16.8 K of a wave's 100 K cycles.)
-    constexpr bool RESID_LATE = X6_RESID_LATE && NPL == 2 && NT == 4 && !EMBED && NSLOT == 4 && (NW == 4 || NW == 8);
+    constexpr bool RESID_LATE = NPL == 2 && NT == 4 && !EMBED && NSLOT == 4 && (NW == 4 || NW == 8);
     // (SEQ keeps the residual apart the same way -- out-projection from zero, residual added with b_o -- without the counted start)
     constexpr bool RESID_SEP = RESID_LATE || SEQ;
     constexpr int NLOAD = 4 * NT; // plain global loads of one set of a wave's input tiles (attention output; residual)
@@ -1871,7 +1830,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     // sh_b[h] (-1: nothing there; a wave with two empty halves keeps the ring and the barriers going: the idle path below).  Normally the two are
     // mirror images of ONE sequence (blocks i and nb - 1 - i: causal attention costs qb + 1 key tiles for block qb, so every
     // wave of a sequence gets nb + 1 of them); the odd middle blocks of two sequences may share a tile (k_plan_seq).
-    int sh_b[2] = {-1, -1}, sh_qb[2] = {0, 0}, sh_cnt[2] = {0, 0}, sh_pq[2] = {-1, -1}, sh_row0[2] = {0, 0}, sh_pb[2] = {-1, -1};
+    int sh_b[2] = {-1, -1}, sh_qb[2] = {0, 0}, sh_cnt[2] = {0, 0}, sh_pq[2] = {-1, -1}, sh_row0[2] = {0, 0};
     int sh_off[2] = {0, 0};
     float sh_ru[2] = {0.f, 0.f};
     bool sh_tgt[2] = {false, false};
@@ -1895,7 +1854,6 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                 sh_pq[h] = __builtin_amdgcn_readfirstlane(a.seq_padq[b_]), sh_row0[h] = __builtin_amdgcn_readfirstlane(a.seq_row0[b_]);
                 sh_ru[h] = irn_ ? a.r_u[b_] : 0.f;
                 sh_tgt[h] = irn_ && a.seq[(int64_t)b_ * a.L + a.L - 1] != 0;
-                sh_pb[h] = (__builtin_amdgcn_readfirstlane(a.seq_qrow[b_]) - off_) >> 4;
                 sh_pm[h] = seq_diag_mask(sh_cnt[h], sh_qb[h], sh_tgt[h], sh_pq[h]);
                 sh_tadd[h] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, irn_ ? (1.0f - sh_ru[h]) * 1.4426950408889634f : 0.f)));
             }
@@ -1935,10 +1893,10 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             vecs[V_O + 5 * D + tid] = a.c ? pv[11] : 0.f;
         }
     } else if constexpr (NT == 4) {
-        if constexpr (SEQ && SEQ_BATCHED_IO) {
+        if constexpr (SEQ) {
             // layer 0's parameter vectors in ONE round trip: unconditional loads the compiler does not see (a lane beyond the
-            // vectors reads their last element and stores nothing), one wait.  (The plain form below compiled to three dependent
-            // round trips -- the conditional tail loads each behind the stores in front of them -- ahead of the prologue's gather.)
+            // vectors reads their last element and stores nothing), one wait.  (Plain conditional loads compiled to three dependent
+            // round trips -- the tail loads each behind the stores in front of them -- ahead of the prologue's gather.)
             constexpr int NV_ = (X6_SEQ_VECS + 64 * NW - 1) / (64 * NW);
             static_assert(NV_ == 5, "five operands in the wait below");
             unsigned int vq[NV_];
@@ -1951,10 +1909,6 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
 #pragma unroll
             for (int k = 0; k < NV_; ++k)
                 if (tid + 64 * NW * k < X6_SEQ_VECS) vecs[tid + 64 * NW * k] = __builtin_bit_cast(float, vq[k]);
-        } else if constexpr (SEQ) {
-#pragma unroll
-            for (int k = 0; k < (X6_SEQ_VECS + 64 * NW - 1) / (64 * NW); ++k)
-                if (tid + 64 * NW * k < X6_SEQ_VECS) vecs[tid + 64 * NW * k] = a.vecpack[tid + 64 * NW * k];
         }
         if (!SEQ && tid < 256) {
             if (!EMBED) vecs[V_B1 + tid] = a.b1[tid];
@@ -1991,10 +1945,6 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             }
         }
     }
-#ifdef X6_STAGGER
-    if (blockIdx.x >= 256 && blockIdx.x < 512)
-        for (int i = 0; i < X6_STAGGER; ++i) __builtin_amdgcn_s_sleep(127); // (lab) second resident workgroup of a CU starts ~4 us x N late
-#endif
     int mtile = SEQ ? (int)blockIdx.x * NW + wave : (m0 >> 5) + wave; // (not const: SEQ launders it per layer, see layer_body)
     // (SEQ) this lane's half, its sequence's image row of its token
     const bool l_h1 = li >= 16;
@@ -2009,18 +1959,18 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     constexpr int qoff = NOUT * QP0;                // the q tiles' steps (NT tiles x HT) are skipped when QP0
     constexpr int nsteps_c = NFRONT + x6_nstep(NT) - qoff; // executed steps; step i of the sequence is stream block i (+ qoff past the FFN)
     // SEQ: per layer NFRONT + NPRE = 32 steps + ONE empty step (33 = 0 mod NSLOT: the ring's slot numbering repeats from layer
-    // to layer); the last layer has its k | v tail (8 steps) in place of the empty step.  `nsteps` only bounds the ring refills:
-    // behind a layer that is not the last one the refills go on into the next layer's stream.
+    // to layer); behind a layer that is not the launch's last one the refills go on into the next layer's stream.
     constexpr int SEQ_LSTEPS = NFRONT + NPRE + 1;
     static_assert(!SEQ || SEQ_LSTEPS % NSLOT == 0, "slot numbering repeats per layer");
-    // (the non-SEQ kernels see compile-time constants here: `nsteps` and `last` are macros over a constexpr condition)
-    int ly = 0, nsteps_rt = nsteps_c;
-    bool last_rt = true;
-    // (SEQ_LAST_ABSORB: no trip of the layer loop is a front-only one -- `last` and `nsteps` are constants again; end_rt marks the
-    //  launch's last layer, which ends the ring behind its own steps: nothing is fetched at mid-step 31, no empty step follows)
+    int ly = 0;
+    // end_rt (SEQ) marks the launch's last layer, which ends the ring behind its own steps: nothing is fetched at mid-step 31, no
+    // empty step follows.
     bool end_rt = false;
-#define nsteps (SEQ ? (SEQ_LAST_ABSORB ? (1 << 20) : nsteps_rt) : nsteps_c)
-#define last (!SEQ || (!SEQ_LAST_ABSORB && last_rt))
+    // Constants of the instantiation.  `nsteps` bounds the ring refills: the executed steps of a one-layer kernel, no bound for
+    // SEQ (its refills run on through the layer boundaries until end_rt ends them).  `last`: behind the body's steps comes this
+    // stream's q | k | v tail and the kernel ends -- every kernel but SEQ, where the empty step and the next layer's front follow.
+#define nsteps (SEQ ? (1 << 20) : nsteps_c)
+#define last (!SEQ)
     // DMA of sequence step i into slot i % NSLOT: this wave's pieces PPW wave .. PPW wave + PPW - 1.  The slot holds the
     // step's block in stream order, and the instruction's immediate offset moves the global source AND the LDS destination
     // (tools/dma_probe.hip), so the pieces share one address register pair and one M0: base = the middle piece, offsets
@@ -2035,14 +1985,14 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     const uint4 *dma_src_q = SEQ ? a.Wbase + (long long)(a.nl_total - 1) * a.wstride + (PPW * wave + PPG / 2) * 64 + lane : dma_src;
     const uint4 *dma_src_qn = dma_src; // (layer l + 1's q | k | v sits in stream l)
     // SEQ: front step i = 3 h + p of head h computes component (p + 1) % 3 of q | k | v (0 q, 1 k, 2 v): k first, then v with K's
-    // epilogue riding it, then q with V's (SEQ_FRONT_RIDE = 0: q, k, v); it consumes q | k | v tile NT c + h of the stream's tail
+    // epilogue riding it, then q with V's; it consumes q | k | v tile NT c + h of the stream's tail
     // region.  The ONE place that knows the order: the live waves' refills, the idle path and the prefetch of the next layer's
     // front all go through issue().
-    auto front_blk = [](int i) __attribute__((always_inline)) { return NPRE + NT * ((i % 3 + (SEQ_FRONT_RIDE ? 1 : 0)) % 3) + i / 3; };
+    auto front_blk = [](int i) __attribute__((always_inline)) { return NPRE + NT * ((i % 3 + 1) % 3) + i / 3; };
     auto issue = [&](int i) __attribute__((always_inline)) {
         // SEQ: front step i is block front_blk(i) of the OTHER stream's tail region;
-        // body step i is block i - NFRONT of this layer's stream; behind the body: the last layer's k | v tail, else the empty
-        // step (nothing to fetch) and then the NEXT layer's front steps
+        // body step i is block i - NFRONT of this layer's stream; behind the body: the empty step (nothing to fetch) and then
+        // the NEXT layer's front steps
         const int ib = i - NFRONT;
         int blk = (SEQ && i < NFRONT) ? front_blk(i) : (ib < NPRE ? ib : ib + qoff);
         const uint4 *dsrc = (SEQ && i < NFRONT) ? dma_src_q : dma_src;
@@ -2055,12 +2005,11 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             constexpr int grp = decltype(gc)::value;
             const uint4 *src = dsrc + (size_t)blk * (STEP_B / 16) + grp * PPG * 64;
             char *dst = smem + (i % NSLOT) * STEP_B + (PPW * wave + grp * PPG + PPG / 2) * 1024;
-            if constexpr (SEQ && SEQ_ASM_DMA) {
+            if constexpr (SEQ) {
                 // (the sequence-resident form: the DMA as inline asm.  Behind the builtin the compiler puts s_waitcnt vmcnt(0) in
                 //  front of every LDS access it can see -- the image writes, the attention's reads -- i.e. a refill issued before
-                //  the attention would be WAITED for there; the first version therefore left the v step's refill to the end of the
-                //  head and the next head's first step then waited out the whole DMA latency.  The ring's slots are disjoint from
-                //  everything the compiler reads or writes, and every consumer of a slot sits behind a counted wait + barrier.)
+                //  the attention would be WAITED for there.  The ring's slots are disjoint from everything the compiler reads or
+                //  writes, and every consumer of a slot sits behind a counted wait + barrier.)
                 const unsigned int m0v = lds0 + (unsigned int)((i % NSLOT) * STEP_B + (PPW * wave + grp * PPG + PPG / 2) * 1024);
                 x6_static_for<0, PPG>([&](auto jc) __attribute__((always_inline)) {
                     constexpr int off = (decltype(jc)::value - PPG / 2) * 1024;
@@ -2080,7 +2029,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             }
         });
     };
-    if constexpr (SEQ && SEQ_IDLE_SKIP) {
+    if constexpr (SEQ) {
         // ================= a wave with two empty halves: the ring duty and the barriers of the schedule below, nothing else.
         // Its tiles would be zeros that only this wave reads back (the attention scratch, the x' tile; the host gathers consumed
         // rows from live tiles only), and the K / V images take no rows from it -- so it issues its PPW pieces of every step at
@@ -2095,18 +2044,13 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             x6_static_for<1, LEAD>([&](auto ic) __attribute__((always_inline)) { issue(S0 + decltype(ic)::value); }); // (as the live path)
             static_assert(LEAD == 2 && S0 == 0, "the waits below are vmcnt(0): X6_PUBLISH with three ring slots");
 #pragma unroll 1
-            for (ly = 0; ly < a.n_lay + (SEQ_LAST_ABSORB ? 0 : 1); ++ly) {
-#if SEQ_LAST_ABSORB
-                end_rt = ly == a.n_lay - 1; // (the ring ends with the live path's: behind the last full layer's own steps)
-#else
-                last_rt = ly == a.n_lay;
-                nsteps_rt = last_rt ? NFRONT : (1 << 20);
-#endif
+            for (ly = 0; ly < a.n_lay; ++ly) {
+                end_rt = ly == a.n_lay - 1; // (the ring ends with the live path's: behind the launch's last layer's own steps)
                 dma_src = a.Wbase + (long long)ly * a.wstride + (PPW * wave + PPG / 2) * 64 + lane;
                 dma_src_q = a.Wbase + (long long)(ly == 0 ? a.nl_total - 1 : ly - 1) * a.wstride + (PPW * wave + PPG / 2) * 64 + lane;
                 dma_src_qn = dma_src;
                 float nvi[(X6_SEQ_VECS + 64 * NW - 1) / (64 * NW)];
-                if (!last && !end_rt) {
+                if (!end_rt) {
 #pragma unroll
                     for (int k = 0; k < (X6_SEQ_VECS + 64 * NW - 1) / (64 * NW); ++k)
                         nvi[k] = (tid + 64 * NW * k < X6_SEQ_VECS) ? a.vecpack[(size_t)(ly + 1) * X6_SEQ_VECS + tid + 64 * NW * k] : 0.f;
@@ -2114,14 +2058,11 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                 // (unrolled: the ring slot of a step is part of the DMA's address arithmetic, a constant per step)
                 x6_static_for<0, NFRONT>([&](auto ic) __attribute__((always_inline)) {
                     constexpr int i = decltype(ic)::value;
-                    if (i + 1 < nsteps) { // X6_PUBLISH(i)
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        __builtin_amdgcn_s_barrier();
-                        if (i + LEAD < nsteps) issue(i + LEAD);
-                    }
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // X6_PUBLISH(i)
+                    __builtin_amdgcn_s_barrier();
+                    issue(i + LEAD);
                     if constexpr (i % 3 == 2) __builtin_amdgcn_s_barrier(); // head i / 3's rows are in the images
                 });
-                if (last) break;
                 x6_static_for<NFRONT, NFRONT + NPRE>([&](auto ic) __attribute__((always_inline)) {
                     constexpr int i = decltype(ic)::value;
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2140,10 +2081,9 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                 issue(SEQ_LSTEPS - 1 + LEAD);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (no LDS-DMA piece in flight when the wave ends)
-            // (SEQ_BATCHED_IO: the wave ends HERE.  A return joins the live path's control flow at the kernel's end, and the
-            //  compiler then carries this loop's parameter loads as pending into the live prologue: a vmcnt wait in front of it.)
-            if constexpr (SEQ_BATCHED_IO) __builtin_amdgcn_endpgm();
-            return;
+            // (The wave ends HERE.  A return joins the live path's control flow at the kernel's end, and the compiler then carries
+            //  this loop's parameter loads as pending into the live prologue: a vmcnt wait in front of it.)
+            __builtin_amdgcn_endpgm();
         }
     }
     // accumulators start from the residual x; the attention output tile 0 is requested with it
@@ -2167,57 +2107,43 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             // (profiles/seq_round_trips/README.md): the whole prologue -- plan words, parameter vectors, this gather, the first
             // step's DMA and barrier -- is 28.5 K of a wave's 820 K ticks on the bench windows, about 15 of its 440 us; with the
             // gather as sixteen dependent round trips it was 30.9 K.  The tile is stored once: layer 0's residual.  Dead lanes hold zeros.
-            // (SEQ_BATCHED_IO) The token's index comes from a laundered copy of the lane: s_j itself lives through the layer loop, is
-            // spilled at the kernel's start and was reloaded from scratch in front of the tok_row load -- one more round trip in
-            // the chain tok_row -> seq -> rows.
-            bool h1_g = l_h1;
-            int lb_g = l_b, sj_g = s_j;
-            if constexpr (SEQ_BATCHED_IO) {
-                int ln_ = lane;
-                asm volatile("" : "+v"(ln_));
-                h1_g = (ln_ & 31) >= 16;
-                lb_g = h1_g ? sh_b[1] : sh_b[0];
-                sj_g = lb_g >= 0 ? 16 * (h1_g ? sh_qb[1] : sh_qb[0]) + (ln_ & 15) : 0x3FFFFFFF;
-            }
+            // The token's index comes from a laundered copy of the lane: s_j itself lives through the layer loop, is spilled at the
+            // kernel's start and was reloaded from scratch in front of the tok_row load -- one more round trip in the chain
+            // tok_row -> seq -> rows.
+            int ln_ = lane;
+            asm volatile("" : "+v"(ln_));
+            const bool h1_g = (ln_ & 31) >= 16;
+            const int lb_g = h1_g ? sh_b[1] : sh_b[0];
+            const int sj_g = lb_g >= 0 ? 16 * (h1_g ? sh_qb[1] : sh_qb[0]) + (ln_ & 15) : 0x3FFFFFFF;
             const bool live = lb_g >= 0 && sj_g < (h1_g ? sh_cnt[1] : sh_cnt[0]);
             // (its own statement with the wait inside: the compiler otherwise merges what the idle waves' loop left pending into a
             //  second wait at the head of this path)
             int orig = 0;
-            if constexpr (SEQ_BATCHED_IO) {
-                if (live) orig = (int)x6_gld32_sync(a.tok_row + (h1_g ? sh_off[1] : sh_off[0]) + sj_g);
-            } else
-                orig = live ? a.tok_row[(h1_g ? sh_off[1] : sh_off[0]) + sj_g] : 0;
+            if (live) orig = (int)x6_gld32_sync(a.tok_row + (h1_g ? sh_off[1] : sh_off[0]) + sj_g);
             int64_t id = live ? a.seq[orig] : 0;
             id = id < 0 ? 0 : (id > a.n_item ? a.n_item : id);
             const float *e_ = a.E + id * (int64_t)D + 4 * lk;
             const float *p_ = a.pe + (int64_t)(orig % a.L) * D + 4 * lk;
             float4 *xw = reinterpret_cast<float4 *>(const_cast<float *>(a.Rf)) + fbase;
-            // (SEQ_BATCHED_IO) The 16 + 16 pieces of the two rows are requested back to back by loads the compiler does not see and
+            // The 16 + 16 pieces of the two rows are requested back to back by loads the compiler does not see and
             // waited for ONCE: with plain loads the store of piece i may alias E / pe for the compiler, no later pair moves above
             // it, and the gather is sixteen dependent round trips (load a pair, vmcnt(0), store) in front of the first DMA issue.
-            x6_u32x4 eq[SEQ_BATCHED_IO ? 4 * NT : 1], pq[SEQ_BATCHED_IO ? 4 * NT : 1];
-            if constexpr (SEQ_BATCHED_IO) {
-                static_assert(!SEQ_BATCHED_IO || NT == 4, "sixteen operands per statement");
-                x6_static_for<0, 4 * NT>([&](auto ic) __attribute__((always_inline)) {
-                    constexpr int i = decltype(ic)::value; // piece tn * 4 + g: floats tn * 32 + 8 g .. of the row
-                    eq[i] = x6_gld<32 * i>(e_), pq[i] = x6_gld<32 * i>(p_);
-                });
-                asm volatile("s_waitcnt vmcnt(0)"
-                             : "+v"(eq[0]), "+v"(eq[1]), "+v"(eq[2]), "+v"(eq[3]), "+v"(eq[4]), "+v"(eq[5]), "+v"(eq[6]), "+v"(eq[7]), "+v"(eq[8]),
-                               "+v"(eq[9]), "+v"(eq[10]), "+v"(eq[11]), "+v"(eq[12]), "+v"(eq[13]), "+v"(eq[14]), "+v"(eq[15]));
-                asm volatile("" : "+v"(pq[0]), "+v"(pq[1]), "+v"(pq[2]), "+v"(pq[3]), "+v"(pq[4]), "+v"(pq[5]), "+v"(pq[6]), "+v"(pq[7]), "+v"(pq[8]),
-                                  "+v"(pq[9]), "+v"(pq[10]), "+v"(pq[11]), "+v"(pq[12]), "+v"(pq[13]), "+v"(pq[14]), "+v"(pq[15]));
-            }
+            x6_u32x4 eq[4 * NT], pq[4 * NT];
+            static_assert(NT == 4, "sixteen operands per statement");
+            x6_static_for<0, 4 * NT>([&](auto ic) __attribute__((always_inline)) {
+                constexpr int i = decltype(ic)::value; // piece tn * 4 + g: floats tn * 32 + 8 g .. of the row
+                eq[i] = x6_gld<32 * i>(e_), pq[i] = x6_gld<32 * i>(p_);
+            });
+            asm volatile("s_waitcnt vmcnt(0)"
+                         : "+v"(eq[0]), "+v"(eq[1]), "+v"(eq[2]), "+v"(eq[3]), "+v"(eq[4]), "+v"(eq[5]), "+v"(eq[6]), "+v"(eq[7]), "+v"(eq[8]),
+                           "+v"(eq[9]), "+v"(eq[10]), "+v"(eq[11]), "+v"(eq[12]), "+v"(eq[13]), "+v"(eq[14]), "+v"(eq[15]));
+            asm volatile("" : "+v"(pq[0]), "+v"(pq[1]), "+v"(pq[2]), "+v"(pq[3]), "+v"(pq[4]), "+v"(pq[5]), "+v"(pq[6]), "+v"(pq[7]), "+v"(pq[8]),
+                              "+v"(pq[9]), "+v"(pq[10]), "+v"(pq[11]), "+v"(pq[12]), "+v"(pq[13]), "+v"(pq[14]), "+v"(pq[15]));
 #pragma unroll
             for (int tn = 0; tn < NT; ++tn)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    float4 e4, p4;
-                    if constexpr (SEQ_BATCHED_IO) {
-                        e4 = __builtin_bit_cast(float4, eq[tn * 4 + g]), p4 = __builtin_bit_cast(float4, pq[tn * 4 + g]);
-                    } else {
-                        e4 = *reinterpret_cast<const float4 *>(e_ + tn * 32 + 8 * g), p4 = *reinterpret_cast<const float4 *>(p_ + tn * 32 + 8 * g);
-                    }
+                    const float4 e4 = __builtin_bit_cast(float4, eq[tn * 4 + g]), p4 = __builtin_bit_cast(float4, pq[tn * 4 + g]);
                     float4 t4 = make_float4(__fadd_rn(__fmul_rn(e4.x, a.sqrtd), p4.x), __fadd_rn(__fmul_rn(e4.y, a.sqrtd), p4.y),
                                             __fadd_rn(__fmul_rn(e4.z, a.sqrtd), p4.z), __fadd_rn(__fmul_rn(e4.w, a.sqrtd), p4.w));
                     if (!live) t4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -2336,13 +2262,10 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     }
 
     // fragment reads: the stream of a step is 8 groups x (plane 0, 1, 2) = 24 reads in consumption order (k_pack_x6); a
-    // ring of four register sets, three reads ahead
-    // (round 4: RING register sets, RA = RING - 1 reads ahead.  Four sets -- three reads = 3-6 MFMAs = 100-200 cycles ahead --
-    //  no longer cover a ds_read_b128 that queues behind seven other waves' reads once float16 planes halve the MFMAs
-    //  between two reads; eight sets at d = 128 with float16 planes, where two waves per SIMD leave the registers (236 of 256).  The ring index of a fragment
-    //  must not change across a step boundary: NP and NP + 8 are multiples of RING.)
-    constexpr int RING = (NT == 4 && NPL == 2) ? X6_RING4 : 4, RA = RING - 1;
-    constexpr bool SPLIT_ACC = NT == 4 && NPL == 2 && X6_SPLIT_ACC4; // one-tile steps: the h.h products on their own accumulator (below)
+    // ring of RING = four register sets, RA = RING - 1 = three reads (3-6 MFMAs, 100-200 cycles) ahead.  (Eight sets at d = 128
+    // with float16 planes measured no faster and cost 16 more registers.)  The ring index of a fragment must not change across a
+    // step boundary: NP and NP + 8 are multiples of RING.
+    constexpr int RING = 4, RA = RING - 1;
     static_assert(NP % RING == 0 && (NP + 8) % RING == 0 && RA <= NP / 2, "ring index continuity; next-step reads stay behind the barrier");
     x6_u32x4 af[RING];
     auto landed_all = [&]() __attribute__((always_inline)) {
@@ -2373,7 +2296,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     // (lab switches, tools/x6_lab.hip: X6_NO_MFMA drops the matrix instructions, X6_NO_DMA the ring refills past the first
     // three steps, X6_NO_SPLIT the plane split arithmetic -- timing experiments, results are then wrong)
 #ifdef X6_NO_MFMA
-#define X6_MM(W_, X_, T_) asm volatile("" :: "v"(W_), "v"(X_))
+#define X6_MM(W_, X_, T_) { const auto mw_ = (W_); const auto mx_ = (X_); asm volatile("" :: "v"(mw_), "v"(mx_)); } /* (copies: an asm operand does not capture in the step lambdas) */
 #else
 #define X6_MM(W_, X_, T_) T_ = x6_mma(W_, X_, T_)
 #endif
@@ -2414,9 +2337,8 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
         X6_TI(st_b)                                                                                                       \
         __builtin_amdgcn_s_barrier();                                                                                    \
         X6_TI(st_c)                                                                                                       \
-        if ((I_) + LEAD < nsteps && !(SEQ && !SEQ_ASM_DMA && (I_) < NFRONT && (I_) % 3 == 2) &&                          \
-            !(SEQ && SEQ_LAST_ABSORB && (I_) == NFRONT + NPRE - 1 && end_rt)) /* (nothing is fetched behind the launch's last step) */ \
-            X6_ISSUE((I_) + LEAD); /* (SEQ with the builtin DMA: see the front phase) */ \
+        if ((I_) + LEAD < nsteps && !(SEQ && (I_) == NFRONT + NPRE - 1 && end_rt)) /* (nothing is fetched behind the launch's last step) */ \
+            X6_ISSUE((I_) + LEAD);                                                                                        \
         if constexpr (RESID_LATE) { if ((I_) == 1) load_res(); }                                                         \
         X6_TI(st_d)                                                                                                       \
         st_wait += st_b - st_a, st_bar += st_c - st_b, st_iss += st_d - st_c;                                            \
@@ -2573,12 +2495,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     // into the zero-started accumulator, where they and their truncation are 2^-8 of the result, and the 8 h.h products
     // last: 8 full-size truncations per output instead of 48 (the W_h fragments are read from the slot a second time: the
     // step's virtual read sequence is its 24 fragments, then fragments 0, 3, .., 21 again).
-    // (round 4, SPLIT_ACC at d = 128: instead of the second read of the W_h fragments the h.h products run on the step's
-    //  accumulator and the small products on a zero-started second one, added once at the end of the step -- the same eight
-    //  full-size truncations per output, a third fewer LDS reads in these steps (with float16 planes a one-tile step was 24
-    //  reads for 24 MFMAs: every wave of the CU asking the LDS pipe for 1 KB per 32 matrix cycles is the pipe's whole
-    //  bandwidth), and two independent MFMA chains instead of one.)
-    constexpr int NV = SPLIT_ACC ? NP : NP + 8; // fragment reads of a one-tile step
+    constexpr int NV = NP + 8; // fragment reads of a one-tile step
 #ifdef X6_NO_READS
 #define X6_RD_V(v_)
 #define X6_WAIT_V(v_) asm volatile("" : "+v"(af[(v_) & RA]));
@@ -2603,10 +2520,6 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
         X6_TI(sq_0)                                                                                                       \
         const unsigned int sb_ = fr_addr + (unsigned int)((step_ % NSLOT) * STEP_B);                                     \
         const unsigned int sn_ = fr_addr + (unsigned int)(((step_ + 1) % NSLOT) * STEP_B);                               \
-        f32x16 ts_;                                                                                                      \
-        if constexpr (SPLIT_ACC) {                                                                                       \
-            _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) ts_[r_] = 0.f;                                             \
-        }                                                                                                                \
         x6_static_for<0, NV>([&](auto vc_) __attribute__((always_inline)) {                                              \
             constexpr int v_ = decltype(vc_)::value;                                                                     \
             if constexpr (v_ == NV / 2) { X6_PUBLISH(step_) }                                                            \
@@ -2620,19 +2533,13 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                 /* the small products of weight plane pl_: activation planes NPL - 1 - pl_ .. (the h.h product waits) */ \
                 x6_static_for<0, NPL - pl_>([&](auto qc_) __attribute__((always_inline)) {                               \
                     constexpr int xp_ = NPL - 1 - pl_ - decltype(qc_)::value;                                            \
-                    if constexpr (pl_ > 0 || xp_ > 0) {                                                                  \
-                        if constexpr (SPLIT_ACC) { X6_MM(w_, XP_[g_ >> 1][g_ & 1][xp_], ts_); }                          \
-                        else { X6_MM(w_, XP_[g_ >> 1][g_ & 1][xp_], T_); }                                               \
-                    } else if constexpr (SPLIT_ACC) { X6_MM(w_, XP_[g_ >> 1][g_ & 1][0], T_); }                          \
+                    if constexpr (pl_ > 0 || xp_ > 0) { X6_MM(w_, XP_[g_ >> 1][g_ & 1][xp_], T_); }                      \
                 });                                                                                                      \
             } else {                                                                                                     \
                 constexpr int g_ = v_ - NP;                                                                              \
                 X6_MM(w_, XP_[g_ >> 1][g_ & 1][0], T_);                                                                  \
             }                                                                                                            \
         });                                                                                                              \
-        if constexpr (SPLIT_ACC) {                                                                                       \
-            _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) T_[r_] += ts_[r_];                                         \
-        }                                                                                                                \
         X6_TI(sq_1)                                                                                                       \
         st_steps += sq_1 - sq_0;                                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                               \
@@ -2662,12 +2569,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             asm volatile("" : "+v"(vecs_addr), "+v"(fr_addr), "+v"(mtile), "+v"(fb_lo), "+v"(fb_hi));
             fbase = ((size_t)fb_hi << 32) | fb_lo;
         }
-#if SEQ_LAST_ABSORB
         end_rt = ly == a.n_lay - 1; // the launch's last layer: the ring ends behind its own 32 steps (no empty step, no next front)
-#else
-        last_rt = ly == a.n_lay; // the extra trip: only the front of the model's last layer, the ring ends behind its 12 steps
-        nsteps_rt = last_rt ? NFRONT : (1 << 20);
-#endif
         dma_src = a.Wbase + (long long)ly * a.wstride + (PPW * wave + PPG / 2) * 64 + lane;
         dma_src_q = a.Wbase + (long long)(ly == 0 ? a.nl_total - 1 : ly - 1) * a.wstride + (PPW * wave + PPG / 2) * 64 + lane;
         dma_src_qn = dma_src;
@@ -2677,9 +2579,8 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
         // into the workgroup's LDS images, the attention of this wave's own 32 queries, its output to the scratch tiles the
         // out-projection below reads back.  The three steps of a head (k, v, q) run back to back with their result tiles in registers;
         // K's and V's image rows are written from inside the v and the q step by inline asm.  The LDS traffic the compiler can see (q's
-        // scratch store, the attention's reads) sits in ONE region per head, behind the head's last step, and with the builtin DMA
-        // that step leaves its ring refill to the end of the region: a compiler-visible LDS access behind an LDS-DMA issue gets a
-        // vmcnt(0) in front, i.e. it would drain the ring at every step.
+        // scratch store, the attention's reads) sits in ONE region per head, behind the head's last step; the ring's refills are
+        // inline asm (issue()), so the compiler puts no wait for them in front of these accesses.
         float *Kimg = reinterpret_cast<float *>(smem + X6_SEQ_KIMG);
         char *Vimg = smem + X6_SEQ_VIMG;
         float *scr = reinterpret_cast<float *>(smem + X6_SEQ_SCR + wave * X6_SEQ_SCR_B);
@@ -2692,11 +2593,10 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             f32x16 tq, tk, tv, bt;
 #pragma unroll
             for (int r = 0; r < 16; ++r) tq[r] = 0.f, tk[r] = 0.f, tv[r] = 0.f;
-#if SEQ_FRONT_RIDE
             // k, v, q: K's epilogue (bias, split into float16 planes, image row) rides the v step, V's the q step -- four values of
             // a bias group are read (asm) in front of read 6 g + 3 and used three reads later, behind a wait of their own; the image
-            // stores are asm too (a compiler-visible LDS access behind the builtin DMA gets a vmcnt(0) in front, and the compiler may
-            // not move them into a phase it writes itself).  Behind the q step only q's bias + scratch store remain.
+            // stores are asm too (the compiler may not move them into a phase it writes itself).  Behind the q step only q's bias +
+            // scratch store remain.
             // Image writes against image reads: head h's K rows are written during step 3 h + 1 -- behind the mid-step barrier of step
             // 3 h, which every wave reaches only after its attention of head h - 1: ONE workgroup barrier between the last read of the
             // images and the first write (V, a step later: two).  Every row is complete at the barrier behind the q step.
@@ -2717,8 +2617,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                     f16x4 hp, lp;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        float x = __builtin_fmaf(t[4 * g + e], IWS, bv[e]);
-                        if constexpr (c == 1) x *= SEQ_KQ_SCALE; // (exact)
+                        const float x = __builtin_fmaf(t[4 * g + e], IWS, bv[e]);
                         const _Float16 hv = (_Float16)x;
                         hp[e] = hv;
                         lp[e] = (_Float16)(x - (float)hv);
@@ -2746,7 +2645,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             auto ride_v = [&](auto vc) __attribute__((always_inline)) { front_ride(vc, std::integral_constant<int, 2>{}, tv); };
             X6_STEP1(3 * h, Yp, tk)
             X6_STEP1R(3 * h + 1, Yp, tv, ride_k)
-            X6_STEP1R(3 * h + 2, Yp, tq, ride_v) // (builtin DMA: no ring refill behind this step, see X6_PUBLISH)
+            X6_STEP1R(3 * h + 2, Yp, tq, ride_v)
             X6_PH(9)
             bias_tile(bt, V_BQ + 32 * h);
             {
@@ -2756,61 +2655,6 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                         make_float4(__builtin_fmaf(tq[4 * g + 0], IWS, bt[4 * g + 0]), __builtin_fmaf(tq[4 * g + 1], IWS, bt[4 * g + 1]),
                                     __builtin_fmaf(tq[4 * g + 2], IWS, bt[4 * g + 2]), __builtin_fmaf(tq[4 * g + 3], IWS, bt[4 * g + 3]));
             }
-#else
-            // (lab: the order and placement through round 7 -- q, k, v, the three epilogues behind the v step)
-            X6_STEP1(3 * h, Yp, tq)
-            X6_STEP1(3 * h + 1, Yp, tk)
-            X6_STEP1(3 * h + 2, Yp, tv) // (builtin DMA: no ring refill behind this step, see X6_PUBLISH)
-            X6_PH(9)
-            bias_tile(bt, V_BQ + 32 * h);
-            {
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<float4 *>(scr + li_l * 36 + 8 * g + 4 * lk) =
-                        make_float4(__builtin_fmaf(tq[4 * g + 0], IWS, bt[4 * g + 0]), __builtin_fmaf(tq[4 * g + 1], IWS, bt[4 * g + 1]),
-                                    __builtin_fmaf(tq[4 * g + 2], IWS, bt[4 * g + 2]), __builtin_fmaf(tq[4 * g + 3], IWS, bt[4 * g + 3]));
-            }
-            bias_tile(bt, V_BQ + D + 32 * h);
-            if (l_b >= 0) { // (rows [cnt, 16 nb) hold finite values of dead tokens: read with p = 0)
-                // K as two float16 planes (the score products of seq_attn_block): 128 B per key = chunks 0 .. 3 plane h, 4 .. 7
-                // plane l (chunk = 8 channels), chunk index ^ ((key >> 1) & 7): a tile's 16 keys x one chunk = 16 bank groups
-                typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-                const int swk = (s_j >> 1) & 7;
-                char *krow = reinterpret_cast<char *>(Kimg) + irow * 128 + 8 * lk;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f16x4 hp, lp;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float v = __builtin_fmaf(tk[4 * g + e], IWS, bt[4 * g + e]) * SEQ_KQ_SCALE; // (exact)
-                        const _Float16 hv = (_Float16)v;
-                        hp[e] = hv;
-                        lp[e] = (_Float16)(v - (float)hv);
-                    }
-                    *reinterpret_cast<f16x4 *>(krow + ((g ^ swk) << 4)) = hp;
-                    *reinterpret_cast<f16x4 *>(krow + (((4 + g) ^ swk) << 4)) = lp;
-                }
-            }
-            bias_tile(bt, V_BQ + 2 * D + 32 * h);
-            if (l_b >= 0) {
-                typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-                const int swv = ((s_j >> 2) & 1) << 1;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    f16x4 hp, lp;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float v = __builtin_fmaf(tv[4 * g + e], IWS, bt[4 * g + e]);
-                        const _Float16 hv = (_Float16)v;
-                        hp[e] = hv;
-                        lp[e] = (_Float16)(v - (float)hv);
-                    }
-                    char *slot = Vimg + irow * 64 + ((g ^ swv) << 4) + 8 * lk;
-                    *reinterpret_cast<f16x4 *>(slot) = hp;
-                    *reinterpret_cast<f16x4 *>(slot + 16384) = lp;
-                }
-            }
-#endif
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             X6_PH(0)
             __builtin_amdgcn_s_barrier(); // every wave's rows of head h are in the images
@@ -2822,7 +2666,6 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
 #pragma unroll 1
                 for (int blk = 0; blk < 2; ++blk) {
                     const int b_ = blk ? sh_b[1] : sh_b[0], qb_ = blk ? sh_qb[1] : sh_qb[0], row0_ = blk ? sh_row0[1] : sh_row0[0];
-                    if (b_ >= 0 && last && qb_ != (blk ? sh_pb[1] : sh_pb[0])) continue; // (the extra trip for the model's last layer: only the consumed token's block)
                     // (an empty half: block index beyond a zero-length sequence -> zeros, the layer body multiplies whole tiles)
                     seq_attn_block(Kimg + row0_ * 32, Vimg + row0_ * 64, 16384, b_ >= 0 ? (blk ? sh_cnt[1] : sh_cnt[0]) : 0, b_ >= 0 ? qb_ : 16,
                                    blk ? sh_pm[1] : sh_pm[0], blk ? sh_tadd[1] : sh_tadd[0], blk ? sh_tgt[1] : sh_tgt[0],
@@ -2831,11 +2674,9 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             }
             asm volatile("" ::: "memory");
             // (the next head's first image writes ride its v step, behind the mid-step barrier of its k step: every wave is past its
-            //  reads.  SEQ_FRONT_RIDE = 0: they come three steps -- three workgroup barriers -- later.)
+            //  reads)
             X6_PH(2)
-            if (!SEQ_ASM_DMA && 3 * h + 2 + LEAD < nsteps) issue(3 * h + 2 + LEAD); // (builtin DMA: the refill the v step left out)
         }
-        if (last) return; // (the extra trip: the model's last layer goes on, for one row per sequence, in the small-batch kernels)
         // ---- the layer body's inputs: the attention tiles this wave wrote and the residual, as loads the compiler does not see (it
         // would hoist and spread them over the front: registers) with ONE wait; the out-projection accumulates from zero and the
         // residual is added with b_o in front of LayerNorm 1, as in the RESID_LATE form.
@@ -2926,12 +2767,10 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                 x6_split(acc[tn], s2, Yp[tn][s2]);
                 __builtin_amdgcn_sched_barrier(0);
             }
-        if constexpr (SEQ) {
-            if (!last) { // (the launch's last layer too: vecpack has a row for the model's last layer, nothing re-stages these)
+        if constexpr (SEQ) { // (the launch's last layer too: vecpack has a row for the model's last layer, nothing re-stages these)
 #pragma unroll
-                for (int k = 0; k < (X6_SEQ_VECS + 64 * NW - 1) / (64 * NW); ++k)
-                    nv[k] = (tid + 64 * NW * k < X6_SEQ_VECS) ? a.vecpack[(size_t)(ly + 1) * X6_SEQ_VECS + tid + 64 * NW * k] : 0.f;
-            }
+            for (int k = 0; k < (X6_SEQ_VECS + 64 * NW - 1) / (64 * NW); ++k)
+                nv[k] = (tid + 64 * NW * k < X6_SEQ_VECS) ? a.vecpack[(size_t)(ly + 1) * X6_SEQ_VECS + tid + 64 * NW * k] : 0.f;
         }
         if constexpr (NPL == 2) { // FFN-2 accumulates WS x its product onto y in place: y goes on as WS y (exact)
 #pragma unroll
@@ -2996,7 +2835,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             }
         const float rstd = 1.0f / sqrtf(lanes_sum<32>(qs) * invn + 1e-5f);
         if constexpr (ASM_VECS) {
-            // (SEQ_BATCHED_IO) The sequence-resident launch always has an x' image (x6_launch_seq) and stores its sixteen pieces from
+            // The sequence-resident launch always has an x' image (x6_launch_seq) and stores its sixteen pieces from
             // inline asm, at immediate offsets from one base per tile, the base rebuilt HERE from scalars (the workgroup, the wave)
             // and the lane.  (The plain form -- a test of a.Xf around each store, the address rebuilt from a pair reloaded from
             // scratch -- compiled to a vmcnt(0) in front of every store: on gfx9 stores count in vmcnt, so each store waited for
@@ -3004,7 +2843,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
             // what orders them before the next layer's residual loads (load_res, of the same wave) is the explicit
             // s_waitcnt vmcnt(0) of the empty step below, and behind the launch's last layer the one at the kernel's end.
             char *xt = nullptr;
-            if constexpr (SEQ && SEQ_BATCHED_IO) {
+            if constexpr (SEQ) {
                 int mt_ = (int)blockIdx.x * NW + wave; // = mtile, as a scalar
                 asm volatile("" : "+s"(mt_)); // (a value of this trip: the address is not hoisted out of the layer loop and spilled)
                 xt = reinterpret_cast<char *>(a.Xf) + ((size_t)mt_ * (4 * NT) * 64 + lane) * 16;
@@ -3014,7 +2853,7 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                 constexpr int tn = decltype(gc)::value >> 2, g = decltype(gc)::value & 3;
                 const float4 o = make_float4((acc[tn][4 * g + 0] - mu) * rstd * gg.x + be.x, (acc[tn][4 * g + 1] - mu) * rstd * gg.y + be.y,
                                              (acc[tn][4 * g + 2] - mu) * rstd * gg.z + be.z, (acc[tn][4 * g + 3] - mu) * rstd * gg.w + be.w);
-                if constexpr (SEQ && SEQ_BATCHED_IO) x6_gst<1024 * g>(xt + 4096 * tn, __builtin_bit_cast(x6_u32x4, o));
+                if constexpr (SEQ) x6_gst<1024 * g>(xt + 4096 * tn, __builtin_bit_cast(x6_u32x4, o));
                 else if (a.Xf) reinterpret_cast<float4 *>(a.Xf)[((size_t)(mtile * NT + tn) * 4 + g) * 64 + lane] = o;
                 acc[tn][4 * g + 0] = o.x, acc[tn][4 * g + 1] = o.y, acc[tn][4 * g + 2] = o.z, acc[tn][4 * g + 3] = o.w;
             });
@@ -3043,8 +2882,8 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
         }
     X6_T(st_p[4])
     X6_PH(7)
-    if (SEQ && SEQ_LAST_ABSORB && end_rt) return; // (the launch's last layer ends here: x' is stored, the ring is drained)
-    if (SEQ && !last) {
+    if (SEQ && end_rt) return; // (the launch's last layer ends here: x' is stored, the ring is drained)
+    if (SEQ) {
         // ---- the empty step between two layers: publishes the next layer's first step (fetched at mid-step 31), frees step
         // 31's slot for its second one, re-stages the parameter vectors (every wave is past LayerNorm 3: nothing reads the old
         // ones) BEFORE the refill goes out (a compiler-visible LDS store behind a DMA issue would wait for it), and reads the next
@@ -3113,11 +2952,11 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
     }; // (layer_body)
     if constexpr (SEQ) {
 #pragma unroll 1
-        for (ly = 0; ly < a.n_lay + (SEQ_LAST_ABSORB ? 0 : 1); ++ly) layer_body();
+        for (ly = 0; ly < a.n_lay; ++ly) layer_body();
     } else
         layer_body();
     landed_all(); // the reads issued past the last step
-    if constexpr (SEQ && SEQ_LAST_ABSORB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (no LDS-DMA piece in flight when the wave ends: the ring's last issue is waited for at mid-step 30)
+    if constexpr (SEQ) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (no LDS-DMA piece in flight when the wave ends: the ring's last issue is waited for at mid-step 30)
 #ifdef X6_STAMP
     X6_T(st_1)
     if (lane == 0 && a.stamps) {
@@ -5338,7 +5177,7 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
     float qf[8];
     {
         const float4 t0 = *reinterpret_cast<const float4 *>(qscr + lq * 36 + 8 * gq), t1 = *reinterpret_cast<const float4 *>(qscr + lq * 36 + 8 * gq + 4);
-        const float sc = qi < L ? scale * SEQ_KQ_SCALE : 0.f;
+        const float sc = qi < L ? scale : 0.f;
         qf[0] = t0.x * sc, qf[1] = t0.y * sc, qf[2] = t0.z * sc, qf[3] = t0.w * sc;
         qf[4] = t1.x * sc, qf[5] = t1.y * sc, qf[6] = t1.z * sc, qf[7] = t1.w * sc;
     }
@@ -5371,7 +5210,6 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
         sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl, Q[0], sa, 0, 0, 0);
         sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, Q[1], sa, 0, 0, 0);
         sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, Q[0], sa, 0, 0, 0);
-        if (SEQ_KQ_SCALE != 1.0f) sa *= 1.0f / (SEQ_KQ_SCALE * SEQ_KQ_SCALE);
     };
     auto mask_diag = [&](int kt, f32x4 &sa) __attribute__((always_inline)) {
         const unsigned int pmk = pm_diag >> (4 * gq);
@@ -5441,7 +5279,7 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
         float part = qf[0] * tg.k[0];
 #pragma unroll
         for (int e = 1; e < 8; ++e) part = __fmaf_rn(qf[e], tg.k[e], part);
-        st = quad16_sum(part) * (1.0f / (SEQ_KQ_SCALE * SEQ_KQ_SCALE)) + tgt_add;
+        st = quad16_sum(part) + tgt_add;
     }
     mx = quad16_max(mx);
     float m = fmaxf(mx, st);
@@ -6656,8 +6494,8 @@ float irs_h3_operand_bound(const irs_ctx *ctx, const float *st) {
     const float a0 = st[0] * sd + st[1];                 // embedded token
     const float ln = sd * st[2] + st[3] + st[4];         // a LayerNorm output (+ c_l)
     const float xin = sd * fmaxf(a0, ln);                // norm of a layer's input row
-    float v = xin * st[6] + st[7];                       // a V row (and the attention output, a convex combination of V rows)
-    if (irs_seq_shape(ctx->dims)) v *= SEQ_KQ_SCALE;               // ... and a q or k row (st[6] then covers all of W_in's rows)
+    const float v = xin * st[6] + st[7];                 // a V row (and the attention output, a convex combination of V rows);
+                                                         // the sequence-resident form: a q or k row too (st[6] then covers all of W_in's rows)
     const float h = sd * ln * st[5] + st[7];             // a hidden activation
     return fmaxf(fmaxf(fmaxf(a0, ln), fmaxf(v, h)), st[7] * x6_wscale(2)); // (the weight planes hold 2^8 x the weights)
 }
@@ -6759,7 +6597,7 @@ enum class DecFam { GEMM, GEMM_LN, FRAG_GEMM, FRAG_BLOCK, FRAG_FUSED, SMALL16, W
 struct DecodeRoute {
     bool rows_only, small_plan;
     DecPlan plan;
-    DecEmbed embed;  // embedding; *_QKV: + layer 0's q | k | v; SEQ: + layers 0 .. n_layers - 2 and the front of the last one
+    DecEmbed embed;  // embedding; *_QKV: + layer 0's q | k | v; SEQ: + layers 0 .. n_layers - 2
     DecFam layer;    // the layers before the rows-only last one (every layer of a full decode)
     DecFam tail;     // the rest of the rows-only last layer (GEMM, GEMM_LN, SMALL16, WIDE or ANY)
     bool frag;       // x / y live in the fragment-major images (act_xf / act_yf) between the layers
@@ -6811,8 +6649,8 @@ static DecodeRoute decode_route(const irs_ctx *ctx, int B, bool rows_only) {
     // one sequence (the reference IRN's own regime, and the latency metric's): self-attention runs inside the layer kernel;
     // q | k | v alternate between two buffers so that the last (rows-only) layer reads ctx->act_qkv
     r.att_fused = small16 && rows_only && B == 1 && D.n_heads == 4 && L <= 256 && ctx->act_qkv_b1 && nl > 1;
-    // the sequence-resident layer kernel: the throughput shape of config 2 / 3 on float16 planes, layers 0 .. n_layers - 2 and
-    // the front of the last one (its q | k | v and the attention of each consumed token's block) in ONE launch, K / V in LDS.
+    // the sequence-resident layer kernel: the throughput shape of config 2 / 3 on float16 planes, layers 0 .. n_layers - 2 in
+    // ONE launch, K / V in LDS; the last layer then attends from x' with absorbed K / V projections (last_layer).
     // use_seq: 0 never, 1 whenever the shape allows, 2 (default) where it measured ahead: >= SEQ_AUTO_MIN_SEQS sequences (one
     // workgroup per CU: below ~4 rounds of workgroups the last, partly filled round costs more than the fusion saves --
     // profiles/r05/seq_sizes.txt: 6-layer decode 0.98 vs 1.06 ms at 1024 users, 3.83 vs 3.98 at 4096, but 0.89 vs 0.80 at 768)
@@ -7143,7 +6981,6 @@ static int last_layer(const DecodeCall &c, int l, const int32_t *pos, float *xro
     const float *q_r = nullptr;
     const int nt = d > 128 ? d / 32 : 4;       // column tiles per token of the fragment-major images
     if (r.seq) {
-#if SEQ_LAST_ABSORB
         // the sequence-resident launch ended behind layer l - 1: this layer's consumed row attends from x' (tile order) with
         // absorbed K / V projections; u | m ([B][4][d], in place) and c ([B][4]) lie in act_h, which this route does not use
         // otherwise (B L ffn_dim floats, L >= 4: 8 B d)
@@ -7153,12 +6990,6 @@ static int last_layer(const DecodeCall &c, int l, const int32_t *pos, float *xro
         hipLaunchKernelGGL(k_absorb_attn, dim3(B), dim3(256), 0, s, xf, um, cq, c.seq, ctx->act_ru, L, ctx->dims.mask_mode, c.off, c.cnt,
                            qrow, ctx->seq_padq, ctx->seq_row0, ctx->qrow_tile);
         hipLaunchKernelGGL(k_absorb_out, dim3((B + ABS_SO - 1) / ABS_SO), dim3(256), 0, s, um, w.sa_in_w, w.sa_in_b, ao_r, B);
-#else
-        // the sequence-resident launch ran this layer's q | k | v and the attention of every consumed token's block: the
-        // residual row and the attention row come out of the fragment-major images by the tile-order row index
-        hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, xf, ctx->qrow_tile, x_r, d, nt);
-        hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, ctx->act_yf, ctx->qrow_tile, ao_r, d, nt);
-#endif
     } else if (r.kv_only) { // the previous layer's kernel wrote k | v only: queries for the B consumed rows here
         hipLaunchKernelGGL(k_gather_rows_frag, dim3(B), dim3(64), 0, s, xf, qrow, x_r, d, nt);
         LinArgs q{};

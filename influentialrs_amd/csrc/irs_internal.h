@@ -13,14 +13,12 @@
 // variants) that tools/*_lab.hip turn on by including a kernel source with the switch defined.  Several of them change what
 // a kernel COMPUTES, so a stray -D must never produce a library: every switch is legal only together with IRS_LAB, which
 // influentialrs_amd/build.py never defines (and tests/test_cabi.py checks that it does not).
-#if !defined(IRS_LAB) && (defined(X6_DUMP) || defined(X6_STAMP) || defined(X6_NO_SPLIT) || defined(X6_STAGGER) ||            \
-                          defined(X6_NO_MFMA) || defined(X6_NO_READS) || defined(X6_NO_DMA) || defined(X6_NO_BARRIER) ||       \
-                          defined(X6_NW) || defined(ATTN_STAMP) || defined(ATTNP_STAMP) ||               \
-                          defined(IRS_SMALL_TIMING) || defined(IRS_DIRECT_TIMING) || defined(SWEEP_LAB) || defined(X6D_STAMP) ||              \
-                          defined(X6_NO_QKV_STORE) || defined(X6_NSLOT2) || defined(X6_RESID_LATE) || defined(X6_RING4) ||      \
-                          defined(X6_SPLIT_ACC4) || defined(SEQ_EXP) || defined(PLAN_STAMP) ||     \
-                          defined(SEQ_BATCHED_IO))
-#error "a lab switch (X6_* / ATTN* / IRS_*_TIMING) is defined without IRS_LAB: the product library must be built without them"
+// The condition names exactly the switches the sources under csrc/ test (tests/test_cabi.py compares the two sets).
+#if !defined(IRS_LAB) && (defined(X6_DUMP) || defined(X6_STAMP) || defined(X6_NO_SPLIT) || defined(X6_NO_MFMA) ||            \
+                          defined(X6_NO_READS) || defined(X6_NO_DMA) || defined(X6_NO_BARRIER) || defined(X6_NO_QKV_STORE) ||  \
+                          defined(X6_NW) || defined(SEQ_EXP) || defined(PLAN_STAMP) || defined(ATTN_STAMP) ||                  \
+                          defined(IRS_SMALL_TIMING) || defined(IRS_DIRECT_TIMING))
+#error "a lab switch (X6_* / SEQ_EXP / *_STAMP / IRS_*_TIMING) is defined without IRS_LAB: the product library must be built without them"
 #endif
 
 #include <atomic>

@@ -92,3 +92,45 @@ def test_product_build_defines_no_lab_switch():
     r = subprocess.run([build.HIPCC, "--offload-arch=gfx950", "-std=c++17", "-DX6_NO_MFMA", "-fsyntax-only", src],
                        capture_output=True, text=True)
     assert r.returncode != 0 and "IRS_LAB" in r.stderr
+
+
+_LAB_GUARD = re.compile(r"\s*#\s*if\s+!defined\(IRS_LAB\)")
+
+
+def _tested_switches(csrc):
+    """Every macro name a csrc/*.hip or csrc/*.h file tests with #ifdef, #ifndef, #if / #elif NAME or defined(NAME), without
+    include guards (#ifndef NAME followed by an empty #define NAME), compiler-defined names (__...) and IRS_LAB itself."""
+    names = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        txt = open(os.path.join(csrc, f)).read().replace("\\\n", " ")  # a condition may run over several lines
+        lines = txt.split("\n")
+        for i, line in enumerate(lines):
+            m = re.match(r"\s*#\s*(ifdef|ifndef|if|elif)\b(.*)", line)
+            if not m or _LAB_GUARD.match(line):  # (the guard names switches, it does not test them)
+                continue
+            expr =re.sub(r"//.*|/\*.*?\*/", "", m.group(2))
+            if m.group(1) in ("ifdef", "ifndef"):
+                found = re.findall(r"^\s*([A-Za-z_]\w*)", expr)
+                if m.group(1) == "ifndef" and found and i + 1 < len(lines) and \
+                        re.match(r"\s*#\s*define\s+%s\s*$" % re.escape(found[0]), lines[i + 1]):
+                    continue  # an include guard
+            else:
+                found = [n for n in re.findall(r"[A-Za-z_]\w*", expr) if n != "defined"]
+            names.update(found)
+    return {n for n in names if not n.startswith("__") and n != "IRS_LAB"}
+
+
+def test_lab_guard_names_exactly_the_switches_the_sources_test():
+    """A switch the sources test but the guard does not name lets a stray -D build a library that computes something else; a
+    name in the guard that no source tests is a record of a form that is gone.  The two sets are equal."""
+    csrc = os.path.join(REPO, "influentialrs_amd", "csrc")
+    txt = open(os.path.join(csrc, "irs_internal.h")).read().replace("\\\n", " ")
+    cond = [l for l in txt.split("\n") if _LAB_GUARD.match(l)]
+    assert len(cond) == 1, cond
+    guarded = set(re.findall(r"defined\(\s*(\w+)\s*\)", cond[0])) - {"IRS_LAB"}
+    tested = _tested_switches(csrc)
+    assert len(tested) >= 10, tested
+    unguarded, stale = sorted(tested - guarded), sorted(guarded - tested)
+    assert not unguarded and not stale, f"tested in csrc/ but not guarded: {unguarded}; guarded but tested nowhere: {stale}"

@@ -1,5 +1,5 @@
 """The sequence-resident decoder's front when a head's steps run in the order k, v, q and the K / V epilogues (bias, split into
-float16 planes, image rows) ride between the matrix instructions of the NEXT step (k_block_x6<.., SEQ>, SEQ_FRONT_RIDE).
+float16 planes, image rows) ride between the matrix instructions of the NEXT step (k_block_x6<.., SEQ>).
 
 What the new placement can break, and where it would show:
   * the ring: front step i now fetches component (i % 3 + 1) % 3 -- in the live waves' refills, in the idle path of empty waves and

@@ -1,5 +1,5 @@
 """The model's last decoder layer behind the sequence-resident launch: the one consumed row per sequence attends from x' with
-absorbed K / V projections (k_absorb_qu, k_absorb_attn, k_absorb_out; SEQ_LAST_ABSORB), and k_block_x6<.., SEQ> ends behind
+absorbed K / V projections (k_absorb_qu, k_absorb_attn, k_absorb_out), and k_block_x6<.., SEQ> ends behind
 its last full layer instead of running a front-only trip for every token.
 
 What the change can break, and where it would show:

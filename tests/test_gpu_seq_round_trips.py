@@ -1,4 +1,4 @@
-"""The sequence-resident decoder launch with its global-memory traffic batched (k_block_x6<.., SEQ>, SEQ_BATCHED_IO): layer 0's
+"""The sequence-resident decoder launch with its global-memory traffic batched (k_block_x6<.., SEQ>): layer 0's
 parameter vectors and the 32 pieces of a token's embedding and position rows requested by inline-asm loads with ONE wait each,
 the token's row index by an inline-asm load of its own, the x' tile of LayerNorm 3 stored by inline-asm stores with no wait
 between them, the idle waves ending the program where they stand.  None of it changes arithmetic.

@@ -3,7 +3,7 @@ the program asks for no such thing (no GPU needed: hipcc -S, tools/isa_vm_drain_
 
 A `s_waitcnt vmcnt` the COMPILER writes stands in front of an operation it tracks itself; a chain of them is a chain of dependent
 round trips.  Two phases of k_block_x6<3, 8, false, 4, 2, SEQ = true> store sixteen 16-byte pieces of a token tile: the prologue
-(the embedded tokens, layer 0's residual) and LayerNorm 3 (x').  Before SEQ_BATCHED_IO the first held 22 compiler-written vmcnt
+(the embedded tokens, layer 0's residual) and LayerNorm 3 (x').  Before the batched form the first held 22 compiler-written vmcnt
 waits (a pair of row pieces per round trip: the store of piece i may alias the tables) and the second 17 (one in front of every
 store: the address came back from scratch inside an `if (a.Xf)` block, and stores count in vmcnt on gfx9).  Now every batch of
 loads is inline asm with one wait that names its registers, the stores are inline asm, and what is left to the compiler is the
