@@ -146,6 +146,13 @@ int irs_finalize_weights(irs_ctx *ctx, void *dev_arena, size_t bytes, void *stre
 
 size_t irs_workspace_bytes(const irs_ctx *ctx);
 int irs_bind_workspace(irs_ctx *ctx, void *dev_ws, size_t bytes);
+/* Calls on one context, in any order (tests/test_gpu_engine_state.py holds the three statements below):
+ *  - The caller orders them: all on one stream, or with events between streams.  Every entry point works on the stream it is
+ *    given and nowhere else, so other streams of the process, the null stream included, and other contexts may run beside it.
+ *  - Between calls the workspace's contents belong to the library.  The memory needs no initialisation before the bind, and
+ *    binding the same or other memory again at any time (with no call of the context in flight) starts from a clean state.
+ *  - A call's results do not depend on the calls before it: other entry points, other shapes, other bindings since unbound.  The
+ *    one exception is documented where it lives: bit 0 (IRS_ROW_FALLBACK) of irs_score_topk_carry's status words. */
 
 /* ---- decoder (replaces InfluentialNet.decoding, influentialRS.py:157-200;
  *      SampleNet.decoding, uRS.py:52-64) --------------------------------- */

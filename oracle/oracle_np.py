@@ -485,3 +485,29 @@ def eval_get_grad(sd, cfg, histories: np.ndarray, new_seqs: np.ndarray, targets,
         iois.append(tp[-1] - tp[0])
         avg_ps.append(sum(pp) / len(pp))
     return t_probs, p_probs, avg_ps, iois
+
+
+def eval_accuracy_metrics(sd, cfg, seqs: np.ndarray, top_k=20, use_h=True):
+    """Evaluator.get_accuracy_metrics_in_batch (evaluator.py:94-133) on post-padded rows [B, max_len + 1]: per row,
+    end = get_end_index (the index before the first 0, the last index without one), the label is seq[end], the logits are
+    those at position end - 1 of the decode of seq[:-1], the items are sorted by score descending and, under use_h, the history
+    seq[:end] is removed; a hit if the label is among the first top_k, and a reciprocal rank only for rows whose label
+    survived the filter.  Returns (hit_count, rr[], ranks[B] with 0 for a skipped row)."""
+    seqs = np.asarray(seqs, dtype=np.int64)
+    W, b = sd["project.weight"], sd["project.bias"]
+    hit, rr, ranks = 0, [], []
+    for seq in seqs:
+        end = _first_none_zero_index(seq)
+        label = int(seq[end])
+        x, _ = decode(sd, cfg, seq[:-1], None, evaluator=True)
+        s = score_chain(x[end - 1], W, b)
+        hist = seq[:end] if use_h else np.zeros(0, dtype=np.int64)
+        if label in set(int(v) for v in hist):  # removed with the history: neither a hit nor a reciprocal rank
+            ranks.append(0)
+            continue
+        r = rank_of(s, label - 1, hist - 1)
+        ranks.append(r)
+        if r <= top_k:
+            hit += 1
+        rr.append(np.reciprocal(float(r)))
+    return hit, np.array(rr), np.array(ranks, dtype=np.int64)

@@ -255,6 +255,64 @@ def eval_case(name, cfg_name, n_rows, seed=17):
     g["meta"] = np.array([cfg_name, str(seed), torch.__version__])
     np.savez_compressed(os.path.join(OUT, f"{name}.npz"), **g)
     print(f"[golden] {name}: rows={n_rows} pp[0]={g['pp'][0]:.5f} ir={ir[:4]}")
+    eval_accuracy_case(name.replace("eval_", "eval_accuracy_"), cfg_name, seed, ev=ev)
+
+
+ACC_TOP_K, ACC_USE_H = (1, 20), (True, False)
+
+
+def accuracy_batch(cfg, sd, seed):
+    """The 8 post-padded rows [8, max_len + 1] of the accuracy golden.  The logits a row is ranked on sit at the position in
+    front of its label and the mask is causal, so a label can be chosen AFTER the rest of the row, from the CPU oracle's ranking
+    of that position:
+      0: a full window (no zero: end = max_len, the label is the column seq[:-1] cuts off)
+      1: the label also occurs in its history (skipped under use_h, counted without)
+      2 / 3: the label's rank with the history removed is exactly 20 / exactly 1
+      4 / 5: the label's rank over the whole catalog is exactly 20 / exactly 1
+      6: the label's filtered rank is 21 (one behind a hit at top_k = 20)
+      7: the shortest row, one history item and the label."""
+    from oracle import oracle_np as O
+    L, N = cfg.max_len, cfg.n_item
+    rng = np.random.default_rng(seed + 1)
+    lens = [L + 1, L // 2, L - 3, 5, L // 3, 7, L - 1, 2]
+    seqs = np.zeros((8, L + 1), dtype=np.int64)
+    for i, n in enumerate(lens):
+        seqs[i, :n] = rng.choice(N, size=n, replace=False) + 1
+    seqs[1, lens[1] - 1] = seqs[1, 2]
+    W, b = sd["project.weight"], sd["project.bias"]
+    for i, (filtered, place) in {2: (True, 20), 3: (True, 1), 4: (False, 20), 5: (False, 1), 6: (True, 21)}.items():
+        end = lens[i] - 1
+        x, _ = O.decode(sd, cfg, seqs[i, :-1], None, evaluator=True)
+        order = O.topk(O.score_chain(x[end - 1], W, b), N)[1] + 1  # 1-based ids, (score desc, id asc)
+        if filtered:
+            order = order[~np.isin(order, seqs[i, :end])]
+        seqs[i, end] = order[place - 1]
+    return seqs
+
+
+def eval_accuracy_case(name, cfg_name, seed=17, ev=None):
+    """Evaluator.get_accuracy_metrics_in_batch of the unmodified reference on accuracy_batch(), at every (top_k, use_h) of
+    ACC_TOP_K x ACC_USE_H: arrays only (the rows as int16, hit counts, reciprocal ranks)."""
+    cfg = synth.make_config(cfg_name)
+    sd = synth.irn_state_dict(cfg, seed, evaluator=True)
+    if ev is None:
+        torch.manual_seed(0)
+        net = _load(SampleNet(cfg), sd)
+        net.eval()
+        ev = Evaluator(cfg, net, "cpu")
+        ev.eval()
+    seqs = accuracy_batch(cfg, sd, seed)
+    assert seqs.max() < 2 ** 15
+    g = {"seqs": seqs.astype(np.int16)}
+    with torch.no_grad():
+        for k in ACC_TOP_K:
+            for h in ACC_USE_H:
+                hit, rr = ev.get_accuracy_metrics_in_batch(torch.from_numpy(seqs), k, h)
+                g[f"hit_k{k}_h{int(h)}"] = np.array(hit, dtype=np.int64)
+                g[f"rr_k{k}_h{int(h)}"] = np.asarray(rr, dtype=np.float64)
+    np.savez_compressed(os.path.join(OUT, f"{name}.npz"), **g)
+    print(f"[golden] {name}: " + " ".join(f"{k}={v.tolist() if v.ndim == 0 else np.round(1 / v).astype(int).tolist()}"
+                                           for k, v in g.items() if k != "seqs"))
 
 
 def contract_case():
@@ -421,6 +479,8 @@ CASES = {
     "irn_c4d": lambda: irn_case("irn_c4d", "c4d", 32),
     "eval_tiny": lambda: eval_case("eval_tiny", "eval_tiny", 8),
     "eval_default": lambda: eval_case("eval_default", "eval_default", 6),
+    "eval_accuracy_tiny": lambda: eval_accuracy_case("eval_accuracy_tiny", "eval_tiny"),
+    "eval_accuracy_default": lambda: eval_accuracy_case("eval_accuracy_default", "eval_default"),
     "contract": contract_case,
     "harness_tiny": harness_case,
     "train_tiny": train_case,

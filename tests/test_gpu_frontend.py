@@ -144,6 +144,34 @@ def test_evaluator_handlers_match_reference(golden, name, cfgname):
         assert np.abs(got - ref).max() < 5e-5
 
 
+@pytest.mark.parametrize("name,cfgname", [("eval_accuracy_tiny", "eval_tiny"), ("eval_accuracy_default", "eval_default")])
+def test_evaluator_accuracy_metrics_match_reference_and_oracle(oracle, golden, name, cfgname):
+    """Evaluator.get_accuracy_metrics_in_batch against the unmodified reference's recorded (hit, rr) and against the numpy
+    restatement oracle.eval_accuracy_metrics, on the golden's 8 post-padded rows (a full window, a label inside its own
+    history, labels at rank exactly top_k and one behind): hit counts equal, reciprocal ranks equal as reciprocals of
+    integer ranks."""
+    g = golden(name)
+    cfg = synth.make_config(cfgname)
+    sd = synth.irn_state_dict(cfg, 17, evaluator=True)
+    net = SampleNet(cfg)
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    net.to(DEV)
+    ev = Evaluator(cfg, net, DEV)
+    ev.eval()
+    seqs_np = g["seqs"].astype(np.int64)
+    seqs = torch.from_numpy(seqs_np).to(DEV)
+    before = seqs.clone()
+    with torch.no_grad():
+        for k in (1, 20):
+            for h in (True, False):
+                hit, rr = ev.get_accuracy_metrics_in_batch(seqs, k, h)
+                o_hit, o_rr, _ = oracle.eval_accuracy_metrics(sd, cfg, seqs_np, k, h)
+                assert hit == int(g[f"hit_k{k}_h{int(h)}"]) == o_hit, (k, h)
+                assert isinstance(rr, np.ndarray) and np.array_equal(rr, g[f"rr_k{k}_h{int(h)}"]), (k, h, 1 / rr)
+                assert np.array_equal(rr, o_rr), (k, h)
+    assert torch.equal(seqs, before)
+
+
 def test_device_eval_batch_matches_reference_loader_layout(golden):
     """irs_build_eval_batch against the reference loader's own output (contract golden:
     DataLoaderEvalIRS._collate_fn over rows built the way get_random_evaluate_data builds them), for gap 0 and 5;

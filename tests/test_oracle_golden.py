@@ -113,6 +113,30 @@ def test_evaluator_metrics(oracle, golden, name, cfgname):
     assert np.allclose(avg, g["avg_ps"], atol=5e-6) and np.allclose(ioi, g["iois"], atol=5e-6)
 
 
+@pytest.mark.parametrize("name,cfgname", [("eval_accuracy_tiny", "eval_tiny"), ("eval_accuracy_default", "eval_default")])
+def test_evaluator_accuracy_metrics(oracle, golden, name, cfgname):
+    """Evaluator.get_accuracy_metrics_in_batch as the unmodified reference ran it on 8 post-padded rows (make_golden.py:
+    accuracy_batch -- a full window, a label inside its own history, labels at rank exactly top_k): the hit count equal, the
+    reciprocal ranks equal as reciprocals of integer ranks."""
+    g = golden(name)
+    cfg = synth.make_config(cfgname)
+    sd = synth.irn_state_dict(cfg, 17, evaluator=True)
+    seqs = g["seqs"].astype(np.int64)
+    assert seqs.shape == (8, cfg.max_len + 1) and (seqs[0] > 0).all() and seqs[1, -1] == 0
+    lab1 = seqs[1][seqs[1] > 0][-1]
+    assert lab1 in seqs[1][seqs[1] > 0][:-1]  # row 1: the label also occurs in its history
+    ranks = {}
+    for k in (1, 20):
+        for h in (True, False):
+            hit, rr, ranks[h] = oracle.eval_accuracy_metrics(sd, cfg, seqs, k, h)
+            assert hit == int(g[f"hit_k{k}_h{int(h)}"]), (k, h)
+            assert np.array_equal(rr, g[f"rr_k{k}_h{int(h)}"]), (k, h, 1 / rr, 1 / g[f"rr_k{k}_h{int(h)}"])
+            assert len(rr) == (7 if h else 8) and hit == int((1 / rr <= k + 0.5).sum())
+    # the edges the batch was built for: skipped under use_h only; ranks exactly top_k, and one behind it
+    assert ranks[True][1] == 0 and ranks[False][1] > 0
+    assert list(ranks[True][[2, 3, 6]]) == [20, 1, 21] and list(ranks[False][[4, 5]]) == [20, 1]
+
+
 def test_selection_definitions(oracle):
     """top-k / rank total order (score desc, id asc), ties, -0 == +0, k > N."""
     s = np.array([1.0, 3.0, 3.0, -0.0, 0.0, 2.0], dtype=np.float32)
