@@ -12,6 +12,7 @@
 // k_block_small*); attention per (sequence, head), masks never materialised (k_attn16, k_attn_mfma, k_attn_row*; k_attn_long, k_attn_row_long behind
 // windows longer than 256 tokens); packing, gathers.
 #include "irs_internal.h"
+#include "plane_split.h"
 
 #include <assert.h>
 
@@ -1641,13 +1642,8 @@ __device__ __forceinline__ void x6_split(const f32x16 &t, int s, x6_f16x8 (&X)[2
     for (int p = 0; p < 2; ++p) X[p] = __builtin_bit_cast(x6_f16x8, make_float4(t[8 * s + p], t[8 * s + p + 1], t[8 * s + p + 2], t[8 * s + p + 3]));
     return;
 #endif
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float v = t[8 * s + j];
-        const _Float16 h = (_Float16)v;
-        X[0][j] = h;
-        X[1][j] = (_Float16)(v - (float)h);
-    }
+    const float v[8] = {t[8 * s], t[8 * s + 1], t[8 * s + 2], t[8 * s + 3], t[8 * s + 4], t[8 * s + 5], t[8 * s + 6], t[8 * s + 7]};
+    irs_split_planes(v, X[0], X[1]); // (plane_split.h: three vector instructions per pair)
 }
 __device__ __forceinline__ f32x16 x6_mma(const x6_bf16x8 &w, const x6_bf16x8 &x, const f32x16 &c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, x, c, 0, 0, 0);
@@ -2615,13 +2611,11 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
                     const float4 bb = __builtin_bit_cast(float4, rb);
                     const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
                     f16x4 hp, lp;
+                    const float x[4] = {__builtin_fmaf(t[4 * g], IWS, bv[0]), __builtin_fmaf(t[4 * g + 1], IWS, bv[1]),
+                                        __builtin_fmaf(t[4 * g + 2], IWS, bv[2]), __builtin_fmaf(t[4 * g + 3], IWS, bv[3])};
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float x = __builtin_fmaf(t[4 * g + e], IWS, bv[e]);
-                        const _Float16 hv = (_Float16)x;
-                        hp[e] = hv;
-                        lp[e] = (_Float16)(x - (float)hv);
-                    }
+                    for (int e = 0; e < 4; ++e) hp[e] = (_Float16)x[e]; // (one mixed fma from t, IWS and the bias: as the compiler selects it)
+                    irs_split_low(x, hp, lp);
                     if constexpr (c == 1) {
                         // K as two float16 planes (the score products of seq_attn_block): 128 B per key = chunks 0 .. 3 plane h, 4 .. 7
                         // plane l (chunk = 8 channels), chunk index ^ ((key >> 1) & 7): a tile's 16 keys x one chunk = 16 bank groups
@@ -2927,13 +2921,11 @@ __global__ void __launch_bounds__(64 * NW, (NT == 8 || NW == 8) ? 1 : 2) k_block
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         f16x4 hp, lp;
+                        const float v[4] = {__builtin_fmaf(qt[4 * g], IWS, bt[4 * g]), __builtin_fmaf(qt[4 * g + 1], IWS, bt[4 * g + 1]),
+                                            __builtin_fmaf(qt[4 * g + 2], IWS, bt[4 * g + 2]), __builtin_fmaf(qt[4 * g + 3], IWS, bt[4 * g + 3])};
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float v = __builtin_fmaf(qt[4 * g + e], IWS, bt[4 * g + e]);
-                            const _Float16 hv = (_Float16)v;
-                            hp[e] = hv;
-                            lp[e] = (_Float16)(v - (float)hv);
-                        }
+                        for (int e = 0; e < 4; ++e) hp[e] = (_Float16)v[e];
+                        irs_split_low(v, hp, lp);
                         *reinterpret_cast<f16x4 *>(slot + 16 * g) = hp;       // channels 8 g + 4 lk .. + 3 of plane h
                         *reinterpret_cast<f16x4 *>(slot + 64 + 16 * g) = lp;  // ... of plane l
                     }
@@ -4710,17 +4702,12 @@ typedef const __attribute__((address_space(1))) void attn_glb_void;
 //     row as [32 f16 h | 32 f16 l] -- the same 128 bytes as 32 floats -- so the fill is pure LDS-DMA (16 key rows x 64 B of
 //     one plane per instruction, chunks swizzled on the source side) and costs no vector instruction;
 //   * two planes are 256 B per key, the float32 images' footprint: three workgroups per CU as before;
-//   * p = exp2(s - m) is split into two planes (3 vector instructions per value: v_cvt_pk_f16_f32, back, subtract, again).
+//   * p = exp2(s - m) is split into two planes (3 vector instructions per PAIR: v_cvt_pk_f16_f32 and two mixed fmas, plane_split.h).
 // The plane images are [plane][key][64 B], V^T operands come by the transposing ds_read_b64_tr_b16, and the two score tiles of a
 // pair sit side by side as the 32-key B operand.
 typedef __attribute__((ext_vector_type(4))) short attn_s16x4; // operand type of the transposing LDS read
 __device__ __forceinline__ void attn_split8h(const float (&v)[8], x6_f16x8 (&P)[2]) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const _Float16 h = (_Float16)v[j];
-        P[0][j] = h;
-        P[1][j] = (_Float16)(v[j] - (float)h);
-    }
+    irs_split_planes(v, P[0], P[1]);
 }
 // The head count for the fragment-major store: the float32 form takes it as an argument; the plane form, launched only over
 // (head, sequence) grids, reads the x extent of its grid (its argument is this empty struct: one byte behind out_frag).
@@ -5197,8 +5184,15 @@ __device__ __forceinline__ void seq_attn_block(const float *Ks, const char *Vp, 
     // scores on exact float16 plane products (round 5): K arrives as two planes (the front's epilogue splits each key row
     // once), q is split here once per block; Kl.qh + Kh.ql + Kh.qh on v_mfma_f32_16x16x32_f16 (the whole head dim in one
     // instruction: 3 x 16 cycles per tile instead of 8 x 32 on the float32 pipe).  Lane (lq, gq): key 16 kt + lq, channels 8 gq ..
+    // (q keeps the plain statement, once per block: qf = t * sc is a product, and the compiler contracts it into the subtraction --
+    //  l = f16(fma(t, sc, -h)), the product unrounded; the helper's f16(qf - h) differs from that in the last bit of some l)
     x6_f16x8 Q[2];
-    attn_split8h(qf, Q);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const _Float16 h = (_Float16)qf[j];
+        Q[0][j] = h;
+        Q[1][j] = (_Float16)(qf[j] - (float)h);
+    }
     const char *Kc = reinterpret_cast<const char *>(Ks);
     auto score_tile = [&](int kt, f32x4 &sa) __attribute__((always_inline)) {
         const int key = kt * 16 + lq;
