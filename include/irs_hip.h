@@ -691,6 +691,95 @@ size_t irs_guide_scratch_bytes(const irs_ctx *ctx, int32_t kind, int32_t F);
 int irs_bind_guide(irs_ctx *ctx, int32_t kind, const void *dev_table, int32_t F, int32_t k_c, void *dev_scratch, size_t bytes,
                    void *stream);
 
+/* ---- lookahead choice: among the top k_c candidates, the one that moves the target furthest (opt-in; BUILD-DEFINED: the
+ *      reference steers with the impressionability mask alone, Rec2Inf with a static feature distance; here the model itself is
+ *      asked where the target stands one step after each candidate.  The host-side alternative costs k_c decode round trips per
+ *      step) ------------------------------------------------------------------------------------------------------------------
+ * A context can hold one bound LOOKAHEAD with a candidate count k_c in [1, IRS_MAX_LOOKAHEAD_KC].  While it does, a greedy step
+ * of the loops does this for a live row, behind the top-k, the survivor pass, the trace sweep and the arrival offer and BEFORE
+ * the path step:
+ *   1. EXPAND.  It walks the row's ranked list exactly as irs_path_step does, with the same admissibility test: the window
+ *      seq[row, 0 .. hep[row]], plus the bound exclusion list (looked up through the until loop's row map), plus the path so far
+ *      under no_repeat.  The list ends at its first negative id.  The first min(k_c, available) survivors are collected in rank
+ *      order.  For survivor j, child row * k_c + j is the parent window after irs_path_step would have chosen that item, byte
+ *      for byte: grow (hep < L - 2: the item goes to slot hep + 1, child_hep = hep + 1) or shift (slots 1 .. L - 2 move down by
+ *      one, the item goes to slot L - 2, child_hep = hep), the target kept in slot L - 1.  child_user is the parent's user (0
+ *      without one), child_target0 the parent's target as a 0-based id, seq[row][L - 1] - 1.  A slot j without a survivor holds
+ *      a copy of the parent window with the parent's hep (well-formed to decode), candidate id -1 and candidate value -inf.
+ *      cand_ids0 [M, k_c] int64 (0-based) and cand_val [M, k_c] float are the survivors' entries of the list.  A row with
+ *      fin != 0 expands as a row without survivors.
+ *   2. SCORE.  One rows-only decode of the M k_c child windows at child_hep, then irs_score_lse and irs_score_gather (one id per
+ *      row: child_target0) on those rows.  lp[row][j] = (float)((double)ts - ((double)max + log((double)sumexp))), the path
+ *      trace's expression, rounded to float32 once; a slot without a candidate reads -inf.  t == 0, or t outside the catalog:
+ *      ts is -inf, and so is every lp.
+ *   3. CHOOSE.  If the target itself is among the row's candidates it is chosen outright: offering it is the arrival.  Otherwise
+ *      the candidates are walked in rank order: a later one replaces the current best only if its lp is STRICTLY greater; a NaN
+ *      never replaces anything and is replaced by anything that is not a NaN (the guide's tie rules: ties go to the better rank,
+ *      and an all -inf row keeps its first survivor, the greedy choice).  The row's list is then rewritten as irs_arrival_offer
+ *      rewrites it: entry 0 becomes (cand_val, cand_ids0) of the chosen candidate -- its ORIGINAL score -- and entry 1 becomes
+ *      (-inf, -1) when k > 1.  A row without a survivor is not written (the unchanged path step reports IRS_ROW_NO_CANDIDATE);
+ *      a row with fin != 0 is not written.  lp [M, k_c] float32, the values compared, and choice [M] int32 (the chosen slot, -1:
+ *      none; -1 for a row with fin != 0) are written for every row, so that every decision can be replayed from arrays.
+ *   4. STEP.  The unchanged irs_path_step takes its only survivor and the unchanged trace record finds the chosen item in entry
+ *      0; irs_generate_paths_until retires a user whose choice was the target.
+ * Consequences: k_c = 1 gives the greedy search id for id; after the step the row's window equals the chosen child's window
+ * byte for byte; no atomics, so two identical calls give identical bytes.
+ * irs_lookahead_scratch_bytes(ctx, rows, k_c): the caller-owned scratch for `rows` parent rows: the child windows, hep, users
+ *   and targets, the child rows [rows k_c, d], max / sumexp / target score, candidate ids and values, lp and choice, every array
+ *   rounded up to 256 bytes.  0 for invalid arguments (rows < 1, k_c outside [1, IRS_MAX_LOOKAHEAD_KC]).  irs_workspace_bytes
+ *   does not change.
+ * irs_bind_lookahead(ctx, k_c, dev_scratch, bytes, dev_rec_item, dev_rec_lp, users, ld):
+ *   k_c == 0 unbinds.  dev_scratch: 16-byte aligned, >= irs_lookahead_scratch_bytes(ctx, users, k_c), valid until the unbind.
+ *   dev_rec_item int32 [users, ld, k_c] (1-based candidate ids, 0: none) and dev_rec_lp float [users, ld, k_c] are the RECORD;
+ *   both may be NULL (they go together).  When given, the choose step of a loop also writes each live row's candidates and lp
+ *   at the caller's row (through the until loop's row map) and the step's column (the device step counter), exactly as the
+ *   trace record does; irs_generate_paths_until zeroes rows [0, B) of both at entry, so a record is zero behind an arrival.
+ *   Bind and unbind drop the captured steps of the context; the binding is part of a captured step's key.
+ *   Refused before any launch, each with a message naming irs_bind_lookahead: k_c outside [0, IRS_MAX_LOOKAHEAD_KC], users or
+ *   ld < 1, one record pointer without the other, a scratch that is NULL, too small or misaligned -> IRS_E_INVALID; world != 1
+ *   -> IRS_E_UNSUPPORTED; a bound guide (irs_bind_guide) -> IRS_E_UNSUPPORTED, and irs_bind_guide refuses the same way while
+ *   a lookahead is bound.
+ * While bound:
+ *   irs_generate_paths (stream launches and the captured step alike) and irs_generate_paths_until apply the rule;
+ *     sample != 0 -> IRS_E_UNSUPPORTED; k < k_c, B > users, max_path_len > ld (with a record) -> IRS_E_INVALID; B k_c above
+ *     max_seqs or max_rows -> IRS_E_INVALID with both numbers in the message; all before any launch;
+ *   irs_beam_step[_until], irs_beam_search[_until] and the two _sharded loops return IRS_E_UNSUPPORTED;
+ *   exclusions, no_repeat, the trace and the arrival rule compose as under a guide; with exact candidates bound as well the
+ *     loops ask the survivor pass for want = k_c;
+ *   the route where one workgroup ranks and steps a row is not taken;
+ *   irs_path_step ALONE is unchanged: the rule lives in the loops and in the two entry points below;
+ *   irs_decoder_route_last reports the INNER decode (of the children), the last one a step launches.
+ * irs_lookahead_expand / irs_lookahead_choose are the two kernels alone, for tests and for replaying a decision from arrays (no
+ * binding needed; bound exclusions are honoured as irs_path_step honours them).  Unlike the loops they are SYNCHRONOUS and take
+ * no stream: the kernel is launched on the null stream and the call returns when it has finished.  The caller makes sure that
+ * the work that produces the inputs has finished (a stream created non-blocking does not wait for the null stream, nor the null
+ * stream for it); the outputs are complete on return.  Not for use inside a stream capture.
+ *  dev_seq int64 [M, L], dev_hep int32 [M], dev_user int64 [M] (may be NULL on a context whose mask needs no user)
+ *  dev_val float [M, k] / dev_ids0 int64 [M, k]: the rows' ranked lists (expand reads them, choose rewrites them)
+ *  dev_fin int32 [M] (may be NULL); dev_paths float [users, path_ld] (may be NULL) / step: the path so far under no_repeat, as in
+ *            irs_arrival_offer; dev_row_map int32 [M] (may be NULL: the identity): row -> bound user
+ *  expand out: dev_child_seq int64 [M k_c, L], dev_child_hep int32 [M k_c], dev_child_user int64 [M k_c], dev_child_target0
+ *            int64 [M k_c], dev_cand_ids0 int64 [M, k_c], dev_cand_val float [M, k_c]
+ *  choose in: dev_cand_ids0 / dev_cand_val, dev_max / dev_sumexp / dev_target_score float [M, k_c] (of the child rows)
+ *  choose out: dev_val / dev_ids0 rewritten, dev_lp float [M, k_c], dev_choice int32 [M]
+ * Null pointers, M < 1, k outside [1, max_k], k_c outside [1, min(k, IRS_MAX_LOOKAHEAD_KC)], step < 0 or beyond path_ld, M above
+ * the bound exclusion users, no_repeat bound and dev_paths NULL, a NULL dev_user on a context whose mask needs one ->
+ * IRS_E_INVALID; world != 1 -> IRS_E_UNSUPPORTED; all before any launch.
+ * Both kernels: one wave per row, no LDS, no atomics.  With nothing bound every entry point launches exactly what it launched
+ * before. */
+#define IRS_MAX_LOOKAHEAD_KC 32
+size_t irs_lookahead_scratch_bytes(const irs_ctx *ctx, int32_t rows, int32_t k_c);
+int irs_bind_lookahead(irs_ctx *ctx, int32_t k_c, void *dev_scratch, size_t bytes, int32_t *dev_rec_item, float *dev_rec_lp,
+                       int32_t users, int32_t ld);
+int irs_lookahead_expand(irs_ctx *ctx, const int64_t *dev_seq, const int32_t *dev_hep, const int64_t *dev_user, int32_t M,
+                         const float *dev_val, const int64_t *dev_ids0, int32_t k, int32_t k_c, const int32_t *dev_fin,
+                         const float *dev_paths, int32_t path_ld, int32_t step, const int32_t *dev_row_map, int64_t *dev_child_seq,
+                         int32_t *dev_child_hep, int64_t *dev_child_user, int64_t *dev_child_target0, int64_t *dev_cand_ids0,
+                         float *dev_cand_val);
+int irs_lookahead_choose(irs_ctx *ctx, const int64_t *dev_seq, int32_t M, int32_t k_c, const int64_t *dev_cand_ids0,
+                         const float *dev_cand_val, const float *dev_max, const float *dev_sumexp, const float *dev_target_score,
+                         const int32_t *dev_fin, float *dev_val, int64_t *dev_ids0, int32_t k, float *dev_lp, int32_t *dev_choice);
+
 /* ---- arrival rule: offer the target once its rank or probability allows (opt-in; a deployed recommender shows a slate, so a
  *      persuasion path has done its work once the target stands among the best items the window leaves, not only when it is the
  *      best of them) --------------------------------------------------------------------------------------------------------------
@@ -962,7 +1051,8 @@ int irs_decoder_seq_last(const irs_ctx *ctx);
  *   rows_only, small_plan, plan, embed, layer, tail, frag, seq, kv_planes, att_fused, kv_only, x6, npl, nt
  * plan: 0 NONE (full decode), 1 MULTI, 2 SMALL, 3 IN_EMBED; embed: 0 FULL, 1 PACKED, 2 FRAG, 3 FRAG_QKV, 4 SMALL16_QKV, 5 ANY_QKV,
  * 6 SEQ; layer / tail: 0 GEMM, 1 GEMM_LN, 2 FRAG_GEMM, 3 FRAG_BLOCK, 4 FRAG_FUSED, 5 SMALL16, 6 WIDE, 7 ANY; the flags 0 / 1.
- * Writes min(n, IRS_ROUTE_FIELDS) fields to out and returns that number; IRS_E_STATE before any decode.  Launches nothing. */
+ * Writes min(n, IRS_ROUTE_FIELDS) fields to out and returns that number; IRS_E_STATE before any decode.  Launches nothing.
+ * Behind a search loop with a bound lookahead (irs_bind_lookahead) it reports the step's inner decode, of the child windows. */
 #define IRS_ROUTE_FIELDS 14
 int irs_decoder_route_last(const irs_ctx *ctx, int32_t *out, int32_t n);
 /* (tests / lab) device address of a decoder workspace buffer: 0 x (fragment-major), 1 attention output (fragment-major), 2 / 3 the

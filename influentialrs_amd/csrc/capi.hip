@@ -693,6 +693,7 @@ extern "C" int irs_bind_guide(irs_ctx *ctx, int32_t kind, const void *table, int
     const int f_max = kind == IRS_GUIDE_BINARY ? IRS_MAX_GUIDE_BITS : IRS_MAX_GUIDE_FLOATS;
     if (F > f_max) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide: F %d > %d (%s)", F, f_max, kind == IRS_GUIDE_BINARY ? "bits" : "floats");
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide needs the whole catalog on one device");
+    if (ctx->look_on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide: a lookahead is bound (irs_bind_lookahead): one choice rule at a time");
     if (k_c > ctx->dims.max_k) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_guide: k_c %d > max_k %d", k_c, ctx->dims.max_k);
     const int64_t rows = ctx->dims.n_item + 1;
     irs_guide g{table, rows, F, 0, k_c, kind};
@@ -721,6 +722,104 @@ static int check_guide(irs_ctx *ctx, const char *fn, int k, int sample) {
 static int refuse_guide(irs_ctx *ctx, const char *fn) {
     if (ctx->guide_on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a guide is bound (irs_bind_guide): greedy loops only", fn);
     return IRS_OK;
+}
+
+// ------------------------------------------------------------------ bound lookahead (irs_bind_lookahead; lookahead.hip)
+extern "C" size_t irs_lookahead_scratch_bytes(const irs_ctx *ctx, int32_t rows, int32_t k_c) {
+    if (!ctx || rows < 1 || k_c < 1 || k_c > IRS_MAX_LOOKAHEAD_KC) return 0;
+    return irs_look_layout(nullptr, rows, k_c, ctx->dims.max_len, ctx->dims.d, nullptr);
+}
+
+extern "C" int irs_bind_lookahead(irs_ctx *ctx, int32_t k_c, void *scratch, size_t bytes, int32_t *rec_item, float *rec_lp,
+                                  int32_t users, int32_t ld) {
+    if (!ctx) return IRS_E_INVALID;
+    if (k_c == 0) { // unbind
+        if (ctx->look_on) irs_drop_graphs(ctx);
+        ctx->look_on = ctx->look_kc = ctx->look_users = ctx->look_ld = 0;
+        ctx->look_scratch = nullptr, ctx->look_rec_item = nullptr, ctx->look_rec_lp = nullptr;
+        return IRS_OK;
+    }
+    if (k_c < 0 || k_c > IRS_MAX_LOOKAHEAD_KC) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_lookahead: k_c %d outside [0, %d]", k_c, IRS_MAX_LOOKAHEAD_KC);
+    if (users < 1 || ld < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_lookahead: users >= 1 and ld >= 1");
+    if ((rec_item == nullptr) != (rec_lp == nullptr)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_lookahead: the two record arrays go together");
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_lookahead needs the whole catalog on one device");
+    if (ctx->guide_on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_lookahead: a guide is bound (irs_bind_guide): one choice rule at a time");
+    const size_t need = irs_look_layout(nullptr, users, k_c, ctx->dims.max_len, ctx->dims.d, nullptr);
+    if (!scratch || bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_lookahead: scratch too small: %zu < %zu", scratch ? bytes : (size_t)0, need);
+    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_lookahead: scratch must be 16-byte aligned");
+    ctx->look_on = 1, ctx->look_kc = k_c, ctx->look_users = users, ctx->look_ld = ld;
+    ctx->look_scratch = scratch, ctx->look_rec_item = rec_item, ctx->look_rec_lp = rec_lp;
+    irs_drop_graphs(ctx); // (a captured step holds the two kernels and the inner decode with these pointers, or none of them)
+    return IRS_OK;
+}
+// the greedy loops while a lookahead is bound: the rule is deterministic, it chooses among k_c candidates of the list, and its
+// B * k_c children are decoded and scored in one call each
+static int check_lookahead(irs_ctx *ctx, const char *fn, int B, int P, int k, int sample) {
+    if (!ctx->look_on) return IRS_OK;
+    const int kc = ctx->look_kc;
+    if (sample) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a lookahead is bound (irs_bind_lookahead): the choice is deterministic, sample must be 0", fn);
+    if (k < kc) IRS_FAIL(ctx, IRS_E_INVALID, "%s: a lookahead is bound (irs_bind_lookahead): k=%d < k_c=%d", fn, k, kc);
+    if (B > ctx->look_users) IRS_FAIL(ctx, IRS_E_INVALID, "%s: B=%d, the lookahead is bound for %d users", fn, B, ctx->look_users);
+    if (ctx->look_rec_item && P > ctx->look_ld)
+        IRS_FAIL(ctx, IRS_E_INVALID, "%s: path length %d, the lookahead record is bound for %d steps", fn, P, ctx->look_ld);
+    if ((int64_t)B * kc > ctx->max_seqs || (int64_t)B * kc > ctx->max_rows)
+        IRS_FAIL(ctx, IRS_E_INVALID, "%s: a lookahead is bound (irs_bind_lookahead): B*k_c=%lld exceeds max_seqs=%d / max_rows=%d", fn,
+                 (long long)B * kc, ctx->max_seqs, ctx->max_rows);
+    return IRS_OK;
+}
+// the beam steps and loops have no lookahead form: they refuse while one is bound
+static int refuse_lookahead(irs_ctx *ctx, const char *fn) {
+    if (ctx->look_on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a lookahead is bound (irs_bind_lookahead): greedy loops only", fn);
+    return IRS_OK;
+}
+
+// The two kernels alone (tests, and replaying a recorded decision from arrays): SYNCHRONOUS calls.  They take no stream: the
+// kernel is launched on the null stream and the call returns when it has finished, so nothing of it is in flight between calls
+// and there is no stream order for a caller to keep (include/irs_hip.h).  What the two entry points share:
+static int look_run_sync(irs_ctx *ctx, int rc) {
+    if (rc) return rc;
+    IRS_CHECK_HIP(ctx, hipStreamSynchronize(nullptr));
+    return IRS_OK;
+}
+static int check_look_call(irs_ctx *ctx, const char *fn, bool ptrs_ok, int M, int k, int k_c) {
+    if (!ptrs_ok) IRS_FAIL(ctx, IRS_E_INVALID, "%s: null pointer", fn);
+    if (M < 1) IRS_FAIL(ctx, IRS_E_INVALID, "%s: M must be >= 1", fn);
+    if (k < 1 || k > ctx->dims.max_k) IRS_FAIL(ctx, IRS_E_INVALID, "%s: k must be in [1, %d]", fn, ctx->dims.max_k);
+    if (k_c < 1 || k_c > k || k_c > IRS_MAX_LOOKAHEAD_KC)
+        IRS_FAIL(ctx, IRS_E_INVALID, "%s: k_c must be in [1, min(k, %d)]", fn, IRS_MAX_LOOKAHEAD_KC);
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s needs the whole catalog on one device", fn);
+    return IRS_OK;
+}
+
+extern "C" int irs_lookahead_expand(irs_ctx *ctx, const int64_t *seq, const int32_t *hep, const int64_t *user, int32_t M, const float *val,
+                                    const int64_t *ids0, int32_t k, int32_t k_c, const int32_t *fin, const float *paths, int32_t path_ld,
+                                    int32_t step, const int32_t *row_map, int64_t *child_seq, int32_t *child_hep, int64_t *child_user,
+                                    int64_t *child_target0, int64_t *cand_ids0, float *cand_val) {
+    if (!ctx) return IRS_E_INVALID;
+    int rc = check_look_call(ctx, "irs_lookahead_expand",
+                             seq && hep && val && ids0 && child_seq && child_hep && child_user && child_target0 && cand_ids0 && cand_val, M, k, k_c);
+    if (rc) return rc;
+    if (ctx->dims.mask_mode == IRS_MASK_IRN && !user) IRS_FAIL(ctx, IRS_E_INVALID, "irs_lookahead_expand: user is null");
+    if (step < 0 || (paths && (path_ld < 1 || step > path_ld)))
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_lookahead_expand: step must be in [0, path_ld], path_ld >= 1");
+    if (ctx->excl_on && ctx->excl_no_repeat && !paths) IRS_FAIL(ctx, IRS_E_INVALID, "irs_lookahead_expand: no_repeat is bound: dev_paths is null");
+    if ((rc = check_excl(ctx, "irs_lookahead_expand", M, step))) return rc;
+    const irs_look_expand_args a{seq, hep, user, M, ctx->dims.max_len, k, k_c, val, ids0, fin, nullptr, step,
+                                 excl_args(ctx, 1, row_map, paths, path_ld, 1, nullptr, step),
+                                 child_seq, child_user, child_target0, cand_ids0, child_hep, cand_val};
+    return look_run_sync(ctx, irs_launch_lookahead_expand(ctx, a, nullptr));
+}
+
+extern "C" int irs_lookahead_choose(irs_ctx *ctx, const int64_t *seq, int32_t M, int32_t k_c, const int64_t *cand_ids0, const float *cand_val,
+                                    const float *mx, const float *sm, const float *tscore, const int32_t *fin, float *val, int64_t *ids0,
+                                    int32_t k, float *lp, int32_t *choice) {
+    if (!ctx) return IRS_E_INVALID;
+    const int rc = check_look_call(ctx, "irs_lookahead_choose", seq && cand_ids0 && cand_val && mx && sm && tscore && val && ids0 && lp && choice,
+                                   M, k, k_c);
+    if (rc) return rc;
+    const irs_look_choose_args a{seq, M, ctx->dims.max_len, k, k_c, cand_ids0, cand_val, mx, sm, tscore, fin, val, ids0, lp, choice,
+                                 nullptr, nullptr, 0, nullptr, nullptr};
+    return look_run_sync(ctx, irs_launch_lookahead_choose(ctx, a, nullptr));
 }
 
 extern "C" int irs_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int32_t B, const float *val, const int64_t *ids0,
@@ -755,13 +854,16 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
     // small shard, few rows: the workgroup that ranks a row's candidates also takes the row's path step
     // (not while exact candidates are bound: the survivor pass goes between the ranking and the step; nor while exclusions are
     //  bound: only the separate step kernel has the form that tests them; nor while a path trace is bound: its sweep reads the
-    //  window before the step, its record kernel the lists after it; nor while a guide is bound: the guided step is a kernel of its own)
-    if (merged && !ctx->surv_scratch && !ctx->excl_on && !ctx->tr_on && !ctx->guide_on && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k))
+    //  window before the step, its record kernel the lists after it; nor while a guide is bound: the guided step is a kernel of its own;
+    //  nor while a lookahead is bound: its expand, inner decode and choose go between the ranking and the step)
+    if (merged && !ctx->surv_scratch && !ctx->excl_on && !ctx->tr_on && !ctx->guide_on && !ctx->look_on && sweep != IRS_SWEEP_EXHAUSTIVE &&
+        irs_topk_is_direct(ctx, B, k))
         return irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, &pa);
     if ((rc = irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, nullptr, nullptr, carry)))
         return rc;
     if (ctx->surv_scratch) {
-        const int want = ctx->guide_on ? ctx->guide.k_c : (pa.sample ? pa.sample_k : 1); // (a guided step chooses among k_c)
+        // (a guided step and a lookahead step choose among k_c)
+        const int want = ctx->guide_on ? ctx->guide.k_c : (ctx->look_on ? ctx->look_kc : (pa.sample ? pa.sample_k : 1));
         const irs_surv_args sa{ctx->xrows, pa.seq, pa.hep, B, 1, k, want, ctx->surv_rows, nullptr, surv_fin, nullptr,
                                ctx->top_val, ctx->top_ids, pa.status, nullptr, pa.ex};
         if ((rc = irs_launch_survivors(ctx, sa, ctx->surv_scratch, s))) return rc;
@@ -775,6 +877,31 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
     if (ctx->arr_on && (rc = irs_launch_arrival_offer(ctx, pa.seq, pa.hep, B, tr.mx, tr.sm, tr.ts, tr.rank, surv_fin, ctx->top_val,
                                                       ctx->top_ids, k, ctx->arr_rank, ctx->arr_lp, pa.status, pa.ex, s)))
         return rc;
+    if (ctx->look_on) {
+        // Lookahead choice: expand -> decode of the B * k_c children -> LSE and the target's score on their rows -> choose.
+        // The inner decode and the two scoring passes run on the context's workspace in the middle of the step.  What they write
+        // there: the decoder's activations (act_*) and plan tables (tok_row, seq_*, m_dev, tile_*, qrow_tile, n_wg_dev), all dead
+        // once the outer decode has delivered ctx->xrows; ctx->lse_part, which no launch of this step reads again (the trace sweep
+        // has reduced its own partials into the trace scratch); ctx->route_last, which then reports the inner decode.  What must
+        // survive them and does, because they write none of it: ctx->xrows (anyway read for the last time by the survivor pass and
+        // the trace sweep above), ctx->top_val / top_ids, the trace scratch, ctx->row_status, the carried thresholds (ctx->thr
+        // and thr_valid / thr_M / thr_k: irs_launch_topk's alone) and ctx->step_ctr (ctx->step_pair is null here, so the inner
+        // plan kernel does not hand the step counter over).  Everything the lookahead itself produces -- child windows, hep,
+        // users, targets, the child rows, max / sumexp / target score, candidates, lp, choice -- lies in the caller's scratch.
+        const int kc = ctx->look_kc, N = B * kc;
+        irs_look_rows lk;
+        irs_look_layout(ctx->look_scratch, ctx->look_users, kc, ctx->dims.max_len, ctx->dims.d, &lk);
+        const irs_look_expand_args ea{pa.seq, pa.hep, user, B, ctx->dims.max_len, k, kc, ctx->top_val, ctx->top_ids, surv_fin,
+                                      pa.step_ptr, pa.step_arg, pa.ex, lk.seq, lk.user, lk.tgt0, lk.ids0, lk.hep, lk.val};
+        if ((rc = irs_launch_lookahead_expand(ctx, ea, s))) return rc;
+        if ((rc = irs_launch_decode(ctx, lk.seq, user ? lk.user : nullptr, N, nullptr, lk.hep, lk.x, nullptr, s))) return rc;
+        if ((rc = irs_launch_lse(ctx, lk.x, N, lk.mx, lk.sm, s))) return rc;
+        if ((rc = irs_launch_gather(ctx, lk.x, N, lk.tgt0, 1, lk.ts, s))) return rc;
+        const irs_look_choose_args ca{pa.seq, B, ctx->dims.max_len, k, kc, lk.ids0, lk.val, lk.mx, lk.sm, lk.ts, surv_fin, ctx->top_val,
+                                      ctx->top_ids, lk.lp, lk.choice, ctx->look_rec_item, ctx->look_rec_lp, ctx->look_ld, row_map,
+                                      ctx->step_ctr};
+        if ((rc = irs_launch_lookahead_choose(ctx, ca, s))) return rc;
+    }
     if ((rc = irs_launch_path_step(ctx, pa, B, ctx->top_val, ctx->top_ids, k, s))) return rc;
     if (ctx->tr_on) { // (the step index is still this step's: the merged loop publishes the next one in its second word)
         const irs_trace_rec rec{tr.mx, tr.sm, tr.ts, tr.rank, ctx->tr_item, ctx->tr_target, ctx->tr_rank, ctx->tr_ld};
@@ -1038,6 +1165,7 @@ static int check_search(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W
     // (a bound guide is looked at first, like the bindings at the top of the sharded loops: what it refuses needs no weights)
     int rc = W ? refuse_guide(ctx, fn) : check_guide(ctx, fn, k, sample);
     if (rc) return rc;
+    if ((rc = W ? refuse_lookahead(ctx, fn) : check_lookahead(ctx, fn, B, P, k, sample))) return rc;
     if (W && (rc = refuse_arrival(ctx, fn))) return rc;
     if ((rc = irs_ready_filter(ctx, sweep))) return rc;
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s needs the whole catalog on one device", fn);
@@ -1055,7 +1183,7 @@ static int check_search(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W
     if ((rc = irs_check_k(ctx, fn, k, 1, sweep, sample, sample_k))) return rc;
     if ((rc = check_excl(ctx, fn, B, P))) return rc;
     if (ctx->surv_scratch) { // exact candidates: the bound scratch must serve this call's rows
-        const int rows = W ? B * W : B, want = W ? W : (ctx->guide_on ? ctx->guide.k_c : (sample ? sample_k : 1));
+        const int rows = W ? B * W : B, want = W ? W : (ctx->guide_on ? ctx->guide.k_c : (ctx->look_on ? ctx->look_kc : (sample ? sample_k : 1)));
         if (want > k) IRS_FAIL(ctx, IRS_E_INVALID, "%s: exact candidates need k >= %d", fn, want);
         const size_t need = irs_surv_scratch(ctx, rows, want);
         if (ctx->surv_bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bound survivor scratch too small: %zu < %zu", fn, ctx->surv_bytes, need);
@@ -1117,6 +1245,8 @@ extern "C" int irs_generate_paths(irs_ctx *ctx, int64_t *seq, const int64_t *use
         key.tr_item = ctx->tr_item, key.tr_target = ctx->tr_target, key.tr_rank = ctx->tr_rank, key.tr_scratch = ctx->tr_scratch;
         key.arr_rank = ctx->arr_rank;
         memcpy(&key.arr_lp_bits, &ctx->arr_lp, sizeof(key.arr_lp_bits));
+        key.look_scratch = ctx->look_scratch, key.look_item = ctx->look_rec_item, key.look_lp = ctx->look_rec_lp;
+        key.look_kc = ctx->look_kc, key.look_ld = ctx->look_ld;
         return irs_replay_steps(ctx, &ctx->g_greedy, key, [&](hipStream_t q) {
             return enqueue_step(ctx, pa, user, B, k, sweep, q);
         }, max_path_len, s);
@@ -1150,6 +1280,11 @@ extern "C" int irs_generate_paths_until(irs_ctx *ctx, int64_t *seq, const int64_
         IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->tr_item, 0, n, s));
         IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->tr_target, 0, n, s));
         IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->tr_rank, 0, n, s));
+    }
+    if (ctx->look_on && ctx->look_rec_item) { // the lookahead record of a user ends with its arrival too
+        const size_t n = (size_t)B * ctx->look_ld * ctx->look_kc * 4;
+        IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->look_rec_item, 0, n, s));
+        IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->look_rec_lp, 0, n, s));
     }
     // the first steps run in place on the caller's rows (identity map); the first compaction that removes a row moves the rest.
     // (the step writes stage[row][i]: it reads the index from the same device counter as irs_generate_paths' steps)
@@ -1206,6 +1341,7 @@ extern "C" int irs_beam_step(irs_ctx *ctx, const int64_t *seq_in, const int32_t 
     int rc = refuse_trace(ctx, "irs_beam_step");
     if (rc) return rc;
     if ((rc = refuse_guide(ctx, "irs_beam_step"))) return rc;
+    if ((rc = refuse_lookahead(ctx, "irs_beam_step"))) return rc;
     if ((rc = check_excl(ctx, "irs_beam_step", B, P))) return rc;
     const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k,
                              excl_args(ctx, W, nullptr, paths_in, P, 0, nullptr, step)};
@@ -1285,6 +1421,7 @@ extern "C" int irs_beam_step_until(irs_ctx *ctx, const int64_t *seq_in, const in
     int rc = refuse_trace(ctx, "irs_beam_step_until");
     if (rc) return rc;
     if ((rc = refuse_guide(ctx, "irs_beam_step_until"))) return rc;
+    if ((rc = refuse_lookahead(ctx, "irs_beam_step_until"))) return rc;
     if ((rc = check_excl(ctx, "irs_beam_step_until", B, P))) return rc;
     const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k,
                              excl_args(ctx, W, nullptr, paths_in, P, 0, nullptr, step)};

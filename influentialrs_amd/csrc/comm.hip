@@ -321,6 +321,8 @@ static int ready_sharded(irs_ctx *ctx, irs_comm *comm, const char *fn, int sweep
         IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a bound path trace (irs_bind_path_trace) needs the whole catalog on one device", fn);
     if (ctx->guide_on) // (irs_bind_guide refuses a sharded context; the guided step exists for the single-device greedy loops only)
         IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a bound guide (irs_bind_guide) needs the whole catalog on one device", fn);
+    if (ctx->look_on) // (irs_bind_lookahead refuses a sharded context; the rule exists for the single-device greedy loops only)
+        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a bound lookahead (irs_bind_lookahead) needs the whole catalog on one device", fn);
     if (ctx->arr_on) // (the rule reads the trace, which these loops refuse: irs_set_arrival_rule)
         IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: an arrival rule (irs_set_arrival_rule) is for the single-device greedy and sampled loops", fn);
     if ((rc = irs_ready_filter(ctx, sweep))) return rc;

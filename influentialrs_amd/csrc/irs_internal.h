@@ -73,10 +73,12 @@ struct irs_step_key {
     uint64_t seed;
     const void *comm, *seq, *user, *hep, *paths, *status;
     const void *tr_item, *tr_target, *tr_rank, *tr_scratch; // the bound path trace (irs_bind_path_trace); null: none
+    const void *look_scratch, *look_item, *look_lp; // the bound lookahead (irs_bind_lookahead): scratch and record; null: none
     int32_t arr_rank;     // the arrival rule (irs_set_arrival_rule): rank_max, 0: clause off
     uint32_t arr_lp_bits; // the bits of ctx->arr_lp: lp_min, a NaN's while only the rank clause is on, 0 without a rule
+    int32_t look_kc, look_ld; // the bound lookahead's candidate count (0: none) and the record's row stride
 };
-static_assert(sizeof(irs_step_key) == 8 * sizeof(int32_t) + 11 * 8 + 2 * sizeof(int32_t), "irs_step_key is compared with memcmp: no padding");
+static_assert(sizeof(irs_step_key) == 8 * sizeof(int32_t) + 14 * 8 + 4 * sizeof(int32_t), "irs_step_key is compared with memcmp: no padding");
 struct irs_step_graph {
     hipGraphExec_t exec; // null: nothing captured
     irs_step_key key;
@@ -158,6 +160,72 @@ struct irs_guide {
     const void *table;
     int64_t rows;
     int F, words, k_c, kind;
+};
+// ---- a bound lookahead (irs_bind_lookahead; lookahead.hip).  The caller's scratch holds, for `rows` parent rows and N = rows * k_c
+// children (child row * k_c + j): what the expand step writes, what the inner decode / LSE / gather write, and what the choose
+// step writes.  Every array is rounded up to 256 bytes; a call on fewer rows uses the heads of the same arrays.
+struct irs_look_rows {
+    int64_t *seq;    // [N][L] child windows
+    int64_t *user;   // [N] the parent's user (0 without one)
+    int64_t *tgt0;   // [N] the parent's target as a 0-based id (t - 1): the inner gather's id list
+    int64_t *ids0;   // [N] candidate ids, 0-based, -1: no candidate
+    int32_t *hep;    // [N]
+    float *x;        // [N][d] the children's decoded rows
+    float *mx, *sm, *ts; // [N] max, sum exp(e - max), the target's score on the child row
+    float *val;      // [N] the candidates' scores in the parent's list
+    float *lp;       // [N] what the choose step compared
+    int32_t *choice; // [rows] the chosen slot, -1: none
+};
+static inline size_t irs_look_layout(void *base, int rows, int k_c, int L, int d, irs_look_rows *o) {
+    auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+    const size_t N = (size_t)rows * k_c;
+    const size_t n_seq = up(N * L * 8), r8 = up(N * 8), r4 = up(N * 4), n_x = up(N * d * 4), c4 = up((size_t)rows * 4);
+    if (o) {
+        char *p = (char *)base;
+        o->seq = (int64_t *)p, p += n_seq;
+        o->user = (int64_t *)p, p += r8;
+        o->tgt0 = (int64_t *)p, p += r8;
+        o->ids0 = (int64_t *)p, p += r8;
+        o->hep = (int32_t *)p, p += r4;
+        o->x = (float *)p, p += n_x;
+        o->mx = (float *)p, p += r4;
+        o->sm = (float *)p, p += r4;
+        o->ts = (float *)p, p += r4;
+        o->val = (float *)p, p += r4;
+        o->lp = (float *)p, p += r4;
+        o->choice = (int32_t *)p;
+    }
+    return n_seq + 3 * r8 + 7 * r4 + n_x + c4;
+}
+struct irs_look_expand_args { // irs_lookahead_expand's arguments as the kernel takes them
+    const int64_t *seq;  // [M][L] parent windows
+    const int32_t *hep;  // [M]
+    const int64_t *user; // [M] or null
+    int M, L, k, k_c;
+    const float *val;    // [M][k] the parents' ranked lists
+    const int64_t *ids0; // [M][k]
+    const int32_t *fin;  // [M] or null: != 0 expands to no candidate
+    const int32_t *step_ptr; // device step counter, or step_arg
+    int step_arg;
+    irs_excl ex;         // bound exclusions (zero: none)
+    int64_t *c_seq, *c_user, *c_tgt0, *c_ids0;
+    int32_t *c_hep;
+    float *c_val;
+};
+struct irs_look_choose_args { // irs_lookahead_choose's arguments as the kernel takes them
+    const int64_t *seq;  // [M][L] parent windows (the target in slot L - 1)
+    int M, L, k, k_c;
+    const int64_t *c_ids0; // [M][k_c]
+    const float *c_val, *mx, *sm, *ts; // [M][k_c]
+    const int32_t *fin;  // [M] or null: != 0 leaves the list alone
+    float *val;          // [M][k] in / out
+    int64_t *ids0;       // [M][k] in / out
+    float *lp;           // [M][k_c]
+    int32_t *choice;     // [M]
+    int32_t *rec_item;   // [users][ld][k_c] or null
+    float *rec_lp;       // [users][ld][k_c] or null
+    int rec_ld;
+    const int32_t *rec_map, *rec_step; // row -> the caller's row (null: the identity); the device step counter
 };
 struct irs_eval_batch_args { // irs_build_eval_batch's arguments as the kernel takes them
     const int64_t *items, *offsets;
@@ -297,6 +365,13 @@ struct irs_ctx {
     // the one nearest to the target in the bound feature table; the beam and the sharded entry points then refuse
     int guide_on;
     irs_guide guide;
+
+    // bound lookahead (irs_bind_lookahead): the model-based choice of the greedy loops -- among the first k_c admissible candidates,
+    // the one under which the target's next-step log-probability is highest; the beam and the sharded entry points then refuse
+    int look_on, look_kc, look_users, look_ld;
+    void *look_scratch;
+    int32_t *look_rec_item; // [look_users][look_ld][look_kc] or null
+    float *look_rec_lp;
 
     // arrival rule (irs_set_arrival_rule): between the trace sweep and the path step, a live row whose target stands at rank
     // <= arr_rank (0: clause off) or at log-probability >= arr_lp (arr_lp_on) is offered the target alone; needs a bound trace
@@ -475,6 +550,10 @@ int irs_launch_guide_pack(irs_ctx *ctx, const uint8_t *table, int64_t rows, int 
 // the path step while a guide is bound (irs_launch_path_step chooses it)
 int irs_launch_path_step_guided(irs_ctx *ctx, const irs_path_args &pa, int B, const float *val, const int64_t *ids0, int k,
                                 hipStream_t s);
+
+// ---- lookahead.hip ---- (the one-step lookahead choice; arguments already validated)
+int irs_launch_lookahead_expand(irs_ctx *ctx, const irs_look_expand_args &a, hipStream_t s);
+int irs_launch_lookahead_choose(irs_ctx *ctx, const irs_look_choose_args &a, hipStream_t s);
 
 // ---- replay.hip ---- (path replay: irs_replay_windows / irs_replay_paths; arguments already validated)
 struct irs_replay_args { // the builder's arguments as the kernel takes them; the rows are [0, R) of row_user / row_step and of the outputs

@@ -93,6 +93,13 @@ class Engine:
         with torch.cuda.device(self.device):
             self._check(fn(self.h, *args, self._stream()))
 
+    def _call_sync(self, fn, *args):
+        """A synchronous entry point that takes no stream (irs_lookahead_expand / irs_lookahead_choose): the work on torch's
+        current stream, which produced the inputs, is drained first; the outputs are complete when the call returns."""
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream(self.device).synchronize()
+            self._check(fn(self.h, *args))
+
     def _inplace(self, t: torch.Tensor, dtype, what: str) -> torch.Tensor:
         """A buffer the library updates in place: it must already be what the kernels assume (a copy would
         silently drop the update)."""
@@ -673,6 +680,107 @@ class Engine:
                     t.record_stream(stream)
             self.unbind_guide()
 
+    # ------------------------------------------------------------------ bound lookahead (irs_bind_lookahead)
+    def lookahead_scratch_bytes(self, rows: int, k_c: int) -> int:
+        n = int(self.lib.irs_lookahead_scratch_bytes(self.h, rows, k_c))
+        if n == 0:
+            raise IrsError(f"lookahead_scratch_bytes: rows={rows} / k_c={k_c} (rows >= 1, k_c in [1, {_lib.IRS_MAX_LOOKAHEAD_KC}])")
+        return n
+
+    def bind_lookahead(self, k_c: int, users: int, ld: int, record: bool = False):
+        """irs_bind_lookahead: until unbind_lookahead a greedy step of generate_paths / generate_paths_until takes, among its
+        first k_c admissible candidates, the one under which the target's log-probability at the NEXT step is highest (one
+        decode of users * k_c child windows and one float32 catalog pass per step); the beam and the sharded loops refuse.
+        record: the loops also write every live row's candidates and values, (items int32 [users, ld, k_c], 1-based, 0 = none;
+        lp float32 [users, ld, k_c]).  Returns (items, lp) or None; the engine holds scratch and record until unbound."""
+        k_c, users, ld = int(k_c), int(users), int(ld)
+        # (an invalid k_c gets the library's message: the scratch is then only a placeholder)
+        ok = 1 <= k_c <= _lib.IRS_MAX_LOOKAHEAD_KC and users >= 1
+        nbytes = self.lookahead_scratch_bytes(users, k_c) if ok else 256
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        rec = None
+        if record and ok and ld >= 1:
+            rec = (torch.zeros((users, ld, k_c), dtype=torch.int32, device=self.device),
+                   torch.zeros((users, ld, k_c), dtype=torch.float32, device=self.device))
+        self._check(self.lib.irs_bind_lookahead(self.h, k_c, _ptr(scratch), scratch.numel(), _ptr(rec[0]) if rec else None,
+                                                _ptr(rec[1]) if rec else None, users, ld))
+        self._lookahead_held = (scratch, rec)
+        return rec
+
+    def unbind_lookahead(self):
+        self._check(self.lib.irs_bind_lookahead(self.h, 0, None, 0, None, None, 0, 0))
+        self._lookahead_held = None
+
+    def lookahead_expand(self, seqs, hep, users, val, ids0, k_c: int, *, fin=None, paths=None, step: int = 0, row_map=None):
+        """irs_lookahead_expand: the kernel alone, synchronously (the current stream is drained first).  Returns (child_seq [M * k_c, L] int64, child_hep [M * k_c] int32, child_user
+        [M * k_c] int64, child_target0 [M * k_c] int64, cand_ids0 [M, k_c] int64, cand_val [M, k_c] float32)."""
+        seqs, hep = self._dev(seqs, torch.int64), self._dev(hep, torch.int32)
+        users = None if users is None else self._dev(users, torch.int64)
+        val, ids0 = self._dev(val, torch.float32), self._dev(ids0, torch.int64)
+        M = seqs.shape[0]
+        if seqs.dim() != 2 or seqs.shape[1] != self.L or val.dim() != 2 or val.shape != ids0.shape or val.shape[0] != M or \
+                hep.numel() != M or (users is not None and users.numel() != M):
+            raise IrsError("lookahead_expand: seqs [M, max_len], val / ids0 [M, k], hep / users [M]")
+        fin = None if fin is None else self._dev(fin, torch.int32)
+        paths = None if paths is None else self._dev(paths, torch.float32)
+        row_map = None if row_map is None else self._dev(row_map, torch.int32)
+        if (fin is not None and fin.numel() != M) or (row_map is not None and row_map.numel() != M) or \
+                (paths is not None and paths.dim() != 2):
+            raise IrsError("lookahead_expand: fin / row_map [M], paths [rows, path_ld]")
+        k_c = int(k_c)
+        n = M * max(k_c, 1)
+        c_seq = torch.empty((n, self.L), dtype=torch.int64, device=self.device)
+        c_hep = torch.empty(n, dtype=torch.int32, device=self.device)
+        c_user = torch.empty(n, dtype=torch.int64, device=self.device)
+        c_tgt = torch.empty(n, dtype=torch.int64, device=self.device)
+        c_ids = torch.empty((M, max(k_c, 1)), dtype=torch.int64, device=self.device)
+        c_val = torch.empty((M, max(k_c, 1)), dtype=torch.float32, device=self.device)
+        self._call_sync(self.lib.irs_lookahead_expand, _ptr(seqs), _ptr(hep), _ptr(users), M, _ptr(val), _ptr(ids0), val.shape[1], k_c,
+                   _ptr(fin), _ptr(paths), paths.shape[1] if paths is not None else 0, step, _ptr(row_map), _ptr(c_seq), _ptr(c_hep),
+                   _ptr(c_user), _ptr(c_tgt), _ptr(c_ids), _ptr(c_val))
+        return c_seq, c_hep, c_user, c_tgt, c_ids, c_val
+
+    def lookahead_choose(self, seqs, cand_ids0, cand_val, mx, sm, ts, val, ids0, *, fin=None):
+        """irs_lookahead_choose: the kernel alone and synchronous like lookahead_expand, on expand's candidates and the children's (max, sumexp, target score), each
+        [M, k_c] (or flat [M * k_c]); val / ids0 are rewritten in place.  Returns (lp [M, k_c] float32, choice [M] int32)."""
+        seqs = self._dev(seqs, torch.int64)
+        cand_ids0, cand_val = self._dev(cand_ids0, torch.int64), self._dev(cand_val, torch.float32)
+        mx, sm, ts = (self._dev(t, torch.float32) for t in (mx, sm, ts))
+        val = self._inplace(val, torch.float32, "lookahead_choose: val")
+        ids0 = self._inplace(ids0, torch.int64, "lookahead_choose: ids0")
+        M = seqs.shape[0]
+        if seqs.dim() != 2 or seqs.shape[1] != self.L or cand_ids0.dim() != 2 or cand_ids0.shape[0] != M or \
+                cand_val.shape != cand_ids0.shape or val.dim() != 2 or val.shape != ids0.shape or val.shape[0] != M or \
+                any(t.numel() != cand_ids0.numel() for t in (mx, sm, ts)):
+            raise IrsError("lookahead_choose: seqs [M, max_len], cand_ids0 / cand_val / mx / sm / ts [M, k_c], val / ids0 [M, k]")
+        fin = None if fin is None else self._dev(fin, torch.int32)
+        if fin is not None and fin.numel() != M:
+            raise IrsError("lookahead_choose: fin [M]")
+        k_c = cand_ids0.shape[1]
+        lp = torch.empty((M, k_c), dtype=torch.float32, device=self.device)
+        choice = torch.empty(M, dtype=torch.int32, device=self.device)
+        self._call_sync(self.lib.irs_lookahead_choose, _ptr(seqs), M, k_c, _ptr(cand_ids0), _ptr(cand_val), _ptr(mx), _ptr(sm), _ptr(ts),
+                   _ptr(fin), _ptr(val), _ptr(ids0), val.shape[1], _ptr(lp), _ptr(choice))
+        return lp, choice
+
+    @contextlib.contextmanager
+    def _lookahead(self, k_c: Optional[int], users: int, ld: int, record: bool = False, graph: bool = False):
+        """While a search call runs with lookahead=k_c: scratch (and record) bound before and unbound after, like _guide (and
+        with its cost: bind and unbind drop the context's captured steps).  Yields the record (items, lp), or None."""
+        if k_c is None:
+            yield None
+            return
+        rec = self.bind_lookahead(k_c, users, ld, record)
+        held = self._lookahead_held
+        try:
+            yield rec
+        finally:
+            stream = torch.cuda.current_stream(self.device)
+            if graph:
+                stream.synchronize()
+            held[0].record_stream(stream)  # (the loops only enqueue: the scratch must outlive the work on the stream)
+            self.unbind_lookahead()
+
     # ------------------------------------------------------------------ arrival rule (irs_set_arrival_rule)
     def set_arrival_rule(self, rank_max: Optional[int] = None, lp_min: Optional[float] = None):
         """irs_set_arrival_rule: until cleared (both None) a live row of the greedy / sampled loops whose target stands at rank
@@ -739,7 +847,7 @@ class Engine:
                        status: Optional[torch.Tensor] = None, exact_candidates: bool = False,
                        exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
                        guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
-                       arrive_lp: Optional[float] = None):
+                       arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False):
         """Runs the whole search loop on the device.  `seqs` and `hep` are the
         working window state and are modified in place.  exact_candidates: a row whose k candidates are hidden by its window
         chooses among the exact best admissible items of the catalog instead (IRS_ROW_RESCUED; the result of k = n_item).
@@ -753,7 +861,11 @@ class Engine:
         its first guide_k admissible candidates, the one nearest to the target seqs[b, L - 1] (the Rec2Inf rule); greedy only.
         arrive_rank / arrive_lp: an arrival rule is set for this call (irs_set_arrival_rule; needs trace=True): a row whose
         target stands at rank <= arrive_rank among what its window leaves, or at log-probability >= arrive_lp, is offered the
-        target at that step (IRS_ROW_OFFERED in its status word); this loop then searches on behind the arrival."""
+        target at that step (IRS_ROW_OFFERED in its status word); this loop then searches on behind the arrival.
+        lookahead (k_c in [1, 32]): a lookahead is bound for this call (irs_bind_lookahead): a step takes, among its first k_c
+        admissible candidates, the one under which the target's next-step log-probability is highest; greedy only, not with
+        guide.  lookahead_record: the return value grows a last member, (items int32 [B, max_path_len, k_c], lp float32 [B,
+        max_path_len, k_c]): every step's candidates (1-based, 0 = none) and the values compared."""
         seqs = self._inplace(seqs, torch.int64, "generate_paths: seqs")
         hep = self._inplace(hep, torch.int32, "generate_paths: hep")
         if users is not None:
@@ -769,13 +881,15 @@ class Engine:
         status = self._inplace(status, torch.int32, "generate_paths: status")
         if paths.shape != (B, max_path_len):
             raise IrsError("generate_paths: paths must be [B, max_path_len]")
-        want = guide_k if guide is not None else (sample_k if sample else 1)
+        want = guide_k if guide is not None else (lookahead if lookahead is not None else (sample_k if sample else 1))
         with self._arrival_rule(arrive_rank, arrive_lp, bool(use_graph)), self._exact_candidates(exact_candidates, B, want, bool(use_graph)), \
                 self._exclusions(exclude, no_repeat, B, bool(use_graph)), self._guide(guide, guide_k, bool(use_graph)), \
+                self._lookahead(lookahead, B, max_path_len, lookahead_record, bool(use_graph)) as looked, \
                 self._path_trace(trace, B, max_path_len, bool(use_graph)) as traced:
             self._call(self.lib.irs_generate_paths, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                     int(sample), sample_k, seed, int(use_graph), _ptr(paths), _ptr(status))
-        return (paths, status, traced) if trace else (paths, status)
+        out = (paths, status, traced) if trace else (paths, status)
+        return out + (looked,) if (lookahead is not None and lookahead_record) else out
 
     def generate_paths_until(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
                              k: int = 100, sweep: int = IRS_SWEEP_BF16, sample=False, sample_k=3, seed=0,
@@ -783,14 +897,15 @@ class Engine:
                              status: Optional[torch.Tensor] = None, exact_candidates: bool = False,
                              exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
                              guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
-                             arrive_lp: Optional[float] = None):
+                             arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False):
         """generate_paths that stops a user at its target (seqs[b, L - 1]) and the call when nobody is left
         (irs_generate_paths_until): returns (paths, status, steps_run, row_steps).  Paths are zero behind the target.
         `seqs` and `hep` are working state: modified, and unspecified afterwards.  One host read of 4 bytes per check.
         trace: as in generate_paths, a fifth member (lp_item, lp_target, rank_target), exactly zero behind a user's arrival.
         guide / guide_k: as in generate_paths -- with the Rec2Inf rule this loop is the reference's get_path.
         arrive_rank / arrive_lp: as in generate_paths (needs trace=True) -- a user is retired at the step that offered it its
-        target, so the search stops as soon as the rule allows."""
+        target, so the search stops as soon as the rule allows.
+        lookahead / lookahead_record: as in generate_paths; the record is the last member, exactly zero behind a user's arrival."""
         seqs = self._inplace(seqs, torch.int64, "generate_paths_until: seqs")
         hep = self._inplace(hep, torch.int32, "generate_paths_until: hep")
         if users is not None:
@@ -807,14 +922,16 @@ class Engine:
         if paths.shape != (B, max_path_len):
             raise IrsError("generate_paths_until: paths must be [B, max_path_len]")
         stats = (ctypes.c_int64 * 2)(0, 0)
-        want = guide_k if guide is not None else (sample_k if sample else 1)
+        want = guide_k if guide is not None else (lookahead if lookahead is not None else (sample_k if sample else 1))
         with self._arrival_rule(arrive_rank, arrive_lp), self._exact_candidates(exact_candidates, B, want), \
-                self._exclusions(exclude, no_repeat, B), \
-                self._guide(guide, guide_k), self._path_trace(trace, B, max_path_len) as traced:
+                self._exclusions(exclude, no_repeat, B), self._guide(guide, guide_k), \
+                self._lookahead(lookahead, B, max_path_len, lookahead_record) as looked, \
+                self._path_trace(trace, B, max_path_len) as traced:
             self._call(self.lib.irs_generate_paths_until, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                           int(sample), sample_k, seed, check_every, _ptr(paths), _ptr(status), stats)
         out = (paths, status, int(stats[0]), int(stats[1]))
-        return out + (traced,) if trace else out
+        out = out + (traced,) if trace else out
+        return out + (looked,) if (lookahead is not None and lookahead_record) else out
 
     # ------------------------------------------------------------------ beam search (build-defined extension)
     def beam_step(self, state_in, val, ids0, lse, step: int, state_out, status):

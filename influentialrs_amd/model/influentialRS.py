@@ -182,10 +182,11 @@ def _takes_exact_candidates(fn):
     disturbed.  The search reads the switch from self._exact_candidates for the time of the call.
     exclude=None and no_repeat=False (bound exclusions) are taken the same way, into self._exclude / self._no_repeat, and
     trace=False (the path trace) into self._trace, guide=None and guide_k=5 (the guided choice) into self._guide / self._guide_k,
-    arrive_rank=None and arrive_lp=None (the arrival rule) into self._arrive_rank / self._arrive_lp."""
+    arrive_rank=None and arrive_lp=None (the arrival rule) into self._arrive_rank / self._arrive_lp, lookahead=None and
+    lookahead_record=False (the lookahead choice) into self._lookahead / self._lookahead_record."""
     @functools.wraps(fn)
     def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None, guide_k=5,
-             arrive_rank=None, arrive_lp=None, **kw):
+             arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, **kw):
         prev = (getattr(self, "_exact_candidates", False), getattr(self, "_exclude", None), getattr(self, "_no_repeat", False),
                 getattr(self, "_trace", False))
         prev_guide = (getattr(self, "_guide", None), getattr(self, "_guide_k", 5))
@@ -193,12 +194,15 @@ def _takes_exact_candidates(fn):
         prev_arrive = (getattr(self, "_arrive_rank", None), getattr(self, "_arrive_lp", None))
         self._guide, self._guide_k = guide, int(guide_k)
         self._arrive_rank, self._arrive_lp = arrive_rank, arrive_lp
+        prev_look = (getattr(self, "_lookahead", None), getattr(self, "_lookahead_record", False))
+        self._lookahead, self._lookahead_record = lookahead, bool(lookahead_record)
         try:
             return fn(self, *args, **kw)
         finally:
             self._exact_candidates, self._exclude, self._no_repeat, self._trace = prev
             self._guide, self._guide_k = prev_guide
             self._arrive_rank, self._arrive_lp = prev_arrive
+            self._lookahead, self._lookahead_record = prev_look
     return call
 
 
@@ -473,7 +477,15 @@ class IRSNN(nn.Module):
         the first step where the target stands at rank <= arrive_rank (>= 1) among what its window leaves, or where the model
         gives it a log-probability >= arrive_lp (<= 0): the step then offers the target itself.  With stop_at_target=True the
         user is retired there.  The keywords imply trace=True: self.last_trace is filled, and its `offered` (bool [B]) says for
-        whom the rule fired.  A target that the window, the exclusion list or (no_repeat) the path hides is never offered."""
+        whom the rule fired.  A target that the window, the exclusion list or (no_repeat) the path hides is never offered.
+        lookahead=None, lookahead_record=False (extension, keyword only, taken the same way; greedy search on one device, off by
+        default): the one-step lookahead choice (irs_bind_lookahead).  lookahead=k_c in [1, 32]: every step decodes, for each
+        of its first k_c admissible top-100 candidates, the window the user would have after accepting it, and offers the
+        candidate under which the model gives the target the highest log-probability at the NEXT step (ties: the better rank;
+        the target itself, once among the candidates, is offered outright).  k_c = 1 is the greedy search.  A step then decodes
+        B (1 + k_c) windows and runs one more float32 catalog pass.  Not with guide, sample=True or beam_width > 1.
+        lookahead_record=True: self.last_lookahead = dict(items int32 [B, max_path_len, k_c] -- each step's candidates, 1-based,
+        0 = none -- and lp float32 [B, max_path_len, k_c], the values compared), cut to 0 after the arrival like last_trace."""
         exact_candidates = getattr(self, "_exact_candidates", False)
         exclude, no_repeat = getattr(self, "_exclude", None), getattr(self, "_no_repeat", False)
         trace = getattr(self, "_trace", False)
@@ -494,6 +506,23 @@ class IRSNN(nn.Module):
             arrive_lp = None if arrive_lp is None else float(arrive_lp)
             trace = True
         arrive = dict(arrive_rank=arrive_rank, arrive_lp=arrive_lp) if (arrive_rank is not None or arrive_lp is not None) else {}
+        lookahead, lookahead_record = getattr(self, "_lookahead", None), getattr(self, "_lookahead_record", False)
+        if lookahead is not None:
+            if isinstance(lookahead, bool) or not isinstance(lookahead, (int, np.integer)) or not 1 <= lookahead <= 32:
+                raise ValueError(f"lookahead={lookahead!r}: an int from 1 to 32, the candidates a step looks ahead from (None: off)")
+            if guide is not None:
+                raise ValueError("lookahead and guide are two rules for the same choice: use one of them")
+            if sample:
+                raise ValueError("lookahead is not built for the sampled search: the choice is deterministic, use sample=False")
+            if beam_width > 1:
+                raise ValueError("lookahead is not built for beam search (beam_width > 1): use beam_width=1 (the lookahead choice "
+                                 "is a rule of the greedy step)")
+            if self.net._hip.world != 1:
+                raise ValueError("lookahead is not built for an item-sharded catalog: irs_bind_lookahead needs the whole catalog "
+                                 "on one device")
+            lookahead = int(lookahead)
+        elif lookahead_record:
+            raise ValueError("lookahead_record=True needs lookahead=k_c")
         if guide is not None:
             if beam_width > 1:
                 raise ValueError("guide is not built for beam search (beam_width > 1): use beam_width=1 (the guided choice is a "
@@ -538,20 +567,23 @@ class IRSNN(nn.Module):
         ids0 = exclusion_ids0(exclude, no_repeat, seqs, L - (gap_len + 1) - 1, dev)
         excl = dict(exclude=ids0, no_repeat=no_repeat) if (ids0 is not None or no_repeat) else {}
         guided = dict(guide=guide, guide_k=guide_k) if guide is not None else {}
+        if lookahead is not None:  # (the children of a step are decoded and scored in one call each: B * k_c sequences and rows)
+            guided = dict(lookahead=lookahead, lookahead_record=lookahead_record)
+        n_eng = B * (lookahead or 1)
         if beam_width > 1:
             paths_t, status = self._beam_paths(work, users, max_path_len, gap_len, beam_width, beam_stop, exact_candidates, excl)
         elif stop_at_target:
             if hip.world != 1:
                 raise ValueError("stop_at_target is not built for an item-sharded catalog: irs_generate_paths_sharded runs "
                                  "every step")
-            eng = hip.get(B, B)
+            eng = hip.get(n_eng, n_eng)
             paths_t, status, _, _, *traced = eng.generate_paths_until(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
                                                                       sample=sample, sample_k=sample_k, seed=seed,
                                                                       check_every=STOP_CHECK_EVERY,
                                                                       exact_candidates=exact_candidates, trace=trace, **excl,
                                                                       **guided, **arrive)
         elif hip.world == 1:
-            eng = hip.get(B, B)
+            eng = hip.get(n_eng, n_eng)
             paths_t, status, *traced = eng.generate_paths(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
                                                           sample=sample, sample_k=sample_k, seed=seed, use_graph=False,
                                                           exact_candidates=exact_candidates, trace=trace, **excl, **guided,
@@ -574,6 +606,14 @@ class IRSNN(nn.Module):
         if trace:
             self.last_trace = path_trace_summary(*(a.detach().cpu().numpy() for a in traced[0]), paths, targets)
             self.last_trace["offered"] = (status & IRS_ROW_OFFERED).ne(0).detach().cpu().numpy()
+        if lookahead is not None and lookahead_record:
+            items, lp = (a.detach().cpu().numpy().copy() for a in traced[-1])
+            for i in range(B):  # (cut after the arrival, like last_trace)
+                pos = get_item_index(paths[i], targets[i])
+                if pos != -1:
+                    items[i, pos + 1:] = 0
+                    lp[i, pos + 1:] = 0
+            self.last_lookahead = dict(items=items, lp=lp)
         histories = seqs[:, :-1].detach().cpu().numpy()
         actual_history = []
         for i in range(B):
