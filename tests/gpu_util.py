@@ -1,4 +1,7 @@
 """Helpers shared by the -m gpu tests: build an Engine from synthetic weights."""
+import contextlib
+import os
+
 import numpy as np
 import torch
 
@@ -7,13 +10,36 @@ from influentialrs_amd.engine import Engine
 from influentialrs_amd._lib import IRS_MASK_CAUSAL, IRS_MASK_IRN
 
 
-def make_engine(cfg, sd_np, *, evaluator=False, max_rows=64, max_seqs=0, rank=0, world=1, max_k=100, device="cuda:0"):
+@contextlib.contextmanager
+def _attn_env(attn):
+    if attn is None:
+        yield
+        return
+    old = os.environ.pop("IRS_ATTN_GEMM", None)
+    try:
+        if attn != "h3":
+            os.environ["IRS_ATTN_GEMM"] = attn
+        yield
+    finally:
+        os.environ.pop("IRS_ATTN_GEMM", None)
+        if old is not None:
+            os.environ["IRS_ATTN_GEMM"] = old
+
+
+def make_engine(cfg, sd_np, *, evaluator=False, max_rows=64, max_seqs=0, rank=0, world=1, max_k=100, device="cuda:0", attn=None,
+                arena_fill=None):
+    """attn: IRS_ATTN_GEMM while the context is created ("f32"; "h3": unset, the default; None: the environment as it is).
+    arena_fill: the derived arena exists before the first finalisation, every byte = arena_fill (otherwise finalize() allocates
+    it uninitialised)."""
     dev = torch.device(device)
-    eng = Engine(n_item=cfg.n_item, n_user=(0 if evaluator else cfg.n_user), d=cfg.emb_dim, max_len=cfg.max_len,
-                 n_heads=cfg.n_heads, ffn_dim=cfg.ffn_dim, n_layers=cfg.n_layers,
-                 u_dim=(0 if evaluator else cfg.u_emb_dim),
-                 mask_mode=(IRS_MASK_CAUSAL if evaluator else IRS_MASK_IRN), device=dev, max_rows=max_rows,
-                 max_seqs=max_seqs, max_k=max_k, rank=rank, world=world)
+    with _attn_env(attn):
+        eng = Engine(n_item=cfg.n_item, n_user=(0 if evaluator else cfg.n_user), d=cfg.emb_dim, max_len=cfg.max_len,
+                     n_heads=cfg.n_heads, ffn_dim=cfg.ffn_dim, n_layers=cfg.n_layers,
+                     u_dim=(0 if evaluator else cfg.u_emb_dim),
+                     mask_mode=(IRS_MASK_CAUSAL if evaluator else IRS_MASK_IRN), device=dev, max_rows=max_rows,
+                     max_seqs=max_seqs, max_k=max_k, rank=rank, world=world)
+    if arena_fill is not None:
+        eng._arena = torch.full((int(eng.lib.irs_derived_bytes(eng.h)) + 256,), arena_fill, dtype=torch.uint8, device=dev)
     # (a value may already be a tensor on the device: upload_state_dict's, shared by many engines)
     sd = {k: (v if torch.is_tensor(v) else torch.from_numpy(v)).to(dev) for k, v in sd_np.items()}
     eng.bind_state_dict(sd)
