@@ -626,21 +626,162 @@ extern "C" int irs_build_eval_batch(irs_ctx *ctx, const int64_t *items, const in
 static irs_excl excl_args(const irs_ctx *ctx, int div, const int32_t *map, const float *paths, int path_ld, int path_by_user,
                           const int32_t *step_ptr, int step_arg) {
     irs_excl e = {};
-    if (!ctx->excl_on) return e;
-    e.rows = ctx->excl_rows, e.cnt = ctx->excl_cnt, e.stride = ctx->excl_stride;
+    const auto &x = ctx->opt.excl;
+    if (!x.on) return e;
+    e.rows = x.rows, e.cnt = x.cnt, e.stride = x.stride;
     e.map = map, e.div = div;
-    if (ctx->excl_no_repeat) e.paths = paths, e.path_ld = path_ld, e.path_by_user = path_by_user, e.step_ptr = step_ptr, e.step_arg = step_arg;
+    if (x.no_repeat) e.paths = paths, e.path_ld = path_ld, e.path_by_user = path_by_user, e.step_ptr = step_ptr, e.step_arg = step_arg;
     e.on = 1;
     return e;
 }
-// the call's users fit the binding; under no_repeat a wave holds the path in one entry per lane
+
+// every change of a search option comes here: a captured step holds the kernels and the pointers of the options bound when it
+// was captured, or lacks them (irs_internal.h: irs_step_key)
+static void opts_changed(irs_ctx *ctx) { irs_drop_graphs(ctx); }
+
+// a caller's scratch: large enough, and aligned for the 16-byte accesses of the kernels that use it
+static int check_scratch(irs_ctx *ctx, const char *fn, const void *scratch, size_t bytes, size_t need) {
+    if (!scratch || bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "%s: scratch too small: %zu < %zu", fn, scratch ? bytes : (size_t)0, need);
+    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "%s: scratch must be 16-byte aligned", fn);
+    return IRS_OK;
+}
+
+// ------------------------------------------------------------------ which entry point admits which search option
+// A search call as the rules see it.  W == 0: a greedy call over B rows; else B * W beam rows.  P: the path length (the steps:
+// the step index).  ptrs_ok: none of a loop's required pointers is null
+struct search_call {
+    int B, W, P, k, sweep, sample, sample_k;
+    bool ptrs_ok;
+};
+
+// ---- an option's argument checks, where an entry point admits it
+// exclusions: the call's users fit the binding; under no_repeat a wave holds the path in one entry per lane
 static int check_excl(irs_ctx *ctx, const char *fn, int users, int path_len) {
-    if (!ctx->excl_on) return IRS_OK;
-    if (users > ctx->excl_users) IRS_FAIL(ctx, IRS_E_INVALID, "%s: %d users, exclusions are bound for %d", fn, users, ctx->excl_users);
-    if (ctx->excl_no_repeat && path_len > IRS_MAX_PATH)
+    const auto &x = ctx->opt.excl;
+    if (!x.on) return IRS_OK;
+    if (users > x.users) IRS_FAIL(ctx, IRS_E_INVALID, "%s: %d users, exclusions are bound for %d", fn, users, x.users);
+    if (x.no_repeat && path_len > IRS_MAX_PATH)
         IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: no_repeat is bound: path length %d > %d", fn, path_len, IRS_MAX_PATH);
     return IRS_OK;
 }
+static int args_excl(irs_ctx *ctx, const char *fn, const search_call &c) { return check_excl(ctx, fn, c.B, c.P); }
+// exact candidates: the bound scratch must serve this call's rows
+static int args_surv(irs_ctx *ctx, const char *fn, const search_call &c) {
+    const int rows = c.W ? c.B * c.W : c.B, want = irs_opt_choices(ctx->opt, c.W, c.sample, c.sample_k);
+    if (want > c.k) IRS_FAIL(ctx, IRS_E_INVALID, "%s: exact candidates need k >= %d", fn, want);
+    const size_t need = irs_surv_scratch(ctx, rows, want);
+    if (ctx->opt.surv.bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bound survivor scratch too small: %zu < %zu", fn, ctx->opt.surv.bytes, need);
+    ctx->surv_rows = rows;
+    return IRS_OK;
+}
+static int args_trace(irs_ctx *ctx, const char *fn, const search_call &c) {
+    const auto &t = ctx->opt.trace;
+    if (c.B > t.users || c.P > t.ld)
+        IRS_FAIL(ctx, IRS_E_INVALID, "%s: B=%d / path length %d, the path trace is bound for [%d, %d]", fn, c.B, c.P, t.users, t.ld);
+    return IRS_OK;
+}
+// a guide: the rule is deterministic, and it chooses among k_c candidates of the list
+static int args_guide(irs_ctx *ctx, const char *fn, const search_call &c) {
+    const int kc = ctx->opt.guide.g.k_c;
+    if (c.sample) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a guide is bound (irs_bind_guide): the guided choice is deterministic, sample must be 0", fn);
+    if (c.k < kc) IRS_FAIL(ctx, IRS_E_INVALID, "%s: a guide is bound (irs_bind_guide): k=%d < k_c=%d", fn, c.k, kc);
+    return IRS_OK;
+}
+// a lookahead: the rule is deterministic, it chooses among k_c candidates of the list, and its B * k_c children are decoded and
+// scored in one call each
+static int args_look(irs_ctx *ctx, const char *fn, const search_call &c) {
+    const auto &l = ctx->opt.look;
+    if (c.sample) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a lookahead is bound (irs_bind_lookahead): the choice is deterministic, sample must be 0", fn);
+    if (c.k < l.kc) IRS_FAIL(ctx, IRS_E_INVALID, "%s: a lookahead is bound (irs_bind_lookahead): k=%d < k_c=%d", fn, c.k, l.kc);
+    if (c.B > l.users) IRS_FAIL(ctx, IRS_E_INVALID, "%s: B=%d, the lookahead is bound for %d users", fn, c.B, l.users);
+    if (l.rec_item && c.P > l.ld)
+        IRS_FAIL(ctx, IRS_E_INVALID, "%s: path length %d, the lookahead record is bound for %d steps", fn, c.P, l.ld);
+    if ((int64_t)c.B * l.kc > ctx->max_seqs || (int64_t)c.B * l.kc > ctx->max_rows)
+        IRS_FAIL(ctx, IRS_E_INVALID, "%s: a lookahead is bound (irs_bind_lookahead): B*k_c=%lld exceeds max_seqs=%d / max_rows=%d", fn,
+                 (long long)c.B * l.kc, ctx->max_seqs, ctx->max_rows);
+    return IRS_OK;
+}
+// an arrival rule reads what the trace sweep leaves in the bound scratch
+static int args_arrive(irs_ctx *ctx, const char *fn, const search_call &) {
+    if (!ctx->opt.trace.on)
+        IRS_FAIL(ctx, IRS_E_STATE, "%s: an arrival rule is set (irs_set_arrival_rule) and no path trace is bound (irs_bind_path_trace): "
+                                   "the rule reads what the trace records", fn);
+    return IRS_OK;
+}
+
+// ---- the options, one row each.  greedy: its argument checks where a greedy entry point looks at it.  beam: why the beam entry
+// points refuse it ("<fn>: <what>: <beam>"); null: they admit it, with the same argument checks.  sharded: the sharded loops'
+// refusal, which every option has (a shard sees its own items only; most bindings refuse a sharded context themselves, so a
+// binding cannot exist there, and must not be ignored if it does)
+enum { OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_N };
+static const struct {
+    bool (*on)(const irs_search_opts &);
+    int (*args)(irs_ctx *, const char *, const search_call &);
+    const char *what, *beam, *sharded;
+} OPTS[OPT_N] = {
+    {[](const irs_search_opts &o) { return o.surv.scratch != nullptr; }, args_surv, nullptr, nullptr,
+     "%s: exact candidates (irs_bind_survivor_scratch) need the whole catalog on one device"},
+    {[](const irs_search_opts &o) { return o.excl.on != 0; }, args_excl, nullptr, nullptr,
+     "%s: bound exclusions (irs_bind_exclusions) need the whole catalog on one device"},
+    {[](const irs_search_opts &o) { return o.trace.on != 0; }, args_trace, "a path trace is bound (irs_bind_path_trace)",
+     "greedy and sampled loops only", "%s: a bound path trace (irs_bind_path_trace) needs the whole catalog on one device"},
+    {[](const irs_search_opts &o) { return o.guide.on != 0; }, args_guide, "a guide is bound (irs_bind_guide)", "greedy loops only",
+     "%s: a bound guide (irs_bind_guide) needs the whole catalog on one device"},
+    {[](const irs_search_opts &o) { return o.look.on != 0; }, args_look, "a lookahead is bound (irs_bind_lookahead)", "greedy loops only",
+     "%s: a bound lookahead (irs_bind_lookahead) needs the whole catalog on one device"},
+    {[](const irs_search_opts &o) { return o.arrive.on != 0; }, args_arrive, "an arrival rule is set (irs_set_arrival_rule)",
+     "greedy and sampled loops only", "%s: an arrival rule (irs_set_arrival_rule) is for the single-device greedy and sampled loops"},
+};
+
+// ---- the entry points, one row each: what it checks, in its order -- the first failing check decides the code and the message.
+// The orders differ, and an option that a row does not name is not looked at there; both are behaviour (tests/
+// test_search_options_host.py holds every answer).  The loops' rows also hold their common checks: readiness, the whole catalog on
+// one device, the call's shape, k.
+enum { AT_GREEDY_LOOP, AT_PATH_STEP, AT_BEAM_STEP, AT_BEAM_LOOP, AT_SHARDED_LOOP };
+enum { DO_READY = OPT_N, DO_WORLD, DO_SHAPE, DO_K, DO_END };
+static const int PLAN[][12] = {
+    /* AT_GREEDY_LOOP  */ {OPT_ARRIVE, OPT_GUIDE, OPT_LOOK, DO_READY, DO_WORLD, DO_SHAPE, OPT_TRACE, DO_K, OPT_EXCL, OPT_SURV, DO_END},
+    /* AT_PATH_STEP    */ {OPT_EXCL, OPT_GUIDE, DO_END},
+    /* AT_BEAM_STEP    */ {OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
+    /* AT_BEAM_LOOP    */ {OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, DO_READY, DO_WORLD, OPT_TRACE, DO_SHAPE, DO_K, OPT_EXCL, OPT_SURV, DO_END},
+    /* AT_SHARDED_LOOP */ {OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, DO_END},
+};
+static int search_rules(irs_ctx *ctx, const char *fn, int at, const search_call &c) {
+    const bool beam = at == AT_BEAM_STEP || at == AT_BEAM_LOOP;
+    int rc;
+    for (const int *p = PLAN[at]; *p != DO_END; ++p) {
+        switch (*p) {
+        case DO_READY:
+            if ((rc = irs_ready_filter(ctx, c.sweep))) return rc;
+            break;
+        case DO_WORLD:
+            if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s needs the whole catalog on one device", fn);
+            break;
+        case DO_SHAPE:
+            if (beam) {
+                if ((rc = irs_check_beam_args(ctx, fn, c.ptrs_ok, c.B, c.W, c.P))) return rc;
+                if ((int64_t)c.B * c.W > ctx->max_seqs || (int64_t)c.B * c.W > ctx->max_rows)
+                    IRS_FAIL(ctx, IRS_E_INVALID, "%s: B*W=%d exceeds max_seqs=%d / max_rows=%d", fn, c.B * c.W, ctx->max_seqs, ctx->max_rows);
+            } else {
+                if (!c.ptrs_ok || c.B < 1 || c.P < 1) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad arguments", fn);
+                if (c.B > ctx->max_seqs || c.B > ctx->max_rows) IRS_FAIL(ctx, IRS_E_INVALID, "%s: B too large", fn);
+            }
+            break;
+        case DO_K:
+            if ((rc = irs_check_k(ctx, fn, c.k, 1, c.sweep, c.sample, c.sample_k))) return rc;
+            break;
+        default: {
+            const auto &o = OPTS[*p];
+            if (!o.on(ctx->opt)) break;
+            if (at == AT_SHARDED_LOOP) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, o.sharded, fn);
+            if (beam && o.beam) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: %s: %s", fn, o.what, o.beam);
+            if ((rc = o.args(ctx, fn, c))) return rc;
+        }
+        }
+    }
+    return IRS_OK;
+}
+int irs_sharded_option_rules(irs_ctx *ctx, const char *fn) { return search_rules(ctx, fn, AT_SHARDED_LOOP, search_call{}); }
 
 extern "C" size_t irs_exclusion_scratch_bytes(const irs_ctx *ctx, int32_t users, int32_t n_excl) {
     if (!ctx || users < 1 || n_excl < 0 || n_excl > IRS_MAX_EXCL) return 0;
@@ -651,8 +792,8 @@ extern "C" int irs_bind_exclusions(irs_ctx *ctx, const int64_t *excl_ids0, int32
                                    void *scratch, size_t bytes, void *stream) {
     if (!ctx) return IRS_E_INVALID;
     if (!excl_ids0 && users == 0 && n_excl == 0 && !no_repeat && !scratch && bytes == 0) { // unbind
-        if (ctx->excl_on) irs_drop_graphs(ctx);
-        ctx->excl_on = 0, ctx->excl_rows = nullptr, ctx->excl_cnt = nullptr, ctx->excl_users = ctx->excl_stride = ctx->excl_no_repeat = 0;
+        if (ctx->opt.excl.on) opts_changed(ctx);
+        ctx->opt.excl = {};
         return IRS_OK;
     }
     if (n_excl < 0) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_exclusions: n_excl must be >= 0");
@@ -661,13 +802,11 @@ extern "C" int irs_bind_exclusions(irs_ctx *ctx, const int64_t *excl_ids0, int32
     if (users < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_exclusions: users must be >= 1");
     if ((excl_ids0 == nullptr) != (n_excl == 0)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_exclusions: a list and n_excl >= 1 go together");
     if (n_excl == 0 && !no_repeat) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_exclusions: neither a list nor no_repeat");
-    const size_t need = irs_excl_scratch(users, n_excl);
-    if (!scratch || bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_exclusions: scratch too small: %zu < %zu", scratch ? bytes : (size_t)0, need);
-    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_exclusions: scratch must be 16-byte aligned");
-    const int rc = irs_launch_excl_prepare(ctx, excl_ids0, users, n_excl, scratch, (hipStream_t)stream);
+    int rc = check_scratch(ctx, "irs_bind_exclusions", scratch, bytes, irs_excl_scratch(users, n_excl));
     if (rc) return rc;
-    ctx->excl_on = 1, ctx->excl_users = users, ctx->excl_no_repeat = no_repeat ? 1 : 0;
-    irs_drop_graphs(ctx); // (a captured step holds the binding's pointers, or none)
+    if ((rc = irs_launch_excl_prepare(ctx, excl_ids0, users, n_excl, scratch, (hipStream_t)stream))) return rc;
+    ctx->opt.excl.on = 1, ctx->opt.excl.users = users, ctx->opt.excl.no_repeat = no_repeat ? 1 : 0;
+    opts_changed(ctx);
     return IRS_OK;
 }
 
@@ -681,8 +820,8 @@ extern "C" int irs_bind_guide(irs_ctx *ctx, int32_t kind, const void *table, int
                               void *stream) {
     if (!ctx) return IRS_E_INVALID;
     if (!table) { // unbind
-        if (ctx->guide_on) irs_drop_graphs(ctx);
-        ctx->guide_on = 0, ctx->guide = irs_guide{};
+        if (ctx->opt.guide.on) opts_changed(ctx);
+        ctx->opt.guide = {};
         return IRS_OK;
     }
     if (kind != IRS_GUIDE_BINARY && kind != IRS_GUIDE_FLOAT)
@@ -693,34 +832,20 @@ extern "C" int irs_bind_guide(irs_ctx *ctx, int32_t kind, const void *table, int
     const int f_max = kind == IRS_GUIDE_BINARY ? IRS_MAX_GUIDE_BITS : IRS_MAX_GUIDE_FLOATS;
     if (F > f_max) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide: F %d > %d (%s)", F, f_max, kind == IRS_GUIDE_BINARY ? "bits" : "floats");
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide needs the whole catalog on one device");
-    if (ctx->look_on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide: a lookahead is bound (irs_bind_lookahead): one choice rule at a time");
+    if (ctx->opt.look.on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide: a lookahead is bound (irs_bind_lookahead): one choice rule at a time");
     if (k_c > ctx->dims.max_k) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_guide: k_c %d > max_k %d", k_c, ctx->dims.max_k);
     const int64_t rows = ctx->dims.n_item + 1;
     irs_guide g{table, rows, F, 0, k_c, kind};
     if (kind == IRS_GUIDE_BINARY) {
-        const size_t need = irs_guide_scratch(ctx->dims.n_item, kind, F);
-        if (!scratch || bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_guide: scratch too small: %zu < %zu", scratch ? bytes : (size_t)0, need);
-        if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_guide: scratch must be 16-byte aligned");
-        g.words = (F + 31) / 32, g.table = scratch;
-        const int rc = irs_launch_guide_pack(ctx, (const uint8_t *)table, rows, F, (uint32_t *)scratch, (hipStream_t)stream);
+        int rc = check_scratch(ctx, "irs_bind_guide", scratch, bytes, irs_guide_scratch(ctx->dims.n_item, kind, F));
         if (rc) return rc;
+        g.words = (F + 31) / 32, g.table = scratch;
+        if ((rc = irs_launch_guide_pack(ctx, (const uint8_t *)table, rows, F, (uint32_t *)scratch, (hipStream_t)stream))) return rc;
     } else if (((uintptr_t)table) & 3) {
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_guide: a float table must be 4-byte aligned");
     }
-    ctx->guide = g, ctx->guide_on = 1;
-    irs_drop_graphs(ctx); // (a captured step holds the guided kernel with this table, or the plain one)
-    return IRS_OK;
-}
-// the greedy entry points while a guide is bound: the rule is deterministic, and it chooses among k_c candidates of the list
-static int check_guide(irs_ctx *ctx, const char *fn, int k, int sample) {
-    if (!ctx->guide_on) return IRS_OK;
-    if (sample) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a guide is bound (irs_bind_guide): the guided choice is deterministic, sample must be 0", fn);
-    if (k < ctx->guide.k_c) IRS_FAIL(ctx, IRS_E_INVALID, "%s: a guide is bound (irs_bind_guide): k=%d < k_c=%d", fn, k, ctx->guide.k_c);
-    return IRS_OK;
-}
-// the beam steps and loops have no guided form: they refuse while a guide is bound
-static int refuse_guide(irs_ctx *ctx, const char *fn) {
-    if (ctx->guide_on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a guide is bound (irs_bind_guide): greedy loops only", fn);
+    ctx->opt.guide.g = g, ctx->opt.guide.on = 1;
+    opts_changed(ctx);
     return IRS_OK;
 }
 
@@ -734,42 +859,19 @@ extern "C" int irs_bind_lookahead(irs_ctx *ctx, int32_t k_c, void *scratch, size
                                   int32_t users, int32_t ld) {
     if (!ctx) return IRS_E_INVALID;
     if (k_c == 0) { // unbind
-        if (ctx->look_on) irs_drop_graphs(ctx);
-        ctx->look_on = ctx->look_kc = ctx->look_users = ctx->look_ld = 0;
-        ctx->look_scratch = nullptr, ctx->look_rec_item = nullptr, ctx->look_rec_lp = nullptr;
+        if (ctx->opt.look.on) opts_changed(ctx);
+        ctx->opt.look = {};
         return IRS_OK;
     }
     if (k_c < 0 || k_c > IRS_MAX_LOOKAHEAD_KC) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_lookahead: k_c %d outside [0, %d]", k_c, IRS_MAX_LOOKAHEAD_KC);
     if (users < 1 || ld < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_lookahead: users >= 1 and ld >= 1");
     if ((rec_item == nullptr) != (rec_lp == nullptr)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_lookahead: the two record arrays go together");
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_lookahead needs the whole catalog on one device");
-    if (ctx->guide_on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_lookahead: a guide is bound (irs_bind_guide): one choice rule at a time");
-    const size_t need = irs_look_layout(nullptr, users, k_c, ctx->dims.max_len, ctx->dims.d, nullptr);
-    if (!scratch || bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_lookahead: scratch too small: %zu < %zu", scratch ? bytes : (size_t)0, need);
-    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_lookahead: scratch must be 16-byte aligned");
-    ctx->look_on = 1, ctx->look_kc = k_c, ctx->look_users = users, ctx->look_ld = ld;
-    ctx->look_scratch = scratch, ctx->look_rec_item = rec_item, ctx->look_rec_lp = rec_lp;
-    irs_drop_graphs(ctx); // (a captured step holds the two kernels and the inner decode with these pointers, or none of them)
-    return IRS_OK;
-}
-// the greedy loops while a lookahead is bound: the rule is deterministic, it chooses among k_c candidates of the list, and its
-// B * k_c children are decoded and scored in one call each
-static int check_lookahead(irs_ctx *ctx, const char *fn, int B, int P, int k, int sample) {
-    if (!ctx->look_on) return IRS_OK;
-    const int kc = ctx->look_kc;
-    if (sample) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a lookahead is bound (irs_bind_lookahead): the choice is deterministic, sample must be 0", fn);
-    if (k < kc) IRS_FAIL(ctx, IRS_E_INVALID, "%s: a lookahead is bound (irs_bind_lookahead): k=%d < k_c=%d", fn, k, kc);
-    if (B > ctx->look_users) IRS_FAIL(ctx, IRS_E_INVALID, "%s: B=%d, the lookahead is bound for %d users", fn, B, ctx->look_users);
-    if (ctx->look_rec_item && P > ctx->look_ld)
-        IRS_FAIL(ctx, IRS_E_INVALID, "%s: path length %d, the lookahead record is bound for %d steps", fn, P, ctx->look_ld);
-    if ((int64_t)B * kc > ctx->max_seqs || (int64_t)B * kc > ctx->max_rows)
-        IRS_FAIL(ctx, IRS_E_INVALID, "%s: a lookahead is bound (irs_bind_lookahead): B*k_c=%lld exceeds max_seqs=%d / max_rows=%d", fn,
-                 (long long)B * kc, ctx->max_seqs, ctx->max_rows);
-    return IRS_OK;
-}
-// the beam steps and loops have no lookahead form: they refuse while one is bound
-static int refuse_lookahead(irs_ctx *ctx, const char *fn) {
-    if (ctx->look_on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a lookahead is bound (irs_bind_lookahead): greedy loops only", fn);
+    if (ctx->opt.guide.on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_lookahead: a guide is bound (irs_bind_guide): one choice rule at a time");
+    const int rc = check_scratch(ctx, "irs_bind_lookahead", scratch, bytes, irs_look_layout(nullptr, users, k_c, ctx->dims.max_len, ctx->dims.d, nullptr));
+    if (rc) return rc;
+    ctx->opt.look = {1, k_c, users, ld, scratch, rec_item, rec_lp};
+    opts_changed(ctx);
     return IRS_OK;
 }
 
@@ -802,7 +904,7 @@ extern "C" int irs_lookahead_expand(irs_ctx *ctx, const int64_t *seq, const int3
     if (ctx->dims.mask_mode == IRS_MASK_IRN && !user) IRS_FAIL(ctx, IRS_E_INVALID, "irs_lookahead_expand: user is null");
     if (step < 0 || (paths && (path_ld < 1 || step > path_ld)))
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_lookahead_expand: step must be in [0, path_ld], path_ld >= 1");
-    if (ctx->excl_on && ctx->excl_no_repeat && !paths) IRS_FAIL(ctx, IRS_E_INVALID, "irs_lookahead_expand: no_repeat is bound: dev_paths is null");
+    if (ctx->opt.excl.on && ctx->opt.excl.no_repeat && !paths) IRS_FAIL(ctx, IRS_E_INVALID, "irs_lookahead_expand: no_repeat is bound: dev_paths is null");
     if ((rc = check_excl(ctx, "irs_lookahead_expand", M, step))) return rc;
     const irs_look_expand_args a{seq, hep, user, M, ctx->dims.max_len, k, k_c, val, ids0, fin, nullptr, step,
                                  excl_args(ctx, 1, row_map, paths, path_ld, 1, nullptr, step),
@@ -830,9 +932,8 @@ extern "C" int irs_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int32_t B
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_path_step: bad arguments");
     if (sample && (sample_k < 1 || sample_k > IRS_MAX_SAMPLE_K))
         IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_path_step: sample_k must be in [1, %d]", IRS_MAX_SAMPLE_K);
-    int rc = check_excl(ctx, "irs_path_step", B, step);
+    const int rc = search_rules(ctx, "irs_path_step", AT_PATH_STEP, search_call{B, 0, step, k, 0, sample, sample_k, true});
     if (rc) return rc;
-    if ((rc = check_guide(ctx, "irs_path_step", k, sample))) return rc;
     const irs_path_args pa{seq, hep, ctx->dims.max_len, paths, path_ld, sample, sample_k, seed, status, nullptr, step, nullptr, 1,
                            excl_args(ctx, 1, nullptr, paths, path_ld, 1, nullptr, step)};
     return irs_launch_path_step(ctx, pa, B, val, ids0, k, (hipStream_t)stream);
@@ -856,28 +957,26 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
     //  bound: only the separate step kernel has the form that tests them; nor while a path trace is bound: its sweep reads the
     //  window before the step, its record kernel the lists after it; nor while a guide is bound: the guided step is a kernel of its own;
     //  nor while a lookahead is bound: its expand, inner decode and choose go between the ranking and the step)
-    if (merged && !ctx->surv_scratch && !ctx->excl_on && !ctx->tr_on && !ctx->guide_on && !ctx->look_on && sweep != IRS_SWEEP_EXHAUSTIVE &&
-        irs_topk_is_direct(ctx, B, k))
+    if (merged && !irs_opt_splits_step(ctx->opt) && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k))
         return irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, &pa);
     if ((rc = irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, nullptr, nullptr, carry)))
         return rc;
-    if (ctx->surv_scratch) {
-        // (a guided step and a lookahead step choose among k_c)
-        const int want = ctx->guide_on ? ctx->guide.k_c : (ctx->look_on ? ctx->look_kc : (pa.sample ? pa.sample_k : 1));
-        const irs_surv_args sa{ctx->xrows, pa.seq, pa.hep, B, 1, k, want, ctx->surv_rows, nullptr, surv_fin, nullptr,
-                               ctx->top_val, ctx->top_ids, pa.status, nullptr, pa.ex};
-        if ((rc = irs_launch_survivors(ctx, sa, ctx->surv_scratch, s))) return rc;
+    const irs_search_opts &o = ctx->opt;
+    if (o.surv.scratch) {
+        const irs_surv_args sa{ctx->xrows, pa.seq, pa.hep, B, 1, k, irs_opt_choices(o, 0, pa.sample, pa.sample_k), ctx->surv_rows, nullptr,
+                               surv_fin, nullptr, ctx->top_val, ctx->top_ids, pa.status, nullptr, pa.ex};
+        if ((rc = irs_launch_survivors(ctx, sa, o.surv.scratch, s))) return rc;
     }
     irs_trace_rows tr = {};
-    if (ctx->tr_on) { // how the target stands before the step chooses: into the scratch, by launch row
-        irs_trace_layout(ctx->tr_scratch, ctx->tr_users, &tr);
+    if (o.trace.on) { // how the target stands before the step chooses: into the scratch, by launch row
+        irs_trace_layout(o.trace.scratch, o.trace.users, &tr);
         if ((rc = irs_launch_target_trace(ctx, ctx->xrows, pa.seq, pa.hep, B, tr, tr.mx, tr.sm, tr.ts, tr.rank, s))) return rc;
     }
-    // arrival rule: a row whose target stands well enough is offered the target alone (the entry points have seen to tr_on)
-    if (ctx->arr_on && (rc = irs_launch_arrival_offer(ctx, pa.seq, pa.hep, B, tr.mx, tr.sm, tr.ts, tr.rank, surv_fin, ctx->top_val,
-                                                      ctx->top_ids, k, ctx->arr_rank, ctx->arr_lp, pa.status, pa.ex, s)))
+    // arrival rule: a row whose target stands well enough is offered the target alone (the entry points have seen to the trace)
+    if (o.arrive.on && (rc = irs_launch_arrival_offer(ctx, pa.seq, pa.hep, B, tr.mx, tr.sm, tr.ts, tr.rank, surv_fin, ctx->top_val,
+                                                      ctx->top_ids, k, o.arrive.rank, o.arrive.lp, pa.status, pa.ex, s)))
         return rc;
-    if (ctx->look_on) {
+    if (o.look.on) {
         // Lookahead choice: expand -> decode of the B * k_c children -> LSE and the target's score on their rows -> choose.
         // The inner decode and the two scoring passes run on the context's workspace in the middle of the step.  What they write
         // there: the decoder's activations (act_*) and plan tables (tok_row, seq_*, m_dev, tile_*, qrow_tile, n_wg_dev), all dead
@@ -888,9 +987,9 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
         // and thr_valid / thr_M / thr_k: irs_launch_topk's alone) and ctx->step_ctr (ctx->step_pair is null here, so the inner
         // plan kernel does not hand the step counter over).  Everything the lookahead itself produces -- child windows, hep,
         // users, targets, the child rows, max / sumexp / target score, candidates, lp, choice -- lies in the caller's scratch.
-        const int kc = ctx->look_kc, N = B * kc;
+        const int kc = o.look.kc, N = B * kc;
         irs_look_rows lk;
-        irs_look_layout(ctx->look_scratch, ctx->look_users, kc, ctx->dims.max_len, ctx->dims.d, &lk);
+        irs_look_layout(o.look.scratch, o.look.users, kc, ctx->dims.max_len, ctx->dims.d, &lk);
         const irs_look_expand_args ea{pa.seq, pa.hep, user, B, ctx->dims.max_len, k, kc, ctx->top_val, ctx->top_ids, surv_fin,
                                       pa.step_ptr, pa.step_arg, pa.ex, lk.seq, lk.user, lk.tgt0, lk.ids0, lk.hep, lk.val};
         if ((rc = irs_launch_lookahead_expand(ctx, ea, s))) return rc;
@@ -898,13 +997,13 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
         if ((rc = irs_launch_lse(ctx, lk.x, N, lk.mx, lk.sm, s))) return rc;
         if ((rc = irs_launch_gather(ctx, lk.x, N, lk.tgt0, 1, lk.ts, s))) return rc;
         const irs_look_choose_args ca{pa.seq, B, ctx->dims.max_len, k, kc, lk.ids0, lk.val, lk.mx, lk.sm, lk.ts, surv_fin, ctx->top_val,
-                                      ctx->top_ids, lk.lp, lk.choice, ctx->look_rec_item, ctx->look_rec_lp, ctx->look_ld, row_map,
+                                      ctx->top_ids, lk.lp, lk.choice, o.look.rec_item, o.look.rec_lp, o.look.ld, row_map,
                                       ctx->step_ctr};
         if ((rc = irs_launch_lookahead_choose(ctx, ca, s))) return rc;
     }
     if ((rc = irs_launch_path_step(ctx, pa, B, ctx->top_val, ctx->top_ids, k, s))) return rc;
-    if (ctx->tr_on) { // (the step index is still this step's: the merged loop publishes the next one in its second word)
-        const irs_trace_rec rec{tr.mx, tr.sm, tr.ts, tr.rank, ctx->tr_item, ctx->tr_target, ctx->tr_rank, ctx->tr_ld};
+    if (o.trace.on) { // (the step index is still this step's: the merged loop publishes the next one in its second word)
+        const irs_trace_rec rec{tr.mx, tr.sm, tr.ts, tr.rank, o.trace.item, o.trace.target, o.trace.rank, o.trace.ld};
         if ((rc = irs_launch_trace_record(ctx, rec, pa.seq, pa.hep, pa.paths, pa.path_ld, ctx->step_ctr, row_map, surv_fin, ctx->top_val,
                                           ctx->top_ids, k, B, s)))
             return rc;
@@ -929,12 +1028,10 @@ extern "C" int irs_topk_ensure_survivors(irs_ctx *ctx, const float *xrows, const
     if (want < 1 || want > k || want > 32) IRS_FAIL(ctx, IRS_E_INVALID, "irs_topk_ensure_survivors: want must be in [1, min(k, 32)]");
     if (rows_per_status < 1 || M % rows_per_status)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_topk_ensure_survivors: rows_per_status must be >= 1 and divide M");
-    if (scratch_bytes < irs_surv_scratch(ctx, M, want))
-        IRS_FAIL(ctx, IRS_E_INVALID, "irs_topk_ensure_survivors: scratch too small: %zu < %zu", scratch_bytes, irs_surv_scratch(ctx, M, want));
-    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_topk_ensure_survivors: scratch must be 16-byte aligned");
-    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_topk_ensure_survivors needs the whole catalog on one device");
-    int rc = check_excl(ctx, "irs_topk_ensure_survivors", M / rows_per_status, 0);
+    int rc = check_scratch(ctx, "irs_topk_ensure_survivors", scratch, scratch_bytes, irs_surv_scratch(ctx, M, want));
     if (rc) return rc;
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_topk_ensure_survivors needs the whole catalog on one device");
+    if ((rc = check_excl(ctx, "irs_topk_ensure_survivors", M / rows_per_status, 0))) return rc;
     if ((rc = ready(ctx))) return rc;
     const irs_surv_args sa{xrows, seq, hep, M, rows_per_status, k, want, M, cum, fin, done, val, ids0, status, nullptr,
                            excl_args(ctx, rows_per_status, nullptr, nullptr, 0, 0, nullptr, 0)}; // (no path argument: the list only)
@@ -945,9 +1042,8 @@ extern "C" int irs_bind_survivor_scratch(irs_ctx *ctx, void *scratch, size_t byt
     if (!ctx) return IRS_E_INVALID;
     if ((scratch == nullptr) != (bytes == 0)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_survivor_scratch: a scratch and its size go together");
     if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_survivor_scratch: scratch must be 16-byte aligned");
-    ctx->surv_scratch = scratch;
-    ctx->surv_bytes = bytes;
-    irs_drop_graphs(ctx); // (a captured step holds or lacks the pass)
+    ctx->opt.surv = {scratch, bytes};
+    opts_changed(ctx);
     return IRS_OK;
 }
 
@@ -964,9 +1060,7 @@ extern "C" int irs_score_target_trace(irs_ctx *ctx, const float *xrows, const in
     if (rc) return rc;
     if ((rc = check_rows(ctx, "irs_score_target_trace", xrows, M))) return rc;
     if (!seq || !hep || !scratch || !omax || !osum || !tscore || !rank) IRS_FAIL(ctx, IRS_E_INVALID, "irs_score_target_trace: null pointer");
-    if (scratch_bytes < irs_trace_layout(nullptr, M, nullptr))
-        IRS_FAIL(ctx, IRS_E_INVALID, "irs_score_target_trace: scratch too small: %zu < %zu", scratch_bytes, irs_trace_layout(nullptr, M, nullptr));
-    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_score_target_trace: scratch must be 16-byte aligned");
+    if ((rc = check_scratch(ctx, "irs_score_target_trace", scratch, scratch_bytes, irs_trace_layout(nullptr, M, nullptr)))) return rc;
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_score_target_trace needs the whole catalog on one device");
     irs_trace_rows tr;
     irs_trace_layout(scratch, M, &tr);
@@ -977,24 +1071,17 @@ extern "C" int irs_bind_path_trace(irs_ctx *ctx, float *lp_item, float *lp_targe
                                    void *scratch, size_t bytes) {
     if (!ctx) return IRS_E_INVALID;
     if (!lp_item && !lp_target && !rank_target) { // unbind
-        if (ctx->tr_on) irs_drop_graphs(ctx);
-        ctx->tr_on = 0, ctx->tr_item = ctx->tr_target = nullptr, ctx->tr_rank = nullptr, ctx->tr_users = ctx->tr_ld = 0, ctx->tr_scratch = nullptr;
+        if (ctx->opt.trace.on) opts_changed(ctx);
+        ctx->opt.trace = {};
         return IRS_OK;
     }
     if (!lp_item || !lp_target || !rank_target) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_path_trace: the three arrays go together");
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_path_trace needs the whole catalog on one device");
     if (users < 1 || users > ctx->max_rows || ld < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_path_trace: users in [1, max_rows=%d], ld >= 1", ctx->max_rows);
-    const size_t need = irs_trace_layout(nullptr, users, nullptr);
-    if (!scratch || bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_path_trace: scratch too small: %zu < %zu", scratch ? bytes : (size_t)0, need);
-    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_path_trace: scratch must be 16-byte aligned");
-    ctx->tr_on = 1, ctx->tr_item = lp_item, ctx->tr_target = lp_target, ctx->tr_rank = rank_target, ctx->tr_users = users, ctx->tr_ld = ld;
-    ctx->tr_scratch = scratch;
-    irs_drop_graphs(ctx); // (a captured step holds the sweep and the record kernel with these pointers, or neither)
-    return IRS_OK;
-}
-// the beam steps and loops carry no trace: they refuse while one is bound
-static int refuse_trace(irs_ctx *ctx, const char *fn) {
-    if (ctx->tr_on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a path trace is bound (irs_bind_path_trace): greedy and sampled loops only", fn);
+    const int rc = check_scratch(ctx, "irs_bind_path_trace", scratch, bytes, irs_trace_layout(nullptr, users, nullptr));
+    if (rc) return rc;
+    ctx->opt.trace = {1, lp_item, lp_target, rank_target, users, ld, scratch};
+    opts_changed(ctx);
     return IRS_OK;
 }
 
@@ -1006,21 +1093,9 @@ extern "C" int irs_set_arrival_rule(irs_ctx *ctx, int32_t rank_max, float lp_min
     const int on = (rank_max >= 1 || lp_on) ? 1 : 0;
     if (on && ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_set_arrival_rule needs the whole catalog on one device");
     const float lp = lp_on ? lp_min : (on ? __builtin_nanf("") : 0.f); // (what the kernel takes: NaN is "clause off")
-    if (on != ctx->arr_on || rank_max != ctx->arr_rank || lp_on != ctx->arr_lp_on || memcmp(&lp, &ctx->arr_lp, sizeof(lp)))
-        irs_drop_graphs(ctx); // (a captured step holds the offer kernel with these two values, or lacks it)
-    ctx->arr_on = on, ctx->arr_rank = on ? rank_max : 0, ctx->arr_lp_on = lp_on, ctx->arr_lp = lp;
-    return IRS_OK;
-}
-// the greedy / sampled loops while a rule is set: the rule reads what the trace sweep leaves in the bound scratch
-static int check_arrival(irs_ctx *ctx, const char *fn) {
-    if (ctx && ctx->arr_on && !ctx->tr_on)
-        IRS_FAIL(ctx, IRS_E_STATE, "%s: an arrival rule is set (irs_set_arrival_rule) and no path trace is bound (irs_bind_path_trace): "
-                                   "the rule reads what the trace records", fn);
-    return IRS_OK;
-}
-// the beam loops have no offer: they refuse while a rule is set (with a trace bound they refuse already)
-static int refuse_arrival(irs_ctx *ctx, const char *fn) {
-    if (ctx->arr_on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: an arrival rule is set (irs_set_arrival_rule): greedy and sampled loops only", fn);
+    auto &a = ctx->opt.arrive;
+    if (on != a.on || rank_max != a.rank || lp_on != a.lp_on || memcmp(&lp, &a.lp, sizeof(lp))) opts_changed(ctx);
+    a = {on, on ? rank_max : 0, lp_on, lp};
     return IRS_OK;
 }
 
@@ -1036,7 +1111,7 @@ extern "C" int irs_arrival_offer(irs_ctx *ctx, const int64_t *seq, const int32_t
     if (rank_max == 0 && !irs_arrival_lp_on(lp_min)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_arrival_offer: both clauses are off");
     if (step < 0 || (paths && (path_ld < 1 || step > path_ld)))
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_arrival_offer: step must be in [0, path_ld], path_ld >= 1");
-    if (ctx->excl_on && ctx->excl_no_repeat && !paths) IRS_FAIL(ctx, IRS_E_INVALID, "irs_arrival_offer: no_repeat is bound: dev_paths is null");
+    if (ctx->opt.excl.on && ctx->opt.excl.no_repeat && !paths) IRS_FAIL(ctx, IRS_E_INVALID, "irs_arrival_offer: no_repeat is bound: dev_paths is null");
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_arrival_offer needs the whole catalog on one device");
     const int rc = check_excl(ctx, "irs_arrival_offer", M, step);
     if (rc) return rc;
@@ -1090,8 +1165,7 @@ extern "C" int irs_replay_paths(irs_ctx *ctx, int32_t layout, const int64_t *seq
     if (chunk < 1 || chunk > replay_chunk_max(ctx))
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_replay_paths: chunk must be in [1, min(max_rows, max_seqs) = %d]", replay_chunk_max(ctx));
     const size_t need = irs_replay_layout(nullptr, chunk, ctx->dims.max_len, ctx->dims.d, nullptr);
-    if (scratch_bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "irs_replay_paths: scratch too small: %zu < %zu", scratch_bytes, need);
-    if (((uintptr_t)scratch) & 15) IRS_FAIL(ctx, IRS_E_INVALID, "irs_replay_paths: scratch must be 16-byte aligned");
+    if ((rc = check_scratch(ctx, "irs_replay_paths", scratch, scratch_bytes, need))) return rc;
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_replay_paths needs the whole catalog on one device");
     if (layout == IRS_REPLAY_FULL && ctx->dims.mask_mode == IRS_MASK_IRN)
         IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_replay_paths: IRS_REPLAY_FULL on an IRS_MASK_IRN context (its mask gives column L-1 a meaning)");
@@ -1158,38 +1232,12 @@ int irs_check_beam_args(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W
     return IRS_OK;
 }
 
-// the common opening of the four single-device search entry points.  W == 0: a greedy loop over B rows; else a beam search over
-// B * W rows.  ptrs_ok: none of the call's required pointers is null
+// the common opening of the four single-device search loops.  W == 0: a greedy loop over B rows; else a beam search over B * W
+// rows.  ptrs_ok: none of the call's required pointers is null.  (A null context has no options: an arrival rule without a trace,
+// the greedy loops' first refusal, is looked at behind it.)
 static int check_search(irs_ctx *ctx, const char *fn, bool ptrs_ok, int B, int W, int P, int k, int sweep, int sample, int sample_k) {
     if (!ctx) return IRS_E_INVALID;
-    // (a bound guide is looked at first, like the bindings at the top of the sharded loops: what it refuses needs no weights)
-    int rc = W ? refuse_guide(ctx, fn) : check_guide(ctx, fn, k, sample);
-    if (rc) return rc;
-    if ((rc = W ? refuse_lookahead(ctx, fn) : check_lookahead(ctx, fn, B, P, k, sample))) return rc;
-    if (W && (rc = refuse_arrival(ctx, fn))) return rc;
-    if ((rc = irs_ready_filter(ctx, sweep))) return rc;
-    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s needs the whole catalog on one device", fn);
-    if (W) {
-        if ((rc = refuse_trace(ctx, fn))) return rc;
-        if ((rc = irs_check_beam_args(ctx, fn, ptrs_ok, B, W, P))) return rc;
-        if ((int64_t)B * W > ctx->max_seqs || (int64_t)B * W > ctx->max_rows)
-            IRS_FAIL(ctx, IRS_E_INVALID, "%s: B*W=%d exceeds max_seqs=%d / max_rows=%d", fn, B * W, ctx->max_seqs, ctx->max_rows);
-    } else {
-        if (!ptrs_ok || B < 1 || P < 1) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad arguments", fn);
-        if (B > ctx->max_seqs || B > ctx->max_rows) IRS_FAIL(ctx, IRS_E_INVALID, "%s: B too large", fn);
-        if (ctx->tr_on && (B > ctx->tr_users || P > ctx->tr_ld))
-            IRS_FAIL(ctx, IRS_E_INVALID, "%s: B=%d / path length %d, the path trace is bound for [%d, %d]", fn, B, P, ctx->tr_users, ctx->tr_ld);
-    }
-    if ((rc = irs_check_k(ctx, fn, k, 1, sweep, sample, sample_k))) return rc;
-    if ((rc = check_excl(ctx, fn, B, P))) return rc;
-    if (ctx->surv_scratch) { // exact candidates: the bound scratch must serve this call's rows
-        const int rows = W ? B * W : B, want = W ? W : (ctx->guide_on ? ctx->guide.k_c : (ctx->look_on ? ctx->look_kc : (sample ? sample_k : 1)));
-        if (want > k) IRS_FAIL(ctx, IRS_E_INVALID, "%s: exact candidates need k >= %d", fn, want);
-        const size_t need = irs_surv_scratch(ctx, rows, want);
-        if (ctx->surv_bytes < need) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bound survivor scratch too small: %zu < %zu", fn, ctx->surv_bytes, need);
-        ctx->surv_rows = rows;
-    }
-    return IRS_OK;
+    return search_rules(ctx, fn, W ? AT_BEAM_LOOP : AT_GREEDY_LOOP, search_call{B, W, P, k, sweep, sample, sample_k, ptrs_ok});
 }
 
 // the path step's arguments inside a search loop: the step index comes from the device counter
@@ -1231,9 +1279,8 @@ int irs_beam_finish(irs_ctx *ctx, size_t rows, int P, float *paths, double *scor
 extern "C" int irs_generate_paths(irs_ctx *ctx, int64_t *seq, const int64_t *user, int32_t *hep, int32_t B,
                                   int32_t max_path_len, int32_t k, int32_t sweep, int32_t sample, int32_t sample_k,
                                   uint64_t seed, int32_t use_graph, float *paths, int32_t *status, void *stream) {
-    int rc = check_arrival(ctx, "irs_generate_paths");
+    int rc = check_search(ctx, "irs_generate_paths", seq && hep && paths && status, B, 0, max_path_len, k, sweep, sample, sample_k);
     if (rc) return rc;
-    if ((rc = check_search(ctx, "irs_generate_paths", seq && hep && paths && status, B, 0, max_path_len, k, sweep, sample, sample_k))) return rc;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
     const irs_path_args pa = loop_path_args(ctx, seq, hep, paths, max_path_len, sample, sample_k, seed, status, paths);
@@ -1242,11 +1289,6 @@ extern "C" int irs_generate_paths(irs_ctx *ctx, int64_t *seq, const int64_t *use
         key.kind = IRS_STEP_GREEDY, key.B = B, key.P = max_path_len, key.k = k, key.sweep = sweep;
         key.sample = sample, key.sample_k = sample_k, key.seed = seed;
         key.seq = seq, key.user = user, key.hep = hep, key.paths = paths, key.status = status;
-        key.tr_item = ctx->tr_item, key.tr_target = ctx->tr_target, key.tr_rank = ctx->tr_rank, key.tr_scratch = ctx->tr_scratch;
-        key.arr_rank = ctx->arr_rank;
-        memcpy(&key.arr_lp_bits, &ctx->arr_lp, sizeof(key.arr_lp_bits));
-        key.look_scratch = ctx->look_scratch, key.look_item = ctx->look_rec_item, key.look_lp = ctx->look_rec_lp;
-        key.look_kc = ctx->look_kc, key.look_ld = ctx->look_ld;
         return irs_replay_steps(ctx, &ctx->g_greedy, key, [&](hipStream_t q) {
             return enqueue_step(ctx, pa, user, B, k, sweep, q);
         }, max_path_len, s);
@@ -1264,9 +1306,8 @@ extern "C" int irs_generate_paths_until(irs_ctx *ctx, int64_t *seq, const int64_
                                         int32_t max_path_len, int32_t k, int32_t sweep, int32_t sample, int32_t sample_k,
                                         uint64_t seed, int32_t check_every, float *paths, int32_t *status, int64_t *host_stats,
                                         void *stream) {
-    int rc = check_arrival(ctx, "irs_generate_paths_until");
+    int rc = check_search(ctx, "irs_generate_paths_until", seq && hep && paths && status, B, 0, max_path_len, k, sweep, sample, sample_k);
     if (rc) return rc;
-    if ((rc = check_search(ctx, "irs_generate_paths_until", seq && hep && paths && status, B, 0, max_path_len, k, sweep, sample, sample_k))) return rc;
     if (check_every < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_generate_paths_until: check_every must be >= 1");
     if (max_path_len > IRS_MAX_PATH)
         IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_generate_paths_until: max_path_len %d > %d", max_path_len, IRS_MAX_PATH);
@@ -1275,17 +1316,7 @@ extern "C" int irs_generate_paths_until(irs_ctx *ctx, int64_t *seq, const int64_
     if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
     IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->un_fin, 0, sizeof(int32_t) * B, s));
     IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->un_status, 0, sizeof(int32_t) * B, s));
-    if (ctx->tr_on) { // the trace of a user ends with its arrival: zero behind it (rows [0, B), all ld columns)
-        const size_t n = (size_t)B * ctx->tr_ld * 4;
-        IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->tr_item, 0, n, s));
-        IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->tr_target, 0, n, s));
-        IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->tr_rank, 0, n, s));
-    }
-    if (ctx->look_on && ctx->look_rec_item) { // the lookahead record of a user ends with its arrival too
-        const size_t n = (size_t)B * ctx->look_ld * ctx->look_kc * 4;
-        IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->look_rec_item, 0, n, s));
-        IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->look_rec_lp, 0, n, s));
-    }
+    if ((rc = irs_opt_zero_records(ctx, B, s))) return rc;
     // the first steps run in place on the caller's rows (identity map); the first compaction that removes a row moves the rest.
     // (the step writes stage[row][i]: it reads the index from the same device counter as irs_generate_paths' steps)
     irs_path_args pa = loop_path_args(ctx, seq, hep, ctx->un_stage, P, sample, sample_k, seed, ctx->un_status, paths);
@@ -1338,11 +1369,8 @@ extern "C" int irs_beam_step(irs_ctx *ctx, const int64_t *seq_in, const int32_t 
         !status || B < 1 || W < 1 || k < 1 || P < 1 || step < 0 || step >= P)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step: bad arguments");
     if (W > 1 && (!lse_max || !lse_sum)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step: W > 1 needs the row log-sum-exp");
-    int rc = refuse_trace(ctx, "irs_beam_step");
+    const int rc = search_rules(ctx, "irs_beam_step", AT_BEAM_STEP, search_call{B, W, P, k, 0, 0, 0, true});
     if (rc) return rc;
-    if ((rc = refuse_guide(ctx, "irs_beam_step"))) return rc;
-    if ((rc = refuse_lookahead(ctx, "irs_beam_step"))) return rc;
-    if ((rc = check_excl(ctx, "irs_beam_step", B, P))) return rc;
     const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k,
                              excl_args(ctx, W, nullptr, paths_in, P, 0, nullptr, step)};
     return irs_launch_beam_step(ctx, beam_state(seq_in, hep_in, cum_in, paths_in, nullptr), {seq_out, hep_out, cum_out, paths_out, nullptr},
@@ -1370,11 +1398,11 @@ static int enqueue_beam_step(irs_ctx *ctx, int in, const int64_t *user, int B, i
         return rc;
     // bound exclusions: a beam row's user through the loop's map, its path so far in the step's input state
     const irs_excl ex = excl_args(ctx, W, until ? until->map : nullptr, ctx->bm[in].paths, P, 0, ctx->step_ctr, 0);
-    if (ctx->surv_scratch) { // exact candidates: a live unfinished beam of a user that is not done sees its best W admissible items
+    if (ctx->opt.surv.scratch) { // exact candidates: a live unfinished beam of a user that is not done sees its best W admissible items
         const irs_surv_args sa{ctx->xrows, ctx->bm[in].seq, ctx->bm[in].hep, rows, W, k, W, ctx->surv_rows, ctx->bm[in].cum,
                                until ? ctx->bm[in].fin : nullptr, until ? until->done : nullptr, ctx->top_val, ctx->top_ids, status,
                                until ? until->map : nullptr, ex};
-        if ((rc = irs_launch_survivors(ctx, sa, ctx->surv_scratch, s))) return rc;
+        if ((rc = irs_launch_survivors(ctx, sa, ctx->opt.surv.scratch, s))) return rc;
     }
     return irs_enqueue_beam_tail(ctx, in, lmax, lsum, B, W, k, P, status, until, s, &ex);
 }
@@ -1418,11 +1446,8 @@ extern "C" int irs_beam_step_until(irs_ctx *ctx, const int64_t *seq_in, const in
     if (W > 1 && (!lse_max || !lse_sum)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_until: W > 1 needs the row log-sum-exp");
     if (stop_rule != IRS_BEAM_STOP_ALL && stop_rule != IRS_BEAM_STOP_BEST)
         IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_until: stop_rule %d (IRS_BEAM_STOP_ALL or IRS_BEAM_STOP_BEST)", stop_rule);
-    int rc = refuse_trace(ctx, "irs_beam_step_until");
+    const int rc = search_rules(ctx, "irs_beam_step_until", AT_BEAM_STEP, search_call{B, W, P, k, 0, 0, 0, true});
     if (rc) return rc;
-    if ((rc = refuse_guide(ctx, "irs_beam_step_until"))) return rc;
-    if ((rc = refuse_lookahead(ctx, "irs_beam_step_until"))) return rc;
-    if ((rc = check_excl(ctx, "irs_beam_step_until", B, P))) return rc;
     const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k,
                              excl_args(ctx, W, nullptr, paths_in, P, 0, nullptr, step)};
     const irs_beam_until until{done, nullptr, stop_rule};

@@ -313,18 +313,7 @@ __global__ void k_short_list(const int64_t *__restrict__ ids0, int k, int n, int
 static int ready_sharded(irs_ctx *ctx, irs_comm *comm, const char *fn, int sweep) {
     int rc = comm_check(ctx, comm, fn);
     if (rc) return rc;
-    if (ctx->surv_scratch) // (a shard could only rescue a starved row against its own items: irs_bind_survivor_scratch)
-        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: exact candidates (irs_bind_survivor_scratch) need the whole catalog on one device", fn);
-    if (ctx->excl_on) // (irs_bind_exclusions refuses a sharded context; a binding cannot exist here, and must not be ignored if it does)
-        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: bound exclusions (irs_bind_exclusions) need the whole catalog on one device", fn);
-    if (ctx->tr_on) // (the trace's sweep and rank need the whole catalog: irs_bind_path_trace)
-        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a bound path trace (irs_bind_path_trace) needs the whole catalog on one device", fn);
-    if (ctx->guide_on) // (irs_bind_guide refuses a sharded context; the guided step exists for the single-device greedy loops only)
-        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a bound guide (irs_bind_guide) needs the whole catalog on one device", fn);
-    if (ctx->look_on) // (irs_bind_lookahead refuses a sharded context; the rule exists for the single-device greedy loops only)
-        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a bound lookahead (irs_bind_lookahead) needs the whole catalog on one device", fn);
-    if (ctx->arr_on) // (the rule reads the trace, which these loops refuse: irs_set_arrival_rule)
-        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: an arrival rule (irs_set_arrival_rule) is for the single-device greedy and sampled loops", fn);
+    if ((rc = irs_sharded_option_rules(ctx, fn))) return rc; // (no search option has a sharded form)
     if ((rc = irs_ready_filter(ctx, sweep))) return rc;
     if (sweep != IRS_SWEEP_BF16 && sweep != IRS_SWEEP_F32) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad sweep", fn);
     return IRS_OK;

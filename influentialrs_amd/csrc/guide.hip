@@ -185,9 +185,9 @@ static auto guided_kernel(bool excl, bool slots_short) {
 int irs_launch_path_step_guided(irs_ctx *ctx, const irs_path_args &pa, int B, const float *val, const int64_t *ids0, int k,
                                 hipStream_t s) {
     const bool s4 = irs_window_slots(ctx) == IRS_WIN_SLOTS_SHORT;
-    const auto kern = ctx->guide.kind == IRS_GUIDE_BINARY ? guided_kernel<IRS_GUIDE_BINARY>(pa.ex.on, s4)
+    const auto kern = ctx->opt.guide.g.kind == IRS_GUIDE_BINARY ? guided_kernel<IRS_GUIDE_BINARY>(pa.ex.on, s4)
                                                           : guided_kernel<IRS_GUIDE_FLOAT>(pa.ex.on, s4);
-    hipLaunchKernelGGL(kern, dim3((B + 3) / 4), dim3(256), 0, s, pa, ctx->guide, B, val, ids0, k);
+    hipLaunchKernelGGL(kern, dim3((B + 3) / 4), dim3(256), 0, s, pa, ctx->opt.guide.g, B, val, ids0, k);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }

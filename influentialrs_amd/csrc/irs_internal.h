@@ -65,20 +65,18 @@ struct irs_prof_ev {
 };
 
 // ---- captured steps.  A search loop captures its step body once as a hipGraph and replays it.  The body bakes in kernel
-// choices, workspace addresses and every argument of the call, so the cache key holds all of them: a loop fills ONE key (fields
-// it does not bake in stay zero) and irs_replay_steps compares it as a whole.
+// choices, workspace addresses, the call's arguments and the search options bound at the time.  The cache key holds the call:
+// its arguments and the caller's pointers -- a loop fills ONE key (fields it does not bake in stay zero) and irs_replay_steps
+// compares it as a whole.  Everything else is covered by the drop: whatever changes a kernel choice, the workspace, the derived
+// weights or a search option (capi.hip: opts_changed) destroys the captured steps (irs_drop_graphs), so a key never meets a step
+// captured under other bindings.
 enum { IRS_STEP_GREEDY = 1, IRS_STEP_BEAM, IRS_STEP_SHARDED_BEAM, IRS_STEP_SHARDED_BEAM_SPLIT };
 struct irs_step_key {
     int32_t kind, B, W, P, k, sweep, sample, sample_k;
     uint64_t seed;
     const void *comm, *seq, *user, *hep, *paths, *status;
-    const void *tr_item, *tr_target, *tr_rank, *tr_scratch; // the bound path trace (irs_bind_path_trace); null: none
-    const void *look_scratch, *look_item, *look_lp; // the bound lookahead (irs_bind_lookahead): scratch and record; null: none
-    int32_t arr_rank;     // the arrival rule (irs_set_arrival_rule): rank_max, 0: clause off
-    uint32_t arr_lp_bits; // the bits of ctx->arr_lp: lp_min, a NaN's while only the rank clause is on, 0 without a rule
-    int32_t look_kc, look_ld; // the bound lookahead's candidate count (0: none) and the record's row stride
 };
-static_assert(sizeof(irs_step_key) == 8 * sizeof(int32_t) + 14 * 8 + 4 * sizeof(int32_t), "irs_step_key is compared with memcmp: no padding");
+static_assert(sizeof(irs_step_key) == 8 * sizeof(int32_t) + 7 * 8, "irs_step_key is compared with memcmp: no padding");
 struct irs_step_graph {
     hipGraphExec_t exec; // null: nothing captured
     irs_step_key key;
@@ -238,6 +236,69 @@ struct irs_eval_batch_args { // irs_build_eval_batch's arguments as the kernel t
     int32_t *raw_n, *status;
 };
 
+// ---- search options: what a caller binds to a context for its search calls.  Every change goes through opts_changed
+// (capi.hip), which drops the captured steps; which entry point admits which option is capi.hip's search_rules.
+struct irs_search_opts {
+    // exact candidates (irs_bind_survivor_scratch): the caller's scratch while bound; the single-device loops then run the
+    // survivor pass between their top-k and their step, the sharded loops refuse
+    struct {
+        void *scratch;
+        size_t bytes;
+    } surv;
+
+    // bound exclusions (irs_bind_exclusions): the prepared rows in the caller's scratch while bound; every step and loop entry
+    // point then drops window + list (+ path under no_repeat), the sharded loops refuse
+    struct {
+        int on;              // a binding exists (a list, no_repeat, or both)
+        const int32_t *cnt;  // [users] valid ids of a user's row
+        const int64_t *rows; // [users][stride] ascending, INT64_MAX behind the valid ids
+        int users, stride, no_repeat;
+    } excl;
+
+    // path trace (irs_bind_path_trace): the caller's three [users][ld] arrays and scratch while bound; the greedy loops then
+    // run the target sweep before their step and the record kernel after it, the beam and the sharded loops refuse
+    struct {
+        int on;
+        float *item, *target;
+        int32_t *rank;
+        int users, ld;
+        void *scratch;
+    } trace;
+
+    // bound guide (irs_bind_guide): the Rec2Inf choice rule of the greedy path step -- among the first k_c admissible candidates,
+    // the one nearest to the target in the bound feature table; the beam and the sharded entry points then refuse
+    struct {
+        int on;
+        irs_guide g;
+    } guide;
+
+    // bound lookahead (irs_bind_lookahead): the model-based choice of the greedy loops -- among the first k_c admissible candidates,
+    // the one under which the target's next-step log-probability is highest; the beam and the sharded entry points then refuse
+    struct {
+        int on, kc, users, ld;
+        void *scratch;
+        int32_t *rec_item; // [users][ld][kc] or null
+        float *rec_lp;
+    } look;
+
+    // arrival rule (irs_set_arrival_rule): between the trace sweep and the path step, a live row whose target stands at rank
+    // <= rank (0: clause off) or at log-probability >= lp (lp_on) is offered the target alone; needs a bound trace
+    struct {
+        int on, rank, lp_on;
+        float lp;
+    } arrive;
+};
+// the candidates a step chooses among: a guided and a lookahead step among their k_c, a sampled step among sample_k, a beam
+// step of width W among W
+static inline int irs_opt_choices(const irs_search_opts &o, int W, int sample, int sample_k) {
+    return W ? W : (o.guide.on ? o.guide.g.k_c : (o.look.on ? o.look.kc : (sample ? sample_k : 1)));
+}
+// some option puts a launch of its own between the ranking and the greedy step, or needs a step kernel of its own: the merged
+// top-k + step kernel cannot run (the arrival rule needs a trace, which is in the list)
+static inline bool irs_opt_splits_step(const irs_search_opts &o) {
+    return o.surv.scratch || o.excl.on || o.trace.on || o.guide.on || o.look.on;
+}
+
 struct irs_ctx {
     irs_dims dims;
     irs_shard shard;
@@ -340,43 +401,10 @@ struct irs_ctx {
     // captured steps of the search loops (irs_replay_steps): three independent caches, dropped together by irs_drop_graphs
     irs_step_graph g_greedy, g_beam, g_sharded;
 
-    // exact candidates (irs_bind_survivor_scratch): the caller's scratch while bound; the single-device loops then run the
-    // survivor pass between their top-k and their step, the sharded loops refuse
-    void *surv_scratch;
-    size_t surv_bytes;
-    int surv_rows; // rows of the running search call (its first step's): the scratch layout its later, smaller steps keep
-
-    // bound exclusions (irs_bind_exclusions): the prepared rows in the caller's scratch while bound; every step and loop entry
-    // point then drops window + list (+ path under no_repeat), the sharded loops refuse
-    int excl_on;                // a binding exists (a list, no_repeat, or both)
-    const int32_t *excl_cnt;    // [excl_users] valid ids of a user's row
-    const int64_t *excl_rows;   // [excl_users][excl_stride] ascending, INT64_MAX behind the valid ids
-    int excl_users, excl_stride, excl_no_repeat;
-
-    // path trace (irs_bind_path_trace): the caller's three [tr_users][tr_ld] arrays and scratch while bound; the greedy loops then
-    // run the target sweep before their step and the record kernel after it, the beam and the sharded loops refuse
-    int tr_on;
-    float *tr_item, *tr_target;
-    int32_t *tr_rank;
-    int tr_users, tr_ld;
-    void *tr_scratch;
-
-    // bound guide (irs_bind_guide): the Rec2Inf choice rule of the greedy path step -- among the first k_c admissible candidates,
-    // the one nearest to the target in the bound feature table; the beam and the sharded entry points then refuse
-    int guide_on;
-    irs_guide guide;
-
-    // bound lookahead (irs_bind_lookahead): the model-based choice of the greedy loops -- among the first k_c admissible candidates,
-    // the one under which the target's next-step log-probability is highest; the beam and the sharded entry points then refuse
-    int look_on, look_kc, look_users, look_ld;
-    void *look_scratch;
-    int32_t *look_rec_item; // [look_users][look_ld][look_kc] or null
-    float *look_rec_lp;
-
-    // arrival rule (irs_set_arrival_rule): between the trace sweep and the path step, a live row whose target stands at rank
-    // <= arr_rank (0: clause off) or at log-probability >= arr_lp (arr_lp_on) is offered the target alone; needs a bound trace
-    int arr_on, arr_rank, arr_lp_on;
-    float arr_lp;
+    // what the caller has bound for the search entry points (irs_search_opts above), and the rows of the running search call
+    // (its first step's): the layout of opt.surv.scratch that its later, smaller steps keep
+    irs_search_opts opt;
+    int surv_rows;
 
     // profiling
     int prof_family;
@@ -403,6 +431,23 @@ struct irs_ctx {
         return (code);                                            \
     } while (0)
 
+// a user's trace and lookahead record end with its arrival: the until loop zeroes rows [0, B) of them, all ld columns, first
+static inline int irs_opt_zero_records(irs_ctx *ctx, int B, hipStream_t s) {
+    const irs_search_opts &o = ctx->opt;
+    if (o.trace.on) {
+        const size_t n = (size_t)B * o.trace.ld * 4;
+        IRS_CHECK_HIP(ctx, hipMemsetAsync(o.trace.item, 0, n, s));
+        IRS_CHECK_HIP(ctx, hipMemsetAsync(o.trace.target, 0, n, s));
+        IRS_CHECK_HIP(ctx, hipMemsetAsync(o.trace.rank, 0, n, s));
+    }
+    if (o.look.on && o.look.rec_item) {
+        const size_t n = (size_t)B * o.look.ld * o.look.kc * 4;
+        IRS_CHECK_HIP(ctx, hipMemsetAsync(o.look.rec_item, 0, n, s));
+        IRS_CHECK_HIP(ctx, hipMemsetAsync(o.look.rec_lp, 0, n, s));
+    }
+    return IRS_OK;
+}
+
 // profiling bracket helpers (no-ops unless the family is enabled)
 void irs_prof_begin(irs_ctx *ctx, int family, hipStream_t s);
 void irs_prof_end(irs_ctx *ctx, int family, hipStream_t s, double flops, double bytes);
@@ -415,6 +460,9 @@ enum { IRS_CAPTURE_BODY = 1, IRS_CAPTURE_HIP = 2 };
 int irs_replay_steps(irs_ctx *ctx, irs_step_graph *g, const irs_step_key &key, const std::function<int(hipStream_t)> &body,
                      int times, hipStream_t s, int *capture_failed = nullptr);
 void irs_drop_graphs(irs_ctx *ctx);
+// which search entry point admits which bound option, in the order that entry point checks (capi.hip: search_rules); the
+// sharded loops of comm.hip come here for theirs
+int irs_sharded_option_rules(irs_ctx *ctx, const char *fn);
 // the probability clause of an arrival rule is on for lp_min <= 0 (-inf included); lp_min > 0 and NaN turn it off
 static inline bool irs_arrival_lp_on(float lp_min) { return lp_min <= 0.f; }
 // event records are not captured: with a profiling family enabled every loop runs on the stream and records its brackets

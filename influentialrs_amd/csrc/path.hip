@@ -382,7 +382,7 @@ int irs_launch_pack_topk(irs_ctx *ctx, const float *val, const int64_t *ids0, in
 }
 
 int irs_launch_path_step(irs_ctx *ctx, const irs_path_args &pa, int B, const float *val, const int64_t *ids0, int k, hipStream_t s) {
-    if (ctx->guide_on) return irs_launch_path_step_guided(ctx, pa, B, val, ids0, k, s); // (irs_bind_guide: guide.hip)
+    if (ctx->opt.guide.on) return irs_launch_path_step_guided(ctx, pa, B, val, ids0, k, s); // (irs_bind_guide: guide.hip)
     constexpr int S4 = IRS_WIN_SLOTS_SHORT, S16 = IRS_WIN_SLOTS_LONG;
     const auto kern = irs_window_slots(ctx) == S4 ? (pa.ex.on ? k_path_step<true, S4> : k_path_step<false, S4>)
                                                   : (pa.ex.on ? k_path_step<true, S16> : k_path_step<false, S16>);

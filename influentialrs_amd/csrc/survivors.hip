@@ -301,8 +301,8 @@ int irs_launch_excl_prepare(irs_ctx *ctx, const int64_t *ids0, int users, int n_
     const int stride = excl_stride(n_excl);
     hipLaunchKernelGGL(k_excl_prepare, dim3(users), dim3(256), 0, s, ids0, n_excl, stride, ctx->dims.n_item, cnt, rows);
     IRS_CHECK_HIP(ctx, hipGetLastError());
-    ctx->excl_cnt = cnt;
-    ctx->excl_rows = stride ? rows : nullptr;
-    ctx->excl_stride = stride;
+    ctx->opt.excl.cnt = cnt;
+    ctx->opt.excl.rows = stride ? rows : nullptr;
+    ctx->opt.excl.stride = stride;
     return IRS_OK;
 }

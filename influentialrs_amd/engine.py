@@ -418,28 +418,6 @@ class Engine:
                    scratch.numel() * scratch.element_size())
         return val, ids0, status
 
-    @contextlib.contextmanager
-    def _exact_candidates(self, on: bool, rows: int, want: int, graph: bool = False):
-        """While a search call runs with exact_candidates: a scratch sized for the call's rows, bound before and unbound after
-        (irs_bind_survivor_scratch).  Binding and unbinding each drop ALL captured steps of the context, so with the keyword set
-        use_graph saves nothing: the step is captured again on every call, and steps captured by earlier calls are lost.  A
-        caller that wants a captured step with the pass inside binds a scratch of its own once (irs_bind_survivor_scratch) and
-        calls without the keyword.  graph: the call replays a captured step -- the stream is drained before the unbind destroys it."""
-        if not on:
-            yield
-            return
-        scratch = torch.empty(self.survivor_scratch_bytes(rows, want), dtype=torch.uint8, device=self.device)
-        self._check(self.lib.irs_bind_survivor_scratch(self.h, _ptr(scratch), scratch.numel()))
-        try:
-            yield
-        finally:
-            stream = torch.cuda.current_stream(self.device)
-            if graph:
-                stream.synchronize()
-            # (the loops only enqueue: the scratch must outlive the work on the stream)
-            scratch.record_stream(stream)
-            self._check(self.lib.irs_bind_survivor_scratch(self.h, None, 0))
-
     # ------------------------------------------------------------------ bound exclusions (irs_bind_exclusions)
     def exclusion_scratch_bytes(self, users: int, n_excl: int) -> int:
         n = int(self.lib.irs_exclusion_scratch_bytes(self.h, users, n_excl))
@@ -473,25 +451,6 @@ class Engine:
 
     def unbind_exclusions(self):
         self._call(self.lib.irs_bind_exclusions, None, 0, 0, 0, None, 0)
-
-    @contextlib.contextmanager
-    def _exclusions(self, excl_ids0: Optional[torch.Tensor], no_repeat: bool, users: int, graph: bool = False):
-        """While a search call runs with `exclude` / `no_repeat`: the lists bound before and unbound after, like _exact_candidates
-        (and with its cost: bind and unbind drop the context's captured steps)."""
-        if excl_ids0 is None and not no_repeat:
-            yield
-            return
-        if excl_ids0 is not None and excl_ids0.shape[0] != users:
-            raise IrsError(f"exclude: {excl_ids0.shape[0]} lists for {users} users")
-        scratch = self.bind_exclusions(excl_ids0, users, no_repeat)
-        try:
-            yield
-        finally:
-            stream = torch.cuda.current_stream(self.device)
-            if graph:
-                stream.synchronize()
-            scratch.record_stream(stream)
-            self.unbind_exclusions()
 
     # ------------------------------------------------------------------ path trace (irs_bind_path_trace)
     def path_trace_scratch_bytes(self, rows: int) -> int:
@@ -535,23 +494,6 @@ class Engine:
 
     def unbind_path_trace(self):
         self._check(self.lib.irs_bind_path_trace(self.h, None, None, None, 0, 0, None, 0))
-
-    @contextlib.contextmanager
-    def _path_trace(self, on: bool, users: int, ld: int, graph: bool = False):
-        """While a search call runs with trace=True: the three arrays and the scratch bound before and unbound after, like
-        _exact_candidates (and with its cost: bind and unbind drop the context's captured steps).  Yields the arrays, or None."""
-        if not on:
-            yield None
-            return
-        lp_item, lp_target, rank, scratch = self.bind_path_trace(users, ld)
-        try:
-            yield lp_item, lp_target, rank
-        finally:
-            stream = torch.cuda.current_stream(self.device)
-            if graph:
-                stream.synchronize()
-            scratch.record_stream(stream)
-            self.unbind_path_trace()
 
     # ------------------------------------------------------------------ path replay (irs_replay_windows / irs_replay_paths)
     def replay_scratch_bytes(self, chunk: int) -> int:
@@ -661,25 +603,6 @@ class Engine:
         self._call(self.lib.irs_bind_guide, 0, None, 0, 0, None, 0)
         self._guide_held = None
 
-    @contextlib.contextmanager
-    def _guide(self, table: Optional[torch.Tensor], k_c: int, graph: bool = False):
-        """While a search call runs with guide=...: the table bound before and unbound after, like _exclusions (and with its
-        cost: bind and unbind drop the context's captured steps)."""
-        if table is None:
-            yield
-            return
-        held = self.bind_guide(table, k_c)
-        try:
-            yield
-        finally:
-            stream = torch.cuda.current_stream(self.device)
-            if graph:
-                stream.synchronize()
-            for t in held:  # (the loops only enqueue: table and scratch must outlive the work on the stream)
-                if t is not None:
-                    t.record_stream(stream)
-            self.unbind_guide()
-
     # ------------------------------------------------------------------ bound lookahead (irs_bind_lookahead)
     def lookahead_scratch_bytes(self, rows: int, k_c: int) -> int:
         n = int(self.lib.irs_lookahead_scratch_bytes(self.h, rows, k_c))
@@ -763,24 +686,6 @@ class Engine:
                    _ptr(fin), _ptr(val), _ptr(ids0), val.shape[1], _ptr(lp), _ptr(choice))
         return lp, choice
 
-    @contextlib.contextmanager
-    def _lookahead(self, k_c: Optional[int], users: int, ld: int, record: bool = False, graph: bool = False):
-        """While a search call runs with lookahead=k_c: scratch (and record) bound before and unbound after, like _guide (and
-        with its cost: bind and unbind drop the context's captured steps).  Yields the record (items, lp), or None."""
-        if k_c is None:
-            yield None
-            return
-        rec = self.bind_lookahead(k_c, users, ld, record)
-        held = self._lookahead_held
-        try:
-            yield rec
-        finally:
-            stream = torch.cuda.current_stream(self.device)
-            if graph:
-                stream.synchronize()
-            held[0].record_stream(stream)  # (the loops only enqueue: the scratch must outlive the work on the stream)
-            self.unbind_lookahead()
-
     # ------------------------------------------------------------------ arrival rule (irs_set_arrival_rule)
     def set_arrival_rule(self, rank_max: Optional[int] = None, lp_min: Optional[float] = None):
         """irs_set_arrival_rule: until cleared (both None) a live row of the greedy / sampled loops whose target stands at rank
@@ -813,20 +718,92 @@ class Engine:
                    float("nan") if lp_min is None else float(lp_min), _ptr(paths), paths.shape[1] if paths is not None else 0,
                    step, _ptr(row_map), _ptr(status))
 
+    # ------------------------------------------------------------------ the per-call keywords of the search methods
     @contextlib.contextmanager
-    def _arrival_rule(self, rank_max: Optional[int], lp_min: Optional[float], graph: bool = False):
-        """While a search call runs with arrive_rank= / arrive_lp=: the rule set before and cleared after (set and clear drop the
-        context's captured steps, like the bindings)."""
-        if rank_max is None and lp_min is None:
-            yield
-            return
-        self.set_arrival_rule(rank_max, lp_min)
+    def _search_options(self, users: int, ld: int, beam: int = 0, sample=False, sample_k=3, graph: bool = False, *,
+                        exact_candidates: bool = False, exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
+                        guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
+                        arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False):
+        """While a search call runs with per-call keywords: what they ask for is bound before and unbound after.  Yields (the
+        trace arrays (lp_item, lp_target, rank_target) or None, the lookahead record (items, lp) or None).
+        users / ld: the call's users and path length; beam: its beam width, 0 for the greedy loops.  graph: the call replays
+        a captured step -- the stream is drained once before the first unbind destroys it.
+        Every bind and unbind drops ALL captured steps of the context, so with a keyword set use_graph saves nothing: the step
+        is captured again on every call, and steps captured by earlier calls are lost.  A caller that wants a captured step
+        with an option inside binds it once itself (bind_* / set_arrival_rule) and calls without the keyword."""
+        out = {}
+
+        def survivors():  # (for the call's rows and the candidates a step chooses among: csrc/irs_internal.h, irs_opt_choices)
+            want = beam or (guide_k if guide is not None else (lookahead if lookahead is not None else (sample_k if sample else 1)))
+            scratch = torch.empty(self.survivor_scratch_bytes(users * max(beam, 1), want), dtype=torch.uint8, device=self.device)
+            self._check(self.lib.irs_bind_survivor_scratch(self.h, _ptr(scratch), scratch.numel()))
+            return (scratch,)
+
+        def exclusions():
+            if exclude is not None and exclude.shape[0] != users:
+                raise IrsError(f"exclude: {exclude.shape[0]} lists for {users} users")
+            return (self.bind_exclusions(exclude, users, no_repeat),)
+
+        def look():
+            out["looked"] = self.bind_lookahead(lookahead, users, ld, lookahead_record)
+            return self._lookahead_held[:1]
+
+        def traced():
+            lp_item, lp_target, rank, scratch = self.bind_path_trace(users, ld)
+            out["traced"] = (lp_item, lp_target, rank)
+            return (scratch,)
+
+        # (asked for, bind -> the tensors it holds for the call, unbind), in bind order: irs_bind_lookahead refuses behind a
+        # bound guide ("one choice rule at a time"), and a caller who asks for both gets that message
+        options = (
+            (arrive_rank is not None or arrive_lp is not None, lambda: self.set_arrival_rule(arrive_rank, arrive_lp) or (),
+             lambda: self.set_arrival_rule(None, None)),
+            (exact_candidates, survivors, lambda: self._check(self.lib.irs_bind_survivor_scratch(self.h, None, 0))),
+            (exclude is not None or no_repeat, exclusions, self.unbind_exclusions),
+            (guide is not None, lambda: self.bind_guide(guide, guide_k), self.unbind_guide),
+            (lookahead is not None, look, self.unbind_lookahead),
+            (trace, traced, self.unbind_path_trace),
+        )
+        bound = []
         try:
-            yield
+            for asked, bind, unbind in options:
+                if asked:
+                    bound.append((bind(), unbind))
+            yield out.get("traced"), out.get("looked")
         finally:
-            if graph:
-                torch.cuda.current_stream(self.device).synchronize()
-            self.set_arrival_rule(None, None)
+            stream = torch.cuda.current_stream(self.device)
+            if graph and bound:
+                stream.synchronize()
+            for held, unbind in reversed(bound):
+                for t in held:  # (the loops only enqueue: scratch and table must outlive the work on the stream)
+                    if t is not None:
+                        t.record_stream(stream)
+                unbind()
+
+    def _greedy_call(self, what: str, seqs, users, hep, max_path_len: int, paths, status):
+        """What generate_paths and generate_paths_until check and allocate alike: (seqs, users, hep, B, paths, status)."""
+        seqs = self._inplace(seqs, torch.int64, f"{what}: seqs")
+        hep = self._inplace(hep, torch.int32, f"{what}: hep")
+        if users is not None:
+            users = self._dev(users, torch.int64)
+        B = seqs.shape[0]
+        if seqs.shape[1] != self.L or hep.shape[0] != B or (users is not None and users.shape[0] != B):
+            raise IrsError(f"{what}: inconsistent shapes")
+        if paths is None:
+            paths = torch.zeros((B, max_path_len), dtype=torch.float32, device=self.device)
+        if status is None:
+            status = torch.zeros(B, dtype=torch.int32, device=self.device)
+        paths = self._inplace(paths, torch.float32, f"{what}: paths")
+        status = self._inplace(status, torch.int32, f"{what}: status")
+        if paths.shape != (B, max_path_len):
+            raise IrsError(f"{what}: paths must be [B, max_path_len]")
+        return seqs, users, hep, B, paths, status
+
+    @staticmethod
+    def _recorded(recorded, trace: bool, lookahead_record: bool):
+        """The members a greedy loop's return value grows: the trace arrays, then the lookahead record."""
+        traced, looked = recorded
+        return ((traced,) if trace else ()) + ((looked,) if lookahead_record else ())
 
     # ------------------------------------------------------------------ path search
     def path_step(self, seqs, hep, val, ids0, step: int, paths, status, sample=False, sample_k=3, seed=0):
@@ -851,7 +828,7 @@ class Engine:
         """Runs the whole search loop on the device.  `seqs` and `hep` are the
         working window state and are modified in place.  exact_candidates: a row whose k candidates are hidden by its window
         chooses among the exact best admissible items of the catalog instead (IRS_ROW_RESCUED; the result of k = n_item).
-        With the keyword set use_graph saves nothing: the step is captured again on every call (_exact_candidates).
+        With a per-call keyword set use_graph saves nothing: the step is captured again on every call (_search_options).
         exclude (int64 [B, E], 0-based ids, -1 = unused) / no_repeat: bound for this call (irs_bind_exclusions): a step drops
         window + the user's list (+ its own path so far); the same holds in the three other loops.
         trace: a path trace is bound for this call (irs_bind_path_trace) and the return value grows a third member, (lp_item,
@@ -866,30 +843,13 @@ class Engine:
         admissible candidates, the one under which the target's next-step log-probability is highest; greedy only, not with
         guide.  lookahead_record: the return value grows a last member, (items int32 [B, max_path_len, k_c], lp float32 [B,
         max_path_len, k_c]): every step's candidates (1-based, 0 = none) and the values compared."""
-        seqs = self._inplace(seqs, torch.int64, "generate_paths: seqs")
-        hep = self._inplace(hep, torch.int32, "generate_paths: hep")
-        if users is not None:
-            users = self._dev(users, torch.int64)
-        B = seqs.shape[0]
-        if seqs.shape[1] != self.L or hep.shape[0] != B or (users is not None and users.shape[0] != B):
-            raise IrsError("generate_paths: inconsistent shapes")
-        if paths is None:
-            paths = torch.zeros((B, max_path_len), dtype=torch.float32, device=self.device)
-        if status is None:
-            status = torch.zeros(B, dtype=torch.int32, device=self.device)
-        paths = self._inplace(paths, torch.float32, "generate_paths: paths")
-        status = self._inplace(status, torch.int32, "generate_paths: status")
-        if paths.shape != (B, max_path_len):
-            raise IrsError("generate_paths: paths must be [B, max_path_len]")
-        want = guide_k if guide is not None else (lookahead if lookahead is not None else (sample_k if sample else 1))
-        with self._arrival_rule(arrive_rank, arrive_lp, bool(use_graph)), self._exact_candidates(exact_candidates, B, want, bool(use_graph)), \
-                self._exclusions(exclude, no_repeat, B, bool(use_graph)), self._guide(guide, guide_k, bool(use_graph)), \
-                self._lookahead(lookahead, B, max_path_len, lookahead_record, bool(use_graph)) as looked, \
-                self._path_trace(trace, B, max_path_len, bool(use_graph)) as traced:
+        seqs, users, hep, B, paths, status = self._greedy_call("generate_paths", seqs, users, hep, max_path_len, paths, status)
+        with self._search_options(B, max_path_len, 0, sample, sample_k, bool(use_graph), exact_candidates=exact_candidates, exclude=exclude,
+                                  no_repeat=no_repeat, trace=trace, guide=guide, guide_k=guide_k, arrive_rank=arrive_rank,
+                                  arrive_lp=arrive_lp, lookahead=lookahead, lookahead_record=lookahead_record) as recorded:
             self._call(self.lib.irs_generate_paths, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                     int(sample), sample_k, seed, int(use_graph), _ptr(paths), _ptr(status))
-        out = (paths, status, traced) if trace else (paths, status)
-        return out + (looked,) if (lookahead is not None and lookahead_record) else out
+        return (paths, status) + self._recorded(recorded, trace, lookahead is not None and lookahead_record)
 
     def generate_paths_until(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
                              k: int = 100, sweep: int = IRS_SWEEP_BF16, sample=False, sample_k=3, seed=0,
@@ -906,32 +866,14 @@ class Engine:
         arrive_rank / arrive_lp: as in generate_paths (needs trace=True) -- a user is retired at the step that offered it its
         target, so the search stops as soon as the rule allows.
         lookahead / lookahead_record: as in generate_paths; the record is the last member, exactly zero behind a user's arrival."""
-        seqs = self._inplace(seqs, torch.int64, "generate_paths_until: seqs")
-        hep = self._inplace(hep, torch.int32, "generate_paths_until: hep")
-        if users is not None:
-            users = self._dev(users, torch.int64)
-        B = seqs.shape[0]
-        if seqs.shape[1] != self.L or hep.shape[0] != B or (users is not None and users.shape[0] != B):
-            raise IrsError("generate_paths_until: inconsistent shapes")
-        if paths is None:
-            paths = torch.zeros((B, max_path_len), dtype=torch.float32, device=self.device)
-        if status is None:
-            status = torch.zeros(B, dtype=torch.int32, device=self.device)
-        paths = self._inplace(paths, torch.float32, "generate_paths_until: paths")
-        status = self._inplace(status, torch.int32, "generate_paths_until: status")
-        if paths.shape != (B, max_path_len):
-            raise IrsError("generate_paths_until: paths must be [B, max_path_len]")
+        seqs, users, hep, B, paths, status = self._greedy_call("generate_paths_until", seqs, users, hep, max_path_len, paths, status)
         stats = (ctypes.c_int64 * 2)(0, 0)
-        want = guide_k if guide is not None else (lookahead if lookahead is not None else (sample_k if sample else 1))
-        with self._arrival_rule(arrive_rank, arrive_lp), self._exact_candidates(exact_candidates, B, want), \
-                self._exclusions(exclude, no_repeat, B), self._guide(guide, guide_k), \
-                self._lookahead(lookahead, B, max_path_len, lookahead_record) as looked, \
-                self._path_trace(trace, B, max_path_len) as traced:
+        with self._search_options(B, max_path_len, 0, sample, sample_k, exact_candidates=exact_candidates, exclude=exclude,
+                                  no_repeat=no_repeat, trace=trace, guide=guide, guide_k=guide_k, arrive_rank=arrive_rank,
+                                  arrive_lp=arrive_lp, lookahead=lookahead, lookahead_record=lookahead_record) as recorded:
             self._call(self.lib.irs_generate_paths_until, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                           int(sample), sample_k, seed, check_every, _ptr(paths), _ptr(status), stats)
-        out = (paths, status, int(stats[0]), int(stats[1]))
-        out = out + (traced,) if trace else out
-        return out + (looked,) if (lookahead is not None and lookahead_record) else out
+        return (paths, status, int(stats[0]), int(stats[1])) + self._recorded(recorded, trace, lookahead is not None and lookahead_record)
 
     # ------------------------------------------------------------------ beam search (build-defined extension)
     def beam_step(self, state_in, val, ids0, lse, step: int, state_out, status):
@@ -964,8 +906,8 @@ class Engine:
         scores = torch.zeros((B, beam), dtype=torch.float64, device=self.device)
         status = torch.zeros(B, dtype=torch.int32, device=self.device)
         fin = torch.empty((B, beam, self.L), dtype=torch.int64, device=self.device) if want_windows else None
-        with self._exact_candidates(exact_candidates, B * beam, beam, bool(use_graph)), \
-                self._exclusions(exclude, no_repeat, B, bool(use_graph)):
+        with self._search_options(B, max_path_len, beam, graph=bool(use_graph), exact_candidates=exact_candidates, exclude=exclude,
+                                  no_repeat=no_repeat):
             self._call(self.lib.irs_beam_search, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
                                                  int(use_graph), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(status))
         return (paths, scores, status, fin) if want_windows else (paths, scores, status)
@@ -1019,7 +961,7 @@ class Engine:
             raise IrsError("beam_search_until: paths [B, W, P], scores / fin [B, W], status [B]")
         win = torch.empty((B, beam, self.L), dtype=torch.int64, device=self.device) if want_windows else None
         stats = (ctypes.c_int64 * 2)(0, 0)
-        with self._exact_candidates(exact_candidates, B * beam, beam), self._exclusions(exclude, no_repeat, B):
+        with self._search_options(B, max_path_len, beam, exact_candidates=exact_candidates, exclude=exclude, no_repeat=no_repeat):
             self._call(self.lib.irs_beam_search_until, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
                        int(stop_rule), int(check_every), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(win), _ptr(status), stats)
         out = (paths, scores, status, fin, int(stats[0]), int(stats[1]))

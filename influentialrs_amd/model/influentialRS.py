@@ -20,6 +20,7 @@ Behaviour pinned by the reference (file:line = /root/reference/model/influential
   * candidate width 100 (:421); all 100 in the window -> IndexError (:429);
   * selection order is (score desc, id asc); torch's tie order is unspecified.
 """
+import dataclasses
 import functools
 import math
 import os
@@ -176,33 +177,99 @@ class InfluentialNet(nn.Module):
         return xr
 
 
+@dataclasses.dataclass(frozen=True)
+class SearchOptions:
+    """get_seq_in_batch's keyword-only extensions, as _takes_exact_candidates holds them for the time of one call."""
+    exact_candidates: bool = False
+    exclude: object = None
+    no_repeat: bool = False
+    trace: bool = False
+    guide: object = None
+    guide_k: int = 5
+    arrive_rank: object = None
+    arrive_lp: object = None
+    lookahead: object = None
+    lookahead_record: bool = False
+
+
+def search_option_kwargs(opts: SearchOptions, beam_width: int, sample: bool, world: int) -> dict:
+    """What the options ask of a search over `world` item shards with this beam width and choice: ValueError where an option
+    has no such form or a value is out of range, else the engine's greedy-loop keywords for them (exclude / no_repeat aside: the
+    lists need the windows, exclusion_ids0).  An arrival rule implies trace=True."""
+    trace = opts.trace
+    kw = {}
+    if opts.arrive_rank is not None or opts.arrive_lp is not None:
+        rank, lp = opts.arrive_rank, opts.arrive_lp
+        if rank is not None and (isinstance(rank, bool) or int(rank) != rank or rank < 1):
+            raise ValueError(f"arrive_rank={rank!r}: a rank of 1 or more (None: no rank clause)")
+        if lp is not None and not float(lp) <= 0:
+            raise ValueError(f"arrive_lp={lp!r}: a log-probability, at most 0 (None: no probability clause)")
+        if beam_width > 1:
+            raise ValueError("arrive_rank / arrive_lp is not built for beam search (beam_width > 1): the arrival rule reads "
+                             "the path trace, which is not carried through beam state")
+        if world != 1:
+            raise ValueError("arrive_rank / arrive_lp is not built for an item-sharded catalog: irs_set_arrival_rule needs "
+                             "the whole catalog on one device")
+        kw.update(arrive_rank=None if rank is None else int(rank), arrive_lp=None if lp is None else float(lp))
+        trace = True
+    if opts.lookahead is not None:
+        k_c = opts.lookahead
+        if isinstance(k_c, bool) or not isinstance(k_c, (int, np.integer)) or not 1 <= k_c <= 32:
+            raise ValueError(f"lookahead={k_c!r}: an int from 1 to 32, the candidates a step looks ahead from (None: off)")
+        if opts.guide is not None:
+            raise ValueError("lookahead and guide are two rules for the same choice: use one of them")
+        if sample:
+            raise ValueError("lookahead is not built for the sampled search: the choice is deterministic, use sample=False")
+        if beam_width > 1:
+            raise ValueError("lookahead is not built for beam search (beam_width > 1): use beam_width=1 (the lookahead choice "
+                             "is a rule of the greedy step)")
+        if world != 1:
+            raise ValueError("lookahead is not built for an item-sharded catalog: irs_bind_lookahead needs the whole catalog "
+                             "on one device")
+        kw.update(lookahead=int(k_c), lookahead_record=opts.lookahead_record)
+    elif opts.lookahead_record:
+        raise ValueError("lookahead_record=True needs lookahead=k_c")
+    if opts.guide is not None:
+        if beam_width > 1:
+            raise ValueError("guide is not built for beam search (beam_width > 1): use beam_width=1 (the guided choice is a "
+                             "rule of the greedy step)")
+        if sample:
+            raise ValueError("guide is not built for the sampled search: the guided choice is deterministic, use sample=False")
+        if world != 1:
+            raise ValueError("guide is not built for an item-sharded catalog: irs_bind_guide needs the whole catalog on one "
+                             "device")
+        if not 1 <= opts.guide_k <= 32:
+            raise ValueError(f"guide_k={opts.guide_k}: the guided step chooses among 1 to 32 candidates")
+        kw.update(guide=opts.guide, guide_k=opts.guide_k)
+    if trace and beam_width > 1:
+        raise ValueError("trace is not built for beam search (beam_width > 1): no trace is carried through beam state")
+    if trace and world != 1:
+        raise ValueError("trace is not built for an item-sharded catalog: irs_bind_path_trace needs the whole catalog on "
+                         "one device")
+    if (opts.exclude is not None or opts.no_repeat) and world != 1:
+        raise ValueError("exclude / no_repeat is not built for an item-sharded catalog: irs_bind_exclusions needs the whole "
+                         "catalog on one device")
+    if opts.exact_candidates and world != 1:
+        raise ValueError("exact_candidates is not built for an item-sharded catalog: a shard can only rescue a row against "
+                         "its own items")
+    return dict(exact_candidates=opts.exact_candidates, trace=trace, **kw)
+
+
 def _takes_exact_candidates(fn):
-    """Gives get_seq_in_batch its keyword exact_candidates=False.  It is taken here, keyword only, so that the declared
-    parameter list stays what it was (it ends with beam_stop): positional callers and code that reads the signature are not
-    disturbed.  The search reads the switch from self._exact_candidates for the time of the call.
-    exclude=None and no_repeat=False (bound exclusions) are taken the same way, into self._exclude / self._no_repeat, and
-    trace=False (the path trace) into self._trace, guide=None and guide_k=5 (the guided choice) into self._guide / self._guide_k,
-    arrive_rank=None and arrive_lp=None (the arrival rule) into self._arrive_rank / self._arrive_lp, lookahead=None and
-    lookahead_record=False (the lookahead choice) into self._lookahead / self._lookahead_record."""
+    """Gives get_seq_in_batch its keywords exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None,
+    guide_k=5, arrive_rank=None, arrive_lp=None, lookahead=None and lookahead_record=False.  They are taken here, keyword only,
+    so that the declared parameter list stays what it was (it ends with beam_stop): positional callers and code that reads the
+    signature are not disturbed.  The search reads them from self._search_options, a SearchOptions, for the time of the call."""
     @functools.wraps(fn)
     def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None, guide_k=5,
              arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, **kw):
-        prev = (getattr(self, "_exact_candidates", False), getattr(self, "_exclude", None), getattr(self, "_no_repeat", False),
-                getattr(self, "_trace", False))
-        prev_guide = (getattr(self, "_guide", None), getattr(self, "_guide_k", 5))
-        self._exact_candidates, self._exclude, self._no_repeat, self._trace = bool(exact_candidates), exclude, bool(no_repeat), bool(trace)
-        prev_arrive = (getattr(self, "_arrive_rank", None), getattr(self, "_arrive_lp", None))
-        self._guide, self._guide_k = guide, int(guide_k)
-        self._arrive_rank, self._arrive_lp = arrive_rank, arrive_lp
-        prev_look = (getattr(self, "_lookahead", None), getattr(self, "_lookahead_record", False))
-        self._lookahead, self._lookahead_record = lookahead, bool(lookahead_record)
+        prev = self._search_options
+        self._search_options = SearchOptions(bool(exact_candidates), exclude, bool(no_repeat), bool(trace), guide, int(guide_k),
+                                             arrive_rank, arrive_lp, lookahead, bool(lookahead_record))
         try:
             return fn(self, *args, **kw)
         finally:
-            self._exact_candidates, self._exclude, self._no_repeat, self._trace = prev
-            self._guide, self._guide_k = prev_guide
-            self._arrive_rank, self._arrive_lp = prev_arrive
-            self._lookahead, self._lookahead_record = prev_look
+            self._search_options = prev
     return call
 
 
@@ -254,6 +321,7 @@ def exclusion_ids0(exclude, no_repeat, seqs, hep: int, device):
 
 class IRSNN(nn.Module):
     """Task handler (reference :219-470)."""
+    _search_options = SearchOptions()  # (off between calls: _takes_exact_candidates)
 
     def __init__(self, config, net, device):
         super().__init__()
@@ -486,65 +554,10 @@ class IRSNN(nn.Module):
         B (1 + k_c) windows and runs one more float32 catalog pass.  Not with guide, sample=True or beam_width > 1.
         lookahead_record=True: self.last_lookahead = dict(items int32 [B, max_path_len, k_c] -- each step's candidates, 1-based,
         0 = none -- and lp float32 [B, max_path_len, k_c], the values compared), cut to 0 after the arrival like last_trace."""
-        exact_candidates = getattr(self, "_exact_candidates", False)
-        exclude, no_repeat = getattr(self, "_exclude", None), getattr(self, "_no_repeat", False)
-        trace = getattr(self, "_trace", False)
-        guide, guide_k = getattr(self, "_guide", None), getattr(self, "_guide_k", 5)
-        arrive_rank, arrive_lp = getattr(self, "_arrive_rank", None), getattr(self, "_arrive_lp", None)
-        if arrive_rank is not None or arrive_lp is not None:
-            if arrive_rank is not None and (isinstance(arrive_rank, bool) or int(arrive_rank) != arrive_rank or arrive_rank < 1):
-                raise ValueError(f"arrive_rank={arrive_rank!r}: a rank of 1 or more (None: no rank clause)")
-            if arrive_lp is not None and not float(arrive_lp) <= 0:
-                raise ValueError(f"arrive_lp={arrive_lp!r}: a log-probability, at most 0 (None: no probability clause)")
-            if beam_width > 1:
-                raise ValueError("arrive_rank / arrive_lp is not built for beam search (beam_width > 1): the arrival rule reads "
-                                 "the path trace, which is not carried through beam state")
-            if self.net._hip.world != 1:
-                raise ValueError("arrive_rank / arrive_lp is not built for an item-sharded catalog: irs_set_arrival_rule needs "
-                                 "the whole catalog on one device")
-            arrive_rank = None if arrive_rank is None else int(arrive_rank)
-            arrive_lp = None if arrive_lp is None else float(arrive_lp)
-            trace = True
-        arrive = dict(arrive_rank=arrive_rank, arrive_lp=arrive_lp) if (arrive_rank is not None or arrive_lp is not None) else {}
-        lookahead, lookahead_record = getattr(self, "_lookahead", None), getattr(self, "_lookahead_record", False)
-        if lookahead is not None:
-            if isinstance(lookahead, bool) or not isinstance(lookahead, (int, np.integer)) or not 1 <= lookahead <= 32:
-                raise ValueError(f"lookahead={lookahead!r}: an int from 1 to 32, the candidates a step looks ahead from (None: off)")
-            if guide is not None:
-                raise ValueError("lookahead and guide are two rules for the same choice: use one of them")
-            if sample:
-                raise ValueError("lookahead is not built for the sampled search: the choice is deterministic, use sample=False")
-            if beam_width > 1:
-                raise ValueError("lookahead is not built for beam search (beam_width > 1): use beam_width=1 (the lookahead choice "
-                                 "is a rule of the greedy step)")
-            if self.net._hip.world != 1:
-                raise ValueError("lookahead is not built for an item-sharded catalog: irs_bind_lookahead needs the whole catalog "
-                                 "on one device")
-            lookahead = int(lookahead)
-        elif lookahead_record:
-            raise ValueError("lookahead_record=True needs lookahead=k_c")
-        if guide is not None:
-            if beam_width > 1:
-                raise ValueError("guide is not built for beam search (beam_width > 1): use beam_width=1 (the guided choice is a "
-                                 "rule of the greedy step)")
-            if sample:
-                raise ValueError("guide is not built for the sampled search: the guided choice is deterministic, use sample=False")
-            if self.net._hip.world != 1:
-                raise ValueError("guide is not built for an item-sharded catalog: irs_bind_guide needs the whole catalog on one "
-                                 "device")
-            if not 1 <= guide_k <= 32:
-                raise ValueError(f"guide_k={guide_k}: the guided step chooses among 1 to 32 candidates")
-        if trace and beam_width > 1:
-            raise ValueError("trace is not built for beam search (beam_width > 1): no trace is carried through beam state")
-        if trace and self.net._hip.world != 1:
-            raise ValueError("trace is not built for an item-sharded catalog: irs_bind_path_trace needs the whole catalog on "
-                             "one device")
-        if (exclude is not None or no_repeat) and self.net._hip.world != 1:
-            raise ValueError("exclude / no_repeat is not built for an item-sharded catalog: irs_bind_exclusions needs the whole "
-                             "catalog on one device")
-        if exact_candidates and self.net._hip.world != 1:
-            raise ValueError("exact_candidates is not built for an item-sharded catalog: a shard can only rescue a row against "
-                             "its own items")
+        opts = self._search_options
+        greedy_kw = search_option_kwargs(opts, beam_width, sample, self.net._hip.world)
+        exact_candidates, exclude, no_repeat = opts.exact_candidates, opts.exclude, opts.no_repeat
+        trace, lookahead = greedy_kw["trace"], greedy_kw.get("lookahead")
         if stop_at_target and beam_width > 1:
             raise ValueError("stop_at_target is not built for beam search (beam_width > 1): irs_beam_search runs every step")
         if beam_stop is not None:
@@ -566,10 +579,7 @@ class IRSNN(nn.Module):
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if sample else 0
         ids0 = exclusion_ids0(exclude, no_repeat, seqs, L - (gap_len + 1) - 1, dev)
         excl = dict(exclude=ids0, no_repeat=no_repeat) if (ids0 is not None or no_repeat) else {}
-        guided = dict(guide=guide, guide_k=guide_k) if guide is not None else {}
-        if lookahead is not None:  # (the children of a step are decoded and scored in one call each: B * k_c sequences and rows)
-            guided = dict(lookahead=lookahead, lookahead_record=lookahead_record)
-        n_eng = B * (lookahead or 1)
+        n_eng = B * (lookahead or 1)  # (the children of a lookahead step are decoded and scored in one call each)
         if beam_width > 1:
             paths_t, status = self._beam_paths(work, users, max_path_len, gap_len, beam_width, beam_stop, exact_candidates, excl)
         elif stop_at_target:
@@ -579,15 +589,12 @@ class IRSNN(nn.Module):
             eng = hip.get(n_eng, n_eng)
             paths_t, status, _, _, *traced = eng.generate_paths_until(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
                                                                       sample=sample, sample_k=sample_k, seed=seed,
-                                                                      check_every=STOP_CHECK_EVERY,
-                                                                      exact_candidates=exact_candidates, trace=trace, **excl,
-                                                                      **guided, **arrive)
+                                                                      check_every=STOP_CHECK_EVERY, **excl, **greedy_kw)
         elif hip.world == 1:
             eng = hip.get(n_eng, n_eng)
             paths_t, status, *traced = eng.generate_paths(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
-                                                          sample=sample, sample_k=sample_k, seed=seed, use_graph=False,
-                                                          exact_candidates=exact_candidates, trace=trace, **excl, **guided,
-                                                          **arrive)
+                                                          sample=sample, sample_k=sample_k, seed=seed, use_graph=False, **excl,
+                                                          **greedy_kw)
         else:  # item-sharded: irs_generate_paths_sharded (decode, row all-gather, shard sweep, key all-to-all, merge, path
             # step per search step, below the C ABI on one stream)
             eng = hip.get(B, B * hip.world)
@@ -606,7 +613,7 @@ class IRSNN(nn.Module):
         if trace:
             self.last_trace = path_trace_summary(*(a.detach().cpu().numpy() for a in traced[0]), paths, targets)
             self.last_trace["offered"] = (status & IRS_ROW_OFFERED).ne(0).detach().cpu().numpy()
-        if lookahead is not None and lookahead_record:
+        if lookahead is not None and opts.lookahead_record:
             items, lp = (a.detach().cpu().numpy().copy() for a in traced[-1])
             for i in range(B):  # (cut after the arrival, like last_trace)
                 pos = get_item_index(paths[i], targets[i])
@@ -623,3 +630,8 @@ class IRSNN(nn.Module):
                 paths[i][pos + 1:] = 0
             actual_history.append(histories[i][histories[i] != 0])
         return paths, targets, actual_history, n_early_success
+
+
+# the options of the running call under the keywords' own names, read-only: irn._trace, irn._guide_k, ... (False / None / 5 between calls)
+for _f in dataclasses.fields(SearchOptions):
+    setattr(IRSNN, "_" + _f.name, property(lambda self, _n=_f.name: getattr(self._search_options, _n)))

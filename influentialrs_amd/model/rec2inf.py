@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from .._lib import IRS_ROW_NO_CANDIDATE
-from .influentialRS import STOP_CHECK_EVERY, exclusion_ids0, path_trace_summary
+from .influentialRS import STOP_CHECK_EVERY, SearchOptions, exclusion_ids0, path_trace_summary, search_option_kwargs
 from .layers import get_item_index
 
 
@@ -66,8 +66,8 @@ class Rec2Inf(nn.Module):
         is the reference's predict_next(use_h=True), which drops the history and not only the window."""
         if guide is None:
             raise ValueError("Rec2Inf needs a guide: a [n_item + 1, F] feature table (for the plain greedy path use guide_k=1)")
-        if not 1 <= guide_k <= 32:
-            raise ValueError(f"guide_k={guide_k}: the guided step chooses among 1 to 32 candidates")
+        # (the guide's own checks, as IRSNN.get_seq_in_batch makes them; the sharded catalog is refused below in this handler's words)
+        options = search_option_kwargs(SearchOptions(exact_candidates=exact_candidates, trace=trace, guide=guide, guide_k=guide_k), 1, False, 1)
         hip = self.net._hip
         if hip.world != 1:
             raise ValueError("Rec2Inf is not built for an item-sharded catalog: irs_bind_guide needs the whole catalog on one "
@@ -80,7 +80,7 @@ class Rec2Inf(nn.Module):
         ids0 = exclusion_ids0(exclude, no_repeat, work, L - 2, dev)
         excl = dict(exclude=ids0, no_repeat=no_repeat) if (ids0 is not None or no_repeat) else {}
         eng = hip.get(B, B)
-        common = dict(k=100, sweep=hip.sweep, exact_candidates=exact_candidates, trace=trace, guide=guide, guide_k=guide_k, **excl)
+        common = dict(k=100, sweep=hip.sweep, **options, **excl)
         if stop_at_target:
             paths_t, status, _, _, *traced = eng.generate_paths_until(work, None, hep, max_path_len, check_every=STOP_CHECK_EVERY,
                                                                       **common)

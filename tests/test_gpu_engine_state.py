@@ -459,7 +459,8 @@ def _g8(env, graph, k=E.K, **kw):
 def test_a_held_binding_changes_the_plain_probe_and_unbinding_restores_it(oracle):
     """Sensitivity, through the public API: a binding that is held changes the plain B = 8 search -- graph and no graph, the
     captured form following every time -- to what the same binding gives on a fresh engine, and unbinding restores the plain
-    value.  (No getter reports the single-device caches: the results are the evidence.)"""
+    value.  A trace bound a second time, to other arrays, is followed too: no option is part of the captured step's key, every
+    bind and unbind drops the captured steps.  (No getter reports the single-device caches: the results are the evidence.)"""
     inp, want, _ = _expected("S", oracle)
     plain_p = E.BY_ID["greedy_b8"]
     plain = want["greedy_b8"]
@@ -483,11 +484,19 @@ def test_a_held_binding_changes_the_plain_probe_and_unbinding_restores_it(oracle
     exp_trace_arrays = tuple(t.clone() for t in tr[2])
     torch.cuda.synchronize()
     exp_k1_plain, exp_k1_exact = fresh(k=1), fresh(k=1, exact_candidates=True)
+    KC = 5
+    f = Env(_fresh("S"), inp)
+    seq, hep = inp["s8_seq"].clone(), inp["s8_hep"].clone()
+    lk = f.eng.generate_paths(seq, inp["s8_usr"], hep, E.P_GREEDY, k=E.K, lookahead=KC, lookahead_record=True)
+    exp_look = (lk[0], lk[1], seq, hep)
+    exp_look_record = tuple(t.clone() for t in lk[2])
+    torch.cuda.synchronize()
     # each binding matters on these inputs
     assert (exp_excl[0][:, 0] != plain[0][:, 0]).all()                       # the lists hold step 0's chosen item
     assert not torch.equal(exp_guide[0], plain[0])
     assert int((exp_trace[1] & IRS_ROW_OFFERED).ne(0).sum()) > 0 and not torch.equal(exp_trace[0], plain[0])
     assert int((exp_k1_exact[1] & IRS_ROW_RESCUED).ne(0).sum()) > 0 and not torch.equal(exp_k1_exact[0], exp_k1_plain[0])
+    assert not torch.equal(exp_look[0], plain[0])
 
     env = Env(_fresh("S"), inp)
     eng = env.eng
@@ -511,20 +520,44 @@ def test_a_held_binding_changes_the_plain_probe_and_unbinding_restores_it(oracle
     rounds(exp_guide)
     eng.unbind_guide()
     rounds(plain)
+    # ---- lookahead, with its record
+    record = eng.bind_lookahead(KC, 8, E.P_GREEDY, record=True)
+
+    def record_written():
+        for got, exp in zip(record, exp_look_record):
+            assert torch.equal(_bits(got), _bits(exp))
+            got.zero_()
+    rounds(exp_look, extra=record_written)
+    torch.cuda.synchronize()
+    eng.unbind_lookahead()
+    rounds(plain)
+    assert not any(bool(t.any()) for t in record)  # (unbound: nothing writes the record any more)
     # ---- path trace + arrival rule
     arrays = eng.bind_path_trace(8, E.P_GREEDY)
     eng.set_arrival_rule(rank_max=RANK)
 
-    def trace_written():
+    def trace_written(arrays=arrays):
         for got, exp in zip(arrays[:3], exp_trace_arrays):
             assert torch.equal(_bits(got), _bits(exp))
             got.zero_()
     rounds(exp_trace, extra=trace_written)
     torch.cuda.synchronize()
+    # ---- the trace bound again, to fresh arrays (the old ones are held, so the allocator cannot hand them out again), with the
+    # step captured under the first binding still the last thing the cache saw: the replay must write the new arrays only
+    for t in arrays[:3]:
+        t.zero_()
+    eng.unbind_path_trace()
+    again = eng.bind_path_trace(8, E.P_GREEDY)
+    assert not {t.data_ptr() for t in again} & {t.data_ptr() for t in arrays}
+    d = _diff(plain_p, _g8(env, True), exp_trace)
+    assert d is None, f"rebound trace, graph=True: {d}"
+    trace_written(again)
+    torch.cuda.synchronize()
+    assert not any(bool(t.any()) for t in arrays[:3])
     eng.set_arrival_rule(None, None)
     eng.unbind_path_trace()
     rounds(plain)
-    assert not any(bool(t.any()) for t in arrays[:3])  # (unbound: nothing writes the arrays any more)
+    assert not any(bool(t.any()) for t in arrays[:3] + again[:3])  # (unbound: nothing writes the arrays any more)
     # ---- survivor scratch: at k = 1 the one candidate is soon inside the window
     rounds(exp_k1_plain, k=1)
     surv = torch.empty(eng.survivor_scratch_bytes(8, 1), dtype=torch.uint8, device=DEV)

@@ -261,7 +261,7 @@ def test_keywords_are_off_by_default_and_keyword_only():
         assert par["guide"].default is None and par["guide_k"].default == 5, fn
     for fn in (Engine.beam_search, Engine.beam_search_until, Engine.generate_paths_sharded):
         assert "guide" not in inspect.signature(fn).parameters, fn
-    for name in ("guide_scratch_bytes", "bind_guide", "unbind_guide", "_guide"):
+    for name in ("guide_scratch_bytes", "bind_guide", "unbind_guide", "_search_options"):
         assert hasattr(Engine, name), name
     sig = inspect.signature(IRSNN.get_seq_in_batch, follow_wrapped=False).parameters
     for name, default in (("guide", None), ("guide_k", 5)):

@@ -400,7 +400,7 @@ def test_keywords_are_off_by_default_and_keyword_only():
         assert par["lookahead"].default is None and par["lookahead_record"].default is False, fn
     for fn in (Engine.beam_search, Engine.beam_search_until, Engine.generate_paths_sharded):
         assert "lookahead" not in inspect.signature(fn).parameters, fn
-    for name in ("lookahead_scratch_bytes", "bind_lookahead", "unbind_lookahead", "lookahead_expand", "lookahead_choose", "_lookahead"):
+    for name in ("lookahead_scratch_bytes", "bind_lookahead", "unbind_lookahead", "lookahead_expand", "lookahead_choose", "_search_options"):
         assert hasattr(Engine, name), name
     par = inspect.signature(Engine.bind_lookahead).parameters
     assert list(par) == ["self", "k_c", "users", "ld", "record"] and par["record"].default is False
