@@ -636,6 +636,75 @@ int irs_score_target_trace(irs_ctx *ctx, const float *dev_xrows, const int64_t *
 int irs_bind_path_trace(irs_ctx *ctx, float *dev_lp_item, float *dev_lp_target, int32_t *dev_rank_target, int32_t users, int32_t ld,
                         void *dev_scratch, size_t bytes);
 
+/* ---- beam trace: the path trace of every beam, carried through beam state (opt-in, off by default; BUILD-DEFINED like the beam
+ *      search itself; replaces an irs_replay_paths pass over all B * W * P windows behind the search, which decodes every one of
+ *      them a second time) ------------------------------------------------------------------------------------------------------
+ * A separate binding from the path trace above: what irs_bind_path_trace admits and refuses is unchanged.
+ * For output beam j of user b after the last step, and column i < P: the three values are those of the row the beam's ANCESTOR
+ * was at step i, measured BEFORE step i chose, with exactly the path trace's definitions -- lse over the whole catalog,
+ * lp_target = e_{t-1} - lse, rank_target among what the ancestor's window leaves (exclusions and no_repeat do not enter),
+ * lp_item = e_{c-1} - lse for the item c that step appended to this beam -- and its arithmetic: (double)e - ((double)max +
+ * log((double)sumexp)) from the float32 results of the trace sweep (irs_score_target_trace) on that step's input row, rounded to
+ * float32 once; lp_target and rank_target are 0 when the row has no target.
+ *   e_{c-1} is the LIST value the beam step read for the chosen candidate (dev_val / the loop's ranked list); where the survivor
+ *     pass rewrote the list (irs_bind_survivor_scratch), it is the rewritten value.
+ *   lp_item is NOT the term the step added to the beam's score: the score uses the (max, sumexp) pair of the top-k call, the
+ *     trace the sweep's own, and for W == 1 the score takes no log-sum-exp at all (irs_beam_search).
+ *   A finished beam (the _until forms) keeps its columns up to and including the step that chose its target; later columns stay
+ *     0; when it survives a step it is copied whole, possibly into another slot.  A user that is done on entry to a step is
+ *     not written.  A dead output beam (score -inf) reads 0 in every column.
+ *   On return the beam order is that of dev_paths / dev_scores.
+ * The arrays are the caller's, float dev_lp_item / dev_lp_target [users, W, ld], int32 dev_rank_target [users, W, ld], addressed
+ * by the CALLER's user row: irs_beam_search_until goes through its compaction map, and nothing of the trace is compacted.
+ *
+ * irs_bind_beam_trace binds them (all three NULL unbinds; no launch, no stream).  dev_scratch: caller-owned, >=
+ * irs_beam_trace_scratch_bytes(users, W) bytes -- irs_path_trace_scratch_bytes(users * W) plus one link word and one float per
+ * beam row, each array rounded up to 256 -- 16-byte aligned, valid until the unbind.  Checks, before anything else: world != 1 ->
+ * IRS_E_UNSUPPORTED; the three arrays not all given, W outside [1, 32], users < 1, users * W above max_seqs or max_rows, ld
+ * outside [1, 64], a scratch too small or misaligned -> IRS_E_INVALID.  Binding and unbinding drop the captured steps.
+ * While bound:
+ *   irs_beam_search (stream launches and the two captured ping-pong steps alike) and irs_beam_search_until zero rows [0, B) of
+ *     the three arrays at entry and run, per step: decode, top-k (+ lse), the survivor pass if bound, the trace sweep over the
+ *     live * W rows of the step's input state, the linked beam step, the carry, the step counter.  Paths, scores, status and fin
+ *     are those of the unbound search.  B > users, W different from the bound W, P > ld -> IRS_E_INVALID before any launch.
+ *   every other search entry point -- irs_generate_paths[_until], irs_path_step, irs_beam_step[_until] and the two _sharded
+ *     loops -- returns IRS_E_UNSUPPORTED with a message that names the binding: it is never silently ignored.
+ * With nothing bound every entry point checks and launches exactly what it did before this binding existed.
+ *
+ * The two kernels alone, so that a loop can be composed from public calls (the step honours and refuses the other bindings as
+ * irs_beam_step does -- exclusions honoured; path trace, guide, lookahead refused -- and neither looks at a bound beam trace).
+ * Like irs_lookahead_expand / irs_lookahead_choose they are SYNCHRONOUS and take no stream: the kernel is launched on the null
+ * stream and the call returns when it has finished; a caller whose inputs were produced on another stream waits for that stream
+ * first, and the outputs are complete on return:
+ * irs_beam_step_linked is irs_beam_step when dev_fin_in, dev_fin_out and dev_done are all NULL (stop_rule is then ignored), and
+ *   irs_beam_step_until when all three are given (one or two of them: IRS_E_INVALID); checks and outputs are theirs.  Besides,
+ *   per output beam row b * W + j: dev_link int32 [B, W] and dev_link_val float [B, W] --
+ *     IRS_BEAM_LINK_DEAD                      a dead beam                                              (value 0)
+ *     p in [0, W)                             a child of input beam p: column `step` is new            (the candidate's list value)
+ *     IRS_BEAM_LINK_COPY | p                  input beam p whole: a surviving finished beam, or beam p = j of a done user  (0)
+ * irs_beam_trace_carry applies the links to the three arrays IN PLACE, one workgroup per user: every input row is read first
+ *   (columns [0, step), all ld columns of a row that is copied whole), then every output slot is written in all ld columns -- the
+ *   parent's columns [0, step), then column `step` formed as above from dev_max / dev_sumexp / dev_target_score / dev_rank of the
+ *   PARENT's row (the sweep on the step's input state) and dev_link_val of the output row, then zeros; or the parent's whole
+ *   row; or zeros.  A slot that is a whole copy of itself is not written.  dev_row_map int32 [B] (may be NULL: the identity):
+ *   launch user -> the user row of the three arrays.  No atomics, no float reductions: identical calls give identical bits.
+ *   Null pointers, B < 1, W outside [1, 32], ld outside [1, 64], step outside [0, ld) -> IRS_E_INVALID before the launch. */
+#define IRS_BEAM_LINK_DEAD (-1)
+#define IRS_BEAM_LINK_COPY 256
+size_t irs_beam_trace_scratch_bytes(const irs_ctx *ctx, int32_t users, int32_t W); /* 0 for invalid arguments */
+int irs_bind_beam_trace(irs_ctx *ctx, float *dev_lp_item, float *dev_lp_target, int32_t *dev_rank_target, int32_t users, int32_t W,
+                        int32_t ld, void *dev_scratch, size_t bytes);
+int irs_beam_step_linked(irs_ctx *ctx, const int64_t *dev_seq_in, const int32_t *dev_hep_in, const double *dev_cum_in,
+                         const float *dev_paths_in, const int32_t *dev_fin_in, const float *dev_val, const int64_t *dev_ids0,
+                         const float *dev_lse_max, const float *dev_lse_sum, int32_t B, int32_t W, int32_t k, int32_t step,
+                         int32_t P, int32_t stop_rule, int64_t *dev_seq_out, int32_t *dev_hep_out, double *dev_cum_out,
+                         float *dev_paths_out, int32_t *dev_fin_out, int32_t *dev_done, int32_t *dev_status, int32_t *dev_link,
+                         float *dev_link_val);
+int irs_beam_trace_carry(irs_ctx *ctx, const int32_t *dev_link, const float *dev_link_val, const float *dev_max,
+                         const float *dev_sumexp, const float *dev_target_score, const int32_t *dev_rank, int32_t B, int32_t W,
+                         int32_t step, float *dev_lp_item, float *dev_lp_target, int32_t *dev_rank_target, int32_t ld,
+                         const int32_t *dev_row_map);
+
 /* ---- guided choice: the Rec2Inf rule of the greedy path step (opt-in; replaces the Python double loop over users and steps of
  *      the reference's get_path, main_baselines.py:93-121, and its distance cal_fv_dist, utils.py:202-206) ----------------------
  * A context can hold one bound GUIDE: a feature table over the catalog and a candidate count k_c in [1, IRS_MAX_GUIDE_KC].

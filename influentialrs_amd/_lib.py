@@ -24,6 +24,8 @@ IRS_GUIDE_BINARY, IRS_GUIDE_FLOAT = 1, 2  # irs_bind_guide
 IRS_REPLAY_SLOT, IRS_REPLAY_FULL = 0, 1  # irs_replay_windows / irs_replay_paths: the search loops' layout, the evaluator's
 IRS_MAX_GUIDE_KC, IRS_MAX_GUIDE_BITS, IRS_MAX_GUIDE_FLOATS = 32, 1024, 512
 IRS_MAX_LOOKAHEAD_KC = 32  # irs_bind_lookahead
+IRS_BEAM_LINK_DEAD, IRS_BEAM_LINK_COPY = -1, 256  # irs_beam_step_linked's link word: dead / parent p / IRS_BEAM_LINK_COPY | p
+IRS_MAX_PATH = 64  # path length of the beam searches, and the ld of a bound beam trace
 # irs_decoder_route_last (include/irs_hip.h): its field order and the names of the enum-valued fields, in the order of
 # decoder.hip's enum class DecPlan / DecEmbed / DecFam (tests/test_decoder_routes.py checks that they agree)
 ROUTE_FIELDS = ("rows_only", "small_plan", "plan", "embed", "layer", "tail", "frag", "seq", "kv_planes", "att_fused", "kv_only",
@@ -111,6 +113,13 @@ SIGNATURES = {
     "irs_score_target_trace": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p]),
     "irs_bind_path_trace": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t]),
+    "irs_beam_trace_scratch_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),
+    "irs_bind_beam_trace": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_size_t]),
+    "irs_beam_step_linked": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "irs_beam_trace_carry": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                       c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "irs_guide_scratch_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),
     "irs_bind_guide": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "irs_lookahead_scratch_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),

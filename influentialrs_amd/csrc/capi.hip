@@ -708,16 +708,25 @@ static int args_arrive(irs_ctx *ctx, const char *fn, const search_call &) {
                                    "the rule reads what the trace records", fn);
     return IRS_OK;
 }
+// a beam trace: the call's users, width and path length fit the bound arrays, whose row stride holds the bound W
+static int args_btrace(irs_ctx *ctx, const char *fn, const search_call &c) {
+    const auto &t = ctx->opt.btrace;
+    if (c.B > t.users || c.W != t.W || c.P > t.ld)
+        IRS_FAIL(ctx, IRS_E_INVALID, "%s: B=%d / W=%d / path length %d, the beam trace is bound for [%d, %d, %d]", fn, c.B, c.W, c.P,
+                 t.users, t.W, t.ld);
+    return IRS_OK;
+}
 
 // ---- the options, one row each.  greedy: its argument checks where a greedy entry point looks at it.  beam: why the beam entry
 // points refuse it ("<fn>: <what>: <beam>"); null: they admit it, with the same argument checks.  sharded: the sharded loops'
 // refusal, which every option has (a shard sees its own items only; most bindings refuse a sharded context themselves, so a
-// binding cannot exist there, and must not be ignored if it does)
-enum { OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_N };
+// binding cannot exist there, and must not be ignored if it does).  loops_only: why every entry point but the two beam LOOPS
+// refuses it (the same message form); null for the options the greedy side admits
+enum { OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_BTRACE, OPT_N };
 static const struct {
     bool (*on)(const irs_search_opts &);
     int (*args)(irs_ctx *, const char *, const search_call &);
-    const char *what, *beam, *sharded;
+    const char *what, *beam, *sharded, *loops_only;
 } OPTS[OPT_N] = {
     {[](const irs_search_opts &o) { return o.surv.scratch != nullptr; }, args_surv, nullptr, nullptr,
      "%s: exact candidates (irs_bind_survivor_scratch) need the whole catalog on one device"},
@@ -731,23 +740,29 @@ static const struct {
      "%s: a bound lookahead (irs_bind_lookahead) needs the whole catalog on one device"},
     {[](const irs_search_opts &o) { return o.arrive.on != 0; }, args_arrive, "an arrival rule is set (irs_set_arrival_rule)",
      "greedy and sampled loops only", "%s: an arrival rule (irs_set_arrival_rule) is for the single-device greedy and sampled loops"},
+    {[](const irs_search_opts &o) { return o.btrace.on != 0; }, args_btrace, "a beam trace is bound (irs_bind_beam_trace)", nullptr,
+     "%s: a bound beam trace (irs_bind_beam_trace) needs the whole catalog on one device",
+     "irs_beam_search and irs_beam_search_until only"},
 };
 
 // ---- the entry points, one row each: what it checks, in its order -- the first failing check decides the code and the message.
 // The orders differ, and an option that a row does not name is not looked at there; both are behaviour (tests/
 // test_search_options_host.py holds every answer).  The loops' rows also hold their common checks: readiness, the whole catalog on
 // one device, the call's shape, k.
-enum { AT_GREEDY_LOOP, AT_PATH_STEP, AT_BEAM_STEP, AT_BEAM_LOOP, AT_SHARDED_LOOP };
+// A bound beam trace is refused first wherever it is refused (nothing else of the call is looked at); the beam loops look at it
+// once the call's shape stands.  AT_BEAM_STEP_LINKED, the trace's own step (irs_beam_step_linked), does not look at it.
+enum { AT_GREEDY_LOOP, AT_PATH_STEP, AT_BEAM_STEP, AT_BEAM_LOOP, AT_SHARDED_LOOP, AT_BEAM_STEP_LINKED };
 enum { DO_READY = OPT_N, DO_WORLD, DO_SHAPE, DO_K, DO_END };
-static const int PLAN[][12] = {
-    /* AT_GREEDY_LOOP  */ {OPT_ARRIVE, OPT_GUIDE, OPT_LOOK, DO_READY, DO_WORLD, DO_SHAPE, OPT_TRACE, DO_K, OPT_EXCL, OPT_SURV, DO_END},
-    /* AT_PATH_STEP    */ {OPT_EXCL, OPT_GUIDE, DO_END},
-    /* AT_BEAM_STEP    */ {OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
-    /* AT_BEAM_LOOP    */ {OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, DO_READY, DO_WORLD, OPT_TRACE, DO_SHAPE, DO_K, OPT_EXCL, OPT_SURV, DO_END},
-    /* AT_SHARDED_LOOP */ {OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, DO_END},
+static const int PLAN[][13] = {
+    /* AT_GREEDY_LOOP  */ {OPT_BTRACE, OPT_ARRIVE, OPT_GUIDE, OPT_LOOK, DO_READY, DO_WORLD, DO_SHAPE, OPT_TRACE, DO_K, OPT_EXCL, OPT_SURV, DO_END},
+    /* AT_PATH_STEP    */ {OPT_BTRACE, OPT_EXCL, OPT_GUIDE, DO_END},
+    /* AT_BEAM_STEP    */ {OPT_BTRACE, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
+    /* AT_BEAM_LOOP    */ {OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, DO_READY, DO_WORLD, OPT_TRACE, DO_SHAPE, OPT_BTRACE, DO_K, OPT_EXCL, OPT_SURV, DO_END},
+    /* AT_SHARDED_LOOP */ {OPT_BTRACE, OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, DO_END},
+    /* AT_BEAM_STEP_LINKED */ {OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
 };
 static int search_rules(irs_ctx *ctx, const char *fn, int at, const search_call &c) {
-    const bool beam = at == AT_BEAM_STEP || at == AT_BEAM_LOOP;
+    const bool beam = at == AT_BEAM_STEP || at == AT_BEAM_LOOP || at == AT_BEAM_STEP_LINKED;
     int rc;
     for (const int *p = PLAN[at]; *p != DO_END; ++p) {
         switch (*p) {
@@ -774,6 +789,7 @@ static int search_rules(irs_ctx *ctx, const char *fn, int at, const search_call 
             const auto &o = OPTS[*p];
             if (!o.on(ctx->opt)) break;
             if (at == AT_SHARDED_LOOP) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, o.sharded, fn);
+            if (o.loops_only && at != AT_BEAM_LOOP) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: %s: %s", fn, o.what, o.loops_only);
             if (beam && o.beam) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: %s: %s", fn, o.what, o.beam);
             if ((rc = o.args(ctx, fn, c))) return rc;
         }
@@ -1083,6 +1099,52 @@ extern "C" int irs_bind_path_trace(irs_ctx *ctx, float *lp_item, float *lp_targe
     ctx->opt.trace = {1, lp_item, lp_target, rank_target, users, ld, scratch};
     opts_changed(ctx);
     return IRS_OK;
+}
+
+// ------------------------------------------------------------------ beam trace (irs_bind_beam_trace; beam_trace.hip)
+static bool beam_trace_shape_ok(const irs_ctx *ctx, int users, int W) {
+    return users >= 1 && W >= 1 && W <= 32 && (int64_t)users * W <= ctx->max_seqs && (int64_t)users * W <= ctx->max_rows;
+}
+
+extern "C" size_t irs_beam_trace_scratch_bytes(const irs_ctx *ctx, int32_t users, int32_t W) {
+    if (!ctx || !beam_trace_shape_ok(ctx, users, W)) return 0;
+    return irs_beam_trace_layout(nullptr, users * W, nullptr, nullptr);
+}
+
+extern "C" int irs_bind_beam_trace(irs_ctx *ctx, float *lp_item, float *lp_target, int32_t *rank_target, int32_t users, int32_t W,
+                                   int32_t ld, void *scratch, size_t bytes) {
+    if (!ctx) return IRS_E_INVALID;
+    if (!lp_item && !lp_target && !rank_target) { // unbind
+        if (ctx->opt.btrace.on) opts_changed(ctx);
+        ctx->opt.btrace = {};
+        return IRS_OK;
+    }
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_beam_trace needs the whole catalog on one device");
+    if (!lp_item || !lp_target || !rank_target) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_beam_trace: the three arrays go together");
+    if (W < 1 || W > 32) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_beam_trace: beam width must be in [1, 32]");
+    if (!beam_trace_shape_ok(ctx, users, W))
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_beam_trace: users >= 1 and users*W within max_seqs=%d / max_rows=%d", ctx->max_seqs, ctx->max_rows);
+    if (ld < 1 || ld > IRS_MAX_PATH) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_beam_trace: ld must be in [1, %d]", IRS_MAX_PATH);
+    const int rc = check_scratch(ctx, "irs_bind_beam_trace", scratch, bytes, irs_beam_trace_layout(nullptr, users * W, nullptr, nullptr));
+    if (rc) return rc;
+    ctx->opt.btrace = {1, lp_item, lp_target, rank_target, users, W, ld, scratch};
+    opts_changed(ctx);
+    return IRS_OK;
+}
+
+extern "C" int irs_beam_trace_carry(irs_ctx *ctx, const int32_t *link, const float *link_val, const float *mx, const float *sm,
+                                    const float *tscore, const int32_t *rank, int32_t B, int32_t W, int32_t step, float *lp_item,
+                                    float *lp_target, int32_t *rank_target, int32_t ld, const int32_t *row_map) {
+    if (!ctx) return IRS_E_INVALID;
+    if (!link || !link_val || !mx || !sm || !tscore || !rank || !lp_item || !lp_target || !rank_target)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_trace_carry: null pointer");
+    if (B < 1) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_trace_carry: B must be >= 1");
+    if (W < 1 || W > 32) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_trace_carry: beam width must be in [1, 32]");
+    if (ld < 1 || ld > IRS_MAX_PATH) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_trace_carry: ld must be in [1, %d]", IRS_MAX_PATH);
+    if (step < 0 || step >= ld) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_trace_carry: step must be in [0, ld)");
+    const irs_beam_carry_args a{{(int32_t *)link, (float *)link_val}, mx, sm, tscore, rank, W, ld, step, nullptr, lp_item, lp_target,
+                                rank_target, row_map};
+    return look_run_sync(ctx, irs_launch_beam_trace_carry(ctx, a, B, nullptr)); // (synchronous, on the null stream: irs_hip.h)
 }
 
 // ------------------------------------------------------------------ arrival rule (irs_set_arrival_rule; path.hip: k_arrival_offer)
@@ -1404,7 +1466,33 @@ static int enqueue_beam_step(irs_ctx *ctx, int in, const int64_t *user, int B, i
                                until ? until->map : nullptr, ex};
         if ((rc = irs_launch_survivors(ctx, sa, ctx->opt.surv.scratch, s))) return rc;
     }
-    return irs_enqueue_beam_tail(ctx, in, lmax, lsum, B, W, k, P, status, until, s, &ex);
+    const auto &bt = ctx->opt.btrace;
+    if (!bt.on) return irs_enqueue_beam_tail(ctx, in, lmax, lsum, B, W, k, P, status, until, s, &ex);
+    // A bound beam trace: how the target stands on every row of the step's INPUT state, before the step chooses (where the greedy
+    // loop puts the same sweep); the linked step; the carry, at the caller's user rows; then the step counter.  The sweep writes
+    // its partials to ctx->lse_part and its results to the bound scratch: of what the step still reads, lse_max / lse_sum were
+    // reduced out of lse_part by the top-k call above, and top_val / top_ids / row_status are not the sweep's to write.
+    irs_trace_rows tr;
+    irs_beam_link lk;
+    irs_beam_trace_layout(bt.scratch, bt.users * bt.W, &tr, &lk);
+    if ((rc = irs_launch_target_trace(ctx, ctx->xrows, ctx->bm[in].seq, ctx->bm[in].hep, rows, tr, tr.mx, tr.sm, tr.ts, tr.rank, s))) return rc;
+    const irs_beam_cand cand{ctx->top_val, ctx->top_ids, lmax, lsum, k, ex};
+    if ((rc = irs_launch_beam_step(ctx, ctx->bm[in], ctx->bm[in ^ 1], cand, B, W, 0, ctx->step_ctr, P, status, until, s, &lk))) return rc;
+    const irs_beam_carry_args ca{lk, tr.mx, tr.sm, tr.ts, tr.rank, W, bt.ld, 0, ctx->step_ctr, bt.item, bt.target, bt.rank,
+                                 until ? until->map : nullptr};
+    if ((rc = irs_launch_beam_trace_carry(ctx, ca, B, s))) return rc;
+    return irs_launch_inc(ctx, ctx->step_ctr, s);
+}
+
+// a beam loop under a bound beam trace starts from zeros in rows [0, B) of the three arrays, all ld columns
+static int beam_trace_zero(irs_ctx *ctx, int B, hipStream_t s) {
+    const auto &bt = ctx->opt.btrace;
+    if (!bt.on) return IRS_OK;
+    const size_t n = (size_t)B * bt.W * bt.ld * 4;
+    IRS_CHECK_HIP(ctx, hipMemsetAsync(bt.item, 0, n, s));
+    IRS_CHECK_HIP(ctx, hipMemsetAsync(bt.target, 0, n, s));
+    IRS_CHECK_HIP(ctx, hipMemsetAsync(bt.rank, 0, n, s));
+    return IRS_OK;
 }
 
 extern "C" int irs_beam_search(irs_ctx *ctx, const int64_t *seq0, const int64_t *user, const int32_t *hep0, int32_t B,
@@ -1416,6 +1504,7 @@ extern "C" int irs_beam_search(irs_ctx *ctx, const int64_t *seq0, const int64_t 
     hipStream_t s = (hipStream_t)stream;
     int64_t *const usr = ctx->bm_side[0].user;
     if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
+    if ((rc = beam_trace_zero(ctx, B, s))) return rc;
     if ((rc = irs_launch_beam_init(ctx, seq0, user, hep0, B, W, P, ctx->bm[0], usr, s))) return rc;
     int done = 0;
     if (irs_may_capture(ctx, use_graph) && P >= 2) { // the two ping-pong steps per graph; an odd last step runs on the stream
@@ -1455,6 +1544,35 @@ extern "C" int irs_beam_step_until(irs_ctx *ctx, const int64_t *seq_in, const in
                                 cand, B, W, step, nullptr, P, status, &until, (hipStream_t)stream);
 }
 
+// either beam step, with the link word and the chosen candidate's list value per output row (irs_beam_trace_carry's inputs);
+// synchronous on the null stream, like the carry alone and the two lookahead kernels alone (look_run_sync)
+extern "C" int irs_beam_step_linked(irs_ctx *ctx, const int64_t *seq_in, const int32_t *hep_in, const double *cum_in,
+                                    const float *paths_in, const int32_t *fin_in, const float *val, const int64_t *ids0,
+                                    const float *lse_max, const float *lse_sum, int32_t B, int32_t W, int32_t k, int32_t step,
+                                    int32_t P, int32_t stop_rule, int64_t *seq_out, int32_t *hep_out, double *cum_out,
+                                    float *paths_out, int32_t *fin_out, int32_t *done, int32_t *status, int32_t *link,
+                                    float *link_val) {
+    if (!ctx) return IRS_E_INVALID;
+    if (!seq_in || !hep_in || !cum_in || !paths_in || !val || !ids0 || !seq_out || !hep_out || !cum_out || !paths_out || !status ||
+        !link || !link_val || B < 1 || W < 1 || k < 1 || P < 1 || step < 0 || step >= P)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_linked: bad arguments");
+    const bool until_form = fin_in && fin_out && done;
+    if (!until_form && (fin_in || fin_out || done))
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_linked: dev_fin_in, dev_fin_out and dev_done go together");
+    if (W > 1 && (!lse_max || !lse_sum)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_linked: W > 1 needs the row log-sum-exp");
+    if (until_form && stop_rule != IRS_BEAM_STOP_ALL && stop_rule != IRS_BEAM_STOP_BEST)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_linked: stop_rule %d (IRS_BEAM_STOP_ALL or IRS_BEAM_STOP_BEST)", stop_rule);
+    const int rc = search_rules(ctx, "irs_beam_step_linked", AT_BEAM_STEP_LINKED, search_call{B, W, P, k, 0, 0, 0, true});
+    if (rc) return rc;
+    const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k,
+                             excl_args(ctx, W, nullptr, paths_in, P, 0, nullptr, step)};
+    const irs_beam_until until{done, nullptr, stop_rule};
+    const irs_beam_link lk{link, link_val};
+    return look_run_sync(ctx, irs_launch_beam_step(ctx, beam_state(seq_in, hep_in, cum_in, paths_in, fin_in),
+                                                   {seq_out, hep_out, cum_out, paths_out, fin_out}, cand, B, W, step, nullptr, P, status,
+                                                   until_form ? &until : nullptr, nullptr, &lk));
+}
+
 // The loop.  The beam state of the live users sits in side `cur` of ctx->bm; a step reads it and writes side cur ^ 1, a compaction
 // reads THAT and writes the side the step has just freed.  user / done / map (`sd`) move at compactions only, between the two
 // sides of ctx->bm_side and un_map.  The buffers and the step counter are the ones a cached beam graph bakes in: irs_beam_search
@@ -1473,6 +1591,7 @@ extern "C" int irs_beam_search_until(irs_ctx *ctx, const int64_t *seq0, const in
     irs_beam_side sd = ctx->bm_side[0]; // (its map is null: the identity until the first compaction)
     const irs_beam_out res{paths, scores, fin, seq_final};
     if ((rc = irs_search_begin(ctx, status, B, s))) return rc;
+    if ((rc = beam_trace_zero(ctx, B, s))) return rc;
     if ((rc = irs_launch_beam_init(ctx, seq0, user, hep0, B, W, P, ctx->bm[0], sd.user, s))) return rc;
     IRS_CHECK_HIP(ctx, hipMemsetAsync(ctx->bm[0].fin, 0, sizeof(int32_t) * B * W, s));
     IRS_CHECK_HIP(ctx, hipMemsetAsync(sd.done, 0, sizeof(int32_t) * B, s));

@@ -152,6 +152,29 @@ struct irs_trace_rec { // what the record kernel takes: a step's rows (the scrat
     int32_t *rank_target;
     int ld;
 };
+// ---- beam trace (irs_bind_beam_trace; beam_trace.hip).  A linked beam step says, per output beam row, where it came from (the
+// link word of irs_hip.h: IRS_BEAM_LINK_DEAD, parent p, or IRS_BEAM_LINK_COPY | p) and the list value of the candidate it chose
+// (0 where it chose none); the carry kernel moves the recorded columns along.  Both null: the step as it was.
+struct irs_beam_link {
+    int32_t *link; // [B * W]
+    float *val;    // [B * W]
+};
+// the bound scratch: the trace sweep's rows for `rows` = users * W beam rows, then the link words and the link values
+static inline size_t irs_beam_trace_layout(void *base, int rows, irs_trace_rows *tr, irs_beam_link *lk) {
+    const size_t head = irs_trace_layout(base, rows, tr), r4 = ((size_t)rows * 4 + 255) / 256 * 256;
+    if (lk) lk->link = (int32_t *)((char *)base + head), lk->val = (float *)((char *)base + head + r4);
+    return head + 2 * r4;
+}
+struct irs_beam_carry_args { // irs_beam_trace_carry's arguments as the kernel takes them
+    irs_beam_link lk;                  // by launch row b * W + j
+    const float *mx, *sm, *ts;         // [B * W] the sweep's results on the step's INPUT rows
+    const int32_t *rank;               // [B * W]
+    int W, ld, step_arg;
+    const int32_t *step_ptr;           // device step counter, or step_arg
+    float *lp_item, *lp_target;        // [users][W][ld], by the caller's user row
+    int32_t *rank_target;
+    const int32_t *map;                // launch user -> the caller's user row; null: the identity
+};
 // ---- a bound guide as the guided path step takes it (irs_bind_guide; guide.hip).  table: the packed words [rows][words] of a
 // binary guide (in the caller's scratch) or the caller's float32 [rows][F] table, rows = n_item + 1, row i = 1-based item i.
 struct irs_guide {
@@ -287,6 +310,16 @@ struct irs_search_opts {
         int on, rank, lp_on;
         float lp;
     } arrive;
+
+    // beam trace (irs_bind_beam_trace): the caller's three [users][W][ld] arrays and scratch while bound; the two beam loops then
+    // run the target sweep before a linked beam step and the carry kernel after it, every other search entry point refuses
+    struct {
+        int on;
+        float *item, *target;
+        int32_t *rank;
+        int users, W, ld;
+        void *scratch;
+    } btrace;
 };
 // the candidates a step chooses among: a guided and a lookahead step among their k_c, a sampled step among sample_k, a beam
 // step of width W among W
@@ -583,8 +616,13 @@ int irs_launch_set_step(irs_ctx *ctx, int32_t *step_pair, int step, hipStream_t 
 int irs_launch_beam_init(irs_ctx *ctx, const int64_t *seq0, const int64_t *user0, const int32_t *hep0, int B, int W, int P,
                          const irs_beam_state &st, int64_t *user, hipStream_t s);
 // until == nullptr: the plain step (fin is not touched); else the step of irs_beam_step_until / irs_beam_search_until
+// link != nullptr: the linked form of either, which also writes link->link / link->val (irs_beam_link)
 int irs_launch_beam_step(irs_ctx *ctx, const irs_beam_state &in, const irs_beam_state &out, const irs_beam_cand &cand, int B, int W,
-                         int step, const int32_t *step_ptr, int P, int32_t *status, const irs_beam_until *until, hipStream_t s);
+                         int step, const int32_t *step_ptr, int P, int32_t *status, const irs_beam_until *until, hipStream_t s,
+                         const irs_beam_link *link = nullptr);
+
+// ---- beam_trace.hip ---- (arguments already validated: 1 <= W <= 32, 1 <= ld <= IRS_MAX_PATH)
+int irs_launch_beam_trace_carry(irs_ctx *ctx, const irs_beam_carry_args &a, int B, hipStream_t s);
 // dst == nullptr sends every user to the caller's outputs (out / side_out are then not touched)
 int irs_launch_beam_retire(irs_ctx *ctx, const int32_t *dst, int B, int W, int P, const irs_beam_state &in,
                            const irs_beam_side &side_in, const irs_beam_state &out, const irs_beam_side &side_out,

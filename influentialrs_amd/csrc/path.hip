@@ -113,13 +113,22 @@ __global__ void __launch_bounds__(256) k_merge(const float *__restrict__ val_in,
 // EXCL (irs_bind_exclusions): a beam's survivors are its candidates outside window + the user's bound list + (no_repeat) the
 // beam's own path so far, in.paths[row, 0 .. step): the parent's path of whatever it becomes.  All beams of a user read one list.
 // A finished beam and a dead beam open nothing.  Without EXCL the kernel is, again, the one it was.
+// LK (irs_beam_step_linked, the loops under irs_bind_beam_trace): a trailing irs_beam_link argument makes the LINKED form, which
+// keeps every candidate's float32 list value beside its score and stores, per output beam row, the link word (irs_hip.h) and the
+// chosen candidate's list value: what the carry kernel (beam_trace.hip) needs to move a beam's recorded columns along.  The link
+// is a parameter PACK so that the forms without it keep their kernel arguments -- the offsets of the hidden ones behind them
+// included -- and with them their instructions: every addition sits behind `if constexpr (LINK)`.
 #define BEAM_MAXW 32
-template <bool UNTIL, bool EXCL, int SLOTS>
+template <typename T>
+__device__ __forceinline__ const T &irs_pack_first(const T &t) { return t; }
+template <bool UNTIL, bool EXCL, int SLOTS, typename... LK>
 __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, const irs_beam_state out, const irs_beam_cand cand,
                                                     int W, int L, int step_arg, const int32_t *__restrict__ step_ptr, int P,
-                                                    int32_t *__restrict__ status, const irs_beam_until until) {
+                                                    int32_t *__restrict__ status, const irs_beam_until until, const LK... lk) {
+    constexpr bool LINK = sizeof...(LK) != 0;
     __shared__ double c_score[BEAM_MAXW * BEAM_MAXW];
     __shared__ int64_t c_item[BEAM_MAXW * BEAM_MAXW];
+    __shared__ float c_val[LINK ? BEAM_MAXW * BEAM_MAXW : 1]; // (LINK only: never referenced otherwise)
     __shared__ int c_order[BEAM_MAXW];
     __shared__ int s_flags[2]; // UNTIL: [0] some output beam is live and unfinished, [1] output beam 0 is finished
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, nthr = blockDim.x;
@@ -136,6 +145,10 @@ __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, con
                     out.hep[row] = in.hep[row];
                     out.cum[row] = in.cum[row];
                     out.fin[row] = in.fin[row];
+                    if constexpr (LINK) {
+                        const irs_beam_link &l = irs_pack_first(lk...);
+                        l.link[row] = IRS_BEAM_LINK_COPY | j, l.val[row] = 0.f;
+                    }
                 }
             }
             return;
@@ -190,6 +203,7 @@ __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, con
                         if (lane == 0) {
                             c_score[j * W + found] = cj + ((double)v - norm);
                             c_item[j * W + found] = item;
+                            if constexpr (LINK) c_val[j * W + found] = v;
                         }
                         ++found;
                     }
@@ -227,6 +241,10 @@ __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, con
                 out.cum[orow] = -INFINITY;
                 out.hep[orow] = in.hep[b * W];
                 if constexpr (UNTIL) out.fin[orow] = 0;
+                if constexpr (LINK) {
+                    const irs_beam_link &l = irs_pack_first(lk...);
+                    l.link[orow] = IRS_BEAM_LINK_DEAD, l.val[orow] = 0.f;
+                }
             }
             continue;
         }
@@ -245,6 +263,10 @@ __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, con
                     out.cum[orow] = sc;
                     out.fin[orow] = 1;
                     if (t == 0) s_flags[1] = 1;
+                    if constexpr (LINK) {
+                        const irs_beam_link &l = irs_pack_first(lk...);
+                        l.link[orow] = IRS_BEAM_LINK_COPY | parent, l.val[orow] = 0.f;
+                    }
                 }
                 continue;
             }
@@ -258,6 +280,12 @@ __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, con
         }
         for (int p = lane; p < P; p += 64) po[p] = (p < step) ? pi[p] : (p == step ? (float)item : 0.f);
         if (lane == 0) out.cum[orow] = sc;
+        if constexpr (LINK) {
+            if (lane == 0) {
+                const irs_beam_link &l = irs_pack_first(lk...);
+                l.link[orow] = parent, l.val[orow] = c_val[ci];
+            }
+        }
         if constexpr (UNTIL) {
             const int f = item == wi[L - 1] ? 1 : 0; // the end symbol: the parent window's target
             if (lane == 0) {
@@ -296,10 +324,23 @@ int irs_launch_beam_init(irs_ctx *ctx, const int64_t *seq0, const int64_t *user0
 }
 
 int irs_launch_beam_step(irs_ctx *ctx, const irs_beam_state &in, const irs_beam_state &out, const irs_beam_cand &cand, int B, int W,
-                         int step, const int32_t *step_ptr, int P, int32_t *status, const irs_beam_until *until, hipStream_t s) {
+                         int step, const int32_t *step_ptr, int P, int32_t *status, const irs_beam_until *until, hipStream_t s,
+                         const irs_beam_link *link) {
     if (W < 1 || W > BEAM_MAXW) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam width %d outside [1, %d]", W, BEAM_MAXW);
     const int waves = W < 4 ? 4 : (W > 16 ? 16 : W);
     constexpr int S4 = IRS_WIN_SLOTS_SHORT, S16 = IRS_WIN_SLOTS_LONG;
+    if (link) { // the linked forms: the same choice of UNTIL / EXCL / SLOTS, the link as the trailing argument
+        using LK = irs_beam_link;
+        const auto kern = irs_window_slots(ctx) == S4
+                              ? (cand.ex.on ? (until ? k_beam_step<true, true, S4, LK> : k_beam_step<false, true, S4, LK>)
+                                            : (until ? k_beam_step<true, false, S4, LK> : k_beam_step<false, false, S4, LK>))
+                              : (cand.ex.on ? (until ? k_beam_step<true, true, S16, LK> : k_beam_step<false, true, S16, LK>)
+                                            : (until ? k_beam_step<true, false, S16, LK> : k_beam_step<false, false, S16, LK>));
+        hipLaunchKernelGGL(kern, dim3(B), dim3(64 * waves), 0, s, in, out, cand, W, ctx->dims.max_len, step, step_ptr, P, status,
+                           until ? *until : irs_beam_until{}, *link);
+        IRS_CHECK_HIP(ctx, hipGetLastError());
+        return IRS_OK;
+    }
     const auto kern = irs_window_slots(ctx) == S4
                           ? (cand.ex.on ? (until ? k_beam_step<true, true, S4> : k_beam_step<false, true, S4>)
                                         : (until ? k_beam_step<true, false, S4> : k_beam_step<false, false, S4>))

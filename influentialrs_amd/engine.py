@@ -495,6 +495,80 @@ class Engine:
     def unbind_path_trace(self):
         self._check(self.lib.irs_bind_path_trace(self.h, None, None, None, 0, 0, None, 0))
 
+    # ------------------------------------------------------------------ beam trace (irs_bind_beam_trace)
+    def beam_trace_scratch_bytes(self, users: int, W: int) -> int:
+        n = int(self.lib.irs_beam_trace_scratch_bytes(self.h, users, W))
+        if n == 0:
+            raise IrsError(f"beam_trace_scratch_bytes: users={users}, W={W} (need users >= 1, 1 <= W <= 32 and users * W <= "
+                           f"min(max_seqs={self.max_seqs}, max_rows={self.max_rows}))")
+        return n
+
+    def bind_beam_trace(self, users: int, W: int, ld: int):
+        """irs_bind_beam_trace (opt-in, off by default): until unbind_beam_trace the two beam loops of width W record, per output
+        beam, (lp_item, lp_target float32 [users, W, ld], rank_target int32 [users, W, ld]) -- the path trace's values along the
+        beam's ancestors, in the beam order of paths / scores; every other search entry point refuses.  Returns (lp_item,
+        lp_target, rank_target, scratch): the caller keeps all four alive while bound."""
+        lp_item = torch.zeros((users, W, ld), dtype=torch.float32, device=self.device)
+        lp_target = torch.zeros((users, W, ld), dtype=torch.float32, device=self.device)
+        rank = torch.zeros((users, W, ld), dtype=torch.int32, device=self.device)
+        scratch = torch.empty(self.beam_trace_scratch_bytes(users, W), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.irs_bind_beam_trace(self.h, _ptr(lp_item), _ptr(lp_target), _ptr(rank), users, W, ld, _ptr(scratch),
+                                                 scratch.numel()))
+        return lp_item, lp_target, rank, scratch
+
+    def unbind_beam_trace(self):
+        self._check(self.lib.irs_bind_beam_trace(self.h, None, None, None, 0, 0, 0, None, 0))
+
+    def beam_step_linked(self, state_in, val, ids0, lse, step: int, state_out, status, *, done=None,
+                         stop_rule: int = _lib.IRS_BEAM_STOP_BEST):
+        """irs_beam_step_linked: beam_step (four-tensor states, done None) or beam_step_until (five-tensor states with fin, and
+        done[B]) that also returns (link int32 [B, W], link_val float32 [B, W]): per output beam IRS_BEAM_LINK_DEAD, its parent
+        p, or IRS_BEAM_LINK_COPY | p, and the list value of the candidate a child chose.  A synchronous call (_call_sync)."""
+        kinds = (torch.int64, torch.int32, torch.float64, torch.float32, torch.int32)
+        if len(state_in) != len(state_out) or (len(state_in) == 5) != (done is not None) or len(state_in) not in (4, 5):
+            raise IrsError("beam_step_linked: four-tensor states without done, or five-tensor states (fin last) with done")
+        s_in = [self._inplace(t, k, "beam_step_linked: state_in") for t, k in zip(state_in, kinds)] + [None]
+        s_out = [self._inplace(t, k, "beam_step_linked: state_out") for t, k in zip(state_out, kinds)] + [None]
+        if done is not None:
+            done = self._inplace(done, torch.int32, "beam_step_linked: done")
+        status = self._inplace(status, torch.int32, "beam_step_linked: status")
+        val, ids0 = self._dev(val, torch.float32), self._dev(ids0, torch.int64)
+        B, W, _ = s_in[0].shape
+        lmax, lsum = lse if lse is not None else (None, None)
+        if lmax is not None:
+            lmax, lsum = self._dev(lmax, torch.float32), self._dev(lsum, torch.float32)
+        link = torch.empty((B, W), dtype=torch.int32, device=self.device)
+        link_val = torch.empty((B, W), dtype=torch.float32, device=self.device)
+        self._call_sync(self.lib.irs_beam_step_linked, _ptr(s_in[0]), _ptr(s_in[1]), _ptr(s_in[2]), _ptr(s_in[3]), _ptr(s_in[4]),
+                   _ptr(val), _ptr(ids0), _ptr(lmax), _ptr(lsum), B, W, val.shape[1], step, s_in[3].shape[2], int(stop_rule),
+                   _ptr(s_out[0]), _ptr(s_out[1]), _ptr(s_out[2]), _ptr(s_out[3]), _ptr(s_out[4]), _ptr(done), _ptr(status),
+                   _ptr(link), _ptr(link_val))
+        return link, link_val
+
+    def beam_trace_carry(self, link, link_val, mx, sm, ts, rank, step: int, lp_item, lp_target, rank_target, row_map=None):
+        """irs_beam_trace_carry: applies a linked step's (link, link_val [B, W]) to the three [users, W, ld] arrays in place;
+        (mx, sm, ts, rank) are score_target_trace's results on the step's B * W INPUT rows; row_map int32 [B] (None: the
+        identity) names the user row of the arrays.  A synchronous call (_call_sync)."""
+        link, link_val = self._dev(link, torch.int32), self._dev(link_val, torch.float32)
+        mx, sm, ts = (self._dev(t, torch.float32) for t in (mx, sm, ts))
+        rank = self._dev(rank, torch.int32)
+        lp_item = self._inplace(lp_item, torch.float32, "beam_trace_carry: lp_item")
+        lp_target = self._inplace(lp_target, torch.float32, "beam_trace_carry: lp_target")
+        rank_target = self._inplace(rank_target, torch.int32, "beam_trace_carry: rank_target")
+        B, W = link.shape
+        users, ld = lp_item.shape[0], lp_item.shape[2]
+        if link_val.shape != (B, W) or any(t.numel() != B * W for t in (mx, sm, ts, rank)) or lp_item.dim() != 3 or \
+                lp_item.shape != (users, W, ld) or lp_target.shape != lp_item.shape or rank_target.shape != lp_item.shape:
+            raise IrsError("beam_trace_carry: link / link_val [B, W], sweep rows [B * W], the three arrays [users, W, ld]")
+        if row_map is not None:
+            row_map = self._dev(row_map, torch.int32)
+            if row_map.numel() != B:
+                raise IrsError("beam_trace_carry: row_map [B]")
+        elif B > users:
+            raise IrsError(f"beam_trace_carry: {B} users, the arrays hold {users}")
+        self._call_sync(self.lib.irs_beam_trace_carry, _ptr(link), _ptr(link_val), _ptr(mx), _ptr(sm), _ptr(ts), _ptr(rank), B, W, step,
+                   _ptr(lp_item), _ptr(lp_target), _ptr(rank_target), ld, _ptr(row_map))
+
     # ------------------------------------------------------------------ path replay (irs_replay_windows / irs_replay_paths)
     def replay_scratch_bytes(self, chunk: int) -> int:
         n = int(self.lib.irs_replay_scratch_bytes(self.h, chunk))
@@ -723,9 +797,11 @@ class Engine:
     def _search_options(self, users: int, ld: int, beam: int = 0, sample=False, sample_k=3, graph: bool = False, *,
                         exact_candidates: bool = False, exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
                         guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
-                        arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False):
+                        arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False,
+                        beam_trace: bool = False):
         """While a search call runs with per-call keywords: what they ask for is bound before and unbound after.  Yields (the
-        trace arrays (lp_item, lp_target, rank_target) or None, the lookahead record (items, lp) or None).
+        trace arrays (lp_item, lp_target, rank_target) or None, the lookahead record (items, lp) or None); beam_trace (the beam
+        loops' trace=True) binds a beam trace for the call's width instead, whose [users, W, ld] arrays take the first place.
         users / ld: the call's users and path length; beam: its beam width, 0 for the greedy loops.  graph: the call replays
         a captured step -- the stream is drained once before the first unbind destroys it.
         Every bind and unbind drops ALL captured steps of the context, so with a keyword set use_graph saves nothing: the step
@@ -753,6 +829,11 @@ class Engine:
             out["traced"] = (lp_item, lp_target, rank)
             return (scratch,)
 
+        def beam_traced():
+            lp_item, lp_target, rank, scratch = self.bind_beam_trace(users, beam, ld)
+            out["traced"] = (lp_item, lp_target, rank)
+            return (scratch,)
+
         # (asked for, bind -> the tensors it holds for the call, unbind), in bind order: irs_bind_lookahead refuses behind a
         # bound guide ("one choice rule at a time"), and a caller who asks for both gets that message
         options = (
@@ -763,6 +844,7 @@ class Engine:
             (guide is not None, lambda: self.bind_guide(guide, guide_k), self.unbind_guide),
             (lookahead is not None, look, self.unbind_lookahead),
             (trace, traced, self.unbind_path_trace),
+            (beam_trace, beam_traced, self.unbind_beam_trace),
         )
         bound = []
         try:
@@ -895,8 +977,10 @@ class Engine:
     def beam_search(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
                     beam: int, k: int = 100, sweep: int = IRS_SWEEP_BF16, use_graph: bool = False,
                     want_windows: bool = False, exact_candidates: bool = False, exclude: Optional[torch.Tensor] = None,
-                    no_repeat: bool = False):
-        """(paths[B,W,P] f32, scores[B,W] f64, status[B] i32[, windows[B,W,L]]); beam 0 is the best."""
+                    no_repeat: bool = False, trace: bool = False):
+        """(paths[B,W,P] f32, scores[B,W] f64, status[B] i32[, windows[B,W,L]]); beam 0 is the best.
+        trace: a beam trace is bound for this call (irs_bind_beam_trace) and the return value grows a last member, (lp_item,
+        lp_target float32 [B, W, P], rank_target int32 [B, W, P]): the path trace's values along each output beam's ancestors."""
         seqs = self._dev(seqs, torch.int64)
         hep = self._dev(hep, torch.int32)
         if users is not None:
@@ -907,10 +991,11 @@ class Engine:
         status = torch.zeros(B, dtype=torch.int32, device=self.device)
         fin = torch.empty((B, beam, self.L), dtype=torch.int64, device=self.device) if want_windows else None
         with self._search_options(B, max_path_len, beam, graph=bool(use_graph), exact_candidates=exact_candidates, exclude=exclude,
-                                  no_repeat=no_repeat):
+                                  no_repeat=no_repeat, beam_trace=trace) as recorded:
             self._call(self.lib.irs_beam_search, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
                                                  int(use_graph), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(status))
-        return (paths, scores, status, fin) if want_windows else (paths, scores, status)
+        out = (paths, scores, status, fin) if want_windows else (paths, scores, status)
+        return out + self._recorded(recorded, trace, False)
 
     def beam_step_until(self, state_in, val, ids0, lse, step: int, stop_rule: int, state_out, done, status):
         """One beam step with the end symbol (irs_beam_step_until); state = beam_step's four tensors plus fin[B,W] i32;
@@ -934,10 +1019,11 @@ class Engine:
                           check_every: int = 1, want_windows: bool = False, paths: Optional[torch.Tensor] = None,
                           scores: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
                           fin: Optional[torch.Tensor] = None, exact_candidates: bool = False,
-                          exclude: Optional[torch.Tensor] = None, no_repeat: bool = False):
+                          exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False):
         """Beam search that ends a beam at its target (seqs[b, L - 1]) and retires finished users (irs_beam_search_until):
         (paths[B,W,P] f32, scores[B,W] f64, status[B] i32, fin[B,W] i32, steps_run, window_steps[, windows[B,W,L]]); beam 0 is
-        the best.  One host read of 4 bytes per check."""
+        the best.  One host read of 4 bytes per check.
+        trace: as in beam_search, the last member; a finished beam's columns are exactly zero behind its arrival."""
         seqs = self._dev(seqs, torch.int64)
         hep = self._dev(hep, torch.int32)
         if users is not None:
@@ -961,11 +1047,12 @@ class Engine:
             raise IrsError("beam_search_until: paths [B, W, P], scores / fin [B, W], status [B]")
         win = torch.empty((B, beam, self.L), dtype=torch.int64, device=self.device) if want_windows else None
         stats = (ctypes.c_int64 * 2)(0, 0)
-        with self._search_options(B, max_path_len, beam, exact_candidates=exact_candidates, exclude=exclude, no_repeat=no_repeat):
+        with self._search_options(B, max_path_len, beam, exact_candidates=exact_candidates, exclude=exclude, no_repeat=no_repeat,
+                                  beam_trace=trace) as recorded:
             self._call(self.lib.irs_beam_search_until, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
                        int(stop_rule), int(check_every), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(win), _ptr(status), stats)
         out = (paths, scores, status, fin, int(stats[0]), int(stats[1]))
-        return out + (win,) if want_windows else out
+        return (out + (win,) if want_windows else out) + self._recorded(recorded, trace, False)
 
     # ------------------------------------------------------------------ item-sharded loops below the ABI (comm.hip)
     def allgather_rows(self, comm: "Comm", rows_local: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -190,6 +190,8 @@ class SearchOptions:
     arrive_lp: object = None
     lookahead: object = None
     lookahead_record: bool = False
+    beam_trace: bool = False
+    beam_pick: str = "score"
 
 
 def search_option_kwargs(opts: SearchOptions, beam_width: int, sample: bool, world: int) -> dict:
@@ -241,6 +243,16 @@ def search_option_kwargs(opts: SearchOptions, beam_width: int, sample: bool, wor
         if not 1 <= opts.guide_k <= 32:
             raise ValueError(f"guide_k={opts.guide_k}: the guided step chooses among 1 to 32 candidates")
         kw.update(guide=opts.guide, guide_k=opts.guide_k)
+    if opts.beam_pick not in ("score", "target"):
+        raise ValueError(f"beam_pick={opts.beam_pick!r}: use \"score\" (beam 0) or \"target\"")
+    if opts.beam_pick == "target" and not opts.beam_trace:
+        raise ValueError("beam_pick=\"target\" reads the beam trace: use beam_trace=True")
+    if opts.beam_trace:
+        if beam_width == 1:
+            raise ValueError("beam_trace needs beam_width > 1: use trace=True for the greedy / sampled search")
+        if world != 1:
+            raise ValueError("beam_trace is not built for an item-sharded catalog: irs_bind_beam_trace needs the whole catalog "
+                             "on one device")
     if trace and beam_width > 1:
         raise ValueError("trace is not built for beam search (beam_width > 1): no trace is carried through beam state")
     if trace and world != 1:
@@ -257,15 +269,16 @@ def search_option_kwargs(opts: SearchOptions, beam_width: int, sample: bool, wor
 
 def _takes_exact_candidates(fn):
     """Gives get_seq_in_batch its keywords exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None,
-    guide_k=5, arrive_rank=None, arrive_lp=None, lookahead=None and lookahead_record=False.  They are taken here, keyword only,
+    guide_k=5, arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, beam_trace=False and
+    beam_pick="score".  They are taken here, keyword only,
     so that the declared parameter list stays what it was (it ends with beam_stop): positional callers and code that reads the
     signature are not disturbed.  The search reads them from self._search_options, a SearchOptions, for the time of the call."""
     @functools.wraps(fn)
     def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None, guide_k=5,
-             arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, **kw):
+             arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, beam_trace=False, beam_pick="score", **kw):
         prev = self._search_options
         self._search_options = SearchOptions(bool(exact_candidates), exclude, bool(no_repeat), bool(trace), guide, int(guide_k),
-                                             arrive_rank, arrive_lp, lookahead, bool(lookahead_record))
+                                             arrive_rank, arrive_lp, lookahead, bool(lookahead_record), bool(beam_trace), beam_pick)
         try:
             return fn(self, *args, **kw)
         finally:
@@ -296,6 +309,61 @@ def path_trace_summary(lp_item, lp_target, rank_target, paths, targets, n_live=N
                 ioi=lp_target[rows, last].astype(np.float64) - lp_target[:, 0].astype(np.float64),
                 ior=rank_target[:, 0].astype(np.int64) - rank_target[rows, last].astype(np.int64),
                 avg_lp_item=np.array([lp_item[i, :n_steps[i]].astype(np.float64).mean() for i in range(B)]))
+
+
+def beam_trace_summary(lp_item, lp_target, rank_target, paths, scores, targets):
+    """get_seq_in_batch's last_beam_trace from a beam search's arrays ([B, W, P] each, scores [B, W], targets [B]).  A beam's
+    recorded steps end with its arrival (the first path entry equal to the user's target) or run to P; a dead beam (score
+    -inf) has none.  Behind them the three arrays are cut to 0, as path_trace_summary cuts a greedy trace."""
+    lp_item = np.array(lp_item, dtype=np.float32)
+    lp_target = np.array(lp_target, dtype=np.float32)
+    rank_target = np.array(rank_target, dtype=np.int32)
+    paths, scores = np.asarray(paths), np.asarray(scores)
+    B, W, P = lp_item.shape
+    n_steps = np.full((B, W), P, dtype=np.int64)
+    for b in range(B):
+        for j in range(W):
+            if not scores[b, j] > -np.inf:
+                n_steps[b, j] = 0
+            else:
+                pos = get_item_index(paths[b, j], np.asarray(targets).reshape(-1)[b])
+                if pos != -1:
+                    n_steps[b, j] = pos + 1
+            for a in (lp_item, lp_target, rank_target):
+                a[b, j, n_steps[b, j]:] = 0
+    return dict(lp_item=lp_item, lp_target=lp_target, rank_target=rank_target, paths=np.array(paths), scores=np.array(scores),
+                n_steps=n_steps)
+
+
+def pick_beam(paths, scores, lp_target, n_steps, targets, how="score"):
+    """The beam get_seq_in_batch returns per user, int64 [B].  "score": beam 0, the best score.  "target": the live beam (score
+    > -inf) whose path holds the user's target at the earliest step -- ties go to the higher score, then to the lower index;
+    if no live beam holds it, the live beam with the largest lp_target in its last recorded column n_steps - 1, ties broken
+    the same way.  A user without a live beam gets beam 0."""
+    paths, scores, lp_target, n_steps = (np.asarray(a) for a in (paths, scores, lp_target, n_steps))
+    B, W, P = paths.shape
+    if how == "score":
+        return np.zeros(B, dtype=np.int64)
+    if how != "target":
+        raise ValueError(f"beam_pick={how!r}: use \"score\" or \"target\"")
+    tg = np.asarray(targets).reshape(B, 1, 1)
+    hit = paths == tg
+    first = np.where(hit.any(axis=2), hit.argmax(axis=2), P)  # P: the path never holds the target
+    last = lp_target[np.arange(B)[:, None], np.arange(W)[None, :], np.maximum(n_steps - 1, 0)].astype(np.float64)
+    live = scores > -np.inf
+    out = np.zeros(B, dtype=np.int64)
+    for b in range(B):
+        if not live[b].any():
+            continue
+        arrived = live[b] & (first[b] < P)
+        # lexsort: the last key is the primary one; every key ascending, the index last among ties
+        if arrived.any():
+            order = np.lexsort((np.arange(W), -scores[b], first[b]))
+            out[b] = next(j for j in order if arrived[j])
+        else:
+            order = np.lexsort((np.arange(W), -scores[b], -last[b]))
+            out[b] = next(j for j in order if live[b, j])
+    return out
 
 
 def exclusion_ids0(exclude, no_repeat, seqs, hep: int, device):
@@ -475,27 +543,30 @@ class IRSNN(nn.Module):
             a[ru, rs] = v.cpu().numpy()
         return path_trace_summary(*out, items, targets, n_live=n_live)
 
-    def _beam_paths(self, seqs, users, max_path_len, gap_len, beam_width, beam_stop=None, exact_candidates=False, excl=None):
+    def _beam_paths(self, seqs, users, max_path_len, gap_len, beam_width, beam_stop=None, exact_candidates=False, excl=None,
+                    beam_trace=False):
         """Best-beam paths [B, P] + status via the build-defined beam search (no reference
         counterpart; beam_width == 1 equals the greedy search).  All beams and their
         cumulative log-probabilities are kept in self.last_beams = (paths[B,W,P], scores[B,W]).
         beam_stop "best" / "all": irs_beam_search_until -- a beam ends at its target, finished users are retired;
-        self.last_beam_stop = dict(finished [B,W], steps, window_steps)."""
+        self.last_beam_stop = dict(finished [B,W], steps, window_steps).
+        beam_trace (one device): the search also returns the three [B, W, P] arrays of irs_bind_beam_trace, the last value."""
         B, L = seqs.shape
         dev = seqs.device
         hip = self.net._hip
         W = beam_width
         hep = torch.full((B,), L - (gap_len + 1) - 1, dtype=torch.int32, device=dev)
+        traced = ()
         if beam_stop is not None:
             eng = hip.get(B * W, B * W)
-            paths, scores, status, fin, steps, window_steps = eng.beam_search_until(
+            paths, scores, status, fin, steps, window_steps, *traced = eng.beam_search_until(
                 seqs.contiguous(), users, hep, max_path_len, W, k=100, sweep=hip.sweep, stop_rule=_BEAM_STOP_RULES[beam_stop],
-                check_every=BEAM_STOP_CHECK_EVERY, exact_candidates=exact_candidates, **(excl or {}))
+                check_every=BEAM_STOP_CHECK_EVERY, exact_candidates=exact_candidates, trace=beam_trace, **(excl or {}))
             self.last_beam_stop = dict(finished=fin.detach().cpu().numpy(), steps=steps, window_steps=window_steps)
         elif hip.world == 1:
             eng = hip.get(B * W, B * W)
-            paths, scores, status = eng.beam_search(seqs.contiguous(), users, hep, max_path_len, W, k=100, sweep=hip.sweep,
-                                                    exact_candidates=exact_candidates, **(excl or {}))
+            paths, scores, status, *traced = eng.beam_search(seqs.contiguous(), users, hep, max_path_len, W, k=100, sweep=hip.sweep,
+                                                             exact_candidates=exact_candidates, trace=beam_trace, **(excl or {}))
         else:  # item-sharded: the whole loop runs below the C ABI (irs_beam_search_sharded: row all-gather, packed top-100
             # all-to-all, log-sum-exp all-reduce per step, one stream-ordered sequence; captured into a hipGraph over RCCL)
             eng = hip.get(B * W, B * W * hip.world)
@@ -505,7 +576,7 @@ class IRSNN(nn.Module):
                                                             sweep=hip.sweep, split_decode=False,
                                                             use_graph=hip.comm.is_rccl and _SHARDED_GRAPH)
         self.last_beams = (paths.detach().cpu().numpy(), scores.detach().cpu().numpy())
-        return paths[:, 0].contiguous(), status
+        return paths, status, (traced[0] if traced else None)
 
     @_takes_exact_candidates
     def get_seq_in_batch(self, seqs, users, targets, max_path_len=20, gap_len=20, sample=False, sample_k=3,
@@ -553,7 +624,13 @@ class IRSNN(nn.Module):
         the target itself, once among the candidates, is offered outright).  k_c = 1 is the greedy search.  A step then decodes
         B (1 + k_c) windows and runs one more float32 catalog pass.  Not with guide, sample=True or beam_width > 1.
         lookahead_record=True: self.last_lookahead = dict(items int32 [B, max_path_len, k_c] -- each step's candidates, 1-based,
-        0 = none -- and lp float32 [B, max_path_len, k_c], the values compared), cut to 0 after the arrival like last_trace."""
+        0 = none -- and lp float32 [B, max_path_len, k_c], the values compared), cut to 0 after the arrival like last_trace.
+        beam_trace=False, beam_pick="score" (extension, keyword only, taken the same way; beam_width > 1 on one device, off by
+        default): the beam search carries the trace of every beam through its state (irs_bind_beam_trace), with or without
+        beam_stop.  self.last_beam_trace = dict(lp_item, lp_target, rank_target [B, W, max_path_len], cut to 0 after each beam's
+        arrival; paths, scores; n_steps [B, W]; picked [B]).  beam_pick="target" (needs beam_trace=True) returns, per user,
+        the beam pick_beam names instead of beam 0: the live beam that reaches the target first, else the one that ends with the
+        target most probable.  The returned tuple keeps its shape."""
         opts = self._search_options
         greedy_kw = search_option_kwargs(opts, beam_width, sample, self.net._hip.world)
         exact_candidates, exclude, no_repeat = opts.exact_candidates, opts.exclude, opts.no_repeat
@@ -581,7 +658,17 @@ class IRSNN(nn.Module):
         excl = dict(exclude=ids0, no_repeat=no_repeat) if (ids0 is not None or no_repeat) else {}
         n_eng = B * (lookahead or 1)  # (the children of a lookahead step are decoded and scored in one call each)
         if beam_width > 1:
-            paths_t, status = self._beam_paths(work, users, max_path_len, gap_len, beam_width, beam_stop, exact_candidates, excl)
+            all_paths, status, beam_traced = self._beam_paths(work, users, max_path_len, gap_len, beam_width, beam_stop, exact_candidates,
+                                                              excl, opts.beam_trace)
+            paths_t = all_paths[:, 0].contiguous()
+            if opts.beam_trace:  # (what beam_pick="target" names is decided on the host, from the trace as the caller will see it)
+                allp, alls = self.last_beams
+                self.last_beam_trace = beam_trace_summary(*(a.detach().cpu().numpy() for a in beam_traced), allp, alls,
+                                                          targets.detach().cpu().numpy())
+                bt = self.last_beam_trace
+                pick = pick_beam(allp, alls, bt["lp_target"], bt["n_steps"], targets.detach().cpu().numpy(), opts.beam_pick)
+                self.last_beam_trace["picked"] = pick
+                paths_t = all_paths[torch.arange(B, device=dev), torch.from_numpy(pick).to(dev)].contiguous()
         elif stop_at_target:
             if hip.world != 1:
                 raise ValueError("stop_at_target is not built for an item-sharded catalog: irs_generate_paths_sharded runs "
