@@ -589,6 +589,63 @@ size_t irs_exclusion_scratch_bytes(const irs_ctx *ctx, int32_t users, int32_t n_
 int irs_bind_exclusions(irs_ctx *ctx, const int64_t *dev_excl_ids0, int32_t users, int32_t n_excl, int32_t no_repeat,
                         void *dev_scratch, size_t bytes, void *stream);
 
+/* ---- recommend: the exact top-n unseen items of every row (opt-in; replaces sort + history filter + cut of top_k_items,
+ *      IRSNN.get_accuracy_metrics_in_batch, influentialRS.py:375-383; the baselines' predict_next(seqs, users, top_k, use_h),
+ *      sas.py:357-388; the list Rec2Inf's get_path is built on, main_baselines.py:104) ---------------------------------------
+ * For row m, a catalog item j (0-based global id) is ADMISSIBLE when both hold:
+ *   item j + 1 does not occur in seq[m, 0 .. hep[m]] -- the path step's own test; dev_seq == NULL, or hep[m] < 0, is an empty window;
+ *   if an exclusion set is bound (irs_bind_exclusions), j is not in the list of bound user m.  A bound no_repeat has nothing to
+ *   read here -- there is no path -- and is ignored.
+ * The row's SLATE is the best n admissible items of the whole catalog in the library's total order (score descending, id
+ * ascending); scores are the exact float32 chain of irs_score_topk, bit for bit.  Per row:
+ *   count[m] = min(n, admissible items of the catalog); entries [count, n) are (-inf, -1), and lp = -inf there;
+ *   lp[m, i] = (float)((double)val - ((double)max + log((double)sumexp))): the expression the path trace stores, so a slate's
+ *   log-probabilities equal the trace's.
+ * irs_recommend_take is the kernel alone, on the caller's lists: a list val[m, 0 .. k) / ids0[m, 0 .. k) ends at its first negative
+ *   id, and its first n admissible entries are copied in order.  It works on whatever shard the context holds, as irs_beam_step
+ *   does, needs neither weights nor workspace, and writes nothing but its four outputs.  One wave per row, 64 entries per round
+ *   (one per lane), the window held once per wave in LDS; no scratch, no atomics.
+ *    dev_seq int64 [M, L] / dev_hep int32 [M] (both NULL: no window); dev_val float [M, k], dev_ids0 int64 [M, k]
+ *    dev_lse_max / dev_lse_sum float [M]: the row's (max, sum exp) -- irs_score_lse / irs_score_topk_lse; NULL with out_lp NULL
+ *    out_val float [M, n], out_ids0 int64 [M, n], out_lp float [M, n] (may be NULL), out_count int32 [M]
+ * irs_recommend is the whole call on ONE device holding the catalog:
+ *   1. irs_score_topk_lse of the rows at list length k into the scratch (out_lp NULL: irs_score_topk, no log-sum-exp);
+ *   2. the exact repair of SHORT rows -- a list that shows all k valid entries and fewer than n admissible ones -- with want = n:
+ *      the flag, strips and merge launches of irs_topk_ensure_survivors, which return at once when no row is short;
+ *   3. the take kernel.
+ *   The result is what the same call returns with k = n_item.  dev_status gets the top-k's bits, plus IRS_ROW_RESCUED on the
+ *   repaired rows; a row with fewer than n admissible items in the whole catalog is reported through out_count, not by a
+ *   status bit.
+ *   Context state: it counts as one irs_score_topk_lse call of the same rows and nothing more.  It drops no captured step and
+ *   reads and writes no search binding except the exclusion set; no search option refuses it (guide, lookahead, path trace, beam
+ *   trace, arrival rule, survivor scratch).  Nothing is allocated, irs_workspace_bytes does not change.  No float atomics: two
+ *   identical calls give identical bits in val, ids0, count and status; lp inherits the unordered float32 sum of irs_score_lse.
+ *    dev_scratch: caller-owned, >= irs_recommend_scratch_bytes(M, n, k) bytes, 16-byte aligned: the ranked lists (ids, then
+ *            values: 12 M k bytes), the (max, sum exp) pairs, M empty windows for a call without dev_seq, and irs_survivor_scratch_bytes'
+ *            layout for want = n (not monotone in M: a caller that walks row blocks of several sizes asks for each).
+ *    Without dev_seq and without a bound list every entry is admissible and the repair is not launched; without dev_seq and
+ *    with a list it runs on empty windows (one 4 M-byte memset more).
+ * Checks, all before any launch: null required pointers (one of dev_seq / dev_hep without the other), M < 1, M > max_rows, k
+ * outside [1, max_k], n outside [1, min(k, IRS_MAX_RECOMMEND)], out_lp without dev_lse_max / dev_lse_sum (take), a scratch too
+ * small or not 16-byte aligned, more rows than the users of a bound exclusion LIST (a binding of no_repeat alone holds nothing
+ * this call reads: it is ignored, its user count included) -> IRS_E_INVALID; world != 1 (irs_recommend only) ->
+ * IRS_E_UNSUPPORTED; weights, derived weights or workspace unbound (irs_recommend only) -> IRS_E_STATE.
+ * Neither entry point takes a stream.  All their work is ENQUEUED ON THE NULL STREAM (the legacy default stream) and the call
+ * returns without waiting, like every entry point that takes one: the outputs are complete in null-stream order.  A caller that
+ * works on the null stream -- torch's default -- needs nothing more.  A blocking stream is ordered against the null stream by the
+ * runtime in both directions.  A stream created non-blocking is not: its owner puts an event between the work that produced the
+ * inputs and this call, and another between this call and whatever reads the outputs (the Python engine does, with
+ * wait_stream both ways; no host wait).  Not for use inside a stream capture.
+ * IRS_MAX_RECOMMEND: the strip selection of the repair holds 512 keys and compacts to `want` whenever more than 256 are held. */
+#define IRS_MAX_RECOMMEND 128
+size_t irs_recommend_scratch_bytes(const irs_ctx *ctx, int32_t rows, int32_t n, int32_t k); /* 0 for invalid arguments */
+int irs_recommend_take(irs_ctx *ctx, const int64_t *dev_seq, const int32_t *dev_hep, int32_t M, const float *dev_val,
+                       const int64_t *dev_ids0, int32_t k, const float *dev_lse_max, const float *dev_lse_sum, int32_t n,
+                       float *out_val, int64_t *out_ids0, float *out_lp, int32_t *out_count);
+int irs_recommend(irs_ctx *ctx, const float *dev_xrows, const int64_t *dev_seq, const int32_t *dev_hep, int32_t M, int32_t n,
+                  int32_t k, int32_t sweep, float *out_val, int64_t *out_ids0, float *out_lp, int32_t *out_count,
+                  int32_t *dev_status, void *dev_scratch, size_t scratch_bytes);
+
 /* ---- path trace: how the target stands at every step of a greedy / sampled search (opt-in; replaces the saved-path round trip
  *      through Evaluator.get_grad_in_batch -- t_probs, p_probs, IoI, mean path log-probability, evaluator.py:195-205 -- and
  *      get_rr_increase_in_batch's rank before and after, evaluator.py:266-286, with their Python loop of decode + LogSoftmax +

@@ -25,6 +25,7 @@ IRS_REPLAY_SLOT, IRS_REPLAY_FULL = 0, 1  # irs_replay_windows / irs_replay_paths
 IRS_MAX_GUIDE_KC, IRS_MAX_GUIDE_BITS, IRS_MAX_GUIDE_FLOATS = 32, 1024, 512
 IRS_MAX_LOOKAHEAD_KC = 32  # irs_bind_lookahead
 IRS_BEAM_LINK_DEAD, IRS_BEAM_LINK_COPY = -1, 256  # irs_beam_step_linked's link word: dead / parent p / IRS_BEAM_LINK_COPY | p
+IRS_MAX_RECOMMEND = 128  # irs_recommend / irs_recommend_take: items of a slate
 IRS_MAX_PATH = 64  # path length of the beam searches, and the ld of a bound beam trace
 # irs_decoder_route_last (include/irs_hip.h): its field order and the names of the enum-valued fields, in the order of
 # decoder.hip's enum class DecPlan / DecEmbed / DecFam (tests/test_decoder_routes.py checks that they agree)
@@ -109,6 +110,11 @@ SIGNATURES = {
     "irs_bind_survivor_scratch": (c_int32, [c_void_p, c_void_p, c_size_t]),
     "irs_exclusion_scratch_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),
     "irs_bind_exclusions": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    "irs_recommend_scratch_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32]),
+    "irs_recommend_take": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
+                                     c_void_p, c_void_p, c_void_p, c_void_p]),
+    "irs_recommend": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "irs_path_trace_scratch_bytes": (c_size_t, [c_void_p, c_int32]),
     "irs_score_target_trace": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p]),

@@ -751,7 +751,8 @@ static const struct {
 // one device, the call's shape, k.
 // A bound beam trace is refused first wherever it is refused (nothing else of the call is looked at); the beam loops look at it
 // once the call's shape stands.  AT_BEAM_STEP_LINKED, the trace's own step (irs_beam_step_linked), does not look at it.
-enum { AT_GREEDY_LOOP, AT_PATH_STEP, AT_BEAM_STEP, AT_BEAM_LOOP, AT_SHARDED_LOOP, AT_BEAM_STEP_LINKED };
+// AT_RECOMMEND (irs_recommend / irs_recommend_take) is no search: only the exclusion set applies to it, and no option refuses it.
+enum { AT_GREEDY_LOOP, AT_PATH_STEP, AT_BEAM_STEP, AT_BEAM_LOOP, AT_SHARDED_LOOP, AT_BEAM_STEP_LINKED, AT_RECOMMEND };
 enum { DO_READY = OPT_N, DO_WORLD, DO_SHAPE, DO_K, DO_END };
 static const int PLAN[][13] = {
     /* AT_GREEDY_LOOP  */ {OPT_BTRACE, OPT_ARRIVE, OPT_GUIDE, OPT_LOOK, DO_READY, DO_WORLD, DO_SHAPE, OPT_TRACE, DO_K, OPT_EXCL, OPT_SURV, DO_END},
@@ -760,6 +761,7 @@ static const int PLAN[][13] = {
     /* AT_BEAM_LOOP    */ {OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, DO_READY, DO_WORLD, OPT_TRACE, DO_SHAPE, OPT_BTRACE, DO_K, OPT_EXCL, OPT_SURV, DO_END},
     /* AT_SHARDED_LOOP */ {OPT_BTRACE, OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, DO_END},
     /* AT_BEAM_STEP_LINKED */ {OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
+    /* AT_RECOMMEND    */ {OPT_EXCL, DO_END},
 };
 static int search_rules(irs_ctx *ctx, const char *fn, int at, const search_call &c) {
     const bool beam = at == AT_BEAM_STEP || at == AT_BEAM_LOOP || at == AT_BEAM_STEP_LINKED;
@@ -1061,6 +1063,94 @@ extern "C" int irs_bind_survivor_scratch(irs_ctx *ctx, void *scratch, size_t byt
     ctx->opt.surv = {scratch, bytes};
     opts_changed(ctx);
     return IRS_OK;
+}
+
+// ------------------------------------------------------------------ recommend: the top-n admissible items of every row (recommend.hip)
+// Both entry points take no stream: their launches are enqueued on the null stream and the call returns without waiting (irs_hip.h)
+// The caller's scratch, in this order: the rows' ranked lists (ids, then values), their (max, sum exp), the empty windows of a call
+// without dev_seq, then the survivor pass's own layout for want = n
+struct recommend_rows {
+    int64_t *ids0; // [M][k]
+    float *val;    // [M][k]
+    float *mx, *sm; // [M]
+    int32_t *no_hep; // [M] all -1: the empty windows the repair reads when the caller gives none ...
+    const int64_t *no_seq; // ... and the window rows that go with them: behind hep = -1 no slot of a row is ever read, so this
+                           // points at no_hep's own bytes and is NOT [M][L] -- it only keeps the pass's pointer non-null
+    void *surv;
+};
+static size_t recommend_layout(const irs_ctx *ctx, void *base, int M, int n, int k, recommend_rows *o) {
+    const size_t n_val = align_up((size_t)M * k * sizeof(float), 16), n_ids = align_up((size_t)M * k * sizeof(int64_t), 16);
+    const size_t r4 = align_up((size_t)M * sizeof(float), 16);
+    if (o) {
+        char *p = (char *)base;
+        o->ids0 = (int64_t *)p, o->val = (float *)(p + n_ids);
+        o->mx = (float *)(p + n_ids + n_val), o->sm = (float *)(p + n_ids + n_val + r4);
+        o->no_hep = (int32_t *)(p + n_ids + n_val + 2 * r4), o->no_seq = (const int64_t *)o->no_hep;
+        o->surv = p + n_ids + n_val + 3 * r4;
+    }
+    return n_ids + n_val + 3 * r4 + irs_surv_scratch(ctx, M, n);
+}
+static bool recommend_shape_ok(const irs_ctx *ctx, int M, int n, int k) {
+    return M >= 1 && M <= ctx->max_rows && k >= 1 && k <= ctx->dims.max_k && n >= 1 && n <= k && n <= IRS_MAX_RECOMMEND;
+}
+static int check_recommend(irs_ctx *ctx, const char *fn, bool ptrs_ok, int M, int n, int k) {
+    if (!ptrs_ok) IRS_FAIL(ctx, IRS_E_INVALID, "%s: null pointer", fn);
+    if (M < 1) IRS_FAIL(ctx, IRS_E_INVALID, "%s: M must be >= 1", fn);
+    if (M > ctx->max_rows) IRS_FAIL(ctx, IRS_E_INVALID, "%s: M=%d exceeds max_rows=%d", fn, M, ctx->max_rows);
+    if (k < 1 || k > ctx->dims.max_k) IRS_FAIL(ctx, IRS_E_INVALID, "%s: k must be in [1, %d]", fn, ctx->dims.max_k);
+    if (n < 1 || n > k || n > IRS_MAX_RECOMMEND) IRS_FAIL(ctx, IRS_E_INVALID, "%s: n must be in [1, min(k, %d)]", fn, IRS_MAX_RECOMMEND);
+    return IRS_OK;
+}
+// the exclusion lists as the take and the repair read them: never a path, and a binding without a list (no_repeat alone) is none:
+// nothing of it is read, so nothing of it is checked either (its user count included)
+static irs_excl recommend_excl(const irs_ctx *ctx) {
+    const irs_excl e = excl_args(ctx, 1, nullptr, nullptr, 0, 0, nullptr, 0);
+    return e.rows ? e : irs_excl{};
+}
+
+extern "C" size_t irs_recommend_scratch_bytes(const irs_ctx *ctx, int32_t rows, int32_t n, int32_t k) {
+    if (!ctx || !recommend_shape_ok(ctx, rows, n, k)) return 0;
+    return recommend_layout(ctx, nullptr, rows, n, k, nullptr);
+}
+
+extern "C" int irs_recommend_take(irs_ctx *ctx, const int64_t *seq, const int32_t *hep, int32_t M, const float *val, const int64_t *ids0,
+                                  int32_t k, const float *lse_max, const float *lse_sum, int32_t n, float *out_val, int64_t *out_ids0,
+                                  float *out_lp, int32_t *out_count) {
+    if (!ctx) return IRS_E_INVALID;
+    const char *fn = "irs_recommend_take";
+    int rc = check_recommend(ctx, fn, val && ids0 && out_val && out_ids0 && out_count && (seq == nullptr) == (hep == nullptr), M, n, k);
+    if (rc) return rc;
+    if (out_lp && (!lse_max || !lse_sum)) IRS_FAIL(ctx, IRS_E_INVALID, "%s: out_lp needs dev_lse_max and dev_lse_sum", fn);
+    const irs_excl ex = recommend_excl(ctx);
+    if (ex.on && (rc = search_rules(ctx, fn, AT_RECOMMEND, search_call{M, 0, 0, k, 0, 0, 0, true}))) return rc;
+    return irs_launch_recommend_take(ctx, seq, hep, M, val, ids0, k, lse_max, lse_sum, n, out_val, out_ids0, out_lp, out_count, ex, nullptr);
+}
+
+extern "C" int irs_recommend(irs_ctx *ctx, const float *xrows, const int64_t *seq, const int32_t *hep, int32_t M, int32_t n, int32_t k,
+                             int32_t sweep, float *out_val, int64_t *out_ids0, float *out_lp, int32_t *out_count, int32_t *status,
+                             void *scratch, size_t scratch_bytes) {
+    if (!ctx) return IRS_E_INVALID;
+    const char *fn = "irs_recommend";
+    int rc = check_recommend(ctx, fn, xrows && out_val && out_ids0 && out_count && status && (seq == nullptr) == (hep == nullptr), M, n, k);
+    if (rc) return rc;
+    if (sweep != IRS_SWEEP_BF16 && sweep != IRS_SWEEP_F32) IRS_FAIL(ctx, IRS_E_INVALID, "%s: bad sweep", fn);
+    if ((rc = check_scratch(ctx, fn, scratch, scratch_bytes, recommend_layout(ctx, nullptr, M, n, k, nullptr)))) return rc;
+    const irs_excl ex = recommend_excl(ctx);
+    if (ex.on && (rc = search_rules(ctx, fn, AT_RECOMMEND, search_call{M, 0, 0, k, sweep, 0, 0, true}))) return rc;
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s needs the whole catalog on one device", fn);
+    if ((rc = irs_ready_filter(ctx, sweep))) return rc;
+    hipStream_t s = nullptr; // (the null stream: irs_hip.h)
+    recommend_rows r;
+    recommend_layout(ctx, scratch, M, n, k, &r);
+    if ((rc = irs_launch_topk(ctx, xrows, M, k, sweep, r.val, r.ids0, status, s, nullptr, out_lp ? r.mx : nullptr, out_lp ? r.sm : nullptr)))
+        return rc;
+    if (seq || ex.on) { // (with neither a window nor a list every entry is admissible: no row can be short)
+        if (!seq) IRS_CHECK_HIP(ctx, hipMemsetAsync(r.no_hep, 0xFF, (size_t)M * sizeof(int32_t), s)); // every byte 0xFF: hep = -1
+        const irs_surv_args sa{xrows, seq ? seq : r.no_seq, seq ? hep : r.no_hep, M, 1, k, n, M, nullptr, nullptr, nullptr, r.val, r.ids0, status,
+                               nullptr, ex};
+        if ((rc = irs_launch_survivors(ctx, sa, r.surv, s))) return rc;
+    }
+    return irs_launch_recommend_take(ctx, seq, hep, M, r.val, r.ids0, k, r.mx, r.sm, n, out_val, out_ids0, out_lp, out_count, ex, s);
 }
 
 // ------------------------------------------------------------------ path trace (irs_bind_path_trace)

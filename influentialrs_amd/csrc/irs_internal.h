@@ -582,6 +582,12 @@ int irs_launch_excl_prepare(irs_ctx *ctx, const int64_t *ids0, int users, int n_
 size_t irs_surv_scratch(const irs_ctx *ctx, int rows, int want);
 int irs_launch_survivors(irs_ctx *ctx, const irs_surv_args &a, void *scratch, hipStream_t s);
 
+// ---- recommend.hip ---- (the first n admissible entries of every row's list; arguments already validated.  seq null: no window;
+// out_lp null: mx / sm are not read; ex: the bound exclusion lists, never a path)
+int irs_launch_recommend_take(irs_ctx *ctx, const int64_t *seq, const int32_t *hep, int M, const float *val, const int64_t *ids0, int k,
+                              const float *mx, const float *sm, int n, float *out_val, int64_t *out_ids0, float *out_lp,
+                              int32_t *out_count, const irs_excl &ex, hipStream_t s);
+
 // ---- comm.hip ---- (collectives in bytes, stream-ordered; irs_comm_check: the communicator is the context's shard)
 int irs_comm_check(irs_ctx *ctx, const irs_comm *c, const char *fn);
 int irs_comm_allgather(irs_ctx *ctx, irs_comm *c, const void *send, void *recv, size_t bytes_per_rank, hipStream_t s);

@@ -15,7 +15,11 @@
 #define SURV_STRIPS 256          // item strips of a large shard
 #define SURV_STRIP_MIN_ITEMS 128 // a strip holds at least this many items (smaller shards: fewer strips, down to one)
 #define SURV_KEYS_CAP (1 << 21)  // rows x strips x want <= this (16 MiB of keys) while strips > 1: the strip count shrinks
-#define SURV_BUF 512             // keys of LDS per selection: compacted to `want` (<= 32) whenever more than 256 are held
+#define SURV_BUF 512             // keys of LDS per selection: compacted to `want` whenever more than SURV_BUF - 256 are held
+// surv_select appends at most 256 keys between two looks at the held count and compacts to `want` keys as soon as more than
+// SURV_BUF - 256 are held: a slot stays below SURV_BUF as long as want <= SURV_BUF - 256.  The public pass asks for at most 32
+// (irs_topk_ensure_survivors), irs_recommend for at most IRS_MAX_RECOMMEND.
+static_assert(IRS_MAX_RECOMMEND <= SURV_BUF - 256 && IRS_MAX_GUIDE_KC <= SURV_BUF - 256, "surv_select: want must fit between two compactions");
 #define SURV_ROW_GROUPS 64       // workgroups that share the recorded rows, per strip and in the merge: each loops over its rows
 #define SURV_HDR 256             // bytes in front of the list: word 0 is the count
 

@@ -100,6 +100,22 @@ class Engine:
             torch.cuda.current_stream(self.device).synchronize()
             self._check(fn(self.h, *args))
 
+    def _call_null(self, fn, *args, tensors=()):
+        """An entry point that takes no stream and enqueues on the null stream without waiting (irs_recommend, irs_recommend_take).
+        On torch's default stream, which is the null stream, that is all.  On any other current stream the default stream waits
+        for it first and it waits for the default stream afterwards -- two events, no host wait -- and `tensors` (everything the
+        call reads or writes) are marked as used on the default stream."""
+        with torch.cuda.device(self.device):
+            cur, null = torch.cuda.current_stream(self.device), torch.cuda.default_stream(self.device)
+            if cur != null:
+                null.wait_stream(cur)
+            self._check(fn(self.h, *args))
+            if cur != null:
+                cur.wait_stream(null)
+                for t in tensors:
+                    if t is not None:
+                        t.record_stream(null)
+
     def _inplace(self, t: torch.Tensor, dtype, what: str) -> torch.Tensor:
         """A buffer the library updates in place: it must already be what the kernels assume (a copy would
         silently drop the update)."""
@@ -451,6 +467,77 @@ class Engine:
 
     def unbind_exclusions(self):
         self._call(self.lib.irs_bind_exclusions, None, 0, 0, 0, None, 0)
+
+    # ------------------------------------------------------------------ recommend (irs_recommend, irs_recommend_take)
+    def recommend_scratch_bytes(self, rows: int, n: int, k: int) -> int:
+        nb = int(self.lib.irs_recommend_scratch_bytes(self.h, rows, n, k))
+        if nb == 0:
+            raise IrsError(f"recommend_scratch_bytes: rows={rows} / n={n} / k={k} (rows in [1, max_rows={self.max_rows}], k in "
+                           f"[1, max_k={self.max_k}], n in [1, min(k, {_lib.IRS_MAX_RECOMMEND})])")
+        return nb
+
+    def _window(self, what: str, seqs, hep, M: int):
+        if (seqs is None) != (hep is None):
+            raise IrsError(f"{what}: seqs and hep go together")
+        if seqs is None:
+            return None, None
+        seqs, hep = self._dev(seqs, torch.int64), self._dev(hep, torch.int32)
+        if tuple(seqs.shape) != (M, self.L) or hep.numel() != M:
+            raise IrsError(f"{what}: seqs [M, max_len] and hep [M] for M = {M} rows")
+        return seqs, hep
+
+    def recommend(self, xrows: torch.Tensor, n: int, *, seqs: Optional[torch.Tensor] = None, hep: Optional[torch.Tensor] = None,
+                  k: int = 100, sweep: int = IRS_SWEEP_BF16, log_probs: bool = True):
+        """irs_recommend: per row the best n items of the whole catalog that are neither in the window seqs[m, :hep[m] + 1] (None:
+        no window) nor in the bound user's exclusion list (bind_exclusions), exact whatever the window hides of the top k.
+        Returns (val[M, n] float32, ids0[M, n] int64 0-based, lp[M, n] float32 or None, count[M] int32, status[M] int32); entries
+        behind count[m] are (-inf, -1, -inf).  The scratch is the engine's, kept for the next call of the same shape.  The work goes on
+        the null stream, ordered against torch's current stream by events (_call_null)."""
+        xrows = self._dev(xrows, torch.float32)
+        if xrows.dim() != 2 or xrows.shape[1] != self.d:
+            raise IrsError("recommend: xrows [M, d]")
+        M = xrows.shape[0]
+        seqs, hep = self._window("recommend", seqs, hep, M)
+        need = self.recommend_scratch_bytes(M, n, k)
+        held = getattr(self, "_recommend_scratch", None)
+        if held is None or held[0] != (M, n, k):
+            held = ((M, n, k), torch.empty(need, dtype=torch.uint8, device=self.device))
+            self._recommend_scratch = held
+        scratch = held[1]
+        val = torch.empty((M, n), dtype=torch.float32, device=self.device)
+        ids = torch.empty((M, n), dtype=torch.int64, device=self.device)
+        lp = torch.empty((M, n), dtype=torch.float32, device=self.device) if log_probs else None
+        count = torch.empty(M, dtype=torch.int32, device=self.device)
+        st = torch.empty(M, dtype=torch.int32, device=self.device)
+        self._call_null(self.lib.irs_recommend, _ptr(xrows), _ptr(seqs), _ptr(hep), M, n, k, sweep, _ptr(val), _ptr(ids), _ptr(lp),
+                        _ptr(count), _ptr(st), _ptr(scratch), scratch.numel(),
+                        tensors=(xrows, seqs, hep, val, ids, lp, count, st, scratch))
+        return val, ids, lp, count, st
+
+    def recommend_take(self, val: torch.Tensor, ids0: torch.Tensor, n: int, *, seqs: Optional[torch.Tensor] = None,
+                       hep: Optional[torch.Tensor] = None, lse: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """irs_recommend_take, the kernel alone: the first n admissible entries of the caller's ranked lists val / ids0 [M, k] (a
+        list ends at its first negative id).  lse: the rows' (max, sumexp) for the log-probabilities (None: no lp).  Returns
+        (val[M, n], ids0[M, n], lp[M, n] or None, count[M])."""
+        val, ids0 = self._dev(val, torch.float32), self._dev(ids0, torch.int64)
+        if val.dim() != 2 or val.shape != ids0.shape:
+            raise IrsError("recommend_take: val and ids0 [M, k]")
+        M, k = val.shape
+        seqs, hep = self._window("recommend_take", seqs, hep, M)
+        mx = sm = None
+        if lse is not None:
+            mx, sm = self._dev(lse[0], torch.float32), self._dev(lse[1], torch.float32)
+            if mx.numel() != M or sm.numel() != M:
+                raise IrsError("recommend_take: lse is (max[M], sumexp[M])")
+        # (allocated with the shape the caller asked for even where the library is going to refuse it: its message is the answer)
+        o_val = torch.empty((M, max(n, 0)), dtype=torch.float32, device=self.device)
+        o_ids = torch.empty((M, max(n, 0)), dtype=torch.int64, device=self.device)
+        o_lp = torch.empty((M, max(n, 0)), dtype=torch.float32, device=self.device) if lse is not None else None
+        count = torch.empty(M, dtype=torch.int32, device=self.device)
+        self._call_null(self.lib.irs_recommend_take, _ptr(seqs), _ptr(hep), M, _ptr(val), _ptr(ids0), k, _ptr(mx), _ptr(sm), n,
+                        _ptr(o_val), _ptr(o_ids), _ptr(o_lp), _ptr(count),
+                        tensors=(seqs, hep, val, ids0, mx, sm, o_val, o_ids, o_lp, count))
+        return o_val, o_ids, o_lp, count
 
     # ------------------------------------------------------------------ path trace (irs_bind_path_trace)
     def path_trace_scratch_bytes(self, rows: int) -> int:

@@ -126,6 +126,36 @@ class Evaluator(nn.Module):
             rr.append(np.reciprocal(float(ranks[i])))
         return hit, np.array(rr)
 
+    def predict_next(self, seqs, top_k=20, use_h=True):
+        """The list behind get_accuracy_metrics_in_batch (extension; the baselines' predict_next, reference sas.py:357-388): int64
+        [B, top_k] of 1-based ids, best first, 0 where fewer exist.  Row end - 1 of the evaluator (end: the row's last item, the
+        label), and when use_h the prefix seqs[b, :end] left out -- passed as the row's window, hep = end - 1 -- so the label's
+        rank in get_accuracy_metrics_in_batch is its position here plus one.  Exact whatever the prefix hides of the top 100
+        (irs_recommend).  self.last_recommend holds ids, scores, log_probs, count and status.  One device holds the catalog."""
+        hip = self.net._hip
+        if hip.world != 1:
+            raise ValueError("predict_next is not built for an item-sharded catalog")
+        if not 1 <= int(top_k) <= 100:
+            raise ValueError(f"top_k={top_k!r}: 1 to 100 items (the ranked list a slate is taken from holds 100)")
+        dev = seqs.device
+        if dev.type != "cuda" or next(self.net.parameters()).device.type != "cuda":
+            raise ValueError("predict_next runs on the HIP engine only: move the evaluator and its batch to a GPU (there is no "
+                             "CPU fallback in this package)")
+        self.net.eval()
+        B = seqs.size(0)
+        end = self._first_none_zero_index_batch(seqs)
+        b = torch.arange(B, device=dev)
+        xr = self._rows(seqs[:, :-1], b, end - 1)
+        eng = hip.get(B, B)
+        win = hep = None
+        if use_h:
+            win, _ = self.net._pad_to_len(seqs[:, :-1].to(torch.int64))
+            hep = (end - 1).to(torch.int32)
+        val, ids0, lp, count, status = eng.recommend(xr, int(top_k), seqs=win, hep=hep, k=100, sweep=hip.sweep)
+        ids = ids0 + 1  # (-1 behind count: 0, the pad id)
+        self.last_recommend = dict(ids=ids, scores=val, log_probs=lp, count=count, status=status)
+        return ids
+
     def get_grad_in_batch(self, histories, new_seqs, targets, start_pos, l_paths):
         """Step-wise log-probabilities of the path items and of the target along
         the path (reference :162-243).  Returns (t_probs [B,S], p_probs [B,S],

@@ -490,6 +490,46 @@ class IRSNN(nn.Module):
             rr.append(np.reciprocal(float(ranks[i])))
         return hit_count, np.array(rr)
 
+    def predict_next(self, raw, seqs, users, top_k=20, gap_len=20, use_h=True):
+        """The top_k items the model would show each user next (extension; the baselines' predict_next, reference sas.py:357-388):
+        int64 [B, top_k] of 1-based ids, best first, 0 where fewer exist.  It is the list get_accuracy_metrics_in_batch cuts
+        top_k_items from (reference :375-383): row L - gap_len - 2 of the decoder, the raw history `raw` (a list of B arrays /
+        tensors of 1-based ids) left out when use_h, nothing left out otherwise -- the reference filters no window here.  Exact
+        whatever the history hides of the top 100 (irs_recommend).  self.last_recommend holds ids, scores, log_probs, count and
+        status of the call.  `raw` is bound as an exclusion set for the call and unbound afterwards, as
+        get_seq_in_batch(exclude=) does.  One device holds the catalog."""
+        hip = self.net._hip
+        if hip.world != 1:
+            raise ValueError("predict_next is not built for an item-sharded catalog")
+        dev = seqs.device
+        B, L = seqs.shape
+        if not 1 <= int(top_k) <= 100:
+            raise ValueError(f"top_k={top_k!r}: 1 to 100 items (the ranked list a slate is taken from holds 100)")
+        if use_h:
+            if len(raw) != B:
+                raise ValueError(f"raw: {len(raw)} histories for {B} users")
+            longest = max([len(a) for a in raw] + [0])
+            if longest > 4096:
+                raise ValueError(f"raw: a history of {longest} ids, irs_bind_exclusions takes at most 4096 per user")
+        if dev.type != "cuda" or next(self.net.parameters()).device.type != "cuda":
+            raise ValueError("predict_next runs on the HIP engine only: move the network and its batch to a GPU (there is no "
+                             "CPU fallback in this package)")
+        excl = pad_ragged_ids(raw, dev) if use_h else None
+        self.net.eval()
+        pos = torch.full((B,), L - (gap_len + 1) - 1, dtype=torch.int32, device=dev)
+        xr = self.net.decode_rows(seqs.clone(), users, pos)
+        eng = hip.get(B, B)
+        held = eng.bind_exclusions(excl, B) if excl is not None else None
+        try:
+            val, ids0, lp, count, status = eng.recommend(xr, int(top_k), k=100, sweep=hip.sweep)
+        finally:
+            if held is not None:
+                held.record_stream(torch.cuda.current_stream(dev))
+                eng.unbind_exclusions()
+        ids = ids0 + 1  # (-1 behind count: 0, the pad id)
+        self.last_recommend = dict(ids=ids, scores=val, log_probs=lp, count=count, status=status)
+        return ids
+
     REPLAY_CHUNK = 4096  # rows per pass of replay_paths: one decode and one catalog sweep each
 
     def replay_paths(self, seqs, users, paths, gap_len=0):
