@@ -68,7 +68,8 @@ extern "C" {
 
 /* per-row status bits written by the selection kernels */
 #define IRS_ROW_OK 0
-#define IRS_ROW_FALLBACK 1     /* candidate buffers overflowed; row was re-done by the exhaustive exact kernel */
+#define IRS_ROW_FALLBACK 1     /* candidate buffers overflowed; row was re-done by the exhaustive exact kernel
+                                  (dense form, irs_set_topk_dense: more than 1024 items within the filter's error of the k-th) */
 #define IRS_ROW_NO_CANDIDATE 2 /* every one of the k candidates is in the window
                                   (the reference raises IndexError at influentialRS.py:429) */
 #define IRS_ROW_FEWER_THAN_K 4 /* catalog shard has fewer than k items; tail filled with (-inf, -1) */
@@ -1173,6 +1174,20 @@ int irs_get_decoder_gemm_effective(const irs_ctx *ctx); /* the mode that runs (I
 int irs_set_decoder_seq(irs_ctx *ctx, int32_t mode);
 int irs_get_decoder_seq(const irs_ctx *ctx);
 int irs_decoder_seq_last(const irs_ctx *ctx);
+/* Dense form of the swept top-k (small catalogs, many rows).  Where a shard's padded item count fits a row's candidate array
+ * (n_tiles * 32 <= 4096), irs_score_topk[_carry] and the search loops' steps with IRS_SWEEP_BF16, d_pad >= 32 and k <= 256 can run
+ * as three launches instead of five: k_prep_x, ONE bf16 sweep that stores every approximate score of a row into its candidate array
+ * (k_sweep_ring16, image mode), and k_dense_select, one workgroup per row: a bound T from the 256 per-thread maxima, the items with
+ * approx >= T - 2 eps re-scored with the exact chain and ranked.  Results are those of the other routes bit for bit.  Not taken with
+ * IRS_SWEEP_F32 (which stays an independent check), when the log-sum-exp is wanted, or for a fused path step.
+ * On this form nothing is speculative: IRS_ROW_FALLBACK is set only for a row with more than 1024 items within 2 eps of its k-th
+ * approximate score (near-duplicate catalogs), which the selection workgroup redoes exhaustively; a carried call is a plain call.
+ * mode: 0 never, 1 wherever the form is eligible (any row count), 2 (default) where it is eligible and measured ahead -- see
+ * profiles/dense_topk/README.md for where that is.  Environment IRS_TOPK_DENSE=0 / 1 / auto at creation or this call.
+ * irs_topk_dense_last: 1 when the last top-k launch took this form. */
+int irs_set_topk_dense(irs_ctx *ctx, int32_t mode);
+int irs_get_topk_dense(const irs_ctx *ctx);
+int irs_topk_dense_last(const irs_ctx *ctx);
 /* irs_decoder_route_last (tests): the kernel route the last irs_decode took, as int32 fields in this order:
  *   rows_only, small_plan, plan, embed, layer, tail, frag, seq, kv_planes, att_fused, kv_only, x6, npl, nt
  * plan: 0 NONE (full decode), 1 MULTI, 2 SMALL, 3 IN_EMBED; embed: 0 FULL, 1 PACKED, 2 FRAG, 3 FRAG_QKV, 4 SMALL16_QKV, 5 ANY_QKV,

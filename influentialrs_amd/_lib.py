@@ -171,6 +171,9 @@ SIGNATURES = {
     "irs_set_decoder_seq": (c_int32, [c_void_p, c_int32]),
     "irs_get_decoder_seq": (c_int32, [c_void_p]),
     "irs_decoder_seq_last": (c_int32, [c_void_p]),
+    "irs_set_topk_dense": (c_int32, [c_void_p, c_int32]),
+    "irs_get_topk_dense": (c_int32, [c_void_p]),
+    "irs_topk_dense_last": (c_int32, [c_void_p]),
     "irs_decoder_route_last": (c_int32, [c_void_p, POINTER(c_int32), c_int32]),
     "irs_debug_ptr": (c_void_p, [c_void_p, c_int32]),
     "irs_h3_range_bound": (c_float, [c_void_p]),

@@ -97,6 +97,8 @@ extern "C" int irs_create_ex(irs_ctx **out, const irs_dims *dims, const irs_shar
         c->use_attn_h3 = ea ? (strcmp(ea, "h3") == 0) : 1; // (IRS_ATTN_GEMM=f32: float32 K / V rows and the float32-MFMA attention)
         const char *es = getenv("IRS_DECODER_SEQ");
         c->use_seq = es ? (strcmp(es, "auto") == 0 ? 2 : (atoi(es) != 0 ? 1 : 0)) : 2;
+        const char *ed = getenv("IRS_TOPK_DENSE");
+        c->use_dense = ed ? (strcmp(ed, "auto") == 0 ? 2 : (atoi(ed) != 0 ? 1 : 0)) : 2;
         const char *ec = getenv("IRS_THR_CARRY"); // steps between two pre-pass + threshold selections inside a path search (0 / 1: every step)
         c->carry_period = ec ? atoi(ec) : 8;
         if (c->carry_period < 0 || c->carry_period > 1024) c->carry_period = 8;
@@ -408,6 +410,17 @@ extern "C" int irs_set_decoder_seq(irs_ctx *ctx, int32_t mode) {
 }
 extern "C" int irs_get_decoder_seq(const irs_ctx *ctx) { return ctx ? ctx->use_seq : IRS_E_INVALID; }
 extern "C" int irs_decoder_seq_last(const irs_ctx *ctx) { return ctx ? (ctx->seq_last ? 1 : 0) : IRS_E_INVALID; }
+extern "C" int irs_set_topk_dense(irs_ctx *ctx, int32_t mode) {
+    if (!ctx) return IRS_E_INVALID;
+    if (mode < 0 || mode > 2) IRS_FAIL(ctx, IRS_E_INVALID, "top-k dense mode %d (0 off, 1 on, 2 auto)", mode);
+    if (ctx->use_dense != mode) {
+        ctx->use_dense = mode;
+        irs_drop_graphs(ctx); // (a captured step bakes the form in: like every route switch, a change drops the captured steps)
+    }
+    return IRS_OK;
+}
+extern "C" int irs_get_topk_dense(const irs_ctx *ctx) { return ctx ? ctx->use_dense : IRS_E_INVALID; }
+extern "C" int irs_topk_dense_last(const irs_ctx *ctx) { return ctx ? (ctx->dense_last ? 1 : 0) : IRS_E_INVALID; }
 extern "C" int irs_decoder_route_last(const irs_ctx *ctx, int32_t *out, int32_t n) {
     if (!ctx || !out || n < 0) return IRS_E_INVALID;
     if (ctx->route_n == 0) return IRS_E_STATE;

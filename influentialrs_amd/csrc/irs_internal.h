@@ -393,6 +393,8 @@ struct irs_ctx {
     int lse_slots;
     float *ref_tmp;     // [m_pad]
     int thr_valid, thr_M, thr_k, thr_age, carry_period; // carried emission thresholds (irs_launch_topk)
+    int use_dense;    // dense form of the swept top-k on small catalogs (irs_set_topk_dense): 0 never, 1 wherever eligible, 2 auto (default)
+    bool dense_last;  // the last irs_launch_topk took it
     unsigned int *fb_count;        // [1] rows recorded for the cooperative exhaustive fallback
     int32_t *fb_list;              // [max_rows]
     unsigned long long *exh_keys;  // [EXH_FB_MAX][strips][k] per-strip lists (null on small shards)

@@ -17,6 +17,8 @@
 //   5. k_refine      A_k = k-th largest emitted approx score; survivors (>= A_k - 2 eps) are
 //                    re-scored with the exact chain and sorted by (score desc, id asc)
 //   6. k_exhaustive  rows whose buffers overflowed are redone exactly over the whole shard
+// Small shards (n_tiles * 32 <= 4096) with many rows take a dense form of 2-5 instead (TOPK_DENSE): ONE sweep stores every
+// approximate score of a row into its candidate array (k_sweep_ring16, MODE_IMAGE), k_dense_select bounds, re-scores and ranks.
 // With |approx - exact| <= eps every member of the exact top-k survives 4 and 5,
 // so the result equals the exhaustive exact top-k bit for bit ("Why the
 // bf16 filter is exact").  The fp32 sweep (IRS_SWEEP_F32) uses v_mfma_f32_32x32x2_f32,
@@ -41,6 +43,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 #define MODE_LSE 4
 #define MODE_CEGRAD 5 // DENSE's orientation; writes scale * (softmax - onehot(label)) instead of the logits
 #define MODE_TRACE 6  // COUNT against (ref_score, ref_id) and LSE's (max, sum exp) partials, both from the chain-order scores
+#define MODE_IMAGE 7  // k_sweep_ring16 alone: every approximate score, as the accumulators hold it, into a per-row float image (dense / ld)
 
 struct SweepArgs {
     // operands
@@ -680,7 +683,7 @@ static constexpr size_t ring16_lds_bytes(int KS, int RT16, int NW, int NSLOT) {
 
 template <int KS, int RT16, int NW, int NSLOT, int MODE, int DBG = 0>
 __global__ void __launch_bounds__(NW * 64, 2) k_sweep_ring16(SweepArgs a) {
-    static_assert(MODE == MODE_PRE || MODE == MODE_EMIT, "top-k modes only");
+    static_assert(MODE == MODE_PRE || MODE == MODE_EMIT || MODE == MODE_IMAGE, "top-k modes only");
     static_assert(KS >= 2 && KS % 2 == 0 && RT16 % 2 == 0, "32-wide k-steps, whole 32-row tiles");
     constexpr int KS2 = KS / 2;              // k-steps of 32 per sub-tile
     constexpr int RT = RT16 / 2;             // 32-row tiles per wave (a.UT, a.xb and a.thr count those)
@@ -727,8 +730,11 @@ __global__ void __launch_bounds__(NW * 64, 2) k_sweep_ring16(SweepArgs a) {
             xr[u][k2] = live ? a.xb[((size_t)ut * KS + 2 * k2 + (q >> 1)) * 64 + (q & 1) * 32 + (u & 1) * 16 + c]
                              : make_uint4(0u, 0u, 0u, 0u);
         if (MODE == MODE_PRE) aux[u] = -INFINITY;
-        else aux[u] = live ? fmaxf(a.thr[ut * 32 + (u & 1) * 16 + c], -3.0e38f) : INFINITY;
+        else if (MODE == MODE_EMIT) aux[u] = live ? fmaxf(a.thr[ut * 32 + (u & 1) * 16 + c], -3.0e38f) : INFINITY;
+        else aux[u] = 0.f;
     }
+    // IMAGE: row c of row tile 0, items 4q .. 4q+3 of the image's first tile; row tiles beyond the padded row count store nothing
+    float *const img = MODE == MODE_IMAGE ? a.dense + (size_t)(ut0 * 32 + c) * a.ld + 4 * q : nullptr;
     __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0), seen by the compiler's counter model (see k_sweep_ring)
     auto issue = [&](int s) __attribute__((always_inline)) { // DMA of step s into slot s % NSLOT
         const int slot = s % NSLOT;
@@ -820,12 +826,22 @@ __global__ void __launch_bounds__(NW * 64, 2) k_sweep_ring16(SweepArgs a) {
     }
     int gcount = 0, gw = strip * 4; // PRE: tiles folded into the current group; group index (k_sweep_bf16's wave id)
 
-    // test (EMIT) or fold (PRE) of row tile U of accumulator set Y
+    // IMAGE: first item of the pending sub-tile (-1: there is none yet).  The stores ride the test slots; they need no count of
+    // their own in the ring's waits: vmcnt(N) leaves at most N operations of ANY kind in flight and the DMAs retire in issue
+    // order among themselves, so "all but the youngest N DMAs have landed" holds with stores in flight as well.
+    int pcol = -1;
+    // test (EMIT), fold (PRE) or store (IMAGE: one 16-byte store per lane, bias included through the C operand, pad items -inf) of
+    // row tile U of accumulator set Y
 #define R16_CHECK_(Y_, U_)                                                                                      \
     {                                                                                                           \
-        const float m_ = vmax2(vmax3(acc[Y_][U_][0], acc[Y_][U_][1], acc[Y_][U_][2]), acc[Y_][U_][3]);          \
-        if (MODE == MODE_PRE) aux[U_] = vmax2(aux[U_], m_);                                                     \
-        else hm[U_] = __ballot(m_ >= aux[U_]);                                                                  \
+        if (MODE == MODE_IMAGE) {                                                                               \
+            if (pcol >= 0 && ut0 + ((U_) >> 1) < a.UT)                                                          \
+                *reinterpret_cast<f32x4 *>(img + (size_t)((U_) * 16) * a.ld + pcol) = acc[Y_][U_];              \
+        } else {                                                                                                \
+            const float m_ = vmax2(vmax3(acc[Y_][U_][0], acc[Y_][U_][1], acc[Y_][U_][2]), acc[Y_][U_][3]);      \
+            if (MODE == MODE_PRE) aux[U_] = vmax2(aux[U_], m_);                                                 \
+            else hm[U_] = __ballot(m_ >= aux[U_]);                                                              \
+        }                                                                                                       \
     }
     // Hits of the pending sub-tile (accumulator set Y = sub-tile Y of step sy).  What in-kernel stamps and two failed
     // forms established: (1) per row tile AND register a compare, a branch and a ballot-compacted append (the 32x32x16
@@ -923,6 +939,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_sweep_ring16(SweepArgs a) {
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             // accumulator set `sub` is multiplied; set sub ^ 1 (the previous sub-tile) is tested between the MFMAs
+            if (MODE == MODE_IMAGE) pcol = sub == 1 ? (tfirst + s * ts) * 32 : s > 0 ? (tfirst + (s - 1) * ts) * 32 + 16 : -1;
 #pragma unroll
             for (int k2 = 0; k2 < KS2; ++k2) {
                 const int j = sub * KS2 + k2; // compile-time after unrolling
@@ -994,7 +1011,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_sweep_ring16(SweepArgs a) {
                     dbg_t[2] += th1 - th0;
                     if (th1 - th0 > 100) ++dbg_n;
                 }
-            } else if (sub == 0 && s > 0)
+            } else if (MODE == MODE_PRE && sub == 0 && s > 0)
                 pre_group_end(s - 1); // tile s - 1 is folded completely (its second sub-tile rode this phase)
         }
         all_landed(); // the reads of the next step's first k-steps were requested PD k-steps ago
@@ -1009,13 +1026,14 @@ __global__ void __launch_bounds__(NW * 64, 2) k_sweep_ring16(SweepArgs a) {
         o[5] = (unsigned long long)nstep;
     }
     // the last sub-tile (set 1 of step nstep - 1) has not been tested yet
+    if (MODE == MODE_IMAGE) pcol = (tfirst + (nstep - 1) * ts) * 32 + 16;
 #pragma unroll
     for (int u = 0; u < RT16; ++u) R16_CHECK_(1, u)
     if (MODE == MODE_EMIT) {
         handle(std::integral_constant<int, 1>{}, nstep - 1);
         flush_raw();
         emit_flush(a, eq, lane);
-    } else {
+    } else if (MODE == MODE_PRE) {
         pre_group_end(nstep - 1);
         for (; gw < strip * 4 + 4; ++gw) // the last strip may hold fewer than four groups: the selection reads all of them
 #pragma unroll
@@ -2362,6 +2380,119 @@ __global__ void __launch_bounds__(256) k_topk_direct(const float *__restrict__ x
 #endif
 }
 
+// Dense form of the swept top-k (small catalogs, many rows), selection: one workgroup per row over the row's image of
+// approximate scores (k_sweep_ring16<.., MODE_IMAGE>: img[row][ld], ld = n_tiles * 32 <= DIRECT_MAX_ITEMS).  k_topk_direct's
+// front on approximate keys: thread t holds items 1024 q + 4 t + e; the k-th largest of the 256 per-thread maxima is a bound
+// T <= a_(k), the k-th largest approximate score.  k items have approx >= a_(k), so the exact k-th score is >= a_(k) - eps and
+// every item of the exact top-k has approx >= a_(k) - 2 eps >= T - 2 eps: those survive (all items where n_local < 4k: some of
+// the first k threads would hold no key).  k_refine's tail on the survivors: exact chain, order by rank counting.  Nothing is
+// speculative; only a row with more than IRS_REFINE_CAP survivors (thousands of items within 2 eps of the k-th: near-duplicate
+// catalogs) is redone exhaustively, here, and carries IRS_ROW_FALLBACK.
+__global__ void __launch_bounds__(256) k_dense_select(const float *__restrict__ x, int d, const float *__restrict__ W,
+                                                      const float *__restrict__ bias, const float *__restrict__ img, int ld,
+                                                      const float *__restrict__ eps, int n_local, int64_t item_lo, int k,
+                                                      float *__restrict__ val, int64_t *__restrict__ ids,
+                                                      int32_t *__restrict__ status) {
+    static_assert(IRS_REFINE_CAP + 2 <= EXH_BUF, "the survivors share the exhaustive path's key buffer");
+    __shared__ __attribute__((aligned(16))) unsigned long long rkeys[EXH_BUF];
+    __shared__ __attribute__((aligned(16))) unsigned long long tmax[256];
+    __shared__ float xs[256];
+    __shared__ unsigned int wsum[4];
+    __shared__ unsigned int s_thr;
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *ar = img + (size_t)row * ld;
+    constexpr int KPT = DIRECT_MAX_ITEMS / 256;
+    float sc[KPT]; // approximate scores of this thread's items (pad items of the last tile: -inf, and never kept)
+#pragma unroll
+    for (int q = 0; q < KPT / 4; ++q) {
+        const int j = q * 1024 + 4 * tid; // (ld is a multiple of 32: a float4 lies inside the image or outside)
+        float4 v = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        if (j < ld) v = *reinterpret_cast<const float4 *>(ar + j);
+        sc[4 * q + 0] = v.x, sc[4 * q + 1] = v.y, sc[4 * q + 2] = v.z, sc[4 * q + 3] = v.w;
+    }
+    for (int i = tid; i < d; i += 256) xs[i] = x[(size_t)row * d + i];
+    float thr = -INFINITY;
+    if (n_local >= 4 * k) {
+        unsigned long long mx = 0ull;
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) {
+            const int j = (i >> 2) * 1024 + 4 * tid + (i & 3);
+            const unsigned long long key = j < n_local ? ((unsigned long long)irs_fkey(sc[i]) << 32) | (0xFFFFFFFFu - (unsigned int)j) : 0ull;
+            mx = key > mx ? key : mx;
+        }
+        tmax[tid] = mx;
+        __syncthreads();
+        int above = 0;
+        const ulonglong2 *t2 = reinterpret_cast<const ulonglong2 *>(tmax);
+#pragma unroll 8
+        for (int i = 0; i < 128; ++i) {
+            const ulonglong2 v = t2[i];
+            above += (v.x > mx) + (v.y > mx);
+        }
+        if (above == k - 1) s_thr = (unsigned int)(mx >> 32);
+        __syncthreads();
+        thr = irs_unkey(s_thr) - 2.0f * eps[row];
+    } else
+        __syncthreads();
+    // survivors: !(score < thr) keeps everything when the bound is not a number
+    unsigned int keep = 0u;
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+        const int j = (i >> 2) * 1024 + 4 * tid + (i & 3);
+        if (j < n_local && !(sc[i] < thr)) keep |= 1u << i;
+    }
+    const int mine = __popc(keep);
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    unsigned int slot = incl - mine;
+    for (int w = 0; w < wave; ++w) slot += wsum[w];
+    const unsigned int nr = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (nr > IRS_REFINE_CAP) {
+        if (tid == 0) status[row] |= IRS_ROW_FALLBACK;
+        exhaustive_row(x, d, W, bias, n_local, item_lo, k, row, val, ids, status, rkeys, xs, false);
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < KPT; ++i)
+        if ((keep >> i) & 1u) rkeys[slot++] = (unsigned long long)((i >> 2) * 1024 + 4 * tid + (i & 3));
+    __syncthreads();
+    // exact re-score
+    for (int i = tid; i < (int)nr; i += 256) {
+        const unsigned int j = (unsigned int)rkeys[i];
+        const float e = irs_chain(xs, W + (size_t)j * d, bias[j], d);
+        rkeys[i] = ((unsigned long long)irs_fkey(e) << 32) | (0xFFFFFFFFu - j);
+    }
+    if ((nr & 1) && tid == 0) rkeys[nr] = 0ull; // the rank loop reads pairs
+    __syncthreads();
+    // order by rank counting (keys distinct): winners go straight to their slots
+    {
+        const ulonglong2 *r2 = reinterpret_cast<const ulonglong2 *>(rkeys);
+        for (int i = tid; i < (int)nr; i += 256) {
+            const unsigned long long me = rkeys[i];
+            int above = 0;
+            for (int j = 0; j < (int)(nr + 1) / 2; ++j) {
+                const ulonglong2 v = r2[j];
+                above += (v.x > me) + (v.y > me);
+            }
+            if (above < k) {
+                val[(size_t)row * k + above] = irs_unkey((unsigned int)(me >> 32));
+                ids[(size_t)row * k + above] = item_lo + (int64_t)(0xFFFFFFFFu - (unsigned int)me);
+            }
+        }
+        for (int i = (int)nr + tid; i < k; i += 256) {
+            val[(size_t)row * k + i] = -INFINITY;
+            ids[(size_t)row * k + i] = -1;
+        }
+    }
+    if (tid == 0 && (int)nr < k) status[row] |= IRS_ROW_FEWER_THAN_K;
+}
+
 __global__ void __launch_bounds__(256) k_exhaustive(const float *__restrict__ x, int d, const float *__restrict__ W,
                                                     const float *__restrict__ bias, int64_t n_local, int64_t item_lo,
                                                     int k, int only_flagged, float *__restrict__ val,
@@ -2547,7 +2678,7 @@ static void ring_emit_grid(SweepArgs &a, int slots) {
 template <auto KERN, int NW, int MODE>
 static void launch_ring_kernel(SweepArgs &a, size_t lds, hipStream_t s) {
     const int slots = ring_slots<KERN>(NW * 64, lds);
-    if (MODE == MODE_EMIT) ring_emit_grid(a, slots);
+    if (MODE == MODE_EMIT || MODE == MODE_IMAGE) ring_emit_grid(a, slots);
     else a.tiles_per_wg = 0;
     hipLaunchKernelGGL(KERN, dim3(((a.n_strips + 7) / 8) * 8 * a.n_ublocks), dim3(NW * 64), lds, s, a);
 }
@@ -2603,6 +2734,19 @@ static int launch_sweep_bf16(irs_ctx *ctx, SweepArgs &a, hipStream_t s) {
         default: IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "unsupported d_pad %d", ctx->d_pad);
         }
 #undef L_
+    }
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
+// the image sweep of the dense top-k form (a.dense / a.ld set): the 16x16x32 ring at any row count (KS >= 2)
+static int launch_sweep_image(irs_ctx *ctx, SweepArgs &a, hipStream_t s) {
+    switch (ctx->KS) {
+    case 2: launch_ring16<2, 4, 4, MODE_IMAGE>(a, s); break;
+    case 4: launch_ring16<4, 4, 4, MODE_IMAGE>(a, s); break;
+    case 8: launch_ring16<8, 4, 4, MODE_IMAGE>(a, s); break;
+    case 16: launch_ring16<16, 4, 4, MODE_IMAGE>(a, s); break;
+    default: IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "unsupported d_pad %d", ctx->d_pad);
     }
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
@@ -2760,7 +2904,15 @@ enum TopkForm {
     TOPK_DIRECT1, // direct, one launch (<= 32 rows): scoring and selection in one kernel
     TOPK_DIRECT2, // direct, two launches: scoring, then selection with one workgroup per row
     TOPK_SWEPT,   // prep, pre-pass + threshold selection, emission sweep, refine (+ cooperative fallback)
+    TOPK_DENSE,   // prep, image sweep (every approximate score of a small catalog), selection + refine with one workgroup per row
 };
+// The dense form needs: the bf16 filter (IRS_SWEEP_F32 stays the independent check on its own route), a row's image inside its
+// candidate array, the 16x16x32 ring (KS >= 2), k within k_dense_select's 256 maxima, no log-sum-exp and no fused path step.
+static_assert(IRS_CAND_CAP == DIRECT_MAX_ITEMS && DIRECT_MAX_ITEMS == 16 * 256, "k_dense_select: 16 items per thread; the float image fits the row's candidate array");
+#define DENSE_AUTO_MIN_ROWS 1025 // auto (irs_set_topk_dense mode 2): above the direct forms, whose rows it leaves alone (profiles/dense_topk: it measured ahead from 256 rows up)
+static bool topk_dense_ok(const irs_ctx *ctx, int k, int sweep, bool want_lse, bool fused_step) {
+    return sweep == IRS_SWEEP_BF16 && (int64_t)ctx->n_tiles * 32 <= IRS_CAND_CAP && ctx->KS >= 2 && k <= 256 && !want_lse && !fused_step;
+}
 struct TopkPlan {
     TopkForm form;
     bool fused_lse; // swept: the emission sweep runs on the float32 catalog and accumulates the log-sum-exp as well
@@ -2773,8 +2925,18 @@ struct TopkPlan {
     int r_sel;      // rank of the sampled group maximum that becomes the emission threshold
 };
 
-static TopkPlan topk_plan(const irs_ctx *ctx, const float *xrows, int M, int k, int sweep, bool want_lse, int carry) {
+static TopkPlan topk_plan(const irs_ctx *ctx, const float *xrows, int M, int k, int sweep, bool want_lse, int carry, bool fused_step) {
     TopkPlan p{};
+    // use_dense: 0 never, 1 wherever the form is eligible, 2 (default) where it is eligible and measured ahead.  It reads and
+    // writes none of the carried-threshold state: a carried call on it is a plain call.
+    // (auto, k <= 128 only: the k-th largest of 256 per-thread maxima keeps about n (1 - (1 - k / 256)^(256 / n)) items -- 140 of
+    //  3415 at k = 100, 370 at k = 200, and every item at k = 256, which would send each row down the exhaustive path)
+    if (topk_dense_ok(ctx, k, sweep, want_lse, fused_step) &&
+        (ctx->use_dense == 1 ||
+         (ctx->use_dense == 2 && M >= DENSE_AUTO_MIN_ROWS && k <= 128 && !irs_topk_is_direct(ctx, M, k)))) {
+        p.form = TOPK_DENSE;
+        return p;
+    }
     if (irs_topk_is_direct(ctx, M, k)) { // latency path on a small shard: no fallback needed
         p.form = M <= 32 ? TOPK_DIRECT1 : TOPK_DIRECT2;
         p.lse_after = want_lse;
@@ -2942,15 +3104,45 @@ static int topk_refine(irs_ctx *ctx, const TopkPlan &p, const float *xrows, int 
     return IRS_OK;
 }
 
+// dense form: k_prep_x, the image sweep into the rows' candidate arrays, k_dense_select.  The sweep reports EMIT's work (the
+// same matrix product over the whole shard) to the profiling families the emission sweep reports to.
+static int topk_dense(irs_ctx *ctx, const TopkPlan &p, const float *xrows, int M, int k, float *val, int64_t *ids0, int32_t *status,
+                      hipStream_t s) {
+    SweepArgs a;
+    sweep_common(ctx, a, xrows, M);
+    int rc;
+    if ((rc = topk_prep(ctx, p, xrows, M, a.M_pad, IRS_SWEEP_BF16, status, s))) return rc;
+    a.dense = reinterpret_cast<float *>(ctx->cand);
+    a.ld = (int64_t)ctx->n_tiles * 32;
+    sweep_decompose(a, 0, ctx->n_tiles, (a.UT + 7) / 8, 0);
+    const double flops = 2.0 * ctx->dims.d * (double)M * (double)ctx->n_local;
+    const double bytes = (double)ctx->n_tiles * 32.0 * ctx->d_pad * 2.0;
+    irs_prof_begin(ctx, IRS_PROF_SWEEP, s);
+    irs_prof_begin(ctx, IRS_PROF_SWEEP_EMIT, s); // (one family is enabled at a time)
+    rc = launch_sweep_image(ctx, a, s);
+    irs_prof_end(ctx, IRS_PROF_SWEEP, s, flops, bytes);
+    irs_prof_end(ctx, IRS_PROF_SWEEP_EMIT, s, flops, bytes);
+    if (rc) return rc;
+    irs_prof_begin(ctx, IRS_PROF_REFINE, s);
+    hipLaunchKernelGGL(k_dense_select, dim3(M), dim3(256), 0, s, xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b, a.dense, (int)a.ld,
+                       ctx->eps, (int)ctx->n_local, ctx->shard.item_lo, k, val, ids0, status);
+    irs_prof_end(ctx, IRS_PROF_REFINE, s, 0.0, 0.0);
+    IRS_CHECK_HIP(ctx, hipGetLastError());
+    return IRS_OK;
+}
+
 // lse_max / lse_sum non-null: the rows' log-sum-exp over the shard as well (beam search).  On the swept path with the
 // bf16 filter it comes out of the SAME pass as the candidates: pre-pass and threshold on the bf16 catalog sample as
 // usual, then one sweep of the float32 catalog that emits against the threshold and accumulates (max, sum exp).
 int irs_launch_topk(irs_ctx *ctx, const float *xrows, int M, int k, int sweep, float *val, int64_t *ids0,
                     int32_t *status, hipStream_t s, const irs_path_args *path, float *lse_max, float *lse_sum, int carry) {
-    const TopkPlan p = topk_plan(ctx, xrows, M, k, sweep, lse_max != nullptr, carry);
+    const TopkPlan p = topk_plan(ctx, xrows, M, k, sweep, lse_max != nullptr, carry, path != nullptr);
     if (path && p.form == TOPK_SWEPT) IRS_FAIL(ctx, IRS_E_STATE, "fused path step needs the direct top-k");
+    ctx->dense_last = p.form == TOPK_DENSE;
     int rc;
-    if (p.form != TOPK_SWEPT) {
+    if (p.form == TOPK_DENSE) {
+        if ((rc = topk_dense(ctx, p, xrows, M, k, val, ids0, status, s))) return rc;
+    } else if (p.form != TOPK_SWEPT) {
         if ((rc = topk_direct(ctx, p, xrows, M, k, val, ids0, status, path, s))) return rc;
     } else {
         SweepArgs a;

@@ -1309,6 +1309,21 @@ class Engine:
         return bool(self.lib.irs_decoder_seq_last(self.h))
 
     @property
+    def topk_dense(self) -> int:
+        """Dense form of the swept top-k on small catalogs (irs_set_topk_dense, include/irs_hip.h): 0 never, 1 wherever the form
+        is eligible, 2 auto (default).  The setter takes False / True / None (= auto) or the numbers."""
+        return int(self.lib.irs_get_topk_dense(self.h))
+
+    @topk_dense.setter
+    def topk_dense(self, mode):
+        self._check(self.lib.irs_set_topk_dense(self.h, 2 if mode is None else int(mode)))
+
+    @property
+    def topk_dense_last(self) -> bool:
+        """True when the last top-k launch (score_topk, or the last step of a search loop run without a graph) took the dense form."""
+        return bool(self.lib.irs_topk_dense_last(self.h))
+
+    @property
     def decoder_route_last(self) -> Dict[str, object]:
         """(tests) The kernel route the last decode took (irs_decoder_route_last): plan / embed / layer / tail as their enum
         names (_lib.ROUTE_NAMES), the flags as bools, npl / nt as ints."""
