@@ -1204,6 +1204,7 @@ void *irs_debug_ptr(const irs_ctx *ctx, int32_t which);
  * weights (embedded tokens, LayerNorm outputs, hidden activations, V rows, the weights themselves) and keeps half the range as
  * margin: a model whose bound is 32752 or more runs IRS_GEMM_X6 (no range limit) wherever IRS_GEMM_H3 is selected, with float32
  * V rows -- irs_get_decoder_gemm_effective reports the mode that RUNS (irs_get_decoder_gemm the selected one).  irs_h3_range_bound returns the bound (-1 before finalisation).
+ * A NaN or infinite weight makes the bound infinite; the split-bf16 kernels then return the NaN rows the float32 kernels return.
  * (The reference has no counterpart: model/influentialRS.py:67-74 multiplies in float32 throughout.) */
 float irs_h3_range_bound(const irs_ctx *ctx);
 

@@ -1569,12 +1569,20 @@ __global__ void __launch_bounds__(256) k_pack_x6(const float *__restrict__ Wo, c
         float v = W ? W[(size_t)n * ld + k] : 0.f;
         unsigned int bits = 0;
         if constexpr (NPL == 3) {
+            // An infinite weight goes into the LAST plane alone, which the kernel multiplies with the activation's leading plane
+            // only: inf x keeps the sign of x, as in float32.  Split like a finite value it is (inf, NaN, NaN), and the leading
+            // plane would also meet the activation's residual planes, whose signs are arbitrary (inf - inf): every product NaN,
+            // which the relu (fmaxf) then turns into 0 -- finite rows from a model the float32 kernels answer with NaN.
+            if ((__float_as_uint(v) & 0x7FFFFFFFu) == 0x7F800000u) {
+                bits = p == 2 ? __float_as_uint(v) >> 16 : 0u;
+            } else {
 #pragma unroll
-            for (int q = 0; q <= p; ++q) { // plane q = bf16(v - the planes before it), round to nearest even
-                unsigned int u = __float_as_uint(v);
-                u += 0x7FFFu + ((u >> 16) & 1u);
-                bits = u >> 16;
-                v -= __uint_as_float(bits << 16);
+                for (int q = 0; q <= p; ++q) { // plane q = bf16(v - the planes before it), round to nearest even
+                    unsigned int u = __float_as_uint(v);
+                    u += 0x7FFFu + ((u >> 16) & 1u);
+                    bits = u >> 16;
+                    v -= __uint_as_float(bits << 16);
+                }
             }
         } else { // float16 planes of 2^8 v: h = f16(v), l = f16(v - h), round to nearest even (the conversion instruction's mode)
             v *= x6_wscale(2);
@@ -6436,8 +6444,13 @@ int irs_launch_pack_x6(irs_ctx *ctx, hipStream_t s) {
 // Non-negative floats order like their bit patterns: atomicMax on the bits.
 __global__ void __launch_bounds__(256) k_absmax(const float *__restrict__ p, size_t n, unsigned int *__restrict__ out) {
     float m = 0.f;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) m = fmaxf(m, fabsf(p[i]));
-    if (!(m == m)) m = INFINITY; // a NaN weight fails the bound
+    bool nan = false; // (fmaxf returns its other operand for a NaN: the maximum alone would drop it)
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const float v = p[i];
+        nan |= v != v;
+        m = fmaxf(m, fabsf(v));
+    }
+    if (nan) m = INFINITY; // a NaN weight fails the bound
     for (int o = 32; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
 }
