@@ -590,6 +590,58 @@ size_t irs_exclusion_scratch_bytes(const irs_ctx *ctx, int32_t users, int32_t n_
 int irs_bind_exclusions(irs_ctx *ctx, const int64_t *dev_excl_ids0, int32_t users, int32_t n_excl, int32_t no_repeat,
                         void *dev_scratch, size_t bytes, void *stream);
 
+/* ---- offer set: search and recommend inside a bound subset of the catalog (opt-in; BUILD-DEFINED: the reference always offers
+ *      the whole catalog) -------------------------------------------------------------------------------------------------
+ * An OFFER SET is a strictly ascending array of C distinct 0-based item ids, 1 <= C <= n_item, bound to a context and shared
+ * by all rows.  While it is bound, "the catalog" reads "the set" wherever a search or a slate decides what to OFFER:
+ *   - the ranked list a step of irs_generate_paths[_until] / irs_beam_search[_until] or a slate of irs_recommend starts from
+ *     is the best k items of the set in the library's total order (irs_fkey of the score descending, then id ascending);
+ *   - its scores are the exact float32 chain (bias-seeded, k-ascending fma): bit for bit irs_score_gather's value for that
+ *     row and item (one corner: a chain that ends at exactly -0 is returned as +0; the order folds the two anyway);
+ *   - a list with C < k ends in (-inf, -1) and carries IRS_ROW_FEWER_THAN_K, which every consumer already reads as "the
+ *     whole catalog was shown";
+ *   - exact candidates (irs_bind_survivor_scratch), irs_recommend's repair and irs_topk_ensure_survivors repair a starved
+ *     row FROM THE SET; irs_recommend's count is the number of admissible items of the set, cut at n;
+ *   - the arrival rule (irs_set_arrival_rule, irs_arrival_offer) never offers a target that is not in the set, exactly like
+ *     an excluded one; a caller who wants the target offerable puts it in the set.
+ * What describes the user's MODEL stays a statement about the whole catalog: log-probabilities (irs_recommend's out_lp, the
+ * traces' lp_item / lp_target, the lookahead's), the log-sum-exp behind a beam's cumulative score, rank_target of the two
+ * traces, and the values the arrival rule compares.  The set restricts offers, not the softmax.  Guide, lookahead,
+ * exclusions, no_repeat, both traces, both _until loops and long windows read the list and need nothing else.
+ * irs_path_step, irs_beam_step[_until|_linked], irs_recommend_take and the lookahead kernels alone are kernels on the
+ * caller's lists: they do not look at the binding.
+ *  dev_ids0  int64 [n_ids].  The binding enqueues ONE launch that copies it into the scratch: an entry outside
+ *            [0, n_item) or not greater than its predecessor in the caller's array becomes a HOLE (-1), and the number of
+ *            holes goes to int32 word 0 of the scratch.  That launch compares integers only, and no later kernel indexes
+ *            project.* with anything but a sanitised id: a hole is never scored into a list and never offered.  A set with
+ *            holes is not a valid set (its sanitised ids need not ascend): read word 0 once after binding and rebind a
+ *            repaired array if it is not 0.  The caller's array may be freed once the launch has run.
+ *  dev_scratch  caller-owned, 16-byte aligned, >= irs_offer_set_scratch_bytes(n_ids, rows) = 256 + 8 C_pad (rounded up to
+ *            256) + 4 rows C_pad bytes, C_pad = n_ids rounded up to 64: the header, the sanitised ids, and the float32
+ *            scores of one PASS of `rows` rows.  The binding takes rows = what `bytes` holds, at most max_rows.  It must stay
+ *            valid, and untouched, until the unbind.  Nothing of project.* is copied: the kernels read the weights where
+ *            they lie, so an in-place weight update followed by irs_finalize_weights needs no rebinding.
+ * irs_bind_offer_set(ctx, NULL, 0, NULL, 0) unbinds.  A second bind replaces the first.  Bind and unbind drop the
+ * captured steps of the context.  Refused before any launch: world != 1 -> IRS_E_UNSUPPORTED (the sharded loops return it too
+ * should a binding exist); an array without n_ids >= 1, n_ids outside [1, n_item], a scratch that is NULL, too small for one
+ * row or not 16-byte aligned -> IRS_E_INVALID.  While bound, a loop or irs_recommend call with more rows (B; B * W) than
+ * one pass holds returns IRS_E_INVALID before any launch, and the route where one workgroup ranks and steps a row is not
+ * taken.  With nothing bound every entry point launches exactly what it launched before offer sets existed.
+ * irs_score_topk_offer is the ranking alone: dev_val / dev_ids0 [M, k] and dev_status [M] in irs_score_topk's format, k in
+ * [1, max_k], M in [1, max_rows]; it walks M in passes of the bound rows (two launches per pass: the scores on float32 MFMAs,
+ * one selection workgroup per row).  No float atomics: two identical calls give identical bits.  IRS_E_STATE with no set
+ * bound.
+ * Neither entry point takes a stream, like irs_recommend: the work is enqueued on the null stream and the call returns without
+ * waiting, so the scratch and the outputs are complete in null-stream order.  Blocking streams are ordered against it by the
+ * runtime; a non-blocking stream needs an event on either side; not for use inside a stream capture.  Inside the loops the
+ * same launchers run on the loop's stream, captured or not.
+ * irs_score_topk_offer checks its arguments before the context's readiness: a NULL row pointer, M outside [1, max_rows], k
+ * outside [1, max_k] or a NULL output -> IRS_E_INVALID; then weights / workspace, then the binding -> IRS_E_STATE. */
+size_t irs_offer_set_scratch_bytes(const irs_ctx *ctx, int64_t n_ids, int32_t rows); /* 0 for invalid arguments */
+int irs_bind_offer_set(irs_ctx *ctx, const int64_t *dev_ids0, int64_t n_ids, void *dev_scratch, size_t bytes);
+int irs_score_topk_offer(irs_ctx *ctx, const float *dev_xrows, int32_t M, int32_t k, float *dev_val, int64_t *dev_ids0,
+                         int32_t *dev_status);
+
 /* ---- recommend: the exact top-n unseen items of every row (opt-in; replaces sort + history filter + cut of top_k_items,
  *      IRSNN.get_accuracy_metrics_in_batch, influentialRS.py:375-383; the baselines' predict_next(seqs, users, top_k, use_h),
  *      sas.py:357-388; the list Rec2Inf's get_path is built on, main_baselines.py:104) ---------------------------------------
@@ -618,9 +670,11 @@ int irs_bind_exclusions(irs_ctx *ctx, const int64_t *dev_excl_ids0, int32_t user
  *   repaired rows; a row with fewer than n admissible items in the whole catalog is reported through out_count, not by a
  *   status bit.
  *   Context state: it counts as one irs_score_topk_lse call of the same rows and nothing more.  It drops no captured step and
- *   reads and writes no search binding except the exclusion set; no search option refuses it (guide, lookahead, path trace, beam
- *   trace, arrival rule, survivor scratch).  Nothing is allocated, irs_workspace_bytes does not change.  No float atomics: two
- *   identical calls give identical bits in val, ids0, count and status; lp inherits the unordered float32 sum of irs_score_lse.
+ *   reads and writes no search binding except the exclusion set and a bound offer set (irs_bind_offer_set: "the whole catalog"
+ *   then reads "the set" in all of the above, and (max, sum exp) come from irs_score_lse over the whole catalog); no search option
+ *   refuses it (guide, lookahead, path trace, beam trace, arrival rule, survivor scratch).  Nothing is allocated,
+ *   irs_workspace_bytes does not change.  No float atomics: two identical calls give identical bits in val, ids0, count and
+ *   status; lp inherits the unordered float32 sum of irs_score_lse.
  *    dev_scratch: caller-owned, >= irs_recommend_scratch_bytes(M, n, k) bytes, 16-byte aligned: the ranked lists (ids, then
  *            values: 12 M k bytes), the (max, sum exp) pairs, M empty windows for a call without dev_seq, and irs_survivor_scratch_bytes'
  *            layout for want = n (not monotone in M: a caller that walks row blocks of several sizes asks for each).

@@ -110,6 +110,9 @@ SIGNATURES = {
     "irs_bind_survivor_scratch": (c_int32, [c_void_p, c_void_p, c_size_t]),
     "irs_exclusion_scratch_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),
     "irs_bind_exclusions": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    "irs_offer_set_scratch_bytes": (c_size_t, [c_void_p, c_int64, c_int32]),
+    "irs_bind_offer_set": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_size_t]),
+    "irs_score_topk_offer": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "irs_recommend_scratch_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32]),
     "irs_recommend_take": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
                                      c_void_p, c_void_p, c_void_p, c_void_p]),

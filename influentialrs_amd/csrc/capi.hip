@@ -730,12 +730,20 @@ static int args_btrace(irs_ctx *ctx, const char *fn, const search_call &c) {
     return IRS_OK;
 }
 
+// an offer set: one pass of the bound scratch serves the call's rows
+static int args_offer(irs_ctx *ctx, const char *fn, const search_call &c) {
+    const int rows = c.W ? c.B * c.W : c.B;
+    if (rows > ctx->opt.offer.rows)
+        IRS_FAIL(ctx, IRS_E_INVALID, "%s: %d rows, the offer set's scratch (irs_bind_offer_set) is sized for %d", fn, rows, ctx->opt.offer.rows);
+    return IRS_OK;
+}
+
 // ---- the options, one row each.  greedy: its argument checks where a greedy entry point looks at it.  beam: why the beam entry
 // points refuse it ("<fn>: <what>: <beam>"); null: they admit it, with the same argument checks.  sharded: the sharded loops'
 // refusal, which every option has (a shard sees its own items only; most bindings refuse a sharded context themselves, so a
 // binding cannot exist there, and must not be ignored if it does).  loops_only: why every entry point but the two beam LOOPS
 // refuses it (the same message form); null for the options the greedy side admits
-enum { OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_BTRACE, OPT_N };
+enum { OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_BTRACE, OPT_OFFER, OPT_N };
 static const struct {
     bool (*on)(const irs_search_opts &);
     int (*args)(irs_ctx *, const char *, const search_call &);
@@ -756,6 +764,8 @@ static const struct {
     {[](const irs_search_opts &o) { return o.btrace.on != 0; }, args_btrace, "a beam trace is bound (irs_bind_beam_trace)", nullptr,
      "%s: a bound beam trace (irs_bind_beam_trace) needs the whole catalog on one device",
      "irs_beam_search and irs_beam_search_until only"},
+    {[](const irs_search_opts &o) { return o.offer.on != 0; }, args_offer, nullptr, nullptr,
+     "%s: a bound offer set (irs_bind_offer_set) needs the whole catalog on one device"},
 };
 
 // ---- the entry points, one row each: what it checks, in its order -- the first failing check decides the code and the message.
@@ -765,14 +775,17 @@ static const struct {
 // A bound beam trace is refused first wherever it is refused (nothing else of the call is looked at); the beam loops look at it
 // once the call's shape stands.  AT_BEAM_STEP_LINKED, the trace's own step (irs_beam_step_linked), does not look at it.
 // AT_RECOMMEND (irs_recommend / irs_recommend_take) is no search: only the exclusion set applies to it, and no option refuses it.
+// A bound offer set is looked at last by the loops; the standalone steps and irs_recommend_take are kernels on the caller's
+// lists and do not look at it (irs_recommend, which ranks inside the set, makes the set's argument check itself).  The set's
+// sharded refusal is defensive: irs_bind_offer_set refuses a sharded context, so no test can reach it.
 enum { AT_GREEDY_LOOP, AT_PATH_STEP, AT_BEAM_STEP, AT_BEAM_LOOP, AT_SHARDED_LOOP, AT_BEAM_STEP_LINKED, AT_RECOMMEND };
 enum { DO_READY = OPT_N, DO_WORLD, DO_SHAPE, DO_K, DO_END };
-static const int PLAN[][13] = {
-    /* AT_GREEDY_LOOP  */ {OPT_BTRACE, OPT_ARRIVE, OPT_GUIDE, OPT_LOOK, DO_READY, DO_WORLD, DO_SHAPE, OPT_TRACE, DO_K, OPT_EXCL, OPT_SURV, DO_END},
+static const int PLAN[][14] = {
+    /* AT_GREEDY_LOOP  */ {OPT_BTRACE, OPT_ARRIVE, OPT_GUIDE, OPT_LOOK, DO_READY, DO_WORLD, DO_SHAPE, OPT_TRACE, DO_K, OPT_EXCL, OPT_SURV, OPT_OFFER, DO_END},
     /* AT_PATH_STEP    */ {OPT_BTRACE, OPT_EXCL, OPT_GUIDE, DO_END},
     /* AT_BEAM_STEP    */ {OPT_BTRACE, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
-    /* AT_BEAM_LOOP    */ {OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, DO_READY, DO_WORLD, OPT_TRACE, DO_SHAPE, OPT_BTRACE, DO_K, OPT_EXCL, OPT_SURV, DO_END},
-    /* AT_SHARDED_LOOP */ {OPT_BTRACE, OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, DO_END},
+    /* AT_BEAM_LOOP    */ {OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, DO_READY, DO_WORLD, OPT_TRACE, DO_SHAPE, OPT_BTRACE, DO_K, OPT_EXCL, OPT_SURV, OPT_OFFER, DO_END},
+    /* AT_SHARDED_LOOP */ {OPT_BTRACE, OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_OFFER, DO_END},
     /* AT_BEAM_STEP_LINKED */ {OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
     /* AT_RECOMMEND    */ {OPT_EXCL, DO_END},
 };
@@ -839,6 +852,54 @@ extern "C" int irs_bind_exclusions(irs_ctx *ctx, const int64_t *excl_ids0, int32
     ctx->opt.excl.on = 1, ctx->opt.excl.users = users, ctx->opt.excl.no_repeat = no_repeat ? 1 : 0;
     opts_changed(ctx);
     return IRS_OK;
+}
+
+// ------------------------------------------------------------------ offer set (irs_bind_offer_set; offer_set.hip)
+static bool offer_shape_ok(const irs_ctx *ctx, int64_t n_ids, int rows) {
+    return n_ids >= 1 && n_ids <= ctx->dims.n_item && rows >= 1 && rows <= ctx->max_rows;
+}
+
+extern "C" size_t irs_offer_set_scratch_bytes(const irs_ctx *ctx, int64_t n_ids, int32_t rows) {
+    if (!ctx || !offer_shape_ok(ctx, n_ids, rows)) return 0;
+    return irs_offer_layout(nullptr, n_ids, rows, nullptr);
+}
+
+// Neither entry point takes a stream: their launches are enqueued on the null stream and the call returns without waiting, as
+// irs_recommend's are (irs_hip.h)
+extern "C" int irs_bind_offer_set(irs_ctx *ctx, const int64_t *ids0, int64_t n_ids, void *scratch, size_t bytes) {
+    if (!ctx) return IRS_E_INVALID;
+    const char *fn = "irs_bind_offer_set";
+    if (!ids0 && n_ids == 0) { // unbind
+        if (ctx->opt.offer.on) opts_changed(ctx);
+        ctx->opt.offer = {};
+        return IRS_OK;
+    }
+    if (!ids0) IRS_FAIL(ctx, IRS_E_INVALID, "%s: an id array and n_ids >= 1 go together", fn);
+    if (n_ids < 1 || n_ids > ctx->dims.n_item) IRS_FAIL(ctx, IRS_E_INVALID, "%s: n_ids must be in [1, n_item=%lld]", fn, (long long)ctx->dims.n_item);
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s needs the whole catalog on one device", fn);
+    int rc = check_scratch(ctx, fn, scratch, bytes, irs_offer_layout(nullptr, n_ids, 1, nullptr));
+    if (rc) return rc;
+    // the rows of a pass: what the scratch holds behind the ids, at most max_rows
+    irs_offer_rows o;
+    const size_t head = irs_offer_layout(scratch, n_ids, 0, &o);
+    const size_t fit = (bytes - head) / ((size_t)o.c_pad * sizeof(float));
+    const int rows = fit < (size_t)ctx->max_rows ? (int)fit : ctx->max_rows;
+    if ((rc = irs_launch_offer_prepare(ctx, ids0, n_ids, o, nullptr))) return rc;
+    ctx->opt.offer = {1, o.ids, n_ids, scratch, rows};
+    opts_changed(ctx);
+    return IRS_OK;
+}
+
+extern "C" int irs_score_topk_offer(irs_ctx *ctx, const float *xrows, int32_t M, int32_t k, float *val, int64_t *ids0, int32_t *status) {
+    // (the argument checks first: k bounds the selection's LDS buffer, and a context without weights can be asked about them)
+    if (!ctx) return IRS_E_INVALID;
+    int rc = check_rows(ctx, "irs_score_topk_offer", xrows, M);
+    if (rc) return rc;
+    if (k < 1 || k > ctx->dims.max_k) IRS_FAIL(ctx, IRS_E_INVALID, "irs_score_topk_offer: k must be in [1, %d]", ctx->dims.max_k);
+    if (!val || !ids0 || !status) IRS_FAIL(ctx, IRS_E_INVALID, "irs_score_topk_offer: null output");
+    if ((rc = ready(ctx))) return rc;
+    if (!ctx->opt.offer.on) IRS_FAIL(ctx, IRS_E_STATE, "irs_score_topk_offer: no offer set is bound (irs_bind_offer_set)");
+    return irs_launch_offer_topk(ctx, xrows, M, k, val, ids0, status, nullptr);
 }
 
 // ------------------------------------------------------------------ bound guide (irs_bind_guide; guide.hip)
@@ -970,6 +1031,17 @@ extern "C" int irs_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int32_t B
     return irs_launch_path_step(ctx, pa, B, val, ids0, k, (hipStream_t)stream);
 }
 
+// The ranked lists a step or a slate starts from.  Nothing bound: irs_launch_topk as it always was.  An offer set bound: the best k
+// of the set from its own launcher, and where the caller needs the rows' (max, sum exp) they are irs_launch_lse's over the whole
+// catalog -- the set restricts offers, not the softmax.  No threshold carry applies then, and the thr_* state is not touched.
+static int launch_lists(irs_ctx *ctx, const float *xrows, int M, int k, int sweep, float *val, int64_t *ids0, int32_t *status, hipStream_t s,
+                        float *lse_max, float *lse_sum, int carry) {
+    if (!ctx->opt.offer.on) return irs_launch_topk(ctx, xrows, M, k, sweep, val, ids0, status, s, nullptr, lse_max, lse_sum, carry);
+    const int rc = irs_launch_offer_topk(ctx, xrows, M, k, val, ids0, status, s);
+    if (rc || !lse_max) return rc;
+    return irs_launch_lse(ctx, xrows, M, lse_max, lse_sum, s);
+}
+
 // one search step on one device: decode -> rows at hep -> top-k -> choose/update.  `pa` is the loop's (loop_path_args): the step
 // index comes from the device counter
 // surv_fin (may be null): rows the survivor pass skips -- the until loop's finished rows, stepped until the next compaction
@@ -987,11 +1059,11 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
     // (not while exact candidates are bound: the survivor pass goes between the ranking and the step; nor while exclusions are
     //  bound: only the separate step kernel has the form that tests them; nor while a path trace is bound: its sweep reads the
     //  window before the step, its record kernel the lists after it; nor while a guide is bound: the guided step is a kernel of its own;
-    //  nor while a lookahead is bound: its expand, inner decode and choose go between the ranking and the step)
+    //  nor while a lookahead is bound: its expand, inner decode and choose go between the ranking and the step; nor while an offer
+    //  set is bound: the lists come from its own launcher)
     if (merged && !irs_opt_splits_step(ctx->opt) && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k))
         return irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, &pa);
-    if ((rc = irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, nullptr, nullptr, carry)))
-        return rc;
+    if ((rc = launch_lists(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, nullptr, carry))) return rc;
     const irs_search_opts &o = ctx->opt;
     if (o.surv.scratch) {
         const irs_surv_args sa{ctx->xrows, pa.seq, pa.hep, B, 1, k, irs_opt_choices(o, 0, pa.sample, pa.sample_k), ctx->surv_rows, nullptr,
@@ -1150,13 +1222,13 @@ extern "C" int irs_recommend(irs_ctx *ctx, const float *xrows, const int64_t *se
     if ((rc = check_scratch(ctx, fn, scratch, scratch_bytes, recommend_layout(ctx, nullptr, M, n, k, nullptr)))) return rc;
     const irs_excl ex = recommend_excl(ctx);
     if (ex.on && (rc = search_rules(ctx, fn, AT_RECOMMEND, search_call{M, 0, 0, k, sweep, 0, 0, true}))) return rc;
+    if (ctx->opt.offer.on && (rc = args_offer(ctx, fn, search_call{M, 0, 0, k, sweep, 0, 0, true}))) return rc;
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s needs the whole catalog on one device", fn);
     if ((rc = irs_ready_filter(ctx, sweep))) return rc;
     hipStream_t s = nullptr; // (the null stream: irs_hip.h)
     recommend_rows r;
     recommend_layout(ctx, scratch, M, n, k, &r);
-    if ((rc = irs_launch_topk(ctx, xrows, M, k, sweep, r.val, r.ids0, status, s, nullptr, out_lp ? r.mx : nullptr, out_lp ? r.sm : nullptr)))
-        return rc;
+    if ((rc = launch_lists(ctx, xrows, M, k, sweep, r.val, r.ids0, status, s, out_lp ? r.mx : nullptr, out_lp ? r.sm : nullptr, 0))) return rc;
     if (seq || ex.on) { // (with neither a window nor a list every entry is admissible: no row can be short)
         if (!seq) IRS_CHECK_HIP(ctx, hipMemsetAsync(r.no_hep, 0xFF, (size_t)M * sizeof(int32_t), s)); // every byte 0xFF: hep = -1
         const irs_surv_args sa{xrows, seq ? seq : r.no_seq, seq ? hep : r.no_hep, M, 1, k, n, M, nullptr, nullptr, nullptr, r.val, r.ids0, status,
@@ -1559,8 +1631,7 @@ static int enqueue_beam_step(irs_ctx *ctx, int in, const int64_t *user, int B, i
     int rc;
     if ((rc = irs_launch_decode(ctx, ctx->bm[in].seq, user, rows, nullptr, ctx->bm[in].hep, ctx->xrows, nullptr, s))) return rc;
     // W > 1: top-k and log-sum-exp out of one call (one pass over the float32 catalog on the swept path)
-    if ((rc = irs_launch_topk(ctx, ctx->xrows, rows, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, lmax, lsum)))
-        return rc;
+    if ((rc = launch_lists(ctx, ctx->xrows, rows, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, lmax, lsum, 0))) return rc;
     // bound exclusions: a beam row's user through the loop's map, its path so far in the step's input state
     const irs_excl ex = excl_args(ctx, W, until ? until->map : nullptr, ctx->bm[in].paths, P, 0, ctx->step_ctr, 0);
     if (ctx->opt.surv.scratch) { // exact candidates: a live unfinished beam of a user that is not done sees its best W admissible items

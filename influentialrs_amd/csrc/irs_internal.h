@@ -259,6 +259,28 @@ struct irs_eval_batch_args { // irs_build_eval_batch's arguments as the kernel t
     int32_t *raw_n, *status;
 };
 
+// ---- a bound offer set (irs_bind_offer_set; offer_set.hip).  The caller's scratch holds a header whose int32 word 0 is the number
+// of holes the prepare launch found, the sanitised ids padded with -1 to whole tiles of the score kernel, and the float32 scores
+// of one pass: `rows` rows x c_pad.
+#define IRS_OFFER_TILE 64
+#define IRS_OFFER_HDR 256
+struct irs_offer_rows {
+    int32_t *holes; // [1] entries of the caller's array that became -1
+    int64_t *ids;   // [c_pad] 0-based ids, ascending where the caller's were; -1: a hole, and everything behind C
+    float *sc;      // [rows][c_pad]
+    int64_t c_pad;
+};
+static inline size_t irs_offer_layout(void *base, int64_t n_ids, int rows, irs_offer_rows *o) {
+    const size_t c_pad = ((size_t)n_ids + IRS_OFFER_TILE - 1) / IRS_OFFER_TILE * IRS_OFFER_TILE;
+    const size_t n_id = (c_pad * 8 + 255) / 256 * 256;
+    if (o) {
+        char *p = (char *)base;
+        o->holes = (int32_t *)p, o->ids = (int64_t *)(p + IRS_OFFER_HDR), o->sc = (float *)(p + IRS_OFFER_HDR + n_id);
+        o->c_pad = (int64_t)c_pad;
+    }
+    return IRS_OFFER_HDR + n_id + (size_t)rows * c_pad * 4;
+}
+
 // ---- search options: what a caller binds to a context for its search calls.  Every change goes through opts_changed
 // (capi.hip), which drops the captured steps; which entry point admits which option is capi.hip's search_rules.
 struct irs_search_opts {
@@ -320,6 +342,17 @@ struct irs_search_opts {
         int users, W, ld;
         void *scratch;
     } btrace;
+
+    // offer set (irs_bind_offer_set): the sanitised ids and the score pass in the caller's scratch (irs_offer_layout) while bound;
+    // irs_score_topk_offer ranks inside it, and the single-device loops, irs_recommend, the survivor pass and the arrival rule read
+    // "the set" where they read "the catalog"; the sharded loops refuse
+    struct {
+        int on;
+        const int64_t *ids; // [n] (in the scratch)
+        int64_t n;
+        void *scratch;
+        int rows;           // rows of a pass: what the scratch was sized for
+    } offer;
 };
 // the candidates a step chooses among: a guided and a lookahead step among their k_c, a sampled step among sample_k, a beam
 // step of width W among W
@@ -327,9 +360,9 @@ static inline int irs_opt_choices(const irs_search_opts &o, int W, int sample, i
     return W ? W : (o.guide.on ? o.guide.g.k_c : (o.look.on ? o.look.kc : (sample ? sample_k : 1)));
 }
 // some option puts a launch of its own between the ranking and the greedy step, or needs a step kernel of its own: the merged
-// top-k + step kernel cannot run (the arrival rule needs a trace, which is in the list)
+// top-k + step kernel cannot run (the arrival rule needs a trace, which is in the list; an offer set's lists come from its own launcher)
 static inline bool irs_opt_splits_step(const irs_search_opts &o) {
-    return o.surv.scratch || o.excl.on || o.trace.on || o.guide.on || o.look.on;
+    return o.surv.scratch || o.excl.on || o.trace.on || o.guide.on || o.look.on || o.offer.on;
 }
 
 struct irs_ctx {
@@ -583,6 +616,10 @@ size_t irs_excl_scratch(int users, int n_excl);
 int irs_launch_excl_prepare(irs_ctx *ctx, const int64_t *ids0, int users, int n_excl, void *scratch, hipStream_t s);
 size_t irs_surv_scratch(const irs_ctx *ctx, int rows, int want);
 int irs_launch_survivors(irs_ctx *ctx, const irs_surv_args &a, void *scratch, hipStream_t s);
+
+// ---- offer_set.hip ---- (arguments already validated; irs_launch_offer_topk reads ctx->opt.offer)
+int irs_launch_offer_prepare(irs_ctx *ctx, const int64_t *ids0, int64_t n_ids, const irs_offer_rows &o, hipStream_t s);
+int irs_launch_offer_topk(irs_ctx *ctx, const float *xrows, int M, int k, float *val, int64_t *ids0, int32_t *status, hipStream_t s);
 
 // ---- recommend.hip ---- (the first n admissible entries of every row's list; arguments already validated.  seq null: no window;
 // out_lp null: mx / sm are not read; ex: the bound exclusion lists, never a path)

@@ -492,13 +492,16 @@ int irs_launch_trace_record(irs_ctx *ctx, const irs_trace_rec &t, const int64_t 
 // user's bound list and (no_repeat) the row's path so far -- gets its list rewritten to the target alone: (ts, t - 1), then the
 // end mark.  The unchanged step kernels then choose it as the only survivor.  Rows that do not fire are not written.
 // One wave per row; no LDS, no atomics (the status word is this row's, and the step kernels behind write it the same way).
-template <bool EXCL, int SLOTS>
+// OFFER: an offer set is bound (irs_bind_offer_set): a target that is not one of oset[0 .. on) is not offered -- one binary search
+// of the ascending ids, irs_excl_listed's.
+template <bool EXCL, int SLOTS, bool OFFER>
 __global__ void __launch_bounds__(256) k_arrival_offer(const int64_t *__restrict__ seq, const int32_t *__restrict__ hep, int L, int B,
                                                        int64_t n_item, const float *__restrict__ mx, const float *__restrict__ sm,
                                                        const float *__restrict__ ts, const int32_t *__restrict__ rank,
                                                        const int32_t *__restrict__ fin, float *__restrict__ val,
                                                        int64_t *__restrict__ ids0, int k, int rank_max, float lp_min,
-                                                       int32_t *__restrict__ status, const irs_excl ex) {
+                                                       int32_t *__restrict__ status, const irs_excl ex,
+                                                       const int64_t *__restrict__ oset, int on) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= B) return;
@@ -515,6 +518,9 @@ __global__ void __launch_bounds__(256) k_arrival_offer(const int64_t *__restrict
     const int64_t *w = seq + (size_t)row * L;
     const int64_t t = w[L - 1];
     if (t < 1 || t > n_item) return;
+    if constexpr (OFFER) {
+        if (!irs_excl_listed(oset, on, t - 1)) return; // (the same search in every lane)
+    }
     irs_window<SLOTS> win;
     win.load(w, hep[row], L, lane);
     bool hit = false, listed = false;
@@ -539,10 +545,14 @@ int irs_launch_arrival_offer(irs_ctx *ctx, const int64_t *seq, const int32_t *he
                              const float *ts, const int32_t *rank, const int32_t *fin, float *val, int64_t *ids0, int k, int rank_max,
                              float lp_min, int32_t *status, const irs_excl &ex, hipStream_t s) {
     constexpr int S4 = IRS_WIN_SLOTS_SHORT, S16 = IRS_WIN_SLOTS_LONG;
-    const auto kern = irs_window_slots(ctx) == S4 ? (ex.on ? k_arrival_offer<true, S4> : k_arrival_offer<false, S4>)
-                                                  : (ex.on ? k_arrival_offer<true, S16> : k_arrival_offer<false, S16>);
+    const auto &of = ctx->opt.offer; // a bound offer set: the target must be in it
+    const bool s4 = irs_window_slots(ctx) == S4;
+    const auto kern = of.on ? (s4 ? (ex.on ? k_arrival_offer<true, S4, true> : k_arrival_offer<false, S4, true>)
+                                  : (ex.on ? k_arrival_offer<true, S16, true> : k_arrival_offer<false, S16, true>))
+                            : (s4 ? (ex.on ? k_arrival_offer<true, S4, false> : k_arrival_offer<false, S4, false>)
+                                  : (ex.on ? k_arrival_offer<true, S16, false> : k_arrival_offer<false, S16, false>));
     hipLaunchKernelGGL(kern, dim3((B + 3) / 4), dim3(256), 0, s, seq, hep, ctx->dims.max_len, B, ctx->dims.n_item, mx, sm, ts, rank, fin,
-                       val, ids0, k, rank_max, lp_min, status, ex);
+                       val, ids0, k, rank_max, lp_min, status, ex, of.on ? of.ids : nullptr, of.on ? (int)of.n : 0);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }

@@ -10,6 +10,9 @@
 // in the recorded list: two identical calls give identical bits.
 // With a bound exclusion set (irs_bind_exclusions; the EXCL forms, launched only while one is bound) "window" reads "window +
 // the user's list + (no_repeat) the row's path so far" in all of the above; k_excl_prepare, at the end, is the binding's launch.
+// With a bound offer set (irs_bind_offer_set; the OFFER forms) "the whole float32 shard" reads "the set": the strips cut the
+// sanitised id array, a key carries the LOCAL index (local order is id order: the set ascends), and the window test and the
+// output map local -> global through the array.  A hole scores nothing.  k_surv_flag is the same kernel either way.
 #include "irs_internal.h"
 
 #define SURV_STRIPS 256          // item strips of a large shard
@@ -150,12 +153,14 @@ __device__ __forceinline__ unsigned int surv_select(KeyFn &&keyfn, AdmitFn &&adm
 // running threshold.  EXCL: the row's path entries are sorted in with the window (INT64_MAX fills both), and an item that is in
 // neither is searched in the user's bound row.
 // WSLOTS: window slots of the sort buffer, 256 (max_len <= 256) or IRS_MAX_LEN_LONG.
-template <bool EXCL, int WSLOTS>
+// OFFER: the items are oids[0 .. n_local) (n_local = the set's size), not [0, n_local) of the shard.
+template <bool EXCL, int WSLOTS, bool OFFER>
 __global__ void __launch_bounds__(256) k_surv_strips(const irs_excl ex, const float *__restrict__ x, int d, const float *__restrict__ W,
                                                      const float *__restrict__ bias, int64_t n_local, int64_t item_lo,
                                                      const int64_t *__restrict__ seq, int L, const int32_t *__restrict__ hep,
                                                      int want, int n_strips, const unsigned int *__restrict__ count,
-                                                     const int32_t *__restrict__ list, unsigned long long *__restrict__ keys) {
+                                                     const int32_t *__restrict__ list, unsigned long long *__restrict__ keys,
+                                                     const int64_t *__restrict__ oids) {
     __shared__ unsigned long long buf[SURV_BUF];
     __shared__ float xs[256];
     constexpr int WIN = EXCL ? 2 * WSLOTS : WSLOTS; // EXCL: the window slots + IRS_MAX_PATH path slots, up to a power of two for the sort
@@ -191,11 +196,17 @@ __global__ void __launch_bounds__(256) k_surv_strips(const irs_excl ex, const fl
         surv_bitonic<long long, false>(win, WIN);
         const unsigned int n = surv_select(
             [&](int64_t j) -> unsigned long long {
-                const float e = irs_chain(xs, W + (size_t)j * d, bias[j], d);
+                int64_t id = j;
+                if constexpr (OFFER) {
+                    id = oids[j];
+                    if (id < 0) return 0ull; // (a hole: no key)
+                }
+                const float e = irs_chain(xs, W + (size_t)id * d, bias[id], d);
                 return ((unsigned long long)irs_fkey(e) << 32) | (0xFFFFFFFFu - (unsigned int)j);
             },
             [&](unsigned long long key) -> bool { // the item is not in win[0 .. wl)
-                const long long item = (long long)(item_lo + (int64_t)(0xFFFFFFFFu - (unsigned int)key) + 1);
+                const int64_t loc = (int64_t)(0xFFFFFFFFu - (unsigned int)key);
+                const long long item = (long long)((OFFER ? oids[loc] : item_lo + loc) + 1);
                 const int wn = EXCL ? WIN : wl; // (EXCL: window and path entries lie mixed in front of the fill)
                 int lo = 0, hi = wn;
                 while (lo < hi) {
@@ -213,10 +224,12 @@ __global__ void __launch_bounds__(256) k_surv_strips(const irs_excl ex, const fl
 }
 
 // ---- list rewrite: the best `want` of a recorded row's strip keys, in the library's order; the list ends behind them
+// (oids: the offer form's id array, through which a key's local index leaves; null: the index is the shard's)
 __global__ void __launch_bounds__(256) k_surv_merge(int64_t item_lo, int k, int want, int n_strips, int rps,
                                                     const unsigned int *__restrict__ count, const int32_t *__restrict__ list,
                                                     const unsigned long long *__restrict__ keys, const int32_t *__restrict__ status_map,
-                                                    float *__restrict__ val, int64_t *__restrict__ ids, int32_t *__restrict__ status) {
+                                                    float *__restrict__ val, int64_t *__restrict__ ids, int32_t *__restrict__ status,
+                                                    const int64_t *__restrict__ oids) {
     __shared__ unsigned long long buf[SURV_BUF];
     const unsigned int n_rows = *count;
     if (n_rows == 0u) return;
@@ -229,7 +242,8 @@ __global__ void __launch_bounds__(256) k_surv_merge(int64_t item_lo, int k, int 
             const unsigned long long kk = buf[i];
             const bool live = i < (int)n;
             val[(size_t)row * k + i] = live ? irs_unkey((unsigned int)(kk >> 32)) : -INFINITY;
-            ids[(size_t)row * k + i] = live ? item_lo + (int64_t)(0xFFFFFFFFu - (unsigned int)kk) : (int64_t)-1;
+            const int64_t loc = (int64_t)(0xFFFFFFFFu - (unsigned int)kk);
+            ids[(size_t)row * k + i] = live ? (oids ? oids[loc] : item_lo + loc) : (int64_t)-1;
         }
         if (threadIdx.x == 0) {
             const int u = row / rps;
@@ -251,16 +265,23 @@ int irs_launch_survivors(irs_ctx *ctx, const irs_surv_args &a, void *scratch, hi
     const bool long_win = irs_window_slots(ctx) != S4;
     const auto k_flag = long_win ? (a.ex.on ? k_surv_flag<true, S16> : k_surv_flag<false, S16>)
                                  : (a.ex.on ? k_surv_flag<true, S4> : k_surv_flag<false, S4>);
-    const auto k_strips = long_win ? (a.ex.on ? k_surv_strips<true, IRS_MAX_LEN_LONG> : k_surv_strips<false, IRS_MAX_LEN_LONG>)
-                                   : (a.ex.on ? k_surv_strips<true, 256> : k_surv_strips<false, 256>);
+    // a bound offer set: the repair comes from the set (the strip count stays the one the scratch was sized for)
+    const auto &of = ctx->opt.offer;
+    const int64_t *oids = of.on ? of.ids : nullptr;
+    const int64_t n_span = of.on ? of.n : ctx->n_local;
+    constexpr int LW = IRS_MAX_LEN_LONG;
+    const auto k_strips = of.on ? (long_win ? (a.ex.on ? k_surv_strips<true, LW, true> : k_surv_strips<false, LW, true>)
+                                            : (a.ex.on ? k_surv_strips<true, 256, true> : k_surv_strips<false, 256, true>))
+                                : (long_win ? (a.ex.on ? k_surv_strips<true, LW, false> : k_surv_strips<false, LW, false>)
+                                            : (a.ex.on ? k_surv_strips<true, 256, false> : k_surv_strips<false, 256, false>));
     hipLaunchKernelGGL(k_flag, dim3((a.M + 3) / 4), dim3(256), 0, s, a.ex, a.seq, L, a.hep, a.M, a.rps, a.k, a.want, a.cum, a.fin, a.done,
                        a.ids0, count, list);
     int ny = 4096 / ns < 4 ? 4 : (4096 / ns > SURV_ROW_GROUPS ? SURV_ROW_GROUPS : 4096 / ns);
     if (ny > a.M) ny = a.M;
-    hipLaunchKernelGGL(k_strips, dim3(ns, ny), dim3(256), 0, s, a.ex, a.xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b, ctx->n_local,
-                       ctx->shard.item_lo, a.seq, L, a.hep, a.want, ns, count, list, keys);
+    hipLaunchKernelGGL(k_strips, dim3(ns, ny), dim3(256), 0, s, a.ex, a.xrows, ctx->dims.d, ctx->proj_w, ctx->proj_b, n_span,
+                       ctx->shard.item_lo, a.seq, L, a.hep, a.want, ns, count, list, keys, oids);
     hipLaunchKernelGGL(k_surv_merge, dim3(a.M < SURV_ROW_GROUPS ? a.M : SURV_ROW_GROUPS), dim3(256), 0, s, ctx->shard.item_lo, a.k, a.want, ns, a.rps, count, list,
-                       keys, a.status_map, a.val, a.ids0, a.status);
+                       keys, a.status_map, a.val, a.ids0, a.status, oids);
     IRS_CHECK_HIP(ctx, hipGetLastError());
     return IRS_OK;
 }

@@ -468,6 +468,52 @@ class Engine:
     def unbind_exclusions(self):
         self._call(self.lib.irs_bind_exclusions, None, 0, 0, 0, None, 0)
 
+    # ------------------------------------------------------------------ offer set (irs_bind_offer_set)
+    def offer_set_scratch_bytes(self, n_ids: int, rows: int) -> int:
+        n = int(self.lib.irs_offer_set_scratch_bytes(self.h, n_ids, rows))
+        if n == 0:
+            raise IrsError(f"offer_set_scratch_bytes: n_ids={n_ids} / rows={rows} (n_ids in [1, n_item={self.n_item}], rows in "
+                           f"[1, max_rows={self.max_rows}])")
+        return n
+
+    def bind_offer_set(self, ids0: torch.Tensor, rows: Optional[int] = None, *, prepared: bool = False) -> torch.Tensor:
+        """irs_bind_offer_set: ids0 int64, global 0-based ids in any order (sorted and made unique on the device here).  Until
+        unbind_offer_set the search loops, recommend and the survivor pass offer items of the set only; score_topk_offer ranks
+        inside it.  rows: the rows of one pass of the scratch (default max_rows).  The hole count is read once -- the call's one
+        host wait -- and an id outside [0, n_item) raises.  prepared: bind the array as it is (what the C caller does).
+        Returns the scratch, which the engine also keeps alive while bound.  The binding's launch goes on the null stream,
+        ordered against torch's current stream by events (_call_null)."""
+        ids0 = self._dev(ids0, torch.int64).reshape(-1)
+        if not prepared:
+            ids0 = torch.unique(ids0, sorted=True)
+        n = ids0.numel()
+        rows = self.max_rows if rows is None else rows
+        scratch = torch.empty(self.offer_set_scratch_bytes(n, rows), dtype=torch.uint8, device=self.device)
+        self._call_null(self.lib.irs_bind_offer_set, _ptr(ids0), n, _ptr(scratch), scratch.numel(), tensors=(ids0, scratch))
+        self._offer_scratch = scratch
+        holes = int(scratch[:4].view(torch.int32).item())
+        if holes:
+            self.unbind_offer_set()
+            raise IrsError(f"bind_offer_set: {holes} of {n} ids are outside [0, n_item={self.n_item}), repeated or not ascending")
+        return scratch
+
+    def unbind_offer_set(self):
+        with torch.cuda.device(self.device):  # (no launch: nothing to order)
+            self._check(self.lib.irs_bind_offer_set(self.h, None, 0, None, 0))
+        self._offer_scratch = None
+
+    def score_topk_offer(self, xrows: torch.Tensor, k: int = 100):
+        """irs_score_topk_offer: (val[M,k] float32, ids0[M,k] int64 global 0-based, status[M] int32), the best k of the bound set.
+        The work goes on the null stream, ordered against torch's current stream by events (_call_null)."""
+        xrows = self._dev(xrows, torch.float32)
+        M = xrows.shape[0]
+        val = torch.empty((M, k), dtype=torch.float32, device=self.device)
+        ids = torch.empty((M, k), dtype=torch.int64, device=self.device)
+        st = torch.empty(M, dtype=torch.int32, device=self.device)
+        self._call_null(self.lib.irs_score_topk_offer, _ptr(xrows), M, k, _ptr(val), _ptr(ids), _ptr(st),
+                        tensors=(xrows, val, ids, st, getattr(self, "_offer_scratch", None)))
+        return val, ids, st
+
     # ------------------------------------------------------------------ recommend (irs_recommend, irs_recommend_take)
     def recommend_scratch_bytes(self, rows: int, n: int, k: int) -> int:
         nb = int(self.lib.irs_recommend_scratch_bytes(self.h, rows, n, k))
@@ -885,10 +931,12 @@ class Engine:
                         exact_candidates: bool = False, exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
                         guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
                         arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False,
-                        beam_trace: bool = False):
+                        beam_trace: bool = False, offer: Optional[torch.Tensor] = None):
         """While a search call runs with per-call keywords: what they ask for is bound before and unbound after.  Yields (the
         trace arrays (lp_item, lp_target, rank_target) or None, the lookahead record (items, lp) or None); beam_trace (the beam
         loops' trace=True) binds a beam trace for the call's width instead, whose [users, W, ld] arrays take the first place.
+        offer (int64, 0-based ids, any order): an offer set is bound for the call (bind_offer_set), its scratch sized for the
+        call's rows.
         users / ld: the call's users and path length; beam: its beam width, 0 for the greedy loops.  graph: the call replays
         a captured step -- the stream is drained once before the first unbind destroys it.
         Every bind and unbind drops ALL captured steps of the context, so with a keyword set use_graph saves nothing: the step
@@ -932,6 +980,7 @@ class Engine:
             (lookahead is not None, look, self.unbind_lookahead),
             (trace, traced, self.unbind_path_trace),
             (beam_trace, beam_traced, self.unbind_beam_trace),
+            (offer is not None, lambda: (self.bind_offer_set(offer, users * max(beam, 1)),), self.unbind_offer_set),
         )
         bound = []
         try:
@@ -993,7 +1042,8 @@ class Engine:
                        status: Optional[torch.Tensor] = None, exact_candidates: bool = False,
                        exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
                        guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
-                       arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False):
+                       arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False,
+                       offer: Optional[torch.Tensor] = None):
         """Runs the whole search loop on the device.  `seqs` and `hep` are the
         working window state and are modified in place.  exact_candidates: a row whose k candidates are hidden by its window
         chooses among the exact best admissible items of the catalog instead (IRS_ROW_RESCUED; the result of k = n_item).
@@ -1011,11 +1061,14 @@ class Engine:
         lookahead (k_c in [1, 32]): a lookahead is bound for this call (irs_bind_lookahead): a step takes, among its first k_c
         admissible candidates, the one under which the target's next-step log-probability is highest; greedy only, not with
         guide.  lookahead_record: the return value grows a last member, (items int32 [B, max_path_len, k_c], lp float32 [B,
-        max_path_len, k_c]): every step's candidates (1-based, 0 = none) and the values compared."""
+        max_path_len, k_c]): every step's candidates (1-based, 0 = none) and the values compared.
+        offer (int64, 0-based ids): an offer set is bound for this call (irs_bind_offer_set): every step offers items of the set
+        only; log-probabilities and target ranks stay statements about the whole catalog.  The same holds in the three other
+        loops."""
         seqs, users, hep, B, paths, status = self._greedy_call("generate_paths", seqs, users, hep, max_path_len, paths, status)
         with self._search_options(B, max_path_len, 0, sample, sample_k, bool(use_graph), exact_candidates=exact_candidates, exclude=exclude,
                                   no_repeat=no_repeat, trace=trace, guide=guide, guide_k=guide_k, arrive_rank=arrive_rank,
-                                  arrive_lp=arrive_lp, lookahead=lookahead, lookahead_record=lookahead_record) as recorded:
+                                  arrive_lp=arrive_lp, lookahead=lookahead, lookahead_record=lookahead_record, offer=offer) as recorded:
             self._call(self.lib.irs_generate_paths, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                     int(sample), sample_k, seed, int(use_graph), _ptr(paths), _ptr(status))
         return (paths, status) + self._recorded(recorded, trace, lookahead is not None and lookahead_record)
@@ -1026,7 +1079,8 @@ class Engine:
                              status: Optional[torch.Tensor] = None, exact_candidates: bool = False,
                              exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
                              guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
-                             arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False):
+                             arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False,
+                             offer: Optional[torch.Tensor] = None):
         """generate_paths that stops a user at its target (seqs[b, L - 1]) and the call when nobody is left
         (irs_generate_paths_until): returns (paths, status, steps_run, row_steps).  Paths are zero behind the target.
         `seqs` and `hep` are working state: modified, and unspecified afterwards.  One host read of 4 bytes per check.
@@ -1039,7 +1093,7 @@ class Engine:
         stats = (ctypes.c_int64 * 2)(0, 0)
         with self._search_options(B, max_path_len, 0, sample, sample_k, exact_candidates=exact_candidates, exclude=exclude,
                                   no_repeat=no_repeat, trace=trace, guide=guide, guide_k=guide_k, arrive_rank=arrive_rank,
-                                  arrive_lp=arrive_lp, lookahead=lookahead, lookahead_record=lookahead_record) as recorded:
+                                  arrive_lp=arrive_lp, lookahead=lookahead, lookahead_record=lookahead_record, offer=offer) as recorded:
             self._call(self.lib.irs_generate_paths_until, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                           int(sample), sample_k, seed, check_every, _ptr(paths), _ptr(status), stats)
         return (paths, status, int(stats[0]), int(stats[1])) + self._recorded(recorded, trace, lookahead is not None and lookahead_record)
@@ -1064,7 +1118,7 @@ class Engine:
     def beam_search(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
                     beam: int, k: int = 100, sweep: int = IRS_SWEEP_BF16, use_graph: bool = False,
                     want_windows: bool = False, exact_candidates: bool = False, exclude: Optional[torch.Tensor] = None,
-                    no_repeat: bool = False, trace: bool = False):
+                    no_repeat: bool = False, trace: bool = False, offer: Optional[torch.Tensor] = None):
         """(paths[B,W,P] f32, scores[B,W] f64, status[B] i32[, windows[B,W,L]]); beam 0 is the best.
         trace: a beam trace is bound for this call (irs_bind_beam_trace) and the return value grows a last member, (lp_item,
         lp_target float32 [B, W, P], rank_target int32 [B, W, P]): the path trace's values along each output beam's ancestors."""
@@ -1078,7 +1132,7 @@ class Engine:
         status = torch.zeros(B, dtype=torch.int32, device=self.device)
         fin = torch.empty((B, beam, self.L), dtype=torch.int64, device=self.device) if want_windows else None
         with self._search_options(B, max_path_len, beam, graph=bool(use_graph), exact_candidates=exact_candidates, exclude=exclude,
-                                  no_repeat=no_repeat, beam_trace=trace) as recorded:
+                                  no_repeat=no_repeat, beam_trace=trace, offer=offer) as recorded:
             self._call(self.lib.irs_beam_search, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
                                                  int(use_graph), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(status))
         out = (paths, scores, status, fin) if want_windows else (paths, scores, status)
@@ -1106,7 +1160,8 @@ class Engine:
                           check_every: int = 1, want_windows: bool = False, paths: Optional[torch.Tensor] = None,
                           scores: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
                           fin: Optional[torch.Tensor] = None, exact_candidates: bool = False,
-                          exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False):
+                          exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
+                          offer: Optional[torch.Tensor] = None):
         """Beam search that ends a beam at its target (seqs[b, L - 1]) and retires finished users (irs_beam_search_until):
         (paths[B,W,P] f32, scores[B,W] f64, status[B] i32, fin[B,W] i32, steps_run, window_steps[, windows[B,W,L]]); beam 0 is
         the best.  One host read of 4 bytes per check.
@@ -1135,7 +1190,7 @@ class Engine:
         win = torch.empty((B, beam, self.L), dtype=torch.int64, device=self.device) if want_windows else None
         stats = (ctypes.c_int64 * 2)(0, 0)
         with self._search_options(B, max_path_len, beam, exact_candidates=exact_candidates, exclude=exclude, no_repeat=no_repeat,
-                                  beam_trace=trace) as recorded:
+                                  beam_trace=trace, offer=offer) as recorded:
             self._call(self.lib.irs_beam_search_until, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
                        int(stop_rule), int(check_every), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(win), _ptr(status), stats)
         out = (paths, scores, status, fin, int(stats[0]), int(stats[1]))

@@ -13,6 +13,7 @@ import torch.optim as optim
 
 from .. import _lib
 from ._backend import make_scheduler, project_ce, project_ce_sharded
+from .influentialRS import _takes_offer, offer_ids0
 from .layers import get_end_index
 
 
@@ -126,12 +127,15 @@ class Evaluator(nn.Module):
             rr.append(np.reciprocal(float(ranks[i])))
         return hit, np.array(rr)
 
+    @_takes_offer
     def predict_next(self, seqs, top_k=20, use_h=True):
         """The list behind get_accuracy_metrics_in_batch (extension; the baselines' predict_next, reference sas.py:357-388): int64
         [B, top_k] of 1-based ids, best first, 0 where fewer exist.  Row end - 1 of the evaluator (end: the row's last item, the
         label), and when use_h the prefix seqs[b, :end] left out -- passed as the row's window, hep = end - 1 -- so the label's
         rank in get_accuracy_metrics_in_batch is its position here plus one.  Exact whatever the prefix hides of the top 100
-        (irs_recommend).  self.last_recommend holds ids, scores, log_probs, count and status.  One device holds the catalog."""
+        (irs_recommend).  self.last_recommend holds ids, scores, log_probs, count and status.  offer=None (keyword only, taken by
+        _takes_offer; 1-based item ids): the slate is taken from these items only (irs_bind_offer_set, bound for the call); log_probs stay the
+        model's over the whole catalog.  One device holds the catalog."""
         hip = self.net._hip
         if hip.world != 1:
             raise ValueError("predict_next is not built for an item-sharded catalog")
@@ -151,7 +155,14 @@ class Evaluator(nn.Module):
         if use_h:
             win, _ = self.net._pad_to_len(seqs[:, :-1].to(torch.int64))
             hep = (end - 1).to(torch.int32)
-        val, ids0, lp, count, status = eng.recommend(xr, int(top_k), seqs=win, hep=hep, k=100, sweep=hip.sweep)
+        off = offer_ids0(self._call_offer, eng.n_item, dev)
+        held = eng.bind_offer_set(off, B) if off is not None else None
+        try:
+            val, ids0, lp, count, status = eng.recommend(xr, int(top_k), seqs=win, hep=hep, k=100, sweep=hip.sweep)
+        finally:
+            if held is not None:
+                held.record_stream(torch.cuda.current_stream(dev))
+                eng.unbind_offer_set()
         ids = ids0 + 1  # (-1 behind count: 0, the pad id)
         self.last_recommend = dict(ids=ids, scores=val, log_probs=lp, count=count, status=status)
         return ids

@@ -190,6 +190,7 @@ class SearchOptions:
     arrive_lp: object = None
     lookahead: object = None
     lookahead_record: bool = False
+    offer: object = dataclasses.field(default=None, kw_only=True)  # (keyword only: no positional constructor shifts)
     beam_trace: bool = False
     beam_pick: str = "score"
 
@@ -197,7 +198,8 @@ class SearchOptions:
 def search_option_kwargs(opts: SearchOptions, beam_width: int, sample: bool, world: int) -> dict:
     """What the options ask of a search over `world` item shards with this beam width and choice: ValueError where an option
     has no such form or a value is out of range, else the engine's greedy-loop keywords for them (exclude / no_repeat aside: the
-    lists need the windows, exclusion_ids0).  An arrival rule implies trace=True."""
+    lists need the windows, exclusion_ids0; offer aside as well: offer_ids0 makes its device array).  An arrival rule implies
+    trace=True."""
     trace = opts.trace
     kw = {}
     if opts.arrive_rank is not None or opts.arrive_lp is not None:
@@ -261,6 +263,9 @@ def search_option_kwargs(opts: SearchOptions, beam_width: int, sample: bool, wor
     if (opts.exclude is not None or opts.no_repeat) and world != 1:
         raise ValueError("exclude / no_repeat is not built for an item-sharded catalog: irs_bind_exclusions needs the whole "
                          "catalog on one device")
+    if opts.offer is not None and world != 1:
+        raise ValueError("offer is not built for an item-sharded catalog: irs_bind_offer_set needs the whole catalog on one "
+                         "device")
     if opts.exact_candidates and world != 1:
         raise ValueError("exact_candidates is not built for an item-sharded catalog: a shard can only rescue a row against "
                          "its own items")
@@ -269,20 +274,36 @@ def search_option_kwargs(opts: SearchOptions, beam_width: int, sample: bool, wor
 
 def _takes_exact_candidates(fn):
     """Gives get_seq_in_batch its keywords exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None,
-    guide_k=5, arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, beam_trace=False and
-    beam_pick="score".  They are taken here, keyword only,
+    guide_k=5, arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, beam_trace=False,
+    beam_pick="score" and offer=None.  They are taken here, keyword only,
     so that the declared parameter list stays what it was (it ends with beam_stop): positional callers and code that reads the
     signature are not disturbed.  The search reads them from self._search_options, a SearchOptions, for the time of the call."""
     @functools.wraps(fn)
     def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None, guide_k=5,
-             arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, beam_trace=False, beam_pick="score", **kw):
+             arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, beam_trace=False, beam_pick="score", offer=None,
+             **kw):
         prev = self._search_options
         self._search_options = SearchOptions(bool(exact_candidates), exclude, bool(no_repeat), bool(trace), guide, int(guide_k),
-                                             arrive_rank, arrive_lp, lookahead, bool(lookahead_record), bool(beam_trace), beam_pick)
+                                             arrive_rank, arrive_lp, lookahead, bool(lookahead_record), bool(beam_trace), beam_pick, offer=offer)
         try:
             return fn(self, *args, **kw)
         finally:
             self._search_options = prev
+    return call
+
+
+def _takes_offer(fn):
+    """Gives a front-end method its keyword offer=None (1-based item ids: offer_ids0), keyword only, the way
+    _takes_exact_candidates gives get_seq_in_batch its keywords: the declared parameter list stays what it was.  The method reads
+    it from self._call_offer for the time of the call."""
+    @functools.wraps(fn)
+    def call(self, *args, offer=None, **kw):
+        prev = getattr(self, "_call_offer", None)
+        self._call_offer = offer
+        try:
+            return fn(self, *args, **kw)
+        finally:
+            self._call_offer = prev
     return call
 
 
@@ -364,6 +385,22 @@ def pick_beam(paths, scores, lp_target, n_steps, targets, how="score"):
             order = np.lexsort((np.arange(W), -scores[b], -last[b]))
             out[b] = next(j for j in order if live[b, j])
     return out
+
+
+def offer_ids0(offer, n_item: int, device):
+    """The array irs_bind_offer_set takes (int64, 0-based ids) from a front end's `offer`: 1-based item ids in any order, a
+    tensor, an array or a list; repeats are dropped by the binding.  None: no offer set."""
+    if offer is None:
+        return None
+    ids = (offer.detach().to(device) if torch.is_tensor(offer) else torch.as_tensor(np.asarray(offer), device=device)).reshape(-1)
+    if ids.numel() == 0:
+        raise ValueError("offer: an empty set leaves nothing to offer (None: no offer set)")
+    if ids.dtype.is_floating_point or ids.dtype == torch.bool:
+        raise ValueError(f"offer: 1-based integer item ids (got {ids.dtype})")
+    ids = ids.to(torch.int64)
+    if int(ids.min().item()) < 1 or int(ids.max().item()) > n_item:
+        raise ValueError(f"offer: item ids must be in [1, n_item={n_item}]")
+    return ids - 1
 
 
 def exclusion_ids0(exclude, no_repeat, seqs, hep: int, device):
@@ -490,6 +527,7 @@ class IRSNN(nn.Module):
             rr.append(np.reciprocal(float(ranks[i])))
         return hit_count, np.array(rr)
 
+    @_takes_offer
     def predict_next(self, raw, seqs, users, top_k=20, gap_len=20, use_h=True):
         """The top_k items the model would show each user next (extension; the baselines' predict_next, reference sas.py:357-388):
         int64 [B, top_k] of 1-based ids, best first, 0 where fewer exist.  It is the list get_accuracy_metrics_in_batch cuts
@@ -497,7 +535,9 @@ class IRSNN(nn.Module):
         tensors of 1-based ids) left out when use_h, nothing left out otherwise -- the reference filters no window here.  Exact
         whatever the history hides of the top 100 (irs_recommend).  self.last_recommend holds ids, scores, log_probs, count and
         status of the call.  `raw` is bound as an exclusion set for the call and unbound afterwards, as
-        get_seq_in_batch(exclude=) does.  One device holds the catalog."""
+        get_seq_in_batch(exclude=) does.  offer=None (keyword only, taken by _takes_offer; 1-based item ids): the slate is taken from these items
+        only (irs_bind_offer_set, bound for the call); count is then the number of admissible items of the set, cut at top_k, and
+        log_probs stay the model's over the whole catalog.  One device holds the catalog."""
         hip = self.net._hip
         if hip.world != 1:
             raise ValueError("predict_next is not built for an item-sharded catalog")
@@ -519,10 +559,16 @@ class IRSNN(nn.Module):
         pos = torch.full((B,), L - (gap_len + 1) - 1, dtype=torch.int32, device=dev)
         xr = self.net.decode_rows(seqs.clone(), users, pos)
         eng = hip.get(B, B)
+        off = offer_ids0(self._call_offer, eng.n_item, dev)
         held = eng.bind_exclusions(excl, B) if excl is not None else None
+        held_off = None
         try:
+            held_off = eng.bind_offer_set(off, B) if off is not None else None
             val, ids0, lp, count, status = eng.recommend(xr, int(top_k), k=100, sweep=hip.sweep)
         finally:
+            if held_off is not None:
+                held_off.record_stream(torch.cuda.current_stream(dev))
+                eng.unbind_offer_set()
             if held is not None:
                 held.record_stream(torch.cuda.current_stream(dev))
                 eng.unbind_exclusions()
@@ -670,7 +716,13 @@ class IRSNN(nn.Module):
         beam_stop.  self.last_beam_trace = dict(lp_item, lp_target, rank_target [B, W, max_path_len], cut to 0 after each beam's
         arrival; paths, scores; n_steps [B, W]; picked [B]).  beam_pick="target" (needs beam_trace=True) returns, per user,
         the beam pick_beam names instead of beam 0: the live beam that reaches the target first, else the one that ends with the
-        target most probable.  The returned tuple keeps its shape."""
+        target most probable.  The returned tuple keeps its shape.
+        offer=None (extension, keyword only, taken the same way; one device, off by default): the offer set (irs_bind_offer_set).
+        offer: 1-based item ids, a tensor, an array or a list, shared by all users; every step of every search form then offers
+        items of the set only -- the persuasion path is made of items that may be shown.  A target outside the set is never
+        offered: put it in the set to make it reachable.  What describes the model (last_trace, beam scores, the lookahead's
+        and the arrival rule's values) stays a statement about the whole catalog.  Combine with exact_candidates=True where
+        the window can hide the best 100 of a small set."""
         opts = self._search_options
         greedy_kw = search_option_kwargs(opts, beam_width, sample, self.net._hip.world)
         exact_candidates, exclude, no_repeat = opts.exact_candidates, opts.exclude, opts.no_repeat
@@ -696,10 +748,12 @@ class IRSNN(nn.Module):
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if sample else 0
         ids0 = exclusion_ids0(exclude, no_repeat, seqs, L - (gap_len + 1) - 1, dev)
         excl = dict(exclude=ids0, no_repeat=no_repeat) if (ids0 is not None or no_repeat) else {}
+        off = offer_ids0(opts.offer, self.n_item, dev)
+        off = dict(offer=off) if off is not None else {}
         n_eng = B * (lookahead or 1)  # (the children of a lookahead step are decoded and scored in one call each)
         if beam_width > 1:
             all_paths, status, beam_traced = self._beam_paths(work, users, max_path_len, gap_len, beam_width, beam_stop, exact_candidates,
-                                                              excl, opts.beam_trace)
+                                                              {**excl, **off}, opts.beam_trace)
             paths_t = all_paths[:, 0].contiguous()
             if opts.beam_trace:  # (what beam_pick="target" names is decided on the host, from the trace as the caller will see it)
                 allp, alls = self.last_beams
@@ -716,18 +770,21 @@ class IRSNN(nn.Module):
             eng = hip.get(n_eng, n_eng)
             paths_t, status, _, _, *traced = eng.generate_paths_until(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
                                                                       sample=sample, sample_k=sample_k, seed=seed,
-                                                                      check_every=STOP_CHECK_EVERY, **excl, **greedy_kw)
+                                                                      check_every=STOP_CHECK_EVERY, **excl, **off, **greedy_kw)
         elif hip.world == 1:
             eng = hip.get(n_eng, n_eng)
             paths_t, status, *traced = eng.generate_paths(work, users, hep, max_path_len, k=100, sweep=hip.sweep,
                                                           sample=sample, sample_k=sample_k, seed=seed, use_graph=False, **excl,
-                                                          **greedy_kw)
+                                                          **off, **greedy_kw)
         else:  # item-sharded: irs_generate_paths_sharded (decode, row all-gather, shard sweep, key all-to-all, merge, path
             # step per search step, below the C ABI on one stream)
             eng = hip.get(B, B * hip.world)
             paths_t, status = eng.generate_paths_sharded(hip.comm, work, users, hep, max_path_len, k=100, sweep=hip.sweep,
                                                          sample=sample, sample_k=sample_k, seed=seed, use_graph=False)
         if int((status & IRS_ROW_NO_CANDIDATE).sum().item()) > 0:
+            if off and not excl:
+                raise IndexError("index 0 is out of bounds: every item of the offer set is already in the window"
+                                 + ("" if exact_candidates else " (among its best 100)"))
             if excl:
                 raise IndexError("index 0 is out of bounds: every admissible item is excluded (window + exclusion list"
                                  + (" + path)" if no_repeat else ")") + ("" if exact_candidates else " among the top-100 candidates"))

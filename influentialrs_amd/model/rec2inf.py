@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from .._lib import IRS_ROW_NO_CANDIDATE
-from .influentialRS import STOP_CHECK_EVERY, SearchOptions, exclusion_ids0, path_trace_summary, search_option_kwargs
+from .influentialRS import STOP_CHECK_EVERY, SearchOptions, exclusion_ids0, _takes_offer, offer_ids0, path_trace_summary, search_option_kwargs
 from .layers import get_item_index
 
 
@@ -53,6 +53,7 @@ class Rec2Inf(nn.Module):
         self.net = net.module if isinstance(net, nn.DataParallel) else net
         self.device = device
 
+    @_takes_offer
     def get_seq_in_batch(self, seqs, targets, guide, guide_k=5, max_path_len=20, stop_at_target=True, exclude=None,
                          no_repeat=False, exact_candidates=False, trace=False):
         """Persuasion paths by the Rec2Inf rule: returns (paths float32 [B, max_path_len], targets int64 [B], list of B history
@@ -63,7 +64,8 @@ class Rec2Inf(nn.Module):
         stop_at_target=True stops decoding a user once it has arrived (irs_generate_paths_until), as get_path does; False runs
         every step and cuts on the host: the same paths.
         exclude / no_repeat / exact_candidates / trace: as in IRSNN.get_seq_in_batch.  exclude with the users' whole histories
-        is the reference's predict_next(use_h=True), which drops the history and not only the window."""
+        is the reference's predict_next(use_h=True), which drops the history and not only the window.
+        offer=None (keyword only, taken by _takes_offer; 1-based item ids): as in IRSNN.get_seq_in_batch -- the path is made of items of the set."""
         if guide is None:
             raise ValueError("Rec2Inf needs a guide: a [n_item + 1, F] feature table (for the plain greedy path use guide_k=1)")
         # (the guide's own checks, as IRSNN.get_seq_in_batch makes them; the sharded catalog is refused below in this handler's words)
@@ -80,7 +82,8 @@ class Rec2Inf(nn.Module):
         ids0 = exclusion_ids0(exclude, no_repeat, work, L - 2, dev)
         excl = dict(exclude=ids0, no_repeat=no_repeat) if (ids0 is not None or no_repeat) else {}
         eng = hip.get(B, B)
-        common = dict(k=100, sweep=hip.sweep, **options, **excl)
+        off = offer_ids0(self._call_offer, self.n_item, dev)
+        common = dict(k=100, sweep=hip.sweep, **options, **excl, **(dict(offer=off) if off is not None else {}))
         if stop_at_target:
             paths_t, status, _, _, *traced = eng.generate_paths_until(work, None, hep, max_path_len, check_every=STOP_CHECK_EVERY,
                                                                       **common)
