@@ -1011,6 +1011,65 @@ int irs_arrival_offer(irs_ctx *ctx, const int64_t *dev_seq, const int32_t *dev_h
                       float *dev_val, int64_t *dev_ids0, int32_t k, int32_t rank_max, float lp_min, const float *dev_paths,
                       int32_t path_ld, int32_t step, const int32_t *dev_row_map, int32_t *dev_status, void *stream);
 
+/* ---- beam rule: an arrival rule and a target-aware ranking on beam trace state (opt-in, off by default; BUILD-DEFINED like the
+ *      beam search itself.  Without it a beam search ranks by acceptance alone -- the cumulative log-probability of the offered
+ *      items -- and meets the target only where it happens to be a beam's most probable admissible child) ----------------------
+ * A separate option from the arrival rule above: what irs_set_arrival_rule admits and refuses is unchanged, and the beam loops
+ * still refuse it.  A context can hold one BEAM RULE, irs_set_beam_rule(ctx, rank_max, lp_min, target_weight):
+ *   rank_max and lp_min mean what they mean in irs_set_arrival_rule: rank_max >= 1 turns the rank clause on, 0 turns it off,
+ *     rank_max < 0 -> IRS_E_INVALID; lp_min <= 0 turns the probability clause on (-inf included), lp_min > 0 or NaN turns it off.
+ *   target_weight is lambda: finite and >= 0, 0 turns the ranking off; negative, NaN or infinite -> IRS_E_INVALID.
+ *   All three off clears the rule.  Setting a rule on a context with world != 1 -> IRS_E_UNSUPPORTED.
+ *   Setting, changing or clearing the rule drops the captured steps, so a captured step never meets another rule.
+ * The rule reads what the beam trace's sweep leaves on the device and nothing else: while a rule is set, irs_beam_search (stream
+ * launches and the two captured ping-pong steps alike) and irs_beam_search_until need a bound beam trace (irs_bind_beam_trace)
+ * and return IRS_E_STATE, with a message that names both calls, before any launch, without one.  With one they run, per step:
+ * decode, top-k (+ lse), the survivor pass if bound, the trace sweep, the RULED step, the carry (unchanged), the step counter.
+ * Every other search entry point -- irs_generate_paths[_until], irs_path_step, irs_beam_step[_until], irs_beam_step_linked and
+ * the two _sharded loops -- returns IRS_E_UNSUPPORTED with a message that names the rule: it is never silently ignored.
+ *
+ * A ruled step.  For a live, unfinished input beam row r of a user that is not done, let
+ *   t   = seq[r][L-1],  rk = dev_rank[r],
+ *   lpt = rk ? (float)((double)ts - ((double)max + log((double)sumexp))) : 0 -- the very expression the beam trace stores as
+ *         lp_target, so that every decision can be replayed from the recorded arrays alone.
+ * 1. ARRIVAL.  The rule fires for r when rk != 0, a clause holds -- the rank clause is on and rk <= rank_max, or the probability
+ *    clause is on and lpt >= lp_min (a NaN never fires) -- and t is admissible under the beam step's own test: it lies in
+ *    [1, n_item], outside the window seq[r][0 .. hep[r]], outside the bound exclusion list of the user, under no_repeat outside
+ *    the beam's own path [0, step), and inside a bound offer set (irs_bind_offer_set).  A fired beam contributes exactly ONE
+ *    candidate, the target: index parent * W + 0, list value ts, score cum + ((double)ts - norm) with the step's usual
+ *    norm = (double)lse_max + log((double)lse_sum) (no norm at W == 1).  Its ranked list is not walked and not rewritten, and
+ *    IRS_ROW_OFFERED is OR-ed into the user's status word (through the until loop's map).  In the until forms the child is
+ *    finished by the existing end-symbol test; in the plain forms the search goes on behind the arrival, as the greedy loop does.
+ *    The carry then gives lp_item == lp_target bit for bit at a fired step.
+ * 2. RANKING.  Every candidate keeps its acceptance score s = cum_parent + log p(item | parent): dev_cum_out, dev_scores and the
+ *    trace hold what they held.  The candidates are ORDERED by the key s + (double)lambda * (double)bonus, descending, then by
+ *    index ascending.  bonus = lpt(r) for the children of row r, 0 for a row without a target or with a NaN lpt, and 0 for a
+ *    finished beam that re-enters as itself (it has arrived: 0 is the largest value lpt can take).  This is the one-step-lagged
+ *    form of sum log p(item) + lambda * lp_target(state): the term is common to all children of a parent, so it decides between
+ *    prefixes, costs no decode and carries no state across steps.  At lambda == 0 the key IS s (0 * -inf is never formed), and a
+ *    ruled step with both clauses off besides would be the linked step bit for bit.
+ * 3. STOP RULES.  IRS_BEAM_STOP_BEST stays "done once output beam 0 is finished".  Under lambda > 0 the argument that BEST
+ *    returns what ALL would (irs_beam_search_until) no longer holds: a child's bonus can exceed its parent's, so a later
+ *    candidate's key can overtake a finished beam 0.  BEST then returns the earlier answer.
+ * 4. RETURNED SCORES.  dev_scores / dev_cum_out are acceptance sums in KEY order: with lambda > 0 they need not be descending.
+ *
+ * irs_beam_step_ruled is the step alone: irs_beam_step_linked's arguments, checks and outputs (the until form when dev_fin_in,
+ * dev_fin_out and dev_done are all given; it refuses what irs_beam_step_linked refuses and looks at neither a bound beam trace nor
+ * a set rule), then
+ *  dev_max / dev_sumexp / dev_target_score float [B*W], dev_rank int32 [B*W]: irs_score_target_trace on the step's INPUT rows
+ *  rank_max, lp_min, target_weight: as in irs_set_beam_rule; all three off -> IRS_E_INVALID
+ * It honours bound exclusions and a bound offer set's membership for the target, as irs_arrival_offer does.  Null pointers and
+ * bad values -> IRS_E_INVALID; world != 1 -> IRS_E_UNSUPPORTED; all before the launch.  SYNCHRONOUS on the null stream, like
+ * irs_beam_step_linked.  No float atomics; the status word takes an integer atomic OR: identical calls give identical bytes. */
+int irs_set_beam_rule(irs_ctx *ctx, int32_t rank_max, float lp_min, float target_weight);
+int irs_beam_step_ruled(irs_ctx *ctx, const int64_t *dev_seq_in, const int32_t *dev_hep_in, const double *dev_cum_in,
+                        const float *dev_paths_in, const int32_t *dev_fin_in, const float *dev_val, const int64_t *dev_ids0,
+                        const float *dev_lse_max, const float *dev_lse_sum, int32_t B, int32_t W, int32_t k, int32_t step,
+                        int32_t P, int32_t stop_rule, int64_t *dev_seq_out, int32_t *dev_hep_out, double *dev_cum_out,
+                        float *dev_paths_out, int32_t *dev_fin_out, int32_t *dev_done, int32_t *dev_status, int32_t *dev_link,
+                        float *dev_link_val, const float *dev_max, const float *dev_sumexp, const float *dev_target_score,
+                        const int32_t *dev_rank, int32_t rank_max, float lp_min, float target_weight);
+
 /* ---- path replay: every step of SAVED paths scored in one batched pass (opt-in; replaces the Python loop of dependent launches
  *      of Evaluator.get_grad_in_batch, evaluator.py:162-243 -- one decode + LogSoftmax + gather per step -- and the two extra
  *      decodes of get_rr_increase_in_batch, evaluator.py:245-290; and gives the loops that carry no trace -- beam, sharded, paths

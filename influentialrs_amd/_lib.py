@@ -17,7 +17,7 @@ IRS_MASK_IRN, IRS_MASK_CAUSAL = 0, 1
 IRS_CREATE_LONG_WINDOWS, IRS_MAX_LEN_LONG = 1, 1024  # irs_create_ex: max_len above 256
 IRS_SWEEP_BF16, IRS_SWEEP_F32, IRS_SWEEP_EXHAUSTIVE = 0, 1, 2
 IRS_ROW_FALLBACK, IRS_ROW_NO_CANDIDATE, IRS_ROW_FEWER_THAN_K, IRS_ROW_RESCUED = 1, 2, 4, 8
-IRS_ROW_OFFERED = 16  # irs_set_arrival_rule: the row's list was rewritten to the target alone
+IRS_ROW_OFFERED = 16  # irs_set_arrival_rule: the row's list was rewritten to the target alone; irs_set_beam_rule: a beam of the user was offered its target
 IRS_GEMM_F32, IRS_GEMM_X6, IRS_GEMM_H3 = 0, 1, 2
 IRS_BEAM_STOP_ALL, IRS_BEAM_STOP_BEST = 0, 1
 IRS_GUIDE_BINARY, IRS_GUIDE_FLOAT = 1, 2  # irs_bind_guide
@@ -141,6 +141,11 @@ SIGNATURES = {
     "irs_arrival_offer": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                     c_void_p]),
+    "irs_set_beam_rule": (c_int32, [c_void_p, c_int32, c_float, c_float]),
+    "irs_beam_step_ruled": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int32, c_float, c_float]),
     "irs_replay_scratch_bytes": (c_size_t, [c_void_p, c_int32]),
     "irs_replay_windows": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p,
                                      c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -730,6 +730,14 @@ static int args_btrace(irs_ctx *ctx, const char *fn, const search_call &c) {
     return IRS_OK;
 }
 
+// a beam rule reads what the beam trace's sweep leaves in the bound scratch
+static int args_brule(irs_ctx *ctx, const char *fn, const search_call &) {
+    if (!ctx->opt.btrace.on)
+        IRS_FAIL(ctx, IRS_E_STATE, "%s: a beam rule is set (irs_set_beam_rule) and no beam trace is bound (irs_bind_beam_trace): "
+                                   "the rule reads what the trace sweep leaves", fn);
+    return IRS_OK;
+}
+
 // an offer set: one pass of the bound scratch serves the call's rows
 static int args_offer(irs_ctx *ctx, const char *fn, const search_call &c) {
     const int rows = c.W ? c.B * c.W : c.B;
@@ -743,7 +751,7 @@ static int args_offer(irs_ctx *ctx, const char *fn, const search_call &c) {
 // refusal, which every option has (a shard sees its own items only; most bindings refuse a sharded context themselves, so a
 // binding cannot exist there, and must not be ignored if it does).  loops_only: why every entry point but the two beam LOOPS
 // refuses it (the same message form); null for the options the greedy side admits
-enum { OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_BTRACE, OPT_OFFER, OPT_N };
+enum { OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_BTRACE, OPT_OFFER, OPT_BRULE, OPT_N };
 static const struct {
     bool (*on)(const irs_search_opts &);
     int (*args)(irs_ctx *, const char *, const search_call &);
@@ -766,6 +774,8 @@ static const struct {
      "irs_beam_search and irs_beam_search_until only"},
     {[](const irs_search_opts &o) { return o.offer.on != 0; }, args_offer, nullptr, nullptr,
      "%s: a bound offer set (irs_bind_offer_set) needs the whole catalog on one device"},
+    {[](const irs_search_opts &o) { return o.brule.on != 0; }, args_brule, "a beam rule is set (irs_set_beam_rule)", nullptr,
+     "%s: a beam rule (irs_set_beam_rule) needs the whole catalog on one device", "irs_beam_search and irs_beam_search_until only"},
 };
 
 // ---- the entry points, one row each: what it checks, in its order -- the first failing check decides the code and the message.
@@ -778,19 +788,24 @@ static const struct {
 // A bound offer set is looked at last by the loops; the standalone steps and irs_recommend_take are kernels on the caller's
 // lists and do not look at it (irs_recommend, which ranks inside the set, makes the set's argument check itself).  The set's
 // sharded refusal is defensive: irs_bind_offer_set refuses a sharded context, so no test can reach it.
-enum { AT_GREEDY_LOOP, AT_PATH_STEP, AT_BEAM_STEP, AT_BEAM_LOOP, AT_SHARDED_LOOP, AT_BEAM_STEP_LINKED, AT_RECOMMEND };
+// A beam rule (irs_set_beam_rule) is refused right behind a bound beam trace wherever that is refused, and by irs_beam_step_linked;
+// the beam loops look at it (is a beam trace bound?) behind the arrival rule and before readiness, so that a rule without a trace
+// is answered before anything else of the call.  AT_BEAM_STEP_RULED, the rule's own step (irs_beam_step_ruled), takes the rule as
+// arguments and looks at neither.
+enum { AT_GREEDY_LOOP, AT_PATH_STEP, AT_BEAM_STEP, AT_BEAM_LOOP, AT_SHARDED_LOOP, AT_BEAM_STEP_LINKED, AT_RECOMMEND, AT_BEAM_STEP_RULED };
 enum { DO_READY = OPT_N, DO_WORLD, DO_SHAPE, DO_K, DO_END };
-static const int PLAN[][14] = {
-    /* AT_GREEDY_LOOP  */ {OPT_BTRACE, OPT_ARRIVE, OPT_GUIDE, OPT_LOOK, DO_READY, DO_WORLD, DO_SHAPE, OPT_TRACE, DO_K, OPT_EXCL, OPT_SURV, OPT_OFFER, DO_END},
-    /* AT_PATH_STEP    */ {OPT_BTRACE, OPT_EXCL, OPT_GUIDE, DO_END},
-    /* AT_BEAM_STEP    */ {OPT_BTRACE, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
-    /* AT_BEAM_LOOP    */ {OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, DO_READY, DO_WORLD, OPT_TRACE, DO_SHAPE, OPT_BTRACE, DO_K, OPT_EXCL, OPT_SURV, OPT_OFFER, DO_END},
-    /* AT_SHARDED_LOOP */ {OPT_BTRACE, OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_OFFER, DO_END},
-    /* AT_BEAM_STEP_LINKED */ {OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
+static const int PLAN[][16] = {
+    /* AT_GREEDY_LOOP  */ {OPT_BTRACE, OPT_BRULE, OPT_ARRIVE, OPT_GUIDE, OPT_LOOK, DO_READY, DO_WORLD, DO_SHAPE, OPT_TRACE, DO_K, OPT_EXCL, OPT_SURV, OPT_OFFER, DO_END},
+    /* AT_PATH_STEP    */ {OPT_BTRACE, OPT_BRULE, OPT_EXCL, OPT_GUIDE, DO_END},
+    /* AT_BEAM_STEP    */ {OPT_BTRACE, OPT_BRULE, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
+    /* AT_BEAM_LOOP    */ {OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_BRULE, DO_READY, DO_WORLD, OPT_TRACE, DO_SHAPE, OPT_BTRACE, DO_K, OPT_EXCL, OPT_SURV, OPT_OFFER, DO_END},
+    /* AT_SHARDED_LOOP */ {OPT_BTRACE, OPT_BRULE, OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_OFFER, DO_END},
+    /* AT_BEAM_STEP_LINKED */ {OPT_BRULE, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
     /* AT_RECOMMEND    */ {OPT_EXCL, DO_END},
+    /* AT_BEAM_STEP_RULED */ {OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
 };
 static int search_rules(irs_ctx *ctx, const char *fn, int at, const search_call &c) {
-    const bool beam = at == AT_BEAM_STEP || at == AT_BEAM_LOOP || at == AT_BEAM_STEP_LINKED;
+    const bool beam = at == AT_BEAM_STEP || at == AT_BEAM_LOOP || at == AT_BEAM_STEP_LINKED || at == AT_BEAM_STEP_RULED;
     int rc;
     for (const int *p = PLAN[at]; *p != DO_END; ++p) {
         switch (*p) {
@@ -1356,6 +1371,23 @@ extern "C" int irs_arrival_offer(irs_ctx *ctx, const int64_t *seq, const int32_t
                                     excl_args(ctx, 1, row_map, paths, path_ld, 1, nullptr, step), (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------ beam rule (irs_set_beam_rule; path.hip: k_beam_step's ruled form)
+static bool beam_weight_ok(float w) { return w >= 0.f && w <= 3.402823466e38f; } // finite and >= 0 (a NaN fails both)
+
+extern "C" int irs_set_beam_rule(irs_ctx *ctx, int32_t rank_max, float lp_min, float target_weight) {
+    if (!ctx) return IRS_E_INVALID;
+    if (rank_max < 0) IRS_FAIL(ctx, IRS_E_INVALID, "irs_set_beam_rule: rank_max must be >= 0 (0: the rank clause is off)");
+    if (!beam_weight_ok(target_weight)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_set_beam_rule: target_weight must be finite and >= 0 (0: ranking is off)");
+    const int lp_on = irs_arrival_lp_on(lp_min) ? 1 : 0;
+    const int on = (rank_max >= 1 || lp_on || target_weight > 0.f) ? 1 : 0;
+    if (on && ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_set_beam_rule needs the whole catalog on one device");
+    const float lp = lp_on ? lp_min : (on ? __builtin_nanf("") : 0.f); // (what the kernel takes: NaN is "clause off")
+    auto &r = ctx->opt.brule;
+    if (on != r.on || rank_max != r.rank || lp_on != r.lp_on || memcmp(&lp, &r.lp, sizeof(lp)) || target_weight != r.weight) opts_changed(ctx);
+    r = {on, on ? rank_max : 0, lp_on, lp, on ? target_weight : 0.f};
+    return IRS_OK;
+}
+
 // ------------------------------------------------------------------ path replay (replay.hip)
 static int replay_chunk_max(const irs_ctx *ctx) { return ctx->max_rows < ctx->max_seqs ? ctx->max_rows : ctx->max_seqs; }
 
@@ -1651,7 +1683,14 @@ static int enqueue_beam_step(irs_ctx *ctx, int in, const int64_t *user, int B, i
     irs_beam_trace_layout(bt.scratch, bt.users * bt.W, &tr, &lk);
     if ((rc = irs_launch_target_trace(ctx, ctx->xrows, ctx->bm[in].seq, ctx->bm[in].hep, rows, tr, tr.mx, tr.sm, tr.ts, tr.rank, s))) return rc;
     const irs_beam_cand cand{ctx->top_val, ctx->top_ids, lmax, lsum, k, ex};
-    if ((rc = irs_launch_beam_step(ctx, ctx->bm[in], ctx->bm[in ^ 1], cand, B, W, 0, ctx->step_ctr, P, status, until, s, &lk))) return rc;
+    // a beam rule: the ruled form of the linked step reads the sweep's four values where the sweep has just left them
+    const auto &br = ctx->opt.brule;
+    const auto &of = ctx->opt.offer;
+    const irs_beam_rule ru{tr.mx, tr.sm, tr.ts, tr.rank, br.rank, br.lp, br.weight, ctx->dims.n_item, of.on ? of.ids : nullptr,
+                           of.on ? (int)of.n : 0};
+    if ((rc = irs_launch_beam_step(ctx, ctx->bm[in], ctx->bm[in ^ 1], cand, B, W, 0, ctx->step_ctr, P, status, until, s, &lk,
+                                   br.on ? &ru : nullptr)))
+        return rc;
     const irs_beam_carry_args ca{lk, tr.mx, tr.sm, tr.ts, tr.rank, W, bt.ld, 0, ctx->step_ctr, bt.item, bt.target, bt.rank,
                                  until ? until->map : nullptr};
     if ((rc = irs_launch_beam_trace_carry(ctx, ca, B, s))) return rc;
@@ -1745,6 +1784,43 @@ extern "C" int irs_beam_step_linked(irs_ctx *ctx, const int64_t *seq_in, const i
     return look_run_sync(ctx, irs_launch_beam_step(ctx, beam_state(seq_in, hep_in, cum_in, paths_in, fin_in),
                                                    {seq_out, hep_out, cum_out, paths_out, fin_out}, cand, B, W, step, nullptr, P, status,
                                                    until_form ? &until : nullptr, nullptr, &lk));
+}
+
+// the linked step under a rule given as arguments (irs_hip.h, "beam rule"): what the loops launch while irs_set_beam_rule holds one
+extern "C" int irs_beam_step_ruled(irs_ctx *ctx, const int64_t *seq_in, const int32_t *hep_in, const double *cum_in,
+                                   const float *paths_in, const int32_t *fin_in, const float *val, const int64_t *ids0,
+                                   const float *lse_max, const float *lse_sum, int32_t B, int32_t W, int32_t k, int32_t step,
+                                   int32_t P, int32_t stop_rule, int64_t *seq_out, int32_t *hep_out, double *cum_out,
+                                   float *paths_out, int32_t *fin_out, int32_t *done, int32_t *status, int32_t *link,
+                                   float *link_val, const float *mx, const float *sm, const float *tscore, const int32_t *rank,
+                                   int32_t rank_max, float lp_min, float target_weight) {
+    if (!ctx) return IRS_E_INVALID;
+    if (!seq_in || !hep_in || !cum_in || !paths_in || !val || !ids0 || !seq_out || !hep_out || !cum_out || !paths_out || !status ||
+        !link || !link_val || !mx || !sm || !tscore || !rank || B < 1 || W < 1 || k < 1 || P < 1 || step < 0 || step >= P)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_ruled: bad arguments");
+    const bool until_form = fin_in && fin_out && done;
+    if (!until_form && (fin_in || fin_out || done))
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_ruled: dev_fin_in, dev_fin_out and dev_done go together");
+    if (W > 1 && (!lse_max || !lse_sum)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_ruled: W > 1 needs the row log-sum-exp");
+    if (until_form && stop_rule != IRS_BEAM_STOP_ALL && stop_rule != IRS_BEAM_STOP_BEST)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_ruled: stop_rule %d (IRS_BEAM_STOP_ALL or IRS_BEAM_STOP_BEST)", stop_rule);
+    if (rank_max < 0) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_ruled: rank_max must be >= 0 (0: the rank clause is off)");
+    if (!beam_weight_ok(target_weight)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_ruled: target_weight must be finite and >= 0 (0: ranking is off)");
+    const bool lp_on = irs_arrival_lp_on(lp_min);
+    if (rank_max == 0 && !lp_on && !(target_weight > 0.f)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_beam_step_ruled: all clauses are off");
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_beam_step_ruled needs the whole catalog on one device");
+    const int rc = search_rules(ctx, "irs_beam_step_ruled", AT_BEAM_STEP_RULED, search_call{B, W, P, k, 0, 0, 0, true});
+    if (rc) return rc;
+    const irs_beam_cand cand{val, ids0, W > 1 ? lse_max : nullptr, W > 1 ? lse_sum : nullptr, k,
+                             excl_args(ctx, W, nullptr, paths_in, P, 0, nullptr, step)};
+    const irs_beam_until until{done, nullptr, stop_rule};
+    const irs_beam_link lk{link, link_val};
+    const auto &of = ctx->opt.offer;
+    const irs_beam_rule ru{mx, sm, tscore, rank, rank_max, lp_on ? lp_min : __builtin_nanf(""), target_weight, ctx->dims.n_item,
+                           of.on ? of.ids : nullptr, of.on ? (int)of.n : 0};
+    return look_run_sync(ctx, irs_launch_beam_step(ctx, beam_state(seq_in, hep_in, cum_in, paths_in, fin_in),
+                                                   {seq_out, hep_out, cum_out, paths_out, fin_out}, cand, B, W, step, nullptr, P, status,
+                                                   until_form ? &until : nullptr, nullptr, &lk, &ru));
 }
 
 // The loop.  The beam state of the live users sits in side `cur` of ctx->bm; a step reads it and writes side cur ^ 1, a compaction

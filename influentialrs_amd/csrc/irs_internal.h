@@ -165,6 +165,18 @@ static inline size_t irs_beam_trace_layout(void *base, int rows, irs_trace_rows 
     if (lk) lk->link = (int32_t *)((char *)base + head), lk->val = (float *)((char *)base + head + r4);
     return head + 2 * r4;
 }
+// ---- beam rule (irs_set_beam_rule; path.hip: the ruled form of k_beam_step).  What the ruled step takes behind the link: the
+// trace sweep's four values on the step's INPUT rows, the rule, and what the arrival test needs besides the step's own arguments.
+struct irs_beam_rule {
+    const float *mx, *sm, *ts; // [B * W]
+    const int32_t *rank;       // [B * W]
+    int rank_max;              // 0: the rank clause is off
+    float lp_min;              // NaN: the probability clause is off
+    float weight;              // lambda >= 0; 0: the key is the score
+    int64_t n_item;
+    const int64_t *oset;       // a bound offer set's ascending ids0 (null: none): a target outside it is not offered
+    int on;                    // ids in oset
+};
 struct irs_beam_carry_args { // irs_beam_trace_carry's arguments as the kernel takes them
     irs_beam_link lk;                  // by launch row b * W + j
     const float *mx, *sm, *ts;         // [B * W] the sweep's results on the step's INPUT rows
@@ -342,6 +354,14 @@ struct irs_search_opts {
         int users, W, ld;
         void *scratch;
     } btrace;
+
+    // beam rule (irs_set_beam_rule): behind the trace sweep of the two beam loops, the ruled beam step offers the target to a beam
+    // whose target stands at rank <= rank (0: clause off) or at log-probability >= lp (lp_on), and orders the candidates by
+    // score + weight * lp_target(parent); needs a bound beam trace, every other search entry point refuses
+    struct {
+        int on, rank, lp_on;
+        float lp, weight;
+    } brule;
 
     // offer set (irs_bind_offer_set): the sanitised ids and the score pass in the caller's scratch (irs_offer_layout) while bound;
     // irs_score_topk_offer ranks inside it, and the single-device loops, irs_recommend, the survivor pass and the arrival rule read
@@ -662,9 +682,10 @@ int irs_launch_beam_init(irs_ctx *ctx, const int64_t *seq0, const int64_t *user0
                          const irs_beam_state &st, int64_t *user, hipStream_t s);
 // until == nullptr: the plain step (fin is not touched); else the step of irs_beam_step_until / irs_beam_search_until
 // link != nullptr: the linked form of either, which also writes link->link / link->val (irs_beam_link)
+// rule != nullptr (with a link): the ruled form of the linked step (irs_beam_rule)
 int irs_launch_beam_step(irs_ctx *ctx, const irs_beam_state &in, const irs_beam_state &out, const irs_beam_cand &cand, int B, int W,
                          int step, const int32_t *step_ptr, int P, int32_t *status, const irs_beam_until *until, hipStream_t s,
-                         const irs_beam_link *link = nullptr);
+                         const irs_beam_link *link = nullptr, const irs_beam_rule *rule = nullptr);
 
 // ---- beam_trace.hip ---- (arguments already validated: 1 <= W <= 32, 1 <= ld <= IRS_MAX_PATH)
 int irs_launch_beam_trace_carry(irs_ctx *ctx, const irs_beam_carry_args &a, int B, hipStream_t s);

@@ -118,17 +118,42 @@ __global__ void __launch_bounds__(256) k_merge(const float *__restrict__ val_in,
 // chosen candidate's list value: what the carry kernel (beam_trace.hip) needs to move a beam's recorded columns along.  The link
 // is a parameter PACK so that the forms without it keep their kernel arguments -- the offsets of the hidden ones behind them
 // included -- and with them their instructions: every addition sits behind `if constexpr (LINK)`.
+// RULED (irs_beam_step_ruled, the loops under irs_set_beam_rule): a second trailing argument, irs_beam_rule, makes the ruled form
+// of the linked step; again a member of the pack, and every addition sits behind `if constexpr (RULED)`.
+//   phase 1: a live unfinished beam reads its row's four sweep values once (the same address in every lane) and forms lpt, the
+//     expression the beam trace stores as lp_target.  If the arrival test holds -- a clause, and the target admissible under the
+//     walk's own test: a catalog item outside the window, the user's list, (no_repeat) the beam's path, and inside a bound offer set
+//     (k_arrival_offer's search) -- the target is the beam's ONE candidate, with its sweep score as list value, and the list is not
+//     walked; IRS_ROW_OFFERED goes to the user's status word.  Otherwise the walk, as ever.  Beside every score a KEY is kept in
+//     LDS: score + (double)weight * (double)lpt of the parent (0 without a target, at a NaN lpt, for a finished beam, and at
+//     weight == 0, so that 0 * -inf is never formed).
+//   phase 2 ranks by (key desc, index asc); at weight == 0 the key has the score's bits and the order is the linked step's.
+//   phase 3 is the linked step's: out.cum is the SCORE.  The end-symbol test makes the child of a fired beam finished.
+// LDS: 8 + 8 + 4 + 8 KB of candidate arrays (28 KB of the 64 KB a workgroup may take); no float atomics.
 #define BEAM_MAXW 32
-template <typename T>
-__device__ __forceinline__ const T &irs_pack_first(const T &t) { return t; }
+template <typename T, typename... R>
+__device__ __forceinline__ const T &irs_pack_first(const T &t, const R &...) { return t; }
+template <typename T, typename U>
+__device__ __forceinline__ const U &irs_pack_second(const T &, const U &u) { return u; }
+// the ruled key's two operations, each rounded on its own as irs_hip.h states them: s + (double)lambda * (double)bonus is never
+// contracted into one fused multiply-add, so that a replay in plain float64 forms the same bits
+__device__ __forceinline__ double irs_beam_bonus(float weight, float lpt) {
+#pragma clang fp contract(off)
+    return (double)weight * (double)lpt;
+}
+__device__ __forceinline__ double irs_beam_key(double score, double add) {
+#pragma clang fp contract(off)
+    return score + add;
+}
 template <bool UNTIL, bool EXCL, int SLOTS, typename... LK>
 __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, const irs_beam_state out, const irs_beam_cand cand,
                                                     int W, int L, int step_arg, const int32_t *__restrict__ step_ptr, int P,
                                                     int32_t *__restrict__ status, const irs_beam_until until, const LK... lk) {
-    constexpr bool LINK = sizeof...(LK) != 0;
+    constexpr bool LINK = sizeof...(LK) != 0, RULED = sizeof...(LK) == 2;
     __shared__ double c_score[BEAM_MAXW * BEAM_MAXW];
     __shared__ int64_t c_item[BEAM_MAXW * BEAM_MAXW];
     __shared__ float c_val[LINK ? BEAM_MAXW * BEAM_MAXW : 1]; // (LINK only: never referenced otherwise)
+    __shared__ double c_key[RULED ? BEAM_MAXW * BEAM_MAXW : 1]; // (RULED only, likewise)
     __shared__ int c_order[BEAM_MAXW];
     __shared__ int s_flags[2]; // UNTIL: [0] some output beam is live and unfinished, [1] output beam 0 is finished
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, nthr = blockDim.x;
@@ -168,7 +193,10 @@ __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, con
         int found = 0;
         if constexpr (UNTIL) {
             if (in.fin[row]) { // a finished beam: itself, with its final score; its lists are not read
-                if (lane == 0 && cj > -INFINITY) c_score[j * W] = cj;
+                if (lane == 0 && cj > -INFINITY) {
+                    c_score[j * W] = cj;
+                    if constexpr (RULED) c_key[j * W] = cj; // (it has arrived: bonus 0, the largest lp_target there is)
+                }
                 continue;
             }
         }
@@ -181,6 +209,38 @@ __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, con
             irs_excl_view ev = {};
             if constexpr (EXCL) ev = irs_excl_open(cand.ex, row, lane, step);
             bool more = true;
+            double add = 0.0; // RULED: weight * lp_target of this row, the term every child of the beam carries in its key
+            if constexpr (RULED) {
+                const irs_beam_rule &ru = irs_pack_second(lk...);
+                const int rk = ru.rank[row];
+                if (rk != 0) {
+                    const float tsv = ru.ts[row];
+                    const float lpt = (float)((double)tsv - ((double)ru.mx[row] + log((double)ru.sm[row])));
+                    if (ru.weight > 0.f && lpt == lpt) add = irs_beam_bonus(ru.weight, lpt);
+                    // (a NaN lpt, or a NaN lp_min -- the clause is off --, never fires)
+                    bool fire = (ru.rank_max >= 1 && rk <= ru.rank_max) || lpt >= ru.lp_min;
+                    const int64_t t = w[L - 1];
+                    fire = fire && t >= 1 && t <= ru.n_item;
+                    if (fire && ru.oset) fire = irs_excl_listed(ru.oset, ru.on, t - 1); // (the same search in every lane)
+                    if (fire) {
+                        bool hit = false, listed = false;
+                        if constexpr (EXCL) {
+                            hit = (ev.pth == t);
+                            listed = irs_excl_listed(ev.list, ev.n, t - 1); // (the same search in every lane)
+                        }
+                        hit = win.holds(t, hit);
+                        if (!__any(hit) && !listed) { // the target alone: the list is not walked
+                            if (lane == 0) {
+                                const double sc = cj + ((double)tsv - norm);
+                                c_score[j * W] = sc, c_key[j * W] = irs_beam_key(sc, add);
+                                c_item[j * W] = t, c_val[j * W] = tsv;
+                                atomicOr(&status[(UNTIL && until.map) ? until.map[b] : b], IRS_ROW_OFFERED);
+                            }
+                            found = 1, more = false;
+                        }
+                    }
+                }
+            }
             for (int c0 = 0; c0 < k && found < W && more; c0 += 64) { // 64 candidates per round, one per lane
                 const int cl = c0 + lane;
                 const int64_t cid = cl < k ? cand.ids0[(size_t)row * k + cl] : (int64_t)-1;
@@ -204,6 +264,7 @@ __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, con
                             c_score[j * W + found] = cj + ((double)v - norm);
                             c_item[j * W + found] = item;
                             if constexpr (LINK) c_val[j * W + found] = v;
+                            if constexpr (RULED) c_key[j * W + found] = irs_beam_key(cj + ((double)v - norm), add);
                         }
                         ++found;
                     }
@@ -218,9 +279,17 @@ __global__ void __launch_bounds__(1024) k_beam_step(const irs_beam_state in, con
         const double sx = c_score[x];
         if (sx > -INFINITY) {
             int rank = 0;
-            for (int y = 0; y < WW; ++y) {
-                const double sy = c_score[y];
-                rank += (sy > sx || (sy == sx && y < x)) ? 1 : 0;
+            if constexpr (RULED) { // by key, among the slots that hold a candidate (a key may be -inf; a score of one is not)
+                const double kx = c_key[x];
+                for (int y = 0; y < WW; ++y) {
+                    const double ky = c_key[y];
+                    rank += (c_score[y] > -INFINITY && (ky > kx || (ky == kx && y < x))) ? 1 : 0;
+                }
+            } else {
+                for (int y = 0; y < WW; ++y) {
+                    const double sy = c_score[y];
+                    rank += (sy > sx || (sy == sx && y < x)) ? 1 : 0;
+                }
             }
             if (rank < W) c_order[rank] = x;
         }
@@ -325,10 +394,23 @@ int irs_launch_beam_init(irs_ctx *ctx, const int64_t *seq0, const int64_t *user0
 
 int irs_launch_beam_step(irs_ctx *ctx, const irs_beam_state &in, const irs_beam_state &out, const irs_beam_cand &cand, int B, int W,
                          int step, const int32_t *step_ptr, int P, int32_t *status, const irs_beam_until *until, hipStream_t s,
-                         const irs_beam_link *link) {
+                         const irs_beam_link *link, const irs_beam_rule *rule) {
     if (W < 1 || W > BEAM_MAXW) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "beam width %d outside [1, %d]", W, BEAM_MAXW);
     const int waves = W < 4 ? 4 : (W > 16 ? 16 : W);
     constexpr int S4 = IRS_WIN_SLOTS_SHORT, S16 = IRS_WIN_SLOTS_LONG;
+    if (link && rule) { // the ruled forms: the link and the rule as the trailing arguments
+        using LK = irs_beam_link;
+        using RU = irs_beam_rule;
+        const auto kern = irs_window_slots(ctx) == S4
+                              ? (cand.ex.on ? (until ? k_beam_step<true, true, S4, LK, RU> : k_beam_step<false, true, S4, LK, RU>)
+                                            : (until ? k_beam_step<true, false, S4, LK, RU> : k_beam_step<false, false, S4, LK, RU>))
+                              : (cand.ex.on ? (until ? k_beam_step<true, true, S16, LK, RU> : k_beam_step<false, true, S16, LK, RU>)
+                                            : (until ? k_beam_step<true, false, S16, LK, RU> : k_beam_step<false, false, S16, LK, RU>));
+        hipLaunchKernelGGL(kern, dim3(B), dim3(64 * waves), 0, s, in, out, cand, W, ctx->dims.max_len, step, step_ptr, P, status,
+                           until ? *until : irs_beam_until{}, *link, *rule);
+        IRS_CHECK_HIP(ctx, hipGetLastError());
+        return IRS_OK;
+    }
     if (link) { // the linked forms: the same choice of UNTIL / EXCL / SLOTS, the link as the trailing argument
         using LK = irs_beam_link;
         const auto kern = irs_window_slots(ctx) == S4

@@ -702,6 +702,47 @@ class Engine:
         self._call_sync(self.lib.irs_beam_trace_carry, _ptr(link), _ptr(link_val), _ptr(mx), _ptr(sm), _ptr(ts), _ptr(rank), B, W, step,
                    _ptr(lp_item), _ptr(lp_target), _ptr(rank_target), ld, _ptr(row_map))
 
+    # ------------------------------------------------------------------ beam rule (irs_set_beam_rule)
+    def set_beam_rule(self, rank_max: Optional[int] = None, lp_min: Optional[float] = None, target_weight: float = 0.0):
+        """irs_set_beam_rule (opt-in, off by default): until cleared (None, None, 0) the two beam loops, which then need a bound
+        beam trace (trace=True), offer the target alone to a beam whose target stands at rank <= rank_max among what its window
+        leaves, or at log-probability >= lp_min (IRS_ROW_OFFERED in the user's status word), and order the candidates of a step
+        by score + target_weight * lp_target(parent); the returned scores stay acceptance sums.  Every other search entry point
+        refuses while a rule is set."""
+        self._check(self.lib.irs_set_beam_rule(self.h, 0 if rank_max is None else int(rank_max),
+                                               float("nan") if lp_min is None else float(lp_min), float(target_weight)))
+
+    def beam_step_ruled(self, state_in, val, ids0, lse, step: int, state_out, status, mx, sm, ts, rank, *, done=None,
+                        stop_rule: int = _lib.IRS_BEAM_STOP_BEST, rank_max: Optional[int] = None, lp_min: Optional[float] = None,
+                        target_weight: float = 0.0):
+        """irs_beam_step_ruled: beam_step_linked under a rule given as arguments; (mx, sm, ts, rank) are score_target_trace's
+        results on the step's B * W INPUT rows.  Returns (link, link_val) as beam_step_linked does.  A synchronous call."""
+        kinds = (torch.int64, torch.int32, torch.float64, torch.float32, torch.int32)
+        if len(state_in) != len(state_out) or (len(state_in) == 5) != (done is not None) or len(state_in) not in (4, 5):
+            raise IrsError("beam_step_ruled: four-tensor states without done, or five-tensor states (fin last) with done")
+        s_in = [self._inplace(t, k, "beam_step_ruled: state_in") for t, k in zip(state_in, kinds)] + [None]
+        s_out = [self._inplace(t, k, "beam_step_ruled: state_out") for t, k in zip(state_out, kinds)] + [None]
+        if done is not None:
+            done = self._inplace(done, torch.int32, "beam_step_ruled: done")
+        status = self._inplace(status, torch.int32, "beam_step_ruled: status")
+        val, ids0 = self._dev(val, torch.float32), self._dev(ids0, torch.int64)
+        mx, sm, ts = (self._dev(t, torch.float32) for t in (mx, sm, ts))
+        rank = self._dev(rank, torch.int32)
+        B, W, _ = s_in[0].shape
+        if any(t.numel() != B * W for t in (mx, sm, ts, rank)):
+            raise IrsError("beam_step_ruled: the sweep's rows [B * W]")
+        lmax, lsum = lse if lse is not None else (None, None)
+        if lmax is not None:
+            lmax, lsum = self._dev(lmax, torch.float32), self._dev(lsum, torch.float32)
+        link = torch.empty((B, W), dtype=torch.int32, device=self.device)
+        link_val = torch.empty((B, W), dtype=torch.float32, device=self.device)
+        self._call_sync(self.lib.irs_beam_step_ruled, _ptr(s_in[0]), _ptr(s_in[1]), _ptr(s_in[2]), _ptr(s_in[3]), _ptr(s_in[4]),
+                        _ptr(val), _ptr(ids0), _ptr(lmax), _ptr(lsum), B, W, val.shape[1], step, s_in[3].shape[2], int(stop_rule),
+                        _ptr(s_out[0]), _ptr(s_out[1]), _ptr(s_out[2]), _ptr(s_out[3]), _ptr(s_out[4]), _ptr(done), _ptr(status),
+                        _ptr(link), _ptr(link_val), _ptr(mx), _ptr(sm), _ptr(ts), _ptr(rank), 0 if rank_max is None else int(rank_max),
+                        float("nan") if lp_min is None else float(lp_min), float(target_weight))
+        return link, link_val
+
     # ------------------------------------------------------------------ path replay (irs_replay_windows / irs_replay_paths)
     def replay_scratch_bytes(self, chunk: int) -> int:
         n = int(self.lib.irs_replay_scratch_bytes(self.h, chunk))
@@ -931,12 +972,12 @@ class Engine:
                         exact_candidates: bool = False, exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
                         guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
                         arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False,
-                        beam_trace: bool = False, offer: Optional[torch.Tensor] = None):
+                        beam_trace: bool = False, offer: Optional[torch.Tensor] = None, target_weight: float = 0.0):
         """While a search call runs with per-call keywords: what they ask for is bound before and unbound after.  Yields (the
         trace arrays (lp_item, lp_target, rank_target) or None, the lookahead record (items, lp) or None); beam_trace (the beam
         loops' trace=True) binds a beam trace for the call's width instead, whose [users, W, ld] arrays take the first place.
         offer (int64, 0-based ids, any order): an offer set is bound for the call (bind_offer_set), its scratch sized for the
-        call's rows.
+        call's rows.  In a beam call (beam >= 1) arrive_rank / arrive_lp / target_weight set the BEAM rule (set_beam_rule).
         users / ld: the call's users and path length; beam: its beam width, 0 for the greedy loops.  graph: the call replays
         a captured step -- the stream is drained once before the first unbind destroys it.
         Every bind and unbind drops ALL captured steps of the context, so with a keyword set use_graph saves nothing: the step
@@ -971,9 +1012,11 @@ class Engine:
 
         # (asked for, bind -> the tensors it holds for the call, unbind), in bind order: irs_bind_lookahead refuses behind a
         # bound guide ("one choice rule at a time"), and a caller who asks for both gets that message
+        arrive = arrive_rank is not None or arrive_lp is not None
         options = (
-            (arrive_rank is not None or arrive_lp is not None, lambda: self.set_arrival_rule(arrive_rank, arrive_lp) or (),
-             lambda: self.set_arrival_rule(None, None)),
+            (arrive and not beam, lambda: self.set_arrival_rule(arrive_rank, arrive_lp) or (), lambda: self.set_arrival_rule(None, None)),
+            (bool(beam) and (arrive or target_weight != 0), lambda: self.set_beam_rule(arrive_rank, arrive_lp, target_weight) or (),
+             lambda: self.set_beam_rule(None, None, 0.0)),
             (exact_candidates, survivors, lambda: self._check(self.lib.irs_bind_survivor_scratch(self.h, None, 0))),
             (exclude is not None or no_repeat, exclusions, self.unbind_exclusions),
             (guide is not None, lambda: self.bind_guide(guide, guide_k), self.unbind_guide),
@@ -1118,10 +1161,13 @@ class Engine:
     def beam_search(self, seqs: torch.Tensor, users: Optional[torch.Tensor], hep: torch.Tensor, max_path_len: int,
                     beam: int, k: int = 100, sweep: int = IRS_SWEEP_BF16, use_graph: bool = False,
                     want_windows: bool = False, exact_candidates: bool = False, exclude: Optional[torch.Tensor] = None,
-                    no_repeat: bool = False, trace: bool = False, offer: Optional[torch.Tensor] = None):
+                    no_repeat: bool = False, trace: bool = False, offer: Optional[torch.Tensor] = None,
+                    arrive_rank: Optional[int] = None, arrive_lp: Optional[float] = None, target_weight: float = 0.0):
         """(paths[B,W,P] f32, scores[B,W] f64, status[B] i32[, windows[B,W,L]]); beam 0 is the best.
         trace: a beam trace is bound for this call (irs_bind_beam_trace) and the return value grows a last member, (lp_item,
-        lp_target float32 [B, W, P], rank_target int32 [B, W, P]): the path trace's values along each output beam's ancestors."""
+        lp_target float32 [B, W, P], rank_target int32 [B, W, P]): the path trace's values along each output beam's ancestors.
+        arrive_rank / arrive_lp / target_weight: a beam rule is set for this call and cleared after it (set_beam_rule; needs
+        trace=True); this loop searches on behind an arrival."""
         seqs = self._dev(seqs, torch.int64)
         hep = self._dev(hep, torch.int32)
         if users is not None:
@@ -1132,7 +1178,8 @@ class Engine:
         status = torch.zeros(B, dtype=torch.int32, device=self.device)
         fin = torch.empty((B, beam, self.L), dtype=torch.int64, device=self.device) if want_windows else None
         with self._search_options(B, max_path_len, beam, graph=bool(use_graph), exact_candidates=exact_candidates, exclude=exclude,
-                                  no_repeat=no_repeat, beam_trace=trace, offer=offer) as recorded:
+                                  no_repeat=no_repeat, beam_trace=trace, offer=offer, arrive_rank=arrive_rank, arrive_lp=arrive_lp,
+                                  target_weight=target_weight) as recorded:
             self._call(self.lib.irs_beam_search, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
                                                  int(use_graph), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(status))
         out = (paths, scores, status, fin) if want_windows else (paths, scores, status)
@@ -1161,11 +1208,13 @@ class Engine:
                           scores: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
                           fin: Optional[torch.Tensor] = None, exact_candidates: bool = False,
                           exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
-                          offer: Optional[torch.Tensor] = None):
+                          offer: Optional[torch.Tensor] = None, arrive_rank: Optional[int] = None,
+                          arrive_lp: Optional[float] = None, target_weight: float = 0.0):
         """Beam search that ends a beam at its target (seqs[b, L - 1]) and retires finished users (irs_beam_search_until):
         (paths[B,W,P] f32, scores[B,W] f64, status[B] i32, fin[B,W] i32, steps_run, window_steps[, windows[B,W,L]]); beam 0 is
         the best.  One host read of 4 bytes per check.
-        trace: as in beam_search, the last member; a finished beam's columns are exactly zero behind its arrival."""
+        trace: as in beam_search, the last member; a finished beam's columns are exactly zero behind its arrival.
+        arrive_rank / arrive_lp / target_weight: as in beam_search; an offered beam is finished at its arrival."""
         seqs = self._dev(seqs, torch.int64)
         hep = self._dev(hep, torch.int32)
         if users is not None:
@@ -1190,7 +1239,8 @@ class Engine:
         win = torch.empty((B, beam, self.L), dtype=torch.int64, device=self.device) if want_windows else None
         stats = (ctypes.c_int64 * 2)(0, 0)
         with self._search_options(B, max_path_len, beam, exact_candidates=exact_candidates, exclude=exclude, no_repeat=no_repeat,
-                                  beam_trace=trace, offer=offer) as recorded:
+                                  beam_trace=trace, offer=offer, arrive_rank=arrive_rank, arrive_lp=arrive_lp,
+                                  target_weight=target_weight) as recorded:
             self._call(self.lib.irs_beam_search_until, _ptr(seqs), _ptr(users), _ptr(hep), B, beam, max_path_len, k, sweep,
                        int(stop_rule), int(check_every), _ptr(paths), _ptr(scores), _ptr(fin), _ptr(win), _ptr(status), stats)
         out = (paths, scores, status, fin, int(stats[0]), int(stats[1]))

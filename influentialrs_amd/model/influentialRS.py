@@ -191,8 +191,33 @@ class SearchOptions:
     lookahead: object = None
     lookahead_record: bool = False
     offer: object = dataclasses.field(default=None, kw_only=True)  # (keyword only: no positional constructor shifts)
+    beam_arrive_rank: object = dataclasses.field(default=None, kw_only=True)  # the beam rule (irs_set_beam_rule), likewise
+    beam_arrive_lp: object = dataclasses.field(default=None, kw_only=True)
+    beam_target_weight: float = dataclasses.field(default=0.0, kw_only=True)
     beam_trace: bool = False
     beam_pick: str = "score"
+
+
+def beam_rule_kwargs(opts: SearchOptions, beam_width: int, world: int) -> dict:
+    """The engine's beam-loop keywords for beam_arrive_rank / beam_arrive_lp / beam_target_weight ({} when none is given);
+    ValueError for a value out of range, for beam_width == 1 and for an item-sharded catalog.  That the rule needs
+    beam_trace=True is the library's own answer (IrsError, IRS_E_STATE)."""
+    rank, lp, lam = opts.beam_arrive_rank, opts.beam_arrive_lp, opts.beam_target_weight
+    if rank is None and lp is None and not lam:
+        return {}
+    if rank is not None and (isinstance(rank, bool) or int(rank) != rank or rank < 1):
+        raise ValueError(f"beam_arrive_rank={rank!r}: a rank of 1 or more (None: no rank clause)")
+    if lp is not None and not float(lp) <= 0:
+        raise ValueError(f"beam_arrive_lp={lp!r}: a log-probability, at most 0 (None: no probability clause)")
+    if not 0 <= float(lam) < float("inf"):
+        raise ValueError(f"beam_target_weight={lam!r}: finite and at least 0 (0: rank by acceptance alone)")
+    if beam_width == 1:
+        raise ValueError("beam_arrive_rank / beam_arrive_lp / beam_target_weight need beam_width > 1: use arrive_rank / arrive_lp "
+                         "for the greedy / sampled search")
+    if world != 1:
+        raise ValueError("the beam rule is not built for an item-sharded catalog: irs_set_beam_rule needs the whole catalog on "
+                         "one device")
+    return dict(arrive_rank=None if rank is None else int(rank), arrive_lp=None if lp is None else float(lp), target_weight=float(lam))
 
 
 def search_option_kwargs(opts: SearchOptions, beam_width: int, sample: bool, world: int) -> dict:
@@ -275,16 +300,19 @@ def search_option_kwargs(opts: SearchOptions, beam_width: int, sample: bool, wor
 def _takes_exact_candidates(fn):
     """Gives get_seq_in_batch its keywords exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None,
     guide_k=5, arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, beam_trace=False,
-    beam_pick="score" and offer=None.  They are taken here, keyword only,
+    beam_pick="score", offer=None, beam_arrive_rank=None, beam_arrive_lp=None and beam_target_weight=0.0.  They are taken here,
+    keyword only,
     so that the declared parameter list stays what it was (it ends with beam_stop): positional callers and code that reads the
     signature are not disturbed.  The search reads them from self._search_options, a SearchOptions, for the time of the call."""
     @functools.wraps(fn)
     def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None, guide_k=5,
              arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, beam_trace=False, beam_pick="score", offer=None,
-             **kw):
+             beam_arrive_rank=None, beam_arrive_lp=None, beam_target_weight=0.0, **kw):
         prev = self._search_options
         self._search_options = SearchOptions(bool(exact_candidates), exclude, bool(no_repeat), bool(trace), guide, int(guide_k),
-                                             arrive_rank, arrive_lp, lookahead, bool(lookahead_record), bool(beam_trace), beam_pick, offer=offer)
+                                             arrive_rank, arrive_lp, lookahead, bool(lookahead_record), bool(beam_trace), beam_pick, offer=offer,
+                                             beam_arrive_rank=beam_arrive_rank, beam_arrive_lp=beam_arrive_lp,
+                                             beam_target_weight=beam_target_weight)
         try:
             return fn(self, *args, **kw)
         finally:
@@ -354,6 +382,27 @@ def beam_trace_summary(lp_item, lp_target, rank_target, paths, scores, targets):
                 a[b, j, n_steps[b, j]:] = 0
     return dict(lp_item=lp_item, lp_target=lp_target, rank_target=rank_target, paths=np.array(paths), scores=np.array(scores),
                 n_steps=n_steps)
+
+
+def beam_rule_summary(trace, targets, rank_max=None, lp_min=None):
+    """What a beam rule adds to last_beam_trace, from the recorded arrays alone (trace: beam_trace_summary's dict): arrival_step
+    int64 [B, W], the step at which a live beam's path holds the user's target (-1: never), and offered bool [B, W]: at that
+    step a clause of the rule holds on (rank_target, lp_target) -- rank_target != 0 and (rank_target <= rank_max, or lp_target >=
+    lp_min as float32; a NaN never holds) -- which is exactly when the rule offered the target there."""
+    paths, n_steps = trace["paths"], trace["n_steps"]
+    B, W, _ = paths.shape
+    tg = np.asarray(targets).reshape(B, 1)
+    rows, cols = np.arange(B)[:, None], np.arange(W)[None, :]
+    last = np.maximum(n_steps - 1, 0)
+    arrived = (n_steps > 0) & (paths[rows, cols, last] == tg)
+    rk, lp = trace["rank_target"][rows, cols, last], trace["lp_target"][rows, cols, last]
+    holds = np.zeros((B, W), dtype=bool)
+    if rank_max is not None and int(rank_max) >= 1:
+        holds |= rk <= int(rank_max)
+    if lp_min is not None and np.float32(lp_min) <= 0:
+        with np.errstate(invalid="ignore"):
+            holds |= lp >= np.float32(lp_min)
+    return dict(arrival_step=np.where(arrived, last, -1).astype(np.int64), offered=arrived & (rk != 0) & holds)
 
 
 def pick_beam(paths, scores, lp_target, n_steps, targets, how="score"):
@@ -630,13 +679,14 @@ class IRSNN(nn.Module):
         return path_trace_summary(*out, items, targets, n_live=n_live)
 
     def _beam_paths(self, seqs, users, max_path_len, gap_len, beam_width, beam_stop=None, exact_candidates=False, excl=None,
-                    beam_trace=False):
+                    beam_trace=False, rule=None):
         """Best-beam paths [B, P] + status via the build-defined beam search (no reference
         counterpart; beam_width == 1 equals the greedy search).  All beams and their
         cumulative log-probabilities are kept in self.last_beams = (paths[B,W,P], scores[B,W]).
         beam_stop "best" / "all": irs_beam_search_until -- a beam ends at its target, finished users are retired;
         self.last_beam_stop = dict(finished [B,W], steps, window_steps).
-        beam_trace (one device): the search also returns the three [B, W, P] arrays of irs_bind_beam_trace, the last value."""
+        beam_trace (one device): the search also returns the three [B, W, P] arrays of irs_bind_beam_trace, the last value.
+        rule (one device): beam_rule_kwargs' keywords, the beam rule of this call (irs_set_beam_rule)."""
         B, L = seqs.shape
         dev = seqs.device
         hip = self.net._hip
@@ -647,12 +697,14 @@ class IRSNN(nn.Module):
             eng = hip.get(B * W, B * W)
             paths, scores, status, fin, steps, window_steps, *traced = eng.beam_search_until(
                 seqs.contiguous(), users, hep, max_path_len, W, k=100, sweep=hip.sweep, stop_rule=_BEAM_STOP_RULES[beam_stop],
-                check_every=BEAM_STOP_CHECK_EVERY, exact_candidates=exact_candidates, trace=beam_trace, **(excl or {}))
+                check_every=BEAM_STOP_CHECK_EVERY, exact_candidates=exact_candidates, trace=beam_trace, **(excl or {}),
+                **(rule or {}))
             self.last_beam_stop = dict(finished=fin.detach().cpu().numpy(), steps=steps, window_steps=window_steps)
         elif hip.world == 1:
             eng = hip.get(B * W, B * W)
             paths, scores, status, *traced = eng.beam_search(seqs.contiguous(), users, hep, max_path_len, W, k=100, sweep=hip.sweep,
-                                                             exact_candidates=exact_candidates, trace=beam_trace, **(excl or {}))
+                                                             exact_candidates=exact_candidates, trace=beam_trace, **(excl or {}),
+                                                             **(rule or {}))
         else:  # item-sharded: the whole loop runs below the C ABI (irs_beam_search_sharded: row all-gather, packed top-100
             # all-to-all, log-sum-exp all-reduce per step, one stream-ordered sequence; captured into a hipGraph over RCCL)
             eng = hip.get(B * W, B * W * hip.world)
@@ -717,6 +769,14 @@ class IRSNN(nn.Module):
         arrival; paths, scores; n_steps [B, W]; picked [B]).  beam_pick="target" (needs beam_trace=True) returns, per user,
         the beam pick_beam names instead of beam 0: the live beam that reaches the target first, else the one that ends with the
         target most probable.  The returned tuple keeps its shape.
+        beam_arrive_rank=None, beam_arrive_lp=None, beam_target_weight=0.0 (extension, keyword only, taken the same way; beam_width
+        > 1 on one device with beam_trace=True, off by default): the beam rule (irs_set_beam_rule), with or without beam_stop.  A
+        beam whose target stands at rank <= beam_arrive_rank among what its window leaves, or at log-probability >=
+        beam_arrive_lp, is offered the target itself (with beam_stop it ends there); the candidates of a step are ordered by
+        acceptance score + beam_target_weight * lp_target of their parent, while the returned scores stay acceptance sums (with
+        a weight they need not be descending).  Without beam_trace=True the library refuses (IrsError).  self.last_beam_trace
+        gains arrival_step int64 [B, W] (-1: the beam never holds the target) and offered bool [B, W], both computed from the
+        recorded arrays (beam_rule_summary).
         offer=None (extension, keyword only, taken the same way; one device, off by default): the offer set (irs_bind_offer_set).
         offer: 1-based item ids, a tensor, an array or a list, shared by all users; every step of every search form then offers
         items of the set only -- the persuasion path is made of items that may be shown.  A target outside the set is never
@@ -725,6 +785,7 @@ class IRSNN(nn.Module):
         the window can hide the best 100 of a small set."""
         opts = self._search_options
         greedy_kw = search_option_kwargs(opts, beam_width, sample, self.net._hip.world)
+        rule = beam_rule_kwargs(opts, beam_width, self.net._hip.world)
         exact_candidates, exclude, no_repeat = opts.exact_candidates, opts.exclude, opts.no_repeat
         trace, lookahead = greedy_kw["trace"], greedy_kw.get("lookahead")
         if stop_at_target and beam_width > 1:
@@ -753,7 +814,7 @@ class IRSNN(nn.Module):
         n_eng = B * (lookahead or 1)  # (the children of a lookahead step are decoded and scored in one call each)
         if beam_width > 1:
             all_paths, status, beam_traced = self._beam_paths(work, users, max_path_len, gap_len, beam_width, beam_stop, exact_candidates,
-                                                              {**excl, **off}, opts.beam_trace)
+                                                              {**excl, **off}, opts.beam_trace, rule)
             paths_t = all_paths[:, 0].contiguous()
             if opts.beam_trace:  # (what beam_pick="target" names is decided on the host, from the trace as the caller will see it)
                 allp, alls = self.last_beams
@@ -762,6 +823,9 @@ class IRSNN(nn.Module):
                 bt = self.last_beam_trace
                 pick = pick_beam(allp, alls, bt["lp_target"], bt["n_steps"], targets.detach().cpu().numpy(), opts.beam_pick)
                 self.last_beam_trace["picked"] = pick
+                if rule:
+                    self.last_beam_trace.update(beam_rule_summary(bt, targets.detach().cpu().numpy(), rule["arrive_rank"],
+                                                                  rule["arrive_lp"]))
                 paths_t = all_paths[torch.arange(B, device=dev), torch.from_numpy(pick).to(dev)].contiguous()
         elif stop_at_target:
             if hip.world != 1:
