@@ -712,7 +712,8 @@ int irs_recommend(irs_ctx *ctx, const float *dev_xrows, const int64_t *dev_seq, 
  *   rank_target[b][i]  = 1 + #{ j : j+1 is not a non-pad entry of w, and (e_j, j) ranks before (e_{t-1}, t-1) } in the library's
  *                        total order: score descending, id ascending, -0 folded onto +0.  Duplicates in the window count once; the
  *                        target in its own window still has a rank.  A bound exclusion list and no_repeat do NOT enter the rank:
- *                        it is the rank among what the window leaves, whatever else the step may drop.
+ *                        it is the rank among what the window leaves, whatever else the step may drop (the rank among what
+ *                        they leave as well is rank_adm: "admissible rank" below).
  *   lp_item[b][i]      = e_{c-1} - lse for the item c the step chose; 0 where it chose nothing (IRS_ROW_NO_CANDIDATE).
  *   t == 0 (or t outside the catalog): lp_target = 0 and rank_target = 0.
  * The values are formed as (double)e - ((double)max + log((double)sumexp)) from the float32 pair (max, sumexp = sum exp(e_j -
@@ -989,8 +990,9 @@ int irs_lookahead_choose(irs_ctx *ctx, const int64_t *dev_seq, int32_t M, int32_
  * guided -- then chooses the target, its only survivor; the trace record finds the target in entry 0, so at a fired step lp_item
  * equals lp_target bit for bit; irs_generate_paths_until sees the target chosen and retires the user; irs_generate_paths
  * searches on behind the arrival, as the reference does.
- * The rank is the trace's.  A rank among what a bound exclusion list and no_repeat ALSO leave is out of scope here: it needs a
- * second count in the sweep and is the next lever.
+ * The rank is the trace's unless the rule was set with irs_set_arrival_rule_ex(..., IRS_RANK_ADMISSIBLE): see "admissible rank"
+ * below for the rank among what a bound exclusion list, no_repeat and an offer set ALSO leave.  That rank carried through beam
+ * state is out of scope here: the beam trace and the beam rule keep the window's.
  * irs_arrival_offer is the kernel alone, on the outputs of irs_score_target_trace:
  *  dev_seq int64 [M, L], dev_hep int32 [M]; dev_max / dev_sumexp / dev_target_score float [M], dev_rank int32 [M] in
  *  dev_fin int32 [M] (may be NULL): rows with fin != 0 are skipped
@@ -1010,6 +1012,59 @@ int irs_arrival_offer(irs_ctx *ctx, const int64_t *dev_seq, const int32_t *dev_h
                       const float *dev_sumexp, const float *dev_target_score, const int32_t *dev_rank, const int32_t *dev_fin,
                       float *dev_val, int64_t *dev_ids0, int32_t k, int32_t rank_max, float lp_min, const float *dev_paths,
                       int32_t path_ld, int32_t step, const int32_t *dev_row_map, int32_t *dev_status, void *stream);
+
+/* ---- admissible rank: the target's rank among what the user could be OFFERED (opt-in; rank_target counts every excluded item
+ *      that outscores the target, so it is not the position a slate of irs_recommend or a step of the search would give it) ----
+ * Row b at step i, measured BEFORE the step chooses, with the path trace's scores e_j and total order (score descending, id
+ * ascending, -0 folded onto +0):
+ *   H(b,i) = the items the step's own admissibility test hides: the non-pad entries of the window seq[b][0 .. hep]; the bound
+ *            exclusion list of the row's user; under no_repeat the non-zero path entries [0, i).
+ *   U      = the valid (sanitised) ids of a bound offer set, or the whole catalog when none is bound.
+ *   rank_adm[b][i] = 1 + #{ j in U \ H, j != t-1 : (e_j, j) ranks before (e_{t-1}, t-1) }.
+ * The rank is defined whether or not the target itself is in H or outside U: it is where the target WOULD stand; the arrival rule
+ * keeps its own admissibility test.  t == 0 or t outside the catalog: 0.  An item counts once however often it occurs in the list
+ * (duplicates are legal there), the window, the path, or across the three.  With nothing but a trace bound, rank_adm equals
+ * rank_target in every cell.  rank_adm <= rank_target without an offer set.  Where the target is admissible and rank_adm <= n, its
+ * 0-based position in irs_recommend's slate of n on the same row and bindings is rank_adm - 1.
+ * One kernel behind the trace sweep corrects the sweep's count exactly: the distinct union of H is gathered per row, each member is
+ * scored with the exact chain (irs_score_gather's bits) and compared with the target; with an offer set the count over U comes
+ * from the set's score pass (same bits).  Integer sums only: two identical calls give identical bits.  (A set with holes is not a
+ * valid set: an id then counts as often as the sanitised array holds it, which is what the set's ranking emits.)
+ * irs_score_target_rank_admissible is irs_score_target_trace's launches and then that kernel.  It takes no stream, like
+ * irs_recommend and irs_score_topk_offer, whose score pass it runs in the bound offer set's scratch: the work is enqueued on the
+ * null stream and the call returns without waiting (the ordering rules are those stated under irs_score_topk_offer):
+ *  dev_xrows / dev_seq / dev_hep / M, dev_trace_scratch / trace_bytes, dev_max / dev_sumexp / dev_target_score / dev_rank: as in
+ *            irs_score_target_trace, with the same results
+ *  dev_paths float [M, path_ld] (may be NULL), step: the non-zero entries [0, step) of row r's path enter H, whether or not
+ *            no_repeat is bound; step in [0, min(path_ld, 64)]
+ *  dev_scratch: caller-owned, >= irs_admissible_scratch_bytes(M) bytes (one int32 per row, rounded up to 256), 16-byte aligned
+ *  dev_rank_adm int32 [M] out
+ *  It reads the bound exclusion LIST (row r is bound user r, as in irs_recommend; a binding of no_repeat alone holds no list)
+ *  and a bound offer set, whose scratch must hold M rows (the set's score pass runs for them).  It is no search: no search
+ *  option refuses it, and it drops no captured step.  Null pointers, M outside [1, max_rows], a scratch too small or misaligned,
+ *  a bad step, more rows than the bound list's users or the set's pass -> IRS_E_INVALID; world != 1 -> IRS_E_UNSUPPORTED; then
+ *  weights / workspace -> IRS_E_STATE; all before any launch.
+ * irs_bind_trace_admissible adds a fourth array to a BOUND path trace: dev_rank_adm int32 [users, ld] with the trace's users and
+ * ld (else IRS_E_INVALID; no trace bound -> IRS_E_STATE), and a caller-owned scratch >= irs_admissible_scratch_bytes(users) that
+ * must stay valid until the unbind.  A NULL array unbinds; unbinding or rebinding the path trace drops this binding as well.
+ * Binding and unbinding drop the captured steps.  While bound, irs_generate_paths and irs_generate_paths_until run the kernel
+ * behind the trace sweep of every step and write the value at the caller's row and the step's column in exactly the cells where
+ * rank_target is written (every column; up to and including the arrival step, zero behind it, in the until loop).  Sampling,
+ * guide, lookahead, exact candidates, exclusions, no_repeat, an offer set and long windows compose: the kernel reads the step's
+ * own exclusion arguments.
+ * irs_set_arrival_rule_ex is irs_set_arrival_rule with the rank the rank clause reads: IRS_RANK_WINDOW (irs_set_arrival_rule's)
+ * or IRS_RANK_ADMISSIBLE, under which rk above is the row's rank_adm of this step; any other kind -> IRS_E_INVALID.  A loop
+ * entered with an IRS_RANK_ADMISSIBLE rule and no admissible binding returns IRS_E_STATE with a message, before any launch.
+ * With rank_max = 1 the rule then fires exactly where the target is the best admissible item: the greedy step's own choice. */
+#define IRS_RANK_WINDOW 0
+#define IRS_RANK_ADMISSIBLE 1
+size_t irs_admissible_scratch_bytes(const irs_ctx *ctx, int32_t rows); /* 0 for invalid arguments */
+int irs_score_target_rank_admissible(irs_ctx *ctx, const float *dev_xrows, const int64_t *dev_seq, const int32_t *dev_hep, int32_t M,
+                                     const float *dev_paths, int32_t path_ld, int32_t step, void *dev_trace_scratch,
+                                     size_t trace_bytes, void *dev_scratch, size_t bytes, float *dev_max, float *dev_sumexp,
+                                     float *dev_target_score, int32_t *dev_rank, int32_t *dev_rank_adm);
+int irs_bind_trace_admissible(irs_ctx *ctx, int32_t *dev_rank_adm, int32_t users, int32_t ld, void *dev_scratch, size_t bytes);
+int irs_set_arrival_rule_ex(irs_ctx *ctx, int32_t rank_max, float lp_min, int32_t rank_kind);
 
 /* ---- beam rule: an arrival rule and a target-aware ranking on beam trace state (opt-in, off by default; BUILD-DEFINED like the
  *      beam search itself.  Without it a beam search ranks by acceptance alone -- the cumulative log-probability of the offered

@@ -25,6 +25,7 @@ IRS_REPLAY_SLOT, IRS_REPLAY_FULL = 0, 1  # irs_replay_windows / irs_replay_paths
 IRS_MAX_GUIDE_KC, IRS_MAX_GUIDE_BITS, IRS_MAX_GUIDE_FLOATS = 32, 1024, 512
 IRS_MAX_LOOKAHEAD_KC = 32  # irs_bind_lookahead
 IRS_BEAM_LINK_DEAD, IRS_BEAM_LINK_COPY = -1, 256  # irs_beam_step_linked's link word: dead / parent p / IRS_BEAM_LINK_COPY | p
+IRS_RANK_WINDOW, IRS_RANK_ADMISSIBLE = 0, 1  # irs_set_arrival_rule_ex: the rank the rank clause reads
 IRS_MAX_RECOMMEND = 128  # irs_recommend / irs_recommend_take: items of a slate
 IRS_MAX_PATH = 64  # path length of the beam searches, and the ld of a bound beam trace
 # irs_decoder_route_last (include/irs_hip.h): its field order and the names of the enum-valued fields, in the order of
@@ -141,6 +142,11 @@ SIGNATURES = {
     "irs_arrival_offer": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                     c_void_p]),
+    "irs_admissible_scratch_bytes": (c_size_t, [c_void_p, c_int32]),
+    "irs_score_target_rank_admissible": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p,
+                                                   c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "irs_bind_trace_admissible": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t]),
+    "irs_set_arrival_rule_ex": (c_int32, [c_void_p, c_int32, c_float, c_int32]),
     "irs_set_beam_rule": (c_int32, [c_void_p, c_int32, c_float, c_float]),
     "irs_beam_step_ruled": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,

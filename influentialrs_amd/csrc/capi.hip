@@ -714,11 +714,19 @@ static int args_look(irs_ctx *ctx, const char *fn, const search_call &c) {
                  (long long)c.B * l.kc, ctx->max_seqs, ctx->max_rows);
     return IRS_OK;
 }
-// an arrival rule reads what the trace sweep leaves in the bound scratch
+// an arrival rule reads what the trace sweep leaves in the bound scratch; one on the admissible rank what k_trace_rank_adm leaves
 static int args_arrive(irs_ctx *ctx, const char *fn, const search_call &) {
     if (!ctx->opt.trace.on)
         IRS_FAIL(ctx, IRS_E_STATE, "%s: an arrival rule is set (irs_set_arrival_rule) and no path trace is bound (irs_bind_path_trace): "
                                    "the rule reads what the trace records", fn);
+    if (ctx->opt.arrive.kind == IRS_RANK_ADMISSIBLE && !ctx->opt.adm.on)
+        IRS_FAIL(ctx, IRS_E_STATE, "%s: an arrival rule on the admissible rank is set (irs_set_arrival_rule_ex, IRS_RANK_ADMISSIBLE) and no "
+                                   "admissible rank is bound (irs_bind_trace_admissible): the rule reads what that binding records", fn);
+    return IRS_OK;
+}
+// an admissible rank shares the bound trace's users and ld (irs_bind_trace_admissible), which args_trace has checked
+static int args_adm(irs_ctx *ctx, const char *fn, const search_call &) {
+    if (!ctx->opt.trace.on) IRS_FAIL(ctx, IRS_E_STATE, "%s: an admissible rank is bound (irs_bind_trace_admissible) without a path trace", fn);
     return IRS_OK;
 }
 // a beam trace: the call's users, width and path length fit the bound arrays, whose row stride holds the bound W
@@ -752,11 +760,14 @@ static int args_offer(irs_ctx *ctx, const char *fn, const search_call &c) {
 // binding cannot exist there, and must not be ignored if it does).  loops_only: why every entry point but the two beam LOOPS
 // refuses it (the same message form); null for the options the greedy side admits
 enum { OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_BTRACE, OPT_OFFER, OPT_BRULE, OPT_N };
+// behind the options that stand alone: an option bound ON TOP of another one, which exists only while that one does.  OPT_ADM
+// (irs_bind_trace_admissible) lives and dies with OPT_TRACE, so a row of PLAN that refuses the trace never gets to it
+enum { OPT_ADM = OPT_N, OPT_ALL };
 static const struct {
     bool (*on)(const irs_search_opts &);
     int (*args)(irs_ctx *, const char *, const search_call &);
     const char *what, *beam, *sharded, *loops_only;
-} OPTS[OPT_N] = {
+} OPTS[OPT_ALL] = {
     {[](const irs_search_opts &o) { return o.surv.scratch != nullptr; }, args_surv, nullptr, nullptr,
      "%s: exact candidates (irs_bind_survivor_scratch) need the whole catalog on one device"},
     {[](const irs_search_opts &o) { return o.excl.on != 0; }, args_excl, nullptr, nullptr,
@@ -776,6 +787,8 @@ static const struct {
      "%s: a bound offer set (irs_bind_offer_set) needs the whole catalog on one device"},
     {[](const irs_search_opts &o) { return o.brule.on != 0; }, args_brule, "a beam rule is set (irs_set_beam_rule)", nullptr,
      "%s: a beam rule (irs_set_beam_rule) needs the whole catalog on one device", "irs_beam_search and irs_beam_search_until only"},
+    {[](const irs_search_opts &o) { return o.adm.on != 0; }, args_adm, "an admissible rank is bound (irs_bind_trace_admissible)",
+     "greedy and sampled loops only", "%s: a bound admissible rank (irs_bind_trace_admissible) needs the whole catalog on one device"},
 };
 
 // ---- the entry points, one row each: what it checks, in its order -- the first failing check decides the code and the message.
@@ -792,10 +805,12 @@ static const struct {
 // the beam loops look at it (is a beam trace bound?) behind the arrival rule and before readiness, so that a rule without a trace
 // is answered before anything else of the call.  AT_BEAM_STEP_RULED, the rule's own step (irs_beam_step_ruled), takes the rule as
 // arguments and looks at neither.
+// A bound admissible rank (irs_bind_trace_admissible) exists only while a path trace is bound, so every row that refuses the
+// trace has refused it already; the greedy loops look at it right behind the trace.  irs_path_step looks at neither.
 enum { AT_GREEDY_LOOP, AT_PATH_STEP, AT_BEAM_STEP, AT_BEAM_LOOP, AT_SHARDED_LOOP, AT_BEAM_STEP_LINKED, AT_RECOMMEND, AT_BEAM_STEP_RULED };
-enum { DO_READY = OPT_N, DO_WORLD, DO_SHAPE, DO_K, DO_END };
+enum { DO_READY = OPT_ALL, DO_WORLD, DO_SHAPE, DO_K, DO_END };
 static const int PLAN[][16] = {
-    /* AT_GREEDY_LOOP  */ {OPT_BTRACE, OPT_BRULE, OPT_ARRIVE, OPT_GUIDE, OPT_LOOK, DO_READY, DO_WORLD, DO_SHAPE, OPT_TRACE, DO_K, OPT_EXCL, OPT_SURV, OPT_OFFER, DO_END},
+    /* AT_GREEDY_LOOP  */ {OPT_BTRACE, OPT_BRULE, OPT_ARRIVE, OPT_GUIDE, OPT_LOOK, DO_READY, DO_WORLD, DO_SHAPE, OPT_TRACE, OPT_ADM, DO_K, OPT_EXCL, OPT_SURV, OPT_OFFER, DO_END},
     /* AT_PATH_STEP    */ {OPT_BTRACE, OPT_BRULE, OPT_EXCL, OPT_GUIDE, DO_END},
     /* AT_BEAM_STEP    */ {OPT_BTRACE, OPT_BRULE, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
     /* AT_BEAM_LOOP    */ {OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_BRULE, DO_READY, DO_WORLD, OPT_TRACE, DO_SHAPE, OPT_BTRACE, DO_K, OPT_EXCL, OPT_SURV, OPT_OFFER, DO_END},
@@ -1090,8 +1105,25 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
         irs_trace_layout(o.trace.scratch, o.trace.users, &tr);
         if ((rc = irs_launch_target_trace(ctx, ctx->xrows, pa.seq, pa.hep, B, tr, tr.mx, tr.sm, tr.ts, tr.rank, s))) return rc;
     }
+    // admissible rank: the trace's rank among what the step may offer -- behind the sweep, before anything rewrites the lists; the
+    // value goes to the scratch by launch row and to the caller's cell of this step, where the record kernel writes rank_target.
+    // A bound offer set's scores are those of this step's ranking: launch_lists wrote them for these B rows (one pass: args_offer),
+    // and neither the survivor pass (its own scratch) nor the trace sweep (the trace scratch, ctx->lse_part) writes them
+    const int32_t *arrive_rank = tr.rank;
+    if (o.adm.on) {
+        irs_adm_args aa = {ctx->xrows, pa.seq, pa.hep, B, tr.ts, tr.refid, tr.count, pa.ex};
+        if (o.offer.on) {
+            irs_offer_rows of;
+            irs_offer_layout(o.offer.scratch, o.offer.n, o.offer.rows, &of);
+            aa.oids = of.ids, aa.on = o.offer.n, aa.oc_pad = of.c_pad, aa.osc = of.sc, aa.oholes = of.holes;
+        }
+        aa.out = (int32_t *)o.adm.scratch;
+        aa.rec = o.adm.rank, aa.rec_ld = o.trace.ld, aa.rec_map = row_map, aa.rec_fin = surv_fin, aa.rec_step = ctx->step_ctr;
+        if ((rc = irs_launch_trace_rank_adm(ctx, aa, s))) return rc;
+        if (o.arrive.kind == IRS_RANK_ADMISSIBLE) arrive_rank = aa.out;
+    }
     // arrival rule: a row whose target stands well enough is offered the target alone (the entry points have seen to the trace)
-    if (o.arrive.on && (rc = irs_launch_arrival_offer(ctx, pa.seq, pa.hep, B, tr.mx, tr.sm, tr.ts, tr.rank, surv_fin, ctx->top_val,
+    if (o.arrive.on && (rc = irs_launch_arrival_offer(ctx, pa.seq, pa.hep, B, tr.mx, tr.sm, tr.ts, arrive_rank, surv_fin, ctx->top_val,
                                                       ctx->top_ids, k, o.arrive.rank, o.arrive.lp, pa.status, pa.ex, s)))
         return rc;
     if (o.look.on) {
@@ -1279,6 +1311,7 @@ extern "C" int irs_bind_path_trace(irs_ctx *ctx, float *lp_item, float *lp_targe
     if (!lp_item && !lp_target && !rank_target) { // unbind
         if (ctx->opt.trace.on) opts_changed(ctx);
         ctx->opt.trace = {};
+        ctx->opt.adm = {}; // (an admissible rank is bound to this trace: irs_bind_trace_admissible)
         return IRS_OK;
     }
     if (!lp_item || !lp_target || !rank_target) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_path_trace: the three arrays go together");
@@ -1287,8 +1320,72 @@ extern "C" int irs_bind_path_trace(irs_ctx *ctx, float *lp_item, float *lp_targe
     const int rc = check_scratch(ctx, "irs_bind_path_trace", scratch, bytes, irs_trace_layout(nullptr, users, nullptr));
     if (rc) return rc;
     ctx->opt.trace = {1, lp_item, lp_target, rank_target, users, ld, scratch};
+    ctx->opt.adm = {}; // (a new trace: the admissible rank of the previous one is dropped with it)
     opts_changed(ctx);
     return IRS_OK;
+}
+
+// ------------------------------------------------------------------ admissible rank (admissible.hip)
+extern "C" size_t irs_admissible_scratch_bytes(const irs_ctx *ctx, int32_t rows) {
+    if (!ctx || rows < 1 || rows > ctx->max_rows) return 0;
+    return irs_adm_layout(rows);
+}
+
+extern "C" int irs_bind_trace_admissible(irs_ctx *ctx, int32_t *rank_adm, int32_t users, int32_t ld, void *scratch, size_t bytes) {
+    if (!ctx) return IRS_E_INVALID;
+    if (!rank_adm) { // unbind
+        if (ctx->opt.adm.on) opts_changed(ctx);
+        ctx->opt.adm = {};
+        return IRS_OK;
+    }
+    const auto &t = ctx->opt.trace;
+    if (!t.on) IRS_FAIL(ctx, IRS_E_STATE, "irs_bind_trace_admissible: no path trace is bound (irs_bind_path_trace)");
+    if (users != t.users || ld != t.ld)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_trace_admissible: [%d, %d], the path trace is bound for [%d, %d]", users, ld, t.users, t.ld);
+    const int rc = check_scratch(ctx, "irs_bind_trace_admissible", scratch, bytes, irs_adm_layout(users));
+    if (rc) return rc;
+    ctx->opt.adm = {1, rank_adm, scratch};
+    opts_changed(ctx);
+    return IRS_OK;
+}
+
+extern "C" int irs_score_target_rank_admissible(irs_ctx *ctx, const float *xrows, const int64_t *seq, const int32_t *hep, int32_t M,
+                                                const float *paths, int32_t path_ld, int32_t step, void *trace_scratch,
+                                                size_t trace_bytes, void *scratch, size_t bytes, float *omax, float *osum, float *tscore,
+                                                int32_t *rank, int32_t *rank_adm) {
+    if (!ctx) return IRS_E_INVALID;
+    const char *fn = "irs_score_target_rank_admissible";
+    int rc = check_rows(ctx, fn, xrows, M);
+    if (rc) return rc;
+    if (!seq || !hep || !omax || !osum || !tscore || !rank || !rank_adm) IRS_FAIL(ctx, IRS_E_INVALID, "%s: null pointer", fn);
+    if ((rc = check_scratch(ctx, fn, trace_scratch, trace_bytes, irs_trace_layout(nullptr, M, nullptr)))) return rc;
+    if ((rc = check_scratch(ctx, fn, scratch, bytes, irs_adm_layout(M)))) return rc;
+    if (step < 0 || (paths && (path_ld < 1 || step > path_ld))) IRS_FAIL(ctx, IRS_E_INVALID, "%s: step must be in [0, path_ld], path_ld >= 1", fn);
+    if (paths && step > IRS_MAX_PATH) IRS_FAIL(ctx, IRS_E_INVALID, "%s: step %d > %d path entries", fn, step, IRS_MAX_PATH);
+    const auto &o = ctx->opt;
+    if (o.excl.on && o.excl.rows && M > o.excl.users) IRS_FAIL(ctx, IRS_E_INVALID, "%s: %d rows, exclusions are bound for %d users", fn, M, o.excl.users);
+    if (o.offer.on && M > o.offer.rows)
+        IRS_FAIL(ctx, IRS_E_INVALID, "%s: %d rows, the offer set's scratch (irs_bind_offer_set) is sized for %d", fn, M, o.offer.rows);
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s needs the whole catalog on one device", fn);
+    if ((rc = ready(ctx))) return rc;
+    hipStream_t s = nullptr; // (the null stream, as irs_recommend and irs_score_topk_offer: irs_hip.h)
+    irs_trace_rows tr;
+    irs_trace_layout(trace_scratch, M, &tr);
+    if ((rc = irs_launch_target_trace(ctx, xrows, seq, hep, M, tr, omax, osum, tscore, rank, s))) return rc;
+    // H: the bound list of user r for row r (a binding of no_repeat alone holds no list), and the caller's path rows whether or
+    // not no_repeat is bound -- the call states what the step at `step` would hide
+    irs_adm_args a = {xrows, seq, hep, M, tscore, tr.refid, tr.count};
+    if (o.excl.on && o.excl.rows) a.ex.rows = o.excl.rows, a.ex.cnt = o.excl.cnt, a.ex.stride = o.excl.stride;
+    if (paths && step > 0) a.ex.paths = paths, a.ex.path_ld = path_ld, a.ex.step_arg = step;
+    a.ex.div = 1, a.ex.on = (a.ex.rows || a.ex.paths) ? 1 : 0;
+    if (o.offer.on) { // the set's scores of these rows: the score pass of irs_score_topk_offer
+        irs_offer_rows of;
+        irs_offer_layout(o.offer.scratch, o.offer.n, o.offer.rows, &of);
+        if ((rc = irs_launch_offer_scores(ctx, xrows, M, of, s))) return rc;
+        a.oids = of.ids, a.on = o.offer.n, a.oc_pad = of.c_pad, a.osc = of.sc, a.oholes = of.holes;
+    }
+    a.out = rank_adm;
+    return irs_launch_trace_rank_adm(ctx, a, s);
 }
 
 // ------------------------------------------------------------------ beam trace (irs_bind_beam_trace; beam_trace.hip)
@@ -1338,17 +1435,28 @@ extern "C" int irs_beam_trace_carry(irs_ctx *ctx, const int32_t *link, const flo
 }
 
 // ------------------------------------------------------------------ arrival rule (irs_set_arrival_rule; path.hip: k_arrival_offer)
-extern "C" int irs_set_arrival_rule(irs_ctx *ctx, int32_t rank_max, float lp_min) {
+static int set_arrival_rule(irs_ctx *ctx, const char *fn, int rank_max, float lp_min, int kind) {
     if (!ctx) return IRS_E_INVALID;
-    if (rank_max < 0) IRS_FAIL(ctx, IRS_E_INVALID, "irs_set_arrival_rule: rank_max must be >= 0 (0: the rank clause is off)");
+    if (rank_max < 0) IRS_FAIL(ctx, IRS_E_INVALID, "%s: rank_max must be >= 0 (0: the rank clause is off)", fn);
+    if (kind != IRS_RANK_WINDOW && kind != IRS_RANK_ADMISSIBLE)
+        IRS_FAIL(ctx, IRS_E_INVALID, "%s: rank_kind %d (IRS_RANK_WINDOW or IRS_RANK_ADMISSIBLE)", fn, kind);
     const int lp_on = irs_arrival_lp_on(lp_min) ? 1 : 0;
     const int on = (rank_max >= 1 || lp_on) ? 1 : 0;
-    if (on && ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_set_arrival_rule needs the whole catalog on one device");
+    if (on && ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s needs the whole catalog on one device", fn);
     const float lp = lp_on ? lp_min : (on ? __builtin_nanf("") : 0.f); // (what the kernel takes: NaN is "clause off")
+    if (!on) kind = IRS_RANK_WINDOW;
     auto &a = ctx->opt.arrive;
-    if (on != a.on || rank_max != a.rank || lp_on != a.lp_on || memcmp(&lp, &a.lp, sizeof(lp))) opts_changed(ctx);
-    a = {on, on ? rank_max : 0, lp_on, lp};
+    if (on != a.on || rank_max != a.rank || lp_on != a.lp_on || memcmp(&lp, &a.lp, sizeof(lp)) || kind != a.kind) opts_changed(ctx);
+    a = {on, on ? rank_max : 0, lp_on, lp, kind};
     return IRS_OK;
+}
+
+extern "C" int irs_set_arrival_rule(irs_ctx *ctx, int32_t rank_max, float lp_min) {
+    return set_arrival_rule(ctx, "irs_set_arrival_rule", rank_max, lp_min, IRS_RANK_WINDOW);
+}
+
+extern "C" int irs_set_arrival_rule_ex(irs_ctx *ctx, int32_t rank_max, float lp_min, int32_t rank_kind) {
+    return set_arrival_rule(ctx, "irs_set_arrival_rule_ex", rank_max, lp_min, rank_kind);
 }
 
 extern "C" int irs_arrival_offer(irs_ctx *ctx, const int64_t *seq, const int32_t *hep, int32_t M, const float *mx, const float *sm,

@@ -152,6 +152,29 @@ struct irs_trace_rec { // what the record kernel takes: a step's rows (the scrat
     int32_t *rank_target;
     int ld;
 };
+// ---- admissible rank (irs_bind_trace_admissible, irs_score_target_rank_admissible; admissible.hip).  What k_trace_rank_adm takes
+// behind the trace sweep: the sweep's rows, the step's bound exclusions (list, map, path, step index), a bound offer set with the
+// scores of the row pass, and where the value goes -- out[row] by launch row, and (rec != null) the caller's [users][ld] cell of
+// the step, exactly where k_trace_record writes rank_target: row rec_map[row] (null: row), column rec_step[0], unless rec_fin[row].
+struct irs_adm_args {
+    const float *xrows;  // [M][d]
+    const int64_t *seq;  // [M][L]
+    const int32_t *hep;  // [M]
+    int M;
+    const float *ts;                 // [M] the target's score
+    const int64_t *refid;            // [M] its local 0-based id, -1: no target
+    const unsigned long long *count; // [M] items of the whole catalog ranked before it
+    irs_excl ex;                     // zero: neither a list nor a path
+    const int64_t *oids;             // a bound offer set's sanitised ids [on] (null: none)
+    int64_t on, oc_pad;
+    const float *osc;                // [M][oc_pad] the set's scores of these rows
+    const int32_t *oholes;           // [1] holes of the set: != 0 and the ids need not ascend
+    int32_t *out;                    // [M]
+    int32_t *rec;                    // [users][rec_ld] or null
+    int rec_ld;
+    const int32_t *rec_map, *rec_fin, *rec_step;
+};
+static inline size_t irs_adm_layout(int rows) { return ((size_t)rows * 4 + 255) / 256 * 256; } // the step's values by launch row
 // ---- beam trace (irs_bind_beam_trace; beam_trace.hip).  A linked beam step says, per output beam row, where it came from (the
 // link word of irs_hip.h: IRS_BEAM_LINK_DEAD, parent p, or IRS_BEAM_LINK_COPY | p) and the list value of the candidate it chose
 // (0 where it chose none); the carry kernel moves the recorded columns along.  Both null: the step as it was.
@@ -322,6 +345,14 @@ struct irs_search_opts {
         void *scratch;
     } trace;
 
+    // admissible rank (irs_bind_trace_admissible): the caller's fourth [users][ld] array of the bound path trace (its users and ld)
+    // and scratch while bound; the greedy loops then run k_trace_rank_adm behind the target sweep.  Only ever on while trace.on
+    struct {
+        int on;
+        int32_t *rank;
+        void *scratch;
+    } adm;
+
     // bound guide (irs_bind_guide): the Rec2Inf choice rule of the greedy path step -- among the first k_c admissible candidates,
     // the one nearest to the target in the bound feature table; the beam and the sharded entry points then refuse
     struct {
@@ -339,10 +370,12 @@ struct irs_search_opts {
     } look;
 
     // arrival rule (irs_set_arrival_rule): between the trace sweep and the path step, a live row whose target stands at rank
-    // <= rank (0: clause off) or at log-probability >= lp (lp_on) is offered the target alone; needs a bound trace
+    // <= rank (0: clause off) or at log-probability >= lp (lp_on) is offered the target alone; needs a bound trace.  kind: which
+    // rank the clause reads -- IRS_RANK_WINDOW the trace's, IRS_RANK_ADMISSIBLE the admissible one (needs adm.on)
     struct {
         int on, rank, lp_on;
         float lp;
+        int kind;
     } arrive;
 
     // beam trace (irs_bind_beam_trace): the caller's three [users][W][ld] arrays and scratch while bound; the two beam loops then
@@ -527,6 +560,7 @@ static inline int irs_opt_zero_records(irs_ctx *ctx, int B, hipStream_t s) {
         IRS_CHECK_HIP(ctx, hipMemsetAsync(o.trace.item, 0, n, s));
         IRS_CHECK_HIP(ctx, hipMemsetAsync(o.trace.target, 0, n, s));
         IRS_CHECK_HIP(ctx, hipMemsetAsync(o.trace.rank, 0, n, s));
+        if (o.adm.on) IRS_CHECK_HIP(ctx, hipMemsetAsync(o.adm.rank, 0, n, s));
     }
     if (o.look.on && o.look.rec_item) {
         const size_t n = (size_t)B * o.look.ld * o.look.kc * 4;
@@ -640,6 +674,11 @@ int irs_launch_survivors(irs_ctx *ctx, const irs_surv_args &a, void *scratch, hi
 // ---- offer_set.hip ---- (arguments already validated; irs_launch_offer_topk reads ctx->opt.offer)
 int irs_launch_offer_prepare(irs_ctx *ctx, const int64_t *ids0, int64_t n_ids, const irs_offer_rows &o, hipStream_t s);
 int irs_launch_offer_topk(irs_ctx *ctx, const float *xrows, int M, int k, float *val, int64_t *ids0, int32_t *status, hipStream_t s);
+// the score pass alone: o.sc[r][*] for `rows` rows (at most what the scratch holds) of x; irs_launch_offer_topk's first launch
+int irs_launch_offer_scores(irs_ctx *ctx, const float *x, int rows, const irs_offer_rows &o, hipStream_t s);
+
+// ---- admissible.hip ---- (arguments already validated)
+int irs_launch_trace_rank_adm(irs_ctx *ctx, const irs_adm_args &a, hipStream_t s);
 
 // ---- recommend.hip ---- (the first n admissible entries of every row's list; arguments already validated.  seq null: no window;
 // out_lp null: mx / sm are not read; ex: the bound exclusion lists, never a path)

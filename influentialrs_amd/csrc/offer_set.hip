@@ -227,6 +227,14 @@ static int offer_scores(irs_ctx *ctx, const float *x, int rows, const irs_offer_
     return IRS_OK;
 }
 
+int irs_launch_offer_scores(irs_ctx *ctx, const float *x, int rows, const irs_offer_rows &o, hipStream_t s) {
+    const int d = ctx->dims.d;
+    if (d <= 32) return offer_scores<8, 4>(ctx, x, rows, o, s);
+    if (d <= 64) return offer_scores<16, 4>(ctx, x, rows, o, s);
+    if (d <= 128) return offer_scores<32, 4>(ctx, x, rows, o, s);
+    return offer_scores<64, 2>(ctx, x, rows, o, s);
+}
+
 int irs_launch_offer_topk(irs_ctx *ctx, const float *xrows, int M, int k, float *val, int64_t *ids0, int32_t *status, hipStream_t s) {
     const auto &b = ctx->opt.offer;
     irs_offer_rows o;
@@ -234,12 +242,7 @@ int irs_launch_offer_topk(irs_ctx *ctx, const float *xrows, int M, int k, float 
     const int d = ctx->dims.d;
     for (int m0 = 0; m0 < M; m0 += b.rows) {
         const int rows = M - m0 < b.rows ? M - m0 : b.rows;
-        const float *x = xrows + (size_t)m0 * d;
-        int rc;
-        if (d <= 32) rc = offer_scores<8, 4>(ctx, x, rows, o, s);
-        else if (d <= 64) rc = offer_scores<16, 4>(ctx, x, rows, o, s);
-        else if (d <= 128) rc = offer_scores<32, 4>(ctx, x, rows, o, s);
-        else rc = offer_scores<64, 2>(ctx, x, rows, o, s);
+        const int rc = irs_launch_offer_scores(ctx, xrows + (size_t)m0 * d, rows, o, s);
         if (rc) return rc;
         hipLaunchKernelGGL(k_offer_select, dim3(rows), dim3(256), 0, s, o.sc, o.ids, b.n, o.c_pad, o.holes, k, val + (size_t)m0 * k,
                            ids0 + (size_t)m0 * k, status + m0);

@@ -33,6 +33,24 @@ def shard_bounds(n_item: int, world: int, rank: int) -> Tuple[int, int]:
     return min(lo_t * 32, n_item), min(hi_t * 32, n_item)
 
 
+def arrive_among_kind(among: str) -> int:
+    """arrive_among="window" | "admissible" as irs_set_arrival_rule_ex's rank_kind; ValueError for anything else."""
+    kinds = {"window": _lib.IRS_RANK_WINDOW, "admissible": _lib.IRS_RANK_ADMISSIBLE}
+    if among not in kinds:
+        raise ValueError(f"arrive_among={among!r}: use \"window\" (rank_target) or \"admissible\" (rank_adm)")
+    return kinds[among]
+
+
+def check_rank_options(trace: bool, rank_admissible: bool, arrive_among: str):
+    """The per-call keywords of the greedy loops: rank_admissible adds a column to the path trace, and an arrival rule among the
+    admissible reads that column.  ValueError otherwise."""
+    arrive_among_kind(arrive_among)
+    if rank_admissible and not trace:
+        raise ValueError("rank_admissible=True adds a column to the path trace: use trace=True")
+    if arrive_among == "admissible" and not rank_admissible:
+        raise ValueError("arrive_among=\"admissible\" reads the admissible rank: use rank_admissible=True")
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -628,6 +646,51 @@ class Engine:
     def unbind_path_trace(self):
         self._check(self.lib.irs_bind_path_trace(self.h, None, None, None, 0, 0, None, 0))
 
+    # ------------------------------------------------------------------ admissible rank (irs_bind_trace_admissible)
+    def admissible_scratch_bytes(self, rows: int) -> int:
+        n = int(self.lib.irs_admissible_scratch_bytes(self.h, rows))
+        if n == 0:
+            raise IrsError(f"admissible_scratch_bytes: rows={rows} (need 1 <= rows <= max_rows={self.max_rows})")
+        return n
+
+    def score_target_rank_admissible(self, xrows: torch.Tensor, seqs: torch.Tensor, hep: torch.Tensor,
+                                     paths: Optional[torch.Tensor] = None, step: int = 0):
+        """irs_score_target_rank_admissible: score_target_trace's four results and rank_adm int32 [M], the target's rank among
+        what the window, the bound exclusion list of user m (bind_exclusions), the non-zero entries paths[m, :step] (float32
+        [M, path_ld], optional) and a bound offer set (bind_offer_set) leave: (max, sumexp, target_score, rank, rank_adm).  Where
+        the target is admissible its 0-based position in recommend()'s slate on the same rows and bindings is rank_adm - 1.
+        The work goes on the null stream, ordered against torch's current stream by events (_call_null)."""
+        xrows = self._dev(xrows, torch.float32)
+        seqs, hep = self._dev(seqs, torch.int64), self._dev(hep, torch.int32)
+        M = xrows.shape[0]
+        if xrows.dim() != 2 or xrows.shape[1] != self.d or tuple(seqs.shape) != (M, self.L) or hep.numel() != M:
+            raise IrsError("score_target_rank_admissible: xrows [M, d], seqs [M, max_len], hep [M]")
+        if paths is not None:
+            paths = self._dev(paths, torch.float32)
+            if paths.dim() != 2 or paths.shape[0] != M:
+                raise IrsError("score_target_rank_admissible: paths [M, path_ld]")
+        t_scratch = torch.empty(self.path_trace_scratch_bytes(M), dtype=torch.uint8, device=self.device)
+        scratch = torch.empty(self.admissible_scratch_bytes(M), dtype=torch.uint8, device=self.device)
+        mx, sm, ts = (torch.empty(M, dtype=torch.float32, device=self.device) for _ in range(3))
+        rank, rank_adm = (torch.empty(M, dtype=torch.int32, device=self.device) for _ in range(2))
+        self._call_null(self.lib.irs_score_target_rank_admissible, _ptr(xrows), _ptr(seqs), _ptr(hep), M, _ptr(paths),
+                        paths.shape[1] if paths is not None else 0, int(step), _ptr(t_scratch), t_scratch.numel(), _ptr(scratch),
+                        scratch.numel(), _ptr(mx), _ptr(sm), _ptr(ts), _ptr(rank), _ptr(rank_adm),
+                        tensors=(xrows, seqs, hep, paths, t_scratch, scratch, mx, sm, ts, rank, rank_adm,
+                                 getattr(self, "_offer_scratch", None)))
+        return mx, sm, ts, rank, rank_adm
+
+    def bind_trace_admissible(self, users: int, ld: int):
+        """irs_bind_trace_admissible: adds rank_adm int32 [users, ld] to the BOUND path trace (the same users and ld) until
+        unbind_trace_admissible or the trace's own unbind / rebind.  Returns (rank_adm, scratch): the caller keeps both alive."""
+        rank_adm = torch.zeros((users, ld), dtype=torch.int32, device=self.device)
+        scratch = torch.empty(self.admissible_scratch_bytes(users), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.irs_bind_trace_admissible(self.h, _ptr(rank_adm), users, ld, _ptr(scratch), scratch.numel()))
+        return rank_adm, scratch
+
+    def unbind_trace_admissible(self):
+        self._check(self.lib.irs_bind_trace_admissible(self.h, None, 0, 0, None, 0))
+
     # ------------------------------------------------------------------ beam trace (irs_bind_beam_trace)
     def beam_trace_scratch_bytes(self, users: int, W: int) -> int:
         n = int(self.lib.irs_beam_trace_scratch_bytes(self.h, users, W))
@@ -935,12 +998,17 @@ class Engine:
         return lp, choice
 
     # ------------------------------------------------------------------ arrival rule (irs_set_arrival_rule)
-    def set_arrival_rule(self, rank_max: Optional[int] = None, lp_min: Optional[float] = None):
-        """irs_set_arrival_rule: until cleared (both None) a live row of the greedy / sampled loops whose target stands at rank
+    def set_arrival_rule(self, rank_max: Optional[int] = None, lp_min: Optional[float] = None, among: str = "window"):
+        """irs_set_arrival_rule[_ex]: until cleared (both None) a live row of the greedy / sampled loops whose target stands at rank
         <= rank_max among what the window leaves, or at log-probability >= lp_min, is offered the target alone
-        (IRS_ROW_OFFERED).  The loops then need a bound path trace (trace=True)."""
-        self._check(self.lib.irs_set_arrival_rule(self.h, 0 if rank_max is None else int(rank_max),
-                                                  float("nan") if lp_min is None else float(lp_min)))
+        (IRS_ROW_OFFERED).  The loops then need a bound path trace (trace=True).  among="admissible": the rank clause reads the
+        admissible rank (IRS_RANK_ADMISSIBLE), and the loops need bind_trace_admissible as well (rank_admissible=True)."""
+        kind = arrive_among_kind(among)
+        rank_max, lp_min = 0 if rank_max is None else int(rank_max), float("nan") if lp_min is None else float(lp_min)
+        if kind == _lib.IRS_RANK_WINDOW:
+            self._check(self.lib.irs_set_arrival_rule(self.h, rank_max, lp_min))
+        else:
+            self._check(self.lib.irs_set_arrival_rule_ex(self.h, rank_max, lp_min, kind))
 
     def arrival_offer(self, seqs, hep, mx, sm, ts, rank, val, ids0, status, *, rank_max: Optional[int] = None,
                       lp_min: Optional[float] = None, fin=None, paths=None, step: int = 0, row_map=None):
@@ -972,18 +1040,22 @@ class Engine:
                         exact_candidates: bool = False, exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
                         guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
                         arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False,
-                        beam_trace: bool = False, offer: Optional[torch.Tensor] = None, target_weight: float = 0.0):
+                        beam_trace: bool = False, offer: Optional[torch.Tensor] = None, target_weight: float = 0.0,
+                        rank_admissible: bool = False, arrive_among: str = "window"):
         """While a search call runs with per-call keywords: what they ask for is bound before and unbound after.  Yields (the
         trace arrays (lp_item, lp_target, rank_target) or None, the lookahead record (items, lp) or None); beam_trace (the beam
         loops' trace=True) binds a beam trace for the call's width instead, whose [users, W, ld] arrays take the first place.
         offer (int64, 0-based ids, any order): an offer set is bound for the call (bind_offer_set), its scratch sized for the
         call's rows.  In a beam call (beam >= 1) arrive_rank / arrive_lp / target_weight set the BEAM rule (set_beam_rule).
+        rank_admissible (with trace): an admissible rank is bound behind the trace (bind_trace_admissible) and the trace arrays
+        grow a fourth, rank_adm; arrive_among="admissible" makes the arrival rule read it (ValueError without rank_admissible).
         users / ld: the call's users and path length; beam: its beam width, 0 for the greedy loops.  graph: the call replays
         a captured step -- the stream is drained once before the first unbind destroys it.
         Every bind and unbind drops ALL captured steps of the context, so with a keyword set use_graph saves nothing: the step
         is captured again on every call, and steps captured by earlier calls are lost.  A caller that wants a captured step
         with an option inside binds it once itself (bind_* / set_arrival_rule) and calls without the keyword."""
         out = {}
+        check_rank_options(trace, rank_admissible, arrive_among)
 
         def survivors():  # (for the call's rows and the candidates a step chooses among: csrc/irs_internal.h, irs_opt_choices)
             want = beam or (guide_k if guide is not None else (lookahead if lookahead is not None else (sample_k if sample else 1)))
@@ -1005,6 +1077,11 @@ class Engine:
             out["traced"] = (lp_item, lp_target, rank)
             return (scratch,)
 
+        def admissible():  # (behind the trace it belongs to; the trace's unbind, which runs later, would drop it as well)
+            rank_adm, scratch = self.bind_trace_admissible(users, ld)
+            out["traced"] = out["traced"] + (rank_adm,)
+            return (scratch,)
+
         def beam_traced():
             lp_item, lp_target, rank, scratch = self.bind_beam_trace(users, beam, ld)
             out["traced"] = (lp_item, lp_target, rank)
@@ -1014,7 +1091,8 @@ class Engine:
         # bound guide ("one choice rule at a time"), and a caller who asks for both gets that message
         arrive = arrive_rank is not None or arrive_lp is not None
         options = (
-            (arrive and not beam, lambda: self.set_arrival_rule(arrive_rank, arrive_lp) or (), lambda: self.set_arrival_rule(None, None)),
+            (arrive and not beam, lambda: self.set_arrival_rule(arrive_rank, arrive_lp, arrive_among) or (),
+             lambda: self.set_arrival_rule(None, None)),
             (bool(beam) and (arrive or target_weight != 0), lambda: self.set_beam_rule(arrive_rank, arrive_lp, target_weight) or (),
              lambda: self.set_beam_rule(None, None, 0.0)),
             (exact_candidates, survivors, lambda: self._check(self.lib.irs_bind_survivor_scratch(self.h, None, 0))),
@@ -1022,6 +1100,7 @@ class Engine:
             (guide is not None, lambda: self.bind_guide(guide, guide_k), self.unbind_guide),
             (lookahead is not None, look, self.unbind_lookahead),
             (trace, traced, self.unbind_path_trace),
+            (trace and rank_admissible, admissible, self.unbind_trace_admissible),
             (beam_trace, beam_traced, self.unbind_beam_trace),
             (offer is not None, lambda: (self.bind_offer_set(offer, users * max(beam, 1)),), self.unbind_offer_set),
         )
@@ -1086,7 +1165,7 @@ class Engine:
                        exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
                        guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
                        arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False,
-                       offer: Optional[torch.Tensor] = None):
+                       offer: Optional[torch.Tensor] = None, rank_admissible: bool = False, arrive_among: str = "window"):
         """Runs the whole search loop on the device.  `seqs` and `hep` are the
         working window state and are modified in place.  exact_candidates: a row whose k candidates are hidden by its window
         chooses among the exact best admissible items of the catalog instead (IRS_ROW_RESCUED; the result of k = n_item).
@@ -1107,11 +1186,16 @@ class Engine:
         max_path_len, k_c]): every step's candidates (1-based, 0 = none) and the values compared.
         offer (int64, 0-based ids): an offer set is bound for this call (irs_bind_offer_set): every step offers items of the set
         only; log-probabilities and target ranks stay statements about the whole catalog.  The same holds in the three other
-        loops."""
+        loops.
+        rank_admissible (needs trace=True): the trace member grows a fourth array, rank_adm int32 [B, max_path_len]: the target's
+        rank among what the window, exclude, no_repeat and offer leave (irs_bind_trace_admissible).  arrive_among="admissible"
+        (needs rank_admissible=True): arrive_rank reads rank_adm instead of rank_target.  The same holds in
+        generate_paths_until."""
         seqs, users, hep, B, paths, status = self._greedy_call("generate_paths", seqs, users, hep, max_path_len, paths, status)
         with self._search_options(B, max_path_len, 0, sample, sample_k, bool(use_graph), exact_candidates=exact_candidates, exclude=exclude,
                                   no_repeat=no_repeat, trace=trace, guide=guide, guide_k=guide_k, arrive_rank=arrive_rank,
-                                  arrive_lp=arrive_lp, lookahead=lookahead, lookahead_record=lookahead_record, offer=offer) as recorded:
+                                  arrive_lp=arrive_lp, lookahead=lookahead, lookahead_record=lookahead_record, offer=offer,
+                                  rank_admissible=rank_admissible, arrive_among=arrive_among) as recorded:
             self._call(self.lib.irs_generate_paths, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                     int(sample), sample_k, seed, int(use_graph), _ptr(paths), _ptr(status))
         return (paths, status) + self._recorded(recorded, trace, lookahead is not None and lookahead_record)
@@ -1123,7 +1207,7 @@ class Engine:
                              exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
                              guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
                              arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False,
-                             offer: Optional[torch.Tensor] = None):
+                             offer: Optional[torch.Tensor] = None, rank_admissible: bool = False, arrive_among: str = "window"):
         """generate_paths that stops a user at its target (seqs[b, L - 1]) and the call when nobody is left
         (irs_generate_paths_until): returns (paths, status, steps_run, row_steps).  Paths are zero behind the target.
         `seqs` and `hep` are working state: modified, and unspecified afterwards.  One host read of 4 bytes per check.
@@ -1136,7 +1220,8 @@ class Engine:
         stats = (ctypes.c_int64 * 2)(0, 0)
         with self._search_options(B, max_path_len, 0, sample, sample_k, exact_candidates=exact_candidates, exclude=exclude,
                                   no_repeat=no_repeat, trace=trace, guide=guide, guide_k=guide_k, arrive_rank=arrive_rank,
-                                  arrive_lp=arrive_lp, lookahead=lookahead, lookahead_record=lookahead_record, offer=offer) as recorded:
+                                  arrive_lp=arrive_lp, lookahead=lookahead, lookahead_record=lookahead_record, offer=offer,
+                                  rank_admissible=rank_admissible, arrive_among=arrive_among) as recorded:
             self._call(self.lib.irs_generate_paths_until, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                           int(sample), sample_k, seed, check_every, _ptr(paths), _ptr(status), stats)
         return (paths, status, int(stats[0]), int(stats[1])) + self._recorded(recorded, trace, lookahead is not None and lookahead_record)

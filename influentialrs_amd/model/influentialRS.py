@@ -194,6 +194,8 @@ class SearchOptions:
     beam_arrive_rank: object = dataclasses.field(default=None, kw_only=True)  # the beam rule (irs_set_beam_rule), likewise
     beam_arrive_lp: object = dataclasses.field(default=None, kw_only=True)
     beam_target_weight: float = dataclasses.field(default=0.0, kw_only=True)
+    rank_admissible: bool = dataclasses.field(default=False, kw_only=True)  # irs_bind_trace_admissible: last_trace["rank_adm"]
+    arrive_among: str = dataclasses.field(default="window", kw_only=True)  # the rank arrive_rank reads (irs_set_arrival_rule_ex)
     beam_trace: bool = False
     beam_pick: str = "score"
 
@@ -241,6 +243,16 @@ def search_option_kwargs(opts: SearchOptions, beam_width: int, sample: bool, wor
                              "the whole catalog on one device")
         kw.update(arrive_rank=None if rank is None else int(rank), arrive_lp=None if lp is None else float(lp))
         trace = True
+    if opts.arrive_among not in ("window", "admissible"):
+        raise ValueError(f"arrive_among={opts.arrive_among!r}: use \"window\" (rank_target) or \"admissible\" (rank_adm)")
+    if opts.arrive_among == "admissible":
+        if not opts.rank_admissible:
+            raise ValueError("arrive_among=\"admissible\" reads the admissible rank: use rank_admissible=True")
+        kw.update(arrive_among="admissible")
+    if opts.rank_admissible:
+        if not trace:
+            raise ValueError("rank_admissible=True adds a column to the path trace: use trace=True")
+        kw.update(rank_admissible=True)
     if opts.lookahead is not None:
         k_c = opts.lookahead
         if isinstance(k_c, bool) or not isinstance(k_c, (int, np.integer)) or not 1 <= k_c <= 32:
@@ -300,19 +312,21 @@ def search_option_kwargs(opts: SearchOptions, beam_width: int, sample: bool, wor
 def _takes_exact_candidates(fn):
     """Gives get_seq_in_batch its keywords exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None,
     guide_k=5, arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, beam_trace=False,
-    beam_pick="score", offer=None, beam_arrive_rank=None, beam_arrive_lp=None and beam_target_weight=0.0.  They are taken here,
+    beam_pick="score", offer=None, beam_arrive_rank=None, beam_arrive_lp=None, beam_target_weight=0.0, rank_admissible=False and
+    arrive_among="window".  They are taken here,
     keyword only,
     so that the declared parameter list stays what it was (it ends with beam_stop): positional callers and code that reads the
     signature are not disturbed.  The search reads them from self._search_options, a SearchOptions, for the time of the call."""
     @functools.wraps(fn)
     def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None, guide_k=5,
              arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, beam_trace=False, beam_pick="score", offer=None,
-             beam_arrive_rank=None, beam_arrive_lp=None, beam_target_weight=0.0, **kw):
+             beam_arrive_rank=None, beam_arrive_lp=None, beam_target_weight=0.0, rank_admissible=False, arrive_among="window", **kw):
         prev = self._search_options
         self._search_options = SearchOptions(bool(exact_candidates), exclude, bool(no_repeat), bool(trace), guide, int(guide_k),
                                              arrive_rank, arrive_lp, lookahead, bool(lookahead_record), bool(beam_trace), beam_pick, offer=offer,
                                              beam_arrive_rank=beam_arrive_rank, beam_arrive_lp=beam_arrive_lp,
-                                             beam_target_weight=beam_target_weight)
+                                             beam_target_weight=beam_target_weight, rank_admissible=bool(rank_admissible),
+                                             arrive_among=arrive_among)
         try:
             return fn(self, *args, **kw)
         finally:
@@ -335,12 +349,37 @@ def _takes_offer(fn):
     return call
 
 
-def path_trace_summary(lp_item, lp_target, rank_target, paths, targets, n_live=None):
+def _takes_rank_admissible(fn):
+    """Gives a front-end method its keywords rank_admissible=False and arrive_among="window", keyword only, the way _takes_offer
+    gives it offer: the declared parameter list stays what it was.  The method reads them from self._call_rank, a pair."""
+    @functools.wraps(fn)
+    def call(self, *args, rank_admissible=False, arrive_among="window", **kw):
+        prev = getattr(self, "_call_rank", (False, "window"))
+        self._call_rank = (bool(rank_admissible), arrive_among)
+        try:
+            return fn(self, *args, **kw)
+        finally:
+            self._call_rank = prev
+    return call
+
+
+def slate_steps(rank_adm, n_steps, r):
+    """The first live step of every user at which the target stands among the first r admissible items (0 < rank_adm <= r), -1
+    where it never does: int64 [B]."""
+    rank_adm = np.asarray(rank_adm)
+    B, P = rank_adm.shape
+    hit = (rank_adm > 0) & (rank_adm <= int(r)) & (np.arange(P)[None, :] < np.asarray(n_steps)[:, None])
+    return np.where(hit.any(axis=1), hit.argmax(axis=1), -1).astype(np.int64)
+
+
+def path_trace_summary(lp_item, lp_target, rank_target, paths, targets, n_live=None, rank_adm=None):
     """get_seq_in_batch's last_trace from the search's arrays ([B, P] each; `paths` before the host cut or after it, `targets`
     [B]).  A user's live steps end with its arrival (the first path entry equal to its target) or run to P (n_live[b] where
     given: a replayed path that ends early); behind them the three arrays are cut to 0 like the path.  Over the live steps, as
     Evaluator.get_grad_in_batch forms iois and avg_ps:
-    ioi = last lp_target - first, ior = first rank_target - last (positive: the target moved up), avg_lp_item = mean lp_item."""
+    ioi = last lp_target - first, ior = first rank_target - last (positive: the target moved up), avg_lp_item = mean lp_item.
+    rank_adm (irs_bind_trace_admissible's array, where given) is cut the same way and comes with slate_step, a function of r:
+    slate_steps(rank_adm, n_steps, r)."""
     lp_item = np.array(lp_item, dtype=np.float32)
     lp_target = np.array(lp_target, dtype=np.float32)
     rank_target = np.array(rank_target, dtype=np.int32)
@@ -354,10 +393,16 @@ def path_trace_summary(lp_item, lp_target, rank_target, paths, targets, n_live=N
             a[i, n_steps[i]:] = 0
     last = n_steps - 1
     rows = np.arange(B)
-    return dict(lp_item=lp_item, lp_target=lp_target, rank_target=rank_target, n_steps=n_steps,
-                ioi=lp_target[rows, last].astype(np.float64) - lp_target[:, 0].astype(np.float64),
-                ior=rank_target[:, 0].astype(np.int64) - rank_target[rows, last].astype(np.int64),
-                avg_lp_item=np.array([lp_item[i, :n_steps[i]].astype(np.float64).mean() for i in range(B)]))
+    out = dict(lp_item=lp_item, lp_target=lp_target, rank_target=rank_target, n_steps=n_steps,
+               ioi=lp_target[rows, last].astype(np.float64) - lp_target[:, 0].astype(np.float64),
+               ior=rank_target[:, 0].astype(np.int64) - rank_target[rows, last].astype(np.int64),
+               avg_lp_item=np.array([lp_item[i, :n_steps[i]].astype(np.float64).mean() for i in range(B)]))
+    if rank_adm is not None:
+        rank_adm = np.array(rank_adm, dtype=np.int32)
+        for i in range(B):
+            rank_adm[i, n_steps[i]:] = 0
+        out.update(rank_adm=rank_adm, slate_step=lambda r: slate_steps(rank_adm, n_steps, r))
+    return out
 
 
 def beam_trace_summary(lp_item, lp_target, rank_target, paths, scores, targets):
@@ -753,7 +798,12 @@ class IRSNN(nn.Module):
         off by default): the arrival rule (irs_set_arrival_rule).  A recommender shows a slate, so a user counts as arrived at
         the first step where the target stands at rank <= arrive_rank (>= 1) among what its window leaves, or where the model
         gives it a log-probability >= arrive_lp (<= 0): the step then offers the target itself.  With stop_at_target=True the
-        user is retired there.  The keywords imply trace=True: self.last_trace is filled, and its `offered` (bool [B]) says for
+        user is retired there.  rank_admissible=True (needs trace=True or an arrival keyword) records the ADMISSIBLE rank as well
+        (irs_bind_trace_admissible): self.last_trace["rank_adm"] [B, max_path_len], the target's rank among what exclude,
+        no_repeat, the window and offer leave -- its position in the slate the user would be shown -- and
+        self.last_trace["slate_step"](r), the first step of every user with rank_adm <= r (-1: none); arrive_among="admissible"
+        (needs rank_admissible=True, else ValueError) makes arrive_rank read that rank instead of the window's.
+        The keywords imply trace=True: self.last_trace is filled, and its `offered` (bool [B]) says for
         whom the rule fired.  A target that the window, the exclusion list or (no_repeat) the path hides is never offered.
         lookahead=None, lookahead_record=False (extension, keyword only, taken the same way; greedy search on one device, off by
         default): the one-step lookahead choice (irs_bind_lookahead).  lookahead=k_c in [1, 32]: every step decodes, for each
@@ -859,7 +909,8 @@ class IRSNN(nn.Module):
         paths = paths_t.detach().cpu().numpy()
         targets = targets.detach().cpu().numpy()
         if trace:
-            self.last_trace = path_trace_summary(*(a.detach().cpu().numpy() for a in traced[0]), paths, targets)
+            tr = [a.detach().cpu().numpy() for a in traced[0]]  # (a fourth array: rank_adm, under rank_admissible=True)
+            self.last_trace = path_trace_summary(*tr[:3], paths, targets, rank_adm=tr[3] if len(tr) > 3 else None)
             self.last_trace["offered"] = (status & IRS_ROW_OFFERED).ne(0).detach().cpu().numpy()
         if lookahead is not None and opts.lookahead_record:
             items, lp = (a.detach().cpu().numpy().copy() for a in traced[-1])

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from .._lib import IRS_ROW_NO_CANDIDATE
-from .influentialRS import STOP_CHECK_EVERY, SearchOptions, exclusion_ids0, _takes_offer, offer_ids0, path_trace_summary, search_option_kwargs
+from .influentialRS import STOP_CHECK_EVERY, SearchOptions, exclusion_ids0, _takes_offer, _takes_rank_admissible, offer_ids0, path_trace_summary, search_option_kwargs
 from .layers import get_item_index
 
 
@@ -54,6 +54,7 @@ class Rec2Inf(nn.Module):
         self.device = device
 
     @_takes_offer
+    @_takes_rank_admissible
     def get_seq_in_batch(self, seqs, targets, guide, guide_k=5, max_path_len=20, stop_at_target=True, exclude=None,
                          no_repeat=False, exact_candidates=False, trace=False):
         """Persuasion paths by the Rec2Inf rule: returns (paths float32 [B, max_path_len], targets int64 [B], list of B history
@@ -65,11 +66,14 @@ class Rec2Inf(nn.Module):
         every step and cuts on the host: the same paths.
         exclude / no_repeat / exact_candidates / trace: as in IRSNN.get_seq_in_batch.  exclude with the users' whole histories
         is the reference's predict_next(use_h=True), which drops the history and not only the window.
-        offer=None (keyword only, taken by _takes_offer; 1-based item ids): as in IRSNN.get_seq_in_batch -- the path is made of items of the set."""
+        offer=None (keyword only, taken by _takes_offer; 1-based item ids): as in IRSNN.get_seq_in_batch -- the path is made of items of the set.
+        rank_admissible=False, arrive_among="window" (keyword only, taken by _takes_rank_admissible): as in IRSNN.get_seq_in_batch --
+        with trace=True, self.last_trace grows rank_adm and slate_step."""
         if guide is None:
             raise ValueError("Rec2Inf needs a guide: a [n_item + 1, F] feature table (for the plain greedy path use guide_k=1)")
         # (the guide's own checks, as IRSNN.get_seq_in_batch makes them; the sharded catalog is refused below in this handler's words)
-        options = search_option_kwargs(SearchOptions(exact_candidates=exact_candidates, trace=trace, guide=guide, guide_k=guide_k), 1, False, 1)
+        options = search_option_kwargs(SearchOptions(exact_candidates=exact_candidates, trace=trace, guide=guide, guide_k=guide_k,
+                                                     rank_admissible=self._call_rank[0], arrive_among=self._call_rank[1]), 1, False, 1)
         hip = self.net._hip
         if hip.world != 1:
             raise ValueError("Rec2Inf is not built for an item-sharded catalog: irs_bind_guide needs the whole catalog on one "
@@ -96,7 +100,8 @@ class Rec2Inf(nn.Module):
         paths = paths_t.detach().cpu().numpy()
         tg = (targets.detach().cpu().numpy() if torch.is_tensor(targets) else np.asarray(targets)).reshape(-1).astype(np.int64)
         if trace:
-            self.last_trace = path_trace_summary(*(a.detach().cpu().numpy() for a in traced[0]), paths, tg)
+            tr = [a.detach().cpu().numpy() for a in traced[0]]
+            self.last_trace = path_trace_summary(*tr[:3], paths, tg, rank_adm=tr[3] if len(tr) > 3 else None)
         n_success = 0
         for i in range(B):
             pos = get_item_index(paths[i], tg[i])
