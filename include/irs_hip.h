@@ -962,6 +962,80 @@ int irs_lookahead_choose(irs_ctx *ctx, const int64_t *dev_seq, int32_t M, int32_
                          const float *dev_cand_val, const float *dev_max, const float *dev_sumexp, const float *dev_target_score,
                          const int32_t *dev_fin, float *dev_val, int64_t *dev_ids0, int32_t k, float *dev_lp, int32_t *dev_choice);
 
+/* ---- sampler: temperature, nucleus and wide top-k draws that can be replayed (opt-in; BUILD-DEFINED: the reference draws among
+ *      three survivors at temperature 1 and keeps no record; the stock sampled step, sample != 0, is that rule and stays as it is) --
+ * A context can hold one bound SAMPLER (top_k, temperature, top_p).  While it does, a step of the greedy loops does this for a
+ * live row, behind the top-k, the survivor pass, the trace sweep and the arrival offer and BEFORE the path step:
+ *   1. WALK.  The row's ranked list is walked exactly as irs_path_step walks it, with the same admissibility test: the window
+ *      seq[row, 0 .. hep[row]], plus the bound exclusion list, plus the path so far under no_repeat.  The list ends at its first
+ *      negative id.  The first n = min(top_k, admissible entries) candidates (v_i, id_i), i = 0 .. n - 1, are kept in list order.
+ *   2. WEIGH, in float32, in an order that is fixed for a given n (two calls give the same bits):
+ *        w_i = expf((v_i - v_0) * inv_T), inv_T = 1.0f / temperature formed once at the bind; v_i = -inf gives w_i = 0;
+ *        S_m = w_0 + ... + w_(m-1), by a scan over the wave;
+ *        the SUPPORT m* is the smallest m >= 1 with S_m >= top_p * S_n (the nucleus; top_p = 1 keeps all n);
+ *        a row whose v_0 is not finite takes candidate 0 with lq = 0 and support = 1.
+ *   3. DRAW.  u = (z >> 40) * 2^-24, z the splitmix64 finaliser of seed + 0x9E3779B97F4A7C15 * (row_id * 1315423911 + step + 1):
+ *      the stock sampled step's expression with the CALLER'S row in place of the launch row -- the until loop's row map, the
+ *      identity elsewhere -- and the device step counter, so a captured step draws what a streamed one draws and a compacted row
+ *      draws what its user would have drawn in irs_generate_paths.  t = u * S_m*; the chosen index is the smallest i < m* with
+ *      S_(i+1) > t, and m* - 1 if there is none.  lq = logf(w_i / S_m*): the chosen candidate's log-probability under the
+ *      distribution it was drawn from.
+ *      ACCURACY against the same expressions in float64 on the same float32 values: a cumulative share S_m / S_m* is within
+ *      5e-5 (two roundings of an argument of magnitude <= 20, expf within 2 ulp, a sum of <= 256 terms, a ratio), so the chosen
+ *      index is the float64 one unless u lies that near a share; lq is within 1e-4 max(1, |lq|) of the float64 value.  The bound
+ *      is relative only from |lq| = 1 on: the ratio nearest to 1 that float32 holds is 1 - 2^-24, so next to lq = 0 no relative
+ *      bound can be met.
+ *   4. REWRITE.  The row's list becomes (v_chosen, id_chosen), then (-inf, -1) when k > 1, exactly as irs_arrival_offer writes
+ *      it.  The unchanged irs_path_step takes its only survivor, the unchanged trace record finds the chosen item in entry 0, and
+ *      irs_generate_paths_until retires a user whose draw was its target.
+ * Rows that are not written: a row with fin != 0 (nothing at all, records included); a row the arrival rule has chosen for at
+ * this step -- IRS_ROW_OFFERED in its status word, and its list the offer's: the row's target seq[row][L - 1] - 1 in entry 0 and
+ * the end mark behind it (the loops' status words keep the bit of an earlier step) -- whose records are u = 0, lq = 0, support = 1;
+ * (so in irs_generate_paths, whose status words keep the bit, a LATER step of such a row whose list is by itself the target and
+ * the end mark -- k = 1, or a one-entry offer set or repaired list -- is read as offered too: the item chosen is the same, the
+ * target, and only the record differs: u = 0, support = 1 where a walk would have recorded the draw);
+ * a row without an admissible candidate, whose list is left alone (the step reports IRS_ROW_NO_CANDIDATE) and whose records are 0.
+ * The records are optional: dev_rec_u float, dev_rec_lq float, dev_rec_support int32, each [users, ld], written at the caller's
+ * row and the step's column (cells outside [users, ld] are not written); irs_generate_paths_until zeroes rows [0, B) of them at
+ * entry, so a record is zero behind an arrival.
+ * irs_bind_sampler(ctx, top_k, temperature, top_p, dev_rec_u, dev_rec_lq, dev_rec_support, users, ld): top_k == 0 unbinds.
+ *   temperature not finite or <= 0, top_p outside (0, 1], a record array with users < 1 or ld < 1 -> IRS_E_INVALID; top_k outside
+ *   [1, min(max_k, IRS_MAX_SAMPLER_K)], world != 1, a bound guide or lookahead (which refuse the same way while a sampler is
+ *   bound: one choice rule at a time) -> IRS_E_UNSUPPORTED.  Bind and unbind drop the captured steps of the context.
+ * While bound:
+ *   irs_generate_paths (stream launches and the captured step alike) and irs_generate_paths_until apply the rule; their `seed`
+ *     keys the draws.  sample != 0 -> IRS_E_INVALID (two samplers); k < top_k, B > users or max_path_len > ld (with a record)
+ *     -> IRS_E_INVALID; top_k > 32 together with a bound survivor scratch -> IRS_E_UNSUPPORTED; all before any launch;
+ *   irs_generate_paths_until(check_every) draws, for the same seed, the u of irs_generate_paths bit for bit in every (row,
+ *     step).  The choices, and so the paths cut at the target, are then the same wherever the lists are: after a compaction the
+ *     decode runs on fewer rows and a float32 score may move in its last bits (by at most 4e-5 max_j ||W_j||_1, the bound of the
+ *     path trace), which moves a choice only where u lies within that distance, over T, of a cumulative share, or where the
+ *     order of two candidates hangs on it;
+ *   irs_beam_step[_until | _linked | _ruled], irs_beam_search[_until] and the two _sharded loops return IRS_E_UNSUPPORTED;
+ *   exclusions, no_repeat, the offer set, the trace and the arrival rule compose; with exact candidates bound as well the loops
+ *     ask the survivor pass for want = top_k;
+ *   the route where one workgroup ranks and steps a row is not taken; irs_path_step ALONE is unchanged.
+ * irs_sampler_choose is the kernel alone on the caller's lists, under the bound parameters and into the bound records (IRS_E_STATE
+ * without a binding); bound exclusions are honoured as irs_path_step honours them.  Like irs_lookahead_expand / irs_lookahead_choose
+ * it is SYNCHRONOUS and takes no stream: the kernel is launched on the null stream and the call returns when it has finished; the
+ * caller makes sure that the work that produces the inputs has finished.  Not for use inside a stream capture.
+ *  dev_seq int64 [M, L], dev_hep int32 [M]; dev_val float [M, k] / dev_ids0 int64 [M, k]: the rows' ranked lists, rewritten
+ *  step / seed: the step index (the records' column) and the draws' seed
+ *  dev_row_ids int32 [M] (may be NULL: the identity): row -> the caller's row: the draw's key, the records' row, the bound user
+ *  dev_status int32 [M]: read only
+ *  dev_fin int32 [M] (may be NULL); dev_paths float [users, path_ld] (may be NULL): the path so far under no_repeat, as in
+ *            irs_arrival_offer
+ * Null pointers, M < 1, k outside [top_k, max_k], step < 0 or beyond path_ld, M above the bound exclusion users, no_repeat bound
+ * and dev_paths NULL -> IRS_E_INVALID; all before the launch.
+ * The kernel: one wave per row, four rows per workgroup; 2 KB of LDS per wave for the candidates besides the window and path
+ * images; no atomics. */
+#define IRS_MAX_SAMPLER_K 256
+int irs_bind_sampler(irs_ctx *ctx, int32_t top_k, float temperature, float top_p, float *dev_rec_u, float *dev_rec_lq,
+                     int32_t *dev_rec_support, int32_t users, int32_t ld);
+int irs_sampler_choose(irs_ctx *ctx, const int64_t *dev_seq, const int32_t *dev_hep, int32_t M, float *dev_val, int64_t *dev_ids0,
+                       int32_t k, int32_t step, uint64_t seed, const int32_t *dev_row_ids, const int32_t *dev_status,
+                       const int32_t *dev_fin, const float *dev_paths, int32_t path_ld);
+
 /* ---- arrival rule: offer the target once its rank or probability allows (opt-in; a deployed recommender shows a slate, so a
  *      persuasion path has done its work once the target stands among the best items the window leaves, not only when it is the
  *      best of them) --------------------------------------------------------------------------------------------------------------

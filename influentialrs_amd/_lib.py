@@ -24,6 +24,7 @@ IRS_GUIDE_BINARY, IRS_GUIDE_FLOAT = 1, 2  # irs_bind_guide
 IRS_REPLAY_SLOT, IRS_REPLAY_FULL = 0, 1  # irs_replay_windows / irs_replay_paths: the search loops' layout, the evaluator's
 IRS_MAX_GUIDE_KC, IRS_MAX_GUIDE_BITS, IRS_MAX_GUIDE_FLOATS = 32, 1024, 512
 IRS_MAX_LOOKAHEAD_KC = 32  # irs_bind_lookahead
+IRS_MAX_SAMPLER_K = 256  # irs_bind_sampler
 IRS_BEAM_LINK_DEAD, IRS_BEAM_LINK_COPY = -1, 256  # irs_beam_step_linked's link word: dead / parent p / IRS_BEAM_LINK_COPY | p
 IRS_RANK_WINDOW, IRS_RANK_ADMISSIBLE = 0, 1  # irs_set_arrival_rule_ex: the rank the rank clause reads
 IRS_MAX_RECOMMEND = 128  # irs_recommend / irs_recommend_take: items of a slate
@@ -138,6 +139,9 @@ SIGNATURES = {
                                        c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "irs_lookahead_choose": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "irs_bind_sampler": (c_int32, [c_void_p, c_int32, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int32, c_int32]),
+    "irs_sampler_choose": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_uint64, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_int32]),
     "irs_set_arrival_rule": (c_int32, [c_void_p, c_int32, c_float]),
     "irs_arrival_offer": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int32, c_int32, c_void_p, c_void_p,

@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libirs_hip.so")
 SOURCES = ["capi.hip", "decoder.hip", "score.hip", "path.hip", "comm.hip", "train.hip", "ce_backward.hip", "ce_sharded.hip", "survivors.hip", "guide.hip",
-           "replay.hip", "lookahead.hip", "beam_trace.hip", "recommend.hip", "offer_set.hip", "admissible.hip"]
+           "replay.hip", "lookahead.hip", "beam_trace.hip", "recommend.hip", "offer_set.hip", "admissible.hip", "sampler.hip"]
 HEADERS = [os.path.join(CSRC, "irs_internal.h"), os.path.join(CSRC, "plane_split.h"), os.path.join(os.path.dirname(HERE), "include", "irs_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",

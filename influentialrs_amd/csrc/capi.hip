@@ -754,6 +754,20 @@ static int args_offer(irs_ctx *ctx, const char *fn, const search_call &c) {
     return IRS_OK;
 }
 
+// a bound sampler: the loop's own sampled step is off, the lists hold its top_k, the records hold the call, and the survivor pass
+// repairs a row to at most 32 candidates
+static int args_sampler(irs_ctx *ctx, const char *fn, const search_call &c) {
+    const auto &m = ctx->opt.sampler;
+    if (c.sample) IRS_FAIL(ctx, IRS_E_INVALID, "%s: a sampler is bound (irs_bind_sampler): two samplers, sample must be 0", fn);
+    if (c.k < m.top_k) IRS_FAIL(ctx, IRS_E_INVALID, "%s: a sampler is bound (irs_bind_sampler): k=%d < top_k=%d", fn, c.k, m.top_k);
+    if ((m.rec_u || m.rec_lq || m.rec_support) && (c.B > m.users || c.P > m.ld))
+        IRS_FAIL(ctx, IRS_E_INVALID, "%s: B=%d / path length %d, the sampler's records are bound for [%d, %d]", fn, c.B, c.P, m.users, m.ld);
+    if (ctx->opt.surv.scratch && m.top_k > 32)
+        IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "%s: a sampler is bound (irs_bind_sampler) with top_k=%d and exact candidates "
+                                         "(irs_bind_survivor_scratch) repair a row to at most 32", fn, m.top_k);
+    return IRS_OK;
+}
+
 // ---- the options, one row each.  greedy: its argument checks where a greedy entry point looks at it.  beam: why the beam entry
 // points refuse it ("<fn>: <what>: <beam>"); null: they admit it, with the same argument checks.  sharded: the sharded loops'
 // refusal, which every option has (a shard sees its own items only; most bindings refuse a sharded context themselves, so a
@@ -762,7 +776,8 @@ static int args_offer(irs_ctx *ctx, const char *fn, const search_call &c) {
 enum { OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_BTRACE, OPT_OFFER, OPT_BRULE, OPT_N };
 // behind the options that stand alone: an option bound ON TOP of another one, which exists only while that one does.  OPT_ADM
 // (irs_bind_trace_admissible) lives and dies with OPT_TRACE, so a row of PLAN that refuses the trace never gets to it
-enum { OPT_ADM = OPT_N, OPT_ALL };
+// OPT_SAMPLER (irs_bind_sampler) stands alone; it sits here because it came last
+enum { OPT_ADM = OPT_N, OPT_SAMPLER, OPT_ALL };
 static const struct {
     bool (*on)(const irs_search_opts &);
     int (*args)(irs_ctx *, const char *, const search_call &);
@@ -789,6 +804,8 @@ static const struct {
      "%s: a beam rule (irs_set_beam_rule) needs the whole catalog on one device", "irs_beam_search and irs_beam_search_until only"},
     {[](const irs_search_opts &o) { return o.adm.on != 0; }, args_adm, "an admissible rank is bound (irs_bind_trace_admissible)",
      "greedy and sampled loops only", "%s: a bound admissible rank (irs_bind_trace_admissible) needs the whole catalog on one device"},
+    {[](const irs_search_opts &o) { return o.sampler.on != 0; }, args_sampler, "a sampler is bound (irs_bind_sampler)", "greedy loops only",
+     "%s: a bound sampler (irs_bind_sampler) needs the whole catalog on one device"},
 };
 
 // ---- the entry points, one row each: what it checks, in its order -- the first failing check decides the code and the message.
@@ -805,19 +822,21 @@ static const struct {
 // the beam loops look at it (is a beam trace bound?) behind the arrival rule and before readiness, so that a rule without a trace
 // is answered before anything else of the call.  AT_BEAM_STEP_RULED, the rule's own step (irs_beam_step_ruled), takes the rule as
 // arguments and looks at neither.
+// A bound sampler (irs_bind_sampler) is looked at right behind the lookahead wherever that is: the greedy loops check its
+// arguments there, the beam entry points and the sharded loops refuse it.  irs_path_step alone does not look at it.
 // A bound admissible rank (irs_bind_trace_admissible) exists only while a path trace is bound, so every row that refuses the
 // trace has refused it already; the greedy loops look at it right behind the trace.  irs_path_step looks at neither.
 enum { AT_GREEDY_LOOP, AT_PATH_STEP, AT_BEAM_STEP, AT_BEAM_LOOP, AT_SHARDED_LOOP, AT_BEAM_STEP_LINKED, AT_RECOMMEND, AT_BEAM_STEP_RULED };
 enum { DO_READY = OPT_ALL, DO_WORLD, DO_SHAPE, DO_K, DO_END };
-static const int PLAN[][16] = {
-    /* AT_GREEDY_LOOP  */ {OPT_BTRACE, OPT_BRULE, OPT_ARRIVE, OPT_GUIDE, OPT_LOOK, DO_READY, DO_WORLD, DO_SHAPE, OPT_TRACE, OPT_ADM, DO_K, OPT_EXCL, OPT_SURV, OPT_OFFER, DO_END},
+static const int PLAN[][20] = {
+    /* AT_GREEDY_LOOP  */ {OPT_BTRACE, OPT_BRULE, OPT_ARRIVE, OPT_GUIDE, OPT_LOOK, OPT_SAMPLER, DO_READY, DO_WORLD, DO_SHAPE, OPT_TRACE, OPT_ADM, DO_K, OPT_EXCL, OPT_SURV, OPT_OFFER, DO_END},
     /* AT_PATH_STEP    */ {OPT_BTRACE, OPT_BRULE, OPT_EXCL, OPT_GUIDE, DO_END},
-    /* AT_BEAM_STEP    */ {OPT_BTRACE, OPT_BRULE, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
-    /* AT_BEAM_LOOP    */ {OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_BRULE, DO_READY, DO_WORLD, OPT_TRACE, DO_SHAPE, OPT_BTRACE, DO_K, OPT_EXCL, OPT_SURV, OPT_OFFER, DO_END},
-    /* AT_SHARDED_LOOP */ {OPT_BTRACE, OPT_BRULE, OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_ARRIVE, OPT_OFFER, DO_END},
-    /* AT_BEAM_STEP_LINKED */ {OPT_BRULE, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
+    /* AT_BEAM_STEP    */ {OPT_BTRACE, OPT_BRULE, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_SAMPLER, OPT_EXCL, DO_END},
+    /* AT_BEAM_LOOP    */ {OPT_GUIDE, OPT_LOOK, OPT_SAMPLER, OPT_ARRIVE, OPT_BRULE, DO_READY, DO_WORLD, OPT_TRACE, DO_SHAPE, OPT_BTRACE, DO_K, OPT_EXCL, OPT_SURV, OPT_OFFER, DO_END},
+    /* AT_SHARDED_LOOP */ {OPT_BTRACE, OPT_BRULE, OPT_SURV, OPT_EXCL, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_SAMPLER, OPT_ARRIVE, OPT_OFFER, DO_END},
+    /* AT_BEAM_STEP_LINKED */ {OPT_BRULE, OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_SAMPLER, OPT_EXCL, DO_END},
     /* AT_RECOMMEND    */ {OPT_EXCL, DO_END},
-    /* AT_BEAM_STEP_RULED */ {OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_EXCL, DO_END},
+    /* AT_BEAM_STEP_RULED */ {OPT_TRACE, OPT_GUIDE, OPT_LOOK, OPT_SAMPLER, OPT_EXCL, DO_END},
 };
 static int search_rules(irs_ctx *ctx, const char *fn, int at, const search_call &c) {
     const bool beam = at == AT_BEAM_STEP || at == AT_BEAM_LOOP || at == AT_BEAM_STEP_LINKED || at == AT_BEAM_STEP_RULED;
@@ -955,6 +974,7 @@ extern "C" int irs_bind_guide(irs_ctx *ctx, int32_t kind, const void *table, int
     if (F > f_max) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide: F %d > %d (%s)", F, f_max, kind == IRS_GUIDE_BINARY ? "bits" : "floats");
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide needs the whole catalog on one device");
     if (ctx->opt.look.on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide: a lookahead is bound (irs_bind_lookahead): one choice rule at a time");
+    if (ctx->opt.sampler.on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_guide: a sampler is bound (irs_bind_sampler): one choice rule at a time");
     if (k_c > ctx->dims.max_k) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_guide: k_c %d > max_k %d", k_c, ctx->dims.max_k);
     const int64_t rows = ctx->dims.n_item + 1;
     irs_guide g{table, rows, F, 0, k_c, kind};
@@ -990,6 +1010,7 @@ extern "C" int irs_bind_lookahead(irs_ctx *ctx, int32_t k_c, void *scratch, size
     if ((rec_item == nullptr) != (rec_lp == nullptr)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_lookahead: the two record arrays go together");
     if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_lookahead needs the whole catalog on one device");
     if (ctx->opt.guide.on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_lookahead: a guide is bound (irs_bind_guide): one choice rule at a time");
+    if (ctx->opt.sampler.on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_lookahead: a sampler is bound (irs_bind_sampler): one choice rule at a time");
     const int rc = check_scratch(ctx, "irs_bind_lookahead", scratch, bytes, irs_look_layout(nullptr, users, k_c, ctx->dims.max_len, ctx->dims.d, nullptr));
     if (rc) return rc;
     ctx->opt.look = {1, k_c, users, ld, scratch, rec_item, rec_lp};
@@ -1046,6 +1067,60 @@ extern "C" int irs_lookahead_choose(irs_ctx *ctx, const int64_t *seq, int32_t M,
     return look_run_sync(ctx, irs_launch_lookahead_choose(ctx, a, nullptr));
 }
 
+// ------------------------------------------------------------------ bound sampler (irs_bind_sampler; sampler.hip)
+extern "C" int irs_bind_sampler(irs_ctx *ctx, int32_t top_k, float temperature, float top_p, float *rec_u, float *rec_lq,
+                                int32_t *rec_support, int32_t users, int32_t ld) {
+    if (!ctx) return IRS_E_INVALID;
+    if (top_k == 0) { // unbind
+        if (ctx->opt.sampler.on) opts_changed(ctx);
+        ctx->opt.sampler = {};
+        return IRS_OK;
+    }
+    const int k_max = ctx->dims.max_k < IRS_MAX_SAMPLER_K ? ctx->dims.max_k : IRS_MAX_SAMPLER_K;
+    if (!(temperature > 0.f) || temperature - temperature != 0.f)
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_sampler: temperature %g must be finite and > 0", (double)temperature);
+    if (!(top_p > 0.f && top_p <= 1.f)) IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_sampler: top_p %g outside (0, 1]", (double)top_p);
+    if (top_k < 1 || top_k > k_max) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_sampler: top_k %d outside [1, %d]", top_k, k_max);
+    if ((rec_u || rec_lq || rec_support) && (users < 1 || ld < 1))
+        IRS_FAIL(ctx, IRS_E_INVALID, "irs_bind_sampler: a record needs users >= 1 and ld >= 1");
+    if (ctx->shard.world != 1) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_sampler needs the whole catalog on one device");
+    if (ctx->opt.guide.on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_sampler: a guide is bound (irs_bind_guide): one choice rule at a time");
+    if (ctx->opt.look.on) IRS_FAIL(ctx, IRS_E_UNSUPPORTED, "irs_bind_sampler: a lookahead is bound (irs_bind_lookahead): one choice rule at a time");
+    const bool rec = rec_u || rec_lq || rec_support;
+    ctx->opt.sampler = {1, top_k, temperature, 1.0f / temperature, top_p, rec_u, rec_lq, rec_support, rec ? users : 0, rec ? ld : 0};
+    opts_changed(ctx);
+    return IRS_OK;
+}
+
+// the kernel's arguments under the bound parameters: the loops' (step_ptr = the device counter) and the entry point's alike
+static irs_sampler_args sampler_args(const irs_ctx *ctx, const int64_t *seq, const int32_t *hep, int M, float *val, int64_t *ids0, int k,
+                                     const int32_t *fin, const int32_t *status, const int32_t *row_ids, const int32_t *step_ptr,
+                                     int step, uint64_t seed, const irs_excl &ex) {
+    const auto &m = ctx->opt.sampler;
+    return irs_sampler_args{seq, hep, M, ctx->dims.max_len, k, m.top_k, m.inv_t, m.top_p, val, ids0, fin, status, row_ids, step_ptr, step,
+                            (unsigned long long)seed, m.rec_u, m.rec_lq, m.rec_support, m.users, m.ld, ex};
+}
+
+extern "C" int irs_sampler_choose(irs_ctx *ctx, const int64_t *seq, const int32_t *hep, int32_t M, float *val, int64_t *ids0, int32_t k,
+                                  int32_t step, uint64_t seed, const int32_t *row_ids, const int32_t *status, const int32_t *fin,
+                                  const float *paths, int32_t path_ld) {
+    if (!ctx) return IRS_E_INVALID;
+    const char *fn = "irs_sampler_choose";
+    if (!ctx->opt.sampler.on) IRS_FAIL(ctx, IRS_E_STATE, "%s: no sampler is bound (irs_bind_sampler)", fn);
+    if (!seq || !hep || !val || !ids0 || !status) IRS_FAIL(ctx, IRS_E_INVALID, "%s: null pointer", fn);
+    if (M < 1) IRS_FAIL(ctx, IRS_E_INVALID, "%s: M must be >= 1", fn);
+    if (k < ctx->opt.sampler.top_k || k > ctx->dims.max_k)
+        IRS_FAIL(ctx, IRS_E_INVALID, "%s: k must be in [top_k=%d, %d]", fn, ctx->opt.sampler.top_k, ctx->dims.max_k);
+    if (step < 0 || (paths && (path_ld < 1 || step > path_ld))) IRS_FAIL(ctx, IRS_E_INVALID, "%s: step must be in [0, path_ld], path_ld >= 1", fn);
+    if (ctx->opt.excl.on && ctx->opt.excl.no_repeat && !paths) IRS_FAIL(ctx, IRS_E_INVALID, "%s: no_repeat is bound: dev_paths is null", fn);
+    const int rc = check_excl(ctx, fn, M, step);
+    if (rc) return rc;
+    // (synchronous, on the null stream, like the two lookahead kernels alone: irs_hip.h)
+    return look_run_sync(ctx, irs_launch_sampler_choose(ctx, sampler_args(ctx, seq, hep, M, val, ids0, k, fin, status, row_ids, nullptr, step,
+                                                                          seed, excl_args(ctx, 1, row_ids, paths, path_ld, 1, nullptr, step)),
+                                                        nullptr));
+}
+
 extern "C" int irs_path_step(irs_ctx *ctx, int64_t *seq, int32_t *hep, int32_t B, const float *val, const int64_t *ids0,
                              int32_t k, int32_t step, float *paths, int32_t path_ld, int32_t sample, int32_t sample_k,
                              uint64_t seed, int32_t *status, void *stream) {
@@ -1090,7 +1165,7 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
     //  bound: only the separate step kernel has the form that tests them; nor while a path trace is bound: its sweep reads the
     //  window before the step, its record kernel the lists after it; nor while a guide is bound: the guided step is a kernel of its own;
     //  nor while a lookahead is bound: its expand, inner decode and choose go between the ranking and the step; nor while an offer
-    //  set is bound: the lists come from its own launcher)
+    //  set is bound: the lists come from its own launcher; nor while a sampler is bound: its choice goes in front of the step)
     if (merged && !irs_opt_splits_step(ctx->opt) && sweep != IRS_SWEEP_EXHAUSTIVE && irs_topk_is_direct(ctx, B, k))
         return irs_launch_topk(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, &pa);
     if ((rc = launch_lists(ctx, ctx->xrows, B, k, sweep, ctx->top_val, ctx->top_ids, ctx->row_status, s, nullptr, nullptr, carry))) return rc;
@@ -1151,6 +1226,11 @@ static int enqueue_step(irs_ctx *ctx, irs_path_args pa, const int64_t *user, int
                                       ctx->step_ctr};
         if ((rc = irs_launch_lookahead_choose(ctx, ca, s))) return rc;
     }
+    // bound sampler: a live row that the arrival rule has not chosen for draws among its first top_k admissible candidates; the
+    // draw is keyed by the caller's row (row_map) and the device step counter
+    if (o.sampler.on && (rc = irs_launch_sampler_choose(ctx, sampler_args(ctx, pa.seq, pa.hep, B, ctx->top_val, ctx->top_ids, k, surv_fin,
+                                                                           pa.status, row_map, ctx->step_ctr, 0, pa.seed, pa.ex), s)))
+        return rc;
     if ((rc = irs_launch_path_step(ctx, pa, B, ctx->top_val, ctx->top_ids, k, s))) return rc;
     if (o.trace.on) { // (the step index is still this step's: the merged loop publishes the next one in its second word)
         const irs_trace_rec rec{tr.mx, tr.sm, tr.ts, tr.rank, o.trace.item, o.trace.target, o.trace.rank, o.trace.ld};

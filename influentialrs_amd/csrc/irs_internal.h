@@ -406,16 +406,29 @@ struct irs_search_opts {
         void *scratch;
         int rows;           // rows of a pass: what the scratch was sized for
     } offer;
+
+    // sampler (irs_bind_sampler): between the arrival offer and the path step of the greedy loops, k_sampler_choose draws one of
+    // the first top_k admissible candidates of a live row -- temperature, nucleus, a draw keyed by the caller's row and the step --
+    // and rewrites the row's list to it alone; the loops are then called with sample = 0.  The records ([users][ld], each may be
+    // null) take the draw, the chosen candidate's log-probability under the proposal and the support.  The beam and the sharded
+    // entry points refuse, and so do a guide and a lookahead: one choice rule at a time
+    struct {
+        int on, top_k;
+        float temperature, inv_t, top_p;
+        float *rec_u, *rec_lq;
+        int32_t *rec_support;
+        int users, ld;
+    } sampler;
 };
-// the candidates a step chooses among: a guided and a lookahead step among their k_c, a sampled step among sample_k, a beam
-// step of width W among W
+// the candidates a step chooses among: a guided and a lookahead step among their k_c, a bound sampler among its top_k, a sampled
+// step among sample_k, a beam step of width W among W
 static inline int irs_opt_choices(const irs_search_opts &o, int W, int sample, int sample_k) {
-    return W ? W : (o.guide.on ? o.guide.g.k_c : (o.look.on ? o.look.kc : (sample ? sample_k : 1)));
+    return W ? W : (o.guide.on ? o.guide.g.k_c : (o.look.on ? o.look.kc : (o.sampler.on ? o.sampler.top_k : (sample ? sample_k : 1))));
 }
 // some option puts a launch of its own between the ranking and the greedy step, or needs a step kernel of its own: the merged
 // top-k + step kernel cannot run (the arrival rule needs a trace, which is in the list; an offer set's lists come from its own launcher)
 static inline bool irs_opt_splits_step(const irs_search_opts &o) {
-    return o.surv.scratch || o.excl.on || o.trace.on || o.guide.on || o.look.on || o.offer.on;
+    return o.surv.scratch || o.excl.on || o.trace.on || o.guide.on || o.look.on || o.offer.on || o.sampler.on;
 }
 
 struct irs_ctx {
@@ -566,6 +579,12 @@ static inline int irs_opt_zero_records(irs_ctx *ctx, int B, hipStream_t s) {
         const size_t n = (size_t)B * o.look.ld * o.look.kc * 4;
         IRS_CHECK_HIP(ctx, hipMemsetAsync(o.look.rec_item, 0, n, s));
         IRS_CHECK_HIP(ctx, hipMemsetAsync(o.look.rec_lp, 0, n, s));
+    }
+    if (o.sampler.on) {
+        const size_t n = (size_t)B * o.sampler.ld * 4;
+        if (o.sampler.rec_u) IRS_CHECK_HIP(ctx, hipMemsetAsync(o.sampler.rec_u, 0, n, s));
+        if (o.sampler.rec_lq) IRS_CHECK_HIP(ctx, hipMemsetAsync(o.sampler.rec_lq, 0, n, s));
+        if (o.sampler.rec_support) IRS_CHECK_HIP(ctx, hipMemsetAsync(o.sampler.rec_support, 0, n, s));
     }
     return IRS_OK;
 }
@@ -745,6 +764,27 @@ int irs_launch_path_step_guided(irs_ctx *ctx, const irs_path_args &pa, int B, co
 // ---- lookahead.hip ---- (the one-step lookahead choice; arguments already validated)
 int irs_launch_lookahead_expand(irs_ctx *ctx, const irs_look_expand_args &a, hipStream_t s);
 int irs_launch_lookahead_choose(irs_ctx *ctx, const irs_look_choose_args &a, hipStream_t s);
+
+// ---- sampler.hip ---- (the bound sampler's choice; arguments already validated)
+struct irs_sampler_args { // irs_sampler_choose's arguments as the kernel takes them
+    const int64_t *seq;      // [M][L]
+    const int32_t *hep;      // [M]
+    int M, L, k, top_k;
+    float inv_t, top_p;
+    float *val;              // [M][k] in / out
+    int64_t *ids0;           // [M][k] in / out
+    const int32_t *fin;      // [M] or null: != 0 leaves the row alone
+    const int32_t *status;   // [M] the step's status words: IRS_ROW_OFFERED marks a row the arrival rule has chosen for
+    const int32_t *row_ids;  // [M] row -> the caller's row (null: the identity): keys the draw, and the records' row
+    const int32_t *step_ptr; // device step counter, or step_arg
+    int step_arg;
+    unsigned long long seed;
+    float *rec_u, *rec_lq;   // [rec_users][rec_ld] or null
+    int32_t *rec_support;
+    int rec_users, rec_ld;
+    irs_excl ex;             // bound exclusions (zero: none)
+};
+int irs_launch_sampler_choose(irs_ctx *ctx, const irs_sampler_args &a, hipStream_t s);
 
 // ---- replay.hip ---- (path replay: irs_replay_windows / irs_replay_paths; arguments already validated)
 struct irs_replay_args { // the builder's arguments as the kernel takes them; the rows are [0, R) of row_user / row_step and of the outputs

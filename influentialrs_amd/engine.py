@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import dataclasses
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -49,6 +50,16 @@ def check_rank_options(trace: bool, rank_admissible: bool, arrive_among: str):
         raise ValueError("rank_admissible=True adds a column to the path trace: use trace=True")
     if arrive_among == "admissible" and not rank_admissible:
         raise ValueError("arrive_among=\"admissible\" reads the admissible rank: use rank_admissible=True")
+
+
+@dataclasses.dataclass(frozen=True)
+class Sampler:
+    """sampler= of Engine.generate_paths[_until] (irs_bind_sampler): a step draws among its first top_k admissible candidates with
+    weights exp((v - v_0) / temperature), cut to the nucleus top_p; record: the call also returns (u, lq, support)."""
+    top_k: int
+    temperature: float = 1.0
+    top_p: float = 1.0
+    record: bool = False
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -997,6 +1008,51 @@ class Engine:
                    _ptr(fin), _ptr(val), _ptr(ids0), val.shape[1], _ptr(lp), _ptr(choice))
         return lp, choice
 
+    # ------------------------------------------------------------------ bound sampler (irs_bind_sampler)
+    def bind_sampler(self, top_k: int, temperature: float = 1.0, top_p: float = 1.0, users: int = 0, ld: int = 0, record: bool = False):
+        """irs_bind_sampler: until unbind_sampler a step of generate_paths / generate_paths_until (called with sample=False) draws
+        among its first top_k admissible candidates: weights exp((v - v_0) / temperature), the nucleus top_p, a draw keyed by
+        (seed, the caller's row, the step); the beam and the sharded loops, a guide and a lookahead refuse.  record: the loops also
+        write (u float32, lq float32, support int32), each [users, ld]: the draw, the chosen candidate's log-probability under
+        the distribution it was drawn from, and the candidates the nucleus kept.  Returns the record or None; the engine holds it
+        until unbound."""
+        rec = None
+        if record:
+            if users < 1 or ld < 1:
+                raise IrsError(f"bind_sampler: record=True needs users >= 1 and ld >= 1 (users={users}, ld={ld})")
+            rec = (torch.zeros((users, ld), dtype=torch.float32, device=self.device),
+                   torch.zeros((users, ld), dtype=torch.float32, device=self.device),
+                   torch.zeros((users, ld), dtype=torch.int32, device=self.device))
+        self._check(self.lib.irs_bind_sampler(self.h, int(top_k), float(temperature), float(top_p), _ptr(rec[0]) if rec else None,
+                                              _ptr(rec[1]) if rec else None, _ptr(rec[2]) if rec else None, int(users), int(ld)))
+        self._sampler_held = rec
+        return rec
+
+    def unbind_sampler(self):
+        self._check(self.lib.irs_bind_sampler(self.h, 0, 1.0, 1.0, None, None, None, 0, 0))
+        self._sampler_held = None
+
+    def sampler_choose(self, seqs, hep, val, ids0, step: int, seed: int, status, *, row_ids=None, fin=None, paths=None):
+        """irs_sampler_choose: the bound sampler's kernel alone on the caller's lists, synchronously (the current stream is drained
+        first); val / ids0 are rewritten in place, the bound
+        record (if any) is written at row row_ids[r] (None: r) and column step.  status is read only."""
+        seqs, hep = self._dev(seqs, torch.int64), self._dev(hep, torch.int32)
+        val = self._inplace(val, torch.float32, "sampler_choose: val")
+        ids0 = self._inplace(ids0, torch.int64, "sampler_choose: ids0")
+        status = self._dev(status, torch.int32)
+        M = seqs.shape[0]
+        if seqs.dim() != 2 or seqs.shape[1] != self.L or val.dim() != 2 or val.shape != ids0.shape or val.shape[0] != M or \
+                hep.numel() != M or status.numel() != M:
+            raise IrsError("sampler_choose: seqs [M, max_len], val / ids0 [M, k], hep / status [M]")
+        row_ids = None if row_ids is None else self._dev(row_ids, torch.int32)
+        fin = None if fin is None else self._dev(fin, torch.int32)
+        paths = None if paths is None else self._dev(paths, torch.float32)
+        if (fin is not None and fin.numel() != M) or (row_ids is not None and row_ids.numel() != M) or \
+                (paths is not None and paths.dim() != 2):
+            raise IrsError("sampler_choose: fin / row_ids [M], paths [rows, path_ld]")
+        self._call_sync(self.lib.irs_sampler_choose, _ptr(seqs), _ptr(hep), M, _ptr(val), _ptr(ids0), val.shape[1], int(step), int(seed),
+                   _ptr(row_ids), _ptr(status), _ptr(fin), _ptr(paths), paths.shape[1] if paths is not None else 0)
+
     # ------------------------------------------------------------------ arrival rule (irs_set_arrival_rule)
     def set_arrival_rule(self, rank_max: Optional[int] = None, lp_min: Optional[float] = None, among: str = "window"):
         """irs_set_arrival_rule[_ex]: until cleared (both None) a live row of the greedy / sampled loops whose target stands at rank
@@ -1041,7 +1097,7 @@ class Engine:
                         guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
                         arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False,
                         beam_trace: bool = False, offer: Optional[torch.Tensor] = None, target_weight: float = 0.0,
-                        rank_admissible: bool = False, arrive_among: str = "window"):
+                        rank_admissible: bool = False, arrive_among: str = "window", sampler: Optional[Sampler] = None):
         """While a search call runs with per-call keywords: what they ask for is bound before and unbound after.  Yields (the
         trace arrays (lp_item, lp_target, rank_target) or None, the lookahead record (items, lp) or None); beam_trace (the beam
         loops' trace=True) binds a beam trace for the call's width instead, whose [users, W, ld] arrays take the first place.
@@ -1051,6 +1107,7 @@ class Engine:
         grow a fourth, rank_adm; arrive_among="admissible" makes the arrival rule read it (ValueError without rank_admissible).
         users / ld: the call's users and path length; beam: its beam width, 0 for the greedy loops.  graph: the call replays
         a captured step -- the stream is drained once before the first unbind destroys it.
+        sampler: a sampler is bound for the call (bind_sampler); its record (u, lq, support), or None, is the third member yielded.
         Every bind and unbind drops ALL captured steps of the context, so with a keyword set use_graph saves nothing: the step
         is captured again on every call, and steps captured by earlier calls are lost.  A caller that wants a captured step
         with an option inside binds it once itself (bind_* / set_arrival_rule) and calls without the keyword."""
@@ -1058,7 +1115,8 @@ class Engine:
         check_rank_options(trace, rank_admissible, arrive_among)
 
         def survivors():  # (for the call's rows and the candidates a step chooses among: csrc/irs_internal.h, irs_opt_choices)
-            want = beam or (guide_k if guide is not None else (lookahead if lookahead is not None else (sample_k if sample else 1)))
+            want = beam or (guide_k if guide is not None else (lookahead if lookahead is not None else (
+                sampler.top_k if sampler is not None else (sample_k if sample else 1))))
             scratch = torch.empty(self.survivor_scratch_bytes(users * max(beam, 1), want), dtype=torch.uint8, device=self.device)
             self._check(self.lib.irs_bind_survivor_scratch(self.h, _ptr(scratch), scratch.numel()))
             return (scratch,)
@@ -1071,6 +1129,10 @@ class Engine:
         def look():
             out["looked"] = self.bind_lookahead(lookahead, users, ld, lookahead_record)
             return self._lookahead_held[:1]
+
+        def sampled():
+            out["drawn"] = self.bind_sampler(sampler.top_k, sampler.temperature, sampler.top_p, users, ld, sampler.record)
+            return out["drawn"] or ()
 
         def traced():
             lp_item, lp_target, rank, scratch = self.bind_path_trace(users, ld)
@@ -1099,6 +1161,7 @@ class Engine:
             (exclude is not None or no_repeat, exclusions, self.unbind_exclusions),
             (guide is not None, lambda: self.bind_guide(guide, guide_k), self.unbind_guide),
             (lookahead is not None, look, self.unbind_lookahead),
+            (sampler is not None, sampled, self.unbind_sampler),
             (trace, traced, self.unbind_path_trace),
             (trace and rank_admissible, admissible, self.unbind_trace_admissible),
             (beam_trace, beam_traced, self.unbind_beam_trace),
@@ -1109,7 +1172,7 @@ class Engine:
             for asked, bind, unbind in options:
                 if asked:
                     bound.append((bind(), unbind))
-            yield out.get("traced"), out.get("looked")
+            yield out.get("traced"), out.get("looked"), out.get("drawn")
         finally:
             stream = torch.cuda.current_stream(self.device)
             if graph and bound:
@@ -1141,9 +1204,9 @@ class Engine:
 
     @staticmethod
     def _recorded(recorded, trace: bool, lookahead_record: bool):
-        """The members a greedy loop's return value grows: the trace arrays, then the lookahead record."""
-        traced, looked = recorded
-        return ((traced,) if trace else ()) + ((looked,) if lookahead_record else ())
+        """The members a greedy loop's return value grows: the trace arrays, then the lookahead record, then the sampler's."""
+        traced, looked, drawn = recorded
+        return ((traced,) if trace else ()) + ((looked,) if lookahead_record else ()) + ((drawn,) if drawn is not None else ())
 
     # ------------------------------------------------------------------ path search
     def path_step(self, seqs, hep, val, ids0, step: int, paths, status, sample=False, sample_k=3, seed=0):
@@ -1165,7 +1228,8 @@ class Engine:
                        exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
                        guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
                        arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False,
-                       offer: Optional[torch.Tensor] = None, rank_admissible: bool = False, arrive_among: str = "window"):
+                       offer: Optional[torch.Tensor] = None, rank_admissible: bool = False, arrive_among: str = "window",
+                       sampler: Optional[Sampler] = None):
         """Runs the whole search loop on the device.  `seqs` and `hep` are the
         working window state and are modified in place.  exact_candidates: a row whose k candidates are hidden by its window
         chooses among the exact best admissible items of the catalog instead (IRS_ROW_RESCUED; the result of k = n_item).
@@ -1190,12 +1254,15 @@ class Engine:
         rank_admissible (needs trace=True): the trace member grows a fourth array, rank_adm int32 [B, max_path_len]: the target's
         rank among what the window, exclude, no_repeat and offer leave (irs_bind_trace_admissible).  arrive_among="admissible"
         (needs rank_admissible=True): arrive_rank reads rank_adm instead of rank_target.  The same holds in
-        generate_paths_until."""
+        generate_paths_until.
+        sampler (Sampler(top_k, temperature, top_p, record)): a sampler is bound for this call (irs_bind_sampler); `seed` keys its
+        draws and sample must be False; not with guide or lookahead.  record: the return value grows a last member, (u, lq
+        float32 [B, max_path_len], support int32 [B, max_path_len])."""
         seqs, users, hep, B, paths, status = self._greedy_call("generate_paths", seqs, users, hep, max_path_len, paths, status)
         with self._search_options(B, max_path_len, 0, sample, sample_k, bool(use_graph), exact_candidates=exact_candidates, exclude=exclude,
                                   no_repeat=no_repeat, trace=trace, guide=guide, guide_k=guide_k, arrive_rank=arrive_rank,
                                   arrive_lp=arrive_lp, lookahead=lookahead, lookahead_record=lookahead_record, offer=offer,
-                                  rank_admissible=rank_admissible, arrive_among=arrive_among) as recorded:
+                                  rank_admissible=rank_admissible, arrive_among=arrive_among, sampler=sampler) as recorded:
             self._call(self.lib.irs_generate_paths, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                     int(sample), sample_k, seed, int(use_graph), _ptr(paths), _ptr(status))
         return (paths, status) + self._recorded(recorded, trace, lookahead is not None and lookahead_record)
@@ -1207,7 +1274,8 @@ class Engine:
                              exclude: Optional[torch.Tensor] = None, no_repeat: bool = False, trace: bool = False,
                              guide: Optional[torch.Tensor] = None, guide_k: int = 5, arrive_rank: Optional[int] = None,
                              arrive_lp: Optional[float] = None, lookahead: Optional[int] = None, lookahead_record: bool = False,
-                             offer: Optional[torch.Tensor] = None, rank_admissible: bool = False, arrive_among: str = "window"):
+                             offer: Optional[torch.Tensor] = None, rank_admissible: bool = False, arrive_among: str = "window",
+                             sampler: Optional[Sampler] = None):
         """generate_paths that stops a user at its target (seqs[b, L - 1]) and the call when nobody is left
         (irs_generate_paths_until): returns (paths, status, steps_run, row_steps).  Paths are zero behind the target.
         `seqs` and `hep` are working state: modified, and unspecified afterwards.  One host read of 4 bytes per check.
@@ -1215,13 +1283,16 @@ class Engine:
         guide / guide_k: as in generate_paths -- with the Rec2Inf rule this loop is the reference's get_path.
         arrive_rank / arrive_lp: as in generate_paths (needs trace=True) -- a user is retired at the step that offered it its
         target, so the search stops as soon as the rule allows.
-        lookahead / lookahead_record: as in generate_paths; the record is the last member, exactly zero behind a user's arrival."""
+        lookahead / lookahead_record: as in generate_paths; the record is the last member, exactly zero behind a user's arrival.
+        sampler: as in generate_paths; for the same seed the draws u are those of generate_paths bit for bit, and the paths those of
+        generate_paths cut at the target wherever the lists agree (include/irs_hip.h); the record (the last member) is exactly zero
+        behind a user's arrival."""
         seqs, users, hep, B, paths, status = self._greedy_call("generate_paths_until", seqs, users, hep, max_path_len, paths, status)
         stats = (ctypes.c_int64 * 2)(0, 0)
         with self._search_options(B, max_path_len, 0, sample, sample_k, exact_candidates=exact_candidates, exclude=exclude,
                                   no_repeat=no_repeat, trace=trace, guide=guide, guide_k=guide_k, arrive_rank=arrive_rank,
                                   arrive_lp=arrive_lp, lookahead=lookahead, lookahead_record=lookahead_record, offer=offer,
-                                  rank_admissible=rank_admissible, arrive_among=arrive_among) as recorded:
+                                  rank_admissible=rank_admissible, arrive_among=arrive_among, sampler=sampler) as recorded:
             self._call(self.lib.irs_generate_paths_until, _ptr(seqs), _ptr(users), _ptr(hep), B, max_path_len, k, sweep,
                                                           int(sample), sample_k, seed, check_every, _ptr(paths), _ptr(status), stats)
         return (paths, status, int(stats[0]), int(stats[1])) + self._recorded(recorded, trace, lookahead is not None and lookahead_record)

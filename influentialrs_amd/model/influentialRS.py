@@ -196,6 +196,10 @@ class SearchOptions:
     beam_target_weight: float = dataclasses.field(default=0.0, kw_only=True)
     rank_admissible: bool = dataclasses.field(default=False, kw_only=True)  # irs_bind_trace_admissible: last_trace["rank_adm"]
     arrive_among: str = dataclasses.field(default="window", kw_only=True)  # the rank arrive_rank reads (irs_set_arrival_rule_ex)
+    temperature: object = dataclasses.field(default=None, kw_only=True)  # the bound sampler (irs_bind_sampler): any of the three binds it
+    top_p: object = dataclasses.field(default=None, kw_only=True)
+    draw_k: object = dataclasses.field(default=None, kw_only=True)
+    draw_record: bool = dataclasses.field(default=False, kw_only=True)  # last_draws
     beam_trace: bool = False
     beam_pick: str = "score"
 
@@ -282,6 +286,35 @@ def search_option_kwargs(opts: SearchOptions, beam_width: int, sample: bool, wor
         if not 1 <= opts.guide_k <= 32:
             raise ValueError(f"guide_k={opts.guide_k}: the guided step chooses among 1 to 32 candidates")
         kw.update(guide=opts.guide, guide_k=opts.guide_k)
+    if opts.temperature is not None or opts.top_p is not None or opts.draw_k is not None:
+        t = 1.0 if opts.temperature is None else opts.temperature
+        p = 1.0 if opts.top_p is None else opts.top_p
+        draw_k = 3 if opts.draw_k is None else opts.draw_k
+        if isinstance(t, bool) or not 0 < float(t) < float("inf"):
+            raise ValueError(f"temperature={t!r}: finite and above 0 (1: the model's own distribution among the candidates)")
+        if isinstance(p, bool) or not 0 < float(p) <= 1:
+            raise ValueError(f"top_p={p!r}: in (0, 1] (1: no nucleus cut)")
+        if isinstance(draw_k, bool) or not isinstance(draw_k, (int, np.integer)) or not 1 <= draw_k <= 100:
+            raise ValueError(f"draw_k={draw_k!r}: an int from 1 to 100, the candidates a step draws among (the loops rank 100)")
+        if sample:
+            raise ValueError("temperature / top_p / draw_k bind the sampler and sample=True is the stock sampled step: two "
+                             "samplers, use sample=False")
+        if opts.guide is not None:
+            raise ValueError("temperature / top_p / draw_k and guide are two rules for the same choice: use one of them")
+        if opts.lookahead is not None:
+            raise ValueError("temperature / top_p / draw_k and lookahead are two rules for the same choice: use one of them")
+        if beam_width > 1:
+            raise ValueError("temperature / top_p / draw_k is not built for beam search (beam_width > 1): use beam_width=1 (the "
+                             "sampler is a rule of the greedy step)")
+        if world != 1:
+            raise ValueError("temperature / top_p / draw_k is not built for an item-sharded catalog: irs_bind_sampler needs the "
+                             "whole catalog on one device")
+        if opts.exact_candidates and draw_k > 32:
+            raise ValueError(f"draw_k={draw_k} with exact_candidates=True: a row is repaired to at most 32 candidates")
+        from ..engine import Sampler
+        kw.update(sampler=Sampler(int(draw_k), float(t), float(p), bool(opts.draw_record)))
+    elif opts.draw_record:
+        raise ValueError("draw_record=True needs the sampler: give temperature, top_p or draw_k")
     if opts.beam_pick not in ("score", "target"):
         raise ValueError(f"beam_pick={opts.beam_pick!r}: use \"score\" (beam 0) or \"target\"")
     if opts.beam_pick == "target" and not opts.beam_trace:
@@ -312,21 +345,23 @@ def search_option_kwargs(opts: SearchOptions, beam_width: int, sample: bool, wor
 def _takes_exact_candidates(fn):
     """Gives get_seq_in_batch its keywords exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None,
     guide_k=5, arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, beam_trace=False,
-    beam_pick="score", offer=None, beam_arrive_rank=None, beam_arrive_lp=None, beam_target_weight=0.0, rank_admissible=False and
-    arrive_among="window".  They are taken here,
+    beam_pick="score", offer=None, beam_arrive_rank=None, beam_arrive_lp=None, beam_target_weight=0.0, rank_admissible=False,
+    arrive_among="window", temperature=None, top_p=None, draw_k=None and draw_record=False.  They are taken here,
     keyword only,
     so that the declared parameter list stays what it was (it ends with beam_stop): positional callers and code that reads the
     signature are not disturbed.  The search reads them from self._search_options, a SearchOptions, for the time of the call."""
     @functools.wraps(fn)
     def call(self, *args, exact_candidates=False, exclude=None, no_repeat=False, trace=False, guide=None, guide_k=5,
              arrive_rank=None, arrive_lp=None, lookahead=None, lookahead_record=False, beam_trace=False, beam_pick="score", offer=None,
-             beam_arrive_rank=None, beam_arrive_lp=None, beam_target_weight=0.0, rank_admissible=False, arrive_among="window", **kw):
+             beam_arrive_rank=None, beam_arrive_lp=None, beam_target_weight=0.0, rank_admissible=False, arrive_among="window",
+             temperature=None, top_p=None, draw_k=None, draw_record=False, **kw):
         prev = self._search_options
         self._search_options = SearchOptions(bool(exact_candidates), exclude, bool(no_repeat), bool(trace), guide, int(guide_k),
                                              arrive_rank, arrive_lp, lookahead, bool(lookahead_record), bool(beam_trace), beam_pick, offer=offer,
                                              beam_arrive_rank=beam_arrive_rank, beam_arrive_lp=beam_arrive_lp,
                                              beam_target_weight=beam_target_weight, rank_admissible=bool(rank_admissible),
-                                             arrive_among=arrive_among)
+                                             arrive_among=arrive_among, temperature=temperature, top_p=top_p, draw_k=draw_k,
+                                             draw_record=bool(draw_record))
         try:
             return fn(self, *args, **kw)
         finally:
@@ -832,7 +867,16 @@ class IRSNN(nn.Module):
         items of the set only -- the persuasion path is made of items that may be shown.  A target outside the set is never
         offered: put it in the set to make it reachable.  What describes the model (last_trace, beam scores, the lookahead's
         and the arrival rule's values) stays a statement about the whole catalog.  Combine with exact_candidates=True where
-        the window can hide the best 100 of a small set."""
+        the window can hide the best 100 of a small set.
+        temperature=None, top_p=None, draw_k=None, draw_record=False (extension, keyword only, taken the same way; greedy search
+        on one device, off by default): any of the first three binds the sampler (irs_bind_sampler) for the call, the others at
+        their defaults temperature 1, top_p 1, draw_k 3: every step draws among its first draw_k admissible candidates with
+        weights exp((score - best score) / temperature), cut to the smallest head that holds top_p of the weight; the draws
+        are keyed by (seed, user row, step), so stop_at_target=True draws what stop_at_target=False draws.  Not with
+        sample=True (ValueError: two samplers), guide, lookahead, beam_width > 1 or a sharded catalog.  draw_record=True:
+        self.last_draws = dict(u, lq float32 [B, max_path_len], support int32 [B, max_path_len]): every step's draw, the chosen
+        item's log-probability under the distribution it was drawn from, and the candidates the nucleus kept; cut to 0 after
+        the arrival like last_trace."""
         opts = self._search_options
         greedy_kw = search_option_kwargs(opts, beam_width, sample, self.net._hip.world)
         rule = beam_rule_kwargs(opts, beam_width, self.net._hip.world)
@@ -856,7 +900,8 @@ class IRSNN(nn.Module):
             raise ValueError("sample_k > 8 is not supported by the HIP path step (include/irs_hip.h)")
         work = seqs.to(torch.int64).clone(memory_format=torch.contiguous_format)  # the search updates it in place
         hep = torch.full((B,), L - (gap_len + 1) - 1, dtype=torch.int32, device=dev)
-        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if sample else 0
+        sampler = greedy_kw.get("sampler")
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if sample or sampler is not None else 0
         ids0 = exclusion_ids0(exclude, no_repeat, seqs, L - (gap_len + 1) - 1, dev)
         excl = dict(exclude=ids0, no_repeat=no_repeat) if (ids0 is not None or no_repeat) else {}
         off = offer_ids0(opts.offer, self.n_item, dev)
@@ -920,6 +965,15 @@ class IRSNN(nn.Module):
                     items[i, pos + 1:] = 0
                     lp[i, pos + 1:] = 0
             self.last_lookahead = dict(items=items, lp=lp)
+        if sampler is not None and sampler.record:
+            u, lq, support = (a.detach().cpu().numpy().copy() for a in traced[-1])
+            for i in range(B):  # (cut after the arrival, like last_trace)
+                pos = get_item_index(paths[i], targets[i])
+                if pos != -1:
+                    u[i, pos + 1:] = 0
+                    lq[i, pos + 1:] = 0
+                    support[i, pos + 1:] = 0
+            self.last_draws = dict(u=u, lq=lq, support=support)
         histories = seqs[:, :-1].detach().cpu().numpy()
         actual_history = []
         for i in range(B):

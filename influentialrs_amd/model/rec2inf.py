@@ -6,6 +6,8 @@ has not seen, offers the one whose feature vector lies nearest to the target's (
 user when the target itself has been offered.  Here the whole loop runs on the device: decode -> exact top-100 -> guided
 step (include/irs_hip.h: irs_bind_guide), through the same search loops IRSNN.get_seq_in_batch uses.  Only get_path's rule
 is built; the reference's baseline recommenders themselves (main_baselines.py's models) are out of scope."""
+import functools
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -43,6 +45,20 @@ def rec2inf_windows(seqs, targets, max_len: int, device):
     return torch.from_numpy(win).to(device), torch.from_numpy(hep).to(device), [np.asarray(r) for r in rows]
 
 
+def _takes_sampler(fn):
+    """Gives get_seq_in_batch the keywords temperature=None, top_p=None and draw_k=None, keyword only, the way _takes_offer gives
+    it offer.  The method reads them from self._call_sampler, SearchOptions' keywords."""
+    @functools.wraps(fn)
+    def call(self, *args, temperature=None, top_p=None, draw_k=None, **kw):
+        prev = getattr(self, "_call_sampler", {})
+        self._call_sampler = dict(temperature=temperature, top_p=top_p, draw_k=draw_k)
+        try:
+            return fn(self, *args, **kw)
+        finally:
+            self._call_sampler = prev
+    return call
+
+
 class Rec2Inf(nn.Module):
     """Task handler: Rec2Inf(config, net, device) over a SampleNet."""
 
@@ -55,6 +71,7 @@ class Rec2Inf(nn.Module):
 
     @_takes_offer
     @_takes_rank_admissible
+    @_takes_sampler
     def get_seq_in_batch(self, seqs, targets, guide, guide_k=5, max_path_len=20, stop_at_target=True, exclude=None,
                          no_repeat=False, exact_candidates=False, trace=False):
         """Persuasion paths by the Rec2Inf rule: returns (paths float32 [B, max_path_len], targets int64 [B], list of B history
@@ -68,12 +85,15 @@ class Rec2Inf(nn.Module):
         is the reference's predict_next(use_h=True), which drops the history and not only the window.
         offer=None (keyword only, taken by _takes_offer; 1-based item ids): as in IRSNN.get_seq_in_batch -- the path is made of items of the set.
         rank_admissible=False, arrive_among="window" (keyword only, taken by _takes_rank_admissible): as in IRSNN.get_seq_in_batch --
-        with trace=True, self.last_trace grows rank_adm and slate_step."""
+        with trace=True, self.last_trace grows rank_adm and slate_step.
+        temperature=None, top_p=None, draw_k=None (keyword only, taken by _takes_sampler): IRSNN.get_seq_in_batch's sampler
+        keywords; the Rec2Inf rule and the sampler are two rules for the same choice, so any of them raises ValueError."""
         if guide is None:
             raise ValueError("Rec2Inf needs a guide: a [n_item + 1, F] feature table (for the plain greedy path use guide_k=1)")
         # (the guide's own checks, as IRSNN.get_seq_in_batch makes them; the sharded catalog is refused below in this handler's words)
         options = search_option_kwargs(SearchOptions(exact_candidates=exact_candidates, trace=trace, guide=guide, guide_k=guide_k,
-                                                     rank_admissible=self._call_rank[0], arrive_among=self._call_rank[1]), 1, False, 1)
+                                                     rank_admissible=self._call_rank[0], arrive_among=self._call_rank[1],
+                                                     **self._call_sampler), 1, False, 1)
         hip = self.net._hip
         if hip.world != 1:
             raise ValueError("Rec2Inf is not built for an item-sharded catalog: irs_bind_guide needs the whole catalog on one "
